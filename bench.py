@@ -13,7 +13,7 @@ reference path timed on this host on a bounded sample).
 
     python bench.py                               # 1 GPU, 1e9 codes: the headline line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python bench.py --workload c2                 # BASELINE configs[1]: 64-bit, 1e8 codes, MIH radius-8 search (m = 2; m = 4 as a variant)
     python bench.py --workload c5shard            # one GPU's share of configs[4]: 256-bit, 5e8 codes, 4096 queries per pass
     python bench.py --workload knn_mih            # exact top-100 through MIH on 1e8 clustered 128-bit codes (--approximate, --uniform-queries)
@@ -42,6 +42,7 @@ HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E peak (MI355X_MICROARCH.md; ~6.3 TB/s is 
 VALU_PEAK_GOPS = 39321.6  # 256 CUs x 64 lanes x 2.4 GHz 32-bit lane-ops/s; v_xor issues at ~2.3 and
 #                           v_bcnt at ~4.2 cycles per wave64 instruction per SIMD, so the xor+popcount mix tops out near 0.6 of it
 METRIC = "queries/sec (k-NN top-100) on 128-bit codes, 1B DB; bit-exact vs linear_search"
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: cap on the bytes written
 
 
 def parse(argv=None):
@@ -65,7 +66,11 @@ def parse(argv=None):
     ap.add_argument("--no-extras", action="store_true", help="default line only: skip the short measurements of the other shapes (`extras`)")
     ap.add_argument("--approximate", action="store_true", help="workload knn_mih: VC_MODE_MIH_APPROX (search_worker.cc:93-157) instead of the exact loop")
     ap.add_argument("--shards", type=int, default=8, help="workload sharded1dev: id-range shards behind vc_sharded_* (all on device 0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="workload c3: write the top-k of the last timed step "
+                    "(distances, ids, counts; float64) to DIR/<name>.npy, at most %d MB in all" % (DUMP_MAX_BYTES >> 20))
     args = ap.parse_args(argv)
+    if args.dump_outputs is not None and args.workload != "c3":
+        ap.error("--dump-outputs is implemented for the headline workload (c3) only")
     d = {"c3": (1e9, 128, 8, 30), "c1": (1 << 20, 64, 200, 50), "c2": (1e8, 64, 1024, 20), "c5shard": (5e8, 256, 4096, 4),
          "knn_mih": (1e8, 128, 4096, 10), "sharded1dev": (1e9, 128, 8, 30)}[args.workload]
     if args.n is None:
@@ -76,7 +81,26 @@ def parse(argv=None):
         args.queries = d[2]
     if args.steps is None:
         args.steps = d[3]
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     return args
+
+
+def dump_outputs(dirname, packed, counts, seed):
+    """--dump-outputs: a caller's view of one step's result -- packed (distance << 32 | id) rows [Q, k] and counts [Q] --
+    as float64 .npy files (exact: distances and ids stay below 2^53).  Rows beyond the size cap are a fixed, seeded
+    sample; query_index.npy names the query row of every dumped row."""
+    packed = np.asarray(packed).view(np.uint64)
+    nq, k = packed.shape
+    rows = np.arange(nq)
+    max_rows = max(1, DUMP_MAX_BYTES // (2 * 8 * k + 2 * 8))
+    if nq > max_rows:
+        rows = np.sort(np.random.default_rng(seed).choice(nq, max_rows, replace=False))
+    packed = packed[rows]
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in (("distances", packed >> np.uint64(32)), ("ids", packed & np.uint64(0xFFFFFFFF)),
+                    ("counts", np.asarray(counts)[rows]), ("query_index", rows)):
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float64))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -389,6 +413,8 @@ def run_headline(args, env, emit, backend_factory=None):
     (out, cnt), elapsed = timed_steps(env, run_steps, args.steps)
     tm = ss.backend.timing()  # HIP events on the launch stream, exactly the timed steps
     out, cnt = out.clone(), cnt.clone()   # the passes below reuse the result buffers
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, out.cpu().numpy(), cnt.cpu().numpy(), args.seed)
     step_ms = None
     if env.cuda and backend_factory is None:
         def one(i):

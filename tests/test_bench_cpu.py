@@ -46,26 +46,26 @@ class BenchDouble(OracleBackend):
         return 0
 
 
-def _worker(rank, world, port, corrupt, ret):
+def _worker(rank, world, port, corrupt, ret, extra):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     os.environ["VC_BENCH_BUCKET"] = "3"                      # 5 steps = one full bucket + a partial one finished by flush()
     import bench
     from oracle import vc_oracle as vo
     buf = io.StringIO()
     rc = bench.main(["--gpus", str(world), "--steps", "5", "--warmup", "1", "--db-size", "6001", "--k", "20", "--queries", "4",
-                     "--cpu-seconds", "0"],
+                     "--cpu-seconds", "0"] + list(extra),
                     backend_factory=lambda bits, lo, hi: BenchDouble(vo, bits, lo, corrupt=corrupt and rank == 1),
                     device_kind="cpu", dist_backend="gloo", out=buf)
     ret[rank] = (rc, buf.getvalue())
 
 
-def _run(corrupt):
+def _run(corrupt, extra=()):
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
     ret = mp.Manager().dict()
-    mp.spawn(_worker, args=(2, port, corrupt, ret), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, port, corrupt, ret, tuple(extra)), nprocs=2, join=True)
     return dict(ret)
 
 
@@ -88,3 +88,20 @@ def test_bench_exits_nonzero_when_the_result_check_fails(oracle):
     assert ret[0][0] != 0 and ret[1][0] != 0                 # every rank learns it (all-reduce of the check)
     j = json.loads(ret[0][1].strip())
     assert j["results_check"] == "FAILED"
+
+
+def test_bench_dump_outputs_is_the_last_timed_step(oracle, tmp_path):
+    """--dump-outputs: the merged top-k of the last timed step (5 steps over 4 query batches: batch 0), written by rank 0
+    as float64 .npy files, equal to the oracle's top-k over the whole database."""
+    ret = _run(False, ["--dump-outputs", str(tmp_path / "out")])
+    assert ret[0][0] == 0 and ret[1][0] == 0
+    got = {n: np.load(str(tmp_path / "out" / (n + ".npy"))) for n in ("distances", "ids", "counts", "query_index")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    codes = oracle.gen_codes(6001, 128, 34)
+    rng = np.random.default_rng(35)
+    q = [rng.integers(0, 256, size=(4, 16), dtype=np.uint8) for _ in range(4)][0]
+    assert np.array_equal(got["query_index"], np.arange(4)) and np.array_equal(got["counts"], np.full(4, 20))
+    for i in range(4):
+        exp = oracle.linear_knn(codes, q[i], 20)
+        assert np.array_equal(got["distances"][i], (exp >> np.uint64(32)).astype(np.float64))
+        assert np.array_equal(got["ids"][i], (exp & np.uint64(0xFFFFFFFF)).astype(np.float64))

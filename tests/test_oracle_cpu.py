@@ -54,19 +54,25 @@ def test_bitmap_golden(oracle, golden):
 
 
 def test_primitives_against_live_reference(oracle):
+    """A random sweep against the reference's outputs stored in tests/golden/reference_sweep.npz; where the reference
+    veneer (oracle/_ref) is built, the live reference must also still give those outputs."""
     R = oracle.ref()
-    if R is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this box)")
-    rng = np.random.default_rng(1)
+    with np.load(os.path.join(ROOT, "tests", "golden", "reference_sweep.npz")) as z:
+        sweep = {name: z[name] for name in z.files}
     for nb in (8, 16, 32, 64, 13):
-        for _ in range(300):
-            a = rng.integers(0, 256, nb, dtype=np.uint8)
-            b = rng.integers(0, 256, nb, dtype=np.uint8)
-            assert oracle.hamming(a, b) == R.vcref_hamming(a.tobytes(), b.tobytes(), nb)
+        a, b, d = sweep["ham_a_%d" % nb], sweep["ham_b_%d" % nb], sweep["ham_d_%d" % nb]
+        assert a.shape == b.shape == (300, nb) and d.shape == (300,)
+        for x, y, dist in zip(a, b, d):
+            assert oracle.hamming(x, y) == dist
+            if R is not None:
+                assert R.vcref_hamming(x.tobytes(), y.tobytes(), nb) == dist
     for ln in (1, 2, 3, 4):
-        for _ in range(500):
-            p = rng.integers(0, 256, ln, dtype=np.uint8).tobytes()
-            assert oracle.binary_to_int(p) == R.vcref_binary_to_int(p, ln)
+        p, v = sweep["b2i_in_%d" % ln], sweep["b2i_out_%d" % ln]
+        assert p.shape == (500, ln) and v.shape == (500,)
+        for x, val in zip(p, v):
+            assert oracle.binary_to_int(x.tobytes()) == val
+            if R is not None:
+                assert R.vcref_binary_to_int(x.tobytes(), ln) == val
 
 
 # ----------------------------------------------------------------------------- loops (restated; cross-validated)
