@@ -233,8 +233,11 @@ int vc_device_status(vc_engine* e, uint32_t* n_gave_up);
 /* ---- multi-GPU merge ---------------------------------------------------------------------
  * replaces: mpi_coordinator::gather_vectors + master-side heap (mpi_coordinator.cc:34-69,
  * search_worker.cc:179-199).  d_lists holds n_lists blocks of nq*k packed values (the all-gathered
- * per-shard top-k, UINT64_MAX padded); writes the merged ascending top-k to d_out (nq*k) and the
- * valid count per query to d_counts (may be NULL).  Asynchronous on `stream`; no engine needed. */
+ * per-shard top-k); UINT64_MAX marks an empty entry.  A list may be in any order, with its empty entries
+ * anywhere and values repeated within it or across lists: ascending lists with the empty entries at the
+ * tail (what the engine's rows are) take the fast merge, others are sorted first.  Writes the k smallest
+ * values ascending to d_out (nq*k, UINT64_MAX padded) and the number of non-empty ones per query to
+ * d_counts (may be NULL).  Asynchronous on `stream`; no engine needed. */
 int vc_merge_topk_dev(const uint64_t* d_lists, uint32_t n_lists, uint32_t nq, uint32_t k,
                       uint64_t* d_out, uint32_t* d_counts, void* stream);
 

@@ -271,6 +271,61 @@ def test_merge_of_sorted_lists_equals_numpy(vc, n_lists, nq, k):
         assert c[q] == int((exp != INF).sum())
 
 
+def _merge_lists(kind, n_lists, nq, k, rng):
+    """[n_lists, nq, k] packed values for vc_merge_topk_dev in one of the layouts its contract allows besides the sorted one
+    (distances < 2048, ids random; no value is UINT64_MAX except the padding)"""
+    lists = np.full((n_lists, nq, k), INF, dtype=np.uint64)
+    if kind == "all_inf":
+        return lists
+    for g in range(n_lists):
+        for q in range(nq):
+            fill = k if (g + q) % 3 == 0 else int(rng.integers(1, k + 1))
+            if kind == "duplicates":                                   # a handful of values, repeated within and across lists
+                pool = (np.arange(1, 6, dtype=np.uint64) << np.uint64(32)) | np.uint64(q + 7)
+                vals = np.sort(pool[rng.integers(0, len(pool), size=fill)])
+                if g % 2:
+                    rng.shuffle(vals)
+            else:
+                vals = (rng.integers(0, 2048, size=fill).astype(np.uint64) << np.uint64(32)) | \
+                    rng.integers(0, 1 << 32, size=fill).astype(np.uint64)
+                vals = np.sort(vals) if kind == "interior_inf" else rng.permutation(vals)
+            row = lists[g, q]
+            if kind == "interior_inf":                                 # ascending values, the padding anywhere among them
+                pos = np.sort(rng.choice(k, size=fill, replace=False))
+                if fill < k and pos[-1] == fill - 1:
+                    pos[-1] = k - 1                                    # at least one INF before a value
+                row[pos] = vals
+            else:
+                row[:fill] = vals
+    return lists
+
+
+@pytest.mark.parametrize("kind", ["random_order", "interior_inf", "all_inf", "duplicates"])
+@pytest.mark.parametrize("n_lists,nq,k", [(1, 3, 7), (8, 8, 100), (16, 5, 384), (16, 5, 385), (3, 2, 8192)])
+def test_merge_of_lists_in_any_order_equals_numpy(vc, kind, n_lists, nq, k):
+    """vc_merge_topk_dev promises nothing about the order inside a list: lists in random order, ascending lists with the
+    INF padding in the middle, lists of nothing but INF, values repeated within a list and across lists -- on both sides
+    of the LDS merge kernel's 6144-entry limit (16 x 384 is the last shape it takes, 16 x 385 the first the general select
+    takes; at 3 x 8192 the select's radix path keeps the copies of a k-th value repeated far past k to k of them).  Every
+    output slot is checked (the output starts as a sentinel no merge can produce) against numpy's sort."""
+    import torch
+    rng = np.random.default_rng([len(kind), n_lists, nq, k])
+    lists = _merge_lists(kind, n_lists, nq, k, rng)
+    sentinel = 0x7FF00000DEADBEEF                                      # distance 0x7FF00000: never a packed value here
+    d = torch.from_numpy(lists.view(np.int64)).cuda()
+    out = torch.full((nq, k), sentinel, dtype=torch.int64, device="cuda")
+    cnt = torch.full((nq,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+    vc.merge_topk_dev(d.data_ptr(), n_lists, nq, k, out.data_ptr(), cnt.data_ptr())
+    torch.cuda.synchronize()
+    got, c = out.cpu().numpy().view(np.uint64), cnt.cpu().numpy()
+    for q in range(nq):
+        exp = np.sort(lists[:, q].reshape(-1))[:k]
+        bad = np.flatnonzero(got[q] != exp)
+        assert bad.size == 0, "row %d: first mismatch at slot %d: got %#x, expected %#x" % (
+            q, bad[0], int(got[q, bad[0]]), int(exp[bad[0]]))
+        assert c[q] == int((exp != INF).sum()), q
+
+
 @pytest.mark.parametrize("nq,k", [(6, 100), (700, 100), (3000, 100), (1500, 400)])
 def test_host_pointer_calls_pageable_and_page_locked(vc, oracle, nq, k):
     """vc_search_knn's three ways home for the rows (SearchWorker::find's caller holds host memory, search_worker.cc:65-89): one

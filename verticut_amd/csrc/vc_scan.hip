@@ -650,6 +650,7 @@ struct VcRingSrc {
   __device__ uint64_t get(uint32_t q, uint32_t i) const { return buf[(uint64_t)q * cap + i]; }
 };
 struct VcListsSrc {
+  static constexpr bool kSortedLists = false;   // vc_merge_topk_dev's caller promises no order inside a list
   const uint64_t* lists;
   uint32_t n_lists, nq, k;
   __device__ uint32_t slot(uint32_t b) const { return b; }
@@ -666,6 +667,7 @@ struct VcListsSrc {
 // overflowed and the device-side recovery gave up) flags the merged row -- the overflow flags are reduced HERE, on the
 // device, instead of a count read-back and a host wait per shard.
 struct VcSlotsSrc {
+  static constexpr bool kSortedLists = true;    // the shards' own rows: ascending, INF only behind counts[i]
   const uint64_t* base;
   uint64_t slot_words;
   uint32_t cnt_off, n_lists, nq, k;
@@ -716,7 +718,7 @@ __global__ void __launch_bounds__(VC_SEL_THREADS) vc_select_kernel(Src src, uint
     atomicAdd(&s_valid, myvalid);
     __syncthreads();
     const uint32_t valid = s_valid;
-    uint64_t thresh = VC_PACK_INF - 1;  // valid <= k: keep every valid entry
+    uint64_t thresh = VC_PACK_INF;      // valid <= k: keep every valid entry
     if (valid > k) {
       if (threadIdx.x == 0) {
         s_prefix_hi = 0;
@@ -761,17 +763,23 @@ __global__ void __launch_bounds__(VC_SEL_THREADS) vc_select_kernel(Src src, uint
       }
       thresh = prefix;  // exact value of the k-th smallest
     }
+    // the entries below the k-th smallest (fewer than k), then copies of it up to k: a value repeated past the k-th slot
+    // (gathered lists that overlap) would otherwise take more than VC_SORT_CAP slots and push smaller entries out
     if (threadIdx.x == 0) s_fill = 0;
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < n; i += VC_SEL_THREADS) {
       const uint64_t v = src.get(q, i);
-      if (v <= thresh) {
+      if (v < thresh) {
         const uint32_t slot = atomicAdd(&s_fill, 1u);
         if (slot < VC_SORT_CAP) a[slot] = v;
       }
     }
     __syncthreads();
-    const uint32_t fill = min(s_fill, (uint32_t)VC_SORT_CAP);
+    uint32_t fill = min(s_fill, (uint32_t)VC_SORT_CAP);
+    if (valid > k) {
+      for (uint32_t i = fill + threadIdx.x; i < k; i += VC_SEL_THREADS) a[i] = thresh;
+      fill = k;
+    }
     P = 2;
     while (P < fill) P <<= 1;
     for (uint32_t i = fill + threadIdx.x; i < P; i += VC_SEL_THREADS) a[i] = VC_PACK_INF;
@@ -1468,8 +1476,36 @@ hipError_t vc_launch_recover(const uint64_t* cols, uint64_t stride, uint64_t n, 
 // its index in its own list + the entries below it in every other list (binary searches in LDS; ties between lists break
 // by list number, so duplicates keep distinct ranks) -- entries ranked below k are written, the tail is padded.  No
 // sort, two barriers: ~3 us where the general select kernel (no order assumed) takes 10.
+// Lists of a source that does not promise order (vc_merge_topk_dev's) are checked after staging -- one pass, one block-wide
+// OR: a list is in order iff it never descends, which also rules out INF in front of a value -- and a block that finds one
+// out of order sorts the staged entries in place and writes the first k of them instead of ranking.
 #define VC_MERGE_THREADS 256
 #define VC_MERGE_MAX_ENTRIES 6144u     // 48 KiB of LDS
+
+// Bitonic network over a[0, n) in LDS for any n: positions n .. pow2(n)-1 stand for +INF and are never touched (every
+// comparator puts its minimum at the lower index, so a comparator that reaches past n would leave both sides as they are).
+// vc_bitonic_lds would need the padding stored: 64 KiB of LDS instead of the 48 this kernel is launched with at its limit.
+__device__ __forceinline__ void vc_merge_sort_lds(uint64_t* a, uint32_t n) {
+  uint32_t P = 1;
+  while (P < n) P <<= 1;
+  for (uint32_t p = 2; p <= P; p <<= 1) {
+    for (uint32_t d = p >> 1; d > 0; d >>= 1) {
+      for (uint32_t t = threadIdx.x; t < (P >> 1); t += VC_MERGE_THREADS) {
+        const uint32_t lo = ((t & ~(d - 1)) << 1) | (t & (d - 1));   // bit log2(d) of lo is clear
+        const uint32_t hi = d == (p >> 1) ? lo ^ (p - 1) : lo | d;   // first step of a stage: mirror inside the p-block
+        if (hi < n) {
+          const uint64_t x = a[lo], y = a[hi];
+          if (x > y) {
+            a[lo] = y;
+            a[hi] = x;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 template <class Src>
 __global__ void __launch_bounds__(VC_MERGE_THREADS) vc_merge_sorted_kernel(Src src, uint32_t k, uint64_t* __restrict__ out,
                                                                             uint32_t* __restrict__ out_count) {
@@ -1479,6 +1515,24 @@ __global__ void __launch_bounds__(VC_MERGE_THREADS) vc_merge_sorted_kernel(Src s
   if (threadIdx.x == 0) s_total = 0;
   for (uint32_t i = threadIdx.x; i < n; i += VC_MERGE_THREADS) m_lists[i] = src.get(q, i);
   __syncthreads();
+  if constexpr (!Src::kSortedLists) {
+    int unordered = 0;
+    for (uint32_t i = threadIdx.x; i + 1 < n; i += VC_MERGE_THREADS)
+      unordered |= m_lists[i] > m_lists[i + 1] && (i + 1) % k != 0;   // (the modulo only where a pair descends)
+    if (__syncthreads_or(unordered)) {                                // block-uniform
+      vc_merge_sort_lds(m_lists, n);
+      uint32_t mine = 0;
+      for (uint32_t i = threadIdx.x; i < k; i += VC_MERGE_THREADS) {   // k <= n: the sorted prefix, INF-padded already
+        const uint64_t v = m_lists[i];
+        out[(uint64_t)q * k + i] = v;
+        mine += v != VC_PACK_INF;
+      }
+      if (mine) atomicAdd(&s_total, mine);
+      __syncthreads();
+      if (out_count && threadIdx.x == 0) out_count[q] = src.overflowed(q) ? 0xFFFFFFFFu : s_total;
+      return;
+    }
+  }
   uint32_t mine = 0;
   for (uint32_t i = threadIdx.x; i < n; i += VC_MERGE_THREADS) {
     const uint64_t v = m_lists[i];

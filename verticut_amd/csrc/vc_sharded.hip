@@ -554,6 +554,9 @@ int vc_sharded_search_knn(vc_sharded* h, const void* queries, uint32_t nq, uint3
     VS_HIP(h, hipStreamSynchronize(S));
   }
   for (uint32_t i = 0; i < nq; ++i) {
+    // the MIH modes have no host-side recovery above: a row flagged by the slot merge (UINT32_MAX) must not be reversed
+    // past its k entries nor reported as more than k results
+    if (mode != VC_MODE_LINEAR) cnt[i] = std::min(cnt[i], k);
     if (order == VC_ORDER_FARTHEST_FIRST) std::reverse(out + (size_t)i * k, out + (size_t)i * k + cnt[i]);
     if (counts) counts[i] = cnt[i];
     if (stats) stats[i].n_results = cnt[i];
