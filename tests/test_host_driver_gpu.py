@@ -237,11 +237,15 @@ def test_bitmap_file_read_back_and_verify(vc, oracle, tmp_path):
             e.read_bitmap_file(0, tmp_path / "long.raw")
 
 
-@pytest.mark.parametrize("bits,m", [(128, 4), (64, 4)])
-def test_index_save_and_load(vc, oracle, tmp_path, bits, m):
+# VC_MIH_LINES "1" forces the directory lines (2 GB per 32-bit table), which a build and a load derive alike; "0" is what
+# 30 000 records get anyway, so those cases keep their ids
+@pytest.mark.parametrize("bits,m,lines", [pytest.param(128, 4, "0", id="128-4"), pytest.param(64, 4, "0", id="64-4"),
+                                          pytest.param(128, 4, "1", id="128-4-lines"), pytest.param(64, 4, "1", id="64-4-lines")])
+def test_index_save_and_load(vc, oracle, tmp_path, monkeypatch, bits, m, lines):
     """the built index (bucket lists of build_hash_tables.cc:36-64 as id runs + offsets, bitmaps, rank directories)
     survives a round trip through a file: same buckets, same search results and statistics; a file built for another
     database shape is refused."""
+    monkeypatch.setenv("VC_MIH_LINES", lines)                                  # read when an engine is created
     n, k = 30000, 20
     rng = np.random.default_rng(bits)
     codes = oracle.gen_codes(n, bits, 3, kind=1, n_centres=120, max_flips=6)

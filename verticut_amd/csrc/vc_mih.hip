@@ -25,7 +25,9 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <sched.h>
+#include <type_traits>
 
 #include "vc_internal.hpp"
 #include "vc_mih.hpp"
@@ -2343,6 +2345,18 @@ __global__ void __launch_bounds__(1024) vc_radius_offsets_kernel(const uint32_t*
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+// the one dispatch on the code width: f(std::integral_constant<int, W>{}) for the widths the kernels are instantiated for
+template <class F>
+static hipError_t with_w(uint32_t W, F&& f) {
+  switch (W) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
 // per-query result segments (ring[q * cap ..], count[q] entries each, cap a power of two) -> ascending per query at out[offs[q] ..]
 // (vc_sharded_search_radius: the shards' concatenated results of a query are ordered by the same kernel the radius search uses)
 hipError_t vc_launch_sort_compact_segments(uint64_t* d_ring, uint32_t cap, const uint32_t* d_count, const uint64_t* d_offs,
@@ -2368,19 +2382,17 @@ hipError_t vc_launch_mih_replay(const VcMihReplayArgs& a, hipStream_t s) {
 hipError_t vc_launch_minsub_count(const uint64_t* cols, uint64_t stride, uint64_t n, uint32_t W, uint32_t m, uint32_t sbits,
                                   const uint64_t* d_queries, const uint32_t* d_list, const uint32_t* d_flag, uint32_t nq,
                                   const uint32_t* d_radius, unsigned long long* d_seen, uint32_t n_cu, hipStream_t s) {
-  for (uint32_t q0 = 0; q0 < nq; q0 += MC_Q) {
-    const uint32_t qt = std::min<uint32_t>(MC_Q, nq - q0);
-    const dim3 grid((uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)n_cu * 8));
-#define MC_CASE(W_) case W_: hipLaunchKernelGGL(mih_minsub_count_kernel<W_>, grid, dim3(256), 0, s, cols, stride, n, m, sbits, d_queries + (size_t)q0 * W, d_list + q0, d_flag + q0, qt, d_radius, d_seen); break;
-    switch (W) {
-      MC_CASE(1) MC_CASE(2) MC_CASE(4) MC_CASE(8)
-      default: return hipErrorInvalidValue;
+  const dim3 grid((uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)n_cu * 8));
+  return with_w(W, [&](auto w) {
+    for (uint32_t q0 = 0; q0 < nq; q0 += MC_Q) {
+      const uint32_t qt = std::min<uint32_t>(MC_Q, nq - q0);
+      hipLaunchKernelGGL(mih_minsub_count_kernel<decltype(w)::value>, grid, dim3(256), 0, s, cols, stride, n, m, sbits,
+                         d_queries + (size_t)q0 * W, d_list + q0, d_flag + q0, qt, d_radius, d_seen);
+      hipError_t r = hipGetLastError();
+      if (r != hipSuccess) return r;
     }
-#undef MC_CASE
-    hipError_t r = hipGetLastError();
-    if (r != hipSuccess) return r;
-  }
-  return hipSuccess;
+    return hipSuccess;
+  });
 }
 
 // Host wait for a word a kernel publishes to mapped host memory (sequence number last).  The first ~30 us spin hot --
@@ -2432,13 +2444,19 @@ struct VcMihIndex {
   uint32_t group_hint = 2;                  // shells grouped into the query kernel's first pass (adapts to where queries stop)
 };
 
-#define MIH_CHECK(call)                                                                                  \
-  do {                                                                                                   \
-    hipError_t _r = (call);                                                                              \
-    if (_r != hipSuccess) {                                                                              \
-      if (err) *err = std::string(#call) + ": " + hipGetErrorString(_r);                                 \
-      return _r == hipErrorOutOfMemory ? VC_ERR_NOMEM : VC_ERR_HIP;                                      \
-    }                                                                                                    \
+// the host side's one error path: *err (if given) says what went wrong, the return value is the VC_ERR_* code
+static int fail(std::string* err, int code, const std::string& what) {
+  if (err) *err = what;
+  return code;
+}
+// a failed HIP call: hipErrorOutOfMemory gives VC_ERR_NOMEM, any other error VC_ERR_HIP; *err names the call
+static int hip_fail(std::string* err, hipError_t r, const char* what) {
+  return fail(err, r == hipErrorOutOfMemory ? VC_ERR_NOMEM : VC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(r));
+}
+#define MIH_CHECK(call)                                    \
+  do {                                                     \
+    hipError_t _r = (call);                                \
+    if (_r != hipSuccess) return hip_fail(err, _r, #call); \
   } while (0)
 
 static size_t query_kernel_lds(uint32_t buf_entries, uint32_t m, uint32_t sbits, uint32_t W, uint32_t lo);
@@ -2495,74 +2513,134 @@ static bool want_dir_lines(uint32_t sbits, uint32_t m, uint64_t n, uint32_t W, b
   return free_b > index_bytes && (size_t)m * MIH_NLINES * 64 <= (free_b - index_bytes) / 4;
 }
 
-int vc_mih_build(VcMihIndex** out, const uint64_t* d_cols, uint64_t stride, uint64_t n, uint32_t W, uint32_t m,
-                 uint32_t sbits, uint32_t id_base, uint32_t flags, uint32_t n_cu, uint32_t cand_cap, const VcKnobs& knobs,
-                 hipStream_t s, std::string* err) {
-  if (sbits != 8 && sbits != 16 && sbits != 32) {
-    if (err) *err = "substring width must be 8, 16 or 32 bits (bits / n_tables)";
-    return VC_ERR_INVALID;
+// which optional per-table structures an index gets: one decision for a build and a load
+struct MihMemPolicy {
+  bool bcodes, bent, lines;
+};
+static MihMemPolicy mem_policy(uint32_t sbits, uint32_t m, uint64_t n, uint32_t W, const VcKnobs& knobs) {
+  // bucket-order code copies for the tables whose buckets are big (see VcTableView::bcodes): m more copies of the
+  // codes, so only while they fit comfortably (dev knob VC_MIH_BCODES=0/1 overrides)
+  bool want_bcodes = sbits <= 16;
+  bool want_bent = sbits == 32 && W <= 2;   // (VcTableView::bent; VC_MIH_BENT=0/1 overrides)
+  size_t free_b = 0, total_b = 0;
+  if ((want_bcodes || want_bent) && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+    if ((size_t)m * n * W * 8 > free_b / 3) want_bcodes = false;
+    // (55 % of the free memory: 128 GB of records at 1e9 x 128 bit next to 50 GB of codes + index on a 288 GB part)
+    if ((size_t)m * n * 16 * W > free_b / 100 * 55) want_bent = false;
   }
-  int rc = upload_binom(err);
-  if (rc) return rc;
-  VcMihIndex* ix = new VcMihIndex();
+  if (knobs.mih_bcodes >= 0) want_bcodes = knobs.mih_bcodes != 0;   // dev knob VC_MIH_BCODES
+  if (knobs.mih_bent >= 0) want_bent = knobs.mih_bent != 0 && sbits == 32 && W <= 2;
+  return {want_bcodes, want_bent, want_dir_lines(sbits, m, n, W, want_bent, knobs)};
+}
+
+// device memory owned by `owner` (an index's allocs, or a DevScratch)
+template <class T>
+static hipError_t dev_alloc(std::vector<void*>& owner, T** p, size_t bytes) {
+  hipError_t r = hipMalloc((void**)p, std::max<size_t>(bytes, 256));
+  if (r == hipSuccess) owner.push_back(*p);
+  return r;
+}
+
+// device scratch of one call, freed on every way out
+struct DevScratch {
+  std::vector<void*> bufs;
+  DevScratch() = default;
+  DevScratch(const DevScratch&) = delete;
+  ~DevScratch() { for (void* p : bufs) (void)hipFree(p); }
+};
+
+// an index under construction: freed on every way out until publish_index hands it to the caller
+using MihIndexPtr = std::unique_ptr<VcMihIndex, void (*)(VcMihIndex*)>;
+
+static MihIndexPtr new_index(uint64_t n, uint32_t W, uint32_t m, uint32_t sbits, uint32_t id_base, uint32_t flags, uint32_t n_cu,
+                             uint32_t cand_cap, const VcKnobs& knobs) {
+  MihIndexPtr ix(new VcMihIndex(), vc_mih_free);
   ix->W = W; ix->m = m; ix->sbits = sbits; ix->id_base = id_base; ix->flags = flags; ix->n_cu = n_cu; ix->cap = cand_cap; ix->n = n;
   ix->knobs = knobs;
   ix->lds_per_block = device_lds_per_block();
   ix->h_tables.resize(m);
-  auto fail_free = [&](int code) { vc_mih_free(ix); return code; };
-  auto dalloc = [&](void** p, size_t bytes, bool keep) -> hipError_t {
-    hipError_t r = hipMalloc(p, std::max<size_t>(bytes, 256));
-    if (r == hipSuccess && keep) ix->allocs.push_back(*p);
-    return r;
-  };
+  return ix;
+}
 
-  // bucket-order code copies for the tables whose buckets are big (see VcTableView::bcodes): m more copies of the
-  // codes, so only while they fit comfortably (dev knob VC_MIH_BCODES=0/1 overrides)
-  bool want_bcodes = sbits <= 16;
-  {
-    size_t free_b = 0, total_b = 0;
-    if (want_bcodes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)m * n * W * 8 > free_b / 3) want_bcodes = false;
-    if (knobs.mih_bcodes >= 0) want_bcodes = knobs.mih_bcodes != 0;   // dev knob VC_MIH_BCODES
+// the per-table structures that follow from ids, offsets, bitmap and blockrank (none of them is in the index file): the
+// block directory and the directory lines of 32-bit tables, the bucket-order code copies, the {id, code} records
+static int build_derived(VcMihIndex* ix, VcTableView& tv, const MihMemPolicy& pol, const uint64_t* d_cols, uint64_t stride,
+                         hipStream_t s, std::string* err) {
+  const uint64_t n = ix->n;
+  const uint32_t W = ix->W, n_cu = ix->n_cu;
+  if (ix->sbits == 32) {
+    const uint32_t nblocks = 1u << 24;
+    uint2* blockoff = nullptr;
+    MIH_CHECK(dev_alloc(ix->allocs, &blockoff, ((size_t)nblocks + 1) * 8));
+    hipLaunchKernelGGL(mih_blockoff_kernel, dim3(n_cu * 16), dim3(256), 0, s, tv.blockrank, tv.offsets, nblocks, tv.n_unique, blockoff);
+    MIH_CHECK(hipGetLastError());
+    tv.blockoff = blockoff;
+    if (pol.lines) {
+      uint4* lines = nullptr;
+      MIH_CHECK(dev_alloc(ix->allocs, &lines, (size_t)MIH_NLINES * 64));
+      hipLaunchKernelGGL(mih_lines_kernel, dim3(n_cu * 16), dim3(256), 0, s, tv.bitmap, tv.blockrank, tv.offsets, MIH_NLINES, lines);
+      MIH_CHECK(hipGetLastError());
+      tv.lines = lines;
+    }
   }
-  bool want_bent = sbits == 32 && W <= 2;   // (VcTableView::bent; VC_MIH_BENT=0/1 overrides)
-  {
-    size_t free_b = 0, total_b = 0;
-    if (want_bent && hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)m * n * 16 * W > free_b / 100 * 55) want_bent = false;   // (55 % of the free memory: 128 GB of records at 1e9 x 128 bit next to 50 GB of codes + index on a 288 GB part)
-    if (knobs.mih_bent >= 0) want_bent = knobs.mih_bent != 0 && sbits == 32 && W <= 2;
+  if (pol.bcodes && n) {
+    uint64_t* bc = nullptr;
+    MIH_CHECK(dev_alloc(ix->allocs, &bc, (size_t)n * W * 8 + 16));   // (+ one entry: mih_bucket_stream_kernel reads 16-byte pairs)
+    hipLaunchKernelGGL(mih_bcodes_kernel, dim3(grid_for(n * W, n_cu)), dim3(256), 0, s, d_cols, stride, W, tv.ids, n, bc);
+    MIH_CHECK(hipGetLastError());
+    tv.bcodes = bc;
   }
-  const bool want_lines = want_dir_lines(sbits, m, n, W, want_bent, knobs);
+  if (pol.bent && n) {
+    uint4* be = nullptr;
+    MIH_CHECK(dev_alloc(ix->allocs, &be, (size_t)n * 16 * W));
+    hipLaunchKernelGGL(mih_bent_kernel, dim3(grid_for(n, n_cu)), dim3(256), 0, s, d_cols, stride, W, tv.ids, n, be);
+    MIH_CHECK(hipGetLastError());
+    tv.bent = be;
+  }
+  return VC_OK;
+}
+
+// the tables' views go to the device, and the index to the caller
+static int publish_index(MihIndexPtr ix, VcMihIndex** out, hipStream_t s, std::string* err) {
+  MIH_CHECK(hipMalloc((void**)&ix->d_tables, sizeof(VcTableView) * ix->m));
+  MIH_CHECK(hipMemcpyAsync(ix->d_tables, ix->h_tables.data(), sizeof(VcTableView) * ix->m, hipMemcpyHostToDevice, s));
+  MIH_CHECK(hipStreamSynchronize(s));
+  *out = ix.release();
+  return VC_OK;
+}
+
+int vc_mih_build(VcMihIndex** out, const uint64_t* d_cols, uint64_t stride, uint64_t n, uint32_t W, uint32_t m,
+                 uint32_t sbits, uint32_t id_base, uint32_t flags, uint32_t n_cu, uint32_t cand_cap, const VcKnobs& knobs,
+                 hipStream_t s, std::string* err) {
+  if (sbits != 8 && sbits != 16 && sbits != 32)
+    return fail(err, VC_ERR_INVALID, "substring width must be 8, 16 or 32 bits (bits / n_tables)");
+  int rc = upload_binom(err);
+  if (rc) return rc;
+  MihIndexPtr ix = new_index(n, W, m, sbits, id_base, flags, n_cu, cand_cap, knobs);
+  const MihMemPolicy pol = mem_policy(sbits, m, n, W, knobs);
   const uint64_t nkeyspace = 1ull << sbits;
   const uint64_t bm_words = std::max<uint64_t>(nkeyspace / 32, 8);
   const uint32_t mask = sbits == 32 ? 0xFFFFFFFFu : (uint32_t)(nkeyspace - 1);
   const uint64_t nn = std::max<uint64_t>(n, 1);
 
+  DevScratch tmp;
   uint32_t *k_in = nullptr, *k_out = nullptr, *v_in = nullptr;
   uint32_t* d_temp = nullptr;      // work area of the sort and of the scans (vc_sort.hip)
   uint32_t* d_scan_in = nullptr;   // counts (direct) or blockpop (ranked)
-#define B_CHECK(call)                                                                     \
-  do {                                                                                    \
-    hipError_t _r = (call);                                                               \
-    if (_r != hipSuccess) {                                                               \
-      if (err) *err = std::string(#call) + ": " + hipGetErrorString(_r);                  \
-      (void)hipFree(k_in); (void)hipFree(k_out); (void)hipFree(v_in); (void)hipFree(d_temp); (void)hipFree(d_scan_in); \
-      return fail_free(_r == hipErrorOutOfMemory ? VC_ERR_NOMEM : VC_ERR_HIP);            \
-    }                                                                                     \
-  } while (0)
-
-  B_CHECK(dalloc((void**)&k_in, nn * 4, false));
-  B_CHECK(dalloc((void**)&k_out, nn * 4, false));
-  B_CHECK(dalloc((void**)&v_in, nn * 4, false));
+  MIH_CHECK(dev_alloc(tmp.bufs, &k_in, nn * 4));
+  MIH_CHECK(dev_alloc(tmp.bufs, &k_out, nn * 4));
+  MIH_CHECK(dev_alloc(tmp.bufs, &v_in, nn * 4));
   const uint64_t scan_n = sbits == 32 ? (1ull << 24) : nkeyspace + 1;
   const size_t temp_words = std::max(vc_radix_sort_work_words(n), vc_scan_work_words(scan_n));
-  B_CHECK(dalloc((void**)&d_temp, temp_words * 4, false));
-  B_CHECK(dalloc((void**)&d_scan_in, (scan_n + 1) * 4, false));
+  MIH_CHECK(dev_alloc(tmp.bufs, &d_temp, temp_words * 4));
+  MIH_CHECK(dev_alloc(tmp.bufs, &d_scan_in, (scan_n + 1) * 4));
   const uint32_t passes = vc_radix_sort_passes(sbits);
 
   for (uint32_t t = 0; t < m; ++t) {
     uint32_t *ids = nullptr, *bitmap = nullptr, *offsets = nullptr, *blockrank = nullptr;
-    B_CHECK(dalloc((void**)&ids, nn * 4, true));
-    B_CHECK(dalloc((void**)&bitmap, bm_words * 4, true));
-    B_CHECK(hipMemsetAsync(bitmap, 0, bm_words * 4, s));
+    MIH_CHECK(dev_alloc(ix->allocs, &ids, nn * 4));
+    MIH_CHECK(dev_alloc(ix->allocs, &bitmap, bm_words * 4));
+    MIH_CHECK(hipMemsetAsync(bitmap, 0, bm_words * 4, s));
     const uint32_t bitpos = t * sbits;
     if (n) {
       // stable LSD radix sort by key (vc_sort.hip): ids stay ascending inside a bucket = append order of
@@ -2573,80 +2651,47 @@ int vc_mih_build(VcMihIndex** out, const uint64_t* d_cols, uint64_t stride, uint
       if ((passes & 1u) == 0) { std::swap(kb[0], kb[1]); std::swap(vb[0], vb[1]); }
       hipLaunchKernelGGL(mih_keys_kernel, dim3(grid_for(n, n_cu)), dim3(256), 0, s, d_cols + (uint64_t)(bitpos >> 6) * stride, n,
                          bitpos & 63, mask, kb[0], vb[0]);
-      B_CHECK(hipGetLastError());
-      B_CHECK(vc_radix_sort_pairs(kb, vb, n, sbits, d_temp, s));   // result in pair (passes & 1) = (k_out, ids)
+      MIH_CHECK(hipGetLastError());
+      MIH_CHECK(vc_radix_sort_pairs(kb, vb, n, sbits, d_temp, s));   // result in pair (passes & 1) = (k_out, ids)
     }
     VcTableView tv{};
     if (sbits < 32) {
-      B_CHECK(dalloc((void**)&offsets, (nkeyspace + 1) * 4, true));
-      B_CHECK(hipMemsetAsync(d_scan_in, 0, (nkeyspace + 1) * 4, s));
+      MIH_CHECK(dev_alloc(ix->allocs, &offsets, (nkeyspace + 1) * 4));
+      MIH_CHECK(hipMemsetAsync(d_scan_in, 0, (nkeyspace + 1) * 4, s));
       if (n) {
         hipLaunchKernelGGL(mih_runs_kernel, dim3(grid_for(n, n_cu)), dim3(256), 0, s, k_out, n, bitmap, d_scan_in);
-        B_CHECK(hipGetLastError());
+        MIH_CHECK(hipGetLastError());
       }
-      B_CHECK(vc_exclusive_scan_u32(d_scan_in, offsets, nkeyspace + 1, d_temp, s));
+      MIH_CHECK(vc_exclusive_scan_u32(d_scan_in, offsets, nkeyspace + 1, d_temp, s));
       tv.n_unique = 0;
     } else {
       if (n) {
         hipLaunchKernelGGL(mih_runs_kernel, dim3(grid_for(n, n_cu)), dim3(256), 0, s, k_out, n, bitmap, (uint32_t*)nullptr);
-        B_CHECK(hipGetLastError());
+        MIH_CHECK(hipGetLastError());
       }
       const uint32_t nblocks = 1u << 24;
-      B_CHECK(dalloc((void**)&blockrank, (size_t)nblocks * 4, true));
+      MIH_CHECK(dev_alloc(ix->allocs, &blockrank, (size_t)nblocks * 4));
       hipLaunchKernelGGL(mih_blockpop_kernel, dim3(n_cu * 16), dim3(256), 0, s, bitmap, nblocks, d_scan_in);
-      B_CHECK(hipGetLastError());
-      B_CHECK(vc_exclusive_scan_u32(d_scan_in, blockrank, nblocks, d_temp, s));
+      MIH_CHECK(hipGetLastError());
+      MIH_CHECK(vc_exclusive_scan_u32(d_scan_in, blockrank, nblocks, d_temp, s));
       uint32_t last_rank = 0, last_pop = 0;
-      B_CHECK(hipMemcpyAsync(&last_rank, blockrank + nblocks - 1, 4, hipMemcpyDeviceToHost, s));
-      B_CHECK(hipMemcpyAsync(&last_pop, d_scan_in + nblocks - 1, 4, hipMemcpyDeviceToHost, s));
-      B_CHECK(hipStreamSynchronize(s));
+      MIH_CHECK(hipMemcpyAsync(&last_rank, blockrank + nblocks - 1, 4, hipMemcpyDeviceToHost, s));
+      MIH_CHECK(hipMemcpyAsync(&last_pop, d_scan_in + nblocks - 1, 4, hipMemcpyDeviceToHost, s));
+      MIH_CHECK(hipStreamSynchronize(s));
       tv.n_unique = last_rank + last_pop;
-      B_CHECK(dalloc((void**)&offsets, ((size_t)tv.n_unique + 1) * 4, true));
+      MIH_CHECK(dev_alloc(ix->allocs, &offsets, ((size_t)tv.n_unique + 1) * 4));
       hipLaunchKernelGGL(mih_ranked_offsets_kernel, dim3(grid_for(nn, n_cu)), dim3(256), 0, s, k_out, n, bitmap, blockrank,
                          offsets, tv.n_unique);
-      B_CHECK(hipGetLastError());
-      uint2* blockoff = nullptr;
-      B_CHECK(dalloc((void**)&blockoff, ((size_t)nblocks + 1) * 8, true));
-      hipLaunchKernelGGL(mih_blockoff_kernel, dim3(n_cu * 16), dim3(256), 0, s, blockrank, offsets, nblocks, tv.n_unique, blockoff);
-      B_CHECK(hipGetLastError());
-      tv.blockoff = blockoff;
-      if (want_lines) {
-        uint4* lines = nullptr;
-        B_CHECK(dalloc((void**)&lines, (size_t)MIH_NLINES * 64, true));
-        hipLaunchKernelGGL(mih_lines_kernel, dim3(n_cu * 16), dim3(256), 0, s, bitmap, blockrank, offsets, MIH_NLINES, lines);
-        B_CHECK(hipGetLastError());
-        tv.lines = lines;
-      }
+      MIH_CHECK(hipGetLastError());
     }
     tv.offsets = offsets;
     tv.ids = ids;
     tv.bitmap = bitmap;
     tv.blockrank = blockrank;
-    tv.bcodes = nullptr;
-    if (want_bcodes && n) {
-      uint64_t* bc = nullptr;
-      B_CHECK(dalloc((void**)&bc, (size_t)n * W * 8 + 16, true));   // (+ one entry: mih_bucket_stream_kernel reads 16-byte pairs)
-      hipLaunchKernelGGL(mih_bcodes_kernel, dim3(grid_for(n * W, n_cu)), dim3(256), 0, s, d_cols, stride, W, ids, n, bc);
-      B_CHECK(hipGetLastError());
-      tv.bcodes = bc;
-    }
-    tv.bent = nullptr;
-    if (want_bent && n) {
-      uint4* be = nullptr;
-      B_CHECK(dalloc((void**)&be, (size_t)n * 16 * W, true));
-      hipLaunchKernelGGL(mih_bent_kernel, dim3(grid_for(n, n_cu)), dim3(256), 0, s, d_cols, stride, W, ids, n, be);
-      B_CHECK(hipGetLastError());
-      tv.bent = be;
-    }
+    if ((rc = build_derived(ix.get(), tv, pol, d_cols, stride, s, err))) return rc;
     ix->h_tables[t] = tv;
   }
-  B_CHECK(hipMalloc((void**)&ix->d_tables, sizeof(VcTableView) * m));
-  B_CHECK(hipMemcpyAsync(ix->d_tables, ix->h_tables.data(), sizeof(VcTableView) * m, hipMemcpyHostToDevice, s));
-  B_CHECK(hipStreamSynchronize(s));
-  (void)hipFree(k_in); (void)hipFree(k_out); (void)hipFree(v_in); (void)hipFree(d_temp); (void)hipFree(d_scan_in);
-#undef B_CHECK
-  *out = ix;
-  return VC_OK;
+  return publish_index(std::move(ix), out, s, err);
 }
 
 // ---- BaseProxy-style views (tests / adapters; not on the search path) --------------------------------
@@ -2724,10 +2769,7 @@ int vc_mih_bitmap_test(VcMihIndex* ix, uint32_t table, uint32_t index, int* bit,
 int vc_mih_bitmap_read(VcMihIndex* ix, uint32_t table, uint64_t word_off, uint64_t n_words, uint32_t* out, hipStream_t s,
                        std::string* err) {
   const uint64_t words = (1ull << ix->sbits) / 32;
-  if (word_off + n_words > words) {
-    if (err) *err = "bitmap read out of range";
-    return VC_ERR_INVALID;
-  }
+  if (word_off + n_words > words) return fail(err, VC_ERR_INVALID, "bitmap read out of range");
   MIH_CHECK(hipMemcpyAsync(out, ix->h_tables[table].bitmap + word_off, n_words * 4, hipMemcpyDeviceToHost, s));
   MIH_CHECK(hipStreamSynchronize(s));
   return VC_OK;
@@ -2759,10 +2801,7 @@ static int cols_checksum(const uint64_t* d_cols, uint64_t stride, uint32_t W, ui
   if (r == hipSuccess) r = hipMemcpyAsync(&h, d_sum, 8, hipMemcpyDeviceToHost, s);
   if (r == hipSuccess) r = hipStreamSynchronize(s);
   (void)hipFree(d_sum);
-  if (r != hipSuccess) {
-    if (err) *err = std::string("index checksum: ") + hipGetErrorString(r);
-    return VC_ERR_HIP;
-  }
+  if (r != hipSuccess) return fail(err, VC_ERR_HIP, std::string("index checksum: ") + hipGetErrorString(r));
   *out = h;
   return VC_OK;
 }
@@ -2773,10 +2812,7 @@ static int copy_out(FILE* fh, const void* d_src, size_t bytes, hipStream_t s, st
     const size_t cnt = std::min(buf.size(), bytes - off);
     MIH_CHECK(hipMemcpyAsync(buf.data(), (const char*)d_src + off, cnt, hipMemcpyDeviceToHost, s));
     MIH_CHECK(hipStreamSynchronize(s));
-    if (fwrite(buf.data(), 1, cnt, fh) != cnt) {
-      if (err) *err = "short write to the index file";
-      return VC_ERR_INVALID;
-    }
+    if (fwrite(buf.data(), 1, cnt, fh) != cnt) return fail(err, VC_ERR_INVALID, "short write to the index file");
   }
   return VC_OK;
 }
@@ -2784,10 +2820,7 @@ static int copy_out(FILE* fh, const void* d_src, size_t bytes, hipStream_t s, st
 static int copy_in(FILE* fh, void* d_dst, size_t bytes, hipStream_t s, std::vector<char>& buf, std::string* err) {
   for (size_t off = 0; off < bytes; off += buf.size()) {
     const size_t cnt = std::min(buf.size(), bytes - off);
-    if (fread(buf.data(), 1, cnt, fh) != cnt) {
-      if (err) *err = "index file is truncated";
-      return VC_ERR_INVALID;
-    }
+    if (fread(buf.data(), 1, cnt, fh) != cnt) return fail(err, VC_ERR_INVALID, "index file is truncated");
     MIH_CHECK(hipMemcpyAsync((char*)d_dst + off, buf.data(), cnt, hipMemcpyHostToDevice, s));
     MIH_CHECK(hipStreamSynchronize(s));
   }
@@ -2799,10 +2832,7 @@ int vc_mih_save(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, const c
   int rc0 = cols_checksum(d_cols, stride, ix->W, ix->n, ix->n_cu, s, &digest, err);
   if (rc0) return rc0;
   FILE* fh = fopen(path, "wb");
-  if (!fh) {
-    if (err) *err = std::string("Can't create file ") + path + ".";
-    return VC_ERR_INVALID;
-  }
+  if (!fh) return fail(err, VC_ERR_INVALID, std::string("Can't create file ") + path + ".");
   VcIndexHeader h{};
   memcpy(h.magic, kIndexMagic, 8);
   h.version = VC_INDEX_VERSION; h.bits = ix->W * 64; h.m = ix->m; h.sbits = ix->sbits; h.id_base = ix->id_base; h.n = ix->n;
@@ -2833,106 +2863,68 @@ int vc_mih_save(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, const c
 int vc_mih_load(VcMihIndex** out, const char* path, const uint64_t* d_cols, uint64_t stride, uint64_t n, uint32_t W, uint32_t m,
                 uint32_t sbits, uint32_t id_base, uint32_t flags, uint32_t n_cu, uint32_t cand_cap, const VcKnobs& knobs,
                 hipStream_t s, std::string* err) {
-  FILE* fh = fopen(path, "rb");
-  if (!fh) {
-    if (err) *err = std::string("Can't open file ") + path + ".";
-    return VC_ERR_INVALID;
-  }
+  const std::unique_ptr<FILE, int (*)(FILE*)> file(fopen(path, "rb"), fclose);
+  FILE* fh = file.get();
+  if (!fh) return fail(err, VC_ERR_INVALID, std::string("Can't open file ") + path + ".");
   VcIndexHeader h{};
-  if (fread(&h, sizeof h, 1, fh) != 1 || memcmp(h.magic, kIndexMagic, 8) != 0 || h.version != VC_INDEX_VERSION) {
-    fclose(fh);
-    if (err) *err = "not a verticut_gpu index file (bad magic or version)";
-    return VC_ERR_INVALID;
-  }
-  if (h.bits != W * 64 || h.m != m || h.sbits != sbits || h.n != n || h.id_base != id_base) {
-    fclose(fh);
-    if (err) *err = "index file was built for another database shape (bits / n_tables / records / id_base differ)";
-    return VC_ERR_STATE;
-  }
+  if (fread(&h, sizeof h, 1, fh) != 1 || memcmp(h.magic, kIndexMagic, 8) != 0 || h.version != VC_INDEX_VERSION)
+    return fail(err, VC_ERR_INVALID, "not a verticut_gpu index file (bad magic or version)");
+  if (h.bits != W * 64 || h.m != m || h.sbits != sbits || h.n != n || h.id_base != id_base)
+    return fail(err, VC_ERR_STATE, "index file was built for another database shape (bits / n_tables / records / id_base differ)");
   {   // the file must be exactly as long as its header says (truncated copies, appended garbage)
     const long at = ftell(fh);
     uint64_t size = 0;
     if (at < 0 || fseek(fh, 0, SEEK_END) != 0) size = 0; else size = (uint64_t)ftell(fh);
-    if (size != h.file_bytes || fseek(fh, at, SEEK_SET) != 0) {
-      fclose(fh);
-      if (err) *err = "index file is truncated or has trailing bytes (size differs from its header)";
-      return VC_ERR_INVALID;
-    }
+    if (size != h.file_bytes || fseek(fh, at, SEEK_SET) != 0)
+      return fail(err, VC_ERR_INVALID, "index file is truncated or has trailing bytes (size differs from its header)");
   }
   int rc = upload_binom(err);
-  if (rc) { fclose(fh); return rc; }
+  if (rc) return rc;
   {   // the index must have been built from THESE records, not merely from a database of the same shape
     uint64_t digest = 0;
-    if ((rc = cols_checksum(d_cols, stride, W, n, n_cu, s, &digest, err))) { fclose(fh); return rc; }
-    if (digest != h.cols_checksum) {
-      fclose(fh);
-      if (err) *err = "index file was built from other records than the resident ones (code checksum differs)";
-      return VC_ERR_STATE;
-    }
+    if ((rc = cols_checksum(d_cols, stride, W, n, n_cu, s, &digest, err))) return rc;
+    if (digest != h.cols_checksum)
+      return fail(err, VC_ERR_STATE, "index file was built from other records than the resident ones (code checksum differs)");
   }
-  VcMihIndex* ix = new VcMihIndex();
-  ix->W = W; ix->m = m; ix->sbits = sbits; ix->id_base = id_base; ix->flags = flags; ix->n_cu = n_cu; ix->cap = cand_cap; ix->n = n;
-  ix->knobs = knobs;
-  ix->lds_per_block = device_lds_per_block();
-  ix->h_tables.resize(m);
+  MihIndexPtr ix = new_index(n, W, m, sbits, id_base, flags, n_cu, cand_cap, knobs);
+  const MihMemPolicy pol = mem_policy(sbits, m, n, W, knobs);
   std::vector<char> buf(32u << 20);
   const uint64_t bm_words = std::max<uint64_t>((1ull << sbits) / 32, 8);
-  bool want_bcodes = sbits <= 16;
-  {
-    size_t free_b = 0, total_b = 0;
-    if (want_bcodes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)m * n * W * 8 > free_b / 3) want_bcodes = false;
-    if (knobs.mih_bcodes >= 0) want_bcodes = knobs.mih_bcodes != 0;
-  }
-  bool want_bent = sbits == 32 && W <= 2;
-  {
-    size_t free_b = 0, total_b = 0;
-    if (want_bent && hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)m * n * 16 * W > free_b / 100 * 55) want_bent = false;   // (55 % of the free memory: 128 GB of records at 1e9 x 128 bit next to 50 GB of codes + index on a 288 GB part)
-    if (knobs.mih_bent >= 0) want_bent = knobs.mih_bent != 0 && sbits == 32 && W <= 2;
-  }
-  const bool want_lines = want_dir_lines(sbits, m, n, W, want_bent, knobs);
-  auto dalloc = [&](void** p, size_t bytes) -> int {
-    hipError_t r = hipMalloc(p, std::max<size_t>(bytes, 256));
-    if (r != hipSuccess) {
-      if (err) *err = std::string("index load: ") + hipGetErrorString(r);
-      return r == hipErrorOutOfMemory ? VC_ERR_NOMEM : VC_ERR_HIP;
-    }
-    ix->allocs.push_back(*p);
-    return VC_OK;
-  };
-  for (uint32_t t = 0; t < m && rc == VC_OK; ++t) {
+  for (uint32_t t = 0; t < m; ++t) {
     uint64_t th[2];
-    if (fread(th, sizeof th, 1, fh) != 1) { rc = VC_ERR_INVALID; if (err) *err = "index file is truncated"; break; }
+    if (fread(th, sizeof th, 1, fh) != 1) return fail(err, VC_ERR_INVALID, "index file is truncated");
     const uint64_t expect = sbits == 32 ? th[0] + 1 : (1ull << sbits) + 1;
-    if (th[1] != expect || th[0] > n) { rc = VC_ERR_INVALID; if (err) *err = "index file is corrupt (table directory)"; break; }
-    VcTableView tv{};
+    if (th[1] != expect || th[0] > n) return fail(err, VC_ERR_INVALID, "index file is corrupt (table directory)");
     uint32_t *ids = nullptr, *offsets = nullptr, *bitmap = nullptr, *blockrank = nullptr;
-    if ((rc = dalloc((void**)&ids, (size_t)std::max<uint64_t>(n, 1) * 4))) break;
-    if ((rc = dalloc((void**)&offsets, (size_t)th[1] * 4))) break;
-    if ((rc = dalloc((void**)&bitmap, (size_t)bm_words * 4))) break;
-    if ((rc = copy_in(fh, ids, (size_t)n * 4, s, buf, err))) break;
-    if ((rc = copy_in(fh, offsets, (size_t)th[1] * 4, s, buf, err))) break;
-    if ((rc = copy_in(fh, bitmap, (size_t)bm_words * 4, s, buf, err))) break;
+    MIH_CHECK(dev_alloc(ix->allocs, &ids, (size_t)std::max<uint64_t>(n, 1) * 4));
+    MIH_CHECK(dev_alloc(ix->allocs, &offsets, (size_t)th[1] * 4));
+    MIH_CHECK(dev_alloc(ix->allocs, &bitmap, (size_t)bm_words * 4));
+    if ((rc = copy_in(fh, ids, (size_t)n * 4, s, buf, err))) return rc;
+    if ((rc = copy_in(fh, offsets, (size_t)th[1] * 4, s, buf, err))) return rc;
+    if ((rc = copy_in(fh, bitmap, (size_t)bm_words * 4, s, buf, err))) return rc;
     if (sbits == 32) {
-      if ((rc = dalloc((void**)&blockrank, (size_t)(1u << 24) * 4))) break;
-      if ((rc = copy_in(fh, blockrank, (size_t)(1u << 24) * 4, s, buf, err))) break;
+      MIH_CHECK(dev_alloc(ix->allocs, &blockrank, (size_t)(1u << 24) * 4));
+      if ((rc = copy_in(fh, blockrank, (size_t)(1u << 24) * 4, s, buf, err))) return rc;
     }
+    VcTableView tv{};
     tv.ids = ids; tv.offsets = offsets; tv.bitmap = bitmap; tv.blockrank = blockrank; tv.n_unique = (uint32_t)th[0];
     {   // device validation pass: see the kernels above.  Order matters: offsets and ranks first, entries last (the
         // entry check dereferences offsets[rank(key)], which is only safe to trust once... it is bounds-checked anyway)
+      DevScratch tmp;
       uint32_t *d_bad = nullptr, *d_seen = nullptr, *d_pop = nullptr, *d_exp = nullptr, *d_work = nullptr;
       const uint32_t nblocks = 1u << 24;
-      hipError_t r = hipMalloc((void**)&d_bad, 4);
+      hipError_t r = dev_alloc(tmp.bufs, &d_bad, 4);
       if (r == hipSuccess) r = hipMemsetAsync(d_bad, 0, 4, s);
-      if (r == hipSuccess) r = hipMalloc((void**)&d_seen, (size_t)((n + 31) / 32 + 1) * 4);
+      if (r == hipSuccess) r = dev_alloc(tmp.bufs, &d_seen, (size_t)((n + 31) / 32 + 1) * 4);
       if (r == hipSuccess) r = hipMemsetAsync(d_seen, 0, (size_t)((n + 31) / 32 + 1) * 4, s);
       if (r == hipSuccess) {
         hipLaunchKernelGGL(mih_validate_offsets_kernel, dim3(grid_for(th[1], n_cu)), dim3(256), 0, s, offsets, th[1], n, d_bad);
         r = hipGetLastError();
       }
       if (r == hipSuccess && sbits == 32) {
-        r = hipMalloc((void**)&d_pop, (size_t)(nblocks + 1) * 4);
-        if (r == hipSuccess) r = hipMalloc((void**)&d_exp, (size_t)nblocks * 4);
-        if (r == hipSuccess) r = hipMalloc((void**)&d_work, std::max<size_t>(vc_scan_work_words(nblocks), 64) * 4);
+        r = dev_alloc(tmp.bufs, &d_pop, (size_t)(nblocks + 1) * 4);
+        if (r == hipSuccess) r = dev_alloc(tmp.bufs, &d_exp, (size_t)nblocks * 4);
+        if (r == hipSuccess) r = dev_alloc(tmp.bufs, &d_work, std::max<size_t>(vc_scan_work_words(nblocks), 64) * 4);
         if (r == hipSuccess) {
           hipLaunchKernelGGL(mih_blockpop_kernel, dim3(n_cu * 16), dim3(256), 0, s, bitmap, nblocks, d_pop);
           r = hipGetLastError();
@@ -2954,64 +2946,19 @@ int vc_mih_load(VcMihIndex** out, const char* path, const uint64_t* d_cols, uint
         if (r == hipSuccess) r = hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s);
         if (r == hipSuccess) r = hipStreamSynchronize(s);
       }
-      (void)hipFree(d_bad); (void)hipFree(d_seen); (void)hipFree(d_pop); (void)hipFree(d_exp); (void)hipFree(d_work);
-      if (r != hipSuccess) {
-        if (err) *err = std::string("index validation: ") + hipGetErrorString(r);
-        rc = r == hipErrorOutOfMemory ? VC_ERR_NOMEM : VC_ERR_HIP;
-        break;
-      }
+      if (r != hipSuccess) return hip_fail(err, r, "index validation");
       if (bad) {
         char msg[160];
         snprintf(msg, sizeof msg, "index file is corrupt: table %u fails validation (%s%s%s%s%s)", t, bad & MIH_BAD_OFFSETS ? "offsets " : "",
                  bad & MIH_BAD_RANK ? "rank-directory " : "", bad & MIH_BAD_ID ? "id-range " : "", bad & MIH_BAD_DUP ? "duplicate-ids " : "",
                  bad & MIH_BAD_BUCKET ? "bucket-membership " : "");
-        if (err) *err = msg;
-        rc = VC_ERR_STATE;
-        break;
+        return fail(err, VC_ERR_STATE, msg);
       }
     }
-    if (sbits == 32) {   // derived directory, not in the file (see VcTableView::blockoff)
-      uint2* blockoff = nullptr;
-      if ((rc = dalloc((void**)&blockoff, ((size_t)(1u << 24) + 1) * 8))) break;
-      hipLaunchKernelGGL(mih_blockoff_kernel, dim3(n_cu * 16), dim3(256), 0, s, blockrank, offsets, 1u << 24, tv.n_unique, blockoff);
-      tv.blockoff = blockoff;
-      if (want_lines) {
-        uint4* lines = nullptr;
-        if ((rc = dalloc((void**)&lines, (size_t)MIH_NLINES * 64))) break;
-        hipLaunchKernelGGL(mih_lines_kernel, dim3(n_cu * 16), dim3(256), 0, s, bitmap, blockrank, offsets, MIH_NLINES, lines);
-        tv.lines = lines;
-      }
-    }
-    if (want_bcodes && n) {
-      uint64_t* bc = nullptr;
-      if ((rc = dalloc((void**)&bc, (size_t)n * W * 8 + 16))) break;
-      hipLaunchKernelGGL(mih_bcodes_kernel, dim3(grid_for(n * W, n_cu)), dim3(256), 0, s, d_cols, stride, W, ids, n, bc);
-      tv.bcodes = bc;
-    }
-    if (want_bent && n) {
-      uint4* be = nullptr;
-      if ((rc = dalloc((void**)&be, (size_t)n * 16 * W))) break;
-      hipLaunchKernelGGL(mih_bent_kernel, dim3(grid_for(n, n_cu)), dim3(256), 0, s, d_cols, stride, W, ids, n, be);
-      tv.bent = be;
-    }
+    if ((rc = build_derived(ix.get(), tv, pol, d_cols, stride, s, err))) return rc;
     ix->h_tables[t] = tv;
   }
-  fclose(fh);
-  if (rc == VC_OK) {
-    hipError_t r = hipMalloc((void**)&ix->d_tables, sizeof(VcTableView) * m);
-    if (r == hipSuccess) r = hipMemcpyAsync(ix->d_tables, ix->h_tables.data(), sizeof(VcTableView) * m, hipMemcpyHostToDevice, s);
-    if (r == hipSuccess) r = hipStreamSynchronize(s);
-    if (r != hipSuccess) {
-      if (err) *err = std::string("index load: ") + hipGetErrorString(r);
-      rc = VC_ERR_HIP;
-    }
-  }
-  if (rc != VC_OK) {
-    vc_mih_free(ix);
-    return rc;
-  }
-  *out = ix;
-  return VC_OK;
+  return publish_index(std::move(ix), out, s, err);
 }
 
 // ---- search -------------------------------------------------------------------------------------------
@@ -3065,14 +3012,10 @@ static int ensure_tile(VcMihIndex* ix, uint32_t slots, uint32_t k, uint32_t cap,
 
 static hipError_t launch_probe(const ProbeParams& p, uint32_t W, uint32_t n_list, hipStream_t s) {
   const dim3 grid((p.nkeys + MIH_PCH - 1) / MIH_PCH, p.m_probe ? p.m_probe : p.m, n_list);
-  switch (W) {
-    case 1: hipLaunchKernelGGL(mih_probe_kernel<1>, grid, dim3(MIH_BLK), 0, s, p); break;
-    case 2: hipLaunchKernelGGL(mih_probe_kernel<2>, grid, dim3(MIH_BLK), 0, s, p); break;
-    case 4: hipLaunchKernelGGL(mih_probe_kernel<4>, grid, dim3(MIH_BLK), 0, s, p); break;
-    case 8: hipLaunchKernelGGL(mih_probe_kernel<8>, grid, dim3(MIH_BLK), 0, s, p); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_w(W, [&](auto w) {
+    hipLaunchKernelGGL(mih_probe_kernel<decltype(w)::value>, grid, dim3(MIH_BLK), 0, s, p);
+    return hipGetLastError();
+  });
 }
 
 static size_t query_kernel_lds(uint32_t buf_entries, uint32_t m, uint32_t sbits, uint32_t W = VC_MAX_W, uint32_t lo = MQ_LO_MAX) {
@@ -3084,23 +3027,35 @@ static size_t query_kernel_lds(uint32_t buf_entries, uint32_t m, uint32_t sbits,
 
 static hipError_t launch_query_kernel(const QueryKernelParams& p, uint32_t W, uint32_t nq, hipStream_t s) {
   const size_t lds = query_kernel_lds(p.buf_entries, p.m, p.sbits, W, p.mode == MQ_MODE_RADIUS ? MQ_LO_RADIUS : MQ_LO_KNN);
-#define MQ_LAUNCH_K(K_) hipLaunchKernelGGL((K_), dim3(nq), dim3(MQ_BLK), lds, s, p)
-#define MQ_LAUNCH(W_)                                                                                           \
-  case W_:                                                                                                      \
-    if (p.mode == MQ_MODE_RADIUS) MQ_LAUNCH_K((mih_query_kernel<W_, MQ_LO_RADIUS, false>));                     \
-    else if (p.use_lines && MQ_LO_KNN == 7u) MQ_LAUNCH_K((mih_query_kernel<W_, MQ_LO_KNN, MQ_LO_KNN == 7u>));   \
-    else MQ_LAUNCH_K((mih_query_kernel<W_, MQ_LO_KNN, false>));                                                 \
-    break;
-  switch (W) {
-    MQ_LAUNCH(1)
-    MQ_LAUNCH(2)
-    MQ_LAUNCH(4)
-    MQ_LAUNCH(8)
-    default: return hipErrorInvalidValue;
+  return with_w(W, [&](auto w) {
+    constexpr int W_ = decltype(w)::value;
+    const dim3 grid(nq), block(MQ_BLK);
+    if (p.mode == MQ_MODE_RADIUS) hipLaunchKernelGGL((mih_query_kernel<W_, MQ_LO_RADIUS, false>), grid, block, lds, s, p);
+    else if (p.use_lines && MQ_LO_KNN == 7u) hipLaunchKernelGGL((mih_query_kernel<W_, MQ_LO_KNN, MQ_LO_KNN == 7u>), grid, block, lds, s, p);
+    else hipLaunchKernelGGL((mih_query_kernel<W_, MQ_LO_KNN, false>), grid, block, lds, s, p);
+    return hipGetLastError();
+  });
+}
+
+// vc_get_timing's records of a launch: every launch is counted, every knobs.timing_every-th one is bracketed by a pair of
+// events on its stream (at most 4096 pairs between two reads of vc_mih_timing)
+template <class F>
+static hipError_t timed_launch(VcMihIndex* ix, hipStream_t s, F&& launch) {
+  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+  ++ix->launches_all;
+  if (ix->ev_used < 4096 && ix->launch_tick++ % std::max(ix->knobs.timing_every, 1u) == 0) {
+    if (ix->ev_used == ix->ev_pool.size()) {
+      hipEvent_t a, b;
+      if (hipEventCreate(&a) == hipSuccess) {
+        if (hipEventCreate(&b) == hipSuccess) ix->ev_pool.emplace_back(a, b); else (void)hipEventDestroy(a);
+      }
+    }
+    if (ix->ev_used < ix->ev_pool.size()) ev = &ix->ev_pool[ix->ev_used++];
   }
-#undef MQ_LAUNCH
-#undef MQ_LAUNCH_K
-  return hipGetLastError();
+  if (ev) (void)hipEventRecord(ev->first, s);
+  const hipError_t r = launch();
+  if (ev) (void)hipEventRecord(ev->second, s);
+  return r;
 }
 
 // launch + measurement: events on the launch stream around the kernel, then the reduction of its work counters
@@ -3120,22 +3075,9 @@ static hipError_t timed_query_launch(VcMihIndex* ix, const QueryKernelParams& p_
     if (r == hipSuccess) r = hipMemsetAsync(ix->d_totals, 0, 32, s);
     if (r != hipSuccess) return r;
   }
-  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
-  ++ix->launches_all;
-  if (ix->ev_used < 4096 && ix->launch_tick++ % std::max(ix->knobs.timing_every, 1u) == 0) {
-    if (ix->ev_used == ix->ev_pool.size()) {
-      hipEvent_t a, b;
-      if (hipEventCreate(&a) == hipSuccess) {
-        if (hipEventCreate(&b) == hipSuccess) ix->ev_pool.emplace_back(a, b); else (void)hipEventDestroy(a);
-      }
-    }
-    if (ix->ev_used < ix->ev_pool.size()) ev = &ix->ev_pool[ix->ev_used++];
-  }
-  if (ev) (void)hipEventRecord(ev->first, s);
   // (approximate k-NN on the 512-bit-granule instantiation -- its deep shells are sector-bound like the radius search's -- measured
   // 10 % slower than on 128-bit granules, 0.81 vs 0.89 M queries/s: r04_sweeps.md)
-  hipError_t r = launch_query_kernel(p, W, nq, s);
-  if (ev) (void)hipEventRecord(ev->second, s);
+  hipError_t r = timed_launch(ix, s, [&] { return launch_query_kernel(p, W, nq, s); });
   if (r != hipSuccess) return r;
   // (k-NN launches: heavy_ctr = the tile's counter block + 2.  Radius search has no counters to publish, and its work
   // counters are summed by vc_radius_offsets_kernel, which follows anyway)
@@ -3172,13 +3114,9 @@ static uint32_t stream_resident_blocks(uint32_t W, uint32_t n_cu) {
   if (W > 8) return n_cu;
   if (!per_cu[W]) {
     int b = 0;
-    hipError_t r = hipErrorInvalidValue;
-    switch (W) {
-      case 1: r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, mih_bucket_stream_kernel<1>, 256, 0); break;
-      case 2: r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, mih_bucket_stream_kernel<2>, 256, 0); break;
-      case 4: r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, mih_bucket_stream_kernel<4>, 256, 0); break;
-      case 8: r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, mih_bucket_stream_kernel<8>, 256, 0); break;
-    }
+    const hipError_t r = with_w(W, [&](auto w) {
+      return hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, mih_bucket_stream_kernel<decltype(w)::value>, 256, 0);
+    });
     if (r != hipSuccess) (void)hipGetLastError();
     per_cu[W] = (r == hipSuccess && b > 0) ? (uint32_t)b : 2u;
   }
@@ -3199,28 +3137,12 @@ static hipError_t timed_stream_launch(VcMihIndex* ix, StreamParams sp, uint32_t 
     (void)hipMemsetAsync(d_trace, 0, (size_t)nblocks * 24, s);
     sp.trace = d_trace;
   }
-  std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
-  ++ix->launches_all;
-  if (ix->ev_used < 4096 && ix->launch_tick++ % std::max(ix->knobs.timing_every, 1u) == 0) {
-    if (ix->ev_used == ix->ev_pool.size()) {
-      hipEvent_t a, b;
-      if (hipEventCreate(&a) == hipSuccess) {
-        if (hipEventCreate(&b) == hipSuccess) ix->ev_pool.emplace_back(a, b); else (void)hipEventDestroy(a);
-      }
-    }
-    if (ix->ev_used < ix->ev_pool.size()) ev = &ix->ev_pool[ix->ev_used++];
-  }
-  if (ev) (void)hipEventRecord(ev->first, s);
-  const dim3 grid(nq * sp.split);
-  switch (W) {
-    case 1: hipLaunchKernelGGL(mih_bucket_stream_kernel<1>, grid, dim3(256), 0, s, sp); break;
-    case 2: hipLaunchKernelGGL(mih_bucket_stream_kernel<2>, grid, dim3(256), 0, s, sp); break;
-    case 4: hipLaunchKernelGGL(mih_bucket_stream_kernel<4>, grid, dim3(256), 0, s, sp); break;
-    case 8: hipLaunchKernelGGL(mih_bucket_stream_kernel<8>, grid, dim3(256), 0, s, sp); break;
-    default: return hipErrorInvalidValue;
-  }
-  hipError_t r = hipGetLastError();
-  if (ev) (void)hipEventRecord(ev->second, s);
+  const hipError_t r = timed_launch(ix, s, [&] {
+    return with_w(W, [&](auto w) {
+      hipLaunchKernelGGL(mih_bucket_stream_kernel<decltype(w)::value>, dim3(nblocks), dim3(256), 0, s, sp);
+      return hipGetLastError();
+    });
+  });
   if (d_trace) {   // dev: when do the blocks start, finish their probe look-up and end?  (us after the first block's start)
     std::vector<unsigned long long> h((size_t)nblocks * 3);
     if (hipMemcpyAsync(h.data(), d_trace, h.size() * 8, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess) {
@@ -3345,10 +3267,7 @@ int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint6
                   uint32_t k, bool approximate, uint64_t* d_out, uint32_t* d_cnt, vc_query_stats* host_stats, hipStream_t s,
                   std::string* err, const VcMihScanFallback* fb, vc_query_stats* d_stats) {
   const bool stats = host_stats != nullptr || d_stats != nullptr;   // the cost model prices the statistics pass either way
-  if (n != ix->n) {
-    if (err) *err = "index is stale: codes were added after vc_build_index()";
-    return VC_ERR_STATE;
-  }
+  if (n != ix->n) return fail(err, VC_ERR_STATE, "index is stale: codes were added after vc_build_index()");
   int rc = upload_binom(err);
   if (rc) return rc;
   const uint32_t cap = std::max(ix->cap, 4 * k);
@@ -3400,6 +3319,18 @@ int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint6
 
   for (uint32_t q0 = 0; q0 < nq; q0 += tile) {
     const uint32_t qt = std::min(tile, nq - q0);
+    // the queries in[0 .. n_in) answered by the scan now, stop rule replayed; those it cannot settle (ring overflow, too many
+    // ties) are written to `back`, and *n_back says how many
+    auto scan_handoff = [&](const uint32_t* in, uint32_t n_in, uint32_t* back, uint32_t* n_back) -> int {
+      VcMihScanTarget tgt{st.ring, cap, st.count, st.radius, st.seen, st.sub, st.loc};
+      MIH_CHECK(hipMemsetAsync(d_ctr, 0, 4, s));
+      const int frc = fb->fn(fb->ctx, d_q + (size_t)q0 * ix->W, in, n_in, k, stop_mult, tgt, stats, back, d_ctr, s);
+      if (frc) return fail(err, frc, "scan fallback of the exact k-NN loop failed");
+      MIH_CHECK(hipMemcpyAsync(h_ctr, d_ctr, 4, hipMemcpyDeviceToHost, s));
+      MIH_CHECK(hipStreamSynchronize(s));
+      *n_back = h_ctr[0];
+      return VC_OK;
+    };
     uint32_t *cur = lists[0], *nxt = lists[1], *redo = lists[2];
     uint32_t n_cur = qt, r_start = 0, n_heavy = qt;
     if (inblock) {
@@ -3459,18 +3390,11 @@ int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint6
           MIH_CHECK(hipStreamSynchronize(s));
           const uint32_t n_scan = h_ctr[0], n_keep = h_ctr[1];
           if (n_scan) {
-            VcMihScanTarget tgt{st.ring, cap, st.count, st.radius, st.seen, st.sub, st.loc};
-            MIH_CHECK(hipMemsetAsync(d_ctr, 0, 4, s));
             // unresolved queries (ring overflow, too many ties) rejoin the radius loop: appended behind the kept ones
-            rc = fb->fn(fb->ctx, d_q + (size_t)q0 * ix->W, nxt, n_scan, k, stop_mult, tgt, stats, redo + n_keep, d_ctr, s);
-            if (rc) {
-              if (err) *err = "scan fallback of the exact k-NN loop failed";
-              return rc;
-            }
-            MIH_CHECK(hipMemcpyAsync(h_ctr, d_ctr, 4, hipMemcpyDeviceToHost, s));
-            MIH_CHECK(hipStreamSynchronize(s));
-            if (trace) fprintf(stderr, "[vc_mih] cost model: %u of %u unfinished queries answered by the verify kernel, %u came back\n", n_scan, n_heavy, h_ctr[0]);
-            n_cur = n_keep + h_ctr[0];
+            uint32_t n_back = 0;
+            if ((rc = scan_handoff(nxt, n_scan, redo + n_keep, &n_back))) return rc;
+            if (trace) fprintf(stderr, "[vc_mih] cost model: %u of %u unfinished queries answered by the verify kernel, %u came back\n", n_scan, n_heavy, n_back);
+            n_cur = n_keep + n_back;
             std::swap(cur, redo);          // the radius loop goes on with the kept (+ unresolved) queries
           }
         }
@@ -3489,17 +3413,10 @@ int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint6
         const double est_mih = (double)n_cur * ix->m * binom_host(S, r) / 4e10 + 40e-6;
         const double est_scan = scan_cost_s(n, ix->W, n_cur) * (stats ? 2.5 : 1.0);
         if (est_mih > est_scan || ix->knobs.mih_switch == 2) {
-          VcMihScanTarget tgt{st.ring, cap, st.count, st.radius, st.seen, st.sub, st.loc};
-          MIH_CHECK(hipMemsetAsync(d_ctr, 0, 8, s));
-          rc = fb->fn(fb->ctx, d_q + (size_t)q0 * ix->W, cur, n_cur, k, stop_mult, tgt, stats, nxt, d_ctr, s);
-          if (rc) {
-            if (err) *err = "scan fallback of the exact k-NN loop failed";
-            return rc;
-          }
-          MIH_CHECK(hipMemcpyAsync(h_ctr, d_ctr, 4, hipMemcpyDeviceToHost, s));
-          MIH_CHECK(hipStreamSynchronize(s));
-          if (trace) fprintf(stderr, "[vc_mih] shell r=%u: %u queries answered by the verify kernel (cost model), %u continue\n", r, n_cur - h_ctr[0], h_ctr[0]);
-          n_cur = h_ctr[0];
+          uint32_t n_back = 0;
+          if ((rc = scan_handoff(cur, n_cur, nxt, &n_back))) return rc;
+          if (trace) fprintf(stderr, "[vc_mih] shell r=%u: %u queries answered by the verify kernel (cost model), %u continue\n", r, n_cur - n_back, n_back);
+          n_cur = n_back;
           std::swap(cur, nxt);
           switched = true;
           if (n_cur == 0) break;
@@ -3529,10 +3446,7 @@ int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint6
         MIH_CHECK(hipStreamSynchronize(s));
         if (h_ctr[1] == 0) break;
         // overflowed queries go round again with their tightened limit; swap the redo list with a scratch list
-        if (round > 64) {
-          if (err) *err = "MIH overflow recovery did not converge";
-          return VC_ERR_CAPACITY;
-        }
+        if (round > 64) return fail(err, VC_ERR_CAPACITY, "MIH overflow recovery did not converge");
         // `cur` has been fully consumed by this round: reuse it as the work list of the recovery round so the
         // commit kernel can refill `redo`
         n_work = h_ctr[1];
@@ -3579,6 +3493,25 @@ int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint6
 }
 
 // ---- fixed-radius neighbour search (BASELINE config 2) ----------------------------------------------------
+// pigeonhole (search_R_neighbors shells, search_worker.cc:222-227) with multi-index hashing's sharper radii:
+// R = m q + a  =>  tables 0..a search substring radius q (n_big of them), the others q - 1 (small_shells shells)
+struct RadiusPlan {
+  uint32_t m, rq, ra, rsub, n_big, small_shells;
+  uint64_t probes;   // bucket probes per query over the shells 0..rsub
+  uint32_t tables_at(uint32_t r) const { return r < small_shells ? m : n_big; }
+};
+static RadiusPlan radius_plan(const VcMihIndex* ix, uint32_t radius) {   // radius <= W * 64
+  RadiusPlan p{};
+  p.m = ix->m;
+  p.rq = radius / ix->m;
+  p.ra = radius % ix->m;
+  p.rsub = std::min(ix->sbits, p.rq);
+  p.n_big = std::min(ix->m, p.ra + 1);
+  p.small_shells = p.rq ? std::min(ix->sbits, p.rq - 1) + 1 : 0;
+  for (uint32_t r = 0; r <= p.rsub; ++r) p.probes += (uint64_t)p.tables_at(r) * binom_host(ix->sbits, r);
+  return p;
+}
+
 void vc_radius_work_free(VcRadiusWork* w) {
   if (!w) return;
   (void)hipFree(w->d_ring); (void)hipFree(w->d_compact); (void)hipFree(w->d_aux); (void)hipFree(w->d_offs);
@@ -3598,51 +3531,32 @@ static int radius_search_device(VcMihIndex* ix, bool use_mih, const uint64_t* d_
   if (use_mih && (rc = upload_binom(err))) return rc;
   const uint32_t bits = W * 64;
   if (radius > bits) radius = bits;
-  // pigeonhole (search_R_neighbors shells, search_worker.cc:222-227) with multi-index hashing's sharper radii:
-  // R = m q + a  =>  tables 0..a search substring radius q (n_big of them), the others q - 1 (small_shells shells)
-  const uint32_t rq = use_mih ? radius / ix->m : 0, ra = use_mih ? radius % ix->m : 0;
-  const uint32_t rsub = use_mih ? std::min(ix->sbits, rq) : 0;
-  const uint32_t n_big = use_mih ? std::min(ix->m, ra + 1) : 0;
-  const uint32_t small_shells = (use_mih && rq) ? std::min(ix->sbits, rq - 1) + 1 : 0;
-  auto tables_at = [&](uint32_t r) { return r < small_shells ? ix->m : n_big; };
+  const RadiusPlan rp = use_mih ? radius_plan(ix, radius) : RadiusPlan{};
   bool inblock = false;
   if (use_mih && ix->knobs.mih_host_loop == 0) {
-    uint64_t probes = 0;
-    for (uint32_t r = 0; r <= rsub; ++r) probes += (uint64_t)tables_at(r) * binom_host(ix->sbits, r);
     const double avg_bucket = (double)ix->n / (ix->sbits >= 32 ? 4294967296.0 : (double)(1ull << ix->sbits));
-    inblock = probes <= MQ_RADIUS_BUDGET && rsub <= 16 && (double)probes * avg_bucket <= MQ_ENTRY_BUDGET;
+    inblock = rp.probes <= MQ_RADIUS_BUDGET && rp.rsub <= 16 && (double)rp.probes * avg_bucket <= MQ_ENTRY_BUDGET;
     if (ix->knobs.mih_stream == 2 && ix->sbits <= 16) inblock = false;   // tests: small databases through the streaming kernel too
   }
   // <= 16-bit substrings whose shells exceed the query kernel's entry budget: stream the buckets (mih_bucket_stream_kernel)
-  uint32_t stream_probes = 0;
   bool stream = false;
   if (use_mih && !inblock && ix->knobs.mih_host_loop == 0 && ix->knobs.mih_stream != 0 && ix->sbits <= 16) {
-    for (uint32_t r = 0; r <= rsub; ++r) stream_probes += tables_at(r) * binom_host(ix->sbits, r);
-    stream = stream_probes <= MS_MAXP;
+    stream = rp.probes <= MS_MAXP;
     for (const VcTableView& tv : ix->h_tables) stream = stream && tv.bcodes != nullptr;
   }
   const uint32_t TQ = use_mih ? MIH_RADIUS_TILE : 64u;
   uint32_t cap = std::max(wk->cap, use_mih ? std::max(ix->cap, 4096u) : 65536u);
   while (cap & (cap - 1)) cap += cap & (0u - cap);   // power of two: the in-place segment sort pads to one
-#define R_CHECK(call)                                                      \
-  do {                                                                     \
-    hipError_t _r = (call);                                                \
-    if (_r != hipSuccess) {                                                \
-      if (err) *err = std::string(#call) + ": " + hipGetErrorString(_r);   \
-      return _r == hipErrorOutOfMemory ? VC_ERR_NOMEM : VC_ERR_HIP;        \
-    }                                                                      \
-  } while (0)
-
   const uint32_t hs = (bits + 1 + 7) & ~7u;
   const size_t aux_words = (size_t)TQ * (3 + hs) + 8;   // count[TQ] | tau[TQ] | sorted[TQ] | hist[TQ*hs] | tot (2 x u64)
   if (wk->aux_words < aux_words) {
     (void)hipFree(wk->d_aux);
     wk->d_aux = nullptr;
-    R_CHECK(hipMalloc((void**)&wk->d_aux, aux_words * 4));
+    MIH_CHECK(hipMalloc((void**)&wk->d_aux, aux_words * 4));
     wk->aux_words = aux_words;
   }
   if (!wk->h_tot) {
-    R_CHECK(hipHostMalloc((void**)&wk->h_tot, 32, hipHostMallocMapped));
+    MIH_CHECK(hipHostMalloc((void**)&wk->h_tot, 32, hipHostMallocMapped));
     wk->h_tot[2] = 0;
     if (hipHostGetDevicePointer((void**)&wk->h_tot_dev, wk->h_tot, 0) != hipSuccess) { (void)hipGetLastError(); wk->h_tot_dev = nullptr; }
   }
@@ -3658,10 +3572,10 @@ static int radius_search_device(VcMihIndex* ix, bool use_mih, const uint64_t* d_
     if (wk->cap != cap || !wk->d_ring) {
       (void)hipFree(wk->d_ring);
       wk->d_ring = nullptr;
-      R_CHECK(hipMalloc((void**)&wk->d_ring, (size_t)TQ * cap * 8));
+      MIH_CHECK(hipMalloc((void**)&wk->d_ring, (size_t)TQ * cap * 8));
       wk->cap = cap;
     }
-    if (nq == 0) R_CHECK(hipMemsetAsync(d_tot, 0, 16, s));   // (else the first tile's offsets kernel starts the totals over)
+    if (nq == 0) MIH_CHECK(hipMemsetAsync(d_tot, 0, 16, s));   // (else the first tile's offsets kernel starts the totals over)
     for (uint32_t q0 = 0; q0 < nq; q0 += TQ) {
       const uint32_t qt = std::min(TQ, nq - q0);
       const uint32_t* sorted_flag = nullptr;
@@ -3675,41 +3589,41 @@ static int radius_search_device(VcMihIndex* ix, bool use_mih, const uint64_t* d_
           QueryKernelParams qp{};
           qp.cols = d_cols; qp.stride = stride; qp.n = ix->n; qp.tables = ix->d_tables; qp.queries = d_q + (size_t)q0 * W;
           qp.st = st; qp.m = ix->m; qp.sbits = ix->sbits; qp.id_base = id_base; qp.flags = ix->flags; qp.cap = cap; qp.k = 0;
-          qp.mode = MQ_MODE_RADIUS; qp.radius = radius; qp.r_last = rsub; qp.n_big = n_big; qp.small_shells = small_shells;
+          qp.mode = MQ_MODE_RADIUS; qp.radius = radius; qp.r_last = rp.rsub; qp.n_big = rp.n_big; qp.small_shells = rp.small_shells;
           qp.buf_entries = 2048;
-          R_CHECK(timed_query_launch(ix, qp, W, qt, s));
+          MIH_CHECK(timed_query_launch(ix, qp, W, qt, s));
           sorted_flag = d_sorted;
           work = st.work;
         } else if (stream) {
           uint32_t* list = ix->d_lists;
           hipLaunchKernelGGL(mih_init_kernel, dim3((qt + 255) / 256), dim3(256), 0, s, st, qt, list, vc_pack(radius + 1, 0));
-          R_CHECK(hipGetLastError());
+          MIH_CHECK(hipGetLastError());
           StreamParams sp{};
           sp.queries = d_q + (size_t)q0 * W; sp.tables = ix->d_tables; sp.ring = wk->d_ring; sp.count = d_count; sp.n = ix->n;
           sp.m = ix->m; sp.sbits = ix->sbits; sp.id_base = id_base; sp.flags = ix->flags; sp.cap = cap; sp.radius = radius;
-          sp.rsub = rsub; sp.n_big = n_big; sp.small_shells = small_shells; sp.nprobes = stream_probes;
+          sp.rsub = rp.rsub; sp.n_big = rp.n_big; sp.small_shells = rp.small_shells; sp.nprobes = (uint32_t)rp.probes;
           // enough blocks to fill the chip when the batch is small: a query's probe list is dealt out to `split` blocks
           // (r04: 8 x n_cu blocks were 2048 for a tile of 1024 queries, 1.6 residency waves of 1280 -- the last fifth of the launch
           // ran on 768 blocks and fewer; one wave of blocks that are all resident ends 1.3 % earlier, more and smaller blocks pay
           // for their look-ups: 0.396 / 0.391 / 0.406 ms at 8 / 4 / 16 blocks per CU, profiles/r04_stream_trace.txt)
-          sp.split = std::max(1u, std::min(std::min(stream_probes, 64u), stream_resident_blocks(W, n_cu) / qt));
-          R_CHECK(timed_stream_launch(ix, sp, W, qt, s));
+          sp.split = std::max(1u, std::min(std::min(sp.nprobes, 64u), stream_resident_blocks(W, n_cu) / qt));
+          MIH_CHECK(timed_stream_launch(ix, sp, W, qt, s));
         } else {
           uint32_t* list = ix->d_lists;
           hipLaunchKernelGGL(mih_init_kernel, dim3((qt + 255) / 256), dim3(256), 0, s, st, qt, list, vc_pack(radius + 1, 0));
-          R_CHECK(hipGetLastError());
-          for (uint32_t r = 0; r <= rsub; ++r) {
+          MIH_CHECK(hipGetLastError());
+          for (uint32_t r = 0; r <= rp.rsub; ++r) {
             ProbeParams p{};
             p.cols = d_cols; p.stride = stride; p.tables = ix->d_tables; p.queries = d_q + (size_t)q0 * W; p.list = list;
             p.st = st; p.r = r; p.nkeys = binom_host(ix->sbits, r); p.m = ix->m; p.sbits = ix->sbits; p.id_base = id_base;
-            p.flags = ix->flags; p.cap = cap; p.count_seen = 1; p.n = ix->n; p.m_probe = tables_at(r);
-            R_CHECK(launch_probe(p, W, qt, s));
+            p.flags = ix->flags; p.cap = cap; p.count_seen = 1; p.n = ix->n; p.m_probe = rp.tables_at(r);
+            MIH_CHECK(launch_probe(p, W, qt, s));
           }
         }
       } else {
-        R_CHECK(hipMemsetAsync(wk->d_aux, 0, (size_t)TQ * (3 + hs) * 4, s));
+        MIH_CHECK(hipMemsetAsync(wk->d_aux, 0, (size_t)TQ * (3 + hs) * 4, s));
         hipLaunchKernelGGL(vc_fill_u32_kernel, dim3((qt + 255) / 256), dim3(256), 0, s, d_tau, qt, radius);
-        R_CHECK(hipGetLastError());
+        MIH_CHECK(hipGetLastError());
         size_t lds;
         const VcScanShape sh = vc_scan_pick_shape(W, qt, &lds, knobs);
         VcScanParams p{};
@@ -3717,17 +3631,17 @@ static int radius_search_device(VcMihIndex* ix, bool use_mih, const uint64_t* d_
         p.id_base = id_base; p.qt = qt; p.k = 0xFFFFFFFFu;   // never re-derive tau: it is the fixed radius
         p.cap = cap; p.hist_stride = hs; p.queries = d_q + (size_t)q0 * W; p.tau = d_tau; p.count = d_count; p.qs = 1;
         p.hist = d_hist; p.buf = wk->d_ring;
-        R_CHECK(vc_launch_scan(p, W, n_cu, 0, knobs, s));
+        MIH_CHECK(vc_launch_scan(p, W, n_cu, 0, knobs, s));
       }
       // place the tile's segments behind the previous tiles' (+ the call's totals, + the query kernel's work counters), then
       // order what did not arrive sorted (hand-written bitonic network; the query kernel's small segments do) and copy out
       const unsigned long long seq = (poll && q0 + TQ >= nq) ? ++wk->seq : 0ull;
       hipLaunchKernelGGL(vc_radius_offsets_kernel, dim3(work ? 2 : 1), dim3(1024), 0, s, d_count, qt, d_offsets + q0, d_tot, q0 == 0 ? 1u : 0u,
                          (volatile unsigned long long*)wk->h_tot_dev, seq, work, work ? ix->d_totals : (unsigned long long*)nullptr);
-      R_CHECK(hipGetLastError());
+      MIH_CHECK(hipGetLastError());
       hipLaunchKernelGGL(vc_sort_compact_segments_kernel, dim3(qt), dim3(1024), 0, s, wk->d_ring, cap, d_count, sorted_flag,
                          d_offsets + q0, d_out, out_cap);
-      R_CHECK(hipGetLastError());
+      MIH_CHECK(hipGetLastError());
     }
     // total + largest segment: the last offsets kernel wrote them to mapped host memory; the host polls the sequence word and
     // returns while the last copy-out kernel may still run (results are in stream order; host readers copy behind it)
@@ -3736,25 +3650,19 @@ static int radius_search_device(VcMihIndex* ix, bool use_mih, const uint64_t* d_
       landed = poll_mapped_word((volatile unsigned long long*)(wk->h_tot + 2), (unsigned long long)wk->seq);
     }
     if (!landed) {
-      R_CHECK(hipMemcpyAsync(wk->h_tot, d_tot, 16, hipMemcpyDeviceToHost, s));
-      R_CHECK(hipStreamSynchronize(s));
+      MIH_CHECK(hipMemcpyAsync(wk->h_tot, d_tot, 16, hipMemcpyDeviceToHost, s));
+      MIH_CHECK(hipStreamSynchronize(s));
     }
     const uint64_t mx = wk->h_tot[1];
     *total = wk->h_tot[0];
     if (mx <= cap) break;
     uint64_t want = cap;
     while (want < mx) want <<= 1;
-    if (attempt > 8 || want * TQ * 8 > (64ull << 30)) {
-      if (err) *err = "radius search: a query has more neighbours than the work ring can hold";
-      return VC_ERR_CAPACITY;
-    }
+    if (attempt > 8 || want * TQ * 8 > (64ull << 30))
+      return fail(err, VC_ERR_CAPACITY, "radius search: a query has more neighbours than the work ring can hold");
     cap = (uint32_t)want;
   }
-#undef R_CHECK
-  if (*total > out_cap) {
-    if (err) *err = "radius search: output buffer too small (needed counts are in out_offsets)";
-    return VC_ERR_CAPACITY;
-  }
+  if (*total > out_cap) return fail(err, VC_ERR_CAPACITY, "radius search: output buffer too small (needed counts are in out_offsets)");
   return VC_OK;
 }
 
@@ -3762,19 +3670,11 @@ int vc_radius_search(VcMihIndex* ix, bool use_mih, const uint64_t* d_cols, uint6
                      uint32_t id_base, uint32_t n_cu, const VcKnobs* knobs, const uint64_t* d_q, uint32_t nq, uint32_t radius,
                      uint64_t* out, uint64_t out_cap, uint64_t* out_offsets, bool device_out, VcRadiusWork* wk, hipStream_t s,
                      std::string* err) {
-  if (use_mih && n != ix->n) {
-    if (err) *err = "index is stale: codes were added after vc_build_index()";
-    return VC_ERR_STATE;
-  }
+  if (use_mih && n != ix->n) return fail(err, VC_ERR_STATE, "index is stale: codes were added after vc_build_index()");
   if (use_mih) {
     // a radius whose substring shells cost more probes than scanning the shard costs distance evaluations is answered
     // by the scan (identical results; search_R_neighbors would enumerate up to 2^s keys per table, search_worker.cc:222-264)
-    const uint32_t rr = std::min(radius, W * 64), rq = rr / ix->m, ra = rr % ix->m;   // radii q (tables 0..a) and q - 1, as below
-    const uint32_t rsub = std::min(ix->sbits, rq), n_big = std::min(ix->m, ra + 1);
-    const uint32_t small_shells = rq ? std::min(ix->sbits, rq - 1) + 1 : 0;
-    double probes = 0;
-    for (uint32_t r = 0; r <= rsub; ++r) probes += (double)(r < small_shells ? ix->m : n_big) * binom_host(ix->sbits, r);
-    if (probes > (double)std::max<uint64_t>(n, 1u << 20)) use_mih = false;
+    if (radius_plan(ix, std::min(radius, W * 64)).probes > std::max<uint64_t>(n, 1u << 20)) use_mih = false;
   }
   const uint32_t TQ = use_mih ? MIH_RADIUS_TILE : 64u;
   if (wk->tq != TQ) {   // tile shape changed (scan <-> MIH): start over with fresh buffers
@@ -3790,42 +3690,30 @@ int vc_radius_search(VcMihIndex* ix, bool use_mih, const uint64_t* d_cols, uint6
   if (wk->offs_cap < (size_t)nq + 1) {
     (void)hipFree(wk->d_offs);
     wk->d_offs = nullptr;
-    if (hipMalloc((void**)&wk->d_offs, ((size_t)nq + 1) * 8) != hipSuccess) {
-      if (err) *err = "radius search: offsets allocation failed";
-      return VC_ERR_NOMEM;
-    }
+    if (hipMalloc((void**)&wk->d_offs, ((size_t)nq + 1) * 8) != hipSuccess)
+      return fail(err, VC_ERR_NOMEM, "radius search: offsets allocation failed");
     wk->offs_cap = (size_t)nq + 1;
   }
   uint64_t total = 0;
   for (int pass = 0; pass < 2; ++pass) {
     if (!wk->d_compact) {
       if (wk->compact_cap == 0) wk->compact_cap = std::max<uint64_t>(out_cap, 1u << 16);
-      if (hipMalloc((void**)&wk->d_compact, wk->compact_cap * 8) != hipSuccess) {
-        if (err) *err = "radius search: staging allocation failed";
-        return VC_ERR_NOMEM;
-      }
+      if (hipMalloc((void**)&wk->d_compact, wk->compact_cap * 8) != hipSuccess)
+        return fail(err, VC_ERR_NOMEM, "radius search: staging allocation failed");
     }
     std::string e2;
     int rc = radius_search_device(ix, use_mih, d_cols, stride, n, W, id_base, n_cu, knobs, d_q, nq, radius, wk->d_compact, wk->compact_cap,
                                   wk->d_offs, &total, wk, s, &e2);
     if (rc == VC_OK) break;
-    if (rc != VC_ERR_CAPACITY || total <= wk->compact_cap || pass == 1) {
-      if (err) *err = e2;
-      return rc;
-    }
+    if (rc != VC_ERR_CAPACITY || total <= wk->compact_cap || pass == 1) return fail(err, rc, e2);
     (void)hipFree(wk->d_compact);   // the staging buffer was too small: now the needed size is known
     wk->d_compact = nullptr;
     wk->compact_cap = total * 2;
   }
   if (hipMemcpyAsync(out_offsets, wk->d_offs, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
       (total <= out_cap && total && hipMemcpyAsync(out, wk->d_compact, total * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-      hipStreamSynchronize(s) != hipSuccess) {
-    if (err) *err = "radius search: copy back failed";
-    return VC_ERR_HIP;
-  }
-  if (total > out_cap) {
-    if (err) *err = "radius search: output buffer too small (needed counts are in out_offsets)";
-    return VC_ERR_CAPACITY;
-  }
+      hipStreamSynchronize(s) != hipSuccess)
+    return fail(err, VC_ERR_HIP, "radius search: copy back failed");
+  if (total > out_cap) return fail(err, VC_ERR_CAPACITY, "radius search: output buffer too small (needed counts are in out_offsets)");
   return VC_OK;
 }
