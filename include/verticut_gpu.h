@@ -60,6 +60,12 @@ extern "C" {
 #define VC_FLAG_LEAN_TIMING 0x8u       /* time only the verify-kernel launches (vc_timing.scan_*): no event pair around each
                                           search call, so vc_timing.total_ms / calls stay 0.  Each event record is a barrier
                                           packet in the stream (~4 us); a throughput loop that keeps its own clock sets this. */
+#define VC_FLAG_GLOBAL_STOP 0x10u      /* sharded store (vc_sharded_config.engine.flags), VC_MODE_MIH_EXACT: the stop rule is decided on
+                                          the MERGED rows, as the reference's master does (search_worker.cc:179-207), so rows, counts
+                                          and statistics are those of one vc_engine holding the union.  A plain vc_engine ignores it
+                                          (its stop is global already); other modes are unchanged.  Refused (VC_ERR_INVALID) with
+                                          n_tables == 0, VC_FLAG_USE_BITMAP, VC_FLAG_REF_SIGNEXT_KEYS, or VC_FLAG_REF_STOP_LITERAL4
+                                          with n_tables < 4. */
 
 /* ---- synthetic data kinds for vc_add_synthetic (the reference ships no data: .gitignore:7-8) */
 #define VC_SYNTH_UNIFORM 0
@@ -254,7 +260,11 @@ int vc_merge_topk_dev(const uint64_t* d_lists, uint32_t n_lists, uint32_t nq, ui
  *   VC_EXCHANGE_AUTO       RCCL when there is one shard per device, more than one device and librccl loads; else peer copy
  * LINEAR results are exactly those of one engine holding everything (the top-k of a union is the top-k of the parts'
  * top-k).  MIH modes: every shard runs to its OWN stop rule, which is exact for the shard, so exact-mode distances
- * equal the single-engine result; statistics report the widest radius and the summed reads / candidates. */
+ * equal the single-engine result; statistics report the widest radius and the summed reads / candidates.  With
+ * VC_FLAG_GLOBAL_STOP in engine.flags, VC_MODE_MIH_EXACT instead stops where ONE engine over the union stops: the shards run
+ * in capped rounds (shells 0..t, own stop rule active), a kernel on the root judges the merged rows (pigeonhole check +
+ * the union's stop rule) and only undecided queries run again; queries beyond the shards' in-block shells are answered by
+ * a scan of the union with the stop rule replayed.  Rows, counts and all statistics then equal one vc_engine's. */
 #define VC_MAX_SHARDS 16
 #define VC_EXCHANGE_AUTO 0
 #define VC_EXCHANGE_PEER_COPY 1

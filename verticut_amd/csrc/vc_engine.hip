@@ -915,6 +915,37 @@ __global__ void vc_linear_stats_kernel(const uint32_t* __restrict__ cnt, uint32_
   out[i] = o;
 }
 
+int vc_engine_view(vc_engine* e, VcEngineView* v) {
+  if (!e || !v) return VC_ERR_INVALID;
+  v->cols = e->d_cols;
+  v->stride = e->stride;
+  v->n = e->n;
+  v->W = e->W;
+  v->m = e->m;
+  v->sbits = e->sbits;
+  v->id_base = e->cfg.id_base;
+  v->n_cu = e->n_cu;
+  v->reach =e->mih ? vc_mih_knn_reach(e->mih) : 0;
+  return VC_OK;
+}
+
+int vc_engine_knn_capped(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t r_cap, uint64_t* d_out, uint32_t* d_counts,
+                         vc_query_stats* d_stats, hipStream_t s) {
+  int rc = check_knn_args(e, d_queries, nq, k, VC_MODE_MIH_EXACT);
+  if (rc) return rc;
+  if (!d_out || !d_counts) return VC_ERR_INVALID;
+  if ((rc = bind_device(e))) return rc;
+  hipStream_t saved = e->stream;
+  e->stream = s;
+  timing_begin(e);
+  const VcMihScanFallback fb{mih_scan_fallback, e, e->n_cu};
+  rc = vc_mih_search(e->mih, e->d_cols, e->stride, e->n, (const uint64_t*)d_queries, nq, k, false, d_out, d_counts, nullptr, e->stream,
+                     &e->err, &fb, d_stats, r_cap);
+  timing_end(e);
+  e->stream = saved;
+  return rc;
+}
+
 extern "C" {
 
 int vc_search_knn_dev_stats(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out,

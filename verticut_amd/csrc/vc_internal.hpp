@@ -104,6 +104,16 @@ hipError_t vc_radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], uint64_t n,
 // n_lists x [nq][k] sorted lists -> merged top-k
 hipError_t vc_launch_select_lists(const uint64_t* d_lists, uint32_t n_lists, uint32_t nq, uint32_t k, uint64_t* d_out,
                                   uint32_t* d_out_count, hipStream_t s);
+// ---- vc_engine.hip: what the sharded store's global stop (vc_sharded.hip) needs of a shard's engine
+struct VcEngineView {
+  const uint64_t* cols;   // column-major codes, word j of record i at cols[j * stride + i]
+  uint64_t stride, n;
+  uint32_t W, m, sbits, id_base, n_cu, reach;   // reach: vc_mih_knn_reach of the index (0 without one)
+};
+int vc_engine_view(vc_engine* e, VcEngineView* v);
+// exact MIH k-NN capped at shell r_cap (vc_mih_search's r_cap) on stream s; d_stats as vc_search_knn_dev_stats
+int vc_engine_knn_capped(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t r_cap, uint64_t* d_out, uint32_t* d_counts,
+                         vc_query_stats* d_stats, hipStream_t s);
 // the same over the gathered shard slots of vc_sharded_* (rows + counts per slot; a flagged shard row flags the merged row)
 hipError_t vc_launch_select_slots(const uint64_t* d_base, uint64_t slot_words, uint32_t cnt_off_words, uint32_t n_lists, uint32_t nq,
                                   uint32_t k, uint64_t* d_out, uint32_t* d_out_count, hipStream_t s);

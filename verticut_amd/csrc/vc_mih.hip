@@ -2395,6 +2395,94 @@ hipError_t vc_launch_minsub_count(const uint64_t* cols, uint64_t stride, uint64_
   });
 }
 
+// The union scan of the sharded global stop (vc_sharded.hip), tie at the threshold: per query, this shard's items at full
+// distance dist[q] whose minimum substring distance is <= radius[q], smallest ids first, at most need[q] of them.  Two passes:
+// the shard in VC_TIE_CHUNKS id ranges counted by the whole grid, then one block per query walks, in id order, only the
+// ranges that hold such items (a block-wide ordered compaction keeps the ids in that order).
+__device__ __forceinline__ bool mih_tie_hit(const uint64_t* __restrict__ cols, uint64_t stride, uint64_t i, uint32_t W, uint32_t m,
+                                            uint32_t sbits, const uint64_t* qw, uint32_t D, uint32_t rad) {
+  uint32_t d = 0;
+  for (uint32_t j = 0; j < W; ++j) d += (uint32_t)__popcll(cols[(uint64_t)j * stride + i] ^ qw[j]);
+  if (d != D) return false;
+  const uint32_t smask = sbits == 32 ? 0xFFFFFFFFu : ((1u << sbits) - 1u);
+  uint32_t ms = 0xFFFFFFFFu;
+  for (uint32_t t = 0; t < m; ++t) {
+    const uint32_t bp = t * sbits;
+    ms = min(ms, (uint32_t)__popc((uint32_t)((cols[(uint64_t)(bp >> 6) * stride + i] ^ qw[bp >> 6]) >> (bp & 63)) & smask));
+  }
+  return ms <= rad;
+}
+
+__global__ void __launch_bounds__(256) mih_tie_count_kernel(const uint64_t* __restrict__ cols, uint64_t stride, uint64_t n, uint32_t W,
+                                                            uint32_t m, uint32_t sbits, const uint64_t* __restrict__ queries,
+                                                            const uint32_t* __restrict__ dist, const uint32_t* __restrict__ radius,
+                                                            const uint32_t* __restrict__ need, uint32_t* __restrict__ chunk_cnt) {
+  __shared__ uint32_t s_cnt;
+  const uint32_t c = blockIdx.x, q = blockIdx.y;
+  if (need[q] == 0) return;
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  uint64_t qw[VC_MAX_W];
+  for (uint32_t j = 0; j < VC_MAX_W; ++j) qw[j] = j < W ? queries[(uint64_t)q * W + j] : 0;
+  const uint64_t len = (n + VC_TIE_CHUNKS - 1) / VC_TIE_CHUNKS, lo = (uint64_t)c * len, hi = min(n, lo + len);
+  uint32_t mine = 0;
+  for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) mine += mih_tie_hit(cols, stride, i, W, m, sbits, qw, dist[q], radius[q]);
+  if (mine) atomicAdd(&s_cnt, mine);
+  __syncthreads();
+  if (threadIdx.x == 0) chunk_cnt[(uint64_t)q * VC_TIE_CHUNKS + c] = s_cnt;
+}
+
+__global__ void __launch_bounds__(256) mih_tie_collect_kernel(const uint64_t* __restrict__ cols, uint64_t stride, uint64_t n, uint32_t W,
+                                                              uint32_t m, uint32_t sbits, uint32_t id_base,
+                                                              const uint64_t* __restrict__ queries, uint32_t k,
+                                                              const uint32_t* __restrict__ dist, const uint32_t* __restrict__ radius,
+                                                              const uint32_t* __restrict__ need, const uint32_t* __restrict__ chunk_cnt,
+                                                              uint32_t* __restrict__ ids, uint32_t* __restrict__ cnt) {
+  __shared__ uint32_t s_wave[256 / VC_WAVE];
+  const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid % VC_WAVE, wave = tid / VC_WAVE;
+  const uint32_t want = min(need[q], k);
+  uint64_t qw[VC_MAX_W];
+  for (uint32_t j = 0; j < VC_MAX_W; ++j) qw[j] = j < W ? queries[(uint64_t)q * W + j] : 0;
+  const uint64_t len = (n + VC_TIE_CHUNKS - 1) / VC_TIE_CHUNKS;
+  uint32_t got = 0;   // block-uniform
+  for (uint32_t c = 0; c < VC_TIE_CHUNKS && got < want; ++c) {
+    if (chunk_cnt[(uint64_t)q * VC_TIE_CHUNKS + c] == 0) continue;
+    const uint64_t hi = min(n, (uint64_t)(c + 1) * len);
+    for (uint64_t base = (uint64_t)c * len; base < hi && got < want; base += blockDim.x) {
+      const uint64_t i = base + tid;
+      const bool hit = i < hi && mih_tie_hit(cols, stride, i, W, m, sbits, qw, dist[q], radius[q]);
+      const uint64_t b = __ballot(hit);
+      if (lane == 0) s_wave[wave] = (uint32_t)__popcll(b);
+      __syncthreads();
+      uint32_t before = 0, total = 0;
+      for (uint32_t w = 0; w < blockDim.x / VC_WAVE; ++w) {
+        before += w < wave ? s_wave[w] : 0u;
+        total += s_wave[w];
+      }
+      if (hit) {
+        const uint32_t pos = got + before + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+        if (pos < want) ids[(uint64_t)q * k + pos] = id_base + (uint32_t)i;
+      }
+      got += total;
+      __syncthreads();
+    }
+  }
+  if (tid == 0) cnt[q] = min(got, want);
+}
+
+hipError_t vc_launch_tie_collect(const uint64_t* cols, uint64_t stride, uint64_t n, uint32_t W, uint32_t m, uint32_t sbits, uint32_t id_base,
+                                 const uint64_t* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_dist, const uint32_t* d_radius,
+                                 const uint32_t* d_need, uint32_t* d_chunk_scratch, uint32_t* d_ids, uint32_t* d_cnt, hipStream_t s) {
+  if (nq == 0) return hipSuccess;
+  hipLaunchKernelGGL(mih_tie_count_kernel, dim3(VC_TIE_CHUNKS, nq), dim3(256), 0, s, cols, stride, n, W, m, sbits, d_queries, d_dist,
+                     d_radius, d_need, d_chunk_scratch);
+  hipError_t r = hipGetLastError();
+  if (r != hipSuccess) return r;
+  hipLaunchKernelGGL(mih_tie_collect_kernel, dim3(nq), dim3(256), 0, s, cols, stride, n, W, m, sbits, id_base, d_queries, k, d_dist,
+                     d_radius, d_need, (const uint32_t*)d_chunk_scratch, d_ids, d_cnt);
+  return hipGetLastError();
+}
+
 // Host wait for a word a kernel publishes to mapped host memory (sequence number last).  The first ~30 us spin hot --
 // that is where the win over hipStreamSynchronize lies (~10 us per call) --, after that every probe is followed by a
 // pause instruction and, beyond 200 us, a sched_yield: a long launch (uniform queries, 1e9 shells) no longer burns a core,
@@ -3263,9 +3351,21 @@ static double scan_cost_s(uint64_t n, uint32_t W, uint32_t nq) {
   return (double)(nq / 32) * pass(32) + (nq % 32 ? pass(nq % 32) : 0.0);
 }
 
+// capped run: the queries still open after shell r_cap leave the loop there, radius = r_cap
+__global__ void __launch_bounds__(256) mih_set_radius_kernel(uint32_t* __restrict__ radius, const uint32_t* __restrict__ list, uint32_t n,
+                                                             uint32_t r) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) radius[list[i]] = r;
+}
+
+uint32_t vc_mih_knn_reach(const VcMihIndex* ix) {
+  const double avg_bucket = (double)ix->n / (ix->sbits >= 32 ? 4294967296.0 : (double)(1ull << ix->sbits));
+  return inblock_last_shell(ix->sbits, ix->m, ix->knobs.mih_budget ? ix->knobs.mih_budget : MQ_KNN_BUDGET, ix->sbits, avg_bucket);
+}
+
 int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint64_t n, const uint64_t* d_q, uint32_t nq,
                   uint32_t k, bool approximate, uint64_t* d_out, uint32_t* d_cnt, vc_query_stats* host_stats, hipStream_t s,
-                  std::string* err, const VcMihScanFallback* fb, vc_query_stats* d_stats) {
+                  std::string* err, const VcMihScanFallback* fb, vc_query_stats* d_stats, uint32_t r_cap) {
   const bool stats = host_stats != nullptr || d_stats != nullptr;   // the cost model prices the statistics pass either way
   if (n != ix->n) return fail(err, VC_ERR_STATE, "index is stale: codes were added after vc_build_index()");
   int rc = upload_binom(err);
@@ -3304,11 +3404,14 @@ int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint6
   uint64_t knn_budget = MQ_KNN_BUDGET;
   if (nq < 1024) knn_budget = std::max<uint64_t>(2500, MQ_KNN_BUDGET * nq / 1024);
   if (ix->knobs.mih_budget) knn_budget = ix->knobs.mih_budget;   // dev knob VC_MIH_BUDGET
-  const uint32_t r_last = inblock_last_shell(S, ix->m, knn_budget, S, avg_bucket);
+  // capped run (the rounds of the sharded global stop, vc_sharded.hip): shells 0..r_cap with the stop rule active, no switch
+  const bool capped = r_cap < S;
+  const uint32_t r_end = capped ? r_cap : S;
+  const uint32_t r_last = inblock_last_shell(S, ix->m, knn_budget, r_end, avg_bucket);
   const bool trace = ix->knobs.mih_trace;   // VC_MIH_TRACE: per-shell wall times on stderr
   // the scan switch reproduces the radius loop only where that loop is exact and its counters have a closed form
-  const bool switch_ok = !approximate && ix->knobs.mih_switch != 0 && !(ix->flags & (VC_FLAG_USE_BITMAP | VC_FLAG_REF_SIGNEXT_KEYS)) &&
-                         stop_mult == std::min(ix->m, 4u) && n >= 1;
+  const bool switch_ok = !approximate && !capped && ix->knobs.mih_switch != 0 &&
+                         !(ix->flags & (VC_FLAG_USE_BITMAP | VC_FLAG_REF_SIGNEXT_KEYS)) && stop_mult == std::min(ix->m, 4u) && n >= 1;
   // Shells that share the FIRST pass of the query kernel (32-bit substrings): their candidates are tagged by shell and the
   // stop rule is evaluated shell by shell afterwards, so grouping changes no result and no statistic -- it saves a scan /
   // drain round per grouped shell and wastes the probes of the shells behind the one a query stops in.  The depth follows
@@ -3364,7 +3467,7 @@ int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint6
       if (!ix->h_ctr_dev) MIH_CHECK(hipMemcpyAsync(h_ctr + 2, d_ctr + 2, 24, hipMemcpyDeviceToHost, s));
       if (!landed) MIH_CHECK(hipStreamSynchronize(s));
       n_heavy = n_cur = h_ctr[2];
-      if (S == 32 && qt >= 64)       // next launch: group up to shell 2 when most queries of this one needed it
+      if (S == 32 && qt >= 64 && !capped)   // next launch: group up to shell 2 when most queries of this one needed it
         ix->group_hint = (uint64_t)(h_ctr[6] + h_ctr[7]) * 10 >= (uint64_t)qt * 6 ? 3u : 2u;
       r_start = r_last + 1;
       if (trace)
@@ -3376,6 +3479,11 @@ int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint6
         if ((rc = ensure_tile(ix, tile, k, cap, true, &st, err))) return rc;   // the rings exist from the first hand-over on
         hipLaunchKernelGGL(mih_seed_ring_kernel, dim3(n_heavy), dim3(256), 0, s, st, (const uint32_t*)cur, k, cap);
         MIH_CHECK(hipGetLastError());
+        if (capped && r_last == r_end) {   // the kernel ran every shell of the cap: the open queries end here
+          hipLaunchKernelGGL(mih_set_radius_kernel, dim3((n_heavy + 255) / 256), dim3(256), 0, s, st.radius, (const uint32_t*)cur, n_heavy, r_end);
+          MIH_CHECK(hipGetLastError());
+          n_cur = 0;
+        }
         if (fb && fb->fn && switch_ok) {
           // Cost model, per query: the hand-over left an upper bound of the probes each query may still need (its k-th
           // distance so far bounds its last shell).  The multi-block kernels sustain ~4e10 probes/s; the verify kernel's price per
@@ -3404,7 +3512,7 @@ int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint6
       MIH_CHECK(hipGetLastError());
     }
     bool switched = false;
-    for (uint32_t r = r_start; r <= S && n_cur; ++r) {       // search_worker.cc:170: radius <= n_local_bytes_*8
+    for (uint32_t r = r_start; r <= r_end && n_cur; ++r) {   // search_worker.cc:170: radius <= n_local_bytes_*8
       // Cost model: this shell alone is m * C(S, r) bucket probes per active query (the multi-block kernels sustain ~4e10
       // probes/s plus ~40 us of launches and a host round trip per shell); the verify kernel costs scan_cost_s (x 2.5 when the
       // statistics pass is wanted).  Beyond the break-even the remaining queries are
@@ -3429,7 +3537,7 @@ int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint6
       p.flags = ix->flags; p.cap = cap; p.n = ix->n;
       CommitParams c{};
       c.st = st; c.next_list = nxt; c.redo_list = redo; c.ctr = d_ctr; c.k = k; c.cap = cap; c.r = r; c.sbits = S;
-      c.stop_mult = stop_mult; c.approximate = approximate; c.last_shell = r == S;
+      c.stop_mult = stop_mult; c.approximate = approximate; c.last_shell = r == r_end;
       MIH_CHECK(hipMemsetAsync(d_ctr, 0, 8, s));
       const uint32_t* work = cur;
       uint32_t n_work = n_cur;

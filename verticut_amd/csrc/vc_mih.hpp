@@ -65,11 +65,23 @@ hipError_t vc_launch_minsub_count(const uint64_t* cols, uint64_t stride, uint64_
                                   const uint64_t* d_queries, const uint32_t* d_list, const uint32_t* d_flag, uint32_t nq,
                                   const uint32_t* d_radius, unsigned long long* d_seen, uint32_t n_cu, hipStream_t s);
 
+// ids[q][0..cnt[q]) = the items at full distance dist[q] with minimum substring distance <= radius[q], smallest ids first,
+// at most need[q] (<= k) of them (the tie check of the sharded global stop's union scan).  d_chunk_scratch: nq * VC_TIE_CHUNKS words.
+#define VC_TIE_CHUNKS 1024u
+hipError_t vc_launch_tie_collect(const uint64_t* cols, uint64_t stride, uint64_t n, uint32_t W, uint32_t m, uint32_t sbits, uint32_t id_base,
+                                 const uint64_t* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_dist, const uint32_t* d_radius,
+                                 const uint32_t* d_need, uint32_t* d_chunk_scratch, uint32_t* d_ids, uint32_t* d_cnt, hipStream_t s);
+
 // d_q [nq][W]; d_out [nq][k] ascending INF-padded; d_cnt [nq]; stats (host, may be null) filled after a sync.
 // d_stats (device, may be null): the same records written by a kernel in stream order, no host wait for them.
+// r_cap < sbits: exact mode capped at shell r_cap (stop rule active, no scan switch); a query still open there ends with
+// radius = r_cap and the k best of shells 0..r_cap.
 int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint64_t n, const uint64_t* d_q, uint32_t nq,
                   uint32_t k, bool approximate, uint64_t* d_out, uint32_t* d_cnt, vc_query_stats* stats, hipStream_t s,
-                  std::string* err, const VcMihScanFallback* fb = nullptr, vc_query_stats* d_stats = nullptr);
+                  std::string* err, const VcMihScanFallback* fb = nullptr, vc_query_stats* d_stats = nullptr,
+                  uint32_t r_cap = 0xFFFFFFFFu);
+// last shell the exact k-NN query kernel runs in one launch for a full batch (the in-block reach)
+uint32_t vc_mih_knn_reach(const VcMihIndex* ix);
 int vc_mih_bucket(VcMihIndex* ix, uint32_t table, uint32_t index, std::vector<uint32_t>* local_ids, hipStream_t s,
                   std::string* err);
 int vc_mih_bitmap_test(VcMihIndex* ix, uint32_t table, uint32_t index, int* bit, hipStream_t s, std::string* err);

@@ -20,9 +20,11 @@
 #include <rccl/rccl.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <string>
 #include <thread>
 #include <vector>
@@ -81,6 +83,7 @@ struct Lane {
   void* q = nullptr;        size_t q_bytes = 0;   // the batch's queries on this device (peer copy from the root)
   uint64_t* gath = nullptr; size_t gath_bytes = 0;   // [G][slot]: shard g's rows | counts | statistics at slot g; on the root
                                                      // (and, with RCCL, everywhere) the gathered results of all shards
+  uint32_t* aux = nullptr;  size_t aux_bytes = 0;    // union scan of VC_FLAG_GLOBAL_STOP: its per-query inputs and outputs here
 };
 
 }  // namespace
@@ -102,6 +105,15 @@ struct vc_sharded {
   uint64_t* d_out = nullptr;    size_t out_bytes = 0;
   uint32_t* d_ocnt = nullptr;   size_t ocnt_bytes = 0;
   vc_query_stats* d_ostats = nullptr; size_t ostats_bytes = 0;
+  // VC_FLAG_GLOBAL_STOP (root device): round lists + counters + floors, gathered queries, merged rows / counts / statistics,
+  // the union scan's per-query words and the shards' tie ids
+  uint32_t* gs_u32 = nullptr;   size_t gs_u32_bytes = 0;
+  uint64_t* gs_q = nullptr;     size_t gs_q_bytes = 0;
+  uint64_t* gs_rows = nullptr;  size_t gs_rows_bytes = 0;
+  uint32_t* gs_cnt = nullptr;   size_t gs_cnt_bytes = 0;
+  vc_query_stats* gs_st = nullptr; size_t gs_st_bytes = 0;
+  uint32_t* gs_scan = nullptr;  size_t gs_scan_bytes = 0;
+  uint32_t gs_cap0 = 1;         // first round's cap (VC_MIH_GS_CAP)
   RcclApi rccl;
   std::vector<ncclComm_t> comms;
   uint32_t exchange = VC_EXCHANGE_PEER_COPY;   // what is in use
@@ -165,13 +177,15 @@ int vc_sharded_destroy(vc_sharded* h) {
       if (c) (void)h->rccl.CommDestroy(c);
   for (Lane& l : h->lanes) {
     (void)hipSetDevice(l.dev);
-    (void)hipFree(l.q); (void)hipFree(l.gath);
+    (void)hipFree(l.q); (void)hipFree(l.gath); (void)hipFree(l.aux);
     if (l.done) (void)hipEventDestroy(l.done);
     if (l.stream) (void)hipStreamDestroy(l.stream);
   }
   for (vc_engine* e : h->eng) vc_destroy(e);
   (void)hipSetDevice(h->root);
   (void)hipFree(h->d_hq); (void)hipFree(h->d_out); (void)hipFree(h->d_ocnt); (void)hipFree(h->d_ostats);
+  (void)hipFree(h->gs_u32); (void)hipFree(h->gs_q); (void)hipFree(h->gs_rows); (void)hipFree(h->gs_cnt); (void)hipFree(h->gs_st);
+  (void)hipFree(h->gs_scan);
   if (h->ev_q) (void)hipEventDestroy(h->ev_q);
   if (h->root_stream) (void)hipStreamDestroy(h->root_stream);
   delete h;
@@ -187,6 +201,16 @@ int vc_sharded_create(const vc_sharded_config* cfg, vc_sharded** out) {
   if (cfg->exchange > VC_EXCHANGE_RCCL) return sfail(nullptr, VC_ERR_INVALID, "unknown exchange %u", cfg->exchange);
   if (cfg->engine.capacity == 0 || cfg->engine.capacity + (uint64_t)cfg->engine.id_base > 0x100000000ull)
     return sfail(nullptr, VC_ERR_INVALID, "capacity must be > 0 and id_base + capacity <= 2^32 (ids are uint32)");
+  if (cfg->engine.flags & VC_FLAG_GLOBAL_STOP) {   // the global stop reproduces an exact radius loop whose statistics have a closed form
+    const uint32_t f = cfg->engine.flags, m = cfg->engine.n_tables;
+    if (m == 0) return sfail(nullptr, VC_ERR_INVALID, "VC_FLAG_GLOBAL_STOP needs an MIH index (n_tables > 0)");
+    if (f & VC_FLAG_REF_SIGNEXT_KEYS)
+      return sfail(nullptr, VC_ERR_INVALID, "VC_FLAG_GLOBAL_STOP: VC_FLAG_REF_SIGNEXT_KEYS makes the radius loop inexact");
+    if ((f & VC_FLAG_REF_STOP_LITERAL4) && m < 4)
+      return sfail(nullptr, VC_ERR_INVALID, "VC_FLAG_GLOBAL_STOP: VC_FLAG_REF_STOP_LITERAL4 with fewer than 4 tables makes the radius loop inexact");
+    if (f & VC_FLAG_USE_BITMAP)
+      return sfail(nullptr, VC_ERR_INVALID, "VC_FLAG_GLOBAL_STOP: the statistics of VC_FLAG_USE_BITMAP would need the union's bitmap");
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sfail(nullptr, VC_ERR_NO_DEVICE, "no HIP device visible");
   vc_sharded* h = new vc_sharded();
@@ -195,6 +219,7 @@ int vc_sharded_create(const vc_sharded_config* cfg, vc_sharded** out) {
   h->D = cfg->n_devices ? cfg->n_devices : (uint32_t)std::min<int>(ndev, (int)cfg->n_shards);
   h->capacity = cfg->engine.capacity;
   h->nbytes = cfg->engine.bits / 8;
+  if (const char* v = getenv("VC_MIH_GS_CAP")) h->gs_cap0 = (uint32_t)std::max(0, atoi(v));   // dev knob: first round's cap
   h->eng.assign(h->G, nullptr);
   h->dev.resize(h->G);
   h->lo.resize(h->G);
@@ -393,8 +418,11 @@ __global__ void vc_sharded_stats_kernel(const uint64_t* __restrict__ base, uint6
 // Everything of a batch is enqueued, nothing is waited for (LINEAR; the MIH modes make the host wait inside each shard's
 // vc_search_knn_dev -- how many queries continue decides what is enqueued next -- which is why lanes of different devices
 // then run on host threads): queries, rows, counts and statistics live in HBM on the root device, valid in `S` order.
+// r_cap != VC_NO_CAP (VC_MODE_MIH_EXACT only): every shard runs capped at that shell (vc_engine_knn_capped), the round of the
+// global stop; the slots stay in the root lane's gather buffer for its settle kernel.
+#define VC_NO_CAP 0xFFFFFFFFu
 static int sharded_search_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out,
-                              uint32_t* d_counts, vc_query_stats* d_stats, hipStream_t S) {
+                              uint32_t* d_counts, vc_query_stats* d_stats, hipStream_t S, uint32_t r_cap = VC_NO_CAP) {
   const SlotLayout L(nq, k, d_stats != nullptr);
   const size_t qbytes = (size_t)nq * h->nbytes;
   int rc;
@@ -445,8 +473,9 @@ static int sharded_search_dev(vc_sharded* h, const void* d_queries, uint32_t nq,
             !hip(hipMemsetAsync(slot + L.cnt_off, 0, (L.words - L.cnt_off) * 8, ls), "hipMemsetAsync")) return;
         continue;
       }
-      const int r = vc_search_knn_dev_stats(h->eng[g], q, nq, k, mode, slot, (uint32_t*)(slot + L.cnt_off),
-                                            d_stats ? (vc_query_stats*)(slot + L.stats_off) : nullptr, ls);
+      vc_query_stats* sst = d_stats ? (vc_query_stats*)(slot + L.stats_off) : nullptr;
+      const int r = r_cap != VC_NO_CAP ? vc_engine_knn_capped(h->eng[g], q, nq, k, r_cap, slot, (uint32_t*)(slot + L.cnt_off), sst, ls)
+                                       : vc_search_knn_dev_stats(h->eng[g], q, nq, k, mode, slot, (uint32_t*)(slot + L.cnt_off), sst, ls);
       if (r != VC_OK) { lane_rc[li] = r; lane_err[li] = std::string("shard ") + std::to_string(g) + ": " + vc_last_error(h->eng[g]); return; }
     }
     if (!is_root) hip(hipEventRecord(l.done, ls), "hipEventRecord");
@@ -491,6 +520,380 @@ static int sharded_search_dev(vc_sharded* h, const void* d_queries, uint32_t nq,
   return VC_OK;
 }
 
+// ---- VC_FLAG_GLOBAL_STOP ------------------------------------------------------------------------------------------------
+// Exact MIH over the shards with the stop decision of ONE SearchWorker over the union (the reference's master tests the
+// merged heap, qmax.top().dist <= radius * 4, and broadcasts is_stop: search_worker.cc:179-207, mpi_coordinator.cc:26-69).
+// The shards run in CAPPED rounds (vc_engine_knn_capped: shells 0..t, the shard's own stop rule active, no scan switch); the
+// merged rows of a round are judged on the root by gs_settle_kernel, one thread per query.  What it rests on (D = merged k-th
+// distance, e_g = last shell shard g evaluated, mult = the stop multiplier min(m, 4)):
+//   * a shard's rows hold every one of its items below m (e_g + 1) (pigeonhole), so D <= m (e_lo + 1) over the non-empty
+//     shards makes D the union's exact k-th distance D*; a shard that stopped by its own rule always meets it;
+//   * the union loop stops at R = ceil(D* / mult) - 1 (0 for D* = 0) -- when mult == m and D* = m r0 it may already stop at
+//     r0 - 1 (then R = r0 - 1 iff shell r0 - 1 holds k items at or below D*: mih_replay_kernel's rule), else at r0;
+//   * no shard stops before R (its local k-th distance is never below the union's), so in a round capped at t = R every shard
+//     ends at e_g = R: the merged rows are the union loop's rows at R and the shards' candidate counts add up to its count.
+// A query is settled when its round ended every shard in the shell R requires; otherwise the kernel files it under the cap
+// the next round needs.  Queries that need a shell beyond the shards' in-block reach (far or uniform queries) go to the
+// union scan: LINEAR over the shards gives D* and the rows, mih_tie_collect_kernel decides the tie at the threshold and
+// vc_launch_minsub_count counts the candidates -- the union-wide counterpart of the single engine's scan + replay.
+#define GS_CAPS 17u   // caps 0..16 (inblock_last_shell never goes beyond 16)
+
+__device__ __forceinline__ unsigned long long gs_leaves(uint32_t S, uint32_t R) {   // table 0's gets of shells 0..R: sum of C(S, r)
+  unsigned long long c = 1, sum = 0;
+  for (uint32_t r = 0; r <= R && r <= S; ++r) {
+    sum += c;
+    c = c * (S - r) / (r + 1);
+  }
+  return sum;
+}
+
+__global__ void __launch_bounds__(256) gs_iota_kernel(uint32_t* __restrict__ p, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = i;
+}
+
+struct GsSettleArgs {
+  const uint64_t* base;          // the round's gathered slots (rows | counts | statistics per shard)
+  uint64_t slot_words, stats_off;
+  uint32_t G, nonempty;          // bit g: shard g holds records
+  uint32_t n, t, k, m, S, mult, reach, nq;
+  const uint32_t* list;          // [n] query of merged row j
+  const uint64_t* rows;          // [n][k] merged rows
+  const uint32_t* cnt;           // [n]
+  uint32_t* floor_;              // [nq] the union loop cannot stop below this shell
+  uint64_t* out;                 // final rows / counts / statistics, by query
+  uint32_t* out_cnt;
+  vc_query_stats* out_stats;     // may be null
+  uint32_t* next;                // [GS_CAPS][nq] lists of the next round, counters next_ctr[cap]
+  uint32_t* next_ctr;
+  uint32_t* scan;                // union-scan list, counter *scan_ctr
+  uint32_t* scan_ctr;
+};
+
+__global__ void __launch_bounds__(256) gs_settle_kernel(const GsSettleArgs a) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= a.n) return;
+  const uint32_t q = a.list[j];
+  const uint32_t c = min(a.cnt[j], a.k);
+  const uint64_t* row = a.rows + (uint64_t)j * a.k;
+  uint32_t e_lo = 0xFFFFFFFFu, e_hi = 0;
+  unsigned long long seen = 0;
+  for (uint32_t g = 0; g < a.G; ++g) {
+    if (!((a.nonempty >> g) & 1u)) continue;
+    const vc_query_stats s = ((const vc_query_stats*)(a.base + (uint64_t)g * a.slot_words + a.stats_off))[j];
+    e_lo = min(e_lo, s.radius);
+    e_hi = max(e_hi, s.radius);
+    seen += s.n_candidates;
+  }
+  const uint32_t D = c == a.k ? (uint32_t)(row[a.k - 1] >> 32) : 0xFFFFFFFFu;
+  uint32_t flo = a.floor_[q];
+  // every shard ended exactly in shell t: the rows are the union loop's at t -- if it does not stop there, it stops later
+  const bool at_t = e_lo == a.t && e_hi == a.t;
+  if (at_t && !(c == a.k && D <= a.mult * (a.t + 1))) flo = max(flo, a.t + 1);
+  uint32_t R = 0xFFFFFFFFu, next = 0xFFFFFFFFu;
+  if (c < a.k) {
+    if (e_lo >= a.S) R = a.S;                        // every shell searched: the union holds fewer than k items
+    else next = a.t + 1;
+  } else if (D > a.m * (e_lo + 1)) {
+    next = (D + a.m - 1) / a.m - 1;                  // pigeonhole not met: D only bounds D* from above
+  } else {
+    const uint32_t rs = min(a.S, D == 0 ? 0u : (D + a.mult - 1) / a.mult - 1);
+    const bool tie = a.mult == a.m && D != 0 && D % a.m == 0;
+    const uint32_t want = (tie && flo > rs) ? rs + 1 : rs;
+    if (e_lo == want && e_hi == want) R = want;
+    else next = want;
+  }
+  a.floor_[q] = flo;
+  if (R != 0xFFFFFFFFu) {
+    uint64_t* o = a.out + (uint64_t)q * a.k;
+    for (uint32_t i = 0; i < a.k; ++i) o[i] = row[i];
+    a.out_cnt[q] = c;
+    if (a.out_stats) {
+      vc_query_stats s{};
+      s.radius = R;
+      s.n_results = c;
+      s.n_sub_reads = gs_leaves(a.S, R);
+      s.n_candidates = seen;
+      a.out_stats[q] = s;
+    }
+  } else if (next <= a.reach) {
+    a.next[(uint64_t)next * a.nq + atomicAdd(&a.next_ctr[next], 1u)] = q;
+  } else {
+    a.scan[atomicAdd(a.scan_ctr, 1u)] = q;
+  }
+}
+
+// union scan, step 1: the rule applied to the LINEAR rows (sd = [dist | radius | need | R | iota | ones], nq apart)
+__global__ void __launch_bounds__(256) gs_scan_plan_kernel(uint32_t n, uint32_t k, uint32_t m, uint32_t S, uint32_t mult,
+                                                           const uint32_t* __restrict__ list, const uint32_t* __restrict__ floor_,
+                                                           const uint64_t* __restrict__ rows, const uint32_t* __restrict__ cnt,
+                                                           uint32_t* __restrict__ sd, uint32_t nq) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t c = min(cnt[j], k);
+  const uint64_t* row = rows + (uint64_t)j * k;
+  uint32_t dist = 0, rad = 0, need = 0, R = S;       // fewer than k items: the loop runs to its last shell
+  if (c == k) {
+    const uint32_t D = (uint32_t)(row[k - 1] >> 32);
+    const uint32_t rs = min(S, D == 0 ? 0u : (D + mult - 1) / mult - 1);
+    R = rs;
+    if (mult == m && D != 0 && D % m == 0) {
+      if (floor_[list[j]] > rs) {
+        R = rs + 1;
+      } else {                                       // does shell rs = D/m - 1 already hold k items at or below D?
+        uint32_t below = 0;
+        while (below < k && (uint32_t)(row[below] >> 32) < D) ++below;
+        dist = D;
+        rad = rs;
+        need = k - below;
+      }
+    }
+  }
+  sd[j] = dist;
+  sd[nq + j] = rad;
+  sd[2 * (size_t)nq + j] = need;
+  sd[3 * (size_t)nq + j] = R;
+  sd[4 * (size_t)nq + j] = j;
+  sd[5 * (size_t)nq + j] = 1;
+}
+
+// union scan, step 2: the shards' ties (ids ascending within a shard, shards in id order) decide the tie at the threshold
+__global__ void __launch_bounds__(256) gs_scan_tie_kernel(uint32_t n, uint32_t k, uint32_t G, uint32_t* __restrict__ sd, uint32_t nq,
+                                                          const uint32_t* __restrict__ tie_ids, const uint32_t* __restrict__ tie_cnt,
+                                                          uint64_t* __restrict__ rows) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t need = sd[2 * (size_t)nq + j], rs = sd[nq + j], D = sd[j];
+  if (need == 0) return;
+  uint32_t total = 0;
+  for (uint32_t g = 0; g < G; ++g) total += tie_cnt[(size_t)g * nq + j];
+  if (total < need) {
+    sd[3 * (size_t)nq + j] = rs + 1;                 // shell rs has too few: the loop stops at D/m with the scan's rows
+    return;
+  }
+  uint32_t w = k - need;                             // the rows below D stay; the ties of shell rs follow, smallest ids first
+  for (uint32_t g = 0; g < G && w < k; ++g)
+    for (uint32_t i = 0; i < tie_cnt[(size_t)g * nq + j] && w < k; ++i)
+      rows[(uint64_t)j * k + w++] = ((uint64_t)D << 32) | tie_ids[((size_t)g * nq + j) * k + i];
+  sd[3 * (size_t)nq + j] = rs;
+}
+
+// union scan, step 3: rows, counts and the statistics of one SearchWorker stopping at R
+__global__ void __launch_bounds__(256) gs_scan_final_kernel(uint32_t n, uint32_t k, uint32_t S, const uint32_t* __restrict__ list,
+                                                            const uint32_t* __restrict__ sd, uint32_t nq, const uint64_t* __restrict__ rows,
+                                                            const uint32_t* __restrict__ cnt, const unsigned long long* __restrict__ seen,
+                                                            uint32_t n_lanes, uint64_t* __restrict__ out, uint32_t* __restrict__ out_cnt,
+                                                            vc_query_stats* __restrict__ out_stats) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t q = list[j];
+  for (uint32_t i = 0; i < k; ++i) out[(uint64_t)q * k + i] = rows[(uint64_t)j * k + i];
+  out_cnt[q] = cnt[j];
+  if (out_stats) {
+    const uint32_t R = sd[3 * (size_t)nq + j];
+    vc_query_stats s{};
+    s.radius = R;
+    s.n_results = cnt[j];
+    s.n_sub_reads = gs_leaves(S, R);
+    for (uint32_t l = 0; l < n_lanes; ++l) s.n_candidates += seen[(size_t)l * nq + j];
+    out_stats[q] = s;
+  }
+}
+
+static int sharded_global_stop(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out, uint32_t* d_counts,
+                               vc_query_stats* d_stats, hipStream_t S) {
+  const uint32_t W = h->nbytes / 8, m = h->cfg.engine.n_tables, Sb = h->cfg.engine.bits / m;
+  const uint32_t mult = (h->cfg.engine.flags & VC_FLAG_REF_STOP_LITERAL4) ? 4u : std::min(m, 4u);
+  const bool trace = getenv("VC_MIH_GS_TRACE") != nullptr;   // dev: per-round wall times on stderr
+  uint32_t nonempty = 0, reach = GS_CAPS - 1;
+  std::vector<VcEngineView> view(h->G);
+  for (uint32_t g = 0; g < h->G; ++g) {
+    vc_engine_view(h->eng[g], &view[g]);
+    if (shard_size(h, g) == 0) continue;
+    nonempty |= 1u << g;
+    reach = std::min(reach, view[g].reach);
+  }
+  int rc;
+  VS_HIP(h, hipSetDevice(h->root));
+  if (!d_counts) {
+    if ((rc = sgrow(h, &h->d_ocnt, &h->ocnt_bytes, (size_t)nq * 4))) return rc;
+    d_counts = h->d_ocnt;
+  }
+  const size_t LW = (size_t)GS_CAPS * nq;   // words of one set of round lists
+  if ((rc = sgrow(h, &h->gs_u32, &h->gs_u32_bytes, (2 * LW + 2 * (size_t)nq + 96) * 4))) return rc;
+  if ((rc = sgrow(h, &h->gs_q, &h->gs_q_bytes, (size_t)nq * h->nbytes))) return rc;
+  if ((rc = sgrow(h, &h->gs_rows, &h->gs_rows_bytes, (size_t)nq * k * 8))) return rc;
+  if ((rc = sgrow(h, &h->gs_cnt, &h->gs_cnt_bytes, (size_t)nq * 4))) return rc;
+  if ((rc = sgrow(h, &h->gs_st, &h->gs_st_bytes, (size_t)nq * sizeof(vc_query_stats)))) return rc;
+  uint32_t* lists[2] = {h->gs_u32, h->gs_u32 + LW};
+  uint32_t* ctr[2] = {h->gs_u32 + 2 * LW, h->gs_u32 + 2 * LW + 32};
+  uint32_t* scan_ctr = h->gs_u32 + 2 * LW + 64;
+  uint32_t* scan = h->gs_u32 + 2 * LW + 96;
+  uint32_t* floor_ = scan + nq;
+  VS_HIP(h, hipMemsetAsync(floor_, 0, (size_t)nq * 4, S));
+  VS_HIP(h, hipMemsetAsync(scan_ctr, 0, 4, S));
+  std::vector<uint32_t> n_at(GS_CAPS + 1, 0);   // queries per cap of the coming round | union scan
+  uint32_t n_scan = 0;
+  if (nonempty == 0) {   // nothing to probe: the union scan reports the empty union (R = last shell, no candidates)
+    hipLaunchKernelGGL(gs_iota_kernel, dim3((nq + 255) / 256), dim3(256), 0, S, scan, nq);
+    VS_HIP(h, hipGetLastError());
+    n_scan = nq;
+  } else {
+    const uint32_t t0 = std::min(h->gs_cap0, reach);
+    hipLaunchKernelGGL(gs_iota_kernel, dim3((nq + 255) / 256), dim3(256), 0, S, lists[0] + (size_t)t0 * nq, nq);
+    VS_HIP(h, hipGetLastError());
+    n_at[t0] = nq;
+  }
+  Lane& Rl = h->lanes[h->root_lane];
+  int cur = 0;
+  for (uint32_t round = 0; round < 8; ++round) {
+    bool any = false;
+    for (uint32_t t = 0; t < GS_CAPS; ++t) any = any || n_at[t];
+    if (!any) break;
+    const auto t_round = std::chrono::steady_clock::now();
+    VS_HIP(h, hipSetDevice(h->root));
+    VS_HIP(h, hipMemsetAsync(ctr[cur ^ 1], 0, GS_CAPS * 4, S));
+    for (uint32_t t = 0; t < GS_CAPS; ++t) {
+      const uint32_t n = n_at[t];
+      if (!n) continue;
+      const uint32_t* list = lists[cur] + (size_t)t * nq;
+      VS_HIP(h, hipSetDevice(h->root));
+      VS_HIP(h, vc_launch_gather_queries((const uint64_t*)d_queries, list, n, W, h->gs_q, S));
+      if ((rc = sharded_search_dev(h, h->gs_q, n, k, VC_MODE_MIH_EXACT, h->gs_rows, h->gs_cnt, h->gs_st, S, t))) return rc;
+      const SlotLayout L(n, k, true);
+      GsSettleArgs a{};
+      a.base = Rl.gath; a.slot_words = L.words; a.stats_off = L.stats_off; a.G = h->G; a.nonempty = nonempty;
+      a.n = n; a.t = t; a.k = k; a.m = m; a.S = Sb; a.mult = mult; a.reach = reach; a.nq = nq;
+      a.list = list; a.rows = h->gs_rows; a.cnt = h->gs_cnt; a.floor_ = floor_;
+      a.out = d_out; a.out_cnt = d_counts; a.out_stats = d_stats;
+      a.next = lists[cur ^ 1]; a.next_ctr = ctr[cur ^ 1]; a.scan = scan; a.scan_ctr = scan_ctr;
+      VS_HIP(h, hipSetDevice(h->root));
+      hipLaunchKernelGGL(gs_settle_kernel, dim3((n + 255) / 256), dim3(256), 0, S, a);
+      VS_HIP(h, hipGetLastError());
+    }
+    cur ^= 1;
+    std::vector<uint32_t> c(GS_CAPS + 1);
+    VS_HIP(h, hipMemcpyAsync(c.data(), ctr[cur], GS_CAPS * 4, hipMemcpyDeviceToHost, S));
+    VS_HIP(h, hipMemcpyAsync(c.data() + GS_CAPS, scan_ctr, 4, hipMemcpyDeviceToHost, S));
+    VS_HIP(h, hipStreamSynchronize(S));
+    if (trace) {
+      fprintf(stderr, "[vc_gs] round %u:", round);
+      for (uint32_t t = 0; t < GS_CAPS; ++t) if (n_at[t]) fprintf(stderr, " cap %u x %u", t, n_at[t]);
+      fprintf(stderr, " -> open");
+      for (uint32_t t = 0; t < GS_CAPS; ++t) if (c[t]) fprintf(stderr, " cap %u x %u", t, c[t]);
+      fprintf(stderr, ", union scan %u  %.1f us\n", c[GS_CAPS],
+              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_round).count());
+    }
+    n_at.assign(c.begin(), c.begin() + GS_CAPS);
+    n_scan = c[GS_CAPS];
+  }
+  // (the rounds settle a query in at most four: the first cap, the pigeonhole cap, R, and R + 1 after a tie; 8 is a bound)
+  for (uint32_t t = 0; t < GS_CAPS; ++t)
+    if (n_at[t]) {
+      VS_HIP(h, hipMemcpyAsync(scan + n_scan, lists[cur] + (size_t)t * nq, (size_t)n_at[t] * 4, hipMemcpyDeviceToDevice, S));
+      n_scan += n_at[t];
+    }
+  if (n_scan == 0) return VC_OK;
+  // ---- the union scan
+  const auto t_scan = std::chrono::steady_clock::now();
+  const uint32_t n = n_scan, NL = (uint32_t)h->lanes.size();
+  VS_HIP(h, hipSetDevice(h->root));
+  // root words: seen [NL][nq] u64 | sd [6][nq] | tie counts [G][nq] | tie ids [G][nq][k]
+  const size_t seen_w = 2 * (size_t)NL * nq, sd_w = 6 * (size_t)nq, tc_w = (size_t)h->G * nq;
+  if ((rc = sgrow(h, &h->gs_scan, &h->gs_scan_bytes, (seen_w + sd_w + tc_w + (size_t)h->G * nq * k) * 4))) return rc;
+  unsigned long long* seen = (unsigned long long*)h->gs_scan;
+  uint32_t* sd = h->gs_scan + seen_w;
+  uint32_t* tie_cnt = sd + sd_w;
+  uint32_t* tie_ids = tie_cnt + tc_w;
+  VS_HIP(h, vc_launch_gather_queries((const uint64_t*)d_queries, scan, n, W, h->gs_q, S));
+  if ((rc = sharded_search_dev(h, h->gs_q, n, k, VC_MODE_LINEAR, h->gs_rows, h->gs_cnt, nullptr, S))) return rc;
+  VS_HIP(h, hipSetDevice(h->root));
+  hipLaunchKernelGGL(gs_scan_plan_kernel, dim3((n + 255) / 256), dim3(256), 0, S, n, k, m, Sb, mult, (const uint32_t*)scan,
+                     (const uint32_t*)floor_, (const uint64_t*)h->gs_rows, (const uint32_t*)h->gs_cnt, sd, nq);
+  VS_HIP(h, hipGetLastError());
+  // one pass over the lanes: the per-query words go out, fn runs the lane's shards, results come back
+  auto over_lanes = [&](auto&& fn) -> int {
+    for (uint32_t li = 0; li < NL; ++li) {
+      Lane& l = h->lanes[li];
+      const bool is_root = li == h->root_lane;
+      hipStream_t ls = is_root ? S : l.stream;
+      const size_t LS = l.shards.size();
+      VS_HIP(h, hipSetDevice(h->root));
+      if (!is_root) VS_HIP(h, hipEventRecord(h->ev_q, S));
+      VS_HIP(h, hipSetDevice(l.dev));
+      // lane words: seen [nq] u64 | sd [6][nq] | tie counts [LS][nq] | tie ids [LS][nq][k] | tie chunk counts [nq][VC_TIE_CHUNKS]
+      if ((rc = sgrow(h, &l.aux, &l.aux_bytes, (2 * (size_t)nq + sd_w + LS * nq + LS * nq * k + (size_t)nq * VC_TIE_CHUNKS) * 4))) return rc;
+      if (!is_root) VS_HIP(h, hipStreamWaitEvent(ls, h->ev_q, 0));
+      VS_HIP(h, hipMemcpyPeerAsync(l.aux + 2 * (size_t)nq, l.dev, sd, h->root, sd_w * 4, ls));
+      const uint64_t* lq = is_root ? h->gs_q : (const uint64_t*)l.q;
+      if ((rc = fn(li, l, ls, lq))) return rc;
+      if (!is_root) {
+        VS_HIP(h, hipEventRecord(l.done, ls));
+        VS_HIP(h, hipSetDevice(h->root));
+        VS_HIP(h, hipStreamWaitEvent(S, l.done, 0));
+      }
+    }
+    VS_HIP(h, hipSetDevice(h->root));
+    return VC_OK;
+  };
+  // the tie at the threshold: every shard's smallest-id ties whose substrings reach below D/m
+  if ((rc = over_lanes([&](uint32_t, Lane& l, hipStream_t ls, const uint64_t* lq) -> int {
+         const uint32_t* lsd = l.aux + 2 * (size_t)nq;
+         uint32_t* lcnt = l.aux + 2 * (size_t)nq + sd_w;
+         uint32_t* lids = lcnt + l.shards.size() * nq;
+         for (size_t i = 0; i < l.shards.size(); ++i) {
+           const uint32_t g = l.shards[i];
+           if (!((nonempty >> g) & 1u)) {
+             VS_HIP(h, hipMemsetAsync(lcnt + i * nq, 0, (size_t)n * 4, ls));
+           } else {
+             const VcEngineView& v = view[g];
+             VS_HIP(h, vc_launch_tie_collect(v.cols, v.stride, v.n, W, m, Sb, v.id_base, lq, n, k, lsd, lsd + nq, lsd + 2 * (size_t)nq,
+                                             lids + l.shards.size() * nq * k, lids + i * nq * k, lcnt + i * nq, ls));
+           }
+           VS_HIP(h, hipMemcpyPeerAsync(tie_cnt + (size_t)g * nq, h->root, lcnt + i * nq, l.dev, (size_t)n * 4, ls));
+           VS_HIP(h, hipMemcpyPeerAsync(tie_ids + (size_t)g * nq * k, h->root, lids + i * nq * k, l.dev, (size_t)n * k * 4, ls));
+         }
+         return VC_OK;
+       })))
+    return rc;
+  hipLaunchKernelGGL(gs_scan_tie_kernel, dim3((n + 255) / 256), dim3(256), 0, S, n, k, h->G, sd, nq, (const uint32_t*)tie_ids,
+                     (const uint32_t*)tie_cnt, h->gs_rows);
+  VS_HIP(h, hipGetLastError());
+  // the candidates of the union loop up to R: every item whose minimum substring distance is <= R
+  if (d_stats) {
+    if ((rc = over_lanes([&](uint32_t li, Lane& l, hipStream_t ls, const uint64_t* lq) -> int {
+           const uint32_t* lsd = l.aux + 2 * (size_t)nq;
+           unsigned long long* lseen = (unsigned long long*)l.aux;
+           VS_HIP(h, hipMemsetAsync(lseen, 0, (size_t)n * 8, ls));
+           for (uint32_t g : l.shards) {
+             if (!((nonempty >> g) & 1u)) continue;
+             const VcEngineView& v = view[g];
+             VS_HIP(h, vc_launch_minsub_count(v.cols, v.stride, v.n, W, m, Sb, lq, lsd + 4 * (size_t)nq, lsd + 5 * (size_t)nq, n,
+                                              lsd + 3 * (size_t)nq, lseen, v.n_cu, ls));
+           }
+           VS_HIP(h, hipMemcpyPeerAsync(seen + (size_t)li * nq, h->root, lseen, l.dev, (size_t)n * 8, ls));
+           return VC_OK;
+         })))
+      return rc;
+  }
+  hipLaunchKernelGGL(gs_scan_final_kernel, dim3((n + 255) / 256), dim3(256), 0, S, n, k, Sb, (const uint32_t*)scan, (const uint32_t*)sd,
+                     nq, (const uint64_t*)h->gs_rows, (const uint32_t*)h->gs_cnt, (const unsigned long long*)seen, NL, d_out, d_counts, d_stats);
+  VS_HIP(h, hipGetLastError());
+  if (trace) {
+    VS_HIP(h, hipStreamSynchronize(S));
+    fprintf(stderr, "[vc_gs] union scan: %u queries  %.1f us\n", n,
+            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_scan).count());
+  }
+  return VC_OK;
+}
+
+static int sharded_search_any(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out,
+                              uint32_t* d_counts, vc_query_stats* d_stats, hipStream_t S) {
+  if (mode == VC_MODE_MIH_EXACT && (h->cfg.engine.flags & VC_FLAG_GLOBAL_STOP))
+    return sharded_global_stop(h, d_queries, nq, k, d_out, d_counts, d_stats, S);
+  return sharded_search_dev(h, d_queries, nq, k, mode, d_out, d_counts, d_stats, S);
+}
+
 int vc_sharded_root_device(const vc_sharded* h, int* device) {
   if (!h || !device) return VC_ERR_INVALID;
   *device = h->root;
@@ -500,7 +903,7 @@ int vc_sharded_root_device(const vc_sharded* h, int* device) {
 int vc_sharded_search_knn_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out,
                               uint32_t* d_counts, vc_query_stats* d_stats, void* stream) {
   if (!h || !d_queries || !d_out || nq == 0 || k == 0 || k > VC_MAX_K || mode > VC_MODE_MIH_APPROX) return VC_ERR_INVALID;
-  return sharded_search_dev(h, d_queries, nq, k, mode, d_out, d_counts, d_stats, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+  return sharded_search_any(h, d_queries, nq, k, mode, d_out, d_counts, d_stats, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
 }
 
 int vc_sharded_search_knn(vc_sharded* h, const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order,
@@ -516,7 +919,7 @@ int vc_sharded_search_knn(vc_sharded* h, const void* queries, uint32_t nq, uint3
   if ((rc = sgrow(h, &h->d_ocnt, &h->ocnt_bytes, (size_t)nq * 4))) return rc;
   if (stats && (rc = sgrow(h, &h->d_ostats, &h->ostats_bytes, (size_t)nq * sizeof(vc_query_stats)))) return rc;
   VS_HIP(h, hipMemcpyAsync(h->d_hq, queries, qbytes, hipMemcpyHostToDevice, S));
-  if ((rc = sharded_search_dev(h, h->d_hq, nq, k, mode, h->d_out, h->d_ocnt, stats ? h->d_ostats : nullptr, S))) return rc;
+  if ((rc = sharded_search_any(h, h->d_hq, nq, k, mode, h->d_out, h->d_ocnt, stats ? h->d_ostats : nullptr, S))) return rc;
   std::vector<uint32_t> cnt(nq);
   VS_HIP(h, hipSetDevice(h->root));
   VS_HIP(h, hipMemcpyAsync(out, h->d_out, rows * 8, hipMemcpyDeviceToHost, S));

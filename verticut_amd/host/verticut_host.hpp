@@ -230,8 +230,10 @@ class ShardedEngine : public Backend {
 // VC_SHARDS=G [VC_DEVICES=0,1,...]: the drivers' switch from one engine to the sharded store (no argv position is free for
 // it: run_distributed_search.py:74-79 fixes them all).  G = 1 (or unset) is the one-GPU Engine -- a one-shard store would
 // only add an exchange, a merge and copies --; anything that is not a number in 1..VC_MAX_SHARDS is refused, not guessed at.
-// Under VC_SHARDS the printed n_sub_reads / n_local_reads are SUMS over the shards and radius the widest shard's (every
-// shard stops by its own rule, verticut_gpu.h), not the figures of one SearchWorker over the whole database.
+// Under VC_SHARDS every shard stops by its own rule unless VC_GLOBAL_STOP=1: then the exact search stops where one
+// SearchWorker over the whole database stops (VC_FLAG_GLOBAL_STOP, verticut_gpu.h) and prints its rows and statistics.
+// Without it the printed n_sub_reads / n_local_reads are SUMS over the shards and radius the widest shard's.
+// VC_GLOBAL_STOP=1 with VC_REF_QUIRKS=1 is refused: the reference's quirks make its radius loop inexact.
 inline Backend* make_backend(uint32_t bits, uint32_t n_tables, uint64_t capacity, uint32_t flags) {
   const char* g = getenv("VC_SHARDS");
   long shards = 1;
@@ -240,6 +242,12 @@ inline Backend* make_backend(uint32_t bits, uint32_t n_tables, uint64_t capacity
     shards = strtol(g, &end, 10);
     if (end == g || *end != '\0' || shards < 1 || shards > VC_MAX_SHARDS)
       throw EngineError(VC_ERR_INVALID, std::string("VC_SHARDS must be a number in 1..") + std::to_string(VC_MAX_SHARDS) + ", got '" + g + "'");
+  }
+  const char* gs = getenv("VC_GLOBAL_STOP");
+  if (gs && atoi(gs)) {
+    if (flags & (VC_FLAG_REF_SIGNEXT_KEYS | VC_FLAG_REF_STOP_LITERAL4))
+      throw EngineError(VC_ERR_INVALID, "VC_GLOBAL_STOP=1 cannot be combined with VC_REF_QUIRKS=1 (the quirks make the radius loop inexact)");
+    flags |= VC_FLAG_GLOBAL_STOP;   // a one-GPU Engine ignores it: its stop is global already
   }
   if (shards <= 1) return new Engine(bits, n_tables, capacity, flags);
   std::vector<int> devices;
