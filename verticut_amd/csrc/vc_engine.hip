@@ -97,8 +97,8 @@ static int grow(vc_engine* e, T** p, size_t* have, size_t need) {
   return VC_OK;
 }
 
-// environment knobs (developer / test switches): read here, once per engine, never on a launch path
-static void read_knobs(VcKnobs* k) {
+// environment knobs (developer / test switches): read here, once per engine (and once per sharded handle), never on a launch path
+void read_knobs(VcKnobs* k) {
   if (const char* w = getenv("VC_SCAN_WRAP")) k->scan_wrap = (uint32_t)atoi(w);
   if (const char* w = getenv("VC_SCAN_DIAG")) k->scan_diag = (uint32_t)atoi(w);
   if (const char* w = getenv("VC_SCAN_TRACE")) k->scan_trace = atoi(w) != 0;
@@ -129,6 +129,9 @@ static void read_knobs(VcKnobs* k) {
   if (const char* v = getenv("VC_MIH_QTILE")) k->mih_qtile = atoi(v);
   if (const char* v = getenv("VC_RECOVER_SPIN_LIMIT")) k->recover_spin_limit = (uint32_t)strtoul(v, nullptr, 10);
   if (const char* v = getenv("VC_RECOVER_TEST_FAIL")) k->recover_test_fail = (uint32_t)strtoul(v, nullptr, 10);
+  k->stream_trace = getenv("VC_STREAM_TRACE") != nullptr;
+  if (const char* v = getenv("VC_MIH_GS_CAP")) k->gs_cap = (uint32_t)std::max(0, atoi(v));
+  k->gs_trace = getenv("VC_MIH_GS_TRACE") != nullptr;
 }
 
 static int bind_device(vc_engine* e) {

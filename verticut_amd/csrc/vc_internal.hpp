@@ -36,7 +36,11 @@ struct VcKnobs {
   int mih_group = 0;                          // VC_MIH_GROUP=1..3: shells sharing the query kernel's first pass (0 = adaptive)
   uint32_t recover_spin_limit = 0;            // VC_RECOVER_SPIN_LIMIT: bound of the recovery grid barrier's spin (0 = default, ~3 s)
   uint32_t recover_test_fail = 0;             // VC_RECOVER_TEST_FAIL=N (tests): the first N recover launches wait for a block that never comes
+  bool stream_trace = false;                  // VC_STREAM_TRACE (dev): per-block start / look-up / end times of mih_bucket_stream_kernel on stderr
+  uint32_t gs_cap = 1;                        // VC_MIH_GS_CAP (dev): cap of the sharded global stop's first round
+  bool gs_trace = false;                      // VC_MIH_GS_TRACE (dev): per-round wall times of the sharded global stop on stderr
 };
+void read_knobs(VcKnobs* k);   // vc_engine.hip: the one place that reads the environment (once per engine / sharded handle)
 
 // ---- vc_scan.hip ------------------------------------------------------------------------------
 // Scan-kernel shape chosen per call: BLK threads, U column loads per thread per chunk.

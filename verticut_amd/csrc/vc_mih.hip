@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -2505,6 +2506,8 @@ static bool poll_mapped_word(volatile T* flag, T expect) {
   }
 }
 
+struct MihCounters;   // the tile's counter block (search section)
+
 struct VcMihIndex {
   uint32_t W = 0, m = 0, sbits = 0, id_base = 0, flags = 0, n_cu = 0, cap = 0;
   uint64_t n = 0;
@@ -2516,10 +2519,10 @@ struct VcMihIndex {
   uint32_t tile_k = 0, tile_cap = 0;
   void* d_tile = nullptr;
   size_t tile_bytes = 0;
-  uint32_t* d_lists = nullptr;   // 4 slot lists of qtile_max entries + counters + the launch order
-  uint32_t* h_ctr = nullptr;     // pinned: the counters the host reads back after every launch sequence
-  uint32_t* h_ctr_dev = nullptr; // its device-side alias (mapped): the query kernel's counters are stored there directly
-  uint32_t ctr_seq = 0;          // sequence number of the last counter publication (h_ctr[8] when it has landed)
+  uint32_t* d_lists = nullptr;   // 4 slot lists of qtile_max entries + counters + the launch order (MihLists, carved by ensure_tile)
+  MihCounters* h_ctr = nullptr;     // pinned: the counters the host reads back after every launch sequence
+  MihCounters* h_ctr_dev = nullptr; // its device-side alias (mapped): the query kernel's counters are stored there directly
+  uint32_t ctr_seq = 0;          // sequence number of the last counter publication (h_ctr->seq when it has landed)
   // measurement (vc_get_timing): event pairs around every mih_query_kernel launch, device totals of its work counters
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
   size_t ev_used = 0;
@@ -3050,14 +3053,49 @@ int vc_mih_load(VcMihIndex** out, const char* path, const uint64_t* d_cols, uint
 }
 
 // ---- search -------------------------------------------------------------------------------------------
-// per-slot state of a search tile.  The candidate rings ([slot][cap], 2 GB at the default cap) are used only by the
-// multi-block shells and are allocated the first time a query gets there (with_ring).
+// per-slot state of a search tile.  The candidate rings ([slot][cap], 8 GiB at the default tile and cap) are used only by
+// the multi-block shells and are allocated the first time a query gets there (with_ring).
+//
+// The tile's counter block, one per index, behind the four slot lists.  Every word is written by the kernel named next
+// to it and read back by the host; the same 16 words exist once more in mapped host memory (VcMihIndex::h_ctr), where
+// mih_work_reduce_kernel publishes `heavy` .. `stop_hist` and then `seq`.
+struct MihCounters {
+  uint32_t next;           // mih_commit_kernel: queries that go on to the next shell | mih_partition_kernel: queries for the scan |
+                           // the scan fallback: queries it could not settle (came back)
+  uint32_t redo;           // mih_commit_kernel: queries whose ring overflowed (recovery round) | mih_partition_kernel: queries kept
+  uint32_t heavy;          // mih_query_kernel: queries handed over unfinished (QueryKernelParams::heavy_ctr)
+  uint32_t unused3;
+  uint32_t stop_hist[4];   // mih_query_kernel: queries of the launch by stop shell 0 / 1 / 2 / later (QueryKernelParams::radius_hist)
+  uint32_t seq;            // mapped host copy only: sequence number of the launch whose counters have landed
+  uint32_t unused9[7];
+};
+static_assert(sizeof(MihCounters) == 64, "the counter block is 16 words");
+static_assert(offsetof(MihCounters, redo) == 4, "CommitParams::ctr / mih_partition_kernel: [0] = next / scan, [1] = redo / keep");
+static_assert(offsetof(MihCounters, heavy) == 2 * 4 && offsetof(MihCounters, seq) == 8 * 4,
+              "mih_work_reduce_kernel publishes words 2..7 of the block and writes the sequence number to word 8");
+static_assert(offsetof(MihCounters, stop_hist) == 4 * 4, "the stop-shell histogram is words 4..7");
+// what a launch of the query kernel counts (re-zeroed by the reduce kernel), and the words of it the host reads
+constexpr size_t MIH_CTR_LAUNCH_BYTES = offsetof(MihCounters, seq);
+constexpr size_t MIH_CTR_PUBLISHED_BYTES = offsetof(MihCounters, seq) - offsetof(MihCounters, heavy);
+
+// VcMihIndex::d_lists: list[0..3] of qtile_max slots each | MihCounters | order[qtile_max].  Roles during a k-NN tile:
+//   cur  (starts as list[0]) the queries still open: the query kernel writes the handed-over ones there, every shell reads it;
+//   nxt  (list[1])           filled by the shell's commit kernel with the queries that go on; swapped with cur after the shell;
+//   redo (list[2])           queries of the shell whose ring overflowed (they go round again); the cost model's kept queries;
+//   kept (list[3])           copy of the hand-over list, so that the rows of every handed-over query are exported at the end.
+// The cost-model switch borrows nxt / redo for its scan list and for what comes back, and swaps the result into cur.
+struct MihLists {
+  uint32_t* list[4];
+  MihCounters* ctr;
+  uint32_t* order;         // mih_order_kernel: the query kernel's launch order
+};
+
 static uint32_t qtile_max(const VcMihIndex* ix) {
   const int v = ix->knobs.mih_qtile;
   return v > 0 ? std::min(std::max((uint32_t)v, MIH_QTILE_MIN), MIH_QTILE_LIMIT) : MIH_QTILE_MAX;
 }
 // `slots`: queries of the call's largest launch (the state is laid out for exactly that many, so one call passes one value)
-static int ensure_tile(VcMihIndex* ix, uint32_t slots, uint32_t k, uint32_t cap, bool with_ring, MihState* st, std::string* err) {
+static int ensure_tile(VcMihIndex* ix, uint32_t slots, uint32_t k, uint32_t cap, bool with_ring, MihState* st, MihLists* ls, std::string* err) {
   const size_t Q = std::max(slots, MIH_QTILE_MIN);
   size_t bytes = 0;
   auto take = [&](size_t b) { size_t o = bytes; bytes += (b + 255) & ~(size_t)255; return o; };
@@ -3078,11 +3116,14 @@ static int ensure_tile(VcMihIndex* ix, uint32_t slots, uint32_t k, uint32_t cap,
     MIH_CHECK(hipMalloc((void**)&ix->d_ring, Q * cap * 8));
     ix->ring_entries = Q * cap;
   }
-  if (!ix->d_lists) {   // 4 slot lists + 4 counters + 4 stop-shell counts (the counters start at zero; the reduce kernel re-zeroes what a launch counted)
-    const size_t QM = qtile_max(ix);   // (laid out for the largest tile once: the counter block must not move between calls)
-    MIH_CHECK(hipMalloc((void**)&ix->d_lists, (5 * QM + 16) * 4));   // ... + the launch order [QM] behind a 16-word counter block
-    MIH_CHECK(hipMemset(ix->d_lists + 4 * QM, 0, 64));
+  const size_t QM = qtile_max(ix);   // (laid out for the largest tile once: the counter block must not move between calls)
+  if (!ix->d_lists) {   // (the counters start at zero; the reduce kernel re-zeroes what a launch counted)
+    MIH_CHECK(hipMalloc((void**)&ix->d_lists, (4 + 1) * QM * sizeof(uint32_t) + sizeof(MihCounters)));   // four lists + the launch order
+    MIH_CHECK(hipMemset(ix->d_lists + 4 * QM, 0, sizeof(MihCounters)));
   }
+  for (size_t i = 0; i < 4; ++i) ls->list[i] = ix->d_lists + i * QM;
+  ls->ctr = (MihCounters*)(ix->d_lists + 4 * QM);
+  ls->order = (uint32_t*)(ls->ctr + 1);
   uint8_t* b = (uint8_t*)ix->d_tile;
   st->thresh = (uint64_t*)(b + o_thresh);
   st->ring = ix->d_ring;
@@ -3096,6 +3137,35 @@ static int ensure_tile(VcMihIndex* ix, uint32_t slots, uint32_t k, uint32_t cap,
   st->topn = (uint32_t*)(b + o_topn);
   st->work = (unsigned long long*)(b + o_work);
   return VC_OK;
+}
+
+// A block of pinned host memory that a kernel publishes into through its device alias, sequence number last (the k-NN tile's
+// counters, the radius search's totals).  *dev stays null where the mapping is refused: the waits below then copy.
+// (pageable memory would make the read-back a staged copy)
+template <class T>
+static hipError_t alloc_mapped(T** host, T** dev) {
+  const hipError_t r = hipHostMalloc((void**)host, sizeof(T), hipHostMallocMapped);
+  if (r != hipSuccess) return r;
+  (*host)->seq = 0;
+  if (hipHostGetDevicePointer((void**)dev, *host, 0) != hipSuccess) { (void)hipGetLastError(); *dev = nullptr; }
+  return hipSuccess;
+}
+// Wait until the launch sequence numbered `seq` has published: poll the mapped sequence word (`poll`; returns ~10 us before
+// hipStreamSynchronize does), else -- polling switched off, no mapping, a long launch or a fault -- wait properly, after a
+// copy of `bytes` from d_src to h_dst where the kernels did not write through the mapping (d_src = null: they did).
+template <class T>
+static hipError_t wait_mapped(volatile T* seq_word, T seq, bool poll, void* h_dst, const void* d_src, size_t bytes, hipStream_t s) {
+  if (poll && poll_mapped_word(seq_word, seq)) return hipSuccess;
+  if (d_src) {
+    const hipError_t r = hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, s);
+    if (r != hipSuccess) return r;
+  }
+  return hipStreamSynchronize(s);
+}
+
+// entries of an average bucket: the expected cost of a probe
+static double avg_bucket(const VcMihIndex* ix) {
+  return (double)ix->n / (ix->sbits >= 32 ? 4294967296.0 : (double)(1ull << ix->sbits));
 }
 
 static hipError_t launch_probe(const ProbeParams& p, uint32_t W, uint32_t n_list, hipStream_t s) {
@@ -3146,8 +3216,30 @@ static hipError_t timed_launch(VcMihIndex* ix, hipStream_t s, F&& launch) {
   return r;
 }
 
-// launch + measurement: events on the launch stream around the kernel, then the reduction of its work counters
-static hipError_t timed_query_launch(VcMihIndex* ix, const QueryKernelParams& p_in, uint32_t W, uint32_t nq, hipStream_t s) {
+// dev knob VC_MIH_PHASES: the query kernel's phase clocks (QueryKernelParams::phase_dbg) of one launch on stderr
+static void print_query_phases(const unsigned long long* d_phase, uint32_t r_last, uint32_t nq, hipStream_t s) {
+  unsigned long long h[128];
+  if (hipMemcpyAsync(h, d_phase, 1024, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess) {
+    fprintf(stderr, "[vc_mih lifetimes] stop shell: blocks, mean lifetime us, last end (us after the first block's start):");
+    for (int c = 0; c < 6; ++c)
+      if (h[16 + c]) fprintf(stderr, "  %s%d: %llu, %.1f, %.1f", c == 5 ? "handed over after " : "", c == 5 ? (int)r_last : c, h[16 + c], h[8 + c] * 0.01 / h[16 + c], (h[25 + c] - h[24]) * 0.01);
+    fprintf(stderr, "\n");
+    for (int c = 0; c < 6; ++c)
+      if (h[16 + c]) {
+        const unsigned long long* q = h + 32 + c * 8;
+        const double nb = (double)h[16 + c];
+        fprintf(stderr, "[vc_mih phases] %s%d (%llu blocks), us per block: set-up %.1f | plan+scan %.1f | directory %.1f | verify %.1f | evaluate %.1f | finish %.1f | out %.1f\n",
+                c == 5 ? "handed over after " : "stop shell ", c == 5 ? (int)r_last : c, h[16 + c], (q[7] + q[0]) * 0.01 / nb, q[1] * 0.01 / nb,
+                q[2] * 0.01 / nb, q[3] * 0.01 / nb, q[4] * 0.01 / nb, q[5] * 0.01 / nb, q[6] * 0.01 / nb);
+      }
+  }
+  fprintf(stderr, "[vc_mih phases] %u blocks, us per block: set-up %.1f | plan+scan %.1f | directory %.1f | verify %.1f | evaluate %.1f | finish %.1f | out %.1f\n", nq,
+            (h[7] + h[0]) * 0.01 / nq, h[1] * 0.01 / nq, h[2] * 0.01 / nq, h[3] * 0.01 / nq, h[4] * 0.01 / nq, h[5] * 0.01 / nq, h[6] * 0.01 / nq);
+}
+
+// launch + measurement: events on the launch stream around the kernel, then the reduction of its work counters.
+// `ctr`: the tile's counter block of a k-NN launch (p.heavy_ctr and p.radius_hist point into it), null for the radius search
+static hipError_t timed_query_launch(VcMihIndex* ix, const QueryKernelParams& p_in, MihCounters* ctr, uint32_t W, uint32_t nq, hipStream_t s) {
   QueryKernelParams p = p_in;
   static unsigned long long* d_phase = nullptr;   // dev knob VC_MIH_PHASES: one buffer per process is enough
   if (ix->knobs.mih_phases && p.mode != MQ_MODE_RADIUS) {
@@ -3167,31 +3259,12 @@ static hipError_t timed_query_launch(VcMihIndex* ix, const QueryKernelParams& p_
   // 10 % slower than on 128-bit granules, 0.81 vs 0.89 M queries/s: r04_sweeps.md)
   hipError_t r = timed_launch(ix, s, [&] { return launch_query_kernel(p, W, nq, s); });
   if (r != hipSuccess) return r;
-  // (k-NN launches: heavy_ctr = the tile's counter block + 2.  Radius search has no counters to publish, and its work
-  // counters are summed by vc_radius_offsets_kernel, which follows anyway)
+  // (k-NN launches: the reduce kernel publishes the tile's counter block.  Radius search has no counters to publish, and its
+  // work counters are summed by vc_radius_offsets_kernel, which follows anyway)
   if (p.mode != MQ_MODE_RADIUS)
-    hipLaunchKernelGGL(mih_work_reduce_kernel, dim3(2), dim3(1024), 0, s, p.st.work, nq, ix->d_totals,
-                     p.heavy_ctr ? p.heavy_ctr - 2 : (uint32_t*)nullptr,
-                     p.heavy_ctr ? (volatile uint32_t*)ix->h_ctr_dev : (volatile uint32_t*)nullptr, ++ix->ctr_seq);
-  if (p.phase_dbg) {
-    unsigned long long h[128];
-    if (hipMemcpyAsync(h, p.phase_dbg, 1024, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess) {
-      fprintf(stderr, "[vc_mih lifetimes] stop shell: blocks, mean lifetime us, last end (us after the first block's start):");
-      for (int c = 0; c < 6; ++c)
-        if (h[16 + c]) fprintf(stderr, "  %s%d: %llu, %.1f, %.1f", c == 5 ? "handed over after " : "", c == 5 ? (int)p.r_last : c, h[16 + c], h[8 + c] * 0.01 / h[16 + c], (h[25 + c] - h[24]) * 0.01);
-      fprintf(stderr, "\n");
-      for (int c = 0; c < 6; ++c)
-        if (h[16 + c]) {
-          const unsigned long long* q = h + 32 + c * 8;
-          const double nb = (double)h[16 + c];
-          fprintf(stderr, "[vc_mih phases] %s%d (%llu blocks), us per block: set-up %.1f | plan+scan %.1f | directory %.1f | verify %.1f | evaluate %.1f | finish %.1f | out %.1f\n",
-                  c == 5 ? "handed over after " : "stop shell ", c == 5 ? (int)p.r_last : c, h[16 + c], (q[7] + q[0]) * 0.01 / nb, q[1] * 0.01 / nb,
-                  q[2] * 0.01 / nb, q[3] * 0.01 / nb, q[4] * 0.01 / nb, q[5] * 0.01 / nb, q[6] * 0.01 / nb);
-        }
-    }
-    fprintf(stderr, "[vc_mih phases] %u blocks, us per block: set-up %.1f | plan+scan %.1f | directory %.1f | verify %.1f | evaluate %.1f | finish %.1f | out %.1f\n", nq,
-              (h[7] + h[0]) * 0.01 / nq, h[1] * 0.01 / nq, h[2] * 0.01 / nq, h[3] * 0.01 / nq, h[4] * 0.01 / nq, h[5] * 0.01 / nq, h[6] * 0.01 / nq);
-  }
+    hipLaunchKernelGGL(mih_work_reduce_kernel, dim3(2), dim3(1024), 0, s, p.st.work, nq, ix->d_totals, (uint32_t*)ctr,
+                     ctr ? (volatile uint32_t*)ix->h_ctr_dev : (volatile uint32_t*)nullptr, ++ix->ctr_seq);
+  if (p.phase_dbg) print_query_phases(p.phase_dbg, p.r_last, nq, s);
   return hipGetLastError();
 }
 
@@ -3211,6 +3284,39 @@ static uint32_t stream_resident_blocks(uint32_t W, uint32_t n_cu) {
   return per_cu[W] * n_cu;
 }
 
+// dev knob VC_STREAM_TRACE: when do the blocks of a stream launch start, finish their probe look-up and end?  (us after the
+// first block's start; d_trace: per block start | probes looked up | end, 10 ns ticks)
+static void print_stream_trace(const unsigned long long* d_trace, uint32_t nblocks, uint32_t nq, uint32_t split, hipStream_t s) {
+  std::vector<unsigned long long> h((size_t)nblocks * 3);
+  if (hipMemcpyAsync(h.data(), d_trace, h.size() * 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return;
+  unsigned long long t0 = ~0ull;
+  for (uint32_t b = 0; b < nblocks; ++b) t0 = std::min(t0, h[3 * b]);
+  std::vector<double> st, lk, en, life;
+  for (uint32_t b = 0; b < nblocks; ++b) {
+    st.push_back((h[3 * b] - t0) * 0.01);
+    lk.push_back((h[3 * b + 1] - h[3 * b]) * 0.01);
+    en.push_back((h[3 * b + 2] - t0) * 0.01);
+    life.push_back((h[3 * b + 2] - h[3 * b]) * 0.01);
+  }
+  auto pr = [&](const char* name, std::vector<double> v) {
+    std::sort(v.begin(), v.end());
+    auto q = [&](double f) { return v[(size_t)(f * (v.size() - 1))]; };
+    fprintf(stderr, "[stream trace] %-10s min/p10/p50/p90/p99/max us: %.1f %.1f %.1f %.1f %.1f %.1f\n", name, q(0), q(.1), q(.5), q(.9), q(.99), q(1));
+  };
+  fprintf(stderr, "[stream trace] %u blocks (%u queries x %u parts)\n", nblocks, nq, split);
+  pr("start", st); pr("look-up", lk); pr("end", en); pr("lifetime", life);
+  // blocks alive over time (20 samples of the launch's span)
+  const double span = *std::max_element(en.begin(), en.end());
+  fprintf(stderr, "[stream trace] blocks alive at 5%%..100%% of %.1f us:", span);
+  for (int i = 1; i <= 20; ++i) {
+    const double t = span * i / 20.0 - 1e-9;
+    uint32_t alive = 0;
+    for (uint32_t b = 0; b < nblocks; ++b) alive += st[b] <= t && en[b] > t;
+    fprintf(stderr, " %u", alive);
+  }
+  fprintf(stderr, "\n");
+}
+
 static hipError_t timed_stream_launch(VcMihIndex* ix, StreamParams sp, uint32_t W, uint32_t nq, hipStream_t s) {
   if (!ix->d_stotals) {
     hipError_t r = hipMalloc((void**)&ix->d_stotals, MS_TOT_LINES * 128);
@@ -3218,10 +3324,9 @@ static hipError_t timed_stream_launch(VcMihIndex* ix, StreamParams sp, uint32_t 
     if (r != hipSuccess) return r;
   }
   sp.totals = ix->d_stotals;
-  static const bool dev_trace = getenv("VC_STREAM_TRACE") != nullptr;   // dev: per-block start / look-up / end times on stderr
   const uint32_t nblocks = nq * sp.split;
   unsigned long long* d_trace = nullptr;
-  if (dev_trace && hipMalloc((void**)&d_trace, (size_t)nblocks * 24) == hipSuccess) {
+  if (ix->knobs.stream_trace && hipMalloc((void**)&d_trace, (size_t)nblocks * 24) == hipSuccess) {
     (void)hipMemsetAsync(d_trace, 0, (size_t)nblocks * 24, s);
     sp.trace = d_trace;
   }
@@ -3231,36 +3336,8 @@ static hipError_t timed_stream_launch(VcMihIndex* ix, StreamParams sp, uint32_t 
       return hipGetLastError();
     });
   });
-  if (d_trace) {   // dev: when do the blocks start, finish their probe look-up and end?  (us after the first block's start)
-    std::vector<unsigned long long> h((size_t)nblocks * 3);
-    if (hipMemcpyAsync(h.data(), d_trace, h.size() * 8, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess) {
-      unsigned long long t0 = ~0ull;
-      for (uint32_t b = 0; b < nblocks; ++b) t0 = std::min(t0, h[3 * b]);
-      std::vector<double> st, lk, en, life;
-      for (uint32_t b = 0; b < nblocks; ++b) {
-        st.push_back((h[3 * b] - t0) * 0.01);
-        lk.push_back((h[3 * b + 1] - h[3 * b]) * 0.01);
-        en.push_back((h[3 * b + 2] - t0) * 0.01);
-        life.push_back((h[3 * b + 2] - h[3 * b]) * 0.01);
-      }
-      auto pr = [&](const char* name, std::vector<double> v) {
-        std::sort(v.begin(), v.end());
-        auto q = [&](double f) { return v[(size_t)(f * (v.size() - 1))]; };
-        fprintf(stderr, "[stream trace] %-10s min/p10/p50/p90/p99/max us: %.1f %.1f %.1f %.1f %.1f %.1f\n", name, q(0), q(.1), q(.5), q(.9), q(.99), q(1));
-      };
-      fprintf(stderr, "[stream trace] %u blocks (%u queries x %u parts)\n", nblocks, nq, sp.split);
-      pr("start", st); pr("look-up", lk); pr("end", en); pr("lifetime", life);
-      // blocks alive over time (20 samples of the launch's span)
-      const double span = *std::max_element(en.begin(), en.end());
-      fprintf(stderr, "[stream trace] blocks alive at 5%%..100%% of %.1f us:", span);
-      for (int i = 1; i <= 20; ++i) {
-        const double t = span * i / 20.0 - 1e-9;
-        uint32_t alive = 0;
-        for (uint32_t b = 0; b < nblocks; ++b) alive += st[b] <= t && en[b] > t;
-        fprintf(stderr, " %u", alive);
-      }
-      fprintf(stderr, "\n");
-    }
+  if (d_trace) {
+    print_stream_trace(d_trace, nblocks, nq, sp.split, s);
     (void)hipFree(d_trace);
   }
   return r;
@@ -3359,243 +3436,331 @@ __global__ void __launch_bounds__(256) mih_set_radius_kernel(uint32_t* __restric
 }
 
 uint32_t vc_mih_knn_reach(const VcMihIndex* ix) {
-  const double avg_bucket = (double)ix->n / (ix->sbits >= 32 ? 4294967296.0 : (double)(1ull << ix->sbits));
-  return inblock_last_shell(ix->sbits, ix->m, ix->knobs.mih_budget ? ix->knobs.mih_budget : MQ_KNN_BUDGET, ix->sbits, avg_bucket);
+  return inblock_last_shell(ix->sbits, ix->m, ix->knobs.mih_budget ? ix->knobs.mih_budget : MQ_KNN_BUDGET, ix->sbits, avg_bucket(ix));
 }
 
-int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint64_t n, const uint64_t* d_q, uint32_t nq,
-                  uint32_t k, bool approximate, uint64_t* d_out, uint32_t* d_cnt, vc_query_stats* host_stats, hipStream_t s,
-                  std::string* err, const VcMihScanFallback* fb, vc_query_stats* d_stats, uint32_t r_cap) {
-  const bool stats = host_stats != nullptr || d_stats != nullptr;   // the cost model prices the statistics pass either way
-  if (n != ix->n) return fail(err, VC_ERR_STATE, "index is stale: codes were added after vc_build_index()");
-  int rc = upload_binom(err);
-  if (rc) return rc;
-  const uint32_t cap = std::max(ix->cap, 4 * k);
-  const uint32_t S = ix->sbits;
-  // stop multiplier: the reference's literal 4 (search_worker.cc:204); min(m,4) keeps m < 4 exact
-  const uint32_t stop_mult = (ix->flags & VC_FLAG_REF_STOP_LITERAL4) ? 4u : std::min(ix->m, 4u);
-  MihState st;
-  if (!ix->h_ctr) {
-    MIH_CHECK(hipHostMalloc((void**)&ix->h_ctr, 64, hipHostMallocMapped));
-    ix->h_ctr[8] = 0;
-    if (hipHostGetDevicePointer((void**)&ix->h_ctr_dev, ix->h_ctr, 0) != hipSuccess) { (void)hipGetLastError(); ix->h_ctr_dev = nullptr; }
-  }   // pageable memory makes the read-back a staged copy
-  uint32_t* h_ctr = ix->h_ctr;
+// the fields of the kernels' parameter blocks that follow from the index and the database; the callers set the rest
+static QueryKernelParams query_kernel_params(const VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, const MihState& st) {
+  QueryKernelParams p{};
+  p.cols = d_cols; p.stride = stride; p.n = ix->n; p.tables = ix->d_tables;
+  p.st = st; p.m = ix->m; p.sbits = ix->sbits; p.id_base = ix->id_base; p.flags = ix->flags;
+  return p;
+}
+static ProbeParams probe_params(const VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, const MihState& st, uint32_t r) {
+  ProbeParams p{};
+  p.cols = d_cols; p.stride = stride; p.tables = ix->d_tables;
+  p.st = st; p.r = r; p.nkeys = binom_host(ix->sbits, r); p.m = ix->m; p.sbits = ix->sbits; p.id_base = ix->id_base;
+  p.flags = ix->flags; p.n = ix->n;
+  return p;
+}
 
+// What one vc_mih_search call decides before its first launch.
+struct KnnPlan {
+  uint32_t cap;           // entries of a candidate ring
+  uint32_t stop_mult;     // stop multiplier: the reference's literal 4 (search_worker.cc:204); min(m,4) keeps m < 4 exact
+  uint32_t buf_entries;   // candidates of one query-kernel block: up to k of every shell class of a grouped pass + one round of survivors
+  bool inblock;           // shells 0..r_last run in mih_query_kernel (else every shell runs through the multi-block kernels)
+  uint32_t tile;          // queries of a launch
+  bool capped;            // capped run (the rounds of the sharded global stop, vc_sharded.hip): shells 0..r_cap with the stop rule active, no switch
+  uint32_t r_end;         // last shell of the call
+  uint32_t r_last;        // last shell of the query kernel
+  bool switch_ok;         // the cost model may hand queries to the verify kernel
+  uint32_t group;         // shells that share the query kernel's first pass
+};
+
+static KnnPlan knn_plan(const VcMihIndex* ix, uint64_t n, uint32_t nq, uint32_t k, bool approximate, const VcMihScanFallback* fb, uint32_t r_cap) {
+  KnnPlan pl{};
+  const uint32_t S = ix->sbits;
+  pl.cap = std::max(ix->cap, 4 * k);
+  pl.stop_mult = (ix->flags & VC_FLAG_REF_STOP_LITERAL4) ? 4u : std::min(ix->m, 4u);
   // Shells 0..r_last run inside ONE launch, one block per query (mih_query_kernel); the host reads ONE counter per
   // tile (how many queries are not finished) and only those continue shell by shell through the multi-block kernels.
-  uint32_t buf_entries = 1024;     // candidates of one block: up to k of every shell class of a grouped pass + one round of survivors
-  while (buf_entries < MQ_MAX_GROUP * k + MQ_ROUND) buf_entries <<= 1;
+  pl.buf_entries = 1024;
+  while (pl.buf_entries < MQ_MAX_GROUP * k + MQ_ROUND) pl.buf_entries <<= 1;
   // the query kernel's LDS request (top-k + candidate buffer, hit lists, binomials, masks) must fit a workgroup of this
   // device (k = 3073..7168 asks for ~82 KB); otherwise every shell runs through the multi-block kernels
-  const bool inblock = ix->knobs.mih_host_loop == 0 && buf_entries <= 8192 && ix->m <= 64 &&
-                       query_kernel_lds(buf_entries, ix->m, S, ix->W, MQ_LO_KNN) <= ix->lds_per_block;
+  pl.inblock = ix->knobs.mih_host_loop == 0 && pl.buf_entries <= 8192 && ix->m <= 64 &&
+               query_kernel_lds(pl.buf_entries, ix->m, S, ix->W, MQ_LO_KNN) <= ix->lds_per_block;
   // the call's queries in as few launches as the tile limit allows, equally filled (20 000 queries = 2 x 10 000, not 16 384 + 3 616)
   const uint32_t QM = qtile_max(ix);
   const uint32_t n_tiles = std::max(1u, (nq + QM - 1) / QM);
-  const uint32_t tile = std::max(64u, std::min(QM, (((nq + n_tiles - 1) / n_tiles) + 63u) & ~63u));
-  if ((rc = ensure_tile(ix, tile, k, cap, !inblock, &st, err))) return rc;
-  uint32_t* lists[4] = {ix->d_lists, ix->d_lists + QM, ix->d_lists + 2 * QM, ix->d_lists + 3 * QM};
-  uint32_t* d_ctr = ix->d_lists + 4 * QM;
-  const double avg_bucket = (double)ix->n / (S >= 32 ? 4294967296.0 : (double)(1ull << S));
+  pl.tile = std::max(64u, std::min(QM, (((nq + n_tiles - 1) / n_tiles) + 63u) & ~63u));
   // One block per query: a small batch leaves most of the chip idle while a few blocks walk a big shell, so the probe
   // budget per query shrinks with the batch (a lone query runs shells 0..2 in its block -- 2 116 probes at m = 4 -- and
   // the bigger ones through the multi-block kernels, which spread a shell over all CUs).
   uint64_t knn_budget = MQ_KNN_BUDGET;
   if (nq < 1024) knn_budget = std::max<uint64_t>(2500, MQ_KNN_BUDGET * nq / 1024);
   if (ix->knobs.mih_budget) knn_budget = ix->knobs.mih_budget;   // dev knob VC_MIH_BUDGET
-  // capped run (the rounds of the sharded global stop, vc_sharded.hip): shells 0..r_cap with the stop rule active, no switch
-  const bool capped = r_cap < S;
-  const uint32_t r_end = capped ? r_cap : S;
-  const uint32_t r_last = inblock_last_shell(S, ix->m, knn_budget, r_end, avg_bucket);
-  const bool trace = ix->knobs.mih_trace;   // VC_MIH_TRACE: per-shell wall times on stderr
+  pl.capped = r_cap < S;
+  pl.r_end = pl.capped ? r_cap : S;
+  pl.r_last = inblock_last_shell(S, ix->m, knn_budget, pl.r_end, avg_bucket(ix));
   // the scan switch reproduces the radius loop only where that loop is exact and its counters have a closed form
-  const bool switch_ok = !approximate && !capped && ix->knobs.mih_switch != 0 &&
-                         !(ix->flags & (VC_FLAG_USE_BITMAP | VC_FLAG_REF_SIGNEXT_KEYS)) && stop_mult == std::min(ix->m, 4u) && n >= 1;
+  pl.switch_ok = fb && fb->fn && !approximate && !pl.capped && ix->knobs.mih_switch != 0 &&
+                 !(ix->flags & (VC_FLAG_USE_BITMAP | VC_FLAG_REF_SIGNEXT_KEYS)) && pl.stop_mult == std::min(ix->m, 4u) && n >= 1;
   // Shells that share the FIRST pass of the query kernel (32-bit substrings): their candidates are tagged by shell and the
   // stop rule is evaluated shell by shell afterwards, so grouping changes no result and no statistic -- it saves a scan /
   // drain round per grouped shell and wastes the probes of the shells behind the one a query stops in.  The depth follows
   // the workload: the kernel counts where the queries of a launch stopped, and the next launch groups up to the shell
   // most of them needed (at most 3; VC_MIH_GROUP fixes it).
-  uint32_t group = ix->knobs.mih_group > 0 ? (uint32_t)ix->knobs.mih_group : ix->group_hint;
-  group = std::max(1u, std::min(group, std::min(3u, r_last + 1)));
+  pl.group = ix->knobs.mih_group > 0 ? (uint32_t)ix->knobs.mih_group : ix->group_hint;
+  pl.group = std::max(1u, std::min(pl.group, std::min(3u, pl.r_last + 1)));
+  return pl;
+}
 
-  for (uint32_t q0 = 0; q0 < nq; q0 += tile) {
-    const uint32_t qt = std::min(tile, nq - q0);
-    // the queries in[0 .. n_in) answered by the scan now, stop rule replayed; those it cannot settle (ring overflow, too many
-    // ties) are written to `back`, and *n_back says how many
-    auto scan_handoff = [&](const uint32_t* in, uint32_t n_in, uint32_t* back, uint32_t* n_back) -> int {
-      VcMihScanTarget tgt{st.ring, cap, st.count, st.radius, st.seen, st.sub, st.loc};
-      MIH_CHECK(hipMemsetAsync(d_ctr, 0, 4, s));
-      const int frc = fb->fn(fb->ctx, d_q + (size_t)q0 * ix->W, in, n_in, k, stop_mult, tgt, stats, back, d_ctr, s);
-      if (frc) return fail(err, frc, "scan fallback of the exact k-NN loop failed");
-      MIH_CHECK(hipMemcpyAsync(h_ctr, d_ctr, 4, hipMemcpyDeviceToHost, s));
-      MIH_CHECK(hipStreamSynchronize(s));
-      *n_back = h_ctr[0];
-      return VC_OK;
-    };
-    uint32_t *cur = lists[0], *nxt = lists[1], *redo = lists[2];
-    uint32_t n_cur = qt, r_start = 0, n_heavy = qt;
-    if (inblock) {
-      QueryKernelParams qp{};
-      qp.cols = d_cols; qp.stride = stride; qp.n = ix->n; qp.tables = ix->d_tables; qp.queries = d_q + (size_t)q0 * ix->W;
-      qp.st = st; qp.m = ix->m; qp.sbits = S; qp.id_base = ix->id_base; qp.flags = ix->flags; qp.cap = cap; qp.k = k;
-      qp.mode = approximate ? MQ_MODE_APPROX : MQ_MODE_EXACT; qp.stop_mult = stop_mult; qp.r_last = r_last;
-      qp.buf_entries = buf_entries; qp.heavy_list = cur; qp.heavy_ctr = d_ctr + 2;
-      qp.out = d_out + (size_t)q0 * k; qp.out_cnt = d_cnt + q0; qp.group = group; qp.radius_hist = d_ctr + 4;
-      qp.use_lines = (S == 32 && !ix->h_tables.empty() && ix->h_tables[0].lines) ? 1u : 0u;
-      // (r04, same box: the query kernel 0.353 -> 0.319 ms per 4096 queries at 1e9, 0.277 -> 0.269 ms at 1e8, for a pre-pass of
-      // ~3 us; VC_MIH_ORDER=0 switches it off)
-      const bool want_order = ix->knobs.mih_order != 0;
-      if (want_order && qt >= 4 * ix->n_cu * 2 && ix->m <= MO_BLK) {   // at least two residency waves of blocks: a launch order matters
-        uint32_t* d_order = d_ctr + 16;
-        const uint32_t per_block = MO_BLK / ix->m;
-        hipLaunchKernelGGL(mih_order_kernel, dim3((qt + per_block - 1) / per_block), dim3(MO_BLK), 0, s, (const VcTableView*)ix->d_tables,
-                           d_q + (size_t)q0 * ix->W, ix->W, ix->m, S, qt, d_order);
-        MIH_CHECK(hipGetLastError());
-        qp.order = d_order;
-      }
-      const auto t_q = std::chrono::steady_clock::now();
-      if (!ix->h_ctr_dev) MIH_CHECK(hipMemsetAsync(d_ctr, 0, 32, s));   // (else zeroed at allocation and by every reduce kernel since)
-      MIH_CHECK(timed_query_launch(ix, qp, ix->W, qt, s));
-      // unfinished queries + where the others stopped: published by the reduce kernel into mapped host memory, sequence
-      // number last; polling that word returns ~10 us before hipStreamSynchronize does (VC_MIH_POLL=0: plain synchronise)
-      bool landed = false;
-      if (ix->h_ctr_dev && ix->knobs.mih_poll) {
-        landed = poll_mapped_word((volatile uint32_t*)(h_ctr + 8), (uint32_t)ix->ctr_seq);   // long launches (or a fault): wait properly
-      }
-      if (!ix->h_ctr_dev) MIH_CHECK(hipMemcpyAsync(h_ctr + 2, d_ctr + 2, 24, hipMemcpyDeviceToHost, s));
-      if (!landed) MIH_CHECK(hipStreamSynchronize(s));
-      n_heavy = n_cur = h_ctr[2];
-      if (S == 32 && qt >= 64 && !capped)   // next launch: group up to shell 2 when most queries of this one needed it
-        ix->group_hint = (uint64_t)(h_ctr[6] + h_ctr[7]) * 10 >= (uint64_t)qt * 6 ? 3u : 2u;
-      r_start = r_last + 1;
-      if (trace)
-        fprintf(stderr, "[vc_mih] shells 0..%u in the query kernel (group %u): %u queries, %u continue, stopped in shell 0/1/2/later %u/%u/%u/%u  %.1f us\n",
-                r_last, group, qt, n_cur, h_ctr[4], h_ctr[5], h_ctr[6], h_ctr[7],
-                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_q).count());
-      if (n_heavy) {
-        MIH_CHECK(hipMemcpyAsync(lists[3], cur, (size_t)n_heavy * 4, hipMemcpyDeviceToDevice, s));
-        if ((rc = ensure_tile(ix, tile, k, cap, true, &st, err))) return rc;   // the rings exist from the first hand-over on
-        hipLaunchKernelGGL(mih_seed_ring_kernel, dim3(n_heavy), dim3(256), 0, s, st, (const uint32_t*)cur, k, cap);
-        MIH_CHECK(hipGetLastError());
-        if (capped && r_last == r_end) {   // the kernel ran every shell of the cap: the open queries end here
-          hipLaunchKernelGGL(mih_set_radius_kernel, dim3((n_heavy + 255) / 256), dim3(256), 0, s, st.radius, (const uint32_t*)cur, n_heavy, r_end);
-          MIH_CHECK(hipGetLastError());
-          n_cur = 0;
-        }
-        if (fb && fb->fn && switch_ok) {
-          // Cost model, per query: the hand-over left an upper bound of the probes each query may still need (its k-th
-          // distance so far bounds its last shell).  The multi-block kernels sustain ~4e10 probes/s; the verify kernel's price per
-          // query is scan_cost_s's (x 2.5 with the statistics pass).  Queries beyond the break-even are answered
-          // by the scan NOW, stop rule replayed (mih_replay_kernel) -- the others keep their radius loop.
-          const double limit = ix->knobs.mih_switch == 2 ? -1.0 : scan_cost_s(n, ix->W, 32) / 32 * (stats ? 2.5 : 1.0) * 4e10;
-          MIH_CHECK(hipMemsetAsync(d_ctr, 0, 8, s));
-          hipLaunchKernelGGL(mih_partition_kernel, dim3((n_heavy + 255) / 256), dim3(256), 0, s, (const uint32_t*)cur, n_heavy, st.work,
-                             limit < 0 ? 0ull : (unsigned long long)limit, nxt, redo, d_ctr);
-          MIH_CHECK(hipGetLastError());
-          MIH_CHECK(hipMemcpyAsync(h_ctr, d_ctr, 8, hipMemcpyDeviceToHost, s));
-          MIH_CHECK(hipStreamSynchronize(s));
-          const uint32_t n_scan = h_ctr[0], n_keep = h_ctr[1];
-          if (n_scan) {
-            // unresolved queries (ring overflow, too many ties) rejoin the radius loop: appended behind the kept ones
-            uint32_t n_back = 0;
-            if ((rc = scan_handoff(nxt, n_scan, redo + n_keep, &n_back))) return rc;
-            if (trace) fprintf(stderr, "[vc_mih] cost model: %u of %u unfinished queries answered by the verify kernel, %u came back\n", n_scan, n_heavy, n_back);
-            n_cur = n_keep + n_back;
-            std::swap(cur, redo);          // the radius loop goes on with the kept (+ unresolved) queries
-          }
-        }
-      }
-    } else {
-      hipLaunchKernelGGL(mih_init_kernel, dim3((qt + 255) / 256), dim3(256), 0, s, st, qt, cur, (uint64_t)VC_PACK_INF);
+// One tile of a k-NN call on its way through the steps below: which list is live (roles: see MihLists) and how long it is.
+struct KnnTile {
+  uint32_t q0, qt;              // the call's queries q0 .. q0 + qt
+  uint32_t *cur, *nxt, *redo;
+  uint32_t n_cur;               // open queries (entries of cur)
+  uint32_t n_heavy;             // queries whose rows come from the multi-block state: those the query kernel handed over (or all)
+  uint32_t r_start;             // first shell of the multi-block loop
+};
+
+// The arguments of one vc_mih_search call and the steps of its tile loop, in the order vc_mih_search takes them.
+struct KnnSearch {
+  VcMihIndex* ix;
+  const uint64_t* d_cols;
+  uint64_t stride, n;
+  const uint64_t* d_q;
+  uint32_t k;
+  bool approximate, stats;      // stats: the cost model prices the statistics pass whether it goes to the host or stays on the device
+  uint64_t* d_out;
+  uint32_t* d_cnt;
+  const VcMihScanFallback* fb;
+  hipStream_t s;
+  std::string* err;
+  KnnPlan pl;
+  MihState st;                  // (ensure_tile: the ring joins it at the first hand-over)
+  MihLists ls;
+
+  const uint64_t* queries(const KnnTile& t) const { return d_q + (size_t)t.q0 * ix->W; }
+
+  // shells 0..r_last of every query of the tile in one launch; afterwards cur holds the queries that are not finished
+  int run_query_kernel(KnnTile& t) {
+    const bool trace = ix->knobs.mih_trace;   // VC_MIH_TRACE: per-shell wall times on stderr
+    QueryKernelParams qp = query_kernel_params(ix, d_cols, stride, st);
+    qp.queries = queries(t); qp.cap = pl.cap; qp.k = k;
+    qp.mode = approximate ? MQ_MODE_APPROX : MQ_MODE_EXACT; qp.stop_mult = pl.stop_mult; qp.r_last = pl.r_last;
+    qp.buf_entries = pl.buf_entries; qp.heavy_list = t.cur; qp.heavy_ctr = &ls.ctr->heavy;
+    qp.out = d_out + (size_t)t.q0 * k; qp.out_cnt = d_cnt + t.q0; qp.group = pl.group; qp.radius_hist = ls.ctr->stop_hist;
+    qp.use_lines = (ix->sbits == 32 && !ix->h_tables.empty() && ix->h_tables[0].lines) ? 1u : 0u;
+    // (r04, same box: the query kernel 0.353 -> 0.319 ms per 4096 queries at 1e9, 0.277 -> 0.269 ms at 1e8, for a pre-pass of
+    // ~3 us; VC_MIH_ORDER=0 switches it off)
+    const bool want_order = ix->knobs.mih_order != 0;
+    if (want_order && t.qt >= 4 * ix->n_cu * 2 && ix->m <= MO_BLK) {   // at least two residency waves of blocks: a launch order matters
+      const uint32_t per_block = MO_BLK / ix->m;
+      hipLaunchKernelGGL(mih_order_kernel, dim3((t.qt + per_block - 1) / per_block), dim3(MO_BLK), 0, s, (const VcTableView*)ix->d_tables,
+                         queries(t), ix->W, ix->m, ix->sbits, t.qt, ls.order);
       MIH_CHECK(hipGetLastError());
+      qp.order = ls.order;
+    }
+    const auto t_q = std::chrono::steady_clock::now();
+    if (!ix->h_ctr_dev) MIH_CHECK(hipMemsetAsync(ls.ctr, 0, MIH_CTR_LAUNCH_BYTES, s));   // (else zeroed at allocation and by every reduce kernel since)
+    MIH_CHECK(timed_query_launch(ix, qp, ls.ctr, ix->W, t.qt, s));
+    // unfinished queries + where the others stopped: published by the reduce kernel into mapped host memory, sequence
+    // number last; polling that word returns ~10 us before hipStreamSynchronize does (VC_MIH_POLL=0: plain synchronise)
+    const MihCounters* h = ix->h_ctr;
+    MIH_CHECK(wait_mapped((volatile uint32_t*)&ix->h_ctr->seq, (uint32_t)ix->ctr_seq, ix->h_ctr_dev && ix->knobs.mih_poll, &ix->h_ctr->heavy,
+                          ix->h_ctr_dev ? nullptr : &ls.ctr->heavy, MIH_CTR_PUBLISHED_BYTES, s));
+    t.n_heavy = t.n_cur = h->heavy;
+    if (ix->sbits == 32 && t.qt >= 64 && !pl.capped)   // next launch: group up to shell 2 when most queries of this one needed it
+      ix->group_hint = (uint64_t)(h->stop_hist[2] + h->stop_hist[3]) * 10 >= (uint64_t)t.qt * 6 ? 3u : 2u;
+    t.r_start = pl.r_last + 1;
+    if (trace)
+      fprintf(stderr, "[vc_mih] shells 0..%u in the query kernel (group %u): %u queries, %u continue, stopped in shell 0/1/2/later %u/%u/%u/%u  %.1f us\n",
+              pl.r_last, pl.group, t.qt, t.n_cur, h->stop_hist[0], h->stop_hist[1], h->stop_hist[2], h->stop_hist[3],
+              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_q).count());
+    return VC_OK;
+  }
+
+  // every shell through the multi-block kernels (no query kernel): all queries of the tile start open, in cur
+  int open_all(KnnTile& t) {
+    hipLaunchKernelGGL(mih_init_kernel, dim3((t.qt + 255) / 256), dim3(256), 0, s, st, t.qt, t.cur, (uint64_t)VC_PACK_INF);
+    MIH_CHECK(hipGetLastError());
+    return VC_OK;
+  }
+
+  // the queries the query kernel left unfinished (cur) move to the multi-block state: the list is kept for the export, their
+  // rings are seeded with what they found so far.  A capped run whose query kernel ran every shell of the cap ends here.
+  int hand_over(KnnTile& t) {
+    MIH_CHECK(hipMemcpyAsync(ls.list[3], t.cur, (size_t)t.n_heavy * 4, hipMemcpyDeviceToDevice, s));
+    int rc;
+    if ((rc = ensure_tile(ix, pl.tile, k, pl.cap, true, &st, &ls, err))) return rc;   // the rings exist from the first hand-over on
+    hipLaunchKernelGGL(mih_seed_ring_kernel, dim3(t.n_heavy), dim3(256), 0, s, st, (const uint32_t*)t.cur, k, pl.cap);
+    MIH_CHECK(hipGetLastError());
+    if (pl.capped && pl.r_last == pl.r_end) {   // the kernel ran every shell of the cap: the open queries end here
+      hipLaunchKernelGGL(mih_set_radius_kernel, dim3((t.n_heavy + 255) / 256), dim3(256), 0, s, st.radius, (const uint32_t*)t.cur, t.n_heavy, pl.r_end);
+      MIH_CHECK(hipGetLastError());
+      t.n_cur = 0;
+    }
+    return VC_OK;
+  }
+
+  // the queries in[0 .. n_in) answered by the scan now, stop rule replayed; those it cannot settle (ring overflow, too many
+  // ties) are written to `back`, and *n_back says how many
+  int scan_handoff(const KnnTile& t, const uint32_t* in, uint32_t n_in, uint32_t* back, uint32_t* n_back) {
+    VcMihScanTarget tgt{st.ring, pl.cap, st.count, st.radius, st.seen, st.sub, st.loc};
+    MIH_CHECK(hipMemsetAsync(&ls.ctr->next, 0, sizeof ls.ctr->next, s));
+    const int frc = fb->fn(fb->ctx, queries(t), in, n_in, k, pl.stop_mult, tgt, stats, back, &ls.ctr->next, s);
+    if (frc) return fail(err, frc, "scan fallback of the exact k-NN loop failed");
+    MIH_CHECK(hipMemcpyAsync(&ix->h_ctr->next, &ls.ctr->next, sizeof ls.ctr->next, hipMemcpyDeviceToHost, s));
+    MIH_CHECK(hipStreamSynchronize(s));
+    *n_back = ix->h_ctr->next;
+    return VC_OK;
+  }
+
+  // Cost model, per query: the hand-over left an upper bound of the probes each query may still need (its k-th
+  // distance so far bounds its last shell).  The multi-block kernels sustain ~4e10 probes/s; the verify kernel's price per
+  // query is scan_cost_s's (x 2.5 with the statistics pass).  Queries beyond the break-even are answered
+  // by the scan NOW, stop rule replayed (mih_replay_kernel) -- the others keep their radius loop.
+  int scan_costly_queries(KnnTile& t) {
+    const double limit = ix->knobs.mih_switch == 2 ? -1.0 : scan_cost_s(n, ix->W, 32) / 32 * (stats ? 2.5 : 1.0) * 4e10;
+    MIH_CHECK(hipMemsetAsync(ls.ctr, 0, offsetof(MihCounters, heavy), s));
+    hipLaunchKernelGGL(mih_partition_kernel, dim3((t.n_heavy + 255) / 256), dim3(256), 0, s, (const uint32_t*)t.cur, t.n_heavy, st.work,
+                       limit < 0 ? 0ull : (unsigned long long)limit, t.nxt, t.redo, &ls.ctr->next);
+    MIH_CHECK(hipGetLastError());
+    MIH_CHECK(hipMemcpyAsync(ix->h_ctr, ls.ctr, offsetof(MihCounters, heavy), hipMemcpyDeviceToHost, s));
+    MIH_CHECK(hipStreamSynchronize(s));
+    const uint32_t n_scan = ix->h_ctr->next, n_keep = ix->h_ctr->redo;
+    if (n_scan) {
+      // unresolved queries (ring overflow, too many ties) rejoin the radius loop: appended behind the kept ones
+      uint32_t n_back = 0;
+      int rc;
+      if ((rc = scan_handoff(t, t.nxt, n_scan, t.redo + n_keep, &n_back))) return rc;
+      if (ix->knobs.mih_trace) fprintf(stderr, "[vc_mih] cost model: %u of %u unfinished queries answered by the verify kernel, %u came back\n", n_scan, t.n_heavy, n_back);
+      t.n_cur = n_keep + n_back;
+      std::swap(t.cur, t.redo);          // the radius loop goes on with the kept (+ unresolved) queries
+    }
+    return VC_OK;
+  }
+
+  // Cost model: this shell alone is m * C(S, r) bucket probes per active query (the multi-block kernels sustain ~4e10
+  // probes/s plus ~40 us of launches and a host round trip per shell); the verify kernel costs scan_cost_s (x 2.5 when the
+  // statistics pass is wanted).  Beyond the break-even the remaining queries are
+  // answered by the scan with the stop rule replayed -- same rows, same statistics (see mih_replay_kernel).
+  // *switched: the scan has taken the open queries; cur holds those it could not settle
+  int scan_if_shell_costs_more(KnnTile& t, uint32_t r, bool* switched) {
+    const double est_mih = (double)t.n_cur * ix->m * binom_host(ix->sbits, r) / 4e10 + 40e-6;
+    const double est_scan = scan_cost_s(n, ix->W, t.n_cur) * (stats ? 2.5 : 1.0);
+    if (!(est_mih > est_scan || ix->knobs.mih_switch == 2)) return VC_OK;
+    uint32_t n_back = 0;
+    int rc;
+    if ((rc = scan_handoff(t, t.cur, t.n_cur, t.nxt, &n_back))) return rc;
+    if (ix->knobs.mih_trace) fprintf(stderr, "[vc_mih] shell r=%u: %u queries answered by the verify kernel (cost model), %u continue\n", r, t.n_cur - n_back, n_back);
+    t.n_cur = n_back;
+    std::swap(t.cur, t.nxt);
+    *switched = true;
+    return VC_OK;
+  }
+
+  // shell r of the open queries through the multi-block kernels: probe, select, commit, and again for the queries whose
+  // ring overflowed.  The queries that go on are in cur afterwards (the commit kernel fills nxt; swapped here).
+  int run_shell(KnnTile& t, uint32_t r) {
+    const auto t_shell = std::chrono::steady_clock::now();
+    ProbeParams p = probe_params(ix, d_cols, stride, st, r);
+    p.queries = queries(t); p.cap = pl.cap;
+    CommitParams c{};
+    c.st = st; c.next_list = t.nxt; c.redo_list = t.redo; c.ctr = &ls.ctr->next; c.k = k; c.cap = pl.cap; c.r = r; c.sbits = ix->sbits;
+    c.stop_mult = pl.stop_mult; c.approximate = approximate; c.last_shell = r == pl.r_end;
+    MIH_CHECK(hipMemsetAsync(ls.ctr, 0, offsetof(MihCounters, heavy), s));
+    MihCounters* h = ix->h_ctr;
+    const uint32_t* work = t.cur;
+    uint32_t n_work = t.n_cur;
+    h->next = h->redo = 0;
+    for (int round = 0;; ++round) {
+      p.list = work;
+      p.count_seen = round == 0;
+      MIH_CHECK(launch_probe(p, ix->W, n_work, s));
+      MIH_CHECK(vc_launch_select_ring_list(st.ring, pl.cap, st.count, work, n_work, k, st.topk, st.topn, s));
+      c.list = work;
+      hipLaunchKernelGGL(mih_commit_kernel, dim3(n_work), dim3(VC_WAVE), 0, s, c);
+      MIH_CHECK(hipGetLastError());
+      MIH_CHECK(hipMemcpyAsync(h, ls.ctr, offsetof(MihCounters, heavy), hipMemcpyDeviceToHost, s));
+      MIH_CHECK(hipStreamSynchronize(s));
+      if (h->redo == 0) break;
+      // overflowed queries go round again with their tightened limit; swap the redo list with a scratch list
+      if (round > 64) return fail(err, VC_ERR_CAPACITY, "MIH overflow recovery did not converge");
+      // `cur` has been fully consumed by this round: reuse it as the work list of the recovery round so the
+      // commit kernel can refill `redo`
+      n_work = h->redo;
+      MIH_CHECK(hipMemcpyAsync(t.cur, t.redo, (size_t)n_work * 4, hipMemcpyDeviceToDevice, s));
+      MIH_CHECK(hipMemsetAsync(&ls.ctr->redo, 0, sizeof ls.ctr->redo, s));
+      work = t.cur;
+    }
+    if (ix->knobs.mih_trace)
+      fprintf(stderr, "[vc_mih] shell r=%u keys=%u active=%u -> next=%u  %.1f us\n", r, p.nkeys, t.n_cur, h->next,
+              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_shell).count());
+    t.n_cur = h->next;
+    std::swap(t.cur, t.nxt);
+    return VC_OK;
+  }
+
+  // rows of the queries that went through the multi-block shells (the query kernel wrote the others itself)
+  int export_rows(const KnnTile& t) {
+    hipLaunchKernelGGL(mih_export_kernel, dim3(t.n_heavy), dim3(256), 0, s, st, pl.inblock ? (const uint32_t*)ls.list[3] : (const uint32_t*)nullptr, k, pl.cap,
+                       d_out + (size_t)t.q0 * k, d_cnt + t.q0);
+    MIH_CHECK(hipGetLastError());
+    return VC_OK;
+  }
+
+  int export_stats_dev(const KnnTile& t, vc_query_stats* d_stats) {
+    hipLaunchKernelGGL(mih_stats_export_kernel, dim3((t.qt + 255) / 256), dim3(256), 0, s, st, (const uint32_t*)(d_cnt + t.q0), t.qt, d_stats + t.q0);
+    MIH_CHECK(hipGetLastError());
+    return VC_OK;
+  }
+
+  int export_stats_host(const KnnTile& t, vc_query_stats* host_stats) {
+    const uint32_t qt = t.qt;
+    std::vector<unsigned long long> seen(qt), sub(qt), loc(qt);
+    std::vector<uint32_t> rad(qt);
+    MIH_CHECK(hipMemcpyAsync(seen.data(), st.seen, qt * 8, hipMemcpyDeviceToHost, s));
+    MIH_CHECK(hipMemcpyAsync(sub.data(), st.sub, qt * 8, hipMemcpyDeviceToHost, s));
+    MIH_CHECK(hipMemcpyAsync(loc.data(), st.loc, qt * 8, hipMemcpyDeviceToHost, s));
+    MIH_CHECK(hipMemcpyAsync(rad.data(), st.radius, qt * 4, hipMemcpyDeviceToHost, s));
+    MIH_CHECK(hipStreamSynchronize(s));
+    for (uint32_t i = 0; i < qt; ++i) {
+      vc_query_stats& o = host_stats[t.q0 + i];
+      o.radius = rad[i];
+      o.n_results = 0;
+      o.n_main_reads = 0;
+      o.n_sub_reads = sub[i];
+      o.n_local_reads = loc[i];
+      o.n_candidates = seen[i];
+    }
+    return VC_OK;
+  }
+};
+
+int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint64_t n, const uint64_t* d_q, uint32_t nq,
+                  uint32_t k, bool approximate, uint64_t* d_out, uint32_t* d_cnt, vc_query_stats* host_stats, hipStream_t s,
+                  std::string* err, const VcMihScanFallback* fb, vc_query_stats* d_stats, uint32_t r_cap) {
+  if (n != ix->n) return fail(err, VC_ERR_STATE, "index is stale: codes were added after vc_build_index()");
+  int rc = upload_binom(err);
+  if (rc) return rc;
+  if (!ix->h_ctr) MIH_CHECK(alloc_mapped(&ix->h_ctr, &ix->h_ctr_dev));
+  KnnSearch c{ix, d_cols, stride, n, d_q, k, approximate, host_stats != nullptr || d_stats != nullptr, d_out, d_cnt, fb, s, err,
+              knn_plan(ix, n, nq, k, approximate, fb, r_cap), MihState{}, MihLists{}};
+  const KnnPlan& pl = c.pl;
+  if ((rc = ensure_tile(ix, pl.tile, k, pl.cap, !pl.inblock, &c.st, &c.ls, err))) return rc;
+
+  for (uint32_t q0 = 0; q0 < nq; q0 += pl.tile) {
+    const uint32_t qt = std::min(pl.tile, nq - q0);
+    KnnTile t{q0, qt, c.ls.list[0], c.ls.list[1], c.ls.list[2], qt, qt, 0};
+    if (!pl.inblock) rc = c.open_all(t);                                       // cur = every query of the tile
+    else {
+      rc = c.run_query_kernel(t);                                              // cur = the unfinished queries, n_heavy of them
+      if (!rc && t.n_heavy) rc = c.hand_over(t);                               // list[3] = cur; a capped run at its cap leaves here (n_cur = 0)
+      if (!rc && t.n_heavy && pl.switch_ok) rc = c.scan_costly_queries(t);     // the scan may answer some: cur = the kept ones + what came back
     }
     bool switched = false;
-    for (uint32_t r = r_start; r <= r_end && n_cur; ++r) {   // search_worker.cc:170: radius <= n_local_bytes_*8
-      // Cost model: this shell alone is m * C(S, r) bucket probes per active query (the multi-block kernels sustain ~4e10
-      // probes/s plus ~40 us of launches and a host round trip per shell); the verify kernel costs scan_cost_s (x 2.5 when the
-      // statistics pass is wanted).  Beyond the break-even the remaining queries are
-      // answered by the scan with the stop rule replayed -- same rows, same statistics (see mih_replay_kernel).
-      if (fb && fb->fn && switch_ok && !switched) {
-        const double est_mih = (double)n_cur * ix->m * binom_host(S, r) / 4e10 + 40e-6;
-        const double est_scan = scan_cost_s(n, ix->W, n_cur) * (stats ? 2.5 : 1.0);
-        if (est_mih > est_scan || ix->knobs.mih_switch == 2) {
-          uint32_t n_back = 0;
-          if ((rc = scan_handoff(cur, n_cur, nxt, &n_back))) return rc;
-          if (trace) fprintf(stderr, "[vc_mih] shell r=%u: %u queries answered by the verify kernel (cost model), %u continue\n", r, n_cur - n_back, n_back);
-          n_cur = n_back;
-          std::swap(cur, nxt);
-          switched = true;
-          if (n_cur == 0) break;
-        }
-      }
-      const auto t_shell = std::chrono::steady_clock::now();
-      ProbeParams p{};
-      p.cols = d_cols; p.stride = stride; p.tables = ix->d_tables; p.queries = d_q + (size_t)q0 * ix->W;
-      p.st = st; p.r = r; p.nkeys = binom_host(S, r); p.m = ix->m; p.sbits = S; p.id_base = ix->id_base;
-      p.flags = ix->flags; p.cap = cap; p.n = ix->n;
-      CommitParams c{};
-      c.st = st; c.next_list = nxt; c.redo_list = redo; c.ctr = d_ctr; c.k = k; c.cap = cap; c.r = r; c.sbits = S;
-      c.stop_mult = stop_mult; c.approximate = approximate; c.last_shell = r == r_end;
-      MIH_CHECK(hipMemsetAsync(d_ctr, 0, 8, s));
-      const uint32_t* work = cur;
-      uint32_t n_work = n_cur;
-      h_ctr[0] = h_ctr[1] = 0;
-      for (int round = 0;; ++round) {
-        p.list = work;
-        p.count_seen = round == 0;
-        MIH_CHECK(launch_probe(p, ix->W, n_work, s));
-        MIH_CHECK(vc_launch_select_ring_list(st.ring, cap, st.count, work, n_work, k, st.topk, st.topn, s));
-        c.list = work;
-        hipLaunchKernelGGL(mih_commit_kernel, dim3(n_work), dim3(VC_WAVE), 0, s, c);
-        MIH_CHECK(hipGetLastError());
-        MIH_CHECK(hipMemcpyAsync(h_ctr, d_ctr, 8, hipMemcpyDeviceToHost, s));
-        MIH_CHECK(hipStreamSynchronize(s));
-        if (h_ctr[1] == 0) break;
-        // overflowed queries go round again with their tightened limit; swap the redo list with a scratch list
-        if (round > 64) return fail(err, VC_ERR_CAPACITY, "MIH overflow recovery did not converge");
-        // `cur` has been fully consumed by this round: reuse it as the work list of the recovery round so the
-        // commit kernel can refill `redo`
-        n_work = h_ctr[1];
-        MIH_CHECK(hipMemcpyAsync(cur, redo, (size_t)n_work * 4, hipMemcpyDeviceToDevice, s));
-        MIH_CHECK(hipMemsetAsync(d_ctr + 1, 0, 4, s));
-        work = cur;
-      }
-      if (trace)
-        fprintf(stderr, "[vc_mih] shell r=%u keys=%u active=%u -> next=%u  %.1f us\n", r, p.nkeys, n_cur, h_ctr[0],
-                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_shell).count());
-      n_cur = h_ctr[0];
-      std::swap(cur, nxt);
+    for (uint32_t r = t.r_start; !rc && r <= pl.r_end && t.n_cur; ++r) {       // search_worker.cc:170: radius <= n_local_bytes_*8
+      if (pl.switch_ok && !switched) rc = c.scan_if_shell_costs_more(t, r, &switched);   // the scan may answer the rest: cur = what came back
+      if (!rc && t.n_cur) rc = c.run_shell(t, r);                              // cur = the queries that go on to shell r + 1
     }
-    // rows of the queries that went through the multi-block shells (the query kernel wrote the others itself)
-    if (n_heavy) {
-      hipLaunchKernelGGL(mih_export_kernel, dim3(n_heavy), dim3(256), 0, s, st, inblock ? (const uint32_t*)lists[3] : (const uint32_t*)nullptr, k, cap,
-                         d_out + (size_t)q0 * k, d_cnt + q0);
-      MIH_CHECK(hipGetLastError());
-    }
-    if (d_stats) {
-      hipLaunchKernelGGL(mih_stats_export_kernel, dim3((qt + 255) / 256), dim3(256), 0, s, st, (const uint32_t*)(d_cnt + q0), qt, d_stats + q0);
-      MIH_CHECK(hipGetLastError());
-    }
-    if (host_stats) {
-      std::vector<unsigned long long> seen(qt), sub(qt), loc(qt);
-      std::vector<uint32_t> rad(qt);
-      MIH_CHECK(hipMemcpyAsync(seen.data(), st.seen, qt * 8, hipMemcpyDeviceToHost, s));
-      MIH_CHECK(hipMemcpyAsync(sub.data(), st.sub, qt * 8, hipMemcpyDeviceToHost, s));
-      MIH_CHECK(hipMemcpyAsync(loc.data(), st.loc, qt * 8, hipMemcpyDeviceToHost, s));
-      MIH_CHECK(hipMemcpyAsync(rad.data(), st.radius, qt * 4, hipMemcpyDeviceToHost, s));
-      MIH_CHECK(hipStreamSynchronize(s));
-      for (uint32_t i = 0; i < qt; ++i) {
-        vc_query_stats& o = host_stats[q0 + i];
-        o.radius = rad[i];
-        o.n_results = 0;
-        o.n_main_reads = 0;
-        o.n_sub_reads = sub[i];
-        o.n_local_reads = loc[i];
-        o.n_candidates = seen[i];
-      }
-    }
+    if (!rc && t.n_heavy) rc = c.export_rows(t);
+    if (!rc && d_stats) rc = c.export_stats_dev(t, d_stats);
+    if (!rc && host_stats) rc = c.export_stats_host(t, host_stats);
+    if (rc) return rc;
   }
   return VC_OK;
 }
@@ -3627,6 +3792,132 @@ void vc_radius_work_free(VcRadiusWork* w) {
   *w = VcRadiusWork();
 }
 
+// wk->d_aux of one call: count[TQ] | tau[TQ] | sorted[TQ] | hist[TQ * hs] | tot (total, largest: 8-byte aligned)
+struct RadiusAux {
+  uint32_t *count, *tau, *sorted, *hist;
+  unsigned long long* tot;   // VcRadiusTotals::total, ::largest
+  static size_t scan_words(uint32_t TQ, uint32_t hs) { return (size_t)TQ * (3 + hs); }   // what the linear scan clears: everything in front of tot
+  static size_t words(uint32_t TQ, uint32_t hs) { return scan_words(TQ, hs) + 8; }
+  RadiusAux(uint32_t* base, uint32_t TQ, uint32_t hs)
+      : count(base), tau(base + TQ), sorted(base + 2 * TQ), hist(base + 3 * TQ),
+        tot((unsigned long long*)(base + ((scan_words(TQ, hs) + 1) & ~(size_t)1))) {}
+};
+constexpr size_t RADIUS_TOT_BYTES = offsetof(VcRadiusTotals, seq);   // the device's part of the totals
+static_assert(RADIUS_TOT_BYTES == 16 && sizeof(VcRadiusTotals) == 32, "vc_radius_offsets_kernel: tot[0..1], host_tot[0..2]");
+
+enum RadiusRoute {
+  RADIUS_QUERY_KERNEL,   // shells 0..rsub inside mih_query_kernel, one block per query
+  RADIUS_STREAM,         // <= 16-bit substrings whose shells exceed the query kernel's entry budget: stream the buckets (mih_bucket_stream_kernel)
+  RADIUS_HOST_SHELLS,    // one probe launch per shell
+  RADIUS_LINEAR_SCAN     // no index (or a radius the scan answers cheaper): the verify kernel with a fixed threshold
+};
+static RadiusRoute radius_route(const VcMihIndex* ix, bool use_mih, const RadiusPlan& rp) {
+  if (!use_mih) return RADIUS_LINEAR_SCAN;
+  if (ix->knobs.mih_host_loop != 0) return RADIUS_HOST_SHELLS;
+  bool inblock = rp.probes <= MQ_RADIUS_BUDGET && rp.rsub <= 16 && (double)rp.probes * avg_bucket(ix) <= MQ_ENTRY_BUDGET;
+  if (ix->knobs.mih_stream == 2 && ix->sbits <= 16) inblock = false;   // tests: small databases through the streaming kernel too
+  if (inblock) return RADIUS_QUERY_KERNEL;
+  bool stream = ix->knobs.mih_stream != 0 && ix->sbits <= 16 && rp.probes <= MS_MAXP;
+  for (const VcTableView& tv : ix->h_tables) stream = stream && tv.bcodes != nullptr;
+  return stream ? RADIUS_STREAM : RADIUS_HOST_SHELLS;
+}
+
+// One attempt of a radius call: every route leaves the tile's neighbours in the work ring, [slot][cap], with their counts
+// in aux.count.  (W == ix->W and id_base == ix->id_base wherever there is an index.)
+struct RadiusSearch {
+  VcMihIndex* ix;
+  const uint64_t* d_cols;
+  uint64_t stride, n;
+  uint32_t W, id_base, n_cu;
+  const VcKnobs* knobs;
+  const uint64_t* d_q;
+  uint32_t radius, cap, hs, tq;
+  RadiusPlan rp;
+  RadiusAux aux;
+  VcRadiusWork* wk;
+  hipStream_t s;
+  std::string* err;
+  MihState st;
+  MihLists ls;
+
+  // the index's tile state with the call's own ring and counters in it
+  int mih_state() {
+    const int rc = ensure_tile(ix, MIH_RADIUS_TILE, 1, 1, false, &st, &ls, err);
+    st.ring = wk->d_ring;   // radius search keeps every neighbour: the big ring instead of the tile's
+    st.count = aux.count;
+    st.topn = aux.sorted;
+    return rc;
+  }
+  int open_all(uint32_t qt) {
+    hipLaunchKernelGGL(mih_init_kernel, dim3((qt + 255) / 256), dim3(256), 0, s, st, qt, ls.list[0], vc_pack(radius + 1, 0));
+    MIH_CHECK(hipGetLastError());
+    return VC_OK;
+  }
+
+  // its small segments arrive sorted (aux.sorted says which); its work counters are summed by the offsets kernel
+  int by_query_kernel(uint32_t q0, uint32_t qt) {
+    QueryKernelParams qp = query_kernel_params(ix, d_cols, stride, st);
+    qp.queries = d_q + (size_t)q0 * W; qp.cap = cap; qp.k = 0;
+    qp.mode = MQ_MODE_RADIUS; qp.radius = radius; qp.r_last = rp.rsub; qp.n_big = rp.n_big; qp.small_shells = rp.small_shells;
+    qp.buf_entries = 2048;
+    MIH_CHECK(timed_query_launch(ix, qp, nullptr, W, qt, s));
+    return VC_OK;
+  }
+
+  int by_stream(uint32_t q0, uint32_t qt) {
+    int rc;
+    if ((rc = open_all(qt))) return rc;
+    StreamParams sp{};
+    sp.queries = d_q + (size_t)q0 * W; sp.tables = ix->d_tables; sp.ring = wk->d_ring; sp.count = aux.count; sp.n = ix->n;
+    sp.m = ix->m; sp.sbits = ix->sbits; sp.id_base = id_base; sp.flags = ix->flags; sp.cap = cap; sp.radius = radius;
+    sp.rsub = rp.rsub; sp.n_big = rp.n_big; sp.small_shells = rp.small_shells; sp.nprobes = (uint32_t)rp.probes;
+    // enough blocks to fill the chip when the batch is small: a query's probe list is dealt out to `split` blocks
+    // (r04: 8 x n_cu blocks were 2048 for a tile of 1024 queries, 1.6 residency waves of 1280 -- the last fifth of the launch
+    // ran on 768 blocks and fewer; one wave of blocks that are all resident ends 1.3 % earlier, more and smaller blocks pay
+    // for their look-ups: 0.396 / 0.391 / 0.406 ms at 8 / 4 / 16 blocks per CU, profiles/r04_stream_trace.txt)
+    sp.split = std::max(1u, std::min(std::min(sp.nprobes, 64u), stream_resident_blocks(W, n_cu) / qt));
+    MIH_CHECK(timed_stream_launch(ix, sp, W, qt, s));
+    return VC_OK;
+  }
+
+  int by_host_shells(uint32_t q0, uint32_t qt) {
+    int rc;
+    if ((rc = open_all(qt))) return rc;
+    for (uint32_t r = 0; r <= rp.rsub; ++r) {
+      ProbeParams p = probe_params(ix, d_cols, stride, st, r);
+      p.queries = d_q + (size_t)q0 * W; p.list = ls.list[0]; p.cap = cap; p.count_seen = 1; p.m_probe = rp.tables_at(r);
+      MIH_CHECK(launch_probe(p, W, qt, s));
+    }
+    return VC_OK;
+  }
+
+  int by_linear_scan(uint32_t q0, uint32_t qt) {
+    MIH_CHECK(hipMemsetAsync(wk->d_aux, 0, RadiusAux::scan_words(tq, hs) * 4, s));
+    hipLaunchKernelGGL(vc_fill_u32_kernel, dim3((qt + 255) / 256), dim3(256), 0, s, aux.tau, qt, radius);
+    MIH_CHECK(hipGetLastError());
+    size_t lds;
+    const VcScanShape sh = vc_scan_pick_shape(W, qt, &lds, knobs);
+    VcScanParams p{};
+    p.cols = d_cols; p.stride = stride; p.n = n; p.nchunks = (n + sh.chunk_items() - 1) / sh.chunk_items();
+    p.id_base = id_base; p.qt = qt; p.k = 0xFFFFFFFFu;   // never re-derive tau: it is the fixed radius
+    p.cap = cap; p.hist_stride = hs; p.queries = d_q + (size_t)q0 * W; p.tau = aux.tau; p.count = aux.count; p.qs = 1;
+    p.hist = aux.hist; p.buf = wk->d_ring;
+    MIH_CHECK(vc_launch_scan(p, W, n_cu, 0, knobs, s));
+    return VC_OK;
+  }
+
+  int run(RadiusRoute route, uint32_t q0, uint32_t qt) {
+    int rc;
+    if (route != RADIUS_LINEAR_SCAN && (rc = mih_state())) return rc;
+    switch (route) {
+      case RADIUS_QUERY_KERNEL: return by_query_kernel(q0, qt);
+      case RADIUS_STREAM: return by_stream(q0, qt);
+      case RADIUS_HOST_SHELLS: return by_host_shells(q0, qt);
+      default: return by_linear_scan(q0, qt);
+    }
+  }
+};
+
 // All items within full distance <= radius of each query, ascending per query, written to d_out (device memory,
 // out_cap entries) with d_offsets[nq + 1] (device).  Everything is enqueued on `s`; the host synchronises ONCE at the
 // end to learn the total and whether a query outgrew its ring (then the ring is doubled and the call repeated).
@@ -3640,41 +3931,23 @@ static int radius_search_device(VcMihIndex* ix, bool use_mih, const uint64_t* d_
   const uint32_t bits = W * 64;
   if (radius > bits) radius = bits;
   const RadiusPlan rp = use_mih ? radius_plan(ix, radius) : RadiusPlan{};
-  bool inblock = false;
-  if (use_mih && ix->knobs.mih_host_loop == 0) {
-    const double avg_bucket = (double)ix->n / (ix->sbits >= 32 ? 4294967296.0 : (double)(1ull << ix->sbits));
-    inblock = rp.probes <= MQ_RADIUS_BUDGET && rp.rsub <= 16 && (double)rp.probes * avg_bucket <= MQ_ENTRY_BUDGET;
-    if (ix->knobs.mih_stream == 2 && ix->sbits <= 16) inblock = false;   // tests: small databases through the streaming kernel too
-  }
-  // <= 16-bit substrings whose shells exceed the query kernel's entry budget: stream the buckets (mih_bucket_stream_kernel)
-  bool stream = false;
-  if (use_mih && !inblock && ix->knobs.mih_host_loop == 0 && ix->knobs.mih_stream != 0 && ix->sbits <= 16) {
-    stream = rp.probes <= MS_MAXP;
-    for (const VcTableView& tv : ix->h_tables) stream = stream && tv.bcodes != nullptr;
-  }
+  const RadiusRoute route = radius_route(ix, use_mih, rp);
   const uint32_t TQ = use_mih ? MIH_RADIUS_TILE : 64u;
   uint32_t cap = std::max(wk->cap, use_mih ? std::max(ix->cap, 4096u) : 65536u);
   while (cap & (cap - 1)) cap += cap & (0u - cap);   // power of two: the in-place segment sort pads to one
   const uint32_t hs = (bits + 1 + 7) & ~7u;
-  const size_t aux_words = (size_t)TQ * (3 + hs) + 8;   // count[TQ] | tau[TQ] | sorted[TQ] | hist[TQ*hs] | tot (2 x u64)
+  const size_t aux_words = RadiusAux::words(TQ, hs);
   if (wk->aux_words < aux_words) {
     (void)hipFree(wk->d_aux);
     wk->d_aux = nullptr;
     MIH_CHECK(hipMalloc((void**)&wk->d_aux, aux_words * 4));
     wk->aux_words = aux_words;
   }
-  if (!wk->h_tot) {
-    MIH_CHECK(hipHostMalloc((void**)&wk->h_tot, 32, hipHostMallocMapped));
-    wk->h_tot[2] = 0;
-    if (hipHostGetDevicePointer((void**)&wk->h_tot_dev, wk->h_tot, 0) != hipSuccess) { (void)hipGetLastError(); wk->h_tot_dev = nullptr; }
-  }
+  if (!wk->h_tot) MIH_CHECK(alloc_mapped(&wk->h_tot, &wk->h_tot_dev));
   const bool poll = wk->h_tot_dev && (!knobs || knobs->mih_poll);
-  uint32_t* d_count = wk->d_aux;
-  uint32_t* d_tau = wk->d_aux + TQ;
-  uint32_t* d_sorted = wk->d_aux + 2 * TQ;
-  uint32_t* d_hist = wk->d_aux + 3 * TQ;
-  unsigned long long* d_tot = (unsigned long long*)(wk->d_aux + (((size_t)TQ * (3 + hs) + 1) & ~(size_t)1));
-  MihState st{};
+  const RadiusAux aux(wk->d_aux, TQ, hs);
+  // the routes whose segments the copy-out kernel finds sorted, and whose work counters the offsets kernel sums: the query kernel's
+  const uint32_t* sorted_flag = route == RADIUS_QUERY_KERNEL ? aux.sorted : nullptr;
 
   for (int attempt = 0;; ++attempt) {
     if (wk->cap != cap || !wk->d_ring) {
@@ -3683,86 +3956,27 @@ static int radius_search_device(VcMihIndex* ix, bool use_mih, const uint64_t* d_
       MIH_CHECK(hipMalloc((void**)&wk->d_ring, (size_t)TQ * cap * 8));
       wk->cap = cap;
     }
-    if (nq == 0) MIH_CHECK(hipMemsetAsync(d_tot, 0, 16, s));   // (else the first tile's offsets kernel starts the totals over)
+    RadiusSearch c{ix, d_cols, stride, n, W, id_base, n_cu, knobs, d_q, radius, cap, hs, TQ, rp, aux, wk, s, err, MihState{}, MihLists{}};
+    if (nq == 0) MIH_CHECK(hipMemsetAsync(aux.tot, 0, RADIUS_TOT_BYTES, s));   // (else the first tile's offsets kernel starts the totals over)
     for (uint32_t q0 = 0; q0 < nq; q0 += TQ) {
       const uint32_t qt = std::min(TQ, nq - q0);
-      const uint32_t* sorted_flag = nullptr;
-      const unsigned long long* work = nullptr;   // mih_query_kernel's per-query work counters of this tile
-      if (use_mih) {
-        if ((rc = ensure_tile(ix, MIH_RADIUS_TILE, 1, 1, false, &st, err))) return rc;
-        st.ring = wk->d_ring;   // radius search keeps every neighbour: the big ring instead of the tile's
-        st.count = d_count;
-        st.topn = d_sorted;
-        if (inblock) {
-          QueryKernelParams qp{};
-          qp.cols = d_cols; qp.stride = stride; qp.n = ix->n; qp.tables = ix->d_tables; qp.queries = d_q + (size_t)q0 * W;
-          qp.st = st; qp.m = ix->m; qp.sbits = ix->sbits; qp.id_base = id_base; qp.flags = ix->flags; qp.cap = cap; qp.k = 0;
-          qp.mode = MQ_MODE_RADIUS; qp.radius = radius; qp.r_last = rp.rsub; qp.n_big = rp.n_big; qp.small_shells = rp.small_shells;
-          qp.buf_entries = 2048;
-          MIH_CHECK(timed_query_launch(ix, qp, W, qt, s));
-          sorted_flag = d_sorted;
-          work = st.work;
-        } else if (stream) {
-          uint32_t* list = ix->d_lists;
-          hipLaunchKernelGGL(mih_init_kernel, dim3((qt + 255) / 256), dim3(256), 0, s, st, qt, list, vc_pack(radius + 1, 0));
-          MIH_CHECK(hipGetLastError());
-          StreamParams sp{};
-          sp.queries = d_q + (size_t)q0 * W; sp.tables = ix->d_tables; sp.ring = wk->d_ring; sp.count = d_count; sp.n = ix->n;
-          sp.m = ix->m; sp.sbits = ix->sbits; sp.id_base = id_base; sp.flags = ix->flags; sp.cap = cap; sp.radius = radius;
-          sp.rsub = rp.rsub; sp.n_big = rp.n_big; sp.small_shells = rp.small_shells; sp.nprobes = (uint32_t)rp.probes;
-          // enough blocks to fill the chip when the batch is small: a query's probe list is dealt out to `split` blocks
-          // (r04: 8 x n_cu blocks were 2048 for a tile of 1024 queries, 1.6 residency waves of 1280 -- the last fifth of the launch
-          // ran on 768 blocks and fewer; one wave of blocks that are all resident ends 1.3 % earlier, more and smaller blocks pay
-          // for their look-ups: 0.396 / 0.391 / 0.406 ms at 8 / 4 / 16 blocks per CU, profiles/r04_stream_trace.txt)
-          sp.split = std::max(1u, std::min(std::min(sp.nprobes, 64u), stream_resident_blocks(W, n_cu) / qt));
-          MIH_CHECK(timed_stream_launch(ix, sp, W, qt, s));
-        } else {
-          uint32_t* list = ix->d_lists;
-          hipLaunchKernelGGL(mih_init_kernel, dim3((qt + 255) / 256), dim3(256), 0, s, st, qt, list, vc_pack(radius + 1, 0));
-          MIH_CHECK(hipGetLastError());
-          for (uint32_t r = 0; r <= rp.rsub; ++r) {
-            ProbeParams p{};
-            p.cols = d_cols; p.stride = stride; p.tables = ix->d_tables; p.queries = d_q + (size_t)q0 * W; p.list = list;
-            p.st = st; p.r = r; p.nkeys = binom_host(ix->sbits, r); p.m = ix->m; p.sbits = ix->sbits; p.id_base = id_base;
-            p.flags = ix->flags; p.cap = cap; p.count_seen = 1; p.n = ix->n; p.m_probe = rp.tables_at(r);
-            MIH_CHECK(launch_probe(p, W, qt, s));
-          }
-        }
-      } else {
-        MIH_CHECK(hipMemsetAsync(wk->d_aux, 0, (size_t)TQ * (3 + hs) * 4, s));
-        hipLaunchKernelGGL(vc_fill_u32_kernel, dim3((qt + 255) / 256), dim3(256), 0, s, d_tau, qt, radius);
-        MIH_CHECK(hipGetLastError());
-        size_t lds;
-        const VcScanShape sh = vc_scan_pick_shape(W, qt, &lds, knobs);
-        VcScanParams p{};
-        p.cols = d_cols; p.stride = stride; p.n = n; p.nchunks = (n + sh.chunk_items() - 1) / sh.chunk_items();
-        p.id_base = id_base; p.qt = qt; p.k = 0xFFFFFFFFu;   // never re-derive tau: it is the fixed radius
-        p.cap = cap; p.hist_stride = hs; p.queries = d_q + (size_t)q0 * W; p.tau = d_tau; p.count = d_count; p.qs = 1;
-        p.hist = d_hist; p.buf = wk->d_ring;
-        MIH_CHECK(vc_launch_scan(p, W, n_cu, 0, knobs, s));
-      }
+      if ((rc = c.run(route, q0, qt))) return rc;
+      const unsigned long long* work = route == RADIUS_QUERY_KERNEL ? c.st.work : nullptr;   // mih_query_kernel's per-query work counters of this tile
       // place the tile's segments behind the previous tiles' (+ the call's totals, + the query kernel's work counters), then
       // order what did not arrive sorted (hand-written bitonic network; the query kernel's small segments do) and copy out
       const unsigned long long seq = (poll && q0 + TQ >= nq) ? ++wk->seq : 0ull;
-      hipLaunchKernelGGL(vc_radius_offsets_kernel, dim3(work ? 2 : 1), dim3(1024), 0, s, d_count, qt, d_offsets + q0, d_tot, q0 == 0 ? 1u : 0u,
+      hipLaunchKernelGGL(vc_radius_offsets_kernel, dim3(work ? 2 : 1), dim3(1024), 0, s, aux.count, qt, d_offsets + q0, aux.tot, q0 == 0 ? 1u : 0u,
                          (volatile unsigned long long*)wk->h_tot_dev, seq, work, work ? ix->d_totals : (unsigned long long*)nullptr);
       MIH_CHECK(hipGetLastError());
-      hipLaunchKernelGGL(vc_sort_compact_segments_kernel, dim3(qt), dim3(1024), 0, s, wk->d_ring, cap, d_count, sorted_flag,
+      hipLaunchKernelGGL(vc_sort_compact_segments_kernel, dim3(qt), dim3(1024), 0, s, wk->d_ring, cap, aux.count, sorted_flag,
                          d_offsets + q0, d_out, out_cap);
       MIH_CHECK(hipGetLastError());
     }
     // total + largest segment: the last offsets kernel wrote them to mapped host memory; the host polls the sequence word and
     // returns while the last copy-out kernel may still run (results are in stream order; host readers copy behind it)
-    bool landed = false;
-    if (poll && nq) {
-      landed = poll_mapped_word((volatile unsigned long long*)(wk->h_tot + 2), (unsigned long long)wk->seq);
-    }
-    if (!landed) {
-      MIH_CHECK(hipMemcpyAsync(wk->h_tot, d_tot, 16, hipMemcpyDeviceToHost, s));
-      MIH_CHECK(hipStreamSynchronize(s));
-    }
-    const uint64_t mx = wk->h_tot[1];
-    *total = wk->h_tot[0];
+    MIH_CHECK(wait_mapped((volatile unsigned long long*)&wk->h_tot->seq, (unsigned long long)wk->seq, poll && nq, wk->h_tot, aux.tot, RADIUS_TOT_BYTES, s));
+    const uint64_t mx = wk->h_tot->largest;
+    *total = wk->h_tot->total;
     if (mx <= cap) break;
     uint64_t want = cap;
     while (want < mx) want <<= 1;

@@ -88,11 +88,17 @@ int vc_mih_bitmap_test(VcMihIndex* ix, uint32_t table, uint32_t index, int* bit,
 int vc_mih_bitmap_read(VcMihIndex* ix, uint32_t table, uint64_t word_off, uint64_t n_words, uint32_t* out, hipStream_t s,
                        std::string* err);
 // grow-only device buffers of the radius search, owned by the engine (allocation costs more than a search)
+struct VcRadiusTotals {   // vc_radius_offsets_kernel's running totals: `total` and `largest` in device memory (tot[0], tot[1]), all in the mapped copy
+  unsigned long long total;     // entries of the call so far
+  unsigned long long largest;   // largest segment of the call so far (beyond the ring's capacity: the call is repeated)
+  unsigned long long seq;       // mapped host copy only: sequence number of the call that wrote the two
+  unsigned long long unused;
+};
 struct VcRadiusWork {
   uint64_t *d_ring = nullptr, *d_compact = nullptr, *d_offs = nullptr;
   uint32_t* d_aux = nullptr;
-  unsigned long long* h_tot = nullptr;   // pinned, mapped: total entries | largest segment | sequence number of the call that wrote them
-  unsigned long long* h_tot_dev = nullptr;
+  VcRadiusTotals* h_tot = nullptr;       // pinned, mapped: the last vc_radius_offsets_kernel of a call publishes there
+  VcRadiusTotals* h_tot_dev = nullptr;
   unsigned long long seq = 0;
   size_t aux_words = 0, offs_cap = 0;
   uint64_t compact_cap = 0;

@@ -113,7 +113,7 @@ struct vc_sharded {
   uint32_t* gs_cnt = nullptr;   size_t gs_cnt_bytes = 0;
   vc_query_stats* gs_st = nullptr; size_t gs_st_bytes = 0;
   uint32_t* gs_scan = nullptr;  size_t gs_scan_bytes = 0;
-  uint32_t gs_cap0 = 1;         // first round's cap (VC_MIH_GS_CAP)
+  VcKnobs knobs;                // the handle's own developer knobs: gs_cap (first round's cap), gs_trace
   RcclApi rccl;
   std::vector<ncclComm_t> comms;
   uint32_t exchange = VC_EXCHANGE_PEER_COPY;   // what is in use
@@ -219,7 +219,7 @@ int vc_sharded_create(const vc_sharded_config* cfg, vc_sharded** out) {
   h->D = cfg->n_devices ? cfg->n_devices : (uint32_t)std::min<int>(ndev, (int)cfg->n_shards);
   h->capacity = cfg->engine.capacity;
   h->nbytes = cfg->engine.bits / 8;
-  if (const char* v = getenv("VC_MIH_GS_CAP")) h->gs_cap0 = (uint32_t)std::max(0, atoi(v));   // dev knob: first round's cap
+  read_knobs(&h->knobs);
   h->eng.assign(h->G, nullptr);
   h->dev.resize(h->G);
   h->lo.resize(h->G);
@@ -704,7 +704,7 @@ static int sharded_global_stop(vc_sharded* h, const void* d_queries, uint32_t nq
                                vc_query_stats* d_stats, hipStream_t S) {
   const uint32_t W = h->nbytes / 8, m = h->cfg.engine.n_tables, Sb = h->cfg.engine.bits / m;
   const uint32_t mult = (h->cfg.engine.flags & VC_FLAG_REF_STOP_LITERAL4) ? 4u : std::min(m, 4u);
-  const bool trace = getenv("VC_MIH_GS_TRACE") != nullptr;   // dev: per-round wall times on stderr
+  const bool trace = h->knobs.gs_trace;   // dev: per-round wall times on stderr
   uint32_t nonempty = 0, reach = GS_CAPS - 1;
   std::vector<VcEngineView> view(h->G);
   for (uint32_t g = 0; g < h->G; ++g) {
@@ -739,7 +739,7 @@ static int sharded_global_stop(vc_sharded* h, const void* d_queries, uint32_t nq
     VS_HIP(h, hipGetLastError());
     n_scan = nq;
   } else {
-    const uint32_t t0 = std::min(h->gs_cap0, reach);
+    const uint32_t t0 = std::min(h->knobs.gs_cap, reach);
     hipLaunchKernelGGL(gs_iota_kernel, dim3((nq + 255) / 256), dim3(256), 0, S, lists[0] + (size_t)t0 * nq, nq);
     VS_HIP(h, hipGetLastError());
     n_at[t0] = nq;
