@@ -15,6 +15,11 @@
 //   VC_EXCHANGE_PEER_COPY  hipMemcpyPeerAsync of each shard's rows into the root device's gather buffer, ordered
 //                          behind the shard's search by an event; also the path when several shards share a device
 // No CPU compute anywhere: the host moves pointers, the merge is the device kernel of vc_scan.hip.
+//
+// In this file: DevBuf (grow-only scratch), Lane, vc_sharded | create / ingest / look-up | ShardBatch = one batch through the
+// shards (prepare_lanes, send_queries, run_lanes, exchange, merge; sharded_search_dev) | VC_FLAG_GLOBAL_STOP: the stop rule
+// (gs_stop_shell), the kernels, the layouts they share with the host (GsRoundLists, GsScanCols, GsScanBlock) and GsSearch,
+// the steps of a flagged call (sharded_global_stop, GsSearch::union_scan) | the search entry points.
 // ============================================================================
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -71,19 +76,45 @@ struct RcclApi {
   }
 };
 
+// Grow-only device scratch: the pointer and how many bytes are behind it.  It has no destructor on purpose: hipFree acts on
+// the CURRENT device, so the owner binds the buffer's device and then releases it (vc_sharded_destroy, ScopedBufs).
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  int grow(vc_sharded* h, size_t need);   // at least `need` bytes, on the current device; the contents are lost when it grows
+  void release() { (void)hipFree(p); p = nullptr; bytes = 0; }
+  template <class T> T* as() const { return (T*)p; }
+};
+
 // One lane per distinct device: the shards that live there run ONE AFTER THE OTHER on the lane's stream -- at most one
 // persistent-grid kernel sequence per GPU (the recovery kernel's grid barrier needs its whole grid resident; a neighbour
 // shard's full-chip verify grid on another stream could keep it off the CUs for seconds: ADVICE round 3) -- while the
 // lanes, i.e. the devices, run concurrently.  The root device's lane runs on the caller's stream.
+enum LaneBuf {
+  LANE_Q,      // the batch's queries on this device (peer copy from the root)
+  LANE_GATH,   // [G][slot]: shard g's rows | counts | statistics at slot g (SlotLayout); on the root (and, with RCCL, everywhere)
+               // the gathered results of all shards
+  LANE_AUX,    // union scan of VC_FLAG_GLOBAL_STOP: its per-query inputs and outputs here (GsScanBlock, gs_lane_block)
+  LANE_BUFS
+};
 struct Lane {
   int dev = 0;
   std::vector<uint32_t> shards;
-  hipStream_t stream = nullptr;                   // own stream (the root lane uses the caller's)
-  hipEvent_t done = nullptr;                      // behind the lane's last shard of a batch
-  void* q = nullptr;        size_t q_bytes = 0;   // the batch's queries on this device (peer copy from the root)
-  uint64_t* gath = nullptr; size_t gath_bytes = 0;   // [G][slot]: shard g's rows | counts | statistics at slot g; on the root
-                                                     // (and, with RCCL, everywhere) the gathered results of all shards
-  uint32_t* aux = nullptr;  size_t aux_bytes = 0;    // union scan of VC_FLAG_GLOBAL_STOP: its per-query inputs and outputs here
+  hipStream_t stream = nullptr;   // own stream (the root lane uses the caller's)
+  hipEvent_t done = nullptr;      // behind the lane's last shard of a batch
+  DevBuf buf[LANE_BUFS];
+  const void* q() const { return buf[LANE_Q].p; }
+  uint64_t* gath() const { return buf[LANE_GATH].as<uint64_t>(); }
+  uint64_t* slot(uint32_t g, size_t slot_words) const { return gath() + (size_t)g * slot_words; }
+};
+
+// The handle's scratch on the root device.
+enum RootBuf {
+  ROOT_HQ, ROOT_OUT, ROOT_OCNT, ROOT_OSTATS,   // host-pointer API: staged queries, merged rows, counts, statistics
+  // VC_FLAG_GLOBAL_STOP: round lists + counters + floors (GsRoundLists), gathered queries, merged rows / counts / statistics
+  // of a round, the union scan's per-query words and the shards' tie ids (GsScanBlock, gs_root_block)
+  GS_LISTS, GS_Q, GS_ROWS, GS_CNT, GS_ST, GS_SCAN,
+  ROOT_BUFS
 };
 
 }  // namespace
@@ -101,23 +132,13 @@ struct vc_sharded {
   int root = 0;                         // device that merges
   hipStream_t root_stream = nullptr;    // stream of the host-pointer calls / VC_STREAM_OWN
   hipEvent_t ev_q = nullptr;            // "the batch's queries are ready" on the caller's stream
-  void* d_hq = nullptr;         size_t hq_bytes = 0;      // host-pointer API: staged queries, merged rows, counts, statistics
-  uint64_t* d_out = nullptr;    size_t out_bytes = 0;
-  uint32_t* d_ocnt = nullptr;   size_t ocnt_bytes = 0;
-  vc_query_stats* d_ostats = nullptr; size_t ostats_bytes = 0;
-  // VC_FLAG_GLOBAL_STOP (root device): round lists + counters + floors, gathered queries, merged rows / counts / statistics,
-  // the union scan's per-query words and the shards' tie ids
-  uint32_t* gs_u32 = nullptr;   size_t gs_u32_bytes = 0;
-  uint64_t* gs_q = nullptr;     size_t gs_q_bytes = 0;
-  uint64_t* gs_rows = nullptr;  size_t gs_rows_bytes = 0;
-  uint32_t* gs_cnt = nullptr;   size_t gs_cnt_bytes = 0;
-  vc_query_stats* gs_st = nullptr; size_t gs_st_bytes = 0;
-  uint32_t* gs_scan = nullptr;  size_t gs_scan_bytes = 0;
+  DevBuf buf[ROOT_BUFS];                // see RootBuf
   VcKnobs knobs;                // the handle's own developer knobs: gs_cap (first round's cap), gs_trace
   RcclApi rccl;
   std::vector<ncclComm_t> comms;
   uint32_t exchange = VC_EXCHANGE_PEER_COPY;   // what is in use
   std::string err;
+  Lane& root_lane_ref() { return lanes[root_lane]; }
 };
 
 static thread_local std::string g_sharded_create_err;
@@ -139,17 +160,23 @@ static int sfail(vc_sharded* h, int code, const char* fmt, ...) {
       return sfail(h, _r == hipErrorOutOfMemory ? VC_ERR_NOMEM : VC_ERR_HIP, "%s: %s", #call, hipGetErrorString(_r)); \
   } while (0)
 
-template <class T>
-static int sgrow(vc_sharded* h, T** p, size_t* have, size_t need) {
-  if (need <= *have) return VC_OK;
-  if (*p) VS_HIP(h, hipFree(*p));
-  *p = nullptr;
-  *have = 0;
+int DevBuf::grow(vc_sharded* h, size_t need) {
+  if (need <= bytes) return VC_OK;
+  if (p) VS_HIP(h, hipFree(p));
+  p = nullptr;
+  bytes = 0;
   need = (need + 255) & ~(size_t)255;
-  VS_HIP(h, hipMalloc((void**)p, need));
-  *have = need;
+  VS_HIP(h, hipMalloc(&p, need));
+  bytes = need;
   return VC_OK;
 }
+
+// Temporaries of one call on one device, released on every way out (the caller keeps that device current until then).
+template <size_t N>
+struct ScopedBufs {
+  DevBuf b[N];
+  ~ScopedBufs() { for (DevBuf& x : b) x.release(); }
+};
 
 static uint32_t shard_of(const vc_sharded* h, uint64_t pos) {   // pos relative to id_base, < capacity
   uint32_t g = (uint32_t)std::min<uint64_t>(h->G - 1, pos * h->G / std::max<uint64_t>(h->capacity, 1));
@@ -177,15 +204,13 @@ int vc_sharded_destroy(vc_sharded* h) {
       if (c) (void)h->rccl.CommDestroy(c);
   for (Lane& l : h->lanes) {
     (void)hipSetDevice(l.dev);
-    (void)hipFree(l.q); (void)hipFree(l.gath); (void)hipFree(l.aux);
+    for (DevBuf& b : l.buf) b.release();
     if (l.done) (void)hipEventDestroy(l.done);
     if (l.stream) (void)hipStreamDestroy(l.stream);
   }
   for (vc_engine* e : h->eng) vc_destroy(e);
   (void)hipSetDevice(h->root);
-  (void)hipFree(h->d_hq); (void)hipFree(h->d_out); (void)hipFree(h->d_ocnt); (void)hipFree(h->d_ostats);
-  (void)hipFree(h->gs_u32); (void)hipFree(h->gs_q); (void)hipFree(h->gs_rows); (void)hipFree(h->gs_cnt); (void)hipFree(h->gs_st);
-  (void)hipFree(h->gs_scan);
+  for (DevBuf& b : h->buf) b.release();
   if (h->ev_q) (void)hipEventDestroy(h->ev_q);
   if (h->root_stream) (void)hipStreamDestroy(h->root_stream);
   delete h;
@@ -384,7 +409,10 @@ int vc_sharded_get_bucket(vc_sharded* h, uint32_t table, uint32_t index, uint32_
   return total ? VC_OK : VC_NOT_FOUND;
 }
 
+}  // extern "C"
+
 // ---- a batch -------------------------------------------------------------------------------------------------
+// (C++ from here to the entry points at the end; the kernels keep their C names, which profiles and traces carry)
 // Slot of shard g in a gather buffer: [nq][k] rows | [nq] counts (padded to 8 bytes) | [nq] vc_query_stats (when wanted).
 // Rows, counts and statistics travel together: ONE peer copy per remote shard, or ONE all-gather.
 struct SlotLayout {
@@ -399,7 +427,7 @@ struct SlotLayout {
 static_assert(sizeof(vc_query_stats) == 40, "slot layout assumes 5 words per vc_query_stats");
 
 // SearchWorker::get_stat over the shards: every shard stops by its own rule -- the widest radius, the summed work
-__global__ void vc_sharded_stats_kernel(const uint64_t* __restrict__ base, uint64_t slot_words, uint64_t stats_off, uint32_t G, uint32_t nq,
+extern "C" __global__ void vc_sharded_stats_kernel(const uint64_t* __restrict__ base, uint64_t slot_words, uint64_t stats_off, uint32_t G, uint32_t nq,
                                         const uint32_t* __restrict__ merged_cnt, vc_query_stats* __restrict__ out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nq) return;
@@ -415,32 +443,55 @@ __global__ void vc_sharded_stats_kernel(const uint64_t* __restrict__ base, uint6
   out[i] = s;
 }
 
+// A caller that passes no count buffer gets the handle's own (the root device is current).
+static int counts_or_own(vc_sharded* h, uint32_t nq, uint32_t** d_counts) {
+  if (*d_counts) return VC_OK;
+  if (int rc = h->buf[ROOT_OCNT].grow(h, (size_t)nq * 4)) return rc;
+  *d_counts = h->buf[ROOT_OCNT].as<uint32_t>();
+  return VC_OK;
+}
+
+// One batch through the shards, and its steps in the order sharded_search_dev takes them.
 // Everything of a batch is enqueued, nothing is waited for (LINEAR; the MIH modes make the host wait inside each shard's
 // vc_search_knn_dev -- how many queries continue decides what is enqueued next -- which is why lanes of different devices
 // then run on host threads): queries, rows, counts and statistics live in HBM on the root device, valid in `S` order.
 // r_cap != VC_NO_CAP (VC_MODE_MIH_EXACT only): every shard runs capped at that shell (vc_engine_knn_capped), the round of the
 // global stop; the slots stay in the root lane's gather buffer for its settle kernel.
 #define VC_NO_CAP 0xFFFFFFFFu
-static int sharded_search_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out,
-                              uint32_t* d_counts, vc_query_stats* d_stats, hipStream_t S, uint32_t r_cap = VC_NO_CAP) {
-  const SlotLayout L(nq, k, d_stats != nullptr);
-  const size_t qbytes = (size_t)nq * h->nbytes;
-  int rc;
-  for (uint32_t li = 0; li < h->lanes.size(); ++li) {
-    Lane& l = h->lanes[li];
-    const bool everything = li == h->root_lane || h->exchange == VC_EXCHANGE_RCCL;   // gathered results of all shards land here
-    VS_HIP(h, hipSetDevice(l.dev));
-    if ((rc = sgrow(h, &l.gath, &l.gath_bytes, L.words * 8 * (everything ? h->G : l.shards.back() + 1)))) return rc;
-    if (li != h->root_lane && (rc = sgrow(h, (uint8_t**)&l.q, &l.q_bytes, qbytes))) return rc;
+struct ShardBatch {
+  vc_sharded* h;
+  const void* d_queries;
+  uint32_t nq, k, mode;
+  uint64_t* d_out;
+  uint32_t* d_counts;
+  vc_query_stats* d_stats;
+  hipStream_t S;
+  uint32_t r_cap;
+  SlotLayout L;
+  size_t qbytes;
+  std::vector<int> lane_rc;             // run_lane: the first failure of every lane, reported by run_lanes
+  std::vector<std::string> lane_err;
+
+  // every lane's gather buffer and query copy, the count buffer
+  int prepare_lanes() {
+    int rc;
+    for (uint32_t li = 0; li < h->lanes.size(); ++li) {
+      Lane& l = h->lanes[li];
+      const bool everything = li == h->root_lane || h->exchange == VC_EXCHANGE_RCCL;   // gathered results of all shards land here
+      VS_HIP(h, hipSetDevice(l.dev));
+      if ((rc = l.buf[LANE_GATH].grow(h, L.words * 8 * (everything ? h->G : l.shards.back() + 1)))) return rc;
+      if (li != h->root_lane && (rc = l.buf[LANE_Q].grow(h, qbytes))) return rc;
+    }
+    if (!d_counts) {
+      VS_HIP(h, hipSetDevice(h->root));
+      if ((rc = counts_or_own(h, nq, &d_counts))) return rc;
+    }
+    return VC_OK;
   }
-  Lane& R = h->lanes[h->root_lane];
-  if (!d_counts) {
-    VS_HIP(h, hipSetDevice(h->root));
-    if ((rc = sgrow(h, &h->d_ocnt, &h->ocnt_bytes, (size_t)nq * 4))) return rc;
-    d_counts = h->d_ocnt;
-  }
-  // ---- the queries reach every device once: an event on the caller's stream, a peer copy per remote lane
-  if (h->lanes.size() > 1) {
+
+  // the queries reach every device once: an event on the caller's stream, a peer copy per remote lane
+  int send_queries() {
+    if (h->lanes.size() <= 1) return VC_OK;
     VS_HIP(h, hipSetDevice(h->root));
     VS_HIP(h, hipEventRecord(h->ev_q, S));
     for (uint32_t li = 0; li < h->lanes.size(); ++li) {
@@ -448,24 +499,25 @@ static int sharded_search_dev(vc_sharded* h, const void* d_queries, uint32_t nq,
       Lane& l = h->lanes[li];
       VS_HIP(h, hipSetDevice(l.dev));
       VS_HIP(h, hipStreamWaitEvent(l.stream, h->ev_q, 0));   // also orders the lane behind the previous batch's copies out of its slots
-      VS_HIP(h, hipMemcpyPeerAsync(l.q, l.dev, d_queries, h->root, qbytes, l.stream));
+      VS_HIP(h, hipMemcpyPeerAsync(l.buf[LANE_Q].p, l.dev, d_queries, h->root, qbytes, l.stream));
     }
+    return VC_OK;
   }
-  // ---- every shard answers the batch for its id range, the shards of a device one after the other
-  std::vector<int> lane_rc(h->lanes.size(), VC_OK);
-  std::vector<std::string> lane_err(h->lanes.size());
-  auto run_lane = [&](uint32_t li) {
+
+  // the shards of one device answer the batch for their id ranges, one after the other (on a host thread of its own in the
+  // MIH modes: binds the lane's device for that thread, touches only the lane's lane_rc / lane_err)
+  void run_lane(uint32_t li) {
     Lane& l = h->lanes[li];
     const bool is_root = li == h->root_lane;
     hipStream_t ls = is_root ? S : l.stream;
-    const void* q = is_root ? d_queries : l.q;
+    const void* q = is_root ? d_queries : l.q();
     auto hip = [&](hipError_t r, const char* what) {
       if (r != hipSuccess && lane_rc[li] == VC_OK) { lane_rc[li] = VC_ERR_HIP; lane_err[li] = std::string(what) + ": " + hipGetErrorString(r); }
       return r == hipSuccess;
     };
     if (!hip(hipSetDevice(l.dev), "hipSetDevice")) return;
     for (uint32_t g : l.shards) {
-      uint64_t* slot = l.gath + (size_t)g * L.words;
+      uint64_t* slot = l.slot(g, L.words);
       if (shard_size(h, g) == 0) {
         // an empty shard (a store filled below its capacity) contributes INF rows, zero counts, zero statistics; its engine
         // is never asked -- an exact radius loop over nothing would walk every shell of every table (search_worker.cc:170)
@@ -479,45 +531,74 @@ static int sharded_search_dev(vc_sharded* h, const void* d_queries, uint32_t nq,
       if (r != VC_OK) { lane_rc[li] = r; lane_err[li] = std::string("shard ") + std::to_string(g) + ": " + vc_last_error(h->eng[g]); return; }
     }
     if (!is_root) hip(hipEventRecord(l.done, ls), "hipEventRecord");
-  };
-  if (mode == VC_MODE_LINEAR || h->lanes.size() == 1) {
-    for (uint32_t li = 0; li < h->lanes.size(); ++li) run_lane(li);
-  } else {
-    std::vector<std::thread> th;
-    for (uint32_t li = 0; li < h->lanes.size(); ++li) th.emplace_back(run_lane, li);
-    for (auto& t : th) t.join();
   }
-  for (uint32_t li = 0; li < h->lanes.size(); ++li)
-    if (lane_rc[li]) return sfail(h, lane_rc[li], "%s", lane_err[li].c_str());
-  // ---- ONE exchange (replaces gather_vectors, mpi_coordinator.cc:34-69): every shard's slot -> the root's gather buffer
-  if (h->exchange == VC_EXCHANGE_RCCL) {
-    ncclResult_t nr = h->rccl.GroupStart();
-    for (uint32_t g = 0; g < h->G && nr == ncclSuccess; ++g) {   // rank g = shard g = its device's lane; in place: the send slot sits in the receive buffer
-      Lane& l = h->lanes[h->lane_of[g]];
-      nr = h->rccl.AllGather(l.gath + (size_t)g * L.words, l.gath, L.words, ncclUint64, h->comms[g], h->lane_of[g] == h->root_lane ? S : l.stream);
+
+  // every lane: in turn where nothing waits (LINEAR) or there is one lane, else concurrently
+  int run_lanes() {
+    lane_rc.assign(h->lanes.size(), VC_OK);
+    lane_err.assign(h->lanes.size(), std::string());
+    if (mode == VC_MODE_LINEAR || h->lanes.size() == 1) {
+      for (uint32_t li = 0; li < h->lanes.size(); ++li) run_lane(li);
+    } else {
+      std::vector<std::thread> th;
+      for (uint32_t li = 0; li < h->lanes.size(); ++li) th.emplace_back([this, li] { run_lane(li); });
+      for (auto& t : th) t.join();
     }
-    const ncclResult_t ne = h->rccl.GroupEnd();
-    if (nr == ncclSuccess) nr = ne;
-    if (nr != ncclSuccess) return sfail(h, VC_ERR_HIP, "ncclAllGather: %s", h->rccl.GetErrorString(nr));
-  } else {
+    for (uint32_t li = 0; li < h->lanes.size(); ++li)
+      if (lane_rc[li]) return sfail(h, lane_rc[li], "%s", lane_err[li].c_str());
+    return VC_OK;
+  }
+
+  // ONE exchange (replaces gather_vectors, mpi_coordinator.cc:34-69): every shard's slot -> the root's gather buffer
+  int exchange() {
+    Lane& R = h->root_lane_ref();
+    if (h->exchange == VC_EXCHANGE_RCCL) {
+      ncclResult_t nr = h->rccl.GroupStart();
+      for (uint32_t g = 0; g < h->G && nr == ncclSuccess; ++g) {   // rank g = shard g = its device's lane; in place: the send slot sits in the receive buffer
+        Lane& l = h->lanes[h->lane_of[g]];
+        nr = h->rccl.AllGather(l.slot(g, L.words), l.gath(), L.words, ncclUint64, h->comms[g], h->lane_of[g] == h->root_lane ? S : l.stream);
+      }
+      const ncclResult_t ne = h->rccl.GroupEnd();
+      if (nr == ncclSuccess) nr = ne;
+      if (nr != ncclSuccess) return sfail(h, VC_ERR_HIP, "ncclAllGather: %s", h->rccl.GetErrorString(nr));
+      return VC_OK;
+    }
     VS_HIP(h, hipSetDevice(h->root));
     for (uint32_t li = 0; li < h->lanes.size(); ++li) {
       if (li == h->root_lane) continue;      // the root's shards wrote their slots in place
       Lane& l = h->lanes[li];
       VS_HIP(h, hipStreamWaitEvent(S, l.done, 0));
       for (uint32_t g : l.shards)
-        VS_HIP(h, hipMemcpyPeerAsync(R.gath + (size_t)g * L.words, h->root, l.gath + (size_t)g * L.words, l.dev, L.words * 8, S));
+        VS_HIP(h, hipMemcpyPeerAsync(R.slot(g, L.words), h->root, l.slot(g, L.words), l.dev, L.words * 8, S));
     }
+    return VC_OK;
   }
-  // ---- merge (replaces the master's heap, search_worker.cc:179-199); a flagged shard row flags the merged row
-  VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, vc_launch_select_slots(R.gath, L.words, (uint32_t)L.cnt_off, h->G, nq, k, d_out, d_counts, S));
-  if (d_stats) {
-    hipLaunchKernelGGL(vc_sharded_stats_kernel, dim3((nq + 255) / 256), dim3(256), 0, S, (const uint64_t*)R.gath, (uint64_t)L.words,
-                       (uint64_t)L.stats_off, h->G, nq, (const uint32_t*)d_counts, d_stats);
-    VS_HIP(h, hipGetLastError());
+
+  // merge (replaces the master's heap, search_worker.cc:179-199); a flagged shard row flags the merged row.
+  // Returns with the root device current.
+  int merge() {
+    Lane& R = h->root_lane_ref();
+    VS_HIP(h, hipSetDevice(h->root));
+    VS_HIP(h, vc_launch_select_slots(R.gath(), L.words, (uint32_t)L.cnt_off, h->G, nq, k, d_out, d_counts, S));
+    if (d_stats) {
+      hipLaunchKernelGGL(vc_sharded_stats_kernel, dim3((nq + 255) / 256), dim3(256), 0, S, (const uint64_t*)R.gath(), (uint64_t)L.words,
+                         (uint64_t)L.stats_off, h->G, nq, (const uint32_t*)d_counts, d_stats);
+      VS_HIP(h, hipGetLastError());
+    }
+    return VC_OK;
   }
-  return VC_OK;
+};
+
+// Any device may be current on entry; the root device is on a successful return.
+static int sharded_search_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out,
+                              uint32_t* d_counts, vc_query_stats* d_stats, hipStream_t S, uint32_t r_cap = VC_NO_CAP) {
+  ShardBatch b{h, d_queries, nq, k, mode, d_out, d_counts, d_stats, S, r_cap, SlotLayout(nq, k, d_stats != nullptr), (size_t)nq * h->nbytes, {}, {}};
+  int rc = b.prepare_lanes();
+  if (!rc) rc = b.send_queries();
+  if (!rc) rc = b.run_lanes();
+  if (!rc) rc = b.exchange();
+  if (!rc) rc = b.merge();
+  return rc;
 }
 
 // ---- VC_FLAG_GLOBAL_STOP ------------------------------------------------------------------------------------------------
@@ -529,13 +610,15 @@ static int sharded_search_dev(vc_sharded* h, const void* d_queries, uint32_t nq,
 //   * a shard's rows hold every one of its items below m (e_g + 1) (pigeonhole), so D <= m (e_lo + 1) over the non-empty
 //     shards makes D the union's exact k-th distance D*; a shard that stopped by its own rule always meets it;
 //   * the union loop stops at R = ceil(D* / mult) - 1 (0 for D* = 0) -- when mult == m and D* = m r0 it may already stop at
-//     r0 - 1 (then R = r0 - 1 iff shell r0 - 1 holds k items at or below D*: mih_replay_kernel's rule), else at r0;
+//     r0 - 1 (then R = r0 - 1 iff shell r0 - 1 holds k items at or below D*: mih_replay_kernel's rule), else at r0
+//     (gs_stop_shell);
 //   * no shard stops before R (its local k-th distance is never below the union's), so in a round capped at t = R every shard
 //     ends at e_g = R: the merged rows are the union loop's rows at R and the shards' candidate counts add up to its count.
 // A query is settled when its round ended every shard in the shell R requires; otherwise the kernel files it under the cap
 // the next round needs.  Queries that need a shell beyond the shards' in-block reach (far or uniform queries) go to the
 // union scan: LINEAR over the shards gives D* and the rows, mih_tie_collect_kernel decides the tie at the threshold and
 // vc_launch_minsub_count counts the candidates -- the union-wide counterpart of the single engine's scan + replay.
+// The host side is GsSearch below: sharded_global_stop() shows the rounds, GsSearch::union_scan() the scan.
 #define GS_CAPS 17u   // caps 0..16 (inblock_last_shell never goes beyond 16)
 
 __device__ __forceinline__ unsigned long long gs_leaves(uint32_t S, uint32_t R) {   // table 0's gets of shells 0..R: sum of C(S, r)
@@ -547,10 +630,55 @@ __device__ __forceinline__ unsigned long long gs_leaves(uint32_t S, uint32_t R) 
   return sum;
 }
 
-__global__ void __launch_bounds__(256) gs_iota_kernel(uint32_t* __restrict__ p, uint32_t n) {
+// Where the union's radius loop stops once its k-th distance is D (m tables of S-bit substrings, stop multiplier mult): the
+// loop leaves shell r when D <= mult (r + 1) (search_worker.cc:201-205), i.e. in shell rs = ceil(D / mult) - 1, its last
+// shell at the latest.  `tie`: D sits exactly on the threshold of shell rs + 1 while the pigeonhole bound of shell rs is the
+// same D (mult == m), so shell rs stops the loop only if it already holds k items at or below D, else shell rs + 1 does.
+// mih_replay_kernel (vc_mih.hip) states the same rule for the single engine's scan; the two must agree.
+struct GsStopShell {
+  uint32_t rs;
+  bool tie;
+};
+__device__ __forceinline__ GsStopShell gs_stop_shell(uint32_t D, uint32_t m, uint32_t S, uint32_t mult) {
+  return {min(S, D == 0 ? 0u : (D + mult - 1) / mult - 1), mult == m && D != 0 && D % m == 0};
+}
+
+extern "C" __global__ void __launch_bounds__(256) gs_iota_kernel(uint32_t* __restrict__ p, uint32_t n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = i;
 }
+
+// Queries per cap: what gs_settle_kernel counts into the next round's lists, and what the host reads back after a round.
+struct GsCapCounters {
+  uint32_t at_cap[GS_CAPS];
+};
+#define GS_CTR_SLOT_WORDS 32u   // words a counter block occupies in the buffer
+static_assert(sizeof(GsCapCounters) == GS_CAPS * 4 && sizeof(GsCapCounters) <= GS_CTR_SLOT_WORDS * 4,
+              "gs_settle_kernel indexes next_ctr[cap], cap <= reach < GS_CAPS; a block fits its slot");
+
+// vc_sharded::buf[GS_LISTS] of one call: list[0] | list[1] | ctr[0] | ctr[1] | scan_ctr | scan[nq] | floor_[nq].
+// list[i] is [GS_CAPS][nq]: under cap t the queries whose next round is capped at shell t, ctr[i]->at_cap[t] of them.  One
+// set is the round that runs, the other is filled by its settle kernels; the sets swap after a round.
+struct GsRoundLists {
+  uint32_t* list[2];
+  GsCapCounters* ctr[2];
+  uint32_t* scan_ctr;   // entries of scan
+  uint32_t* scan;       // the queries for the union scan
+  uint32_t* floor_;     // per query: the union loop cannot stop below this shell
+  uint32_t nq;
+  static size_t words(uint32_t nq) { return 2 * (size_t)GS_CAPS * nq + 3 * (size_t)GS_CTR_SLOT_WORDS + 2 * (size_t)nq; }
+  static GsRoundLists carve(uint32_t* base, uint32_t nq) {
+    GsRoundLists ls{};
+    ls.nq = nq;
+    for (uint32_t*& l : ls.list) { l = base; base += (size_t)GS_CAPS * nq; }
+    for (GsCapCounters*& c : ls.ctr) { c = (GsCapCounters*)base; base += GS_CTR_SLOT_WORDS; }
+    ls.scan_ctr = base; base += GS_CTR_SLOT_WORDS;
+    ls.scan = base; base += nq;
+    ls.floor_ = base;
+    return ls;
+  }
+  uint32_t* of_cap(int set, uint32_t t) const { return list[set] + (size_t)t * nq; }
+};
 
 struct GsSettleArgs {
   const uint64_t* base;          // the round's gathered slots (rows | counts | statistics per shard)
@@ -570,7 +698,7 @@ struct GsSettleArgs {
   uint32_t* scan_ctr;
 };
 
-__global__ void __launch_bounds__(256) gs_settle_kernel(const GsSettleArgs a) {
+extern "C" __global__ void __launch_bounds__(256) gs_settle_kernel(const GsSettleArgs a) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= a.n) return;
   const uint32_t q = a.list[j];
@@ -597,9 +725,8 @@ __global__ void __launch_bounds__(256) gs_settle_kernel(const GsSettleArgs a) {
   } else if (D > a.m * (e_lo + 1)) {
     next = (D + a.m - 1) / a.m - 1;                  // pigeonhole not met: D only bounds D* from above
   } else {
-    const uint32_t rs = min(a.S, D == 0 ? 0u : (D + a.mult - 1) / a.mult - 1);
-    const bool tie = a.mult == a.m && D != 0 && D % a.m == 0;
-    const uint32_t want = (tie && flo > rs) ? rs + 1 : rs;
+    const GsStopShell stop = gs_stop_shell(D, a.m, a.S, a.mult);
+    const uint32_t want = (stop.tie && flo > stop.rs) ? stop.rs + 1 : stop.rs;
     if (e_lo == want && e_hi == want) R = want;
     else next = want;
   }
@@ -623,8 +750,28 @@ __global__ void __launch_bounds__(256) gs_settle_kernel(const GsSettleArgs a) {
   }
 }
 
-// union scan, step 1: the rule applied to the LINEAR rows (sd = [dist | radius | need | R | iota | ones], nq apart)
-__global__ void __launch_bounds__(256) gs_scan_plan_kernel(uint32_t n, uint32_t k, uint32_t m, uint32_t S, uint32_t mult,
+// The union scan's per-query words ("sd"): six columns of nq words each, in this order, row j = the j-th query of the scan
+// list.  Written by gs_scan_plan_kernel on the root, copied to every lane, read there by the tie collection and the count.
+template <class Word>
+struct GsScanCols {
+  Word* dist;     // D where the tie at the threshold is open (need > 0), else 0: vc_launch_tie_collect's d_dist
+  Word* radius;   // the shell rs whose ties decide (vc_launch_tie_collect's d_radius)
+  Word* need;     // how many ties of shell rs complete the k rows; 0: nothing to decide
+  Word* R;        // the shell the union loop stops in (vc_launch_minsub_count's d_radius; the final statistics)
+  Word* iota;     // j: vc_launch_minsub_count's query list
+  Word* ones;     // 1: vc_launch_minsub_count's flags
+  static __host__ __device__ size_t words(uint32_t nq) { return sizeof(GsScanCols) / sizeof(Word*) * (size_t)nq; }
+  static __host__ __device__ GsScanCols carve(Word* base, uint32_t nq) {
+    GsScanCols c;
+    for (Word** col : {&c.dist, &c.radius, &c.need, &c.R, &c.iota, &c.ones}) { *col = base; base += nq; }
+    return c;
+  }
+};
+using GsScanWords = GsScanCols<uint32_t>;
+using GsScanWordsIn = GsScanCols<const uint32_t>;
+
+// union scan, step 1: the rule applied to the LINEAR rows
+extern "C" __global__ void __launch_bounds__(256) gs_scan_plan_kernel(uint32_t n, uint32_t k, uint32_t m, uint32_t S, uint32_t mult,
                                                            const uint32_t* __restrict__ list, const uint32_t* __restrict__ floor_,
                                                            const uint64_t* __restrict__ rows, const uint32_t* __restrict__ cnt,
                                                            uint32_t* __restrict__ sd, uint32_t nq) {
@@ -635,51 +782,53 @@ __global__ void __launch_bounds__(256) gs_scan_plan_kernel(uint32_t n, uint32_t 
   uint32_t dist = 0, rad = 0, need = 0, R = S;       // fewer than k items: the loop runs to its last shell
   if (c == k) {
     const uint32_t D = (uint32_t)(row[k - 1] >> 32);
-    const uint32_t rs = min(S, D == 0 ? 0u : (D + mult - 1) / mult - 1);
-    R = rs;
-    if (mult == m && D != 0 && D % m == 0) {
-      if (floor_[list[j]] > rs) {
-        R = rs + 1;
+    const GsStopShell stop = gs_stop_shell(D, m, S, mult);
+    R = stop.rs;
+    if (stop.tie) {
+      if (floor_[list[j]] > stop.rs) {
+        R = stop.rs + 1;
       } else {                                       // does shell rs = D/m - 1 already hold k items at or below D?
         uint32_t below = 0;
         while (below < k && (uint32_t)(row[below] >> 32) < D) ++below;
         dist = D;
-        rad = rs;
+        rad = stop.rs;
         need = k - below;
       }
     }
   }
-  sd[j] = dist;
-  sd[nq + j] = rad;
-  sd[2 * (size_t)nq + j] = need;
-  sd[3 * (size_t)nq + j] = R;
-  sd[4 * (size_t)nq + j] = j;
-  sd[5 * (size_t)nq + j] = 1;
+  const GsScanWords w = GsScanWords::carve(sd, nq);
+  w.dist[j] = dist;
+  w.radius[j] = rad;
+  w.need[j] = need;
+  w.R[j] = R;
+  w.iota[j] = j;
+  w.ones[j] = 1;
 }
 
 // union scan, step 2: the shards' ties (ids ascending within a shard, shards in id order) decide the tie at the threshold
-__global__ void __launch_bounds__(256) gs_scan_tie_kernel(uint32_t n, uint32_t k, uint32_t G, uint32_t* __restrict__ sd, uint32_t nq,
+extern "C" __global__ void __launch_bounds__(256) gs_scan_tie_kernel(uint32_t n, uint32_t k, uint32_t G, uint32_t* __restrict__ sd, uint32_t nq,
                                                           const uint32_t* __restrict__ tie_ids, const uint32_t* __restrict__ tie_cnt,
                                                           uint64_t* __restrict__ rows) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  const uint32_t need = sd[2 * (size_t)nq + j], rs = sd[nq + j], D = sd[j];
+  const GsScanWords w = GsScanWords::carve(sd, nq);
+  const uint32_t need = w.need[j], rs = w.radius[j], D = w.dist[j];
   if (need == 0) return;
   uint32_t total = 0;
   for (uint32_t g = 0; g < G; ++g) total += tie_cnt[(size_t)g * nq + j];
   if (total < need) {
-    sd[3 * (size_t)nq + j] = rs + 1;                 // shell rs has too few: the loop stops at D/m with the scan's rows
+    w.R[j] = rs + 1;                                 // shell rs has too few: the loop stops at D/m with the scan's rows
     return;
   }
-  uint32_t w = k - need;                             // the rows below D stay; the ties of shell rs follow, smallest ids first
-  for (uint32_t g = 0; g < G && w < k; ++g)
-    for (uint32_t i = 0; i < tie_cnt[(size_t)g * nq + j] && w < k; ++i)
-      rows[(uint64_t)j * k + w++] = ((uint64_t)D << 32) | tie_ids[((size_t)g * nq + j) * k + i];
-  sd[3 * (size_t)nq + j] = rs;
+  uint32_t wr = k - need;                            // the rows below D stay; the ties of shell rs follow, smallest ids first
+  for (uint32_t g = 0; g < G && wr < k; ++g)
+    for (uint32_t i = 0; i < tie_cnt[(size_t)g * nq + j] && wr < k; ++i)
+      rows[(uint64_t)j * k + wr++] = ((uint64_t)D << 32) | tie_ids[((size_t)g * nq + j) * k + i];
+  w.R[j] = rs;
 }
 
 // union scan, step 3: rows, counts and the statistics of one SearchWorker stopping at R
-__global__ void __launch_bounds__(256) gs_scan_final_kernel(uint32_t n, uint32_t k, uint32_t S, const uint32_t* __restrict__ list,
+extern "C" __global__ void __launch_bounds__(256) gs_scan_final_kernel(uint32_t n, uint32_t k, uint32_t S, const uint32_t* __restrict__ list,
                                                             const uint32_t* __restrict__ sd, uint32_t nq, const uint64_t* __restrict__ rows,
                                                             const uint32_t* __restrict__ cnt, const unsigned long long* __restrict__ seen,
                                                             uint32_t n_lanes, uint64_t* __restrict__ out, uint32_t* __restrict__ out_cnt,
@@ -690,7 +839,7 @@ __global__ void __launch_bounds__(256) gs_scan_final_kernel(uint32_t n, uint32_t
   for (uint32_t i = 0; i < k; ++i) out[(uint64_t)q * k + i] = rows[(uint64_t)j * k + i];
   out_cnt[q] = cnt[j];
   if (out_stats) {
-    const uint32_t R = sd[3 * (size_t)nq + j];
+    const uint32_t R = GsScanWordsIn::carve(sd, nq).R[j];
     vc_query_stats s{};
     s.radius = R;
     s.n_results = cnt[j];
@@ -700,191 +849,313 @@ __global__ void __launch_bounds__(256) gs_scan_final_kernel(uint32_t n, uint32_t
   }
 }
 
-static int sharded_global_stop(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out, uint32_t* d_counts,
-                               vc_query_stats* d_stats, hipStream_t S) {
-  const uint32_t W = h->nbytes / 8, m = h->cfg.engine.n_tables, Sb = h->cfg.engine.bits / m;
-  const uint32_t mult = (h->cfg.engine.flags & VC_FLAG_REF_STOP_LITERAL4) ? 4u : std::min(m, 4u);
-  const bool trace = h->knobs.gs_trace;   // dev: per-round wall times on stderr
-  uint32_t nonempty = 0, reach = GS_CAPS - 1;
-  std::vector<VcEngineView> view(h->G);
-  for (uint32_t g = 0; g < h->G; ++g) {
-    vc_engine_view(h->eng[g], &view[g]);
-    if (shard_size(h, g) == 0) continue;
-    nonempty |= 1u << g;
-    reach = std::min(reach, view[g].reach);
+// The union scan's words on one device: seen | sd | tie_cnt | tie_ids | chunk_scratch, everything nq apart per row so that
+// what crosses devices is a run of n <= nq words.  Two shapes of the one layout:
+//   the root (gs_root_block, vc_sharded::buf[GS_SCAN]): a seen row per LANE, tie counts / ids per shard of the store, no scratch;
+//   a lane (gs_lane_block, Lane::buf[LANE_AUX]):        one seen row, tie counts / ids per shard of the LANE, the tie kernel's scratch.
+struct GsScanBlock {
+  unsigned long long* seen;   // [seen_rows][nq] candidates of the union loop up to R (vc_launch_minsub_count)
+  uint32_t* sd;               // GsScanCols
+  uint32_t* tie_cnt;          // [shards][nq]
+  uint32_t* tie_ids;          // [shards][nq][k]
+  uint32_t* chunk_scratch;    // [nq][VC_TIE_CHUNKS] (lanes only, else null)
+  uint32_t nq, k;
+  unsigned long long* seen_of(uint32_t row) const { return seen + (size_t)row * nq; }
+  uint32_t* cnt_of(size_t shard) const { return tie_cnt + shard * nq; }
+  uint32_t* ids_of(size_t shard) const { return tie_ids + shard * nq * k; }
+  static size_t words(size_t seen_rows, size_t shards, uint32_t nq, uint32_t k, bool scratch) {
+    return seen_rows * nq * (sizeof(unsigned long long) / 4) + GsScanWords::words(nq) + shards * nq + shards * nq * k +
+           (scratch ? (size_t)nq * VC_TIE_CHUNKS : 0);
   }
-  int rc;
-  VS_HIP(h, hipSetDevice(h->root));
-  if (!d_counts) {
-    if ((rc = sgrow(h, &h->d_ocnt, &h->ocnt_bytes, (size_t)nq * 4))) return rc;
-    d_counts = h->d_ocnt;
+  static GsScanBlock carve(uint32_t* base, size_t seen_rows, size_t shards, uint32_t nq, uint32_t k, bool scratch) {
+    GsScanBlock b{};
+    b.nq = nq;
+    b.k = k;
+    b.seen = (unsigned long long*)base; base += seen_rows * nq * (sizeof(unsigned long long) / 4);
+    b.sd = base;                        base += GsScanWords::words(nq);
+    b.tie_cnt = base;                   base += shards * nq;
+    b.tie_ids = base;                   base += shards * nq * k;
+    b.chunk_scratch = scratch ? base : nullptr;
+    return b;
   }
-  const size_t LW = (size_t)GS_CAPS * nq;   // words of one set of round lists
-  if ((rc = sgrow(h, &h->gs_u32, &h->gs_u32_bytes, (2 * LW + 2 * (size_t)nq + 96) * 4))) return rc;
-  if ((rc = sgrow(h, &h->gs_q, &h->gs_q_bytes, (size_t)nq * h->nbytes))) return rc;
-  if ((rc = sgrow(h, &h->gs_rows, &h->gs_rows_bytes, (size_t)nq * k * 8))) return rc;
-  if ((rc = sgrow(h, &h->gs_cnt, &h->gs_cnt_bytes, (size_t)nq * 4))) return rc;
-  if ((rc = sgrow(h, &h->gs_st, &h->gs_st_bytes, (size_t)nq * sizeof(vc_query_stats)))) return rc;
-  uint32_t* lists[2] = {h->gs_u32, h->gs_u32 + LW};
-  uint32_t* ctr[2] = {h->gs_u32 + 2 * LW, h->gs_u32 + 2 * LW + 32};
-  uint32_t* scan_ctr = h->gs_u32 + 2 * LW + 64;
-  uint32_t* scan = h->gs_u32 + 2 * LW + 96;
-  uint32_t* floor_ = scan + nq;
-  VS_HIP(h, hipMemsetAsync(floor_, 0, (size_t)nq * 4, S));
-  VS_HIP(h, hipMemsetAsync(scan_ctr, 0, 4, S));
-  std::vector<uint32_t> n_at(GS_CAPS + 1, 0);   // queries per cap of the coming round | union scan
-  uint32_t n_scan = 0;
-  if (nonempty == 0) {   // nothing to probe: the union scan reports the empty union (R = last shell, no candidates)
-    hipLaunchKernelGGL(gs_iota_kernel, dim3((nq + 255) / 256), dim3(256), 0, S, scan, nq);
-    VS_HIP(h, hipGetLastError());
-    n_scan = nq;
-  } else {
-    const uint32_t t0 = std::min(h->knobs.gs_cap, reach);
-    hipLaunchKernelGGL(gs_iota_kernel, dim3((nq + 255) / 256), dim3(256), 0, S, lists[0] + (size_t)t0 * nq, nq);
-    VS_HIP(h, hipGetLastError());
-    n_at[t0] = nq;
-  }
-  Lane& Rl = h->lanes[h->root_lane];
-  int cur = 0;
-  for (uint32_t round = 0; round < 8; ++round) {
-    bool any = false;
-    for (uint32_t t = 0; t < GS_CAPS; ++t) any = any || n_at[t];
-    if (!any) break;
-    const auto t_round = std::chrono::steady_clock::now();
+};
+// (the owning device is current: the buffer may grow)
+static int gs_root_block(vc_sharded* h, uint32_t nq, uint32_t k, GsScanBlock* out) {
+  if (int rc = h->buf[GS_SCAN].grow(h, GsScanBlock::words(h->lanes.size(), h->G, nq, k, false) * 4)) return rc;
+  *out = GsScanBlock::carve(h->buf[GS_SCAN].as<uint32_t>(), h->lanes.size(), h->G, nq, k, false);
+  return VC_OK;
+}
+static int gs_lane_block(vc_sharded* h, Lane& l, uint32_t nq, uint32_t k, GsScanBlock* out) {
+  if (int rc = l.buf[LANE_AUX].grow(h, GsScanBlock::words(1, l.shards.size(), nq, k, true) * 4)) return rc;
+  *out = GsScanBlock::carve(l.buf[LANE_AUX].as<uint32_t>(), 1, l.shards.size(), nq, k, true);
+  return VC_OK;
+}
+
+#define GS_MAX_ROUNDS 8u   // the rounds settle a query in at most four: the first cap, the pigeonhole cap, R, and R + 1 after a tie; 8 is a bound
+
+// One flagged call: what is fixed for it, and its steps in the order sharded_global_stop() and union_scan() take them.
+// Current device: every step is entered and left with the ROOT device current (prepare() binds it; sharded_search_dev and
+// over_lanes, the two that bind others, return with it).
+struct GsSearch {
+  vc_sharded* h;
+  const void* d_queries;
+  uint32_t nq, k;
+  uint64_t* d_out;
+  uint32_t* d_counts;
+  vc_query_stats* d_stats;
+  hipStream_t S;
+  // ---- fixed by prepare()
+  uint32_t W, m, Sb, mult;
+  uint32_t nonempty;                 // bit g: shard g holds records
+  uint32_t reach;                    // last shell every non-empty shard's query kernel reaches: the largest cap of a round
+  bool trace;                        // dev (VC_MIH_GS_TRACE): per-round wall times on stderr
+  std::vector<VcEngineView> view;
+  GsRoundLists ls;
+  uint64_t* gs_q;                    // the gathered queries of a cap group / of the union scan
+  uint64_t* rows;                    // their merged rows, counts, statistics
+  uint32_t* cnt;
+  vc_query_stats* st;
+  // ---- the rounds
+  int cur;                           // the list set of the round that runs
+  GsCapCounters todo;                // queries per cap of the coming round
+  uint32_t n_scan;                   // queries of the union scan so far
+  GsScanBlock rb;                    // the root's union-scan words (union_scan)
+
+  int prepare() {
+    W = h->nbytes / 8; m = h->cfg.engine.n_tables; Sb = h->cfg.engine.bits / m;
+    mult = (h->cfg.engine.flags & VC_FLAG_REF_STOP_LITERAL4) ? 4u : std::min(m, 4u);
+    trace = h->knobs.gs_trace;
+    nonempty = 0; reach = GS_CAPS - 1;
+    view.resize(h->G);
+    for (uint32_t g = 0; g < h->G; ++g) {
+      vc_engine_view(h->eng[g], &view[g]);
+      if (shard_size(h, g) == 0) continue;
+      nonempty |= 1u << g;
+      reach = std::min(reach, view[g].reach);
+    }
+    int rc;
     VS_HIP(h, hipSetDevice(h->root));
-    VS_HIP(h, hipMemsetAsync(ctr[cur ^ 1], 0, GS_CAPS * 4, S));
+    if ((rc = counts_or_own(h, nq, &d_counts))) return rc;
+    if ((rc = h->buf[GS_LISTS].grow(h, GsRoundLists::words(nq) * 4))) return rc;
+    if ((rc = h->buf[GS_Q].grow(h, (size_t)nq * h->nbytes))) return rc;
+    if ((rc = h->buf[GS_ROWS].grow(h, (size_t)nq * k * 8))) return rc;
+    if ((rc = h->buf[GS_CNT].grow(h, (size_t)nq * 4))) return rc;
+    if ((rc = h->buf[GS_ST].grow(h, (size_t)nq * sizeof(vc_query_stats)))) return rc;
+    ls = GsRoundLists::carve(h->buf[GS_LISTS].as<uint32_t>(), nq);
+    gs_q = h->buf[GS_Q].as<uint64_t>();
+    rows = h->buf[GS_ROWS].as<uint64_t>();
+    cnt = h->buf[GS_CNT].as<uint32_t>();
+    st = h->buf[GS_ST].as<vc_query_stats>();
+    cur = 0; todo = GsCapCounters{}; n_scan = 0;
+    VS_HIP(h, hipMemsetAsync(ls.floor_, 0, (size_t)nq * 4, S));
+    VS_HIP(h, hipMemsetAsync(ls.scan_ctr, 0, 4, S));
+    return VC_OK;
+  }
+
+  // every query starts under the first round's cap (VC_MIH_GS_CAP, within the shards' reach) -- or, with nothing to probe, in
+  // the union scan, which reports the empty union (R = last shell, no candidates)
+  int seed_first_round() {
+    const uint32_t t0 = std::min(h->knobs.gs_cap, reach);
+    hipLaunchKernelGGL(gs_iota_kernel, dim3((nq + 255) / 256), dim3(256), 0, S, nonempty == 0 ? ls.scan : ls.of_cap(0, t0), nq);
+    VS_HIP(h, hipGetLastError());
+    if (nonempty == 0) n_scan = nq;
+    else todo.at_cap[t0] = nq;
+    return VC_OK;
+  }
+
+  bool round_open() const {
+    for (uint32_t n : todo.at_cap)
+      if (n) return true;
+    return false;
+  }
+
+  GsSettleArgs settle_args(uint32_t t, uint32_t n, const uint32_t* list) const {   // after the cap group's search: it may grow the slots
+    const SlotLayout L(n, k, true);
+    GsSettleArgs a{};
+    a.base = h->root_lane_ref().gath(); a.slot_words = L.words; a.stats_off = L.stats_off; a.G = h->G; a.nonempty = nonempty;
+    a.n = n; a.t = t; a.k = k; a.m = m; a.S = Sb; a.mult = mult; a.reach = reach; a.nq = nq;
+    a.list = list; a.rows = rows; a.cnt = cnt; a.floor_ = ls.floor_;
+    a.out = d_out; a.out_cnt = d_counts; a.out_stats = d_stats;
+    a.next = ls.list[cur ^ 1]; a.next_ctr = ls.ctr[cur ^ 1]->at_cap; a.scan = ls.scan; a.scan_ctr = ls.scan_ctr;
+    return a;
+  }
+
+  // one round: per cap with queries, gather them, run every shard capped at that shell, merge, and let the settle kernel
+  // finish them or file them in the other list set.  (The host waits inside each shard's capped search, not here.)
+  int run_round() {
+    int rc;
+    VS_HIP(h, hipMemsetAsync(ls.ctr[cur ^ 1], 0, sizeof(GsCapCounters), S));
     for (uint32_t t = 0; t < GS_CAPS; ++t) {
-      const uint32_t n = n_at[t];
+      const uint32_t n = todo.at_cap[t];
       if (!n) continue;
-      const uint32_t* list = lists[cur] + (size_t)t * nq;
-      VS_HIP(h, hipSetDevice(h->root));
-      VS_HIP(h, vc_launch_gather_queries((const uint64_t*)d_queries, list, n, W, h->gs_q, S));
-      if ((rc = sharded_search_dev(h, h->gs_q, n, k, VC_MODE_MIH_EXACT, h->gs_rows, h->gs_cnt, h->gs_st, S, t))) return rc;
-      const SlotLayout L(n, k, true);
-      GsSettleArgs a{};
-      a.base = Rl.gath; a.slot_words = L.words; a.stats_off = L.stats_off; a.G = h->G; a.nonempty = nonempty;
-      a.n = n; a.t = t; a.k = k; a.m = m; a.S = Sb; a.mult = mult; a.reach = reach; a.nq = nq;
-      a.list = list; a.rows = h->gs_rows; a.cnt = h->gs_cnt; a.floor_ = floor_;
-      a.out = d_out; a.out_cnt = d_counts; a.out_stats = d_stats;
-      a.next = lists[cur ^ 1]; a.next_ctr = ctr[cur ^ 1]; a.scan = scan; a.scan_ctr = scan_ctr;
-      VS_HIP(h, hipSetDevice(h->root));
-      hipLaunchKernelGGL(gs_settle_kernel, dim3((n + 255) / 256), dim3(256), 0, S, a);
+      const uint32_t* list = ls.of_cap(cur, t);
+      VS_HIP(h, vc_launch_gather_queries((const uint64_t*)d_queries, list, n, W, gs_q, S));
+      if ((rc = sharded_search_dev(h, gs_q, n, k, VC_MODE_MIH_EXACT, rows, cnt, st, S, t))) return rc;
+      hipLaunchKernelGGL(gs_settle_kernel, dim3((n + 255) / 256), dim3(256), 0, S, settle_args(t, n, list));
       VS_HIP(h, hipGetLastError());
     }
     cur ^= 1;
-    std::vector<uint32_t> c(GS_CAPS + 1);
-    VS_HIP(h, hipMemcpyAsync(c.data(), ctr[cur], GS_CAPS * 4, hipMemcpyDeviceToHost, S));
-    VS_HIP(h, hipMemcpyAsync(c.data() + GS_CAPS, scan_ctr, 4, hipMemcpyDeviceToHost, S));
+    return VC_OK;
+  }
+
+  // the round ends: the host waits for its counters -- what stays open per cap (the coming round) and the union scan's total
+  int read_round_counters(uint32_t round, std::chrono::steady_clock::time_point t_round) {
+    GsCapCounters open;
+    uint32_t open_scan;
+    VS_HIP(h, hipMemcpyAsync(&open, ls.ctr[cur], sizeof(GsCapCounters), hipMemcpyDeviceToHost, S));
+    VS_HIP(h, hipMemcpyAsync(&open_scan, ls.scan_ctr, 4, hipMemcpyDeviceToHost, S));
     VS_HIP(h, hipStreamSynchronize(S));
     if (trace) {
       fprintf(stderr, "[vc_gs] round %u:", round);
-      for (uint32_t t = 0; t < GS_CAPS; ++t) if (n_at[t]) fprintf(stderr, " cap %u x %u", t, n_at[t]);
+      for (uint32_t t = 0; t < GS_CAPS; ++t) if (todo.at_cap[t]) fprintf(stderr, " cap %u x %u", t, todo.at_cap[t]);
       fprintf(stderr, " -> open");
-      for (uint32_t t = 0; t < GS_CAPS; ++t) if (c[t]) fprintf(stderr, " cap %u x %u", t, c[t]);
-      fprintf(stderr, ", union scan %u  %.1f us\n", c[GS_CAPS],
+      for (uint32_t t = 0; t < GS_CAPS; ++t) if (open.at_cap[t]) fprintf(stderr, " cap %u x %u", t, open.at_cap[t]);
+      fprintf(stderr, ", union scan %u  %.1f us\n", open_scan,
               std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_round).count());
     }
-    n_at.assign(c.begin(), c.begin() + GS_CAPS);
-    n_scan = c[GS_CAPS];
+    todo = open;
+    n_scan = open_scan;
+    return VC_OK;
   }
-  // (the rounds settle a query in at most four: the first cap, the pigeonhole cap, R, and R + 1 after a tie; 8 is a bound)
-  for (uint32_t t = 0; t < GS_CAPS; ++t)
-    if (n_at[t]) {
-      VS_HIP(h, hipMemcpyAsync(scan + n_scan, lists[cur] + (size_t)t * nq, (size_t)n_at[t] * 4, hipMemcpyDeviceToDevice, S));
-      n_scan += n_at[t];
-    }
-  if (n_scan == 0) return VC_OK;
-  // ---- the union scan
-  const auto t_scan = std::chrono::steady_clock::now();
-  const uint32_t n = n_scan, NL = (uint32_t)h->lanes.size();
-  VS_HIP(h, hipSetDevice(h->root));
-  // root words: seen [NL][nq] u64 | sd [6][nq] | tie counts [G][nq] | tie ids [G][nq][k]
-  const size_t seen_w = 2 * (size_t)NL * nq, sd_w = 6 * (size_t)nq, tc_w = (size_t)h->G * nq;
-  if ((rc = sgrow(h, &h->gs_scan, &h->gs_scan_bytes, (seen_w + sd_w + tc_w + (size_t)h->G * nq * k) * 4))) return rc;
-  unsigned long long* seen = (unsigned long long*)h->gs_scan;
-  uint32_t* sd = h->gs_scan + seen_w;
-  uint32_t* tie_cnt = sd + sd_w;
-  uint32_t* tie_ids = tie_cnt + tc_w;
-  VS_HIP(h, vc_launch_gather_queries((const uint64_t*)d_queries, scan, n, W, h->gs_q, S));
-  if ((rc = sharded_search_dev(h, h->gs_q, n, k, VC_MODE_LINEAR, h->gs_rows, h->gs_cnt, nullptr, S))) return rc;
-  VS_HIP(h, hipSetDevice(h->root));
-  hipLaunchKernelGGL(gs_scan_plan_kernel, dim3((n + 255) / 256), dim3(256), 0, S, n, k, m, Sb, mult, (const uint32_t*)scan,
-                     (const uint32_t*)floor_, (const uint64_t*)h->gs_rows, (const uint32_t*)h->gs_cnt, sd, nq);
-  VS_HIP(h, hipGetLastError());
-  // one pass over the lanes: the per-query words go out, fn runs the lane's shards, results come back
-  auto over_lanes = [&](auto&& fn) -> int {
-    for (uint32_t li = 0; li < NL; ++li) {
+
+  // what the last round left open joins the union scan's list
+  int leftovers_to_scan() {
+    for (uint32_t t = 0; t < GS_CAPS; ++t)
+      if (todo.at_cap[t]) {
+        VS_HIP(h, hipMemcpyAsync(ls.scan + n_scan, ls.of_cap(cur, t), (size_t)todo.at_cap[t] * 4, hipMemcpyDeviceToDevice, S));
+        n_scan += todo.at_cap[t];
+      }
+    return VC_OK;
+  }
+
+  // ---- the union scan over the n_scan queries of ls.scan
+  // LINEAR over the shards gives the rows and D*; the rule gives R, or leaves the tie at the threshold open
+  int scan_plan() {
+    int rc;
+    const uint32_t n = n_scan;
+    if ((rc = gs_root_block(h, nq, k, &rb))) return rc;
+    VS_HIP(h, vc_launch_gather_queries((const uint64_t*)d_queries, ls.scan, n, W, gs_q, S));
+    if ((rc = sharded_search_dev(h, gs_q, n, k, VC_MODE_LINEAR, rows, cnt, nullptr, S))) return rc;
+    hipLaunchKernelGGL(gs_scan_plan_kernel, dim3((n + 255) / 256), dim3(256), 0, S, n, k, m, Sb, mult, (const uint32_t*)ls.scan,
+                       (const uint32_t*)ls.floor_, (const uint64_t*)rows, (const uint32_t*)cnt, rb.sd, nq);
+    VS_HIP(h, hipGetLastError());
+    return VC_OK;
+  }
+
+  // One pass over the lanes, in lane order: the per-query words (rb.sd) go out to the lane's block, fn enqueues the lane's
+  // shards on the lane's stream and the copies of their results into rb, the root's stream waits for the lane.
+  // Entered and left with the root device current (inside, the lane's device is, for fn too).  Order: a remote lane starts
+  // behind everything enqueued on S so far (ev_q) and S continues behind the lane's last copy (Lane::done); the root lane
+  // runs on S itself.  The queries are where the scan's LINEAR search left them: gs_q on the root, Lane::q() elsewhere.
+  template <class Fn>
+  int over_lanes(Fn&& fn) {
+    int rc;
+    for (uint32_t li = 0; li < h->lanes.size(); ++li) {
       Lane& l = h->lanes[li];
       const bool is_root = li == h->root_lane;
-      hipStream_t ls = is_root ? S : l.stream;
-      const size_t LS = l.shards.size();
-      VS_HIP(h, hipSetDevice(h->root));
+      hipStream_t lstream = is_root ? S : l.stream;
       if (!is_root) VS_HIP(h, hipEventRecord(h->ev_q, S));
       VS_HIP(h, hipSetDevice(l.dev));
-      // lane words: seen [nq] u64 | sd [6][nq] | tie counts [LS][nq] | tie ids [LS][nq][k] | tie chunk counts [nq][VC_TIE_CHUNKS]
-      if ((rc = sgrow(h, &l.aux, &l.aux_bytes, (2 * (size_t)nq + sd_w + LS * nq + LS * nq * k + (size_t)nq * VC_TIE_CHUNKS) * 4))) return rc;
-      if (!is_root) VS_HIP(h, hipStreamWaitEvent(ls, h->ev_q, 0));
-      VS_HIP(h, hipMemcpyPeerAsync(l.aux + 2 * (size_t)nq, l.dev, sd, h->root, sd_w * 4, ls));
-      const uint64_t* lq = is_root ? h->gs_q : (const uint64_t*)l.q;
-      if ((rc = fn(li, l, ls, lq))) return rc;
+      GsScanBlock lb;
+      if ((rc = gs_lane_block(h, l, nq, k, &lb))) return rc;
+      if (!is_root) VS_HIP(h, hipStreamWaitEvent(lstream, h->ev_q, 0));
+      VS_HIP(h, hipMemcpyPeerAsync(lb.sd, l.dev, rb.sd, h->root, GsScanWords::words(nq) * 4, lstream));
+      const uint64_t* lq = is_root ? gs_q : (const uint64_t*)l.q();
+      if ((rc = fn(li, l, lb, lstream, lq))) return rc;
       if (!is_root) {
-        VS_HIP(h, hipEventRecord(l.done, ls));
+        VS_HIP(h, hipEventRecord(l.done, lstream));
         VS_HIP(h, hipSetDevice(h->root));
         VS_HIP(h, hipStreamWaitEvent(S, l.done, 0));
       }
     }
-    VS_HIP(h, hipSetDevice(h->root));
     return VC_OK;
-  };
-  // the tie at the threshold: every shard's smallest-id ties whose substrings reach below D/m
-  if ((rc = over_lanes([&](uint32_t, Lane& l, hipStream_t ls, const uint64_t* lq) -> int {
-         const uint32_t* lsd = l.aux + 2 * (size_t)nq;
-         uint32_t* lcnt = l.aux + 2 * (size_t)nq + sd_w;
-         uint32_t* lids = lcnt + l.shards.size() * nq;
-         for (size_t i = 0; i < l.shards.size(); ++i) {
-           const uint32_t g = l.shards[i];
-           if (!((nonempty >> g) & 1u)) {
-             VS_HIP(h, hipMemsetAsync(lcnt + i * nq, 0, (size_t)n * 4, ls));
-           } else {
-             const VcEngineView& v = view[g];
-             VS_HIP(h, vc_launch_tie_collect(v.cols, v.stride, v.n, W, m, Sb, v.id_base, lq, n, k, lsd, lsd + nq, lsd + 2 * (size_t)nq,
-                                             lids + l.shards.size() * nq * k, lids + i * nq * k, lcnt + i * nq, ls));
-           }
-           VS_HIP(h, hipMemcpyPeerAsync(tie_cnt + (size_t)g * nq, h->root, lcnt + i * nq, l.dev, (size_t)n * 4, ls));
-           VS_HIP(h, hipMemcpyPeerAsync(tie_ids + (size_t)g * nq * k, h->root, lids + i * nq * k, l.dev, (size_t)n * k * 4, ls));
-         }
-         return VC_OK;
-       })))
+  }
+
+  // the tie at the threshold: every shard's smallest-id ties whose substrings reach below D/m, to the root by shard
+  int collect_ties() {
+    const uint32_t n = n_scan;
+    return over_lanes([&](uint32_t, Lane& l, const GsScanBlock& lb, hipStream_t lstream, const uint64_t* lq) -> int {
+      const GsScanWordsIn sd = GsScanWordsIn::carve(lb.sd, nq);
+      for (size_t i = 0; i < l.shards.size(); ++i) {
+        const uint32_t g = l.shards[i];
+        if (!((nonempty >> g) & 1u)) {
+          VS_HIP(h, hipMemsetAsync(lb.cnt_of(i), 0, (size_t)n * 4, lstream));
+        } else {
+          const VcEngineView& v = view[g];
+          VS_HIP(h, vc_launch_tie_collect(v.cols, v.stride, v.n, W, m, Sb, v.id_base, lq, n, k, sd.dist, sd.radius, sd.need,
+                                          lb.chunk_scratch, lb.ids_of(i), lb.cnt_of(i), lstream));
+        }
+        VS_HIP(h, hipMemcpyPeerAsync(rb.cnt_of(g), h->root, lb.cnt_of(i), l.dev, (size_t)n * 4, lstream));
+        VS_HIP(h, hipMemcpyPeerAsync(rb.ids_of(g), h->root, lb.ids_of(i), l.dev, (size_t)n * k * 4, lstream));
+      }
+      return VC_OK;
+    });
+  }
+
+  // the ties complete the rows where shell rs holds enough of them; R is final afterwards
+  int apply_ties() {
+    const uint32_t n = n_scan;
+    hipLaunchKernelGGL(gs_scan_tie_kernel, dim3((n + 255) / 256), dim3(256), 0, S, n, k, h->G, rb.sd, nq, (const uint32_t*)rb.tie_ids,
+                       (const uint32_t*)rb.tie_cnt, rows);
+    VS_HIP(h, hipGetLastError());
+    return VC_OK;
+  }
+
+  // the candidates of the union loop up to R: every item whose minimum substring distance is <= R, summed per lane
+  int count_candidates() {
+    const uint32_t n = n_scan;
+    return over_lanes([&](uint32_t li, Lane& l, const GsScanBlock& lb, hipStream_t lstream, const uint64_t* lq) -> int {
+      const GsScanWordsIn sd = GsScanWordsIn::carve(lb.sd, nq);
+      VS_HIP(h, hipMemsetAsync(lb.seen, 0, (size_t)n * 8, lstream));
+      for (uint32_t g : l.shards) {
+        if (!((nonempty >> g) & 1u)) continue;
+        const VcEngineView& v = view[g];
+        VS_HIP(h, vc_launch_minsub_count(v.cols, v.stride, v.n, W, m, Sb, lq, sd.iota, sd.ones, n, sd.R, lb.seen, v.n_cu, lstream));
+      }
+      VS_HIP(h, hipMemcpyPeerAsync(rb.seen_of(li), h->root, lb.seen, l.dev, (size_t)n * 8, lstream));
+      return VC_OK;
+    });
+  }
+
+  // rows, counts and statistics of the scanned queries into the caller's buffers
+  int scan_finish(std::chrono::steady_clock::time_point t_scan) {
+    const uint32_t n = n_scan;
+    hipLaunchKernelGGL(gs_scan_final_kernel, dim3((n + 255) / 256), dim3(256), 0, S, n, k, Sb, (const uint32_t*)ls.scan, (const uint32_t*)rb.sd,
+                       nq, (const uint64_t*)rows, (const uint32_t*)cnt, (const unsigned long long*)rb.seen, (uint32_t)h->lanes.size(), d_out,
+                       d_counts, d_stats);
+    VS_HIP(h, hipGetLastError());
+    if (trace) {
+      VS_HIP(h, hipStreamSynchronize(S));
+      fprintf(stderr, "[vc_gs] union scan: %u queries  %.1f us\n", n,
+              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_scan).count());
+    }
+    return VC_OK;
+  }
+
+  int union_scan() {
+    const auto t_scan = std::chrono::steady_clock::now();
+    int rc = scan_plan();
+    if (!rc) rc = collect_ties();
+    if (!rc) rc = apply_ties();
+    if (!rc && d_stats) rc = count_candidates();   // (only the statistics need them)
+    if (!rc) rc = scan_finish(t_scan);
     return rc;
-  hipLaunchKernelGGL(gs_scan_tie_kernel, dim3((n + 255) / 256), dim3(256), 0, S, n, k, h->G, sd, nq, (const uint32_t*)tie_ids,
-                     (const uint32_t*)tie_cnt, h->gs_rows);
-  VS_HIP(h, hipGetLastError());
-  // the candidates of the union loop up to R: every item whose minimum substring distance is <= R
-  if (d_stats) {
-    if ((rc = over_lanes([&](uint32_t li, Lane& l, hipStream_t ls, const uint64_t* lq) -> int {
-           const uint32_t* lsd = l.aux + 2 * (size_t)nq;
-           unsigned long long* lseen = (unsigned long long*)l.aux;
-           VS_HIP(h, hipMemsetAsync(lseen, 0, (size_t)n * 8, ls));
-           for (uint32_t g : l.shards) {
-             if (!((nonempty >> g) & 1u)) continue;
-             const VcEngineView& v = view[g];
-             VS_HIP(h, vc_launch_minsub_count(v.cols, v.stride, v.n, W, m, Sb, lq, lsd + 4 * (size_t)nq, lsd + 5 * (size_t)nq, n,
-                                              lsd + 3 * (size_t)nq, lseen, v.n_cu, ls));
-           }
-           VS_HIP(h, hipMemcpyPeerAsync(seen + (size_t)li * nq, h->root, lseen, l.dev, (size_t)n * 8, ls));
-           return VC_OK;
-         })))
-      return rc;
   }
-  hipLaunchKernelGGL(gs_scan_final_kernel, dim3((n + 255) / 256), dim3(256), 0, S, n, k, Sb, (const uint32_t*)scan, (const uint32_t*)sd,
-                     nq, (const uint64_t*)h->gs_rows, (const uint32_t*)h->gs_cnt, (const unsigned long long*)seen, NL, d_out, d_counts, d_stats);
-  VS_HIP(h, hipGetLastError());
-  if (trace) {
-    VS_HIP(h, hipStreamSynchronize(S));
-    fprintf(stderr, "[vc_gs] union scan: %u queries  %.1f us\n", n,
-            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_scan).count());
+};
+
+static int sharded_global_stop(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out, uint32_t* d_counts,
+                               vc_query_stats* d_stats, hipStream_t S) {
+  GsSearch c{h, d_queries, nq, k, d_out, d_counts, d_stats, S};
+  int rc = c.prepare();
+  if (!rc) rc = c.seed_first_round();
+  for (uint32_t round = 0; !rc && round < GS_MAX_ROUNDS && c.round_open(); ++round) {
+    const auto t_round = std::chrono::steady_clock::now();
+    rc = c.run_round();                                    // enqueued on S: every open cap group searched capped and judged
+    if (!rc) rc = c.read_round_counters(round, t_round);   // the round ends here: the host waits for what it left open
   }
-  return VC_OK;
+  if (!rc) rc = c.leftovers_to_scan();                     // (a query still open after the last round is scanned too)
+  if (!rc && c.n_scan) rc = c.union_scan();                // the union scan takes over: everything the rounds could not settle
+  return rc;
 }
 
 static int sharded_search_any(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out,
@@ -893,6 +1164,8 @@ static int sharded_search_any(vc_sharded* h, const void* d_queries, uint32_t nq,
     return sharded_global_stop(h, d_queries, nq, k, d_out, d_counts, d_stats, S);
   return sharded_search_dev(h, d_queries, nq, k, mode, d_out, d_counts, d_stats, S);
 }
+
+extern "C" {
 
 int vc_sharded_root_device(const vc_sharded* h, int* device) {
   if (!h || !device) return VC_ERR_INVALID;
@@ -906,6 +1179,44 @@ int vc_sharded_search_knn_dev(vc_sharded* h, const void* d_queries, uint32_t nq,
   return sharded_search_any(h, d_queries, nq, k, mode, d_out, d_counts, d_stats, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
 }
 
+// the merged rows and counts (and statistics, when wanted) of the host-pointer call reach the host; waits for them
+static int fetch_results(vc_sharded* h, uint32_t nq, uint32_t k, uint64_t* out, uint32_t* cnt, vc_query_stats* stats, hipStream_t S) {
+  VS_HIP(h, hipMemcpyAsync(out, h->buf[ROOT_OUT].p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipMemcpyAsync(cnt, h->buf[ROOT_OCNT].p, (size_t)nq * 4, hipMemcpyDeviceToHost, S));
+  if (stats) VS_HIP(h, hipMemcpyAsync(stats, h->buf[ROOT_OSTATS].p, (size_t)nq * sizeof(vc_query_stats), hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipStreamSynchronize(S));
+  return VC_OK;
+}
+
+// A shard's device-side ring-overflow recovery gave up (its grid never met; never seen outside tests): the LINEAR batch is
+// answered again through the shards' host API, whose host-driven recovery always ends, one shard after the other;
+// the rows go back into the root's slots and are merged by the same kernel into the handle's row / count buffers.
+static int reanswer_linear_by_host(vc_sharded* h, const void* queries, uint32_t nq, uint32_t k, hipStream_t S) {
+  const SlotLayout L(nq, k, false);
+  Lane& R = h->root_lane_ref();
+  int rc;
+  VS_HIP(h, hipSetDevice(h->root));
+  if ((rc = R.buf[LANE_GATH].grow(h, L.words * 8 * h->G))) return rc;
+  std::vector<uint64_t> slot(L.words);
+  for (uint32_t g = 0; g < h->G; ++g) {
+    uint32_t* c = (uint32_t*)(slot.data() + L.cnt_off);
+    std::fill(slot.begin(), slot.begin() + L.rows, VC_PACK_INF);
+    std::fill(slot.begin() + L.rows, slot.end(), 0ull);
+    if (shard_size(h, g)) {
+      rc = vc_search_knn(h->eng[g], queries, nq, k, VC_MODE_LINEAR, VC_ORDER_ASCENDING, slot.data(), c, nullptr);
+      if (rc) return sfail(h, rc, "shard %u: %s", g, vc_last_error(h->eng[g]));
+      for (uint32_t i = 0; i < nq; ++i)
+        for (uint32_t j = c[i]; j < k; ++j) slot[(size_t)i * k + j] = VC_PACK_INF;
+    }
+    VS_HIP(h, hipSetDevice(h->root));
+    VS_HIP(h, hipMemcpyAsync(R.slot(g, L.words), slot.data(), L.words * 8, hipMemcpyHostToDevice, S));
+    VS_HIP(h, hipStreamSynchronize(S));   // `slot` is reused by the next shard
+  }
+  VS_HIP(h, vc_launch_select_slots(R.gath(), L.words, (uint32_t)L.cnt_off, h->G, nq, k, h->buf[ROOT_OUT].as<uint64_t>(),
+                                   h->buf[ROOT_OCNT].as<uint32_t>(), S));
+  return VC_OK;
+}
+
 int vc_sharded_search_knn(vc_sharded* h, const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order,
                           uint64_t* out, uint32_t* counts, vc_query_stats* stats) {
   if (!h || !queries || !out || nq == 0 || k == 0 || k > VC_MAX_K || mode > VC_MODE_MIH_APPROX || order > VC_ORDER_FARTHEST_FIRST)
@@ -914,47 +1225,22 @@ int vc_sharded_search_knn(vc_sharded* h, const void* queries, uint32_t nq, uint3
   int rc;
   hipStream_t S = h->root_stream;
   VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = sgrow(h, (uint8_t**)&h->d_hq, &h->hq_bytes, qbytes))) return rc;
-  if ((rc = sgrow(h, &h->d_out, &h->out_bytes, rows * 8))) return rc;
-  if ((rc = sgrow(h, &h->d_ocnt, &h->ocnt_bytes, (size_t)nq * 4))) return rc;
-  if (stats && (rc = sgrow(h, &h->d_ostats, &h->ostats_bytes, (size_t)nq * sizeof(vc_query_stats)))) return rc;
-  VS_HIP(h, hipMemcpyAsync(h->d_hq, queries, qbytes, hipMemcpyHostToDevice, S));
-  if ((rc = sharded_search_any(h, h->d_hq, nq, k, mode, h->d_out, h->d_ocnt, stats ? h->d_ostats : nullptr, S))) return rc;
+  if ((rc = h->buf[ROOT_HQ].grow(h, qbytes))) return rc;
+  if ((rc = h->buf[ROOT_OUT].grow(h, rows * 8))) return rc;
+  if ((rc = h->buf[ROOT_OCNT].grow(h, (size_t)nq * 4))) return rc;
+  if (stats && (rc = h->buf[ROOT_OSTATS].grow(h, (size_t)nq * sizeof(vc_query_stats)))) return rc;
+  VS_HIP(h, hipMemcpyAsync(h->buf[ROOT_HQ].p, queries, qbytes, hipMemcpyHostToDevice, S));
+  if ((rc = sharded_search_any(h, h->buf[ROOT_HQ].p, nq, k, mode, h->buf[ROOT_OUT].as<uint64_t>(), h->buf[ROOT_OCNT].as<uint32_t>(),
+                               stats ? h->buf[ROOT_OSTATS].as<vc_query_stats>() : nullptr, S)))
+    return rc;
   std::vector<uint32_t> cnt(nq);
   VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, hipMemcpyAsync(out, h->d_out, rows * 8, hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipMemcpyAsync(cnt.data(), h->d_ocnt, (size_t)nq * 4, hipMemcpyDeviceToHost, S));
-  if (stats) VS_HIP(h, hipMemcpyAsync(stats, h->d_ostats, (size_t)nq * sizeof(vc_query_stats), hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipStreamSynchronize(S));
+  if ((rc = fetch_results(h, nq, k, out, cnt.data(), stats, S))) return rc;
   bool gave_up = false;
   for (uint32_t i = 0; i < nq; ++i) gave_up = gave_up || cnt[i] == 0xFFFFFFFFu;
   if (gave_up && mode == VC_MODE_LINEAR) {
-    // A shard's device-side ring-overflow recovery gave up (its grid never met; never seen outside tests): the batch is
-    // answered again through the shards' host API, whose host-driven recovery always ends, one shard after the other;
-    // the rows go back into the root's slots and are merged by the same kernel.
-    const SlotLayout L(nq, k, false);
-    Lane& R = h->lanes[h->root_lane];
-    VS_HIP(h, hipSetDevice(h->root));
-    if ((rc = sgrow(h, &R.gath, &R.gath_bytes, L.words * 8 * h->G))) return rc;
-    std::vector<uint64_t> slot(L.words);
-    for (uint32_t g = 0; g < h->G; ++g) {
-      uint32_t* c = (uint32_t*)(slot.data() + L.cnt_off);
-      std::fill(slot.begin(), slot.begin() + L.rows, VC_PACK_INF);
-      std::fill(slot.begin() + L.rows, slot.end(), 0ull);
-      if (shard_size(h, g)) {
-        rc = vc_search_knn(h->eng[g], queries, nq, k, VC_MODE_LINEAR, VC_ORDER_ASCENDING, slot.data(), c, nullptr);
-        if (rc) return sfail(h, rc, "shard %u: %s", g, vc_last_error(h->eng[g]));
-        for (uint32_t i = 0; i < nq; ++i)
-          for (uint32_t j = c[i]; j < k; ++j) slot[(size_t)i * k + j] = VC_PACK_INF;
-      }
-      VS_HIP(h, hipSetDevice(h->root));
-      VS_HIP(h, hipMemcpyAsync(R.gath + (size_t)g * L.words, slot.data(), L.words * 8, hipMemcpyHostToDevice, S));
-      VS_HIP(h, hipStreamSynchronize(S));   // `slot` is reused by the next shard
-    }
-    VS_HIP(h, vc_launch_select_slots(R.gath, L.words, (uint32_t)L.cnt_off, h->G, nq, k, h->d_out, h->d_ocnt, S));
-    VS_HIP(h, hipMemcpyAsync(out, h->d_out, rows * 8, hipMemcpyDeviceToHost, S));
-    VS_HIP(h, hipMemcpyAsync(cnt.data(), h->d_ocnt, (size_t)nq * 4, hipMemcpyDeviceToHost, S));
-    VS_HIP(h, hipStreamSynchronize(S));
+    if ((rc = reanswer_linear_by_host(h, queries, nq, k, S))) return rc;
+    if ((rc = fetch_results(h, nq, k, out, cnt.data(), nullptr, S))) return rc;
   }
   for (uint32_t i = 0; i < nq; ++i) {
     // the MIH modes have no host-side recovery above: a row flagged by the slot merge (UINT32_MAX) must not be reversed
@@ -967,6 +1253,46 @@ int vc_sharded_search_knn(vc_sharded* h, const void* queries, uint32_t nq, uint3
   return VC_OK;
 }
 
+// every shard's neighbours within `radius` through its host API: res[g] holds them query after query, offs[g] where each starts
+static int radius_by_shard(vc_sharded* h, const void* queries, uint32_t nq, uint32_t radius, uint32_t mode,
+                           std::vector<std::vector<uint64_t>>* res, std::vector<std::vector<uint64_t>>* offs) {
+  for (uint32_t g = 0; g < h->G; ++g) {
+    if (shard_size(h, g) == 0) continue;
+    uint64_t cap = (uint64_t)nq * 64;
+    for (int attempt = 0;; ++attempt) {
+      (*res)[g].resize(std::max<uint64_t>(cap, 1));
+      const int rc = vc_search_radius(h->eng[g], queries, nq, radius, mode, (*res)[g].data(), cap, (*offs)[g].data());
+      if (rc == VC_OK) break;
+      if (rc != VC_ERR_CAPACITY || attempt) return sfail(h, rc, "shard %u: %s", g, vc_last_error(h->eng[g]));
+      cap = (*offs)[g][nq];   // the needed size came back in the offsets
+    }
+  }
+  return VC_OK;
+}
+
+// the padded segments ([nq][cap2], count[q] entries each) are ordered and packed on the root device by the radius search's own
+// segment sort, one block per query, into out[0 .. total) at out_offsets
+static int sort_segments_on_root(vc_sharded* h, const std::vector<uint64_t>& ring, uint64_t cap2, const std::vector<uint32_t>& count,
+                                 const uint64_t* out_offsets, uint64_t total, uint32_t nq, uint64_t* out) {
+  hipStream_t S = h->root_stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  enum { RING, OFFS, OUT, COUNT, N_TMP };
+  ScopedBufs<N_TMP> tmp;
+  int rc;
+  if ((rc = tmp.b[RING].grow(h, ring.size() * 8))) return rc;
+  if ((rc = tmp.b[OFFS].grow(h, ((size_t)nq + 1) * 8))) return rc;
+  if ((rc = tmp.b[OUT].grow(h, total * 8))) return rc;
+  if ((rc = tmp.b[COUNT].grow(h, (size_t)nq * 4))) return rc;
+  VS_HIP(h, hipMemcpyAsync(tmp.b[RING].p, ring.data(), ring.size() * 8, hipMemcpyHostToDevice, S));
+  VS_HIP(h, hipMemcpyAsync(tmp.b[OFFS].p, out_offsets, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice, S));
+  VS_HIP(h, hipMemcpyAsync(tmp.b[COUNT].p, count.data(), (size_t)nq * 4, hipMemcpyHostToDevice, S));
+  VS_HIP(h, vc_launch_sort_compact_segments(tmp.b[RING].as<uint64_t>(), (uint32_t)cap2, tmp.b[COUNT].as<uint32_t>(), tmp.b[OFFS].as<uint64_t>(),
+                                            tmp.b[OUT].as<uint64_t>(), total, nq, S));
+  VS_HIP(h, hipMemcpyAsync(out, tmp.b[OUT].p, total * 8, hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipStreamSynchronize(S));
+  return VC_OK;
+}
+
 // All items within `radius` of every query over all shards (search_R_neighbors per rank + gather_vectors + the master's dedup,
 // search_worker.cc:177-199,222-264: every shard searches its id range, the per-query results of the shards are brought together and
 // ordered).  Shard by shard through the shards' host API (a shard's radius search waits for its own total anyway); the
@@ -976,17 +1302,7 @@ int vc_sharded_search_radius(vc_sharded* h, const void* queries, uint32_t nq, ui
   if (!h || !queries || !out_offsets || nq == 0 || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) || (!out && out_cap))
     return VC_ERR_INVALID;
   std::vector<std::vector<uint64_t>> res(h->G), offs(h->G, std::vector<uint64_t>((size_t)nq + 1, 0));
-  for (uint32_t g = 0; g < h->G; ++g) {
-    if (shard_size(h, g) == 0) continue;
-    uint64_t cap = (uint64_t)nq * 64;
-    for (int attempt = 0;; ++attempt) {
-      res[g].resize(std::max<uint64_t>(cap, 1));
-      const int rc = vc_search_radius(h->eng[g], queries, nq, radius, mode, res[g].data(), cap, offs[g].data());
-      if (rc == VC_OK) break;
-      if (rc != VC_ERR_CAPACITY || attempt) return sfail(h, rc, "shard %u: %s", g, vc_last_error(h->eng[g]));
-      cap = offs[g][nq];   // the needed size came back in the offsets
-    }
-  }
+  if (int rc = radius_by_shard(h, queries, nq, radius, mode, &res, &offs)) return rc;
   // per-query totals -> output offsets; the largest query sizes the segment ring (a power of two, as the sort wants it)
   std::vector<uint32_t> count(nq);
   uint64_t total = 0, mx = 0;
@@ -1012,25 +1328,7 @@ int vc_sharded_search_radius(vc_sharded* h, const void* queries, uint32_t nq, ui
     for (uint32_t g = 0; g < h->G; ++g)
       dst = std::copy(res[g].begin() + offs[g][q], res[g].begin() + offs[g][q + 1], dst);
   }
-  hipStream_t S = h->root_stream;
-  VS_HIP(h, hipSetDevice(h->root));
-  uint64_t *d_ring = nullptr, *d_offs = nullptr, *d_out = nullptr;
-  uint32_t* d_count = nullptr;
-  auto cleanup = [&]() { (void)hipFree(d_ring); (void)hipFree(d_offs); (void)hipFree(d_out); (void)hipFree(d_count); };
-#define VR_HIP(call) do { hipError_t _r = (call); if (_r != hipSuccess) { cleanup(); return sfail(h, _r == hipErrorOutOfMemory ? VC_ERR_NOMEM : VC_ERR_HIP, "%s: %s", #call, hipGetErrorString(_r)); } } while (0)
-  VR_HIP(hipMalloc((void**)&d_ring, ring.size() * 8));
-  VR_HIP(hipMalloc((void**)&d_offs, ((size_t)nq + 1) * 8));
-  VR_HIP(hipMalloc((void**)&d_out, total * 8));
-  VR_HIP(hipMalloc((void**)&d_count, (size_t)nq * 4));
-  VR_HIP(hipMemcpyAsync(d_ring, ring.data(), ring.size() * 8, hipMemcpyHostToDevice, S));
-  VR_HIP(hipMemcpyAsync(d_offs, out_offsets, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice, S));
-  VR_HIP(hipMemcpyAsync(d_count, count.data(), (size_t)nq * 4, hipMemcpyHostToDevice, S));
-  VR_HIP(vc_launch_sort_compact_segments(d_ring, (uint32_t)cap2, d_count, d_offs, d_out, total, nq, S));
-  VR_HIP(hipMemcpyAsync(out, d_out, total * 8, hipMemcpyDeviceToHost, S));
-  VR_HIP(hipStreamSynchronize(S));
-#undef VR_HIP
-  cleanup();
-  return VC_OK;
+  return sort_segments_on_root(h, ring, cap2, count, out_offsets, total, nq, out);
 }
 
 }  // extern "C"
