@@ -335,3 +335,53 @@ def np_sub_distances(codes, query, m):
 
 def pack(dist, ids):
     return (dist.astype(np.uint64) << np.uint64(32)) | ids.astype(np.uint64)
+
+
+class MihExactModel:
+    """numpy model of the exact-mode radius loop (vco_mih_find_mt above; search_worker.cc:170-207) for ONE query, masked
+    keys, no bitmap.  Shell r of the loop has seen exactly the items whose minimum substring distance is <= r, so the
+    loop needs no key enumeration: a uniform query over 32-bit substrings, which costs MihOracle.find 1e8 probes, costs
+    this one sort.  Built once per query; find(k) answers any k.
+
+        seen(r)  = items with minsub <= r
+        stop     = the first r in 0..s with |seen(r)| >= k and k-th smallest (dist, id) of seen(r) has dist <= (r + 1) * mult
+                   (mult = min(m, 4)); r = s if the loop never stops (fewer than k items)
+    """
+
+    def __init__(self, codes, query, m, id_base=0):
+        codes = _bytes(codes)
+        self.s = codes.shape[1] * 8 // m
+        self.mult = min(m, 4)
+        n = codes.shape[0]
+        if n:
+            packed = pack(np_distances(codes, query), np.arange(n, dtype=np.uint64) + np.uint64(id_base))
+            minsub = np_sub_distances(codes, query, m).min(axis=1)
+        else:
+            packed, minsub = np.empty(0, dtype=np.uint64), np.empty(0, dtype=np.uint32)
+        order = np.argsort(packed, kind="stable")
+        self.packed = packed[order]              # ascending (dist, id)
+        self.minsub = minsub[order]
+        self.seen_at = np.cumsum(np.bincount(self.minsub, minlength=self.s + 1)[: self.s + 1])   # |seen(r)|
+
+    def find(self, k):
+        """(row ascending packed, dict of the vc_query_stats fields)"""
+        from math import comb
+        radius, row = self.s, None
+        for r in range(self.s + 1):
+            if self.seen_at[r] < k:
+                continue
+            row = self.packed[np.flatnonzero(self.minsub <= r)[:k]]
+            if int(row[-1] >> np.uint64(32)) <= (r + 1) * self.mult:
+                radius = r
+                break
+        if row is None or radius == self.s:
+            row = self.packed[np.flatnonzero(self.minsub <= radius)[:k]]
+        stats = {"radius": radius, "n_results": len(row), "n_main_reads": 0,
+                 "n_sub_reads": sum(comb(self.s, j) for j in range(radius + 1)), "n_local_reads": 0,
+                 "n_candidates": int(self.seen_at[radius])}
+        return row, stats
+
+
+def np_mih_exact(codes, query, m, k, id_base=0):
+    """One query, one k through MihExactModel: (row, stats)."""
+    return MihExactModel(codes, query, m, id_base).find(k)
