@@ -102,6 +102,7 @@ void read_knobs(VcKnobs* k) {
   if (const char* w = getenv("VC_SCAN_WRAP")) k->scan_wrap = (uint32_t)atoi(w);
   if (const char* w = getenv("VC_SCAN_DIAG")) k->scan_diag = (uint32_t)atoi(w);
   if (const char* w = getenv("VC_SCAN_TRACE")) k->scan_trace = atoi(w) != 0;
+  if (const char* w = getenv("VC_SCAN_SHAPE_TRACE")) k->scan_shape_trace = atoi(w) != 0;
   if (const char* w = getenv("VC_SCAN_RESIDENT_MB")) k->resident_mb = std::max(0, atoi(w));
   if (const char* s2 = getenv("VC_SAMPLE2")) { k->sample2_set = true; k->sample2 = strtoull(s2, nullptr, 10); }
   if (const char* s1 = getenv("VC_SAMPLE1")) { k->sample1_set = true; k->sample1 = strtoull(s1, nullptr, 10); }

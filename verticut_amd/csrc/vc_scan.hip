@@ -1217,12 +1217,19 @@ uint32_t resident_grid(K kernel, int blk, size_t lds, uint32_t n_cu, uint32_t wa
 }
 
 template <int W>
-hipError_t launch_scan_w(const VcScanParams& p, const VcScanShape& sh, size_t lds, uint32_t n_cu, uint32_t want, hipStream_t s) {
+hipError_t launch_scan_w(const VcScanParams& p, const VcScanShape& sh, size_t lds, uint32_t n_cu, uint32_t want, bool shape_trace,
+                         hipStream_t s) {
+  // dev knob VC_SCAN_SHAPE_TRACE: one line per launch naming the instantiation that was launched (not the one asked for)
+#define VC_SHAPE_TRACE(U_, B_, NB_, QT_)                                                                    \
+  if (shape_trace)                                                                                          \
+    fprintf(stderr, "[scan shape] W=%d U=%d BLK=%d NB=%d QT=%d grid=%u nchunks=%llu qt=%u\n", W, (int)(U_), (int)(B_), (int)(NB_), \
+            (int)(QT_), grid, (unsigned long long)p.nchunks, p.qt);
 #define VC_LAUNCH_QT(NB_, U_, QT_, MW_)                                                                     \
   {                                                                                                         \
     auto kern = vc_scan_kernel<W, U_, 256, NB_, QT_, MW_>;                                                  \
     const size_t lds_q = (size_t)QT_ * (W * 8 + 4);                                                         \
     const uint32_t grid = (uint32_t)std::min<uint64_t>(p.nchunks, resident_grid(kern, 256, lds_q, n_cu, want)); \
+    VC_SHAPE_TRACE(U_, 256, NB_, QT_)                                                                       \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_q, s, p);                                           \
     return hipGetLastError();                                                                               \
   }
@@ -1248,6 +1255,7 @@ hipError_t launch_scan_w(const VcScanParams& p, const VcScanShape& sh, size_t ld
   {                                                                                                         \
     auto kern = vc_scan_kernel<W, U_, B_, NB_>;                                                             \
     const uint32_t grid = (uint32_t)std::min<uint64_t>(p.nchunks, resident_grid(kern, B_, lds, n_cu, want)); \
+    VC_SHAPE_TRACE(U_, B_, NB_, 0)                                                                          \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(B_), lds, s, p);                                              \
   }
   // (shapes with more than 8 tile loads per lane and buffer are never picked -- vc_scan_pick_shape -- and not built:
@@ -1269,6 +1277,7 @@ hipError_t launch_scan_w(const VcScanParams& p, const VcScanShape& sh, size_t ld
   VC_SCAN_CASE(1, 512)
 #undef VC_SCAN_CASE
 #undef VC_LAUNCH
+#undef VC_SHAPE_TRACE
   return hipErrorInvalidValue;
 }
 
@@ -1399,11 +1408,12 @@ hipError_t vc_launch_scan(const VcScanParams& p, uint32_t W, uint32_t n_cu, uint
   if (p.nchunks == 0 || p.qt == 0) return hipSuccess;
   size_t lds;
   const VcScanShape sh = vc_scan_pick_shape(W, p.qt, &lds, knobs, shape_n);
+  const bool tr = knobs && knobs->scan_shape_trace;
   switch (W) {
-    case 1: return launch_scan_w<1>(p, sh, lds, n_cu, want_blocks, s);
-    case 2: return launch_scan_w<2>(p, sh, lds, n_cu, want_blocks, s);
-    case 4: return launch_scan_w<4>(p, sh, lds, n_cu, want_blocks, s);
-    case 8: return launch_scan_w<8>(p, sh, lds, n_cu, want_blocks, s);
+    case 1: return launch_scan_w<1>(p, sh, lds, n_cu, want_blocks, tr, s);
+    case 2: return launch_scan_w<2>(p, sh, lds, n_cu, want_blocks, tr, s);
+    case 4: return launch_scan_w<4>(p, sh, lds, n_cu, want_blocks, tr, s);
+    case 8: return launch_scan_w<8>(p, sh, lds, n_cu, want_blocks, tr, s);
   }
   return hipErrorInvalidValue;
 }
