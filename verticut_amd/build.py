@@ -34,23 +34,34 @@ def _stale():
 LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 
 
-def kernel_resources(obj):
-    """{kernel name: {private_segment_fixed_size, sgpr_spill_count, vgpr_spill_count, vgpr_count, sgpr_count}} of the
-    gfx950 code object inside a hipcc object file: .hip_fatbin section -> offload bundle -> AMDGPU metadata note."""
-    import tempfile
-    tools = {t: os.path.join(LLVM_BIN, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")}
+def _llvm_tools(*names):
+    tools = {t: os.path.join(LLVM_BIN, t) for t in names}
     for t, path in tools.items():
         if not os.path.exists(path):
-            raise RuntimeError("%s not found: cannot inspect the code object of %s" % (path, obj))
+            raise RuntimeError("%s not found: cannot inspect a code object" % path)
+    return tools
+
+
+def extract_code_object(obj, co):
+    """Write the gfx950 code object inside a hipcc object file to `co`: .hip_fatbin section -> offload bundle."""
+    tools = _llvm_tools("llvm-objcopy", "clang-offload-bundler")
+    fat = co + ".fatbin"
+    subprocess.check_call([tools["llvm-objcopy"], "--dump-section", ".hip_fatbin=" + fat, obj, co + ".copy.o"])
+    subprocess.check_call([tools["clang-offload-bundler"], "--unbundle", "--type=o",
+                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co])
+    return co
+
+
+def kernel_resources(obj):
+    """{kernel name: {private_segment_fixed_size, group_segment_fixed_size, sgpr_spill_count, vgpr_spill_count, vgpr_count,
+    sgpr_count}} of the gfx950 code object inside a hipcc object file, from its AMDGPU metadata note."""
+    import tempfile
     with tempfile.TemporaryDirectory() as td:
-        fat, co = os.path.join(td, "fat.bin"), os.path.join(td, "gfx950.co")
-        subprocess.check_call([tools["llvm-objcopy"], "--dump-section", ".hip_fatbin=" + fat, obj, os.path.join(td, "copy.o")])
-        subprocess.check_call([tools["clang-offload-bundler"], "--unbundle", "--type=o",
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co])
-        notes = subprocess.check_output([tools["llvm-readelf"], "--notes", co]).decode(errors="replace")
+        co = extract_code_object(obj, os.path.join(td, "gfx950.co"))
+        notes = subprocess.check_output([_llvm_tools("llvm-readelf")["llvm-readelf"], "--notes", co]).decode(errors="replace")
     # the note is YAML: "amdhsa.kernels:" holds one "  - .agpr_count: ..." record per kernel, keys at four spaces
     res, rec, in_kernels = {}, None, False
-    keys = ("private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count", "vgpr_count", "sgpr_count")
+    keys = ("private_segment_fixed_size", "group_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count", "vgpr_count", "sgpr_count")
 
     def close(r):
         if r and "name" in r:

@@ -393,16 +393,20 @@ __device__ __forceinline__ void vc_lookup(const VcTableView& tv, uint32_t sbits,
   }
 }
 
-// j-th r-subset of {0..s-1} in colexicographic order == numeric order of the masks (combinadic unranking)
-__device__ __forceinline__ uint32_t vc_unrank(uint32_t j, uint32_t r, uint32_t s) {
-  uint32_t mask = 0;
-  uint32_t c = s;
+// j-th r-subset of {0..s-1} in colexicographic order == numeric order of the masks (combinadic unranking);
+// binom(c, i) = C(c, i) from whichever copy of the table the caller reads
+template <typename Binom>
+__device__ __forceinline__ uint32_t vc_unrank_walk(uint32_t j, uint32_t r, uint32_t s, Binom binom) {
+  uint32_t mask = 0, c = s;
   for (uint32_t i = r; i >= 1; --i) {
-    do { --c; } while (c_binom[c][i] > j);   // largest c with C(c,i) <= j
-    j -= c_binom[c][i];
+    do { --c; } while (binom(c, i) > j);   // largest c with C(c,i) <= j
+    j -= binom(c, i);
     mask |= 1u << c;
   }
   return mask;
+}
+__device__ __forceinline__ uint32_t vc_unrank(uint32_t j, uint32_t r, uint32_t s) {
+  return vc_unrank_walk(j, r, s, [](uint32_t c, uint32_t i) { return c_binom[c][i]; });
 }
 
 // next mask with the same popcount (Gosper), 64-bit so s = 32 cannot overflow
@@ -411,6 +415,116 @@ __device__ __forceinline__ uint32_t vc_next_comb(uint32_t x) {
   const uint64_t c = v & (0 - v);
   const uint64_t rr = v + c;
   return (uint32_t)((((rr ^ v) >> 2) >> (__ffsll((long long)v) - 1)) | rr);
+}
+
+// ------------------------------------------------------------------------------------------
+// verify primitives: the one copy of every rule the probe, query, stream, replay and tie kernels share
+// ------------------------------------------------------------------------------------------
+// Substring t of a code: bits [t s, t s + s); smask = 2^s - 1.  s is 8, 16 or 32 (vc_mih_build): no substring straddles a 64-bit
+// word.  Codes in registers select the word by a compile-time loop -- a run-time index would move the array to scratch.
+template <int W>
+__device__ __forceinline__ uint32_t vc_substr(const uint64_t (&w)[W], uint32_t t, uint32_t s, uint32_t smask) {
+  const uint32_t bp = t * s;
+  uint32_t v = 0;
+#pragma unroll
+  for (int j = 0; j < W; ++j)
+    if ((uint32_t)j == (bp >> 6)) v = (uint32_t)(w[j] >> (bp & 63)) & smask;
+  return v;
+}
+// ... of x ^ q: its popcount is the substring distance
+template <int W>
+__device__ __forceinline__ uint32_t vc_substr(const uint64_t (&x)[W], const uint64_t (&q)[W], uint32_t t, uint32_t s, uint32_t smask) {
+  const uint32_t bp = t * s;
+  uint32_t v = 0;
+#pragma unroll
+  for (int j = 0; j < W; ++j)
+    if ((uint32_t)j == (bp >> 6)) v = (uint32_t)((x[j] ^ q[j]) >> (bp & 63)) & smask;
+  return v;
+}
+// the same from memory, for the kernels whose W is a run-time value: word j of the code at w[j * stride], the query dense
+__device__ __forceinline__ uint32_t vc_substr_mem(const uint64_t* w, uint64_t stride, uint32_t t, uint32_t s, uint32_t smask) {
+  const uint32_t bp = t * s;
+  return (uint32_t)(w[(uint64_t)(bp >> 6) * stride] >> (bp & 63)) & smask;
+}
+__device__ __forceinline__ uint32_t vc_substr_mem(const uint64_t* x, uint64_t stride, const uint64_t* q, uint32_t t, uint32_t s,
+                                                  uint32_t smask) {
+  const uint32_t bp = t * s;
+  return (uint32_t)((x[(uint64_t)(bp >> 6) * stride] ^ q[bp >> 6]) >> (bp & 63)) & smask;
+}
+
+// OWNER RULE (replaces the reference's dedup map knn_found_, search_worker.cc:179-207): an item is reported by the first table
+// holding its minimum substring distance, in the shell equal to that distance -- exactly once over the whole radius loop.
+// Returns whether table t, which found x at substring distance dt, is that table; dist = the full distance, which comes free
+// with the per-substring distances (compute_hamming_dist, image_tools.h:21-33).  signext = (flags & VC_FLAG_REF_SIGNEXT_KEYS)
+// && s < 32: binaryToInt's sign-extended keys (Pilaf/image_tools.h:13) let a table fetch an item only if the substrings' top
+// bits agree, and a table that could not reach the item does not own it.
+template <int W>
+__device__ __forceinline__ bool vc_owner_dist(const uint64_t (&x)[W], const uint64_t (&qw)[W], uint32_t m, uint32_t s, uint32_t smask,
+                                              uint32_t t, uint32_t dt, bool signext, uint32_t& dist) {
+  bool own = true;
+  dist = 0;
+  for (uint32_t tt = 0; tt < m; ++tt) {
+    const uint32_t field = vc_substr(x, qw, tt, s, smask);
+    const uint32_t d = __popc(field);
+    dist += d;
+    bool reach = true;   // could table tt have fetched this item at shell d?
+    if (signext) reach = ((field >> (s - 1)) & 1u) == 0;
+    if (tt != t && reach && (d < dt || (d == dt && tt < t))) own = false;
+  }
+  return own;
+}
+
+// Exclusive prefix of v over the threads of a block of nwaves waves, and the block's total, through the caller's
+// s_wsum[nwaves].  One barrier inside; the caller puts another one before s_wsum is used again.
+__device__ __forceinline__ uint32_t vc_block_excl_scan(uint32_t v, uint32_t* s_wsum, uint32_t nwaves, uint32_t& total) {
+  const uint32_t wave = threadIdx.x / VC_WAVE;
+  uint32_t wtot;
+  const uint32_t excl = vc_wave_excl_scan(v, wtot);
+  if (vc_lane() == 0) s_wsum[wave] = wtot;
+  __syncthreads();
+  uint32_t wbase = 0;
+  total = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < nwaves; ++w) {
+    if (w < wave) wbase += s_wsum[w];
+    total += s_wsum[w];
+  }
+  return excl + wbase;
+}
+
+// bucket of entry e in an exclusive prefix array of n bucket lengths: the largest b < n with s_pref[b] <= e
+__device__ __forceinline__ uint32_t vc_slot_of(const uint32_t* s_pref, uint32_t n, uint32_t e) {
+  uint32_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (s_pref[mid] <= e) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// entry pos of a table: its local id, and its code from the table's bucket-order copy (a contiguous stream) where there
+// is one, else gathered from the columns through the id
+template <int W>
+__device__ __forceinline__ void vc_load_entry(const VcTableView& tv, uint32_t pos, const uint64_t* cols, uint64_t stride, uint64_t n,
+                                              uint32_t& local, uint64_t (&x)[W]) {
+  local = tv.ids[pos];
+  if (tv.bcodes) {
+#pragma unroll
+    for (int j = 0; j < W; ++j) x[j] = tv.bcodes[(uint64_t)j * n + pos];
+  } else {
+#pragma unroll
+    for (int j = 0; j < W; ++j) x[j] = cols[(uint64_t)j * stride + local];
+  }
+}
+
+// Wave-aggregated append: the lanes set in kmask (= __ballot of the lanes that keep a value, not 0; all lanes call) get
+// consecutive positions behind *counter, for ONE atomic of the wave.  The result means nothing in the other lanes.
+__device__ __forceinline__ uint32_t vc_wave_append(uint32_t* counter, uint64_t kmask) {
+  const uint32_t lane = vc_lane();
+  uint32_t base = 0;
+  if (lane == 0) base = atomicAdd(counter, (uint32_t)__popcll(kmask));
+  base = __builtin_amdgcn_readfirstlane(base);
+  return base + (uint32_t)__popcll(kmask & ((1ull << lane) - 1ull));
 }
 
 template <int W>
@@ -426,16 +540,12 @@ __global__ void __launch_bounds__(MIH_BLK) mih_probe_kernel(const ProbeParams p)
   const uint32_t s = p.sbits;
   const uint32_t smask = s == 32 ? 0xFFFFFFFFu : ((1u << s) - 1u);
   const uint32_t lane = vc_lane();
-  const uint32_t wave = threadIdx.x / VC_WAVE;
 
   uint64_t qw[W];
 #pragma unroll
   for (int j = 0; j < W; ++j) qw[j] = p.queries[(uint64_t)slot * W + j];
-  const uint32_t bitpos = t * s;
-  uint32_t qkey = 0;
-#pragma unroll
-  for (int j = 0; j < W; ++j)
-    if ((uint32_t)j == (bitpos >> 6)) qkey = (uint32_t)(qw[j] >> (bitpos & 63)) & smask;
+  const uint32_t qkey = vc_substr(qw, t, s, smask);
+  const bool signext = (p.flags & VC_FLAG_REF_SIGNEXT_KEYS) && s < 32;
 
   if (threadIdx.x == 0) { s_n = 0; s_leaves = 0; s_hits = 0; }
   __syncthreads();
@@ -455,7 +565,7 @@ __global__ void __launch_bounds__(MIH_BLK) mih_probe_kernel(const ProbeParams p)
       ++leaves;
       // binaryToInt's sign-extended keys: a probe that flips the substring's top bit keeps the query's
       // high bits and can match nothing (Pilaf/image_tools.h:13); reproduced only on request
-      const bool dead = (p.flags & VC_FLAG_REF_SIGNEXT_KEYS) && s < 32 && ((mask >> (s - 1)) & 1u);
+      const bool dead = signext && ((mask >> (s - 1)) & 1u);
       bool bit = false;
       if (!dead) vc_lookup(tv, s, qkey ^ mask, offv[i], lenv[i], bit);
       hits += (p.flags & VC_FLAG_USE_BITMAP) ? (bit ? 1u : 0u) : 1u;
@@ -502,17 +612,8 @@ __global__ void __launch_bounds__(MIH_BLK) mih_probe_kernel(const ProbeParams p)
     lv[i] = idx < nb ? s_pref[idx] : 0;
     lsum += lv[i];
   }
-  uint32_t wtot;
-  uint32_t excl = vc_wave_excl_scan(lsum, wtot);
-  if (lane == 0) s_wsum[wave] = wtot;
-  __syncthreads();
-  uint32_t wbase = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < MIH_BLK / VC_WAVE; ++w) {
-    if ((uint32_t)w < wave) wbase += s_wsum[w];
-    total += s_wsum[w];
-  }
-  excl += wbase;
+  uint32_t total;
+  uint32_t excl = vc_block_excl_scan(lsum, s_wsum, MIH_BLK / VC_WAVE, total);
 #pragma unroll
   for (int i = 0; i < MIH_PPT; ++i) {
     const uint32_t idx = threadIdx.x * MIH_PPT + i;
@@ -540,42 +641,16 @@ __global__ void __launch_bounds__(MIH_BLK) mih_probe_kernel(const ProbeParams p)
       const uint32_t e = it * ROUND + g * MIH_BLK + threadIdx.x;
       live[g] = e < total;
       const uint32_t ec = live[g] ? e : 0;   // clamp: entry 0 exists whenever total > 0
-      uint32_t lo = 0, hi = nb;               // largest b with s_pref[b] <= e
-      while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (s_pref[mid] <= ec) lo = mid; else hi = mid;
-      }
-      const uint32_t pos = s_off[lo] + (ec - s_pref[lo]);
-      local[g] = tv.ids[pos];
-      if (tv.bcodes) {
-#pragma unroll
-        for (int j = 0; j < W; ++j) x[g][j] = tv.bcodes[(uint64_t)j * p.n + pos];
-      } else {
-#pragma unroll
-        for (int j = 0; j < W; ++j) x[g][j] = p.cols[(uint64_t)j * p.stride + local[g]];
-      }
+      const uint32_t b = vc_slot_of(s_pref, nb, ec);
+      vc_load_entry(tv, s_off[b] + (ec - s_pref[b]), p.cols, p.stride, p.n, local[g], x[g]);
     }
 #pragma unroll
     for (uint32_t g = 0; g < MIH_EPT; ++g) {
       bool emit = live[g];
       uint64_t packed = 0;
       if (live[g]) {
-        // per-substring distances come free with the full distance (compute_hamming_dist, image_tools.h:21-33)
-        uint32_t dist = 0;
-        for (uint32_t tt = 0; tt < p.m; ++tt) {
-          const uint32_t bp = tt * s;
-          uint32_t field = 0;
-#pragma unroll
-          for (int j = 0; j < W; ++j)
-            if ((uint32_t)j == (bp >> 6)) field = (uint32_t)((x[g][j] ^ qw[j]) >> (bp & 63)) & smask;
-          const uint32_t d = __popc(field);
-          dist += d;
-          // owner rule: the item is reported by the first table holding its minimum substring distance, in the
-          // shell equal to that distance -- exactly once over the whole radius loop (replaces knn_found_).
-          bool reach = true;  // could table tt have fetched this item at shell d?  (sign-extended keys: only if top bits agree)
-          if ((p.flags & VC_FLAG_REF_SIGNEXT_KEYS) && s < 32) reach = ((field >> (s - 1)) & 1u) == 0;
-          if (tt != t && reach && (d < p.r || (d == p.r && tt < t))) emit = false;
-        }
+        uint32_t dist;
+        emit = vc_owner_dist(x[g], qw, p.m, s, smask, t, p.r, signext, dist);
         packed = vc_pack(dist, p.id_base + local[g]);
       }
       const uint64_t emask = __ballot(emit);
@@ -585,13 +660,8 @@ __global__ void __launch_bounds__(MIH_BLK) mih_probe_kernel(const ProbeParams p)
       const bool keep = emit && packed < thresh;
       const uint64_t kmask = __ballot(keep);
       if (kmask == 0) continue;
-      uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(&p.st.count[slot], (uint32_t)__popcll(kmask));
-      base = __shfl(base, 0, VC_WAVE);
-      if (keep) {
-        const uint32_t pos = base + (uint32_t)__popcll(kmask & ((1ull << lane) - 1ull));
-        if (pos < p.cap) ring[pos] = packed;
-      }
+      const uint32_t pos = vc_wave_append(&p.st.count[slot], kmask);
+      if (keep && pos < p.cap) ring[pos] = packed;
     }
   }
   if (p.count_seen && lane == 0 && seen_acc) atomicAdd(&p.st.seen[slot], (unsigned long long)seen_acc);
@@ -702,8 +772,7 @@ __global__ void __launch_bounds__(MO_BLK) mih_order_kernel(const VcTableView* __
   s_sc[threadIdx.x] = 0;
   __syncthreads();
   if (ql < per_block && q < nq) {
-    const uint32_t bp = t * sbits;
-    const uint32_t key = (uint32_t)(queries[(uint64_t)q * W + (bp >> 6)] >> (bp & 63)) & smask;
+    const uint32_t key = vc_substr_mem(queries + (uint64_t)q * W, 1, t, sbits, smask);
     const VcTableView& tv = tables[t];
     uint32_t len = 0;
     if (sbits == 32 && tv.lines) {          // one sector: occupancy, first entry position and the buckets' extents
@@ -762,7 +831,7 @@ __global__ void __launch_bounds__(MO_BLK) mih_order_kernel(const VcTableView* __
 // Per block: hits (non-empty buckets) are compacted into an LDS list; when it holds >= MQ_HFLUSH entries (and at the
 // end of a shell) it is DRAINED: rank -> offsets for the 32-bit tables, block prefix sum of the bucket lengths,
 // balanced expansion of the entries over the threads (binary search in the LDS prefix array), gather of id + code,
-// full distance + every substring distance, OWNER RULE (vc_mih.hip mih_probe_kernel), survivors below the running
+// full distance + every substring distance, OWNER RULE (vc_owner_dist), survivors below the running
 // threshold appended to an UNSORTED candidate buffer in LDS and counted in a distance histogram.  After a shell one
 // wave cuts the histogram (smallest d whose cumulative count reaches k): that is the stop rule's k-th distance and the
 // next threshold; the buffer is compacted when it fills and ordered once, when the query ends (k-NN modes; radius
@@ -867,13 +936,7 @@ __device__ __forceinline__ uint32_t mq_unrank(const uint32_t* sb, uint32_t j, ui
     while ((c2 + 1) * c2 / 2 <= j) ++c2;
     return (1u << c2) | (1u << (j - c2 * (c2 - 1) / 2));
   }
-  uint32_t mask = 0, c = s;
-  for (uint32_t i = r; i >= 1; --i) {
-    do { --c; } while (sb[c * MQ_BW + i] > j);   // largest c with C(c,i) <= j
-    j -= sb[c * MQ_BW + i];
-    mask |= 1u << c;
-  }
-  return mask;
+  return vc_unrank_walk(j, r, s, [sb](uint32_t c, uint32_t i) { return sb[c * MQ_BW + i]; });
 }
 
 // smallest d with sum_{d' <= d} h[d'] >= k, 0xFFFFFFFF if the histogram holds fewer than k (one wave, LDS histogram)
@@ -1025,14 +1088,7 @@ __global__ void __launch_bounds__(MQ_BLK, (W <= 2 ? MQ_MINW : 0)) mih_query_kern
   uint64_t qw[W];
 #pragma unroll
   for (int j = 0; j < W; ++j) qw[j] = p.queries[(uint64_t)slot * W + j];
-  auto qkey = [&](uint32_t t) {
-    const uint32_t bp = t * s;
-    uint32_t v = 0;
-#pragma unroll
-    for (int j = 0; j < W; ++j)
-      if ((uint32_t)j == (bp >> 6)) v = (uint32_t)(qw[j] >> (bp & 63)) & smask;
-    return v;
-  };
+  auto qkey = [&](uint32_t t) { return vc_substr(qw, t, s, smask); };
 
   // the binomial table feeds combination unranking beyond the closed forms (|hi| >= 3: shells >= 3) and the <= 16-bit key
   // walk; a 32-bit k-NN query that stops in shells 0..2 -- most do -- never reads it, so it is copied when first needed
@@ -1244,17 +1300,8 @@ __global__ void __launch_bounds__(MQ_BLK, (W <= 2 ? MQ_MINW : 0)) mih_query_kern
       lv[i] = idx < H ? s_pref[idx] : 0;
       lsum += lv[i];
     }
-    uint32_t wtot;
-    uint32_t excl = vc_wave_excl_scan(lsum, wtot);
-    if (lane == 0) s_wsum[wave] = wtot;
-    __syncthreads();
-    uint32_t wbase = 0, total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < MQ_BLK / VC_WAVE; ++w) {
-      if (w < wave) wbase += s_wsum[w];
-      total += s_wsum[w];
-    }
-    excl += wbase;
+    uint32_t total;
+    uint32_t excl = vc_block_excl_scan(lsum, s_wsum, MQ_BLK / VC_WAVE, total);
 #pragma unroll
     for (uint32_t i = 0; i < MQ_HMAX / MQ_BLK; ++i) {
       const uint32_t idx = tid * (MQ_HMAX / MQ_BLK) + i;
@@ -1279,13 +1326,8 @@ __global__ void __launch_bounds__(MQ_BLK, (W <= 2 ? MQ_MINW : 0)) mih_query_kern
     const bool fastmap = MQ_BMW && knn && total <= MQ_BMW * 32u;     // (block-uniform)
     if (fastmap) {
       const uint32_t c = tid < MQ_BMW ? __popc(s_bm[tid]) : 0u;
-      uint32_t wt;
-      uint32_t ex = vc_wave_excl_scan(c, wt);
-      if (lane == 0) s_wsum[wave] = wt;
-      __syncthreads();
-#pragma unroll
-      for (uint32_t w = 0; w < MQ_BLK / VC_WAVE; ++w)
-        if (w < wave) ex += s_wsum[w];
+      uint32_t nstarts;   // (not needed)
+      const uint32_t ex = vc_block_excl_scan(c, s_wsum, MQ_BLK / VC_WAVE, nstarts);
       if (tid < MQ_BMW) s_bmpre[tid] = ex;
       __syncthreads();
     }
@@ -1319,15 +1361,12 @@ __global__ void __launch_bounds__(MQ_BLK, (W <= 2 ? MQ_MINW : 0)) mih_query_kern
         const uint32_t e = e0 + g * MQ_BLK + tid;
         live[g] = e < total;
         const uint32_t ec = live[g] ? e : 0;
-        uint32_t lo = 0, hi = H;               // largest b with s_pref[b] <= e
+        uint32_t lo;                           // largest b with s_pref[b] <= e
         if (fastmap) {
           const uint32_t wi = ec >> 5;
           lo = s_bmpre[wi] + __popc(s_bm[wi] & (0xFFFFFFFFu >> (31u - (ec & 31u)))) - 1u;   // bucket starts at or before e, minus one
         } else {
-          while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (s_pref[mid] <= ec) lo = mid; else hi = mid;
-          }
+          lo = vc_slot_of(s_pref, H, ec);
         }
         meta[g] = s_meta[lo];
         const VcTableView& tv = s_tv[meta[g] & 0xFFu];
@@ -1342,22 +1381,17 @@ __global__ void __launch_bounds__(MQ_BLK, (W <= 2 ? MQ_MINW : 0)) mih_query_kern
           }
           continue;
         }
-        local[g] = tv.ids[pos];
-        if (tv.bcodes) {
-#pragma unroll
-          for (int j = 0; j < W; ++j) x[g][j] = tv.bcodes[(uint64_t)j * p.n + pos];
-        } else {
-#pragma unroll
-          for (int j = 0; j < W; ++j) x[g][j] = p.cols[(uint64_t)j * p.stride + local[g]];
-        }
+        vc_load_entry(tv, pos, p.cols, p.stride, p.n, local[g], x[g]);
       }
 #pragma unroll
       for (uint32_t g = 0; g < MQ_EPT; ++g) {
         bool emit = live[g];
         uint64_t packed = 0;
         if (live[g] && MQ_FAST_OWNER && s == 32 && m == 2u * W) {
-          // the reference's native shape -- 32-bit substrings, every table one half of a code word -- unrolled: the substring
-          // distances are the popcounts of the 2 W dwords of x ^ q, no field extraction, no loop over a run-time table count
+          // vc_owner_dist for the reference's native shape -- 32-bit substrings, every table one half of a code word -- unrolled:
+          // the substring distances are the popcounts of the 2 W dwords of x ^ q, no field extraction, no loop over a run-time
+          // table count.  It may ignore VC_FLAG_REF_SIGNEXT_KEYS: a 32-bit key fills binaryToInt's uint32_t, the extension is
+          // shifted out.  (Written out here: as a helper next to vc_owner_dist it costs the W = 4 instantiations 5 VGPRs.)
           const uint32_t t = meta[g] & 0xFFu, dt = meta[g] >> 8;
           uint32_t dist = 0;
 #pragma unroll
@@ -1365,27 +1399,14 @@ __global__ void __launch_bounds__(MQ_BLK, (W <= 2 ? MQ_MINW : 0)) mih_query_kern
             const uint64_t xq = x[g][j] ^ qw[j];
             const uint32_t d0 = __popc((uint32_t)xq), d1 = __popc((uint32_t)(xq >> 32));
             dist += d0 + d1;
-            // owner rule: reported by the first table holding the minimum substring distance
             if (((uint32_t)(2 * j) != t && (d0 < dt || (d0 == dt && (uint32_t)(2 * j) < t))) ||
                 ((uint32_t)(2 * j + 1) != t && (d1 < dt || (d1 == dt && (uint32_t)(2 * j + 1) < t)))) emit = false;
           }
           packed = vc_pack(dist, p.id_base + local[g]);
-        } else if (live[g]) {
+        } else if (live[g]) {   // owner rule: table t found the entry at substring distance dt
           const uint32_t t = meta[g] & 0xFFu, dt = meta[g] >> 8;
-          uint32_t dist = 0;
-          for (uint32_t tt = 0; tt < m; ++tt) {
-            const uint32_t bp = tt * s;
-            uint32_t field = 0;
-#pragma unroll
-            for (int j = 0; j < W; ++j)
-              if ((uint32_t)j == (bp >> 6)) field = (uint32_t)((x[g][j] ^ qw[j]) >> (bp & 63)) & smask;
-            const uint32_t d = __popc(field);
-            dist += d;
-            // owner rule (see mih_probe_kernel): reported by the first table holding the minimum substring distance
-            bool reach = true;
-            if ((p.flags & VC_FLAG_REF_SIGNEXT_KEYS) && s < 32) reach = ((field >> (s - 1)) & 1u) == 0;
-            if (tt != t && reach && (d < dt || (d == dt && tt < t))) emit = false;
-          }
+          uint32_t dist;
+          emit = vc_owner_dist(x[g], qw, m, s, smask, t, dt, (p.flags & VC_FLAG_REF_SIGNEXT_KEYS) && s < 32, dist);
           packed = vc_pack(dist, p.id_base + local[g]);
         }
         const uint64_t emask = __ballot(emit);
@@ -1398,11 +1419,9 @@ __global__ void __launch_bounds__(MQ_BLK, (W <= 2 ? MQ_MINW : 0)) mih_query_kern
         const bool keep = emit && packed < thresh;
         const uint64_t kmask = __ballot(keep);
         if (kmask == 0) continue;
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&s_ncand, (uint32_t)__popcll(kmask));
-        base = __builtin_amdgcn_readfirstlane(base);
+        const uint32_t at = vc_wave_append(&s_ncand, kmask);
         if (keep) {
-          s_buf[kk + base + (uint32_t)__popcll(kmask & ((1ull << lane) - 1ull))] = packed | ((uint64_t)cls << MQ_TAG_SHIFT);
+          s_buf[kk + at] = packed | ((uint64_t)cls << MQ_TAG_SHIFT);
           if (knn) atomicAdd(&s_hist[cls * HB + (uint32_t)(packed >> 32)], 1u);
         }
       }
@@ -1856,14 +1875,7 @@ __global__ void __launch_bounds__(256) mih_bucket_stream_kernel(const StreamPara
   uint64_t qw[W];
 #pragma unroll
   for (int j = 0; j < W; ++j) qw[j] = p.queries[(uint64_t)slot * W + j];
-  auto qkey = [&](uint32_t t) {
-    const uint32_t bp = t * s;
-    uint32_t v = 0;
-#pragma unroll
-    for (int j = 0; j < W; ++j)
-      if ((uint32_t)j == (bp >> 6)) v = (uint32_t)(qw[j] >> (bp & 63)) & smask;
-    return v;
-  };
+  const bool signext = (p.flags & VC_FLAG_REF_SIGNEXT_KEYS) && s < 32;
   if (tid < 2) s_tot[tid] = 0;
   if (p.trace && tid == 0) p.trace[3ull * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
   __syncthreads();
@@ -1885,10 +1897,10 @@ __global__ void __launch_bounds__(256) mih_bucket_stream_kernel(const StreamPara
     }
     const uint32_t mask = r ? vc_unrank(j, r, s) : 0u;
     // binaryToInt's sign-extended keys (Pilaf/image_tools.h:13): a probe that flips the top bit matches nothing
-    const bool dead = (p.flags & VC_FLAG_REF_SIGNEXT_KEYS) && ((mask >> (s - 1)) & 1u);
+    const bool dead = signext && ((mask >> (s - 1)) & 1u);
     uint32_t off = 0, len = 0;
     if (!dead) {
-      const uint32_t key = qkey(t) ^ mask;
+      const uint32_t key = vc_substr(qw, t, s, smask) ^ mask;
       off = p.tables[t].offsets[key];
       len = p.tables[t].offsets[key + 1] - off;
     }
@@ -1944,18 +1956,9 @@ __global__ void __launch_bounds__(256) mih_bucket_stream_kernel(const StreamPara
     for (int j = 0; j < W; ++j) dist += (uint32_t)__popcll(x[j] ^ qw[j]);
     bool hit = valid && dist <= p.radius;
     if (__ballot(hit) == 0) return;
-    if (hit) {   // owner rule (mih_probe_kernel): reported by the first table holding the minimum substring distance
-      for (uint32_t tt = 0; tt < m; ++tt) {
-        const uint32_t bp = tt * s;
-        uint32_t field = 0;
-#pragma unroll
-        for (int j = 0; j < W; ++j)
-          if ((uint32_t)j == (bp >> 6)) field = (uint32_t)((x[j] ^ qw[j]) >> (bp & 63)) & smask;
-        const uint32_t d = __popc(field);
-        bool reach = true;
-        if (p.flags & VC_FLAG_REF_SIGNEXT_KEYS) reach = ((field >> (s - 1)) & 1u) == 0;
-        if (tt != t && reach && (d < dt || (d == dt && tt < t))) hit = false;
-      }
+    if (hit) {   // (the owner rule's sum of substring distances is dist again)
+      uint32_t dsum;
+      hit = vc_owner_dist(x, qw, m, s, smask, t, dt, signext, dsum);
     }
     const uint64_t km = __ballot(hit);
     if (km == 0) return;
@@ -2101,11 +2104,8 @@ __global__ void __launch_bounds__(256) mih_replay_kernel(const VcMihReplayArgs a
           if ((uint32_t)(v >> 32) != D) continue;
           const uint32_t local = (uint32_t)v - a.id_base;
           bool all_eq = true;
-          for (uint32_t t = 0; t < m; ++t) {
-            const uint32_t bp = t * S;
-            const uint64_t x = a.cols[(uint64_t)(bp >> 6) * a.stride + local] ^ a.queries[(uint64_t)q * a.W + (bp >> 6)];
-            all_eq = all_eq && (uint32_t)__popc((uint32_t)(x >> (bp & 63)) & smask) == r0;
-          }
+          for (uint32_t t = 0; t < m; ++t)
+            all_eq = all_eq && (uint32_t)__popc(vc_substr_mem(a.cols + local, a.stride, a.queries + (uint64_t)q * a.W, t, S, smask)) == r0;
           if (!all_eq) {
             const uint32_t at = atomicAdd(&s_ntie, 1u);
             if (at < MR_TIES) s_tie[at] = v;
@@ -2165,6 +2165,7 @@ __global__ void __launch_bounds__(256) mih_minsub_count_kernel(const uint64_t* _
 #pragma unroll
     for (int q = 0; q < MC_Q; ++q) {
       if ((uint32_t)q >= nq) break;
+      // (vc_substr written out: through the helper the W = 1 instantiation grows from 1 075 to 1 386 instructions, 52 to 56 VGPRs)
       uint32_t ms = 0xFFFFFFFFu;
       for (uint32_t t = 0; t < m; ++t) {
         const uint32_t bp = t * sbits;
@@ -2406,11 +2407,8 @@ __device__ __forceinline__ bool mih_tie_hit(const uint64_t* __restrict__ cols, u
   for (uint32_t j = 0; j < W; ++j) d += (uint32_t)__popcll(cols[(uint64_t)j * stride + i] ^ qw[j]);
   if (d != D) return false;
   const uint32_t smask = sbits == 32 ? 0xFFFFFFFFu : ((1u << sbits) - 1u);
-  uint32_t ms = 0xFFFFFFFFu;
-  for (uint32_t t = 0; t < m; ++t) {
-    const uint32_t bp = t * sbits;
-    ms = min(ms, (uint32_t)__popc((uint32_t)((cols[(uint64_t)(bp >> 6) * stride + i] ^ qw[bp >> 6]) >> (bp & 63)) & smask));
-  }
+  uint32_t ms = 0xFFFFFFFFu;   // minimum substring distance = the shell in which the radius loop first verifies the item
+  for (uint32_t t = 0; t < m; ++t) ms = min(ms, (uint32_t)__popc(vc_substr_mem(cols + i, stride, qw, t, sbits, smask)));
   return ms <= rad;
 }
 
