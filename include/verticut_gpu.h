@@ -315,6 +315,25 @@ int vc_sharded_root_device(const vc_sharded* h, int* device);
  * replaces: search_R_neighbors on every rank + gather_vectors + the master-side dedup (search_worker.cc:177-199,222-264). */
 int vc_sharded_search_radius(vc_sharded* h, const void* queries, uint32_t nq, uint32_t radius, uint32_t mode,
                              uint64_t* out, uint64_t out_cap, uint64_t* out_offsets);
+/* Device-resident, stream-ordered form: arguments and result layout as vc_search_radius_dev, modes VC_MODE_LINEAR and
+ * VC_MODE_MIH_EXACT; d_queries (nq*bits/8 bytes), d_out (out_cap packed values) and d_offsets (nq+1 entries) are device memory on
+ * the ROOT device (vc_sharded_root_device), `stream` a stream of that device (NULL = its null stream, VC_STREAM_OWN = the
+ * handle's own).  Results of query i, ascending packed, at d_out[d_offsets[i] .. d_offsets[i+1]): those of one vc_engine holding
+ * the union, hence those of vc_sharded_search_radius.  VC_ERR_CAPACITY when the union's total exceeds out_cap: d_offsets then
+ * holds the needed counts (d_offsets[nq] the total) and d_out is untouched.
+ * The queries reach every other device by one peer copy; every non-empty shard runs its own radius search into a buffer of the
+ * handle on its device (the shards of a device one after the other, the devices concurrently on host threads), and as in
+ * vc_search_radius_dev each of these makes the host wait once for the shard's total -- one wait per shard and call; their sum is
+ * the union's total, so nothing further is waited for.  A remote shard's offsets and results travel to the root by one
+ * hipMemcpyPeerAsync each -- peer copies whatever vc_sharded_config.exchange says: the lengths vary and only the root needs
+ * them -- and shards of the root device are read in place.  Two kernels on the root finish the call: the union's offsets, and a
+ * rank merge that places every value by binary searches in the other shards' (ascending, id-disjoint) segments.  There is no
+ * padded ring and no size limit besides memory: scratch is proportional to the results found.  The merge may still be running
+ * on `stream` when the call returns; results are valid in stream order.
+ * replaces: search_R_neighbors on every rank + gather_vectors + the master-side dedup (search_worker.cc:177-199,222-264;
+ * mpi_coordinator.cc:34-69) for callers that keep the batch in HBM. */
+int vc_sharded_search_radius_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t radius, uint32_t mode,
+                                 uint64_t* d_out, uint64_t out_cap, uint64_t* d_offsets, void* stream);
 /* borrow shard g's engine (bucket views, timing, files); its id range is [*first_id, *first_id + *n_ids) */
 int vc_sharded_shard(vc_sharded* h, uint32_t shard, vc_engine** e, uint64_t* first_id, uint64_t* n_ids);
 

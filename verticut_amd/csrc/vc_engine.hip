@@ -950,6 +950,24 @@ int vc_engine_knn_capped(vc_engine* e, const void* d_queries, uint32_t nq, uint3
   return rc;
 }
 
+int vc_engine_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t radius, uint32_t mode, uint64_t* d_out, uint64_t out_cap,
+                         uint64_t* d_offsets, uint64_t* total, hipStream_t s) {
+  if (!e || !d_queries || !d_offsets || !total || (!d_out && out_cap) || nq == 0) return VC_ERR_INVALID;
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "radius search: mode must be LINEAR or MIH_EXACT");
+  if (mode == VC_MODE_MIH_EXACT && !e->mih) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
+  int rc = bind_device(e);
+  if (rc) return rc;
+  hipStream_t saved = e->stream;
+  e->stream = s;
+  timing_begin(e);
+  *total = 0;
+  rc = vc_radius_search(e->mih, mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs,
+                        (const uint64_t*)d_queries, nq, radius, d_out, out_cap, d_offsets, true, &e->radius_work, e->stream, &e->err, total);
+  timing_end(e);
+  e->stream = saved;
+  return rc;
+}
+
 extern "C" {
 
 int vc_search_knn_dev_stats(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out,

@@ -119,6 +119,10 @@ int vc_engine_view(vc_engine* e, VcEngineView* v);
 // exact MIH k-NN capped at shell r_cap (vc_mih_search's r_cap) on stream s; d_stats as vc_search_knn_dev_stats
 int vc_engine_knn_capped(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t r_cap, uint64_t* d_out, uint32_t* d_counts,
                          vc_query_stats* d_stats, hipStream_t s);
+// vc_search_radius_dev on stream s with the shard's total returned to the host: *total = entries found, also when they exceed
+// out_cap (VC_ERR_CAPACITY: the caller grows its buffer to *total and repeats, no read-back of the offsets)
+int vc_engine_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t radius, uint32_t mode, uint64_t* d_out, uint64_t out_cap,
+                         uint64_t* d_offsets, uint64_t* total, hipStream_t s);
 // the same over the gathered shard slots of vc_sharded_* (rows + counts per slot; a flagged shard row flags the merged row)
 hipError_t vc_launch_select_slots(const uint64_t* d_base, uint64_t slot_words, uint32_t cnt_off_words, uint32_t n_lists, uint32_t nq,
                                   uint32_t k, uint64_t* d_out, uint32_t* d_out_count, hipStream_t s);

@@ -3989,7 +3989,7 @@ static int radius_search_device(VcMihIndex* ix, bool use_mih, const uint64_t* d_
 int vc_radius_search(VcMihIndex* ix, bool use_mih, const uint64_t* d_cols, uint64_t stride, uint64_t n, uint32_t W,
                      uint32_t id_base, uint32_t n_cu, const VcKnobs* knobs, const uint64_t* d_q, uint32_t nq, uint32_t radius,
                      uint64_t* out, uint64_t out_cap, uint64_t* out_offsets, bool device_out, VcRadiusWork* wk, hipStream_t s,
-                     std::string* err) {
+                     std::string* err, uint64_t* total_out) {
   if (use_mih && n != ix->n) return fail(err, VC_ERR_STATE, "index is stale: codes were added after vc_build_index()");
   if (use_mih) {
     // a radius whose substring shells cost more probes than scanning the shard costs distance evaluations is answered
@@ -4003,8 +4003,10 @@ int vc_radius_search(VcMihIndex* ix, bool use_mih, const uint64_t* d_cols, uint6
   }
   if (device_out) {
     uint64_t total = 0;
-    return radius_search_device(ix, use_mih, d_cols, stride, n, W, id_base, n_cu, knobs, d_q, nq, radius, out, out_cap, out_offsets,
-                                &total, wk, s, err);
+    const int rc = radius_search_device(ix, use_mih, d_cols, stride, n, W, id_base, n_cu, knobs, d_q, nq, radius, out, out_cap,
+                                        out_offsets, &total, wk, s, err);
+    if (total_out) *total_out = total;
+    return rc;
   }
   // host-pointer API: stage in device memory, grow the staging buffer to what the call needs, one copy back
   if (wk->offs_cap < (size_t)nq + 1) {

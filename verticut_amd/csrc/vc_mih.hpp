@@ -110,7 +110,8 @@ void vc_radius_work_free(VcRadiusWork* w);
 // device_out = false: out / out_offsets are host memory (staged through the engine's buffers);
 // device_out = true : out (out_cap entries) / out_offsets (nq + 1) are device memory, everything is enqueued on `s`
 // and the host synchronises once at the end.
+// total_out (may be null; device_out only): the entries the call found, also when they exceed out_cap (VC_ERR_CAPACITY).
 int vc_radius_search(VcMihIndex* ix, bool use_mih, const uint64_t* d_cols, uint64_t stride, uint64_t n, uint32_t W,
                      uint32_t id_base, uint32_t n_cu, const VcKnobs* knobs, const uint64_t* d_q, uint32_t nq, uint32_t radius,
                      uint64_t* out, uint64_t out_cap, uint64_t* out_offsets, bool device_out, VcRadiusWork* work, hipStream_t s,
-                     std::string* err);
+                     std::string* err, uint64_t* total_out = nullptr);

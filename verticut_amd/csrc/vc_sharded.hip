@@ -19,7 +19,8 @@
 // In this file: DevBuf (grow-only scratch), Lane, vc_sharded | create / ingest / look-up | ShardBatch = one batch through the
 // shards (prepare_lanes, send_queries, run_lanes, exchange, merge; sharded_search_dev) | VC_FLAG_GLOBAL_STOP: the stop rule
 // (gs_stop_shell), the kernels, the layouts they share with the host (GsRoundLists, GsScanCols, GsScanBlock) and GsSearch,
-// the steps of a flagged call (sharded_global_stop, GsSearch::union_scan) | the search entry points.
+// the steps of a flagged call (sharded_global_stop, GsSearch::union_scan) | the device-resident radius search: its two kernels
+// (union offsets, rank merge) and ShardRadius, the steps of a call (sharded_radius_dev) | the search entry points.
 // ============================================================================
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -36,6 +37,7 @@
 
 #include "vc_internal.hpp"
 #include "vc_mih.hpp"
+#include "vc_sharded_radius.hpp"
 
 namespace {
 
@@ -82,6 +84,7 @@ struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
   int grow(vc_sharded* h, size_t need);   // at least `need` bytes, on the current device; the contents are lost when it grows
+  hipError_t regrow(size_t need);         // the same without the handle's error text (lane threads keep their own)
   void release() { (void)hipFree(p); p = nullptr; bytes = 0; }
   template <class T> T* as() const { return (T*)p; }
 };
@@ -117,6 +120,13 @@ enum RootBuf {
   ROOT_BUFS
 };
 
+// vc_sharded_search_radius_dev, per shard: its flat results and its nq + 1 offsets on the shard's own device; for a shard of
+// another device also the root's copies of both (a shard of the root device is read where it lies).
+struct RadiusShardBufs {
+  DevBuf res, offs;             // on the shard's device
+  DevBuf root_res, root_offs;   // on the root device (remote shards only)
+};
+
 }  // namespace
 
 struct vc_sharded {
@@ -133,6 +143,7 @@ struct vc_sharded {
   hipStream_t root_stream = nullptr;    // stream of the host-pointer calls / VC_STREAM_OWN
   hipEvent_t ev_q = nullptr;            // "the batch's queries are ready" on the caller's stream
   DevBuf buf[ROOT_BUFS];                // see RootBuf
+  std::vector<RadiusShardBufs> rad;     // see RadiusShardBufs
   VcKnobs knobs;                // the handle's own developer knobs: gs_cap (first round's cap), gs_trace
   RcclApi rccl;
   std::vector<ncclComm_t> comms;
@@ -160,14 +171,20 @@ static int sfail(vc_sharded* h, int code, const char* fmt, ...) {
       return sfail(h, _r == hipErrorOutOfMemory ? VC_ERR_NOMEM : VC_ERR_HIP, "%s: %s", #call, hipGetErrorString(_r)); \
   } while (0)
 
-int DevBuf::grow(vc_sharded* h, size_t need) {
-  if (need <= bytes) return VC_OK;
-  if (p) VS_HIP(h, hipFree(p));
+hipError_t DevBuf::regrow(size_t need) {
+  if (need <= bytes) return hipSuccess;
+  hipError_t r = p ? hipFree(p) : hipSuccess;
   p = nullptr;
   bytes = 0;
+  if (r != hipSuccess) return r;
   need = (need + 255) & ~(size_t)255;
-  VS_HIP(h, hipMalloc(&p, need));
+  if ((r = hipMalloc(&p, need)) != hipSuccess) { p = nullptr; return r; }
   bytes = need;
+  return hipSuccess;
+}
+
+int DevBuf::grow(vc_sharded* h, size_t need) {
+  VS_HIP(h, regrow(need));
   return VC_OK;
 }
 
@@ -208,9 +225,16 @@ int vc_sharded_destroy(vc_sharded* h) {
     if (l.done) (void)hipEventDestroy(l.done);
     if (l.stream) (void)hipStreamDestroy(l.stream);
   }
+  for (uint32_t g = 0; g < h->rad.size(); ++g) {
+    if (!h->rad[g].res.p && !h->rad[g].offs.p) continue;   // (a handle whose creation failed may name a device that does not exist)
+    (void)hipSetDevice(h->dev[g]);
+    h->rad[g].res.release();
+    h->rad[g].offs.release();
+  }
   for (vc_engine* e : h->eng) vc_destroy(e);
   (void)hipSetDevice(h->root);
   for (DevBuf& b : h->buf) b.release();
+  for (RadiusShardBufs& b : h->rad) { b.root_res.release(); b.root_offs.release(); }
   if (h->ev_q) (void)hipEventDestroy(h->ev_q);
   if (h->root_stream) (void)hipStreamDestroy(h->root_stream);
   delete h;
@@ -250,6 +274,7 @@ int vc_sharded_create(const vc_sharded_config* cfg, vc_sharded** out) {
   h->lo.resize(h->G);
   h->hi.resize(h->G);
   h->lane_of.resize(h->G);
+  h->rad.resize(h->G);
   int rc = VC_OK;
   for (uint32_t g = 0; g < h->G && rc == VC_OK; ++g) {
     h->dev[g] = cfg->n_devices ? cfg->device_ids[g % h->D] : (int)(g % h->D);
@@ -451,6 +476,22 @@ static int counts_or_own(vc_sharded* h, uint32_t nq, uint32_t** d_counts) {
   return VC_OK;
 }
 
+// The queries of a batch reach every device once: an event on the caller's stream, a peer copy per remote lane into its LANE_Q
+// buffer (grown by the caller).
+static int send_queries_to_lanes(vc_sharded* h, const void* d_queries, size_t qbytes, hipStream_t S) {
+  if (h->lanes.size() <= 1) return VC_OK;
+  VS_HIP(h, hipSetDevice(h->root));
+  VS_HIP(h, hipEventRecord(h->ev_q, S));
+  for (uint32_t li = 0; li < h->lanes.size(); ++li) {
+    if (li == h->root_lane) continue;
+    Lane& l = h->lanes[li];
+    VS_HIP(h, hipSetDevice(l.dev));
+    VS_HIP(h, hipStreamWaitEvent(l.stream, h->ev_q, 0));   // also orders the lane behind the previous batch's copies out of its buffers
+    VS_HIP(h, hipMemcpyPeerAsync(l.buf[LANE_Q].p, l.dev, d_queries, h->root, qbytes, l.stream));
+  }
+  return VC_OK;
+}
+
 // One batch through the shards, and its steps in the order sharded_search_dev takes them.
 // Everything of a batch is enqueued, nothing is waited for (LINEAR; the MIH modes make the host wait inside each shard's
 // vc_search_knn_dev -- how many queries continue decides what is enqueued next -- which is why lanes of different devices
@@ -490,19 +531,7 @@ struct ShardBatch {
   }
 
   // the queries reach every device once: an event on the caller's stream, a peer copy per remote lane
-  int send_queries() {
-    if (h->lanes.size() <= 1) return VC_OK;
-    VS_HIP(h, hipSetDevice(h->root));
-    VS_HIP(h, hipEventRecord(h->ev_q, S));
-    for (uint32_t li = 0; li < h->lanes.size(); ++li) {
-      if (li == h->root_lane) continue;
-      Lane& l = h->lanes[li];
-      VS_HIP(h, hipSetDevice(l.dev));
-      VS_HIP(h, hipStreamWaitEvent(l.stream, h->ev_q, 0));   // also orders the lane behind the previous batch's copies out of its slots
-      VS_HIP(h, hipMemcpyPeerAsync(l.buf[LANE_Q].p, l.dev, d_queries, h->root, qbytes, l.stream));
-    }
-    return VC_OK;
-  }
+  int send_queries() { return send_queries_to_lanes(h, d_queries, qbytes, S); }
 
   // the shards of one device answer the batch for their id ranges, one after the other (on a host thread of its own in the
   // MIH modes: binds the lane's device for that thread, touches only the lane's lane_rc / lane_err)
@@ -1165,6 +1194,266 @@ static int sharded_search_any(vc_sharded* h, const void* d_queries, uint32_t nq,
   return sharded_search_dev(h, d_queries, nq, k, mode, d_out, d_counts, d_stats, S);
 }
 
+
+// ---- radius search over the shards, device-resident ---------------------------------------------------------------------------
+// vc_sharded_search_radius_dev (search_R_neighbors on every rank + gather_vectors + the master's dedup, search_worker.cc:177-199,
+// 222-264, for callers that keep the batch in HBM).  Every non-empty shard answers the batch for its id range into its own flat
+// result array + nq + 1 offsets; what a query's union looks like follows from two facts: a shard's segment is ascending, and the
+// shards hold disjoint id ranges, so no two packed values (dist << 32 | id) of a query are equal.  The union is therefore a
+// merge of G sorted lists of DISTINCT values, and the place of value v -- element i of shard g's segment of query q -- is
+//     out_offs[q] + i + sum over g' != g of lower_bound(segment of g' for q, v)
+// (i values of its own list and lower_bound values of every other list are smaller; no tie rule is needed).  Two kernels on the
+// root: the union's offsets (a scan over the queries of the shards' summed segment lengths) and the rank merge, whose grid runs
+// over ELEMENTS -- (shard, chunk of that shard's flat array) -- so that a heavy query is spread over many blocks.
+// Scratch is what the shards found (no padded ring); the host waits once per shard, inside the shard's own call, for its total:
+// the sum of those totals is the union's total, so the capacity decision and the merge grid need no further wait.
+static_assert(VC_RMERGE_SHARDS == VC_MAX_SHARDS, "VcRadiusMergeArgs holds one pointer pair per shard");
+
+// d_offsets[q] = sum over q' < q and all shards of len_g(q'), d_offsets[nq] = the total.  One block walks nq in tiles of its
+// 1024 threads with a running carry.  A query's length is at most 2^32 (ids are uint32), so its low and high 16-bit halves each
+// add up to less than 2^32 over a wave: two 32-bit wave scans make the 64-bit one.
+extern "C" __global__ void __launch_bounds__(1024) vc_sharded_radius_offsets_kernel(const VcRadiusMergeArgs a, uint64_t* __restrict__ offsets) {
+  __shared__ uint64_t s_w[1024 / VC_WAVE];
+  const uint32_t lane = vc_lane(), wave = threadIdx.x / VC_WAVE;
+  uint64_t carry = 0;
+  for (uint32_t q0 = 0; q0 < a.nq; q0 += 1024) {
+    const uint32_t q = q0 + threadIdx.x;
+    uint64_t len = 0;
+    if (q < a.nq)
+      for (uint32_t g = 0; g < a.G; ++g)
+        if (a.offs[g]) len += a.offs[g][q + 1] - a.offs[g][q];
+    uint32_t tlo, thi;
+    const uint32_t elo = vc_wave_excl_scan((uint32_t)(len & 0xFFFFu), tlo);
+    const uint32_t ehi = vc_wave_excl_scan((uint32_t)(len >> 16), thi);
+    if (lane == 0) s_w[wave] = ((uint64_t)thi << 16) + tlo;
+    __syncthreads();
+    uint64_t base = carry, tile = 0;
+    for (uint32_t w = 0; w < 1024 / VC_WAVE; ++w) {
+      if (w < wave) base += s_w[w];
+      tile += s_w[w];
+    }
+    if (q < a.nq) offsets[q] = base + ((uint64_t)ehi << 16) + elo;
+    carry += tile;
+    __syncthreads();   // the next tile rewrites s_w
+  }
+  if (threadIdx.x == 0) offsets[a.nq] = carry;
+}
+
+// the q in [lo, hi) with offs[q] <= e < offs[q + 1]; needs offs[lo] <= e < offs[hi]
+__device__ __forceinline__ uint32_t rmerge_query_of(const uint64_t* __restrict__ offs, uint32_t lo, uint32_t hi, uint64_t e) {
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (offs[mid] <= e) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// One block per (shard g, chunk of VC_RMERGE_CHUNK elements of g's flat result array); a chunk may hold parts of many queries
+// and a query may span many chunks.  The block finds the chunk's first and last query, keeps that range of g's offsets in LDS
+// (queries beyond the window -- a chunk that crosses more than VC_RMERGE_CHUNK queries, most of them empty -- are read from
+// global memory), every thread finds its element's query there, ranks the value in the other shards' segments of that query by
+// binary search in global memory and writes it once.  No atomics, no scratch, nothing padded.
+extern "C" __global__ void __launch_bounds__(VC_RMERGE_THREADS) vc_sharded_radius_merge_kernel(const VcRadiusMergeArgs a) {
+  constexpr uint32_t WIN = VC_RMERGE_CHUNK + 2;
+  __shared__ uint64_t s_off[WIN];
+  __shared__ uint32_t s_q[2];
+  uint32_t g = 0;
+  while (g + 1 < VC_RMERGE_SHARDS && blockIdx.x >= a.first_block[g + 1]) ++g;   // first_block[g] <= blockIdx.x < first_block[g + 1]
+  const uint64_t* __restrict__ og = a.offs[g];
+  const uint64_t* __restrict__ sg = a.seg[g];
+  const uint64_t e0 = (uint64_t)(blockIdx.x - a.first_block[g]) * VC_RMERGE_CHUNK;
+  const uint64_t e1 = min(e0 + VC_RMERGE_CHUNK, a.total_g[g]);
+  if (e0 >= e1) return;                                                         // (never: the grid holds no empty chunk)
+  // og[0] = 0 <= e < total_g = og[nq] for every element of the shard; two waves search at the same time
+  if (threadIdx.x == 0) s_q[0] = rmerge_query_of(og, 0, a.nq, e0);
+  if (threadIdx.x == VC_WAVE) s_q[1] = rmerge_query_of(og, 0, a.nq, e1 - 1);
+  __syncthreads();
+  const uint32_t q_lo = s_q[0], q_hi = s_q[1];
+  const uint32_t nwin = min(q_hi - q_lo + 2, WIN);                              // og[q_lo .. q_hi + 1], as far as the window goes
+  for (uint32_t i = threadIdx.x; i < nwin; i += VC_RMERGE_THREADS) s_off[i] = og[q_lo + i];
+  __syncthreads();
+  auto off = [&](uint32_t q) { return q - q_lo < nwin ? s_off[q - q_lo] : og[q]; };
+  for (uint32_t j = 0; j < VC_RMERGE_PER_THREAD; ++j) {
+    const uint64_t e = e0 + (uint64_t)j * VC_RMERGE_THREADS + threadIdx.x;
+    if (e >= e1) break;
+    const uint64_t v = sg[e];
+    uint32_t lo = q_lo, hi = q_hi + 1;                                          // off(lo) <= e < off(hi)
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (off(mid) <= e) lo = mid; else hi = mid;
+    }
+    const uint32_t q = lo;
+    uint64_t pos = a.out_offs[q] + (e - off(q));
+    for (uint32_t g2 = 0; g2 < a.G; ++g2) {
+      if (g2 == g || !a.offs[g2]) continue;
+      const uint64_t b = a.offs[g2][q];
+      const uint64_t* __restrict__ seg = a.seg[g2] + b;
+      uint64_t l = 0, r = a.offs[g2][q + 1] - b;                                // lower_bound: how many of g2's values are below v
+      while (l < r) {
+        const uint64_t mid = l + (r - l) / 2;
+        if (seg[mid] < v) l = mid + 1; else r = mid;
+      }
+      pos += l;
+    }
+    if (pos < a.total) a.out[pos] = v;
+  }
+}
+
+// One radius batch through the shards, and its steps in the order sharded_radius_dev takes them.  Queries, results and offsets
+// live in HBM on the root device; the merge may still run on `S` when the call returns (results are valid in `S` order).
+struct ShardRadius {
+  vc_sharded* h;
+  const void* d_queries;
+  uint32_t nq, radius, mode;
+  uint64_t* d_out;
+  uint64_t out_cap;
+  uint64_t* d_offsets;
+  hipStream_t S;
+  size_t qbytes;
+  uint64_t total_g[VC_MAX_SHARDS];      // what every shard found (empty shards: 0), known to the host after run_lanes
+  VcRadiusMergeArgs A;
+  std::vector<int> lane_rc;             // run_lane: the first failure of every lane, reported by run_lanes
+  std::vector<std::string> lane_err;
+
+  // every non-empty shard's offsets and (first call: starting size) result buffer on its own device, the remote lanes' query copy
+  int prepare_buffers() {
+    int rc;
+    size_t first_bytes;
+    if (!vc_rshard_bytes(vc_rshard_first_cap(nq), &first_bytes)) return sfail(h, VC_ERR_NOMEM, "radius search: batch too large");
+    for (uint32_t li = 0; li < h->lanes.size(); ++li) {
+      Lane& l = h->lanes[li];
+      VS_HIP(h, hipSetDevice(l.dev));
+      if (li != h->root_lane && (rc = l.buf[LANE_Q].grow(h, qbytes))) return rc;
+      for (uint32_t g : l.shards) {
+        if (shard_size(h, g) == 0) continue;
+        if ((rc = h->rad[g].offs.grow(h, vc_rshard_offs_bytes(nq)))) return rc;
+        if ((rc = h->rad[g].res.grow(h, first_bytes))) return rc;
+      }
+    }
+    return VC_OK;
+  }
+
+  int send_queries() { return send_queries_to_lanes(h, d_queries, qbytes, S); }
+
+  // the shards of one device answer the batch for their id ranges, one after the other; every shard's call makes the host wait
+  // for its total.  A shard whose result buffer was too small grows it to the reported total and repeats once.  (On a host
+  // thread of its own when there are several lanes: binds the lane's device for that thread, touches only the lane's shards'
+  // buffers and totals and the lane's lane_rc / lane_err.)
+  void run_lane(uint32_t li) {
+    Lane& l = h->lanes[li];
+    const bool is_root = li == h->root_lane;
+    hipStream_t ls = is_root ? S : l.stream;
+    const void* q = is_root ? d_queries : l.q();
+    auto hip = [&](hipError_t r, const char* what) {
+      if (r != hipSuccess && lane_rc[li] == VC_OK) {
+        lane_rc[li] = r == hipErrorOutOfMemory ? VC_ERR_NOMEM : VC_ERR_HIP;
+        lane_err[li] = std::string(what) + ": " + hipGetErrorString(r);
+      }
+      return r == hipSuccess;
+    };
+    if (!hip(hipSetDevice(l.dev), "hipSetDevice")) return;
+    for (uint32_t g : l.shards) {
+      if (shard_size(h, g) == 0) continue;   // never asked: zero-length segments
+      RadiusShardBufs& B = h->rad[g];
+      for (int attempt = 0;; ++attempt) {
+        const uint64_t cap = B.res.bytes / 8;
+        const int r = vc_engine_radius_dev(h->eng[g], q, nq, radius, mode, B.res.as<uint64_t>(), cap, B.offs.as<uint64_t>(), &total_g[g], ls);
+        if (r == VC_OK) break;
+        size_t need;
+        if (r != VC_ERR_CAPACITY || attempt || !vc_rshard_must_repeat(total_g[g], cap) || !vc_rshard_bytes(total_g[g], &need)) {
+          lane_rc[li] = r;
+          lane_err[li] = std::string("shard ") + std::to_string(g) + ": " + vc_last_error(h->eng[g]);
+          return;
+        }
+        if (!hip(B.res.regrow(need), "result buffer")) return;   // (the first attempt has been waited for: nothing reads the old one)
+      }
+    }
+    if (!is_root) hip(hipEventRecord(l.done, ls), "hipEventRecord");
+  }
+
+  // every lane: in turn when there is one, else concurrently (every shard call waits on the host, in both modes)
+  int run_lanes() {
+    lane_rc.assign(h->lanes.size(), VC_OK);
+    lane_err.assign(h->lanes.size(), std::string());
+    for (uint64_t& t : total_g) t = 0;
+    if (h->lanes.size() == 1) {
+      run_lane(0);
+    } else {
+      std::vector<std::thread> th;
+      for (uint32_t li = 0; li < h->lanes.size(); ++li) th.emplace_back([this, li] { run_lane(li); });
+      for (auto& t : th) t.join();
+    }
+    for (uint32_t li = 0; li < h->lanes.size(); ++li)
+      if (lane_rc[li]) return sfail(h, lane_rc[li], "%s", lane_err[li].c_str());
+    return VC_OK;
+  }
+
+  // replaces gather_vectors (mpi_coordinator.cc:34-69): a remote shard's offsets and its total_g results reach the root by one
+  // peer copy each, behind its lane's `done` event -- always peer copies, whatever the handle's exchange: the lengths vary and
+  // only the root needs the data.  Shards of the root device are read where they lie.  Leaves the pointers in A.
+  int exchange() {
+    VS_HIP(h, hipSetDevice(h->root));
+    int rc;
+    for (uint32_t g = 0; g < h->G; ++g) {   // the root's copies first (growing one waits for the device)
+      if (h->lane_of[g] == h->root_lane || shard_size(h, g) == 0) continue;
+      size_t bytes;
+      if (!vc_rshard_bytes(total_g[g], &bytes)) return sfail(h, VC_ERR_NOMEM, "radius search: shard %u found too much", g);
+      if ((rc = h->rad[g].root_offs.grow(h, vc_rshard_offs_bytes(nq)))) return rc;
+      if ((rc = h->rad[g].root_res.grow(h, bytes))) return rc;
+    }
+    for (uint32_t li = 0; li < h->lanes.size(); ++li) {
+      if (li == h->root_lane) continue;
+      Lane& l = h->lanes[li];
+      VS_HIP(h, hipStreamWaitEvent(S, l.done, 0));
+      for (uint32_t g : l.shards) {
+        if (shard_size(h, g) == 0) continue;
+        RadiusShardBufs& B = h->rad[g];
+        VS_HIP(h, hipMemcpyPeerAsync(B.root_offs.p, h->root, B.offs.p, l.dev, vc_rshard_offs_bytes(nq), S));
+        if (total_g[g]) VS_HIP(h, hipMemcpyPeerAsync(B.root_res.p, h->root, B.res.p, l.dev, (size_t)total_g[g] * 8, S));
+      }
+    }
+    for (uint32_t g = 0; g < VC_MAX_SHARDS; ++g) {
+      const bool empty = g >= h->G || shard_size(h, g) == 0, local = !empty && h->lane_of[g] == h->root_lane;
+      A.offs[g] = empty ? nullptr : (local ? h->rad[g].offs : h->rad[g].root_offs).as<uint64_t>();
+      A.seg[g] = empty ? nullptr : (local ? h->rad[g].res : h->rad[g].root_res).as<uint64_t>();
+    }
+    return VC_OK;
+  }
+
+  // the union's offsets (also when the call is going to report VC_ERR_CAPACITY: they are the needed counts)
+  int offsets() {
+    if (!vc_rmerge_plan(total_g, h->G, &A)) return sfail(h, VC_ERR_CAPACITY, "radius search: more results than one merge launch can place");
+    A.nq = nq;
+    A.out_offs = d_offsets;
+    A.out = d_out;
+    hipLaunchKernelGGL(vc_sharded_radius_offsets_kernel, dim3(1), dim3(1024), 0, S, A, d_offsets);
+    VS_HIP(h, hipGetLastError());
+    return VC_OK;
+  }
+
+  // the rank merge straight to the final positions; not launched when the results do not fit or there are none
+  int merge() {
+    if (A.total > out_cap) return sfail(h, VC_ERR_CAPACITY, "radius search: output buffer too small (needed counts are in d_offsets)");
+    if (A.total == 0) return VC_OK;
+    hipLaunchKernelGGL(vc_sharded_radius_merge_kernel, dim3(A.first_block[VC_RMERGE_SHARDS]), dim3(VC_RMERGE_THREADS), 0, S, A);
+    VS_HIP(h, hipGetLastError());
+    return VC_OK;
+  }
+};
+
+// Any device may be current on entry; the root device is on return from exchange() onwards.
+static int sharded_radius_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t radius, uint32_t mode, uint64_t* d_out,
+                              uint64_t out_cap, uint64_t* d_offsets, hipStream_t S) {
+  ShardRadius b{h, d_queries, nq, radius, mode, d_out, out_cap, d_offsets, S, (size_t)nq * h->nbytes, {}, {}, {}, {}};
+  int rc = b.prepare_buffers();
+  if (!rc) rc = b.send_queries();
+  if (!rc) rc = b.run_lanes();
+  if (!rc) rc = b.exchange();
+  if (!rc) rc = b.offsets();
+  if (!rc) rc = b.merge();
+  return rc;
+}
+
 extern "C" {
 
 int vc_sharded_root_device(const vc_sharded* h, int* device) {
@@ -1329,6 +1618,13 @@ int vc_sharded_search_radius(vc_sharded* h, const void* queries, uint32_t nq, ui
       dst = std::copy(res[g].begin() + offs[g][q], res[g].begin() + offs[g][q + 1], dst);
   }
   return sort_segments_on_root(h, ring, cap2, count, out_offsets, total, nq, out);
+}
+
+int vc_sharded_search_radius_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t radius, uint32_t mode, uint64_t* d_out,
+                                 uint64_t out_cap, uint64_t* d_offsets, void* stream) {
+  if (!h || !d_queries || !d_offsets || nq == 0 || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) || (!d_out && out_cap))
+    return VC_ERR_INVALID;
+  return sharded_radius_dev(h, d_queries, nq, radius, mode, d_out, out_cap, d_offsets, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
 }
 
 }  // extern "C"

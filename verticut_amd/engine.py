@@ -32,6 +32,7 @@ EXPORTS = [
     "vc_sharded_create", "vc_sharded_destroy", "vc_sharded_last_error", "vc_sharded_exchange", "vc_sharded_add_codes",
     "vc_sharded_add_synthetic", "vc_sharded_size", "vc_sharded_build_index", "vc_sharded_get_code", "vc_sharded_get_bucket",
     "vc_sharded_search_knn", "vc_sharded_shard", "vc_sharded_search_knn_dev", "vc_sharded_root_device", "vc_search_knn_dev_stats", "vc_sharded_search_radius",
+    "vc_sharded_search_radius_dev",
 ]
 MAX_SHARDS = 16
 EXCHANGE_AUTO, EXCHANGE_PEER_COPY, EXCHANGE_RCCL = 0, 1, 2
@@ -140,6 +141,7 @@ def load_library():
     L.vc_sharded_search_knn_dev.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp]
     L.vc_sharded_root_device.argtypes = [vp, C.POINTER(C.c_int)]
     L.vc_sharded_search_radius.argtypes = [vp, vp, u32, u32, u32, vp, u64, vp]
+    L.vc_sharded_search_radius_dev.argtypes = [vp, vp, u32, u32, u32, vp, u64, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -471,6 +473,12 @@ class ShardedEngine:
                 return [out[int(offs[i]):int(offs[i + 1])].copy() for i in range(nq)]
             cap = int(offs[nq])
         raise VcError(VC_ERR_CAPACITY, "radius search output does not fit")
+
+    def search_radius_dev(self, d_queries, nq, radius, d_out, out_cap, d_offsets, mode=MODE_MIH_EXACT, stream=None):
+        """vc_sharded_search_radius_dev: raw device addresses on the root device, results valid in `stream` order; returns VC_OK
+        or VC_ERR_CAPACITY (d_offsets then holds the needed counts, d_offsets[nq] the total; d_out is untouched)."""
+        return self._check(self._L.vc_sharded_search_radius_dev(self._h, d_queries, nq, radius, mode, d_out, out_cap, d_offsets, stream),
+                           ok=(VC_OK, VC_ERR_CAPACITY))
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)
