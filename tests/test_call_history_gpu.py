@@ -305,6 +305,43 @@ def test_any_order_of_the_calls_returns_the_same(vc, oracle, monkeypatch, name, 
         assert int((far >= 2).sum()) * 10 >= len(far) * 6                 # the far batch is one that moves group_hint to 3
 
 
+# ----------------------------------------------------------------------------- the scan fallback's tile, the clean state's layout
+def test_fallback_tile_and_group_layout_do_not_leak(vc, oracle, monkeypatch, capfd):
+    """query_tile = 4 and every exact MIH query handed to the verify kernel (VC_MIH_SWITCH=2), which scans in tiles of 32 whatever
+    the engine's tile is.  LINEAR calls before and after it keep the engine's tile -- every verify launch of theirs names qt <= 4 --
+    and three group layouts follow each other on one state buffer (GQ 5, GQ 40 in the fallback, GQ 64 in two groups): a state
+    handed back clean for one layout is not taken for clean by the next.  Both orders of the calls return the same, exact rows."""
+    import scan_shapes_common as S
+    bits, m, id_base, k = 128, 4, 300, 10
+    monkeypatch.setenv("VC_MIH_SWITCH", "2")                              # knobs are read at vc_create
+    monkeypatch.setenv("VC_SCAN_SHAPE_TRACE", "1")
+    codes = H.make_codes(oracle, bits, m, n=20_000)
+    q = H.make_queries(codes, bits, m)
+    exp = Expect(oracle, codes, q, m, id_base)
+    # (uniform queries: their k-th distance lies shells beyond the query kernel's own, so they do reach the forced switch)
+    calls = [H.knn("knn", H.LINEAR, k, 5, "near"), H.knn("knn", H.EXACT, k, 40, "uniform"), H.knn("knn_dev", H.LINEAR, k, 70, "far", stream="null")]
+    for i in range(len(q)):                                               # LINEAR rows: the oracle's scan, not the model's sort
+        assert np.array_equal(exp.linear(i, k)[0], oracle.linear_knn(codes, q[i], k, id_base=id_base))
+    seen = {}
+    for seq in (calls, calls[::-1]):
+        with vc.Engine(bits, capacity=len(codes), n_tables=m, id_base=id_base, query_tile=4) as e:
+            e.add_codes(codes)
+            e.build_index()
+            run = Runner(vc, e, q)
+            for c in seq:
+                capfd.readouterr()
+                run_and_check(vc, run, c, lambda c, idx: expected_knn(exp, c, idx), None, seen, "tile")
+                tiles = [t["qt"] for t in S.parse_trace(capfd.readouterr().err)]
+                print("%r: verify tiles %s" % (tuple(c), tiles))
+                if c.mode == H.LINEAR:
+                    want = [4] * (c.nq // 4) + [c.nq % 4] * (c.nq % 4 != 0)       # (a group of 64 is whole tiles: 70 = 16 x 4, then 4 + 2)
+                    assert tiles == want, (tuple(c), tiles)
+                else:
+                    # the forced switch hands all 40 unfinished queries over at once: one group of 40 in the fallback's tile of 32
+                    assert tiles == [32, 8], (tuple(c), tiles)
+                assert e.device_status() == 0
+
+
 # ----------------------------------------------------------------------------- ring-overflow history
 def test_ring_overflow_history(vc, oracle):
     """duplicate-heavy clusters behind a small candidate ring: LINEAR batches whose rows overflow the ring (thousands of ties at the

@@ -1,5 +1,5 @@
 import sys, time, os
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np, torch
 from verticut_amd import engine as vc
 e = vc.Engine(128, capacity=125_000_000, query_tile=8, flags=vc.FLAG_LEAN_TIMING)

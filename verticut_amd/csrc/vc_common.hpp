@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/verticut_gpu.h"
+#include "vc_linear_plan.hpp"
 
 #define VC_WAVE 64
 #define VC_MAX_K 8192u           // LDS bitonic capacity of the select kernel (64 KiB of uint64)
@@ -15,7 +16,6 @@
 #define VC_PAD_ITEMS 8192ull     // column stride granularity: every scan chunk shape divides this
 #define VC_MAX_W 8               // 512-bit codes
 #define VC_PACK_INF 0xFFFFFFFFFFFFFFFFull
-#define VC_SHIST_COPIES 16       // partial histograms per bootstrap stage (spreads the flush atomics over L2 channels)
 
 // native 16-byte vector (two uint64): one global_load_dwordx4 per lane
 typedef unsigned long long vc_u64x2 __attribute__((ext_vector_type(2)));
@@ -131,8 +131,3 @@ struct VcScanParams {
   uint32_t shist_copies;
   uint32_t bits;
 };
-// The linear path gives every query its own 128-byte line for its threshold and for its ring cursor: both are read /
-// updated coherently by every wave that enters the rare path, coherent traffic to one line is served by ONE memory
-// channel, and eight queries sharing a line overloaded that channel enough to slow the whole (channel-interleaved)
-// code stream by 5-14 % depending on where the allocation happened to land (tools/placement_probe.py).
-#define VC_QUERY_LINE_WORDS 32u

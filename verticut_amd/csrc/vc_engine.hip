@@ -19,7 +19,7 @@ struct vc_engine {
   int device = 0;
   uint32_t bits = 0, W = 0, m = 0, sbits = 0, n_cu = 0;
   uint32_t cap = 65536, qtile = 32, scan_blocks = 0;
-  bool qtile_auto = true;        // vc_config.query_tile == 0 and no VC_QUERY_TILE: the tile follows the database size (linear_tile)
+  bool qtile_auto = true;        // vc_config.query_tile == 0 and no VC_QUERY_TILE: the tile follows the database size (vc_linear_tile)
   uint64_t n = 0, stride = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
   uint64_t* d_cols = nullptr;
@@ -29,7 +29,7 @@ struct vc_engine {
   uint8_t* h_pin = nullptr;     size_t pin_bytes = 0;     // pinned host staging of the host-pointer search calls (queries | rows | counts)
   uint8_t* h_pipe = nullptr;    hipEvent_t pipe_ev[2] = {nullptr, nullptr};   // two pinned chunks: large result sets on their way to pageable memory
   uint64_t* d_q = nullptr;      size_t q_bytes = 0;       // queries [nq][W]
-  uint32_t* d_state = nullptr;  size_t state_bytes = 0;   // per tile: count | hist | shist | tau
+  uint32_t* d_state = nullptr;  size_t state_bytes = 0;   // per group: LinearState (vc_linear_plan.hpp)
   uint64_t* d_ring = nullptr;   size_t ring_bytes = 0;    // per tile: [qt][cap]
   uint64_t* d_out = nullptr;    size_t out_bytes = 0;     // [nq][k]
   uint32_t* d_cnt = nullptr;    size_t cnt_bytes = 0;     // [nq] result counts | [nq] raw ring counts
@@ -38,10 +38,7 @@ struct vc_engine {
   uint64_t* d_frows = nullptr;  size_t frows_bytes = 0;
   uint32_t* d_fcnt = nullptr;   size_t fcnt_bytes = 0;
   uint32_t* d_rec = nullptr;                              // scratch of the device-side ring-overflow recovery (zero at first use)
-  // the last kernel of a linear step (vc_recover_kernel) hands the per-step state back zeroed: no memset per step
-  const uint32_t* clean_ptr = nullptr;  size_t clean_words = 0;
-  uint64_t clean_layout = 0;                              // (queries per group, histogram stride) the clean state is laid out for:
-                                                          // the threshold lines are "clean" at ~0, everything else at 0
+  CleanState clean;                                       // the last kernel of a linear step hands d_state back zeroed: no memset per step
   uint32_t scan_event_tick = 0;                           // VC_FLAG_LEAN_TIMING: only every timing_sample-th verify launch is timed
   VcKnobs knobs;                                          // environment knobs, read once at vc_create
   uint32_t recover_sabotage = 0;                          // test knob VC_RECOVER_TEST_FAIL: recover launches still to be made to give up
@@ -97,6 +94,17 @@ static int grow(vc_engine* e, T** p, size_t* have, size_t need) {
   return VC_OK;
 }
 
+// device memory that lives as long as a scope
+template <class T>
+struct ScopedDev {
+  T* p = nullptr;
+  ScopedDev() = default;
+  ScopedDev(const ScopedDev&) = delete;
+  ScopedDev& operator=(const ScopedDev&) = delete;
+  ~ScopedDev() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t bytes) { return hipMalloc((void**)&p, bytes); }
+};
+
 // environment knobs (developer / test switches): read here, once per engine (and once per sharded handle), never on a launch path
 void read_knobs(VcKnobs* k) {
   if (const char* w = getenv("VC_SCAN_WRAP")) k->scan_wrap = (uint32_t)atoi(w);
@@ -138,6 +146,9 @@ void read_knobs(VcKnobs* k) {
 static int bind_device(vc_engine* e) {
   VC_HIP(e, hipSetDevice(e->device));
   return VC_OK;
+}
+static hipStream_t caller_stream(const vc_engine* e, void* stream) {   // NULL = the HIP null stream
+  return stream == VC_STREAM_OWN ? e->own_stream : (hipStream_t)stream;
 }
 
 extern "C" {
@@ -296,7 +307,7 @@ int vc_destroy(vc_engine* e) {
 
 int vc_set_stream(vc_engine* e, void* stream) {
   if (!e) return VC_ERR_INVALID;
-  e->stream = stream == VC_STREAM_OWN ? e->own_stream : (hipStream_t)stream;   // NULL = the HIP null stream
+  e->stream = caller_stream(e, stream);
   return VC_OK;
 }
 
@@ -550,314 +561,326 @@ int vc_get_timing(const vc_engine* ce, vc_timing* t) {
 }
 
 // ---- LINEAR: linear_search.cc:39-64 for a batch of queries ------------------------------------------
-struct LinearBufs {
-  uint32_t hs, QT, GQ, cap;   // histogram stride, queries per tile (one verify launch), per group (one bootstrap), ring entries
-  size_t state_words;
-  uint32_t *d_count, *d_hist, *d_shist, *d_shist2, *d_tau;
+struct LinearSearch;
+struct LinearGroup {       // the queries of one bootstrap / select / recover: [g0, g0 + gq) of the batch
+  uint32_t g0, gq;
+  const uint64_t* dq;
+  uint64_t* rows;          // [gq][k] ascending (INF padded)
+  uint32_t* counts;        // [gq]
+  bool fold;               // the verify prologue cuts the bootstrap histograms itself (no vc_tau_init_kernel)
 };
+struct LinearTile {        // the queries of one verify launch: [t0, t0 + qt) of the group
+  uint32_t t0, qt;
+  const uint64_t* dq;
+  const uint64_t* d_limit;   // nullable: append only packed values <= limit[q] (host-driven recovery)
+  const uint32_t* d_shist;   // set: the kernel's prologue cuts the bootstrap histograms itself
+  uint64_t shist_cstride;
+};
+// runs between the select and the recover launch of a group: its rings and cursors are still intact
+typedef std::function<int(const LinearSearch& ls, const LinearGroup& g)> LinearHook;
 
-// Queries whose bootstrap is done by ONE pair of sampling launches: the tiles of a group share them (the stage
-// kernels read the sampled prefix once per 32 queries instead of once per tile) and one select launch.
-#define VC_GROUP_QUERIES 64u
-#define VC_RESIDENT_MB_DEFAULT 240   // of the 256 MB Infinity Cache (profiles/r02_sweeps.md: 224-256 MB best, 320 MB thrashes)
+// One linear search call: the plan, the carved state and the launch sequence of a group as named steps.
+struct LinearSearch {
+  vc_engine* e;
+  uint32_t k;
+  LinearPlan plan;
+  LinearState st;
 
-// Queries per database pass when the caller left it to the engine (vc_config.query_tile = 0).  A pass over a BIG database is
-// priced by its bytes and 32 queries keep it near the VALU / HBM balance point; a pass over a small one is priced by its
-// launches (~50 us of bootstrap / verify / select / recover whatever it reads), so the tile grows as the database shrinks:
-// 32 from 256 MB on, doubling per halving below, at most 512 -- configs[0] (8 MB, 200 queries per call) runs in ONE pass
-// instead of seven: 0.42 -> 0.92 M queries/s (1.3 M with the lane tile of vc_scan_pick_shape fitted to it as well).
-static uint32_t linear_tile(const vc_engine* e) {
-  if (!e->qtile_auto) return e->qtile;
-  const uint64_t bytes = std::max<uint64_t>(e->n, 1) * (e->bits / 8);
-  uint32_t t = 32;
-  for (uint64_t b = bytes; b < ((uint64_t)256 << 20) && t < 512; b <<= 1) t <<= 1;
-  return t;
-}
+  // tile: 0 = the engine's (vc_config.query_tile / VC_QUERY_TILE, else fitted to the database), or the caller's own
+  LinearSearch(vc_engine* e_, uint32_t nq, uint32_t k_, uint32_t tile = 0)
+      : e(e_), k(k_), plan(plan_in(e_, nq, k_, tile)), st(plan.GQ, plan.hs) {}
 
-static int linear_bufs(vc_engine* e, uint32_t nq, uint32_t k, LinearBufs* b) {
-  b->hs = (e->bits + 1 + 7) & ~7u;
-  b->QT = std::min(linear_tile(e), nq);
-  b->GQ = std::min(nq, std::max(b->QT, VC_GROUP_QUERIES / b->QT * b->QT));   // whole tiles, >= one tile
-  b->cap = std::max(e->cap, 4 * k);
-  // count[GQ] and tau[GQ] hold one 128-byte line per query (VC_QUERY_LINE_WORDS); the histograms are dense
-  const size_t hist_words = (((size_t)b->GQ * (1 + 2 * (size_t)VC_SHIST_COPIES) * b->hs) + 31) & ~(size_t)31;   // keeps tau[] line-aligned
-  b->state_words = (size_t)b->GQ * 2 * VC_QUERY_LINE_WORDS + hist_words;
-  int rc;
-  if ((rc = grow(e, &e->d_state, &e->state_bytes, b->state_words * 4))) return rc;
-  if ((rc = grow(e, &e->d_ring, &e->ring_bytes, (size_t)b->GQ * b->cap * 8))) return rc;
-  if (!e->d_rec && e->knobs.device_recover) {
-    const size_t bytes = vc_recover_scratch_words() * 4;
-    VC_HIP(e, hipMalloc((void**)&e->d_rec, bytes));
-    VC_HIP(e, hipMemsetAsync(e->d_rec, 0, bytes, e->stream));
+  static LinearPlanIn plan_in(const vc_engine* e, uint32_t nq, uint32_t k, uint32_t tile) {
+    LinearPlanIn in{};
+    in.n = e->n; in.bits = e->bits; in.nq = nq; in.k = k; in.ring_cap = e->cap;
+    in.explicit_tile = tile ? tile : (e->qtile_auto ? 0u : e->qtile);
+    in.sample1_set = e->knobs.sample1_set; in.sample1 = e->knobs.sample1;   // dev/test knob VC_SAMPLE1
+    in.sample2_set = e->knobs.sample2_set; in.sample2 = e->knobs.sample2;   // dev/test knob VC_SAMPLE2
+    return in;
   }
-  b->d_count = e->d_state;
-  b->d_hist = b->d_count + (size_t)b->GQ * VC_QUERY_LINE_WORDS;
-  b->d_shist = b->d_hist + (size_t)b->GQ * b->hs;
-  b->d_shist2 = b->d_shist + (size_t)VC_SHIST_COPIES * b->GQ * b->hs;
-  b->d_tau = b->d_hist + hist_words;
-  return VC_OK;
-}
+  uint32_t* state(size_t word_off) const { return e->d_state + word_off; }
 
-// one verify launch for a tile whose tau is already set (the tile's state starts at query t0 of the group); d_limit may be null
-static int scan_tile(vc_engine* e, const LinearBufs& b, const uint64_t* dq, uint32_t qt, uint32_t k, const uint64_t* d_limit,
-                     uint32_t t0 = 0, const uint32_t* d_shist = nullptr, uint64_t shist_cstride = 0) {
-  // (the shape follows a small database only where the TILE does too -- query_tile left to the engine -- and only for tiles
-  // beyond the small-tile form: explicit tiles and <= 8 queries keep the headline's kernel, on any database)
-  const uint64_t shape_n = (e->qtile_auto && qt > 8) ? e->n : 0;
-  const VcScanShape sh = vc_scan_pick_shape(e->W, qt, nullptr, &e->knobs, shape_n);
-  VcScanParams p{};
-  p.cols = e->d_cols;
-  p.stride = e->stride;
-  p.n = e->n;
-  p.nchunks = (e->n + sh.chunk_items() - 1) / sh.chunk_items();
-  p.id_base = e->cfg.id_base;
-  p.qt = qt;
-  p.k = k;
-  p.cap = b.cap;
-  p.hist_stride = b.hs;
-  p.queries = dq;
-  p.qs = VC_QUERY_LINE_WORDS;
-  p.tau = b.d_tau + (size_t)t0 * VC_QUERY_LINE_WORDS;
-  p.count = b.d_count + (size_t)t0 * VC_QUERY_LINE_WORDS;
-  p.hist = b.d_hist + (size_t)t0 * b.hs;
-  p.buf = e->d_ring + (size_t)t0 * b.cap;
-  p.limit = d_limit;
-  p.shist = d_shist;             // set: the kernel's prologue cuts the bootstrap histograms itself (no vc_tau_init_kernel)
-  p.shist_cstride = shist_cstride;
-  p.shist_copies = VC_SHIST_COPIES;
-  p.bits = e->bits;
-  p.wrap = e->knobs.scan_wrap;   // diagnostic build only, results are wrong by design
-  p.diag = e->knobs.scan_diag;
-  {   // Infinity-Cache-resident prefix (see the load in vc_scan_kernel)
-    const uint64_t mb = e->knobs.resident_mb < 0 ? VC_RESIDENT_MB_DEFAULT : (uint64_t)e->knobs.resident_mb;
-    p.resident = (mb << 20) / (sh.chunk_items() * (e->bits / 8));
-  }
-  hipEvent_t a = nullptr, bb = nullptr;
-  // VC_FLAG_LEAN_TIMING with vc_config.timing_sample = N > 1: only every N-th verify launch is bracketed by events
-  // (an event record is a barrier packet, ~4-5 us each; a 125 M-code shard step is 0.35 ms)
-  const uint32_t every = (e->cfg.flags & VC_FLAG_LEAN_TIMING) ? std::max(e->cfg.timing_sample, 1u) : 1u;
-  if (e->scan_event_tick++ % every == 0) ev_pair(e, &a, &bb);
-  if (a) VC_HIP(e, hipEventRecord(a, e->stream));
-  uint64_t* d_trace = nullptr;
-  const uint32_t trace_blocks = 8192;
-  if (e->knobs.scan_trace) {   // dev knob, diagnostic build only: when does every block of the persistent grid start and end
-    VC_HIP(e, hipMalloc((void**)&d_trace, trace_blocks * 16 + 256));   // + the rare-path counters
-    VC_HIP(e, hipMemsetAsync(d_trace, 0, trace_blocks * 16 + 256, e->stream));
-    p.trace = d_trace;
-  }
-  VC_HIP(e, vc_launch_scan(p, e->W, e->n_cu, e->scan_blocks, &e->knobs, e->stream, shape_n));
-  if (d_trace) {
-    std::vector<uint64_t> h(trace_blocks * 2 + 32);
-    VC_HIP(e, hipMemcpyAsync(h.data(), d_trace, trace_blocks * 16 + 256, hipMemcpyDeviceToHost, e->stream));
-    VC_HIP(e, hipStreamSynchronize(e->stream));
-    {
-      const uint32_t* c = (const uint32_t*)(h.data() + trace_blocks * 2);
-      fprintf(stderr, "[scan trace] rare path: %u entries, %u of them appended %u items, %u re-cuts (%u queries)\n", c[0], c[1], c[2], c[3], qt);
-      fprintf(stderr, "[scan trace] appended items by pass of the chunk loop:");
-      for (int i = 0; i < 56; ++i) fprintf(stderr, " %u", c[8 + i]);
-      fprintf(stderr, "\n");
+  int open() {   // the engine's grow-only buffers, sized for the plan
+    int rc;
+    if ((rc = grow(e, &e->d_state, &e->state_bytes, st.state_words * 4))) return rc;
+    if ((rc = grow(e, &e->d_ring, &e->ring_bytes, (size_t)plan.GQ * plan.cap * 8))) return rc;
+    if (!e->d_rec && e->knobs.device_recover) {
+      VC_HIP(e, hipMalloc((void**)&e->d_rec, VcRecoverScratch::words * 4));
+      VC_HIP(e, hipMemsetAsync(e->d_rec, 0, VcRecoverScratch::words * 4, e->stream));
     }
-    (void)hipFree(d_trace);
-    std::vector<double> st, en;
-    uint64_t t0 = UINT64_MAX;
-    for (uint32_t i = 0; i < trace_blocks; ++i)
-      if (h[2 * i] && h[2 * i + 1]) t0 = std::min(t0, h[2 * i]);
-    for (uint32_t i = 0; i < trace_blocks; ++i)
-      if (h[2 * i] && h[2 * i + 1]) { st.push_back((h[2 * i] - t0) * 0.01); en.push_back((h[2 * i + 1] - t0) * 0.01); }   // 100 MHz -> us
-    {   // per XCD (blocks map to XCDs round-robin, blockIdx % 8): when does its last block end, and the mean end of its blocks
-      double mx[8] = {}, sum[8] = {};
-      uint32_t cnt[8] = {};
-      for (uint32_t i = 0; i < trace_blocks; ++i)
-        if (h[2 * i] && h[2 * i + 1] && h[2 * i + 1] - t0 < (1ull << 40)) {
-          const double en_us = (h[2 * i + 1] - t0) * 0.01;
-          mx[i & 7] = std::max(mx[i & 7], en_us); sum[i & 7] += en_us; ++cnt[i & 7];
-        }
-      fprintf(stderr, "[scan trace] per XCD last end / mean end us:");
-      for (int x = 0; x < 8; ++x) fprintf(stderr, " %.0f/%.0f", mx[x], cnt[x] ? sum[x] / cnt[x] : 0.0);
-      fprintf(stderr, "\n");
-    }
-    if (!st.empty()) {
-      std::sort(st.begin(), st.end());
-      std::sort(en.begin(), en.end());
-      auto q = [](const std::vector<double>& v, double f) { return v[(size_t)(f * (v.size() - 1))]; };
-      fprintf(stderr, "[scan trace] %zu blocks, qt %u: start us min/p50/p90/max %.1f %.1f %.1f %.1f | end us min/p10/p50/p90/p99/max %.1f %.1f %.1f %.1f %.1f %.1f\n",
-              st.size(), qt, q(st, 0), q(st, .5), q(st, .9), q(st, 1), q(en, 0), q(en, .1), q(en, .5), q(en, .9), q(en, .99), q(en, 1));
-    }
+    return VC_OK;
   }
-  if (a) {
-    VC_HIP(e, hipEventRecord(bb, e->stream));
-    e->ev_scans.emplace_back(a, bb);
-    e->scan_bytes += e->n * (e->bits / 8);
-  }
-  return VC_OK;
-}
 
-// d_q: [nq][W] words on the device.  Results: d_out [nq][k] ascending (INF padded), d_cnt[0..nq) counts
-// (UINT32_MAX == the ring overflowed, the device-side recovery did not run or gave up, and the row is only an upper bound).
-typedef std::function<int(uint32_t g0, uint32_t gq, const LinearBufs& b)> LinearHook;
-static int linear_batch(vc_engine* e, const uint64_t* d_q, uint32_t nq, uint32_t k, uint64_t* d_out, uint32_t* d_cnt,
-                        const LinearHook* after_select = nullptr) {
-  LinearBufs b;
-  int rc = linear_bufs(e, nq, k, &b);
-  if (rc) return rc;
-  // Threshold bootstrap: exact distance histogram of the first `sample` codes -> tau (k-th best of the sample), so that
-  // the verify kernel's first tiles do not flood the ring / histogram atomics from every wave at once (that flood cost
-  // ~0.4 ms per launch while eight queries shared one line for their ring cursors and one for their thresholds).
-  // Round 1 ran two stages (64 K codes exactly, then 2 M codes counting only distances <= tau1): 4 launches, 26 us.
-  // With one line per query the flood is mild and the threshold of ONE exact stage over 1 M codes starts the verify
-  // kernel just as well -- 2 launches, 15 us; a 125 M-code shard step 0.397 -> 0.384 ms, 1e9 unchanged
-  // (profiles/r02_sweeps.md; below 512 K codes the verify pass pays for the looser threshold, beyond 1 M nothing is
-  // gained -- an exact threshold makes a 1e9 pass no faster).  The refining stage stays selectable (VC_SAMPLE2, tests).
-  uint64_t sample = std::min<uint64_t>(e->n, std::max<uint64_t>(std::max<uint64_t>(262144, 64ull * k), std::min<uint64_t>(e->n / 16, 1048576)));
-  uint64_t sample2 = 0;
-  if (e->knobs.sample2_set) sample2 = std::min<uint64_t>(e->n, e->knobs.sample2);   // dev/test knob VC_SAMPLE2
-  if (e->knobs.sample1_set) sample = std::min<uint64_t>(e->n, e->knobs.sample1);      // dev/test knob VC_SAMPLE1
-  if (sample2 && !e->knobs.sample1_set) sample = std::min<uint64_t>(sample, std::max<uint64_t>(65536, 64ull * k));   // stage 1 only has to seed stage 2
-  for (uint32_t g0 = 0; g0 < nq; g0 += b.GQ) {
-    const uint32_t gq = std::min(b.GQ, nq - g0);
-    const uint64_t* dg = d_q + (size_t)g0 * e->W;
-    // per-step state: zero from the previous step's last kernel, or (first use, new buffer, after an error) memset now
-    const uint64_t layout = ((uint64_t)b.GQ << 32) | b.hs;
-    const bool clean = e->knobs.device_recover && e->clean_ptr == e->d_state && e->clean_words >= b.state_words && e->clean_layout == layout;
-    e->clean_ptr = nullptr;
-    if (!clean) {
-      VC_HIP(e, hipMemsetAsync(e->d_state, 0, e->state_bytes, e->stream));
-      VC_HIP(e, hipMemsetAsync(b.d_tau, 0xFF, (size_t)b.GQ * VC_QUERY_LINE_WORDS * 4, e->stream));   // "no threshold yet"
-    }
+  LinearGroup group(const uint64_t* d_q, uint32_t nq, uint32_t g0, uint64_t* d_out, uint32_t* d_cnt) const {
+    LinearGroup g{g0, std::min(plan.GQ, nq - g0), d_q + (size_t)g0 * e->W, d_out + (size_t)g0 * k, d_cnt + g0, false};
     // small tiles: the verify kernel's prologue turns the sampled histograms into thresholds itself (one launch less and
     // no coherent read of the threshold lines by every block at start)
-    const bool fold = !sample2 && e->knobs.tau_fold && vc_scan_is_small(e->W, std::min(b.QT, gq), &e->knobs) &&
-                      (gq % b.QT == 0 || vc_scan_is_small(e->W, gq % b.QT, &e->knobs));
-    VC_HIP(e, vc_launch_sample_hist(e->d_cols, e->stride, e->W, sample, dg, gq, b.d_shist, b.hs, k, e->bits, b.d_tau, VC_QUERY_LINE_WORDS, false,
-                                    e->n_cu, e->knobs.sample_blocks_per_cu, e->stream, !fold));
-    if (sample2)
-      VC_HIP(e, vc_launch_sample_hist(e->d_cols, e->stride, e->W, sample2, dg, gq, b.d_shist2, b.hs, k, e->bits, b.d_tau, VC_QUERY_LINE_WORDS, true,
-                                      e->n_cu, e->knobs.sample_blocks_per_cu, e->stream));
-    for (uint32_t t0 = 0; t0 < gq; t0 += b.QT)
-      if ((rc = scan_tile(e, b, dg + (size_t)t0 * e->W, std::min(b.QT, gq - t0), k, nullptr, t0,
-                          fold ? b.d_shist + (size_t)t0 * b.hs : nullptr, (uint64_t)gq * b.hs))) return rc;
-    VC_HIP(e, vc_launch_select_ring(e->d_ring, b.cap, b.d_count, b.d_tau, VC_QUERY_LINE_WORDS, gq, k, d_out + (size_t)g0 * k,
-                                    d_cnt + g0, e->stream));
-    // (the exact-MIH switch replays the radius loop's stop rule here: rings and cursors of the group are still intact)
-    if (after_select && (rc = (*after_select)(g0, gq, b))) return rc;
-    // rows whose ring overflowed (count reported as UINT32_MAX) are recomputed exactly on the device: a no-op launch otherwise
-    if (e->knobs.device_recover)
-      for (uint32_t c0 = 0; c0 < gq; c0 += 64)   // one launch serves 64 queries (a group is larger only when one tile is: query_tile > 64)
-        VC_HIP(e, vc_launch_recover(e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->bits, dg + (size_t)c0 * e->W, std::min(64u, gq - c0), k,
-                                    e->d_ring + (size_t)c0 * b.cap, b.cap, b.d_count + (size_t)c0 * VC_QUERY_LINE_WORDS,
-                                    b.d_hist + (size_t)c0 * b.hs, b.hs, VC_QUERY_LINE_WORDS, e->d_rec, d_out + (size_t)(g0 + c0) * k,
-                                    d_cnt + g0 + c0, b.d_tau + (size_t)c0 * VC_QUERY_LINE_WORDS, b.d_shist + (size_t)c0 * b.hs,
-                                    (uint64_t)gq * b.hs, VC_SHIST_COPIES, e->n_cu, e->knobs.recover_spin_limit,
-                                    e->recover_sabotage ? (e->recover_sabotage--, 1u) : 0u, e->stream));
-    // the recover kernel handed the group's state back clean (the 16 partial histograms of a group of gq queries sit
-    // gq * hs words apart, which is what it was told); the refining stage's histograms (dev knob) are not covered
-    if (e->knobs.device_recover && !sample2) {
-      e->clean_ptr = e->d_state;
-      e->clean_words = e->state_bytes / 4;
-      e->clean_layout = layout;
-    }
+    g.fold = !plan.sample2 && e->knobs.tau_fold && vc_scan_is_small(e->W, std::min(plan.QT, g.gq), &e->knobs) &&
+             (g.gq % plan.QT == 0 || vc_scan_is_small(e->W, g.gq % plan.QT, &e->knobs));
+    return g;
   }
+  LinearTile tile(const LinearGroup& g, uint32_t t0) const {
+    return LinearTile{t0, std::min(plan.QT, g.gq - t0), g.dq + (size_t)t0 * e->W, nullptr,
+                      g.fold ? state(st.at(t0).shist) : nullptr, g.fold ? st.shist_copy_stride(g.gq) : 0};
+  }
+
+  // per-step state: zero from the previous step's last kernel, or (first use, new buffer, other layout, after an error) memset now
+  int prepare_state() {
+    const bool clean = e->knobs.device_recover && e->clean.matches(e->d_state, st);
+    e->clean.invalidate();
+    if (clean) return VC_OK;
+    VC_HIP(e, hipMemsetAsync(e->d_state, 0, e->state_bytes, e->stream));
+    VC_HIP(e, hipMemsetAsync(state(st.tau), 0xFF, st.tau_words() * 4, e->stream));   // "no threshold yet"
+    return VC_OK;
+  }
+
+  int bootstrap(const LinearGroup& g) {
+    VcSampleArgs a{};
+    a.cols = e->d_cols; a.stride = e->stride; a.s_items = plan.sample; a.W = e->W; a.bits = e->bits; a.k = k;
+    a.queries = g.dq; a.qt = g.gq; a.shist = state(st.shist); a.hist_stride = st.hs; a.tau = state(st.tau); a.qs = VC_QUERY_LINE_WORDS;
+    a.refine = false; a.cut = !g.fold; a.n_cu = e->n_cu; a.blocks_per_cu = e->knobs.sample_blocks_per_cu;
+    VC_HIP(e, vc_launch_sample_hist(a, e->stream));
+    if (!plan.sample2) return VC_OK;
+    a.s_items = plan.sample2; a.shist = state(st.shist2); a.refine = true; a.cut = true;   // the refining stage
+    VC_HIP(e, vc_launch_sample_hist(a, e->stream));
+    return VC_OK;
+  }
+
+  VcScanParams scan_params(const LinearTile& t, const VcScanShape& sh) const {
+    const LinearState::At at = st.at(t.t0);
+    VcScanParams p{};
+    vc_scan_extent(sh, e->n, e->bits, e->knobs.resident_mb < 0 ? VC_RESIDENT_MB_DEFAULT : (uint64_t)e->knobs.resident_mb, &p);
+    p.cols = e->d_cols; p.stride = e->stride; p.n = e->n; p.id_base = e->cfg.id_base; p.bits = e->bits;
+    p.qt = t.qt; p.k = k; p.cap = plan.cap; p.hist_stride = st.hs;
+    p.queries = t.dq; p.qs = VC_QUERY_LINE_WORDS;
+    p.tau = state(at.tau); p.count = state(at.count); p.hist = state(at.hist);
+    p.buf = e->d_ring + (size_t)t.t0 * plan.cap;
+    p.limit = t.d_limit;
+    p.shist = t.d_shist; p.shist_cstride = t.shist_cstride; p.shist_copies = VC_SHIST_COPIES;
+    p.wrap = e->knobs.scan_wrap;   // diagnostic build only, results are wrong by design
+    p.diag = e->knobs.scan_diag;
+    return p;
+  }
+
+  // Dev knob VC_SCAN_TRACE, diagnostic build only: the launch with a trace buffer attached -- when does every block of the
+  // persistent grid start and end, what did the rare path do -- dumped on stderr.  Synchronises the stream.
+  int dump_scan_trace(VcScanParams p, const VcScanShape& sh) {
+    const uint32_t trace_blocks = 8192;
+    const size_t bytes = trace_blocks * 16 + 256;   // + the rare-path counters
+    ScopedDev<uint64_t> d_trace;
+    VC_HIP(e, d_trace.alloc(bytes));
+    VC_HIP(e, hipMemsetAsync(d_trace.p, 0, bytes, e->stream));
+    p.trace = d_trace.p;
+    VC_HIP(e, vc_launch_scan(p, sh, e->W, e->n_cu, e->scan_blocks, &e->knobs, e->stream));
+    std::vector<uint64_t> h(trace_blocks * 2 + 32);
+    VC_HIP(e, hipMemcpyAsync(h.data(), d_trace.p, bytes, hipMemcpyDeviceToHost, e->stream));
+    VC_HIP(e, hipStreamSynchronize(e->stream));
+    const uint32_t* c = (const uint32_t*)(h.data() + trace_blocks * 2);
+    fprintf(stderr, "[scan trace] rare path: %u entries, %u of them appended %u items, %u re-cuts (%u queries)\n", c[0], c[1], c[2], c[3], p.qt);
+    fprintf(stderr, "[scan trace] appended items by pass of the chunk loop:");
+    for (int i = 0; i < 56; ++i) fprintf(stderr, " %u", c[8 + i]);
+    fprintf(stderr, "\n");
+    std::vector<double> start, end;
+    uint64_t first = UINT64_MAX;
+    for (uint32_t i = 0; i < trace_blocks; ++i)
+      if (h[2 * i] && h[2 * i + 1]) first = std::min(first, h[2 * i]);
+    // per XCD (blocks map to XCDs round-robin, blockIdx % 8): when does its last block end, and the mean end of its blocks
+    double mx[8] = {}, sum[8] = {};
+    uint32_t cnt[8] = {};
+    for (uint32_t i = 0; i < trace_blocks; ++i) {
+      if (!h[2 * i] || !h[2 * i + 1]) continue;
+      const double en_us = (h[2 * i + 1] - first) * 0.01;   // 100 MHz -> us
+      start.push_back((h[2 * i] - first) * 0.01);
+      end.push_back(en_us);
+      if (h[2 * i + 1] - first < (1ull << 40)) { mx[i & 7] = std::max(mx[i & 7], en_us); sum[i & 7] += en_us; ++cnt[i & 7]; }
+    }
+    fprintf(stderr, "[scan trace] per XCD last end / mean end us:");
+    for (int x = 0; x < 8; ++x) fprintf(stderr, " %.0f/%.0f", mx[x], cnt[x] ? sum[x] / cnt[x] : 0.0);
+    fprintf(stderr, "\n");
+    if (start.empty()) return VC_OK;
+    std::sort(start.begin(), start.end());
+    std::sort(end.begin(), end.end());
+    auto q = [](const std::vector<double>& v, double f) { return v[(size_t)(f * (v.size() - 1))]; };
+    fprintf(stderr, "[scan trace] %zu blocks, qt %u: start us min/p50/p90/max %.1f %.1f %.1f %.1f | end us min/p10/p50/p90/p99/max %.1f %.1f %.1f %.1f %.1f %.1f\n",
+            start.size(), p.qt, q(start, 0), q(start, .5), q(start, .9), q(start, 1), q(end, 0), q(end, .1), q(end, .5), q(end, .9), q(end, .99), q(end, 1));
+    return VC_OK;
+  }
+
+  // The verify launch between two events.  VC_FLAG_LEAN_TIMING with vc_config.timing_sample = N > 1: only every N-th verify
+  // launch is bracketed (an event record is a barrier packet, ~4-5 us each; a 125 M-code shard step is 0.35 ms)
+  int timed_scan_launch(const VcScanParams& p, const VcScanShape& sh) {
+    hipEvent_t a = nullptr, b = nullptr;
+    const uint32_t every = (e->cfg.flags & VC_FLAG_LEAN_TIMING) ? std::max(e->cfg.timing_sample, 1u) : 1u;
+    if (e->scan_event_tick++ % every == 0) ev_pair(e, &a, &b);
+    if (a) VC_HIP(e, hipEventRecord(a, e->stream));
+    if (e->knobs.scan_trace) {
+      const int rc = dump_scan_trace(p, sh);
+      if (rc) return rc;
+    } else {
+      VC_HIP(e, vc_launch_scan(p, sh, e->W, e->n_cu, e->scan_blocks, &e->knobs, e->stream));
+    }
+    if (a) {
+      VC_HIP(e, hipEventRecord(b, e->stream));
+      e->ev_scans.emplace_back(a, b);
+      e->scan_bytes += e->n * (e->bits / 8);
+    }
+    return VC_OK;
+  }
+
+  // one verify launch for a tile whose thresholds are set (or cut by the launch itself: LinearTile::d_shist)
+  int verify(const LinearTile& t) {
+    const VcScanShape sh = vc_scan_pick_shape(e->W, t.qt, &e->knobs, plan.shape_n(t.qt));
+    return timed_scan_launch(scan_params(t, sh), sh);
+  }
+
+  // rings -> rows and counts (UINT32_MAX == the ring overflowed: the row is only an upper bound until it is recovered)
+  int select(const LinearGroup& g) {
+    VC_HIP(e, vc_launch_select_ring(e->d_ring, plan.cap, state(st.count), state(st.tau), VC_QUERY_LINE_WORDS, g.gq, k, g.rows, g.counts, e->stream));
+    return VC_OK;
+  }
+
+  // rows whose ring overflowed are recomputed exactly on the device: a no-op launch otherwise.  One launch serves VC_REC_MAXQ
+  // queries (a group is larger only when one tile is: query_tile > 64); as the last kernel of the step it hands the chunk's
+  // state back clean (the 16 partial histograms of a group of gq queries sit gq * hs words apart, which is what it is told)
+  int recover(const LinearGroup& g) {
+    if (!e->knobs.device_recover) return VC_OK;
+    for (uint32_t c0 = 0; c0 < g.gq; c0 += VC_REC_MAXQ) {
+      const LinearState::At at = st.at(c0);
+      VcRecoverArgs a{};
+      a.cols = e->d_cols; a.stride = e->stride; a.n = e->n; a.W = e->W; a.id_base = e->cfg.id_base; a.bits = e->bits;
+      a.queries = g.dq + (size_t)c0 * e->W; a.nq = std::min(VC_REC_MAXQ, g.gq - c0); a.k = k;
+      a.ring = e->d_ring + (size_t)c0 * plan.cap; a.cap = plan.cap;
+      a.count = state(at.count); a.hist = state(at.hist); a.hist_stride = st.hs; a.qs = VC_QUERY_LINE_WORDS;
+      a.scratch = e->d_rec; a.out = g.rows + (size_t)c0 * k; a.out_count = g.counts + c0;
+      a.clean_tau = state(at.tau); a.clean_shist = state(at.shist);
+      a.clean_copy_stride = st.shist_copy_stride(g.gq); a.clean_copies = VC_SHIST_COPIES;
+      a.n_cu = e->n_cu; a.spin_limit = e->knobs.recover_spin_limit;
+      a.absent = e->recover_sabotage ? (e->recover_sabotage--, 1u) : 0u;
+      VC_HIP(e, vc_launch_recover(a, e->stream));
+    }
+    return VC_OK;
+  }
+
+  // the recover kernel handed the group's state back clean; the refining stage's histograms (dev knob) are not covered
+  void hand_back_clean() {
+    if (e->knobs.device_recover && !plan.sample2) e->clean.set(e->d_state, st);
+  }
+
+  // d_q: [nq][W] words on the device.  Results: d_out [nq][k] ascending (INF padded), d_cnt[0..nq) counts
+  // (UINT32_MAX == the ring overflowed, the device-side recovery did not run or gave up, and the row is only an upper bound).
+  int run(const uint64_t* d_q, uint32_t nq, uint64_t* d_out, uint32_t* d_cnt, const LinearHook* after_select = nullptr) {
+    int rc = open();
+    if (rc) return rc;
+    for (uint32_t g0 = 0; g0 < nq; g0 += plan.GQ) {
+      const LinearGroup g = group(d_q, nq, g0, d_out, d_cnt);
+      if ((rc = prepare_state())) return rc;
+      if ((rc = bootstrap(g))) return rc;
+      for (uint32_t t0 = 0; t0 < g.gq; t0 += plan.QT)
+        if ((rc = verify(tile(g, t0)))) return rc;
+      if ((rc = select(g))) return rc;
+      // (the exact-MIH switch replays the radius loop's stop rule here)
+      if (after_select && (rc = (*after_select)(*this, g))) return rc;
+      if ((rc = recover(g))) return rc;
+      hand_back_clean();
+    }
+    return VC_OK;
+  }
+};
+
+// ---- ring-overflow recovery, host-driven (the interval arithmetic: RecoverInterval, vc_linear_plan.hpp) ----------------
+struct RecoverRec {
+  uint32_t q;            // query index in the caller's batch
+  RecoverInterval iv;
+};
+struct RecoverBufs {     // one tile's queries, limits, rows and counts
+  ScopedDev<uint64_t> q, lim, rows;
+  ScopedDev<uint32_t> cnt;
+  int alloc(vc_engine* e, uint32_t QT, uint32_t k) {
+    hipError_t r;
+    if ((r = q.alloc((size_t)QT * e->W * 8)) != hipSuccess || (r = lim.alloc((size_t)QT * 8)) != hipSuccess ||
+        (r = rows.alloc((size_t)QT * k * 8)) != hipSuccess || (r = cnt.alloc((size_t)QT * 4)) != hipSuccess)
+      return fail(e, VC_ERR_HIP, "ring overflow recovery: hipMalloc: %s", hipGetErrorString(r));
+    return VC_OK;
+  }
+};
+struct RecoverRound {    // what one probing scan of a tile brings back
+  std::vector<uint64_t> rows;   // [qt][k] the best of what fitted
+  std::vector<uint32_t> cnt;    // [qt] their counts
+  std::vector<uint32_t> raw;    // [qt] exact number of items <= probe
+};
+
+// one scan of qt queries appending only packed values <= their probes; synchronises the stream
+static int recover_probe(LinearSearch& ls, RecoverBufs& b, const uint64_t* d_q, RecoverRec* recs, uint32_t qt, RecoverRound* r) {
+  vc_engine* e = ls.e;
+  const size_t W = e->W;
+  const uint32_t k = ls.k;
+  std::vector<uint64_t> lim(qt);
+  std::vector<uint32_t> tau(qt);
+  for (uint32_t i = 0; i < qt; ++i) {
+    VC_HIP(e, hipMemcpyAsync(b.q.p + i * W, d_q + (size_t)recs[i].q * W, W * 8, hipMemcpyDeviceToDevice, e->stream));
+    lim[i] = recs[i].iv.next_probe();
+    tau[i] = (uint32_t)(lim[i] >> 32);
+  }
+  VC_HIP(e, hipMemsetAsync(e->d_state, 0, ls.st.state_words * 4, e->stream));
+  VC_HIP(e, hipMemcpyAsync(b.lim.p, lim.data(), qt * 8, hipMemcpyHostToDevice, e->stream));
+  VC_HIP(e, hipMemcpy2DAsync(ls.state(ls.st.tau), VC_QUERY_LINE_WORDS * 4, tau.data(), 4, 4, qt, hipMemcpyHostToDevice, e->stream));
+  const LinearGroup g{0, qt, b.q.p, b.rows.p, b.cnt.p, false};
+  LinearTile t = ls.tile(g, 0);
+  t.d_limit = b.lim.p;
+  int rc;
+  if ((rc = ls.verify(t))) return rc;
+  if ((rc = ls.select(g))) return rc;
+  r->rows.resize((size_t)qt * k);
+  r->cnt.resize(qt);
+  r->raw.resize(qt);
+  VC_HIP(e, hipMemcpyAsync(r->rows.data(), b.rows.p, r->rows.size() * 8, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipMemcpyAsync(r->cnt.data(), b.cnt.p, qt * 4, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipMemcpy2DAsync(r->raw.data(), 4, ls.state(ls.st.count), VC_QUERY_LINE_WORDS * 4, 4, qt, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipStreamSynchronize(e->stream));
   return VC_OK;
 }
 
-// Ring-overflow recovery (host-driven, rare: more than `cap` items at or below the k-th distance).  The truncated
-// ring still yields a valid upper bound on the k-th best packed value (the k-th best of what fitted); the query is
-// scanned again appending only packed values <= a probe, and the append counter tells EXACTLY how many items lie at
-// or below the probe whether they fitted or not.  Per query an interval (lo, hi] is kept with count(<= lo) < k <=
-// count(<= hi):
-//   * probe = hi; the k-th best of what fitted becomes the new hi.  With entries arriving in random order that
-//     quarters the survivors per round (cap >= 4k); but arrival order is NOT random (the same early waves deliver
-//     ids just under the limit round after round: tests/campaign/parity_campaign.py case 259 needed > 64 rounds), so
-//   * whenever a round fails to halve the survivors the next probe bisects (lo, hi] instead: fewer than k items
-//     below it -> lo = probe; otherwise hi = min(probe, k-th best of what fitted).
-// Each bisection halves a 64-bit interval, the other steps never widen it: it ends.
+// Rare: more than `cap` items at or below the k-th distance and no device-side recovery.  Every overflowed query keeps a
+// RecoverInterval and is scanned again, a tile at a time, until its ring holds everything at or below its probe.
 static int linear_recover(vc_engine* e, const uint64_t* d_q, uint32_t k, const std::vector<uint32_t>& over,
                           uint64_t* out /*host [nq][k]*/, uint32_t* cnt /*host [nq]*/) {
-  LinearBufs b;
-  int rc = linear_bufs(e, (uint32_t)over.size(), k, &b);
+  LinearSearch ls(e, (uint32_t)over.size(), k);
+  int rc = ls.open();
   if (rc) return rc;
-  e->clean_ptr = nullptr;   // this path memsets the state itself and leaves it used
-  const size_t W = e->W;
-  uint64_t *d_rq = nullptr, *d_lim = nullptr, *d_rout = nullptr;
-  uint32_t* d_rcnt = nullptr;
-  auto cleanup = [&]() { (void)hipFree(d_rq); (void)hipFree(d_lim); (void)hipFree(d_rout); (void)hipFree(d_rcnt); };
-#define RC(call) do { hipError_t _r = (call); if (_r != hipSuccess) { cleanup(); return fail(e, VC_ERR_HIP, "%s: %s", #call, hipGetErrorString(_r)); } } while (0)
-  RC(hipMalloc((void**)&d_rq, b.QT * W * 8));
-  RC(hipMalloc((void**)&d_lim, b.QT * 8));
-  RC(hipMalloc((void**)&d_rout, (size_t)b.QT * k * 8));
-  RC(hipMalloc((void**)&d_rcnt, b.QT * 4));
-  struct Rec {
-    uint32_t q;          // query index in the caller's batch
-    uint64_t lo, hi;     // count(<= lo) < k (valid only if has_lo), count(<= hi) >= k
-    bool has_lo;
-    uint64_t prev;       // survivors of the previous round (0 = none yet)
-    bool bisect;         // this round's probe is the midpoint, not hi
-    uint64_t probe;
-  };
-  std::vector<Rec> todo;
-  for (uint32_t q : over) todo.push_back(Rec{q, 0, out[(size_t)q * k + k - 1], false, 0, false, 0});
-  const bool trace = e->knobs.recover_trace;   // dev knob VC_RECOVER_TRACE
+  e->clean.invalidate();   // this path memsets the state itself and leaves it used
+  const uint32_t QT = ls.plan.QT;
+  RecoverBufs b;
+  if ((rc = b.alloc(e, QT, k))) return rc;
+  std::vector<RecoverRec> todo;
+  for (uint32_t q : over) todo.push_back(RecoverRec{q, RecoverInterval(out[(size_t)q * k + k - 1])});
+  const uint64_t want = std::min<uint64_t>(k, e->n);
   for (int round = 0; !todo.empty(); ++round) {
-    if (round > 200) { cleanup(); return fail(e, VC_ERR_CAPACITY, "ring overflow recovery did not converge"); }
-    std::vector<Rec> next;
-    for (size_t t0 = 0; t0 < todo.size(); t0 += b.QT) {
-      const uint32_t qt = (uint32_t)std::min<size_t>(b.QT, todo.size() - t0);
-      std::vector<uint64_t> lim(qt);
-      std::vector<uint32_t> tau(qt);
+    if (round > VC_RECOVER_MAX_ROUNDS) return fail(e, VC_ERR_CAPACITY, "ring overflow recovery did not converge");
+    std::vector<RecoverRec> next;
+    for (size_t t0 = 0; t0 < todo.size(); t0 += QT) {
+      const uint32_t qt = (uint32_t)std::min<size_t>(QT, todo.size() - t0);
+      RecoverRound r;
+      if ((rc = recover_probe(ls, b, d_q, &todo[t0], qt, &r))) return rc;
       for (uint32_t i = 0; i < qt; ++i) {
-        Rec& r = todo[t0 + i];
-        RC(hipMemcpyAsync(d_rq + i * W, d_q + (size_t)r.q * W, W * 8, hipMemcpyDeviceToDevice, e->stream));
-        if (!r.bisect) r.probe = r.hi;
-        else if (r.has_lo) r.probe = r.lo + (r.hi - r.lo + 1) / 2;   // rounds up: lo < probe <= hi, so the interval always shrinks
-        else if (r.hi >> 32) r.probe = ((r.hi >> 32) << 32) - 1;   // first: everything strictly nearer than hi's distance
-        else r.probe = r.hi / 2;
-        lim[i] = r.probe;
-        tau[i] = (uint32_t)(lim[i] >> 32);
-      }
-      RC(hipMemsetAsync(e->d_state, 0, b.state_words * 4, e->stream));
-      RC(hipMemcpyAsync(d_lim, lim.data(), qt * 8, hipMemcpyHostToDevice, e->stream));
-      RC(hipMemcpy2DAsync(b.d_tau, VC_QUERY_LINE_WORDS * 4, tau.data(), 4, 4, qt, hipMemcpyHostToDevice, e->stream));
-      if ((rc = scan_tile(e, b, d_rq, qt, k, d_lim))) { cleanup(); return rc; }
-      RC(vc_launch_select_ring(e->d_ring, b.cap, b.d_count, b.d_tau, VC_QUERY_LINE_WORDS, qt, k, d_rout, d_rcnt, e->stream));
-      std::vector<uint64_t> rout((size_t)qt * k);
-      std::vector<uint32_t> rcnt(qt), raw(qt);
-      RC(hipMemcpyAsync(rout.data(), d_rout, rout.size() * 8, hipMemcpyDeviceToHost, e->stream));
-      RC(hipMemcpyAsync(rcnt.data(), d_rcnt, qt * 4, hipMemcpyDeviceToHost, e->stream));
-      RC(hipMemcpy2DAsync(raw.data(), 4, b.d_count, VC_QUERY_LINE_WORDS * 4, 4, qt, hipMemcpyDeviceToHost, e->stream));
-      RC(hipStreamSynchronize(e->stream));
-      for (uint32_t i = 0; i < qt; ++i) {
-        Rec r = todo[t0 + i];
-        const uint64_t c = raw[i];                     // exact number of items <= probe
-        const uint64_t want = std::min<uint64_t>(k, e->n);
-        if (trace && i == 0)
-          fprintf(stderr, "[vc recover] round %d query %u: %s probe %016llx -> %llu items (cap %u)\n", round, r.q,
-                  r.bisect ? "bisect" : "bound ", (unsigned long long)r.probe, (unsigned long long)c, b.cap);
-        if (c < want) {                                // only a bisection probe can undershoot
-          r.lo = r.probe;
-          r.has_lo = true;
-          r.bisect = true;
-          next.push_back(r);
-          continue;
+        RecoverRec rec = todo[t0 + i];
+        if (e->knobs.recover_trace && i == 0)   // dev knob VC_RECOVER_TRACE
+          fprintf(stderr, "[vc recover] round %d query %u: %s probe %016llx -> %llu items (cap %u)\n", round, rec.q,
+                  rec.iv.bisect ? "bisect" : "bound ", (unsigned long long)rec.iv.probe, (unsigned long long)r.raw[i], ls.plan.cap);
+        const RecoverInterval::Outcome o = rec.iv.update(r.raw[i], r.rows[(size_t)i * k + k - 1], ls.plan.cap, want);
+        if (o != RecoverInterval::UNDERSHOOT) {   // a valid row
+          memcpy(out + (size_t)rec.q * k, r.rows.data() + (size_t)i * k, (size_t)k * 8);
+          cnt[rec.q] = r.cnt[i];
         }
-        // a valid row: everything <= probe was counted, the best min(c, cap) >= k of it was stored
-        memcpy(out + (size_t)r.q * k, rout.data() + (size_t)i * k, (size_t)k * 8);
-        cnt[r.q] = rcnt[i];
-        if (c <= b.cap) continue;                      // nothing was dropped: exact, done
-        r.hi = std::min(r.probe, rout[(size_t)i * k + k - 1]);
-        r.bisect = r.prev != 0 && c * 2 > r.prev;      // poor progress since the last valid round -> bisect next
-        r.prev = c;
-        next.push_back(r);
+        if (o != RecoverInterval::DONE) next.push_back(rec);
       }
     }
     todo.swap(next);
   }
-#undef RC
-  cleanup();
   return VC_OK;
 }
 
 // Cost-model switch of the exact MIH k-NN loop (VcMihScanFallback, vc_mih.hpp): the listed queries are answered by the
-// verify kernel in HBM-bound tiles of 8 and the stop rule of search_worker.cc:201-205 is replayed on each tile's
+// verify kernel in tiles of VC_FALLBACK_TILE and the stop rule of search_worker.cc:201-205 is replayed on each tile's
 // candidates (mih_replay_kernel) between the select and the recover launch; with statistics wanted, one more pass over
 // the shard counts the items the radius loop would have verified (minimum substring distance <= radius).
 static int mih_scan_fallback(void* ctx, const uint64_t* d_q, const uint32_t* d_list, uint32_t n, uint32_t k, uint32_t stop_mult,
@@ -869,30 +892,38 @@ static int mih_scan_fallback(void* ctx, const uint64_t* d_q, const uint32_t* d_l
   if ((rc = grow(e, &e->d_fcnt, &e->fcnt_bytes, (size_t)n * 8))) return rc;
   uint32_t* d_flag = e->d_fcnt + n;
   VC_HIP(e, vc_launch_gather_queries(d_q, d_list, n, e->W, e->d_fq, s));
-  const LinearHook hook = [&](uint32_t g0, uint32_t gq, const LinearBufs& b) -> int {
+  const LinearHook replay = [&](const LinearSearch& ls, const LinearGroup& g) -> int {
     VcMihReplayArgs a{};
-    a.lin_ring = e->d_ring; a.lin_count = b.d_count; a.rows = e->d_frows + (size_t)g0 * k; a.rows_cnt = e->d_fcnt + g0;
-    a.queries = e->d_fq + (size_t)g0 * e->W; a.list = d_list + g0; a.cols = e->d_cols; a.stride = e->stride;
-    a.lin_cap = b.cap; a.lin_qs = VC_QUERY_LINE_WORDS; a.gq = gq; a.k = k; a.m = e->m; a.sbits = e->sbits; a.W = e->W;
+    a.lin_ring = e->d_ring; a.lin_count = ls.state(ls.st.count); a.rows = g.rows; a.rows_cnt = g.counts;
+    a.queries = g.dq; a.list = d_list + g.g0; a.cols = e->d_cols; a.stride = e->stride;
+    a.lin_cap = ls.plan.cap; a.lin_qs = VC_QUERY_LINE_WORDS; a.gq = g.gq; a.k = k; a.m = e->m; a.sbits = e->sbits; a.W = e->W;
     a.stop_mult = stop_mult; a.id_base = e->cfg.id_base; a.tgt = tgt; a.unresolved = d_unresolved; a.n_unresolved = d_n_unresolved;
-    a.resolved_flag = d_flag + g0;
+    a.resolved_flag = d_flag + g.g0;
     VC_HIP(e, vc_launch_mih_replay(a, s));
     return VC_OK;
   };
-  const uint32_t saved_tile = e->qtile;
-  const bool saved_auto = e->qtile_auto;
-  // 32 queries per pass: a pass of 8 sits on the HBM roofline, but the switch is asked for QUERIES, and per query the VALU-bound
-  // pass of 32 is the cheaper one (8.2 ms per 32 against 2.5 ms per 8 at 1e9 x 128 bit: 3 900 against 3 200 queries/s)
-  e->qtile = 32;
-  e->qtile_auto = false;
-  rc = linear_batch(e, e->d_fq, n, k, e->d_frows, e->d_fcnt, &hook);
-  e->qtile = saved_tile;
-  e->qtile_auto = saved_auto;
-  if (rc) return rc;
+  if ((rc = LinearSearch(e, n, k, VC_FALLBACK_TILE).run(e->d_fq, n, e->d_frows, e->d_fcnt, &replay))) return rc;
   if (want_stats)
     VC_HIP(e, vc_launch_minsub_count(e->d_cols, e->stride, e->n, e->W, e->m, e->sbits, e->d_fq, d_list, d_flag, n, tgt.radius, tgt.seen, e->n_cu, s));
   return VC_OK;
 }
+
+// Borrows a stream for one search call on device pointers and brackets the call with its timing events; the engine's own stream
+// comes back on every return.
+struct StreamCall {
+  vc_engine* e;
+  hipStream_t saved;
+  StreamCall(vc_engine* e_, hipStream_t s) : e(e_), saved(e_->stream) {
+    e->stream = s;
+    timing_begin(e);
+  }
+  StreamCall(const StreamCall&) = delete;
+  StreamCall& operator=(const StreamCall&) = delete;
+  ~StreamCall() {
+    timing_end(e);
+    e->stream = saved;
+  }
+};
 
 static int check_knn_args(vc_engine* e, const void* q, uint32_t nq, uint32_t k, uint32_t mode) {
   if (!e || !q || nq == 0) return VC_ERR_INVALID;
@@ -939,15 +970,10 @@ int vc_engine_knn_capped(vc_engine* e, const void* d_queries, uint32_t nq, uint3
   if (rc) return rc;
   if (!d_out || !d_counts) return VC_ERR_INVALID;
   if ((rc = bind_device(e))) return rc;
-  hipStream_t saved = e->stream;
-  e->stream = s;
-  timing_begin(e);
+  const StreamCall call(e, s);
   const VcMihScanFallback fb{mih_scan_fallback, e, e->n_cu};
-  rc = vc_mih_search(e->mih, e->d_cols, e->stride, e->n, (const uint64_t*)d_queries, nq, k, false, d_out, d_counts, nullptr, e->stream,
-                     &e->err, &fb, d_stats, r_cap);
-  timing_end(e);
-  e->stream = saved;
-  return rc;
+  return vc_mih_search(e->mih, e->d_cols, e->stride, e->n, (const uint64_t*)d_queries, nq, k, false, d_out, d_counts, nullptr, e->stream,
+                       &e->err, &fb, d_stats, r_cap);
 }
 
 int vc_engine_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t radius, uint32_t mode, uint64_t* d_out, uint64_t out_cap,
@@ -957,15 +983,10 @@ int vc_engine_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint3
   if (mode == VC_MODE_MIH_EXACT && !e->mih) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
   int rc = bind_device(e);
   if (rc) return rc;
-  hipStream_t saved = e->stream;
-  e->stream = s;
-  timing_begin(e);
+  const StreamCall call(e, s);
   *total = 0;
-  rc = vc_radius_search(e->mih, mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs,
-                        (const uint64_t*)d_queries, nq, radius, d_out, out_cap, d_offsets, true, &e->radius_work, e->stream, &e->err, total);
-  timing_end(e);
-  e->stream = saved;
-  return rc;
+  return vc_radius_search(e->mih, mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs,
+                          (const uint64_t*)d_queries, nq, radius, d_out, out_cap, d_offsets, true, &e->radius_work, e->stream, &e->err, total);
 }
 
 extern "C" {
@@ -976,13 +997,11 @@ int vc_search_knn_dev_stats(vc_engine* e, const void* d_queries, uint32_t nq, ui
   if (rc) return rc;
   if (!d_out) return VC_ERR_INVALID;
   if ((rc = bind_device(e))) return rc;
-  hipStream_t saved = e->stream;
-  e->stream = stream == VC_STREAM_OWN ? e->own_stream : (hipStream_t)stream;   // NULL = the HIP null stream
-  if ((rc = grow(e, &e->d_cnt, &e->cnt_bytes, (size_t)nq * 8))) { e->stream = saved; return rc; }
+  if ((rc = grow(e, &e->d_cnt, &e->cnt_bytes, (size_t)nq * 8))) return rc;   // outside the timed bracket; grow() uses no stream
   uint32_t* cnt = d_counts ? d_counts : e->d_cnt;
-  timing_begin(e);
+  const StreamCall call(e, caller_stream(e, stream));
   if (mode == VC_MODE_LINEAR) {
-    rc = linear_batch(e, (const uint64_t*)d_queries, nq, k, d_out, cnt);
+    rc = LinearSearch(e, nq, k).run((const uint64_t*)d_queries, nq, d_out, cnt);
     if (rc == VC_OK && d_stats) {
       hipLaunchKernelGGL(vc_linear_stats_kernel, dim3((nq + 255) / 256), dim3(256), 0, e->stream, (const uint32_t*)cnt, nq, e->n, d_stats);
       if (hipGetLastError() != hipSuccess) rc = fail(e, VC_ERR_HIP, "vc_linear_stats_kernel launch failed");
@@ -992,8 +1011,6 @@ int vc_search_knn_dev_stats(vc_engine* e, const void* d_queries, uint32_t nq, ui
     rc = vc_mih_search(e->mih, e->d_cols, e->stride, e->n, (const uint64_t*)d_queries, nq, k, mode == VC_MODE_MIH_APPROX,
                        d_out, cnt, nullptr, e->stream, &e->err, &fb, d_stats);
   }
-  timing_end(e);
-  e->stream = saved;
   return rc;
 }
 
@@ -1077,7 +1094,7 @@ int vc_search_knn(vc_engine* e, const void* queries, uint32_t nq, uint32_t k, ui
   std::vector<vc_query_stats> st;
   timing_begin(e);
   if (mode == VC_MODE_LINEAR) {
-    rc = linear_batch(e, e->d_q, nq, k, e->d_out, e->d_cnt);
+    rc = LinearSearch(e, nq, k).run(e->d_q, nq, e->d_out, e->d_cnt);
   } else {
     if (stats) st.resize(nq);      // (the statistics cost four read-backs and a wait per launch: only when asked for)
     const VcMihScanFallback fb{mih_scan_fallback, e, e->n_cu};
@@ -1107,7 +1124,7 @@ int vc_search_knn(vc_engine* e, const void* queries, uint32_t nq, uint32_t k, ui
       // the device recovery gave up (or is switched off): its last block restores the barrier words itself, but should
       // that block never have run (the grid was cut short) they would stay dirty for the life of the engine -- the
       // stream is idle here, so the three lines are simply rewritten
-      if (e->d_rec) VC_HIP(e, hipMemsetAsync(e->d_rec + vc_recover_barrier_offset_words(), 0, 96 * 4, e->stream));
+      if (e->d_rec) VC_HIP(e, hipMemsetAsync(e->d_rec + VcRecoverScratch::bar, 0, VcRecoverScratch::bar_words * 4, e->stream));
       if ((rc = linear_recover(e, e->d_q, k, over, out, cnt.data()))) return rc;
     }
   }
@@ -1133,7 +1150,7 @@ int vc_device_status(vc_engine* e, uint32_t* n_gave_up) {
   if (!e->d_rec) return VC_OK;
   int rc = bind_device(e);
   if (rc) return rc;
-  uint32_t* d_flag = e->d_rec + vc_recover_scratch_words() - 32;
+  uint32_t* d_flag = e->d_rec + VcRecoverScratch::gave_up;
   VC_HIP(e, hipMemcpyAsync(n_gave_up, d_flag, 4, hipMemcpyDeviceToHost, e->stream));
   VC_HIP(e, hipMemsetAsync(d_flag, 0, 4, e->stream));
   VC_HIP(e, hipStreamSynchronize(e->stream));
@@ -1227,14 +1244,9 @@ int vc_search_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint3
   if (mode == VC_MODE_MIH_EXACT && !e->mih) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
   int rc = bind_device(e);
   if (rc) return rc;
-  hipStream_t saved = e->stream;
-  e->stream = stream == VC_STREAM_OWN ? e->own_stream : (hipStream_t)stream;
-  timing_begin(e);
-  rc = vc_radius_search(e->mih, mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs,
-                        (const uint64_t*)d_queries, nq, radius, d_out, out_cap, d_offsets, true, &e->radius_work, e->stream, &e->err);
-  timing_end(e);
-  e->stream = saved;
-  return rc;
+  const StreamCall call(e, caller_stream(e, stream));
+  return vc_radius_search(e->mih, mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs,
+                          (const uint64_t*)d_queries, nq, radius, d_out, out_cap, d_offsets, true, &e->radius_work, e->stream, &e->err);
 }
 
 }  // extern "C"

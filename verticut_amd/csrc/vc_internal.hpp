@@ -44,15 +44,29 @@ struct VcKnobs {
 void read_knobs(VcKnobs* k);   // vc_engine.hip: the one place that reads the environment (once per engine / sharded handle)
 
 // ---- vc_scan.hip ------------------------------------------------------------------------------
-// Scan-kernel shape chosen per call: BLK threads, U column loads per thread per chunk.
+// Scan-kernel shape chosen per launch: BLK threads, U column loads per thread per chunk.
 struct VcScanShape {
   int blk;      // 256 or 512
   int unroll;   // U
   int dbuf;     // register buffers per lane: 1 (rely on other waves), 2 (prefetch next chunk), 3 (two chunks ahead)
   int small;    // tiles of <= 8 queries use the compile-time-unrolled form of the kernel
+  size_t lds;   // bytes of LDS the general form stages its query tile in
   uint64_t chunk_items() const { return 2ull * blk * unroll; }
 };
-VcScanShape vc_scan_pick_shape(uint32_t W, uint32_t qt, size_t* lds_bytes, const VcKnobs* knobs, uint64_t n_items = 0);
+// 16 B loads in flight per thread per buffer = U*W; keep the two register buffers <= 64 VGPRs each.
+constexpr int vc_scan_default_unroll(int W) { return W <= 2 ? 4 : (W <= 4 ? 2 : 1); }
+// The small-tile rule: a tile of qt queries in this shape runs the compile-time-unrolled form of the verify kernel.
+inline bool vc_scan_shape_is_small(const VcScanShape& sh, uint32_t W, uint32_t qt) {
+  return sh.small && sh.blk == 256 && sh.dbuf == 2 && qt <= 8 && sh.unroll == vc_scan_default_unroll((int)W);
+}
+// n_items: 0, or the database size when the caller wants the tile shape fitted to a small database
+VcScanShape vc_scan_pick_shape(uint32_t W, uint32_t qt, const VcKnobs* knobs, uint64_t n_items = 0);
+// What a pass over n codes is in a shape: its chunks, and how many of them (a prefix of resident_mb megabytes) stay in the
+// Infinity Cache (see the load in vc_scan_kernel).  The shape handed to vc_launch_scan is the one this was derived from.
+inline void vc_scan_extent(const VcScanShape& sh, uint64_t n, uint32_t bits, uint64_t resident_mb, VcScanParams* p) {
+  p->nchunks = (n + sh.chunk_items() - 1) / sh.chunk_items();
+  p->resident = (resident_mb << 20) / (sh.chunk_items() * (bits / 8));
+}
 
 float vc_probe_stream_ms(const uint64_t* cols, uint64_t stride, uint32_t W, uint64_t items, uint64_t* d_sink, uint32_t n_cu,
                          hipStream_t s);
@@ -64,17 +78,27 @@ hipError_t vc_launch_rows_to_cols(const uint64_t* rows, uint64_t* cols, uint64_t
 hipError_t vc_launch_gather_rows(const uint64_t* cols, uint64_t stride, uint32_t W, const uint32_t* d_local_ids,
                                  uint32_t n_ids, uint64_t* d_rows, hipStream_t s);
 // One stage of the threshold bootstrap (two launches): histogram of the first s_items codes (refine: only
-// distances <= tau[q]), then tau[q] = k-th smallest sampled distance.  d_shist [qt][hist_stride] must be zero.
-hipError_t vc_launch_sample_hist(const uint64_t* cols, uint64_t stride, uint32_t W, uint64_t s_items,
-                                 const uint64_t* d_queries, uint32_t qt, uint32_t* d_shist, uint32_t hist_stride,
-                                 uint32_t k, uint32_t bits, uint32_t* d_tau, uint32_t qs, bool refine, uint32_t n_cu,
-                                 uint32_t blocks_per_cu, hipStream_t s, bool cut = true);
-bool vc_scan_is_small(uint32_t W, uint32_t qt, const VcKnobs* knobs, uint64_t n_items = 0);
-// grid = min(chunks, CUs x resident blocks per CU, want_blocks if non-zero)
-// shape_n: 0, or the database size when the caller wants the tile shape fitted to a small database (vc_scan_pick_shape; the
-// caller's nchunks must come from the same shape)
-hipError_t vc_launch_scan(const VcScanParams& p, uint32_t W, uint32_t n_cu, uint32_t want_blocks, const VcKnobs* knobs,
-                          hipStream_t s, uint64_t shape_n = 0);
+// distances <= tau[q]), then tau[q] = k-th smallest sampled distance.  shist [qt][hist_stride] must be zero.
+struct VcSampleArgs {
+  const uint64_t* cols;
+  uint64_t stride, s_items;
+  uint32_t W, bits, k;
+  const uint64_t* queries;
+  uint32_t qt;
+  uint32_t* shist;
+  uint32_t hist_stride;
+  uint32_t* tau;
+  uint32_t qs;              // words between consecutive queries' entries of tau[]
+  bool refine;
+  bool cut;                 // false: no vc_tau_init_kernel launch, the consumer cuts the histograms itself
+  uint32_t n_cu, blocks_per_cu;
+};
+hipError_t vc_launch_sample_hist(const VcSampleArgs& a, hipStream_t s);
+// true when a tile of qt queries runs the small-tile form of the verify kernel (which can cut the bootstrap histograms itself)
+bool vc_scan_is_small(uint32_t W, uint32_t qt, const VcKnobs* knobs);
+// grid = min(chunks, CUs x resident blocks per CU, want_blocks if non-zero); sh: the shape p.nchunks was derived from
+hipError_t vc_launch_scan(const VcScanParams& p, const VcScanShape& sh, uint32_t W, uint32_t n_cu, uint32_t want_blocks,
+                          const VcKnobs* knobs, hipStream_t s);
 // ring -> sorted top-k (per query); out padded with VC_PACK_INF
 // d_tau (nullable): final per-query distance thresholds of the scan -- farther entries are dropped before sorting
 hipError_t vc_launch_select_ring(const uint64_t* d_buf, uint32_t cap, const uint32_t* d_count, const uint32_t* d_tau, uint32_t qs,
@@ -83,19 +107,32 @@ hipError_t vc_launch_select_ring(const uint64_t* d_buf, uint32_t cap, const uint
 hipError_t vc_launch_select_ring_list(const uint64_t* d_buf, uint32_t cap, const uint32_t* d_count, const uint32_t* d_list,
                                       uint32_t n_list, uint32_t k, uint64_t* d_out, uint32_t* d_out_count, hipStream_t s);
 // Exact device-side recovery of the rows whose ring overflowed (count > cap), after vc_launch_select_ring on the same
-// buffers: no-op launch when nothing overflowed.  d_scratch: vc_recover_scratch_words() words, zero at first use
-// (the kernel restores its barrier words itself).  nq <= 64.  clean_copies > 0: as the last kernel of the step it also
-// zeroes the step's state for these queries (ring cursors d_count, thresholds d_clean_tau, d_hist, and clean_copies
-// partial histograms d_clean_shist + c * clean_copy_stride), so that the next step needs no memset.
-size_t vc_recover_scratch_words();
-hipError_t vc_launch_recover(const uint64_t* cols, uint64_t stride, uint64_t n, uint32_t W, uint32_t id_base, uint32_t bits,
-                             const uint64_t* d_queries, uint32_t nq, uint32_t k, uint64_t* d_ring, uint32_t cap,
-                             const uint32_t* d_count, const uint32_t* d_hist, uint32_t hist_stride, uint32_t qs, uint32_t* d_scratch,
-                             uint64_t* d_out, uint32_t* d_out_count, uint32_t* d_clean_tau, uint32_t* d_clean_shist,
-                             uint64_t clean_copy_stride, uint32_t clean_copies, uint32_t n_cu, uint32_t spin_limit, uint32_t absent,
-                             hipStream_t s);
-// offset (words) of the three barrier lines (followed by the give-up counter line) inside the recovery scratch
-size_t vc_recover_barrier_offset_words();
+// buffers: no-op launch when nothing overflowed.  scratch: VcRecoverScratch::words words, zero at first use
+// (the kernel restores its barrier words itself).  nq <= VC_REC_MAXQ.  clean_copies > 0: as the last kernel of the step it also
+// zeroes the step's state for these queries (ring cursors count, thresholds clean_tau, hist, and clean_copies
+// partial histograms clean_shist + c * clean_copy_stride), so that the next step needs no memset.
+struct VcRecoverArgs {
+  const uint64_t* cols;
+  uint64_t stride, n;
+  uint32_t W, id_base, bits;
+  const uint64_t* queries;
+  uint32_t nq, k;
+  uint64_t* ring;
+  uint32_t cap;
+  const uint32_t* count;
+  const uint32_t* hist;
+  uint32_t hist_stride, qs;
+  uint32_t* scratch;
+  uint64_t* out;
+  uint32_t* out_count;
+  uint32_t* clean_tau;
+  uint32_t* clean_shist;
+  uint64_t clean_copy_stride;
+  uint32_t clean_copies;
+  uint32_t n_cu, spin_limit;
+  uint32_t absent;          // test knob: blocks the barrier waits for in vain
+};
+hipError_t vc_launch_recover(const VcRecoverArgs& a, hipStream_t s);
 // ---- vc_sort.hip: the index builder's primitives (hand-written; no device library is linked) --------------------
 // exclusive prefix sum of L uint32 (in place allowed); d_work: vc_scan_work_words(L) words
 size_t vc_scan_work_words(uint64_t L);

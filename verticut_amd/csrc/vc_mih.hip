@@ -3893,14 +3893,14 @@ struct RadiusSearch {
     MIH_CHECK(hipMemsetAsync(wk->d_aux, 0, RadiusAux::scan_words(tq, hs) * 4, s));
     hipLaunchKernelGGL(vc_fill_u32_kernel, dim3((qt + 255) / 256), dim3(256), 0, s, aux.tau, qt, radius);
     MIH_CHECK(hipGetLastError());
-    size_t lds;
-    const VcScanShape sh = vc_scan_pick_shape(W, qt, &lds, knobs);
+    const VcScanShape sh = vc_scan_pick_shape(W, qt, knobs);
     VcScanParams p{};
-    p.cols = d_cols; p.stride = stride; p.n = n; p.nchunks = (n + sh.chunk_items() - 1) / sh.chunk_items();
+    vc_scan_extent(sh, n, 64 * W, 0, &p);   // (no Infinity-Cache-resident prefix on this route)
+    p.cols = d_cols; p.stride = stride; p.n = n;
     p.id_base = id_base; p.qt = qt; p.k = 0xFFFFFFFFu;   // never re-derive tau: it is the fixed radius
     p.cap = cap; p.hist_stride = hs; p.queries = d_q + (size_t)q0 * W; p.tau = aux.tau; p.count = aux.count; p.qs = 1;
     p.hist = aux.hist; p.buf = wk->d_ring;
-    MIH_CHECK(vc_launch_scan(p, W, n_cu, 0, knobs, s));
+    MIH_CHECK(vc_launch_scan(p, sh, W, n_cu, 0, knobs, s));
     return VC_OK;
   }
 

@@ -14,6 +14,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "vc_internal.hpp"
 
 // Build with -DVC_SCAN_DIAGNOSTICS=1 (VC_BUILD_DIAG=1 python -m verticut_amd.build) to enable the VC_SCAN_WRAP /
@@ -903,8 +905,7 @@ __global__ void __launch_bounds__(VC_SEL_THREADS) vc_select_kernel(Src src, uint
 // `gave_up` counter reports it (vc_device_status).
 // ------------------------------------------------------------------------------------------
 #define VC_REC_RQ 4u            // overflowed queries recovered per round of passes (they share the two full sweeps)
-#define VC_REC_BINS 2048u
-#define VC_REC_MAXQ 64u         // = VC_GROUP_QUERIES: queries one select / recover launch serves
+// (VC_REC_BINS, VC_REC_MAXQ and the scratch layout: vc_linear_plan.hpp)
 #define VC_REC_SPIN_LIMIT (3u << 20)   // x s_sleep 32 (~0.9 us): ~3 s
 
 struct VcRecoverParams {
@@ -1217,8 +1218,8 @@ uint32_t resident_grid(K kernel, int blk, size_t lds, uint32_t n_cu, uint32_t wa
 }
 
 template <int W>
-hipError_t launch_scan_w(const VcScanParams& p, const VcScanShape& sh, size_t lds, uint32_t n_cu, uint32_t want, bool shape_trace,
-                         hipStream_t s) {
+hipError_t launch_scan_w(const VcScanParams& p, const VcScanShape& sh, uint32_t n_cu, uint32_t want, bool shape_trace, hipStream_t s) {
+  const size_t lds = sh.lds;
   // dev knob VC_SCAN_SHAPE_TRACE: one line per launch naming the instantiation that was launched (not the one asked for)
 #define VC_SHAPE_TRACE(U_, B_, NB_, QT_)                                                                    \
   if (shape_trace)                                                                                          \
@@ -1234,20 +1235,18 @@ hipError_t launch_scan_w(const VcScanParams& p, const VcScanShape& sh, size_t ld
     return hipGetLastError();                                                                               \
   }
   // small tiles (<= 8 queries; the diagnostic knobs keep the general form): compile-time query loop, one kernel per count
-  if (sh.small && sh.blk == 256 && sh.dbuf == 2 && p.qt <= 8 && !(VC_SCAN_DIAGNOSTICS && (p.wrap || p.diag))) {
-    constexpr int UD = W <= 2 ? 4 : (W <= 4 ? 2 : 1);
+  if (vc_scan_shape_is_small(sh, W, p.qt) && !(VC_SCAN_DIAGNOSTICS && (p.wrap || p.diag))) {
+    constexpr int UD = vc_scan_default_unroll(W);
     constexpr int MW = W <= 2 ? VC_SCAN_SMALL_WAVES : 0;
-    if (sh.unroll == UD && sh.dbuf == 2) {
-      switch (p.qt) {
-        case 1: VC_LAUNCH_QT(2, UD, 1, MW)
-        case 2: VC_LAUNCH_QT(2, UD, 2, MW)
-        case 3: VC_LAUNCH_QT(2, UD, 3, MW)
-        case 4: VC_LAUNCH_QT(2, UD, 4, MW)
-        case 5: VC_LAUNCH_QT(2, UD, 5, MW)
-        case 6: VC_LAUNCH_QT(2, UD, 6, MW)
-        case 7: VC_LAUNCH_QT(2, UD, 7, MW)
-        default: VC_LAUNCH_QT(2, UD, 8, MW)
-      }
+    switch (p.qt) {
+      case 1: VC_LAUNCH_QT(2, UD, 1, MW)
+      case 2: VC_LAUNCH_QT(2, UD, 2, MW)
+      case 3: VC_LAUNCH_QT(2, UD, 3, MW)
+      case 4: VC_LAUNCH_QT(2, UD, 4, MW)
+      case 5: VC_LAUNCH_QT(2, UD, 5, MW)
+      case 6: VC_LAUNCH_QT(2, UD, 6, MW)
+      case 7: VC_LAUNCH_QT(2, UD, 7, MW)
+      default: VC_LAUNCH_QT(2, UD, 8, MW)
     }
   }
 #undef VC_LAUNCH_QT
@@ -1281,19 +1280,29 @@ hipError_t launch_scan_w(const VcScanParams& p, const VcScanShape& sh, size_t ld
   return hipErrorInvalidValue;
 }
 
+// the launchers' dispatch on the code width: f(std::integral_constant<int, W>) for W words per code
+template <class F>
+hipError_t dispatch_w(uint32_t W, F&& f) {
+  switch (W) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+  }
+  return hipErrorInvalidValue;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------
-VcScanShape vc_scan_pick_shape(uint32_t W, uint32_t qt, size_t* lds_bytes, const VcKnobs* knobs, uint64_t n_items) {
-  const size_t lds = (size_t)qt * (W * 8 + 4);
-  if (lds_bytes) *lds_bytes = lds;
+VcScanShape vc_scan_pick_shape(uint32_t W, uint32_t qt, const VcKnobs* knobs, uint64_t n_items) {
   VcScanShape sh;
-  // 16 B loads in flight per thread per buffer = U*W; keep the two register buffers <= 64 VGPRs each.
-  sh.unroll = W <= 2 ? 4 : (W <= 4 ? 2 : 1);
+  sh.lds = (size_t)qt * (W * 8 + 4);
+  sh.unroll = vc_scan_default_unroll((int)W);
   // big LDS tiles leave room for one block per CU only: use 512 threads to keep 2 waves per SIMD.
-  sh.blk = lds > 40 * 1024 ? 512 : 256;
+  sh.blk = sh.lds > 40 * 1024 ? 512 : 256;
   sh.dbuf = 2;
   sh.small = knobs ? knobs->scan_small : 1;
   // A small database (n_items given): fewer items per lane, so that its chunks reach every wave of the grid -- 2^20 codes in
@@ -1319,7 +1328,7 @@ float vc_probe_stream_ms(const uint64_t* cols, uint64_t stride, uint32_t W, uint
   float best = -1.f;
   for (int rep = 0; rep < 4 && nchunks; ++rep) {
     (void)hipEventRecord(a, s);
-    switch (W) {
+    switch (W) {   // (not dispatch_w: a single column has no stride to choose, so there is no probe kernel for W = 1)
       case 2: hipLaunchKernelGGL((vc_stream_probe_kernel<2>), dim3(n_cu * 4), dim3(256), 0, s, cols, stride, nchunks, d_sink); break;
       case 4: hipLaunchKernelGGL((vc_stream_probe_kernel<4>), dim3(n_cu * 4), dim3(256), 0, s, cols, stride, nchunks, d_sink); break;
       case 8: hipLaunchKernelGGL((vc_stream_probe_kernel<8>), dim3(n_cu * 4), dim3(256), 0, s, cols, stride, nchunks, d_sink); break;
@@ -1361,61 +1370,36 @@ hipError_t vc_launch_gather_rows(const uint64_t* cols, uint64_t stride, uint32_t
   return hipGetLastError();
 }
 
-hipError_t vc_launch_sample_hist(const uint64_t* cols, uint64_t stride, uint32_t W, uint64_t s_items,
-                                 const uint64_t* d_queries, uint32_t qt, uint32_t* d_shist, uint32_t hist_stride,
-                                 uint32_t k, uint32_t bits, uint32_t* d_tau, uint32_t qs, bool refine, uint32_t n_cu,
-                                 uint32_t blocks_per_cu, hipStream_t s, bool cut) {
-  if (qt == 0) return hipSuccess;
-  if (s_items == 0) {
-    if (!cut) return hipSuccess;   // the consumer cuts the (all-zero) histogram itself   // nothing to sample: the cut of the (zero) histogram = "accept everything"
-    hipLaunchKernelGGL(vc_tau_init_kernel, dim3(qt), dim3(64), 0, s, d_shist, hist_stride, k, bits, d_tau, refine ? 1u : 0u, qs);
+hipError_t vc_launch_sample_hist(const VcSampleArgs& a, hipStream_t s) {
+  if (a.qt == 0) return hipSuccess;
+  const auto cut = [&]() {
+    hipLaunchKernelGGL(vc_tau_init_kernel, dim3(a.qt), dim3(64), 0, s, a.shist, a.hist_stride, a.k, a.bits, a.tau, a.refine ? 1u : 0u, a.qs);
     return hipGetLastError();
-  }
-  const uint32_t gy = (qt + VC_SAMPLE_QSUB - 1) / VC_SAMPLE_QSUB;
-  const uint64_t npairs = std::max<uint64_t>((s_items + 1) / 2, 1);
-  const uint64_t per_cu = blocks_per_cu ? blocks_per_cu : 8;
-  const uint32_t gx = (uint32_t)std::min<uint64_t>((npairs + 255) / 256, (uint64_t)n_cu * per_cu);
-  const size_t lds = (size_t)VC_SAMPLE_QSUB * W * 8 + (size_t)VC_SAMPLE_QSUB * hist_stride * 4 + VC_SAMPLE_QSUB * 4;
-  VcSampleParams p{cols, stride, s_items, d_queries, d_shist, d_tau, qt, hist_stride, refine ? 1u : 0u, qs};
-#define VC_SH_CASE(W_)                                                                                   \
-  case W_:                                                                                               \
-    hipLaunchKernelGGL((vc_sample_hist_kernel<W_>), dim3(gx, gy), dim3(256), lds, s, p);                  \
-    break;
-  switch (W) {
-    VC_SH_CASE(1)
-    VC_SH_CASE(2)
-    VC_SH_CASE(4)
-    VC_SH_CASE(8)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef VC_SH_CASE
-  hipError_t r = hipGetLastError();
-  if (r != hipSuccess || !cut) return r;
-  hipLaunchKernelGGL(vc_tau_init_kernel, dim3(qt), dim3(64), 0, s, d_shist, hist_stride, k, bits, d_tau, refine ? 1u : 0u, qs);
-  return hipGetLastError();
+  };
+  // nothing to sample: the cut of the (zero) histogram = "accept everything" -- by the consumer itself where it cuts
+  if (a.s_items == 0) return a.cut ? cut() : hipSuccess;
+  const uint32_t gy = (a.qt + VC_SAMPLE_QSUB - 1) / VC_SAMPLE_QSUB;
+  const uint64_t npairs = std::max<uint64_t>((a.s_items + 1) / 2, 1);
+  const uint64_t per_cu = a.blocks_per_cu ? a.blocks_per_cu : 8;
+  const uint32_t gx = (uint32_t)std::min<uint64_t>((npairs + 255) / 256, (uint64_t)a.n_cu * per_cu);
+  const size_t lds = (size_t)VC_SAMPLE_QSUB * a.W * 8 + (size_t)VC_SAMPLE_QSUB * a.hist_stride * 4 + VC_SAMPLE_QSUB * 4;
+  const VcSampleParams p{a.cols, a.stride, a.s_items, a.queries, a.shist, a.tau, a.qt, a.hist_stride, a.refine ? 1u : 0u, a.qs};
+  const hipError_t r = dispatch_w(a.W, [&](auto w) {
+    hipLaunchKernelGGL((vc_sample_hist_kernel<decltype(w)::value>), dim3(gx, gy), dim3(256), lds, s, p);
+    return hipGetLastError();
+  });
+  return (r != hipSuccess || !a.cut) ? r : cut();
 }
 
-// true when a tile of qt queries runs the small-tile form of the verify kernel (which can cut the bootstrap histograms itself)
-bool vc_scan_is_small(uint32_t W, uint32_t qt, const VcKnobs* knobs, uint64_t n_items) {
-  const VcScanShape sh = vc_scan_pick_shape(W, qt, nullptr, knobs, n_items);
-  const int ud = W <= 2 ? 4 : (W <= 4 ? 2 : 1);
-  return sh.small && sh.blk == 256 && sh.dbuf == 2 && qt <= 8 && sh.unroll == ud && !VC_SCAN_DIAGNOSTICS;
+bool vc_scan_is_small(uint32_t W, uint32_t qt, const VcKnobs* knobs) {
+  return vc_scan_shape_is_small(vc_scan_pick_shape(W, qt, knobs), W, qt) && !VC_SCAN_DIAGNOSTICS;
 }
 
-hipError_t vc_launch_scan(const VcScanParams& p, uint32_t W, uint32_t n_cu, uint32_t want_blocks, const VcKnobs* knobs,
-                          hipStream_t s, uint64_t shape_n) {
+hipError_t vc_launch_scan(const VcScanParams& p, const VcScanShape& sh, uint32_t W, uint32_t n_cu, uint32_t want_blocks,
+                          const VcKnobs* knobs, hipStream_t s) {
   if (p.nchunks == 0 || p.qt == 0) return hipSuccess;
-  size_t lds;
-  const VcScanShape sh = vc_scan_pick_shape(W, p.qt, &lds, knobs, shape_n);
   const bool tr = knobs && knobs->scan_shape_trace;
-  switch (W) {
-    case 1: return launch_scan_w<1>(p, sh, lds, n_cu, want_blocks, tr, s);
-    case 2: return launch_scan_w<2>(p, sh, lds, n_cu, want_blocks, tr, s);
-    case 4: return launch_scan_w<4>(p, sh, lds, n_cu, want_blocks, tr, s);
-    case 8: return launch_scan_w<8>(p, sh, lds, n_cu, want_blocks, tr, s);
-  }
-  return hipErrorInvalidValue;
+  return dispatch_w(W, [&](auto w) { return launch_scan_w<decltype(w)::value>(p, sh, n_cu, want_blocks, tr, s); });
 }
 
 hipError_t vc_launch_select_ring(const uint64_t* d_buf, uint32_t cap, const uint32_t* d_count, const uint32_t* d_tau,
@@ -1434,51 +1418,30 @@ hipError_t vc_launch_select_ring_list(const uint64_t* d_buf, uint32_t cap, const
   return hipGetLastError();
 }
 
-size_t vc_recover_barrier_offset_words() { return (size_t)VC_REC_MAXQ * 3 * VC_REC_BINS + (size_t)VC_REC_MAXQ * 32; }
-size_t vc_recover_scratch_words() {   // idhist | rcount lines | barrier lines (3 x 32 words) | gave_up
-  return (size_t)VC_REC_MAXQ * 3 * VC_REC_BINS + (size_t)VC_REC_MAXQ * 32 + 96 + 32;
-}
-
-hipError_t vc_launch_recover(const uint64_t* cols, uint64_t stride, uint64_t n, uint32_t W, uint32_t id_base, uint32_t bits,
-                             const uint64_t* d_queries, uint32_t nq, uint32_t k, uint64_t* d_ring, uint32_t cap,
-                             const uint32_t* d_count, const uint32_t* d_hist, uint32_t hist_stride, uint32_t qs, uint32_t* d_scratch,
-                             uint64_t* d_out, uint32_t* d_out_count, uint32_t* d_clean_tau, uint32_t* d_clean_shist,
-                             uint64_t clean_copy_stride, uint32_t clean_copies, uint32_t n_cu, uint32_t spin_limit, uint32_t absent,
-                             hipStream_t s) {
-  if (nq == 0) return hipSuccess;
-  if (nq > VC_REC_MAXQ) return hipErrorInvalidValue;
+hipError_t vc_launch_recover(const VcRecoverArgs& a, hipStream_t s) {
+  if (a.nq == 0) return hipSuccess;
+  if (a.nq > VC_REC_MAXQ) return hipErrorInvalidValue;
   VcRecoverParams p{};
-  p.cols = cols; p.stride = stride; p.n = n; p.queries = d_queries; p.count = d_count; p.hist = d_hist; p.ring = d_ring;
-  p.idhist = d_scratch;
-  p.rcount = d_scratch + (size_t)VC_REC_MAXQ * 3 * VC_REC_BINS;
-  p.bar = p.rcount + (size_t)VC_REC_MAXQ * 32;
-  p.gave_up = p.bar + 96;
-  p.out = d_out; p.out_count = d_out_count;
-  p.nq = nq; p.k = k; p.cap = cap; p.hist_stride = hist_stride; p.qs = qs; p.bits = bits; p.id_base = id_base;
-  p.clean_tau = d_clean_tau; p.clean_shist = d_clean_shist; p.clean_copy_stride = clean_copy_stride; p.clean_copies = clean_copies;
-  p.spin_limit = spin_limit ? spin_limit : VC_REC_SPIN_LIMIT; p.absent = absent;
+  p.cols = a.cols; p.stride = a.stride; p.n = a.n; p.queries = a.queries; p.count = a.count; p.hist = a.hist; p.ring = a.ring;
+  p.idhist = a.scratch + VcRecoverScratch::idhist;
+  p.rcount = a.scratch + VcRecoverScratch::rcount;
+  p.bar = a.scratch + VcRecoverScratch::bar;
+  p.gave_up = a.scratch + VcRecoverScratch::gave_up;
+  p.out = a.out; p.out_count = a.out_count;
+  p.nq = a.nq; p.k = a.k; p.cap = a.cap; p.hist_stride = a.hist_stride; p.qs = a.qs; p.bits = a.bits; p.id_base = a.id_base;
+  p.clean_tau = a.clean_tau; p.clean_shist = a.clean_shist; p.clean_copy_stride = a.clean_copy_stride; p.clean_copies = a.clean_copies;
+  p.spin_limit = a.spin_limit ? a.spin_limit : VC_REC_SPIN_LIMIT; p.absent = a.absent;
   // block-local position histograms (32 KiB), reused as the sort buffer of the final rows (k entries, padded to a power
   // of two); kept small so that the grids of several engines fit on the chip side by side
   uint32_t kp = 2;
-  while (kp < k) kp <<= 1;
+  while (kp < a.k) kp <<= 1;
   const size_t lds = std::max((size_t)VC_REC_RQ * VC_REC_BINS * 4, (size_t)kp * 8);
-#define VC_REC_CASE(W_)                                                                                              \
-  case W_: {                                                                                                         \
-    auto kern = vc_recover_kernel<W_>;                                                                               \
-    const uint32_t grid = std::min(2 * n_cu, resident_grid(kern, 256, lds, n_cu, 0));                                \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, p);                                                       \
-    break;                                                                                                           \
-  }
-  switch (W) {
-    VC_REC_CASE(1)
-    VC_REC_CASE(2)
-    VC_REC_CASE(4)
-    VC_REC_CASE(8)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef VC_REC_CASE
-  return hipGetLastError();
+  return dispatch_w(a.W, [&](auto w) {
+    auto kern = vc_recover_kernel<decltype(w)::value>;
+    const uint32_t grid = std::min(2 * a.n_cu, resident_grid(kern, 256, lds, a.n_cu, 0));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, p);
+    return hipGetLastError();
+  });
 }
 
 // Merge of G ascending, INF-padded lists of k packed values per query (the per-shard top-k: mpi_coordinator::gather_vectors'
