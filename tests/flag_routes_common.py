@@ -46,11 +46,13 @@ ROUTES = {
     "group2": {"VC_MIH_GROUP": "2"},
     "group3": {"VC_MIH_GROUP": "3"},
     "lines1": {"VC_MIH_LINES": "1"},              # directory lines of the 32-bit tables
+    "bent0": {"VC_MIH_BENT": "0"},                # 32-bit substrings of <= 128-bit codes verify through the id gather
+    "bent0_lines1": {"VC_MIH_BENT": "0", "VC_MIH_LINES": "1"},
 }
 ALL_SHAPES = ("default", "host_loop", "budget1", "bcodes0", "switch2")
 ROUTES_OF = {
-    "A": ALL_SHAPES + ("group1", "group2", "group3", "lines1"),
-    "B": ALL_SHAPES + ("group1", "group2", "group3", "lines1"),
+    "A": ALL_SHAPES + ("group1", "group2", "group3", "lines1", "bent0", "bent0_lines1"),
+    "B": ALL_SHAPES + ("group1", "group2", "group3", "lines1", "bent0", "bent0_lines1"),
     "C": ALL_SHAPES,
     "D": ALL_SHAPES,
     "E": ("default", "host_loop"),

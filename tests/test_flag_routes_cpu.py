@@ -18,13 +18,13 @@ RADIUS, N_RESULTS, N_SUB, N_LOCAL, N_CAND = range(5)
 
 
 def test_every_cell_of_the_tables_is_a_case():
-    """5 shapes x their flag sets x their routes = 68 cells (A 1 x 9, B 3 x 9, C 4 x 5, D 2 x 5, E 1 x 2), each once, and the
+    """5 shapes x their flag sets x their routes = 76 cells (A 1 x 11, B 3 x 11, C 4 x 5, D 2 x 5, E 1 x 2), each once, and the
     flag values are the ABI's"""
     from verticut_amd import engine
     assert (F.BITMAP, F.SIGNEXT, F.LITERAL4) == (engine.FLAG_USE_BITMAP, engine.FLAG_REF_SIGNEXT_KEYS, engine.FLAG_REF_STOP_LITERAL4)
     cases = F.cases()
     ids = [F.case_id(c) for c in cases]
-    assert len(cases) == 68 and len(set(ids)) == 68
+    assert len(cases) == 76 and len(set(ids)) == 76
     for sid in F.SHAPES:
         for fl in F.FLAG_SETS[sid]:
             for knob in ("default", "host_loop", "budget1", "bcodes0", "switch2") if sid != "E" else ("default", "host_loop"):
@@ -32,10 +32,17 @@ def test_every_cell_of_the_tables_is_a_case():
             assert F.switch_forbidden(sid, fl)                         # every listed set keeps the scan switch off
     for sid in "AB":
         for fl in F.FLAG_SETS[sid]:
-            for knob in ("group1", "group2", "group3", "lines1"):
+            for knob in ("group1", "group2", "group3", "lines1", "bent0", "bent0_lines1"):
                 assert (sid, fl, knob) in cases
-    assert all(set(F.ROUTES[r]) <= {"VC_MIH_HOST_LOOP", "VC_MIH_BUDGET", "VC_MIH_BCODES", "VC_MIH_SWITCH", "VC_MIH_GROUP", "VC_MIH_LINES"}
-               for r in F.ROUTES)
+    assert all(set(F.ROUTES[r]) <= {"VC_MIH_HOST_LOOP", "VC_MIH_BUDGET", "VC_MIH_BCODES", "VC_MIH_SWITCH", "VC_MIH_GROUP", "VC_MIH_LINES",
+                                    "VC_MIH_BENT"} for r in F.ROUTES)
+    # the {id, code} records exist at 32-bit substrings of <= 128-bit codes only: the routes without them are listed for A and B alone
+    assert F.ROUTES["bent0"] == {"VC_MIH_BENT": "0"} and F.ROUTES["bent0_lines1"] == {"VC_MIH_BENT": "0", "VC_MIH_LINES": "1"}
+    assert {sid for sid, _, r in cases if r in ("bent0", "bent0_lines1")} == {"A", "B"}
+    for sid in "AB":
+        assert F.SHAPES[sid].bits // F.SHAPES[sid].m == 32 and F.SHAPES[sid].bits <= 128
+    for sid in "CDE":
+        assert "bent0" not in F.ROUTES_OF[sid] and "bent0_lines1" not in F.ROUTES_OF[sid]
     # a flag is listed only where it bites: signext below 32-bit substrings, literal4 below 4 tables
     for sid, sets in F.FLAG_SETS.items():
         sh = F.SHAPES[sid]

@@ -1,7 +1,7 @@
 """The reference-fidelity flags on every MIH execution route.  VC_FLAG_USE_BITMAP, VC_FLAG_REF_SIGNEXT_KEYS and
 VC_FLAG_REF_STOP_LITERAL4 are read in the multi-block probe kernel, in the query kernel's owner rule, granule scan and
 direct-key scan, in both statistics exports, in the planner's scan-switch decision and in the sharded statistics reduction;
-the routes (VC_MIH_HOST_LOOP, VC_MIH_BUDGET, VC_MIH_BCODES, VC_MIH_SWITCH, VC_MIH_GROUP, VC_MIH_LINES) decide which of these
+the routes (VC_MIH_HOST_LOOP, VC_MIH_BUDGET, VC_MIH_BCODES, VC_MIH_SWITCH, VC_MIH_GROUP, VC_MIH_LINES, VC_MIH_BENT) decide which of these
 places a query passes.  Every (shape, flag set, route) cell of flag_routes_common.py builds one engine and serves 16 queries in
 exact and approximate mode, through the host-pointer and the device-resident call; every query is compared with
 MihOracle.find (SearchWorker::find, search_worker.cc:159-264) -- never with another GPU route.  test_flag_routes_cpu.py pins on
@@ -111,13 +111,17 @@ def test_forced_switch_takes_these_queries_when_no_flag_forbids_it(vc, oracle, m
     _check(got, cnt, _host_stats(st), F.expect(oracle, sid, ""), (sid, "switch2 without flags"))
 
 
-@pytest.mark.parametrize("sid,fl,shards", F.SHARDED, ids=["-".join((s, f, "%dshards" % g)) for s, f, g in F.SHARDED])
-def test_flag_set_over_shards(vc, oracle, sid, fl, shards):
+@pytest.mark.parametrize("sid,fl,shards,route", [pytest.param(s, f, g, "default", id="-".join((s, f, "%dshards" % g))) for s, f, g in F.SHARDED]
+                         + [pytest.param("B", "literal4+bitmap", 4, "bent0", id="B-literal4+bitmap-4shards-bent0")])
+def test_flag_set_over_shards(vc, oracle, monkeypatch, sid, fl, shards, route):
     """Each shard stops by its own rule, so the expectation is one MihOracle per shard's id range: rows = the k smallest of
     the shards' rows, radius = the maximum, n_sub_reads / n_local_reads / n_candidates = the sums (vc_sharded_stats_kernel),
-    through the host-pointer and the device-resident call."""
+    through the host-pointer and the device-resident call.  The bent0 case: every shard without its {id, code} records."""
     import torch
     sh = F.SHAPES[sid]
+    assert (sid, fl, shards) in F.SHARDED
+    for name, value in F.ROUTES[route].items():                   # the knobs are read when the store is created
+        monkeypatch.setenv(name, value)
     q = F.make_queries(oracle, sid)
     with vc.ShardedEngine(sh.bits, capacity=sh.n, n_shards=shards, n_tables=sh.m, devices=[0], flags=F.flag_bits(fl)) as s:
         s.add_codes(F.make_codes(oracle, sid))

@@ -360,6 +360,14 @@ def test_generators_reach_their_limits(oracle):
 
 
 # ------------------------------------------------------------------ GPU helpers
+# The 128-bit / 4-table cases below drain their entries either from the {id, code} records (VcTableView::bent, what an index of
+# this size gets: VC_MIH_BENT "1") or through the id gather of vc_load_entry (what it gets when memory is short: "0").  The limits,
+# the expectations and the device counters do not depend on the layout; the cases that had no such parameter keep their ids.
+def _with_bent(cases):
+    """[(values, id)] -> every case under VC_MIH_BENT "1" (id kept) and "0" (id + "-bent0")"""
+    return ([pytest.param(*v, "1", id=i) for v, i in cases] + [pytest.param(*v, "0", id=i + "-bent0") for v, i in cases])
+
+
 def _engine(vc, codes, bits, m, **kw):
     e = vc.Engine(bits, capacity=codes.shape[0], n_tables=m, **kw)
     e.add_codes(codes)
@@ -396,10 +404,11 @@ def _knn_checked(vc, oracle, e, mo, codes, q, k):
 
 # ------------------------------------------------------------------ GPU: hit list
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_ball", RADIUS32_BALLS)
-def test_hit_list_radius_granule_scan(vc, oracle, n_ball):
+@pytest.mark.parametrize("n_ball,bent", _with_bent([((n,), str(n)) for n in RADIUS32_BALLS]))
+def test_hit_list_radius_granule_scan(vc, oracle, monkeypatch, n_ball, bent):
     """32-bit granule scan of the radius search: the first pass of table 0 holds n_ball hits (MQ_HMAX - 1 .. > 2 MQ_HMAX)"""
     L = limits()
+    monkeypatch.setenv("VC_MIH_BENT", bent)
     codes, q, R = radius_ball32(L, n_ball, 1)
     K, qk = keys_of(codes, 4), keys_of(q[None], 4)[0]
     rsub, n_big, small = radius_plan(128, 4, R)
@@ -431,9 +440,8 @@ def test_hit_list_radius_direct_keys(vc, oracle, n_low, n_s3):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("lines", ["0", "1"])
-@pytest.mark.parametrize("n_ball", KNN32_BALLS)
-def test_hit_list_knn_grouping(vc, oracle, monkeypatch, n_ball, lines):
+@pytest.mark.parametrize("n_ball,lines,bent", _with_bent([((n, ln), "%d-%s" % (n, ln)) for ln in ("0", "1") for n in KNN32_BALLS]))
+def test_hit_list_knn_grouping(vc, oracle, monkeypatch, n_ball, lines, bent):
     """exact k-NN over the 2-ball: VC_MIH_GROUP = 3 puts all n_ball hits in one pass, 1 and 2 put n_ball - 132 in the
     shell-2 pass.  The three give identical rows and statistics, equal to MihOracle's."""
     L = limits()
@@ -442,6 +450,7 @@ def test_hit_list_knn_grouping(vc, oracle, monkeypatch, n_ball, lines):
     K, qk = keys_of(codes, 4), keys_of(q[None], 4)[0]
     mo = oracle.MihOracle(codes, 4, key_mode=1)
     monkeypatch.setenv("VC_MIH_LINES", lines)
+    monkeypatch.setenv("VC_MIH_BENT", bent)
     res = []
     for group in (1, 2, 3):
         monkeypatch.setenv("VC_MIH_GROUP", str(group))
@@ -458,12 +467,13 @@ def test_hit_list_knn_grouping(vc, oracle, monkeypatch, n_ball, lines):
 
 # ------------------------------------------------------------------ GPU: drain bitmap and candidate buffer
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", DRAIN_ENTRIES)
-def test_drain_entry_bitmap(vc, oracle, monkeypatch, n):
+@pytest.mark.parametrize("n,bent", _with_bent([((n,), str(n)) for n in DRAIN_ENTRIES]))
+def test_drain_entry_bitmap(vc, oracle, monkeypatch, n, bent):
     """a k-NN drain of n entries: <= MQ_BMW * 32 map entries to buckets through the LDS bitmap, more by binary search.
     VC_MIH_GROUP=1: shell 0 alone in the first pass (a grouped pass would add the 3 n shell-1 entries of tables 1..3).
     No counter says which mapping ran; the entry count does."""
     monkeypatch.setenv("VC_MIH_GROUP", "1")
+    monkeypatch.setenv("VC_MIH_BENT", bent)
     k = 10
     codes, q = heavy_bucket32(n, 4)
     mo = oracle.MihOracle(codes, 4, key_mode=1)
@@ -476,14 +486,14 @@ def test_drain_entry_bitmap(vc, oracle, monkeypatch, n):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("step", [2048, 4096, 8192])
-@pytest.mark.parametrize("past", [0, 1])
-def test_candidate_buffer_steps(vc, oracle, monkeypatch, step, past):
+@pytest.mark.parametrize("step,past,bent", _with_bent([((st, pa), "%d-%d" % (pa, st)) for st in (2048, 4096, 8192) for pa in (0, 1)]))
+def test_candidate_buffer_steps(vc, oracle, monkeypatch, step, past, bent):
     """k at and one past each buf_entries step.  The shell-0 bucket yields 20 000 survivors under an open threshold, more
     than any buffer: mq_compact runs (and keeps everything: no threshold yet), then mq_select_exact.  The device has no
     counter for either; the witness is the data (survivors > buf_entries) and the in-kernel route (mih_launches)."""
     L = limits()
     monkeypatch.setenv("VC_MIH_GROUP", "2")                           # shells 0 and 1 share the first pass: two classes
+    monkeypatch.setenv("VC_MIH_BENT", bent)
     k = (step - L["MQ_ROUND"]) // L["MQ_MAX_GROUP"] + past
     buf = buf_entries(L, k)
     assert buf == step * (2 if past else 1) and 20000 > buf

@@ -45,9 +45,14 @@ def _assert_same(vc, s, one, q, k):
     return got, cnt, st
 
 
-@pytest.mark.parametrize("shards", [1, 3, 8])
-@pytest.mark.parametrize("bits,m", [(128, 4), (64, 2), (256, 8), (64, 4)])
-def test_equal_to_one_engine_over_the_union(vc, oracle, bits, m, shards):
+# one more 128-bit / 4-table case without the {id, code} records (VC_MIH_BENT=0: every shard and the single engine verify through
+# the id gather, as an index does when memory is short); the cases that had no such parameter keep their ids
+@pytest.mark.parametrize("bits,m,shards,bent", [pytest.param(b, m, g, None, id="%d-%d-%d" % (b, m, g)) for g in (1, 3, 8)
+                                                for b, m in ((128, 4), (64, 2), (256, 8), (64, 4))]
+                         + [pytest.param(128, 4, 3, "0", id="128-4-3-bent0")])
+def test_equal_to_one_engine_over_the_union(vc, oracle, monkeypatch, bits, m, shards, bent):
+    if bent is not None:
+        monkeypatch.setenv("VC_MIH_BENT", bent)                         # read when an engine or a sharded store is created
     n, id_base = 20_000, 1234
     rng = np.random.default_rng(bits * 10 + m + shards)
     codes = oracle.gen_codes(n, bits, 7, kind=1, n_centres=60, max_flips=bits // 16)

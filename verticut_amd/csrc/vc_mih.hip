@@ -32,6 +32,7 @@
 
 #include "vc_internal.hpp"
 #include "vc_mih.hpp"
+#include "vc_mih_policy.hpp"
 
 #define MIH_BLK 256
 #define MIH_PPT 4                       // probes per thread
@@ -2586,40 +2587,12 @@ void vc_mih_free(VcMihIndex* ix) {
   delete ix;
 }
 
-// directory lines (VcTableView::lines): 2 GB per 32-bit table, built while that is a small part of what is still free once the
-// records of the index itself (ids, offsets, bitmaps, directories, {id, code} records) have their room (VC_MIH_LINES=0/1 overrides)
-#define MIH_NLINES (1u << 25)
-static bool want_dir_lines(uint32_t sbits, uint32_t m, uint64_t n, uint32_t W, bool want_bent, const VcKnobs& knobs) {
-  if (sbits != 32 || n == 0) return false;
-  if (knobs.mih_lines >= 0) return knobs.mih_lines != 0;
-  // Where most 256-key blocks hold single-entry buckets only (93 % at 1e8 codes) the block directory answers a hit in one round
-  // trip too and the lines gain nothing (r04, same box: 13.7 vs 13.6 M queries/s at 1e8, 9.96 -> 10.25 M at 1e9): build them from
-  // the size on where a block's buckets are rarely all single (n / 2^32 = 0.07: a third of the blocks)
-  if (n < 300000000ull) return false;
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
-  const size_t index_bytes = (size_t)m * (n * 8 + (1ull << 29) + (3ull << 26)) + (want_bent ? (size_t)m * n * 16 * W : 0);
-  return free_b > index_bytes && (size_t)m * MIH_NLINES * 64 <= (free_b - index_bytes) / 4;
-}
-
-// which optional per-table structures an index gets: one decision for a build and a load
-struct MihMemPolicy {
-  bool bcodes, bent, lines;
-};
+// which optional per-table structures an index gets: one decision for a build and a load.  The rule is vc_mih_policy
+// (vc_mih_policy.hpp); here it is given what the device has free at this moment
 static MihMemPolicy mem_policy(uint32_t sbits, uint32_t m, uint64_t n, uint32_t W, const VcKnobs& knobs) {
-  // bucket-order code copies for the tables whose buckets are big (see VcTableView::bcodes): m more copies of the
-  // codes, so only while they fit comfortably (dev knob VC_MIH_BCODES=0/1 overrides)
-  bool want_bcodes = sbits <= 16;
-  bool want_bent = sbits == 32 && W <= 2;   // (VcTableView::bent; VC_MIH_BENT=0/1 overrides)
   size_t free_b = 0, total_b = 0;
-  if ((want_bcodes || want_bent) && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-    if ((size_t)m * n * W * 8 > free_b / 3) want_bcodes = false;
-    // (55 % of the free memory: 128 GB of records at 1e9 x 128 bit next to 50 GB of codes + index on a 288 GB part)
-    if ((size_t)m * n * 16 * W > free_b / 100 * 55) want_bent = false;
-  }
-  if (knobs.mih_bcodes >= 0) want_bcodes = knobs.mih_bcodes != 0;   // dev knob VC_MIH_BCODES
-  if (knobs.mih_bent >= 0) want_bent = knobs.mih_bent != 0 && sbits == 32 && W <= 2;
-  return {want_bcodes, want_bent, want_dir_lines(sbits, m, n, W, want_bent, knobs)};
+  const bool have_free = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+  return vc_mih_policy(sbits, m, n, W, have_free, free_b, MihPolicyKnobs{knobs.mih_bcodes, knobs.mih_bent, knobs.mih_lines});
 }
 
 // device memory owned by `owner` (an index's allocs, or a DevScratch)
@@ -2689,11 +2662,18 @@ static int build_derived(VcMihIndex* ix, VcTableView& tv, const MihMemPolicy& po
   return VC_OK;
 }
 
-// the tables' views go to the device, and the index to the caller
-static int publish_index(MihIndexPtr ix, VcMihIndex** out, hipStream_t s, std::string* err) {
+// the tables' views go to the device, and the index to the caller.  VC_MIH_TRACE: one line on what the index holds (`how` =
+// "built" / "loaded"), read off the published views -- a structure counts when every table has it -- and not off the policy
+static int publish_index(MihIndexPtr ix, VcMihIndex** out, const char* how, hipStream_t s, std::string* err) {
   MIH_CHECK(hipMalloc((void**)&ix->d_tables, sizeof(VcTableView) * ix->m));
   MIH_CHECK(hipMemcpyAsync(ix->d_tables, ix->h_tables.data(), sizeof(VcTableView) * ix->m, hipMemcpyHostToDevice, s));
   MIH_CHECK(hipStreamSynchronize(s));
+  if (ix->knobs.mih_trace) {
+    bool bcodes = ix->m != 0, bent = ix->m != 0, lines = ix->m != 0;
+    for (const VcTableView& tv : ix->h_tables) { bcodes &= tv.bcodes != nullptr; bent &= tv.bent != nullptr; lines &= tv.lines != nullptr; }
+    fprintf(stderr, "[vc_mih] index %s: n=%llu sbits=%u m=%u W=%u bcodes=%d bent=%d lines=%d\n", how, (unsigned long long)ix->n, ix->sbits,
+            ix->m, ix->W, (int)bcodes, (int)bent, (int)lines);
+  }
   *out = ix.release();
   return VC_OK;
 }
@@ -2780,7 +2760,7 @@ int vc_mih_build(VcMihIndex** out, const uint64_t* d_cols, uint64_t stride, uint
     if ((rc = build_derived(ix.get(), tv, pol, d_cols, stride, s, err))) return rc;
     ix->h_tables[t] = tv;
   }
-  return publish_index(std::move(ix), out, s, err);
+  return publish_index(std::move(ix), out, "built", s, err);
 }
 
 // ---- BaseProxy-style views (tests / adapters; not on the search path) --------------------------------
@@ -3047,7 +3027,7 @@ int vc_mih_load(VcMihIndex** out, const char* path, const uint64_t* d_cols, uint
     if ((rc = build_derived(ix.get(), tv, pol, d_cols, stride, s, err))) return rc;
     ix->h_tables[t] = tv;
   }
-  return publish_index(std::move(ix), out, s, err);
+  return publish_index(std::move(ix), out, "loaded", s, err);
 }
 
 // ---- search -------------------------------------------------------------------------------------------
