@@ -63,9 +63,21 @@ extern "C" {
 #define VC_FLAG_GLOBAL_STOP 0x10u      /* sharded store (vc_sharded_config.engine.flags), VC_MODE_MIH_EXACT: the stop rule is decided on
                                           the MERGED rows, as the reference's master does (search_worker.cc:179-207), so rows, counts
                                           and statistics are those of one vc_engine holding the union.  A plain vc_engine ignores it
-                                          (its stop is global already); other modes are unchanged.  Refused (VC_ERR_INVALID) with
+                                          (its stop is global already).  Refused (VC_ERR_INVALID) with
                                           n_tables == 0, VC_FLAG_USE_BITMAP, VC_FLAG_REF_SIGNEXT_KEYS, or VC_FLAG_REF_STOP_LITERAL4
                                           with n_tables < 4. */
+#define VC_FLAG_GLOBAL_APPROX 0x20u    /* sharded store (vc_sharded_config.engine.flags), VC_MODE_MIH_APPROX: the loop stops where ONE
+                                          engine over the union stops, as the reference's master does when it fills one heap of
+                                          knn * APPROXIMATE_FACTOR distinct candidates from all ranks and broadcasts is_stop
+                                          (search_worker.cc:104-139): after the first shell r* in which the distinct candidates of ALL
+                                          shards together, shells 0..r*, reach 20 k -- else after the last shell.  Rows are the k
+                                          smallest (dist, id) among the union's items whose minimum substring distance is <= r*,
+                                          radius = r*, n_sub_reads = table 0's gets of shells 0..r*, n_candidates = the shards'
+                                          distinct counts summed (the shards are id-disjoint): what one vc_engine holding the union
+                                          returns.  Independent of VC_FLAG_GLOBAL_STOP (either or both may be set); MIH_EXACT, LINEAR
+                                          and the radius searches do not look at it.  A plain vc_engine ignores it.  Refused
+                                          (VC_ERR_INVALID) with n_tables == 0 or VC_FLAG_USE_BITMAP (the gets issued then depend on the
+                                          union's bitmap); VC_FLAG_REF_SIGNEXT_KEYS and VC_FLAG_REF_STOP_LITERAL4 are allowed. */
 
 /* ---- synthetic data kinds for vc_add_synthetic (the reference ships no data: .gitignore:7-8) */
 #define VC_SYNTH_UNIFORM 0
@@ -264,7 +276,11 @@ int vc_merge_topk_dev(const uint64_t* d_lists, uint32_t n_lists, uint32_t nq, ui
  * VC_FLAG_GLOBAL_STOP in engine.flags, VC_MODE_MIH_EXACT instead stops where ONE engine over the union stops: the shards run
  * in capped rounds (shells 0..t, own stop rule active), a kernel on the root judges the merged rows (pigeonhole check +
  * the union's stop rule) and only undecided queries run again; queries beyond the shards' in-block shells are answered by
- * a scan of the union with the stop rule replayed.  Rows, counts and all statistics then equal one vc_engine's. */
+ * a scan of the union with the stop rule replayed.  Rows, counts and all statistics then equal one vc_engine's.  With
+ * VC_FLAG_GLOBAL_APPROX, VC_MODE_MIH_APPROX does the same for the approximate rule (search_worker.cc:104-139): rounds capped at
+ * shell t = 0, 1, 2, ... over the open queries, a kernel on the root adds the shards' distinct candidate counts and settles
+ * a query in the first round whose sum reaches 20 k (or at the last shell).  As in every MIH mode the host waits inside the
+ * call; results are valid in stream order. */
 #define VC_MAX_SHARDS 16
 #define VC_EXCHANGE_AUTO 0
 #define VC_EXCHANGE_PEER_COPY 1

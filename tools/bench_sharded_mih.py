@@ -30,8 +30,8 @@ def near_queries(e, n, nq, bits, max_flips, rng):
     return q
 
 
-def captured_stderr(fn):
-    """run fn() with stderr captured; returns the sharded global stop's trace lines"""
+def captured_stderr(fn, prefix="[vc_gs]"):
+    """run fn() with stderr captured; returns the trace lines that start with `prefix` (default: the sharded global stop's)"""
     sys.stderr.flush()
     saved = os.dup(2)
     with tempfile.TemporaryFile(mode="w+") as f:
@@ -42,7 +42,7 @@ def captured_stderr(fn):
             os.dup2(saved, 2)
             os.close(saved)
         f.seek(0)
-        return [ln.strip() for ln in f if ln.startswith("[vc_gs]")]
+        return [ln.strip() for ln in f if ln.startswith(prefix)]
 
 
 def main():

@@ -964,16 +964,17 @@ int vc_engine_view(vc_engine* e, VcEngineView* v) {
   return VC_OK;
 }
 
-int vc_engine_knn_capped(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t r_cap, uint64_t* d_out, uint32_t* d_counts,
-                         vc_query_stats* d_stats, hipStream_t s) {
-  int rc = check_knn_args(e, d_queries, nq, k, VC_MODE_MIH_EXACT);
+int vc_engine_knn_capped(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t r_cap, uint64_t* d_out,
+                         uint32_t* d_counts, vc_query_stats* d_stats, hipStream_t s) {
+  if (mode != VC_MODE_MIH_EXACT && mode != VC_MODE_MIH_APPROX) return VC_ERR_INVALID;
+  int rc = check_knn_args(e, d_queries, nq, k, mode);
   if (rc) return rc;
   if (!d_out || !d_counts) return VC_ERR_INVALID;
   if ((rc = bind_device(e))) return rc;
   const StreamCall call(e, s);
   const VcMihScanFallback fb{mih_scan_fallback, e, e->n_cu};
-  return vc_mih_search(e->mih, e->d_cols, e->stride, e->n, (const uint64_t*)d_queries, nq, k, false, d_out, d_counts, nullptr, e->stream,
-                       &e->err, &fb, d_stats, r_cap);
+  return vc_mih_search(e->mih, e->d_cols, e->stride, e->n, (const uint64_t*)d_queries, nq, k, mode == VC_MODE_MIH_APPROX, d_out, d_counts, nullptr,
+                       e->stream, &e->err, &fb, d_stats, r_cap);
 }
 
 int vc_engine_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t radius, uint32_t mode, uint64_t* d_out, uint64_t out_cap,

@@ -153,9 +153,11 @@ struct VcEngineView {
   uint32_t W, m, sbits, id_base, n_cu, reach;   // reach: vc_mih_knn_reach of the index (0 without one)
 };
 int vc_engine_view(vc_engine* e, VcEngineView* v);
-// exact MIH k-NN capped at shell r_cap (vc_mih_search's r_cap) on stream s; d_stats as vc_search_knn_dev_stats
-int vc_engine_knn_capped(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t r_cap, uint64_t* d_out, uint32_t* d_counts,
-                         vc_query_stats* d_stats, hipStream_t s);
+// MIH k-NN (mode: VC_MODE_MIH_EXACT or VC_MODE_MIH_APPROX) capped at shell r_cap (vc_mih_search's r_cap) on stream s: shells 0..r_cap
+// with the mode's own stop rule active; a query still open at r_cap ends with radius = r_cap and the k best of what it has seen.
+// d_stats as vc_search_knn_dev_stats
+int vc_engine_knn_capped(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t r_cap, uint64_t* d_out,
+                         uint32_t* d_counts, vc_query_stats* d_stats, hipStream_t s);
 // vc_search_radius_dev on stream s with the shard's total returned to the host: *total = entries found, also when they exceed
 // out_cap (VC_ERR_CAPACITY: the caller grows its buffer to *total and repeats, no read-back of the offsets)
 int vc_engine_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t radius, uint32_t mode, uint64_t* d_out, uint64_t out_cap,

@@ -47,7 +47,6 @@
 #define MIH_QTILE_MAX 16384u
 #define MIH_QTILE_LIMIT 65536u           // VC_MIH_QTILE is clamped to MIH_QTILE_MIN .. this
 #define MIH_RADIUS_TILE 4096u            // queries per tile of the radius search (vc_radius_offsets_kernel: four per thread)
-#define MIH_APPROX_FACTOR 20u           // search_worker.h:14
 
 struct VcTableView {
   const uint32_t* offsets;

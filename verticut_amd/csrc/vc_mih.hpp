@@ -72,9 +72,10 @@ hipError_t vc_launch_tie_collect(const uint64_t* cols, uint64_t stride, uint64_t
                                  const uint64_t* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_dist, const uint32_t* d_radius,
                                  const uint32_t* d_need, uint32_t* d_chunk_scratch, uint32_t* d_ids, uint32_t* d_cnt, hipStream_t s);
 
+#define MIH_APPROX_FACTOR 20u   // search_worker.h:14: the approximate loop stops at k * 20 distinct candidates (vc_mih.hip, vc_sharded.hip)
 // d_q [nq][W]; d_out [nq][k] ascending INF-padded; d_cnt [nq]; stats (host, may be null) filled after a sync.
 // d_stats (device, may be null): the same records written by a kernel in stream order, no host wait for them.
-// r_cap < sbits: exact mode capped at shell r_cap (stop rule active, no scan switch); a query still open there ends with
+// r_cap < sbits: either mode capped at shell r_cap (stop rule active, no scan switch); a query still open there ends with
 // radius = r_cap and the k best of shells 0..r_cap.
 int vc_mih_search(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, uint64_t n, const uint64_t* d_q, uint32_t nq,
                   uint32_t k, bool approximate, uint64_t* d_out, uint32_t* d_cnt, vc_query_stats* stats, hipStream_t s,

@@ -21,6 +21,8 @@
 // (gs_stop_shell), the kernels, the layouts they share with the host (GsRoundLists, GsScanCols, GsScanBlock) and GsSearch,
 // the steps of a flagged call (sharded_global_stop, GsSearch::union_scan) | the device-resident radius search: its two kernels
 // (union offsets, rank merge) and ShardRadius, the steps of a call (sharded_radius_dev) | the search entry points.
+// VC_FLAG_GLOBAL_APPROX (behind the global stop): ga_settle_kernel, GaRoundLists and GaSearch, the steps of a flagged approximate call
+// (sharded_global_approx).
 // ============================================================================
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -117,6 +119,7 @@ enum RootBuf {
   // VC_FLAG_GLOBAL_STOP: round lists + counters + floors (GsRoundLists), gathered queries, merged rows / counts / statistics
   // of a round, the union scan's per-query words and the shards' tie ids (GsScanBlock, gs_root_block)
   GS_LISTS, GS_Q, GS_ROWS, GS_CNT, GS_ST, GS_SCAN,
+  GA_LISTS,   // VC_FLAG_GLOBAL_APPROX: the open lists and counters of its rounds (GaRoundLists); gathered queries and a round's merged rows in GS_Q .. GS_ST
   ROOT_BUFS
 };
 
@@ -259,6 +262,11 @@ int vc_sharded_create(const vc_sharded_config* cfg, vc_sharded** out) {
       return sfail(nullptr, VC_ERR_INVALID, "VC_FLAG_GLOBAL_STOP: VC_FLAG_REF_STOP_LITERAL4 with fewer than 4 tables makes the radius loop inexact");
     if (f & VC_FLAG_USE_BITMAP)
       return sfail(nullptr, VC_ERR_INVALID, "VC_FLAG_GLOBAL_STOP: the statistics of VC_FLAG_USE_BITMAP would need the union's bitmap");
+  }
+  if (cfg->engine.flags & VC_FLAG_GLOBAL_APPROX) {   // the union's approximate loop: shards and union must issue the same gets
+    if (cfg->engine.n_tables == 0) return sfail(nullptr, VC_ERR_INVALID, "VC_FLAG_GLOBAL_APPROX needs an MIH index (n_tables > 0)");
+    if (cfg->engine.flags & VC_FLAG_USE_BITMAP)
+      return sfail(nullptr, VC_ERR_INVALID, "VC_FLAG_GLOBAL_APPROX: the statistics of VC_FLAG_USE_BITMAP would need the union's bitmap");
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sfail(nullptr, VC_ERR_NO_DEVICE, "no HIP device visible");
@@ -496,8 +504,8 @@ static int send_queries_to_lanes(vc_sharded* h, const void* d_queries, size_t qb
 // Everything of a batch is enqueued, nothing is waited for (LINEAR; the MIH modes make the host wait inside each shard's
 // vc_search_knn_dev -- how many queries continue decides what is enqueued next -- which is why lanes of different devices
 // then run on host threads): queries, rows, counts and statistics live in HBM on the root device, valid in `S` order.
-// r_cap != VC_NO_CAP (VC_MODE_MIH_EXACT only): every shard runs capped at that shell (vc_engine_knn_capped), the round of the
-// global stop; the slots stay in the root lane's gather buffer for its settle kernel.
+// r_cap != VC_NO_CAP (the MIH modes): every shard runs capped at that shell (vc_engine_knn_capped, in `mode`), the round of the
+// global stop and of the global approximate stop; the slots stay in the root lane's gather buffer for their settle kernels.
 #define VC_NO_CAP 0xFFFFFFFFu
 struct ShardBatch {
   vc_sharded* h;
@@ -555,7 +563,7 @@ struct ShardBatch {
         continue;
       }
       vc_query_stats* sst = d_stats ? (vc_query_stats*)(slot + L.stats_off) : nullptr;
-      const int r = r_cap != VC_NO_CAP ? vc_engine_knn_capped(h->eng[g], q, nq, k, r_cap, slot, (uint32_t*)(slot + L.cnt_off), sst, ls)
+      const int r = r_cap != VC_NO_CAP ? vc_engine_knn_capped(h->eng[g], q, nq, k, mode, r_cap, slot, (uint32_t*)(slot + L.cnt_off), sst, ls)
                                        : vc_search_knn_dev_stats(h->eng[g], q, nq, k, mode, slot, (uint32_t*)(slot + L.cnt_off), sst, ls);
       if (r != VC_OK) { lane_rc[li] = r; lane_err[li] = std::string("shard ") + std::to_string(g) + ": " + vc_last_error(h->eng[g]); return; }
     }
@@ -1187,10 +1195,211 @@ static int sharded_global_stop(vc_sharded* h, const void* d_queries, uint32_t nq
   return rc;
 }
 
+// ---- VC_FLAG_GLOBAL_APPROX ----------------------------------------------------------------------------------------------
+// Approximate MIH over the shards with the stop decision of ONE SearchWorker over the union (the reference's master fills ONE
+// heap of knn_ * APPROXIMATE_FACTOR distinct candidates from all ranks and broadcasts is_stop: search_worker.cc:104-139).  The
+// union's loop stops after the first shell r* in which its distinct candidates of shells 0..r* reach 20 k, else after shell S.
+// What the rounds rest on (c_g(r) = shard g's distinct candidates of shells 0..r, c(r) = the union's):
+//   * the owner rule counts an item once and the shards hold disjoint ids, so c(r) = sum over g of c_g(r);
+//   * shards and union share one key function, so table 0's gets of shells 0..r are the same number everywhere;
+//   * c_g(r) <= c(r): a shard whose own rule stops it in a shell r < t proves c(r) >= 20 k.
+// INVARIANT: a query is settled in a round capped at t only when c(t - 1) < 20 k is known, or t == 0.  Then no shard stops
+// before t, every non-empty shard ends in shell t with the k best of its items of shells 0..t and with c_g(t), and the round's
+// merged rows and summed counts are the union loop's at t: it stops there iff the sum reaches 20 k or t == S.  The schedule is
+// t = 0, 1, 2, ... with every open query in every round, which keeps the invariant by construction and ends after at most S + 1
+// rounds.  A shard that ended elsewhere than in t breaks the argument: ga_settle_kernel counts such shards and the call fails.
+// No pigeonhole bound and no stop multiplier enter, so VC_FLAG_REF_SIGNEXT_KEYS and VC_FLAG_REF_STOP_LITERAL4 are allowed.
+// The host side is GaSearch below: sharded_global_approx() shows the rounds.
+
+// vc_sharded::buf[GA_LISTS] of one call: list[0] | list[1] | open[0] | open[1] | bad.  list[i] is [nq]: the open queries of a
+// round, open[i] of them; one list is the round that runs, the other is filled by its settle kernel; they swap after a round.
+struct GaCounters {
+  uint32_t open[2];   // entries of list[0], list[1]
+  uint32_t bad;       // shards that did not end in their round's shell (never, under the invariant)
+};
+struct GaRoundLists {
+  uint32_t* list[2];
+  GaCounters* ctr;
+  static size_t words(uint32_t nq) { return 2 * (size_t)nq + GS_CTR_SLOT_WORDS; }
+  static GaRoundLists carve(uint32_t* base, uint32_t nq) {
+    GaRoundLists ls{};
+    for (uint32_t*& l : ls.list) { l = base; base += nq; }
+    ls.ctr = (GaCounters*)base;
+    return ls;
+  }
+};
+static_assert(sizeof(GaCounters) <= GS_CTR_SLOT_WORDS * 4, "the counters fit their slot");
+
+struct GaSettleArgs {
+  const uint64_t* base;          // the round's gathered slots (rows | counts | statistics per shard)
+  uint64_t slot_words, stats_off;
+  uint32_t G, nonempty;          // bit g: shard g holds records
+  uint32_t n, t, k, S;           // n queries in a round capped at shell t; S = the last shell
+  const uint32_t* list;          // [n] query of merged row j (< nq)
+  const uint64_t* rows;          // [n][k] merged rows
+  const uint32_t* cnt;           // [n]
+  uint64_t* out;                 // final rows / counts / statistics, by query
+  uint32_t* out_cnt;
+  vc_query_stats* out_stats;     // may be null
+  uint32_t* next;                // [nq] open list of the next round, *next_ctr entries
+  uint32_t* next_ctr;
+  uint32_t* bad;
+};
+
+// One wave per query of the round (GA_SETTLE_BLK / VC_WAVE queries per block): the union's candidate count at shell t is the sum
+// of the shards'; at 20 k (or in the last shell) the merged row is the union loop's answer and goes to the query's own place --
+// the wave's lanes copy its k entries side by side --, else the query stays open.  Every lane reads the same G statistics
+// records, so the decision is uniform over the wave; lane 0 writes the words and takes the counters.
+#define GA_SETTLE_BLK 256u
+extern "C" __global__ void __launch_bounds__(GA_SETTLE_BLK) ga_settle_kernel(const GaSettleArgs a) {
+  const uint32_t j = blockIdx.x * (GA_SETTLE_BLK / VC_WAVE) + threadIdx.x / VC_WAVE;
+  if (j >= a.n) return;
+  const uint32_t lane = vc_lane();
+  const uint32_t q = a.list[j];
+  unsigned long long seen = 0, sub = 0;
+  uint32_t astray = 0;
+  bool first = true;
+  for (uint32_t g = 0; g < a.G; ++g) {
+    if (!((a.nonempty >> g) & 1u)) continue;
+    const vc_query_stats s = ((const vc_query_stats*)(a.base + (uint64_t)g * a.slot_words + a.stats_off))[j];
+    seen += s.n_candidates;
+    if (s.radius != a.t) ++astray;
+    if (first) { sub = s.n_sub_reads; first = false; }   // table 0's gets of shells 0..t: the same on every shard
+  }
+  if (lane == 0 && astray) atomicAdd(a.bad, astray);
+  if (seen >= (unsigned long long)a.k * MIH_APPROX_FACTOR || a.t >= a.S) {   // search_worker.cc:136-137
+    const uint32_t c = min(a.cnt[j], a.k);
+    const uint64_t* row = a.rows + (uint64_t)j * a.k;
+    uint64_t* o = a.out + (uint64_t)q * a.k;
+    for (uint32_t i = lane; i < a.k; i += VC_WAVE) o[i] = row[i];
+    if (lane != 0) return;
+    a.out_cnt[q] = c;
+    if (a.out_stats) {
+      vc_query_stats s{};
+      s.radius = a.t;
+      s.n_results = c;
+      s.n_sub_reads = sub;
+      s.n_candidates = seen;
+      a.out_stats[q] = s;
+    }
+  } else if (lane == 0) {
+    a.next[atomicAdd(a.next_ctr, 1u)] = q;
+  }
+}
+
+// One flagged approximate call: what is fixed for it, and its steps in the order sharded_global_approx() takes them.  Every step
+// is entered and left with the ROOT device current (prepare() binds it; sharded_search_dev returns with it).
+struct GaSearch {
+  vc_sharded* h;
+  const void* d_queries;
+  uint32_t nq, k;
+  uint64_t* d_out;
+  uint32_t* d_counts;
+  vc_query_stats* d_stats;
+  hipStream_t S;
+  // ---- fixed by prepare()
+  uint32_t W, Sb;
+  uint32_t nonempty;                 // bit g: shard g holds records
+  bool trace;                        // dev (VC_MIH_GS_TRACE): per-round wall times on stderr
+  GaRoundLists ls;
+  uint64_t* ga_q;                    // the gathered open queries
+  uint64_t* rows;                    // their merged rows, counts, statistics
+  uint32_t* cnt;
+  vc_query_stats* st;
+  // ---- the rounds
+  int cur;                           // the list of the round that runs
+  uint32_t n_open;                   // its entries
+
+  int prepare() {
+    W = h->nbytes / 8; Sb = h->cfg.engine.bits / h->cfg.engine.n_tables;
+    trace = h->knobs.gs_trace;
+    nonempty = 0;
+    for (uint32_t g = 0; g < h->G; ++g)
+      if (shard_size(h, g)) nonempty |= 1u << g;
+    int rc;
+    VS_HIP(h, hipSetDevice(h->root));
+    if ((rc = counts_or_own(h, nq, &d_counts))) return rc;
+    if ((rc = h->buf[GA_LISTS].grow(h, GaRoundLists::words(nq) * 4))) return rc;
+    if ((rc = h->buf[GS_Q].grow(h, (size_t)nq * h->nbytes))) return rc;
+    if ((rc = h->buf[GS_ROWS].grow(h, (size_t)nq * k * 8))) return rc;
+    if ((rc = h->buf[GS_CNT].grow(h, (size_t)nq * 4))) return rc;
+    if ((rc = h->buf[GS_ST].grow(h, (size_t)nq * sizeof(vc_query_stats)))) return rc;
+    ls = GaRoundLists::carve(h->buf[GA_LISTS].as<uint32_t>(), nq);
+    ga_q = h->buf[GS_Q].as<uint64_t>();
+    rows = h->buf[GS_ROWS].as<uint64_t>();
+    cnt = h->buf[GS_CNT].as<uint32_t>();
+    st = h->buf[GS_ST].as<vc_query_stats>();
+    cur = 0; n_open = 0;
+    VS_HIP(h, hipMemsetAsync(ls.ctr, 0, sizeof(GaCounters), S));
+    return VC_OK;
+  }
+
+  // every query is open in the first round
+  int open_all() {
+    hipLaunchKernelGGL(gs_iota_kernel, dim3((nq + 255) / 256), dim3(256), 0, S, ls.list[0], nq);
+    VS_HIP(h, hipGetLastError());
+    n_open = nq;
+    return VC_OK;
+  }
+
+  GaSettleArgs settle_args(uint32_t t) const {   // after the round's search: it may grow the slots
+    const SlotLayout L(n_open, k, true);
+    GaSettleArgs a{};
+    a.base = h->root_lane_ref().gath(); a.slot_words = L.words; a.stats_off = L.stats_off; a.G = h->G; a.nonempty = nonempty;
+    a.n = n_open; a.t = t; a.k = k; a.S = Sb;
+    a.list = ls.list[cur]; a.rows = rows; a.cnt = cnt;
+    a.out = d_out; a.out_cnt = d_counts; a.out_stats = d_stats;
+    a.next = ls.list[cur ^ 1]; a.next_ctr = &ls.ctr->open[cur ^ 1]; a.bad = &ls.ctr->bad;
+    return a;
+  }
+
+  // one round capped at t: gather the open queries, run every shard through shells 0..t in approximate mode, merge, and let the
+  // settle kernel finish them or keep them open in the other list.  (The host waits inside each shard's capped search, not here.)
+  int run_round(uint32_t t) {
+    int rc;
+    VS_HIP(h, hipMemsetAsync(&ls.ctr->open[cur ^ 1], 0, 4, S));
+    VS_HIP(h, vc_launch_gather_queries((const uint64_t*)d_queries, ls.list[cur], n_open, W, ga_q, S));
+    if ((rc = sharded_search_dev(h, ga_q, n_open, k, VC_MODE_MIH_APPROX, rows, cnt, st, S, t))) return rc;
+    const uint32_t per_block = GA_SETTLE_BLK / VC_WAVE;
+    hipLaunchKernelGGL(ga_settle_kernel, dim3((n_open + per_block - 1) / per_block), dim3(GA_SETTLE_BLK), 0, S, settle_args(t));
+    VS_HIP(h, hipGetLastError());
+    cur ^= 1;
+    return VC_OK;
+  }
+
+  // the round ends: the host waits for its counters -- how many queries stay open, and whether a shard went astray
+  int read_round_counters(uint32_t t, std::chrono::steady_clock::time_point t_round) {
+    GaCounters c;
+    VS_HIP(h, hipMemcpyAsync(&c, ls.ctr, sizeof c, hipMemcpyDeviceToHost, S));
+    VS_HIP(h, hipStreamSynchronize(S));
+    if (trace)
+      fprintf(stderr, "[vc_ga] round %u: %u open -> %u open  %.1f us\n", t, n_open, c.open[cur],
+              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_round).count());
+    n_open = c.open[cur];
+    if (c.bad) return sfail(h, VC_ERR_STATE, "VC_FLAG_GLOBAL_APPROX: %u shard results of the round capped at shell %u ended in another shell", c.bad, t);
+    return VC_OK;
+  }
+};
+
+static int sharded_global_approx(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint64_t* d_out, uint32_t* d_counts,
+                                 vc_query_stats* d_stats, hipStream_t S) {
+  GaSearch c{h, d_queries, nq, k, d_out, d_counts, d_stats, S};
+  int rc = c.prepare();
+  if (!rc) rc = c.open_all();
+  for (uint32_t t = 0; !rc && t <= c.Sb && c.n_open; ++t) {   // the round capped at the last shell settles whatever is open
+    const auto t_round = std::chrono::steady_clock::now();
+    rc = c.run_round(t);                                  // enqueued on S: the open queries searched capped at t and judged
+    if (!rc) rc = c.read_round_counters(t, t_round);      // the round ends here: the host waits for what it left open
+  }
+  return rc;
+}
+
 static int sharded_search_any(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out,
                               uint32_t* d_counts, vc_query_stats* d_stats, hipStream_t S) {
   if (mode == VC_MODE_MIH_EXACT && (h->cfg.engine.flags & VC_FLAG_GLOBAL_STOP))
     return sharded_global_stop(h, d_queries, nq, k, d_out, d_counts, d_stats, S);
+  if (mode == VC_MODE_MIH_APPROX && (h->cfg.engine.flags & VC_FLAG_GLOBAL_APPROX) && h->n)   // (nothing ingested: what the unflagged store returns)
+    return sharded_global_approx(h, d_queries, nq, k, d_out, d_counts, d_stats, S);
   return sharded_search_dev(h, d_queries, nq, k, mode, d_out, d_counts, d_stats, S);
 }
 

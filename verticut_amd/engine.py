@@ -17,6 +17,7 @@ VC_ERR_INVALID, VC_ERR_NO_DEVICE, VC_ERR_HIP, VC_ERR_NOMEM, VC_ERR_STATE, VC_ERR
 MODE_LINEAR, MODE_MIH_EXACT, MODE_MIH_APPROX = 0, 1, 2
 FLAG_USE_BITMAP, FLAG_REF_SIGNEXT_KEYS, FLAG_REF_STOP_LITERAL4, FLAG_LEAN_TIMING = 1, 2, 4, 8
 FLAG_GLOBAL_STOP = 0x10   # sharded store, exact MIH: stop where one engine over the union stops (same rows and statistics)
+FLAG_GLOBAL_APPROX = 0x20 # sharded store, approximate MIH: stop where one engine over the union stops (same rows and statistics)
 SYNTH_UNIFORM, SYNTH_CLUSTERED = 0, 1
 ORDER_ASCENDING, ORDER_FARTHEST_FIRST = 0, 1
 PACK_INF = np.uint64(0xFFFFFFFFFFFFFFFF)

@@ -234,6 +234,8 @@ class ShardedEngine : public Backend {
 // SearchWorker over the whole database stops (VC_FLAG_GLOBAL_STOP, verticut_gpu.h) and prints its rows and statistics.
 // Without it the printed n_sub_reads / n_local_reads are SUMS over the shards and radius the widest shard's.
 // VC_GLOBAL_STOP=1 with VC_REF_QUIRKS=1 is refused: the reference's quirks make its radius loop inexact.
+// VC_GLOBAL_APPROX=1 does the same for the approximate search (VC_FLAG_GLOBAL_APPROX): one heap of 20 k distinct candidates over
+// all shards, as the reference's master fills it (search_worker.cc:104-139).  It may be combined with VC_REF_QUIRKS=1.
 inline Backend* make_backend(uint32_t bits, uint32_t n_tables, uint64_t capacity, uint32_t flags) {
   const char* g = getenv("VC_SHARDS");
   long shards = 1;
@@ -249,6 +251,8 @@ inline Backend* make_backend(uint32_t bits, uint32_t n_tables, uint64_t capacity
       throw EngineError(VC_ERR_INVALID, "VC_GLOBAL_STOP=1 cannot be combined with VC_REF_QUIRKS=1 (the quirks make the radius loop inexact)");
     flags |= VC_FLAG_GLOBAL_STOP;   // a one-GPU Engine ignores it: its stop is global already
   }
+  const char* ga = getenv("VC_GLOBAL_APPROX");
+  if (ga && atoi(ga)) flags |= VC_FLAG_GLOBAL_APPROX;   // (ignored by a one-GPU Engine as well)
   if (shards <= 1) return new Engine(bits, n_tables, capacity, flags);
   std::vector<int> devices;
   if (const char* d = getenv("VC_DEVICES"))
