@@ -242,6 +242,41 @@ int vc_search_radius(vc_engine* e, const void* queries, uint32_t nq, uint32_t ra
 int vc_search_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t radius, uint32_t mode,
                          uint64_t* d_out, uint64_t out_cap, uint64_t* d_offsets, void* stream);
 
+/* ---- queries named by id ------------------------------------------------------------------
+ * replaces: image_search_client::search_image_by_id(id, knn, approximate) (image_search_client.h:12-27; its throughput tester
+ * replays a file of query ids, image_search_test.cc:112-170) and the ID -> BinaryCode read (linear_search.cc:45-46), for a BATCH
+ * of ids whose codes never leave HBM: a gather kernel turns the ids into the [nq][bits/64] query layout out of the column store,
+ * the unchanged search runs on it, and a small kernel shapes the rows. */
+#define VC_IDS_EXCLUDE_SELF 0x1u   /* row = the k nearest items OTHER than the query's own record */
+
+/* ID -> BinaryCode for a batch, in HBM (linear_search.cc:45-46).  d_ids: nq global ids; d_codes: nq*bits/8 bytes; d_found: nq
+ * uint32 (may be NULL), 1 = the id is resident, 0 = it is not (outside [id_base, id_base + vc_size)) and its code is all zero.
+ * One launch on `stream`, nothing is waited for. */
+int vc_get_codes_dev(vc_engine* e, const uint32_t* d_ids, uint32_t nq, void* d_codes, uint32_t* d_found, void* stream);
+/* image_search_client::search_image_by_id for a batch (image_search_client.h:12-27).  ids: nq global ids (host memory); out,
+ * counts, stats, order as vc_search_knn; id_flags: 0 or VC_IDS_EXCLUDE_SELF, any other bit gives VC_ERR_INVALID.
+ *   id_flags == 0          rows, counts and statistics of a resident id are bit for bit those of vc_search_knn /
+ *                          vc_search_knn_dev_stats in the same mode with the same k, queried with the code vc_get_code returns
+ *                          for that id (so the row starts with the record itself, or with its duplicates of smaller id).
+ *   VC_IDS_EXCLUDE_SELF    the row is that of the same call with k + 1, with the entry (distance 0, own id) removed if it is
+ *                          present, cut to k.  The entry is found by value, not by position: duplicates with smaller ids precede
+ *                          it, and with more than k of them it is not in the k + 1 row at all, which is then simply cut to k.
+ *                          n_results and the count are those of the stripped row, the other statistics the k + 1 call's.  k may
+ *                          be at most VC_MAX_K - 1 = 8191 then, else VC_ERR_INVALID.
+ * A batch has no VC_NOT_FOUND: an id that is not resident gives count 0, a UINT64_MAX-padded row and zero statistics, and the call
+ * still returns VC_OK.  Repeated ids are independent queries.  The scratch (gathered queries, k + 1 rows, counts, found words) is
+ * grow-only buffers of the handle, separate from those of the other calls; a result depends on the database and the call only.
+ * Radius search by id is not offered: a missing id would need the variable-length result compacted, and vc_get_codes_dev +
+ * vc_search_radius_dev serves a caller whose ids exist. */
+int vc_search_knn_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, uint32_t id_flags,
+                      uint64_t* out, uint32_t* counts, vc_query_stats* stats);
+/* The same for ids and results in HBM (search_image_by_id, image_search_client.h:12-27): d_ids nq uint32; d_out nq*k ascending,
+ * UINT64_MAX padded; d_counts (may be NULL) and d_stats (may be NULL) as vc_search_knn_dev_stats.  Stream behaviour is exactly
+ * that of vc_search_knn_dev_stats underneath, plus two small launches on `stream` (gather before, strip / found mask after):
+ * VC_MODE_LINEAR waits for nothing on the host, the MIH modes wait as they do there; results are valid in stream order. */
+int vc_search_knn_ids_dev(vc_engine* e, const uint32_t* d_ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t id_flags,
+                          uint64_t* d_out, uint32_t* d_counts, vc_query_stats* d_stats, void* stream);
+
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
  * seconds); the affected queries kept d_counts[i] == UINT32_MAX.  0 in normal operation.  Synchronises the stream.
@@ -350,6 +385,19 @@ int vc_sharded_search_radius(vc_sharded* h, const void* queries, uint32_t nq, ui
  * mpi_coordinator.cc:34-69) for callers that keep the batch in HBM. */
 int vc_sharded_search_radius_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t radius, uint32_t mode,
                                  uint64_t* d_out, uint64_t out_cap, uint64_t* d_offsets, void* stream);
+/* Queries named by id over all shards (search_image_by_id, image_search_client.h:12-27; ID -> BinaryCode, linear_search.cc:45-46):
+ * contract, id_flags and batch rules as vc_get_codes_dev / vc_search_knn_ids / vc_search_knn_ids_dev, with "the call underneath"
+ * = vc_sharded_search_knn / vc_sharded_search_knn_dev on the handle as it was created -- VC_FLAG_GLOBAL_STOP and
+ * VC_FLAG_GLOBAL_APPROX included -- and ids global over the whole store.  Device pointers live on the ROOT device, `stream` is a
+ * stream of that device.  Every non-empty shard gathers the ids IT owns into a [nq][bits/64] staging buffer on its own device
+ * (zero rows for the others); a remote shard's buffer and found words reach the root by one hipMemcpyPeerAsync -- peer copies
+ * whatever vc_sharded_config.exchange says, as in vc_sharded_search_radius_dev -- shards of the root device are read in place, and
+ * one kernel on the root ORs the slots (the id ranges are disjoint).  The gather waits for nothing on the host. */
+int vc_sharded_get_codes_dev(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, void* d_codes, uint32_t* d_found, void* stream);
+int vc_sharded_search_knn_ids(vc_sharded* h, const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order,
+                              uint32_t id_flags, uint64_t* out, uint32_t* counts, vc_query_stats* stats);
+int vc_sharded_search_knn_ids_dev(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t id_flags,
+                                  uint64_t* d_out, uint32_t* d_counts, vc_query_stats* d_stats, void* stream);
 /* borrow shard g's engine (bucket views, timing, files); its id range is [*first_id, *first_id + *n_ids) */
 int vc_sharded_shard(vc_sharded* h, uint32_t shard, vc_engine** e, uint64_t* first_id, uint64_t* n_ids);
 

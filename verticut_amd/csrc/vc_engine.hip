@@ -38,6 +38,16 @@ struct vc_engine {
   uint64_t* d_frows = nullptr;  size_t frows_bytes = 0;
   uint32_t* d_fcnt = nullptr;   size_t fcnt_bytes = 0;
   uint32_t* d_rec = nullptr;                              // scratch of the device-side ring-overflow recovery (zero at first use)
+  // queries named by id (vc_search_knn_ids*): the gathered queries, their found words, the k + 1 rows and counts of the search
+  // underneath; and what the host-pointer form stages on the device (ids, rows, counts, statistics)
+  uint64_t* d_idq = nullptr;    size_t idq_bytes = 0;
+  uint32_t* d_idfound = nullptr; size_t idfound_bytes = 0;
+  uint64_t* d_idrows = nullptr; size_t idrows_bytes = 0;
+  uint32_t* d_idcnt = nullptr;  size_t idcnt_bytes = 0;
+  uint32_t* d_hids = nullptr;   size_t hids_bytes = 0;
+  uint64_t* d_hrows = nullptr;  size_t hrows_bytes = 0;
+  uint32_t* d_hcnt = nullptr;   size_t hcnt_bytes = 0;
+  vc_query_stats* d_hstats = nullptr; size_t hstats_bytes = 0;
   CleanState clean;                                       // the last kernel of a linear step hands d_state back zeroed: no memset per step
   uint32_t scan_event_tick = 0;                           // VC_FLAG_LEAN_TIMING: only every timing_sample-th verify launch is timed
   VcKnobs knobs;                                          // environment knobs, read once at vc_create
@@ -298,6 +308,14 @@ int vc_destroy(vc_engine* e) {
   (void)hipFree(e->d_fq);
   (void)hipFree(e->d_frows);
   (void)hipFree(e->d_fcnt);
+  (void)hipFree(e->d_idq);
+  (void)hipFree(e->d_idfound);
+  (void)hipFree(e->d_idrows);
+  (void)hipFree(e->d_idcnt);
+  (void)hipFree(e->d_hids);
+  (void)hipFree(e->d_hrows);
+  (void)hipFree(e->d_hcnt);
+  (void)hipFree(e->d_hstats);
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->last_call) (void)hipEventDestroy(e->last_call);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -990,17 +1008,10 @@ int vc_engine_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint3
                           (const uint64_t*)d_queries, nq, radius, d_out, out_cap, d_offsets, true, &e->radius_work, e->stream, &e->err, total);
 }
 
-extern "C" {
-
-int vc_search_knn_dev_stats(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out,
-                            uint32_t* d_counts, vc_query_stats* d_stats, void* stream) {
-  int rc = check_knn_args(e, d_queries, nq, k, mode);
-  if (rc) return rc;
-  if (!d_out) return VC_ERR_INVALID;
-  if ((rc = bind_device(e))) return rc;
-  if ((rc = grow(e, &e->d_cnt, &e->cnt_bytes, (size_t)nq * 8))) return rc;   // outside the timed bracket; grow() uses no stream
-  uint32_t* cnt = d_counts ? d_counts : e->d_cnt;
-  const StreamCall call(e, caller_stream(e, stream));
+// the search of vc_search_knn_dev_stats on e->stream, inside the caller's StreamCall
+static int knn_dev_run(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out, uint32_t* cnt,
+                       vc_query_stats* d_stats) {
+  int rc;
   if (mode == VC_MODE_LINEAR) {
     rc = LinearSearch(e, nq, k).run((const uint64_t*)d_queries, nq, d_out, cnt);
     if (rc == VC_OK && d_stats) {
@@ -1013,6 +1024,97 @@ int vc_search_knn_dev_stats(vc_engine* e, const void* d_queries, uint32_t nq, ui
                        d_out, cnt, nullptr, e->stream, &e->err, &fb, d_stats);
   }
   return rc;
+}
+
+extern "C" {
+
+int vc_search_knn_dev_stats(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out,
+                            uint32_t* d_counts, vc_query_stats* d_stats, void* stream) {
+  int rc = check_knn_args(e, d_queries, nq, k, mode);
+  if (rc) return rc;
+  if (!d_out) return VC_ERR_INVALID;
+  if ((rc = bind_device(e))) return rc;
+  if ((rc = grow(e, &e->d_cnt, &e->cnt_bytes, (size_t)nq * 8))) return rc;   // outside the timed bracket; grow() uses no stream
+  const StreamCall call(e, caller_stream(e, stream));
+  return knn_dev_run(e, d_queries, nq, k, mode, d_out, d_counts ? d_counts : e->d_cnt, d_stats);
+}
+
+}  // extern "C"
+
+// ---- queries named by id (vc_ids.hip) --------------------------------------------------------------------------------------
+static int check_ids_args(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t id_flags) {
+  int rc = check_knn_args(e, ids, nq, k, mode);
+  if (rc) return rc;
+  if (id_flags & ~VC_IDS_EXCLUDE_SELF) return fail(e, VC_ERR_INVALID, "unknown id_flags 0x%x", id_flags);
+  if ((id_flags & VC_IDS_EXCLUDE_SELF) && k > VC_MAX_K - 1) return fail(e, VC_ERR_INVALID, "k must be in 1..%u with VC_IDS_EXCLUDE_SELF", VC_MAX_K - 1);
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_get_codes_dev(vc_engine* e, const uint32_t* d_ids, uint32_t nq, void* d_codes, uint32_t* d_found, void* stream) {
+  if (!e || !d_ids || !d_codes || nq == 0) return VC_ERR_INVALID;
+  int rc = bind_device(e);
+  if (rc) return rc;
+  VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, 0, 0, d_ids, nq, (uint64_t*)d_codes, d_found, caller_stream(e, stream)));
+  return VC_OK;
+}
+
+int vc_search_knn_ids_dev(vc_engine* e, const uint32_t* d_ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t id_flags, uint64_t* d_out,
+                          uint32_t* d_counts, vc_query_stats* d_stats, void* stream) {
+  int rc = check_ids_args(e, d_ids, nq, k, mode, id_flags);
+  if (rc) return rc;
+  if (!d_out) return VC_ERR_INVALID;
+  if ((rc = bind_device(e))) return rc;
+  const uint32_t kp = k + ((id_flags & VC_IDS_EXCLUDE_SELF) ? 1u : 0u);
+  if ((rc = grow(e, &e->d_idq, &e->idq_bytes, (size_t)nq * e->W * 8))) return rc;
+  if ((rc = grow(e, &e->d_idfound, &e->idfound_bytes, (size_t)nq * 4))) return rc;
+  if ((rc = grow(e, &e->d_idrows, &e->idrows_bytes, (size_t)nq * kp * 8))) return rc;
+  if ((rc = grow(e, &e->d_idcnt, &e->idcnt_bytes, (size_t)nq * 4))) return rc;
+  const StreamCall call(e, caller_stream(e, stream));
+  VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, d_ids, nq, e->d_idq, e->d_idfound,
+                                 e->stream));
+  if ((rc = knn_dev_run(e, e->d_idq, nq, kp, mode, e->d_idrows, e->d_idcnt, d_stats))) return rc;
+  VC_HIP(e, vc_launch_ids_strip(d_ids, e->d_idfound, e->d_idrows, e->d_idcnt, nq, kp, k, d_out, d_counts, d_stats, e->stream));
+  return VC_OK;
+}
+
+int vc_search_knn_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, uint32_t id_flags,
+                      uint64_t* out, uint32_t* counts, vc_query_stats* stats) {
+  int rc = check_ids_args(e, ids, nq, k, mode, id_flags);
+  if (rc) return rc;
+  if (!out || order > VC_ORDER_FARTHEST_FIRST) return VC_ERR_INVALID;
+  if ((rc = bind_device(e))) return rc;
+  if ((rc = grow(e, &e->d_hids, &e->hids_bytes, (size_t)nq * 4))) return rc;
+  if ((rc = grow(e, &e->d_hrows, &e->hrows_bytes, (size_t)nq * k * 8))) return rc;
+  if ((rc = grow(e, &e->d_hcnt, &e->hcnt_bytes, (size_t)nq * 4))) return rc;
+  if (stats && (rc = grow(e, &e->d_hstats, &e->hstats_bytes, (size_t)nq * sizeof(vc_query_stats)))) return rc;
+  VC_HIP(e, hipMemcpyAsync(e->d_hids, ids, (size_t)nq * 4, hipMemcpyHostToDevice, e->stream));
+  if ((rc = vc_search_knn_ids_dev(e, e->d_hids, nq, k, mode, id_flags, e->d_hrows, e->d_hcnt, stats ? e->d_hstats : nullptr, e->stream))) return rc;
+  std::vector<uint32_t> cnt(nq);
+  VC_HIP(e, hipMemcpyAsync(out, e->d_hrows, (size_t)nq * k * 8, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipMemcpyAsync(cnt.data(), e->d_hcnt, (size_t)nq * 4, hipMemcpyDeviceToHost, e->stream));
+  if (stats) VC_HIP(e, hipMemcpyAsync(stats, e->d_hstats, (size_t)nq * sizeof(vc_query_stats), hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipStreamSynchronize(e->stream));
+  if (mode == VC_MODE_LINEAR && std::find(cnt.begin(), cnt.end(), 0xFFFFFFFFu) != cnt.end()) {
+    // a ring overflowed and the device-side recovery gave up: the batch is answered again by vc_search_knn, whose host-driven
+    // recovery always ends, on the gathered codes, and stripped here by the kernel's rule
+    const uint32_t kp = k + ((id_flags & VC_IDS_EXCLUDE_SELF) ? 1u : 0u);
+    std::vector<uint64_t> codes((size_t)nq * e->W), rows((size_t)nq * kp);
+    std::vector<uint32_t> found(nq), rcnt(nq);
+    VC_HIP(e, hipMemcpyAsync(codes.data(), e->d_idq, codes.size() * 8, hipMemcpyDeviceToHost, e->stream));
+    VC_HIP(e, hipMemcpyAsync(found.data(), e->d_idfound, (size_t)nq * 4, hipMemcpyDeviceToHost, e->stream));
+    VC_HIP(e, hipStreamSynchronize(e->stream));
+    if ((rc = vc_search_knn(e, codes.data(), nq, kp, mode, VC_ORDER_ASCENDING, rows.data(), rcnt.data(), stats))) return rc;
+    vc_ids_strip_host(ids, found.data(), rows.data(), rcnt.data(), nq, kp, k, out, cnt.data(), stats);
+  }
+  for (uint32_t i = 0; i < nq; ++i) {
+    if (mode != VC_MODE_LINEAR) cnt[i] = std::min(cnt[i], k);   // (as vc_sharded_search_knn: a flagged MIH row has k entries)
+    if (order == VC_ORDER_FARTHEST_FIRST) std::reverse(out + (size_t)i * k, out + (size_t)i * k + cnt[i]);
+    if (counts) counts[i] = cnt[i];
+    if (stats) stats[i].n_results = cnt[i];
+  }
+  return VC_OK;
 }
 
 // is `p` page-locked host memory (hipHostMalloc / hipHostRegister / torch pin_memory)?  Then a copy is one DMA, no staging.

@@ -146,6 +146,24 @@ hipError_t vc_radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], uint64_t n,
 // n_lists x [nq][k] sorted lists -> merged top-k
 hipError_t vc_launch_select_lists(const uint64_t* d_lists, uint32_t n_lists, uint32_t nq, uint32_t k, uint64_t* d_out,
                                   uint32_t* d_out_count, hipStream_t s);
+// ---- vc_ids.hip: queries named by id ------------------------------------------------------------------------------
+// ids (global) -> d_q [nq][W] + d_found [nq] (nullable): an id outside [id_base, id_base + n) gives a zero row and found = 0.
+// fill_n != 0: an id outside [fill_base, fill_base + fill_n) (the whole store's resident range) gets local record 0's code as its
+// row, still with found = 0 -- a cheap stand-in query for the search whose row is thrown away
+hipError_t vc_launch_ids_gather(const uint64_t* cols, uint64_t stride, uint32_t W, uint32_t id_base, uint64_t n, uint32_t fill_base,
+                                uint64_t fill_n, const uint32_t* d_ids, uint32_t nq, uint64_t* d_q, uint32_t* d_found, hipStream_t s);
+// rows [nq][kp] / cnt of a search with kp = k + 1 (the entry (0, id) is dropped if present) or kp = k (pass-through) -> d_out
+// [nq][k], d_out_cnt (nullable), d_stats[i].n_results (d_stats nullable: the search's records, rewritten in place); found = 0
+// gives a VC_PACK_INF row, count 0 and a zero record.  rows and d_out must not overlap.
+hipError_t vc_launch_ids_strip(const uint32_t* d_ids, const uint32_t* d_found, const uint64_t* d_rows, const uint32_t* d_cnt, uint32_t nq,
+                               uint32_t kp, uint32_t k, uint64_t* d_out, uint32_t* d_out_cnt, vc_query_stats* d_stats, hipStream_t s);
+// the shards' gathered slots ([nq][W] words | nq found words, slot_words apart; bit g of mask: slot g is filled) ORed into d_q / d_found
+inline uint64_t vc_ids_slot_words(uint32_t nq, uint32_t W) { return (uint64_t)nq * W + ((uint64_t)nq + 1) / 2; }
+hipError_t vc_launch_ids_merge(const uint64_t* d_slots, uint64_t slot_words, uint32_t mask, uint32_t nq, uint32_t W, uint64_t* d_q,
+                               uint32_t* d_found, hipStream_t s);
+// the strip kernel's rule on host memory (counts non-null)
+void vc_ids_strip_host(const uint32_t* ids, const uint32_t* found, const uint64_t* rows, const uint32_t* cnt, uint32_t nq, uint32_t kp, uint32_t k,
+                       uint64_t* out, uint32_t* counts, vc_query_stats* stats);
 // ---- vc_engine.hip: what the sharded store's global stop (vc_sharded.hip) needs of a shard's engine
 struct VcEngineView {
   const uint64_t* cols;   // column-major codes, word j of record i at cols[j * stride + i]

@@ -100,6 +100,8 @@ enum LaneBuf {
   LANE_GATH,   // [G][slot]: shard g's rows | counts | statistics at slot g (SlotLayout); on the root (and, with RCCL, everywhere)
                // the gathered results of all shards
   LANE_AUX,    // union scan of VC_FLAG_GLOBAL_STOP: its per-query inputs and outputs here (GsScanBlock, gs_lane_block)
+  LANE_IDS,    // queries named by id: the batch's ids on this device (peer copy from the root)
+  LANE_IDGATH, // [G][slot]: the gathered words | found words of shard g at slot g (vc_ids_slot_words); on the root all shards' slots
   LANE_BUFS
 };
 struct Lane {
@@ -120,6 +122,9 @@ enum RootBuf {
   // of a round, the union scan's per-query words and the shards' tie ids (GsScanBlock, gs_root_block)
   GS_LISTS, GS_Q, GS_ROWS, GS_CNT, GS_ST, GS_SCAN,
   GA_LISTS,   // VC_FLAG_GLOBAL_APPROX: the open lists and counters of its rounds (GaRoundLists); gathered queries and a round's merged rows in GS_Q .. GS_ST
+  // queries named by id: gathered queries, found words, the k + 1 rows and counts of the search underneath; the host-pointer
+  // form's staged ids, rows, counts and statistics
+  IDS_Q, IDS_FOUND, IDS_ROWS, IDS_CNT, IDS_HIDS, IDS_HROWS, IDS_HCNT, IDS_HSTATS,
   ROOT_BUFS
 };
 
@@ -1663,6 +1668,70 @@ static int sharded_radius_dev(vc_sharded* h, const void* d_queries, uint32_t nq,
   return rc;
 }
 
+// ---- queries named by id over the shards (search_image_by_id, image_search_client.h:12-27) ------------------------------------------
+// d_ids (root device) -> d_q [nq][W] + d_found (nullable) on the root, all enqueued, nothing waited for: the ids reach every other
+// device by one peer copy, every non-empty shard gathers the ids it owns into its slot on its own device (vc_ids_gather_kernel with
+// the shard's id range: zero rows for the rest), a remote shard's slot travels to the root by one peer copy behind its lane's `done`
+// event, the root's shards wrote theirs in place, and vc_ids_merge_kernel ORs the filled slots.  Returns with the root device current.
+// fill (the search calls): the first non-empty shard gives an id that is resident NOWHERE in the store its record 0 as a stand-in query.
+static int sharded_gather_ids(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, uint64_t* d_q, uint32_t* d_found, bool fill, hipStream_t S) {
+  const uint32_t W = h->nbytes / 8;
+  const uint64_t slot_words = vc_ids_slot_words(nq, W);
+  int rc;
+  for (uint32_t li = 0; li < h->lanes.size(); ++li) {
+    Lane& l = h->lanes[li];
+    VS_HIP(h, hipSetDevice(l.dev));
+    if ((rc = l.buf[LANE_IDGATH].grow(h, slot_words * 8 * (li == h->root_lane ? h->G : l.shards.back() + 1)))) return rc;
+    if (li != h->root_lane && (rc = l.buf[LANE_IDS].grow(h, (size_t)nq * 4))) return rc;
+  }
+  if (h->lanes.size() > 1) {
+    VS_HIP(h, hipSetDevice(h->root));
+    VS_HIP(h, hipEventRecord(h->ev_q, S));
+  }
+  uint32_t mask = 0;
+  for (uint32_t li = 0; li < h->lanes.size(); ++li) {
+    Lane& l = h->lanes[li];
+    const bool is_root = li == h->root_lane;
+    hipStream_t ls = is_root ? S : l.stream;
+    VS_HIP(h, hipSetDevice(l.dev));
+    if (!is_root) {
+      VS_HIP(h, hipStreamWaitEvent(ls, h->ev_q, 0));   // also orders the lane behind the previous batch's copies out of its buffers
+      VS_HIP(h, hipMemcpyPeerAsync(l.buf[LANE_IDS].p, l.dev, d_ids, h->root, (size_t)nq * 4, ls));
+    }
+    for (uint32_t g : l.shards) {
+      if (shard_size(h, g) == 0) continue;
+      VcEngineView v;
+      if ((rc = vc_engine_view(h->eng[g], &v))) return sfail(h, rc, "shard %u: no view", g);
+      uint64_t* slot = l.buf[LANE_IDGATH].as<uint64_t>() + (size_t)g * slot_words;
+      VS_HIP(h, vc_launch_ids_gather(v.cols, v.stride, v.W, v.id_base, v.n, h->cfg.engine.id_base, fill && g == 0 ? h->n : 0,
+                                     is_root ? d_ids : l.buf[LANE_IDS].as<uint32_t>(), nq, slot,
+                                     (uint32_t*)(slot + (size_t)nq * W), ls));
+      mask |= 1u << g;
+    }
+    if (!is_root) VS_HIP(h, hipEventRecord(l.done, ls));
+  }
+  VS_HIP(h, hipSetDevice(h->root));
+  uint64_t* root_slots = h->root_lane_ref().buf[LANE_IDGATH].as<uint64_t>();
+  for (uint32_t li = 0; li < h->lanes.size(); ++li) {
+    if (li == h->root_lane) continue;
+    Lane& l = h->lanes[li];
+    VS_HIP(h, hipStreamWaitEvent(S, l.done, 0));
+    for (uint32_t g : l.shards)
+      if (mask >> g & 1)
+        VS_HIP(h, hipMemcpyPeerAsync(root_slots + (size_t)g * slot_words, h->root, l.buf[LANE_IDGATH].as<uint64_t>() + (size_t)g * slot_words,
+                                     l.dev, slot_words * 8, S));
+  }
+  VS_HIP(h, vc_launch_ids_merge(root_slots, slot_words, mask, nq, W, d_q, d_found, S));
+  return VC_OK;
+}
+
+static int check_sharded_ids_args(vc_sharded* h, const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t id_flags, const void* out) {
+  if (!h || !ids || !out || nq == 0 || k == 0 || k > VC_MAX_K || mode > VC_MODE_MIH_APPROX) return VC_ERR_INVALID;
+  if (id_flags & ~VC_IDS_EXCLUDE_SELF) return sfail(h, VC_ERR_INVALID, "unknown id_flags 0x%x", id_flags);
+  if ((id_flags & VC_IDS_EXCLUDE_SELF) && k > VC_MAX_K - 1) return sfail(h, VC_ERR_INVALID, "k must be in 1..%u with VC_IDS_EXCLUDE_SELF", VC_MAX_K - 1);
+  return VC_OK;
+}
+
 extern "C" {
 
 int vc_sharded_root_device(const vc_sharded* h, int* device) {
@@ -1834,6 +1903,72 @@ int vc_sharded_search_radius_dev(vc_sharded* h, const void* d_queries, uint32_t 
   if (!h || !d_queries || !d_offsets || nq == 0 || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) || (!d_out && out_cap))
     return VC_ERR_INVALID;
   return sharded_radius_dev(h, d_queries, nq, radius, mode, d_out, out_cap, d_offsets, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+}
+
+int vc_sharded_get_codes_dev(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, void* d_codes, uint32_t* d_found, void* stream) {
+  if (!h || !d_ids || !d_codes || nq == 0) return VC_ERR_INVALID;
+  return sharded_gather_ids(h, d_ids, nq, (uint64_t*)d_codes, d_found, false, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+}
+
+int vc_sharded_search_knn_ids_dev(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t id_flags,
+                                  uint64_t* d_out, uint32_t* d_counts, vc_query_stats* d_stats, void* stream) {
+  int rc = check_sharded_ids_args(h, d_ids, nq, k, mode, id_flags, d_out);
+  if (rc) return rc;
+  hipStream_t S = stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream;
+  const uint32_t kp = k + ((id_flags & VC_IDS_EXCLUDE_SELF) ? 1u : 0u);
+  VS_HIP(h, hipSetDevice(h->root));
+  if ((rc = h->buf[IDS_Q].grow(h, (size_t)nq * h->nbytes))) return rc;
+  if ((rc = h->buf[IDS_FOUND].grow(h, (size_t)nq * 4))) return rc;
+  if ((rc = h->buf[IDS_ROWS].grow(h, (size_t)nq * kp * 8))) return rc;
+  if ((rc = h->buf[IDS_CNT].grow(h, (size_t)nq * 4))) return rc;
+  if ((rc = sharded_gather_ids(h, d_ids, nq, h->buf[IDS_Q].as<uint64_t>(), h->buf[IDS_FOUND].as<uint32_t>(), true, S))) return rc;
+  if ((rc = sharded_search_any(h, h->buf[IDS_Q].p, nq, kp, mode, h->buf[IDS_ROWS].as<uint64_t>(), h->buf[IDS_CNT].as<uint32_t>(), d_stats, S))) return rc;
+  VS_HIP(h, hipSetDevice(h->root));
+  VS_HIP(h, vc_launch_ids_strip(d_ids, h->buf[IDS_FOUND].as<uint32_t>(), h->buf[IDS_ROWS].as<uint64_t>(), h->buf[IDS_CNT].as<uint32_t>(), nq, kp, k,
+                                d_out, d_counts, d_stats, S));
+  return VC_OK;
+}
+
+int vc_sharded_search_knn_ids(vc_sharded* h, const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order,
+                              uint32_t id_flags, uint64_t* out, uint32_t* counts, vc_query_stats* stats) {
+  int rc = check_sharded_ids_args(h, ids, nq, k, mode, id_flags, out);
+  if (rc) return rc;
+  if (order > VC_ORDER_FARTHEST_FIRST) return VC_ERR_INVALID;
+  hipStream_t S = h->root_stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  if ((rc = h->buf[IDS_HIDS].grow(h, (size_t)nq * 4))) return rc;
+  if ((rc = h->buf[IDS_HROWS].grow(h, (size_t)nq * k * 8))) return rc;
+  if ((rc = h->buf[IDS_HCNT].grow(h, (size_t)nq * 4))) return rc;
+  if (stats && (rc = h->buf[IDS_HSTATS].grow(h, (size_t)nq * sizeof(vc_query_stats)))) return rc;
+  VS_HIP(h, hipMemcpyAsync(h->buf[IDS_HIDS].p, ids, (size_t)nq * 4, hipMemcpyHostToDevice, S));
+  if ((rc = vc_sharded_search_knn_ids_dev(h, h->buf[IDS_HIDS].as<uint32_t>(), nq, k, mode, id_flags, h->buf[IDS_HROWS].as<uint64_t>(),
+                                          h->buf[IDS_HCNT].as<uint32_t>(), stats ? h->buf[IDS_HSTATS].as<vc_query_stats>() : nullptr, S)))
+    return rc;
+  std::vector<uint32_t> cnt(nq);
+  VS_HIP(h, hipSetDevice(h->root));
+  VS_HIP(h, hipMemcpyAsync(out, h->buf[IDS_HROWS].p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipMemcpyAsync(cnt.data(), h->buf[IDS_HCNT].p, (size_t)nq * 4, hipMemcpyDeviceToHost, S));
+  if (stats) VS_HIP(h, hipMemcpyAsync(stats, h->buf[IDS_HSTATS].p, (size_t)nq * sizeof(vc_query_stats), hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipStreamSynchronize(S));
+  if (mode == VC_MODE_LINEAR && std::find(cnt.begin(), cnt.end(), 0xFFFFFFFFu) != cnt.end()) {
+    // a shard's device-side ring-overflow recovery gave up: the batch is answered again by vc_sharded_search_knn (whose shards
+    // recover on the host) on the gathered codes, and stripped here by the kernel's rule
+    const uint32_t kp = k + ((id_flags & VC_IDS_EXCLUDE_SELF) ? 1u : 0u);
+    std::vector<uint64_t> codes((size_t)nq * (h->nbytes / 8)), rows((size_t)nq * kp);
+    std::vector<uint32_t> found(nq), rcnt(nq);
+    VS_HIP(h, hipMemcpyAsync(codes.data(), h->buf[IDS_Q].p, codes.size() * 8, hipMemcpyDeviceToHost, S));
+    VS_HIP(h, hipMemcpyAsync(found.data(), h->buf[IDS_FOUND].p, (size_t)nq * 4, hipMemcpyDeviceToHost, S));
+    VS_HIP(h, hipStreamSynchronize(S));
+    if ((rc = vc_sharded_search_knn(h, codes.data(), nq, kp, mode, VC_ORDER_ASCENDING, rows.data(), rcnt.data(), stats))) return rc;
+    vc_ids_strip_host(ids, found.data(), rows.data(), rcnt.data(), nq, kp, k, out, cnt.data(), stats);
+  }
+  for (uint32_t i = 0; i < nq; ++i) {
+    if (mode != VC_MODE_LINEAR) cnt[i] = std::min(cnt[i], k);   // (as vc_sharded_search_knn: a flagged MIH row has k entries)
+    if (order == VC_ORDER_FARTHEST_FIRST) std::reverse(out + (size_t)i * k, out + (size_t)i * k + cnt[i]);
+    if (counts) counts[i] = cnt[i];
+    if (stats) stats[i].n_results = cnt[i];
+  }
+  return VC_OK;
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@ FLAG_GLOBAL_STOP = 0x10   # sharded store, exact MIH: stop where one engine over
 FLAG_GLOBAL_APPROX = 0x20 # sharded store, approximate MIH: stop where one engine over the union stops (same rows and statistics)
 SYNTH_UNIFORM, SYNTH_CLUSTERED = 0, 1
 ORDER_ASCENDING, ORDER_FARTHEST_FIRST = 0, 1
+IDS_EXCLUDE_SELF = 0x1    # VC_IDS_EXCLUDE_SELF: a by-id row holds the k nearest items other than the query's own record
 PACK_INF = np.uint64(0xFFFFFFFFFFFFFFFF)
 STREAM_OWN = C.c_void_p(-1)   # VC_STREAM_OWN; None / 0 = the HIP null stream (PyTorch's default stream)
 
@@ -34,6 +35,8 @@ EXPORTS = [
     "vc_sharded_add_synthetic", "vc_sharded_size", "vc_sharded_build_index", "vc_sharded_get_code", "vc_sharded_get_bucket",
     "vc_sharded_search_knn", "vc_sharded_shard", "vc_sharded_search_knn_dev", "vc_sharded_root_device", "vc_search_knn_dev_stats", "vc_sharded_search_radius",
     "vc_sharded_search_radius_dev",
+    "vc_get_codes_dev", "vc_search_knn_ids", "vc_search_knn_ids_dev",
+    "vc_sharded_get_codes_dev", "vc_sharded_search_knn_ids", "vc_sharded_search_knn_ids_dev",
 ]
 MAX_SHARDS = 16
 EXCHANGE_AUTO, EXCHANGE_PEER_COPY, EXCHANGE_RCCL = 0, 1, 2
@@ -143,6 +146,12 @@ def load_library():
     L.vc_sharded_root_device.argtypes = [vp, C.POINTER(C.c_int)]
     L.vc_sharded_search_radius.argtypes = [vp, vp, u32, u32, u32, vp, u64, vp]
     L.vc_sharded_search_radius_dev.argtypes = [vp, vp, u32, u32, u32, vp, u64, vp, vp]
+    L.vc_get_codes_dev.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.vc_search_knn_ids.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, vp, vp]
+    L.vc_search_knn_ids_dev.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]
+    L.vc_sharded_get_codes_dev.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.vc_sharded_search_knn_ids.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, vp, vp]
+    L.vc_sharded_search_knn_ids_dev.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -152,6 +161,19 @@ def load_library():
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _search_knn_ids(self, fn, ids, k, mode, order, id_flags, with_stats):
+    """shared by Engine.search_knn_ids and ShardedEngine.search_knn_ids: numpy ids in, (rows, counts[, stats]) out"""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+    nq = ids.shape[0]
+    out = np.empty((nq, k), dtype=np.uint64)
+    counts = np.zeros(nq, dtype=np.uint32)
+    stats = (VcQueryStats * nq)() if with_stats else None
+    self._check(fn(self._h, _p(ids), nq, k, mode, order, id_flags, _p(out), _p(counts), C.cast(stats, C.c_void_p) if with_stats else None))
+    if with_stats:
+        return out, counts, list(stats)
+    return out, counts
 
 
 def split(packed):
@@ -321,6 +343,19 @@ class Engine:
         """vc_search_knn_dev_stats: the same + nq VcQueryStats records written to device memory (d_stats, raw address) in stream order"""
         self._check(self._L.vc_search_knn_dev_stats(self._h, d_queries, nq, k, mode, d_out, d_counts, d_stats, stream))
 
+    # -- queries named by id (image_search_client::search_image_by_id for a batch; the codes never leave HBM)
+    def get_codes_dev(self, d_ids, nq, d_codes, d_found=None, stream=None):
+        """vc_get_codes_dev on raw device addresses: nq uint32 ids -> nq * bits/8 code bytes (+ nq uint32 found words)"""
+        self._check(self._L.vc_get_codes_dev(self._h, d_ids, nq, d_codes, d_found, stream))
+
+    def search_knn_ids(self, ids, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, id_flags=0, with_stats=False):
+        """vc_search_knn_ids: numpy ids; returns like search_knn.  An id that is not resident gives count 0 and a PACK_INF row."""
+        return _search_knn_ids(self, self._L.vc_search_knn_ids, ids, k, mode, order, id_flags, with_stats)
+
+    def search_knn_ids_dev(self, d_ids, nq, k, d_out, d_counts=None, d_stats=None, mode=MODE_LINEAR, id_flags=0, stream=None):
+        """vc_search_knn_ids_dev on raw device addresses; results valid in `stream` order"""
+        self._check(self._L.vc_search_knn_ids_dev(self._h, d_ids, nq, k, mode, id_flags, d_out, d_counts, d_stats, stream))
+
     def search_radius(self, queries, radius, mode=MODE_LINEAR, cap_per_query=4096):
         q = self._queries(queries)
         nq = q.shape[0]
@@ -457,6 +492,19 @@ class ShardedEngine:
     def search_knn_dev(self, d_queries, nq, k, d_out, d_counts=None, d_stats=None, mode=MODE_LINEAR, stream=None):
         """vc_sharded_search_knn_dev: raw device addresses on the root device; results valid in `stream` order"""
         self._check(self._L.vc_sharded_search_knn_dev(self._h, d_queries, nq, k, mode, d_out, d_counts, d_stats, stream))
+
+    # -- queries named by id, over all shards (device addresses on the root device)
+    def get_codes_dev(self, d_ids, nq, d_codes, d_found=None, stream=None):
+        """vc_sharded_get_codes_dev: nq uint32 global ids -> nq * bits/8 code bytes (+ nq uint32 found words) on the root device"""
+        self._check(self._L.vc_sharded_get_codes_dev(self._h, d_ids, nq, d_codes, d_found, stream))
+
+    def search_knn_ids(self, ids, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, id_flags=0, with_stats=False):
+        """vc_sharded_search_knn_ids: numpy ids; returns like search_knn"""
+        return _search_knn_ids(self, self._L.vc_sharded_search_knn_ids, ids, k, mode, order, id_flags, with_stats)
+
+    def search_knn_ids_dev(self, d_ids, nq, k, d_out, d_counts=None, d_stats=None, mode=MODE_LINEAR, id_flags=0, stream=None):
+        """vc_sharded_search_knn_ids_dev: raw device addresses on the root device; results valid in `stream` order"""
+        self._check(self._L.vc_sharded_search_knn_ids_dev(self._h, d_ids, nq, k, mode, id_flags, d_out, d_counts, d_stats, stream))
 
     def search_radius(self, queries, radius, mode=MODE_LINEAR, cap_per_query=64):
         """vc_sharded_search_radius: list of ascending packed arrays, one per query"""

@@ -109,6 +109,9 @@ class Backend {
   virtual int get_bucket(uint32_t table, uint32_t index, uint32_t* ids, void* codes, uint32_t cap, uint32_t* n) = 0;
   virtual int search_knn(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, uint64_t* out,
                          uint32_t* counts, vc_query_stats* stats) = 0;
+  // a batch of queries named by id (vc_search_knn_ids / vc_sharded_search_knn_ids): the codes never leave HBM
+  virtual int search_knn_ids(const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, uint32_t id_flags,
+                             uint64_t* out, uint32_t* counts, vc_query_stats* stats) = 0;
 };
 
 // Owns one vc_engine (one shard / GPU).
@@ -150,6 +153,10 @@ class Engine : public Backend {
   int search_knn(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, uint64_t* out, uint32_t* counts,
                  vc_query_stats* stats) override {
     return vc_search_knn(h_, queries, nq, k, mode, order, out, counts, stats);
+  }
+  int search_knn_ids(const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, uint32_t id_flags, uint64_t* out,
+                     uint32_t* counts, vc_query_stats* stats) override {
+    return vc_search_knn_ids(h_, ids, nq, k, mode, order, id_flags, out, counts, stats);
   }
  private:
   vc_engine* h_ = nullptr;
@@ -221,6 +228,10 @@ class ShardedEngine : public Backend {
   int search_knn(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, uint64_t* out, uint32_t* counts,
                  vc_query_stats* stats) override {
     return vc_sharded_search_knn(h_, queries, nq, k, mode, order, out, counts, stats);
+  }
+  int search_knn_ids(const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, uint32_t id_flags, uint64_t* out,
+                     uint32_t* counts, vc_query_stats* stats) override {
+    return vc_sharded_search_knn_ids(h_, ids, nq, k, mode, order, id_flags, out, counts, stats);
   }
  private:
   vc_sharded* h_ = nullptr;
@@ -416,6 +427,25 @@ class image_search_client {
     std::list<std::pair<uint32_t, uint32_t> > out;
     for (const auto& r : worker_.find(code.data(), code.size(), knn, approximate)) out.push_back({r.image_id, r.dist});
     return out;
+  }
+  // The same for a BATCH of ids in one ABI call (what image_search_test.cc:112-170 replays one id at a time): one
+  // farthest-first list per id, as search_image_by_id returns it; an id that is not in the database gives an empty list
+  // instead of an exception.  The codes are gathered on the device, so 4 096 ids cost little more than one.
+  std::vector<std::list<std::pair<uint32_t, uint32_t> > > search_images_by_id(const std::vector<uint32_t>& ids, int knn,
+                                                                              bool approximate = false) {
+    std::vector<std::list<std::pair<uint32_t, uint32_t> > > all(ids.size());
+    if (ids.empty()) return all;
+    const uint32_t nq = (uint32_t)ids.size();
+    std::vector<uint64_t> out((size_t)nq * knn);
+    std::vector<uint32_t> cnt(nq);
+    e_->check(e_->search_knn_ids(ids.data(), nq, (uint32_t)knn, approximate ? VC_MODE_MIH_APPROX : VC_MODE_MIH_EXACT,
+                                 VC_ORDER_FARTHEST_FIRST, 0, out.data(), cnt.data(), nullptr));
+    for (uint32_t q = 0; q < nq; ++q)
+      for (uint32_t i = 0; i < cnt[q]; ++i) {
+        const uint64_t v = out[(size_t)q * knn + i];
+        all[q].push_back({(uint32_t)(v & 0xffffffffu), (uint32_t)(v >> 32)});
+      }
+    return all;
   }
  private:
   Backend* e_;
