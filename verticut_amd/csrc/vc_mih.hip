@@ -3788,6 +3788,14 @@ enum RadiusRoute {
   RADIUS_HOST_SHELLS,    // one probe launch per shell
   RADIUS_LINEAR_SCAN     // no index (or a radius the scan answers cheaper): the verify kernel with a fixed threshold
 };
+static const char* radius_route_name(RadiusRoute r) {
+  switch (r) {
+    case RADIUS_QUERY_KERNEL: return "query_kernel";
+    case RADIUS_STREAM: return "stream";
+    case RADIUS_HOST_SHELLS: return "host_shells";
+    default: return "linear_scan";
+  }
+}
 static RadiusRoute radius_route(const VcMihIndex* ix, bool use_mih, const RadiusPlan& rp) {
   if (!use_mih) return RADIUS_LINEAR_SCAN;
   if (ix->knobs.mih_host_loop != 0) return RADIUS_HOST_SHELLS;
@@ -3933,6 +3941,9 @@ static int radius_search_device(VcMihIndex* ix, bool use_mih, const uint64_t* d_
       MIH_CHECK(hipMalloc((void**)&wk->d_ring, (size_t)TQ * cap * 8));
       wk->cap = cap;
     }
+    if (knobs && knobs->mih_trace)   // VC_MIH_TRACE: one line per attempt on what was decided (a repeat shows the grown ring)
+      fprintf(stderr, "[vc_mih] radius search: R=%u probes=%llu cap=%u route=%s\n", radius, (unsigned long long)rp.probes, cap,
+              radius_route_name(route));
     RadiusSearch c{ix, d_cols, stride, n, W, id_base, n_cu, knobs, d_q, radius, cap, hs, TQ, rp, aux, wk, s, err, MihState{}, MihLists{}};
     if (nq == 0) MIH_CHECK(hipMemsetAsync(aux.tot, 0, RADIUS_TOT_BYTES, s));   // (else the first tile's offsets kernel starts the totals over)
     for (uint32_t q0 = 0; q0 < nq; q0 += TQ) {
