@@ -179,8 +179,20 @@ int vc_get_code(vc_engine* e, uint32_t id, void* out);
 
 /* ---- index -------------------------------------------------------------------------------
  * replaces: build_hash_tables.cc (bucket contents, rule a12) + generate_bitmap.cc:105-114
- * (bit v of table t set iff bucket (t,v) non-empty).  Must follow the last vc_add_*. */
+ * (bit v of table t set iff bucket (t,v) non-empty).  Must follow the last vc_add_* (or be brought up to
+ * date by vc_update_index). */
 int vc_build_index(vc_engine* e);
+/* Brings the MIH index up to date with the records appended since it was built, loaded or last updated
+ * (build_hash_tables.cc:40-70: get bucket, append, put).  The result is BIT FOR BIT the index
+ * vc_build_index would build from all resident records.  No index yet -> behaves as vc_build_index;
+ * index already current -> VC_OK, nothing done.
+ * Appended ids exceed every indexed id, so each new entry goes to the END of its key's bucket: per table the
+ * new (key, id) pairs are sorted and merged into the table in one streaming pass; no indexed entry is sorted
+ * again.  vc_add_codes / vc_add_synthetic / vc_load_code_file therefore KEEP an existing index and mark it
+ * stale: until the next vc_update_index / vc_build_index / vc_load_index every call that needs an index
+ * returns VC_ERR_STATE exactly as if there were none -- only its device memory stays allocated.
+ * If an update fails, the handle is left with that stale index or with none; vc_build_index works after either. */
+int vc_update_index(vc_engine* e);
 /* HashIndex{table_id,index} -> Image_List get (search_worker.cc:224-246, base_proxy.h:18).
  * Writes up to cap (id, code) pairs in append (= id) order; *n = bucket length.
  * Returns VC_OK (PROXY_FOUND) or VC_NOT_FOUND.  ids / codes may be NULL. */
@@ -341,6 +353,9 @@ int vc_sharded_add_codes(vc_sharded* h, const void* codes, uint64_t n);
 int vc_sharded_add_synthetic(vc_sharded* h, uint64_t n, uint64_t seed, uint32_t kind, uint32_t n_centres, uint32_t max_flips);
 int vc_sharded_size(const vc_sharded* h, uint64_t* n);
 int vc_sharded_build_index(vc_sharded* h);
+/* vc_update_index per non-empty shard: update if it has an index, else build.  Appended ids fill the id-range
+ * shards in order, so only the shard the store ended in and those after it have work to do. */
+int vc_sharded_update_index(vc_sharded* h);
 /* ID -> BinaryCode and HashIndex -> Image_List over all shards (a bucket = the shards' buckets in id order) */
 int vc_sharded_get_code(vc_sharded* h, uint32_t id, void* out);
 int vc_sharded_get_bucket(vc_sharded* h, uint32_t table, uint32_t index, uint32_t* ids, void* codes, uint32_t cap, uint32_t* n);

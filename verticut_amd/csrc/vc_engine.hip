@@ -68,6 +68,7 @@ struct vc_engine {
   vc_timing last{};
 
   VcMihIndex* mih = nullptr;
+  uint64_t n_indexed = 0;   // records the index covers; n_indexed < n: the index is STALE (kept for vc_update_index, served to no one)
   VcRadiusWork radius_work;
   std::string err;
 };
@@ -151,11 +152,20 @@ void read_knobs(VcKnobs* k) {
   k->stream_trace = getenv("VC_STREAM_TRACE") != nullptr;
   if (const char* v = getenv("VC_MIH_GS_CAP")) k->gs_cap = (uint32_t)std::max(0, atoi(v));
   k->gs_trace = getenv("VC_MIH_GS_TRACE") != nullptr;
+  if (const char* v = getenv("VC_MIH_UPDATE")) k->mih_update = atoi(v);
 }
 
 static int bind_device(vc_engine* e) {
   VC_HIP(e, hipSetDevice(e->device));
   return VC_OK;
+}
+// the index a call may consume: the built one while it covers every resident record, else none.  A stale index (records were added
+// since) stays allocated for vc_update_index but every consumer sees "no index", exactly as if the add had freed it.
+static VcMihIndex* live_index(const vc_engine* e) { return e->mih && e->n_indexed == e->n ? e->mih : nullptr; }
+static void drop_index(vc_engine* e) {
+  if (e->mih) vc_mih_free(e->mih);
+  e->mih = nullptr;
+  e->n_indexed = 0;
 }
 static hipStream_t caller_stream(const vc_engine* e, void* stream) {   // NULL = the HIP null stream
   return stream == VC_STREAM_OWN ? e->own_stream : (hipStream_t)stream;
@@ -351,8 +361,7 @@ int vc_add_codes(vc_engine* e, const void* codes, uint64_t n) {
     VC_HIP(e, vc_launch_rows_to_cols((const uint64_t*)e->d_stage, e->d_cols, e->stride, e->W, e->n + off, cnt, e->stream));
     VC_HIP(e, hipStreamSynchronize(e->stream));
   }
-  e->n += n;
-  if (e->mih) { vc_mih_free(e->mih); e->mih = nullptr; }
+  e->n += n;   // (an index, if any, is stale from here on: live_index)
   return VC_OK;
 }
 
@@ -363,8 +372,7 @@ int vc_add_synthetic(vc_engine* e, uint64_t n, uint64_t seed, uint32_t kind, uin
   if (rc) return rc;
   VC_HIP(e, vc_launch_fill_synth(e->d_cols, e->stride, e->W, e->n, n, (uint64_t)e->cfg.id_base + e->n, seed, kind, n_centres, max_flips, e->stream));
   VC_HIP(e, hipStreamSynchronize(e->stream));
-  e->n += n;
-  if (e->mih) { vc_mih_free(e->mih); e->mih = nullptr; }
+  e->n += n;   // (an index, if any, is stale from here on: live_index)
   return VC_OK;
 }
 
@@ -418,7 +426,7 @@ int vc_save_code_file(vc_engine* e, const char* path) {
 
 int vc_write_bitmap_file(vc_engine* e, uint32_t table, const char* path) {
   if (!e || !path) return VC_ERR_INVALID;
-  if (!e->mih) return fail(e, VC_ERR_STATE, "no index built");
+  if (!live_index(e)) return fail(e, VC_ERR_STATE, "no index built");
   if (table >= e->m) return VC_ERR_INVALID;
   int rc = bind_device(e);
   if (rc) return rc;
@@ -429,7 +437,7 @@ int vc_write_bitmap_file(vc_engine* e, uint32_t table, const char* path) {
   std::vector<uint32_t> buf((size_t)std::min(words, batch));
   for (uint64_t off = 0; off < words && rc == VC_OK; off += batch) {
     const uint64_t cnt = std::min(batch, words - off);
-    rc = vc_mih_bitmap_read(e->mih, table, off, cnt, buf.data(), e->stream, &e->err);
+    rc = vc_mih_bitmap_read(live_index(e), table, off, cnt, buf.data(), e->stream, &e->err);
     if (rc == VC_OK && fwrite(buf.data(), 4, cnt, fh) != cnt) rc = fail(e, VC_ERR_INVALID, "short write to %s", path);
   }
   fclose(fh);
@@ -442,7 +450,7 @@ int vc_write_bitmap_file(vc_engine* e, uint32_t table, const char* path) {
 int vc_read_bitmap_file(vc_engine* e, uint32_t table, const char* path, uint64_t* n_mismatch_words) {
   if (!e || !path) return VC_ERR_INVALID;
   if (n_mismatch_words) *n_mismatch_words = 0;
-  if (!e->mih) return fail(e, VC_ERR_STATE, "no index built");
+  if (!live_index(e)) return fail(e, VC_ERR_STATE, "no index built");
   if (table >= e->m) return VC_ERR_INVALID;
   int rc = bind_device(e);
   if (rc) return rc;
@@ -455,7 +463,7 @@ int vc_read_bitmap_file(vc_engine* e, uint32_t table, const char* path, uint64_t
   for (uint64_t off = 0; off < words && rc == VC_OK; off += batch) {
     const uint64_t cnt = std::min(batch, words - off);
     if (fread(file_w.data(), 4, cnt, fh) != cnt) { rc = fail(e, VC_ERR_INVALID, "%s is shorter than 2^%u bits", path, e->sbits); break; }
-    rc = vc_mih_bitmap_read(e->mih, table, off, cnt, dev_w.data(), e->stream, &e->err);
+    rc = vc_mih_bitmap_read(live_index(e), table, off, cnt, dev_w.data(), e->stream, &e->err);
     for (uint64_t i = 0; i < cnt && rc == VC_OK; ++i) bad += file_w[i] != dev_w[i];
   }
   if (rc == VC_OK && fgetc(fh) != EOF) rc = fail(e, VC_ERR_INVALID, "%s is longer than 2^%u bits", path, e->sbits);
@@ -467,10 +475,10 @@ int vc_read_bitmap_file(vc_engine* e, uint32_t table, const char* path, uint64_t
 
 int vc_save_index(vc_engine* e, const char* path) {
   if (!e || !path) return VC_ERR_INVALID;
-  if (!e->mih) return fail(e, VC_ERR_STATE, "no index built");
+  if (!live_index(e)) return fail(e, VC_ERR_STATE, "no index built");
   int rc = bind_device(e);
   if (rc) return rc;
-  return vc_mih_save(e->mih, e->d_cols, e->stride, path, e->stream, &e->err);
+  return vc_mih_save(live_index(e), e->d_cols, e->stride, path, e->stream, &e->err);
 }
 
 int vc_load_index(vc_engine* e, const char* path) {
@@ -478,9 +486,11 @@ int vc_load_index(vc_engine* e, const char* path) {
   if (e->m == 0) return fail(e, VC_ERR_STATE, "engine was created with n_tables = 0 (linear only)");
   int rc = bind_device(e);
   if (rc) return rc;
-  if (e->mih) { vc_mih_free(e->mih); e->mih = nullptr; }
-  return vc_mih_load(&e->mih, path, e->d_cols, e->stride, e->n, e->W, e->m, e->sbits, e->cfg.id_base, e->cfg.flags, e->n_cu, e->cap,
-                     e->knobs, e->stream, &e->err);
+  drop_index(e);
+  rc = vc_mih_load(&e->mih, path, e->d_cols, e->stride, e->n, e->W, e->m, e->sbits, e->cfg.id_base, e->cfg.flags, e->n_cu, e->cap,
+                   e->knobs, e->stream, &e->err);
+  if (rc == VC_OK) e->n_indexed = e->n;
+  return rc;
 }
 
 int vc_get_code(vc_engine* e, uint32_t id, void* out) {
@@ -947,7 +957,7 @@ static int check_knn_args(vc_engine* e, const void* q, uint32_t nq, uint32_t k, 
   if (!e || !q || nq == 0) return VC_ERR_INVALID;
   if (k == 0 || k > VC_MAX_K) return fail(e, VC_ERR_INVALID, "k must be in 1..%u", VC_MAX_K);
   if (mode > VC_MODE_MIH_APPROX) return fail(e, VC_ERR_INVALID, "unknown mode %u", mode);
-  if (mode != VC_MODE_LINEAR && !e->mih) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first (n_tables=%u)", e->m);
+  if (mode != VC_MODE_LINEAR && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first (n_tables=%u)", e->m);
   return VC_OK;
 }
 
@@ -978,7 +988,7 @@ int vc_engine_view(vc_engine* e, VcEngineView* v) {
   v->sbits = e->sbits;
   v->id_base = e->cfg.id_base;
   v->n_cu = e->n_cu;
-  v->reach =e->mih ? vc_mih_knn_reach(e->mih) : 0;
+  v->reach = live_index(e) ? vc_mih_knn_reach(live_index(e)) : 0;
   return VC_OK;
 }
 
@@ -991,7 +1001,7 @@ int vc_engine_knn_capped(vc_engine* e, const void* d_queries, uint32_t nq, uint3
   if ((rc = bind_device(e))) return rc;
   const StreamCall call(e, s);
   const VcMihScanFallback fb{mih_scan_fallback, e, e->n_cu};
-  return vc_mih_search(e->mih, e->d_cols, e->stride, e->n, (const uint64_t*)d_queries, nq, k, mode == VC_MODE_MIH_APPROX, d_out, d_counts, nullptr,
+  return vc_mih_search(live_index(e), e->d_cols, e->stride, e->n, (const uint64_t*)d_queries, nq, k, mode == VC_MODE_MIH_APPROX, d_out, d_counts, nullptr,
                        e->stream, &e->err, &fb, d_stats, r_cap);
 }
 
@@ -999,12 +1009,12 @@ int vc_engine_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint3
                          uint64_t* d_offsets, uint64_t* total, hipStream_t s) {
   if (!e || !d_queries || !d_offsets || !total || (!d_out && out_cap) || nq == 0) return VC_ERR_INVALID;
   if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "radius search: mode must be LINEAR or MIH_EXACT");
-  if (mode == VC_MODE_MIH_EXACT && !e->mih) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
+  if (mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
   int rc = bind_device(e);
   if (rc) return rc;
   const StreamCall call(e, s);
   *total = 0;
-  return vc_radius_search(e->mih, mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs,
+  return vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs,
                           (const uint64_t*)d_queries, nq, radius, d_out, out_cap, d_offsets, true, &e->radius_work, e->stream, &e->err, total);
 }
 
@@ -1020,7 +1030,7 @@ static int knn_dev_run(vc_engine* e, const void* d_queries, uint32_t nq, uint32_
     }
   } else {
     const VcMihScanFallback fb{mih_scan_fallback, e, e->n_cu};
-    rc = vc_mih_search(e->mih, e->d_cols, e->stride, e->n, (const uint64_t*)d_queries, nq, k, mode == VC_MODE_MIH_APPROX,
+    rc = vc_mih_search(live_index(e), e->d_cols, e->stride, e->n, (const uint64_t*)d_queries, nq, k, mode == VC_MODE_MIH_APPROX,
                        d_out, cnt, nullptr, e->stream, &e->err, &fb, d_stats);
   }
   return rc;
@@ -1201,7 +1211,7 @@ int vc_search_knn(vc_engine* e, const void* queries, uint32_t nq, uint32_t k, ui
   } else {
     if (stats) st.resize(nq);      // (the statistics cost four read-backs and a wait per launch: only when asked for)
     const VcMihScanFallback fb{mih_scan_fallback, e, e->n_cu};
-    rc = vc_mih_search(e->mih, e->d_cols, e->stride, e->n, e->d_q, nq, k, mode == VC_MODE_MIH_APPROX, e->d_out,
+    rc = vc_mih_search(live_index(e), e->d_cols, e->stride, e->n, e->d_q, nq, k, mode == VC_MODE_MIH_APPROX, e->d_out,
                        e->d_cnt, stats ? st.data() : nullptr, e->stream, &e->err, &fb);
   }
   timing_end(e);
@@ -1274,19 +1284,39 @@ int vc_build_index(vc_engine* e) {
   if (e->m == 0) return fail(e, VC_ERR_STATE, "engine was created with n_tables = 0 (linear only)");
   int rc = bind_device(e);
   if (rc) return rc;
-  if (e->mih) { vc_mih_free(e->mih); e->mih = nullptr; }
-  return vc_mih_build(&e->mih, e->d_cols, e->stride, e->n, e->W, e->m, e->sbits, e->cfg.id_base, e->cfg.flags, e->n_cu,
-                      e->cap, e->knobs, e->stream, &e->err);
+  drop_index(e);
+  rc = vc_mih_build(&e->mih, e->d_cols, e->stride, e->n, e->W, e->m, e->sbits, e->cfg.id_base, e->cfg.flags, e->n_cu,
+                    e->cap, e->knobs, e->stream, &e->err);
+  if (rc == VC_OK) e->n_indexed = e->n;
+  return rc;
+}
+
+// build_hash_tables.cc:40-70 (get bucket, append, put): the records added since the index was built, loaded or last updated are
+// appended to their buckets -- the stale index is merged with them (vc_mih_update), not rebuilt
+int vc_update_index(vc_engine* e) {
+  if (!e) return VC_ERR_INVALID;
+  if (e->m == 0) return fail(e, VC_ERR_STATE, "engine was created with n_tables = 0 (linear only)");
+  if (!e->mih) return vc_build_index(e);
+  int rc = bind_device(e);
+  if (rc) return rc;
+  if (e->knobs.mih_update == 0 && e->n_indexed != e->n) {   // A/B and test route: the full rebuild
+    const uint64_t added = e->n - e->n_indexed;
+    if ((rc = vc_build_index(e)) == VC_OK) vc_mih_update_trace(e->mih, added, "rebuild", "0");
+    return rc;
+  }
+  rc = vc_mih_update(&e->mih, e->d_cols, e->stride, e->n, e->stream, &e->err);
+  e->n_indexed = e->mih ? vc_mih_records(e->mih) : 0;   // (a failed update leaves the old stale index, or none)
+  return rc;
 }
 
 int vc_get_bucket(vc_engine* e, uint32_t table, uint32_t index, uint32_t* ids, void* codes, uint32_t cap, uint32_t* n) {
   if (!e || !n) return VC_ERR_INVALID;
-  if (!e->mih) return fail(e, VC_ERR_STATE, "no index built");
+  if (!live_index(e)) return fail(e, VC_ERR_STATE, "no index built");
   if (table >= e->m) return fail(e, VC_ERR_INVALID, "table %u >= n_tables %u", table, e->m);
   int rc = bind_device(e);
   if (rc) return rc;
   std::vector<uint32_t> local;
-  rc = vc_mih_bucket(e->mih, table, index, &local, e->stream, &e->err);
+  rc = vc_mih_bucket(live_index(e), table, index, &local, e->stream, &e->err);
   if (rc < 0) return rc;
   *n = (uint32_t)local.size();
   if (local.empty()) return VC_NOT_FOUND;
@@ -1307,34 +1337,34 @@ int vc_get_bucket(vc_engine* e, uint32_t table, uint32_t index, uint32_t* ids, v
 
 int vc_bitmap_test(vc_engine* e, uint32_t table, uint32_t index, int* bit) {
   if (!e || !bit) return VC_ERR_INVALID;
-  if (!e->mih) return fail(e, VC_ERR_STATE, "no index built");
+  if (!live_index(e)) return fail(e, VC_ERR_STATE, "no index built");
   if (table >= e->m) return VC_ERR_INVALID;
   int rc = bind_device(e);
   if (rc) return rc;
-  return vc_mih_bitmap_test(e->mih, table, index, bit, e->stream, &e->err);
+  return vc_mih_bitmap_test(live_index(e), table, index, bit, e->stream, &e->err);
 }
 
 int vc_bitmap_read(vc_engine* e, uint32_t table, uint64_t word_off, uint64_t n_words, uint32_t* out) {
   if (!e || !out) return VC_ERR_INVALID;
-  if (!e->mih) return fail(e, VC_ERR_STATE, "no index built");
+  if (!live_index(e)) return fail(e, VC_ERR_STATE, "no index built");
   if (table >= e->m) return VC_ERR_INVALID;
   int rc = bind_device(e);
   if (rc) return rc;
-  return vc_mih_bitmap_read(e->mih, table, word_off, n_words, out, e->stream, &e->err);
+  return vc_mih_bitmap_read(live_index(e), table, word_off, n_words, out, e->stream, &e->err);
 }
 
 int vc_search_radius(vc_engine* e, const void* queries, uint32_t nq, uint32_t radius, uint32_t mode, uint64_t* out,
                      uint64_t out_cap, uint64_t* out_offsets) {
   if (!e || !queries || !out_offsets || nq == 0) return VC_ERR_INVALID;
   if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "radius search: mode must be LINEAR or MIH_EXACT");
-  if (mode == VC_MODE_MIH_EXACT && !e->mih) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
+  if (mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
   int rc = bind_device(e);
   if (rc) return rc;
   const size_t qbytes = (size_t)nq * (e->bits / 8);
   if ((rc = grow(e, &e->d_q, &e->q_bytes, qbytes))) return rc;
   VC_HIP(e, hipMemcpyAsync(e->d_q, queries, qbytes, hipMemcpyHostToDevice, e->stream));
   timing_begin(e);
-  rc = vc_radius_search(e->mih, mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs,
+  rc = vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs,
                         e->d_q, nq, radius, out, out_cap, out_offsets, false, &e->radius_work, e->stream, &e->err);
   timing_end(e);
   return rc;
@@ -1344,11 +1374,11 @@ int vc_search_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint3
                          uint64_t out_cap, uint64_t* d_offsets, void* stream) {
   if (!e || !d_queries || !d_offsets || (!d_out && out_cap) || nq == 0) return VC_ERR_INVALID;
   if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "radius search: mode must be LINEAR or MIH_EXACT");
-  if (mode == VC_MODE_MIH_EXACT && !e->mih) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
+  if (mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
   int rc = bind_device(e);
   if (rc) return rc;
   const StreamCall call(e, caller_stream(e, stream));
-  return vc_radius_search(e->mih, mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs,
+  return vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs,
                           (const uint64_t*)d_queries, nq, radius, d_out, out_cap, d_offsets, true, &e->radius_work, e->stream, &e->err);
 }
 

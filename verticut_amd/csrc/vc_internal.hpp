@@ -39,6 +39,7 @@ struct VcKnobs {
   bool stream_trace = false;                  // VC_STREAM_TRACE (dev): per-block start / look-up / end times of mih_bucket_stream_kernel on stderr
   uint32_t gs_cap = 1;                        // VC_MIH_GS_CAP (dev): cap of the sharded global stop's first round
   bool gs_trace = false;                      // VC_MIH_GS_TRACE (dev): per-round wall times of the sharded global stop on stderr
+  int mih_update = 1;                         // VC_MIH_UPDATE=0: vc_update_index rebuilds the whole index (A/B runs, tests) instead of merging
   bool scan_shape_trace = false;              // VC_SCAN_SHAPE_TRACE=1 (dev/tests): every verify launch names the instantiation it launched on stderr
 };
 void read_knobs(VcKnobs* k);   // vc_engine.hip: the one place that reads the environment (once per engine / sharded handle)

@@ -135,12 +135,13 @@ __global__ void __launch_bounds__(256) mih_bent_kernel(const uint64_t* __restric
   }
 }
 
-__global__ void __launch_bounds__(256) mih_keys_kernel(const uint64_t* __restrict__ col, uint64_t n, uint32_t shift,
+// keys and local ids of the n records from `first` on (a build: first = 0; an update: the records the index does not cover yet)
+__global__ void __launch_bounds__(256) mih_keys_kernel(const uint64_t* __restrict__ col, uint64_t first, uint64_t n, uint32_t shift,
                                                        uint32_t mask, uint32_t* __restrict__ keys,
                                                        uint32_t* __restrict__ vals) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    keys[i] = (uint32_t)(col[i] >> shift) & mask;
-    vals[i] = (uint32_t)i;
+    keys[i] = (uint32_t)(col[first + i] >> shift) & mask;
+    vals[i] = (uint32_t)(first + i);
   }
 }
 
@@ -272,6 +273,182 @@ __global__ void __launch_bounds__(256) mih_ranked_offsets_kernel(const uint32_t*
     if (p == 0 || keys[p - 1] != key) offsets[vc_rank32(bitmap, blockrank, key)] = (uint32_t)p;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) offsets[n_unique] = (uint32_t)n;
+}
+
+// ------------------------------------------------------------------------------------------
+// index update (vc_mih_update): the nd new (key, id) pairs of a table, sorted by key, are merged into its arrays
+// ------------------------------------------------------------------------------------------
+// first index in [0, n) of the ascending a[] whose element is >= x (n if none)
+__device__ __forceinline__ uint64_t mu_lower_bound(const uint32_t* __restrict__ a, uint64_t n, uint32_t x) {
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (a[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+// ... whose element is > x
+__device__ __forceinline__ uint64_t mu_upper_bound(const uint32_t* __restrict__ a, uint64_t n, uint32_t x) {
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (a[mid] <= x) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// ins[j]: END of key[j]'s bucket in the OLD ids[] (where it would start when it has none) -- new entry j lands at ins[j] + j.
+// Ranked tables also note the key's old rank and flag the first entry of every key that has no old bucket (a NEW bucket).
+__global__ void __launch_bounds__(256) mih_update_ins_kernel(const uint32_t* __restrict__ keys, uint64_t nd, VcTableView old, uint32_t sbits,
+                                                             uint32_t* __restrict__ ins, uint32_t* __restrict__ rank,
+                                                             uint32_t* __restrict__ newflag) {
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nd; j += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t key = keys[j];
+    if (sbits < 32) {
+      ins[j] = old.offsets[key + 1];
+    } else {
+      const uint32_t bit = vc_bit_test(old.bitmap, key) ? 1u : 0u;
+      const uint32_t r = vc_rank32(old.bitmap, old.blockrank, key);
+      ins[j] = old.offsets[r + bit];
+      rank[j] = r;
+      newflag[j] = (!bit && (j == 0 || keys[j - 1] != key)) ? 1u : 0u;
+    }
+  }
+}
+
+// the new buckets of a ranked table in key order: {old rank of the key, final position of its first entry}
+__global__ void __launch_bounds__(256) mih_update_newbuckets_kernel(const uint32_t* __restrict__ newflag, const uint32_t* __restrict__ slot,
+                                                                    const uint32_t* __restrict__ rank, const uint32_t* __restrict__ ins,
+                                                                    uint64_t nd, uint32_t* __restrict__ nb_rank, uint32_t* __restrict__ nb_pos) {
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nd; j += (uint64_t)gridDim.x * blockDim.x) {
+    if (!newflag[j]) continue;
+    nb_rank[slot[j]] = rank[j];
+    nb_pos[slot[j]] = ins[j] + (uint32_t)j;
+  }
+}
+
+// occupancy bits of the new keys (generate_bitmap.cc:54-58 set_idx), one atomic per key run
+__global__ void __launch_bounds__(256) mih_update_bits_kernel(const uint32_t* __restrict__ keys, uint64_t nd, uint32_t* __restrict__ bitmap) {
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nd; j += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t key = keys[j];
+    if (j == 0 || keys[j - 1] != key) atomicOr(&bitmap[key >> 5], 1u << (key & 31));
+  }
+}
+
+// direct tables: offsets[v] += new entries with a key below v, v = 0 .. 2^s
+__global__ void __launch_bounds__(256) mih_update_direct_offsets_kernel(const uint32_t* __restrict__ keys, uint64_t nd, uint32_t len,
+                                                                        uint32_t* __restrict__ offsets) {
+  for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < len; v += gridDim.x * blockDim.x)
+    offsets[v] += (uint32_t)mu_lower_bound(keys, nd, v);   // (keys < 2^s: every one is below v = 2^s)
+}
+
+// The merge.  A (na old elements, order kept) and B (nb new ones, ins[] ascending): A[p] -> p + #{j : ins[j] <= p}, B[j] -> ins[j] + j.
+// Tiled over the OUTPUT: a block takes a contiguous run of MU_TILE-element tiles, binary-searches ins[] ONCE for the new entries
+// before its first output, and then streams -- per tile it stages the final positions of the (at most MU_TILE) new entries that
+// fall into it in LDS, and every output element finds there whether it is a new entry or which old one it is.  An element is
+// PIECES values of type V; consecutive threads move consecutive values, so loads and stores are coalesced at the width of V.
+#define MU_BLK 256u
+#define MU_TILE 2048u
+struct MuIdsSrc {   // ids[]
+  typedef uint32_t V;
+  static constexpr uint32_t PIECES = 1;
+  const uint32_t* old_ids;
+  const uint32_t* new_ids;
+  __device__ __forceinline__ V old(uint64_t p, uint32_t) const { return __builtin_nontemporal_load(old_ids + p); }
+  __device__ __forceinline__ V fresh(uint64_t j, uint32_t) const { return new_ids[j]; }
+};
+struct MuOffsetsSrc {   // ranked offsets[]: A = the old offsets (each moved up by the new entries with a smaller key), B = the new buckets
+  typedef uint32_t V;
+  static constexpr uint32_t PIECES = 1;
+  const uint32_t* old_offsets;
+  const uint32_t* ins;      // of the nd new entries
+  uint64_t nd;
+  const uint32_t* nb_pos;
+  __device__ __forceinline__ V old(uint64_t p, uint32_t) const {
+    const uint32_t x = old_offsets[p];
+    return x + (uint32_t)mu_upper_bound(ins, nd, x);   // old buckets are not empty: ins[j] <= x exactly for the smaller keys
+  }
+  __device__ __forceinline__ V fresh(uint64_t j, uint32_t) const { return nb_pos[j]; }
+};
+template <int W>
+struct MuBentSrc {   // {id, 0, code} records (mih_bent_kernel's layout), 16 W bytes each; a new entry's record comes from the columns
+  typedef uint4 V;
+  static constexpr uint32_t PIECES = W;
+  const uint4* old_bent;
+  const uint32_t* new_ids;
+  const uint64_t* cols;
+  uint64_t stride;
+  __device__ __forceinline__ V old(uint64_t p, uint32_t e) const { return old_bent[p * W + e]; }
+  __device__ __forceinline__ V fresh(uint64_t j, uint32_t e) const {
+    const uint32_t id = new_ids[j];
+    const uint64_t c = cols[(uint64_t)e * stride + id];
+    return e == 0 ? make_uint4(id, 0u, (uint32_t)c, (uint32_t)(c >> 32)) : make_uint4((uint32_t)c, (uint32_t)(c >> 32), 0u, 0u);
+  }
+};
+
+template <class Src>
+__global__ void __launch_bounds__(MU_BLK) mih_update_merge_kernel(const Src src, const uint32_t* __restrict__ ins, uint64_t nb, uint64_t na,
+                                                                  typename Src::V* __restrict__ out) {
+  typedef typename Src::V V;
+  constexpr uint32_t PIECES = Src::PIECES;
+  __shared__ uint32_t s_fin[MU_TILE];   // final positions ins[j] + j of the new entries from jb on (ascending; 0xFFFFFFFF = none: n_out < 2^32)
+  const uint64_t n_out = na + nb;
+  const uint64_t ntiles = (n_out + MU_TILE - 1) / MU_TILE;
+  const uint64_t per = (ntiles + gridDim.x - 1) / gridDim.x;
+  const uint64_t t0 = (uint64_t)blockIdx.x * per, t1 = min(t0 + per, ntiles);
+  if (t0 >= t1) return;
+  uint64_t jb;   // new entries placed before the tile's first output
+  {
+    const uint64_t first = t0 * MU_TILE;
+    uint64_t lo = 0, hi = nb;
+    while (lo < hi) {
+      const uint64_t mid = (lo + hi) >> 1;
+      if ((uint64_t)ins[mid] + mid < first) lo = mid + 1; else hi = mid;
+    }
+    jb = lo;
+  }
+  for (uint64_t t = t0; t < t1; ++t) {
+    const uint64_t o0 = t * MU_TILE, o1 = min(o0 + MU_TILE, n_out);
+    uint32_t staged = 0;   // a tile holds at most o1 - o0 new entries (each takes an output slot), usually far fewer: staged in steps of MU_BLK
+    for (;;) {
+      __syncthreads();     // (the previous tile's readers are done with s_fin)
+      const uint64_t j = jb + staged + threadIdx.x;
+      s_fin[staged + threadIdx.x] = j < nb ? ins[j] + (uint32_t)j : 0xFFFFFFFFu;
+      __syncthreads();
+      const uint32_t last = s_fin[staged + MU_BLK - 1];
+      staged += MU_BLK;
+      if ((uint64_t)last >= o1 || staged >= MU_TILE) break;
+    }
+    uint32_t nbt;   // new entries of this tile: staged positions below o1
+    {
+      uint32_t lo = 0, hi = staged;
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((uint64_t)s_fin[mid] < o1) lo = mid + 1; else hi = mid;
+      }
+      nbt = lo;
+    }
+    const uint32_t npieces = (uint32_t)(o1 - o0) * PIECES;
+#pragma unroll 4
+    for (uint32_t q = threadIdx.x; q < npieces; q += MU_BLK) {
+      const uint32_t el = q / PIECES, e = q - el * PIECES;
+      const uint32_t o = (uint32_t)(o0 + el);
+      uint32_t lo = 0, hi = nbt;   // new entries of the tile placed before output o
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (s_fin[mid] < o) lo = mid + 1; else hi = mid;
+      }
+      V v{};
+      if (lo < nbt && s_fin[lo] == o) {
+        v = src.fresh(jb + lo, e);
+      } else {
+        const uint64_t p = (uint64_t)o - (jb + lo);
+        if (p < na) v = src.old(p, e);   // (always, for insert points within [0, na])
+      }
+      out[(uint64_t)o * PIECES + e] = v;
+    }
+    jb += nbt;
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2717,7 +2894,7 @@ int vc_mih_build(VcMihIndex** out, const uint64_t* d_cols, uint64_t stride, uint
       uint32_t* kb[2] = {k_in, k_out};
       uint32_t* vb[2] = {v_in, ids};
       if ((passes & 1u) == 0) { std::swap(kb[0], kb[1]); std::swap(vb[0], vb[1]); }
-      hipLaunchKernelGGL(mih_keys_kernel, dim3(grid_for(n, n_cu)), dim3(256), 0, s, d_cols + (uint64_t)(bitpos >> 6) * stride, n,
+      hipLaunchKernelGGL(mih_keys_kernel, dim3(grid_for(n, n_cu)), dim3(256), 0, s, d_cols + (uint64_t)(bitpos >> 6) * stride, (uint64_t)0, n,
                          bitpos & 63, mask, kb[0], vb[0]);
       MIH_CHECK(hipGetLastError());
       MIH_CHECK(vc_radix_sort_pairs(kb, vb, n, sbits, d_temp, s));   // result in pair (passes & 1) = (k_out, ids)
@@ -2760,6 +2937,207 @@ int vc_mih_build(VcMihIndex** out, const uint64_t* d_cols, uint64_t stride, uint
     ix->h_tables[t] = tv;
   }
   return publish_index(std::move(ix), out, "built", s, err);
+}
+
+// ---- index update -------------------------------------------------------------------------------------------
+uint64_t vc_mih_records(const VcMihIndex* ix) { return ix->n; }
+
+void vc_mih_update_trace(const VcMihIndex* ix, uint64_t added, const char* route, const char* bent_route) {
+  if (!ix->knobs.mih_trace) return;
+  bool bcodes = ix->m != 0, bent = ix->m != 0, lines = ix->m != 0;
+  for (const VcTableView& tv : ix->h_tables) { bcodes &= tv.bcodes != nullptr; bent &= tv.bent != nullptr; lines &= tv.lines != nullptr; }
+  if (!bent_route) bent_route = bent ? "gather" : "0";
+  fprintf(stderr, "[vc_mih] index updated: n=%llu added=%llu route=%s bent=%s bcodes=%d lines=%d\n", (unsigned long long)ix->n,
+          (unsigned long long)added, route, bent_route, (int)bcodes, (int)lines);
+}
+
+// an array of the index is given back: out of allocs, freed (hipFree waits for the kernels still reading it)
+static void free_alloc(VcMihIndex* ix, const void* p) {
+  if (!p) return;
+  auto it = std::find(ix->allocs.begin(), ix->allocs.end(), p);
+  if (it != ix->allocs.end()) ix->allocs.erase(it);
+  (void)hipFree(const_cast<void*>(p));
+}
+
+// device bytes a table's arrays hold (what an update gives back before it is done: the policy counts them as free, as a build would find them)
+static uint64_t table_bytes(const VcMihIndex* ix, const VcTableView& tv) {
+  const uint64_t n = ix->n, bm = std::max<uint64_t>((1ull << ix->sbits) / 32, 8) * 4;
+  uint64_t b = n * 4 + bm;
+  if (ix->sbits == 32) b += ((uint64_t)tv.n_unique + 1) * 4 + (1ull << 26) + (tv.blockoff ? ((1ull << 24) + 1) * 8 : 0) + (tv.lines ? (uint64_t)MIH_NLINES * 64 : 0);
+  else b += ((1ull << ix->sbits) + 1) * 4;
+  if (tv.bcodes) b += n * ix->W * 8;
+  if (tv.bent) b += n * 16 * ix->W;
+  return b;
+}
+
+template <class Src>
+static hipError_t launch_merge(const Src& src, const uint32_t* ins, uint64_t nb, uint64_t na, typename Src::V* out, uint32_t n_cu, hipStream_t s) {
+  const uint64_t ntiles = (na + nb + MU_TILE - 1) / MU_TILE;
+  if (!ntiles) return hipSuccess;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)n_cu * 8);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(mih_update_merge_kernel<Src>), dim3(grid), dim3(MU_BLK), 0, s, src, ins, nb, na, out);
+  return hipGetLastError();
+}
+
+// device scratch of an update, all of it sized by the number of new records nd (scan_in: the 2^24 block counts of a ranked table)
+struct UpdateScratch {
+  uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr};   // the sort's ping-pong pairs
+  uint32_t *temp = nullptr, *scan_in = nullptr;
+  uint32_t* ins = nullptr;                                                  // insert points
+  uint32_t *rank = nullptr, *flag = nullptr, *slot = nullptr, *nb_rank = nullptr, *nb_pos = nullptr;   // ranked tables: the new buckets
+};
+struct UpdateOutcome {
+  bool touched = false;                      // something the index owns has been changed: a failure now frees the index
+  int bent_merged = 0, bent_gathered = 0;    // tables whose {id, code} records were merged / gathered again
+};
+
+// one table of an update
+static int update_table(VcMihIndex* ix, uint32_t t, const MihMemPolicy& pol, const uint64_t* d_cols, uint64_t stride, uint64_t n0, uint64_t n,
+                        const UpdateScratch& sc, UpdateOutcome* oc, hipStream_t s, std::string* err) {
+  const uint32_t sbits = ix->sbits, W = ix->W, n_cu = ix->n_cu;
+  const uint64_t nd = n - n0, nkeyspace = 1ull << sbits;
+  const uint32_t mask = sbits == 32 ? 0xFFFFFFFFu : (uint32_t)(nkeyspace - 1);
+  const uint32_t bitpos = t * sbits;
+  VcTableView tv = ix->h_tables[t];
+  const VcTableView old = tv;
+
+  // 1. keys of the new records, sorted (stable: equal keys stay in id order); the result lands in pair (passes & 1)
+  hipLaunchKernelGGL(mih_keys_kernel, dim3(grid_for(nd, n_cu)), dim3(256), 0, s, d_cols + (uint64_t)(bitpos >> 6) * stride, n0, nd, bitpos & 63,
+                     mask, sc.keys[0], sc.vals[0]);
+  MIH_CHECK(hipGetLastError());
+  uint32_t* kb[2] = {sc.keys[0], sc.keys[1]};
+  uint32_t* vb[2] = {sc.vals[0], sc.vals[1]};
+  MIH_CHECK(vc_radix_sort_pairs(kb, vb, nd, sbits, sc.temp, s));
+  const uint32_t res = vc_radix_sort_passes(sbits) & 1u;
+  const uint32_t *keys = sc.keys[res], *new_ids = sc.vals[res];
+
+  // 2. insert points
+  hipLaunchKernelGGL(mih_update_ins_kernel, dim3(grid_for(nd, n_cu)), dim3(256), 0, s, keys, nd, old, sbits, sc.ins, sc.rank, sc.flag);
+  MIH_CHECK(hipGetLastError());
+
+  // 3. ids[]: out of place, one table's ids held twice (the update's largest allocation next to the records: when the first
+  // table cannot have it, the old index is still whole)
+  uint32_t* ids = nullptr;
+  MIH_CHECK(dev_alloc(ix->allocs, &ids, n * 4));
+  oc->touched = true;
+  ix->n = n;   // (build_derived sizes by it; a failure from here on frees the index)
+  MIH_CHECK(launch_merge(MuIdsSrc{old.ids, new_ids}, sc.ins, nd, n0, ids, n_cu, s));
+  tv.ids = ids;
+
+  // 4. offsets, 5. bitmap and rank directory
+  if (sbits < 32) {
+    hipLaunchKernelGGL(mih_update_direct_offsets_kernel, dim3(grid_for(nkeyspace + 1, n_cu)), dim3(256), 0, s, keys, nd, (uint32_t)(nkeyspace + 1),
+                       const_cast<uint32_t*>(old.offsets));
+    MIH_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(mih_update_bits_kernel, dim3(grid_for(nd, n_cu)), dim3(256), 0, s, keys, nd, const_cast<uint32_t*>(old.bitmap));
+    MIH_CHECK(hipGetLastError());
+  } else {
+    MIH_CHECK(vc_exclusive_scan_u32(sc.flag, sc.slot, nd, sc.temp, s));
+    uint32_t last_slot = 0, last_flag = 0;
+    MIH_CHECK(hipMemcpyAsync(&last_slot, sc.slot + nd - 1, 4, hipMemcpyDeviceToHost, s));
+    MIH_CHECK(hipMemcpyAsync(&last_flag, sc.flag + nd - 1, 4, hipMemcpyDeviceToHost, s));
+    MIH_CHECK(hipStreamSynchronize(s));
+    const uint32_t n_new = last_slot + last_flag;   // new buckets
+    hipLaunchKernelGGL(mih_update_newbuckets_kernel, dim3(grid_for(nd, n_cu)), dim3(256), 0, s, sc.flag, sc.slot, sc.rank, sc.ins, nd, sc.nb_rank, sc.nb_pos);
+    MIH_CHECK(hipGetLastError());
+    uint32_t* offsets = nullptr;
+    MIH_CHECK(dev_alloc(ix->allocs, &offsets, ((size_t)old.n_unique + n_new + 1) * 4));
+    // old rank r -> r + #{new buckets of old rank <= r}: the merge of step 3 with the new buckets' old ranks as insert points
+    MIH_CHECK(launch_merge(MuOffsetsSrc{old.offsets, sc.ins, nd, sc.nb_pos}, sc.nb_rank, n_new, (uint64_t)old.n_unique + 1, offsets, n_cu, s));
+    tv.offsets = offsets;
+    tv.n_unique = old.n_unique + n_new;
+    hipLaunchKernelGGL(mih_update_bits_kernel, dim3(grid_for(nd, n_cu)), dim3(256), 0, s, keys, nd, const_cast<uint32_t*>(old.bitmap));
+    MIH_CHECK(hipGetLastError());
+    const uint32_t nblocks = 1u << 24;
+    hipLaunchKernelGGL(mih_blockpop_kernel, dim3(n_cu * 16), dim3(256), 0, s, old.bitmap, nblocks, sc.scan_in);
+    MIH_CHECK(hipGetLastError());
+    MIH_CHECK(vc_exclusive_scan_u32(sc.scan_in, const_cast<uint32_t*>(old.blockrank), nblocks, sc.temp, s));
+  }
+
+  // {id, code} records: merged like ids[] while a second copy of this table's records can be had, else gathered again
+  const uint4* old_bent = old.bent;
+  tv.bent = nullptr;
+  if (pol.bent && old_bent) {
+    uint4* be = nullptr;
+    if (hipMalloc((void**)&be, (size_t)n * 16 * W) == hipSuccess) {
+      ix->allocs.push_back(be);
+      if (W == 1) MIH_CHECK(launch_merge(MuBentSrc<1>{old_bent, new_ids, d_cols, stride}, sc.ins, nd, n0, be, n_cu, s));
+      else MIH_CHECK(launch_merge(MuBentSrc<2>{old_bent, new_ids, d_cols, stride}, sc.ins, nd, n0, be, n_cu, s));
+      tv.bent = be;
+      ++oc->bent_merged;
+    } else {
+      (void)hipGetLastError();   // (out of memory is an answer here, not an error)
+    }
+  }
+
+  // 6. what the replaced arrays held goes back; the derived structures follow from the new ones as at a build / load
+  MIH_CHECK(hipStreamSynchronize(s));
+  free_alloc(ix, old.ids);
+  if (sbits == 32) free_alloc(ix, old.offsets);
+  free_alloc(ix, old.blockoff);
+  free_alloc(ix, old.lines);
+  free_alloc(ix, old.bcodes);
+  free_alloc(ix, old_bent);
+  tv.blockoff = nullptr; tv.lines = nullptr; tv.bcodes = nullptr;
+  MihMemPolicy derived = pol;
+  derived.bent = pol.bent && !tv.bent;
+  if (derived.bent) ++oc->bent_gathered;
+  int rc = build_derived(ix, tv, derived, d_cols, stride, s, err);
+  if (rc) return rc;
+  ix->h_tables[t] = tv;   // 7. the table is swapped in whole
+  return VC_OK;
+}
+
+int vc_mih_update(VcMihIndex** pix, const uint64_t* d_cols, uint64_t stride, uint64_t n, hipStream_t s, std::string* err) {
+  VcMihIndex* ix = *pix;
+  const uint64_t n0 = ix->n;
+  if (n < n0) return fail(err, VC_ERR_STATE, "the index covers more records than are resident");
+  if (n == n0) {
+    vc_mih_update_trace(ix, 0, "none", "0");
+    return VC_OK;
+  }
+  const uint64_t nd = n - n0;
+  const uint32_t sbits = ix->sbits, m = ix->m;
+  // the policy of a build of n records: what the old index holds counts as free (all of it is replaced or kept in place)
+  MihMemPolicy pol;
+  {
+    size_t free_b = 0, total_b = 0;
+    const bool have_free = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+    uint64_t held = 0;
+    for (const VcTableView& tv : ix->h_tables) held += table_bytes(ix, tv);
+    pol = vc_mih_policy(sbits, m, n, ix->W, have_free, free_b + held, MihPolicyKnobs{ix->knobs.mih_bcodes, ix->knobs.mih_bent, ix->knobs.mih_lines});
+  }
+
+  DevScratch tmp;
+  UpdateScratch sc;
+  for (uint32_t** a : {&sc.keys[0], &sc.keys[1], &sc.vals[0], &sc.vals[1], &sc.ins}) MIH_CHECK(dev_alloc(tmp.bufs, a, nd * 4));
+  const uint64_t nblocks = 1ull << 24;
+  size_t temp_words = std::max(vc_radix_sort_work_words(nd), vc_scan_work_words(nd));
+  if (sbits == 32) {
+    temp_words = std::max(temp_words, vc_scan_work_words(nblocks));
+    for (uint32_t** a : {&sc.rank, &sc.flag, &sc.slot, &sc.nb_rank, &sc.nb_pos}) MIH_CHECK(dev_alloc(tmp.bufs, a, nd * 4));
+    MIH_CHECK(dev_alloc(tmp.bufs, &sc.scan_in, (nblocks + 1) * 4));
+  }
+  MIH_CHECK(dev_alloc(tmp.bufs, &sc.temp, temp_words * 4));
+
+  UpdateOutcome oc;
+  int rc = VC_OK;
+  for (uint32_t t = 0; t < m && rc == VC_OK; ++t) rc = update_table(ix, t, pol, d_cols, stride, n0, n, sc, &oc, s, err);
+  if (rc == VC_OK) {
+    hipError_t r = hipMemcpyAsync(ix->d_tables, ix->h_tables.data(), sizeof(VcTableView) * m, hipMemcpyHostToDevice, s);
+    if (r == hipSuccess) r = hipStreamSynchronize(s);
+    if (r != hipSuccess) rc = hip_fail(err, r, "index update: table views");
+  }
+  if (rc != VC_OK) {
+    (void)hipStreamSynchronize(s);
+    if (oc.touched) {   // some table is merged and some are not: no index rather than that one
+      vc_mih_free(ix);
+      *pix = nullptr;
+    }
+    return rc;
+  }
+  vc_mih_update_trace(ix, nd, "merge", oc.bent_gathered ? "gather" : oc.bent_merged ? "merge" : "0");
+  return VC_OK;
 }
 
 // ---- BaseProxy-style views (tests / adapters; not on the search path) --------------------------------

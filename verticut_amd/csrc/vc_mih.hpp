@@ -8,6 +8,16 @@ int vc_mih_build(VcMihIndex** out, const uint64_t* d_cols, uint64_t stride, uint
                  uint32_t sbits, uint32_t id_base, uint32_t flags, uint32_t n_cu, uint32_t cand_cap, const VcKnobs& knobs,
                  hipStream_t s, std::string* err);
 void vc_mih_free(VcMihIndex* ix);
+// Index update (build_hash_tables.cc:40-70: get bucket, append, put): *ix covers records [0, n0) of the columns, which now hold
+// n >= n0.  Appended ids exceed every indexed id and a bucket is in ascending id order (rule a12), so the index of all n records
+// is the old one with each new entry appended to its key's bucket: per table a sort of the n - n0 new (key, id) pairs, one
+// insert point per pair, and one streaming merge of ids[] (and of the {id, code} records).  Bit for bit what vc_mih_build gives
+// from all n records.  The VcMihIndex object, its scratch and counters stay.  On failure *ix is the old index (still covering n0
+// records) or, once a table has been touched, freed and null -- never half merged.
+int vc_mih_update(VcMihIndex** ix, const uint64_t* d_cols, uint64_t stride, uint64_t n, hipStream_t s, std::string* err);
+uint64_t vc_mih_records(const VcMihIndex* ix);   // records the index covers
+// VC_MIH_TRACE: "[vc_mih] index updated: n=.. added=.. route=merge|rebuild|none bent=merge|gather|0 bcodes=.. lines=.."
+void vc_mih_update_trace(const VcMihIndex* ix, uint64_t added, const char* route, const char* bent);
 // index persistence: the CSR tables + bitmaps of a built index, and back (the codes themselves travel as a code file)
 int vc_mih_save(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, const char* path, hipStream_t s, std::string* err);
 int vc_mih_load(VcMihIndex** out, const char* path, const uint64_t* d_cols, uint64_t stride, uint64_t n, uint32_t W, uint32_t m,

@@ -424,6 +424,19 @@ int vc_sharded_build_index(vc_sharded* h) {
   return VC_OK;
 }
 
+// Appended ids fill the id-range shards in order, so an update touches the shard the store ended in and the ones after it: every
+// other shard's index is current and its vc_update_index does nothing.  A shard reached for the first time has no index and builds
+// one.  Nothing on the root depends on the store's size between calls (shard_size reads h->n), so there is nothing else to refresh.
+int vc_sharded_update_index(vc_sharded* h) {
+  if (!h) return VC_ERR_INVALID;
+  for (uint32_t g = 0; g < h->G; ++g) {
+    if (shard_size(h, g) == 0) continue;
+    int rc = vc_update_index(h->eng[g]);
+    if (rc) return sfail(h, rc, "shard %u: %s", g, vc_last_error(h->eng[g]));
+  }
+  return VC_OK;
+}
+
 int vc_sharded_get_code(vc_sharded* h, uint32_t id, void* out) {
   if (!h || !out) return VC_ERR_INVALID;
   if (id < h->cfg.engine.id_base || (uint64_t)id - h->cfg.engine.id_base >= h->n) return VC_NOT_FOUND;

@@ -37,6 +37,7 @@ EXPORTS = [
     "vc_sharded_search_radius_dev",
     "vc_get_codes_dev", "vc_search_knn_ids", "vc_search_knn_ids_dev",
     "vc_sharded_get_codes_dev", "vc_sharded_search_knn_ids", "vc_sharded_search_knn_ids_dev",
+    "vc_update_index", "vc_sharded_update_index",
 ]
 MAX_SHARDS = 16
 EXCHANGE_AUTO, EXCHANGE_PEER_COPY, EXCHANGE_RCCL = 0, 1, 2
@@ -111,6 +112,7 @@ def load_library():
     L.vc_size.argtypes = [vp, C.POINTER(u64)]
     L.vc_get_code.argtypes = [vp, u32, vp]
     L.vc_build_index.argtypes = [vp]
+    L.vc_update_index.argtypes = [vp]
     L.vc_get_bucket.argtypes = [vp, u32, u32, vp, vp, u32, C.POINTER(u32)]
     L.vc_bitmap_test.argtypes = [vp, u32, u32, C.POINTER(C.c_int)]
     L.vc_bitmap_read.argtypes = [vp, u32, u64, u64, vp]
@@ -138,6 +140,7 @@ def load_library():
     L.vc_sharded_add_synthetic.argtypes = [vp, u64, u64, u32, u32, u32]
     L.vc_sharded_size.argtypes = [vp, C.POINTER(u64)]
     L.vc_sharded_build_index.argtypes = [vp]
+    L.vc_sharded_update_index.argtypes = [vp]
     L.vc_sharded_get_code.argtypes = [vp, u32, vp]
     L.vc_sharded_get_bucket.argtypes = [vp, u32, u32, vp, vp, u32, C.POINTER(u32)]
     L.vc_sharded_search_knn.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp]
@@ -287,6 +290,10 @@ class Engine:
     # -- index
     def build_index(self):
         self._check(self._L.vc_build_index(self._h))
+
+    def update_index(self):
+        """Merge the records added since the index was built, loaded or last updated into it (a build when there is none)."""
+        self._check(self._L.vc_update_index(self._h))
 
     def get_bucket(self, table, index, cap=1 << 16, with_codes=True):
         """BaseProxy.get(HashIndex{table,index}) -> (ids, codes) or None (PROXY_NOT_FOUND)."""
@@ -455,6 +462,10 @@ class ShardedEngine:
 
     def build_index(self):
         self._check(self._L.vc_sharded_build_index(self._h))
+
+    def update_index(self):
+        """Engine.update_index on every non-empty shard (shards the appended ids did not reach have nothing to do)."""
+        self._check(self._L.vc_sharded_update_index(self._h))
 
     def get_code(self, gid):
         out = np.empty(self.nbytes, dtype=np.uint8)

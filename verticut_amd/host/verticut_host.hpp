@@ -104,6 +104,8 @@ class Backend {
   virtual int add_codes(const void* codes, uint64_t n) = 0;
   virtual int load_code_file(const char* path, uint64_t max_records, uint64_t* n_read) = 0;
   virtual int build_index() = 0;
+  // the records put since the last build / update are appended to their buckets (vc_update_index: build_hash_tables.cc:40-70)
+  virtual int update_index() = 0;
   virtual uint64_t size() const = 0;
   virtual int get_code(uint32_t id, void* out) = 0;
   virtual int get_bucket(uint32_t table, uint32_t index, uint32_t* ids, void* codes, uint32_t cap, uint32_t* n) = 0;
@@ -141,6 +143,7 @@ class Engine : public Backend {
   int add_codes(const void* codes, uint64_t n) override { return vc_add_codes(h_, codes, n); }
   int load_code_file(const char* path, uint64_t max_records, uint64_t* n_read) override { return vc_load_code_file(h_, path, max_records, n_read); }
   int build_index() override { return vc_build_index(h_); }
+  int update_index() override { return vc_update_index(h_); }
   uint64_t size() const override {
     uint64_t n = 0;
     vc_size(h_, &n);
@@ -216,6 +219,7 @@ class ShardedEngine : public Backend {
     return rc;
   }
   int build_index() override { return vc_sharded_build_index(h_); }
+  int update_index() override { return vc_sharded_update_index(h_); }
   uint64_t size() const override {
     uint64_t n = 0;
     vc_sharded_size(h_, &n);
@@ -280,8 +284,10 @@ inline Backend* make_backend(uint32_t bits, uint32_t n_tables, uint64_t capacity
 
 // BaseProxy over the resident index.  put(ID, BinaryCode) appends a record (ids must arrive in order, as
 // build_hash_tables.cc:55-69 produces them); put(HashIndex, Image_List) is accepted and ignored because the
-// buckets are derived from the records by vc_build_index (rule a12) -- the reference's read-modify-write of
-// bucket lists has no equivalent to perform.
+// buckets are derived from the records (rule a12): by Backend::build_index from all of them, or by
+// Backend::update_index, which appends the records put since the last build / update to their buckets -- the
+// reference's get bucket / append / put (build_hash_tables.cc:40-70), done for a whole batch of puts in one
+// merge.  Between a put and the next update_index / build_index, get(HashIndex) fails (the index is stale).
 class GpuProxy : public BaseProxy<Message, Message> {
  public:
   explicit GpuProxy(Backend* e) : e_(e) {}
