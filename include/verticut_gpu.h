@@ -260,6 +260,7 @@ int vc_search_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint3
  * of ids whose codes never leave HBM: a gather kernel turns the ids into the [nq][bits/64] query layout out of the column store,
  * the unchanged search runs on it, and a small kernel shapes the rows. */
 #define VC_IDS_EXCLUDE_SELF 0x1u   /* row = the k nearest items OTHER than the query's own record */
+#define VC_IDS_ONLY_GREATER 0x2u   /* radius-by-id calls only: a segment keeps the entries whose id exceeds the query's own */
 
 /* ID -> BinaryCode for a batch, in HBM (linear_search.cc:45-46).  d_ids: nq global ids; d_codes: nq*bits/8 bytes; d_found: nq
  * uint32 (may be NULL), 1 = the id is resident, 0 = it is not (outside [id_base, id_base + vc_size)) and its code is all zero.
@@ -278,8 +279,8 @@ int vc_get_codes_dev(vc_engine* e, const uint32_t* d_ids, uint32_t nq, void* d_c
  * A batch has no VC_NOT_FOUND: an id that is not resident gives count 0, a UINT64_MAX-padded row and zero statistics, and the call
  * still returns VC_OK.  Repeated ids are independent queries.  The scratch (gathered queries, k + 1 rows, counts, found words) is
  * grow-only buffers of the handle, separate from those of the other calls; a result depends on the database and the call only.
- * Radius search by id is not offered: a missing id would need the variable-length result compacted, and vc_get_codes_dev +
- * vc_search_radius_dev serves a caller whose ids exist. */
+ * Bit 0x2 (VC_IDS_ONLY_GREATER) is refused here like any unknown bit.  Radius search by id is not offered by these k-NN calls: it
+ * is vc_search_radius_ids / vc_search_radius_ids_dev below, which compact the variable-length result on the device. */
 int vc_search_knn_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, uint32_t id_flags,
                       uint64_t* out, uint32_t* counts, vc_query_stats* stats);
 /* The same for ids and results in HBM (search_image_by_id, image_search_client.h:12-27): d_ids nq uint32; d_out nq*k ascending,
@@ -288,6 +289,39 @@ int vc_search_knn_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t k
  * VC_MODE_LINEAR waits for nothing on the host, the MIH modes wait as they do there; results are valid in stream order. */
 int vc_search_knn_ids_dev(vc_engine* e, const uint32_t* d_ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t id_flags,
                           uint64_t* d_out, uint32_t* d_counts, vc_query_stats* d_stats, void* stream);
+
+/* "Which records lie within `radius` of THESE records": vc_search_radius / vc_search_radius_dev for a batch of ids whose codes never
+ * leave HBM (the near-duplicate question; search_R_neighbors, search_worker.cc:222-264, asked through search_image_by_id's id ->
+ * code read, image_search_client.h:12-27).  mode VC_MODE_LINEAR or VC_MODE_MIH_EXACT; result layout as vc_search_radius_dev: offsets
+ * has nq + 1 entries, query i owns out[offsets[i] .. offsets[i+1]), ascending packed (dist, id).
+ * Errors are those of the radius call underneath and are checked before any work: VC_ERR_INVALID for another mode, nq == 0, null
+ * ids / offsets, or out == NULL with out_cap != 0; VC_ERR_STATE in MIH mode without a current index.  id_flags: any combination of
+ * VC_IDS_EXCLUDE_SELF and VC_IDS_ONLY_GREATER, any other bit gives VC_ERR_INVALID.
+ *   id_flags == 0          the segment of a resident id is bit for bit that of vc_search_radius / vc_search_radius_dev in the same
+ *                          mode and radius, queried with the code vc_get_code returns for that id.
+ *   VC_IDS_EXCLUDE_SELF    that segment without the entry (0, own id).  The entry is matched by value, not by position (duplicates
+ *                          with smaller ids precede it); it is always present for a resident id, its distance being 0 <= radius.
+ *   VC_IDS_ONLY_GREATER    that segment without every entry whose id is <= the query's own id -- the own entry included, so adding
+ *                          VC_IDS_EXCLUDE_SELF changes nothing.  Walking all resident ids in batches lists every unordered pair
+ *                          within `radius` exactly once.  The kept entries stay in ascending packed order (a stable compaction).
+ * A batch has no VC_NOT_FOUND: an id that is not resident (outside [id_base, id_base + vc_size)) owns an empty segment and the call
+ * still returns VC_OK.  Repeated ids are independent queries.
+ * Capacity, with T the compacted total: T > out_cap gives VC_ERR_CAPACITY, offsets then holds the compacted prefix sums
+ * (offsets[nq] = T) and out is untouched -- the protocol of vc_search_radius_dev; out_cap = 0 with out = NULL asks for the sizes.
+ * Device form: gather, the radius search underneath and the compaction (count, two scans, copy: 64-bit entries cut into chunks of
+ * 1024 per query, so a long segment spreads over many blocks) are enqueued on `stream`.  The host waits where the radius search
+ * underneath waits -- once per attempt for its total -- and at most once more, for T: not at all when the uncompacted total already
+ * fits out_cap, since T <= that total.  The copy into d_out may still be running when the call returns; results are valid in
+ * stream order.  The scratch (gathered queries, found words, the uncompacted results and their offsets, per-chunk counts) is
+ * grow-only buffers of the handle, separate from those of every other call, every word written before it is read within a call: a
+ * result depends on the database and the call only.  When the scratch for the uncompacted results is too small the call underneath
+ * reports the size needed; the scratch grows and the search runs once more. */
+int vc_search_radius_ids_dev(vc_engine* e, const uint32_t* d_ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags,
+                             uint64_t* d_out, uint64_t out_cap, uint64_t* d_offsets, void* stream);
+/* The same for ids, results and offsets in host memory: the device form on the engine's stream plus the staged ids and the copy home
+ * of the offsets (also with VC_ERR_CAPACITY) and the results; waits for them. */
+int vc_search_radius_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags,
+                         uint64_t* out, uint64_t out_cap, uint64_t* out_offsets);
 
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
@@ -413,6 +447,15 @@ int vc_sharded_search_knn_ids(vc_sharded* h, const uint32_t* ids, uint32_t nq, u
                               uint32_t id_flags, uint64_t* out, uint32_t* counts, vc_query_stats* stats);
 int vc_sharded_search_knn_ids_dev(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t id_flags,
                                   uint64_t* d_out, uint32_t* d_counts, vc_query_stats* d_stats, void* stream);
+/* Radius search by id over all shards: contract, id_flags, capacity protocol and batch rules as vc_search_radius_ids_dev /
+ * vc_search_radius_ids, with "the call underneath" = vc_sharded_search_radius_dev and ids global over the whole store (an id is not
+ * resident when no shard holds it).  Device pointers live on the ROOT device, `stream` is a stream of that device.  The ids are
+ * gathered as in vc_sharded_get_codes_dev, the union's uncompacted result lands in a scratch buffer on the root, and the compaction
+ * runs there.  VC_FLAG_GLOBAL_STOP and VC_FLAG_GLOBAL_APPROX play no part. */
+int vc_sharded_search_radius_ids_dev(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags,
+                                     uint64_t* d_out, uint64_t out_cap, uint64_t* d_offsets, void* stream);
+int vc_sharded_search_radius_ids(vc_sharded* h, const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags,
+                                 uint64_t* out, uint64_t out_cap, uint64_t* out_offsets);
 /* borrow shard g's engine (bucket views, timing, files); its id range is [*first_id, *first_id + *n_ids) */
 int vc_sharded_shard(vc_sharded* h, uint32_t shard, vc_engine** e, uint64_t* first_id, uint64_t* n_ids);
 

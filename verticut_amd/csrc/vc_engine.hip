@@ -48,6 +48,16 @@ struct vc_engine {
   uint64_t* d_hrows = nullptr;  size_t hrows_bytes = 0;
   uint32_t* d_hcnt = nullptr;   size_t hcnt_bytes = 0;
   vc_query_stats* d_hstats = nullptr; size_t hstats_bytes = 0;
+  // radius search by id (vc_search_radius_ids*): the gathered queries, their found words, the uncompacted results and offsets of the
+  // search underneath, the compaction's counts (VcIdsRadiusWork); and the host-pointer form's staged ids, results and offsets
+  uint64_t* d_rq = nullptr;     size_t rq_bytes = 0;
+  uint32_t* d_rfound = nullptr; size_t rfound_bytes = 0;
+  uint64_t* d_rraw = nullptr;   size_t rraw_bytes = 0;
+  uint64_t* d_rroffs = nullptr; size_t rroffs_bytes = 0;
+  uint8_t* d_rwork = nullptr;   size_t rwork_bytes = 0;
+  uint32_t* d_rhids = nullptr;  size_t rhids_bytes = 0;
+  uint64_t* d_rhout = nullptr;  size_t rhout_bytes = 0;
+  uint64_t* d_rhoffs = nullptr; size_t rhoffs_bytes = 0;
   CleanState clean;                                       // the last kernel of a linear step hands d_state back zeroed: no memset per step
   uint32_t scan_event_tick = 0;                           // VC_FLAG_LEAN_TIMING: only every timing_sample-th verify launch is timed
   VcKnobs knobs;                                          // environment knobs, read once at vc_create
@@ -326,6 +336,14 @@ int vc_destroy(vc_engine* e) {
   (void)hipFree(e->d_hrows);
   (void)hipFree(e->d_hcnt);
   (void)hipFree(e->d_hstats);
+  (void)hipFree(e->d_rq);
+  (void)hipFree(e->d_rfound);
+  (void)hipFree(e->d_rraw);
+  (void)hipFree(e->d_rroffs);
+  (void)hipFree(e->d_rwork);
+  (void)hipFree(e->d_rhids);
+  (void)hipFree(e->d_rhout);
+  (void)hipFree(e->d_rhoffs);
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->last_call) (void)hipEventDestroy(e->last_call);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -1126,6 +1144,93 @@ int vc_search_knn_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t k
   }
   return VC_OK;
 }
+
+}  // extern "C"
+
+// ---- radius search for queries named by id ------------------------------------------------------------------------------------------
+static int check_radius_ids_args(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t mode, uint32_t id_flags, const uint64_t* out,
+                                 uint64_t out_cap, const uint64_t* offsets) {
+  if (!e || !ids || !offsets || (!out && out_cap) || nq == 0) return VC_ERR_INVALID;
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "radius search: mode must be LINEAR or MIH_EXACT");
+  if (id_flags & ~(VC_IDS_EXCLUDE_SELF | VC_IDS_ONLY_GREATER)) return fail(e, VC_ERR_INVALID, "unknown id_flags 0x%x", id_flags);
+  if (mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
+  return VC_OK;
+}
+
+int vc_engine_has_index(vc_engine* e) { return e && live_index(e) ? 1 : 0; }
+
+// The whole call on e->stream (inside the caller's StreamCall): gather, the radius search into the handle's scratch -- repeated once with
+// the scratch grown to the total it reported -- count / offsets, and, once T is known to fit, the copy.
+static int radius_ids_run(vc_engine* e, const uint32_t* d_ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* d_out,
+                          uint64_t out_cap, uint64_t* d_offsets) {
+  int rc;
+  if ((rc = grow(e, &e->d_rq, &e->rq_bytes, (size_t)nq * e->W * 8))) return rc;
+  if ((rc = grow(e, &e->d_rfound, &e->rfound_bytes, (size_t)nq * 4))) return rc;
+  if ((rc = grow(e, &e->d_rroffs, &e->rroffs_bytes, ((size_t)nq + 1) * 8))) return rc;
+  if ((rc = grow(e, &e->d_rraw, &e->rraw_bytes, (size_t)8 << 16))) return rc;
+  VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, d_ids, nq, e->d_rq, e->d_rfound, e->stream));
+  uint64_t raw_total = 0;
+  for (int attempt = 0;; ++attempt) {
+    const uint64_t cap = e->rraw_bytes / 8;
+    rc = vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, e->d_rq, nq,
+                          radius, e->d_rraw, cap, e->d_rroffs, true, &e->radius_work, e->stream, &e->err, &raw_total);
+    if (rc == VC_OK) break;
+    if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
+    if ((rc = grow(e, &e->d_rraw, &e->rraw_bytes, (size_t)raw_total * 8))) return rc;   // (the first attempt has been waited for)
+  }
+  const uint64_t items = vc_ids_radius_items(nq, raw_total);
+  if (items > 0xFFFFFFFFull) return fail(e, VC_ERR_CAPACITY, "radius search by id: more results than one compaction can place");
+  if ((rc = grow(e, &e->d_rwork, &e->rwork_bytes, VcIdsRadiusWork::bytes(nq, items)))) return rc;
+  const VcIdsRadiusWork w(e->d_rwork, nq, items);
+  VC_HIP(e, vc_launch_ids_radius_count(w, e->d_rraw, e->d_rroffs, d_ids, e->d_rfound, nq, id_flags, d_offsets, e->stream));
+  if (raw_total > out_cap) {   // T <= raw_total: only then the host has to learn T
+    uint64_t T = 0;
+    VC_HIP(e, hipMemcpyAsync(&T, w.total, 8, hipMemcpyDeviceToHost, e->stream));
+    VC_HIP(e, hipStreamSynchronize(e->stream));
+    if (T > out_cap) return fail(e, VC_ERR_CAPACITY, "radius search: output buffer too small (needed counts are in the offsets)");
+  }
+  if (d_out && raw_total) VC_HIP(e, vc_launch_ids_radius_copy(w, e->d_rraw, e->d_rroffs, d_ids, nq, id_flags, d_offsets, d_out, e->stream));
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_search_radius_ids_dev(vc_engine* e, const uint32_t* d_ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* d_out,
+                             uint64_t out_cap, uint64_t* d_offsets, void* stream) {
+  int rc = check_radius_ids_args(e, d_ids, nq, mode, id_flags, d_out, out_cap, d_offsets);
+  if (rc) return rc;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, caller_stream(e, stream));
+  return radius_ids_run(e, d_ids, nq, radius, mode, id_flags, d_out, out_cap, d_offsets);
+}
+
+int vc_search_radius_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* out,
+                         uint64_t out_cap, uint64_t* out_offsets) {
+  int rc = check_radius_ids_args(e, ids, nq, mode, id_flags, out, out_cap, out_offsets);
+  if (rc) return rc;
+  if ((rc = bind_device(e))) return rc;
+  if ((rc = grow(e, &e->d_rhids, &e->rhids_bytes, (size_t)nq * 4))) return rc;
+  if ((rc = grow(e, &e->d_rhoffs, &e->rhoffs_bytes, ((size_t)nq + 1) * 8))) return rc;
+  if ((rc = grow(e, &e->d_rhout, &e->rhout_bytes, (size_t)out_cap * 8))) return rc;
+  VC_HIP(e, hipMemcpyAsync(e->d_rhids, ids, (size_t)nq * 4, hipMemcpyHostToDevice, e->stream));
+  {
+    const StreamCall call(e, e->stream);
+    rc = radius_ids_run(e, e->d_rhids, nq, radius, mode, id_flags, out_cap ? e->d_rhout : nullptr, out_cap, e->d_rhoffs);
+  }
+  if (rc != VC_OK && rc != VC_ERR_CAPACITY) return rc;
+  // the offsets come home in both cases (VC_ERR_CAPACITY: they are the needed counts); the staged results behind them
+  VC_HIP(e, hipMemcpyAsync(out_offsets, e->d_rhoffs, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipStreamSynchronize(e->stream));
+  if (rc == VC_OK && out_offsets[nq]) {
+    VC_HIP(e, hipMemcpyAsync(out, e->d_rhout, (size_t)out_offsets[nq] * 8, hipMemcpyDeviceToHost, e->stream));
+    VC_HIP(e, hipStreamSynchronize(e->stream));
+  }
+  return rc;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 // is `p` page-locked host memory (hipHostMalloc / hipHostRegister / torch pin_memory)?  Then a copy is one DMA, no staging.
 static bool host_pinned(const void* p) {

@@ -6,6 +6,7 @@
 //                         (k' = k: pass-through that only applies the found mask)
 //   vc_ids_merge_kernel   sharded store: the shards' gathered slots ORed into one query buffer on the root
 // None of them uses LDS or scratch; the search in between is the unchanged vc_search_knn_dev_stats.
+// The radius search by id (vc_search_radius_ids*) compacts a variable-length result instead: vc_ids_radius.hip.
 // ============================================================================
 #include <algorithm>
 

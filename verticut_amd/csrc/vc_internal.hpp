@@ -165,6 +165,31 @@ hipError_t vc_launch_ids_merge(const uint64_t* d_slots, uint64_t slot_words, uin
 // the strip kernel's rule on host memory (counts non-null)
 void vc_ids_strip_host(const uint32_t* ids, const uint32_t* found, const uint64_t* rows, const uint32_t* cnt, uint32_t nq, uint32_t kp, uint32_t k,
                        uint64_t* out, uint32_t* counts, vc_query_stats* stats);
+// ---- vc_ids_radius.hip: radius search by id.  The raw result of the radius search underneath (d_raw ascending per query, d_roffs its nq + 1 offsets) is
+// compacted segment by segment -- an entry stays when its query's id is resident (d_found) and id_flags (VC_IDS_EXCLUDE_SELF,
+// VC_IDS_ONLY_GREATER) keep it.  The work is cut into (query, chunk) items of VC_IDS_RCHUNK entries; w.items bounds their number.
+#define VC_IDS_RCHUNK 1024u
+inline uint64_t vc_ids_radius_items(uint32_t nq, uint64_t raw_total) { return (uint64_t)nq + raw_total / VC_IDS_RCHUNK; }
+struct VcIdsRadiusWork {   // all words of the scratch are written by the count launches before anything reads them
+  uint64_t items;          // vc_ids_radius_items(nq, the raw total): must fit 32 bits
+  uint64_t* total;         // the compacted total T
+  uint32_t *cs, *qsum;     // [nq + 1] chunk starts, [nq] kept entries per query
+  uint32_t *chunk_cnt, *chunk_base;   // [items] kept entries of a chunk, and of the query's chunks before it
+  static size_t bytes(uint32_t nq, uint64_t items) { return 8 + ((size_t)nq * 2 + 1 + items * 2) * 4; }
+  VcIdsRadiusWork(void* p, uint32_t nq, uint64_t items_) : items(items_) {
+    total = (uint64_t*)p;
+    cs = (uint32_t*)(total + 1);
+    qsum = cs + nq + 1;
+    chunk_cnt = qsum + nq;
+    chunk_base = chunk_cnt + items;
+  }
+};
+// plan + count + chunk scan + offsets: d_offsets[0 .. nq] (the compacted prefix sums) and *w.total, nothing is waited for
+hipError_t vc_launch_ids_radius_count(const VcIdsRadiusWork& w, const uint64_t* d_raw, const uint64_t* d_roffs, const uint32_t* d_ids,
+                                      const uint32_t* d_found, uint32_t nq, uint32_t id_flags, uint64_t* d_offsets, hipStream_t s);
+// the kept entries, in order, to d_out[d_offsets[q] ..): the caller has made sure that *w.total entries fit
+hipError_t vc_launch_ids_radius_copy(const VcIdsRadiusWork& w, const uint64_t* d_raw, const uint64_t* d_roffs, const uint32_t* d_ids, uint32_t nq,
+                                     uint32_t id_flags, const uint64_t* d_offsets, uint64_t* d_out, hipStream_t s);
 // ---- vc_engine.hip: what the sharded store's global stop (vc_sharded.hip) needs of a shard's engine
 struct VcEngineView {
   const uint64_t* cols;   // column-major codes, word j of record i at cols[j * stride + i]
@@ -172,6 +197,7 @@ struct VcEngineView {
   uint32_t W, m, sbits, id_base, n_cu, reach;   // reach: vc_mih_knn_reach of the index (0 without one)
 };
 int vc_engine_view(vc_engine* e, VcEngineView* v);
+int vc_engine_has_index(vc_engine* e);   // 1: an MIH index that covers every resident record
 // MIH k-NN (mode: VC_MODE_MIH_EXACT or VC_MODE_MIH_APPROX) capped at shell r_cap (vc_mih_search's r_cap) on stream s: shells 0..r_cap
 // with the mode's own stop rule active; a query still open at r_cap ends with radius = r_cap and the k best of what it has seen.
 // d_stats as vc_search_knn_dev_stats

@@ -125,6 +125,9 @@ enum RootBuf {
   // queries named by id: gathered queries, found words, the k + 1 rows and counts of the search underneath; the host-pointer
   // form's staged ids, rows, counts and statistics
   IDS_Q, IDS_FOUND, IDS_ROWS, IDS_CNT, IDS_HIDS, IDS_HROWS, IDS_HCNT, IDS_HSTATS,
+  // radius search by id: gathered queries, found words, the union's uncompacted results and offsets, the compaction's counts
+  // (VcIdsRadiusWork); the host-pointer form's staged ids, results and offsets
+  RIDS_Q, RIDS_FOUND, RIDS_RAW, RIDS_ROFFS, RIDS_WORK, RIDS_HIDS, RIDS_HOUT, RIDS_HOFFS,
   ROOT_BUFS
 };
 
@@ -1669,14 +1672,16 @@ struct ShardRadius {
 };
 
 // Any device may be current on entry; the root device is on return from exchange() onwards.
+// total (may be null): the union's total once the shards have answered, also when it exceeds out_cap (VC_ERR_CAPACITY).
 static int sharded_radius_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t radius, uint32_t mode, uint64_t* d_out,
-                              uint64_t out_cap, uint64_t* d_offsets, hipStream_t S) {
+                              uint64_t out_cap, uint64_t* d_offsets, hipStream_t S, uint64_t* total = nullptr) {
   ShardRadius b{h, d_queries, nq, radius, mode, d_out, out_cap, d_offsets, S, (size_t)nq * h->nbytes, {}, {}, {}, {}};
   int rc = b.prepare_buffers();
   if (!rc) rc = b.send_queries();
   if (!rc) rc = b.run_lanes();
   if (!rc) rc = b.exchange();
   if (!rc) rc = b.offsets();
+  if (!rc && total) *total = b.A.total;
   if (!rc) rc = b.merge();
   return rc;
 }
@@ -1982,6 +1987,88 @@ int vc_sharded_search_knn_ids(vc_sharded* h, const uint32_t* ids, uint32_t nq, u
     if (stats) stats[i].n_results = cnt[i];
   }
   return VC_OK;
+}
+
+}  // extern "C"
+
+static int check_sharded_radius_ids_args(vc_sharded* h, const uint32_t* ids, uint32_t nq, uint32_t mode, uint32_t id_flags, const uint64_t* out,
+                                         uint64_t out_cap, const uint64_t* offsets) {
+  if (!h || !ids || !offsets || nq == 0 || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) || (!out && out_cap)) return VC_ERR_INVALID;
+  if (id_flags & ~(VC_IDS_EXCLUDE_SELF | VC_IDS_ONLY_GREATER)) return sfail(h, VC_ERR_INVALID, "unknown id_flags 0x%x", id_flags);
+  if (mode == VC_MODE_MIH_EXACT)
+    for (uint32_t g = 0; g < h->G; ++g)
+      if (shard_size(h, g) && !vc_engine_has_index(h->eng[g])) return sfail(h, VC_ERR_STATE, "shard %u: MIH search needs vc_sharded_build_index() first", g);
+  return VC_OK;
+}
+
+// Radius search by id over the shards, all on the root device's stream S: gather, the union's radius search into the handle's scratch --
+// repeated once with the scratch grown to the total it reported -- count / offsets, and, once T is known to fit, the copy.
+static int sharded_radius_ids_run(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags,
+                                  uint64_t* d_out, uint64_t out_cap, uint64_t* d_offsets, hipStream_t S) {
+  int rc;
+  VS_HIP(h, hipSetDevice(h->root));
+  if ((rc = h->buf[RIDS_Q].grow(h, (size_t)nq * h->nbytes))) return rc;
+  if ((rc = h->buf[RIDS_FOUND].grow(h, (size_t)nq * 4))) return rc;
+  if ((rc = h->buf[RIDS_ROFFS].grow(h, ((size_t)nq + 1) * 8))) return rc;
+  if ((rc = h->buf[RIDS_RAW].grow(h, (size_t)8 << 16))) return rc;
+  if ((rc = sharded_gather_ids(h, d_ids, nq, h->buf[RIDS_Q].as<uint64_t>(), h->buf[RIDS_FOUND].as<uint32_t>(), true, S))) return rc;
+  uint64_t raw_total = 0;
+  for (int attempt = 0;; ++attempt) {
+    const uint64_t cap = h->buf[RIDS_RAW].bytes / 8;
+    rc = sharded_radius_dev(h, h->buf[RIDS_Q].p, nq, radius, mode, h->buf[RIDS_RAW].as<uint64_t>(), cap, h->buf[RIDS_ROFFS].as<uint64_t>(), S, &raw_total);
+    if (rc == VC_OK) break;
+    if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
+    VS_HIP(h, hipSetDevice(h->root));
+    if ((rc = h->buf[RIDS_RAW].grow(h, (size_t)raw_total * 8))) return rc;
+  }
+  VS_HIP(h, hipSetDevice(h->root));
+  const uint64_t items = vc_ids_radius_items(nq, raw_total);
+  if (items > 0xFFFFFFFFull) return sfail(h, VC_ERR_CAPACITY, "radius search by id: more results than one compaction can place");
+  if ((rc = h->buf[RIDS_WORK].grow(h, VcIdsRadiusWork::bytes(nq, items)))) return rc;
+  const VcIdsRadiusWork w(h->buf[RIDS_WORK].p, nq, items);
+  const uint64_t *raw = h->buf[RIDS_RAW].as<uint64_t>(), *roffs = h->buf[RIDS_ROFFS].as<uint64_t>();
+  VS_HIP(h, vc_launch_ids_radius_count(w, raw, roffs, d_ids, h->buf[RIDS_FOUND].as<uint32_t>(), nq, id_flags, d_offsets, S));
+  if (raw_total > out_cap) {   // T <= raw_total: only then the host has to learn T
+    uint64_t T = 0;
+    VS_HIP(h, hipMemcpyAsync(&T, w.total, 8, hipMemcpyDeviceToHost, S));
+    VS_HIP(h, hipStreamSynchronize(S));
+    if (T > out_cap) return sfail(h, VC_ERR_CAPACITY, "radius search: output buffer too small (needed counts are in the offsets)");
+  }
+  if (d_out && raw_total) VS_HIP(h, vc_launch_ids_radius_copy(w, raw, roffs, d_ids, nq, id_flags, d_offsets, d_out, S));
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_sharded_search_radius_ids_dev(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags,
+                                     uint64_t* d_out, uint64_t out_cap, uint64_t* d_offsets, void* stream) {
+  int rc = check_sharded_radius_ids_args(h, d_ids, nq, mode, id_flags, d_out, out_cap, d_offsets);
+  if (rc) return rc;
+  return sharded_radius_ids_run(h, d_ids, nq, radius, mode, id_flags, d_out, out_cap, d_offsets, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+}
+
+int vc_sharded_search_radius_ids(vc_sharded* h, const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* out,
+                                 uint64_t out_cap, uint64_t* out_offsets) {
+  int rc = check_sharded_radius_ids_args(h, ids, nq, mode, id_flags, out, out_cap, out_offsets);
+  if (rc) return rc;
+  hipStream_t S = h->root_stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  if ((rc = h->buf[RIDS_HIDS].grow(h, (size_t)nq * 4))) return rc;
+  if ((rc = h->buf[RIDS_HOFFS].grow(h, ((size_t)nq + 1) * 8))) return rc;
+  if ((rc = h->buf[RIDS_HOUT].grow(h, (size_t)out_cap * 8))) return rc;
+  VS_HIP(h, hipMemcpyAsync(h->buf[RIDS_HIDS].p, ids, (size_t)nq * 4, hipMemcpyHostToDevice, S));
+  rc = sharded_radius_ids_run(h, h->buf[RIDS_HIDS].as<uint32_t>(), nq, radius, mode, id_flags, out_cap ? h->buf[RIDS_HOUT].as<uint64_t>() : nullptr, out_cap,
+                              h->buf[RIDS_HOFFS].as<uint64_t>(), S);
+  if (rc != VC_OK && rc != VC_ERR_CAPACITY) return rc;
+  // the offsets come home in both cases (VC_ERR_CAPACITY: they are the needed counts); the staged results behind them
+  VS_HIP(h, hipSetDevice(h->root));
+  VS_HIP(h, hipMemcpyAsync(out_offsets, h->buf[RIDS_HOFFS].p, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipStreamSynchronize(S));
+  if (rc == VC_OK && out_offsets[nq]) {
+    VS_HIP(h, hipMemcpyAsync(out, h->buf[RIDS_HOUT].p, (size_t)out_offsets[nq] * 8, hipMemcpyDeviceToHost, S));
+    VS_HIP(h, hipStreamSynchronize(S));
+  }
+  return rc;
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@ FLAG_GLOBAL_APPROX = 0x20 # sharded store, approximate MIH: stop where one engin
 SYNTH_UNIFORM, SYNTH_CLUSTERED = 0, 1
 ORDER_ASCENDING, ORDER_FARTHEST_FIRST = 0, 1
 IDS_EXCLUDE_SELF = 0x1    # VC_IDS_EXCLUDE_SELF: a by-id row holds the k nearest items other than the query's own record
+IDS_ONLY_GREATER = 0x2    # VC_IDS_ONLY_GREATER (radius-by-id calls only): a segment keeps the entries whose id exceeds the query's own
 PACK_INF = np.uint64(0xFFFFFFFFFFFFFFFF)
 STREAM_OWN = C.c_void_p(-1)   # VC_STREAM_OWN; None / 0 = the HIP null stream (PyTorch's default stream)
 
@@ -37,6 +38,7 @@ EXPORTS = [
     "vc_sharded_search_radius_dev",
     "vc_get_codes_dev", "vc_search_knn_ids", "vc_search_knn_ids_dev",
     "vc_sharded_get_codes_dev", "vc_sharded_search_knn_ids", "vc_sharded_search_knn_ids_dev",
+    "vc_search_radius_ids", "vc_search_radius_ids_dev", "vc_sharded_search_radius_ids", "vc_sharded_search_radius_ids_dev",
     "vc_update_index", "vc_sharded_update_index",
 ]
 MAX_SHARDS = 16
@@ -155,6 +157,10 @@ def load_library():
     L.vc_sharded_get_codes_dev.argtypes = [vp, vp, u32, vp, vp, vp]
     L.vc_sharded_search_knn_ids.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, vp, vp]
     L.vc_sharded_search_knn_ids_dev.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]
+    L.vc_search_radius_ids.argtypes = [vp, vp, u32, u32, u32, u32, vp, u64, vp]
+    L.vc_search_radius_ids_dev.argtypes = [vp, vp, u32, u32, u32, u32, vp, u64, vp, vp]
+    L.vc_sharded_search_radius_ids.argtypes = [vp, vp, u32, u32, u32, u32, vp, u64, vp]
+    L.vc_sharded_search_radius_ids_dev.argtypes = [vp, vp, u32, u32, u32, u32, vp, u64, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -177,6 +183,22 @@ def _search_knn_ids(self, fn, ids, k, mode, order, id_flags, with_stats):
     if with_stats:
         return out, counts, list(stats)
     return out, counts
+
+
+def _search_radius_ids(self, fn, ids, radius, mode, id_flags, cap_per_query):
+    """shared by Engine.search_radius_ids and ShardedEngine.search_radius_ids: numpy ids in, a list of ascending packed arrays out;
+    one retry with offsets[nq] entries on VC_ERR_CAPACITY, as search_radius does"""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+    nq = ids.shape[0]
+    offs = np.zeros(nq + 1, dtype=np.uint64)
+    cap = nq * cap_per_query
+    for _ in range(2):
+        out = np.empty(max(cap, 1), dtype=np.uint64)
+        rc = self._check(fn(self._h, _p(ids), nq, radius, mode, id_flags, _p(out), cap, _p(offs)), ok=(VC_OK, VC_ERR_CAPACITY))
+        if rc == VC_OK:
+            return [out[int(offs[i]):int(offs[i + 1])].copy() for i in range(nq)]
+        cap = int(offs[nq])
+    raise VcError(VC_ERR_CAPACITY, "radius search output does not fit")
 
 
 def split(packed):
@@ -382,6 +404,16 @@ class Engine:
         return self._check(self._L.vc_search_radius_dev(self._h, d_queries, nq, radius, mode, d_out, out_cap, d_offsets, stream),
                            ok=(VC_OK, VC_ERR_CAPACITY))
 
+    def search_radius_ids(self, ids, radius, mode=MODE_LINEAR, id_flags=0, cap_per_query=4096):
+        """vc_search_radius_ids: numpy ids; a list of ascending packed arrays, one per id (empty for an id that is not resident)"""
+        return _search_radius_ids(self, self._L.vc_search_radius_ids, ids, radius, mode, id_flags, cap_per_query)
+
+    def search_radius_ids_dev(self, d_ids, nq, radius, d_out, out_cap, d_offsets, mode=MODE_MIH_EXACT, id_flags=0, stream=None):
+        """vc_search_radius_ids_dev on raw device addresses, results valid in `stream` order; returns VC_OK or VC_ERR_CAPACITY
+        (d_offsets then holds the compacted prefix sums, d_offsets[nq] the total; d_out is untouched)."""
+        return self._check(self._L.vc_search_radius_ids_dev(self._h, d_ids, nq, radius, mode, id_flags, d_out, out_cap, d_offsets, stream),
+                           ok=(VC_OK, VC_ERR_CAPACITY))
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -539,6 +571,16 @@ class ShardedEngine:
         or VC_ERR_CAPACITY (d_offsets then holds the needed counts, d_offsets[nq] the total; d_out is untouched)."""
         return self._check(self._L.vc_sharded_search_radius_dev(self._h, d_queries, nq, radius, mode, d_out, out_cap, d_offsets, stream),
                            ok=(VC_OK, VC_ERR_CAPACITY))
+
+    def search_radius_ids(self, ids, radius, mode=MODE_LINEAR, id_flags=0, cap_per_query=64):
+        """vc_sharded_search_radius_ids: numpy global ids; a list of ascending packed arrays, one per id"""
+        return _search_radius_ids(self, self._L.vc_sharded_search_radius_ids, ids, radius, mode, id_flags, cap_per_query)
+
+    def search_radius_ids_dev(self, d_ids, nq, radius, d_out, out_cap, d_offsets, mode=MODE_MIH_EXACT, id_flags=0, stream=None):
+        """vc_sharded_search_radius_ids_dev: raw device addresses on the root device, results valid in `stream` order; returns VC_OK
+        or VC_ERR_CAPACITY (d_offsets then holds the compacted prefix sums, d_offsets[nq] the total; d_out is untouched)."""
+        return self._check(self._L.vc_sharded_search_radius_ids_dev(self._h, d_ids, nq, radius, mode, id_flags, d_out, out_cap, d_offsets,
+                                                                    stream), ok=(VC_OK, VC_ERR_CAPACITY))
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

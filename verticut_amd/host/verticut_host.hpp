@@ -9,7 +9,8 @@
 //   vc::SearchWorker          find(code, nbytes, knn, approximate) / get_knn / get_stat
 //                             (src/search_worker.h:25-33); results farthest first (search_worker.cc:210-216)
 //   vc::image_search_client   ping / search_image_by_id(id, knn, approximate)
-//                             (src/image_search_client.h:12-27), in process instead of msgpack-rpc
+//                             (src/image_search_client.h:12-27), in process instead of msgpack-rpc;
+//                             search_images_by_id (a batch), search_image_by_id_within (all images within a radius)
 //
 // The message structs stand in for the protobuf messages of src/image_search.proto:3-27 (same field
 // names and accessors; no wire format -- there is no KV tier to talk to any more).
@@ -114,6 +115,9 @@ class Backend {
   // a batch of queries named by id (vc_search_knn_ids / vc_sharded_search_knn_ids): the codes never leave HBM
   virtual int search_knn_ids(const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, uint32_t id_flags,
                              uint64_t* out, uint32_t* counts, vc_query_stats* stats) = 0;
+  // all items within `radius` of a batch of records named by id (vc_search_radius_ids / vc_sharded_search_radius_ids)
+  virtual int search_radius_ids(const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* out,
+                                uint64_t out_cap, uint64_t* out_offsets) = 0;
 };
 
 // Owns one vc_engine (one shard / GPU).
@@ -160,6 +164,10 @@ class Engine : public Backend {
   int search_knn_ids(const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, uint32_t id_flags, uint64_t* out,
                      uint32_t* counts, vc_query_stats* stats) override {
     return vc_search_knn_ids(h_, ids, nq, k, mode, order, id_flags, out, counts, stats);
+  }
+  int search_radius_ids(const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* out, uint64_t out_cap,
+                        uint64_t* out_offsets) override {
+    return vc_search_radius_ids(h_, ids, nq, radius, mode, id_flags, out, out_cap, out_offsets);
   }
  private:
   vc_engine* h_ = nullptr;
@@ -236,6 +244,10 @@ class ShardedEngine : public Backend {
   int search_knn_ids(const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, uint32_t id_flags, uint64_t* out,
                      uint32_t* counts, vc_query_stats* stats) override {
     return vc_sharded_search_knn_ids(h_, ids, nq, k, mode, order, id_flags, out, counts, stats);
+  }
+  int search_radius_ids(const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* out, uint64_t out_cap,
+                        uint64_t* out_offsets) override {
+    return vc_sharded_search_radius_ids(h_, ids, nq, radius, mode, id_flags, out, out_cap, out_offsets);
   }
  private:
   vc_sharded* h_ = nullptr;
@@ -452,6 +464,23 @@ class image_search_client {
         all[q].push_back({(uint32_t)(v & 0xffffffffu), (uint32_t)(v >> 32)});
       }
     return all;
+  }
+  // "Which images lie within `radius` of image `id`": (image id, distance) pairs formed as search_image_by_id forms them, NEAREST
+  // first; by default without the image itself (VC_IDS_ONLY_GREATER lists every pair of a walk over all ids once).  Exact: MIH where
+  // the store has tables, else the linear scan.  An id that is not in the database gives an empty list.
+  std::list<std::pair<uint32_t, uint32_t> > search_image_by_id_within(uint32_t id, uint32_t radius, uint32_t id_flags = VC_IDS_EXCLUDE_SELF) {
+    const uint32_t mode = e_->n_tables() ? VC_MODE_MIH_EXACT : VC_MODE_LINEAR;
+    uint64_t offs[2] = {0, 0};
+    std::vector<uint64_t> res;
+    int rc = e_->search_radius_ids(&id, 1, radius, mode, id_flags, nullptr, 0, offs);   // the size first
+    if (rc == VC_ERR_CAPACITY) {
+      res.resize(offs[1]);
+      rc = e_->search_radius_ids(&id, 1, radius, mode, id_flags, res.data(), res.size(), offs);
+    }
+    e_->check(rc);
+    std::list<std::pair<uint32_t, uint32_t> > out;
+    for (uint64_t i = offs[0]; i < offs[1]; ++i) out.push_back({(uint32_t)(res[i] & 0xffffffffu), (uint32_t)(res[i] >> 32)});
+    return out;
   }
  private:
   Backend* e_;
