@@ -323,6 +323,42 @@ int vc_search_radius_ids_dev(vc_engine* e, const uint32_t* d_ids, uint32_t nq, u
 int vc_search_radius_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags,
                          uint64_t* out, uint64_t out_cap, uint64_t* out_offsets);
 
+/* "Which records are near-duplicates of each other", as a grouping: the connected components of the radius graph over ALL resident
+ * records (two records are adjacent when their full Hamming distance is <= `radius`; a group is what chains of adjacent records
+ * connect).  It replaces a walk of vc_search_radius_ids_dev with VC_IDS_ONLY_GREATER over all ids, the copy home of every pair and
+ * a host union-find: the pairs never leave HBM, and the search's raw result is united as it lies, without the compaction.
+ * labels: N = vc_size entries.  labels[i] = the GLOBAL id of the smallest-id record of the component of record id_base + i -- a
+ * function of the database and the radius only, whatever `batch`, `mode` or the order the device worked in.
+ * mode VC_MODE_LINEAR or VC_MODE_MIH_EXACT.  Errors are checked before any work and leave labels untouched: VC_ERR_INVALID for
+ * another mode, null labels or n_labelled > N; VC_ERR_STATE in MIH mode without a current index (a stale one counts as none, as in
+ * vc_search_radius_ids).  N == 0 gives VC_OK and zero stats; nothing is written.
+ * batch: ids per radius search underneath, 0 = 4096; any value >= 1 is legal, larger than N too; the result does not depend on it.
+ * n_labelled is the incremental form, the companion of vc_update_index: labels[0 .. n_labelled) come IN and entries from n_labelled
+ * on are ignored and overwritten.  PRECONDITION: the incoming labels are what this call produced for the first n_labelled records
+ * ALONE (a store that held exactly those records), at this same radius.  Only the ids id_base + n_labelled .. are queried; of a
+ * query's entries those are united whose id exceeds the query's own or lies below id_base + n_labelled, so every pair with an old
+ * member is seen from its new member and every new-new pair once.  The result is bit for bit that of a call from scratch
+ * (n_labelled == 0) over all N records -- old groups that a new record bridges are merged.  n_labelled == N only re-flattens and
+ * counts.
+ * stats (host memory, may be NULL) is filled when the call returns.
+ * Device form: d_labels IS the union-find forest, in place, and must not be touched by the caller during the call.  Everything is
+ * enqueued on `stream`; the host waits where the radius search underneath waits -- once per batch and attempt, for its total -- and
+ * once more at the end, for the stats.  Labels are valid in stream order.
+ * The scratch (the batch's ids, gathered queries, found words, the raw results and their offsets, two counters) is grow-only
+ * buffers of the handle, separate from those of every other call, every word written before it is read within a call: a result
+ * depends on the database and the call only.  The raw results grow to the LARGEST batch's total: on duplicate-heavy data that is
+ * `batch` x the size of a group of duplicates (4096 ids into a bucket of 250 000 are 8 GB), so choose a smaller batch there. */
+typedef struct vc_cluster_stats {
+  uint64_t n_pairs;     /* unordered pairs {a < b} within `radius` that this call examined: all those with b >= n_labelled */
+  uint64_t n_clusters;  /* components over ALL resident records after the call */
+} vc_cluster_stats;
+int vc_cluster_radius_dev(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
+                          vc_cluster_stats* stats, void* stream);
+/* The same for labels in host memory: the device form on the engine's stream plus the staged labels (the first n_labelled go in,
+ * all N come home); waits for them. */
+int vc_cluster_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
+                      vc_cluster_stats* stats);
+
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
  * seconds); the affected queries kept d_counts[i] == UINT32_MAX.  0 in normal operation.  Synchronises the stream.
@@ -456,6 +492,15 @@ int vc_sharded_search_radius_ids_dev(vc_sharded* h, const uint32_t* d_ids, uint3
                                      uint64_t* d_out, uint64_t out_cap, uint64_t* d_offsets, void* stream);
 int vc_sharded_search_radius_ids(vc_sharded* h, const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags,
                                  uint64_t* out, uint64_t out_cap, uint64_t* out_offsets);
+/* Near-duplicate clustering over all shards: contract, modes, errors, batch, n_labelled (the companion of vc_sharded_update_index)
+ * and stats as vc_cluster_radius_dev / vc_cluster_radius, with N = vc_sharded_size and ids global over the whole store -- the
+ * resident ids are contiguous because the id-range shards fill in order.  d_labels lives on the ROOT device, `stream` is a stream
+ * of that device.  The search underneath is vc_sharded_search_radius_dev into scratch on the root, the batch's ids are gathered as
+ * in vc_sharded_get_codes_dev, and the union runs on the root.  VC_FLAG_GLOBAL_STOP and VC_FLAG_GLOBAL_APPROX play no part. */
+int vc_sharded_cluster_radius_dev(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
+                                  vc_cluster_stats* stats, void* stream);
+int vc_sharded_cluster_radius(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
+                              vc_cluster_stats* stats);
 /* borrow shard g's engine (bucket views, timing, files); its id range is [*first_id, *first_id + *n_ids) */
 int vc_sharded_shard(vc_sharded* h, uint32_t shard, vc_engine** e, uint64_t* first_id, uint64_t* n_ids);
 

@@ -1,0 +1,136 @@
+// ============================================================================
+// vc_cluster.hip -- near-duplicate clustering on the device (vc_cluster_radius*, vc_sharded_cluster_radius*): the connected
+// components of the radius graph, by a lock-free union-find over the RAW result of the radius search underneath.  No compaction,
+// no plan, no LDS: the union needs neither sorted nor gap-free segments.
+// ============================================================================
+#include <algorithm>
+
+#include "vc_internal.hpp"
+
+// labels[] IS the forest, in place: slot i (record id_base + i) holds the GLOBAL id of the record's parent, a root holds its own id.
+// Ids stay below 2^32, so unsigned compares on global ids are the order.  Three invariants hold after every single store:
+//   (1) a parent never exceeds its child: parent(x) <= x, with equality exactly at a root;
+//   (2) only a root's slot is CAS-ed, from "itself" to a smaller id -- a record that stopped being a root never becomes one again;
+//   (3) path halving stores an ancestor of the same tree (the grandparent read a moment ago) into a slot that is no root.
+// From (1): every chain strictly descends, so every walk ends and the forest is acyclic under any interleaving.  From (2) and (3):
+// a store moves a subtree below a smaller record of a tree it is, or becomes, part of -- trees merge and never split, and two records
+// are in one tree exactly when the unions made so far connect them.  From (1) again: the root of a tree is its smallest id.  Once
+// every kept entry has been united the trees are the components of the radius graph, so the flattened label of a record -- the
+// smallest id of its component -- depends on the database and the radius only, not on the order in which the lanes arrived.
+//   vc_cluster_init_kernel     dst[j] = first + j: the labels of the records that come in unlabelled, and a batch's ids
+//   vc_cluster_union_kernel    one thread per entry of the flat raw result: its query by binary search, the keep rule, the union
+//   vc_cluster_flatten_kernel  labels[i] = root of i, in place; counts the roots
+// Slots are read and written with relaxed device-scope atomics (no stale line of a CU's L1 is ever walked), hooked with atomicCAS.
+#define CL_BLK 256u
+
+__device__ __forceinline__ uint32_t cl_ld(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void cl_st(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root of global id x, halving the path on the way: x's slot gets its grandparent, the walk goes on from there
+__device__ __forceinline__ uint32_t cl_find_halving(uint32_t* labels, uint32_t id_base, uint32_t x) {
+  uint32_t p = cl_ld(labels + (x - id_base));
+  while (p != x) {
+    const uint32_t gp = cl_ld(labels + (p - id_base));
+    if (gp == p) return p;
+    cl_st(labels + (x - id_base), gp);   // (3): x is no root (p < x), gp <= p is an ancestor of x
+    x = gp;
+    p = cl_ld(labels + (x - id_base));
+  }
+  return x;
+}
+
+// the root of x by reads alone
+__device__ __forceinline__ uint32_t cl_find(const uint32_t* labels, uint32_t id_base, uint32_t x) {
+  for (;;) {
+    const uint32_t p = cl_ld(labels + (x - id_base));
+    if (p == x) return x;
+    x = p;
+  }
+}
+
+__global__ void __launch_bounds__(CL_BLK) vc_cluster_init_kernel(uint32_t* __restrict__ dst, uint64_t count, uint32_t first) {
+  for (uint64_t j = (uint64_t)blockIdx.x * CL_BLK + threadIdx.x; j < count; j += (uint64_t)gridDim.x * CL_BLK) dst[j] = first + (uint32_t)j;
+}
+
+// raw / roffs: the flat result of the radius search for the queries first_id + 0 .. first_id + nq - 1 and its nq + 1 offsets; total =
+// roffs[nq].  Entry p belongs to the last query q with roffs[q] <= p (queries without entries share their successor's offset and are
+// passed over); the 64 consecutive entries of a wave mostly share one query, so the search's loads are broadcasts out of the cache.
+// KEEP RULE: the entry (dist, v) of the query with id `own` is united when v > own, or when v < first_new = id_base + n_labelled:
+// every pair of new records is seen once, from its smaller member, and every pair with an old member from its new one (old records
+// are not queried).  The own entry and the smaller new ids are dropped.  *n_pairs += the kept entries, one add per wave.
+__global__ void __launch_bounds__(CL_BLK) vc_cluster_union_kernel(const uint64_t* __restrict__ raw, const uint64_t* __restrict__ roffs, uint32_t nq,
+                                                                  uint64_t total, uint32_t first_id, uint64_t first_new, uint32_t id_base,
+                                                                  uint32_t* labels, unsigned long long* __restrict__ n_pairs) {
+  uint32_t kept = 0;   // wave-uniform
+  for (uint64_t p0 = (uint64_t)blockIdx.x * CL_BLK; p0 < total; p0 += (uint64_t)gridDim.x * CL_BLK) {   // (block-uniform bounds: every lane votes)
+    const uint64_t p = p0 + threadIdx.x;
+    bool keep = false;
+    uint32_t own = 0, v = 0;
+    if (p < total) {
+      uint32_t lo = 0, hi = nq;   // roffs[lo] <= p < roffs[hi]
+      while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (roffs[mid] <= p) lo = mid; else hi = mid;
+      }
+      own = first_id + lo;
+      v = (uint32_t)raw[p];
+      keep = v > own || (uint64_t)v < first_new;
+    }
+    kept += (uint32_t)__popcll(__ballot(keep));
+    if (keep) {
+      uint32_t a = own, b = v;
+      for (;;) {
+        a = cl_find_halving(labels, id_base, a);
+        b = cl_find_halving(labels, id_base, b);
+        if (a == b) break;
+        const uint32_t big = a > b ? a : b, small = a > b ? b : a;
+        // (2): hook the LARGER root under the smaller, on the larger root's own slot, expecting it to be a root still.  `small`
+        // may have stopped being a root meanwhile: it is smaller all the same, (1) holds, and the trees are merged.
+        if (atomicCAS(labels + (big - id_base), big, small) == big) break;
+        // somebody else hooked `big`: that is progress of the whole; find again from the two records reached
+      }
+    }
+  }
+  if (vc_lane() == 0 && kept) atomicAdd(n_pairs, (unsigned long long)kept);
+}
+
+// In place, race-free against itself: a walk only reads, and record i writes only its own slot, with its root.  A walk that passes
+// through a slot already written reads that root -- still an ancestor chain ending in the same root -- so every record stores the
+// same value whatever the order.  A root's slot is rewritten with itself.  *n_clusters += the roots, one add per wave.
+__global__ void __launch_bounds__(CL_BLK) vc_cluster_flatten_kernel(uint32_t* labels, uint64_t n, uint32_t id_base,
+                                                                    unsigned long long* __restrict__ n_clusters) {
+  uint32_t roots = 0;   // wave-uniform
+  for (uint64_t i0 = (uint64_t)blockIdx.x * CL_BLK; i0 < n; i0 += (uint64_t)gridDim.x * CL_BLK) {
+    const uint64_t i = i0 + threadIdx.x;
+    bool is_root = false;
+    if (i < n) {
+      const uint32_t x = id_base + (uint32_t)i, r = cl_find(labels, id_base, x);
+      cl_st(labels + i, r);
+      is_root = r == x;
+    }
+    roots += (uint32_t)__popcll(__ballot(is_root));
+  }
+  if (vc_lane() == 0 && roots) atomicAdd(n_clusters, (unsigned long long)roots);
+}
+
+static uint32_t cl_grid(uint64_t items) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + CL_BLK - 1) / CL_BLK, 1), 256 * 8); }
+
+hipError_t vc_launch_cluster_init(uint32_t* d_dst, uint64_t count, uint32_t first, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(vc_cluster_init_kernel, dim3(cl_grid(count)), dim3(CL_BLK), 0, s, d_dst, count, first);
+  return hipGetLastError();
+}
+
+hipError_t vc_launch_cluster_union(const uint64_t* d_raw, const uint64_t* d_roffs, uint32_t nq, uint64_t total, uint32_t first_id, uint64_t first_new,
+                                   uint32_t id_base, uint32_t* d_labels, uint64_t* d_n_pairs, hipStream_t s) {
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL(vc_cluster_union_kernel, dim3(cl_grid(total)), dim3(CL_BLK), 0, s, d_raw, d_roffs, nq, total, first_id, first_new, id_base, d_labels,
+                     (unsigned long long*)d_n_pairs);
+  return hipGetLastError();
+}
+
+hipError_t vc_launch_cluster_flatten(uint32_t* d_labels, uint64_t n, uint32_t id_base, uint64_t* d_n_clusters, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(vc_cluster_flatten_kernel, dim3(cl_grid(n)), dim3(CL_BLK), 0, s, d_labels, n, id_base, (unsigned long long*)d_n_clusters);
+  return hipGetLastError();
+}

@@ -58,6 +58,15 @@ struct vc_engine {
   uint32_t* d_rhids = nullptr;  size_t rhids_bytes = 0;
   uint64_t* d_rhout = nullptr;  size_t rhout_bytes = 0;
   uint64_t* d_rhoffs = nullptr; size_t rhoffs_bytes = 0;
+  // near-duplicate clustering (vc_cluster_radius*): a batch's ids, gathered queries and found words, the raw results and offsets of
+  // the search underneath, the two counters (pairs, clusters); and the host-pointer form's staged labels
+  uint32_t* d_cids = nullptr;   size_t cids_bytes = 0;
+  uint64_t* d_cq = nullptr;     size_t cq_bytes = 0;
+  uint32_t* d_cfound = nullptr; size_t cfound_bytes = 0;
+  uint64_t* d_craw = nullptr;   size_t craw_bytes = 0;
+  uint64_t* d_croffs = nullptr; size_t croffs_bytes = 0;
+  uint64_t* d_cstat = nullptr;  size_t cstat_bytes = 0;
+  uint32_t* d_chlab = nullptr;  size_t chlab_bytes = 0;
   CleanState clean;                                       // the last kernel of a linear step hands d_state back zeroed: no memset per step
   uint32_t scan_event_tick = 0;                           // VC_FLAG_LEAN_TIMING: only every timing_sample-th verify launch is timed
   VcKnobs knobs;                                          // environment knobs, read once at vc_create
@@ -344,6 +353,13 @@ int vc_destroy(vc_engine* e) {
   (void)hipFree(e->d_rhids);
   (void)hipFree(e->d_rhout);
   (void)hipFree(e->d_rhoffs);
+  (void)hipFree(e->d_cids);
+  (void)hipFree(e->d_cq);
+  (void)hipFree(e->d_cfound);
+  (void)hipFree(e->d_craw);
+  (void)hipFree(e->d_croffs);
+  (void)hipFree(e->d_cstat);
+  (void)hipFree(e->d_chlab);
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->last_call) (void)hipEventDestroy(e->last_call);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -1226,6 +1242,92 @@ int vc_search_radius_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_
     VC_HIP(e, hipStreamSynchronize(e->stream));
   }
   return rc;
+}
+
+}  // extern "C"
+
+// ---- near-duplicate clustering: the connected components of the radius graph ----------------------------------------------------------
+static int check_cluster_args(vc_engine* e, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
+  if (!e || !labels) return VC_ERR_INVALID;
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "cluster: mode must be LINEAR or MIH_EXACT");
+  if (n_labelled > e->n) return fail(e, VC_ERR_INVALID, "cluster: n_labelled %llu exceeds the %llu resident records", (unsigned long long)n_labelled, (unsigned long long)e->n);
+  if (e->n && mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
+  return VC_OK;
+}
+
+// The whole call on e->stream (inside the caller's StreamCall), e->n > 0.  Per batch of ids: the ids filled on the device, the gather,
+// the radius search into the handle's scratch -- repeated once with the scratch grown to the total it reported -- and the union over
+// the raw result as it lies; no compaction.  After the last batch one flatten, then the one wait for the two counters.
+static int cluster_run(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_cluster_stats* stats) {
+  int rc;
+  const uint64_t N = e->n, first_new = (uint64_t)e->cfg.id_base + n_labelled;
+  if (batch == 0) batch = VC_CLUSTER_BATCH;
+  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N - n_labelled);
+  if ((rc = grow(e, &e->d_cstat, &e->cstat_bytes, 16))) return rc;
+  if (nq_max) {
+    if ((rc = grow(e, &e->d_cids, &e->cids_bytes, (size_t)nq_max * 4))) return rc;
+    if ((rc = grow(e, &e->d_cq, &e->cq_bytes, (size_t)nq_max * e->W * 8))) return rc;
+    if ((rc = grow(e, &e->d_cfound, &e->cfound_bytes, (size_t)nq_max * 4))) return rc;
+    if ((rc = grow(e, &e->d_croffs, &e->croffs_bytes, ((size_t)nq_max + 1) * 8))) return rc;
+    if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)8 << 16))) return rc;
+  }
+  VC_HIP(e, hipMemsetAsync(e->d_cstat, 0, 16, e->stream));
+  VC_HIP(e, vc_launch_cluster_init(d_labels + n_labelled, N - n_labelled, (uint32_t)first_new, e->stream));
+  for (uint64_t pos = n_labelled; pos < N; pos += batch) {
+    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = e->cfg.id_base + (uint32_t)pos;
+    VC_HIP(e, vc_launch_cluster_init(e->d_cids, nq, first_id, e->stream));
+    VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, e->d_cids, nq, e->d_cq, e->d_cfound, e->stream));
+    uint64_t raw_total = 0;
+    for (int attempt = 0;; ++attempt) {
+      const uint64_t cap = e->craw_bytes / 8;
+      rc = vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, e->d_cq, nq,
+                            radius, e->d_craw, cap, e->d_croffs, true, &e->radius_work, e->stream, &e->err, &raw_total);
+      if (rc == VC_OK) break;
+      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
+      if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)raw_total * 8))) return rc;   // (the first attempt has been waited for)
+    }
+    VC_HIP(e, vc_launch_cluster_union(e->d_craw, e->d_croffs, nq, raw_total, first_id, first_new, e->cfg.id_base, d_labels, e->d_cstat, e->stream));
+  }
+  VC_HIP(e, vc_launch_cluster_flatten(d_labels, N, e->cfg.id_base, e->d_cstat + 1, e->stream));
+  uint64_t st[2] = {0, 0};
+  VC_HIP(e, hipMemcpyAsync(st, e->d_cstat, 16, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipStreamSynchronize(e->stream));
+  if (stats) {
+    stats->n_pairs = st[0];
+    stats->n_clusters = st[1];
+  }
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_cluster_radius_dev(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
+                          vc_cluster_stats* stats, void* stream) {
+  int rc = check_cluster_args(e, mode, n_labelled, d_labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_cluster_stats{0, 0};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, caller_stream(e, stream));
+  return cluster_run(e, radius, mode, batch, n_labelled, d_labels, stats);
+}
+
+int vc_cluster_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats) {
+  int rc = check_cluster_args(e, mode, n_labelled, labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_cluster_stats{0, 0};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  if ((rc = grow(e, &e->d_chlab, &e->chlab_bytes, (size_t)e->n * 4))) return rc;
+  if (n_labelled) VC_HIP(e, hipMemcpyAsync(e->d_chlab, labels, (size_t)n_labelled * 4, hipMemcpyHostToDevice, e->stream));
+  {
+    const StreamCall call(e, e->stream);
+    rc = cluster_run(e, radius, mode, batch, n_labelled, e->d_chlab, stats);
+  }
+  if (rc) return rc;
+  VC_HIP(e, hipMemcpyAsync(labels, e->d_chlab, (size_t)e->n * 4, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipStreamSynchronize(e->stream));
+  return VC_OK;
 }
 
 }  // extern "C"

@@ -190,6 +190,17 @@ hipError_t vc_launch_ids_radius_count(const VcIdsRadiusWork& w, const uint64_t* 
 // the kept entries, in order, to d_out[d_offsets[q] ..): the caller has made sure that *w.total entries fit
 hipError_t vc_launch_ids_radius_copy(const VcIdsRadiusWork& w, const uint64_t* d_raw, const uint64_t* d_roffs, const uint32_t* d_ids, uint32_t nq,
                                      uint32_t id_flags, const uint64_t* d_offsets, uint64_t* d_out, hipStream_t s);
+// ---- vc_cluster.hip: near-duplicate clustering (vc_cluster_radius*).  d_labels [n] is the union-find forest in place: slot i holds
+// the global id of the parent of record id_base + i, never greater than id_base + i.  Nothing here waits.
+#define VC_CLUSTER_BATCH 4096u   // ids per radius search underneath when the caller passes batch = 0
+// d_dst[j] = first + j for j < count: the labels of the records that come in unlabelled, and the ids of a batch
+hipError_t vc_launch_cluster_init(uint32_t* d_dst, uint64_t count, uint32_t first, hipStream_t s);
+// unites every kept entry of the raw result (d_raw, its nq + 1 offsets d_roffs, total = d_roffs[nq]) of the queries first_id ..
+// first_id + nq - 1 with its query: kept = id > the query's own, or id < first_new (= id_base + n_labelled); *d_n_pairs += the kept
+hipError_t vc_launch_cluster_union(const uint64_t* d_raw, const uint64_t* d_roffs, uint32_t nq, uint64_t total, uint32_t first_id, uint64_t first_new,
+                                   uint32_t id_base, uint32_t* d_labels, uint64_t* d_n_pairs, hipStream_t s);
+// d_labels[i] = the root of record i (the smallest id of its component), in place; *d_n_clusters += the roots
+hipError_t vc_launch_cluster_flatten(uint32_t* d_labels, uint64_t n, uint32_t id_base, uint64_t* d_n_clusters, hipStream_t s);
 // ---- vc_engine.hip: what the sharded store's global stop (vc_sharded.hip) needs of a shard's engine
 struct VcEngineView {
   const uint64_t* cols;   // column-major codes, word j of record i at cols[j * stride + i]

@@ -128,6 +128,9 @@ enum RootBuf {
   // radius search by id: gathered queries, found words, the union's uncompacted results and offsets, the compaction's counts
   // (VcIdsRadiusWork); the host-pointer form's staged ids, results and offsets
   RIDS_Q, RIDS_FOUND, RIDS_RAW, RIDS_ROFFS, RIDS_WORK, RIDS_HIDS, RIDS_HOUT, RIDS_HOFFS,
+  // near-duplicate clustering: a batch's ids, gathered queries and found words, the union's raw results and offsets, the two
+  // counters (pairs, clusters); the host-pointer form's staged labels
+  CL_IDS, CL_Q, CL_FOUND, CL_RAW, CL_ROFFS, CL_STAT, CL_HLAB,
   ROOT_BUFS
 };
 
@@ -2069,6 +2072,99 @@ int vc_sharded_search_radius_ids(vc_sharded* h, const uint32_t* ids, uint32_t nq
     VS_HIP(h, hipStreamSynchronize(S));
   }
   return rc;
+}
+
+}  // extern "C"
+
+// ---- near-duplicate clustering over the shards ----------------------------------------------------------------------------------------
+static int check_sharded_cluster_args(vc_sharded* h, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
+  if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
+  if (n_labelled > h->n) return sfail(h, VC_ERR_INVALID, "cluster: n_labelled %llu exceeds the %llu resident records", (unsigned long long)n_labelled, (unsigned long long)h->n);
+  if (mode == VC_MODE_MIH_EXACT)
+    for (uint32_t g = 0; g < h->G; ++g)
+      if (shard_size(h, g) && !vc_engine_has_index(h->eng[g])) return sfail(h, VC_ERR_STATE, "shard %u: MIH search needs vc_sharded_build_index() first", g);
+  return VC_OK;
+}
+
+// All on the root device's stream S, h->n > 0.  Per batch of global ids: the ids filled on the root, the gather over the shards, the
+// union's radius search into the handle's scratch -- repeated once with the scratch grown to the total it reported -- and the
+// union-find over the raw result on the root; after the last batch one flatten, then the one wait for the two counters.
+static int sharded_cluster_run(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
+                               vc_cluster_stats* stats, hipStream_t S) {
+  int rc;
+  const uint32_t id_base = h->cfg.engine.id_base;
+  const uint64_t N = h->n, first_new = (uint64_t)id_base + n_labelled;
+  if (batch == 0) batch = VC_CLUSTER_BATCH;
+  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N - n_labelled);
+  VS_HIP(h, hipSetDevice(h->root));
+  if ((rc = h->buf[CL_STAT].grow(h, 16))) return rc;
+  if (nq_max) {
+    if ((rc = h->buf[CL_IDS].grow(h, (size_t)nq_max * 4))) return rc;
+    if ((rc = h->buf[CL_Q].grow(h, (size_t)nq_max * h->nbytes))) return rc;
+    if ((rc = h->buf[CL_FOUND].grow(h, (size_t)nq_max * 4))) return rc;
+    if ((rc = h->buf[CL_ROFFS].grow(h, ((size_t)nq_max + 1) * 8))) return rc;
+    if ((rc = h->buf[CL_RAW].grow(h, (size_t)8 << 16))) return rc;
+  }
+  uint64_t* d_stat = h->buf[CL_STAT].as<uint64_t>();
+  uint32_t* d_ids = h->buf[CL_IDS].as<uint32_t>();
+  VS_HIP(h, hipMemsetAsync(d_stat, 0, 16, S));
+  VS_HIP(h, vc_launch_cluster_init(d_labels + n_labelled, N - n_labelled, (uint32_t)first_new, S));
+  for (uint64_t pos = n_labelled; pos < N; pos += batch) {
+    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = id_base + (uint32_t)pos;
+    VS_HIP(h, hipSetDevice(h->root));
+    VS_HIP(h, vc_launch_cluster_init(d_ids, nq, first_id, S));
+    if ((rc = sharded_gather_ids(h, d_ids, nq, h->buf[CL_Q].as<uint64_t>(), h->buf[CL_FOUND].as<uint32_t>(), true, S))) return rc;
+    uint64_t raw_total = 0;
+    for (int attempt = 0;; ++attempt) {
+      const uint64_t cap = h->buf[CL_RAW].bytes / 8;
+      rc = sharded_radius_dev(h, h->buf[CL_Q].p, nq, radius, mode, h->buf[CL_RAW].as<uint64_t>(), cap, h->buf[CL_ROFFS].as<uint64_t>(), S, &raw_total);
+      if (rc == VC_OK) break;
+      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
+      VS_HIP(h, hipSetDevice(h->root));
+      if ((rc = h->buf[CL_RAW].grow(h, (size_t)raw_total * 8))) return rc;
+    }
+    VS_HIP(h, hipSetDevice(h->root));
+    VS_HIP(h, vc_launch_cluster_union(h->buf[CL_RAW].as<uint64_t>(), h->buf[CL_ROFFS].as<uint64_t>(), nq, raw_total, first_id, first_new, id_base, d_labels,
+                                      d_stat, S));
+  }
+  VS_HIP(h, hipSetDevice(h->root));
+  VS_HIP(h, vc_launch_cluster_flatten(d_labels, N, id_base, d_stat + 1, S));
+  uint64_t st[2] = {0, 0};
+  VS_HIP(h, hipMemcpyAsync(st, d_stat, 16, hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipStreamSynchronize(S));
+  if (stats) {
+    stats->n_pairs = st[0];
+    stats->n_clusters = st[1];
+  }
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_sharded_cluster_radius_dev(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
+                                  vc_cluster_stats* stats, void* stream) {
+  int rc = check_sharded_cluster_args(h, mode, n_labelled, d_labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_cluster_stats{0, 0};
+  if (h->n == 0) return VC_OK;
+  return sharded_cluster_run(h, radius, mode, batch, n_labelled, d_labels, stats, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+}
+
+int vc_sharded_cluster_radius(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
+                              vc_cluster_stats* stats) {
+  int rc = check_sharded_cluster_args(h, mode, n_labelled, labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_cluster_stats{0, 0};
+  if (h->n == 0) return VC_OK;
+  hipStream_t S = h->root_stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  if ((rc = h->buf[CL_HLAB].grow(h, (size_t)h->n * 4))) return rc;
+  if (n_labelled) VS_HIP(h, hipMemcpyAsync(h->buf[CL_HLAB].p, labels, (size_t)n_labelled * 4, hipMemcpyHostToDevice, S));
+  if ((rc = sharded_cluster_run(h, radius, mode, batch, n_labelled, h->buf[CL_HLAB].as<uint32_t>(), stats, S))) return rc;
+  VS_HIP(h, hipSetDevice(h->root));
+  VS_HIP(h, hipMemcpyAsync(labels, h->buf[CL_HLAB].p, (size_t)h->n * 4, hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipStreamSynchronize(S));
+  return VC_OK;
 }
 
 }  // extern "C"

@@ -40,6 +40,7 @@ EXPORTS = [
     "vc_sharded_get_codes_dev", "vc_sharded_search_knn_ids", "vc_sharded_search_knn_ids_dev",
     "vc_search_radius_ids", "vc_search_radius_ids_dev", "vc_sharded_search_radius_ids", "vc_sharded_search_radius_ids_dev",
     "vc_update_index", "vc_sharded_update_index",
+    "vc_cluster_radius", "vc_cluster_radius_dev", "vc_sharded_cluster_radius", "vc_sharded_cluster_radius_dev",
 ]
 MAX_SHARDS = 16
 EXCHANGE_AUTO, EXCHANGE_PEER_COPY, EXCHANGE_RCCL = 0, 1, 2
@@ -65,6 +66,10 @@ class VcQueryStats(C.Structure):
         ("radius", C.c_uint32), ("n_results", C.c_uint32), ("n_main_reads", C.c_uint64), ("n_sub_reads", C.c_uint64),
         ("n_local_reads", C.c_uint64), ("n_candidates", C.c_uint64),
     ]
+
+
+class VcClusterStats(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("n_clusters", C.c_uint64)]
 
 
 class VcTiming(C.Structure):
@@ -161,6 +166,10 @@ def load_library():
     L.vc_search_radius_ids_dev.argtypes = [vp, vp, u32, u32, u32, u32, vp, u64, vp, vp]
     L.vc_sharded_search_radius_ids.argtypes = [vp, vp, u32, u32, u32, u32, vp, u64, vp]
     L.vc_sharded_search_radius_ids_dev.argtypes = [vp, vp, u32, u32, u32, u32, vp, u64, vp, vp]
+    L.vc_cluster_radius.argtypes = [vp, u32, u32, u32, u64, vp, vp]
+    L.vc_cluster_radius_dev.argtypes = [vp, u32, u32, u32, u64, vp, vp, vp]
+    L.vc_sharded_cluster_radius.argtypes = [vp, u32, u32, u32, u64, vp, vp]
+    L.vc_sharded_cluster_radius_dev.argtypes = [vp, u32, u32, u32, u64, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -199,6 +208,28 @@ def _search_radius_ids(self, fn, ids, radius, mode, id_flags, cap_per_query):
             return [out[int(offs[i]):int(offs[i + 1])].copy() for i in range(nq)]
         cap = int(offs[nq])
     raise VcError(VC_ERR_CAPACITY, "radius search output does not fit")
+
+
+def _cluster_radius(self, fn, radius, mode, batch, labels):
+    """shared by Engine.cluster_radius and ShardedEngine.cluster_radius: (labels [N] uint32, n_pairs, n_clusters)"""
+    n = len(self)
+    out = np.empty(n, dtype=np.uint32)
+    n_labelled = 0
+    if labels is not None:
+        old = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+        n_labelled = old.shape[0]
+        if n_labelled > n:
+            raise VcError(VC_ERR_INVALID, "more labels than resident records")
+        out[:n_labelled] = old
+    st = VcClusterStats()
+    self._check(fn(self._h, radius, mode, batch, n_labelled, _p(out), C.byref(st)))
+    return out, int(st.n_pairs), int(st.n_clusters)
+
+
+def _cluster_radius_dev(self, fn, radius, d_labels, mode, batch, n_labelled, stream):
+    st = VcClusterStats()
+    self._check(fn(self._h, radius, mode, batch, n_labelled, d_labels, C.byref(st), stream))
+    return int(st.n_pairs), int(st.n_clusters)
 
 
 def split(packed):
@@ -414,6 +445,18 @@ class Engine:
         return self._check(self._L.vc_search_radius_ids_dev(self._h, d_ids, nq, radius, mode, id_flags, d_out, out_cap, d_offsets, stream),
                            ok=(VC_OK, VC_ERR_CAPACITY))
 
+    def cluster_radius(self, radius, mode=MODE_LINEAR, batch=0, labels=None):
+        """vc_cluster_radius: the connected components of the radius graph over all resident records.  Returns (labels, n_pairs,
+        n_clusters): labels[i] = the global id of the smallest-id record of the component of record id_base + i.  `labels`: what
+        an earlier call at this radius returned for the first len(labels) records alone -- only the records behind them are
+        queried (the incremental form, after add_codes + update_index); the result equals a call from scratch."""
+        return _cluster_radius(self, self._L.vc_cluster_radius, radius, mode, batch, labels)
+
+    def cluster_radius_dev(self, radius, d_labels, mode=MODE_MIH_EXACT, batch=0, n_labelled=0, stream=None):
+        """vc_cluster_radius_dev: d_labels = the raw device address of len(self) uint32, the union-find forest in place (its first n_labelled
+        entries come in); labels valid in `stream` order.  Returns (n_pairs, n_clusters)."""
+        return _cluster_radius_dev(self, self._L.vc_cluster_radius_dev, radius, d_labels, mode, batch, n_labelled, stream)
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -581,6 +624,18 @@ class ShardedEngine:
         or VC_ERR_CAPACITY (d_offsets then holds the compacted prefix sums, d_offsets[nq] the total; d_out is untouched)."""
         return self._check(self._L.vc_sharded_search_radius_ids_dev(self._h, d_ids, nq, radius, mode, id_flags, d_out, out_cap, d_offsets,
                                                                     stream), ok=(VC_OK, VC_ERR_CAPACITY))
+
+    def cluster_radius(self, radius, mode=MODE_LINEAR, batch=0, labels=None):
+        """vc_sharded_cluster_radius: the connected components of the radius graph over all resident records.  Returns (labels, n_pairs,
+        n_clusters): labels[i] = the global id of the smallest-id record of the component of record id_base + i.  `labels`: what
+        an earlier call at this radius returned for the first len(labels) records alone -- only the records behind them are
+        queried (the incremental form, after add_codes + update_index); the result equals a call from scratch."""
+        return _cluster_radius(self, self._L.vc_sharded_cluster_radius, radius, mode, batch, labels)
+
+    def cluster_radius_dev(self, radius, d_labels, mode=MODE_MIH_EXACT, batch=0, n_labelled=0, stream=None):
+        """vc_sharded_cluster_radius_dev: d_labels = the raw device address of len(self) uint32 on the root device, the union-find forest in place (its first n_labelled
+        entries come in); labels valid in `stream` order.  Returns (n_pairs, n_clusters)."""
+        return _cluster_radius_dev(self, self._L.vc_sharded_cluster_radius_dev, radius, d_labels, mode, batch, n_labelled, stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

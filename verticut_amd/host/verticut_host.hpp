@@ -118,6 +118,9 @@ class Backend {
   // all items within `radius` of a batch of records named by id (vc_search_radius_ids / vc_sharded_search_radius_ids)
   virtual int search_radius_ids(const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* out,
                                 uint64_t out_cap, uint64_t* out_offsets) = 0;
+  // near-duplicate groups: labels[i] = smallest id of the component of record i in the radius graph (vc_cluster_radius /
+  // vc_sharded_cluster_radius; labels[0 .. n_labelled) come in for the incremental form)
+  virtual int cluster_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats) = 0;
 };
 
 // Owns one vc_engine (one shard / GPU).
@@ -168,6 +171,9 @@ class Engine : public Backend {
   int search_radius_ids(const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* out, uint64_t out_cap,
                         uint64_t* out_offsets) override {
     return vc_search_radius_ids(h_, ids, nq, radius, mode, id_flags, out, out_cap, out_offsets);
+  }
+  int cluster_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats) override {
+    return vc_cluster_radius(h_, radius, mode, batch, n_labelled, labels, stats);
   }
  private:
   vc_engine* h_ = nullptr;
@@ -248,6 +254,9 @@ class ShardedEngine : public Backend {
   int search_radius_ids(const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* out, uint64_t out_cap,
                         uint64_t* out_offsets) override {
     return vc_sharded_search_radius_ids(h_, ids, nq, radius, mode, id_flags, out, out_cap, out_offsets);
+  }
+  int cluster_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats) override {
+    return vc_sharded_cluster_radius(h_, radius, mode, batch, n_labelled, labels, stats);
   }
  private:
   vc_sharded* h_ = nullptr;
