@@ -359,6 +359,43 @@ int vc_cluster_radius_dev(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t
 int vc_cluster_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
                       vc_cluster_stats* stats);
 
+/* "Take these records out": the store and its index cut down to the surviving records, in place.  The reference has no delete
+ * (its store has put and get only, base_proxy.h:18-22, and its index is one pass of build_hash_tables.cc over a code file); the call
+ * stands for running build_hash_tables.cc:40-70 again over the code file without the removed records, and replaces the copy home of
+ * the survivors, a second handle, vc_add_codes and vc_build_index.
+ * N = vc_size before the call, K = the survivors.  sel: N words.  kind says how they are read:                                      */
+#define VC_RETAIN_MASK  0u   /* record i survives iff sel[i] != 0 */
+#define VC_RETAIN_ROOTS 1u   /* record i survives iff sel[i] == id_base + i: `sel` is a labels array of vc_cluster_radius*,
+                                the survivors are the groups' representatives */
+/* new_ids (N words, may be NULL): new_ids[i] = the new GLOBAL id of old record id_base + i, or UINT32_MAX if it was removed -- the map
+ * that carries labels, or any table keyed by id, across the call.  *n_kept (may be NULL) = K.
+ * Afterwards vc_size == K, the survivors keep their relative order and survivor number j has global id id_base + j (ids stay ordinals
+ * of the records in file order, build_hash_tables.cc:55,61,69).  capacity, id_base, flags and knobs are unchanged; the freed room
+ * can be filled by vc_add_* again.  Every observable of the handle -- codes, every search with rows, counts, offsets and statistics,
+ * clustering, the zero padding of the columns behind record K -- equals BIT FOR BIT that of a fresh handle of the same vc_config to
+ * which the K surviving codes were added in order.
+ * Index: a CURRENT index is filtered to the survivors (a bucket is an ascending id run and the renumbering is monotone, so the dead
+ * entries are dropped and the ids translated; nothing is sorted) and is bit for bit the index vc_build_index builds from them,
+ * derived structures chosen by the memory policy of a build of K records.  A STALE index (records added since it was built) serves
+ * no one and is dropped, vc_build_index follows; no index before means no index after.  K == 0 drops the index (a store of nothing
+ * has none): the handle equals a fresh empty one.  K == N changes nothing: new_ids is the identity, no column or index byte is
+ * written.
+ * Errors are checked before any work and leave the store, new_ids and *n_kept untouched: VC_ERR_INVALID for a null handle, null sel
+ * with N > 0, kind > 1, new_ids overlapping sel.  N == 0 gives VC_OK and K = 0; nothing is read or written.
+ * Device form: d_sel / d_new_ids are device memory.  Everything is enqueued on `stream`; the host waits inside the call (for K, which
+ * sizes what follows, and per table as the MIH build waits).  When the call returns the store is in its new state for any later
+ * call; d_new_ids is valid in stream order.
+ * Failure: every allocation the column phase needs is made before the first column byte changes -- VC_ERR_NOMEM there leaves the store
+ * as it was.  A failure in the index phase leaves the compacted records with NO index, never a half-filtered one; vc_build_index works
+ * afterwards (the rule of vc_update_index).
+ * Scratch: the keep bitmap (one bit per record), its rank directory, ONE scratch column (8 N bytes, the peak) and, per table, N + 1
+ * scan words -- all call-scoped allocations, every word written before it is read.  The index object with its grow-only search
+ * scratch and counters survives, as in vc_update_index. */
+int vc_retain_dev(vc_engine* e, const uint32_t* d_sel, uint32_t kind, uint32_t* d_new_ids, uint64_t* n_kept, void* stream);
+/* The same for sel / new_ids in host memory: the device form on the engine's stream plus the staged selection and the copy home of
+ * the map; waits for them. */
+int vc_retain(vc_engine* e, const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept);
+
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
  * seconds); the affected queries kept d_counts[i] == UINT32_MAX.  0 in normal operation.  Synchronises the stream.
@@ -507,6 +544,18 @@ int vc_sharded_shard(vc_sharded* h, uint32_t shard, vc_engine** e, uint64_t* fir
 /* ---- measurement ------------------------------------------------------------------------- */
 /* Sums and resets the event records (synchronises with the last recorded call). */
 int vc_get_timing(const vc_engine* e, vc_timing* t);
+/* Removal over all shards: contract, kinds, errors and failure rule as vc_retain_dev / vc_retain, with N = vc_sharded_size, ids
+ * global over the whole store and d_sel / d_new_ids on the ROOT device.  The shards are id ranges filled in order, so after the
+ * removal the survivors again fill shard 0, then shard 1, ...: records move from later shards to earlier ones and trailing shards may
+ * become empty.  The handle equals, shard for shard, a fresh sharded handle of the same config fed the survivors in order.  Every
+ * shard filters its own slice (vc_retain_dev); then, in ascending shard order, a shard receives what it lacks from the front of the
+ * following shards (device / peer copies of column slices), which drop that prefix by the same filter.  When every non-empty shard
+ * held a current index before, every non-empty shard holds one afterwards: filtered where records only left, brought up to date by
+ * vc_update_index where records arrived.  The host waits inside the call.  Argument errors are checked before any work; a failure
+ * after the first shard has changed leaves shards that are no longer filled in id order -- destroy the handle then. */
+int vc_sharded_retain_dev(vc_sharded* h, const uint32_t* d_sel, uint32_t kind, uint32_t* d_new_ids, uint64_t* n_kept, void* stream);
+int vc_sharded_retain(vc_sharded* h, const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept);
+
 /* Stream of the host-pointer calls (default VC_STREAM_OWN). */
 int vc_set_stream(vc_engine* e, void* stream);
 

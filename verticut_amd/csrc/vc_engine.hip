@@ -13,6 +13,7 @@
 
 #include "vc_internal.hpp"
 #include "vc_mih.hpp"
+#include "vc_retain.hpp"
 
 struct vc_engine {
   vc_config cfg;
@@ -172,6 +173,7 @@ void read_knobs(VcKnobs* k) {
   if (const char* v = getenv("VC_MIH_GS_CAP")) k->gs_cap = (uint32_t)std::max(0, atoi(v));
   k->gs_trace = getenv("VC_MIH_GS_TRACE") != nullptr;
   if (const char* v = getenv("VC_MIH_UPDATE")) k->mih_update = atoi(v);
+  if (const char* v = getenv("VC_MIH_RETAIN")) k->mih_retain = atoi(v);
 }
 
 static int bind_device(vc_engine* e) {
@@ -1515,6 +1517,143 @@ int vc_update_index(vc_engine* e) {
   e->n_indexed = e->mih ? vc_mih_records(e->mih) : 0;   // (a failed update leaves the old stale index, or none)
   return rc;
 }
+
+}  // extern "C"
+
+// ---- removal: the store and its index cut down to the surviving records ---------------------------------------------------------
+// The reference has no delete (base_proxy.h:18-22: put and get); this stands for running build_hash_tables.cc:40-70 again over the
+// code file without the removed records -- ids stay the ordinals of the records in file order.
+static bool ranges_overlap(const void* a, const void* b, uint64_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bytes && y < x + bytes;
+}
+static int check_retain_args(vc_engine* e, const uint32_t* sel, uint32_t kind, const uint32_t* new_ids) {
+  if (!e) return VC_ERR_INVALID;
+  if (kind > VC_RETAIN_FROM || (kind == VC_RETAIN_FROM && sel)) return fail(e, VC_ERR_INVALID, "retain: unknown kind %u", kind);
+  if (e->n && !sel && kind != VC_RETAIN_FROM) return fail(e, VC_ERR_INVALID, "retain: null selection");
+  if (e->n && new_ids && sel && ranges_overlap(sel, new_ids, e->n * 4)) return fail(e, VC_ERR_INVALID, "retain: new_ids overlaps the selection");
+  return VC_OK;
+}
+
+// The whole call on e->stream, e->n > 0.  Keep set -> K (the one wait of the column phase) -> map -> columns -> index.  Everything
+// the column phase needs is allocated before the first column byte changes; the scratch is call-scoped.
+static int retain_run(vc_engine* e, const uint32_t* d_sel, uint32_t kind, uint64_t first_kept, uint32_t* d_new_ids, uint64_t* n_kept) {
+  const uint64_t N = e->n, nblocks = vc_keep_blocks(N);
+  hipStream_t s = e->stream;
+  ScopedDev<uint64_t> bits, scratch;
+  ScopedDev<uint32_t> rank, work;
+  VC_HIP(e, bits.alloc(nblocks * VC_KEEP_BLOCK_WORDS * 8));
+  VC_HIP(e, rank.alloc((nblocks + 1) * 4));
+  VC_HIP(e, work.alloc(std::max<size_t>(vc_scan_work_words(nblocks + 1), 1) * 4));
+  VC_HIP(e, scratch.alloc(((N + 1) & ~1ull) * 8));
+  VC_HIP(e, vc_launch_keep_bits(d_sel, kind, e->cfg.id_base, first_kept, N, bits.p, rank.p, work.p, e->n_cu, s));
+  uint32_t k32 = 0;
+  VC_HIP(e, hipMemcpyAsync(&k32, rank.p + nblocks, 4, hipMemcpyDeviceToHost, s));
+  VC_HIP(e, hipStreamSynchronize(s));
+  const uint64_t K = k32;
+  const VcKeepSet ks{bits.p, rank.p, N, K};
+  if (d_new_ids) VC_HIP(e, vc_launch_keep_map(ks, e->cfg.id_base, d_new_ids, e->n_cu, s));
+  if (n_kept) *n_kept = K;
+  if (K == N) {   // nothing removed: no column or index byte is written
+    if (live_index(e)) vc_mih_retain_trace(e->mih, 0, "none", "0");
+    VC_HIP(e, hipStreamSynchronize(s));   // (the keep set is freed on the way out)
+    return VC_OK;
+  }
+  const bool had_live = live_index(e) != nullptr;
+  if (K == 0) {
+    for (uint32_t j = 0; j < e->W; ++j) VC_HIP(e, hipMemsetAsync(e->d_cols + j * e->stride, 0, N * 8, s));
+  } else {
+    for (uint32_t j = 0; j < e->W; ++j) VC_HIP(e, vc_launch_keep_compact_column(ks, e->d_cols + j * e->stride, scratch.p, e->n_cu, s));
+  }
+  hipError_t r = hipStreamSynchronize(s);
+  e->n = K;
+  if (r != hipSuccess || !had_live || K == 0) drop_index(e);   // a stale index, or that of a store of nothing, serves no one
+  if (r != hipSuccess) return fail(e, VC_ERR_HIP, "retain: %s", hipGetErrorString(r));
+  if (!e->mih) return VC_OK;
+  // index phase: a failure leaves the compacted records with no index, never a half-filtered one
+  int rc;
+  if (e->knobs.mih_retain == 0) {   // A/B and test route: the full rebuild
+    if ((rc = vc_build_index(e)) == VC_OK) vc_mih_retain_trace(e->mih, N - K, "rebuild", "0");
+    return rc;
+  }
+  rc = vc_mih_retain(&e->mih, ks, e->d_cols, e->stride, s, &e->err);
+  e->n_indexed = e->mih ? K : 0;
+  return rc;
+}
+
+// what the sharded store needs of a shard: the records from local position `first_kept` on survive (a prefix is given away)
+int vc_engine_retain_from(vc_engine* e, uint64_t first_kept, hipStream_t s) {
+  if (!e || first_kept > e->n) return VC_ERR_INVALID;
+  if (e->n == 0 || first_kept == 0) return VC_OK;
+  int rc = bind_device(e);
+  if (rc) return rc;
+  const StreamCall call(e, s);
+  return retain_run(e, nullptr, VC_RETAIN_FROM, first_kept, nullptr, nullptr);
+}
+
+// ... and `count` records of `src` from its local position `first` on appended to e's columns (device / peer copies, column by column)
+int vc_engine_append_from(vc_engine* e, vc_engine* src, uint64_t first, uint64_t count, hipStream_t s) {
+  if (!e || !src || e->W != src->W || first + count > src->n) return VC_ERR_INVALID;
+  if (e->n + count > e->cfg.capacity) return fail(e, VC_ERR_CAPACITY, "append beyond capacity");
+  if (count == 0) return VC_OK;
+  int rc = bind_device(e);
+  if (rc) return rc;
+  for (uint32_t j = 0; j < e->W; ++j) {
+    uint64_t* dst = e->d_cols + j * e->stride + e->n;
+    const uint64_t* from = src->d_cols + j * src->stride + first;
+    if (e->device == src->device) VC_HIP(e, hipMemcpyAsync(dst, from, count * 8, hipMemcpyDeviceToDevice, s));
+    else VC_HIP(e, hipMemcpyPeerAsync(dst, e->device, from, src->device, count * 8, s));
+  }
+  VC_HIP(e, hipStreamSynchronize(s));
+  e->n += count;   // (an index, if any, is stale from here on: live_index)
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_retain_dev(vc_engine* e, const uint32_t* d_sel, uint32_t kind, uint32_t* d_new_ids, uint64_t* n_kept, void* stream) {
+  int rc = check_retain_args(e, d_sel, kind, d_new_ids);
+  if (rc) return rc;
+  if (kind > VC_RETAIN_ROOTS) return fail(e, VC_ERR_INVALID, "retain: unknown kind %u", kind);
+  if (e->n == 0) {
+    if (n_kept) *n_kept = 0;
+    return VC_OK;
+  }
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, caller_stream(e, stream));
+  return retain_run(e, d_sel, kind, 0, d_new_ids, n_kept);
+}
+
+int vc_retain(vc_engine* e, const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) {
+  int rc = check_retain_args(e, sel, kind, new_ids);
+  if (rc) return rc;
+  if (kind > VC_RETAIN_ROOTS) return fail(e, VC_ERR_INVALID, "retain: unknown kind %u", kind);
+  if (e->n == 0) {
+    if (n_kept) *n_kept = 0;
+    return VC_OK;
+  }
+  if ((rc = bind_device(e))) return rc;
+  const uint64_t N = e->n;
+  ScopedDev<uint32_t> d_sel, d_map;   // staged selection and map: call-scoped, like the rest of the call's scratch
+  VC_HIP(e, d_sel.alloc(N * 4));
+  if (new_ids) VC_HIP(e, d_map.alloc(N * 4));
+  VC_HIP(e, hipMemcpyAsync(d_sel.p, sel, N * 4, hipMemcpyHostToDevice, e->stream));
+  uint64_t K = 0;
+  {
+    const StreamCall call(e, e->stream);
+    rc = retain_run(e, d_sel.p, kind, 0, d_map.p, &K);
+  }
+  if (new_ids && e->n == K) {   // (the map is final once K is known, whatever became of the index)
+    VC_HIP(e, hipMemcpyAsync(new_ids, d_map.p, N * 4, hipMemcpyDeviceToHost, e->stream));
+    VC_HIP(e, hipStreamSynchronize(e->stream));
+  }
+  if (n_kept && (rc == VC_OK || e->n == K)) *n_kept = K;
+  return rc;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int vc_get_bucket(vc_engine* e, uint32_t table, uint32_t index, uint32_t* ids, void* codes, uint32_t cap, uint32_t* n) {
   if (!e || !n) return VC_ERR_INVALID;

@@ -40,6 +40,7 @@ struct VcKnobs {
   uint32_t gs_cap = 1;                        // VC_MIH_GS_CAP (dev): cap of the sharded global stop's first round
   bool gs_trace = false;                      // VC_MIH_GS_TRACE (dev): per-round wall times of the sharded global stop on stderr
   int mih_update = 1;                         // VC_MIH_UPDATE=0: vc_update_index rebuilds the whole index (A/B runs, tests) instead of merging
+  int mih_retain = 1;                         // VC_MIH_RETAIN=0: vc_retain* compacts the columns and rebuilds the whole index (A/B runs, tests) instead of filtering it
   bool scan_shape_trace = false;              // VC_SCAN_SHAPE_TRACE=1 (dev/tests): every verify launch names the instantiation it launched on stderr
 };
 void read_knobs(VcKnobs* k);   // vc_engine.hip: the one place that reads the environment (once per engine / sharded handle)
@@ -201,6 +202,16 @@ hipError_t vc_launch_cluster_union(const uint64_t* d_raw, const uint64_t* d_roff
                                    uint32_t id_base, uint32_t* d_labels, uint64_t* d_n_pairs, hipStream_t s);
 // d_labels[i] = the root of record i (the smallest id of its component), in place; *d_n_clusters += the roots
 hipError_t vc_launch_cluster_flatten(uint32_t* d_labels, uint64_t n, uint32_t id_base, uint64_t* d_n_clusters, hipStream_t s);
+// ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
+struct VcKeepSet;
+#define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)
+// sel -> d_bits (vc_keep_blocks(n) * 4 words) and d_rank (vc_keep_blocks(n) + 1 words, the last one = K); d_work: vc_scan_work_words(blocks + 1) words
+hipError_t vc_launch_keep_bits(const uint32_t* d_sel, uint32_t kind, uint32_t id_base, uint64_t first_kept, uint64_t n, uint64_t* d_bits, uint32_t* d_rank,
+                               uint32_t* d_work, uint32_t n_cu, hipStream_t s);
+// d_new_ids[i] = id_base + new local id of record i, or UINT32_MAX for a removed one
+hipError_t vc_launch_keep_map(const VcKeepSet& ks, uint32_t id_base, uint32_t* d_new_ids, uint32_t n_cu, hipStream_t s);
+// one column compacted through d_scratch (round_up(n, 2) words): survivors in order at [0, K), zeros at [K, round_up(n, 2))
+hipError_t vc_launch_keep_compact_column(const VcKeepSet& ks, uint64_t* d_col, uint64_t* d_scratch, uint32_t n_cu, hipStream_t s);
 // ---- vc_engine.hip: what the sharded store's global stop (vc_sharded.hip) needs of a shard's engine
 struct VcEngineView {
   const uint64_t* cols;   // column-major codes, word j of record i at cols[j * stride + i]
@@ -218,6 +229,11 @@ int vc_engine_knn_capped(vc_engine* e, const void* d_queries, uint32_t nq, uint3
 // out_cap (VC_ERR_CAPACITY: the caller grows its buffer to *total and repeats, no read-back of the offsets)
 int vc_engine_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t radius, uint32_t mode, uint64_t* d_out, uint64_t out_cap,
                          uint64_t* d_offsets, uint64_t* total, hipStream_t s);
+// what vc_sharded_retain* needs of a shard (vc_engine.hip), both on stream s and waited for: the records from local position
+// first_kept on survive (vc_retain's column and index phases with the internal kind VC_RETAIN_FROM); and `count` records of `src`
+// from its local position `first` on appended behind e's own (device or peer copies; e's index, if any, is stale afterwards)
+int vc_engine_retain_from(vc_engine* e, uint64_t first_kept, hipStream_t s);
+int vc_engine_append_from(vc_engine* e, vc_engine* src, uint64_t first, uint64_t count, hipStream_t s);
 // the same over the gathered shard slots of vc_sharded_* (rows + counts per slot; a flagged shard row flags the merged row)
 hipError_t vc_launch_select_slots(const uint64_t* d_base, uint64_t slot_words, uint32_t cnt_off_words, uint32_t n_lists, uint32_t nq,
                                   uint32_t k, uint64_t* d_out, uint32_t* d_out_count, hipStream_t s);

@@ -33,6 +33,7 @@
 #include "vc_internal.hpp"
 #include "vc_mih.hpp"
 #include "vc_mih_policy.hpp"
+#include "vc_retain.hpp"
 
 #define MIH_BLK 256
 #define MIH_PPT 4                       // probes per thread
@@ -448,6 +449,92 @@ __global__ void __launch_bounds__(MU_BLK) mih_update_merge_kernel(const Src src,
       out[(uint64_t)o * PIECES + e] = v;
     }
     jb += nbt;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// index removal (vc_mih_retain): a table filtered to the surviving records.  Deleting records and renumbering the survivors in
+// order is a monotone map on ids, so no entry changes its relative order: S[] = the exclusive scan of the entries' keep flags is
+// where every kept entry goes, and nothing is sorted.
+// ------------------------------------------------------------------------------------------
+// flag[p] = keep bit of ids[p], p < n; flag[n] = 0 (the scan over n + 1 words then ends in S[n] = K)
+__global__ void __launch_bounds__(256) mih_retain_flags_kernel(const uint32_t* __restrict__ ids, uint64_t n, const VcKeepSet ks, uint32_t* __restrict__ flag) {
+  for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p <= n; p += (uint64_t)gridDim.x * blockDim.x)
+    flag[p] = p < n && vc_keep_test(ks, __builtin_nontemporal_load(ids + p)) ? 1u : 0u;
+}
+
+// ids_new[S[p]] = new_local(ids[p]) for the kept entries: consecutive kept entries land side by side
+__global__ void __launch_bounds__(256) mih_retain_ids_kernel(const uint32_t* __restrict__ ids, const uint32_t* __restrict__ S, uint64_t n,
+                                                             const VcKeepSet ks, uint32_t* __restrict__ ids_new) {
+  for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t at = S[p];
+    if (S[p + 1] != at) ids_new[at] = vc_keep_rank(ks, __builtin_nontemporal_load(ids + p));
+  }
+}
+
+// the {id, 0, code} records by the same rule, the id word translated; an element is W pieces of 16 bytes
+template <int W>
+__global__ void __launch_bounds__(256) mih_retain_bent_kernel(const uint4* __restrict__ bent, const uint32_t* __restrict__ S, uint64_t n,
+                                                              const VcKeepSet ks, uint4* __restrict__ out) {
+  for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n * W; q += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t p = q / W;
+    const uint32_t e = (uint32_t)(q - p * W), at = S[p];
+    if (S[p + 1] == at) continue;
+    uint4 v = bent[q];
+    if (e == 0) v.x = vc_keep_rank(ks, v.x);
+    out[(uint64_t)at * W + e] = v;
+  }
+}
+
+// direct tables: offsets[v] = S[offsets[v]], v = 0 .. 2^s (element by element, in place)
+__global__ void __launch_bounds__(256) mih_retain_direct_offsets_kernel(const uint32_t* __restrict__ S, uint32_t len, uint32_t* __restrict__ offsets) {
+  for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < len; v += gridDim.x * blockDim.x) offsets[v] = S[offsets[v]];
+}
+
+// ... and their occupancy words from the new offsets: bit v = bucket v is not empty (words beyond the key space are zero)
+__global__ void __launch_bounds__(256) mih_retain_direct_bitmap_kernel(const uint32_t* __restrict__ offsets, uint32_t nkeys, uint32_t nwords,
+                                                                       uint32_t* __restrict__ bitmap) {
+  for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < nwords; w += gridDim.x * blockDim.x) {
+    uint32_t word = 0;
+    if (w * 32u < nkeys) {
+      uint32_t prev = offsets[w * 32u];
+      for (uint32_t b = 0; b < 32u; ++b) {
+        const uint32_t next = offsets[w * 32u + b + 1u];
+        word |= (next > prev ? 1u : 0u) << b;
+        prev = next;
+      }
+    }
+    bitmap[w] = word;
+  }
+}
+
+// ranked tables: old bucket r survives iff an entry of it does; bf[n_unique] = 0
+__global__ void __launch_bounds__(256) mih_retain_bucket_flags_kernel(const uint32_t* __restrict__ offsets, uint32_t n_unique,
+                                                                      const uint32_t* __restrict__ S, uint32_t* __restrict__ bf) {
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r <= n_unique; r += gridDim.x * blockDim.x)
+    bf[r] = r < n_unique && S[offsets[r + 1]] > S[offsets[r]] ? 1u : 0u;
+}
+
+// offsets_new[newrank(r)] = S[offsets_old[r]] for the surviving buckets (nr = the scan of their flags), offsets_new[U'] = K
+__global__ void __launch_bounds__(256) mih_retain_ranked_offsets_kernel(const uint32_t* __restrict__ offsets, uint32_t n_unique,
+                                                                        const uint32_t* __restrict__ S, const uint32_t* __restrict__ nr,
+                                                                        uint32_t n_unique_new, uint32_t k, uint32_t* __restrict__ offsets_new) {
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_unique; r += gridDim.x * blockDim.x) {
+    const uint32_t at = nr[r];
+    if (nr[r + 1] != at) offsets_new[at] = S[offsets[r]];
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) offsets_new[n_unique_new] = k;
+}
+
+// The occupancy bitmap of a ranked table anew (generate_bitmap.cc:54-58 set_idx), one atomic per surviving bucket.  The key of a
+// bucket is read from its head entry's record in the COMPACTED columns through the NEW ids: a vanished bucket has no survivor to
+// name its key, so its bit is never looked for -- the bitmap was cleared and only the buckets that exist set theirs.
+__global__ void __launch_bounds__(256) mih_retain_head_bits_kernel(const uint64_t* __restrict__ col, uint32_t shift, const uint32_t* __restrict__ ids_new,
+                                                                   const uint32_t* __restrict__ offsets_new, uint32_t n_unique_new,
+                                                                   uint32_t* __restrict__ bitmap) {
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_unique_new; r += gridDim.x * blockDim.x) {
+    const uint32_t key = (uint32_t)(col[ids_new[offsets_new[r]]] >> shift);
+    atomicOr(&bitmap[key >> 5], 1u << (key & 31));
   }
 }
 
@@ -3137,6 +3224,174 @@ int vc_mih_update(VcMihIndex** pix, const uint64_t* d_cols, uint64_t stride, uin
     return rc;
   }
   vc_mih_update_trace(ix, nd, "merge", oc.bent_gathered ? "gather" : oc.bent_merged ? "merge" : "0");
+  return VC_OK;
+}
+
+// ---- index removal ------------------------------------------------------------------------------------------
+void vc_mih_retain_trace(const VcMihIndex* ix, uint64_t removed, const char* route, const char* bent_route) {
+  if (!ix->knobs.mih_trace) return;
+  bool bcodes = ix->m != 0, bent = ix->m != 0, lines = ix->m != 0;
+  for (const VcTableView& tv : ix->h_tables) { bcodes &= tv.bcodes != nullptr; bent &= tv.bent != nullptr; lines &= tv.lines != nullptr; }
+  if (!bent_route) bent_route = bent ? "gather" : "0";
+  fprintf(stderr, "[vc_mih] index retained: n=%llu removed=%llu route=%s bent=%s bcodes=%d lines=%d\n", (unsigned long long)ix->n,
+          (unsigned long long)removed, route, bent_route, (int)bcodes, (int)lines);
+}
+
+// device scratch of a removal: S (n0 + 1 words: the entries' keep flags, scanned in place), and for ranked tables the buckets'
+// flags (scanned in place: the new ranks) and the 2^24 block counts
+struct RetainScratch {
+  uint32_t *S = nullptr, *bf = nullptr, *scan_in = nullptr, *temp = nullptr;
+};
+
+// one table of a removal; the columns hold the K survivors already
+static int retain_table(VcMihIndex* ix, uint32_t t, const MihMemPolicy& pol, const VcKeepSet& ks, const uint64_t* d_cols, uint64_t stride,
+                        const RetainScratch& sc, UpdateOutcome* oc, hipStream_t s, std::string* err) {
+  const uint32_t sbits = ix->sbits, W = ix->W, n_cu = ix->n_cu;
+  const uint64_t n0 = ks.n, K = ks.k, nkeyspace = 1ull << sbits;
+  const uint32_t bitpos = t * sbits;
+  VcTableView tv = ix->h_tables[t];
+  const VcTableView old = tv;
+
+  // 1. S = where every kept entry goes
+  hipLaunchKernelGGL(mih_retain_flags_kernel, dim3(grid_for(n0 + 1, n_cu)), dim3(256), 0, s, old.ids, n0, ks, sc.S);
+  MIH_CHECK(hipGetLastError());
+  MIH_CHECK(vc_exclusive_scan_u32(sc.S, sc.S, n0 + 1, sc.temp, s));
+
+  // 2. ids[]: out of place (when the first table cannot have it, the old index is still whole -- but serves records that are gone:
+  // the caller drops it)
+  uint32_t* ids = nullptr;
+  MIH_CHECK(dev_alloc(ix->allocs, &ids, K * 4));
+  oc->touched = true;
+  ix->n = K;   // (build_derived sizes by it; a failure from here on frees the index)
+  hipLaunchKernelGGL(mih_retain_ids_kernel, dim3(grid_for(n0, n_cu)), dim3(256), 0, s, old.ids, (const uint32_t*)sc.S, n0, ks, ids);
+  MIH_CHECK(hipGetLastError());
+  tv.ids = ids;
+
+  // 3. offsets, 4. bitmap and rank directory
+  if (sbits < 32) {
+    uint32_t* offsets = const_cast<uint32_t*>(old.offsets);
+    hipLaunchKernelGGL(mih_retain_direct_offsets_kernel, dim3(grid_for(nkeyspace + 1, n_cu)), dim3(256), 0, s, (const uint32_t*)sc.S,
+                       (uint32_t)(nkeyspace + 1), offsets);
+    MIH_CHECK(hipGetLastError());
+    const uint32_t bm_words = (uint32_t)std::max<uint64_t>(nkeyspace / 32, 8);
+    hipLaunchKernelGGL(mih_retain_direct_bitmap_kernel, dim3(grid_for(bm_words, n_cu)), dim3(256), 0, s, (const uint32_t*)offsets, (uint32_t)nkeyspace,
+                       bm_words, const_cast<uint32_t*>(old.bitmap));
+    MIH_CHECK(hipGetLastError());
+  } else {
+    const uint32_t U = old.n_unique;
+    hipLaunchKernelGGL(mih_retain_bucket_flags_kernel, dim3(grid_for((uint64_t)U + 1, n_cu)), dim3(256), 0, s, old.offsets, U, (const uint32_t*)sc.S, sc.bf);
+    MIH_CHECK(hipGetLastError());
+    MIH_CHECK(vc_exclusive_scan_u32(sc.bf, sc.bf, (uint64_t)U + 1, sc.temp, s));
+    uint32_t U2 = 0;
+    MIH_CHECK(hipMemcpyAsync(&U2, sc.bf + U, 4, hipMemcpyDeviceToHost, s));
+    MIH_CHECK(hipStreamSynchronize(s));
+    uint32_t* offsets = nullptr;
+    MIH_CHECK(dev_alloc(ix->allocs, &offsets, ((size_t)U2 + 1) * 4));
+    hipLaunchKernelGGL(mih_retain_ranked_offsets_kernel, dim3(grid_for(std::max<uint32_t>(U, 1), n_cu)), dim3(256), 0, s, old.offsets, U,
+                       (const uint32_t*)sc.S, (const uint32_t*)sc.bf, U2, (uint32_t)K, offsets);
+    MIH_CHECK(hipGetLastError());
+    tv.offsets = offsets;
+    tv.n_unique = U2;
+    uint32_t* bitmap = const_cast<uint32_t*>(old.bitmap);
+    MIH_CHECK(hipMemsetAsync(bitmap, 0, (nkeyspace / 32) * 4, s));
+    hipLaunchKernelGGL(mih_retain_head_bits_kernel, dim3(grid_for(std::max<uint32_t>(U2, 1), n_cu)), dim3(256), 0, s,
+                       d_cols + (uint64_t)(bitpos >> 6) * stride, bitpos & 63, (const uint32_t*)ids, (const uint32_t*)offsets, U2, bitmap);
+    MIH_CHECK(hipGetLastError());
+    const uint32_t nblocks = 1u << 24;
+    hipLaunchKernelGGL(mih_blockpop_kernel, dim3(n_cu * 16), dim3(256), 0, s, old.bitmap, nblocks, sc.scan_in);
+    MIH_CHECK(hipGetLastError());
+    MIH_CHECK(vc_exclusive_scan_u32(sc.scan_in, const_cast<uint32_t*>(old.blockrank), nblocks, sc.temp, s));
+  }
+
+  // {id, code} records: filtered like ids[] while a second copy of this table's records can be had, else gathered again
+  const uint4* old_bent = old.bent;
+  tv.bent = nullptr;
+  if (pol.bent && old_bent) {
+    uint4* be = nullptr;
+    if (hipMalloc((void**)&be, (size_t)K * 16 * W) == hipSuccess) {
+      ix->allocs.push_back(be);
+      if (W == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(mih_retain_bent_kernel<1>), dim3(grid_for(n0, n_cu)), dim3(256), 0, s, old_bent, (const uint32_t*)sc.S, n0, ks, be);
+      else hipLaunchKernelGGL(HIP_KERNEL_NAME(mih_retain_bent_kernel<2>), dim3(grid_for(n0 * 2, n_cu)), dim3(256), 0, s, old_bent, (const uint32_t*)sc.S, n0, ks, be);
+      MIH_CHECK(hipGetLastError());
+      tv.bent = be;
+      ++oc->bent_merged;
+    } else {
+      (void)hipGetLastError();   // (out of memory is an answer here, not an error)
+    }
+  }
+
+  // 5. what the replaced arrays held goes back; the derived structures follow from the new ones as at a build / load
+  MIH_CHECK(hipStreamSynchronize(s));
+  free_alloc(ix, old.ids);
+  if (sbits == 32) free_alloc(ix, old.offsets);
+  free_alloc(ix, old.blockoff);
+  free_alloc(ix, old.lines);
+  free_alloc(ix, old.bcodes);
+  free_alloc(ix, old_bent);
+  tv.blockoff = nullptr; tv.lines = nullptr; tv.bcodes = nullptr;
+  MihMemPolicy derived = pol;
+  derived.bent = pol.bent && !tv.bent;
+  if (derived.bent) ++oc->bent_gathered;
+  int rc = build_derived(ix, tv, derived, d_cols, stride, s, err);
+  if (rc) return rc;
+  ix->h_tables[t] = tv;   // 6. the table is swapped in whole
+  return VC_OK;
+}
+
+int vc_mih_retain(VcMihIndex** pix, const VcKeepSet& ks, const uint64_t* d_cols, uint64_t stride, hipStream_t s, std::string* err) {
+  VcMihIndex* ix = *pix;
+  const uint64_t n0 = ix->n, K = ks.k;
+  auto drop = [&]() { vc_mih_free(ix); *pix = nullptr; };
+  if (ks.n != n0 || K == 0 || K > n0) {
+    drop();
+    return fail(err, VC_ERR_STATE, "index removal: the keep set does not fit the index");
+  }
+  if (K == n0) {
+    vc_mih_retain_trace(ix, 0, "none", "0");
+    return VC_OK;
+  }
+  const uint32_t sbits = ix->sbits, m = ix->m;
+  // the policy of a build of K records: what the old index holds counts as free (all of it is replaced or kept in place)
+  MihMemPolicy pol;
+  {
+    size_t free_b = 0, total_b = 0;
+    const bool have_free = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+    uint64_t held = 0;
+    for (const VcTableView& tv : ix->h_tables) held += table_bytes(ix, tv);
+    pol = vc_mih_policy(sbits, m, K, ix->W, have_free, free_b + held, MihPolicyKnobs{ix->knobs.mih_bcodes, ix->knobs.mih_bent, ix->knobs.mih_lines});
+  }
+
+  UpdateOutcome oc;
+  int rc = VC_OK;
+  {
+    DevScratch tmp;
+    RetainScratch sc;
+    const uint64_t nblocks = 1ull << 24;
+    size_t temp_words = vc_scan_work_words(n0 + 1);
+    auto alloc_all = [&]() -> int {
+      MIH_CHECK(dev_alloc(tmp.bufs, &sc.S, (n0 + 1) * 4));
+      if (sbits == 32) {
+        temp_words = std::max(temp_words, vc_scan_work_words(nblocks));
+        MIH_CHECK(dev_alloc(tmp.bufs, &sc.bf, (n0 + 1) * 4));   // (a table has at most n0 buckets)
+        MIH_CHECK(dev_alloc(tmp.bufs, &sc.scan_in, (nblocks + 1) * 4));
+      }
+      MIH_CHECK(dev_alloc(tmp.bufs, &sc.temp, temp_words * 4));
+      return VC_OK;
+    };
+    rc = alloc_all();
+    for (uint32_t t = 0; t < m && rc == VC_OK; ++t) rc = retain_table(ix, t, pol, ks, d_cols, stride, sc, &oc, s, err);
+    if (rc == VC_OK) {
+      hipError_t r = hipMemcpyAsync(ix->d_tables, ix->h_tables.data(), sizeof(VcTableView) * m, hipMemcpyHostToDevice, s);
+      if (r == hipSuccess) r = hipStreamSynchronize(s);
+      if (r != hipSuccess) rc = hip_fail(err, r, "index removal: table views");
+    }
+    if (rc != VC_OK) (void)hipStreamSynchronize(s);
+  }
+  if (rc != VC_OK) {   // the old index names records that are gone, a half-filtered one is worse: no index
+    drop();
+    return rc;
+  }
+  vc_mih_retain_trace(ix, n0 - K, "filter", oc.bent_gathered ? "gather" : oc.bent_merged ? "filter" : "0");
   return VC_OK;
 }
 

@@ -18,6 +18,16 @@ int vc_mih_update(VcMihIndex** ix, const uint64_t* d_cols, uint64_t stride, uint
 uint64_t vc_mih_records(const VcMihIndex* ix);   // records the index covers
 // VC_MIH_TRACE: "[vc_mih] index updated: n=.. added=.. route=merge|rebuild|none bent=merge|gather|0 bcodes=.. lines=.."
 void vc_mih_update_trace(const VcMihIndex* ix, uint64_t added, const char* route, const char* bent);
+// Index removal, the mirror image of the update: the columns hold the ks.k survivors of the ks.n records *ix covers, compacted in
+// order.  Deleting records and renumbering the survivors in order is a monotone map on ids and a bucket is an ascending id run, so
+// the index of the survivors is the old one with the dead entries dropped and the ids translated: per table one scan of the
+// entries' keep flags and one stable scatter -- nothing is sorted.  Bit for bit what vc_mih_build gives from the survivors.  The
+// VcMihIndex object, its scratch and counters stay.  0 < ks.k <= ks.n.  On failure *ix is freed and null: never half filtered, and
+// never the old index, which names records that are gone.
+struct VcKeepSet;
+int vc_mih_retain(VcMihIndex** ix, const VcKeepSet& ks, const uint64_t* d_cols, uint64_t stride, hipStream_t s, std::string* err);
+// VC_MIH_TRACE: "[vc_mih] index retained: n=.. removed=.. route=filter|rebuild|none bent=filter|gather|0 bcodes=.. lines=.."
+void vc_mih_retain_trace(const VcMihIndex* ix, uint64_t removed, const char* route, const char* bent);
 // index persistence: the CSR tables + bitmaps of a built index, and back (the codes themselves travel as a code file)
 int vc_mih_save(VcMihIndex* ix, const uint64_t* d_cols, uint64_t stride, const char* path, hipStream_t s, std::string* err);
 int vc_mih_load(VcMihIndex** out, const char* path, const uint64_t* d_cols, uint64_t stride, uint64_t n, uint32_t W, uint32_t m,

@@ -2168,3 +2168,143 @@ int vc_sharded_cluster_radius(vc_sharded* h, uint32_t radius, uint32_t mode, uin
 }
 
 }  // extern "C"
+
+// ---- removal over the shards ----------------------------------------------------------------------------------------------------------
+// a shard's map names ids of its own range (shard id_base + j); survivor j of shard g is survivor P_g + j of the store
+extern "C" __global__ void __launch_bounds__(256) vc_sharded_retain_shift_kernel(uint32_t* __restrict__ ids, uint64_t n, uint32_t delta) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t v = ids[i];
+    if (v != 0xFFFFFFFFu) ids[i] = v + delta;
+  }
+}
+
+static int check_sharded_retain_args(vc_sharded* h, const uint32_t* sel, uint32_t kind, const uint32_t* new_ids) {
+  if (!h) return VC_ERR_INVALID;
+  if (kind > VC_RETAIN_ROOTS) return sfail(h, VC_ERR_INVALID, "retain: unknown kind %u", kind);
+  if (h->n && !sel) return sfail(h, VC_ERR_INVALID, "retain: null selection");
+  if (h->n && new_ids) {
+    const uintptr_t x = (uintptr_t)sel, y = (uintptr_t)new_ids, bytes = (uintptr_t)h->n * 4;
+    if (x < y + bytes && y < x + bytes) return sfail(h, VC_ERR_INVALID, "retain: new_ids overlaps the selection");
+  }
+  return VC_OK;
+}
+
+// d_sel / d_new_ids on the root device, valid on S; h->n > 0.  Every step is waited for before the next one starts on another
+// device.  1. every shard filters its slice; 2. the maps are shifted to store-wide ids; 3. in ascending shard order a shard takes
+// what it lacks from the front of the following shards, which drop that prefix; 4. the shards that received bring their index up
+// to date.  Nothing on the root depends on the store's size between calls (shard_size reads h->n).
+static int sharded_retain_run(vc_sharded* h, const uint32_t* d_sel, uint32_t kind, uint32_t* d_new_ids, uint64_t* n_kept, hipStream_t S) {
+  const uint32_t G = h->G, id_base = h->cfg.engine.id_base;
+  auto stream_of = [&](uint32_t g) { return h->dev[g] == h->root ? S : h->lanes[h->lane_of[g]].stream; };
+  auto shard_fail = [&](uint32_t g, int rc) { return sfail(h, rc, "shard %u: %s", g, vc_last_error(h->eng[g])); };
+  bool indexed = true;
+  for (uint32_t g = 0; g < G; ++g) indexed = indexed && (shard_size(h, g) == 0 || vc_engine_has_index(h->eng[g]));
+  VS_HIP(h, hipSetDevice(h->root));
+  VS_HIP(h, hipStreamSynchronize(S));
+
+  // 1. the shards' own removals
+  std::vector<uint64_t> had(G, 0), cur(G, 0), arrived(G, 0);
+  uint64_t K = 0;
+  for (uint32_t g = 0; g < G; ++g) {
+    const uint64_t ng = had[g] = shard_size(h, g);
+    if (!ng) continue;
+    const uint32_t* sel_g = d_sel + h->lo[g];
+    uint32_t* map_g = d_new_ids ? d_new_ids + h->lo[g] : nullptr;
+    int rc;
+    if (h->dev[g] == h->root) {
+      rc = vc_retain_dev(h->eng[g], sel_g, kind, map_g, &cur[g], S);
+    } else {   // the slice travels to the shard's device and the map back
+      VS_HIP(h, hipSetDevice(h->dev[g]));
+      ScopedBufs<2> tmp;
+      hipStream_t L = stream_of(g);
+      if ((rc = tmp.b[0].grow(h, ng * 4)) || (map_g && (rc = tmp.b[1].grow(h, ng * 4)))) return rc;
+      VS_HIP(h, hipMemcpyPeerAsync(tmp.b[0].p, h->dev[g], sel_g, h->root, ng * 4, L));
+      rc = vc_retain_dev(h->eng[g], tmp.b[0].as<uint32_t>(), kind, map_g ? tmp.b[1].as<uint32_t>() : nullptr, &cur[g], L);
+      if (rc == VC_OK && map_g) VS_HIP(h, hipMemcpyPeerAsync(map_g, h->root, tmp.b[1].p, h->dev[g], ng * 4, L));
+      VS_HIP(h, hipStreamSynchronize(L));
+    }
+    if (rc) return shard_fail(g, rc);
+    // 2. the shard's ids start at id_base + lo[g], its survivors at id_base + K
+    if (map_g && K != h->lo[g]) {
+      VS_HIP(h, hipSetDevice(h->root));
+      hipLaunchKernelGGL(vc_sharded_retain_shift_kernel, dim3((uint32_t)std::min<uint64_t>((ng + 255) / 256, 4096)), dim3(256), 0, S, map_g, ng,
+                         (uint32_t)K - (uint32_t)h->lo[g]);
+      VS_HIP(h, hipGetLastError());
+    }
+    K += cur[g];
+  }
+  (void)id_base;
+  const std::vector<uint64_t> kept = cur;
+
+  // 3. the survivors fill shard 0, then shard 1, ...
+  uint32_t src = 0;
+  for (uint32_t g = 0; g < G; ++g) {
+    const uint64_t target = K <= h->lo[g] ? 0 : std::min(K, h->hi[g]) - h->lo[g];
+    src = std::max(src, g + 1);
+    while (cur[g] < target) {
+      while (src < G && cur[src] == 0) ++src;
+      if (src >= G) return sfail(h, VC_ERR_STATE, "retain: the shards hold fewer records than they reported");
+      const uint64_t take = std::min(target - cur[g], cur[src]);
+      int rc = vc_engine_append_from(h->eng[g], h->eng[src], 0, take, stream_of(g));
+      if (rc) return shard_fail(g, rc);
+      if ((rc = vc_engine_retain_from(h->eng[src], take, stream_of(src)))) return shard_fail(src, rc);
+      cur[g] += take;
+      arrived[g] += take;
+      cur[src] -= take;
+    }
+  }
+  h->n = K;
+
+  // 4. indexes: filtered where records only left (done above), updated where records arrived, built where none was left
+  for (uint32_t g = 0; g < G; ++g) {
+    const char* route = had[g] == 0 ? "none" : !indexed ? "columns" : cur[g] == 0 ? "empty" : arrived[g] ? "update" : kept[g] == had[g] && cur[g] == kept[g] ? "none" : "filter";
+    if (indexed && cur[g] && !vc_engine_has_index(h->eng[g])) {
+      int rc = vc_update_index(h->eng[g]);
+      if (rc) return shard_fail(g, rc);
+    }
+    if (h->knobs.mih_trace)
+      fprintf(stderr, "[vc_sharded] retained: shard=%u n=%llu kept=%llu given=%llu arrived=%llu route=%s\n", g, (unsigned long long)cur[g],
+              (unsigned long long)kept[g], (unsigned long long)(kept[g] + arrived[g] - cur[g]), (unsigned long long)arrived[g], route);
+  }
+  VS_HIP(h, hipSetDevice(h->root));
+  VS_HIP(h, hipStreamSynchronize(S));
+  if (n_kept) *n_kept = K;
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_sharded_retain_dev(vc_sharded* h, const uint32_t* d_sel, uint32_t kind, uint32_t* d_new_ids, uint64_t* n_kept, void* stream) {
+  int rc = check_sharded_retain_args(h, d_sel, kind, d_new_ids);
+  if (rc) return rc;
+  if (h->n == 0) {
+    if (n_kept) *n_kept = 0;
+    return VC_OK;
+  }
+  return sharded_retain_run(h, d_sel, kind, d_new_ids, n_kept, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+}
+
+int vc_sharded_retain(vc_sharded* h, const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) {
+  int rc = check_sharded_retain_args(h, sel, kind, new_ids);
+  if (rc) return rc;
+  if (h->n == 0) {
+    if (n_kept) *n_kept = 0;
+    return VC_OK;
+  }
+  const uint64_t N = h->n;
+  hipStream_t S = h->root_stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  ScopedBufs<2> tmp;   // staged selection and map: call-scoped
+  if ((rc = tmp.b[0].grow(h, N * 4)) || (new_ids && (rc = tmp.b[1].grow(h, N * 4)))) return rc;
+  VS_HIP(h, hipMemcpyAsync(tmp.b[0].p, sel, N * 4, hipMemcpyHostToDevice, S));
+  rc = sharded_retain_run(h, tmp.b[0].as<uint32_t>(), kind, new_ids ? tmp.b[1].as<uint32_t>() : nullptr, n_kept, S);
+  (void)hipSetDevice(h->root);   // (the buffers are released on the device they live on)
+  if (rc) return rc;
+  if (new_ids) {
+    VS_HIP(h, hipMemcpyAsync(new_ids, tmp.b[1].p, N * 4, hipMemcpyDeviceToHost, S));
+    VS_HIP(h, hipStreamSynchronize(S));
+  }
+  return VC_OK;
+}
+
+}  // extern "C"

@@ -22,6 +22,7 @@ SYNTH_UNIFORM, SYNTH_CLUSTERED = 0, 1
 ORDER_ASCENDING, ORDER_FARTHEST_FIRST = 0, 1
 IDS_EXCLUDE_SELF = 0x1    # VC_IDS_EXCLUDE_SELF: a by-id row holds the k nearest items other than the query's own record
 IDS_ONLY_GREATER = 0x2    # VC_IDS_ONLY_GREATER (radius-by-id calls only): a segment keeps the entries whose id exceeds the query's own
+RETAIN_MASK, RETAIN_ROOTS = 0, 1   # VC_RETAIN_MASK: record i survives iff sel[i] != 0; VC_RETAIN_ROOTS: iff sel[i] == id_base + i (cluster labels)
 PACK_INF = np.uint64(0xFFFFFFFFFFFFFFFF)
 STREAM_OWN = C.c_void_p(-1)   # VC_STREAM_OWN; None / 0 = the HIP null stream (PyTorch's default stream)
 
@@ -41,6 +42,7 @@ EXPORTS = [
     "vc_search_radius_ids", "vc_search_radius_ids_dev", "vc_sharded_search_radius_ids", "vc_sharded_search_radius_ids_dev",
     "vc_update_index", "vc_sharded_update_index",
     "vc_cluster_radius", "vc_cluster_radius_dev", "vc_sharded_cluster_radius", "vc_sharded_cluster_radius_dev",
+    "vc_retain", "vc_retain_dev", "vc_sharded_retain", "vc_sharded_retain_dev",
 ]
 MAX_SHARDS = 16
 EXCHANGE_AUTO, EXCHANGE_PEER_COPY, EXCHANGE_RCCL = 0, 1, 2
@@ -170,6 +172,10 @@ def load_library():
     L.vc_cluster_radius_dev.argtypes = [vp, u32, u32, u32, u64, vp, vp, vp]
     L.vc_sharded_cluster_radius.argtypes = [vp, u32, u32, u32, u64, vp, vp]
     L.vc_sharded_cluster_radius_dev.argtypes = [vp, u32, u32, u32, u64, vp, vp, vp]
+    L.vc_retain.argtypes = [vp, vp, u32, vp, vp]
+    L.vc_retain_dev.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.vc_sharded_retain.argtypes = [vp, vp, u32, vp, vp]
+    L.vc_sharded_retain_dev.argtypes = [vp, vp, u32, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -230,6 +236,24 @@ def _cluster_radius_dev(self, fn, radius, d_labels, mode, batch, n_labelled, str
     st = VcClusterStats()
     self._check(fn(self._h, radius, mode, batch, n_labelled, d_labels, C.byref(st), stream))
     return int(st.n_pairs), int(st.n_clusters)
+
+
+def _retain(self, fn, sel, kind, with_map):
+    """shared by Engine.retain and ShardedEngine.retain: (n_kept, new_ids [N] uint32 | None)"""
+    n = len(self)
+    sel = np.ascontiguousarray(sel, dtype=np.uint32).reshape(-1)
+    if sel.shape[0] != n:
+        raise VcError(VC_ERR_INVALID, "the selection must have one word per resident record")
+    new_ids = np.empty(n, dtype=np.uint32) if with_map else None
+    kept = C.c_uint64(0)
+    self._check(fn(self._h, _p(sel) if n else None, kind, _p(new_ids) if with_map and n else None, C.byref(kept)))
+    return int(kept.value), new_ids
+
+
+def _retain_dev(self, fn, d_sel, kind, d_new_ids, stream):
+    kept = C.c_uint64(0)
+    self._check(fn(self._h, d_sel, kind, d_new_ids, C.byref(kept), stream))
+    return int(kept.value)
 
 
 def split(packed):
@@ -445,6 +469,16 @@ class Engine:
         return self._check(self._L.vc_search_radius_ids_dev(self._h, d_ids, nq, radius, mode, id_flags, d_out, out_cap, d_offsets, stream),
                            ok=(VC_OK, VC_ERR_CAPACITY))
 
+    def retain(self, sel, kind=RETAIN_MASK, with_map=True):
+        """vc_retain: the records `sel` selects survive (RETAIN_MASK: sel[i] != 0; RETAIN_ROOTS: sel is a labels array of
+        cluster_radius and the groups' representatives survive), renumbered in order; a current index is filtered to them.  Returns
+        (n_kept, new_ids): new_ids[i] = the new global id of old record id_base + i or 0xFFFFFFFF (None without with_map)."""
+        return _retain(self, self._L.vc_retain, sel, kind, with_map)
+
+    def retain_dev(self, d_sel, kind=RETAIN_MASK, d_new_ids=None, stream=None):
+        """vc_retain_dev: d_sel / d_new_ids = raw device addresses of len(self) uint32 (d_new_ids may be None).  Returns n_kept."""
+        return _retain_dev(self, self._L.vc_retain_dev, d_sel, kind, d_new_ids, stream)
+
     def cluster_radius(self, radius, mode=MODE_LINEAR, batch=0, labels=None):
         """vc_cluster_radius: the connected components of the radius graph over all resident records.  Returns (labels, n_pairs,
         n_clusters): labels[i] = the global id of the smallest-id record of the component of record id_base + i.  `labels`: what
@@ -624,6 +658,16 @@ class ShardedEngine:
         or VC_ERR_CAPACITY (d_offsets then holds the compacted prefix sums, d_offsets[nq] the total; d_out is untouched)."""
         return self._check(self._L.vc_sharded_search_radius_ids_dev(self._h, d_ids, nq, radius, mode, id_flags, d_out, out_cap, d_offsets,
                                                                     stream), ok=(VC_OK, VC_ERR_CAPACITY))
+
+    def retain(self, sel, kind=RETAIN_MASK, with_map=True):
+        """vc_sharded_retain: the records `sel` selects survive (RETAIN_MASK: sel[i] != 0; RETAIN_ROOTS: sel is a labels array of
+        cluster_radius and the groups' representatives survive), renumbered in order; a current index is filtered to them.  Returns
+        (n_kept, new_ids): new_ids[i] = the new global id of old record id_base + i or 0xFFFFFFFF (None without with_map)."""
+        return _retain(self, self._L.vc_sharded_retain, sel, kind, with_map)
+
+    def retain_dev(self, d_sel, kind=RETAIN_MASK, d_new_ids=None, stream=None):
+        """vc_sharded_retain_dev: d_sel / d_new_ids = raw device addresses of len(self) uint32 on the root device (d_new_ids may be None).  Returns n_kept."""
+        return _retain_dev(self, self._L.vc_sharded_retain_dev, d_sel, kind, d_new_ids, stream)
 
     def cluster_radius(self, radius, mode=MODE_LINEAR, batch=0, labels=None):
         """vc_sharded_cluster_radius: the connected components of the radius graph over all resident records.  Returns (labels, n_pairs,
