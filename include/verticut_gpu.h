@@ -345,8 +345,9 @@ int vc_search_radius_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_
  * enqueued on `stream`; the host waits where the radius search underneath waits -- once per batch and attempt, for its total -- and
  * once more at the end, for the stats.  Labels are valid in stream order.
  * The scratch (the batch's ids, gathered queries, found words, the raw results and their offsets, two counters) is grow-only
- * buffers of the handle, separate from those of every other call, every word written before it is read within a call: a result
- * depends on the database and the call only.  The raw results grow to the LARGEST batch's total: on duplicate-heavy data that is
+ * buffers of the handle, separate from those of every other call but vc_leaders_radius*, which fills the same batch buffers
+ * completely before it reads them -- every word written before it is read within a call: a result depends on the database and the
+ * call only.  The raw results grow to the LARGEST batch's total: on duplicate-heavy data that is
  * `batch` x the size of a group of duplicates (4096 ids into a bucket of 250 000 are 8 GB), so choose a smaller batch there. */
 typedef struct vc_cluster_stats {
   uint64_t n_pairs;     /* unordered pairs {a < b} within `radius` that this call examined: all those with b >= n_labelled */
@@ -358,6 +359,63 @@ int vc_cluster_radius_dev(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t
  * all N come home); waits for them. */
 int vc_cluster_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
                       vc_cluster_stats* stats);
+
+/* "Drop the near-duplicates", as the one-pass rule of a dedup pipeline: walk the records in id order and keep a record iff no record
+ * kept so far lies within `radius` of it.  It stands for one pass of a first-come dedup over the file order of
+ * build_hash_tables.cc:40-70 (ids are the ordinals of the records), asked through search_R_neighbors, search_worker.cc:222-264.  The
+ * kept records, the LEADERS, are the lexicographically first maximal independent set of the radius graph: every dropped record is
+ * within `radius` of a leader, no two leaders are within `radius` of each other, and whether record i leads depends on the records
+ * 0 .. i only.  vc_cluster_radius groups by single linkage instead: its components chain, and nothing bounds how far a member lies
+ * from its label.
+ * labels: N = vc_size entries.  Record id_base + i is a LEADER iff no leader with a smaller id lies within full Hamming distance
+ * `radius` of it.  labels[i] = the record's own GLOBAL id for a leader, otherwise the global id of the SMALLEST-id leader within
+ * `radius` (one exists and it is smaller than the record's own id): labels[i] <= id_base + i always.  The result is a function of
+ * the database and the radius only, whatever `batch`, `mode`, the order the device worked in or the handle's history.
+ * mode VC_MODE_LINEAR or VC_MODE_MIH_EXACT.  Errors are checked before any work and leave labels untouched: VC_ERR_INVALID for a
+ * null handle, null labels, another mode or n_labelled > N; VC_ERR_STATE in MIH mode without a current index (a stale one counts as
+ * none).  N == 0 gives VC_OK and zero stats; nothing is written.  stats (host memory, may be NULL) is filled when the call returns.
+ * batch: ids per radius search underneath, 0 = 4096; any value >= 1 is legal, larger than N too (above 2^29 it is cut to 2^29); the
+ * result does not depend on it.
+ * n_labelled is the incremental form, the companion of vc_update_index: labels[0 .. n_labelled) come IN.  PRECONDITION: they are
+ * this call's result for those records at this same radius -- by the prefix property that is the same for ANY store whose first
+ * n_labelled records are these.  The incoming entries are READ ONLY: the call writes entries n_labelled .. N and not one byte below
+ * (unlike vc_cluster_radius, where old labels change), and the result is bit for bit that of a call from scratch.  n_labelled == N
+ * writes nothing and only counts.
+ * How: the batches are taken in ascending id order, so every record below a batch is final and leads iff labels[v] == v.  Of a
+ * query's entries only those with an id v below its own matter.  A batch is decided in synchronous ROUNDS over one state word per
+ * query in scratch (never a sentinel inside labels: every 32-bit value is a legal id).  Round 1 also settles against the past: a
+ * leader below the batch drops the query, and the smallest such is its label at once.  In a round an undecided query is DROPPED as
+ * soon as one smaller neighbour of the batch is a decided leader, a LEADER when all of them are decided and dropped (or there is
+ * none), and waits otherwise; a round reads the state the previous round left (a word stored in round r carries r and counts as
+ * undecided to the readers of round r).  Every decision is the sequential pass's own, so the fixed point is unique; the smallest
+ * undecided id is decided in every round, so a batch of nq ids ends after at most nq rounds -- the driver returns VC_ERR_HIP should
+ * that bound ever be crossed.  After the last round the queries dropped inside the batch take the minimum over ALL their leader
+ * neighbours.  No kernel waits for another block; rounds are separate launches, and a round launched behind the fixed point returns
+ * on a device counter before it touches an entry.
+ * Device form: everything is enqueued on `stream`; the host waits where the radius search underneath waits -- once per batch and
+ * attempt, for its total -- once per group of 4 rounds of a batch, for the undecided counter, and once at the end, for the stats.
+ * d_labels must not be touched by the caller during the call.  Labels are valid in stream order.
+ * Scratch: the batch buffers (ids, gathered queries, found words, the raw results and their offsets) and the host form's staged
+ * labels are THOSE OF vc_cluster_radius* -- both calls fill them completely before they read them; the state words, the statistics
+ * and the round counters are this call's own.  All grow-only buffers of the handle, every word written before it is read within a
+ * call; the note on the raw results' size at vc_cluster_radius holds here too.
+ * Consuming the result: vc_retain* with VC_RETAIN_ROOTS accepts these labels as they are (a leader is labelled with itself) and
+ * keeps exactly the leaders.  The survivors then are pairwise farther than `radius` apart, every removed record was within
+ * `radius` of a survivor (the one its label named), and a second call at the same radius finds n_pairs == 0 and every record a
+ * leader. */
+typedef struct vc_leader_stats {
+  uint64_t n_pairs;    /* unordered pairs {a < b} within `radius` with b >= n_labelled: the entries (query b, neighbour a < b) examined;
+                          the same number vc_cluster_stats.n_pairs reports for the same arguments */
+  uint64_t n_leaders;  /* records i with labels[i] == id_base + i over ALL N resident records after the call */
+  uint64_t n_rounds;   /* decision rounds that had work, summed over the batches (at least one per batch): a diagnostic that depends
+                          on `batch`, not part of the result */
+} vc_leader_stats;
+int vc_leaders_radius_dev(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
+                          vc_leader_stats* stats, void* stream);
+/* The same for labels in host memory: the device form on the engine's stream plus the staged labels (the first n_labelled go in,
+ * the entries n_labelled .. N come home); waits for them. */
+int vc_leaders_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
+                      vc_leader_stats* stats);
 
 /* "Take these records out": the store and its index cut down to the surviving records, in place.  The reference has no delete
  * (its store has put and get only, base_proxy.h:18-22, and its index is one pass of build_hash_tables.cc over a code file); the call
@@ -538,6 +596,16 @@ int vc_sharded_cluster_radius_dev(vc_sharded* h, uint32_t radius, uint32_t mode,
                                   vc_cluster_stats* stats, void* stream);
 int vc_sharded_cluster_radius(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
                               vc_cluster_stats* stats);
+/* Greedy leader dedup over all shards: contract, modes, errors, batch, n_labelled (the companion of vc_sharded_update_index, incoming
+ * entries read only), stats and scratch sharing as vc_leaders_radius_dev / vc_leaders_radius, with N = vc_sharded_size and ids global
+ * over the whole store.  d_labels lives on the ROOT device, `stream` is a stream of that device.  The search underneath is
+ * vc_sharded_search_radius_dev into scratch on the root, the batch's ids are gathered as in vc_sharded_get_codes_dev, and the
+ * decision kernels run on the root.  VC_FLAG_GLOBAL_STOP and VC_FLAG_GLOBAL_APPROX play no part.  vc_sharded_retain* with
+ * VC_RETAIN_ROOTS consumes the labels unchanged. */
+int vc_sharded_leaders_radius_dev(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
+                                  vc_leader_stats* stats, void* stream);
+int vc_sharded_leaders_radius(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
+                              vc_leader_stats* stats);
 /* borrow shard g's engine (bucket views, timing, files); its id range is [*first_id, *first_id + *n_ids) */
 int vc_sharded_shard(vc_sharded* h, uint32_t shard, vc_engine** e, uint64_t* first_id, uint64_t* n_ids);
 

@@ -68,6 +68,10 @@ struct vc_engine {
   uint64_t* d_croffs = nullptr; size_t croffs_bytes = 0;
   uint64_t* d_cstat = nullptr;  size_t cstat_bytes = 0;
   uint32_t* d_chlab = nullptr;  size_t chlab_bytes = 0;
+  // greedy leader dedup (vc_leaders_radius*): it shares the batch buffers and the staged labels above (both calls fill them completely);
+  // its own are a batch's state words and the statistics with the round counters
+  uint32_t* d_lstate = nullptr; size_t lstate_bytes = 0;
+  uint64_t* d_lstat = nullptr;  size_t lstat_bytes = 0;
   CleanState clean;                                       // the last kernel of a linear step hands d_state back zeroed: no memset per step
   uint32_t scan_event_tick = 0;                           // VC_FLAG_LEAN_TIMING: only every timing_sample-th verify launch is timed
   VcKnobs knobs;                                          // environment knobs, read once at vc_create
@@ -362,6 +366,8 @@ int vc_destroy(vc_engine* e) {
   (void)hipFree(e->d_croffs);
   (void)hipFree(e->d_cstat);
   (void)hipFree(e->d_chlab);
+  (void)hipFree(e->d_lstate);
+  (void)hipFree(e->d_lstat);
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->last_call) (void)hipEventDestroy(e->last_call);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -1328,6 +1334,94 @@ int vc_cluster_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t bat
   }
   if (rc) return rc;
   VC_HIP(e, hipMemcpyAsync(labels, e->d_chlab, (size_t)e->n * 4, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipStreamSynchronize(e->stream));
+  return VC_OK;
+}
+
+}  // extern "C"
+
+// ---- greedy leader dedup: the first maximal independent set of the radius graph -------------------------------------------------------
+static int check_leaders_args(vc_engine* e, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
+  if (!e || !labels) return VC_ERR_INVALID;
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "leaders: mode must be LINEAR or MIH_EXACT");
+  if (n_labelled > e->n) return fail(e, VC_ERR_INVALID, "leaders: n_labelled %llu exceeds the %llu resident records", (unsigned long long)n_labelled, (unsigned long long)e->n);
+  if (e->n && mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
+  return VC_OK;
+}
+
+// The whole call on e->stream (inside the caller's StreamCall), e->n > 0.  cluster_run's loop over the batch buffers it shares with
+// that call (both fill them completely): per batch of ids, in ascending order, the ids filled on the device, the gather, the radius
+// search -- repeated once with the scratch grown to the total it reported -- and the decision over the raw result as it lies, which
+// waits once per group of rounds.  Entries below n_labelled are only read.  After the last batch one count, then the wait for the stats.
+static int leaders_run(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_leader_stats* stats) {
+  int rc;
+  const uint64_t N = e->n;
+  if (batch == 0) batch = VC_CLUSTER_BATCH;
+  batch = std::min(batch, VC_LEADER_BATCH_MAX);
+  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N - n_labelled);
+  if ((rc = grow(e, &e->d_lstat, &e->lstat_bytes, VC_LEADER_STAT_BYTES))) return rc;
+  if (nq_max) {
+    if ((rc = grow(e, &e->d_cids, &e->cids_bytes, (size_t)nq_max * 4))) return rc;
+    if ((rc = grow(e, &e->d_cq, &e->cq_bytes, (size_t)nq_max * e->W * 8))) return rc;
+    if ((rc = grow(e, &e->d_cfound, &e->cfound_bytes, (size_t)nq_max * 4))) return rc;
+    if ((rc = grow(e, &e->d_croffs, &e->croffs_bytes, ((size_t)nq_max + 1) * 8))) return rc;
+    if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)8 << 16))) return rc;
+    if ((rc = grow(e, &e->d_lstate, &e->lstate_bytes, (size_t)nq_max * 4))) return rc;
+  }
+  VC_HIP(e, hipMemsetAsync(e->d_lstat, 0, VC_LEADER_STAT_BYTES, e->stream));
+  for (uint64_t pos = n_labelled; pos < N; pos += batch) {
+    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = e->cfg.id_base + (uint32_t)pos;
+    VC_HIP(e, vc_launch_cluster_init(e->d_cids, nq, first_id, e->stream));
+    VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, e->d_cids, nq, e->d_cq, e->d_cfound, e->stream));
+    uint64_t raw_total = 0;
+    for (int attempt = 0;; ++attempt) {
+      const uint64_t cap = e->craw_bytes / 8;
+      rc = vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, e->d_cq, nq,
+                            radius, e->d_craw, cap, e->d_croffs, true, &e->radius_work, e->stream, &e->err, &raw_total);
+      if (rc == VC_OK) break;
+      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
+      if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)raw_total * 8))) return rc;   // (the first attempt has been waited for)
+    }
+    bool stuck = false;
+    VC_HIP(e, vc_leaders_decide_batch(e->d_craw, e->d_croffs, nq, first_id, e->cfg.id_base, d_labels, e->d_lstate, e->d_lstat, e->stream, &stuck));
+    if (stuck) return fail(e, VC_ERR_HIP, "leaders: the batch at id %u is undecided after %u rounds", first_id, nq);
+  }
+  VC_HIP(e, vc_launch_leaders_count(d_labels, N, e->cfg.id_base, e->d_lstat + 1, e->stream));
+  uint64_t st[3] = {0, 0, 0};
+  VC_HIP(e, hipMemcpyAsync(st, e->d_lstat, 24, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipStreamSynchronize(e->stream));
+  if (stats) *stats = vc_leader_stats{st[0], st[1], st[2]};
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_leaders_radius_dev(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
+                          vc_leader_stats* stats, void* stream) {
+  int rc = check_leaders_args(e, mode, n_labelled, d_labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_leader_stats{0, 0, 0};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, caller_stream(e, stream));
+  return leaders_run(e, radius, mode, batch, n_labelled, d_labels, stats);
+}
+
+int vc_leaders_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats) {
+  int rc = check_leaders_args(e, mode, n_labelled, labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_leader_stats{0, 0, 0};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  if ((rc = grow(e, &e->d_chlab, &e->chlab_bytes, (size_t)e->n * 4))) return rc;
+  if (n_labelled) VC_HIP(e, hipMemcpyAsync(e->d_chlab, labels, (size_t)n_labelled * 4, hipMemcpyHostToDevice, e->stream));
+  {
+    const StreamCall call(e, e->stream);
+    rc = leaders_run(e, radius, mode, batch, n_labelled, e->d_chlab, stats);
+  }
+  if (rc) return rc;
+  if (n_labelled < e->n)   // the incoming entries are read only: they do not travel back
+    VC_HIP(e, hipMemcpyAsync(labels + n_labelled, e->d_chlab + n_labelled, (size_t)(e->n - n_labelled) * 4, hipMemcpyDeviceToHost, e->stream));
   VC_HIP(e, hipStreamSynchronize(e->stream));
   return VC_OK;
 }

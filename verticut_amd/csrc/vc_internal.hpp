@@ -202,6 +202,19 @@ hipError_t vc_launch_cluster_union(const uint64_t* d_raw, const uint64_t* d_roff
                                    uint32_t id_base, uint32_t* d_labels, uint64_t* d_n_pairs, hipStream_t s);
 // d_labels[i] = the root of record i (the smallest id of its component), in place; *d_n_clusters += the roots
 hipError_t vc_launch_cluster_flatten(uint32_t* d_labels, uint64_t n, uint32_t id_base, uint64_t* d_n_clusters, hipStream_t s);
+// ---- vc_leaders.hip: greedy leader dedup (vc_leaders_radius*).  d_labels [n]: slot i holds the global id of the smallest-id leader
+// within the radius of record id_base + i, its own id for a leader; entries below the batch are final and only read.
+#define VC_LEADER_ROUND_GROUP 4u           // decision rounds enqueued between two read-backs of the undecided counter
+#define VC_LEADER_BATCH_MAX (1u << 29)     // a larger `batch` is cut to this: the round number shares the state word with two flags
+#define VC_LEADER_STAT_BYTES 64u           // d_stat: 3 x uint64 (pairs, leaders, rounds that had work), then the 3 round counters (+ 1 pad)
+// One batch: the raw result (d_raw, its nq + 1 offsets d_roffs) of the queries first_id .. first_id + nq - 1 is decided in rounds of
+// at most VC_LEADER_ROUND_GROUP launches between two waits on `s` for the undecided counter, then the batch's labels are written.
+// d_state: nq words of scratch, every one written by the first round.  d_stat[0] += the entries (query b, neighbour a < b),
+// d_stat[2] += the rounds that had work.  *stuck: queries were still undecided after nq rounds (cannot happen; the caller reports it).
+hipError_t vc_leaders_decide_batch(const uint64_t* d_raw, const uint64_t* d_roffs, uint32_t nq, uint32_t first_id, uint32_t id_base, uint32_t* d_labels,
+                                   uint32_t* d_state, uint64_t* d_stat, hipStream_t s, bool* stuck);
+// *d_n_leaders += the records i < n with d_labels[i] == id_base + i; nothing is waited for
+hipError_t vc_launch_leaders_count(const uint32_t* d_labels, uint64_t n, uint32_t id_base, uint64_t* d_n_leaders, hipStream_t s);
 // ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
 struct VcKeepSet;
 #define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)

@@ -131,6 +131,9 @@ enum RootBuf {
   // near-duplicate clustering: a batch's ids, gathered queries and found words, the union's raw results and offsets, the two
   // counters (pairs, clusters); the host-pointer form's staged labels
   CL_IDS, CL_Q, CL_FOUND, CL_RAW, CL_ROFFS, CL_STAT, CL_HLAB,
+  // greedy leader dedup: it shares CL_IDS .. CL_ROFFS and CL_HLAB (both calls fill them completely); its own are a batch's state
+  // words and the statistics with the round counters
+  LD_STATE, LD_STAT,
   ROOT_BUFS
 };
 
@@ -2163,6 +2166,101 @@ int vc_sharded_cluster_radius(vc_sharded* h, uint32_t radius, uint32_t mode, uin
   if ((rc = sharded_cluster_run(h, radius, mode, batch, n_labelled, h->buf[CL_HLAB].as<uint32_t>(), stats, S))) return rc;
   VS_HIP(h, hipSetDevice(h->root));
   VS_HIP(h, hipMemcpyAsync(labels, h->buf[CL_HLAB].p, (size_t)h->n * 4, hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipStreamSynchronize(S));
+  return VC_OK;
+}
+
+}  // extern "C"
+
+// ---- greedy leader dedup over the shards ----------------------------------------------------------------------------------------------
+static int check_sharded_leaders_args(vc_sharded* h, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
+  if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
+  if (n_labelled > h->n) return sfail(h, VC_ERR_INVALID, "leaders: n_labelled %llu exceeds the %llu resident records", (unsigned long long)n_labelled, (unsigned long long)h->n);
+  if (mode == VC_MODE_MIH_EXACT)
+    for (uint32_t g = 0; g < h->G; ++g)
+      if (shard_size(h, g) && !vc_engine_has_index(h->eng[g])) return sfail(h, VC_ERR_STATE, "shard %u: MIH search needs vc_sharded_build_index() first", g);
+  return VC_OK;
+}
+
+// All on the root device's stream S, h->n > 0.  sharded_cluster_run's loop over the batch buffers it shares with that call: per batch
+// of global ids, ascending, the ids filled on the root, the gather over the shards, the union's radius search -- repeated once with
+// the scratch grown to the total it reported -- and the decision rounds over the raw result on the root, which wait once per group
+// of rounds.  Entries below n_labelled are only read.  After the last batch one count, then the wait for the stats.
+static int sharded_leaders_run(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
+                               vc_leader_stats* stats, hipStream_t S) {
+  int rc;
+  const uint32_t id_base = h->cfg.engine.id_base;
+  const uint64_t N = h->n;
+  if (batch == 0) batch = VC_CLUSTER_BATCH;
+  batch = std::min(batch, VC_LEADER_BATCH_MAX);
+  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N - n_labelled);
+  VS_HIP(h, hipSetDevice(h->root));
+  if ((rc = h->buf[LD_STAT].grow(h, VC_LEADER_STAT_BYTES))) return rc;
+  if (nq_max) {
+    if ((rc = h->buf[CL_IDS].grow(h, (size_t)nq_max * 4))) return rc;
+    if ((rc = h->buf[CL_Q].grow(h, (size_t)nq_max * h->nbytes))) return rc;
+    if ((rc = h->buf[CL_FOUND].grow(h, (size_t)nq_max * 4))) return rc;
+    if ((rc = h->buf[CL_ROFFS].grow(h, ((size_t)nq_max + 1) * 8))) return rc;
+    if ((rc = h->buf[CL_RAW].grow(h, (size_t)8 << 16))) return rc;
+    if ((rc = h->buf[LD_STATE].grow(h, (size_t)nq_max * 4))) return rc;
+  }
+  uint64_t* d_stat = h->buf[LD_STAT].as<uint64_t>();
+  uint32_t* d_ids = h->buf[CL_IDS].as<uint32_t>();
+  VS_HIP(h, hipMemsetAsync(d_stat, 0, VC_LEADER_STAT_BYTES, S));
+  for (uint64_t pos = n_labelled; pos < N; pos += batch) {
+    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = id_base + (uint32_t)pos;
+    VS_HIP(h, hipSetDevice(h->root));
+    VS_HIP(h, vc_launch_cluster_init(d_ids, nq, first_id, S));
+    if ((rc = sharded_gather_ids(h, d_ids, nq, h->buf[CL_Q].as<uint64_t>(), h->buf[CL_FOUND].as<uint32_t>(), true, S))) return rc;
+    uint64_t raw_total = 0;
+    for (int attempt = 0;; ++attempt) {
+      const uint64_t cap = h->buf[CL_RAW].bytes / 8;
+      rc = sharded_radius_dev(h, h->buf[CL_Q].p, nq, radius, mode, h->buf[CL_RAW].as<uint64_t>(), cap, h->buf[CL_ROFFS].as<uint64_t>(), S, &raw_total);
+      if (rc == VC_OK) break;
+      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
+      VS_HIP(h, hipSetDevice(h->root));
+      if ((rc = h->buf[CL_RAW].grow(h, (size_t)raw_total * 8))) return rc;
+    }
+    VS_HIP(h, hipSetDevice(h->root));
+    bool stuck = false;
+    VS_HIP(h, vc_leaders_decide_batch(h->buf[CL_RAW].as<uint64_t>(), h->buf[CL_ROFFS].as<uint64_t>(), nq, first_id, id_base, d_labels,
+                                      h->buf[LD_STATE].as<uint32_t>(), d_stat, S, &stuck));
+    if (stuck) return sfail(h, VC_ERR_HIP, "leaders: the batch at id %u is undecided after %u rounds", first_id, nq);
+  }
+  VS_HIP(h, hipSetDevice(h->root));
+  VS_HIP(h, vc_launch_leaders_count(d_labels, N, id_base, d_stat + 1, S));
+  uint64_t st[3] = {0, 0, 0};
+  VS_HIP(h, hipMemcpyAsync(st, d_stat, 24, hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipStreamSynchronize(S));
+  if (stats) *stats = vc_leader_stats{st[0], st[1], st[2]};
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_sharded_leaders_radius_dev(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
+                                  vc_leader_stats* stats, void* stream) {
+  int rc = check_sharded_leaders_args(h, mode, n_labelled, d_labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_leader_stats{0, 0, 0};
+  if (h->n == 0) return VC_OK;
+  return sharded_leaders_run(h, radius, mode, batch, n_labelled, d_labels, stats, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+}
+
+int vc_sharded_leaders_radius(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
+                              vc_leader_stats* stats) {
+  int rc = check_sharded_leaders_args(h, mode, n_labelled, labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_leader_stats{0, 0, 0};
+  if (h->n == 0) return VC_OK;
+  hipStream_t S = h->root_stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  if ((rc = h->buf[CL_HLAB].grow(h, (size_t)h->n * 4))) return rc;
+  if (n_labelled) VS_HIP(h, hipMemcpyAsync(h->buf[CL_HLAB].p, labels, (size_t)n_labelled * 4, hipMemcpyHostToDevice, S));
+  if ((rc = sharded_leaders_run(h, radius, mode, batch, n_labelled, h->buf[CL_HLAB].as<uint32_t>(), stats, S))) return rc;
+  VS_HIP(h, hipSetDevice(h->root));
+  if (n_labelled < h->n)   // the incoming entries are read only: they do not travel back
+    VS_HIP(h, hipMemcpyAsync(labels + n_labelled, h->buf[CL_HLAB].as<uint32_t>() + n_labelled, (size_t)(h->n - n_labelled) * 4, hipMemcpyDeviceToHost, S));
   VS_HIP(h, hipStreamSynchronize(S));
   return VC_OK;
 }

@@ -22,6 +22,7 @@ SYNTH_UNIFORM, SYNTH_CLUSTERED = 0, 1
 ORDER_ASCENDING, ORDER_FARTHEST_FIRST = 0, 1
 IDS_EXCLUDE_SELF = 0x1    # VC_IDS_EXCLUDE_SELF: a by-id row holds the k nearest items other than the query's own record
 IDS_ONLY_GREATER = 0x2    # VC_IDS_ONLY_GREATER (radius-by-id calls only): a segment keeps the entries whose id exceeds the query's own
+LEADER_ROUND_GROUP = 4            # VC_LEADER_ROUND_GROUP (vc_internal.hpp): decision rounds between two read-backs of the undecided counter
 RETAIN_MASK, RETAIN_ROOTS = 0, 1   # VC_RETAIN_MASK: record i survives iff sel[i] != 0; VC_RETAIN_ROOTS: iff sel[i] == id_base + i (cluster labels)
 PACK_INF = np.uint64(0xFFFFFFFFFFFFFFFF)
 STREAM_OWN = C.c_void_p(-1)   # VC_STREAM_OWN; None / 0 = the HIP null stream (PyTorch's default stream)
@@ -43,6 +44,7 @@ EXPORTS = [
     "vc_update_index", "vc_sharded_update_index",
     "vc_cluster_radius", "vc_cluster_radius_dev", "vc_sharded_cluster_radius", "vc_sharded_cluster_radius_dev",
     "vc_retain", "vc_retain_dev", "vc_sharded_retain", "vc_sharded_retain_dev",
+    "vc_leaders_radius", "vc_leaders_radius_dev", "vc_sharded_leaders_radius", "vc_sharded_leaders_radius_dev",
 ]
 MAX_SHARDS = 16
 EXCHANGE_AUTO, EXCHANGE_PEER_COPY, EXCHANGE_RCCL = 0, 1, 2
@@ -72,6 +74,10 @@ class VcQueryStats(C.Structure):
 
 class VcClusterStats(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("n_clusters", C.c_uint64)]
+
+
+class VcLeaderStats(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("n_leaders", C.c_uint64), ("n_rounds", C.c_uint64)]
 
 
 class VcTiming(C.Structure):
@@ -176,6 +182,10 @@ def load_library():
     L.vc_retain_dev.argtypes = [vp, vp, u32, vp, vp, vp]
     L.vc_sharded_retain.argtypes = [vp, vp, u32, vp, vp]
     L.vc_sharded_retain_dev.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.vc_leaders_radius.argtypes = [vp, u32, u32, u32, u64, vp, vp]
+    L.vc_leaders_radius_dev.argtypes = [vp, u32, u32, u32, u64, vp, vp, vp]
+    L.vc_sharded_leaders_radius.argtypes = [vp, u32, u32, u32, u64, vp, vp]
+    L.vc_sharded_leaders_radius_dev.argtypes = [vp, u32, u32, u32, u64, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -236,6 +246,28 @@ def _cluster_radius_dev(self, fn, radius, d_labels, mode, batch, n_labelled, str
     st = VcClusterStats()
     self._check(fn(self._h, radius, mode, batch, n_labelled, d_labels, C.byref(st), stream))
     return int(st.n_pairs), int(st.n_clusters)
+
+
+def _leaders_radius(self, fn, radius, mode, batch, labels):
+    """shared by Engine.leaders_radius and ShardedEngine.leaders_radius: (labels [N] uint32, n_pairs, n_leaders, n_rounds)"""
+    n = len(self)
+    out = np.empty(n, dtype=np.uint32)
+    n_labelled = 0
+    if labels is not None:
+        old = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+        n_labelled = old.shape[0]
+        if n_labelled > n:
+            raise VcError(VC_ERR_INVALID, "more labels than resident records")
+        out[:n_labelled] = old
+    st = VcLeaderStats()
+    self._check(fn(self._h, radius, mode, batch, n_labelled, _p(out), C.byref(st)))
+    return out, int(st.n_pairs), int(st.n_leaders), int(st.n_rounds)
+
+
+def _leaders_radius_dev(self, fn, radius, d_labels, mode, batch, n_labelled, stream):
+    st = VcLeaderStats()
+    self._check(fn(self._h, radius, mode, batch, n_labelled, d_labels, C.byref(st), stream))
+    return int(st.n_pairs), int(st.n_leaders), int(st.n_rounds)
 
 
 def _retain(self, fn, sel, kind, with_map):
@@ -491,6 +523,19 @@ class Engine:
         entries come in); labels valid in `stream` order.  Returns (n_pairs, n_clusters)."""
         return _cluster_radius_dev(self, self._L.vc_cluster_radius_dev, radius, d_labels, mode, batch, n_labelled, stream)
 
+    def leaders_radius(self, radius, mode=MODE_LINEAR, batch=0, labels=None):
+        """vc_leaders_radius: the greedy one-pass dedup over all resident records in id order.  Returns (labels, n_pairs, n_leaders,
+        n_rounds): labels[i] = the record's own global id for a LEADER (no leader with a smaller id within `radius`), else the
+        smallest-id leader within `radius`.  `labels`: what an earlier call at this radius returned for the first len(labels)
+        records -- they are only read and only the records behind them are queried (the incremental form, after add_codes +
+        update_index); the result equals a call from scratch.  retain(labels, RETAIN_ROOTS) keeps exactly the leaders."""
+        return _leaders_radius(self, self._L.vc_leaders_radius, radius, mode, batch, labels)
+
+    def leaders_radius_dev(self, radius, d_labels, mode=MODE_MIH_EXACT, batch=0, n_labelled=0, stream=None):
+        """vc_leaders_radius_dev: d_labels = the raw device address of len(self) uint32 (its first n_labelled entries come in and are
+        only read); labels valid in `stream` order.  Returns (n_pairs, n_leaders, n_rounds)."""
+        return _leaders_radius_dev(self, self._L.vc_leaders_radius_dev, radius, d_labels, mode, batch, n_labelled, stream)
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -680,6 +725,19 @@ class ShardedEngine:
         """vc_sharded_cluster_radius_dev: d_labels = the raw device address of len(self) uint32 on the root device, the union-find forest in place (its first n_labelled
         entries come in); labels valid in `stream` order.  Returns (n_pairs, n_clusters)."""
         return _cluster_radius_dev(self, self._L.vc_sharded_cluster_radius_dev, radius, d_labels, mode, batch, n_labelled, stream)
+
+    def leaders_radius(self, radius, mode=MODE_LINEAR, batch=0, labels=None):
+        """vc_sharded_leaders_radius: the greedy one-pass dedup over all resident records in id order.  Returns (labels, n_pairs, n_leaders,
+        n_rounds): labels[i] = the record's own global id for a LEADER (no leader with a smaller id within `radius`), else the
+        smallest-id leader within `radius`.  `labels`: what an earlier call at this radius returned for the first len(labels)
+        records -- they are only read and only the records behind them are queried (the incremental form, after add_codes +
+        update_index); the result equals a call from scratch.  retain(labels, RETAIN_ROOTS) keeps exactly the leaders."""
+        return _leaders_radius(self, self._L.vc_sharded_leaders_radius, radius, mode, batch, labels)
+
+    def leaders_radius_dev(self, radius, d_labels, mode=MODE_MIH_EXACT, batch=0, n_labelled=0, stream=None):
+        """vc_sharded_leaders_radius_dev: d_labels = the raw device address of len(self) uint32 on the root device (its first n_labelled entries come in and are
+        only read); labels valid in `stream` order.  Returns (n_pairs, n_leaders, n_rounds)."""
+        return _leaders_radius_dev(self, self._L.vc_sharded_leaders_radius_dev, radius, d_labels, mode, batch, n_labelled, stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

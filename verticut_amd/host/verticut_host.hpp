@@ -121,6 +121,10 @@ class Backend {
   // near-duplicate groups: labels[i] = smallest id of the component of record i in the radius graph (vc_cluster_radius /
   // vc_sharded_cluster_radius; labels[0 .. n_labelled) come in for the incremental form)
   virtual int cluster_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats) = 0;
+  // greedy leader dedup: labels[i] = own id for a LEADER (no leader with a smaller id within `radius`), else the smallest-id leader
+  // within `radius` (vc_leaders_radius / vc_sharded_leaders_radius; labels[0 .. n_labelled) come in, read only); retain() with
+  // VC_RETAIN_ROOTS keeps exactly the leaders
+  virtual int leaders_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats) = 0;
   // records taken out of the store and its index, the survivors renumbered in order (vc_retain / vc_sharded_retain; the reference has
   // no delete: this stands for build_hash_tables.cc run again over the code file without them).  kind VC_RETAIN_MASK / VC_RETAIN_ROOTS
   virtual int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) = 0;
@@ -177,6 +181,9 @@ class Engine : public Backend {
   }
   int cluster_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats) override {
     return vc_cluster_radius(h_, radius, mode, batch, n_labelled, labels, stats);
+  }
+  int leaders_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats) override {
+    return vc_leaders_radius(h_, radius, mode, batch, n_labelled, labels, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_retain(h_, sel, kind, new_ids, n_kept); }
  private:
@@ -261,6 +268,9 @@ class ShardedEngine : public Backend {
   }
   int cluster_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats) override {
     return vc_sharded_cluster_radius(h_, radius, mode, batch, n_labelled, labels, stats);
+  }
+  int leaders_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats) override {
+    return vc_sharded_leaders_radius(h_, radius, mode, batch, n_labelled, labels, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_sharded_retain(h_, sel, kind, new_ids, n_kept); }
  private:
