@@ -345,8 +345,8 @@ int vc_search_radius_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_
  * enqueued on `stream`; the host waits where the radius search underneath waits -- once per batch and attempt, for its total -- and
  * once more at the end, for the stats.  Labels are valid in stream order.
  * The scratch (the batch's ids, gathered queries, found words, the raw results and their offsets, two counters) is grow-only
- * buffers of the handle, separate from those of every other call but vc_leaders_radius*, which fills the same batch buffers
- * completely before it reads them -- every word written before it is read within a call: a result depends on the database and the
+ * buffers of the handle, separate from those of every other call but vc_leaders_radius* and vc_dbscan_radius*, which fill the same
+ * batch buffers completely before they read them -- every word written before it is read within a call: a result depends on the database and the
  * call only.  The raw results grow to the LARGEST batch's total: on duplicate-heavy data that is
  * `batch` x the size of a group of duplicates (4096 ids into a bucket of 250 000 are 8 GB), so choose a smaller batch there. */
 typedef struct vc_cluster_stats {
@@ -417,6 +417,65 @@ int vc_leaders_radius_dev(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t
 int vc_leaders_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
                       vc_leader_stats* stats);
 
+/* "Group the near-duplicates by density": DBSCAN over the radius graph.  It stands for search_R_neighbors, search_worker.cc:222-264,
+ * asked for every record of the file order of build_hash_tables.cc:40-70 (ids are the ordinals of the records), followed by the
+ * textbook density rule.  vc_cluster_radius takes ONE neighbour within `radius` as proof that two records belong together, so one
+ * accidental near pair welds two groups; vc_leaders_radius does not chain but has no notion of noise.  Here:
+ *   a record is a CORE iff at least min_pts records lie within `radius` of it;
+ *   the CLUSTERS are the components of the graph whose vertices are the cores, two cores within `radius` being adjacent;
+ *   a non-core record with at least one core within `radius` is a BORDER of the cluster of its smallest-id core neighbour
+ *   (textbook DBSCAN leaves a border between two clusters to the visiting order; here the choice is fixed);
+ *   every other record is NOISE.
+ * N = vc_size.  degrees: N entries, may be NULL (the handle then uses grow-only scratch of its own).  degrees[i] = the number of
+ * resident records within full Hamming distance `radius` of record id_base + i, the record ITSELF counted (scikit-learn's min_samples
+ * convention) and exact duplicates once each; record i is a core iff degrees[i] >= min_pts.
+ * labels: N entries.  Core: the smallest GLOBAL id among the cores of its component.  Border: the label of its smallest-id core
+ * neighbour.  Noise: its own global id.
+ * TELLING THE KINDS APART: no sentinel is used, every 32-bit value being a legal id.  With own = id_base + i:
+ *   noise                        labels[i] == own and degrees[i] <  min_pts
+ *   a cluster's representative   labels[i] == own and degrees[i] >= min_pts
+ *   another core of a cluster    labels[i] != own and degrees[i] >= min_pts
+ *   border                       labels[i] != own and degrees[i] <  min_pts
+ * The result is a function of the database, `radius` and min_pts only, whatever `batch`, `mode`, the order the device worked in or
+ * the handle's history.  min_pts == 1 makes every record a core: the labels are bit for bit those of vc_cluster_radius.  min_pts == 2
+ * makes every record with a neighbour a core: the labels again equal vc_cluster_radius', the isolated records reported as noise.
+ * min_pts > N makes every record noise: the labels are the identity and n_clusters == 0.
+ * mode VC_MODE_LINEAR or VC_MODE_MIH_EXACT.  Errors are checked before any work and leave labels and degrees untouched:
+ * VC_ERR_INVALID for a null handle, null labels, min_pts == 0 or another mode; VC_ERR_STATE in MIH mode without a current index (a
+ * stale one counts as none).  N == 0 gives VC_OK and zero stats; nothing is written.  stats (host memory, may be NULL) is filled when
+ * the call returns.  batch: as in vc_cluster_radius, 0 = 4096, any value >= 1 is legal; the result does not depend on it.
+ * THERE IS NO n_labelled FORM: a new record can raise an old record to core, and the pairs of OLD records which that promotion
+ * makes matter (two old cores to unite, an old border to anchor) are not seen again by a walk of the new records alone.  After
+ * vc_add_codes + vc_update_index call again from scratch.
+ * How: ONE walk of the radius search, as in vc_cluster_radius.  The batches are taken in ascending id order.  The degree of a
+ * queried record is the length of its raw segment (the search returns every record within the radius exactly once, the query's own
+ * included), so after a batch's degree launch every record up to the batch's end has its final degree.  Every unordered pair is
+ * also seen from its LARGER member, and by then both degrees are known: the edge launch acts on the entries whose id is below the
+ * query's own -- two cores are united in a lock-free forest over the cores (labels[] in place, the larger root hooked under the
+ * smaller), exactly one core is noted by the other record as its anchor, the minimum kept.  After the last batch one finish pass
+ * writes the roots and counts the kinds.  No kernel waits for another block.
+ * Device form: everything is enqueued on `stream`; the host waits where the radius search underneath waits -- once per batch and
+ * attempt, for its total -- and once at the end, for the stats.  d_labels and d_degrees must not be touched by the caller during
+ * the call.  Results are valid in stream order.
+ * Scratch: the batch buffers (ids, gathered queries, found words, the raw results and their offsets) and the host form's staged
+ * labels are THOSE OF vc_cluster_radius* / vc_leaders_radius* -- every call fills them completely before it reads them; the degrees
+ * of a call that passes none and the statistics are this call's own.  All grow-only buffers of the handle, every word written
+ * before it is read within a call; the note on the raw results' size at vc_cluster_radius holds here too.
+ * Consuming the result: vc_retain* with VC_RETAIN_ROOTS accepts these labels as they are.  It keeps one representative per cluster
+ * and every noise record (both are labelled with themselves) and drops the borders and the other cores: n_clusters + n_noise
+ * records survive. */
+typedef struct vc_dbscan_stats {
+  uint64_t n_pairs;     /* unordered pairs {a < b} within `radius`: every one examined once (== vc_cluster_stats.n_pairs at n_labelled 0) */
+  uint64_t n_clusters;  /* components of the core graph */
+  uint64_t n_core, n_border, n_noise;   /* sum to N */
+} vc_dbscan_stats;
+int vc_dbscan_radius_dev(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels,
+                         uint32_t* d_degrees, vc_dbscan_stats* stats, void* stream);
+/* The same for labels and degrees (may be NULL) in host memory: the device form on the engine's stream into staged buffers, which
+ * then come home; waits for them. */
+int vc_dbscan_radius(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees,
+                     vc_dbscan_stats* stats);
+
 /* "Take these records out": the store and its index cut down to the surviving records, in place.  The reference has no delete
  * (its store has put and get only, base_proxy.h:18-22, and its index is one pass of build_hash_tables.cc over a code file); the call
  * stands for running build_hash_tables.cc:40-70 again over the code file without the removed records, and replaces the copy home of
@@ -424,7 +483,8 @@ int vc_leaders_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t bat
  * N = vc_size before the call, K = the survivors.  sel: N words.  kind says how they are read:                                      */
 #define VC_RETAIN_MASK  0u   /* record i survives iff sel[i] != 0 */
 #define VC_RETAIN_ROOTS 1u   /* record i survives iff sel[i] == id_base + i: `sel` is a labels array of vc_cluster_radius*,
-                                the survivors are the groups' representatives */
+                                the survivors are the groups' representatives (of vc_leaders_radius*: the leaders; of
+                                vc_dbscan_radius*: one representative per cluster and every noise record) */
 /* new_ids (N words, may be NULL): new_ids[i] = the new GLOBAL id of old record id_base + i, or UINT32_MAX if it was removed -- the map
  * that carries labels, or any table keyed by id, across the call.  *n_kept (may be NULL) = K.
  * Afterwards vc_size == K, the survivors keep their relative order and survivor number j has global id id_base + j (ids stay ordinals
@@ -606,6 +666,15 @@ int vc_sharded_leaders_radius_dev(vc_sharded* h, uint32_t radius, uint32_t mode,
                                   vc_leader_stats* stats, void* stream);
 int vc_sharded_leaders_radius(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
                               vc_leader_stats* stats);
+/* Density clustering over all shards: contract, kinds, modes, errors, batch, stats and scratch sharing as vc_dbscan_radius_dev /
+ * vc_dbscan_radius (no n_labelled form either), with N = vc_sharded_size and ids global over the whole store.  d_labels and d_degrees
+ * live on the ROOT device, `stream` is a stream of that device.  The search underneath is vc_sharded_search_radius_dev into scratch
+ * on the root, the batch's ids are gathered as in vc_sharded_get_codes_dev, and the three kernels run on the root with global ids.
+ * VC_FLAG_GLOBAL_STOP and VC_FLAG_GLOBAL_APPROX play no part.  vc_sharded_retain* with VC_RETAIN_ROOTS consumes the labels unchanged. */
+int vc_sharded_dbscan_radius_dev(vc_sharded* h, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels,
+                                 uint32_t* d_degrees, vc_dbscan_stats* stats, void* stream);
+int vc_sharded_dbscan_radius(vc_sharded* h, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels,
+                             uint32_t* degrees, vc_dbscan_stats* stats);
 /* borrow shard g's engine (bucket views, timing, files); its id range is [*first_id, *first_id + *n_ids) */
 int vc_sharded_shard(vc_sharded* h, uint32_t shard, vc_engine** e, uint64_t* first_id, uint64_t* n_ids);
 

@@ -5,48 +5,16 @@
 // ============================================================================
 #include <algorithm>
 
+#include "vc_forest.hpp"
 #include "vc_internal.hpp"
 
-// labels[] IS the forest, in place: slot i (record id_base + i) holds the GLOBAL id of the record's parent, a root holds its own id.
-// Ids stay below 2^32, so unsigned compares on global ids are the order.  Three invariants hold after every single store:
-//   (1) a parent never exceeds its child: parent(x) <= x, with equality exactly at a root;
-//   (2) only a root's slot is CAS-ed, from "itself" to a smaller id -- a record that stopped being a root never becomes one again;
-//   (3) path halving stores an ancestor of the same tree (the grandparent read a moment ago) into a slot that is no root.
-// From (1): every chain strictly descends, so every walk ends and the forest is acyclic under any interleaving.  From (2) and (3):
-// a store moves a subtree below a smaller record of a tree it is, or becomes, part of -- trees merge and never split, and two records
-// are in one tree exactly when the unions made so far connect them.  From (1) again: the root of a tree is its smallest id.  Once
-// every kept entry has been united the trees are the components of the radius graph, so the flattened label of a record -- the
-// smallest id of its component -- depends on the database and the radius only, not on the order in which the lanes arrived.
+// labels[] IS the forest, in place; the forest, its three invariants and its primitives are vc_forest.hpp's.  Once every kept entry
+// has been united the trees are the components of the radius graph, so the flattened label of a record -- the smallest id of its
+// component -- depends on the database and the radius only, not on the order in which the lanes arrived.
 //   vc_cluster_init_kernel     dst[j] = first + j: the labels of the records that come in unlabelled, and a batch's ids
 //   vc_cluster_union_kernel    one thread per entry of the flat raw result: its query by binary search, the keep rule, the union
 //   vc_cluster_flatten_kernel  labels[i] = root of i, in place; counts the roots
-// Slots are read and written with relaxed device-scope atomics (no stale line of a CU's L1 is ever walked), hooked with atomicCAS.
 #define CL_BLK 256u
-
-__device__ __forceinline__ uint32_t cl_ld(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void cl_st(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of global id x, halving the path on the way: x's slot gets its grandparent, the walk goes on from there
-__device__ __forceinline__ uint32_t cl_find_halving(uint32_t* labels, uint32_t id_base, uint32_t x) {
-  uint32_t p = cl_ld(labels + (x - id_base));
-  while (p != x) {
-    const uint32_t gp = cl_ld(labels + (p - id_base));
-    if (gp == p) return p;
-    cl_st(labels + (x - id_base), gp);   // (3): x is no root (p < x), gp <= p is an ancestor of x
-    x = gp;
-    p = cl_ld(labels + (x - id_base));
-  }
-  return x;
-}
-
-// the root of x by reads alone
-__device__ __forceinline__ uint32_t cl_find(const uint32_t* labels, uint32_t id_base, uint32_t x) {
-  for (;;) {
-    const uint32_t p = cl_ld(labels + (x - id_base));
-    if (p == x) return x;
-    x = p;
-  }
-}
 
 __global__ void __launch_bounds__(CL_BLK) vc_cluster_init_kernel(uint32_t* __restrict__ dst, uint64_t count, uint32_t first) {
   for (uint64_t j = (uint64_t)blockIdx.x * CL_BLK + threadIdx.x; j < count; j += (uint64_t)gridDim.x * CL_BLK) dst[j] = first + (uint32_t)j;
@@ -78,17 +46,7 @@ __global__ void __launch_bounds__(CL_BLK) vc_cluster_union_kernel(const uint64_t
     }
     kept += (uint32_t)__popcll(__ballot(keep));
     if (keep) {
-      uint32_t a = own, b = v;
-      for (;;) {
-        a = cl_find_halving(labels, id_base, a);
-        b = cl_find_halving(labels, id_base, b);
-        if (a == b) break;
-        const uint32_t big = a > b ? a : b, small = a > b ? b : a;
-        // (2): hook the LARGER root under the smaller, on the larger root's own slot, expecting it to be a root still.  `small`
-        // may have stopped being a root meanwhile: it is smaller all the same, (1) holds, and the trees are merged.
-        if (atomicCAS(labels + (big - id_base), big, small) == big) break;
-        // somebody else hooked `big`: that is progress of the whole; find again from the two records reached
-      }
+      cl_unite(labels, id_base, own, v);
     }
   }
   if (vc_lane() == 0 && kept) atomicAdd(n_pairs, (unsigned long long)kept);

@@ -72,6 +72,10 @@ struct vc_engine {
   // its own are a batch's state words and the statistics with the round counters
   uint32_t* d_lstate = nullptr; size_t lstate_bytes = 0;
   uint64_t* d_lstat = nullptr;  size_t lstat_bytes = 0;
+  // density clustering (vc_dbscan_radius*): it shares the same batch buffers and staged labels (it fills them completely too); its
+  // own are the degrees of a call that passes none (and of the host form) and the five statistics
+  uint32_t* d_ddeg = nullptr;   size_t ddeg_bytes = 0;
+  uint64_t* d_dstat = nullptr;  size_t dstat_bytes = 0;
   CleanState clean;                                       // the last kernel of a linear step hands d_state back zeroed: no memset per step
   uint32_t scan_event_tick = 0;                           // VC_FLAG_LEAN_TIMING: only every timing_sample-th verify launch is timed
   VcKnobs knobs;                                          // environment knobs, read once at vc_create
@@ -368,6 +372,8 @@ int vc_destroy(vc_engine* e) {
   (void)hipFree(e->d_chlab);
   (void)hipFree(e->d_lstate);
   (void)hipFree(e->d_lstat);
+  (void)hipFree(e->d_ddeg);
+  (void)hipFree(e->d_dstat);
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->last_call) (void)hipEventDestroy(e->last_call);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -1422,6 +1428,94 @@ int vc_leaders_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t bat
   if (rc) return rc;
   if (n_labelled < e->n)   // the incoming entries are read only: they do not travel back
     VC_HIP(e, hipMemcpyAsync(labels + n_labelled, e->d_chlab + n_labelled, (size_t)(e->n - n_labelled) * 4, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipStreamSynchronize(e->stream));
+  return VC_OK;
+}
+
+}  // extern "C"
+
+// ---- density clustering: DBSCAN over the radius graph ---------------------------------------------------------------------------------
+static int check_dbscan_args(vc_engine* e, uint32_t min_pts, uint32_t mode, const uint32_t* labels) {
+  if (!e || !labels) return VC_ERR_INVALID;
+  if (min_pts == 0) return fail(e, VC_ERR_INVALID, "dbscan: min_pts must be at least 1");
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "dbscan: mode must be LINEAR or MIH_EXACT");
+  if (e->n && mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
+  return VC_OK;
+}
+
+// The whole call on e->stream (inside the caller's StreamCall), e->n > 0.  cluster_run's loop over the batch buffers it shares with
+// that call (both fill them completely): per batch of ids, in ascending order, the ids filled on the device, the gather, the radius
+// search -- repeated once with the scratch grown to the total it reported -- then the batch's degrees and its edges over the raw
+// result as it lies.  d_degrees null: the handle's own.  After the last batch one finish pass, then the one wait for the stats.
+static int dbscan_run(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels, uint32_t* d_degrees,
+                      vc_dbscan_stats* stats) {
+  int rc;
+  const uint64_t N = e->n;
+  if (batch == 0) batch = VC_CLUSTER_BATCH;
+  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N);
+  if ((rc = grow(e, &e->d_dstat, &e->dstat_bytes, VC_DBSCAN_STAT_BYTES))) return rc;
+  if (!d_degrees) {
+    if ((rc = grow(e, &e->d_ddeg, &e->ddeg_bytes, (size_t)N * 4))) return rc;
+    d_degrees = e->d_ddeg;
+  }
+  if ((rc = grow(e, &e->d_cids, &e->cids_bytes, (size_t)nq_max * 4))) return rc;
+  if ((rc = grow(e, &e->d_cq, &e->cq_bytes, (size_t)nq_max * e->W * 8))) return rc;
+  if ((rc = grow(e, &e->d_cfound, &e->cfound_bytes, (size_t)nq_max * 4))) return rc;
+  if ((rc = grow(e, &e->d_croffs, &e->croffs_bytes, ((size_t)nq_max + 1) * 8))) return rc;
+  if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)8 << 16))) return rc;
+  VC_HIP(e, hipMemsetAsync(e->d_dstat, 0, VC_DBSCAN_STAT_BYTES, e->stream));
+  VC_HIP(e, vc_launch_cluster_init(d_labels, N, e->cfg.id_base, e->stream));
+  for (uint64_t pos = 0; pos < N; pos += batch) {
+    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = e->cfg.id_base + (uint32_t)pos;
+    VC_HIP(e, vc_launch_cluster_init(e->d_cids, nq, first_id, e->stream));
+    VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, e->d_cids, nq, e->d_cq, e->d_cfound, e->stream));
+    uint64_t raw_total = 0;
+    for (int attempt = 0;; ++attempt) {
+      const uint64_t cap = e->craw_bytes / 8;
+      rc = vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, e->d_cq, nq,
+                            radius, e->d_craw, cap, e->d_croffs, true, &e->radius_work, e->stream, &e->err, &raw_total);
+      if (rc == VC_OK) break;
+      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
+      if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)raw_total * 8))) return rc;   // (the first attempt has been waited for)
+    }
+    VC_HIP(e, vc_launch_dbscan_edges(e->d_craw, e->d_croffs, nq, raw_total, first_id, e->cfg.id_base, min_pts, d_degrees, d_labels, e->d_dstat, e->stream));
+  }
+  VC_HIP(e, vc_launch_dbscan_finish(d_labels, d_degrees, N, e->cfg.id_base, min_pts, e->d_dstat + 1, e->stream));
+  uint64_t st[5] = {0, 0, 0, 0, 0};
+  VC_HIP(e, hipMemcpyAsync(st, e->d_dstat, VC_DBSCAN_STAT_BYTES, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipStreamSynchronize(e->stream));
+  if (stats) *stats = vc_dbscan_stats{st[0], st[1], st[2], st[3], st[4]};
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_dbscan_radius_dev(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels, uint32_t* d_degrees,
+                         vc_dbscan_stats* stats, void* stream) {
+  int rc = check_dbscan_args(e, min_pts, mode, d_labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_dbscan_stats{0, 0, 0, 0, 0};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, caller_stream(e, stream));
+  return dbscan_run(e, radius, min_pts, mode, batch, d_labels, d_degrees, stats);
+}
+
+int vc_dbscan_radius(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees,
+                     vc_dbscan_stats* stats) {
+  int rc = check_dbscan_args(e, min_pts, mode, labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_dbscan_stats{0, 0, 0, 0, 0};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  if ((rc = grow(e, &e->d_chlab, &e->chlab_bytes, (size_t)e->n * 4))) return rc;
+  {
+    const StreamCall call(e, e->stream);
+    rc = dbscan_run(e, radius, min_pts, mode, batch, e->d_chlab, nullptr, stats);
+  }
+  if (rc) return rc;
+  VC_HIP(e, hipMemcpyAsync(labels, e->d_chlab, (size_t)e->n * 4, hipMemcpyDeviceToHost, e->stream));
+  if (degrees) VC_HIP(e, hipMemcpyAsync(degrees, e->d_ddeg, (size_t)e->n * 4, hipMemcpyDeviceToHost, e->stream));
   VC_HIP(e, hipStreamSynchronize(e->stream));
   return VC_OK;
 }

@@ -215,6 +215,19 @@ hipError_t vc_leaders_decide_batch(const uint64_t* d_raw, const uint64_t* d_roff
                                    uint32_t* d_state, uint64_t* d_stat, hipStream_t s, bool* stuck);
 // *d_n_leaders += the records i < n with d_labels[i] == id_base + i; nothing is waited for
 hipError_t vc_launch_leaders_count(const uint32_t* d_labels, uint64_t n, uint32_t id_base, uint64_t* d_n_leaders, hipStream_t s);
+// ---- vc_dbscan.hip: density clustering (vc_dbscan_radius*).  d_labels [n] starts as the own ids (vc_launch_cluster_init): a core's
+// slot is the forest of vc_forest.hpp over the cores, a non-core's slot its smallest core neighbour seen so far, its own id for
+// none; d_degrees [n] says which is which.  Nothing here waits.
+#define VC_DBSCAN_STAT_BYTES 40u   // d_stat: 5 x uint64 in the order of vc_dbscan_stats (pairs, clusters, cores, borders, noise)
+// One batch, two launches over the raw result (d_raw, its nq + 1 offsets d_roffs, total = d_roffs[nq]) of the queries first_id ..
+// first_id + nq - 1: d_degrees[first_id - id_base + q] = the length of segment q, then every entry (own, v < own) unites two cores
+// or lowers the non-core member's anchor to the core.  The degrees below first_id must be final.  *d_n_pairs += the entries v < own.
+hipError_t vc_launch_dbscan_edges(const uint64_t* d_raw, const uint64_t* d_roffs, uint32_t nq, uint64_t total, uint32_t first_id, uint32_t id_base,
+                                  uint32_t min_pts, uint32_t* d_degrees, uint32_t* d_labels, uint64_t* d_n_pairs, hipStream_t s);
+// after the last batch, in place: d_labels[i] = the root of a core, the root of a border's anchor, the own id of noise;
+// d_counts[0 .. 3] += the roots among the cores, the cores, the borders, the noise
+hipError_t vc_launch_dbscan_finish(uint32_t* d_labels, const uint32_t* d_degrees, uint64_t n, uint32_t id_base, uint32_t min_pts, uint64_t* d_counts,
+                                   hipStream_t s);
 // ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
 struct VcKeepSet;
 #define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)

@@ -134,6 +134,9 @@ enum RootBuf {
   // greedy leader dedup: it shares CL_IDS .. CL_ROFFS and CL_HLAB (both calls fill them completely); its own are a batch's state
   // words and the statistics with the round counters
   LD_STATE, LD_STAT,
+  // density clustering: it shares CL_IDS .. CL_ROFFS and CL_HLAB too; its own are the degrees of a call that passes none (and of the
+  // host form) and the five statistics
+  DB_DEG, DB_STAT,
   ROOT_BUFS
 };
 
@@ -2261,6 +2264,99 @@ int vc_sharded_leaders_radius(vc_sharded* h, uint32_t radius, uint32_t mode, uin
   VS_HIP(h, hipSetDevice(h->root));
   if (n_labelled < h->n)   // the incoming entries are read only: they do not travel back
     VS_HIP(h, hipMemcpyAsync(labels + n_labelled, h->buf[CL_HLAB].as<uint32_t>() + n_labelled, (size_t)(h->n - n_labelled) * 4, hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipStreamSynchronize(S));
+  return VC_OK;
+}
+
+}  // extern "C"
+
+// ---- density clustering over the shards -----------------------------------------------------------------------------------------------
+static int check_sharded_dbscan_args(vc_sharded* h, uint32_t min_pts, uint32_t mode, const uint32_t* labels) {
+  if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
+  if (min_pts == 0) return sfail(h, VC_ERR_INVALID, "dbscan: min_pts must be at least 1");
+  if (mode == VC_MODE_MIH_EXACT)
+    for (uint32_t g = 0; g < h->G; ++g)
+      if (shard_size(h, g) && !vc_engine_has_index(h->eng[g])) return sfail(h, VC_ERR_STATE, "shard %u: MIH search needs vc_sharded_build_index() first", g);
+  return VC_OK;
+}
+
+// All on the root device's stream S, h->n > 0.  sharded_cluster_run's loop over the batch buffers it shares with that call: per batch
+// of global ids, ascending, the ids filled on the root, the gather over the shards, the union's radius search -- repeated once with
+// the scratch grown to the total it reported -- then the batch's degrees and its edges over the raw result on the root.  d_degrees
+// null: the handle's own.  After the last batch one finish pass, then the one wait for the stats.
+static int sharded_dbscan_run(vc_sharded* h, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels, uint32_t* d_degrees,
+                              vc_dbscan_stats* stats, hipStream_t S) {
+  int rc;
+  const uint32_t id_base = h->cfg.engine.id_base;
+  const uint64_t N = h->n;
+  if (batch == 0) batch = VC_CLUSTER_BATCH;
+  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N);
+  VS_HIP(h, hipSetDevice(h->root));
+  if ((rc = h->buf[DB_STAT].grow(h, VC_DBSCAN_STAT_BYTES))) return rc;
+  if (!d_degrees) {
+    if ((rc = h->buf[DB_DEG].grow(h, (size_t)N * 4))) return rc;
+    d_degrees = h->buf[DB_DEG].as<uint32_t>();
+  }
+  if ((rc = h->buf[CL_IDS].grow(h, (size_t)nq_max * 4))) return rc;
+  if ((rc = h->buf[CL_Q].grow(h, (size_t)nq_max * h->nbytes))) return rc;
+  if ((rc = h->buf[CL_FOUND].grow(h, (size_t)nq_max * 4))) return rc;
+  if ((rc = h->buf[CL_ROFFS].grow(h, ((size_t)nq_max + 1) * 8))) return rc;
+  if ((rc = h->buf[CL_RAW].grow(h, (size_t)8 << 16))) return rc;
+  uint64_t* d_stat = h->buf[DB_STAT].as<uint64_t>();
+  uint32_t* d_ids = h->buf[CL_IDS].as<uint32_t>();
+  VS_HIP(h, hipMemsetAsync(d_stat, 0, VC_DBSCAN_STAT_BYTES, S));
+  VS_HIP(h, vc_launch_cluster_init(d_labels, N, id_base, S));
+  for (uint64_t pos = 0; pos < N; pos += batch) {
+    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = id_base + (uint32_t)pos;
+    VS_HIP(h, hipSetDevice(h->root));
+    VS_HIP(h, vc_launch_cluster_init(d_ids, nq, first_id, S));
+    if ((rc = sharded_gather_ids(h, d_ids, nq, h->buf[CL_Q].as<uint64_t>(), h->buf[CL_FOUND].as<uint32_t>(), true, S))) return rc;
+    uint64_t raw_total = 0;
+    for (int attempt = 0;; ++attempt) {
+      const uint64_t cap = h->buf[CL_RAW].bytes / 8;
+      rc = sharded_radius_dev(h, h->buf[CL_Q].p, nq, radius, mode, h->buf[CL_RAW].as<uint64_t>(), cap, h->buf[CL_ROFFS].as<uint64_t>(), S, &raw_total);
+      if (rc == VC_OK) break;
+      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
+      VS_HIP(h, hipSetDevice(h->root));
+      if ((rc = h->buf[CL_RAW].grow(h, (size_t)raw_total * 8))) return rc;
+    }
+    VS_HIP(h, hipSetDevice(h->root));
+    VS_HIP(h, vc_launch_dbscan_edges(h->buf[CL_RAW].as<uint64_t>(), h->buf[CL_ROFFS].as<uint64_t>(), nq, raw_total, first_id, id_base, min_pts, d_degrees,
+                                     d_labels, d_stat, S));
+  }
+  VS_HIP(h, hipSetDevice(h->root));
+  VS_HIP(h, vc_launch_dbscan_finish(d_labels, d_degrees, N, id_base, min_pts, d_stat + 1, S));
+  uint64_t st[5] = {0, 0, 0, 0, 0};
+  VS_HIP(h, hipMemcpyAsync(st, d_stat, VC_DBSCAN_STAT_BYTES, hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipStreamSynchronize(S));
+  if (stats) *stats = vc_dbscan_stats{st[0], st[1], st[2], st[3], st[4]};
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_sharded_dbscan_radius_dev(vc_sharded* h, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels,
+                                 uint32_t* d_degrees, vc_dbscan_stats* stats, void* stream) {
+  int rc = check_sharded_dbscan_args(h, min_pts, mode, d_labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_dbscan_stats{0, 0, 0, 0, 0};
+  if (h->n == 0) return VC_OK;
+  return sharded_dbscan_run(h, radius, min_pts, mode, batch, d_labels, d_degrees, stats, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+}
+
+int vc_sharded_dbscan_radius(vc_sharded* h, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees,
+                             vc_dbscan_stats* stats) {
+  int rc = check_sharded_dbscan_args(h, min_pts, mode, labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_dbscan_stats{0, 0, 0, 0, 0};
+  if (h->n == 0) return VC_OK;
+  hipStream_t S = h->root_stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  if ((rc = h->buf[CL_HLAB].grow(h, (size_t)h->n * 4))) return rc;
+  if ((rc = sharded_dbscan_run(h, radius, min_pts, mode, batch, h->buf[CL_HLAB].as<uint32_t>(), nullptr, stats, S))) return rc;
+  VS_HIP(h, hipSetDevice(h->root));
+  VS_HIP(h, hipMemcpyAsync(labels, h->buf[CL_HLAB].p, (size_t)h->n * 4, hipMemcpyDeviceToHost, S));
+  if (degrees) VS_HIP(h, hipMemcpyAsync(degrees, h->buf[DB_DEG].p, (size_t)h->n * 4, hipMemcpyDeviceToHost, S));
   VS_HIP(h, hipStreamSynchronize(S));
   return VC_OK;
 }

@@ -45,6 +45,7 @@ EXPORTS = [
     "vc_cluster_radius", "vc_cluster_radius_dev", "vc_sharded_cluster_radius", "vc_sharded_cluster_radius_dev",
     "vc_retain", "vc_retain_dev", "vc_sharded_retain", "vc_sharded_retain_dev",
     "vc_leaders_radius", "vc_leaders_radius_dev", "vc_sharded_leaders_radius", "vc_sharded_leaders_radius_dev",
+    "vc_dbscan_radius", "vc_dbscan_radius_dev", "vc_sharded_dbscan_radius", "vc_sharded_dbscan_radius_dev",
 ]
 MAX_SHARDS = 16
 EXCHANGE_AUTO, EXCHANGE_PEER_COPY, EXCHANGE_RCCL = 0, 1, 2
@@ -78,6 +79,13 @@ class VcClusterStats(C.Structure):
 
 class VcLeaderStats(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("n_leaders", C.c_uint64), ("n_rounds", C.c_uint64)]
+
+
+class VcDbscanStats(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("n_clusters", C.c_uint64), ("n_core", C.c_uint64), ("n_border", C.c_uint64), ("n_noise", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 class VcTiming(C.Structure):
@@ -186,6 +194,10 @@ def load_library():
     L.vc_leaders_radius_dev.argtypes = [vp, u32, u32, u32, u64, vp, vp, vp]
     L.vc_sharded_leaders_radius.argtypes = [vp, u32, u32, u32, u64, vp, vp]
     L.vc_sharded_leaders_radius_dev.argtypes = [vp, u32, u32, u32, u64, vp, vp, vp]
+    L.vc_dbscan_radius.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp]
+    L.vc_dbscan_radius_dev.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp]
+    L.vc_sharded_dbscan_radius.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp]
+    L.vc_sharded_dbscan_radius_dev.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -268,6 +280,21 @@ def _leaders_radius_dev(self, fn, radius, d_labels, mode, batch, n_labelled, str
     st = VcLeaderStats()
     self._check(fn(self._h, radius, mode, batch, n_labelled, d_labels, C.byref(st), stream))
     return int(st.n_pairs), int(st.n_leaders), int(st.n_rounds)
+
+
+def _dbscan_radius(self, fn, radius, min_pts, mode, batch):
+    """shared by Engine.dbscan_radius and ShardedEngine.dbscan_radius: (labels [N] uint32, degrees [N] uint32, stats dict)"""
+    n = len(self)
+    labels, degrees = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+    st = VcDbscanStats()
+    self._check(fn(self._h, radius, min_pts, mode, batch, _p(labels), _p(degrees), C.byref(st)))
+    return labels, degrees, st.as_dict()
+
+
+def _dbscan_radius_dev(self, fn, radius, min_pts, d_labels, d_degrees, mode, batch, stream):
+    st = VcDbscanStats()
+    self._check(fn(self._h, radius, min_pts, mode, batch, d_labels, d_degrees, C.byref(st), stream))
+    return st.as_dict()
 
 
 def _retain(self, fn, sel, kind, with_map):
@@ -536,6 +563,20 @@ class Engine:
         only read); labels valid in `stream` order.  Returns (n_pairs, n_leaders, n_rounds)."""
         return _leaders_radius_dev(self, self._L.vc_leaders_radius_dev, radius, d_labels, mode, batch, n_labelled, stream)
 
+    def dbscan_radius(self, radius, min_pts, mode=MODE_LINEAR, batch=0):
+        """vc_dbscan_radius: DBSCAN over all resident records.  Returns (labels, degrees, stats): degrees[i] = the records within
+        `radius` of record i, itself included; a record is a CORE iff degrees[i] >= min_pts; labels[i] = the smallest global id among
+        the cores of a core's component, the label of its smallest-id core neighbour for a BORDER (a non-core record with a core
+        within `radius`), the record's own global id for NOISE.  A record labelled with itself is noise iff degrees[i] < min_pts, a
+        cluster's representative otherwise.  stats: dict of n_pairs, n_clusters, n_core, n_border, n_noise.  There is no incremental
+        form.  retain(labels, RETAIN_ROOTS) keeps one representative per cluster and every noise record."""
+        return _dbscan_radius(self, self._L.vc_dbscan_radius, radius, min_pts, mode, batch)
+
+    def dbscan_radius_dev(self, radius, min_pts, d_labels, d_degrees=None, mode=MODE_MIH_EXACT, batch=0, stream=None):
+        """vc_dbscan_radius_dev: d_labels / d_degrees = the raw device addresses of len(self) uint32 each (d_degrees None: scratch of
+        the handle); both valid in `stream` order.  Returns the stats dict."""
+        return _dbscan_radius_dev(self, self._L.vc_dbscan_radius_dev, radius, min_pts, d_labels, d_degrees, mode, batch, stream)
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -738,6 +779,20 @@ class ShardedEngine:
         """vc_sharded_leaders_radius_dev: d_labels = the raw device address of len(self) uint32 on the root device (its first n_labelled entries come in and are
         only read); labels valid in `stream` order.  Returns (n_pairs, n_leaders, n_rounds)."""
         return _leaders_radius_dev(self, self._L.vc_sharded_leaders_radius_dev, radius, d_labels, mode, batch, n_labelled, stream)
+
+    def dbscan_radius(self, radius, min_pts, mode=MODE_LINEAR, batch=0):
+        """vc_sharded_dbscan_radius: DBSCAN over all resident records.  Returns (labels, degrees, stats): degrees[i] = the records within
+        `radius` of record i, itself included; a record is a CORE iff degrees[i] >= min_pts; labels[i] = the smallest global id among
+        the cores of a core's component, the label of its smallest-id core neighbour for a BORDER (a non-core record with a core
+        within `radius`), the record's own global id for NOISE.  A record labelled with itself is noise iff degrees[i] < min_pts, a
+        cluster's representative otherwise.  stats: dict of n_pairs, n_clusters, n_core, n_border, n_noise.  There is no incremental
+        form.  retain(labels, RETAIN_ROOTS) keeps one representative per cluster and every noise record."""
+        return _dbscan_radius(self, self._L.vc_sharded_dbscan_radius, radius, min_pts, mode, batch)
+
+    def dbscan_radius_dev(self, radius, min_pts, d_labels, d_degrees=None, mode=MODE_MIH_EXACT, batch=0, stream=None):
+        """vc_sharded_dbscan_radius_dev: d_labels / d_degrees = the raw device addresses of len(self) uint32 each on the root device (d_degrees None: scratch of
+        the handle); both valid in `stream` order.  Returns the stats dict."""
+        return _dbscan_radius_dev(self, self._L.vc_sharded_dbscan_radius_dev, radius, min_pts, d_labels, d_degrees, mode, batch, stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

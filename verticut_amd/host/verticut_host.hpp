@@ -125,6 +125,10 @@ class Backend {
   // within `radius` (vc_leaders_radius / vc_sharded_leaders_radius; labels[0 .. n_labelled) come in, read only); retain() with
   // VC_RETAIN_ROOTS keeps exactly the leaders
   virtual int leaders_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats) = 0;
+  // density clustering: degrees[i] (may be null) = records within `radius` of record i, itself included; a CORE has at least min_pts;
+  // labels[i] = the smallest core id of a core's component, the label of a border's smallest-id core neighbour, the own id for noise
+  // (vc_dbscan_radius / vc_sharded_dbscan_radius); retain() with VC_RETAIN_ROOTS keeps one record per cluster and the noise
+  virtual int dbscan_radius(uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats) = 0;
   // records taken out of the store and its index, the survivors renumbered in order (vc_retain / vc_sharded_retain; the reference has
   // no delete: this stands for build_hash_tables.cc run again over the code file without them).  kind VC_RETAIN_MASK / VC_RETAIN_ROOTS
   virtual int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) = 0;
@@ -184,6 +188,9 @@ class Engine : public Backend {
   }
   int leaders_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats) override {
     return vc_leaders_radius(h_, radius, mode, batch, n_labelled, labels, stats);
+  }
+  int dbscan_radius(uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats) override {
+    return vc_dbscan_radius(h_, radius, min_pts, mode, batch, labels, degrees, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_retain(h_, sel, kind, new_ids, n_kept); }
  private:
@@ -271,6 +278,9 @@ class ShardedEngine : public Backend {
   }
   int leaders_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats) override {
     return vc_sharded_leaders_radius(h_, radius, mode, batch, n_labelled, labels, stats);
+  }
+  int dbscan_radius(uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats) override {
+    return vc_sharded_dbscan_radius(h_, radius, min_pts, mode, batch, labels, degrees, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_sharded_retain(h_, sel, kind, new_ids, n_kept); }
  private:
