@@ -476,6 +476,60 @@ int vc_dbscan_radius_dev(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32
 int vc_dbscan_radius(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees,
                      vc_dbscan_stats* stats);
 
+/* "What is in each group": the step after vc_cluster_radius*, vc_leaders_radius* or vc_dbscan_radius*, which all stop at a labels
+ * array.  Per group of equal labels: its size, its typical code and the member to keep.  The reference has nothing of the kind; the
+ * call replaces the copy home of N codes and N labels, a host sort and a per-bit vote.
+ * INPUT: labels, N = vc_size entries, every value in the resident id range [id_base, id_base + N).  Two records are in one group iff
+ * their labels are equal.  Nothing else is assumed -- labels[l - id_base] == l need not hold, a label need not be a member of its own
+ * group: the output of any of the three clustering calls qualifies, and so does any hand-made partition.
+ * OUTPUT, with G the number of distinct labels and the groups numbered 0 .. G - 1 by ASCENDING label:
+ *   groups[g]       the vc_group below.
+ *   centroids       G rows of bits / 8 bytes in the byte layout of vc_add_codes / vc_get_code (8-byte aligned): bit b of row g is 1 iff
+ *                   STRICTLY more than half of the members have bit b set -- a tie in an even-sized group gives 0.  This per-bit
+ *                   majority code minimises the sum of Hamming distances to the members, exactly, in integers.
+ *   rep             the member with the smallest (distance to the centroid, global id): a tie in distance goes to the smaller id.
+ *   rep_labels[i]   the rep of record i's group, N entries.  By construction rep_labels[rep - id_base] == rep, so
+ *                   vc_retain*(rep_labels, VC_RETAIN_ROOTS) keeps exactly the representatives; vc_retain* is unchanged.
+ *   group_index[i]  g, the dense number of record i's group, N entries.
+ * centroids, rep_labels and group_index may each be NULL; groups may be NULL only if groups_cap == 0.
+ * CAPACITY, the protocol of the radius calls: *n_groups (may be NULL) = G always.  G > groups_cap returns VC_ERR_CAPACITY and NONE of
+ * the four outputs is written (rep_labels and group_index do not depend on the cap, but they are not written either: the call ends
+ * at its read-back).  G <= N, so groups_cap = N never fails.
+ * ERRORS: VC_ERR_INVALID for a null handle, null labels with N > 0, null groups with groups_cap > 0 -- checked before any work; and
+ * for a label outside the range, which is detected ON THE DEVICE by a flag word that comes home together with G: keys are clamped
+ * before anything is addressed by them, so no address is ever formed from such a label; the outputs are untouched (*n_groups = 0).
+ * N == 0 gives VC_OK and G = 0; nothing is read or written.  VC_ERR_NOMEM leaves the outputs untouched: the buffers are grown
+ * before the first output word is written.
+ * The result is a function of the codes and `labels` only: no order of lanes, no earlier call on the handle, no VC_GROUP_WINDOW and
+ * no shard layout changes a bit of it.
+ * How: the (label - id_base, id) pairs go through the index builder's stable radix sort, so a group's members lie contiguous in
+ * ascending id order; head flags and three prefix sums number the groups, the work items and the big groups.  The codes of the sorted
+ * ids are fetched by vc_get_codes_dev in windows of VC_GROUP_WINDOW positions (environment, read at vc_create; default 2^20, a multiple
+ * of 1024) plus 1024 of overlap.  Groups of 1 .. 2 take one thread, of 3 .. 1024 one wave, larger ones one wave per 1024 members whose
+ * vote counts, smallest (distance, id) and largest distance meet in integer atomics; only then a second walk of the windows happens.
+ * Device form: everything is enqueued on `stream`; the host waits exactly ONCE, for 16 bytes -- G, the error flag and two counts that
+ * size the launches behind it -- and one word per window.  d_labels must not be touched during the call; it may not overlap an output.
+ * Outputs are valid in stream order.  The call is ordered behind the handle's previous call whatever its stream, like every call.
+ * Scratch: three grow-only buffers of the handle, this call's own (no other call uses them), every word written before it is read
+ * within a call: 24 N bytes and the sort's histograms; the row buffer (min(N, VC_GROUP_WINDOW + 1024) codes) with 4 * bits + bits / 8
+ * + 16 bytes per group above 1024 members; the host form's staged labels and outputs.  Nothing is allocated or released by a call
+ * that needs no more than an earlier one did; a call that needs more re-allocates the buffer, which waits for the device once.
+ * A record count above 2^32 - 3 returns VC_ERR_INVALID (the prefix sums are 32-bit). */
+typedef struct vc_group {       /* 24 bytes */
+  uint32_t label;     /* the value shared by the members' labels[] entries */
+  uint32_t size;      /* members */
+  uint32_t rep;       /* GLOBAL id of the representative (a member) */
+  uint32_t rep_dist;  /* Hamming distance representative -> centroid */
+  uint32_t max_dist;  /* largest distance of a member to the centroid */
+  uint32_t reserved;  /* 0 */
+} vc_group;
+int vc_group_summary_dev(vc_engine* e, const uint32_t* d_labels, uint64_t groups_cap, vc_group* d_groups, void* d_centroids,
+                         uint32_t* d_rep_labels, uint32_t* d_group_index, uint64_t* n_groups, void* stream);
+/* The same for labels and outputs in host memory: the device form on the engine's stream into staged buffers, of which the first G
+ * groups and centroid rows and the two N-entry arrays come home; waits for them. */
+int vc_group_summary(vc_engine* e, const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels,
+                     uint32_t* group_index, uint64_t* n_groups);
+
 /* "Take these records out": the store and its index cut down to the surviving records, in place.  The reference has no delete
  * (its store has put and get only, base_proxy.h:18-22, and its index is one pass of build_hash_tables.cc over a code file); the call
  * stands for running build_hash_tables.cc:40-70 again over the code file without the removed records, and replaces the copy home of
@@ -675,6 +729,19 @@ int vc_sharded_dbscan_radius_dev(vc_sharded* h, uint32_t radius, uint32_t min_pt
                                  uint32_t* d_degrees, vc_dbscan_stats* stats, void* stream);
 int vc_sharded_dbscan_radius(vc_sharded* h, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels,
                              uint32_t* degrees, vc_dbscan_stats* stats);
+/* Label groups summarised over all shards: contract, capacity protocol, errors and scratch as vc_group_summary_dev / vc_group_summary,
+ * with N = vc_sharded_size, ids global over the whole store and every pointer of the device form on the ROOT device, `stream` a stream
+ * of that device.  The same kernels run on the root; only the rows of a window come through vc_sharded_get_codes_dev instead.
+ * Scratch on top of vc_group_summary's (which lies on the root): that gather's own buffers, grow-only on the handle like those of
+ * every by-id call -- per device n_shards slots of (VC_GROUP_WINDOW + 1024) x (bits / 8 + 4) bytes, so a small VC_GROUP_WINDOW is
+ * the way to bound them with many shards and wide codes (16 shards x 512 bits at the default window: 1.1 GB).  As with every
+ * vc_sharded_* call, two calls on one handle must not be in flight on different streams at once.  A group
+ * may have its members in any shards: the result equals BIT FOR BIT that of one engine holding the same codes.
+ * vc_sharded_retain*(rep_labels, VC_RETAIN_ROOTS) keeps exactly the representatives. */
+int vc_sharded_group_summary_dev(vc_sharded* h, const uint32_t* d_labels, uint64_t groups_cap, vc_group* d_groups, void* d_centroids,
+                                 uint32_t* d_rep_labels, uint32_t* d_group_index, uint64_t* n_groups, void* stream);
+int vc_sharded_group_summary(vc_sharded* h, const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels,
+                             uint32_t* group_index, uint64_t* n_groups);
 /* borrow shard g's engine (bucket views, timing, files); its id range is [*first_id, *first_id + *n_ids) */
 int vc_sharded_shard(vc_sharded* h, uint32_t shard, vc_engine** e, uint64_t* first_id, uint64_t* n_ids);
 

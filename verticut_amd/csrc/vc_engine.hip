@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <functional>
 
+#include "vc_groups_plan.hpp"
 #include "vc_internal.hpp"
 #include "vc_mih.hpp"
 #include "vc_retain.hpp"
@@ -76,6 +77,9 @@ struct vc_engine {
   // own are the degrees of a call that passes none (and of the host form) and the five statistics
   uint32_t* d_ddeg = nullptr;   size_t ddeg_bytes = 0;
   uint64_t* d_dstat = nullptr;  size_t dstat_bytes = 0;
+  // label groups summarised (vc_group_summary*): the sort and numbering arrays, the row buffer with the big groups' tables, the host
+  // form's staging (VC_GROUPS_*); its own, shared with no other call, every word written before it is read
+  uint8_t* d_grp[VC_GROUPS_BUFS] = {nullptr, nullptr, nullptr};  size_t grp_bytes[VC_GROUPS_BUFS] = {0, 0, 0};
   CleanState clean;                                       // the last kernel of a linear step hands d_state back zeroed: no memset per step
   uint32_t scan_event_tick = 0;                           // VC_FLAG_LEAN_TIMING: only every timing_sample-th verify launch is timed
   VcKnobs knobs;                                          // environment knobs, read once at vc_create
@@ -182,6 +186,10 @@ void read_knobs(VcKnobs* k) {
   k->gs_trace = getenv("VC_MIH_GS_TRACE") != nullptr;
   if (const char* v = getenv("VC_MIH_UPDATE")) k->mih_update = atoi(v);
   if (const char* v = getenv("VC_MIH_RETAIN")) k->mih_retain = atoi(v);
+  if (const char* v = getenv("VC_GROUP_WINDOW")) {
+    const uint64_t w = strtoull(v, nullptr, 10);
+    if (vc_group_window_valid(w)) k->group_window = (uint32_t)w;
+  }
 }
 
 static int bind_device(vc_engine* e) {
@@ -374,6 +382,7 @@ int vc_destroy(vc_engine* e) {
   (void)hipFree(e->d_lstat);
   (void)hipFree(e->d_ddeg);
   (void)hipFree(e->d_dstat);
+  for (uint8_t* b : e->d_grp) (void)hipFree(b);
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->last_call) (void)hipEventDestroy(e->last_call);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -1518,6 +1527,48 @@ int vc_dbscan_radius(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32_t m
   if (degrees) VC_HIP(e, hipMemcpyAsync(degrees, e->d_ddeg, (size_t)e->n * 4, hipMemcpyDeviceToHost, e->stream));
   VC_HIP(e, hipStreamSynchronize(e->stream));
   return VC_OK;
+}
+
+}  // extern "C"
+
+// ---- label groups summarised (vc_groups.hip) ------------------------------------------------------------------------------------
+static VcGroupsArgs groups_args(vc_engine* e, const uint32_t* d_labels, uint64_t groups_cap, vc_group* d_groups, void* d_centroids, uint32_t* d_rep_labels,
+                                uint32_t* d_group_index) {
+  return VcGroupsArgs{e->n, e->cfg.id_base, e->W, e->knobs.group_window, d_labels, groups_cap, d_groups, (uint64_t*)d_centroids, d_rep_labels, d_group_index,
+                      [e](int which, size_t bytes) -> void* { return grow(e, &e->d_grp[which], &e->grp_bytes[which], bytes) ? nullptr : e->d_grp[which]; }};
+}
+
+extern "C" {
+
+int vc_group_summary_dev(vc_engine* e, const uint32_t* d_labels, uint64_t groups_cap, vc_group* d_groups, void* d_centroids, uint32_t* d_rep_labels,
+                         uint32_t* d_group_index, uint64_t* n_groups, void* stream) {
+  if (!e || (!d_labels && e->n) || (!d_groups && groups_cap)) return VC_ERR_INVALID;
+  if (n_groups) *n_groups = 0;
+  if (e->n == 0) return VC_OK;
+  int rc = bind_device(e);
+  if (rc) return rc;
+  const StreamCall call(e, caller_stream(e, stream));   // (orders the call behind the handle's previous one, whose buffers it may share)
+  hipStream_t s = e->stream;
+  const VcGroupsFetch fetch = [e, s](const uint32_t* d_ids, uint32_t nq, uint64_t* d_rows) { return vc_get_codes_dev(e, d_ids, nq, d_rows, nullptr, (void*)s); };
+  std::string err;
+  rc = vc_groups_run(groups_args(e, d_labels, groups_cap, d_groups, d_centroids, d_rep_labels, d_group_index), fetch, n_groups, s, &err);
+  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;   // (an allocation failure has left its own text)
+}
+
+int vc_group_summary(vc_engine* e, const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels,
+                     uint32_t* group_index, uint64_t* n_groups) {
+  if (!e || (!labels && e->n) || (!groups && groups_cap)) return VC_ERR_INVALID;
+  if (n_groups) *n_groups = 0;
+  if (e->n == 0) return VC_OK;
+  int rc = bind_device(e);
+  if (rc) return rc;
+  const StreamCall call(e, e->stream);
+  hipStream_t s = e->stream;
+  const VcGroupsFetch fetch = [e, s](const uint32_t* d_ids, uint32_t nq, uint64_t* d_rows) { return vc_get_codes_dev(e, d_ids, nq, d_rows, nullptr, (void*)s); };
+  std::string err;
+  rc = vc_groups_run_host(groups_args(e, nullptr, groups_cap, nullptr, nullptr, nullptr, nullptr), fetch, labels, groups, centroids, rep_labels, group_index,
+                          n_groups, s, &err);
+  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;   // (an allocation failure has left its own text)
 }
 
 }  // extern "C"

@@ -1,5 +1,7 @@
 // Host-side launcher declarations shared by the translation units of libverticut_gpu.so.
 #pragma once
+#include <functional>
+
 #include "vc_common.hpp"
 
 // Developer / test knobs from the environment, read ONCE per engine at vc_create (never on a launch path).
@@ -41,6 +43,7 @@ struct VcKnobs {
   bool gs_trace = false;                      // VC_MIH_GS_TRACE (dev): per-round wall times of the sharded global stop on stderr
   int mih_update = 1;                         // VC_MIH_UPDATE=0: vc_update_index rebuilds the whole index (A/B runs, tests) instead of merging
   int mih_retain = 1;                         // VC_MIH_RETAIN=0: vc_retain* compacts the columns and rebuilds the whole index (A/B runs, tests) instead of filtering it
+  uint32_t group_window = 1u << 20;           // VC_GROUP_WINDOW: sorted positions per gather of vc_group_summary* (a multiple of 1024, else ignored)
   bool scan_shape_trace = false;              // VC_SCAN_SHAPE_TRACE=1 (dev/tests): every verify launch names the instantiation it launched on stderr
 };
 void read_knobs(VcKnobs* k);   // vc_engine.hip: the one place that reads the environment (once per engine / sharded handle)
@@ -228,6 +231,29 @@ hipError_t vc_launch_dbscan_edges(const uint64_t* d_raw, const uint64_t* d_roffs
 // d_counts[0 .. 3] += the roots among the cores, the cores, the borders, the noise
 hipError_t vc_launch_dbscan_finish(uint32_t* d_labels, const uint32_t* d_degrees, uint64_t n, uint32_t id_base, uint32_t min_pts, uint64_t* d_counts,
                                    hipStream_t s);
+// ---- vc_groups.hip: label groups summarised (vc_group_summary*, vc_sharded_group_summary*).  One driver for both handle kinds: the
+// codes of a window's sorted ids come through `fetch` (vc_get_codes_dev / the sharded gather, enqueued on s, nothing waited for)
+// as contiguous rows [nq][W].  The plan arithmetic is vc_groups_plan.hpp.
+struct VcGroupsArgs {
+  uint64_t n;               // resident records
+  uint32_t id_base, W, window;   // window: VcKnobs::group_window
+  const uint32_t* d_labels;
+  uint64_t groups_cap;
+  vc_group* d_groups;
+  uint64_t* d_centroids;    // nullable, as d_rep_labels and d_group_index
+  uint32_t* d_rep_labels;
+  uint32_t* d_group_index;
+  // the handle's grow-only buffer number `which`, at least `bytes` large, on the current device; null when it cannot be had (the
+  // handle keeps the error text).  The driver writes every word it reads, so what an earlier call left there never matters.
+  std::function<void*(int which, size_t bytes)> alloc;
+};
+enum { VC_GROUPS_SCRATCH, VC_GROUPS_WORK, VC_GROUPS_STAGE, VC_GROUPS_BUFS };   // sort / numbering arrays; rows + big-group tables; the host form's staging
+typedef std::function<int(const uint32_t* d_ids, uint32_t nq, uint64_t* d_rows)> VcGroupsFetch;
+// the whole call on s with the device of the buffers current: one wait (error flag, G, items, big groups), scratch from a.alloc
+int vc_groups_run(const VcGroupsArgs& a, const VcGroupsFetch& fetch, uint64_t* n_groups, hipStream_t s, std::string* err);
+// the same for host pointers: labels staged, the outputs that are wanted staged and copied home, waited for (a's pointers are ignored)
+int vc_groups_run_host(VcGroupsArgs a, const VcGroupsFetch& fetch, const uint32_t* labels, vc_group* groups, void* centroids, uint32_t* rep_labels,
+                       uint32_t* group_index, uint64_t* n_groups, hipStream_t s, std::string* err);
 // ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
 struct VcKeepSet;
 #define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)

@@ -137,6 +137,9 @@ enum RootBuf {
   // density clustering: it shares CL_IDS .. CL_ROFFS and CL_HLAB too; its own are the degrees of a call that passes none (and of the
   // host form) and the five statistics
   DB_DEG, DB_STAT,
+  // label groups summarised: the sort and numbering arrays, the row buffer with the big groups' tables, the host form's staging
+  // (GRP_SCRATCH + VC_GROUPS_*); its own, every word written before it is read
+  GRP_SCRATCH, GRP_WORK, GRP_STAGE,
   ROOT_BUFS
 };
 
@@ -2359,6 +2362,49 @@ int vc_sharded_dbscan_radius(vc_sharded* h, uint32_t radius, uint32_t min_pts, u
   if (degrees) VS_HIP(h, hipMemcpyAsync(degrees, h->buf[DB_DEG].p, (size_t)h->n * 4, hipMemcpyDeviceToHost, S));
   VS_HIP(h, hipStreamSynchronize(S));
   return VC_OK;
+}
+
+}  // extern "C"
+
+// ---- label groups summarised over the shards: the driver of vc_groups.hip on the root, its rows through the sharded gather ------------
+static VcGroupsFetch sharded_groups_fetch(vc_sharded* h, hipStream_t S) {
+  return [h, S](const uint32_t* d_ids, uint32_t nq, uint64_t* d_rows) { return vc_sharded_get_codes_dev(h, d_ids, nq, d_rows, nullptr, (void*)S); };
+}
+static VcGroupsArgs sharded_groups_args(vc_sharded* h, const uint32_t* d_labels, uint64_t groups_cap, vc_group* d_groups, void* d_centroids,
+                                        uint32_t* d_rep_labels, uint32_t* d_group_index) {
+  return VcGroupsArgs{h->n, h->cfg.engine.id_base, h->nbytes / 8, h->knobs.group_window, d_labels, groups_cap, d_groups, (uint64_t*)d_centroids, d_rep_labels,
+                      d_group_index, [h](int which, size_t bytes) -> void* {   // (the root device is current wherever the driver allocates)
+                        DevBuf& b = h->buf[GRP_SCRATCH + which];
+                        return b.grow(h, bytes) ? nullptr : b.p;
+                      }};
+}
+
+extern "C" {
+
+int vc_sharded_group_summary_dev(vc_sharded* h, const uint32_t* d_labels, uint64_t groups_cap, vc_group* d_groups, void* d_centroids,
+                                 uint32_t* d_rep_labels, uint32_t* d_group_index, uint64_t* n_groups, void* stream) {
+  if (!h || (!d_labels && h->n) || (!d_groups && groups_cap)) return VC_ERR_INVALID;
+  if (n_groups) *n_groups = 0;
+  if (h->n == 0) return VC_OK;
+  hipStream_t S = stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  std::string err;
+  const int rc = vc_groups_run(sharded_groups_args(h, d_labels, groups_cap, d_groups, d_centroids, d_rep_labels, d_group_index), sharded_groups_fetch(h, S),
+                               n_groups, S, &err);
+  return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
+}
+
+int vc_sharded_group_summary(vc_sharded* h, const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels,
+                             uint32_t* group_index, uint64_t* n_groups) {
+  if (!h || (!labels && h->n) || (!groups && groups_cap)) return VC_ERR_INVALID;
+  if (n_groups) *n_groups = 0;
+  if (h->n == 0) return VC_OK;
+  hipStream_t S = h->root_stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  std::string err;
+  const int rc = vc_groups_run_host(sharded_groups_args(h, nullptr, groups_cap, nullptr, nullptr, nullptr, nullptr), sharded_groups_fetch(h, S), labels, groups,
+                                    centroids, rep_labels, group_index, n_groups, S, &err);
+  return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
 }
 
 }  // extern "C"

@@ -46,6 +46,7 @@ EXPORTS = [
     "vc_retain", "vc_retain_dev", "vc_sharded_retain", "vc_sharded_retain_dev",
     "vc_leaders_radius", "vc_leaders_radius_dev", "vc_sharded_leaders_radius", "vc_sharded_leaders_radius_dev",
     "vc_dbscan_radius", "vc_dbscan_radius_dev", "vc_sharded_dbscan_radius", "vc_sharded_dbscan_radius_dev",
+    "vc_group_summary", "vc_group_summary_dev", "vc_sharded_group_summary", "vc_sharded_group_summary_dev",
 ]
 MAX_SHARDS = 16
 EXCHANGE_AUTO, EXCHANGE_PEER_COPY, EXCHANGE_RCCL = 0, 1, 2
@@ -198,6 +199,10 @@ def load_library():
     L.vc_dbscan_radius_dev.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp]
     L.vc_sharded_dbscan_radius.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp]
     L.vc_sharded_dbscan_radius_dev.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp]
+    L.vc_group_summary.argtypes = [vp, vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
+    L.vc_group_summary_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp, C.POINTER(u64), vp]
+    L.vc_sharded_group_summary.argtypes = [vp, vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
+    L.vc_sharded_group_summary_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp, C.POINTER(u64), vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -295,6 +300,33 @@ def _dbscan_radius_dev(self, fn, radius, min_pts, d_labels, d_degrees, mode, bat
     st = VcDbscanStats()
     self._check(fn(self._h, radius, min_pts, mode, batch, d_labels, d_degrees, C.byref(st), stream))
     return st.as_dict()
+
+
+# vc_group, field for field
+GROUP_DTYPE = np.dtype([("label", "<u4"), ("size", "<u4"), ("rep", "<u4"), ("rep_dist", "<u4"), ("max_dist", "<u4"), ("reserved", "<u4")])
+
+
+def _group_summary(self, fn, labels):
+    """shared by Engine.group_summary and ShardedEngine.group_summary: (groups [G] GROUP_DTYPE, centroids [G, bits / 8] uint8,
+    rep_labels [N] uint32, group_index [N] uint32); called with groups_cap = N, so there is no second call"""
+    n = len(self)
+    labels = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+    if labels.shape[0] != n:
+        raise VcError(VC_ERR_INVALID, "the labels must have one word per resident record")
+    groups = np.zeros(n, dtype=GROUP_DTYPE)
+    cents = np.zeros((n, self.bits // 8), dtype=np.uint8)
+    rep_labels, group_index = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+    g = C.c_uint64(0)
+    self._check(fn(self._h, _p(labels) if n else None, n, _p(groups) if n else None, _p(cents) if n else None, _p(rep_labels) if n else None,
+                   _p(group_index) if n else None, C.byref(g)))
+    return groups[:g.value].copy(), cents[:g.value].copy(), rep_labels, group_index
+
+
+def _group_summary_dev(self, fn, d_labels, groups_cap, d_groups, d_centroids, d_rep_labels, d_group_index, stream):
+    """returns (rc, G): rc is VC_OK or VC_ERR_CAPACITY (G > groups_cap: no output was written)"""
+    g = C.c_uint64(0)
+    rc = self._check(fn(self._h, d_labels, groups_cap, d_groups, d_centroids, d_rep_labels, d_group_index, C.byref(g), stream), ok=(VC_OK, VC_ERR_CAPACITY))
+    return rc, int(g.value)
 
 
 def _retain(self, fn, sel, kind, with_map):
@@ -577,6 +609,19 @@ class Engine:
         the handle); both valid in `stream` order.  Returns the stats dict."""
         return _dbscan_radius_dev(self, self._L.vc_dbscan_radius_dev, radius, min_pts, d_labels, d_degrees, mode, batch, stream)
 
+    def group_summary(self, labels):
+        """vc_group_summary: the groups of equal labels (any of the clustering calls' output, or any partition with values in the resident
+        id range) summarised.  Returns (groups, centroids, rep_labels, group_index): groups = structured array GROUP_DTYPE, one entry per
+        group by ascending label (label, size, rep, rep_dist, max_dist); centroids = uint8 [G, bits / 8], the per-bit strict-majority
+        codes; rep_labels[i] = the representative (the member nearest its group's centroid, the smaller id on a tie) of record i's
+        group; group_index[i] = its group's number.  retain(rep_labels, RETAIN_ROOTS) keeps exactly the representatives."""
+        return _group_summary(self, self._L.vc_group_summary, labels)
+
+    def group_summary_dev(self, d_labels, groups_cap, d_groups, d_centroids=None, d_rep_labels=None, d_group_index=None, stream=None):
+        """vc_group_summary_dev: raw device addresses (None for an output that is not wanted); outputs valid in `stream` order.  Returns
+        (rc, G) with rc VC_OK, or VC_ERR_CAPACITY when G > groups_cap (nothing was written)."""
+        return _group_summary_dev(self, self._L.vc_group_summary_dev, d_labels, groups_cap, d_groups, d_centroids, d_rep_labels, d_group_index, stream)
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -793,6 +838,19 @@ class ShardedEngine:
         """vc_sharded_dbscan_radius_dev: d_labels / d_degrees = the raw device addresses of len(self) uint32 each on the root device (d_degrees None: scratch of
         the handle); both valid in `stream` order.  Returns the stats dict."""
         return _dbscan_radius_dev(self, self._L.vc_sharded_dbscan_radius_dev, radius, min_pts, d_labels, d_degrees, mode, batch, stream)
+
+    def group_summary(self, labels):
+        """vc_sharded_group_summary: the groups of equal labels (any of the clustering calls' output, or any partition with values in the resident
+        id range) summarised.  Returns (groups, centroids, rep_labels, group_index): groups = structured array GROUP_DTYPE, one entry per
+        group by ascending label (label, size, rep, rep_dist, max_dist); centroids = uint8 [G, bits / 8], the per-bit strict-majority
+        codes; rep_labels[i] = the representative (the member nearest its group's centroid, the smaller id on a tie) of record i's
+        group; group_index[i] = its group's number.  retain(rep_labels, RETAIN_ROOTS) keeps exactly the representatives."""
+        return _group_summary(self, self._L.vc_sharded_group_summary, labels)
+
+    def group_summary_dev(self, d_labels, groups_cap, d_groups, d_centroids=None, d_rep_labels=None, d_group_index=None, stream=None):
+        """vc_sharded_group_summary_dev: raw device addresses on the root device (None for an output that is not wanted); outputs valid in
+        `stream` order.  Returns (rc, G) with rc VC_OK, or VC_ERR_CAPACITY when G > groups_cap (nothing was written)."""
+        return _group_summary_dev(self, self._L.vc_sharded_group_summary_dev, d_labels, groups_cap, d_groups, d_centroids, d_rep_labels, d_group_index, stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

@@ -129,6 +129,10 @@ class Backend {
   // labels[i] = the smallest core id of a core's component, the label of a border's smallest-id core neighbour, the own id for noise
   // (vc_dbscan_radius / vc_sharded_dbscan_radius); retain() with VC_RETAIN_ROOTS keeps one record per cluster and the noise
   virtual int dbscan_radius(uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats) = 0;
+  // the groups of equal labels summarised (vc_group_summary / vc_sharded_group_summary): sizes, per-bit majority codes, the member
+  // nearest each -- retain() of rep_labels with VC_RETAIN_ROOTS keeps exactly these representatives
+  virtual int group_summary(const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels, uint32_t* group_index,
+                            uint64_t* n_groups) = 0;
   // records taken out of the store and its index, the survivors renumbered in order (vc_retain / vc_sharded_retain; the reference has
   // no delete: this stands for build_hash_tables.cc run again over the code file without them).  kind VC_RETAIN_MASK / VC_RETAIN_ROOTS
   virtual int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) = 0;
@@ -191,6 +195,10 @@ class Engine : public Backend {
   }
   int dbscan_radius(uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats) override {
     return vc_dbscan_radius(h_, radius, min_pts, mode, batch, labels, degrees, stats);
+  }
+  int group_summary(const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels, uint32_t* group_index,
+                    uint64_t* n_groups) override {
+    return vc_group_summary(h_, labels, groups_cap, groups, centroids, rep_labels, group_index, n_groups);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_retain(h_, sel, kind, new_ids, n_kept); }
  private:
@@ -281,6 +289,10 @@ class ShardedEngine : public Backend {
   }
   int dbscan_radius(uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats) override {
     return vc_sharded_dbscan_radius(h_, radius, min_pts, mode, batch, labels, degrees, stats);
+  }
+  int group_summary(const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels, uint32_t* group_index,
+                    uint64_t* n_groups) override {
+    return vc_sharded_group_summary(h_, labels, groups_cap, groups, centroids, rep_labels, group_index, n_groups);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_sharded_retain(h_, sel, kind, new_ids, n_kept); }
  private:
