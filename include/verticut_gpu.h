@@ -345,7 +345,7 @@ int vc_search_radius_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_
  * enqueued on `stream`; the host waits where the radius search underneath waits -- once per batch and attempt, for its total -- and
  * once more at the end, for the stats.  Labels are valid in stream order.
  * The scratch (the batch's ids, gathered queries, found words, the raw results and their offsets, two counters) is grow-only
- * buffers of the handle, separate from those of every other call but vc_leaders_radius* and vc_dbscan_radius*, which fill the same
+ * buffers of the handle, separate from those of every other call but vc_leaders_radius*, vc_dbscan_radius* and vc_cluster_levels*, which fill the same
  * batch buffers completely before they read them -- every word written before it is read within a call: a result depends on the database and the
  * call only.  The raw results grow to the LARGEST batch's total: on duplicate-heavy data that is
  * `batch` x the size of a group of duplicates (4096 ids into a bucket of 250 000 are 8 GB), so choose a smaller batch there. */
@@ -475,6 +475,49 @@ int vc_dbscan_radius_dev(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32
  * then come home; waits for them. */
 int vc_dbscan_radius(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees,
                      vc_dbscan_stats* stats);
+
+/* "Which radius should I cluster at": the grouping of vc_cluster_radius at EVERY radius 0 .. max_radius from ONE walk of the radius
+ * search, with the histogram of the pair distances -- the single-linkage dendrogram cut at every integer height.  Hamming distances
+ * are integers and the raw result of the search at max_radius already holds every pair within every smaller radius, each entry with
+ * its distance; a loop of max_radius + 1 vc_cluster_radius calls walks the store that many times.
+ * labels: LEVEL-MAJOR, (max_radius + 1) * N entries with N = vc_size; labels[r * N + i] (index it in 64 bits) is the label of record
+ * id_base + i at radius r.  Level r equals BIT FOR BIT what vc_cluster_radius* returns for radius = r with the same mode and
+ * n_labelled and any batch -- the smallest GLOBAL id of the record's component -- stats->n_clusters[r] equals that call's n_clusters,
+ * and n_pairs[0] + ... + n_pairs[r] its n_pairs.  The levels are nested: labels[r * N + i] <= labels[(r - 1) * N + i].
+ * mode VC_MODE_LINEAR or VC_MODE_MIH_EXACT.  Errors are checked before any work and leave labels untouched: VC_ERR_INVALID for a
+ * null handle, null labels, another mode, n_labelled > N or max_radius >= VC_LEVELS_MAX; VC_ERR_STATE in MIH mode without a current
+ * index (a stale one counts as none).  N == 0 gives VC_OK and zero stats; nothing is written.  stats (host memory, may be NULL) is
+ * filled when the call returns; its entries above max_radius are 0.
+ * batch: as in vc_cluster_radius, 0 = 4096, any value >= 1 is legal; the result does not depend on it.
+ * n_labelled is the incremental form, the companion of vc_update_index: for EVERY level r the entries labels[r * N .. r * N +
+ * n_labelled) come IN -- the stride is the NEW N, so the caller re-lays the array of its earlier call -- and the entries behind them
+ * are ignored and overwritten.  PRECONDITION: they are this call's level r for the first n_labelled records ALONE.  Only the ids
+ * id_base + n_labelled .. are queried, with the keep rule of vc_cluster_radius.  The result is bit for bit that of a call from scratch;
+ * n_pairs[d] counts the pairs {a < b} of distance d with b >= n_labelled.  n_labelled == N only re-flattens and counts.
+ * How: one forest per level, in place in labels.  Per batch the walk of vc_cluster_radius at max_radius, then one launch over the raw
+ * result: a kept entry of distance d is united in forest d ONLY (not in the forests d .. max_radius: one union per pair), and
+ * counted in n_pairs[d].  After the last batch the cascade, one launch per level r = 1 .. max_radius: every record is united in
+ * forest r with its root in forest r - 1, which is final by then -- by induction forest r connects exactly what the pairs of distance
+ * <= r connect; the incoming labels of the incremental form are trees of their level like any other.  Then one launch flattens all
+ * levels and counts their roots.  No kernel waits for another block.
+ * Device form: d_labels holds the forests and must not be touched by the caller during the call.  Everything is enqueued on
+ * `stream`; the host waits where the radius search underneath waits -- once per batch and attempt, for its total -- and once more at
+ * the end, for the stats.  Labels are valid in stream order.
+ * Scratch: the batch buffers (ids, gathered queries, found words, the raw results and their offsets) and the host form's staged
+ * labels (grown to all levels) are THOSE OF vc_cluster_radius* -- every call fills them completely before it reads them; the 2 x 64
+ * counters are this call's own.  All grow-only buffers of the handle, every word written before it is read within a call; the note
+ * on the raw results' size at vc_cluster_radius holds here too, at max_radius. */
+#define VC_LEVELS_MAX 64            /* levels 0 .. 63 */
+typedef struct vc_levels_stats {    /* 1024 bytes */
+  uint64_t n_pairs[VC_LEVELS_MAX];     /* [d] = unordered pairs {a < b}, b >= n_labelled, at distance EXACTLY d; 0 above max_radius */
+  uint64_t n_clusters[VC_LEVELS_MAX];  /* [r] = components over ALL resident records at radius r; 0 above max_radius */
+} vc_levels_stats;
+int vc_cluster_levels_dev(vc_engine* e, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
+                          vc_levels_stats* stats, void* stream);
+/* The same for labels in host memory: the device form on the engine's stream plus the staged labels (of every level the first
+ * n_labelled go in, all (max_radius + 1) * N come home); waits for them. */
+int vc_cluster_levels(vc_engine* e, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
+                      vc_levels_stats* stats);
 
 /* "What is in each group": the step after vc_cluster_radius*, vc_leaders_radius* or vc_dbscan_radius*, which all stop at a labels
  * array.  Per group of equal labels: its size, its typical code and the member to keep.  The reference has nothing of the kind; the
@@ -729,6 +772,15 @@ int vc_sharded_dbscan_radius_dev(vc_sharded* h, uint32_t radius, uint32_t min_pt
                                  uint32_t* d_degrees, vc_dbscan_stats* stats, void* stream);
 int vc_sharded_dbscan_radius(vc_sharded* h, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels,
                              uint32_t* degrees, vc_dbscan_stats* stats);
+/* Single-linkage clusters at every radius over all shards: contract, layout, modes, errors, batch, n_labelled, stats and scratch
+ * sharing as vc_cluster_levels_dev / vc_cluster_levels, with N = vc_sharded_size and ids global over the whole store.  d_labels
+ * lives on the ROOT device, `stream` is a stream of that device.  The search underneath is vc_sharded_search_radius_dev into scratch
+ * on the root, the batch's ids are gathered as in vc_sharded_get_codes_dev, and the kernels run on the root with global ids: level r
+ * equals bit for bit vc_sharded_cluster_radius* at radius r.  VC_FLAG_GLOBAL_STOP and VC_FLAG_GLOBAL_APPROX play no part. */
+int vc_sharded_cluster_levels_dev(vc_sharded* h, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
+                                  vc_levels_stats* stats, void* stream);
+int vc_sharded_cluster_levels(vc_sharded* h, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
+                              vc_levels_stats* stats);
 /* Label groups summarised over all shards: contract, capacity protocol, errors and scratch as vc_group_summary_dev / vc_group_summary,
  * with N = vc_sharded_size, ids global over the whole store and every pointer of the device form on the ROOT device, `stream` a stream
  * of that device.  The same kernels run on the root; only the rows of a window come through vc_sharded_get_codes_dev instead.

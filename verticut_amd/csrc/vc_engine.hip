@@ -77,6 +77,9 @@ struct vc_engine {
   // own are the degrees of a call that passes none (and of the host form) and the five statistics
   uint32_t* d_ddeg = nullptr;   size_t ddeg_bytes = 0;
   uint64_t* d_dstat = nullptr;  size_t dstat_bytes = 0;
+  // clusters at every radius (vc_cluster_levels*): it shares the same batch buffers and the staged labels, grown to all levels (it fills
+  // them completely too); its own are the 2 x 64 counters (vc_levels_stats as it lies)
+  uint64_t* d_vstat = nullptr;  size_t vstat_bytes = 0;
   // label groups summarised (vc_group_summary*): the sort and numbering arrays, the row buffer with the big groups' tables, the host
   // form's staging (VC_GROUPS_*); its own, shared with no other call, every word written before it is read
   uint8_t* d_grp[VC_GROUPS_BUFS] = {nullptr, nullptr, nullptr};  size_t grp_bytes[VC_GROUPS_BUFS] = {0, 0, 0};
@@ -382,6 +385,7 @@ int vc_destroy(vc_engine* e) {
   (void)hipFree(e->d_lstat);
   (void)hipFree(e->d_ddeg);
   (void)hipFree(e->d_dstat);
+  (void)hipFree(e->d_vstat);
   for (uint8_t* b : e->d_grp) (void)hipFree(b);
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->last_call) (void)hipEventDestroy(e->last_call);
@@ -1349,6 +1353,96 @@ int vc_cluster_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t bat
   }
   if (rc) return rc;
   VC_HIP(e, hipMemcpyAsync(labels, e->d_chlab, (size_t)e->n * 4, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipStreamSynchronize(e->stream));
+  return VC_OK;
+}
+
+}  // extern "C"
+
+// ---- clusters at every radius 0 .. max_radius: one walk, one forest per level --------------------------------------------------------
+static int check_levels_args(vc_engine* e, uint32_t max_radius, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
+  if (!e || !labels) return VC_ERR_INVALID;
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "cluster levels: mode must be LINEAR or MIH_EXACT");
+  if (max_radius >= VC_LEVELS_MAX) return fail(e, VC_ERR_INVALID, "cluster levels: max_radius %u exceeds %u", max_radius, VC_LEVELS_MAX - 1);
+  if (n_labelled > e->n) return fail(e, VC_ERR_INVALID, "cluster levels: n_labelled %llu exceeds the %llu resident records", (unsigned long long)n_labelled, (unsigned long long)e->n);
+  if (e->n && mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
+  return VC_OK;
+}
+
+// The whole call on e->stream (inside the caller's StreamCall), e->n > 0.  cluster_run's loop over the batch buffers it shares with
+// that call (both fill them completely), at max_radius: per batch of ids the ids filled on the device, the gather, the radius search
+// -- repeated once with the scratch grown to the total it reported -- and the union over the raw result as it lies, every kept entry in
+// the forest of its distance.  After the last batch the cascade, one flatten over all levels, then the one wait for the counters.
+static int levels_run(vc_engine* e, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_levels_stats* stats) {
+  int rc;
+  const uint64_t N = e->n, first_new = (uint64_t)e->cfg.id_base + n_labelled;
+  if (batch == 0) batch = VC_CLUSTER_BATCH;
+  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N - n_labelled);
+  if ((rc = grow(e, &e->d_vstat, &e->vstat_bytes, VC_LEVELS_STAT_BYTES))) return rc;
+  if (nq_max) {
+    if ((rc = grow(e, &e->d_cids, &e->cids_bytes, (size_t)nq_max * 4))) return rc;
+    if ((rc = grow(e, &e->d_cq, &e->cq_bytes, (size_t)nq_max * e->W * 8))) return rc;
+    if ((rc = grow(e, &e->d_cfound, &e->cfound_bytes, (size_t)nq_max * 4))) return rc;
+    if ((rc = grow(e, &e->d_croffs, &e->croffs_bytes, ((size_t)nq_max + 1) * 8))) return rc;
+    if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)8 << 16))) return rc;
+  }
+  VC_HIP(e, hipMemsetAsync(e->d_vstat, 0, VC_LEVELS_STAT_BYTES, e->stream));
+  for (uint32_t r = 0; r <= max_radius; ++r)
+    VC_HIP(e, vc_launch_cluster_init(d_labels + (uint64_t)r * N + n_labelled, N - n_labelled, (uint32_t)first_new, e->stream));
+  for (uint64_t pos = n_labelled; pos < N; pos += batch) {
+    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = e->cfg.id_base + (uint32_t)pos;
+    VC_HIP(e, vc_launch_cluster_init(e->d_cids, nq, first_id, e->stream));
+    VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, e->d_cids, nq, e->d_cq, e->d_cfound, e->stream));
+    uint64_t raw_total = 0;
+    for (int attempt = 0;; ++attempt) {
+      const uint64_t cap = e->craw_bytes / 8;
+      rc = vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, e->d_cq, nq,
+                            max_radius, e->d_craw, cap, e->d_croffs, true, &e->radius_work, e->stream, &e->err, &raw_total);
+      if (rc == VC_OK) break;
+      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
+      if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)raw_total * 8))) return rc;   // (the first attempt has been waited for)
+    }
+    VC_HIP(e, vc_launch_levels_union(e->d_craw, e->d_croffs, nq, raw_total, first_id, first_new, e->cfg.id_base, N, max_radius, d_labels, e->d_vstat, e->stream));
+  }
+  VC_HIP(e, vc_launch_levels_cascade(d_labels, N, e->cfg.id_base, max_radius, e->stream));
+  VC_HIP(e, vc_launch_levels_flatten(d_labels, N, e->cfg.id_base, max_radius, e->d_vstat + VC_LEVELS_MAX, e->stream));
+  vc_levels_stats st;
+  VC_HIP(e, hipMemcpyAsync(&st, e->d_vstat, VC_LEVELS_STAT_BYTES, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipStreamSynchronize(e->stream));
+  if (stats) *stats = st;
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_cluster_levels_dev(vc_engine* e, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
+                          vc_levels_stats* stats, void* stream) {
+  int rc = check_levels_args(e, max_radius, mode, n_labelled, d_labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_levels_stats{};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, caller_stream(e, stream));
+  return levels_run(e, max_radius, mode, batch, n_labelled, d_labels, stats);
+}
+
+int vc_cluster_levels(vc_engine* e, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_levels_stats* stats) {
+  int rc = check_levels_args(e, max_radius, mode, n_labelled, labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_levels_stats{};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const size_t N = (size_t)e->n, levels = (size_t)max_radius + 1;
+  if ((rc = grow(e, &e->d_chlab, &e->chlab_bytes, levels * N * 4))) return rc;
+  if (n_labelled)
+    for (size_t r = 0; r < levels; ++r)
+      VC_HIP(e, hipMemcpyAsync(e->d_chlab + r * N, labels + r * N, (size_t)n_labelled * 4, hipMemcpyHostToDevice, e->stream));
+  {
+    const StreamCall call(e, e->stream);
+    rc = levels_run(e, max_radius, mode, batch, n_labelled, e->d_chlab, stats);
+  }
+  if (rc) return rc;
+  VC_HIP(e, hipMemcpyAsync(labels, e->d_chlab, levels * N * 4, hipMemcpyDeviceToHost, e->stream));
   VC_HIP(e, hipStreamSynchronize(e->stream));
   return VC_OK;
 }

@@ -231,6 +231,17 @@ hipError_t vc_launch_dbscan_edges(const uint64_t* d_raw, const uint64_t* d_roffs
 // d_counts[0 .. 3] += the roots among the cores, the cores, the borders, the noise
 hipError_t vc_launch_dbscan_finish(uint32_t* d_labels, const uint32_t* d_degrees, uint64_t n, uint32_t id_base, uint32_t min_pts, uint64_t* d_counts,
                                    hipStream_t s);
+// ---- vc_levels.hip: single-linkage clusters at every radius 0 .. max_radius in one walk (vc_cluster_levels*).  d_labels is level-major,
+// (max_radius + 1) x n: level r at d_labels + r * n is a forest of vc_forest.hpp in place, as vc_cluster.hip's.  Nothing here waits.
+#define VC_LEVELS_STAT_BYTES 1024u   // d_stat: vc_levels_stats as it lies (64 pair counters, then 64 cluster counters)
+// every kept entry (vc_launch_cluster_union's keep rule) of distance d is united with its query in forest d only;
+// d_n_pairs[d] += the kept entries of distance d
+hipError_t vc_launch_levels_union(const uint64_t* d_raw, const uint64_t* d_roffs, uint32_t nq, uint64_t total, uint32_t first_id, uint64_t first_new,
+                                  uint32_t id_base, uint64_t n, uint32_t max_radius, uint32_t* d_labels, uint64_t* d_n_pairs, hipStream_t s);
+// after the last batch: max_radius launches, level r takes in the components of level r - 1
+hipError_t vc_launch_levels_cascade(uint32_t* d_labels, uint64_t n, uint32_t id_base, uint32_t max_radius, hipStream_t s);
+// d_labels[r * n + i] = the root of record i at level r, in place, every level in one launch; d_n_clusters[r] += the roots of level r
+hipError_t vc_launch_levels_flatten(uint32_t* d_labels, uint64_t n, uint32_t id_base, uint32_t max_radius, uint64_t* d_n_clusters, hipStream_t s);
 // ---- vc_groups.hip: label groups summarised (vc_group_summary*, vc_sharded_group_summary*).  One driver for both handle kinds: the
 // codes of a window's sorted ids come through `fetch` (vc_get_codes_dev / the sharded gather, enqueued on s, nothing waited for)
 // as contiguous rows [nq][W].  The plan arithmetic is vc_groups_plan.hpp.

@@ -47,7 +47,9 @@ EXPORTS = [
     "vc_leaders_radius", "vc_leaders_radius_dev", "vc_sharded_leaders_radius", "vc_sharded_leaders_radius_dev",
     "vc_dbscan_radius", "vc_dbscan_radius_dev", "vc_sharded_dbscan_radius", "vc_sharded_dbscan_radius_dev",
     "vc_group_summary", "vc_group_summary_dev", "vc_sharded_group_summary", "vc_sharded_group_summary_dev",
+    "vc_cluster_levels", "vc_cluster_levels_dev", "vc_sharded_cluster_levels", "vc_sharded_cluster_levels_dev",
 ]
+LEVELS_MAX = 64           # VC_LEVELS_MAX: cluster_levels takes max_radius 0 .. 63
 MAX_SHARDS = 16
 EXCHANGE_AUTO, EXCHANGE_PEER_COPY, EXCHANGE_RCCL = 0, 1, 2
 
@@ -76,6 +78,10 @@ class VcQueryStats(C.Structure):
 
 class VcClusterStats(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("n_clusters", C.c_uint64)]
+
+
+class VcLevelsStats(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64 * LEVELS_MAX), ("n_clusters", C.c_uint64 * LEVELS_MAX)]
 
 
 class VcLeaderStats(C.Structure):
@@ -203,6 +209,10 @@ def load_library():
     L.vc_group_summary_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp, C.POINTER(u64), vp]
     L.vc_sharded_group_summary.argtypes = [vp, vp, u64, vp, vp, vp, vp, C.POINTER(u64)]
     L.vc_sharded_group_summary_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp, C.POINTER(u64), vp]
+    L.vc_cluster_levels.argtypes = [vp, u32, u32, u32, u64, vp, vp]
+    L.vc_cluster_levels_dev.argtypes = [vp, u32, u32, u32, u64, vp, vp, vp]
+    L.vc_sharded_cluster_levels.argtypes = [vp, u32, u32, u32, u64, vp, vp]
+    L.vc_sharded_cluster_levels_dev.argtypes = [vp, u32, u32, u32, u64, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -263,6 +273,35 @@ def _cluster_radius_dev(self, fn, radius, d_labels, mode, batch, n_labelled, str
     st = VcClusterStats()
     self._check(fn(self._h, radius, mode, batch, n_labelled, d_labels, C.byref(st), stream))
     return int(st.n_pairs), int(st.n_clusters)
+
+
+def _levels_arrays(st, max_radius):
+    return (np.array(st.n_pairs[:max_radius + 1], dtype=np.uint64), np.array(st.n_clusters[:max_radius + 1], dtype=np.uint64))
+
+
+def _cluster_levels(self, fn, max_radius, mode, batch, labels):
+    """shared by Engine.cluster_levels and ShardedEngine.cluster_levels: (labels [max_radius + 1, N] uint32, n_pairs [max_radius + 1],
+    n_clusters [max_radius + 1]); `labels` [max_radius + 1, n_labelled] of an earlier call is re-laid to the stride N here"""
+    n = len(self)
+    out = np.empty((max_radius + 1, n), dtype=np.uint32)
+    n_labelled = 0
+    if labels is not None:
+        old = np.ascontiguousarray(labels, dtype=np.uint32)
+        if old.ndim != 2 or old.shape[0] != max_radius + 1:
+            raise VcError(VC_ERR_INVALID, "the labels must have one row per level 0 .. max_radius")
+        n_labelled = old.shape[1]
+        if n_labelled > n:
+            raise VcError(VC_ERR_INVALID, "more labels than resident records")
+        out[:, :n_labelled] = old
+    st = VcLevelsStats()
+    self._check(fn(self._h, max_radius, mode, batch, n_labelled, _p(out), C.byref(st)))
+    return (out,) + _levels_arrays(st, max_radius)
+
+
+def _cluster_levels_dev(self, fn, max_radius, d_labels, mode, batch, n_labelled, stream):
+    st = VcLevelsStats()
+    self._check(fn(self._h, max_radius, mode, batch, n_labelled, d_labels, C.byref(st), stream))
+    return _levels_arrays(st, max_radius)
 
 
 def _leaders_radius(self, fn, radius, mode, batch, labels):
@@ -582,6 +621,20 @@ class Engine:
         entries come in); labels valid in `stream` order.  Returns (n_pairs, n_clusters)."""
         return _cluster_radius_dev(self, self._L.vc_cluster_radius_dev, radius, d_labels, mode, batch, n_labelled, stream)
 
+    def cluster_levels(self, max_radius, mode=MODE_LINEAR, batch=0, labels=None):
+        """vc_cluster_levels: cluster_radius at EVERY radius 0 .. max_radius (< LEVELS_MAX) from one walk of the radius search.
+        Returns (labels [max_radius + 1, N], n_pairs, n_clusters): row r equals cluster_radius(r)'s labels, n_clusters[r] its cluster
+        count, n_pairs[d] the pairs at distance exactly d (their prefix sums are cluster_radius' n_pairs).  `labels`: the
+        [max_radius + 1, n_labelled] rows an earlier call returned for the first n_labelled records alone (the incremental form,
+        after add_codes + update_index); the result equals a call from scratch."""
+        return _cluster_levels(self, self._L.vc_cluster_levels, max_radius, mode, batch, labels)
+
+    def cluster_levels_dev(self, max_radius, d_labels, mode=MODE_MIH_EXACT, batch=0, n_labelled=0, stream=None):
+        """vc_cluster_levels_dev: d_labels = the raw device address of (max_radius + 1) * len(self) uint32, level-major, one
+        forest per level in place (of every level the first n_labelled entries come in, at the stride len(self)); labels valid in
+        `stream` order.  Returns (n_pairs, n_clusters), max_radius + 1 entries each."""
+        return _cluster_levels_dev(self, self._L.vc_cluster_levels_dev, max_radius, d_labels, mode, batch, n_labelled, stream)
+
     def leaders_radius(self, radius, mode=MODE_LINEAR, batch=0, labels=None):
         """vc_leaders_radius: the greedy one-pass dedup over all resident records in id order.  Returns (labels, n_pairs, n_leaders,
         n_rounds): labels[i] = the record's own global id for a LEADER (no leader with a smaller id within `radius`), else the
@@ -811,6 +864,20 @@ class ShardedEngine:
         """vc_sharded_cluster_radius_dev: d_labels = the raw device address of len(self) uint32 on the root device, the union-find forest in place (its first n_labelled
         entries come in); labels valid in `stream` order.  Returns (n_pairs, n_clusters)."""
         return _cluster_radius_dev(self, self._L.vc_sharded_cluster_radius_dev, radius, d_labels, mode, batch, n_labelled, stream)
+
+    def cluster_levels(self, max_radius, mode=MODE_LINEAR, batch=0, labels=None):
+        """vc_sharded_cluster_levels: cluster_radius at EVERY radius 0 .. max_radius (< LEVELS_MAX) from one walk of the radius search.
+        Returns (labels [max_radius + 1, N], n_pairs, n_clusters): row r equals cluster_radius(r)'s labels, n_clusters[r] its cluster
+        count, n_pairs[d] the pairs at distance exactly d (their prefix sums are cluster_radius' n_pairs).  `labels`: the
+        [max_radius + 1, n_labelled] rows an earlier call returned for the first n_labelled records alone (the incremental form,
+        after add_codes + update_index); the result equals a call from scratch."""
+        return _cluster_levels(self, self._L.vc_sharded_cluster_levels, max_radius, mode, batch, labels)
+
+    def cluster_levels_dev(self, max_radius, d_labels, mode=MODE_MIH_EXACT, batch=0, n_labelled=0, stream=None):
+        """vc_sharded_cluster_levels_dev: d_labels = the raw device address of (max_radius + 1) * len(self) uint32 on the root device, level-major, one
+        forest per level in place (of every level the first n_labelled entries come in, at the stride len(self)); labels valid in
+        `stream` order.  Returns (n_pairs, n_clusters), max_radius + 1 entries each."""
+        return _cluster_levels_dev(self, self._L.vc_sharded_cluster_levels_dev, max_radius, d_labels, mode, batch, n_labelled, stream)
 
     def leaders_radius(self, radius, mode=MODE_LINEAR, batch=0, labels=None):
         """vc_sharded_leaders_radius: the greedy one-pass dedup over all resident records in id order.  Returns (labels, n_pairs, n_leaders,

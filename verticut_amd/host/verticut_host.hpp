@@ -121,6 +121,10 @@ class Backend {
   // near-duplicate groups: labels[i] = smallest id of the component of record i in the radius graph (vc_cluster_radius /
   // vc_sharded_cluster_radius; labels[0 .. n_labelled) come in for the incremental form)
   virtual int cluster_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats) = 0;
+  // the same at every radius 0 .. max_radius from one walk: labels is level-major, (max_radius + 1) x size(), row r = cluster_radius(r);
+  // stats->n_pairs[d] = the pairs at distance exactly d, n_clusters[r] = the groups at radius r (vc_cluster_levels /
+  // vc_sharded_cluster_levels; of every row the first n_labelled entries come in for the incremental form)
+  virtual int cluster_levels(uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_levels_stats* stats) = 0;
   // greedy leader dedup: labels[i] = own id for a LEADER (no leader with a smaller id within `radius`), else the smallest-id leader
   // within `radius` (vc_leaders_radius / vc_sharded_leaders_radius; labels[0 .. n_labelled) come in, read only); retain() with
   // VC_RETAIN_ROOTS keeps exactly the leaders
@@ -189,6 +193,9 @@ class Engine : public Backend {
   }
   int cluster_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats) override {
     return vc_cluster_radius(h_, radius, mode, batch, n_labelled, labels, stats);
+  }
+  int cluster_levels(uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_levels_stats* stats) override {
+    return vc_cluster_levels(h_, max_radius, mode, batch, n_labelled, labels, stats);
   }
   int leaders_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats) override {
     return vc_leaders_radius(h_, radius, mode, batch, n_labelled, labels, stats);
@@ -283,6 +290,9 @@ class ShardedEngine : public Backend {
   }
   int cluster_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats) override {
     return vc_sharded_cluster_radius(h_, radius, mode, batch, n_labelled, labels, stats);
+  }
+  int cluster_levels(uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_levels_stats* stats) override {
+    return vc_sharded_cluster_levels(h_, max_radius, mode, batch, n_labelled, labels, stats);
   }
   int leaders_radius(uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats) override {
     return vc_sharded_leaders_radius(h_, radius, mode, batch, n_labelled, labels, stats);
