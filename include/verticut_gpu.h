@@ -345,7 +345,7 @@ int vc_search_radius_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_
  * enqueued on `stream`; the host waits where the radius search underneath waits -- once per batch and attempt, for its total -- and
  * once more at the end, for the stats.  Labels are valid in stream order.
  * The scratch (the batch's ids, gathered queries, found words, the raw results and their offsets, two counters) is grow-only
- * buffers of the handle, separate from those of every other call but vc_leaders_radius*, vc_dbscan_radius* and vc_cluster_levels*, which fill the same
+ * buffers of the handle, separate from those of every other call but vc_leaders_radius*, vc_dbscan_radius*, vc_cluster_levels* and vc_dbscan_levels*, which fill the same
  * batch buffers completely before they read them -- every word written before it is read within a call: a result depends on the database and the
  * call only.  The raw results grow to the LARGEST batch's total: on duplicate-heavy data that is
  * `batch` x the size of a group of duplicates (4096 ids into a bucket of 250 000 are 8 GB), so choose a smaller batch there. */
@@ -518,6 +518,54 @@ int vc_cluster_levels_dev(vc_engine* e, uint32_t max_radius, uint32_t mode, uint
  * n_labelled go in, all (max_radius + 1) * N come home); waits for them. */
 int vc_cluster_levels(vc_engine* e, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
                       vc_levels_stats* stats);
+
+/* "Which radius, and which min_pts, should I run DBSCAN at": the grouping of vc_dbscan_radius at EVERY radius 0 .. max_radius from
+ * ONE walk of the radius search, with every record's CORE DISTANCE -- the k-distance that DBSCAN users plot to choose eps -- and the
+ * histogram of the pair distances.  A loop of max_radius + 1 vc_dbscan_radius calls walks the store that many times.
+ * labels: LEVEL-MAJOR, (max_radius + 1) * N entries with N = vc_size; labels[r * N + i] (index it in 64 bits) equals BIT FOR BIT what
+ * vc_dbscan_radius* returns in labels[i] for radius = r with the same min_pts, either mode and any batch.  No sentinel appears in
+ * labels.  vc_retain* with VC_RETAIN_ROOTS takes any one level, labels + r * N, as it is.
+ * core_dist (N entries, may be NULL: the handle then uses scratch of its own): core_dist[i] = the distance from record id_base + i to
+ * its min_pts-th nearest resident record, ITSELF COUNTED (so min_pts == 1 gives 0 everywhere), or VC_CORE_NEVER if fewer than min_pts
+ * records lie within max_radius.  Record i is a core at level r iff core_dist[i] <= r -- the test that stands for vc_dbscan_radius's
+ * degrees[i] >= min_pts; with it the kinds are told apart as there: a non-core record is a border at level r iff labels[r * N + i] !=
+ * id_base + i, else noise.  min_pts == 1 makes every record a core at every level and labels equal to vc_cluster_levels*.
+ * stats (host memory, may be NULL) is filled when the call returns; n_clusters, n_core, n_border and n_noise at [r] equal the
+ * vc_dbscan_stats of vc_dbscan_radius(r, min_pts); every entry above max_radius is 0.
+ * mode VC_MODE_LINEAR or VC_MODE_MIH_EXACT.  Errors are checked before any work and leave the outputs untouched: VC_ERR_INVALID for a
+ * null handle, null labels, min_pts == 0, another mode or max_radius >= VC_LEVELS_MAX; VC_ERR_STATE in MIH mode without a current
+ * index (a stale one counts as none).  N == 0 gives VC_OK and zero stats; nothing is written.
+ * batch: as in vc_dbscan_radius, 0 = 4096, any value >= 1 is legal; the result does not depend on it.
+ * There is NO n_labelled form, for vc_dbscan_radius's reason: a new record changes the degrees, hence the core distances, of the
+ * old ones, so old records turn from border or noise into cores and the old labels are no starting point.
+ * How: a pair {a, b} at distance d joins two cores at exactly the levels r >= w = max(d, core_dist[a], core_dist[b]) -- the
+ * mutual-reachability distance, an integer here.  One forest per level over that level's cores, in place in labels.  Per batch the walk
+ * of vc_dbscan_radius at max_radius, then two launches: the core distances of the batch's queries (entry min_pts - 1 of an ascending
+ * segment), then, over the entries whose neighbour has the smaller id -- every pair once, both core distances final -- the union in
+ * forest w ONLY and, where one end is no core yet at the level t at which the other becomes its core neighbour, a CAS minimum on that
+ * end's anchor candidate of exactly level t.  After the last batch the cascade, one launch per level r = 1 .. max_radius: every core
+ * of level r - 1 is united in forest r with its root in forest r - 1.  One last launch walks every record up the levels: a core
+ * takes its root, a non-core the root of the smallest candidate of the levels <= r, or keeps its own id; it counts the kinds.  No
+ * kernel waits for another block.
+ * Device form: d_labels and d_core_dist hold the state and must not be touched by the caller during the call.  Everything is enqueued
+ * on `stream`; the host waits where the radius search underneath waits -- once per batch and attempt, for its total -- and once more
+ * at the end, for the stats.  Labels and core distances are valid in stream order.
+ * Scratch: the batch buffers and the host form's staged labels (grown to all levels) are THOSE OF vc_cluster_radius* -- every call
+ * fills them completely before it reads them; the core distances of a call that passes none (and of the host form) and the 5 x 64
+ * counters are this call's own.  All grow-only buffers of the handle, every word written before it is read within a call; the note
+ * on the raw results' size at vc_cluster_radius holds here too, at max_radius. */
+#define VC_CORE_NEVER 0xFFFFFFFFu      /* core_dist: fewer than min_pts records within max_radius */
+typedef struct vc_dbscan_levels_stats {   /* 2560 bytes; every entry above max_radius is 0 */
+  uint64_t n_pairs[VC_LEVELS_MAX];     /* [d] = unordered pairs {a < b} at distance EXACTLY d (== vc_levels_stats.n_pairs at n_labelled 0) */
+  uint64_t n_clusters[VC_LEVELS_MAX];  /* [r] == vc_dbscan_stats.n_clusters of vc_dbscan_radius(r, min_pts) */
+  uint64_t n_core[VC_LEVELS_MAX], n_border[VC_LEVELS_MAX], n_noise[VC_LEVELS_MAX];   /* [r], sum to N */
+} vc_dbscan_levels_stats;
+int vc_dbscan_levels_dev(vc_engine* e, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels,
+                         uint32_t* d_core_dist, vc_dbscan_levels_stats* stats, void* stream);
+/* The same for labels and core_dist (may be NULL) in host memory: the device form on the engine's stream into staged buffers, which
+ * then come home; waits for them. */
+int vc_dbscan_levels(vc_engine* e, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels,
+                     uint32_t* core_dist, vc_dbscan_levels_stats* stats);
 
 /* "What is in each group": the step after vc_cluster_radius*, vc_leaders_radius* or vc_dbscan_radius*, which all stop at a labels
  * array.  Per group of equal labels: its size, its typical code and the member to keep.  The reference has nothing of the kind; the
@@ -781,6 +829,16 @@ int vc_sharded_cluster_levels_dev(vc_sharded* h, uint32_t max_radius, uint32_t m
                                   vc_levels_stats* stats, void* stream);
 int vc_sharded_cluster_levels(vc_sharded* h, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
                               vc_levels_stats* stats);
+/* Density clustering at every radius over all shards: contract, layout, core distances, modes, errors, batch, stats and scratch
+ * sharing as vc_dbscan_levels_dev / vc_dbscan_levels (no n_labelled form either), with N = vc_sharded_size and ids global over the
+ * whole store.  d_labels and d_core_dist live on the ROOT device, `stream` is a stream of that device.  The search underneath is
+ * vc_sharded_search_radius_dev into scratch on the root, the batch's ids are gathered as in vc_sharded_get_codes_dev, and the kernels
+ * run on the root with global ids: level r equals bit for bit vc_sharded_dbscan_radius* at radius r.  VC_FLAG_GLOBAL_STOP and
+ * VC_FLAG_GLOBAL_APPROX play no part.  vc_sharded_retain* with VC_RETAIN_ROOTS consumes any one level unchanged. */
+int vc_sharded_dbscan_levels_dev(vc_sharded* h, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels,
+                                 uint32_t* d_core_dist, vc_dbscan_levels_stats* stats, void* stream);
+int vc_sharded_dbscan_levels(vc_sharded* h, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels,
+                             uint32_t* core_dist, vc_dbscan_levels_stats* stats);
 /* Label groups summarised over all shards: contract, capacity protocol, errors and scratch as vc_group_summary_dev / vc_group_summary,
  * with N = vc_sharded_size, ids global over the whole store and every pointer of the device form on the ROOT device, `stream` a stream
  * of that device.  The same kernels run on the root; only the rows of a window come through vc_sharded_get_codes_dev instead.

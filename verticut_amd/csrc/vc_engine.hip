@@ -80,6 +80,11 @@ struct vc_engine {
   // clusters at every radius (vc_cluster_levels*): it shares the same batch buffers and the staged labels, grown to all levels (it fills
   // them completely too); its own are the 2 x 64 counters (vc_levels_stats as it lies)
   uint64_t* d_vstat = nullptr;  size_t vstat_bytes = 0;
+  // density clustering at every radius (vc_dbscan_levels*): it shares the same batch buffers and the staged labels, grown to all levels
+  // (it fills them completely too); its own are the core distances of a call that passes none (and of the host form) and the 5 x 64
+  // counters (vc_dbscan_levels_stats as it lies)
+  uint32_t* d_wcd = nullptr;    size_t wcd_bytes = 0;
+  uint64_t* d_wstat = nullptr;  size_t wstat_bytes = 0;
   // label groups summarised (vc_group_summary*): the sort and numbering arrays, the row buffer with the big groups' tables, the host
   // form's staging (VC_GROUPS_*); its own, shared with no other call, every word written before it is read
   uint8_t* d_grp[VC_GROUPS_BUFS] = {nullptr, nullptr, nullptr};  size_t grp_bytes[VC_GROUPS_BUFS] = {0, 0, 0};
@@ -386,6 +391,8 @@ int vc_destroy(vc_engine* e) {
   (void)hipFree(e->d_ddeg);
   (void)hipFree(e->d_dstat);
   (void)hipFree(e->d_vstat);
+  (void)hipFree(e->d_wcd);
+  (void)hipFree(e->d_wstat);
   for (uint8_t* b : e->d_grp) (void)hipFree(b);
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->last_call) (void)hipEventDestroy(e->last_call);
@@ -1619,6 +1626,99 @@ int vc_dbscan_radius(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32_t m
   if (rc) return rc;
   VC_HIP(e, hipMemcpyAsync(labels, e->d_chlab, (size_t)e->n * 4, hipMemcpyDeviceToHost, e->stream));
   if (degrees) VC_HIP(e, hipMemcpyAsync(degrees, e->d_ddeg, (size_t)e->n * 4, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipStreamSynchronize(e->stream));
+  return VC_OK;
+}
+
+}  // extern "C"
+
+// ---- density clustering at every radius 0 .. max_radius: one walk, one forest per level over that level's cores ----------------------
+static int check_dbscan_levels_args(vc_engine* e, uint32_t max_radius, uint32_t min_pts, uint32_t mode, const uint32_t* labels) {
+  if (!e || !labels) return VC_ERR_INVALID;
+  if (min_pts == 0) return fail(e, VC_ERR_INVALID, "dbscan levels: min_pts must be at least 1");
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "dbscan levels: mode must be LINEAR or MIH_EXACT");
+  if (max_radius >= VC_LEVELS_MAX) return fail(e, VC_ERR_INVALID, "dbscan levels: max_radius %u exceeds %u", max_radius, VC_LEVELS_MAX - 1);
+  if (e->n && mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
+  return VC_OK;
+}
+
+// The whole call on e->stream (inside the caller's StreamCall), e->n > 0.  levels_run's loop over the batch buffers it shares with that
+// call (both fill them completely), at max_radius and in ascending id order: per batch of ids the ids filled on the device, the
+// gather, the radius search -- repeated once with the scratch grown to the total it reported -- then the batch's core distances and
+// its edges over the raw result as it lies.  d_core_dist null: the handle's own.  After the last batch the cascade, one finish pass
+// over all levels, then the one wait for the counters.
+static int dbscan_levels_run(vc_engine* e, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels, uint32_t* d_core_dist,
+                             vc_dbscan_levels_stats* stats) {
+  int rc;
+  const uint64_t N = e->n;
+  if (batch == 0) batch = VC_CLUSTER_BATCH;
+  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N);
+  if ((rc = grow(e, &e->d_wstat, &e->wstat_bytes, VC_DBSCAN_LEVELS_STAT_BYTES))) return rc;
+  if (!d_core_dist) {
+    if ((rc = grow(e, &e->d_wcd, &e->wcd_bytes, (size_t)N * 4))) return rc;
+    d_core_dist = e->d_wcd;
+  }
+  if ((rc = grow(e, &e->d_cids, &e->cids_bytes, (size_t)nq_max * 4))) return rc;
+  if ((rc = grow(e, &e->d_cq, &e->cq_bytes, (size_t)nq_max * e->W * 8))) return rc;
+  if ((rc = grow(e, &e->d_cfound, &e->cfound_bytes, (size_t)nq_max * 4))) return rc;
+  if ((rc = grow(e, &e->d_croffs, &e->croffs_bytes, ((size_t)nq_max + 1) * 8))) return rc;
+  if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)8 << 16))) return rc;
+  VC_HIP(e, hipMemsetAsync(e->d_wstat, 0, VC_DBSCAN_LEVELS_STAT_BYTES, e->stream));
+  for (uint32_t r = 0; r <= max_radius; ++r) VC_HIP(e, vc_launch_cluster_init(d_labels + (uint64_t)r * N, N, e->cfg.id_base, e->stream));
+  for (uint64_t pos = 0; pos < N; pos += batch) {
+    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = e->cfg.id_base + (uint32_t)pos;
+    VC_HIP(e, vc_launch_cluster_init(e->d_cids, nq, first_id, e->stream));
+    VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, e->d_cids, nq, e->d_cq, e->d_cfound, e->stream));
+    uint64_t raw_total = 0;
+    for (int attempt = 0;; ++attempt) {
+      const uint64_t cap = e->craw_bytes / 8;
+      rc = vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, e->d_cq, nq,
+                            max_radius, e->d_craw, cap, e->d_croffs, true, &e->radius_work, e->stream, &e->err, &raw_total);
+      if (rc == VC_OK) break;
+      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
+      if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)raw_total * 8))) return rc;   // (the first attempt has been waited for)
+    }
+    VC_HIP(e, vc_launch_dbscan_levels_edges(e->d_craw, e->d_croffs, nq, raw_total, first_id, e->cfg.id_base, N, max_radius, min_pts, d_core_dist, d_labels,
+                                            e->d_wstat, e->stream));
+  }
+  VC_HIP(e, vc_launch_dbscan_levels_cascade(d_labels, d_core_dist, N, e->cfg.id_base, max_radius, e->stream));
+  VC_HIP(e, vc_launch_dbscan_levels_finish(d_labels, d_core_dist, N, e->cfg.id_base, max_radius, e->d_wstat + VC_LEVELS_MAX, e->stream));
+  vc_dbscan_levels_stats st;
+  VC_HIP(e, hipMemcpyAsync(&st, e->d_wstat, VC_DBSCAN_LEVELS_STAT_BYTES, hipMemcpyDeviceToHost, e->stream));
+  VC_HIP(e, hipStreamSynchronize(e->stream));
+  if (stats) *stats = st;
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_dbscan_levels_dev(vc_engine* e, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels, uint32_t* d_core_dist,
+                         vc_dbscan_levels_stats* stats, void* stream) {
+  int rc = check_dbscan_levels_args(e, max_radius, min_pts, mode, d_labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_dbscan_levels_stats{};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, caller_stream(e, stream));
+  return dbscan_levels_run(e, max_radius, min_pts, mode, batch, d_labels, d_core_dist, stats);
+}
+
+int vc_dbscan_levels(vc_engine* e, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* core_dist,
+                     vc_dbscan_levels_stats* stats) {
+  int rc = check_dbscan_levels_args(e, max_radius, min_pts, mode, labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_dbscan_levels_stats{};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const size_t N = (size_t)e->n, levels = (size_t)max_radius + 1;
+  if ((rc = grow(e, &e->d_chlab, &e->chlab_bytes, levels * N * 4))) return rc;
+  {
+    const StreamCall call(e, e->stream);
+    rc = dbscan_levels_run(e, max_radius, min_pts, mode, batch, e->d_chlab, nullptr, stats);
+  }
+  if (rc) return rc;
+  VC_HIP(e, hipMemcpyAsync(labels, e->d_chlab, levels * N * 4, hipMemcpyDeviceToHost, e->stream));
+  if (core_dist) VC_HIP(e, hipMemcpyAsync(core_dist, e->d_wcd, N * 4, hipMemcpyDeviceToHost, e->stream));
   VC_HIP(e, hipStreamSynchronize(e->stream));
   return VC_OK;
 }

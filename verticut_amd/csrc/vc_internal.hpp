@@ -242,6 +242,23 @@ hipError_t vc_launch_levels_union(const uint64_t* d_raw, const uint64_t* d_roffs
 hipError_t vc_launch_levels_cascade(uint32_t* d_labels, uint64_t n, uint32_t id_base, uint32_t max_radius, hipStream_t s);
 // d_labels[r * n + i] = the root of record i at level r, in place, every level in one launch; d_n_clusters[r] += the roots of level r
 hipError_t vc_launch_levels_flatten(uint32_t* d_labels, uint64_t n, uint32_t id_base, uint32_t max_radius, uint64_t* d_n_clusters, hipStream_t s);
+// ---- vc_dbscan_levels.hip: density clustering at every radius 0 .. max_radius in one walk (vc_dbscan_levels*).  d_labels is level-major,
+// (max_radius + 1) x n, every slot starts as the own id (vc_launch_cluster_init per level); d_core_dist [n] says whether slot (r, i)
+// is the forest of level r (d_core_dist[i] <= r) or record i's anchor candidate of exactly level r.  Nothing here waits.
+#define VC_DBSCAN_LEVELS_STAT_BYTES 2560u   // d_stat: vc_dbscan_levels_stats as it lies (5 x 64 counters: pairs, clusters, cores, borders, noise)
+// One batch, two launches over the raw result at max_radius of the queries first_id .. first_id + nq - 1: their core distances
+// (the distance of entry min_pts - 1 of a segment, VC_CORE_NEVER for a shorter one), then every entry (own, v < own) of distance d
+// is united in forest max(d, both core distances) and lowers the anchor candidates of its two ends.  The core distances below
+// first_id must be final.  d_n_pairs[d] += the entries v < own of distance d.
+hipError_t vc_launch_dbscan_levels_edges(const uint64_t* d_raw, const uint64_t* d_roffs, uint32_t nq, uint64_t total, uint32_t first_id, uint32_t id_base,
+                                         uint64_t n, uint32_t max_radius, uint32_t min_pts, uint32_t* d_core_dist, uint32_t* d_labels, uint64_t* d_n_pairs,
+                                         hipStream_t s);
+// after the last batch: max_radius launches, the cores of level r - 1 carry their components into level r
+hipError_t vc_launch_dbscan_levels_cascade(uint32_t* d_labels, const uint32_t* d_core_dist, uint64_t n, uint32_t id_base, uint32_t max_radius, hipStream_t s);
+// d_labels[r * n + i] = the root of a core, the root of a border's anchor (the smallest candidate of the levels <= r), the own id of
+// noise, in place, one launch; d_counts [4][VC_LEVELS_MAX]: [0][r] += the roots among the cores of level r, [1] cores, [2] borders, [3] noise
+hipError_t vc_launch_dbscan_levels_finish(uint32_t* d_labels, const uint32_t* d_core_dist, uint64_t n, uint32_t id_base, uint32_t max_radius,
+                                          uint64_t* d_counts, hipStream_t s);
 // ---- vc_groups.hip: label groups summarised (vc_group_summary*, vc_sharded_group_summary*).  One driver for both handle kinds: the
 // codes of a window's sorted ids come through `fetch` (vc_get_codes_dev / the sharded gather, enqueued on s, nothing waited for)
 // as contiguous rows [nq][W].  The plan arithmetic is vc_groups_plan.hpp.

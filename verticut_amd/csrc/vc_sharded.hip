@@ -139,6 +139,9 @@ enum RootBuf {
   DB_DEG, DB_STAT,
   // clusters at every radius: it shares CL_IDS .. CL_ROFFS and CL_HLAB (grown to all levels) too; its own are the 2 x 64 counters
   LV_STAT,
+  // density clustering at every radius: it shares CL_IDS .. CL_ROFFS and CL_HLAB (grown to all levels) too; its own are the core
+  // distances of a call that passes none (and of the host form) and the 5 x 64 counters
+  DL_CD, DL_STAT,
   // label groups summarised: the sort and numbering arrays, the row buffer with the big groups' tables, the host form's staging
   // (GRP_SCRATCH + VC_GROUPS_*); its own, every word written before it is read
   GRP_SCRATCH, GRP_WORK, GRP_STAGE,
@@ -2454,6 +2457,100 @@ int vc_sharded_dbscan_radius(vc_sharded* h, uint32_t radius, uint32_t min_pts, u
   VS_HIP(h, hipSetDevice(h->root));
   VS_HIP(h, hipMemcpyAsync(labels, h->buf[CL_HLAB].p, (size_t)h->n * 4, hipMemcpyDeviceToHost, S));
   if (degrees) VS_HIP(h, hipMemcpyAsync(degrees, h->buf[DB_DEG].p, (size_t)h->n * 4, hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipStreamSynchronize(S));
+  return VC_OK;
+}
+
+}  // extern "C"
+
+// ---- density clustering at every radius over the shards -------------------------------------------------------------------------------
+static int check_sharded_dbscan_levels_args(vc_sharded* h, uint32_t max_radius, uint32_t min_pts, uint32_t mode, const uint32_t* labels) {
+  if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
+  if (max_radius >= VC_LEVELS_MAX) return sfail(h, VC_ERR_INVALID, "dbscan levels: max_radius %u exceeds %u", max_radius, VC_LEVELS_MAX - 1);
+  return check_sharded_dbscan_args(h, min_pts, mode, labels);
+}
+
+// All on the root device's stream S, h->n > 0.  sharded_levels_run's loop over the batch buffers it shares with that call, at
+// max_radius and in ascending id order: per batch of global ids the ids filled on the root, the gather over the shards, the union's
+// radius search -- repeated once with the scratch grown to the total it reported -- then the batch's core distances and its edges
+// over the raw result on the root.  d_core_dist null: the handle's own.  After the last batch the cascade, one finish pass over all
+// levels, then the one wait for the counters.
+static int sharded_dbscan_levels_run(vc_sharded* h, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels,
+                                     uint32_t* d_core_dist, vc_dbscan_levels_stats* stats, hipStream_t S) {
+  int rc;
+  const uint32_t id_base = h->cfg.engine.id_base;
+  const uint64_t N = h->n;
+  if (batch == 0) batch = VC_CLUSTER_BATCH;
+  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N);
+  VS_HIP(h, hipSetDevice(h->root));
+  if ((rc = h->buf[DL_STAT].grow(h, VC_DBSCAN_LEVELS_STAT_BYTES))) return rc;
+  if (!d_core_dist) {
+    if ((rc = h->buf[DL_CD].grow(h, (size_t)N * 4))) return rc;
+    d_core_dist = h->buf[DL_CD].as<uint32_t>();
+  }
+  if ((rc = h->buf[CL_IDS].grow(h, (size_t)nq_max * 4))) return rc;
+  if ((rc = h->buf[CL_Q].grow(h, (size_t)nq_max * h->nbytes))) return rc;
+  if ((rc = h->buf[CL_FOUND].grow(h, (size_t)nq_max * 4))) return rc;
+  if ((rc = h->buf[CL_ROFFS].grow(h, ((size_t)nq_max + 1) * 8))) return rc;
+  if ((rc = h->buf[CL_RAW].grow(h, (size_t)8 << 16))) return rc;
+  uint64_t* d_stat = h->buf[DL_STAT].as<uint64_t>();
+  uint32_t* d_ids = h->buf[CL_IDS].as<uint32_t>();
+  VS_HIP(h, hipMemsetAsync(d_stat, 0, VC_DBSCAN_LEVELS_STAT_BYTES, S));
+  for (uint32_t r = 0; r <= max_radius; ++r) VS_HIP(h, vc_launch_cluster_init(d_labels + (uint64_t)r * N, N, id_base, S));
+  for (uint64_t pos = 0; pos < N; pos += batch) {
+    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = id_base + (uint32_t)pos;
+    VS_HIP(h, hipSetDevice(h->root));
+    VS_HIP(h, vc_launch_cluster_init(d_ids, nq, first_id, S));
+    if ((rc = sharded_gather_ids(h, d_ids, nq, h->buf[CL_Q].as<uint64_t>(), h->buf[CL_FOUND].as<uint32_t>(), true, S))) return rc;
+    uint64_t raw_total = 0;
+    for (int attempt = 0;; ++attempt) {
+      const uint64_t cap = h->buf[CL_RAW].bytes / 8;
+      rc = sharded_radius_dev(h, h->buf[CL_Q].p, nq, max_radius, mode, h->buf[CL_RAW].as<uint64_t>(), cap, h->buf[CL_ROFFS].as<uint64_t>(), S, &raw_total);
+      if (rc == VC_OK) break;
+      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
+      VS_HIP(h, hipSetDevice(h->root));
+      if ((rc = h->buf[CL_RAW].grow(h, (size_t)raw_total * 8))) return rc;
+    }
+    VS_HIP(h, hipSetDevice(h->root));
+    VS_HIP(h, vc_launch_dbscan_levels_edges(h->buf[CL_RAW].as<uint64_t>(), h->buf[CL_ROFFS].as<uint64_t>(), nq, raw_total, first_id, id_base, N, max_radius,
+                                            min_pts, d_core_dist, d_labels, d_stat, S));
+  }
+  VS_HIP(h, hipSetDevice(h->root));
+  VS_HIP(h, vc_launch_dbscan_levels_cascade(d_labels, d_core_dist, N, id_base, max_radius, S));
+  VS_HIP(h, vc_launch_dbscan_levels_finish(d_labels, d_core_dist, N, id_base, max_radius, d_stat + VC_LEVELS_MAX, S));
+  vc_dbscan_levels_stats st;
+  VS_HIP(h, hipMemcpyAsync(&st, d_stat, VC_DBSCAN_LEVELS_STAT_BYTES, hipMemcpyDeviceToHost, S));
+  VS_HIP(h, hipStreamSynchronize(S));
+  if (stats) *stats = st;
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_sharded_dbscan_levels_dev(vc_sharded* h, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels,
+                                 uint32_t* d_core_dist, vc_dbscan_levels_stats* stats, void* stream) {
+  int rc = check_sharded_dbscan_levels_args(h, max_radius, min_pts, mode, d_labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_dbscan_levels_stats{};
+  if (h->n == 0) return VC_OK;
+  return sharded_dbscan_levels_run(h, max_radius, min_pts, mode, batch, d_labels, d_core_dist, stats,
+                                   stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+}
+
+int vc_sharded_dbscan_levels(vc_sharded* h, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* core_dist,
+                             vc_dbscan_levels_stats* stats) {
+  int rc = check_sharded_dbscan_levels_args(h, max_radius, min_pts, mode, labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_dbscan_levels_stats{};
+  if (h->n == 0) return VC_OK;
+  hipStream_t S = h->root_stream;
+  const size_t N = (size_t)h->n, levels = (size_t)max_radius + 1;
+  VS_HIP(h, hipSetDevice(h->root));
+  if ((rc = h->buf[CL_HLAB].grow(h, levels * N * 4))) return rc;
+  if ((rc = sharded_dbscan_levels_run(h, max_radius, min_pts, mode, batch, h->buf[CL_HLAB].as<uint32_t>(), nullptr, stats, S))) return rc;
+  VS_HIP(h, hipSetDevice(h->root));
+  VS_HIP(h, hipMemcpyAsync(labels, h->buf[CL_HLAB].p, levels * N * 4, hipMemcpyDeviceToHost, S));
+  if (core_dist) VS_HIP(h, hipMemcpyAsync(core_dist, h->buf[DL_CD].p, N * 4, hipMemcpyDeviceToHost, S));
   VS_HIP(h, hipStreamSynchronize(S));
   return VC_OK;
 }

@@ -48,8 +48,10 @@ EXPORTS = [
     "vc_dbscan_radius", "vc_dbscan_radius_dev", "vc_sharded_dbscan_radius", "vc_sharded_dbscan_radius_dev",
     "vc_group_summary", "vc_group_summary_dev", "vc_sharded_group_summary", "vc_sharded_group_summary_dev",
     "vc_cluster_levels", "vc_cluster_levels_dev", "vc_sharded_cluster_levels", "vc_sharded_cluster_levels_dev",
+    "vc_dbscan_levels", "vc_dbscan_levels_dev", "vc_sharded_dbscan_levels", "vc_sharded_dbscan_levels_dev",
 ]
-LEVELS_MAX = 64           # VC_LEVELS_MAX: cluster_levels takes max_radius 0 .. 63
+LEVELS_MAX = 64           # VC_LEVELS_MAX: cluster_levels and dbscan_levels take max_radius 0 .. 63
+CORE_NEVER = 0xFFFFFFFF   # VC_CORE_NEVER: dbscan_levels' core_dist of a record with fewer than min_pts records within max_radius
 MAX_SHARDS = 16
 EXCHANGE_AUTO, EXCHANGE_PEER_COPY, EXCHANGE_RCCL = 0, 1, 2
 
@@ -93,6 +95,15 @@ class VcDbscanStats(C.Structure):
 
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class VcDbscanLevelsStats(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64 * LEVELS_MAX), ("n_clusters", C.c_uint64 * LEVELS_MAX), ("n_core", C.c_uint64 * LEVELS_MAX),
+                ("n_border", C.c_uint64 * LEVELS_MAX), ("n_noise", C.c_uint64 * LEVELS_MAX)]
+
+    def as_dict(self, max_radius):
+        """{field: uint64 [max_radius + 1]}"""
+        return {name: np.array(getattr(self, name)[:max_radius + 1], dtype=np.uint64) for name, _ in self._fields_}
 
 
 class VcTiming(C.Structure):
@@ -213,6 +224,10 @@ def load_library():
     L.vc_cluster_levels_dev.argtypes = [vp, u32, u32, u32, u64, vp, vp, vp]
     L.vc_sharded_cluster_levels.argtypes = [vp, u32, u32, u32, u64, vp, vp]
     L.vc_sharded_cluster_levels_dev.argtypes = [vp, u32, u32, u32, u64, vp, vp, vp]
+    L.vc_dbscan_levels.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp]
+    L.vc_dbscan_levels_dev.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp]
+    L.vc_sharded_dbscan_levels.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp]
+    L.vc_sharded_dbscan_levels_dev.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -339,6 +354,22 @@ def _dbscan_radius_dev(self, fn, radius, min_pts, d_labels, d_degrees, mode, bat
     st = VcDbscanStats()
     self._check(fn(self._h, radius, min_pts, mode, batch, d_labels, d_degrees, C.byref(st), stream))
     return st.as_dict()
+
+
+def _dbscan_levels(self, fn, max_radius, min_pts, mode, batch):
+    """shared by Engine.dbscan_levels and ShardedEngine.dbscan_levels: (labels [max_radius + 1, N] uint32, core_dist [N] uint32,
+    stats dict of [max_radius + 1] arrays)"""
+    n = len(self)
+    labels, core_dist = np.empty((max_radius + 1, n), dtype=np.uint32), np.empty(n, dtype=np.uint32)
+    st = VcDbscanLevelsStats()
+    self._check(fn(self._h, max_radius, min_pts, mode, batch, _p(labels), _p(core_dist), C.byref(st)))
+    return labels, core_dist, st.as_dict(max_radius)
+
+
+def _dbscan_levels_dev(self, fn, max_radius, min_pts, d_labels, d_core_dist, mode, batch, stream):
+    st = VcDbscanLevelsStats()
+    self._check(fn(self._h, max_radius, min_pts, mode, batch, d_labels, d_core_dist, C.byref(st), stream))
+    return st.as_dict(max_radius)
 
 
 # vc_group, field for field
@@ -662,6 +693,20 @@ class Engine:
         the handle); both valid in `stream` order.  Returns the stats dict."""
         return _dbscan_radius_dev(self, self._L.vc_dbscan_radius_dev, radius, min_pts, d_labels, d_degrees, mode, batch, stream)
 
+    def dbscan_levels(self, max_radius, min_pts, mode=MODE_LINEAR, batch=0):
+        """vc_dbscan_levels: dbscan_radius at EVERY radius 0 .. max_radius (< LEVELS_MAX) from one walk of the radius search.
+        Returns (labels [max_radius + 1, N], core_dist [N], stats): row r equals dbscan_radius(r, min_pts)'s labels; core_dist[i] =
+        the distance to record i's min_pts-th nearest record, itself counted, or CORE_NEVER if there is none within max_radius --
+        record i is a core at level r iff core_dist[i] <= r; stats: dict of n_pairs (the pairs at distance exactly d), n_clusters,
+        n_core, n_border, n_noise, max_radius + 1 entries each.  There is no incremental form.  retain(labels[r], RETAIN_ROOTS)
+        takes any one level."""
+        return _dbscan_levels(self, self._L.vc_dbscan_levels, max_radius, min_pts, mode, batch)
+
+    def dbscan_levels_dev(self, max_radius, min_pts, d_labels, d_core_dist=None, mode=MODE_MIH_EXACT, batch=0, stream=None):
+        """vc_dbscan_levels_dev: d_labels = the raw device address of (max_radius + 1) * len(self) uint32, level-major; d_core_dist
+        = that of len(self) uint32 (None: scratch of the handle); both valid in `stream` order.  Returns the stats dict."""
+        return _dbscan_levels_dev(self, self._L.vc_dbscan_levels_dev, max_radius, min_pts, d_labels, d_core_dist, mode, batch, stream)
+
     def group_summary(self, labels):
         """vc_group_summary: the groups of equal labels (any of the clustering calls' output, or any partition with values in the resident
         id range) summarised.  Returns (groups, centroids, rep_labels, group_index): groups = structured array GROUP_DTYPE, one entry per
@@ -905,6 +950,20 @@ class ShardedEngine:
         """vc_sharded_dbscan_radius_dev: d_labels / d_degrees = the raw device addresses of len(self) uint32 each on the root device (d_degrees None: scratch of
         the handle); both valid in `stream` order.  Returns the stats dict."""
         return _dbscan_radius_dev(self, self._L.vc_sharded_dbscan_radius_dev, radius, min_pts, d_labels, d_degrees, mode, batch, stream)
+
+    def dbscan_levels(self, max_radius, min_pts, mode=MODE_LINEAR, batch=0):
+        """vc_sharded_dbscan_levels: dbscan_radius at EVERY radius 0 .. max_radius (< LEVELS_MAX) from one walk of the radius search.
+        Returns (labels [max_radius + 1, N], core_dist [N], stats): row r equals dbscan_radius(r, min_pts)'s labels; core_dist[i] =
+        the distance to record i's min_pts-th nearest record, itself counted, or CORE_NEVER if there is none within max_radius --
+        record i is a core at level r iff core_dist[i] <= r; stats: dict of n_pairs (the pairs at distance exactly d), n_clusters,
+        n_core, n_border, n_noise, max_radius + 1 entries each.  There is no incremental form.  retain(labels[r], RETAIN_ROOTS)
+        takes any one level."""
+        return _dbscan_levels(self, self._L.vc_sharded_dbscan_levels, max_radius, min_pts, mode, batch)
+
+    def dbscan_levels_dev(self, max_radius, min_pts, d_labels, d_core_dist=None, mode=MODE_MIH_EXACT, batch=0, stream=None):
+        """vc_sharded_dbscan_levels_dev: d_labels = the raw device address of (max_radius + 1) * len(self) uint32 on the root device, level-major; d_core_dist
+        = that of len(self) uint32 (None: scratch of the handle); both valid in `stream` order.  Returns the stats dict."""
+        return _dbscan_levels_dev(self, self._L.vc_sharded_dbscan_levels_dev, max_radius, min_pts, d_labels, d_core_dist, mode, batch, stream)
 
     def group_summary(self, labels):
         """vc_sharded_group_summary: the groups of equal labels (any of the clustering calls' output, or any partition with values in the resident

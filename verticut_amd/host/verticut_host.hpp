@@ -133,6 +133,10 @@ class Backend {
   // labels[i] = the smallest core id of a core's component, the label of a border's smallest-id core neighbour, the own id for noise
   // (vc_dbscan_radius / vc_sharded_dbscan_radius); retain() with VC_RETAIN_ROOTS keeps one record per cluster and the noise
   virtual int dbscan_radius(uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats) = 0;
+  // the same at every radius 0 .. max_radius from one walk: labels is level-major, (max_radius + 1) x size(), row r = dbscan_radius(r,
+  // min_pts); core_dist[i] (may be null) = the distance to record i's min_pts-th nearest record, itself counted, VC_CORE_NEVER for
+  // none within max_radius -- a core at level r iff core_dist[i] <= r (vc_dbscan_levels / vc_sharded_dbscan_levels)
+  virtual int dbscan_levels(uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* core_dist, vc_dbscan_levels_stats* stats) = 0;
   // the groups of equal labels summarised (vc_group_summary / vc_sharded_group_summary): sizes, per-bit majority codes, the member
   // nearest each -- retain() of rep_labels with VC_RETAIN_ROOTS keeps exactly these representatives
   virtual int group_summary(const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels, uint32_t* group_index,
@@ -202,6 +206,9 @@ class Engine : public Backend {
   }
   int dbscan_radius(uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats) override {
     return vc_dbscan_radius(h_, radius, min_pts, mode, batch, labels, degrees, stats);
+  }
+  int dbscan_levels(uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* core_dist, vc_dbscan_levels_stats* stats) override {
+    return vc_dbscan_levels(h_, max_radius, min_pts, mode, batch, labels, core_dist, stats);
   }
   int group_summary(const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels, uint32_t* group_index,
                     uint64_t* n_groups) override {
@@ -299,6 +306,9 @@ class ShardedEngine : public Backend {
   }
   int dbscan_radius(uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats) override {
     return vc_sharded_dbscan_radius(h_, radius, min_pts, mode, batch, labels, degrees, stats);
+  }
+  int dbscan_levels(uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* core_dist, vc_dbscan_levels_stats* stats) override {
+    return vc_sharded_dbscan_levels(h_, max_radius, min_pts, mode, batch, labels, core_dist, stats);
   }
   int group_summary(const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels, uint32_t* group_index,
                     uint64_t* n_groups) override {
