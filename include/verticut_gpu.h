@@ -659,6 +659,72 @@ int vc_retain_dev(vc_engine* e, const uint32_t* d_sel, uint32_t kind, uint32_t* 
  * the map; waits for them. */
 int vc_retain(vc_engine* e, const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept);
 
+/* "Which of my K codes is each record nearest to": the assign step of a vocabulary / coarse quantiser over the binary codes, and the
+ * way to put records into EXISTING groups -- after vc_add_codes, `first = n_old, count = N - n_old` against the centroids of
+ * vc_group_summary* is the companion of vc_update_index.  The reference has nothing of the kind; the call replaces a second handle
+ * that holds the centres, vc_get_codes_dev and vc_search_knn_dev(k = 1, VC_MODE_LINEAR) in batches.
+ * INPUT: centres, n_centres rows of bits / 8 bytes in the byte layout of vc_add_codes / the centroids of vc_group_summary* (8-byte
+ * aligned in the device form); the records id_base + first .. id_base + first + count - 1 -- ordinals, used as n_labelled is.
+ * OUTPUT: out[j] = c | (uint64_t)dist << 32 for record id_base + first + j: the project's packed result with the centre's INDEX in the
+ * id field.  dist is the full Hamming distance to centre c, and c is the centre with the smallest (dist, index): a tie in distance
+ * goes to the smaller index.  Hence out[j] is bit for bit row j of vc_search_knn(k = 1, VC_MODE_LINEAR) on a handle that holds the
+ * centres with id_base = 0.
+ * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle, null centres, n_centres == 0, first + count >
+ * N, null out with count > 0.  count == 0 returns VC_OK and nothing is read or written.  No index is needed and a stale one does not
+ * matter: only the codes are read.
+ * The result is a function of the codes, the centres and the range only: no knob, grid shape, shard layout or earlier call changes a
+ * bit of it.
+ * How: the transposed data flow of the verify kernel.  A thread keeps a few records in registers for the whole launch and the centres
+ * stream past in LDS tiles (VC_ASSIGN_TILE, environment, read at vc_create: centres per tile, default all that fit in 16 KiB); per
+ * pair and 64-bit word two XORs and two population counts, a strict < in ascending centre order.  When `count` is too small to fill
+ * the device and the centres are many, they are cut into slices (VC_ASSIGN_SLICES forces their number) that meet in a 64-bit atomicMin
+ * on `out`, set to all ones by an init launch -- the minimum of the packed value IS the (dist, index) rule, so this stays exact.
+ * Device form: everything is enqueued on `stream`, the host waits for nothing; d_centres must stay untouched until the call has run.
+ * The call is ordered behind the handle's previous call whatever its stream, like every call.  No scratch. */
+int vc_assign_nearest_dev(vc_engine* e, const void* d_centres, uint32_t n_centres, uint64_t first, uint64_t count, uint64_t* d_out, void* stream);
+/* The same for centres and out in host memory: the device form on the engine's stream on staged copies (a grow-only buffer of the
+ * handle, shared with vc_kmajority's staging; every word written before it is read); waits for the result. */
+int vc_assign_nearest(vc_engine* e, const void* centres, uint32_t n_centres, uint64_t first, uint64_t count, uint64_t* out);
+
+/* A grouping with a CHOSEN number of groups: Lloyd iterations in Hamming space ("k-majority") over all N resident records -- assign
+ * every record to the nearest centre (vc_assign_nearest), then move each centre to the per-bit majority of its members (the centroid
+ * of vc_group_summary).  THE RULE, exact in integers:
+ *   C = seeds; prev = none
+ *   for t = 0 .. max_iters - 1:
+ *       a = assign_nearest(C) over all N records; cost[t] = sum of dist(a)
+ *       n_changed[t] = N if t == 0 else #{i : index(a[i]) != prev[i]};  n_iters = t + 1
+ *       if n_changed[t] == 0: converged = 1; break
+ *       for every centre c with at least one member in a: C[c] = per-bit STRICT majority of its members (a tie gives 0)
+ *       a centre without a member keeps its code;  prev = index(a)
+ *   assign = assign_nearest(C)            -- always: the returned pair satisfies assign == vc_assign_nearest(centres)
+ *   labels[i] = id_base + index(assign[i]) -- a legal input of vc_group_summary* and, with its rep_labels, of vc_retain*
+ * It terminates: the potential (sum of distances, sum of centre indices), ordered lexicographically, is never raised by an update in
+ * its first term and is lowered strictly by an assign round that changes anything.
+ * centres: in, the n_centres seeds (the caller chooses them: there is no device-side seeding); out, the final centres.  assign: N
+ * packed words.  labels: N words, may be NULL.  stats: host memory in both forms, may be NULL.
+ * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle, null centres or assign, n_centres == 0,
+ * n_centres > N with N > 0 (the labels must be resident ids), max_iters > VC_KMAJ_MAX_ITERS.  N == 0 gives VC_OK and zero stats;
+ * nothing is read or written.  max_iters == 0 is just the final assign: n_iters = 0, converged = 0.
+ * Device form: everything is enqueued on `stream`; the host waits once per round for 16 bytes (cost and n_changed, reduced on the
+ * device), once inside each update (vc_group_summary's wait) and once at the end for cost_final and n_empty.  Outputs are valid in
+ * stream order.  Scratch: two grow-only buffers of the handle, this call's own (12 N bytes, 28 + bits / 8 bytes per centre, the
+ * counters; the host form's staging), plus those of vc_group_summary*; every word written before it is read.
+ * The result is a function of the codes and the seeds only: no knob, window, shard layout or earlier call changes a bit of it. */
+#define VC_KMAJ_MAX_ITERS 64
+typedef struct vc_kmajority_stats {      /* 1048 bytes */
+  uint32_t n_iters, converged;           /* assign+update rounds run (<= max_iters); 1 = a round changed no assignment */
+  uint64_t n_empty;                      /* centres without a member in the returned assignment */
+  uint64_t cost_final;                   /* sum of the returned assignment's distances */
+  uint64_t cost[VC_KMAJ_MAX_ITERS];      /* [t] = sum of distances of round t's assignment; 0 from n_iters on */
+  uint64_t n_changed[VC_KMAJ_MAX_ITERS]; /* [t] = records whose centre index differs from round t-1's; [0] = N */
+} vc_kmajority_stats;
+int vc_kmajority_dev(vc_engine* e, uint32_t n_centres, uint32_t max_iters, void* d_centres, uint64_t* d_assign, uint32_t* d_labels,
+                     vc_kmajority_stats* stats, void* stream);
+/* The same for centres, assign and labels in host memory: the seeds staged, the device form on the engine's stream, the three arrays
+ * come home; waits for them. */
+int vc_kmajority(vc_engine* e, uint32_t n_centres, uint32_t max_iters, void* centres, uint64_t* assign, uint32_t* labels,
+                 vc_kmajority_stats* stats);
+
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
  * seconds); the affected queries kept d_counts[i] == UINT32_MAX.  0 in normal operation.  Synchronises the stream.
@@ -852,6 +918,21 @@ int vc_sharded_group_summary_dev(vc_sharded* h, const uint32_t* d_labels, uint64
                                  uint32_t* d_rep_labels, uint32_t* d_group_index, uint64_t* n_groups, void* stream);
 int vc_sharded_group_summary(vc_sharded* h, const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels,
                              uint32_t* group_index, uint64_t* n_groups);
+/* Nearest of K codes over all shards: contract and errors as vc_assign_nearest_dev / vc_assign_nearest, with N = vc_sharded_size,
+ * `first` an ordinal of the whole store and every pointer of the device form on the ROOT device, `stream` a stream of that device.
+ * The centres reach every other device by one peer copy; every non-empty shard assigns the part of the range it owns on its own
+ * device (vc_assign_nearest_dev of its engine); a remote shard's slice of `out` travels to the root by one hipMemcpyPeerAsync behind
+ * its lane's event, a root-device shard writes in place.  Nothing is waited for.  The result equals the single engine's bit for bit. */
+int vc_sharded_assign_nearest_dev(vc_sharded* h, const void* d_centres, uint32_t n_centres, uint64_t first, uint64_t count, uint64_t* d_out,
+                                  void* stream);
+int vc_sharded_assign_nearest(vc_sharded* h, const void* centres, uint32_t n_centres, uint64_t first, uint64_t count, uint64_t* out);
+/* k-majority over all shards: rule, errors, waits and scratch as vc_kmajority_dev / vc_kmajority with the pointers of the device form on
+ * the ROOT device.  The same round driver runs on the root; the assign step is vc_sharded_assign_nearest_dev, the update step
+ * vc_sharded_group_summary_dev's.  Centres, assign, labels and statistics equal the single engine's bit for bit. */
+int vc_sharded_kmajority_dev(vc_sharded* h, uint32_t n_centres, uint32_t max_iters, void* d_centres, uint64_t* d_assign, uint32_t* d_labels,
+                             vc_kmajority_stats* stats, void* stream);
+int vc_sharded_kmajority(vc_sharded* h, uint32_t n_centres, uint32_t max_iters, void* centres, uint64_t* assign, uint32_t* labels,
+                         vc_kmajority_stats* stats);
 /* borrow shard g's engine (bucket views, timing, files); its id range is [*first_id, *first_id + *n_ids) */
 int vc_sharded_shard(vc_sharded* h, uint32_t shard, vc_engine** e, uint64_t* first_id, uint64_t* n_ids);
 

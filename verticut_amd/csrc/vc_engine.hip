@@ -88,6 +88,9 @@ struct vc_engine {
   // label groups summarised (vc_group_summary*): the sort and numbering arrays, the row buffer with the big groups' tables, the host
   // form's staging (VC_GROUPS_*); its own, shared with no other call, every word written before it is read
   uint8_t* d_grp[VC_GROUPS_BUFS] = {nullptr, nullptr, nullptr};  size_t grp_bytes[VC_GROUPS_BUFS] = {0, 0, 0};
+  // nearest of K codes and k-majority (vc_assign_nearest*, vc_kmajority*): the round driver's arrays, the host forms' staging
+  // (VC_KMAJ_*); their own, every word written before it is read
+  uint8_t* d_kmaj[VC_KMAJ_BUFS] = {nullptr, nullptr};  size_t kmaj_bytes[VC_KMAJ_BUFS] = {0, 0};
   CleanState clean;                                       // the last kernel of a linear step hands d_state back zeroed: no memset per step
   uint32_t scan_event_tick = 0;                           // VC_FLAG_LEAN_TIMING: only every timing_sample-th verify launch is timed
   VcKnobs knobs;                                          // environment knobs, read once at vc_create
@@ -198,6 +201,8 @@ void read_knobs(VcKnobs* k) {
     const uint64_t w = strtoull(v, nullptr, 10);
     if (vc_group_window_valid(w)) k->group_window = (uint32_t)w;
   }
+  if (const char* v = getenv("VC_ASSIGN_TILE")) k->assign_tile = (uint32_t)strtoul(v, nullptr, 10);
+  if (const char* v = getenv("VC_ASSIGN_SLICES")) k->assign_slices = (uint32_t)strtoul(v, nullptr, 10);
 }
 
 static int bind_device(vc_engine* e) {
@@ -394,6 +399,7 @@ int vc_destroy(vc_engine* e) {
   (void)hipFree(e->d_wcd);
   (void)hipFree(e->d_wstat);
   for (uint8_t* b : e->d_grp) (void)hipFree(b);
+  for (uint8_t* b : e->d_kmaj) (void)hipFree(b);
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->last_call) (void)hipEventDestroy(e->last_call);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -1763,6 +1769,79 @@ int vc_group_summary(vc_engine* e, const uint32_t* labels, uint64_t groups_cap, 
   rc = vc_groups_run_host(groups_args(e, nullptr, groups_cap, nullptr, nullptr, nullptr, nullptr), fetch, labels, groups, centroids, rep_labels, group_index,
                           n_groups, s, &err);
   return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;   // (an allocation failure has left its own text)
+}
+
+}  // extern "C"
+
+// ---- nearest of K codes and k-majority (vc_assign.hip) ----------------------------------------------------------------------------
+static int check_assign_args(vc_engine* e, const void* centres, uint32_t n_centres, uint64_t first, uint64_t count, const uint64_t* out) {
+  if (!e || !centres || n_centres == 0 || first > e->n || count > e->n - first || (!out && count)) return VC_ERR_INVALID;
+  return VC_OK;
+}
+static int check_kmajority_args(vc_engine* e, uint32_t n_centres, uint32_t max_iters, const void* centres, const uint64_t* assign) {
+  if (!e || !centres || !assign || n_centres == 0 || (e->n && n_centres > e->n) || max_iters > VC_KMAJ_MAX_ITERS) return VC_ERR_INVALID;
+  return VC_OK;
+}
+static std::function<void*(int, size_t)> kmaj_alloc(vc_engine* e) {
+  return [e](int which, size_t bytes) -> void* { return grow(e, &e->d_kmaj[which], &e->kmaj_bytes[which], bytes) ? nullptr : e->d_kmaj[which]; };
+}
+// the records [first, first + count) against the centres on e->stream, inside the caller's StreamCall
+static VcAssignAll assign_range(vc_engine* e, uint32_t n_centres, uint64_t first, uint64_t count) {
+  return [e, n_centres, first, count](const uint64_t* d_centres, uint64_t* d_out) -> int {
+    VC_HIP(e, vc_launch_assign(e->d_cols, e->stride, e->W, first, count, d_centres, n_centres, d_out, e->n_cu, &e->knobs, e->stream));
+    return VC_OK;
+  };
+}
+static VcGroupsFetch groups_fetch(vc_engine* e) {
+  hipStream_t s = e->stream;
+  return [e, s](const uint32_t* d_ids, uint32_t nq, uint64_t* d_rows) { return vc_get_codes_dev(e, d_ids, nq, d_rows, nullptr, (void*)s); };
+}
+
+extern "C" {
+
+int vc_assign_nearest_dev(vc_engine* e, const void* d_centres, uint32_t n_centres, uint64_t first, uint64_t count, uint64_t* d_out, void* stream) {
+  int rc = check_assign_args(e, d_centres, n_centres, first, count, d_out);
+  if (rc || count == 0) return rc;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, caller_stream(e, stream));
+  return assign_range(e, n_centres, first, count)((const uint64_t*)d_centres, d_out);
+}
+
+int vc_assign_nearest(vc_engine* e, const void* centres, uint32_t n_centres, uint64_t first, uint64_t count, uint64_t* out) {
+  int rc = check_assign_args(e, centres, n_centres, first, count, out);
+  if (rc || count == 0) return rc;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, e->stream);
+  std::string err;
+  rc = vc_assign_run_host(kmaj_alloc(e), e->W, centres, n_centres, count, out, assign_range(e, n_centres, first, count), e->stream, &err);
+  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
+}
+
+int vc_kmajority_dev(vc_engine* e, uint32_t n_centres, uint32_t max_iters, void* d_centres, uint64_t* d_assign, uint32_t* d_labels,
+                     vc_kmajority_stats* stats, void* stream) {
+  int rc = check_kmajority_args(e, n_centres, max_iters, d_centres, d_assign);
+  if (rc) return rc;
+  if (stats) *stats = vc_kmajority_stats{};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, caller_stream(e, stream));
+  std::string err;
+  rc = vc_kmajority_run(VcKmajArgs{n_centres, max_iters, (uint64_t*)d_centres, d_assign, d_labels, kmaj_alloc(e)}, groups_args(e, nullptr, 0, nullptr, nullptr, nullptr, nullptr),
+                        assign_range(e, n_centres, 0, e->n), groups_fetch(e), stats, e->stream, &err);
+  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
+}
+
+int vc_kmajority(vc_engine* e, uint32_t n_centres, uint32_t max_iters, void* centres, uint64_t* assign, uint32_t* labels, vc_kmajority_stats* stats) {
+  int rc = check_kmajority_args(e, n_centres, max_iters, centres, assign);
+  if (rc) return rc;
+  if (stats) *stats = vc_kmajority_stats{};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, e->stream);
+  std::string err;
+  rc = vc_kmajority_run_host(VcKmajArgs{n_centres, max_iters, nullptr, nullptr, nullptr, kmaj_alloc(e)}, groups_args(e, nullptr, 0, nullptr, nullptr, nullptr, nullptr),
+                             assign_range(e, n_centres, 0, e->n), groups_fetch(e), centres, assign, labels, stats, e->stream, &err);
+  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
 }
 
 }  // extern "C"

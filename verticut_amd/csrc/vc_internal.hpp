@@ -45,6 +45,8 @@ struct VcKnobs {
   int mih_retain = 1;                         // VC_MIH_RETAIN=0: vc_retain* compacts the columns and rebuilds the whole index (A/B runs, tests) instead of filtering it
   uint32_t group_window = 1u << 20;           // VC_GROUP_WINDOW: sorted positions per gather of vc_group_summary* (a multiple of 1024, else ignored)
   bool scan_shape_trace = false;              // VC_SCAN_SHAPE_TRACE=1 (dev/tests): every verify launch names the instantiation it launched on stderr
+  uint32_t assign_tile = 0;                   // VC_ASSIGN_TILE (tests): centres per LDS tile of vc_assign_kernel (0 = all that fit, vc_assign_plan.hpp)
+  uint32_t assign_slices = 0;                 // VC_ASSIGN_SLICES (tests): forces the number of centre slices of a vc_assign_kernel launch (0 = the plan's)
 };
 void read_knobs(VcKnobs* k);   // vc_engine.hip: the one place that reads the environment (once per engine / sharded handle)
 
@@ -282,6 +284,33 @@ int vc_groups_run(const VcGroupsArgs& a, const VcGroupsFetch& fetch, uint64_t* n
 // the same for host pointers: labels staged, the outputs that are wanted staged and copied home, waited for (a's pointers are ignored)
 int vc_groups_run_host(VcGroupsArgs a, const VcGroupsFetch& fetch, const uint32_t* labels, vc_group* groups, void* centroids, uint32_t* rep_labels,
                        uint32_t* group_index, uint64_t* n_groups, hipStream_t s, std::string* err);
+// ---- vc_assign.hip: nearest of K given codes (vc_assign_nearest*) and the k-majority rounds on top of it (vc_kmajority*).  The plan
+// arithmetic is vc_assign_plan.hpp.
+// d_out[j] = c | dist << 32, c the centre (of K rows [W], 8-byte aligned) with the smallest (distance, index) for local record
+// first + j, j < count; the caller has checked first + count <= the records behind cols.  One launch, or an init launch and one
+// whose centre slices meet in atomicMin; nothing is waited for, no scratch.
+hipError_t vc_launch_assign(const uint64_t* cols, uint64_t stride, uint32_t W, uint64_t first, uint64_t count, const uint64_t* d_centres, uint32_t K,
+                            uint64_t* d_out, uint32_t n_cu, const VcKnobs* knobs, hipStream_t s);
+enum { VC_KMAJ_WORK, VC_KMAJ_STAGE, VC_KMAJ_BUFS };   // the round driver's arrays; the host forms' staging (alloc as VcGroupsArgs::alloc)
+// the handle's assign over a range fixed by the caller (all N records for the rounds), enqueued on the call's stream, nothing waited for
+typedef std::function<int(const uint64_t* d_centres, uint64_t* d_out)> VcAssignAll;
+// vc_assign_nearest for host pointers: centres staged, `run` into a staged output of `count` words, which comes home; waits for it
+int vc_assign_run_host(const std::function<void*(int which, size_t bytes)>& alloc, uint32_t W, const void* centres, uint32_t K, uint64_t count, uint64_t* out,
+                       const VcAssignAll& run, hipStream_t s, std::string* err);
+struct VcKmajArgs {
+  uint32_t n_centres, max_iters;   // checked by the caller: 1 <= n_centres <= N, max_iters <= VC_KMAJ_MAX_ITERS
+  uint64_t* d_centres;             // in: seeds, out: final
+  uint64_t* d_assign;              // N packed
+  uint32_t* d_labels;              // N, nullable
+  std::function<void*(int which, size_t bytes)> alloc;   // the handle's grow-only buffers VC_KMAJ_*
+};
+// One driver for both handle kinds, on s with the device of the buffers current.  g: the handle's VcGroupsArgs (n, id_base, W, window,
+// alloc -- the pointers are set here); one wait per round and vc_groups_run's, one at the end.  stats nullable.
+int vc_kmajority_run(const VcKmajArgs& k, VcGroupsArgs g, const VcAssignAll& assign_all, const VcGroupsFetch& fetch, vc_kmajority_stats* stats, hipStream_t s,
+                     std::string* err);
+// the same for host pointers (k's pointers are ignored): seeds staged, centres, assign and labels (nullable) come home, waited for
+int vc_kmajority_run_host(VcKmajArgs k, const VcGroupsArgs& g, const VcAssignAll& assign_all, const VcGroupsFetch& fetch, void* centres, uint64_t* assign,
+                          uint32_t* labels, vc_kmajority_stats* stats, hipStream_t s, std::string* err);
 // ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
 struct VcKeepSet;
 #define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)

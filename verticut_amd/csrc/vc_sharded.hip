@@ -102,6 +102,8 @@ enum LaneBuf {
   LANE_AUX,    // union scan of VC_FLAG_GLOBAL_STOP: its per-query inputs and outputs here (GsScanBlock, gs_lane_block)
   LANE_IDS,    // queries named by id: the batch's ids on this device (peer copy from the root)
   LANE_IDGATH, // [G][slot]: the gathered words | found words of shard g at slot g (vc_ids_slot_words); on the root all shards' slots
+  LANE_ACENT,  // nearest of K codes: the centres on this device (peer copy from the root)
+  LANE_AOUT,   // nearest of K codes: the packed results of this device's shards, one after the other, before they travel to the root
   LANE_BUFS
 };
 struct Lane {
@@ -145,6 +147,9 @@ enum RootBuf {
   // label groups summarised: the sort and numbering arrays, the row buffer with the big groups' tables, the host form's staging
   // (GRP_SCRATCH + VC_GROUPS_*); its own, every word written before it is read
   GRP_SCRATCH, GRP_WORK, GRP_STAGE,
+  // nearest of K codes and k-majority: the round driver's arrays, the host forms' staging (KM_WORK + VC_KMAJ_*); their own, every word
+  // written before it is read
+  KM_WORK, KM_STAGE,
   ROOT_BUFS
 };
 
@@ -2595,6 +2600,144 @@ int vc_sharded_group_summary(vc_sharded* h, const uint32_t* labels, uint64_t gro
   std::string err;
   const int rc = vc_groups_run_host(sharded_groups_args(h, nullptr, groups_cap, nullptr, nullptr, nullptr, nullptr), sharded_groups_fetch(h, S), labels, groups,
                                     centroids, rep_labels, group_index, n_groups, S, &err);
+  return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
+}
+
+}  // extern "C"
+
+// ---- nearest of K codes and k-majority over the shards: vc_assign.hip's driver on the root, the assign step on every shard's device ----
+static int check_sharded_assign_args(vc_sharded* h, const void* centres, uint32_t n_centres, uint64_t first, uint64_t count, const uint64_t* out) {
+  if (!h || !centres || n_centres == 0 || first > h->n || count > h->n - first || (!out && count)) return VC_ERR_INVALID;
+  return VC_OK;
+}
+static int check_sharded_kmajority_args(vc_sharded* h, uint32_t n_centres, uint32_t max_iters, const void* centres, const uint64_t* assign) {
+  if (!h || !centres || !assign || n_centres == 0 || (h->n && n_centres > h->n) || max_iters > VC_KMAJ_MAX_ITERS) return VC_ERR_INVALID;
+  return VC_OK;
+}
+static std::function<void*(int, size_t)> sharded_kmaj_alloc(vc_sharded* h) {
+  return [h](int which, size_t bytes) -> void* {   // (the root device is current wherever the driver allocates)
+    DevBuf& b = h->buf[KM_WORK + which];
+    return b.grow(h, bytes) ? nullptr : b.p;
+  };
+}
+
+// d_centres / d_out on the root device, valid on S; count > 0.  All enqueued, nothing waited for: the centres reach every other lane
+// by one peer copy behind ev_q, every non-empty shard assigns the part of [first, first + count) it owns on its own device -- a
+// root-device shard straight into d_out, a remote one into its lane's buffer, which one peer copy per shard brings to the root behind
+// the lane's `done` event.  Returns with the root device current.
+static int sharded_assign_range(vc_sharded* h, const uint64_t* d_centres, uint32_t K, uint64_t first, uint64_t count, uint64_t* d_out, hipStream_t S) {
+  const size_t cbytes = (size_t)K * h->nbytes;
+  const uint64_t last = first + count;
+  auto part = [&](uint32_t g, uint64_t* a, uint64_t* b) {   // the store ordinals [a, b) of the range that shard g holds
+    *a = std::max(first, h->lo[g]);
+    *b = std::min(last, h->lo[g] + shard_size(h, g));
+    return *a < *b;
+  };
+  int rc;
+  bool remote = false;
+  for (uint32_t li = 0; li < h->lanes.size(); ++li) {
+    if (li == h->root_lane) continue;
+    Lane& l = h->lanes[li];
+    uint64_t words = 0, a, b;
+    for (uint32_t g : l.shards)
+      if (part(g, &a, &b)) words += b - a;
+    if (!words) continue;
+    remote = true;
+    VS_HIP(h, hipSetDevice(l.dev));
+    if ((rc = l.buf[LANE_ACENT].grow(h, cbytes)) || (rc = l.buf[LANE_AOUT].grow(h, (size_t)words * 8))) return rc;
+  }
+  VS_HIP(h, hipSetDevice(h->root));
+  if (remote) VS_HIP(h, hipEventRecord(h->ev_q, S));
+  for (uint32_t li = 0; li < h->lanes.size(); ++li) {
+    Lane& l = h->lanes[li];
+    const bool is_root = li == h->root_lane;
+    hipStream_t ls = is_root ? S : l.stream;
+    uint64_t at = 0, a, b;
+    bool any = false;
+    for (uint32_t g : l.shards) {
+      if (!part(g, &a, &b)) continue;
+      if (!is_root && !any) {
+        VS_HIP(h, hipSetDevice(l.dev));
+        VS_HIP(h, hipStreamWaitEvent(ls, h->ev_q, 0));   // also orders the lane behind the previous call's copies out of its buffers
+        VS_HIP(h, hipMemcpyPeerAsync(l.buf[LANE_ACENT].p, l.dev, d_centres, h->root, cbytes, ls));
+      }
+      any = true;
+      uint64_t* dst = is_root ? d_out + (a - first) : l.buf[LANE_AOUT].as<uint64_t>() + at;
+      if ((rc = vc_assign_nearest_dev(h->eng[g], is_root ? (const void*)d_centres : l.buf[LANE_ACENT].p, K, a - h->lo[g], b - a, dst, ls)))
+        return sfail(h, rc, "shard %u: %s", g, vc_last_error(h->eng[g]));
+      at += b - a;
+    }
+    if (!is_root && any) {
+      VS_HIP(h, hipSetDevice(l.dev));
+      VS_HIP(h, hipEventRecord(l.done, ls));
+    }
+  }
+  VS_HIP(h, hipSetDevice(h->root));
+  for (uint32_t li = 0; li < h->lanes.size(); ++li) {
+    if (li == h->root_lane) continue;
+    Lane& l = h->lanes[li];
+    uint64_t at = 0, a, b;
+    bool any = false;
+    for (uint32_t g : l.shards) {
+      if (!part(g, &a, &b)) continue;
+      if (!any) VS_HIP(h, hipStreamWaitEvent(S, l.done, 0));
+      any = true;
+      VS_HIP(h, hipMemcpyPeerAsync(d_out + (a - first), h->root, l.buf[LANE_AOUT].as<uint64_t>() + at, l.dev, (size_t)(b - a) * 8, S));
+      at += b - a;
+    }
+  }
+  return VC_OK;
+}
+static VcAssignAll sharded_assign_all(vc_sharded* h, uint32_t K, uint64_t first, uint64_t count, hipStream_t S) {
+  return [h, K, first, count, S](const uint64_t* d_centres, uint64_t* d_out) { return sharded_assign_range(h, d_centres, K, first, count, d_out, S); };
+}
+
+extern "C" {
+
+int vc_sharded_assign_nearest_dev(vc_sharded* h, const void* d_centres, uint32_t n_centres, uint64_t first, uint64_t count, uint64_t* d_out,
+                                  void* stream) {
+  const int rc = check_sharded_assign_args(h, d_centres, n_centres, first, count, d_out);
+  if (rc || count == 0) return rc;
+  return sharded_assign_range(h, (const uint64_t*)d_centres, n_centres, first, count, d_out, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+}
+
+int vc_sharded_assign_nearest(vc_sharded* h, const void* centres, uint32_t n_centres, uint64_t first, uint64_t count, uint64_t* out) {
+  int rc = check_sharded_assign_args(h, centres, n_centres, first, count, out);
+  if (rc || count == 0) return rc;
+  hipStream_t S = h->root_stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  std::string err;
+  rc = vc_assign_run_host(sharded_kmaj_alloc(h), h->nbytes / 8, centres, n_centres, count, out, sharded_assign_all(h, n_centres, first, count, S), S, &err);
+  return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
+}
+
+int vc_sharded_kmajority_dev(vc_sharded* h, uint32_t n_centres, uint32_t max_iters, void* d_centres, uint64_t* d_assign, uint32_t* d_labels,
+                             vc_kmajority_stats* stats, void* stream) {
+  int rc = check_sharded_kmajority_args(h, n_centres, max_iters, d_centres, d_assign);
+  if (rc) return rc;
+  if (stats) *stats = vc_kmajority_stats{};
+  if (h->n == 0) return VC_OK;
+  hipStream_t S = stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  std::string err;
+  rc = vc_kmajority_run(VcKmajArgs{n_centres, max_iters, (uint64_t*)d_centres, d_assign, d_labels, sharded_kmaj_alloc(h)},
+                        sharded_groups_args(h, nullptr, 0, nullptr, nullptr, nullptr, nullptr), sharded_assign_all(h, n_centres, 0, h->n, S),
+                        sharded_groups_fetch(h, S), stats, S, &err);
+  return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
+}
+
+int vc_sharded_kmajority(vc_sharded* h, uint32_t n_centres, uint32_t max_iters, void* centres, uint64_t* assign, uint32_t* labels,
+                         vc_kmajority_stats* stats) {
+  int rc = check_sharded_kmajority_args(h, n_centres, max_iters, centres, assign);
+  if (rc) return rc;
+  if (stats) *stats = vc_kmajority_stats{};
+  if (h->n == 0) return VC_OK;
+  hipStream_t S = h->root_stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  std::string err;
+  rc = vc_kmajority_run_host(VcKmajArgs{n_centres, max_iters, nullptr, nullptr, nullptr, sharded_kmaj_alloc(h)},
+                             sharded_groups_args(h, nullptr, 0, nullptr, nullptr, nullptr, nullptr), sharded_assign_all(h, n_centres, 0, h->n, S),
+                             sharded_groups_fetch(h, S), centres, assign, labels, stats, S, &err);
   return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
 }
 

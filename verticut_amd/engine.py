@@ -49,7 +49,10 @@ EXPORTS = [
     "vc_group_summary", "vc_group_summary_dev", "vc_sharded_group_summary", "vc_sharded_group_summary_dev",
     "vc_cluster_levels", "vc_cluster_levels_dev", "vc_sharded_cluster_levels", "vc_sharded_cluster_levels_dev",
     "vc_dbscan_levels", "vc_dbscan_levels_dev", "vc_sharded_dbscan_levels", "vc_sharded_dbscan_levels_dev",
+    "vc_assign_nearest", "vc_assign_nearest_dev", "vc_sharded_assign_nearest", "vc_sharded_assign_nearest_dev",
+    "vc_kmajority", "vc_kmajority_dev", "vc_sharded_kmajority", "vc_sharded_kmajority_dev",
 ]
+KMAJ_MAX_ITERS = 64       # VC_KMAJ_MAX_ITERS: kmajority takes max_iters 0 .. 64
 LEVELS_MAX = 64           # VC_LEVELS_MAX: cluster_levels and dbscan_levels take max_radius 0 .. 63
 CORE_NEVER = 0xFFFFFFFF   # VC_CORE_NEVER: dbscan_levels' core_dist of a record with fewer than min_pts records within max_radius
 MAX_SHARDS = 16
@@ -104,6 +107,16 @@ class VcDbscanLevelsStats(C.Structure):
     def as_dict(self, max_radius):
         """{field: uint64 [max_radius + 1]}"""
         return {name: np.array(getattr(self, name)[:max_radius + 1], dtype=np.uint64) for name, _ in self._fields_}
+
+
+class VcKmajorityStats(C.Structure):
+    _fields_ = [("n_iters", C.c_uint32), ("converged", C.c_uint32), ("n_empty", C.c_uint64), ("cost_final", C.c_uint64),
+                ("cost", C.c_uint64 * KMAJ_MAX_ITERS), ("n_changed", C.c_uint64 * KMAJ_MAX_ITERS)]
+
+    def as_dict(self):
+        """{n_iters, converged, n_empty, cost_final: int; cost, n_changed: uint64 [KMAJ_MAX_ITERS], zero from n_iters on}"""
+        return {name: (np.array(getattr(self, name)[:], dtype=np.uint64) if name in ("cost", "n_changed") else int(getattr(self, name)))
+                for name, _ in self._fields_}
 
 
 class VcTiming(C.Structure):
@@ -228,6 +241,14 @@ def load_library():
     L.vc_dbscan_levels_dev.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp]
     L.vc_sharded_dbscan_levels.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp]
     L.vc_sharded_dbscan_levels_dev.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp]
+    L.vc_assign_nearest.argtypes = [vp, vp, u32, u64, u64, vp]
+    L.vc_assign_nearest_dev.argtypes = [vp, vp, u32, u64, u64, vp, vp]
+    L.vc_sharded_assign_nearest.argtypes = [vp, vp, u32, u64, u64, vp]
+    L.vc_sharded_assign_nearest_dev.argtypes = [vp, vp, u32, u64, u64, vp, vp]
+    L.vc_kmajority.argtypes = [vp, u32, u32, vp, vp, vp, vp]
+    L.vc_kmajority_dev.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
+    L.vc_sharded_kmajority.argtypes = [vp, u32, u32, vp, vp, vp, vp]
+    L.vc_sharded_kmajority_dev.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -397,6 +418,57 @@ def _group_summary_dev(self, fn, d_labels, groups_cap, d_groups, d_centroids, d_
     g = C.c_uint64(0)
     rc = self._check(fn(self._h, d_labels, groups_cap, d_groups, d_centroids, d_rep_labels, d_group_index, C.byref(g), stream), ok=(VC_OK, VC_ERR_CAPACITY))
     return rc, int(g.value)
+
+
+def _assign_nearest(self, fn, centres, first, count):
+    """shared by Engine.assign_nearest and ShardedEngine.assign_nearest: packed uint64 [count], centre index | distance << 32"""
+    centres = np.ascontiguousarray(centres, dtype=np.uint8).reshape(-1, self.nbytes)
+    if count is None:
+        count = len(self) - first
+    if count < 0:
+        raise VcError(VC_ERR_INVALID, "the range starts behind the last resident record")
+    out = np.empty(count, dtype=np.uint64)
+    self._check(fn(self._h, _p(centres), centres.shape[0], first, count, _p(out) if count else None))
+    return out
+
+
+def _get_codes(self, ids):
+    """uint8 [len(ids), bits / 8]: the codes of resident ids, by get_code"""
+    out = np.empty((len(ids), self.nbytes), dtype=np.uint8)
+    for j, gid in enumerate(ids):
+        code = self.get_code(int(gid))
+        if code is None:
+            raise VcError(VC_NOT_FOUND, "id %d is not resident" % int(gid))
+        out[j] = code
+    return out
+
+
+def _kmajority(self, fn, k, seed_ids, seeds, max_iters):
+    """shared by Engine.kmajority and ShardedEngine.kmajority: (centres uint8 [k, bits / 8], assign uint64 [N], labels uint32 [N],
+    stats dict).  seeds: the k start codes; else seed_ids: the ids whose codes are the seeds; else k ids spread evenly over the store."""
+    n = len(self)
+    if seeds is not None:
+        centres = np.array(seeds, dtype=np.uint8).reshape(-1, self.nbytes)
+        if centres.shape[0] != k:
+            raise VcError(VC_ERR_INVALID, "the seeds must be k codes")
+    else:
+        if seed_ids is None:
+            if not 0 < k <= max(n, 1) or n == 0:
+                raise VcError(VC_ERR_INVALID, "k must be in 1 .. the number of resident records")
+            seed_ids = self.id_base + np.arange(k, dtype=np.int64) * n // k
+        if len(seed_ids) != k:
+            raise VcError(VC_ERR_INVALID, "the seed ids must be k ids")
+        centres = _get_codes(self, seed_ids)
+    assign, labels = np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint32)
+    st = VcKmajorityStats()
+    self._check(fn(self._h, k, max_iters, _p(centres), _p(assign), _p(labels), C.byref(st)))
+    return centres, assign, labels, st.as_dict()
+
+
+def _kmajority_dev(self, fn, k, d_centres, d_assign, d_labels, max_iters, stream):
+    st = VcKmajorityStats()
+    self._check(fn(self._h, k, max_iters, d_centres, d_assign, d_labels, C.byref(st), stream))
+    return st.as_dict()
 
 
 def _retain(self, fn, sel, kind, with_map):
@@ -720,6 +792,33 @@ class Engine:
         (rc, G) with rc VC_OK, or VC_ERR_CAPACITY when G > groups_cap (nothing was written)."""
         return _group_summary_dev(self, self._L.vc_group_summary_dev, d_labels, groups_cap, d_groups, d_centroids, d_rep_labels, d_group_index, stream)
 
+    def get_codes(self, ids):
+        """the codes of resident ids, uint8 [len(ids), bits / 8]"""
+        return _get_codes(self, ids)
+
+    def assign_nearest(self, centres, first=0, count=None):
+        """vc_assign_nearest: for the records id_base + first .. + count - 1 (default: to the end) the nearest of the given codes
+        (uint8 [K, bits / 8]) as packed uint64, centre index | distance << 32; a tie in distance goes to the smaller index -- row for row
+        search_knn(k=1, MODE_LINEAR) of an engine that holds the centres with id_base 0.  first=n_old after add_codes assigns the new records."""
+        return _assign_nearest(self, self._L.vc_assign_nearest, centres, first, count)
+
+    def assign_nearest_dev(self, d_centres, n_centres, first, count, d_out, stream=None):
+        """vc_assign_nearest_dev: raw device addresses; d_out valid in `stream` order, nothing is waited for"""
+        self._check(self._L.vc_assign_nearest_dev(self._h, d_centres, n_centres, first, count, d_out, stream))
+
+    def kmajority(self, k, seed_ids=None, seeds=None, max_iters=KMAJ_MAX_ITERS):
+        """vc_kmajority: Hamming k-means over all resident records -- assign to the nearest centre, move each centre to the per-bit
+        strict majority of its members, until a round changes nothing or max_iters rounds ran.  Returns (centres, assign, labels, stats):
+        assign == assign_nearest(centres), labels = id_base + centre index (an input of group_summary), stats a dict of n_iters,
+        converged, n_empty, cost_final and the per-round cost and n_changed.  The seeds are `seeds` (k codes), the codes of `seed_ids`,
+        or by default of k ids spread evenly over the store."""
+        return _kmajority(self, self._L.vc_kmajority, k, seed_ids, seeds, max_iters)
+
+    def kmajority_dev(self, k, d_centres, d_assign, d_labels=None, max_iters=KMAJ_MAX_ITERS, stream=None):
+        """vc_kmajority_dev: raw device addresses -- d_centres holds the seeds on entry and the final centres afterwards;
+        outputs valid in `stream` order.  Returns the stats dict."""
+        return _kmajority_dev(self, self._L.vc_kmajority_dev, k, d_centres, d_assign, d_labels, max_iters, stream)
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -751,6 +850,7 @@ class ShardedEngine:
                  cand_cap=0, query_tile=0, timing_sample=0):
         self._L = load_library()
         self.bits, self.nbytes, self.n_shards, self.n_tables = bits, bits // 8, n_shards, n_tables
+        self.id_base = id_base
         cfg = VcShardedConfig(abi_version=VC_ABI_VERSION, n_shards=n_shards, n_devices=len(devices or []), exchange=exchange)
         for i, d in enumerate(devices or []):
             cfg.device_ids[i] = d
@@ -977,6 +1077,33 @@ class ShardedEngine:
         """vc_sharded_group_summary_dev: raw device addresses on the root device (None for an output that is not wanted); outputs valid in
         `stream` order.  Returns (rc, G) with rc VC_OK, or VC_ERR_CAPACITY when G > groups_cap (nothing was written)."""
         return _group_summary_dev(self, self._L.vc_sharded_group_summary_dev, d_labels, groups_cap, d_groups, d_centroids, d_rep_labels, d_group_index, stream)
+
+    def get_codes(self, ids):
+        """the codes of resident ids, uint8 [len(ids), bits / 8]"""
+        return _get_codes(self, ids)
+
+    def assign_nearest(self, centres, first=0, count=None):
+        """vc_sharded_assign_nearest: for the records id_base + first .. + count - 1 (default: to the end) the nearest of the given codes
+        (uint8 [K, bits / 8]) as packed uint64, centre index | distance << 32; a tie in distance goes to the smaller index -- row for row
+        search_knn(k=1, MODE_LINEAR) of an engine that holds the centres with id_base 0.  first=n_old after add_codes assigns the new records."""
+        return _assign_nearest(self, self._L.vc_sharded_assign_nearest, centres, first, count)
+
+    def assign_nearest_dev(self, d_centres, n_centres, first, count, d_out, stream=None):
+        """vc_sharded_assign_nearest_dev: raw device addresses on the root device; d_out valid in `stream` order, nothing is waited for"""
+        self._check(self._L.vc_sharded_assign_nearest_dev(self._h, d_centres, n_centres, first, count, d_out, stream))
+
+    def kmajority(self, k, seed_ids=None, seeds=None, max_iters=KMAJ_MAX_ITERS):
+        """vc_sharded_kmajority: Hamming k-means over all resident records -- assign to the nearest centre, move each centre to the per-bit
+        strict majority of its members, until a round changes nothing or max_iters rounds ran.  Returns (centres, assign, labels, stats):
+        assign == assign_nearest(centres), labels = id_base + centre index (an input of group_summary), stats a dict of n_iters,
+        converged, n_empty, cost_final and the per-round cost and n_changed.  The seeds are `seeds` (k codes), the codes of `seed_ids`,
+        or by default of k ids spread evenly over the store."""
+        return _kmajority(self, self._L.vc_sharded_kmajority, k, seed_ids, seeds, max_iters)
+
+    def kmajority_dev(self, k, d_centres, d_assign, d_labels=None, max_iters=KMAJ_MAX_ITERS, stream=None):
+        """vc_sharded_kmajority_dev: raw device addresses on the root device -- d_centres holds the seeds on entry and the final centres afterwards;
+        outputs valid in `stream` order.  Returns the stats dict."""
+        return _kmajority_dev(self, self._L.vc_sharded_kmajority_dev, k, d_centres, d_assign, d_labels, max_iters, stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

@@ -141,6 +141,12 @@ class Backend {
   // nearest each -- retain() of rep_labels with VC_RETAIN_ROOTS keeps exactly these representatives
   virtual int group_summary(const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels, uint32_t* group_index,
                             uint64_t* n_groups) = 0;
+  // the nearest of n_centres given codes for the records first .. first + count - 1 (vc_assign_nearest / vc_sharded_assign_nearest):
+  // out[j] = centre index | distance << 32, a tie in distance goes to the smaller index
+  virtual int assign_nearest(const void* centres, uint32_t n_centres, uint64_t first, uint64_t count, uint64_t* out) = 0;
+  // k-majority over all records (vc_kmajority / vc_sharded_kmajority): centres in as seeds, out as the final centres; assign as
+  // assign_nearest(centres) over everything; labels (may be null) = id_base + centre index, a legal input of group_summary()
+  virtual int kmajority(uint32_t n_centres, uint32_t max_iters, void* centres, uint64_t* assign, uint32_t* labels, vc_kmajority_stats* stats) = 0;
   // records taken out of the store and its index, the survivors renumbered in order (vc_retain / vc_sharded_retain; the reference has
   // no delete: this stands for build_hash_tables.cc run again over the code file without them).  kind VC_RETAIN_MASK / VC_RETAIN_ROOTS
   virtual int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) = 0;
@@ -213,6 +219,12 @@ class Engine : public Backend {
   int group_summary(const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels, uint32_t* group_index,
                     uint64_t* n_groups) override {
     return vc_group_summary(h_, labels, groups_cap, groups, centroids, rep_labels, group_index, n_groups);
+  }
+  int assign_nearest(const void* centres, uint32_t n_centres, uint64_t first, uint64_t count, uint64_t* out) override {
+    return vc_assign_nearest(h_, centres, n_centres, first, count, out);
+  }
+  int kmajority(uint32_t n_centres, uint32_t max_iters, void* centres, uint64_t* assign, uint32_t* labels, vc_kmajority_stats* stats) override {
+    return vc_kmajority(h_, n_centres, max_iters, centres, assign, labels, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_retain(h_, sel, kind, new_ids, n_kept); }
  private:
@@ -313,6 +325,12 @@ class ShardedEngine : public Backend {
   int group_summary(const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels, uint32_t* group_index,
                     uint64_t* n_groups) override {
     return vc_sharded_group_summary(h_, labels, groups_cap, groups, centroids, rep_labels, group_index, n_groups);
+  }
+  int assign_nearest(const void* centres, uint32_t n_centres, uint64_t first, uint64_t count, uint64_t* out) override {
+    return vc_sharded_assign_nearest(h_, centres, n_centres, first, count, out);
+  }
+  int kmajority(uint32_t n_centres, uint32_t max_iters, void* centres, uint64_t* assign, uint32_t* labels, vc_kmajority_stats* stats) override {
+    return vc_sharded_kmajority(h_, n_centres, max_iters, centres, assign, labels, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_sharded_retain(h_, sel, kind, new_ids, n_kept); }
  private:
