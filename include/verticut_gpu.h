@@ -700,7 +700,7 @@ int vc_assign_nearest(vc_engine* e, const void* centres, uint32_t n_centres, uin
  *   labels[i] = id_base + index(assign[i]) -- a legal input of vc_group_summary* and, with its rep_labels, of vc_retain*
  * It terminates: the potential (sum of distances, sum of centre indices), ordered lexicographically, is never raised by an update in
  * its first term and is lowered strictly by an assign round that changes anything.
- * centres: in, the n_centres seeds (the caller chooses them: there is no device-side seeding); out, the final centres.  assign: N
+ * centres: in, the n_centres seeds (the caller chooses them; vc_seed_centres* below makes them on the device); out, the final centres.  assign: N
  * packed words.  labels: N words, may be NULL.  stats: host memory in both forms, may be NULL.
  * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle, null centres or assign, n_centres == 0,
  * n_centres > N with N > 0 (the labels must be resident ids), max_iters > VC_KMAJ_MAX_ITERS.  N == 0 gives VC_OK and zero stats;
@@ -724,6 +724,60 @@ int vc_kmajority_dev(vc_engine* e, uint32_t n_centres, uint32_t max_iters, void*
  * come home; waits for them. */
 int vc_kmajority(vc_engine* e, uint32_t n_centres, uint32_t max_iters, void* centres, uint64_t* assign, uint32_t* labels,
                  vc_kmajority_stats* stats);
+
+/* Seeds for vc_kmajority* made on the device: K sequential rounds over all N resident records, one small launch each, no byte home.
+ * Two standard seedings, both exact in integers.  VC_SEED_FARTHEST is the farthest-first traversal (Gonzalez, the 2-approximation of
+ * k-centre); it is deterministic but for its first record, and its pick distances are the covering radii one reads to choose K.
+ * VC_SEED_WEIGHTED samples a record with probability proportional to its Hamming distance to the nearest chosen seed -- for bit
+ * vectors the squared Euclidean distance, so this is k-means++ for the cost vc_kmajority minimises.  THE RULE:
+ *   N resident records with local index i; d(i, c) is the full Hamming distance; draw(t) is output number t (from 0) of SplitMix64
+ *   started at the caller's `seed`: state x starts at seed, every output does x += 0x9E3779B97F4A7C15; z = x;
+ *   z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31 -- all mod 2^64.
+ *   best[i] = (dist = infinity, index = none) for every i
+ *   s_0 = draw(0) % N ;  pick_dist_0 = 0
+ *   for t = 0 .. K-1:
+ *       centre t = code of record s_t
+ *       for every i: if d(i, s_t) < dist(best[i]): best[i] = (d(i, s_t), t)      -- strict: the earlier seed keeps a tie
+ *       if t == K-1: break
+ *       VC_SEED_FARTHEST:  s_{t+1} = the i with the largest dist(best[i]), the SMALLEST i on a tie
+ *       VC_SEED_WEIGHTED:  total = sum_i dist(best[i])
+ *                          if total == 0: s_{t+1} = 0
+ *                          else: target = draw(t+1) % total; s_{t+1} = the smallest i with sum_{j<=i} dist(best[j]) > target
+ *       pick_dist_{t+1} = dist(best[s_{t+1}])           -- before seed t+1 is applied
+ * OUTPUT: centres[t], K rows of bits / 8 bytes, the layout vc_kmajority takes as seeds (8-byte aligned in the device form).
+ * picks[t] = (id_base + s_t) | pick_dist_t << 32, the project's packed word; may be NULL.  assign[i] = index | dist << 32 of best[i]
+ * after the last seed; may be NULL.  stats: host memory in both forms, may be NULL; cost = the sum of dist(best), radius = its
+ * maximum, n_zero_picks = #{t >= 1 : pick_dist_t == 0}.
+ * Hence assign == vc_assign_nearest(centres) bit for bit (the same strict < in ascending index); in the farthest mode pick_dist_t
+ * never rises for t >= 1 and radius <= pick_dist_{K-1}; a record at distance 0 from a seed is never picked while any record is
+ * farther, and once every record coincides with a seed both methods pick record 0 at distance 0.
+ * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle, null centres, n_centres == 0, n_centres > N
+ * with N > 0, a method other than the two.  N == 0 gives VC_OK and zero stats; nothing is read or written.  No index is needed and a
+ * stale one does not matter: only the codes are read.
+ * The result is a function of the codes, K, the method and `seed` only: no knob, grid shape, shard layout or earlier call changes a
+ * bit of it.
+ * How: a pick travels between launches as dist << 32 | (0xFFFFFFFF - i).  The round launch reads it, range-checks i, loads that
+ * record's code (wave-uniform), records it into centres / picks, lowers best over its block's contiguous records and reduces the new
+ * best: farthest, the blocks' maxima of that word meet in 64-bit atomicMax -- the maximum IS the rule -- spread over 16 words on
+ * cache lines of their own, of which the next launch takes the maximum (a thousand blocks on one address measured 10 us a round);
+ * weighted, a sum per block, from which a one-block pick launch finds the block and then the record that cross the target.  A last
+ * launch reduces the statistics.  Blocks hand off only through atomics or through stores that a later launch reads.
+ * Device form: everything is enqueued on `stream`; with stats == NULL the host waits for nothing, otherwise once, at the end, for 16
+ * bytes; there is no wait per round.  The call is ordered behind the handle's previous call whatever its stream, like every call.
+ * Scratch: two grow-only buffers of the handle, this call's own (8 K + 6 160 bytes, 4 bytes per 1024 records, 8 N bytes when
+ * d_assign is NULL -- else best lives in d_assign; the host form's staging); every word written before it is read. */
+#define VC_SEED_FARTHEST 0u
+#define VC_SEED_WEIGHTED 1u
+typedef struct vc_seed_stats {           /* 16 bytes */
+  uint64_t cost;                         /* sum of dist(best) after the last seed */
+  uint32_t radius, n_zero_picks;         /* max of dist(best); picks t >= 1 at distance 0 */
+} vc_seed_stats;
+int vc_seed_centres_dev(vc_engine* e, uint32_t n_centres, uint32_t method, uint64_t seed, void* d_centres, uint64_t* d_picks,
+                        uint64_t* d_assign, vc_seed_stats* stats, void* stream);
+/* The same for centres, picks and assign in host memory: the device form on the engine's stream into staged outputs, which come
+ * home; waits for them. */
+int vc_seed_centres(vc_engine* e, uint32_t n_centres, uint32_t method, uint64_t seed, void* centres, uint64_t* picks,
+                    uint64_t* assign, vc_seed_stats* stats);
 
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
@@ -933,6 +987,19 @@ int vc_sharded_kmajority_dev(vc_sharded* h, uint32_t n_centres, uint32_t max_ite
                              vc_kmajority_stats* stats, void* stream);
 int vc_sharded_kmajority(vc_sharded* h, uint32_t n_centres, uint32_t max_iters, void* centres, uint64_t* assign, uint32_t* labels,
                          vc_kmajority_stats* stats);
+/* Seeding over all shards: rule, outputs and errors as vc_seed_centres_dev / vc_seed_centres with N = vc_sharded_size, i the ordinal
+ * in the whole store (a shard's first ordinal plus the local index: shards are id ranges in order, so the store's prefix order is
+ * the shards' order) and every pointer of the device form on the ROOT device.  Per round the root fetches the chosen record's code
+ * from the shard that owns it (vc_sharded_get_codes_dev) straight into centres[t]; every non-empty shard runs the round launch over
+ * its own records with that code; the root decides the next pick -- farthest: the maximum of the shards' slot words after
+ * translation to store ordinals; weighted: from the shards' totals which shard, then that shard's pick launch with the rest of the
+ * target.  WAITS: the root waits once per round for the shards' words (16 bytes each) and, in the weighted mode, a second time for
+ * the owning shard's pick; once more at the end.  The result equals the single engine's bit for bit for any shard layout, empty
+ * shards included. */
+int vc_sharded_seed_centres_dev(vc_sharded* h, uint32_t n_centres, uint32_t method, uint64_t seed, void* d_centres, uint64_t* d_picks,
+                                uint64_t* d_assign, vc_seed_stats* stats, void* stream);
+int vc_sharded_seed_centres(vc_sharded* h, uint32_t n_centres, uint32_t method, uint64_t seed, void* centres, uint64_t* picks,
+                            uint64_t* assign, vc_seed_stats* stats);
 /* borrow shard g's engine (bucket views, timing, files); its id range is [*first_id, *first_id + *n_ids) */
 int vc_sharded_shard(vc_sharded* h, uint32_t shard, vc_engine** e, uint64_t* first_id, uint64_t* n_ids);
 

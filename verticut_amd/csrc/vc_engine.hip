@@ -91,6 +91,9 @@ struct vc_engine {
   // nearest of K codes and k-majority (vc_assign_nearest*, vc_kmajority*): the round driver's arrays, the host forms' staging
   // (VC_KMAJ_*); their own, every word written before it is read
   uint8_t* d_kmaj[VC_KMAJ_BUFS] = {nullptr, nullptr};  size_t kmaj_bytes[VC_KMAJ_BUFS] = {0, 0};
+  // device-side seeding (vc_seed_centres*): slots, statistics, partials and best; the host form's staging (VC_SEED_*); its own, every
+  // word written before it is read
+  uint8_t* d_seed[VC_SEED_BUFS] = {nullptr, nullptr};  size_t seed_bytes[VC_SEED_BUFS] = {0, 0};
   CleanState clean;                                       // the last kernel of a linear step hands d_state back zeroed: no memset per step
   uint32_t scan_event_tick = 0;                           // VC_FLAG_LEAN_TIMING: only every timing_sample-th verify launch is timed
   VcKnobs knobs;                                          // environment knobs, read once at vc_create
@@ -400,6 +403,7 @@ int vc_destroy(vc_engine* e) {
   (void)hipFree(e->d_wstat);
   for (uint8_t* b : e->d_grp) (void)hipFree(b);
   for (uint8_t* b : e->d_kmaj) (void)hipFree(b);
+  for (uint8_t* b : e->d_seed) (void)hipFree(b);
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->last_call) (void)hipEventDestroy(e->last_call);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -1841,6 +1845,55 @@ int vc_kmajority(vc_engine* e, uint32_t n_centres, uint32_t max_iters, void* cen
   std::string err;
   rc = vc_kmajority_run_host(VcKmajArgs{n_centres, max_iters, nullptr, nullptr, nullptr, kmaj_alloc(e)}, groups_args(e, nullptr, 0, nullptr, nullptr, nullptr, nullptr),
                              assign_range(e, n_centres, 0, e->n), groups_fetch(e), centres, assign, labels, stats, e->stream, &err);
+  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
+}
+
+}  // extern "C"
+
+// ---- device-side seeding (vc_seed.hip) --------------------------------------------------------------------------------------------
+static int check_seed_args(vc_engine* e, uint32_t n_centres, uint32_t method, const void* centres) {
+  if (!e || !centres || n_centres == 0 || (e->n && n_centres > e->n) || (method != VC_SEED_FARTHEST && method != VC_SEED_WEIGHTED)) return VC_ERR_INVALID;
+  return VC_OK;
+}
+static std::function<void*(int, size_t)> seed_alloc(vc_engine* e) {
+  return [e](int which, size_t bytes) -> void* { return grow(e, &e->d_seed[which], &e->seed_bytes[which], bytes) ? nullptr : e->d_seed[which]; };
+}
+// the whole call on e->stream, inside the caller's StreamCall
+static int seed_run(vc_engine* e, uint32_t n_centres, uint32_t method, uint64_t seed, uint64_t* d_centres, uint64_t* d_picks, uint64_t* d_assign,
+                    vc_seed_stats* stats) {
+  std::string err;
+  const int rc = vc_seed_run(VcSeedArgs{e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, n_centres, method, seed, d_centres, d_picks, d_assign, seed_alloc(e)},
+                             stats, e->stream, &err);
+  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
+}
+
+extern "C" {
+
+int vc_seed_centres_dev(vc_engine* e, uint32_t n_centres, uint32_t method, uint64_t seed, void* d_centres, uint64_t* d_picks, uint64_t* d_assign,
+                        vc_seed_stats* stats, void* stream) {
+  int rc = check_seed_args(e, n_centres, method, d_centres);
+  if (rc) return rc;
+  if (stats) *stats = vc_seed_stats{};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, caller_stream(e, stream));
+  return seed_run(e, n_centres, method, seed, (uint64_t*)d_centres, d_picks, d_assign, stats);
+}
+
+int vc_seed_centres(vc_engine* e, uint32_t n_centres, uint32_t method, uint64_t seed, void* centres, uint64_t* picks, uint64_t* assign,
+                    vc_seed_stats* stats) {
+  int rc = check_seed_args(e, n_centres, method, centres);
+  if (rc) return rc;
+  if (stats) *stats = vc_seed_stats{};
+  if (e->n == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, e->stream);
+  std::string err;
+  rc = vc_seed_run_host(VcSeedHostArgs{e->n, e->W, n_centres, centres, picks, assign, stats, seed_alloc(e)},
+                        [&](uint64_t* d_centres, uint64_t* d_picks, uint64_t* d_assign, vc_seed_stats* st) {
+                          return seed_run(e, n_centres, method, seed, d_centres, d_picks, d_assign, st);
+                        },
+                        e->stream, &err);
   return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
 }
 

@@ -311,6 +311,64 @@ int vc_kmajority_run(const VcKmajArgs& k, VcGroupsArgs g, const VcAssignAll& ass
 // the same for host pointers (k's pointers are ignored): seeds staged, centres, assign and labels (nullable) come home, waited for
 int vc_kmajority_run_host(VcKmajArgs k, const VcGroupsArgs& g, const VcAssignAll& assign_all, const VcGroupsFetch& fetch, void* centres, uint64_t* assign,
                           uint32_t* labels, vc_kmajority_stats* stats, hipStream_t s, std::string* err);
+// ---- vc_seed.hip: device-side seeding (vc_seed_centres*, vc_sharded_seed_centres*).  The plan arithmetic -- generator, block ranges,
+// slot word (dist << 32 | 0xFFFFFFFF - i), prefix search -- is vc_seed_plan.hpp.  Nothing here waits but vc_seed_run with stats.
+enum { VC_SEED_WORK, VC_SEED_STAGE, VC_SEED_BUFS };   // slots, statistics, partials, best; the host forms' staging (alloc as VcGroupsArgs::alloc)
+// One round over the n records behind cols: best[i] lowered to (distance to the centre, t) where strictly smaller (t == 0: best counts
+// as infinity), then the reduction of the NEW best for the next pick.  A slot is n_slot <= VC_SEED_SUBSLOTS words VC_SEED_SLOT_STRIDE
+// apart whose maximum is the pick.  The centre is the record that slot d_slot_prev names (then its code goes to d_centre_out [W], the
+// slot word to *d_slot_rec and id_base + index | dist << 32 to *d_pick_out, both nullable; the VC_SEED_SUBSLOTS words of d_slot_zero,
+// nullable, are cleared), or the W words at d_code when that is not null (a shard: the root fetched them; none of those is used).
+// Farthest: the blocks' maxima meet in atomicMax on the n_slot_next words of d_slot_next, which must be 0 before; weighted:
+// d_partial[vc_seed_blocks(n)] gets the blocks' sums.  Both may be null: no reduction.
+struct VcSeedRound {
+  const uint64_t* cols;
+  uint64_t stride, n;
+  uint32_t W, id_base, t, method;
+  const uint64_t* d_slot_prev;
+  uint32_t n_slot_prev;
+  const uint64_t* d_code;
+  uint64_t* d_centre_out;
+  uint64_t* d_pick_out;
+  uint64_t* d_slot_rec;
+  uint64_t* d_best;
+  uint64_t* d_slot_next;
+  uint32_t n_slot_next;
+  uint64_t* d_slot_zero;
+  uint32_t* d_partial;
+};
+hipError_t vc_launch_seed_round(const VcSeedRound& r, hipStream_t s);
+// the weighted pick from a round's partials and best, one block: *d_total (nullable) = their sum; *d_slot (nullable) = the slot word of
+// the smallest i whose running sum of distances exceeds rnd % total, of record 0 at distance 0 when the total is 0
+hipError_t vc_launch_seed_pick(const uint32_t* d_partial, const uint64_t* d_best, uint64_t n, uint64_t rnd, uint64_t* d_slot, uint64_t* d_total, hipStream_t s);
+// d_stat (two words, zero before = vc_seed_stats in memory): cost += the distances of best, radius = their maximum, n_zero_picks = the
+// recorded slot words d_slots[1 .. K - 1] at distance 0 (d_slots nullable: left 0)
+hipError_t vc_launch_seed_finish(const uint64_t* d_best, uint64_t n, const uint64_t* d_slots, uint32_t K, uint64_t* d_stat, hipStream_t s);
+struct VcSeedArgs {
+  const uint64_t* cols;
+  uint64_t stride, n;
+  uint32_t W, id_base;
+  uint32_t n_centres, method;      // checked by the caller: 1 <= n_centres <= n, a known method
+  uint64_t seed;
+  uint64_t* d_centres;             // [n_centres][W]
+  uint64_t* d_picks;               // nullable
+  uint64_t* d_assign;              // nullable: then best lives in the handle's scratch
+  std::function<void*(int which, size_t bytes)> alloc;   // the handle's grow-only buffers VC_SEED_*
+};
+// the single engine's whole call on s; stats (host memory, nullable): one wait at the end for 16 bytes, none without
+int vc_seed_run(const VcSeedArgs& a, vc_seed_stats* stats, hipStream_t s, std::string* err);
+// either handle's host form: `run` (the device form on s) into staged outputs, which come home; waits for them.  picks, assign, stats nullable
+struct VcSeedHostArgs {
+  uint64_t n;
+  uint32_t W, n_centres;
+  void* centres;
+  uint64_t* picks;
+  uint64_t* assign;
+  vc_seed_stats* stats;
+  std::function<void*(int which, size_t bytes)> alloc;
+};
+int vc_seed_run_host(const VcSeedHostArgs& a, const std::function<int(uint64_t* d_centres, uint64_t* d_picks, uint64_t* d_assign, vc_seed_stats* stats)>& run,
+                     hipStream_t s, std::string* err);
 // ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
 struct VcKeepSet;
 #define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)

@@ -39,6 +39,7 @@
 
 #include "vc_internal.hpp"
 #include "vc_mih.hpp"
+#include "vc_seed_plan.hpp"
 #include "vc_sharded_radius.hpp"
 
 namespace {
@@ -104,6 +105,9 @@ enum LaneBuf {
   LANE_IDGATH, // [G][slot]: the gathered words | found words of shard g at slot g (vc_ids_slot_words); on the root all shards' slots
   LANE_ACENT,  // nearest of K codes: the centres on this device (peer copy from the root)
   LANE_AOUT,   // nearest of K codes: the packed results of this device's shards, one after the other, before they travel to the root
+  LANE_SWORK,  // seeding: per shard of this device its slot word, its total and its partials (SeedShard)
+  LANE_SCODE,  // seeding: the round's centre code on this device (peer copy from the root)
+  LANE_SBEST,  // seeding: best of this device's shards, one after the other, before it travels to the root
   LANE_BUFS
 };
 struct Lane {
@@ -150,6 +154,9 @@ enum RootBuf {
   // nearest of K codes and k-majority: the round driver's arrays, the host forms' staging (KM_WORK + VC_KMAJ_*); their own, every word
   // written before it is read
   KM_WORK, KM_STAGE,
+  // seeding: the id word, the statistics and best when the caller gives no assign; the host form's staging (SD_WORK + VC_SEED_*); its own,
+  // every word written before it is read
+  SD_WORK, SD_STAGE,
   ROOT_BUFS
 };
 
@@ -2738,6 +2745,219 @@ int vc_sharded_kmajority(vc_sharded* h, uint32_t n_centres, uint32_t max_iters, 
   rc = vc_kmajority_run_host(VcKmajArgs{n_centres, max_iters, nullptr, nullptr, nullptr, sharded_kmaj_alloc(h)},
                              sharded_groups_args(h, nullptr, 0, nullptr, nullptr, nullptr, nullptr), sharded_assign_all(h, n_centres, 0, h->n, S),
                              sharded_groups_fetch(h, S), centres, assign, labels, stats, S, &err);
+  return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
+}
+
+}  // extern "C"
+
+// ---- device-side seeding over the shards: vc_seed.hip's kernels on every shard's device, the pick decided on the root ---------------------
+static int check_sharded_seed_args(vc_sharded* h, uint32_t n_centres, uint32_t method, const void* centres) {
+  if (!h || !centres || n_centres == 0 || (h->n && n_centres > h->n) || (method != VC_SEED_FARTHEST && method != VC_SEED_WEIGHTED)) return VC_ERR_INVALID;
+  return VC_OK;
+}
+static std::function<void*(int, size_t)> sharded_seed_alloc(vc_sharded* h) {
+  return [h](int which, size_t bytes) -> void* {   // (the root device is current wherever the driver allocates)
+    DevBuf& b = h->buf[SD_WORK + which];
+    return b.grow(h, bytes) ? nullptr : b.p;
+  };
+}
+
+namespace {
+// what a non-empty shard brings to a seeding call; words[0] = its slot word, words[1] = its total, both on its device
+struct SeedShard {
+  uint32_t g, lane;
+  VcEngineView v;
+  uint64_t* words;
+  uint32_t* partial;
+  uint64_t* best;          // a root-device shard: its part of the root's best; else inside its lane's LANE_SBEST
+  const uint64_t* code;    // the round's centre code on its device
+  hipStream_t ls;
+};
+}  // namespace
+
+// THE ROUNDS over the shards (the header states the rule and the waits).  All pointers on the root device, valid on S; N > 0.  The
+// root keeps the picks on the host: per round it fetches the chosen record's code into centres[t] (sharded_gather_ids), every
+// non-empty shard runs the round launch with that code -- on S for a root-device shard, on its lane's stream behind ev_q and a peer
+// copy of the code for a remote one -- and sends its slot word and total home; the root waits for them and decides.  Returns with
+// the root device current.
+static int sharded_seed_run(vc_sharded* h, uint32_t K, uint32_t method, uint64_t seed, uint64_t* d_centres, uint64_t* d_picks, uint64_t* d_assign,
+                            vc_seed_stats* stats, hipStream_t S) {
+  const uint32_t W = h->nbytes / 8, id_base = h->cfg.engine.id_base;
+  const uint64_t N = h->n;
+  int rc;
+  VS_HIP(h, hipSetDevice(h->root));
+  DevBuf& rb = h->buf[SD_WORK];   // the id word | the two statistics words | best [N] unless d_assign holds it
+  if ((rc = rb.grow(h, 24 + (d_assign ? 0 : (size_t)N * 8)))) return rc;
+  uint32_t* d_id = rb.as<uint32_t>();
+  uint64_t* d_stat = rb.as<uint64_t>() + 1;
+  uint64_t* best = d_assign ? d_assign : rb.as<uint64_t>() + 3;
+  std::vector<SeedShard> sh;
+  bool remote = false;
+  for (uint32_t li = 0; li < h->lanes.size(); ++li) {
+    Lane& l = h->lanes[li];
+    const bool is_root = li == h->root_lane;
+    uint64_t words = 0, recs = 0;
+    for (uint32_t g : l.shards) {
+      if (shard_size(h, g) == 0) continue;
+      words += 2 + (vc_seed_blocks(shard_size(h, g)) + 1) / 2;
+      recs += shard_size(h, g);
+    }
+    if (!words) continue;
+    VS_HIP(h, hipSetDevice(l.dev));
+    if ((rc = l.buf[LANE_SWORK].grow(h, (size_t)words * 8))) return rc;
+    if (!is_root && ((rc = l.buf[LANE_SCODE].grow(h, (size_t)W * 8)) || (rc = l.buf[LANE_SBEST].grow(h, (size_t)recs * 8)))) return rc;
+    remote |= !is_root;
+    uint64_t at_w = 0, at_r = 0;
+    for (uint32_t g : l.shards) {
+      if (shard_size(h, g) == 0) continue;
+      SeedShard x;
+      x.g = g;
+      x.lane = li;
+      if ((rc = vc_engine_view(h->eng[g], &x.v))) return sfail(h, rc, "shard %u: no view", g);
+      x.words = l.buf[LANE_SWORK].as<uint64_t>() + at_w;
+      x.partial = (uint32_t*)(x.words + 2);
+      x.best = is_root ? best + h->lo[g] : l.buf[LANE_SBEST].as<uint64_t>() + at_r;
+      x.code = is_root ? nullptr : l.buf[LANE_SCODE].as<uint64_t>();
+      x.ls = is_root ? S : l.stream;
+      at_w += 2 + (vc_seed_blocks(x.v.n) + 1) / 2;
+      at_r += x.v.n;
+      sh.push_back(x);
+    }
+  }
+  std::vector<uint64_t> picks(K), home(2 * (size_t)h->G, 0), totals(h->G, 0);
+  std::vector<uint32_t> ids(K);
+  uint64_t s = vc_seed_draw(seed, 0) % N;
+  uint32_t pick_dist = 0, n_zero = 0;
+  auto wait_lanes = [&]() -> hipError_t {   // every stream a shard of this call works on
+    hipError_t r = hipSuccess;
+    for (size_t j = 0; j < sh.size() && r == hipSuccess; ++j) {
+      if (j && sh[j].lane == sh[j - 1].lane) continue;
+      if ((r = hipSetDevice(h->lanes[sh[j].lane].dev)) == hipSuccess) r = hipStreamSynchronize(sh[j].ls);
+    }
+    return r;
+  };
+  for (uint32_t t = 0; t < K; ++t) {
+    const bool last = t + 1 == K;
+    ids[t] = id_base + (uint32_t)s;
+    picks[t] = vc_pack(pick_dist, ids[t]);
+    n_zero += t >= 1 && pick_dist == 0 ? 1u : 0u;
+    uint64_t* d_code = d_centres + (uint64_t)t * W;
+    VS_HIP(h, hipSetDevice(h->root));
+    VS_HIP(h, hipMemcpyAsync(d_id, &ids[t], 4, hipMemcpyHostToDevice, S));
+    if ((rc = sharded_gather_ids(h, d_id, 1, d_code, nullptr, false, S))) return rc;
+    VS_HIP(h, hipSetDevice(h->root));
+    if (remote) VS_HIP(h, hipEventRecord(h->ev_q, S));
+    for (size_t j = 0; j < sh.size(); ++j) {
+      SeedShard& x = sh[j];
+      Lane& l = h->lanes[x.lane];
+      VS_HIP(h, hipSetDevice(l.dev));
+      if (x.code && (j == 0 || sh[j - 1].lane != x.lane)) {
+        VS_HIP(h, hipStreamWaitEvent(x.ls, h->ev_q, 0));
+        VS_HIP(h, hipMemcpyPeerAsync(l.buf[LANE_SCODE].p, l.dev, d_code, h->root, (size_t)W * 8, x.ls));
+      }
+      const bool farthest = method == VC_SEED_FARTHEST;
+      if (!last) VS_HIP(h, hipMemsetAsync(x.words, 0, 16, x.ls));
+      VcSeedRound r{};   // (a shard's slot is one word: it has few blocks next to the wait that follows)
+      r.cols = x.v.cols; r.stride = x.v.stride; r.n = x.v.n; r.W = W; r.t = t; r.method = method;
+      r.d_code = x.code ? x.code : d_code;
+      r.d_best = x.best;
+      r.d_slot_next = !last && farthest ? x.words : nullptr;
+      r.n_slot_next = 1;
+      r.d_partial = !last && !farthest ? x.partial : nullptr;
+      VS_HIP(h, vc_launch_seed_round(r, x.ls));
+      if (last) continue;
+      if (!farthest) VS_HIP(h, vc_launch_seed_pick(x.partial, x.best, x.v.n, 0, nullptr, x.words + 1, x.ls));
+      VS_HIP(h, hipMemcpyAsync(&home[2 * (size_t)x.g], x.words, 16, hipMemcpyDeviceToHost, x.ls));
+    }
+    if (last) break;
+    VS_HIP(h, wait_lanes());   // the round's wait
+    if (method == VC_SEED_FARTHEST) {
+      uint64_t top = 0;   // the maximum over the shards of the slot word in store ordinals: the rule itself
+      for (const SeedShard& x : sh) {
+        const uint64_t w = home[2 * (size_t)x.g];
+        const uint64_t i = h->lo[x.g] + vc_seed_slot_index(w);
+        if (i < N) top = std::max(top, vc_seed_slot(vc_seed_slot_dist(w), (uint32_t)i));
+      }
+      s = vc_seed_slot_index(top);
+      pick_dist = vc_seed_slot_dist(top);
+      if (s >= N) return sfail(h, VC_ERR_HIP, "seeding: no shard reported a record in round %u", t);
+    } else {
+      uint64_t total = 0, before = 0;
+      for (const SeedShard& x : sh) total += totals[x.g] = home[2 * (size_t)x.g + 1];
+      s = 0;
+      pick_dist = 0;
+      if (total) {
+        const uint64_t target = vc_seed_draw(seed, (uint64_t)t + 1) % total;
+        const uint64_t g = vc_seed_find(totals.data(), (uint64_t)h->G, target, &before, VcSeedWeightPlain());
+        const SeedShard* own = nullptr;
+        for (const SeedShard& x : sh)
+          if (x.g == g) own = &x;
+        if (!own) return sfail(h, VC_ERR_HIP, "seeding: the shards' totals do not reach the target in round %u", t);
+        VS_HIP(h, hipSetDevice(h->lanes[own->lane].dev));
+        VS_HIP(h, vc_launch_seed_pick(own->partial, own->best, own->v.n, target - before, own->words, nullptr, own->ls));   // (the rest is below the shard's total)
+        VS_HIP(h, hipMemcpyAsync(&home[2 * (size_t)own->g], own->words, 8, hipMemcpyDeviceToHost, own->ls));
+        VS_HIP(h, hipStreamSynchronize(own->ls));   // the round's second wait
+        const uint64_t w = home[2 * (size_t)own->g];
+        s = h->lo[own->g] + vc_seed_slot_index(w);
+        pick_dist = vc_seed_slot_dist(w);
+        if (s >= N) return sfail(h, VC_ERR_HIP, "seeding: shard %u reported no record in round %u", own->g, t);
+      }
+    }
+  }
+  // best of the remote shards comes to the root behind their lanes' events
+  for (size_t j = 0; j < sh.size(); ++j) {
+    if (!sh[j].code || (j + 1 < sh.size() && sh[j + 1].lane == sh[j].lane)) continue;
+    VS_HIP(h, hipSetDevice(h->lanes[sh[j].lane].dev));
+    VS_HIP(h, hipEventRecord(h->lanes[sh[j].lane].done, sh[j].ls));
+  }
+  VS_HIP(h, hipSetDevice(h->root));
+  for (size_t j = 0; j < sh.size(); ++j) {
+    const SeedShard& x = sh[j];
+    if (!x.code) continue;
+    Lane& l = h->lanes[x.lane];
+    if (j == 0 || sh[j - 1].lane != x.lane) VS_HIP(h, hipStreamWaitEvent(S, l.done, 0));
+    VS_HIP(h, hipMemcpyPeerAsync(best + h->lo[x.g], h->root, x.best, l.dev, (size_t)x.v.n * 8, S));
+  }
+  if (d_picks) VS_HIP(h, hipMemcpyAsync(d_picks, picks.data(), (size_t)K * 8, hipMemcpyHostToDevice, S));
+  vc_seed_stats st{};
+  if (stats) {
+    VS_HIP(h, hipMemsetAsync(d_stat, 0, 16, S));
+    VS_HIP(h, vc_launch_seed_finish(best, N, nullptr, K, d_stat, S));
+    VS_HIP(h, hipMemcpyAsync(&st, d_stat, sizeof st, hipMemcpyDeviceToHost, S));
+  }
+  VS_HIP(h, hipStreamSynchronize(S));   // the last wait: the picks leave the host, the statistics arrive
+  if (stats) {
+    st.n_zero_picks = n_zero;
+    *stats = st;
+  }
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_sharded_seed_centres_dev(vc_sharded* h, uint32_t n_centres, uint32_t method, uint64_t seed, void* d_centres, uint64_t* d_picks,
+                                uint64_t* d_assign, vc_seed_stats* stats, void* stream) {
+  const int rc = check_sharded_seed_args(h, n_centres, method, d_centres);
+  if (rc) return rc;
+  if (stats) *stats = vc_seed_stats{};
+  if (h->n == 0) return VC_OK;
+  return sharded_seed_run(h, n_centres, method, seed, (uint64_t*)d_centres, d_picks, d_assign, stats, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+}
+
+int vc_sharded_seed_centres(vc_sharded* h, uint32_t n_centres, uint32_t method, uint64_t seed, void* centres, uint64_t* picks, uint64_t* assign,
+                            vc_seed_stats* stats) {
+  int rc = check_sharded_seed_args(h, n_centres, method, centres);
+  if (rc) return rc;
+  if (stats) *stats = vc_seed_stats{};
+  if (h->n == 0) return VC_OK;
+  hipStream_t S = h->root_stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  std::string err;
+  rc = vc_seed_run_host(VcSeedHostArgs{h->n, h->nbytes / 8, n_centres, centres, picks, assign, stats, sharded_seed_alloc(h)},
+                        [&](uint64_t* d_centres, uint64_t* d_picks, uint64_t* d_assign, vc_seed_stats* st) {
+                          return sharded_seed_run(h, n_centres, method, seed, d_centres, d_picks, d_assign, st, S);
+                        },
+                        S, &err);
   return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
 }
 

@@ -51,7 +51,9 @@ EXPORTS = [
     "vc_dbscan_levels", "vc_dbscan_levels_dev", "vc_sharded_dbscan_levels", "vc_sharded_dbscan_levels_dev",
     "vc_assign_nearest", "vc_assign_nearest_dev", "vc_sharded_assign_nearest", "vc_sharded_assign_nearest_dev",
     "vc_kmajority", "vc_kmajority_dev", "vc_sharded_kmajority", "vc_sharded_kmajority_dev",
+    "vc_seed_centres", "vc_seed_centres_dev", "vc_sharded_seed_centres", "vc_sharded_seed_centres_dev",
 ]
+SEED_FARTHEST, SEED_WEIGHTED = 0, 1   # VC_SEED_FARTHEST: farthest-first traversal; VC_SEED_WEIGHTED: distance-weighted sampling ("k-majority++")
 KMAJ_MAX_ITERS = 64       # VC_KMAJ_MAX_ITERS: kmajority takes max_iters 0 .. 64
 LEVELS_MAX = 64           # VC_LEVELS_MAX: cluster_levels and dbscan_levels take max_radius 0 .. 63
 CORE_NEVER = 0xFFFFFFFF   # VC_CORE_NEVER: dbscan_levels' core_dist of a record with fewer than min_pts records within max_radius
@@ -117,6 +119,14 @@ class VcKmajorityStats(C.Structure):
         """{n_iters, converged, n_empty, cost_final: int; cost, n_changed: uint64 [KMAJ_MAX_ITERS], zero from n_iters on}"""
         return {name: (np.array(getattr(self, name)[:], dtype=np.uint64) if name in ("cost", "n_changed") else int(getattr(self, name)))
                 for name, _ in self._fields_}
+
+
+class VcSeedStats(C.Structure):
+    _fields_ = [("cost", C.c_uint64), ("radius", C.c_uint32), ("n_zero_picks", C.c_uint32)]
+
+    def as_dict(self):
+        """{cost, radius, n_zero_picks: int}"""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 class VcTiming(C.Structure):
@@ -249,6 +259,10 @@ def load_library():
     L.vc_kmajority_dev.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
     L.vc_sharded_kmajority.argtypes = [vp, u32, u32, vp, vp, vp, vp]
     L.vc_sharded_kmajority_dev.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
+    L.vc_seed_centres.argtypes = [vp, u32, u32, u64, vp, vp, vp, vp]
+    L.vc_seed_centres_dev.argtypes = [vp, u32, u32, u64, vp, vp, vp, vp, vp]
+    L.vc_sharded_seed_centres.argtypes = [vp, u32, u32, u64, vp, vp, vp, vp]
+    L.vc_sharded_seed_centres_dev.argtypes = [vp, u32, u32, u64, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -469,6 +483,23 @@ def _kmajority_dev(self, fn, k, d_centres, d_assign, d_labels, max_iters, stream
     st = VcKmajorityStats()
     self._check(fn(self._h, k, max_iters, d_centres, d_assign, d_labels, C.byref(st), stream))
     return st.as_dict()
+
+
+def _seed_centres(self, fn, k, method, seed, with_assign):
+    """shared by Engine.seed_centres and ShardedEngine.seed_centres: (centres uint8 [k, bits / 8], picks uint64 [k], assign uint64 [N] |
+    None, stats dict)"""
+    n = len(self)
+    centres, picks = np.zeros((k, self.nbytes), dtype=np.uint8), np.zeros(k, dtype=np.uint64)
+    assign = np.empty(n, dtype=np.uint64) if with_assign else None
+    st = VcSeedStats()
+    self._check(fn(self._h, k, method, seed, _p(centres), _p(picks), _p(assign) if with_assign and n else None, C.byref(st)))
+    return centres, picks, assign, st.as_dict()
+
+
+def _seed_centres_dev(self, fn, k, d_centres, d_picks, d_assign, method, seed, with_stats, stream):
+    st = VcSeedStats()
+    self._check(fn(self._h, k, method, seed, d_centres, d_picks, d_assign, C.byref(st) if with_stats else None, stream))
+    return st.as_dict() if with_stats else None
 
 
 def _retain(self, fn, sel, kind, with_map):
@@ -811,13 +842,26 @@ class Engine:
         strict majority of its members, until a round changes nothing or max_iters rounds ran.  Returns (centres, assign, labels, stats):
         assign == assign_nearest(centres), labels = id_base + centre index (an input of group_summary), stats a dict of n_iters,
         converged, n_empty, cost_final and the per-round cost and n_changed.  The seeds are `seeds` (k codes), the codes of `seed_ids`,
-        or by default of k ids spread evenly over the store."""
+        or by default of k ids spread evenly over the store; seed_centres makes better ones on the device."""
         return _kmajority(self, self._L.vc_kmajority, k, seed_ids, seeds, max_iters)
 
     def kmajority_dev(self, k, d_centres, d_assign, d_labels=None, max_iters=KMAJ_MAX_ITERS, stream=None):
         """vc_kmajority_dev: raw device addresses -- d_centres holds the seeds on entry and the final centres afterwards;
         outputs valid in `stream` order.  Returns the stats dict."""
         return _kmajority_dev(self, self._L.vc_kmajority_dev, k, d_centres, d_assign, d_labels, max_iters, stream)
+
+    def seed_centres(self, k, method=SEED_FARTHEST, seed=0, with_assign=False):
+        """vc_seed_centres: k seeds for kmajority made on the device -- SEED_FARTHEST, the farthest-first traversal, or SEED_WEIGHTED, a record
+        sampled with probability proportional to its distance to the nearest chosen seed (SplitMix64 from `seed`; the first record is
+        draw(0) % N in both).  Returns (centres, picks, assign, stats): picks[t] = id | distance to the seeds before it << 32, assign ==
+        assign_nearest(centres) (None unless with_assign), stats a dict of cost, radius, n_zero_picks.  A function of the codes, k, the
+        method and `seed` only."""
+        return _seed_centres(self, self._L.vc_seed_centres, k, method, seed, with_assign)
+
+    def seed_centres_dev(self, k, d_centres, d_picks=None, d_assign=None, method=SEED_FARTHEST, seed=0, with_stats=True, stream=None):
+        """vc_seed_centres_dev: raw device addresses; outputs valid in `stream` order.  Returns the stats dict; with_stats=False returns
+        None and the host waits for nothing."""
+        return _seed_centres_dev(self, self._L.vc_seed_centres_dev, k, d_centres, d_picks, d_assign, method, seed, with_stats, stream)
 
     def timing(self):
         t = VcTiming()
@@ -1097,13 +1141,26 @@ class ShardedEngine:
         strict majority of its members, until a round changes nothing or max_iters rounds ran.  Returns (centres, assign, labels, stats):
         assign == assign_nearest(centres), labels = id_base + centre index (an input of group_summary), stats a dict of n_iters,
         converged, n_empty, cost_final and the per-round cost and n_changed.  The seeds are `seeds` (k codes), the codes of `seed_ids`,
-        or by default of k ids spread evenly over the store."""
+        or by default of k ids spread evenly over the store; seed_centres makes better ones on the device."""
         return _kmajority(self, self._L.vc_sharded_kmajority, k, seed_ids, seeds, max_iters)
 
     def kmajority_dev(self, k, d_centres, d_assign, d_labels=None, max_iters=KMAJ_MAX_ITERS, stream=None):
         """vc_sharded_kmajority_dev: raw device addresses on the root device -- d_centres holds the seeds on entry and the final centres afterwards;
         outputs valid in `stream` order.  Returns the stats dict."""
         return _kmajority_dev(self, self._L.vc_sharded_kmajority_dev, k, d_centres, d_assign, d_labels, max_iters, stream)
+
+    def seed_centres(self, k, method=SEED_FARTHEST, seed=0, with_assign=False):
+        """vc_sharded_seed_centres: k seeds for kmajority made on the device -- SEED_FARTHEST, the farthest-first traversal, or SEED_WEIGHTED, a record
+        sampled with probability proportional to its distance to the nearest chosen seed (SplitMix64 from `seed`; the first record is
+        draw(0) % N in both).  Returns (centres, picks, assign, stats): picks[t] = id | distance to the seeds before it << 32, assign ==
+        assign_nearest(centres) (None unless with_assign), stats a dict of cost, radius, n_zero_picks.  A function of the codes, k, the
+        method and `seed` only."""
+        return _seed_centres(self, self._L.vc_sharded_seed_centres, k, method, seed, with_assign)
+
+    def seed_centres_dev(self, k, d_centres, d_picks=None, d_assign=None, method=SEED_FARTHEST, seed=0, with_stats=True, stream=None):
+        """vc_sharded_seed_centres_dev: raw device addresses on the root device; outputs valid in `stream` order.  Returns the stats dict; with_stats=False returns
+        None (the root still waits once or twice per round)."""
+        return _seed_centres_dev(self, self._L.vc_sharded_seed_centres_dev, k, d_centres, d_picks, d_assign, method, seed, with_stats, stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

@@ -147,6 +147,9 @@ class Backend {
   // k-majority over all records (vc_kmajority / vc_sharded_kmajority): centres in as seeds, out as the final centres; assign as
   // assign_nearest(centres) over everything; labels (may be null) = id_base + centre index, a legal input of group_summary()
   virtual int kmajority(uint32_t n_centres, uint32_t max_iters, void* centres, uint64_t* assign, uint32_t* labels, vc_kmajority_stats* stats) = 0;
+  // seeds for kmajority() made on the device (vc_seed_centres / vc_sharded_seed_centres): method VC_SEED_FARTHEST or VC_SEED_WEIGHTED;
+  // centres out; picks (id | pick distance << 32), assign (as assign_nearest(centres) over everything) and stats may be null
+  virtual int seed_centres(uint32_t n_centres, uint32_t method, uint64_t seed, void* centres, uint64_t* picks, uint64_t* assign, vc_seed_stats* stats) = 0;
   // records taken out of the store and its index, the survivors renumbered in order (vc_retain / vc_sharded_retain; the reference has
   // no delete: this stands for build_hash_tables.cc run again over the code file without them).  kind VC_RETAIN_MASK / VC_RETAIN_ROOTS
   virtual int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) = 0;
@@ -225,6 +228,9 @@ class Engine : public Backend {
   }
   int kmajority(uint32_t n_centres, uint32_t max_iters, void* centres, uint64_t* assign, uint32_t* labels, vc_kmajority_stats* stats) override {
     return vc_kmajority(h_, n_centres, max_iters, centres, assign, labels, stats);
+  }
+  int seed_centres(uint32_t n_centres, uint32_t method, uint64_t seed, void* centres, uint64_t* picks, uint64_t* assign, vc_seed_stats* stats) override {
+    return vc_seed_centres(h_, n_centres, method, seed, centres, picks, assign, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_retain(h_, sel, kind, new_ids, n_kept); }
  private:
@@ -331,6 +337,9 @@ class ShardedEngine : public Backend {
   }
   int kmajority(uint32_t n_centres, uint32_t max_iters, void* centres, uint64_t* assign, uint32_t* labels, vc_kmajority_stats* stats) override {
     return vc_sharded_kmajority(h_, n_centres, max_iters, centres, assign, labels, stats);
+  }
+  int seed_centres(uint32_t n_centres, uint32_t method, uint64_t seed, void* centres, uint64_t* picks, uint64_t* assign, vc_seed_stats* stats) override {
+    return vc_sharded_seed_centres(h_, n_centres, method, seed, centres, picks, assign, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_sharded_retain(h_, sel, kind, new_ids, n_kept); }
  private:
