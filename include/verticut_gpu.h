@@ -779,6 +779,74 @@ int vc_seed_centres_dev(vc_engine* e, uint32_t n_centres, uint32_t method, uint6
 int vc_seed_centres(vc_engine* e, uint32_t n_centres, uint32_t method, uint64_t seed, void* centres, uint64_t* picks,
                     uint64_t* assign, vc_seed_stats* stats);
 
+/* ---- one result per label group in k-NN search ----------------------------------------------------------------------------------
+ * replaces: search_image_by_id / SearchWorker::find (image_search_client.h:12-27, search_worker.cc:65-89) for a front end that wants
+ * the k nearest DISTINCT pictures: on near-duplicate-heavy data the plain top-k row is mostly copies of a few of them.  The
+ * reference has no such call; the host loop it would take -- search with a guessed larger k, copy rows and labels home, collapse,
+ * repeat -- is what this replaces.  Exact, batched; rows and labels never leave HBM in the device form.
+ * labels: one uint32 per resident record, indexed by id - id_base (N = vc_size entries).  Only EQUALITY of two values matters: 0 and
+ * 0xFFFFFFFF are labels like any other, nothing is validated.  The output of every grouper qualifies (vc_cluster_radius*,
+ * vc_leaders_radius*, vc_dbscan_radius*, one level of the *_levels* calls, vc_kmajority*'s labels), and so does group_index of
+ * vc_group_summary*, a class id or a user's album id.
+ * RULE.  For a query q the HEAD of label L is the smallest packed (dist << 32 | id) over the records with label L.  Row i is the k
+ * smallest heads of query i, ascending, padded with UINT64_MAX.  Equivalently: walk the ascending k-NN list of q and keep an entry
+ * iff no earlier entry has its label -- the form the implementation takes, in ROUNDS:
+ *   round j runs the UNCHANGED k-NN search (vc_search_knn_dev) at k'_j for the queries still unfinished, collapses each row of k'_j
+ *   entries to the first occurrences of its labels and counts them, d.  A query is FINISHED when d >= k (its row: the first k kept
+ *   entries, count k) or when the search returned fewer than k'_j entries (the database is exhausted: the row holds every group,
+ *   count = d < k).  Otherwise it goes to round j + 1 with k'_{j+1} = min(VC_MAX_K, 2 k'_j).  A query still unfinished at
+ *   k' = VC_MAX_K is TRUNCATED -- more than 8192 records of fewer than k groups lie nearest to it -- and gets the d heads found and
+ *   count = d | VC_DISTINCT_TRUNCATED.  A count of UINT32_MAX from the search underneath (its ring-overflow recovery gave up, see
+ *   vc_device_status) is passed on as it is, with the collapsed upper-bound row.
+ * k_first sets k'_0; 0 means min(VC_MAX_K, 2 k), any other value must lie in k .. VC_MAX_K.  A finished row is THE SAME for every
+ * k_first: a top-k' prefix that holds k distinct labels holds the k nearest heads as its first occurrences (a head not in the prefix
+ * is farther than all k' entries).  k_first is a tuning knob only; the statistics differ.
+ * This holds wherever the rows underneath are the true nearest records: VC_MODE_LINEAR always, VC_MODE_MIH_EXACT without
+ * VC_FLAG_REF_SIGNEXT_KEYS and without VC_FLAG_REF_STOP_LITERAL4 at n_tables < 4.  Under those flags the row is the collapse of the
+ * row the underlying call returns at the final k'.  VC_MODE_MIH_APPROX is refused: its 20 k candidate rule has no meaning for groups.
+ * THE SURE PREFIX (VC_MODE_MIH_EXACT).  A row of exact MIH has the true distances and every record nearer than its last distance D,
+ * but of the records that tie at D only some -- genuine ones, not necessarily the smallest ids (vc_search_knn's contract: "among the
+ * items the mode's loop has seen").  A head taken from those ties could be the wrong member, or the wrong group, of its distance.
+ * So in this mode a FULL row of a round with k' < VC_MAX_K counts only up to the entries nearer than D: d is the number of distinct
+ * labels among those, and a query with d < k goes on.  A row that is not full holds the whole database and counts whole.  Rows, row
+ * labels and counts are then word for word those of VC_MODE_LINEAR, for every k_first; n_rounds and n_searched can be larger than
+ * there.  At k' = VC_MAX_K no wider row exists and the whole row counts: an entry at its last distance is a genuine member of a
+ * genuine group of that distance, as in vc_search_knn.
+ * OUTPUT: d_out nq * k packed; d_row_labels (nq * k, may be NULL) the label of every entry, 0 past the count; d_counts (nq, may be
+ * NULL); stats (HOST memory in both forms, may be NULL).
+ * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle, queries, labels or out, nq == 0, k outside
+ * 1 .. VC_MAX_K, a bad k_first, an approximate or unknown mode, a bad order (host form); VC_ERR_STATE in MIH mode without a current
+ * index (a stale one counts as none).  N == 0 gives VC_OK with counts 0, padded rows and zero stats.
+ * WAITS.  The device form makes the host wait ONCE PER ROUND, for the number of unfinished queries (24 bytes) -- in VC_MODE_LINEAR
+ * too, where vc_search_knn_dev itself waits for nothing; the MIH mode's own waits inside the search come on top.  Results are valid
+ * in stream order.
+ * How: the collapse kernel has a form per size class of k' -- up to 64 entries one wave per query without LDS; above, one block per
+ * query with the row's labels and a first-occurrence table of row positions in LDS (no label value is reserved as a marker); the
+ * kept entries are placed by ballot and block sums, never by the order of atomics.  The retry list is the exclusive scan of a flag
+ * per query, so it is ascending; a gather kernel compacts the retry queries; later rounds write straight into d_out through an
+ * index map.  Hence every output word is a function of the database, the labels and the call only.
+ * Scratch: three grow-only buffers of the handle, this call's own; every word written before it is read.  The k' rows of a round
+ * take at most VC_DISTINCT_SCRATCH bytes (environment, read at vc_create; default 64 MiB; always at least one row): a round of n
+ * queries runs in sub-batches of max(1, budget / (8 k')) queries, so a 4096-query call does not allocate 256 MiB at k' = 8192. */
+#define VC_DISTINCT_TRUNCATED 0x80000000u
+typedef struct vc_distinct_stats {   /* 32 bytes */
+  uint32_t n_rounds;      /* search rounds run (>= 1 for nq > 0) */
+  uint32_t k_last;        /* k' of the last round */
+  uint64_t n_searched;    /* queries summed over rounds */
+  uint64_t n_truncated;   /* queries that ended with VC_DISTINCT_TRUNCATED */
+  uint64_t n_short;       /* queries that finished with count < k because the database holds fewer groups */
+} vc_distinct_stats;
+int vc_search_knn_distinct_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* d_labels,
+                               uint32_t k_first, uint64_t* d_out, uint32_t* d_row_labels, uint32_t* d_counts, vc_distinct_stats* stats,
+                               void* stream);
+/* The same for queries, labels and results in host memory: queries and the N labels are staged on the engine's stream ON EVERY CALL,
+ * the device form runs into staged outputs, which come home; waits for them.  order as vc_search_knn: VC_ORDER_FARTHEST_FIRST
+ * reverses the valid part of every row (and of its labels).  Callers who search repeatedly should keep the labels in HBM and use
+ * the device form. */
+int vc_search_knn_distinct(vc_engine* e, const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order,
+                           const uint32_t* labels, uint32_t k_first, uint64_t* out, uint32_t* row_labels, uint32_t* counts,
+                           vc_distinct_stats* stats);
+
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
  * seconds); the affected queries kept d_counts[i] == UINT32_MAX.  0 in normal operation.  Synchronises the stream.
@@ -1000,6 +1068,17 @@ int vc_sharded_seed_centres_dev(vc_sharded* h, uint32_t n_centres, uint32_t meth
                                 uint64_t* d_assign, vc_seed_stats* stats, void* stream);
 int vc_sharded_seed_centres(vc_sharded* h, uint32_t n_centres, uint32_t method, uint64_t seed, void* centres, uint64_t* picks,
                             uint64_t* assign, vc_seed_stats* stats);
+/* One result per label group over all shards: rule, outputs, errors, rounds and waits as vc_search_knn_distinct_dev /
+ * vc_search_knn_distinct with N = vc_sharded_size and ids global over the whole store.  Every pointer of the device form lives on the
+ * ROOT device, `stream` is a stream of that device; labels: all N entries on the root.  The search underneath is
+ * vc_sharded_search_knn_dev on the handle as it was created (VC_FLAG_GLOBAL_STOP included); its merged rows are collapsed on the
+ * root by the same kernels, so rows, labels, counts and statistics equal the single engine's bit for bit. */
+int vc_sharded_search_knn_distinct_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode,
+                                       const uint32_t* d_labels, uint32_t k_first, uint64_t* d_out, uint32_t* d_row_labels,
+                                       uint32_t* d_counts, vc_distinct_stats* stats, void* stream);
+int vc_sharded_search_knn_distinct(vc_sharded* h, const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order,
+                                   const uint32_t* labels, uint32_t k_first, uint64_t* out, uint32_t* row_labels, uint32_t* counts,
+                                   vc_distinct_stats* stats);
 /* borrow shard g's engine (bucket views, timing, files); its id range is [*first_id, *first_id + *n_ids) */
 int vc_sharded_shard(vc_sharded* h, uint32_t shard, vc_engine** e, uint64_t* first_id, uint64_t* n_ids);
 

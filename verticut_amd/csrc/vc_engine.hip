@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <functional>
 
+#include "vc_distinct_plan.hpp"
 #include "vc_groups_plan.hpp"
 #include "vc_internal.hpp"
 #include "vc_mih.hpp"
@@ -94,6 +95,9 @@ struct vc_engine {
   // device-side seeding (vc_seed_centres*): slots, statistics, partials and best; the host form's staging (VC_SEED_*); its own, every
   // word written before it is read
   uint8_t* d_seed[VC_SEED_BUFS] = {nullptr, nullptr};  size_t seed_bytes[VC_SEED_BUFS] = {0, 0};
+  // one result per label group (vc_search_knn_distinct*): flags, maps, retry queries and counters; the k' rows; the host form's staging
+  // (VC_DISTINCT_*); its own, every word written before it is read
+  uint8_t* d_distinct[VC_DISTINCT_BUFS] = {nullptr, nullptr, nullptr};  size_t distinct_bytes[VC_DISTINCT_BUFS] = {0, 0, 0};
   CleanState clean;                                       // the last kernel of a linear step hands d_state back zeroed: no memset per step
   uint32_t scan_event_tick = 0;                           // VC_FLAG_LEAN_TIMING: only every timing_sample-th verify launch is timed
   VcKnobs knobs;                                          // environment knobs, read once at vc_create
@@ -206,6 +210,7 @@ void read_knobs(VcKnobs* k) {
   }
   if (const char* v = getenv("VC_ASSIGN_TILE")) k->assign_tile = (uint32_t)strtoul(v, nullptr, 10);
   if (const char* v = getenv("VC_ASSIGN_SLICES")) k->assign_slices = (uint32_t)strtoul(v, nullptr, 10);
+  if (const char* v = getenv("VC_DISTINCT_SCRATCH")) k->distinct_scratch = strtoull(v, nullptr, 10);
 }
 
 static int bind_device(vc_engine* e) {
@@ -404,6 +409,7 @@ int vc_destroy(vc_engine* e) {
   for (uint8_t* b : e->d_grp) (void)hipFree(b);
   for (uint8_t* b : e->d_kmaj) (void)hipFree(b);
   for (uint8_t* b : e->d_seed) (void)hipFree(b);
+  for (uint8_t* b : e->d_distinct) (void)hipFree(b);
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->last_call) (void)hipEventDestroy(e->last_call);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -1894,6 +1900,61 @@ int vc_seed_centres(vc_engine* e, uint32_t n_centres, uint32_t method, uint64_t 
                           return seed_run(e, n_centres, method, seed, d_centres, d_picks, d_assign, st);
                         },
                         e->stream, &err);
+  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
+}
+
+}  // extern "C"
+
+// ---- one result per label group in k-NN search (vc_distinct.hip) --------------------------------------------------------------------
+static int check_distinct_args(vc_engine* e, const void* q, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* labels, uint32_t k_first,
+                               const uint64_t* out) {
+  if (!e || !q || !labels || !out || nq == 0) return VC_ERR_INVALID;
+  if (k == 0 || k > VC_MAX_K) return fail(e, VC_ERR_INVALID, "k must be in 1..%u", VC_MAX_K);
+  if (!vc_distinct_k_first_ok(k, k_first)) return fail(e, VC_ERR_INVALID, "k_first must be 0 or in k..%u", VC_MAX_K);
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "distinct search: mode must be LINEAR or MIH_EXACT");
+  if (mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first (n_tables=%u)", e->m);
+  return VC_OK;
+}
+static std::function<void*(int, size_t)> distinct_alloc(vc_engine* e) {
+  return [e](int which, size_t bytes) -> void* { return grow(e, &e->d_distinct[which], &e->distinct_bytes[which], bytes) ? nullptr : e->d_distinct[which]; };
+}
+// the whole call on e->stream, inside the caller's StreamCall
+static int distinct_run(vc_engine* e, const uint64_t* d_queries, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* d_labels, uint32_t k_first,
+                        uint64_t* d_out, uint32_t* d_row_labels, uint32_t* d_counts, vc_distinct_stats* stats) {
+  std::string err;
+  const int rc = vc_distinct_run(VcDistinctArgs{e->n, e->cfg.id_base, e->W, d_queries, nq, k, k_first, d_labels, d_out, d_row_labels, d_counts,
+                                                e->knobs.distinct_scratch, mode == VC_MODE_MIH_EXACT, distinct_alloc(e)},
+                                 [&](const uint64_t* d_q, uint32_t n, uint32_t kp, uint64_t* d_rows, uint32_t* d_cnt) {
+                                   return knn_dev_run(e, d_q, n, kp, mode, d_rows, d_cnt, nullptr);
+                                 },
+                                 stats, e->stream, &err);
+  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
+}
+
+extern "C" {
+
+int vc_search_knn_distinct_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* d_labels, uint32_t k_first,
+                               uint64_t* d_out, uint32_t* d_row_labels, uint32_t* d_counts, vc_distinct_stats* stats, void* stream) {
+  int rc = check_distinct_args(e, d_queries, nq, k, mode, d_labels, k_first, d_out);
+  if (rc) return rc;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, caller_stream(e, stream));
+  return distinct_run(e, (const uint64_t*)d_queries, nq, k, mode, d_labels, k_first, d_out, d_row_labels, d_counts, stats);
+}
+
+int vc_search_knn_distinct(vc_engine* e, const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* labels,
+                           uint32_t k_first, uint64_t* out, uint32_t* row_labels, uint32_t* counts, vc_distinct_stats* stats) {
+  int rc = check_distinct_args(e, queries, nq, k, mode, labels, k_first, out);
+  if (rc) return rc;
+  if (order > VC_ORDER_FARTHEST_FIRST) return VC_ERR_INVALID;
+  if ((rc = bind_device(e))) return rc;
+  const StreamCall call(e, e->stream);
+  std::string err;
+  rc = vc_distinct_run_host(VcDistinctHostArgs{e->n, e->W, nq, k, order, queries, labels, out, row_labels, counts, stats, distinct_alloc(e)},
+                            [&](const uint64_t* d_q, const uint32_t* d_labels, uint64_t* d_out, uint32_t* d_rl, uint32_t* d_cnt, vc_distinct_stats* st) {
+                              return distinct_run(e, d_q, nq, k, mode, d_labels, k_first, d_out, d_rl, d_cnt, st);
+                            },
+                            e->stream, &err);
   return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
 }
 

@@ -47,6 +47,7 @@ struct VcKnobs {
   bool scan_shape_trace = false;              // VC_SCAN_SHAPE_TRACE=1 (dev/tests): every verify launch names the instantiation it launched on stderr
   uint32_t assign_tile = 0;                   // VC_ASSIGN_TILE (tests): centres per LDS tile of vc_assign_kernel (0 = all that fit, vc_assign_plan.hpp)
   uint32_t assign_slices = 0;                 // VC_ASSIGN_SLICES (tests): forces the number of centre slices of a vc_assign_kernel launch (0 = the plan's)
+  uint64_t distinct_scratch = 64ull << 20;    // VC_DISTINCT_SCRATCH: bytes of k' rows a sub-batch of vc_search_knn_distinct* may hold (vc_distinct_plan.hpp)
 };
 void read_knobs(VcKnobs* k);   // vc_engine.hip: the one place that reads the environment (once per engine / sharded handle)
 
@@ -369,6 +370,43 @@ struct VcSeedHostArgs {
 };
 int vc_seed_run_host(const VcSeedHostArgs& a, const std::function<int(uint64_t* d_centres, uint64_t* d_picks, uint64_t* d_assign, vc_seed_stats* stats)>& run,
                      hipStream_t s, std::string* err);
+// ---- vc_distinct.hip: one result per label group in k-NN search (vc_search_knn_distinct*, vc_sharded_search_knn_distinct*).  One
+// driver for both handle kinds, parameterised on the search underneath; the plan arithmetic -- the k' schedule, the collapse kernel's
+// form for a k', the verdict on a row, the sub-batches -- is vc_distinct_plan.hpp.
+enum { VC_DISTINCT_WORK, VC_DISTINCT_ROWS, VC_DISTINCT_STAGE, VC_DISTINCT_BUFS };   // flags, maps, retry queries, counters; the k' rows; the host forms' staging
+// the handle's unchanged k-NN search of nq queries [nq][W] at k' into d_rows [nq][k'] and d_cnt [nq], enqueued on the call's stream
+typedef std::function<int(const uint64_t* d_queries, uint32_t nq, uint32_t kp, uint64_t* d_rows, uint32_t* d_cnt)> VcDistinctSearch;
+struct VcDistinctArgs {
+  uint64_t n_labels;               // N, the resident records: d_labels has one word for each, indexed by id - id_base
+  uint32_t id_base, W;
+  const uint64_t* d_queries;       // [nq][W]
+  uint32_t nq, k, k_first;         // checked by the caller: nq > 0, 1 <= k <= VC_MAX_K, vc_distinct_k_first_ok
+  const uint32_t* d_labels;
+  uint64_t* d_out;                 // [nq][k]
+  uint32_t* d_row_labels;          // [nq][k], nullable
+  uint32_t* d_counts;              // [nq], nullable
+  uint64_t budget;                 // VcKnobs::distinct_scratch: bytes of rows scratch per sub-batch
+  bool tie_cut;                    // the search underneath is exact MIH: its rows are sure only below their last distance (vc_distinct_sure_below)
+  std::function<void*(int which, size_t bytes)> alloc;   // the handle's grow-only buffers VC_DISTINCT_* (as VcGroupsArgs::alloc)
+};
+// the whole call on s with the device of the buffers current: one wait per round (24 bytes); stats (host memory) nullable
+int vc_distinct_run(const VcDistinctArgs& a, const VcDistinctSearch& search, vc_distinct_stats* stats, hipStream_t s, std::string* err);
+// either handle's host form: queries and the N labels staged, `run` (the device form on s) into staged outputs, which come home;
+// waits for them, then turns the valid part of every row round for VC_ORDER_FARTHEST_FIRST.  row_labels, counts, stats nullable
+struct VcDistinctHostArgs {
+  uint64_t n_labels;
+  uint32_t W, nq, k, order;
+  const void* queries;
+  const uint32_t* labels;
+  uint64_t* out;
+  uint32_t* row_labels;
+  uint32_t* counts;
+  vc_distinct_stats* stats;
+  std::function<void*(int which, size_t bytes)> alloc;
+};
+int vc_distinct_run_host(const VcDistinctHostArgs& a, const std::function<int(const uint64_t* d_queries, const uint32_t* d_labels, uint64_t* d_out,
+                                                                            uint32_t* d_row_labels, uint32_t* d_counts, vc_distinct_stats* stats)>& run,
+                         hipStream_t s, std::string* err);
 // ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
 struct VcKeepSet;
 #define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)

@@ -37,6 +37,7 @@
 #include <thread>
 #include <vector>
 
+#include "vc_distinct_plan.hpp"
 #include "vc_internal.hpp"
 #include "vc_mih.hpp"
 #include "vc_seed_plan.hpp"
@@ -157,6 +158,9 @@ enum RootBuf {
   // seeding: the id word, the statistics and best when the caller gives no assign; the host form's staging (SD_WORK + VC_SEED_*); its own,
   // every word written before it is read
   SD_WORK, SD_STAGE,
+  // one result per label group: flags, maps, retry queries and counters; the k' rows; the host form's staging (DS_WORK + VC_DISTINCT_*);
+  // its own, every word written before it is read
+  DS_WORK, DS_ROWS, DS_STAGE,
   ROOT_BUFS
 };
 
@@ -2958,6 +2962,68 @@ int vc_sharded_seed_centres(vc_sharded* h, uint32_t n_centres, uint32_t method, 
                           return sharded_seed_run(h, n_centres, method, seed, d_centres, d_picks, d_assign, st, S);
                         },
                         S, &err);
+  return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
+}
+
+}  // extern "C"
+
+// ---- one result per label group over the shards: vc_distinct.hip's driver on the root over the merged rows of the store's own search --------
+static int check_sharded_distinct_args(vc_sharded* h, const void* q, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* labels, uint32_t k_first,
+                                       const uint64_t* out) {
+  if (!h || !q || !labels || !out || nq == 0 || k == 0 || k > VC_MAX_K) return VC_ERR_INVALID;
+  if (!vc_distinct_k_first_ok(k, k_first)) return sfail(h, VC_ERR_INVALID, "k_first must be 0 or in k..%u", VC_MAX_K);
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return sfail(h, VC_ERR_INVALID, "distinct search: mode must be LINEAR or MIH_EXACT");
+  if (mode == VC_MODE_MIH_EXACT)
+    for (uint32_t g = 0; g < h->G; ++g)
+      if (shard_size(h, g) && !vc_engine_has_index(h->eng[g])) return sfail(h, VC_ERR_STATE, "shard %u: MIH search needs vc_sharded_build_index() first", g);
+  return VC_OK;
+}
+static std::function<void*(int, size_t)> sharded_distinct_alloc(vc_sharded* h) {
+  return [h](int which, size_t bytes) -> void* {   // (the search underneath leaves the root device current)
+    if (hipSetDevice(h->root) != hipSuccess) return nullptr;
+    DevBuf& b = h->buf[DS_WORK + which];
+    return b.grow(h, bytes) ? nullptr : b.p;
+  };
+}
+// All pointers on the root device, valid on S: the merged rows of the store's search are collapsed where the caller's labels live
+static int sharded_distinct_run(vc_sharded* h, const uint64_t* d_queries, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* d_labels, uint32_t k_first,
+                                uint64_t* d_out, uint32_t* d_row_labels, uint32_t* d_counts, vc_distinct_stats* stats, hipStream_t S) {
+  VS_HIP(h, hipSetDevice(h->root));
+  std::string err;
+  const int rc = vc_distinct_run(VcDistinctArgs{h->n, h->cfg.engine.id_base, h->nbytes / 8, d_queries, nq, k, k_first, d_labels, d_out, d_row_labels, d_counts,
+                                                h->knobs.distinct_scratch, mode == VC_MODE_MIH_EXACT, sharded_distinct_alloc(h)},
+                                 [&](const uint64_t* d_q, uint32_t n, uint32_t kp, uint64_t* d_rows, uint32_t* d_cnt) {
+                                   const int r = sharded_search_any(h, d_q, n, kp, mode, d_rows, d_cnt, nullptr, S);
+                                   if (r) return r;
+                                   return hipSetDevice(h->root) == hipSuccess ? VC_OK : sfail(h, VC_ERR_HIP, "hipSetDevice(root) failed");
+                                 },
+                                 stats, S, &err);
+  return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
+}
+
+extern "C" {
+
+int vc_sharded_search_knn_distinct_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* d_labels,
+                                       uint32_t k_first, uint64_t* d_out, uint32_t* d_row_labels, uint32_t* d_counts, vc_distinct_stats* stats, void* stream) {
+  const int rc = check_sharded_distinct_args(h, d_queries, nq, k, mode, d_labels, k_first, d_out);
+  if (rc) return rc;
+  return sharded_distinct_run(h, (const uint64_t*)d_queries, nq, k, mode, d_labels, k_first, d_out, d_row_labels, d_counts, stats,
+                              stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+}
+
+int vc_sharded_search_knn_distinct(vc_sharded* h, const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* labels,
+                                   uint32_t k_first, uint64_t* out, uint32_t* row_labels, uint32_t* counts, vc_distinct_stats* stats) {
+  int rc = check_sharded_distinct_args(h, queries, nq, k, mode, labels, k_first, out);
+  if (rc) return rc;
+  if (order > VC_ORDER_FARTHEST_FIRST) return VC_ERR_INVALID;
+  hipStream_t S = h->root_stream;
+  VS_HIP(h, hipSetDevice(h->root));
+  std::string err;
+  rc = vc_distinct_run_host(VcDistinctHostArgs{h->n, h->nbytes / 8, nq, k, order, queries, labels, out, row_labels, counts, stats, sharded_distinct_alloc(h)},
+                            [&](const uint64_t* d_q, const uint32_t* d_labels, uint64_t* d_out, uint32_t* d_rl, uint32_t* d_cnt, vc_distinct_stats* st) {
+                              return sharded_distinct_run(h, d_q, nq, k, mode, d_labels, k_first, d_out, d_rl, d_cnt, st, S);
+                            },
+                            S, &err);
   return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
 }
 

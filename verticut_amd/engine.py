@@ -52,7 +52,9 @@ EXPORTS = [
     "vc_assign_nearest", "vc_assign_nearest_dev", "vc_sharded_assign_nearest", "vc_sharded_assign_nearest_dev",
     "vc_kmajority", "vc_kmajority_dev", "vc_sharded_kmajority", "vc_sharded_kmajority_dev",
     "vc_seed_centres", "vc_seed_centres_dev", "vc_sharded_seed_centres", "vc_sharded_seed_centres_dev",
+    "vc_search_knn_distinct", "vc_search_knn_distinct_dev", "vc_sharded_search_knn_distinct", "vc_sharded_search_knn_distinct_dev",
 ]
+DISTINCT_TRUNCATED = 0x80000000   # VC_DISTINCT_TRUNCATED: flag in a count of search_knn_distinct -- the row holds the groups found within the 8192 nearest records
 SEED_FARTHEST, SEED_WEIGHTED = 0, 1   # VC_SEED_FARTHEST: farthest-first traversal; VC_SEED_WEIGHTED: distance-weighted sampling ("k-majority++")
 KMAJ_MAX_ITERS = 64       # VC_KMAJ_MAX_ITERS: kmajority takes max_iters 0 .. 64
 LEVELS_MAX = 64           # VC_LEVELS_MAX: cluster_levels and dbscan_levels take max_radius 0 .. 63
@@ -126,6 +128,14 @@ class VcSeedStats(C.Structure):
 
     def as_dict(self):
         """{cost, radius, n_zero_picks: int}"""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class VcDistinctStats(C.Structure):
+    _fields_ = [("n_rounds", C.c_uint32), ("k_last", C.c_uint32), ("n_searched", C.c_uint64), ("n_truncated", C.c_uint64), ("n_short", C.c_uint64)]
+
+    def as_dict(self):
+        """{n_rounds, k_last, n_searched, n_truncated, n_short: int}"""
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
@@ -263,6 +273,10 @@ def load_library():
     L.vc_seed_centres_dev.argtypes = [vp, u32, u32, u64, vp, vp, vp, vp, vp]
     L.vc_sharded_seed_centres.argtypes = [vp, u32, u32, u64, vp, vp, vp, vp]
     L.vc_sharded_seed_centres_dev.argtypes = [vp, u32, u32, u64, vp, vp, vp, vp, vp]
+    L.vc_search_knn_distinct.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, vp, vp, vp, vp]
+    L.vc_search_knn_distinct_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp]
+    L.vc_sharded_search_knn_distinct.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, vp, vp, vp, vp]
+    L.vc_sharded_search_knn_distinct_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -499,6 +513,28 @@ def _seed_centres(self, fn, k, method, seed, with_assign):
 def _seed_centres_dev(self, fn, k, d_centres, d_picks, d_assign, method, seed, with_stats, stream):
     st = VcSeedStats()
     self._check(fn(self._h, k, method, seed, d_centres, d_picks, d_assign, C.byref(st) if with_stats else None, stream))
+    return st.as_dict() if with_stats else None
+
+
+def _search_knn_distinct(self, fn, queries, k, labels, mode, order, k_first, with_stats):
+    """shared by Engine.search_knn_distinct and ShardedEngine.search_knn_distinct: (out uint64 [nq, k], row_labels uint32 [nq, k], counts
+    uint32 [nq][, stats dict])"""
+    q = np.ascontiguousarray(queries, dtype=np.uint8).reshape(-1, self.nbytes)
+    nq = q.shape[0]
+    labels = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+    if labels.shape[0] != len(self):
+        raise VcError(VC_ERR_INVALID, "the labels must have one word per resident record")
+    if labels.shape[0] == 0:
+        labels = np.zeros(1, dtype=np.uint32)       # (an empty store: the call reads no label, but takes no null pointer)
+    out, row_labels, counts = np.empty((nq, k), dtype=np.uint64), np.empty((nq, k), dtype=np.uint32), np.zeros(nq, dtype=np.uint32)
+    st = VcDistinctStats()
+    self._check(fn(self._h, _p(q), nq, k, mode, order, _p(labels), k_first, _p(out), _p(row_labels), _p(counts), C.byref(st)))
+    return (out, row_labels, counts, st.as_dict()) if with_stats else (out, row_labels, counts)
+
+
+def _search_knn_distinct_dev(self, fn, d_queries, nq, k, d_labels, d_out, d_row_labels, d_counts, mode, k_first, with_stats, stream):
+    st = VcDistinctStats()
+    self._check(fn(self._h, d_queries, nq, k, mode, d_labels, k_first, d_out, d_row_labels, d_counts, C.byref(st) if with_stats else None, stream))
     return st.as_dict() if with_stats else None
 
 
@@ -863,6 +899,21 @@ class Engine:
         None and the host waits for nothing."""
         return _seed_centres_dev(self, self._L.vc_seed_centres_dev, k, d_centres, d_picks, d_assign, method, seed, with_stats, stream)
 
+    def search_knn_distinct(self, queries, k, labels, mode=MODE_LINEAR, order=ORDER_ASCENDING, k_first=0, with_stats=False):
+        """vc_search_knn_distinct: the k nearest label GROUPS of every query, each by its member nearest to the query.  labels: one
+        uint32 per resident record as cluster_radius, leaders_radius, dbscan_radius, kmajority or group_summary's group_index write
+        them -- only equality matters.  Returns (out [nq, k] uint64, row_labels [nq, k] uint32, counts [nq][, stats dict]); a count
+        may carry DISTINCT_TRUNCATED.  mode MODE_LINEAR or MODE_MIH_EXACT; k_first: the first round's k' (0 = min(8192, 2 k)), which
+        changes the statistics, never a finished row.  Stages the labels on every call: search_knn_distinct_dev keeps them in HBM."""
+        return _search_knn_distinct(self, self._L.vc_search_knn_distinct, queries, k, labels, mode, order, k_first, with_stats)
+
+    def search_knn_distinct_dev(self, d_queries, nq, k, d_labels, d_out, d_row_labels=None, d_counts=None, mode=MODE_LINEAR, k_first=0, with_stats=True,
+                                stream=None):
+        """vc_search_knn_distinct_dev: raw device addresses; the host waits once per round, results valid in `stream` order.
+        Returns the stats dict; with_stats=False returns None."""
+        return _search_knn_distinct_dev(self, self._L.vc_search_knn_distinct_dev, d_queries, nq, k, d_labels, d_out, d_row_labels, d_counts, mode, k_first,
+                                        with_stats, stream)
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -1161,6 +1212,21 @@ class ShardedEngine:
         """vc_sharded_seed_centres_dev: raw device addresses on the root device; outputs valid in `stream` order.  Returns the stats dict; with_stats=False returns
         None (the root still waits once or twice per round)."""
         return _seed_centres_dev(self, self._L.vc_sharded_seed_centres_dev, k, d_centres, d_picks, d_assign, method, seed, with_stats, stream)
+
+    def search_knn_distinct(self, queries, k, labels, mode=MODE_LINEAR, order=ORDER_ASCENDING, k_first=0, with_stats=False):
+        """vc_sharded_search_knn_distinct: the k nearest label GROUPS of every query, each by its member nearest to the query.  labels: one
+        uint32 per resident record as cluster_radius, leaders_radius, dbscan_radius, kmajority or group_summary's group_index write
+        them -- only equality matters.  Returns (out [nq, k] uint64, row_labels [nq, k] uint32, counts [nq][, stats dict]); a count
+        may carry DISTINCT_TRUNCATED.  mode MODE_LINEAR or MODE_MIH_EXACT; k_first: the first round's k' (0 = min(8192, 2 k)), which
+        changes the statistics, never a finished row.  Stages the labels on every call: search_knn_distinct_dev keeps them in HBM."""
+        return _search_knn_distinct(self, self._L.vc_sharded_search_knn_distinct, queries, k, labels, mode, order, k_first, with_stats)
+
+    def search_knn_distinct_dev(self, d_queries, nq, k, d_labels, d_out, d_row_labels=None, d_counts=None, mode=MODE_LINEAR, k_first=0, with_stats=True,
+                                stream=None):
+        """vc_sharded_search_knn_distinct_dev: raw device addresses on the root device; the host waits once per round, results valid in `stream` order.
+        Returns the stats dict; with_stats=False returns None."""
+        return _search_knn_distinct_dev(self, self._L.vc_sharded_search_knn_distinct_dev, d_queries, nq, k, d_labels, d_out, d_row_labels, d_counts, mode, k_first,
+                                        with_stats, stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

@@ -150,6 +150,11 @@ class Backend {
   // seeds for kmajority() made on the device (vc_seed_centres / vc_sharded_seed_centres): method VC_SEED_FARTHEST or VC_SEED_WEIGHTED;
   // centres out; picks (id | pick distance << 32), assign (as assign_nearest(centres) over everything) and stats may be null
   virtual int seed_centres(uint32_t n_centres, uint32_t method, uint64_t seed, void* centres, uint64_t* picks, uint64_t* assign, vc_seed_stats* stats) = 0;
+  // the k nearest label groups of every query, each by its member nearest to the query (vc_search_knn_distinct /
+  // vc_sharded_search_knn_distinct): labels as any grouper above writes them, N entries; mode VC_MODE_LINEAR or VC_MODE_MIH_EXACT;
+  // k_first 0 = the default first k'; row_labels, counts and stats may be null; a count may carry VC_DISTINCT_TRUNCATED
+  virtual int search_knn_distinct(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* labels, uint32_t k_first,
+                                  uint64_t* out, uint32_t* row_labels, uint32_t* counts, vc_distinct_stats* stats) = 0;
   // records taken out of the store and its index, the survivors renumbered in order (vc_retain / vc_sharded_retain; the reference has
   // no delete: this stands for build_hash_tables.cc run again over the code file without them).  kind VC_RETAIN_MASK / VC_RETAIN_ROOTS
   virtual int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) = 0;
@@ -231,6 +236,10 @@ class Engine : public Backend {
   }
   int seed_centres(uint32_t n_centres, uint32_t method, uint64_t seed, void* centres, uint64_t* picks, uint64_t* assign, vc_seed_stats* stats) override {
     return vc_seed_centres(h_, n_centres, method, seed, centres, picks, assign, stats);
+  }
+  int search_knn_distinct(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* labels, uint32_t k_first,
+                          uint64_t* out, uint32_t* row_labels, uint32_t* counts, vc_distinct_stats* stats) override {
+    return vc_search_knn_distinct(h_, queries, nq, k, mode, order, labels, k_first, out, row_labels, counts, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_retain(h_, sel, kind, new_ids, n_kept); }
  private:
@@ -340,6 +349,10 @@ class ShardedEngine : public Backend {
   }
   int seed_centres(uint32_t n_centres, uint32_t method, uint64_t seed, void* centres, uint64_t* picks, uint64_t* assign, vc_seed_stats* stats) override {
     return vc_sharded_seed_centres(h_, n_centres, method, seed, centres, picks, assign, stats);
+  }
+  int search_knn_distinct(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* labels, uint32_t k_first,
+                          uint64_t* out, uint32_t* row_labels, uint32_t* counts, vc_distinct_stats* stats) override {
+    return vc_sharded_search_knn_distinct(h_, queries, nq, k, mode, order, labels, k_first, out, row_labels, counts, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_sharded_retain(h_, sel, kind, new_ids, n_kept); }
  private:
