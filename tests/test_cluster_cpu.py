@@ -39,7 +39,7 @@ def test_cluster_kernels_use_no_lds_and_no_scratch(vc):
     """vc_cluster.o holds exactly the three vc_cluster_* kernels: no scratch, no spills, no LDS (there is no plan and no chunk
     table: a thread finds its query by binary search)"""
     from verticut_amd import build as vb
-    assert "vc_cluster.hip" in vb.SOURCES
+    assert "vc_cluster.hip" in vb.SOURCES and "vc_walk.hip" in vb.SOURCES
     res = vb.kernel_resources(os.path.join(vb.LIBDIR, "vc_cluster.o"))
     assert len(res) == 3, sorted(res)
     for kernel in ("vc_cluster_init_kernel", "vc_cluster_union_kernel", "vc_cluster_flatten_kernel"):      # (mangled names)

@@ -92,3 +92,33 @@ hipError_t vc_launch_cluster_flatten(uint32_t* d_labels, uint64_t n, uint32_t id
   hipLaunchKernelGGL(vc_cluster_flatten_kernel, dim3(cl_grid(n)), dim3(CL_BLK), 0, s, d_labels, n, id_base, (unsigned long long*)d_n_clusters);
   return hipGetLastError();
 }
+
+int vc_cluster_run(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_cluster_stats* stats, hipStream_t s,
+                   std::string* err) {
+  const uint64_t first_new = (uint64_t)v.id_base + n_labelled;
+  uint64_t* d_stat = (uint64_t*)v.alloc(VC_WALK_STAT, 16);
+  if (!d_stat) return VC_ERR_NOMEM;
+  VC_WALK_HIP(hipMemsetAsync(d_stat, 0, 16, s));
+  VC_WALK_HIP(vc_launch_cluster_init(d_labels + n_labelled, v.n - n_labelled, (uint32_t)first_new, s));
+  const int rc = vc_walk_run(v, n_labelled, batch, radius, [&](const VcWalkBatch& b) -> int {   // the union over the raw result as it lies; no compaction
+    VC_WALK_HIP(vc_launch_cluster_union(b.d_raw, b.d_roffs, b.nq, b.raw_total, b.first_id, first_new, v.id_base, d_labels, d_stat, s));
+    return VC_OK;
+  }, s, err);
+  if (rc) return rc;
+  VC_WALK_HIP(vc_launch_cluster_flatten(d_labels, v.n, v.id_base, d_stat + 1, s));
+  uint64_t st[2] = {0, 0};
+  VC_WALK_HIP(hipMemcpyAsync(st, d_stat, 16, hipMemcpyDeviceToHost, s));
+  VC_WALK_HIP(hipStreamSynchronize(s));
+  if (stats) *stats = vc_cluster_stats{st[0], st[1]};
+  return VC_OK;
+}
+
+int vc_cluster_run_host(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats, hipStream_t s,
+                        std::string* err) {
+  uint32_t* d_labels = nullptr;
+  int rc = vc_walk_stage_labels(v, labels, 1, n_labelled, &d_labels, s, err);
+  if (rc || (rc = vc_cluster_run(v, radius, batch, n_labelled, d_labels, stats, s, err))) return rc;
+  VC_WALK_HIP(hipMemcpyAsync(labels, d_labels, (size_t)v.n * 4, hipMemcpyDeviceToHost, s));
+  VC_WALK_HIP(hipStreamSynchronize(s));
+  return VC_OK;
+}

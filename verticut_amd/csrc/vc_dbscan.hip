@@ -137,3 +137,38 @@ hipError_t vc_launch_dbscan_finish(uint32_t* d_labels, const uint32_t* d_degrees
                      (unsigned long long*)d_counts);
   return hipGetLastError();
 }
+
+int vc_dbscan_run(const VcWalkView& v, uint32_t radius, uint32_t min_pts, uint32_t batch, uint32_t* d_labels, uint32_t* d_degrees, vc_dbscan_stats* stats,
+                  hipStream_t s, std::string* err) {
+  const uint64_t N = v.n;
+  uint64_t* d_stat = (uint64_t*)v.alloc(VC_WALK_STAT, VC_DBSCAN_STAT_BYTES);
+  if (!d_stat) return VC_ERR_NOMEM;
+  if (!d_degrees && !(d_degrees = (uint32_t*)v.alloc(VC_WALK_RECORD, (size_t)N * 4))) return VC_ERR_NOMEM;
+  VC_WALK_HIP(hipMemsetAsync(d_stat, 0, VC_DBSCAN_STAT_BYTES, s));
+  VC_WALK_HIP(vc_launch_cluster_init(d_labels, N, v.id_base, s));
+  const int rc = vc_walk_run(v, 0, batch, radius, [&](const VcWalkBatch& b) -> int {   // the batch's degrees, then its edges over the raw result as it lies
+    VC_WALK_HIP(vc_launch_dbscan_edges(b.d_raw, b.d_roffs, b.nq, b.raw_total, b.first_id, v.id_base, min_pts, d_degrees, d_labels, d_stat, s));
+    return VC_OK;
+  }, s, err);
+  if (rc) return rc;
+  VC_WALK_HIP(vc_launch_dbscan_finish(d_labels, d_degrees, N, v.id_base, min_pts, d_stat + 1, s));
+  uint64_t st[5] = {0, 0, 0, 0, 0};
+  VC_WALK_HIP(hipMemcpyAsync(st, d_stat, VC_DBSCAN_STAT_BYTES, hipMemcpyDeviceToHost, s));
+  VC_WALK_HIP(hipStreamSynchronize(s));
+  if (stats) *stats = vc_dbscan_stats{st[0], st[1], st[2], st[3], st[4]};
+  return VC_OK;
+}
+
+int vc_dbscan_run_host(const VcWalkView& v, uint32_t radius, uint32_t min_pts, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats,
+                       hipStream_t s, std::string* err) {
+  const size_t bytes = (size_t)v.n * 4;
+  uint32_t* d_labels = nullptr;
+  uint32_t* d_degrees = (uint32_t*)v.alloc(VC_WALK_RECORD, bytes);
+  if (!d_degrees) return VC_ERR_NOMEM;
+  int rc = vc_walk_stage_labels(v, labels, 1, 0, &d_labels, s, err);
+  if (rc || (rc = vc_dbscan_run(v, radius, min_pts, batch, d_labels, d_degrees, stats, s, err))) return rc;
+  VC_WALK_HIP(hipMemcpyAsync(labels, d_labels, bytes, hipMemcpyDeviceToHost, s));
+  if (degrees) VC_WALK_HIP(hipMemcpyAsync(degrees, d_degrees, bytes, hipMemcpyDeviceToHost, s));
+  VC_WALK_HIP(hipStreamSynchronize(s));
+  return VC_OK;
+}

@@ -200,3 +200,40 @@ hipError_t vc_launch_dbscan_levels_finish(uint32_t* d_labels, const uint32_t* d_
                      (unsigned long long*)d_counts);
   return hipGetLastError();
 }
+
+int vc_dbscan_levels_run(const VcWalkView& v, uint32_t max_radius, uint32_t min_pts, uint32_t batch, uint32_t* d_labels, uint32_t* d_core_dist,
+                         vc_dbscan_levels_stats* stats, hipStream_t s, std::string* err) {
+  const uint64_t N = v.n;
+  uint64_t* d_stat = (uint64_t*)v.alloc(VC_WALK_STAT, VC_DBSCAN_LEVELS_STAT_BYTES);
+  if (!d_stat) return VC_ERR_NOMEM;
+  if (!d_core_dist && !(d_core_dist = (uint32_t*)v.alloc(VC_WALK_RECORD, (size_t)N * 4))) return VC_ERR_NOMEM;
+  VC_WALK_HIP(hipMemsetAsync(d_stat, 0, VC_DBSCAN_LEVELS_STAT_BYTES, s));
+  for (uint32_t r = 0; r <= max_radius; ++r) VC_WALK_HIP(vc_launch_cluster_init(d_labels + (uint64_t)r * N, N, v.id_base, s));
+  const int rc = vc_walk_run(v, 0, batch, max_radius, [&](const VcWalkBatch& b) -> int {   // the batch's core distances, then its edges over the raw result
+    VC_WALK_HIP(vc_launch_dbscan_levels_edges(b.d_raw, b.d_roffs, b.nq, b.raw_total, b.first_id, v.id_base, N, max_radius, min_pts, d_core_dist, d_labels,
+                                              d_stat, s));
+    return VC_OK;
+  }, s, err);
+  if (rc) return rc;
+  VC_WALK_HIP(vc_launch_dbscan_levels_cascade(d_labels, d_core_dist, N, v.id_base, max_radius, s));
+  VC_WALK_HIP(vc_launch_dbscan_levels_finish(d_labels, d_core_dist, N, v.id_base, max_radius, d_stat + VC_LEVELS_MAX, s));
+  vc_dbscan_levels_stats st;
+  VC_WALK_HIP(hipMemcpyAsync(&st, d_stat, VC_DBSCAN_LEVELS_STAT_BYTES, hipMemcpyDeviceToHost, s));
+  VC_WALK_HIP(hipStreamSynchronize(s));
+  if (stats) *stats = st;
+  return VC_OK;
+}
+
+int vc_dbscan_levels_run_host(const VcWalkView& v, uint32_t max_radius, uint32_t min_pts, uint32_t batch, uint32_t* labels, uint32_t* core_dist,
+                              vc_dbscan_levels_stats* stats, hipStream_t s, std::string* err) {
+  const size_t N = (size_t)v.n, levels = (size_t)max_radius + 1;
+  uint32_t* d_labels = nullptr;
+  uint32_t* d_core_dist = (uint32_t*)v.alloc(VC_WALK_RECORD, N * 4);
+  if (!d_core_dist) return VC_ERR_NOMEM;
+  int rc = vc_walk_stage_labels(v, labels, levels, 0, &d_labels, s, err);
+  if (rc || (rc = vc_dbscan_levels_run(v, max_radius, min_pts, batch, d_labels, d_core_dist, stats, s, err))) return rc;
+  VC_WALK_HIP(hipMemcpyAsync(labels, d_labels, levels * N * 4, hipMemcpyDeviceToHost, s));
+  if (core_dist) VC_WALK_HIP(hipMemcpyAsync(core_dist, d_core_dist, N * 4, hipMemcpyDeviceToHost, s));
+  VC_WALK_HIP(hipStreamSynchronize(s));
+  return VC_OK;
+}

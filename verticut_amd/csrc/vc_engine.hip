@@ -61,31 +61,10 @@ struct vc_engine {
   uint32_t* d_rhids = nullptr;  size_t rhids_bytes = 0;
   uint64_t* d_rhout = nullptr;  size_t rhout_bytes = 0;
   uint64_t* d_rhoffs = nullptr; size_t rhoffs_bytes = 0;
-  // near-duplicate clustering (vc_cluster_radius*): a batch's ids, gathered queries and found words, the raw results and offsets of
-  // the search underneath, the two counters (pairs, clusters); and the host-pointer form's staged labels
-  uint32_t* d_cids = nullptr;   size_t cids_bytes = 0;
-  uint64_t* d_cq = nullptr;     size_t cq_bytes = 0;
-  uint32_t* d_cfound = nullptr; size_t cfound_bytes = 0;
-  uint64_t* d_craw = nullptr;   size_t craw_bytes = 0;
-  uint64_t* d_croffs = nullptr; size_t croffs_bytes = 0;
-  uint64_t* d_cstat = nullptr;  size_t cstat_bytes = 0;
-  uint32_t* d_chlab = nullptr;  size_t chlab_bytes = 0;
-  // greedy leader dedup (vc_leaders_radius*): it shares the batch buffers and the staged labels above (both calls fill them completely);
-  // its own are a batch's state words and the statistics with the round counters
-  uint32_t* d_lstate = nullptr; size_t lstate_bytes = 0;
-  uint64_t* d_lstat = nullptr;  size_t lstat_bytes = 0;
-  // density clustering (vc_dbscan_radius*): it shares the same batch buffers and staged labels (it fills them completely too); its
-  // own are the degrees of a call that passes none (and of the host form) and the five statistics
-  uint32_t* d_ddeg = nullptr;   size_t ddeg_bytes = 0;
-  uint64_t* d_dstat = nullptr;  size_t dstat_bytes = 0;
-  // clusters at every radius (vc_cluster_levels*): it shares the same batch buffers and the staged labels, grown to all levels (it fills
-  // them completely too); its own are the 2 x 64 counters (vc_levels_stats as it lies)
-  uint64_t* d_vstat = nullptr;  size_t vstat_bytes = 0;
-  // density clustering at every radius (vc_dbscan_levels*): it shares the same batch buffers and the staged labels, grown to all levels
-  // (it fills them completely too); its own are the core distances of a call that passes none (and of the host form) and the 5 x 64
-  // counters (vc_dbscan_levels_stats as it lies)
-  uint32_t* d_wcd = nullptr;    size_t wcd_bytes = 0;
-  uint64_t* d_wstat = nullptr;  size_t wstat_bytes = 0;
+  // the clustering calls over the radius-graph walk (vc_cluster_radius*, vc_cluster_levels*, vc_leaders_radius*, vc_dbscan_radius*,
+  // vc_dbscan_levels*): the walk's batch buffers, the statistics, the per-record words, leaders' state words and the host forms' staged
+  // labels (VC_WALK_*); shared by the five calls, each writes every word it reads
+  uint8_t* d_walk[VC_WALK_BUFS] = {};  size_t walk_bytes[VC_WALK_BUFS] = {};
   // label groups summarised (vc_group_summary*): the sort and numbering arrays, the row buffer with the big groups' tables, the host
   // form's staging (VC_GROUPS_*); its own, shared with no other call, every word written before it is read
   uint8_t* d_grp[VC_GROUPS_BUFS] = {nullptr, nullptr, nullptr};  size_t grp_bytes[VC_GROUPS_BUFS] = {0, 0, 0};
@@ -392,20 +371,7 @@ int vc_destroy(vc_engine* e) {
   (void)hipFree(e->d_rhids);
   (void)hipFree(e->d_rhout);
   (void)hipFree(e->d_rhoffs);
-  (void)hipFree(e->d_cids);
-  (void)hipFree(e->d_cq);
-  (void)hipFree(e->d_cfound);
-  (void)hipFree(e->d_craw);
-  (void)hipFree(e->d_croffs);
-  (void)hipFree(e->d_cstat);
-  (void)hipFree(e->d_chlab);
-  (void)hipFree(e->d_lstate);
-  (void)hipFree(e->d_lstat);
-  (void)hipFree(e->d_ddeg);
-  (void)hipFree(e->d_dstat);
-  (void)hipFree(e->d_vstat);
-  (void)hipFree(e->d_wcd);
-  (void)hipFree(e->d_wstat);
+  for (uint8_t* b : e->d_walk) (void)hipFree(b);
   for (uint8_t* b : e->d_grp) (void)hipFree(b);
   for (uint8_t* b : e->d_kmaj) (void)hipFree(b);
   for (uint8_t* b : e->d_seed) (void)hipFree(b);
@@ -1296,447 +1262,158 @@ int vc_search_radius_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_
 
 }  // extern "C"
 
-// ---- near-duplicate clustering: the connected components of the radius graph ----------------------------------------------------------
-static int check_cluster_args(vc_engine* e, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
+// ---- the clustering calls over the radius-graph walk: near-duplicate clusters (vc_cluster.hip), clusters at every radius (vc_levels.hip),
+// greedy leaders (vc_leaders.hip), density clustering at one radius (vc_dbscan.hip) and at every radius (vc_dbscan_levels.hip).  The
+// drivers are theirs and vc_walk.hip's; here are the argument checks, the engine's view and the entry points. ------------------------
+// what: the call's name in the texts.  A call at one radius passes max_radius = 0, one without min_pts 1, one that labels every record
+// n_labelled = 0.
+static int check_walk_args(vc_engine* e, const char* what, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
   if (!e || !labels) return VC_ERR_INVALID;
-  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "cluster: mode must be LINEAR or MIH_EXACT");
-  if (n_labelled > e->n) return fail(e, VC_ERR_INVALID, "cluster: n_labelled %llu exceeds the %llu resident records", (unsigned long long)n_labelled, (unsigned long long)e->n);
+  if (min_pts == 0) return fail(e, VC_ERR_INVALID, "%s: min_pts must be at least 1", what);
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "%s: mode must be LINEAR or MIH_EXACT", what);
+  if (max_radius >= VC_LEVELS_MAX) return fail(e, VC_ERR_INVALID, "%s: max_radius %u exceeds %u", what, max_radius, VC_LEVELS_MAX - 1);
+  if (n_labelled > e->n) return fail(e, VC_ERR_INVALID, "%s: n_labelled %llu exceeds the %llu resident records", what, (unsigned long long)n_labelled, (unsigned long long)e->n);
   if (e->n && mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
   return VC_OK;
 }
 
-// The whole call on e->stream (inside the caller's StreamCall), e->n > 0.  Per batch of ids: the ids filled on the device, the gather,
-// the radius search into the handle's scratch -- repeated once with the scratch grown to the total it reported -- and the union over
-// the raw result as it lies; no compaction.  After the last batch one flatten, then the one wait for the two counters.
-static int cluster_run(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_cluster_stats* stats) {
-  int rc;
-  const uint64_t N = e->n, first_new = (uint64_t)e->cfg.id_base + n_labelled;
-  if (batch == 0) batch = VC_CLUSTER_BATCH;
-  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N - n_labelled);
-  if ((rc = grow(e, &e->d_cstat, &e->cstat_bytes, 16))) return rc;
-  if (nq_max) {
-    if ((rc = grow(e, &e->d_cids, &e->cids_bytes, (size_t)nq_max * 4))) return rc;
-    if ((rc = grow(e, &e->d_cq, &e->cq_bytes, (size_t)nq_max * e->W * 8))) return rc;
-    if ((rc = grow(e, &e->d_cfound, &e->cfound_bytes, (size_t)nq_max * 4))) return rc;
-    if ((rc = grow(e, &e->d_croffs, &e->croffs_bytes, ((size_t)nq_max + 1) * 8))) return rc;
-    if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)8 << 16))) return rc;
-  }
-  VC_HIP(e, hipMemsetAsync(e->d_cstat, 0, 16, e->stream));
-  VC_HIP(e, vc_launch_cluster_init(d_labels + n_labelled, N - n_labelled, (uint32_t)first_new, e->stream));
-  for (uint64_t pos = n_labelled; pos < N; pos += batch) {
-    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = e->cfg.id_base + (uint32_t)pos;
-    VC_HIP(e, vc_launch_cluster_init(e->d_cids, nq, first_id, e->stream));
-    VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, e->d_cids, nq, e->d_cq, e->d_cfound, e->stream));
-    uint64_t raw_total = 0;
-    for (int attempt = 0;; ++attempt) {
-      const uint64_t cap = e->craw_bytes / 8;
-      rc = vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, e->d_cq, nq,
-                            radius, e->d_craw, cap, e->d_croffs, true, &e->radius_work, e->stream, &e->err, &raw_total);
-      if (rc == VC_OK) break;
-      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
-      if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)raw_total * 8))) return rc;   // (the first attempt has been waited for)
-    }
-    VC_HIP(e, vc_launch_cluster_union(e->d_craw, e->d_croffs, nq, raw_total, first_id, first_new, e->cfg.id_base, d_labels, e->d_cstat, e->stream));
-  }
-  VC_HIP(e, vc_launch_cluster_flatten(d_labels, N, e->cfg.id_base, e->d_cstat + 1, e->stream));
-  uint64_t st[2] = {0, 0};
-  VC_HIP(e, hipMemcpyAsync(st, e->d_cstat, 16, hipMemcpyDeviceToHost, e->stream));
-  VC_HIP(e, hipStreamSynchronize(e->stream));
-  if (stats) {
-    stats->n_pairs = st[0];
-    stats->n_clusters = st[1];
-  }
-  return VC_OK;
+// The engine as the walk sees it, inside the caller's StreamCall: everything goes to e->stream, the one device is current throughout.
+static VcWalkView walk_view(vc_engine* e, uint32_t mode) {
+  VcWalkView v;
+  v.n = e->n;
+  v.id_base = e->cfg.id_base;
+  v.W = e->W;
+  v.alloc = [e](int which, size_t bytes) -> void* { return grow(e, &e->d_walk[which], &e->walk_bytes[which], bytes) ? nullptr : e->d_walk[which]; };
+  v.held = [e](int which) { return e->walk_bytes[which]; };
+  v.gather = [e](const uint32_t* d_ids, uint32_t nq, uint64_t* d_q, uint32_t* d_found) -> int {
+    VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, d_ids, nq, d_q, d_found, e->stream));
+    return VC_OK;
+  };
+  v.search = [e, mode](const uint64_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_raw, uint64_t cap, uint64_t* d_roffs, uint64_t* raw_total) {
+    return vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, d_q, nq, radius,
+                            d_raw, cap, d_roffs, true, &e->radius_work, e->stream, &e->err, raw_total);
+  };
+  return v;
+}
+
+// An entry point after its checks, e->n > 0: the device bound, `run` (a vc_*_run or vc_*_run_host) on stream s inside a StreamCall.
+template <class Run>
+static int walk_call(vc_engine* e, hipStream_t s, const Run& run) {
+  int rc = bind_device(e);
+  if (rc) return rc;
+  const StreamCall call(e, s);
+  std::string err;
+  rc = run(e->stream, &err);
+  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;   // (a closure of the view has left its own text)
 }
 
 extern "C" {
 
 int vc_cluster_radius_dev(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
                           vc_cluster_stats* stats, void* stream) {
-  int rc = check_cluster_args(e, mode, n_labelled, d_labels);
+  int rc = check_walk_args(e, "cluster", 0, 1, mode, n_labelled, d_labels);
   if (rc) return rc;
   if (stats) *stats = vc_cluster_stats{0, 0};
   if (e->n == 0) return VC_OK;
-  if ((rc = bind_device(e))) return rc;
-  const StreamCall call(e, caller_stream(e, stream));
-  return cluster_run(e, radius, mode, batch, n_labelled, d_labels, stats);
+  return walk_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_cluster_run(walk_view(e, mode), radius, batch, n_labelled, d_labels, stats, s, err);
+  });
 }
 
 int vc_cluster_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats) {
-  int rc = check_cluster_args(e, mode, n_labelled, labels);
+  int rc = check_walk_args(e, "cluster", 0, 1, mode, n_labelled, labels);
   if (rc) return rc;
   if (stats) *stats = vc_cluster_stats{0, 0};
   if (e->n == 0) return VC_OK;
-  if ((rc = bind_device(e))) return rc;
-  if ((rc = grow(e, &e->d_chlab, &e->chlab_bytes, (size_t)e->n * 4))) return rc;
-  if (n_labelled) VC_HIP(e, hipMemcpyAsync(e->d_chlab, labels, (size_t)n_labelled * 4, hipMemcpyHostToDevice, e->stream));
-  {
-    const StreamCall call(e, e->stream);
-    rc = cluster_run(e, radius, mode, batch, n_labelled, e->d_chlab, stats);
-  }
-  if (rc) return rc;
-  VC_HIP(e, hipMemcpyAsync(labels, e->d_chlab, (size_t)e->n * 4, hipMemcpyDeviceToHost, e->stream));
-  VC_HIP(e, hipStreamSynchronize(e->stream));
-  return VC_OK;
+  return walk_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_cluster_run_host(walk_view(e, mode), radius, batch, n_labelled, labels, stats, s, err);
+  });
 }
-
-}  // extern "C"
-
-// ---- clusters at every radius 0 .. max_radius: one walk, one forest per level --------------------------------------------------------
-static int check_levels_args(vc_engine* e, uint32_t max_radius, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
-  if (!e || !labels) return VC_ERR_INVALID;
-  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "cluster levels: mode must be LINEAR or MIH_EXACT");
-  if (max_radius >= VC_LEVELS_MAX) return fail(e, VC_ERR_INVALID, "cluster levels: max_radius %u exceeds %u", max_radius, VC_LEVELS_MAX - 1);
-  if (n_labelled > e->n) return fail(e, VC_ERR_INVALID, "cluster levels: n_labelled %llu exceeds the %llu resident records", (unsigned long long)n_labelled, (unsigned long long)e->n);
-  if (e->n && mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
-  return VC_OK;
-}
-
-// The whole call on e->stream (inside the caller's StreamCall), e->n > 0.  cluster_run's loop over the batch buffers it shares with
-// that call (both fill them completely), at max_radius: per batch of ids the ids filled on the device, the gather, the radius search
-// -- repeated once with the scratch grown to the total it reported -- and the union over the raw result as it lies, every kept entry in
-// the forest of its distance.  After the last batch the cascade, one flatten over all levels, then the one wait for the counters.
-static int levels_run(vc_engine* e, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_levels_stats* stats) {
-  int rc;
-  const uint64_t N = e->n, first_new = (uint64_t)e->cfg.id_base + n_labelled;
-  if (batch == 0) batch = VC_CLUSTER_BATCH;
-  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N - n_labelled);
-  if ((rc = grow(e, &e->d_vstat, &e->vstat_bytes, VC_LEVELS_STAT_BYTES))) return rc;
-  if (nq_max) {
-    if ((rc = grow(e, &e->d_cids, &e->cids_bytes, (size_t)nq_max * 4))) return rc;
-    if ((rc = grow(e, &e->d_cq, &e->cq_bytes, (size_t)nq_max * e->W * 8))) return rc;
-    if ((rc = grow(e, &e->d_cfound, &e->cfound_bytes, (size_t)nq_max * 4))) return rc;
-    if ((rc = grow(e, &e->d_croffs, &e->croffs_bytes, ((size_t)nq_max + 1) * 8))) return rc;
-    if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)8 << 16))) return rc;
-  }
-  VC_HIP(e, hipMemsetAsync(e->d_vstat, 0, VC_LEVELS_STAT_BYTES, e->stream));
-  for (uint32_t r = 0; r <= max_radius; ++r)
-    VC_HIP(e, vc_launch_cluster_init(d_labels + (uint64_t)r * N + n_labelled, N - n_labelled, (uint32_t)first_new, e->stream));
-  for (uint64_t pos = n_labelled; pos < N; pos += batch) {
-    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = e->cfg.id_base + (uint32_t)pos;
-    VC_HIP(e, vc_launch_cluster_init(e->d_cids, nq, first_id, e->stream));
-    VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, e->d_cids, nq, e->d_cq, e->d_cfound, e->stream));
-    uint64_t raw_total = 0;
-    for (int attempt = 0;; ++attempt) {
-      const uint64_t cap = e->craw_bytes / 8;
-      rc = vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, e->d_cq, nq,
-                            max_radius, e->d_craw, cap, e->d_croffs, true, &e->radius_work, e->stream, &e->err, &raw_total);
-      if (rc == VC_OK) break;
-      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
-      if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)raw_total * 8))) return rc;   // (the first attempt has been waited for)
-    }
-    VC_HIP(e, vc_launch_levels_union(e->d_craw, e->d_croffs, nq, raw_total, first_id, first_new, e->cfg.id_base, N, max_radius, d_labels, e->d_vstat, e->stream));
-  }
-  VC_HIP(e, vc_launch_levels_cascade(d_labels, N, e->cfg.id_base, max_radius, e->stream));
-  VC_HIP(e, vc_launch_levels_flatten(d_labels, N, e->cfg.id_base, max_radius, e->d_vstat + VC_LEVELS_MAX, e->stream));
-  vc_levels_stats st;
-  VC_HIP(e, hipMemcpyAsync(&st, e->d_vstat, VC_LEVELS_STAT_BYTES, hipMemcpyDeviceToHost, e->stream));
-  VC_HIP(e, hipStreamSynchronize(e->stream));
-  if (stats) *stats = st;
-  return VC_OK;
-}
-
-extern "C" {
 
 int vc_cluster_levels_dev(vc_engine* e, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
                           vc_levels_stats* stats, void* stream) {
-  int rc = check_levels_args(e, max_radius, mode, n_labelled, d_labels);
+  int rc = check_walk_args(e, "cluster levels", max_radius, 1, mode, n_labelled, d_labels);
   if (rc) return rc;
   if (stats) *stats = vc_levels_stats{};
   if (e->n == 0) return VC_OK;
-  if ((rc = bind_device(e))) return rc;
-  const StreamCall call(e, caller_stream(e, stream));
-  return levels_run(e, max_radius, mode, batch, n_labelled, d_labels, stats);
+  return walk_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_levels_run(walk_view(e, mode), max_radius, batch, n_labelled, d_labels, stats, s, err);
+  });
 }
 
 int vc_cluster_levels(vc_engine* e, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_levels_stats* stats) {
-  int rc = check_levels_args(e, max_radius, mode, n_labelled, labels);
+  int rc = check_walk_args(e, "cluster levels", max_radius, 1, mode, n_labelled, labels);
   if (rc) return rc;
   if (stats) *stats = vc_levels_stats{};
   if (e->n == 0) return VC_OK;
-  if ((rc = bind_device(e))) return rc;
-  const size_t N = (size_t)e->n, levels = (size_t)max_radius + 1;
-  if ((rc = grow(e, &e->d_chlab, &e->chlab_bytes, levels * N * 4))) return rc;
-  if (n_labelled)
-    for (size_t r = 0; r < levels; ++r)
-      VC_HIP(e, hipMemcpyAsync(e->d_chlab + r * N, labels + r * N, (size_t)n_labelled * 4, hipMemcpyHostToDevice, e->stream));
-  {
-    const StreamCall call(e, e->stream);
-    rc = levels_run(e, max_radius, mode, batch, n_labelled, e->d_chlab, stats);
-  }
-  if (rc) return rc;
-  VC_HIP(e, hipMemcpyAsync(labels, e->d_chlab, levels * N * 4, hipMemcpyDeviceToHost, e->stream));
-  VC_HIP(e, hipStreamSynchronize(e->stream));
-  return VC_OK;
+  return walk_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_levels_run_host(walk_view(e, mode), max_radius, batch, n_labelled, labels, stats, s, err);
+  });
 }
-
-}  // extern "C"
-
-// ---- greedy leader dedup: the first maximal independent set of the radius graph -------------------------------------------------------
-static int check_leaders_args(vc_engine* e, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
-  if (!e || !labels) return VC_ERR_INVALID;
-  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "leaders: mode must be LINEAR or MIH_EXACT");
-  if (n_labelled > e->n) return fail(e, VC_ERR_INVALID, "leaders: n_labelled %llu exceeds the %llu resident records", (unsigned long long)n_labelled, (unsigned long long)e->n);
-  if (e->n && mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
-  return VC_OK;
-}
-
-// The whole call on e->stream (inside the caller's StreamCall), e->n > 0.  cluster_run's loop over the batch buffers it shares with
-// that call (both fill them completely): per batch of ids, in ascending order, the ids filled on the device, the gather, the radius
-// search -- repeated once with the scratch grown to the total it reported -- and the decision over the raw result as it lies, which
-// waits once per group of rounds.  Entries below n_labelled are only read.  After the last batch one count, then the wait for the stats.
-static int leaders_run(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_leader_stats* stats) {
-  int rc;
-  const uint64_t N = e->n;
-  if (batch == 0) batch = VC_CLUSTER_BATCH;
-  batch = std::min(batch, VC_LEADER_BATCH_MAX);
-  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N - n_labelled);
-  if ((rc = grow(e, &e->d_lstat, &e->lstat_bytes, VC_LEADER_STAT_BYTES))) return rc;
-  if (nq_max) {
-    if ((rc = grow(e, &e->d_cids, &e->cids_bytes, (size_t)nq_max * 4))) return rc;
-    if ((rc = grow(e, &e->d_cq, &e->cq_bytes, (size_t)nq_max * e->W * 8))) return rc;
-    if ((rc = grow(e, &e->d_cfound, &e->cfound_bytes, (size_t)nq_max * 4))) return rc;
-    if ((rc = grow(e, &e->d_croffs, &e->croffs_bytes, ((size_t)nq_max + 1) * 8))) return rc;
-    if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)8 << 16))) return rc;
-    if ((rc = grow(e, &e->d_lstate, &e->lstate_bytes, (size_t)nq_max * 4))) return rc;
-  }
-  VC_HIP(e, hipMemsetAsync(e->d_lstat, 0, VC_LEADER_STAT_BYTES, e->stream));
-  for (uint64_t pos = n_labelled; pos < N; pos += batch) {
-    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = e->cfg.id_base + (uint32_t)pos;
-    VC_HIP(e, vc_launch_cluster_init(e->d_cids, nq, first_id, e->stream));
-    VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, e->d_cids, nq, e->d_cq, e->d_cfound, e->stream));
-    uint64_t raw_total = 0;
-    for (int attempt = 0;; ++attempt) {
-      const uint64_t cap = e->craw_bytes / 8;
-      rc = vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, e->d_cq, nq,
-                            radius, e->d_craw, cap, e->d_croffs, true, &e->radius_work, e->stream, &e->err, &raw_total);
-      if (rc == VC_OK) break;
-      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
-      if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)raw_total * 8))) return rc;   // (the first attempt has been waited for)
-    }
-    bool stuck = false;
-    VC_HIP(e, vc_leaders_decide_batch(e->d_craw, e->d_croffs, nq, first_id, e->cfg.id_base, d_labels, e->d_lstate, e->d_lstat, e->stream, &stuck));
-    if (stuck) return fail(e, VC_ERR_HIP, "leaders: the batch at id %u is undecided after %u rounds", first_id, nq);
-  }
-  VC_HIP(e, vc_launch_leaders_count(d_labels, N, e->cfg.id_base, e->d_lstat + 1, e->stream));
-  uint64_t st[3] = {0, 0, 0};
-  VC_HIP(e, hipMemcpyAsync(st, e->d_lstat, 24, hipMemcpyDeviceToHost, e->stream));
-  VC_HIP(e, hipStreamSynchronize(e->stream));
-  if (stats) *stats = vc_leader_stats{st[0], st[1], st[2]};
-  return VC_OK;
-}
-
-extern "C" {
 
 int vc_leaders_radius_dev(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
                           vc_leader_stats* stats, void* stream) {
-  int rc = check_leaders_args(e, mode, n_labelled, d_labels);
+  int rc = check_walk_args(e, "leaders", 0, 1, mode, n_labelled, d_labels);
   if (rc) return rc;
   if (stats) *stats = vc_leader_stats{0, 0, 0};
   if (e->n == 0) return VC_OK;
-  if ((rc = bind_device(e))) return rc;
-  const StreamCall call(e, caller_stream(e, stream));
-  return leaders_run(e, radius, mode, batch, n_labelled, d_labels, stats);
+  return walk_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_leaders_run(walk_view(e, mode), radius, batch, n_labelled, d_labels, stats, s, err);
+  });
 }
 
 int vc_leaders_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats) {
-  int rc = check_leaders_args(e, mode, n_labelled, labels);
+  int rc = check_walk_args(e, "leaders", 0, 1, mode, n_labelled, labels);
   if (rc) return rc;
   if (stats) *stats = vc_leader_stats{0, 0, 0};
   if (e->n == 0) return VC_OK;
-  if ((rc = bind_device(e))) return rc;
-  if ((rc = grow(e, &e->d_chlab, &e->chlab_bytes, (size_t)e->n * 4))) return rc;
-  if (n_labelled) VC_HIP(e, hipMemcpyAsync(e->d_chlab, labels, (size_t)n_labelled * 4, hipMemcpyHostToDevice, e->stream));
-  {
-    const StreamCall call(e, e->stream);
-    rc = leaders_run(e, radius, mode, batch, n_labelled, e->d_chlab, stats);
-  }
-  if (rc) return rc;
-  if (n_labelled < e->n)   // the incoming entries are read only: they do not travel back
-    VC_HIP(e, hipMemcpyAsync(labels + n_labelled, e->d_chlab + n_labelled, (size_t)(e->n - n_labelled) * 4, hipMemcpyDeviceToHost, e->stream));
-  VC_HIP(e, hipStreamSynchronize(e->stream));
-  return VC_OK;
+  return walk_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_leaders_run_host(walk_view(e, mode), radius, batch, n_labelled, labels, stats, s, err);
+  });
 }
-
-}  // extern "C"
-
-// ---- density clustering: DBSCAN over the radius graph ---------------------------------------------------------------------------------
-static int check_dbscan_args(vc_engine* e, uint32_t min_pts, uint32_t mode, const uint32_t* labels) {
-  if (!e || !labels) return VC_ERR_INVALID;
-  if (min_pts == 0) return fail(e, VC_ERR_INVALID, "dbscan: min_pts must be at least 1");
-  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "dbscan: mode must be LINEAR or MIH_EXACT");
-  if (e->n && mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
-  return VC_OK;
-}
-
-// The whole call on e->stream (inside the caller's StreamCall), e->n > 0.  cluster_run's loop over the batch buffers it shares with
-// that call (both fill them completely): per batch of ids, in ascending order, the ids filled on the device, the gather, the radius
-// search -- repeated once with the scratch grown to the total it reported -- then the batch's degrees and its edges over the raw
-// result as it lies.  d_degrees null: the handle's own.  After the last batch one finish pass, then the one wait for the stats.
-static int dbscan_run(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels, uint32_t* d_degrees,
-                      vc_dbscan_stats* stats) {
-  int rc;
-  const uint64_t N = e->n;
-  if (batch == 0) batch = VC_CLUSTER_BATCH;
-  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N);
-  if ((rc = grow(e, &e->d_dstat, &e->dstat_bytes, VC_DBSCAN_STAT_BYTES))) return rc;
-  if (!d_degrees) {
-    if ((rc = grow(e, &e->d_ddeg, &e->ddeg_bytes, (size_t)N * 4))) return rc;
-    d_degrees = e->d_ddeg;
-  }
-  if ((rc = grow(e, &e->d_cids, &e->cids_bytes, (size_t)nq_max * 4))) return rc;
-  if ((rc = grow(e, &e->d_cq, &e->cq_bytes, (size_t)nq_max * e->W * 8))) return rc;
-  if ((rc = grow(e, &e->d_cfound, &e->cfound_bytes, (size_t)nq_max * 4))) return rc;
-  if ((rc = grow(e, &e->d_croffs, &e->croffs_bytes, ((size_t)nq_max + 1) * 8))) return rc;
-  if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)8 << 16))) return rc;
-  VC_HIP(e, hipMemsetAsync(e->d_dstat, 0, VC_DBSCAN_STAT_BYTES, e->stream));
-  VC_HIP(e, vc_launch_cluster_init(d_labels, N, e->cfg.id_base, e->stream));
-  for (uint64_t pos = 0; pos < N; pos += batch) {
-    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = e->cfg.id_base + (uint32_t)pos;
-    VC_HIP(e, vc_launch_cluster_init(e->d_cids, nq, first_id, e->stream));
-    VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, e->d_cids, nq, e->d_cq, e->d_cfound, e->stream));
-    uint64_t raw_total = 0;
-    for (int attempt = 0;; ++attempt) {
-      const uint64_t cap = e->craw_bytes / 8;
-      rc = vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, e->d_cq, nq,
-                            radius, e->d_craw, cap, e->d_croffs, true, &e->radius_work, e->stream, &e->err, &raw_total);
-      if (rc == VC_OK) break;
-      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
-      if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)raw_total * 8))) return rc;   // (the first attempt has been waited for)
-    }
-    VC_HIP(e, vc_launch_dbscan_edges(e->d_craw, e->d_croffs, nq, raw_total, first_id, e->cfg.id_base, min_pts, d_degrees, d_labels, e->d_dstat, e->stream));
-  }
-  VC_HIP(e, vc_launch_dbscan_finish(d_labels, d_degrees, N, e->cfg.id_base, min_pts, e->d_dstat + 1, e->stream));
-  uint64_t st[5] = {0, 0, 0, 0, 0};
-  VC_HIP(e, hipMemcpyAsync(st, e->d_dstat, VC_DBSCAN_STAT_BYTES, hipMemcpyDeviceToHost, e->stream));
-  VC_HIP(e, hipStreamSynchronize(e->stream));
-  if (stats) *stats = vc_dbscan_stats{st[0], st[1], st[2], st[3], st[4]};
-  return VC_OK;
-}
-
-extern "C" {
 
 int vc_dbscan_radius_dev(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels, uint32_t* d_degrees,
                          vc_dbscan_stats* stats, void* stream) {
-  int rc = check_dbscan_args(e, min_pts, mode, d_labels);
+  int rc = check_walk_args(e, "dbscan", 0, min_pts, mode, 0, d_labels);
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_stats{0, 0, 0, 0, 0};
   if (e->n == 0) return VC_OK;
-  if ((rc = bind_device(e))) return rc;
-  const StreamCall call(e, caller_stream(e, stream));
-  return dbscan_run(e, radius, min_pts, mode, batch, d_labels, d_degrees, stats);
+  return walk_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_dbscan_run(walk_view(e, mode), radius, min_pts, batch, d_labels, d_degrees, stats, s, err);
+  });
 }
 
 int vc_dbscan_radius(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees,
                      vc_dbscan_stats* stats) {
-  int rc = check_dbscan_args(e, min_pts, mode, labels);
+  int rc = check_walk_args(e, "dbscan", 0, min_pts, mode, 0, labels);
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_stats{0, 0, 0, 0, 0};
   if (e->n == 0) return VC_OK;
-  if ((rc = bind_device(e))) return rc;
-  if ((rc = grow(e, &e->d_chlab, &e->chlab_bytes, (size_t)e->n * 4))) return rc;
-  {
-    const StreamCall call(e, e->stream);
-    rc = dbscan_run(e, radius, min_pts, mode, batch, e->d_chlab, nullptr, stats);
-  }
-  if (rc) return rc;
-  VC_HIP(e, hipMemcpyAsync(labels, e->d_chlab, (size_t)e->n * 4, hipMemcpyDeviceToHost, e->stream));
-  if (degrees) VC_HIP(e, hipMemcpyAsync(degrees, e->d_ddeg, (size_t)e->n * 4, hipMemcpyDeviceToHost, e->stream));
-  VC_HIP(e, hipStreamSynchronize(e->stream));
-  return VC_OK;
+  return walk_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_dbscan_run_host(walk_view(e, mode), radius, min_pts, batch, labels, degrees, stats, s, err);
+  });
 }
-
-}  // extern "C"
-
-// ---- density clustering at every radius 0 .. max_radius: one walk, one forest per level over that level's cores ----------------------
-static int check_dbscan_levels_args(vc_engine* e, uint32_t max_radius, uint32_t min_pts, uint32_t mode, const uint32_t* labels) {
-  if (!e || !labels) return VC_ERR_INVALID;
-  if (min_pts == 0) return fail(e, VC_ERR_INVALID, "dbscan levels: min_pts must be at least 1");
-  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "dbscan levels: mode must be LINEAR or MIH_EXACT");
-  if (max_radius >= VC_LEVELS_MAX) return fail(e, VC_ERR_INVALID, "dbscan levels: max_radius %u exceeds %u", max_radius, VC_LEVELS_MAX - 1);
-  if (e->n && mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first");
-  return VC_OK;
-}
-
-// The whole call on e->stream (inside the caller's StreamCall), e->n > 0.  levels_run's loop over the batch buffers it shares with that
-// call (both fill them completely), at max_radius and in ascending id order: per batch of ids the ids filled on the device, the
-// gather, the radius search -- repeated once with the scratch grown to the total it reported -- then the batch's core distances and
-// its edges over the raw result as it lies.  d_core_dist null: the handle's own.  After the last batch the cascade, one finish pass
-// over all levels, then the one wait for the counters.
-static int dbscan_levels_run(vc_engine* e, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels, uint32_t* d_core_dist,
-                             vc_dbscan_levels_stats* stats) {
-  int rc;
-  const uint64_t N = e->n;
-  if (batch == 0) batch = VC_CLUSTER_BATCH;
-  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N);
-  if ((rc = grow(e, &e->d_wstat, &e->wstat_bytes, VC_DBSCAN_LEVELS_STAT_BYTES))) return rc;
-  if (!d_core_dist) {
-    if ((rc = grow(e, &e->d_wcd, &e->wcd_bytes, (size_t)N * 4))) return rc;
-    d_core_dist = e->d_wcd;
-  }
-  if ((rc = grow(e, &e->d_cids, &e->cids_bytes, (size_t)nq_max * 4))) return rc;
-  if ((rc = grow(e, &e->d_cq, &e->cq_bytes, (size_t)nq_max * e->W * 8))) return rc;
-  if ((rc = grow(e, &e->d_cfound, &e->cfound_bytes, (size_t)nq_max * 4))) return rc;
-  if ((rc = grow(e, &e->d_croffs, &e->croffs_bytes, ((size_t)nq_max + 1) * 8))) return rc;
-  if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)8 << 16))) return rc;
-  VC_HIP(e, hipMemsetAsync(e->d_wstat, 0, VC_DBSCAN_LEVELS_STAT_BYTES, e->stream));
-  for (uint32_t r = 0; r <= max_radius; ++r) VC_HIP(e, vc_launch_cluster_init(d_labels + (uint64_t)r * N, N, e->cfg.id_base, e->stream));
-  for (uint64_t pos = 0; pos < N; pos += batch) {
-    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = e->cfg.id_base + (uint32_t)pos;
-    VC_HIP(e, vc_launch_cluster_init(e->d_cids, nq, first_id, e->stream));
-    VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, e->d_cids, nq, e->d_cq, e->d_cfound, e->stream));
-    uint64_t raw_total = 0;
-    for (int attempt = 0;; ++attempt) {
-      const uint64_t cap = e->craw_bytes / 8;
-      rc = vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, e->d_cq, nq,
-                            max_radius, e->d_craw, cap, e->d_croffs, true, &e->radius_work, e->stream, &e->err, &raw_total);
-      if (rc == VC_OK) break;
-      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
-      if ((rc = grow(e, &e->d_craw, &e->craw_bytes, (size_t)raw_total * 8))) return rc;   // (the first attempt has been waited for)
-    }
-    VC_HIP(e, vc_launch_dbscan_levels_edges(e->d_craw, e->d_croffs, nq, raw_total, first_id, e->cfg.id_base, N, max_radius, min_pts, d_core_dist, d_labels,
-                                            e->d_wstat, e->stream));
-  }
-  VC_HIP(e, vc_launch_dbscan_levels_cascade(d_labels, d_core_dist, N, e->cfg.id_base, max_radius, e->stream));
-  VC_HIP(e, vc_launch_dbscan_levels_finish(d_labels, d_core_dist, N, e->cfg.id_base, max_radius, e->d_wstat + VC_LEVELS_MAX, e->stream));
-  vc_dbscan_levels_stats st;
-  VC_HIP(e, hipMemcpyAsync(&st, e->d_wstat, VC_DBSCAN_LEVELS_STAT_BYTES, hipMemcpyDeviceToHost, e->stream));
-  VC_HIP(e, hipStreamSynchronize(e->stream));
-  if (stats) *stats = st;
-  return VC_OK;
-}
-
-extern "C" {
 
 int vc_dbscan_levels_dev(vc_engine* e, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels, uint32_t* d_core_dist,
                          vc_dbscan_levels_stats* stats, void* stream) {
-  int rc = check_dbscan_levels_args(e, max_radius, min_pts, mode, d_labels);
+  int rc = check_walk_args(e, "dbscan levels", max_radius, min_pts, mode, 0, d_labels);
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_levels_stats{};
   if (e->n == 0) return VC_OK;
-  if ((rc = bind_device(e))) return rc;
-  const StreamCall call(e, caller_stream(e, stream));
-  return dbscan_levels_run(e, max_radius, min_pts, mode, batch, d_labels, d_core_dist, stats);
+  return walk_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_dbscan_levels_run(walk_view(e, mode), max_radius, min_pts, batch, d_labels, d_core_dist, stats, s, err);
+  });
 }
 
 int vc_dbscan_levels(vc_engine* e, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* core_dist,
                      vc_dbscan_levels_stats* stats) {
-  int rc = check_dbscan_levels_args(e, max_radius, min_pts, mode, labels);
+  int rc = check_walk_args(e, "dbscan levels", max_radius, min_pts, mode, 0, labels);
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_levels_stats{};
   if (e->n == 0) return VC_OK;
-  if ((rc = bind_device(e))) return rc;
-  const size_t N = (size_t)e->n, levels = (size_t)max_radius + 1;
-  if ((rc = grow(e, &e->d_chlab, &e->chlab_bytes, levels * N * 4))) return rc;
-  {
-    const StreamCall call(e, e->stream);
-    rc = dbscan_levels_run(e, max_radius, min_pts, mode, batch, e->d_chlab, nullptr, stats);
-  }
-  if (rc) return rc;
-  VC_HIP(e, hipMemcpyAsync(labels, e->d_chlab, levels * N * 4, hipMemcpyDeviceToHost, e->stream));
-  if (core_dist) VC_HIP(e, hipMemcpyAsync(core_dist, e->d_wcd, N * 4, hipMemcpyDeviceToHost, e->stream));
-  VC_HIP(e, hipStreamSynchronize(e->stream));
-  return VC_OK;
+  return walk_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_dbscan_levels_run_host(walk_view(e, mode), max_radius, min_pts, batch, labels, core_dist, stats, s, err);
+  });
 }
 
 }  // extern "C"

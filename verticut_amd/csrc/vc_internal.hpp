@@ -197,9 +197,53 @@ hipError_t vc_launch_ids_radius_count(const VcIdsRadiusWork& w, const uint64_t* 
 // the kept entries, in order, to d_out[d_offsets[q] ..): the caller has made sure that *w.total entries fit
 hipError_t vc_launch_ids_radius_copy(const VcIdsRadiusWork& w, const uint64_t* d_raw, const uint64_t* d_roffs, const uint32_t* d_ids, uint32_t nq,
                                      uint32_t id_flags, const uint64_t* d_offsets, uint64_t* d_out, hipStream_t s);
-// ---- vc_cluster.hip: near-duplicate clustering (vc_cluster_radius*).  d_labels [n] is the union-find forest in place: slot i holds
-// the global id of the parent of record id_base + i, never greater than id_base + i.  Nothing here waits.
+// ---- vc_walk.hip: the radius-graph walk under the five clustering calls (vc_cluster_radius*, vc_cluster_levels*, vc_leaders_radius*,
+// vc_dbscan_radius*, vc_dbscan_levels*) of both handle kinds.  Every record from a first position on goes through the handle's radius
+// search, batch by batch in ascending id order, and one consume step per batch folds the RAW result into the caller's arrays.
 #define VC_CLUSTER_BATCH 4096u   // ids per radius search underneath when the caller passes batch = 0
+inline uint32_t vc_walk_batch(uint32_t batch) { return batch ? batch : VC_CLUSTER_BATCH; }
+// The handle's grow-only buffers of these calls (alloc as VcGroupsArgs::alloc).  The walk's own: a batch's ids, gathered queries, found
+// words, the nq + 1 offsets and the raw results of the search.  The consumers': the statistics; one word per record (dbscan's degrees /
+// core distances when the caller passes none); leaders' state words of a batch; the host forms' staged labels.  The calls share them:
+// each writes every word it reads.
+enum { VC_WALK_IDS, VC_WALK_Q, VC_WALK_FOUND, VC_WALK_ROFFS, VC_WALK_RAW, VC_WALK_STAT, VC_WALK_RECORD, VC_WALK_STATE, VC_WALK_HLAB, VC_WALK_BUFS };
+// What the walk needs of a handle for one call (the search mode and the call's stream are the closures' own).  gather and search
+// enqueue on that stream and return a VC_* code with the device of the handle's buffers current; neither waits, but for search
+// returning VC_ERR_CAPACITY (*raw_total entries do not fit cap): then everything enqueued has been waited for, so that the raw buffer
+// may be regrown.  A closure that fails has left its text in the handle.
+struct VcWalkView {
+  uint64_t n;               // resident records
+  uint32_t id_base, W;
+  std::function<void*(int which, size_t bytes)> alloc;
+  std::function<size_t(int which)> held;   // the bytes behind buffer `which` now: an earlier call may have left more than this one asks for
+  std::function<int(const uint32_t* d_ids, uint32_t nq, uint64_t* d_q, uint32_t* d_found)> gather;   // ids -> rows [nq][W] + found words
+  std::function<int(const uint64_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_raw, uint64_t cap, uint64_t* d_roffs, uint64_t* raw_total)> search;
+};
+struct VcWalkBatch {        // the raw result (ascending per query) of the queries first_id .. first_id + nq - 1, as it lies in the walk's buffers
+  const uint64_t* d_raw;
+  const uint64_t* d_roffs;  // nq + 1 offsets, d_roffs[nq] = raw_total
+  uint32_t nq;
+  uint64_t raw_total;
+  uint32_t first_id;
+};
+// The positions first_pos .. v.n - 1 in batches of vc_walk_batch(batch): per batch the ids filled on the device, the gather, the search
+// at `radius` -- repeated once with the raw buffer grown to the total it reported -- and consume (a VC_* code; it may wait).  The walk
+// itself waits for nothing.  err: the text of a failure of the walk's own; a closure's is in the handle.
+int vc_walk_run(const VcWalkView& v, uint64_t first_pos, uint32_t batch, uint32_t radius, const std::function<int(const VcWalkBatch&)>& consume, hipStream_t s,
+                std::string* err);
+// the host forms' labels staged in VC_WALK_HLAB (*d_labels): `planes` planes of v.n words, of each the first n_labelled copied in
+int vc_walk_stage_labels(const VcWalkView& v, const uint32_t* labels, size_t planes, uint64_t n_labelled, uint32_t** d_labels, hipStream_t s, std::string* err);
+int vc_walk_fail(std::string* err, hipError_t r, const char* what);   // the text and code of a failed HIP call
+#define VC_WALK_HIP(call)                                      \
+  do {                                                         \
+    hipError_t _r = (call);                                    \
+    if (_r != hipSuccess) return vc_walk_fail(err, _r, #call); \
+  } while (0)
+// The five consumers below come in two forms, both the whole call on s with the device of the handle's buffers current, n > 0:
+// vc_*_run on device pointers -- statistics zeroed, labels initialised, the walk, the passes after the last batch, then the one wait
+// for the statistics (stats: host memory, nullable) -- and vc_*_run_host on host pointers: labels staged, run, copied home, waited for.
+// ---- vc_cluster.hip: near-duplicate clustering (vc_cluster_radius*).  d_labels [n] is the union-find forest in place: slot i holds
+// the global id of the parent of record id_base + i, never greater than id_base + i.  Nothing here waits but the two run forms.
 // d_dst[j] = first + j for j < count: the labels of the records that come in unlabelled, and the ids of a batch
 hipError_t vc_launch_cluster_init(uint32_t* d_dst, uint64_t count, uint32_t first, hipStream_t s);
 // unites every kept entry of the raw result (d_raw, its nq + 1 offsets d_roffs, total = d_roffs[nq]) of the queries first_id ..
@@ -208,6 +252,11 @@ hipError_t vc_launch_cluster_union(const uint64_t* d_raw, const uint64_t* d_roff
                                    uint32_t id_base, uint32_t* d_labels, uint64_t* d_n_pairs, hipStream_t s);
 // d_labels[i] = the root of record i (the smallest id of its component), in place; *d_n_clusters += the roots
 hipError_t vc_launch_cluster_flatten(uint32_t* d_labels, uint64_t n, uint32_t id_base, uint64_t* d_n_clusters, hipStream_t s);
+// the records from n_labelled on walked and united, one flatten over all n; VC_WALK_STAT: 2 x uint64 (pairs, clusters)
+int vc_cluster_run(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_cluster_stats* stats, hipStream_t s,
+                   std::string* err);
+int vc_cluster_run_host(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats, hipStream_t s,
+                        std::string* err);
 // ---- vc_leaders.hip: greedy leader dedup (vc_leaders_radius*).  d_labels [n]: slot i holds the global id of the smallest-id leader
 // within the radius of record id_base + i, its own id for a leader; entries below the batch are final and only read.
 #define VC_LEADER_ROUND_GROUP 4u           // decision rounds enqueued between two read-backs of the undecided counter
@@ -221,6 +270,12 @@ hipError_t vc_leaders_decide_batch(const uint64_t* d_raw, const uint64_t* d_roff
                                    uint32_t* d_state, uint64_t* d_stat, hipStream_t s, bool* stuck);
 // *d_n_leaders += the records i < n with d_labels[i] == id_base + i; nothing is waited for
 hipError_t vc_launch_leaders_count(const uint32_t* d_labels, uint64_t n, uint32_t id_base, uint64_t* d_n_leaders, hipStream_t s);
+// the records from n_labelled on walked in batches of at most VC_LEADER_BATCH_MAX and decided (a wait per group of rounds), one count
+// over all n; the entries below n_labelled are only read, and the host form does not copy them back
+int vc_leaders_run(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_leader_stats* stats, hipStream_t s,
+                   std::string* err);
+int vc_leaders_run_host(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats, hipStream_t s,
+                        std::string* err);
 // ---- vc_dbscan.hip: density clustering (vc_dbscan_radius*).  d_labels [n] starts as the own ids (vc_launch_cluster_init): a core's
 // slot is the forest of vc_forest.hpp over the cores, a non-core's slot its smallest core neighbour seen so far, its own id for
 // none; d_degrees [n] says which is which.  Nothing here waits.
@@ -234,6 +289,11 @@ hipError_t vc_launch_dbscan_edges(const uint64_t* d_raw, const uint64_t* d_roffs
 // d_counts[0 .. 3] += the roots among the cores, the cores, the borders, the noise
 hipError_t vc_launch_dbscan_finish(uint32_t* d_labels, const uint32_t* d_degrees, uint64_t n, uint32_t id_base, uint32_t min_pts, uint64_t* d_counts,
                                    hipStream_t s);
+// every record walked from position 0, one finish pass; d_degrees null: the handle's own (VC_WALK_RECORD); degrees (host) nullable
+int vc_dbscan_run(const VcWalkView& v, uint32_t radius, uint32_t min_pts, uint32_t batch, uint32_t* d_labels, uint32_t* d_degrees, vc_dbscan_stats* stats,
+                  hipStream_t s, std::string* err);
+int vc_dbscan_run_host(const VcWalkView& v, uint32_t radius, uint32_t min_pts, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats,
+                       hipStream_t s, std::string* err);
 // ---- vc_levels.hip: single-linkage clusters at every radius 0 .. max_radius in one walk (vc_cluster_levels*).  d_labels is level-major,
 // (max_radius + 1) x n: level r at d_labels + r * n is a forest of vc_forest.hpp in place, as vc_cluster.hip's.  Nothing here waits.
 #define VC_LEVELS_STAT_BYTES 1024u   // d_stat: vc_levels_stats as it lies (64 pair counters, then 64 cluster counters)
@@ -245,6 +305,11 @@ hipError_t vc_launch_levels_union(const uint64_t* d_raw, const uint64_t* d_roffs
 hipError_t vc_launch_levels_cascade(uint32_t* d_labels, uint64_t n, uint32_t id_base, uint32_t max_radius, hipStream_t s);
 // d_labels[r * n + i] = the root of record i at level r, in place, every level in one launch; d_n_clusters[r] += the roots of level r
 hipError_t vc_launch_levels_flatten(uint32_t* d_labels, uint64_t n, uint32_t id_base, uint32_t max_radius, uint64_t* d_n_clusters, hipStream_t s);
+// the records from n_labelled on walked at max_radius (the first n_labelled of every level come in labelled), the cascade, one flatten
+int vc_levels_run(const VcWalkView& v, uint32_t max_radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_levels_stats* stats, hipStream_t s,
+                  std::string* err);
+int vc_levels_run_host(const VcWalkView& v, uint32_t max_radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_levels_stats* stats, hipStream_t s,
+                       std::string* err);
 // ---- vc_dbscan_levels.hip: density clustering at every radius 0 .. max_radius in one walk (vc_dbscan_levels*).  d_labels is level-major,
 // (max_radius + 1) x n, every slot starts as the own id (vc_launch_cluster_init per level); d_core_dist [n] says whether slot (r, i)
 // is the forest of level r (d_core_dist[i] <= r) or record i's anchor candidate of exactly level r.  Nothing here waits.
@@ -262,6 +327,12 @@ hipError_t vc_launch_dbscan_levels_cascade(uint32_t* d_labels, const uint32_t* d
 // noise, in place, one launch; d_counts [4][VC_LEVELS_MAX]: [0][r] += the roots among the cores of level r, [1] cores, [2] borders, [3] noise
 hipError_t vc_launch_dbscan_levels_finish(uint32_t* d_labels, const uint32_t* d_core_dist, uint64_t n, uint32_t id_base, uint32_t max_radius,
                                           uint64_t* d_counts, hipStream_t s);
+// every record walked from position 0 at max_radius, the cascade, one finish pass; d_core_dist null: the handle's own (VC_WALK_RECORD);
+// core_dist (host) nullable
+int vc_dbscan_levels_run(const VcWalkView& v, uint32_t max_radius, uint32_t min_pts, uint32_t batch, uint32_t* d_labels, uint32_t* d_core_dist,
+                         vc_dbscan_levels_stats* stats, hipStream_t s, std::string* err);
+int vc_dbscan_levels_run_host(const VcWalkView& v, uint32_t max_radius, uint32_t min_pts, uint32_t batch, uint32_t* labels, uint32_t* core_dist,
+                              vc_dbscan_levels_stats* stats, hipStream_t s, std::string* err);
 // ---- vc_groups.hip: label groups summarised (vc_group_summary*, vc_sharded_group_summary*).  One driver for both handle kinds: the
 // codes of a window's sorted ids come through `fetch` (vc_get_codes_dev / the sharded gather, enqueued on s, nothing waited for)
 // as contiguous rows [nq][W].  The plan arithmetic is vc_groups_plan.hpp.

@@ -4,6 +4,7 @@
 // compaction, no plan: one wave walks one query's segment between its two offsets; LDS holds only a block's two counter sums.
 // ============================================================================
 #include <algorithm>
+#include <cstdio>
 
 #include "vc_internal.hpp"
 
@@ -201,4 +202,41 @@ hipError_t vc_leaders_decide_batch(const uint64_t* d_raw, const uint64_t* d_roff
   }
   hipLaunchKernelGGL(vc_leaders_assign_kernel, agrid, ablock, 0, s, d_raw, d_roffs, nq, first_id, id_base, d_labels, d_state);
   return hipGetLastError();
+}
+
+int vc_leaders_run(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_leader_stats* stats, hipStream_t s,
+                   std::string* err) {
+  const uint64_t N = v.n;
+  batch = std::min(vc_walk_batch(batch), VC_LEADER_BATCH_MAX);
+  uint64_t* d_stat = (uint64_t*)v.alloc(VC_WALK_STAT, VC_LEADER_STAT_BYTES);
+  uint32_t* d_state = n_labelled < N ? (uint32_t*)v.alloc(VC_WALK_STATE, (size_t)std::min<uint64_t>(batch, N - n_labelled) * 4) : nullptr;
+  if (!d_stat || (n_labelled < N && !d_state)) return VC_ERR_NOMEM;
+  VC_WALK_HIP(hipMemsetAsync(d_stat, 0, VC_LEADER_STAT_BYTES, s));
+  const int rc = vc_walk_run(v, n_labelled, batch, radius, [&](const VcWalkBatch& b) -> int {   // the decision over the raw result as it lies
+    bool stuck = false;
+    VC_WALK_HIP(vc_leaders_decide_batch(b.d_raw, b.d_roffs, b.nq, b.first_id, v.id_base, d_labels, d_state, d_stat, s, &stuck));
+    if (!stuck) return VC_OK;
+    char text[96];
+    snprintf(text, sizeof text, "leaders: the batch at id %u is undecided after %u rounds", b.first_id, b.nq);
+    if (err) *err = text;
+    return VC_ERR_HIP;
+  }, s, err);
+  if (rc) return rc;
+  VC_WALK_HIP(vc_launch_leaders_count(d_labels, N, v.id_base, d_stat + 1, s));
+  uint64_t st[3] = {0, 0, 0};
+  VC_WALK_HIP(hipMemcpyAsync(st, d_stat, 24, hipMemcpyDeviceToHost, s));
+  VC_WALK_HIP(hipStreamSynchronize(s));
+  if (stats) *stats = vc_leader_stats{st[0], st[1], st[2]};
+  return VC_OK;
+}
+
+int vc_leaders_run_host(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats, hipStream_t s,
+                        std::string* err) {
+  uint32_t* d_labels = nullptr;
+  int rc = vc_walk_stage_labels(v, labels, 1, n_labelled, &d_labels, s, err);
+  if (rc || (rc = vc_leaders_run(v, radius, batch, n_labelled, d_labels, stats, s, err))) return rc;
+  if (n_labelled < v.n)   // the incoming entries are read only: they do not travel back
+    VC_WALK_HIP(hipMemcpyAsync(labels + n_labelled, d_labels + n_labelled, (size_t)(v.n - n_labelled) * 4, hipMemcpyDeviceToHost, s));
+  VC_WALK_HIP(hipStreamSynchronize(s));
+  return VC_OK;
 }

@@ -115,3 +115,35 @@ hipError_t vc_launch_levels_flatten(uint32_t* d_labels, uint64_t n, uint32_t id_
   hipLaunchKernelGGL(vc_levels_flatten_kernel, dim3(lv_grid(n), max_radius + 1), dim3(LV_BLK), 0, s, d_labels, n, id_base, (unsigned long long*)d_n_clusters);
   return hipGetLastError();
 }
+
+int vc_levels_run(const VcWalkView& v, uint32_t max_radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_levels_stats* stats, hipStream_t s,
+                  std::string* err) {
+  const uint64_t N = v.n, first_new = (uint64_t)v.id_base + n_labelled;
+  uint64_t* d_stat = (uint64_t*)v.alloc(VC_WALK_STAT, VC_LEVELS_STAT_BYTES);
+  if (!d_stat) return VC_ERR_NOMEM;
+  VC_WALK_HIP(hipMemsetAsync(d_stat, 0, VC_LEVELS_STAT_BYTES, s));
+  for (uint32_t r = 0; r <= max_radius; ++r) VC_WALK_HIP(vc_launch_cluster_init(d_labels + (uint64_t)r * N + n_labelled, N - n_labelled, (uint32_t)first_new, s));
+  const int rc = vc_walk_run(v, n_labelled, batch, max_radius, [&](const VcWalkBatch& b) -> int {   // every kept entry in the forest of its distance
+    VC_WALK_HIP(vc_launch_levels_union(b.d_raw, b.d_roffs, b.nq, b.raw_total, b.first_id, first_new, v.id_base, N, max_radius, d_labels, d_stat, s));
+    return VC_OK;
+  }, s, err);
+  if (rc) return rc;
+  VC_WALK_HIP(vc_launch_levels_cascade(d_labels, N, v.id_base, max_radius, s));
+  VC_WALK_HIP(vc_launch_levels_flatten(d_labels, N, v.id_base, max_radius, d_stat + VC_LEVELS_MAX, s));
+  vc_levels_stats st;
+  VC_WALK_HIP(hipMemcpyAsync(&st, d_stat, VC_LEVELS_STAT_BYTES, hipMemcpyDeviceToHost, s));
+  VC_WALK_HIP(hipStreamSynchronize(s));
+  if (stats) *stats = st;
+  return VC_OK;
+}
+
+int vc_levels_run_host(const VcWalkView& v, uint32_t max_radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_levels_stats* stats, hipStream_t s,
+                       std::string* err) {
+  const size_t levels = (size_t)max_radius + 1;
+  uint32_t* d_labels = nullptr;
+  int rc = vc_walk_stage_labels(v, labels, levels, n_labelled, &d_labels, s, err);
+  if (rc || (rc = vc_levels_run(v, max_radius, batch, n_labelled, d_labels, stats, s, err))) return rc;
+  VC_WALK_HIP(hipMemcpyAsync(labels, d_labels, levels * (size_t)v.n * 4, hipMemcpyDeviceToHost, s));
+  VC_WALK_HIP(hipStreamSynchronize(s));
+  return VC_OK;
+}

@@ -135,20 +135,9 @@ enum RootBuf {
   // radius search by id: gathered queries, found words, the union's uncompacted results and offsets, the compaction's counts
   // (VcIdsRadiusWork); the host-pointer form's staged ids, results and offsets
   RIDS_Q, RIDS_FOUND, RIDS_RAW, RIDS_ROFFS, RIDS_WORK, RIDS_HIDS, RIDS_HOUT, RIDS_HOFFS,
-  // near-duplicate clustering: a batch's ids, gathered queries and found words, the union's raw results and offsets, the two
-  // counters (pairs, clusters); the host-pointer form's staged labels
-  CL_IDS, CL_Q, CL_FOUND, CL_RAW, CL_ROFFS, CL_STAT, CL_HLAB,
-  // greedy leader dedup: it shares CL_IDS .. CL_ROFFS and CL_HLAB (both calls fill them completely); its own are a batch's state
-  // words and the statistics with the round counters
-  LD_STATE, LD_STAT,
-  // density clustering: it shares CL_IDS .. CL_ROFFS and CL_HLAB too; its own are the degrees of a call that passes none (and of the
-  // host form) and the five statistics
-  DB_DEG, DB_STAT,
-  // clusters at every radius: it shares CL_IDS .. CL_ROFFS and CL_HLAB (grown to all levels) too; its own are the 2 x 64 counters
-  LV_STAT,
-  // density clustering at every radius: it shares CL_IDS .. CL_ROFFS and CL_HLAB (grown to all levels) too; its own are the core
-  // distances of a call that passes none (and of the host form) and the 5 x 64 counters
-  DL_CD, DL_STAT,
+  // the clustering calls over the radius-graph walk: the walk's batch buffers, the statistics, the per-record words, leaders' state words
+  // and the host forms' staged labels (WALK_FIRST + VC_WALK_*); shared by the five calls, each writes every word it reads
+  WALK_FIRST, WALK_LAST = WALK_FIRST + VC_WALK_BUFS - 1,
   // label groups summarised: the sort and numbering arrays, the row buffer with the big groups' tables, the host form's staging
   // (GRP_SCRATCH + VC_GROUPS_*); its own, every word written before it is read
   GRP_SCRATCH, GRP_WORK, GRP_STAGE,
@@ -2106,159 +2095,90 @@ int vc_sharded_search_radius_ids(vc_sharded* h, const uint32_t* ids, uint32_t nq
 
 }  // extern "C"
 
-// ---- near-duplicate clustering over the shards ----------------------------------------------------------------------------------------
-static int check_sharded_cluster_args(vc_sharded* h, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
-  if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
-  if (n_labelled > h->n) return sfail(h, VC_ERR_INVALID, "cluster: n_labelled %llu exceeds the %llu resident records", (unsigned long long)n_labelled, (unsigned long long)h->n);
+// ---- the clustering calls over the shards: the drivers of vc_cluster.hip, vc_levels.hip, vc_leaders.hip, vc_dbscan.hip and
+// vc_dbscan_levels.hip on the root, their walk (vc_walk.hip) through the sharded gather and the union's radius search ------------------
+static int check_sharded_index(vc_sharded* h, uint32_t mode) {   // exact MIH needs an index on every non-empty shard
   if (mode == VC_MODE_MIH_EXACT)
     for (uint32_t g = 0; g < h->G; ++g)
       if (shard_size(h, g) && !vc_engine_has_index(h->eng[g])) return sfail(h, VC_ERR_STATE, "shard %u: MIH search needs vc_sharded_build_index() first", g);
   return VC_OK;
 }
-
-// All on the root device's stream S, h->n > 0.  Per batch of global ids: the ids filled on the root, the gather over the shards, the
-// union's radius search into the handle's scratch -- repeated once with the scratch grown to the total it reported -- and the
-// union-find over the raw result on the root; after the last batch one flatten, then the one wait for the two counters.
-static int sharded_cluster_run(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
-                               vc_cluster_stats* stats, hipStream_t S) {
-  int rc;
-  const uint32_t id_base = h->cfg.engine.id_base;
-  const uint64_t N = h->n, first_new = (uint64_t)id_base + n_labelled;
-  if (batch == 0) batch = VC_CLUSTER_BATCH;
-  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N - n_labelled);
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[CL_STAT].grow(h, 16))) return rc;
-  if (nq_max) {
-    if ((rc = h->buf[CL_IDS].grow(h, (size_t)nq_max * 4))) return rc;
-    if ((rc = h->buf[CL_Q].grow(h, (size_t)nq_max * h->nbytes))) return rc;
-    if ((rc = h->buf[CL_FOUND].grow(h, (size_t)nq_max * 4))) return rc;
-    if ((rc = h->buf[CL_ROFFS].grow(h, ((size_t)nq_max + 1) * 8))) return rc;
-    if ((rc = h->buf[CL_RAW].grow(h, (size_t)8 << 16))) return rc;
-  }
-  uint64_t* d_stat = h->buf[CL_STAT].as<uint64_t>();
-  uint32_t* d_ids = h->buf[CL_IDS].as<uint32_t>();
-  VS_HIP(h, hipMemsetAsync(d_stat, 0, 16, S));
-  VS_HIP(h, vc_launch_cluster_init(d_labels + n_labelled, N - n_labelled, (uint32_t)first_new, S));
-  for (uint64_t pos = n_labelled; pos < N; pos += batch) {
-    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = id_base + (uint32_t)pos;
-    VS_HIP(h, hipSetDevice(h->root));
-    VS_HIP(h, vc_launch_cluster_init(d_ids, nq, first_id, S));
-    if ((rc = sharded_gather_ids(h, d_ids, nq, h->buf[CL_Q].as<uint64_t>(), h->buf[CL_FOUND].as<uint32_t>(), true, S))) return rc;
-    uint64_t raw_total = 0;
-    for (int attempt = 0;; ++attempt) {
-      const uint64_t cap = h->buf[CL_RAW].bytes / 8;
-      rc = sharded_radius_dev(h, h->buf[CL_Q].p, nq, radius, mode, h->buf[CL_RAW].as<uint64_t>(), cap, h->buf[CL_ROFFS].as<uint64_t>(), S, &raw_total);
-      if (rc == VC_OK) break;
-      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
-      VS_HIP(h, hipSetDevice(h->root));
-      if ((rc = h->buf[CL_RAW].grow(h, (size_t)raw_total * 8))) return rc;
-    }
-    VS_HIP(h, hipSetDevice(h->root));
-    VS_HIP(h, vc_launch_cluster_union(h->buf[CL_RAW].as<uint64_t>(), h->buf[CL_ROFFS].as<uint64_t>(), nq, raw_total, first_id, first_new, id_base, d_labels,
-                                      d_stat, S));
-  }
-  VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, vc_launch_cluster_flatten(d_labels, N, id_base, d_stat + 1, S));
-  uint64_t st[2] = {0, 0};
-  VS_HIP(h, hipMemcpyAsync(st, d_stat, 16, hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipStreamSynchronize(S));
-  if (stats) {
-    stats->n_pairs = st[0];
-    stats->n_clusters = st[1];
-  }
-  return VC_OK;
+static int check_sharded_cluster_args(vc_sharded* h, const char* what, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {   // what: "cluster" or "leaders"
+  if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
+  if (n_labelled > h->n) return sfail(h, VC_ERR_INVALID, "%s: n_labelled %llu exceeds the %llu resident records", what, (unsigned long long)n_labelled, (unsigned long long)h->n);
+  return check_sharded_index(h, mode);
 }
+static int check_sharded_levels_args(vc_sharded* h, uint32_t max_radius, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
+  if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
+  if (max_radius >= VC_LEVELS_MAX) return sfail(h, VC_ERR_INVALID, "cluster levels: max_radius %u exceeds %u", max_radius, VC_LEVELS_MAX - 1);
+  return check_sharded_cluster_args(h, "cluster", mode, n_labelled, labels);
+}
+static int check_sharded_dbscan_args(vc_sharded* h, uint32_t min_pts, uint32_t mode, const uint32_t* labels) {
+  if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
+  if (min_pts == 0) return sfail(h, VC_ERR_INVALID, "dbscan: min_pts must be at least 1");
+  return check_sharded_index(h, mode);
+}
+static int check_sharded_dbscan_levels_args(vc_sharded* h, uint32_t max_radius, uint32_t min_pts, uint32_t mode, const uint32_t* labels) {
+  if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
+  if (max_radius >= VC_LEVELS_MAX) return sfail(h, VC_ERR_INVALID, "dbscan levels: max_radius %u exceeds %u", max_radius, VC_LEVELS_MAX - 1);
+  return check_sharded_dbscan_args(h, min_pts, mode, labels);
+}
+
+// The store as the walk sees it: its buffers are the root's, everything the root does goes to S.  The gather and the search visit the
+// other devices and come back with the root current, so the drivers never bind one.
+static VcWalkView sharded_walk_view(vc_sharded* h, uint32_t mode, hipStream_t S) {
+  VcWalkView v;
+  v.n = h->n;
+  v.id_base = h->cfg.engine.id_base;
+  v.W = h->nbytes / 8;
+  v.alloc = [h](int which, size_t bytes) -> void* {
+    DevBuf& b = h->buf[WALK_FIRST + which];
+    return b.grow(h, bytes) ? nullptr : b.p;
+  };
+  v.held = [h](int which) { return h->buf[WALK_FIRST + which].bytes; };
+  v.gather = [h, S](const uint32_t* d_ids, uint32_t nq, uint64_t* d_q, uint32_t* d_found) { return sharded_gather_ids(h, d_ids, nq, d_q, d_found, true, S); };
+  v.search = [h, mode, S](const uint64_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_raw, uint64_t cap, uint64_t* d_roffs, uint64_t* raw_total) -> int {
+    const int rc = sharded_radius_dev(h, d_q, nq, radius, mode, d_raw, cap, d_roffs, S, raw_total);
+    if (rc && rc != VC_ERR_CAPACITY) return rc;
+    VS_HIP(h, hipSetDevice(h->root));
+    return rc;
+  };
+  return v;
+}
+
+// An entry point after its checks, h->n > 0: the root bound, `run` (a vc_*_run or vc_*_run_host) with the view on stream S.
+template <class Run>
+static int sharded_walk_call(vc_sharded* h, uint32_t mode, hipStream_t S, const Run& run) {
+  VS_HIP(h, hipSetDevice(h->root));
+  std::string err;
+  const int rc = run(sharded_walk_view(h, mode, S), S, &err);
+  return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;   // (a closure of the view has left its own text)
+}
+static hipStream_t sharded_caller_stream(const vc_sharded* h, void* stream) { return stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream; }
 
 extern "C" {
 
 int vc_sharded_cluster_radius_dev(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
                                   vc_cluster_stats* stats, void* stream) {
-  int rc = check_sharded_cluster_args(h, mode, n_labelled, d_labels);
+  int rc = check_sharded_cluster_args(h, "cluster", mode, n_labelled, d_labels);
   if (rc) return rc;
   if (stats) *stats = vc_cluster_stats{0, 0};
   if (h->n == 0) return VC_OK;
-  return sharded_cluster_run(h, radius, mode, batch, n_labelled, d_labels, stats, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+  return sharded_walk_call(h, mode, sharded_caller_stream(h, stream), [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+    return vc_cluster_run(v, radius, batch, n_labelled, d_labels, stats, S, err);
+  });
 }
 
 int vc_sharded_cluster_radius(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
                               vc_cluster_stats* stats) {
-  int rc = check_sharded_cluster_args(h, mode, n_labelled, labels);
+  int rc = check_sharded_cluster_args(h, "cluster", mode, n_labelled, labels);
   if (rc) return rc;
   if (stats) *stats = vc_cluster_stats{0, 0};
   if (h->n == 0) return VC_OK;
-  hipStream_t S = h->root_stream;
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[CL_HLAB].grow(h, (size_t)h->n * 4))) return rc;
-  if (n_labelled) VS_HIP(h, hipMemcpyAsync(h->buf[CL_HLAB].p, labels, (size_t)n_labelled * 4, hipMemcpyHostToDevice, S));
-  if ((rc = sharded_cluster_run(h, radius, mode, batch, n_labelled, h->buf[CL_HLAB].as<uint32_t>(), stats, S))) return rc;
-  VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, hipMemcpyAsync(labels, h->buf[CL_HLAB].p, (size_t)h->n * 4, hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipStreamSynchronize(S));
-  return VC_OK;
+  return sharded_walk_call(h, mode, h->root_stream, [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+    return vc_cluster_run_host(v, radius, batch, n_labelled, labels, stats, S, err);
+  });
 }
-
-}  // extern "C"
-
-// ---- clusters at every radius over the shards -----------------------------------------------------------------------------------------
-static int check_sharded_levels_args(vc_sharded* h, uint32_t max_radius, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
-  if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
-  if (max_radius >= VC_LEVELS_MAX) return sfail(h, VC_ERR_INVALID, "cluster levels: max_radius %u exceeds %u", max_radius, VC_LEVELS_MAX - 1);
-  return check_sharded_cluster_args(h, mode, n_labelled, labels);
-}
-
-// All on the root device's stream S, h->n > 0.  sharded_cluster_run's loop over the batch buffers it shares with that call, at
-// max_radius: per batch of global ids the ids filled on the root, the gather over the shards, the union's radius search -- repeated
-// once with the scratch grown to the total it reported -- and the union over the raw result on the root, every kept entry in the forest
-// of its distance; after the last batch the cascade, one flatten over all levels, then the one wait for the counters.
-static int sharded_levels_run(vc_sharded* h, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
-                              vc_levels_stats* stats, hipStream_t S) {
-  int rc;
-  const uint32_t id_base = h->cfg.engine.id_base;
-  const uint64_t N = h->n, first_new = (uint64_t)id_base + n_labelled;
-  if (batch == 0) batch = VC_CLUSTER_BATCH;
-  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N - n_labelled);
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[LV_STAT].grow(h, VC_LEVELS_STAT_BYTES))) return rc;
-  if (nq_max) {
-    if ((rc = h->buf[CL_IDS].grow(h, (size_t)nq_max * 4))) return rc;
-    if ((rc = h->buf[CL_Q].grow(h, (size_t)nq_max * h->nbytes))) return rc;
-    if ((rc = h->buf[CL_FOUND].grow(h, (size_t)nq_max * 4))) return rc;
-    if ((rc = h->buf[CL_ROFFS].grow(h, ((size_t)nq_max + 1) * 8))) return rc;
-    if ((rc = h->buf[CL_RAW].grow(h, (size_t)8 << 16))) return rc;
-  }
-  uint64_t* d_stat = h->buf[LV_STAT].as<uint64_t>();
-  uint32_t* d_ids = h->buf[CL_IDS].as<uint32_t>();
-  VS_HIP(h, hipMemsetAsync(d_stat, 0, VC_LEVELS_STAT_BYTES, S));
-  for (uint32_t r = 0; r <= max_radius; ++r) VS_HIP(h, vc_launch_cluster_init(d_labels + (uint64_t)r * N + n_labelled, N - n_labelled, (uint32_t)first_new, S));
-  for (uint64_t pos = n_labelled; pos < N; pos += batch) {
-    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = id_base + (uint32_t)pos;
-    VS_HIP(h, hipSetDevice(h->root));
-    VS_HIP(h, vc_launch_cluster_init(d_ids, nq, first_id, S));
-    if ((rc = sharded_gather_ids(h, d_ids, nq, h->buf[CL_Q].as<uint64_t>(), h->buf[CL_FOUND].as<uint32_t>(), true, S))) return rc;
-    uint64_t raw_total = 0;
-    for (int attempt = 0;; ++attempt) {
-      const uint64_t cap = h->buf[CL_RAW].bytes / 8;
-      rc = sharded_radius_dev(h, h->buf[CL_Q].p, nq, max_radius, mode, h->buf[CL_RAW].as<uint64_t>(), cap, h->buf[CL_ROFFS].as<uint64_t>(), S, &raw_total);
-      if (rc == VC_OK) break;
-      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
-      VS_HIP(h, hipSetDevice(h->root));
-      if ((rc = h->buf[CL_RAW].grow(h, (size_t)raw_total * 8))) return rc;
-    }
-    VS_HIP(h, hipSetDevice(h->root));
-    VS_HIP(h, vc_launch_levels_union(h->buf[CL_RAW].as<uint64_t>(), h->buf[CL_ROFFS].as<uint64_t>(), nq, raw_total, first_id, first_new, id_base, N, max_radius,
-                                     d_labels, d_stat, S));
-  }
-  VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, vc_launch_levels_cascade(d_labels, N, id_base, max_radius, S));
-  VS_HIP(h, vc_launch_levels_flatten(d_labels, N, id_base, max_radius, d_stat + VC_LEVELS_MAX, S));
-  vc_levels_stats st;
-  VS_HIP(h, hipMemcpyAsync(&st, d_stat, VC_LEVELS_STAT_BYTES, hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipStreamSynchronize(S));
-  if (stats) *stats = st;
-  return VC_OK;
-}
-
-extern "C" {
 
 int vc_sharded_cluster_levels_dev(vc_sharded* h, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
                                   vc_levels_stats* stats, void* stream) {
@@ -2266,7 +2186,9 @@ int vc_sharded_cluster_levels_dev(vc_sharded* h, uint32_t max_radius, uint32_t m
   if (rc) return rc;
   if (stats) *stats = vc_levels_stats{};
   if (h->n == 0) return VC_OK;
-  return sharded_levels_run(h, max_radius, mode, batch, n_labelled, d_labels, stats, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+  return sharded_walk_call(h, mode, sharded_caller_stream(h, stream), [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+    return vc_levels_run(v, max_radius, batch, n_labelled, d_labels, stats, S, err);
+  });
 }
 
 int vc_sharded_cluster_levels(vc_sharded* h, uint32_t max_radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
@@ -2275,181 +2197,32 @@ int vc_sharded_cluster_levels(vc_sharded* h, uint32_t max_radius, uint32_t mode,
   if (rc) return rc;
   if (stats) *stats = vc_levels_stats{};
   if (h->n == 0) return VC_OK;
-  hipStream_t S = h->root_stream;
-  const size_t N = (size_t)h->n, levels = (size_t)max_radius + 1;
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[CL_HLAB].grow(h, levels * N * 4))) return rc;
-  uint32_t* d_hlab = h->buf[CL_HLAB].as<uint32_t>();
-  if (n_labelled)
-    for (size_t r = 0; r < levels; ++r) VS_HIP(h, hipMemcpyAsync(d_hlab + r * N, labels + r * N, (size_t)n_labelled * 4, hipMemcpyHostToDevice, S));
-  if ((rc = sharded_levels_run(h, max_radius, mode, batch, n_labelled, d_hlab, stats, S))) return rc;
-  VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, hipMemcpyAsync(labels, d_hlab, levels * N * 4, hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipStreamSynchronize(S));
-  return VC_OK;
+  return sharded_walk_call(h, mode, h->root_stream, [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+    return vc_levels_run_host(v, max_radius, batch, n_labelled, labels, stats, S, err);
+  });
 }
-
-}  // extern "C"
-
-// ---- greedy leader dedup over the shards ----------------------------------------------------------------------------------------------
-static int check_sharded_leaders_args(vc_sharded* h, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
-  if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
-  if (n_labelled > h->n) return sfail(h, VC_ERR_INVALID, "leaders: n_labelled %llu exceeds the %llu resident records", (unsigned long long)n_labelled, (unsigned long long)h->n);
-  if (mode == VC_MODE_MIH_EXACT)
-    for (uint32_t g = 0; g < h->G; ++g)
-      if (shard_size(h, g) && !vc_engine_has_index(h->eng[g])) return sfail(h, VC_ERR_STATE, "shard %u: MIH search needs vc_sharded_build_index() first", g);
-  return VC_OK;
-}
-
-// All on the root device's stream S, h->n > 0.  sharded_cluster_run's loop over the batch buffers it shares with that call: per batch
-// of global ids, ascending, the ids filled on the root, the gather over the shards, the union's radius search -- repeated once with
-// the scratch grown to the total it reported -- and the decision rounds over the raw result on the root, which wait once per group
-// of rounds.  Entries below n_labelled are only read.  After the last batch one count, then the wait for the stats.
-static int sharded_leaders_run(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
-                               vc_leader_stats* stats, hipStream_t S) {
-  int rc;
-  const uint32_t id_base = h->cfg.engine.id_base;
-  const uint64_t N = h->n;
-  if (batch == 0) batch = VC_CLUSTER_BATCH;
-  batch = std::min(batch, VC_LEADER_BATCH_MAX);
-  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N - n_labelled);
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[LD_STAT].grow(h, VC_LEADER_STAT_BYTES))) return rc;
-  if (nq_max) {
-    if ((rc = h->buf[CL_IDS].grow(h, (size_t)nq_max * 4))) return rc;
-    if ((rc = h->buf[CL_Q].grow(h, (size_t)nq_max * h->nbytes))) return rc;
-    if ((rc = h->buf[CL_FOUND].grow(h, (size_t)nq_max * 4))) return rc;
-    if ((rc = h->buf[CL_ROFFS].grow(h, ((size_t)nq_max + 1) * 8))) return rc;
-    if ((rc = h->buf[CL_RAW].grow(h, (size_t)8 << 16))) return rc;
-    if ((rc = h->buf[LD_STATE].grow(h, (size_t)nq_max * 4))) return rc;
-  }
-  uint64_t* d_stat = h->buf[LD_STAT].as<uint64_t>();
-  uint32_t* d_ids = h->buf[CL_IDS].as<uint32_t>();
-  VS_HIP(h, hipMemsetAsync(d_stat, 0, VC_LEADER_STAT_BYTES, S));
-  for (uint64_t pos = n_labelled; pos < N; pos += batch) {
-    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = id_base + (uint32_t)pos;
-    VS_HIP(h, hipSetDevice(h->root));
-    VS_HIP(h, vc_launch_cluster_init(d_ids, nq, first_id, S));
-    if ((rc = sharded_gather_ids(h, d_ids, nq, h->buf[CL_Q].as<uint64_t>(), h->buf[CL_FOUND].as<uint32_t>(), true, S))) return rc;
-    uint64_t raw_total = 0;
-    for (int attempt = 0;; ++attempt) {
-      const uint64_t cap = h->buf[CL_RAW].bytes / 8;
-      rc = sharded_radius_dev(h, h->buf[CL_Q].p, nq, radius, mode, h->buf[CL_RAW].as<uint64_t>(), cap, h->buf[CL_ROFFS].as<uint64_t>(), S, &raw_total);
-      if (rc == VC_OK) break;
-      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
-      VS_HIP(h, hipSetDevice(h->root));
-      if ((rc = h->buf[CL_RAW].grow(h, (size_t)raw_total * 8))) return rc;
-    }
-    VS_HIP(h, hipSetDevice(h->root));
-    bool stuck = false;
-    VS_HIP(h, vc_leaders_decide_batch(h->buf[CL_RAW].as<uint64_t>(), h->buf[CL_ROFFS].as<uint64_t>(), nq, first_id, id_base, d_labels,
-                                      h->buf[LD_STATE].as<uint32_t>(), d_stat, S, &stuck));
-    if (stuck) return sfail(h, VC_ERR_HIP, "leaders: the batch at id %u is undecided after %u rounds", first_id, nq);
-  }
-  VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, vc_launch_leaders_count(d_labels, N, id_base, d_stat + 1, S));
-  uint64_t st[3] = {0, 0, 0};
-  VS_HIP(h, hipMemcpyAsync(st, d_stat, 24, hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipStreamSynchronize(S));
-  if (stats) *stats = vc_leader_stats{st[0], st[1], st[2]};
-  return VC_OK;
-}
-
-extern "C" {
 
 int vc_sharded_leaders_radius_dev(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
                                   vc_leader_stats* stats, void* stream) {
-  int rc = check_sharded_leaders_args(h, mode, n_labelled, d_labels);
+  int rc = check_sharded_cluster_args(h, "leaders", mode, n_labelled, d_labels);
   if (rc) return rc;
   if (stats) *stats = vc_leader_stats{0, 0, 0};
   if (h->n == 0) return VC_OK;
-  return sharded_leaders_run(h, radius, mode, batch, n_labelled, d_labels, stats, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+  return sharded_walk_call(h, mode, sharded_caller_stream(h, stream), [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+    return vc_leaders_run(v, radius, batch, n_labelled, d_labels, stats, S, err);
+  });
 }
 
 int vc_sharded_leaders_radius(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* labels,
                               vc_leader_stats* stats) {
-  int rc = check_sharded_leaders_args(h, mode, n_labelled, labels);
+  int rc = check_sharded_cluster_args(h, "leaders", mode, n_labelled, labels);
   if (rc) return rc;
   if (stats) *stats = vc_leader_stats{0, 0, 0};
   if (h->n == 0) return VC_OK;
-  hipStream_t S = h->root_stream;
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[CL_HLAB].grow(h, (size_t)h->n * 4))) return rc;
-  if (n_labelled) VS_HIP(h, hipMemcpyAsync(h->buf[CL_HLAB].p, labels, (size_t)n_labelled * 4, hipMemcpyHostToDevice, S));
-  if ((rc = sharded_leaders_run(h, radius, mode, batch, n_labelled, h->buf[CL_HLAB].as<uint32_t>(), stats, S))) return rc;
-  VS_HIP(h, hipSetDevice(h->root));
-  if (n_labelled < h->n)   // the incoming entries are read only: they do not travel back
-    VS_HIP(h, hipMemcpyAsync(labels + n_labelled, h->buf[CL_HLAB].as<uint32_t>() + n_labelled, (size_t)(h->n - n_labelled) * 4, hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipStreamSynchronize(S));
-  return VC_OK;
+  return sharded_walk_call(h, mode, h->root_stream, [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+    return vc_leaders_run_host(v, radius, batch, n_labelled, labels, stats, S, err);
+  });
 }
-
-}  // extern "C"
-
-// ---- density clustering over the shards -----------------------------------------------------------------------------------------------
-static int check_sharded_dbscan_args(vc_sharded* h, uint32_t min_pts, uint32_t mode, const uint32_t* labels) {
-  if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
-  if (min_pts == 0) return sfail(h, VC_ERR_INVALID, "dbscan: min_pts must be at least 1");
-  if (mode == VC_MODE_MIH_EXACT)
-    for (uint32_t g = 0; g < h->G; ++g)
-      if (shard_size(h, g) && !vc_engine_has_index(h->eng[g])) return sfail(h, VC_ERR_STATE, "shard %u: MIH search needs vc_sharded_build_index() first", g);
-  return VC_OK;
-}
-
-// All on the root device's stream S, h->n > 0.  sharded_cluster_run's loop over the batch buffers it shares with that call: per batch
-// of global ids, ascending, the ids filled on the root, the gather over the shards, the union's radius search -- repeated once with
-// the scratch grown to the total it reported -- then the batch's degrees and its edges over the raw result on the root.  d_degrees
-// null: the handle's own.  After the last batch one finish pass, then the one wait for the stats.
-static int sharded_dbscan_run(vc_sharded* h, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels, uint32_t* d_degrees,
-                              vc_dbscan_stats* stats, hipStream_t S) {
-  int rc;
-  const uint32_t id_base = h->cfg.engine.id_base;
-  const uint64_t N = h->n;
-  if (batch == 0) batch = VC_CLUSTER_BATCH;
-  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N);
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[DB_STAT].grow(h, VC_DBSCAN_STAT_BYTES))) return rc;
-  if (!d_degrees) {
-    if ((rc = h->buf[DB_DEG].grow(h, (size_t)N * 4))) return rc;
-    d_degrees = h->buf[DB_DEG].as<uint32_t>();
-  }
-  if ((rc = h->buf[CL_IDS].grow(h, (size_t)nq_max * 4))) return rc;
-  if ((rc = h->buf[CL_Q].grow(h, (size_t)nq_max * h->nbytes))) return rc;
-  if ((rc = h->buf[CL_FOUND].grow(h, (size_t)nq_max * 4))) return rc;
-  if ((rc = h->buf[CL_ROFFS].grow(h, ((size_t)nq_max + 1) * 8))) return rc;
-  if ((rc = h->buf[CL_RAW].grow(h, (size_t)8 << 16))) return rc;
-  uint64_t* d_stat = h->buf[DB_STAT].as<uint64_t>();
-  uint32_t* d_ids = h->buf[CL_IDS].as<uint32_t>();
-  VS_HIP(h, hipMemsetAsync(d_stat, 0, VC_DBSCAN_STAT_BYTES, S));
-  VS_HIP(h, vc_launch_cluster_init(d_labels, N, id_base, S));
-  for (uint64_t pos = 0; pos < N; pos += batch) {
-    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = id_base + (uint32_t)pos;
-    VS_HIP(h, hipSetDevice(h->root));
-    VS_HIP(h, vc_launch_cluster_init(d_ids, nq, first_id, S));
-    if ((rc = sharded_gather_ids(h, d_ids, nq, h->buf[CL_Q].as<uint64_t>(), h->buf[CL_FOUND].as<uint32_t>(), true, S))) return rc;
-    uint64_t raw_total = 0;
-    for (int attempt = 0;; ++attempt) {
-      const uint64_t cap = h->buf[CL_RAW].bytes / 8;
-      rc = sharded_radius_dev(h, h->buf[CL_Q].p, nq, radius, mode, h->buf[CL_RAW].as<uint64_t>(), cap, h->buf[CL_ROFFS].as<uint64_t>(), S, &raw_total);
-      if (rc == VC_OK) break;
-      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
-      VS_HIP(h, hipSetDevice(h->root));
-      if ((rc = h->buf[CL_RAW].grow(h, (size_t)raw_total * 8))) return rc;
-    }
-    VS_HIP(h, hipSetDevice(h->root));
-    VS_HIP(h, vc_launch_dbscan_edges(h->buf[CL_RAW].as<uint64_t>(), h->buf[CL_ROFFS].as<uint64_t>(), nq, raw_total, first_id, id_base, min_pts, d_degrees,
-                                     d_labels, d_stat, S));
-  }
-  VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, vc_launch_dbscan_finish(d_labels, d_degrees, N, id_base, min_pts, d_stat + 1, S));
-  uint64_t st[5] = {0, 0, 0, 0, 0};
-  VS_HIP(h, hipMemcpyAsync(st, d_stat, VC_DBSCAN_STAT_BYTES, hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipStreamSynchronize(S));
-  if (stats) *stats = vc_dbscan_stats{st[0], st[1], st[2], st[3], st[4]};
-  return VC_OK;
-}
-
-extern "C" {
 
 int vc_sharded_dbscan_radius_dev(vc_sharded* h, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels,
                                  uint32_t* d_degrees, vc_dbscan_stats* stats, void* stream) {
@@ -2457,7 +2230,9 @@ int vc_sharded_dbscan_radius_dev(vc_sharded* h, uint32_t radius, uint32_t min_pt
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_stats{0, 0, 0, 0, 0};
   if (h->n == 0) return VC_OK;
-  return sharded_dbscan_run(h, radius, min_pts, mode, batch, d_labels, d_degrees, stats, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+  return sharded_walk_call(h, mode, sharded_caller_stream(h, stream), [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+    return vc_dbscan_run(v, radius, min_pts, batch, d_labels, d_degrees, stats, S, err);
+  });
 }
 
 int vc_sharded_dbscan_radius(vc_sharded* h, uint32_t radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* degrees,
@@ -2466,82 +2241,10 @@ int vc_sharded_dbscan_radius(vc_sharded* h, uint32_t radius, uint32_t min_pts, u
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_stats{0, 0, 0, 0, 0};
   if (h->n == 0) return VC_OK;
-  hipStream_t S = h->root_stream;
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[CL_HLAB].grow(h, (size_t)h->n * 4))) return rc;
-  if ((rc = sharded_dbscan_run(h, radius, min_pts, mode, batch, h->buf[CL_HLAB].as<uint32_t>(), nullptr, stats, S))) return rc;
-  VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, hipMemcpyAsync(labels, h->buf[CL_HLAB].p, (size_t)h->n * 4, hipMemcpyDeviceToHost, S));
-  if (degrees) VS_HIP(h, hipMemcpyAsync(degrees, h->buf[DB_DEG].p, (size_t)h->n * 4, hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipStreamSynchronize(S));
-  return VC_OK;
+  return sharded_walk_call(h, mode, h->root_stream, [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+    return vc_dbscan_run_host(v, radius, min_pts, batch, labels, degrees, stats, S, err);
+  });
 }
-
-}  // extern "C"
-
-// ---- density clustering at every radius over the shards -------------------------------------------------------------------------------
-static int check_sharded_dbscan_levels_args(vc_sharded* h, uint32_t max_radius, uint32_t min_pts, uint32_t mode, const uint32_t* labels) {
-  if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
-  if (max_radius >= VC_LEVELS_MAX) return sfail(h, VC_ERR_INVALID, "dbscan levels: max_radius %u exceeds %u", max_radius, VC_LEVELS_MAX - 1);
-  return check_sharded_dbscan_args(h, min_pts, mode, labels);
-}
-
-// All on the root device's stream S, h->n > 0.  sharded_levels_run's loop over the batch buffers it shares with that call, at
-// max_radius and in ascending id order: per batch of global ids the ids filled on the root, the gather over the shards, the union's
-// radius search -- repeated once with the scratch grown to the total it reported -- then the batch's core distances and its edges
-// over the raw result on the root.  d_core_dist null: the handle's own.  After the last batch the cascade, one finish pass over all
-// levels, then the one wait for the counters.
-static int sharded_dbscan_levels_run(vc_sharded* h, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels,
-                                     uint32_t* d_core_dist, vc_dbscan_levels_stats* stats, hipStream_t S) {
-  int rc;
-  const uint32_t id_base = h->cfg.engine.id_base;
-  const uint64_t N = h->n;
-  if (batch == 0) batch = VC_CLUSTER_BATCH;
-  const uint32_t nq_max = (uint32_t)std::min<uint64_t>(batch, N);
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[DL_STAT].grow(h, VC_DBSCAN_LEVELS_STAT_BYTES))) return rc;
-  if (!d_core_dist) {
-    if ((rc = h->buf[DL_CD].grow(h, (size_t)N * 4))) return rc;
-    d_core_dist = h->buf[DL_CD].as<uint32_t>();
-  }
-  if ((rc = h->buf[CL_IDS].grow(h, (size_t)nq_max * 4))) return rc;
-  if ((rc = h->buf[CL_Q].grow(h, (size_t)nq_max * h->nbytes))) return rc;
-  if ((rc = h->buf[CL_FOUND].grow(h, (size_t)nq_max * 4))) return rc;
-  if ((rc = h->buf[CL_ROFFS].grow(h, ((size_t)nq_max + 1) * 8))) return rc;
-  if ((rc = h->buf[CL_RAW].grow(h, (size_t)8 << 16))) return rc;
-  uint64_t* d_stat = h->buf[DL_STAT].as<uint64_t>();
-  uint32_t* d_ids = h->buf[CL_IDS].as<uint32_t>();
-  VS_HIP(h, hipMemsetAsync(d_stat, 0, VC_DBSCAN_LEVELS_STAT_BYTES, S));
-  for (uint32_t r = 0; r <= max_radius; ++r) VS_HIP(h, vc_launch_cluster_init(d_labels + (uint64_t)r * N, N, id_base, S));
-  for (uint64_t pos = 0; pos < N; pos += batch) {
-    const uint32_t nq = (uint32_t)std::min<uint64_t>(batch, N - pos), first_id = id_base + (uint32_t)pos;
-    VS_HIP(h, hipSetDevice(h->root));
-    VS_HIP(h, vc_launch_cluster_init(d_ids, nq, first_id, S));
-    if ((rc = sharded_gather_ids(h, d_ids, nq, h->buf[CL_Q].as<uint64_t>(), h->buf[CL_FOUND].as<uint32_t>(), true, S))) return rc;
-    uint64_t raw_total = 0;
-    for (int attempt = 0;; ++attempt) {
-      const uint64_t cap = h->buf[CL_RAW].bytes / 8;
-      rc = sharded_radius_dev(h, h->buf[CL_Q].p, nq, max_radius, mode, h->buf[CL_RAW].as<uint64_t>(), cap, h->buf[CL_ROFFS].as<uint64_t>(), S, &raw_total);
-      if (rc == VC_OK) break;
-      if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
-      VS_HIP(h, hipSetDevice(h->root));
-      if ((rc = h->buf[CL_RAW].grow(h, (size_t)raw_total * 8))) return rc;
-    }
-    VS_HIP(h, hipSetDevice(h->root));
-    VS_HIP(h, vc_launch_dbscan_levels_edges(h->buf[CL_RAW].as<uint64_t>(), h->buf[CL_ROFFS].as<uint64_t>(), nq, raw_total, first_id, id_base, N, max_radius,
-                                            min_pts, d_core_dist, d_labels, d_stat, S));
-  }
-  VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, vc_launch_dbscan_levels_cascade(d_labels, d_core_dist, N, id_base, max_radius, S));
-  VS_HIP(h, vc_launch_dbscan_levels_finish(d_labels, d_core_dist, N, id_base, max_radius, d_stat + VC_LEVELS_MAX, S));
-  vc_dbscan_levels_stats st;
-  VS_HIP(h, hipMemcpyAsync(&st, d_stat, VC_DBSCAN_LEVELS_STAT_BYTES, hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipStreamSynchronize(S));
-  if (stats) *stats = st;
-  return VC_OK;
-}
-
-extern "C" {
 
 int vc_sharded_dbscan_levels_dev(vc_sharded* h, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* d_labels,
                                  uint32_t* d_core_dist, vc_dbscan_levels_stats* stats, void* stream) {
@@ -2549,8 +2252,9 @@ int vc_sharded_dbscan_levels_dev(vc_sharded* h, uint32_t max_radius, uint32_t mi
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_levels_stats{};
   if (h->n == 0) return VC_OK;
-  return sharded_dbscan_levels_run(h, max_radius, min_pts, mode, batch, d_labels, d_core_dist, stats,
-                                   stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+  return sharded_walk_call(h, mode, sharded_caller_stream(h, stream), [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+    return vc_dbscan_levels_run(v, max_radius, min_pts, batch, d_labels, d_core_dist, stats, S, err);
+  });
 }
 
 int vc_sharded_dbscan_levels(vc_sharded* h, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint32_t batch, uint32_t* labels, uint32_t* core_dist,
@@ -2559,16 +2263,9 @@ int vc_sharded_dbscan_levels(vc_sharded* h, uint32_t max_radius, uint32_t min_pt
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_levels_stats{};
   if (h->n == 0) return VC_OK;
-  hipStream_t S = h->root_stream;
-  const size_t N = (size_t)h->n, levels = (size_t)max_radius + 1;
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[CL_HLAB].grow(h, levels * N * 4))) return rc;
-  if ((rc = sharded_dbscan_levels_run(h, max_radius, min_pts, mode, batch, h->buf[CL_HLAB].as<uint32_t>(), nullptr, stats, S))) return rc;
-  VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, hipMemcpyAsync(labels, h->buf[CL_HLAB].p, levels * N * 4, hipMemcpyDeviceToHost, S));
-  if (core_dist) VS_HIP(h, hipMemcpyAsync(core_dist, h->buf[DL_CD].p, N * 4, hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipStreamSynchronize(S));
-  return VC_OK;
+  return sharded_walk_call(h, mode, h->root_stream, [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+    return vc_dbscan_levels_run_host(v, max_radius, min_pts, batch, labels, core_dist, stats, S, err);
+  });
 }
 
 }  // extern "C"
