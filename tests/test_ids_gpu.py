@@ -23,7 +23,7 @@ def _make(vc, name, flags=0, devices=(0,), indexed=True, cand_cap=0):
     s = I.SHAPES[name]
     if s["shards"]:
         e = vc.ShardedEngine(s["bits"], capacity=s["capacity"], n_shards=s["shards"], n_tables=s["m"], devices=list(devices),
-                             id_base=s["id_base"], flags=flags)
+                             id_base=s["id_base"], flags=flags, cand_cap=cand_cap)
     else:
         e = vc.Engine(s["bits"], capacity=s["capacity"], n_tables=s["m"], id_base=s["id_base"], flags=flags, cand_cap=cand_cap)
     e.add_codes(I.codes_of(name))
@@ -384,19 +384,23 @@ def test_history_independence(vc, name):
 # ---- a LINEAR batch whose device-side ring-overflow recovery gives up -----------------------------------------------------------
 def test_host_form_recovers_on_the_host_when_the_device_gives_up(vc, oracle, monkeypatch):
     """rings of 4 entries against the group of 40 identical codes: the rows overflow; the first recover launch is made to give
-    up (test knob, bounded spin), so the host form answers the batch through vc_search_knn's host-driven recovery and strips on
-    the host -- the same rows"""
+    up (test knob, bounded spin), so the host form answers the batch through the host-form k-NN of its handle kind, whose
+    host-driven recovery always ends, and strips on the host -- the same rows.  The fallback is one driver for both kinds, so
+    the sharded shape H3 runs it too; its shards each sabotage their own first recover launch."""
     monkeypatch.setenv("VC_RECOVER_TEST_FAIL", "1")
     monkeypatch.setenv("VC_RECOVER_SPIN_LIMIT", "200")
-    name, k = "S128", 6
-    ids = np.array([I.GROUP40[0], I.GROUP40[39], 0xFFFFFFFF, I.GROUP7[3]], dtype=np.uint32)
-    with _make(vc, name, cand_cap=4) as store:
-        for id_flags in (vc.IDS_EXCLUDE_SELF, 0):                             # (the knob sabotages the first launch only)
-            got, cnt = store.search_knn_ids(ids, k, mode=vc.MODE_LINEAR, id_flags=id_flags)
-            for i, qid in enumerate(ids):
-                exp = _linear_expect(oracle, name, qid, k, bool(id_flags))
-                assert cnt[i] == len(exp) and np.array_equal(got[i], I.padded(exp, k)), (id_flags, i)
-        assert store.device_status() == 1
+    k = 6
+    for name in ("S128", "H3"):
+        base = I.SHAPES[name]["id_base"]
+        ids = np.array([base + I.GROUP40[0], base + I.GROUP40[39], 0xFFFFFFFF, base + I.GROUP7[3]], dtype=np.uint32)
+        with _make(vc, name, cand_cap=4) as store:
+            for id_flags in (vc.IDS_EXCLUDE_SELF, 0):                         # (the knob sabotages the first launch only)
+                got, cnt = store.search_knn_ids(ids, k, mode=vc.MODE_LINEAR, id_flags=id_flags)
+                for i, qid in enumerate(ids):
+                    exp = _linear_expect(oracle, name, qid, k, bool(id_flags))
+                    assert cnt[i] == len(exp) and np.array_equal(got[i], I.padded(exp, k)), (name, id_flags, i)
+            if name == "S128":
+                assert store.device_status() == 1
 
 
 # ---- 7. two devices -------------------------------------------------------------------------------------------------------------

@@ -93,7 +93,7 @@ hipError_t vc_launch_cluster_flatten(uint32_t* d_labels, uint64_t n, uint32_t id
   return hipGetLastError();
 }
 
-int vc_cluster_run(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_cluster_stats* stats, hipStream_t s,
+int vc_cluster_run(const VcStoreView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_cluster_stats* stats, hipStream_t s,
                    std::string* err) {
   const uint64_t first_new = (uint64_t)v.id_base + n_labelled;
   uint64_t* d_stat = (uint64_t*)v.alloc(VC_WALK_STAT, 16);
@@ -113,7 +113,7 @@ int vc_cluster_run(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_
   return VC_OK;
 }
 
-int vc_cluster_run_host(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats, hipStream_t s,
+int vc_cluster_run_host(const VcStoreView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats, hipStream_t s,
                         std::string* err) {
   uint32_t* d_labels = nullptr;
   int rc = vc_walk_stage_labels(v, labels, 1, n_labelled, &d_labels, s, err);

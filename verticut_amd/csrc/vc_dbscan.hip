@@ -138,7 +138,7 @@ hipError_t vc_launch_dbscan_finish(uint32_t* d_labels, const uint32_t* d_degrees
   return hipGetLastError();
 }
 
-int vc_dbscan_run(const VcWalkView& v, uint32_t radius, uint32_t min_pts, uint32_t batch, uint32_t* d_labels, uint32_t* d_degrees, vc_dbscan_stats* stats,
+int vc_dbscan_run(const VcStoreView& v, uint32_t radius, uint32_t min_pts, uint32_t batch, uint32_t* d_labels, uint32_t* d_degrees, vc_dbscan_stats* stats,
                   hipStream_t s, std::string* err) {
   const uint64_t N = v.n;
   uint64_t* d_stat = (uint64_t*)v.alloc(VC_WALK_STAT, VC_DBSCAN_STAT_BYTES);
@@ -159,7 +159,7 @@ int vc_dbscan_run(const VcWalkView& v, uint32_t radius, uint32_t min_pts, uint32
   return VC_OK;
 }
 
-int vc_dbscan_run_host(const VcWalkView& v, uint32_t radius, uint32_t min_pts, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats,
+int vc_dbscan_run_host(const VcStoreView& v, uint32_t radius, uint32_t min_pts, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats,
                        hipStream_t s, std::string* err) {
   const size_t bytes = (size_t)v.n * 4;
   uint32_t* d_labels = nullptr;

@@ -201,7 +201,7 @@ hipError_t vc_launch_dbscan_levels_finish(uint32_t* d_labels, const uint32_t* d_
   return hipGetLastError();
 }
 
-int vc_dbscan_levels_run(const VcWalkView& v, uint32_t max_radius, uint32_t min_pts, uint32_t batch, uint32_t* d_labels, uint32_t* d_core_dist,
+int vc_dbscan_levels_run(const VcStoreView& v, uint32_t max_radius, uint32_t min_pts, uint32_t batch, uint32_t* d_labels, uint32_t* d_core_dist,
                          vc_dbscan_levels_stats* stats, hipStream_t s, std::string* err) {
   const uint64_t N = v.n;
   uint64_t* d_stat = (uint64_t*)v.alloc(VC_WALK_STAT, VC_DBSCAN_LEVELS_STAT_BYTES);
@@ -224,7 +224,7 @@ int vc_dbscan_levels_run(const VcWalkView& v, uint32_t max_radius, uint32_t min_
   return VC_OK;
 }
 
-int vc_dbscan_levels_run_host(const VcWalkView& v, uint32_t max_radius, uint32_t min_pts, uint32_t batch, uint32_t* labels, uint32_t* core_dist,
+int vc_dbscan_levels_run_host(const VcStoreView& v, uint32_t max_radius, uint32_t min_pts, uint32_t batch, uint32_t* labels, uint32_t* core_dist,
                               vc_dbscan_levels_stats* stats, hipStream_t s, std::string* err) {
   const size_t N = (size_t)v.n, levels = (size_t)max_radius + 1;
   uint32_t* d_labels = nullptr;

@@ -270,7 +270,7 @@ struct DistinctWork {
 
 // THE ROUNDS (the header states the rule).  Per round: the search underneath and the collapse, sub-batch by sub-batch; then, unless
 // no query can be left, the scan of the flags and the gather; then the one wait, for the length of the retry list and the tally.
-int vc_distinct_run(const VcDistinctArgs& a, const VcDistinctSearch& search, vc_distinct_stats* stats, hipStream_t s, std::string* err) {
+int vc_distinct_run(const VcDistinctArgs& a, const VcKnnSearch& search, vc_distinct_stats* stats, hipStream_t s, std::string* err) {
   if (stats) *stats = vc_distinct_stats{};
   if (a.n_labels == 0) {
     const uint64_t total = (uint64_t)a.nq * a.k;
@@ -303,7 +303,7 @@ int vc_distinct_run(const VcDistinctArgs& a, const VcDistinctSearch& search, vc_
     if (!rows) return VC_ERR_NOMEM;
     for (uint32_t first = 0; first < n; first += batch) {
       const uint32_t nb = std::min(batch, n - first);
-      const int rc = search(q + (uint64_t)first * a.W, nb, kp, rows, cnt);
+      const int rc = search(q + (uint64_t)first * a.W, nb, kp, rows, cnt, nullptr);
       if (rc) return rc;
       CollapseArgs c{};
       c.rows = rows; c.cnt = cnt; c.n = nb; c.kp = kp; c.k = a.k; c.tie_cut = a.tie_cut ? 1u : 0u;

@@ -41,42 +41,9 @@ struct vc_engine {
   uint64_t* d_frows = nullptr;  size_t frows_bytes = 0;
   uint32_t* d_fcnt = nullptr;   size_t fcnt_bytes = 0;
   uint32_t* d_rec = nullptr;                              // scratch of the device-side ring-overflow recovery (zero at first use)
-  // queries named by id (vc_search_knn_ids*): the gathered queries, their found words, the k + 1 rows and counts of the search
-  // underneath; and what the host-pointer form stages on the device (ids, rows, counts, statistics)
-  uint64_t* d_idq = nullptr;    size_t idq_bytes = 0;
-  uint32_t* d_idfound = nullptr; size_t idfound_bytes = 0;
-  uint64_t* d_idrows = nullptr; size_t idrows_bytes = 0;
-  uint32_t* d_idcnt = nullptr;  size_t idcnt_bytes = 0;
-  uint32_t* d_hids = nullptr;   size_t hids_bytes = 0;
-  uint64_t* d_hrows = nullptr;  size_t hrows_bytes = 0;
-  uint32_t* d_hcnt = nullptr;   size_t hcnt_bytes = 0;
-  vc_query_stats* d_hstats = nullptr; size_t hstats_bytes = 0;
-  // radius search by id (vc_search_radius_ids*): the gathered queries, their found words, the uncompacted results and offsets of the
-  // search underneath, the compaction's counts (VcIdsRadiusWork); and the host-pointer form's staged ids, results and offsets
-  uint64_t* d_rq = nullptr;     size_t rq_bytes = 0;
-  uint32_t* d_rfound = nullptr; size_t rfound_bytes = 0;
-  uint64_t* d_rraw = nullptr;   size_t rraw_bytes = 0;
-  uint64_t* d_rroffs = nullptr; size_t rroffs_bytes = 0;
-  uint8_t* d_rwork = nullptr;   size_t rwork_bytes = 0;
-  uint32_t* d_rhids = nullptr;  size_t rhids_bytes = 0;
-  uint64_t* d_rhout = nullptr;  size_t rhout_bytes = 0;
-  uint64_t* d_rhoffs = nullptr; size_t rhoffs_bytes = 0;
-  // the clustering calls over the radius-graph walk (vc_cluster_radius*, vc_cluster_levels*, vc_leaders_radius*, vc_dbscan_radius*,
-  // vc_dbscan_levels*): the walk's batch buffers, the statistics, the per-record words, leaders' state words and the host forms' staged
-  // labels (VC_WALK_*); shared by the five calls, each writes every word it reads
-  uint8_t* d_walk[VC_WALK_BUFS] = {};  size_t walk_bytes[VC_WALK_BUFS] = {};
-  // label groups summarised (vc_group_summary*): the sort and numbering arrays, the row buffer with the big groups' tables, the host
-  // form's staging (VC_GROUPS_*); its own, shared with no other call, every word written before it is read
-  uint8_t* d_grp[VC_GROUPS_BUFS] = {nullptr, nullptr, nullptr};  size_t grp_bytes[VC_GROUPS_BUFS] = {0, 0, 0};
-  // nearest of K codes and k-majority (vc_assign_nearest*, vc_kmajority*): the round driver's arrays, the host forms' staging
-  // (VC_KMAJ_*); their own, every word written before it is read
-  uint8_t* d_kmaj[VC_KMAJ_BUFS] = {nullptr, nullptr};  size_t kmaj_bytes[VC_KMAJ_BUFS] = {0, 0};
-  // device-side seeding (vc_seed_centres*): slots, statistics, partials and best; the host form's staging (VC_SEED_*); its own, every
-  // word written before it is read
-  uint8_t* d_seed[VC_SEED_BUFS] = {nullptr, nullptr};  size_t seed_bytes[VC_SEED_BUFS] = {0, 0};
-  // one result per label group (vc_search_knn_distinct*): flags, maps, retry queries and counters; the k' rows; the host form's staging
-  // (VC_DISTINCT_*); its own, every word written before it is read
-  uint8_t* d_distinct[VC_DISTINCT_BUFS] = {nullptr, nullptr, nullptr};  size_t distinct_bytes[VC_DISTINCT_BUFS] = {0, 0, 0};
+  // the scratch of the drivers this engine shares with the sharded store (VcScratch, vc_internal.hpp): the walk's, the groups',
+  // k-majority's, seeding's, the distinct search's and the two by-id searches'
+  DevBuf scratch[VC_SCRATCH_BUFS];
   CleanState clean;                                       // the last kernel of a linear step hands d_state back zeroed: no memset per step
   uint32_t scan_event_tick = 0;                           // VC_FLAG_LEAN_TIMING: only every timing_sample-th verify launch is timed
   VcKnobs knobs;                                          // environment knobs, read once at vc_create
@@ -355,27 +322,7 @@ int vc_destroy(vc_engine* e) {
   (void)hipFree(e->d_fq);
   (void)hipFree(e->d_frows);
   (void)hipFree(e->d_fcnt);
-  (void)hipFree(e->d_idq);
-  (void)hipFree(e->d_idfound);
-  (void)hipFree(e->d_idrows);
-  (void)hipFree(e->d_idcnt);
-  (void)hipFree(e->d_hids);
-  (void)hipFree(e->d_hrows);
-  (void)hipFree(e->d_hcnt);
-  (void)hipFree(e->d_hstats);
-  (void)hipFree(e->d_rq);
-  (void)hipFree(e->d_rfound);
-  (void)hipFree(e->d_rraw);
-  (void)hipFree(e->d_rroffs);
-  (void)hipFree(e->d_rwork);
-  (void)hipFree(e->d_rhids);
-  (void)hipFree(e->d_rhout);
-  (void)hipFree(e->d_rhoffs);
-  for (uint8_t* b : e->d_walk) (void)hipFree(b);
-  for (uint8_t* b : e->d_grp) (void)hipFree(b);
-  for (uint8_t* b : e->d_kmaj) (void)hipFree(b);
-  for (uint8_t* b : e->d_seed) (void)hipFree(b);
-  for (uint8_t* b : e->d_distinct) (void)hipFree(b);
+  for (DevBuf& b : e->scratch) b.release();
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   if (e->last_call) (void)hipEventDestroy(e->last_call);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -1101,6 +1048,51 @@ int vc_search_knn_dev_stats(vc_engine* e, const void* d_queries, uint32_t nq, ui
 
 }  // extern "C"
 
+// ---- the engine as the drivers it shares with the sharded store see it ---------------------------------------------------------
+static VcScratchAlloc scratch_alloc(vc_engine* e) {   // buffer `which` of the engine's table (VcScratch)
+  return [e](int which, size_t bytes) -> void* {
+    DevBuf& b = e->scratch[which];
+    hipError_t r = b.regrow(bytes);
+    if (r != hipSuccess) fail(e, r == hipErrorOutOfMemory ? VC_ERR_NOMEM : VC_ERR_HIP, "scratch buffer %d: %s", which, hipGetErrorString(r));
+    return r == hipSuccess ? b.p : nullptr;
+  };
+}
+
+// The view of one call, used inside the caller's StreamCall: everything goes to e->stream, the one device is current throughout.
+static VcStoreView store_view(vc_engine* e, uint32_t mode) {
+  VcStoreView v;
+  v.n = e->n;
+  v.id_base = e->cfg.id_base;
+  v.W = e->W;
+  v.alloc = scratch_alloc(e);
+  v.held = [e](int which) { return e->scratch[which].bytes; };
+  v.gather = [e](const uint32_t* d_ids, uint32_t nq, uint64_t* d_q, uint32_t* d_found) -> int {
+    VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, d_ids, nq, d_q, d_found, e->stream));
+    return VC_OK;
+  };
+  v.search = [e, mode](const uint64_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_raw, uint64_t cap, uint64_t* d_roffs, uint64_t* raw_total) {
+    return vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, d_q, nq, radius,
+                            d_raw, cap, d_roffs, true, &e->radius_work, e->stream, &e->err, raw_total);
+  };
+  v.knn = [e, mode](const uint64_t* d_q, uint32_t nq, uint32_t kp, uint64_t* d_rows, uint32_t* d_cnt, vc_query_stats* d_stats) {
+    return knn_dev_run(e, d_q, nq, kp, mode, d_rows, d_cnt, d_stats);
+  };
+  return v;
+}
+
+// what a driver returned: its own text, if it left one, into the handle (a closure of the view has left its text there itself)
+static int driver_done(vc_engine* e, int rc, const std::string& err) { return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc; }
+// An entry point after its checks: the device bound, `run` (a driver's vc_*_run or vc_*_run_host) on stream s inside a StreamCall.
+template <class Run>
+static int store_call(vc_engine* e, hipStream_t s, const Run& run) {
+  int rc = bind_device(e);
+  if (rc) return rc;
+  const StreamCall call(e, s);
+  std::string err;
+  rc = run(e->stream, &err);
+  return driver_done(e, rc, err);
+}
+
 // ---- queries named by id (vc_ids.hip) --------------------------------------------------------------------------------------
 static int check_ids_args(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t id_flags) {
   int rc = check_knn_args(e, ids, nq, k, mode);
@@ -1126,17 +1118,13 @@ int vc_search_knn_ids_dev(vc_engine* e, const uint32_t* d_ids, uint32_t nq, uint
   if (rc) return rc;
   if (!d_out) return VC_ERR_INVALID;
   if ((rc = bind_device(e))) return rc;
-  const uint32_t kp = k + ((id_flags & VC_IDS_EXCLUDE_SELF) ? 1u : 0u);
-  if ((rc = grow(e, &e->d_idq, &e->idq_bytes, (size_t)nq * e->W * 8))) return rc;
-  if ((rc = grow(e, &e->d_idfound, &e->idfound_bytes, (size_t)nq * 4))) return rc;
-  if ((rc = grow(e, &e->d_idrows, &e->idrows_bytes, (size_t)nq * kp * 8))) return rc;
-  if ((rc = grow(e, &e->d_idcnt, &e->idcnt_bytes, (size_t)nq * 4))) return rc;
-  const StreamCall call(e, caller_stream(e, stream));
-  VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, d_ids, nq, e->d_idq, e->d_idfound,
-                                 e->stream));
-  if ((rc = knn_dev_run(e, e->d_idq, nq, kp, mode, e->d_idrows, e->d_idcnt, d_stats))) return rc;
-  VC_HIP(e, vc_launch_ids_strip(d_ids, e->d_idfound, e->d_idrows, e->d_idcnt, nq, kp, k, d_out, d_counts, d_stats, e->stream));
-  return VC_OK;
+  const uint32_t kp = vc_ids_kp(k, id_flags);
+  const VcStoreView v = store_view(e, mode);
+  VcIdsKnnBufs b;
+  if ((rc = vc_ids_knn_reserve(v, nq, kp, &b))) return rc;   // outside the timed bracket, as vc_search_knn_dev_stats
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_ids_knn_run(v, b, d_ids, nq, kp, k, d_out, d_counts, d_stats, s, err);
+  });
 }
 
 int vc_search_knn_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, uint32_t id_flags,
@@ -1145,41 +1133,26 @@ int vc_search_knn_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t k
   if (rc) return rc;
   if (!out || order > VC_ORDER_FARTHEST_FIRST) return VC_ERR_INVALID;
   if ((rc = bind_device(e))) return rc;
-  if ((rc = grow(e, &e->d_hids, &e->hids_bytes, (size_t)nq * 4))) return rc;
-  if ((rc = grow(e, &e->d_hrows, &e->hrows_bytes, (size_t)nq * k * 8))) return rc;
-  if ((rc = grow(e, &e->d_hcnt, &e->hcnt_bytes, (size_t)nq * 4))) return rc;
-  if (stats && (rc = grow(e, &e->d_hstats, &e->hstats_bytes, (size_t)nq * sizeof(vc_query_stats)))) return rc;
-  VC_HIP(e, hipMemcpyAsync(e->d_hids, ids, (size_t)nq * 4, hipMemcpyHostToDevice, e->stream));
-  if ((rc = vc_search_knn_ids_dev(e, e->d_hids, nq, k, mode, id_flags, e->d_hrows, e->d_hcnt, stats ? e->d_hstats : nullptr, e->stream))) return rc;
-  std::vector<uint32_t> cnt(nq);
-  VC_HIP(e, hipMemcpyAsync(out, e->d_hrows, (size_t)nq * k * 8, hipMemcpyDeviceToHost, e->stream));
-  VC_HIP(e, hipMemcpyAsync(cnt.data(), e->d_hcnt, (size_t)nq * 4, hipMemcpyDeviceToHost, e->stream));
-  if (stats) VC_HIP(e, hipMemcpyAsync(stats, e->d_hstats, (size_t)nq * sizeof(vc_query_stats), hipMemcpyDeviceToHost, e->stream));
-  VC_HIP(e, hipStreamSynchronize(e->stream));
-  if (mode == VC_MODE_LINEAR && std::find(cnt.begin(), cnt.end(), 0xFFFFFFFFu) != cnt.end()) {
-    // a ring overflowed and the device-side recovery gave up: the batch is answered again by vc_search_knn, whose host-driven
-    // recovery always ends, on the gathered codes, and stripped here by the kernel's rule
-    const uint32_t kp = k + ((id_flags & VC_IDS_EXCLUDE_SELF) ? 1u : 0u);
-    std::vector<uint64_t> codes((size_t)nq * e->W), rows((size_t)nq * kp);
-    std::vector<uint32_t> found(nq), rcnt(nq);
-    VC_HIP(e, hipMemcpyAsync(codes.data(), e->d_idq, codes.size() * 8, hipMemcpyDeviceToHost, e->stream));
-    VC_HIP(e, hipMemcpyAsync(found.data(), e->d_idfound, (size_t)nq * 4, hipMemcpyDeviceToHost, e->stream));
-    VC_HIP(e, hipStreamSynchronize(e->stream));
-    if ((rc = vc_search_knn(e, codes.data(), nq, kp, mode, VC_ORDER_ASCENDING, rows.data(), rcnt.data(), stats))) return rc;
-    vc_ids_strip_host(ids, found.data(), rows.data(), rcnt.data(), nq, kp, k, out, cnt.data(), stats);
-  }
-  for (uint32_t i = 0; i < nq; ++i) {
-    if (mode != VC_MODE_LINEAR) cnt[i] = std::min(cnt[i], k);   // (as vc_sharded_search_knn: a flagged MIH row has k entries)
-    if (order == VC_ORDER_FARTHEST_FIRST) std::reverse(out + (size_t)i * k, out + (size_t)i * k + cnt[i]);
-    if (counts) counts[i] = cnt[i];
-    if (stats) stats[i].n_results = cnt[i];
-  }
-  return VC_OK;
+  const uint32_t kp = vc_ids_kp(k, id_flags);
+  const VcStoreView v = store_view(e, mode);
+  hipStream_t s = e->stream;
+  std::string err;
+  rc = vc_ids_knn_run_host(v, VcIdsKnnHostArgs{ids, nq, kp, k, order, mode == VC_MODE_LINEAR, out, counts, stats},
+                           [&](const VcIdsKnnBufs& b, const uint32_t* d_ids, uint64_t* d_out, uint32_t* d_counts, vc_query_stats* d_stats) {
+                             return store_call(e, s, [&](hipStream_t cs, std::string* cerr) {
+                               return vc_ids_knn_run(v, b, d_ids, nq, kp, k, d_out, d_counts, d_stats, cs, cerr);
+                             });
+                           },
+                           [&](const uint64_t* codes, uint64_t* rows, uint32_t* rcnt) {
+                             return vc_search_knn(e, codes, nq, kp, mode, VC_ORDER_ASCENDING, rows, rcnt, stats);
+                           },
+                           s, &err);
+  return driver_done(e, rc, err);
 }
 
 }  // extern "C"
 
-// ---- radius search for queries named by id ------------------------------------------------------------------------------------------
+// ---- radius search for queries named by id (vc_ids_radius.hip) -------------------------------------------------------------------
 static int check_radius_ids_args(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t mode, uint32_t id_flags, const uint64_t* out,
                                  uint64_t out_cap, const uint64_t* offsets) {
   if (!e || !ids || !offsets || (!out && out_cap) || nq == 0) return VC_ERR_INVALID;
@@ -1191,49 +1164,15 @@ static int check_radius_ids_args(vc_engine* e, const uint32_t* ids, uint32_t nq,
 
 int vc_engine_has_index(vc_engine* e) { return e && live_index(e) ? 1 : 0; }
 
-// The whole call on e->stream (inside the caller's StreamCall): gather, the radius search into the handle's scratch -- repeated once with
-// the scratch grown to the total it reported -- count / offsets, and, once T is known to fit, the copy.
-static int radius_ids_run(vc_engine* e, const uint32_t* d_ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* d_out,
-                          uint64_t out_cap, uint64_t* d_offsets) {
-  int rc;
-  if ((rc = grow(e, &e->d_rq, &e->rq_bytes, (size_t)nq * e->W * 8))) return rc;
-  if ((rc = grow(e, &e->d_rfound, &e->rfound_bytes, (size_t)nq * 4))) return rc;
-  if ((rc = grow(e, &e->d_rroffs, &e->rroffs_bytes, ((size_t)nq + 1) * 8))) return rc;
-  if ((rc = grow(e, &e->d_rraw, &e->rraw_bytes, (size_t)8 << 16))) return rc;
-  VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, d_ids, nq, e->d_rq, e->d_rfound, e->stream));
-  uint64_t raw_total = 0;
-  for (int attempt = 0;; ++attempt) {
-    const uint64_t cap = e->rraw_bytes / 8;
-    rc = vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, e->d_rq, nq,
-                          radius, e->d_rraw, cap, e->d_rroffs, true, &e->radius_work, e->stream, &e->err, &raw_total);
-    if (rc == VC_OK) break;
-    if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
-    if ((rc = grow(e, &e->d_rraw, &e->rraw_bytes, (size_t)raw_total * 8))) return rc;   // (the first attempt has been waited for)
-  }
-  const uint64_t items = vc_ids_radius_items(nq, raw_total);
-  if (items > 0xFFFFFFFFull) return fail(e, VC_ERR_CAPACITY, "radius search by id: more results than one compaction can place");
-  if ((rc = grow(e, &e->d_rwork, &e->rwork_bytes, VcIdsRadiusWork::bytes(nq, items)))) return rc;
-  const VcIdsRadiusWork w(e->d_rwork, nq, items);
-  VC_HIP(e, vc_launch_ids_radius_count(w, e->d_rraw, e->d_rroffs, d_ids, e->d_rfound, nq, id_flags, d_offsets, e->stream));
-  if (raw_total > out_cap) {   // T <= raw_total: only then the host has to learn T
-    uint64_t T = 0;
-    VC_HIP(e, hipMemcpyAsync(&T, w.total, 8, hipMemcpyDeviceToHost, e->stream));
-    VC_HIP(e, hipStreamSynchronize(e->stream));
-    if (T > out_cap) return fail(e, VC_ERR_CAPACITY, "radius search: output buffer too small (needed counts are in the offsets)");
-  }
-  if (d_out && raw_total) VC_HIP(e, vc_launch_ids_radius_copy(w, e->d_rraw, e->d_rroffs, d_ids, nq, id_flags, d_offsets, d_out, e->stream));
-  return VC_OK;
-}
-
 extern "C" {
 
 int vc_search_radius_ids_dev(vc_engine* e, const uint32_t* d_ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* d_out,
                              uint64_t out_cap, uint64_t* d_offsets, void* stream) {
   int rc = check_radius_ids_args(e, d_ids, nq, mode, id_flags, d_out, out_cap, d_offsets);
   if (rc) return rc;
-  if ((rc = bind_device(e))) return rc;
-  const StreamCall call(e, caller_stream(e, stream));
-  return radius_ids_run(e, d_ids, nq, radius, mode, id_flags, d_out, out_cap, d_offsets);
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_ids_radius_run(store_view(e, mode), d_ids, nq, radius, id_flags, d_out, out_cap, d_offsets, s, err);
+  });
 }
 
 int vc_search_radius_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* out,
@@ -1241,30 +1180,24 @@ int vc_search_radius_ids(vc_engine* e, const uint32_t* ids, uint32_t nq, uint32_
   int rc = check_radius_ids_args(e, ids, nq, mode, id_flags, out, out_cap, out_offsets);
   if (rc) return rc;
   if ((rc = bind_device(e))) return rc;
-  if ((rc = grow(e, &e->d_rhids, &e->rhids_bytes, (size_t)nq * 4))) return rc;
-  if ((rc = grow(e, &e->d_rhoffs, &e->rhoffs_bytes, ((size_t)nq + 1) * 8))) return rc;
-  if ((rc = grow(e, &e->d_rhout, &e->rhout_bytes, (size_t)out_cap * 8))) return rc;
-  VC_HIP(e, hipMemcpyAsync(e->d_rhids, ids, (size_t)nq * 4, hipMemcpyHostToDevice, e->stream));
-  {
-    const StreamCall call(e, e->stream);
-    rc = radius_ids_run(e, e->d_rhids, nq, radius, mode, id_flags, out_cap ? e->d_rhout : nullptr, out_cap, e->d_rhoffs);
-  }
-  if (rc != VC_OK && rc != VC_ERR_CAPACITY) return rc;
-  // the offsets come home in both cases (VC_ERR_CAPACITY: they are the needed counts); the staged results behind them
-  VC_HIP(e, hipMemcpyAsync(out_offsets, e->d_rhoffs, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, e->stream));
-  VC_HIP(e, hipStreamSynchronize(e->stream));
-  if (rc == VC_OK && out_offsets[nq]) {
-    VC_HIP(e, hipMemcpyAsync(out, e->d_rhout, (size_t)out_offsets[nq] * 8, hipMemcpyDeviceToHost, e->stream));
-    VC_HIP(e, hipStreamSynchronize(e->stream));
-  }
-  return rc;
+  const VcStoreView v = store_view(e, mode);
+  hipStream_t s = e->stream;
+  std::string err;
+  rc = vc_ids_radius_run_host(v, ids, nq, out, out_cap, out_offsets,
+                              [&](const uint32_t* d_ids, uint64_t* d_out, uint64_t* d_offsets) {
+                                return store_call(e, s, [&](hipStream_t cs, std::string* cerr) {
+                                  return vc_ids_radius_run(v, d_ids, nq, radius, id_flags, d_out, out_cap, d_offsets, cs, cerr);
+                                });
+                              },
+                              s, &err);
+  return driver_done(e, rc, err);
 }
 
 }  // extern "C"
 
 // ---- the clustering calls over the radius-graph walk: near-duplicate clusters (vc_cluster.hip), clusters at every radius (vc_levels.hip),
 // greedy leaders (vc_leaders.hip), density clustering at one radius (vc_dbscan.hip) and at every radius (vc_dbscan_levels.hip).  The
-// drivers are theirs and vc_walk.hip's; here are the argument checks, the engine's view and the entry points. ------------------------
+// drivers are theirs and vc_walk.hip's; here are the argument checks and the entry points. ------------------------
 // what: the call's name in the texts.  A call at one radius passes max_radius = 0, one without min_pts 1, one that labels every record
 // n_labelled = 0.
 static int check_walk_args(vc_engine* e, const char* what, uint32_t max_radius, uint32_t min_pts, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {
@@ -1277,36 +1210,6 @@ static int check_walk_args(vc_engine* e, const char* what, uint32_t max_radius, 
   return VC_OK;
 }
 
-// The engine as the walk sees it, inside the caller's StreamCall: everything goes to e->stream, the one device is current throughout.
-static VcWalkView walk_view(vc_engine* e, uint32_t mode) {
-  VcWalkView v;
-  v.n = e->n;
-  v.id_base = e->cfg.id_base;
-  v.W = e->W;
-  v.alloc = [e](int which, size_t bytes) -> void* { return grow(e, &e->d_walk[which], &e->walk_bytes[which], bytes) ? nullptr : e->d_walk[which]; };
-  v.held = [e](int which) { return e->walk_bytes[which]; };
-  v.gather = [e](const uint32_t* d_ids, uint32_t nq, uint64_t* d_q, uint32_t* d_found) -> int {
-    VC_HIP(e, vc_launch_ids_gather(e->d_cols, e->stride, e->W, e->cfg.id_base, e->n, e->cfg.id_base, e->n, d_ids, nq, d_q, d_found, e->stream));
-    return VC_OK;
-  };
-  v.search = [e, mode](const uint64_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_raw, uint64_t cap, uint64_t* d_roffs, uint64_t* raw_total) {
-    return vc_radius_search(live_index(e), mode == VC_MODE_MIH_EXACT, e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, e->n_cu, &e->knobs, d_q, nq, radius,
-                            d_raw, cap, d_roffs, true, &e->radius_work, e->stream, &e->err, raw_total);
-  };
-  return v;
-}
-
-// An entry point after its checks, e->n > 0: the device bound, `run` (a vc_*_run or vc_*_run_host) on stream s inside a StreamCall.
-template <class Run>
-static int walk_call(vc_engine* e, hipStream_t s, const Run& run) {
-  int rc = bind_device(e);
-  if (rc) return rc;
-  const StreamCall call(e, s);
-  std::string err;
-  rc = run(e->stream, &err);
-  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;   // (a closure of the view has left its own text)
-}
-
 extern "C" {
 
 int vc_cluster_radius_dev(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
@@ -1315,8 +1218,8 @@ int vc_cluster_radius_dev(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t
   if (rc) return rc;
   if (stats) *stats = vc_cluster_stats{0, 0};
   if (e->n == 0) return VC_OK;
-  return walk_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
-    return vc_cluster_run(walk_view(e, mode), radius, batch, n_labelled, d_labels, stats, s, err);
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_cluster_run(store_view(e, mode), radius, batch, n_labelled, d_labels, stats, s, err);
   });
 }
 
@@ -1325,8 +1228,8 @@ int vc_cluster_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t bat
   if (rc) return rc;
   if (stats) *stats = vc_cluster_stats{0, 0};
   if (e->n == 0) return VC_OK;
-  return walk_call(e, e->stream, [&](hipStream_t s, std::string* err) {
-    return vc_cluster_run_host(walk_view(e, mode), radius, batch, n_labelled, labels, stats, s, err);
+  return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_cluster_run_host(store_view(e, mode), radius, batch, n_labelled, labels, stats, s, err);
   });
 }
 
@@ -1336,8 +1239,8 @@ int vc_cluster_levels_dev(vc_engine* e, uint32_t max_radius, uint32_t mode, uint
   if (rc) return rc;
   if (stats) *stats = vc_levels_stats{};
   if (e->n == 0) return VC_OK;
-  return walk_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
-    return vc_levels_run(walk_view(e, mode), max_radius, batch, n_labelled, d_labels, stats, s, err);
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_levels_run(store_view(e, mode), max_radius, batch, n_labelled, d_labels, stats, s, err);
   });
 }
 
@@ -1346,8 +1249,8 @@ int vc_cluster_levels(vc_engine* e, uint32_t max_radius, uint32_t mode, uint32_t
   if (rc) return rc;
   if (stats) *stats = vc_levels_stats{};
   if (e->n == 0) return VC_OK;
-  return walk_call(e, e->stream, [&](hipStream_t s, std::string* err) {
-    return vc_levels_run_host(walk_view(e, mode), max_radius, batch, n_labelled, labels, stats, s, err);
+  return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_levels_run_host(store_view(e, mode), max_radius, batch, n_labelled, labels, stats, s, err);
   });
 }
 
@@ -1357,8 +1260,8 @@ int vc_leaders_radius_dev(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t
   if (rc) return rc;
   if (stats) *stats = vc_leader_stats{0, 0, 0};
   if (e->n == 0) return VC_OK;
-  return walk_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
-    return vc_leaders_run(walk_view(e, mode), radius, batch, n_labelled, d_labels, stats, s, err);
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_leaders_run(store_view(e, mode), radius, batch, n_labelled, d_labels, stats, s, err);
   });
 }
 
@@ -1367,8 +1270,8 @@ int vc_leaders_radius(vc_engine* e, uint32_t radius, uint32_t mode, uint32_t bat
   if (rc) return rc;
   if (stats) *stats = vc_leader_stats{0, 0, 0};
   if (e->n == 0) return VC_OK;
-  return walk_call(e, e->stream, [&](hipStream_t s, std::string* err) {
-    return vc_leaders_run_host(walk_view(e, mode), radius, batch, n_labelled, labels, stats, s, err);
+  return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_leaders_run_host(store_view(e, mode), radius, batch, n_labelled, labels, stats, s, err);
   });
 }
 
@@ -1378,8 +1281,8 @@ int vc_dbscan_radius_dev(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_stats{0, 0, 0, 0, 0};
   if (e->n == 0) return VC_OK;
-  return walk_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
-    return vc_dbscan_run(walk_view(e, mode), radius, min_pts, batch, d_labels, d_degrees, stats, s, err);
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_dbscan_run(store_view(e, mode), radius, min_pts, batch, d_labels, d_degrees, stats, s, err);
   });
 }
 
@@ -1389,8 +1292,8 @@ int vc_dbscan_radius(vc_engine* e, uint32_t radius, uint32_t min_pts, uint32_t m
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_stats{0, 0, 0, 0, 0};
   if (e->n == 0) return VC_OK;
-  return walk_call(e, e->stream, [&](hipStream_t s, std::string* err) {
-    return vc_dbscan_run_host(walk_view(e, mode), radius, min_pts, batch, labels, degrees, stats, s, err);
+  return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_dbscan_run_host(store_view(e, mode), radius, min_pts, batch, labels, degrees, stats, s, err);
   });
 }
 
@@ -1400,8 +1303,8 @@ int vc_dbscan_levels_dev(vc_engine* e, uint32_t max_radius, uint32_t min_pts, ui
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_levels_stats{};
   if (e->n == 0) return VC_OK;
-  return walk_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
-    return vc_dbscan_levels_run(walk_view(e, mode), max_radius, min_pts, batch, d_labels, d_core_dist, stats, s, err);
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_dbscan_levels_run(store_view(e, mode), max_radius, min_pts, batch, d_labels, d_core_dist, stats, s, err);
   });
 }
 
@@ -1411,18 +1314,23 @@ int vc_dbscan_levels(vc_engine* e, uint32_t max_radius, uint32_t min_pts, uint32
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_levels_stats{};
   if (e->n == 0) return VC_OK;
-  return walk_call(e, e->stream, [&](hipStream_t s, std::string* err) {
-    return vc_dbscan_levels_run_host(walk_view(e, mode), max_radius, min_pts, batch, labels, core_dist, stats, s, err);
+  return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_dbscan_levels_run_host(store_view(e, mode), max_radius, min_pts, batch, labels, core_dist, stats, s, err);
   });
 }
 
 }  // extern "C"
 
 // ---- label groups summarised (vc_groups.hip) ------------------------------------------------------------------------------------
+// the codes of a window on e->stream, inside the caller's StreamCall
+static VcGroupsFetch groups_fetch(vc_engine* e) {
+  hipStream_t s = e->stream;
+  return [e, s](const uint32_t* d_ids, uint32_t nq, uint64_t* d_rows) { return vc_get_codes_dev(e, d_ids, nq, d_rows, nullptr, (void*)s); };
+}
 static VcGroupsArgs groups_args(vc_engine* e, const uint32_t* d_labels, uint64_t groups_cap, vc_group* d_groups, void* d_centroids, uint32_t* d_rep_labels,
                                 uint32_t* d_group_index) {
   return VcGroupsArgs{e->n, e->cfg.id_base, e->W, e->knobs.group_window, d_labels, groups_cap, d_groups, (uint64_t*)d_centroids, d_rep_labels, d_group_index,
-                      [e](int which, size_t bytes) -> void* { return grow(e, &e->d_grp[which], &e->grp_bytes[which], bytes) ? nullptr : e->d_grp[which]; }};
+                      scratch_alloc(e)};
 }
 
 extern "C" {
@@ -1435,11 +1343,9 @@ int vc_group_summary_dev(vc_engine* e, const uint32_t* d_labels, uint64_t groups
   int rc = bind_device(e);
   if (rc) return rc;
   const StreamCall call(e, caller_stream(e, stream));   // (orders the call behind the handle's previous one, whose buffers it may share)
-  hipStream_t s = e->stream;
-  const VcGroupsFetch fetch = [e, s](const uint32_t* d_ids, uint32_t nq, uint64_t* d_rows) { return vc_get_codes_dev(e, d_ids, nq, d_rows, nullptr, (void*)s); };
   std::string err;
-  rc = vc_groups_run(groups_args(e, d_labels, groups_cap, d_groups, d_centroids, d_rep_labels, d_group_index), fetch, n_groups, s, &err);
-  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;   // (an allocation failure has left its own text)
+  rc = vc_groups_run(groups_args(e, d_labels, groups_cap, d_groups, d_centroids, d_rep_labels, d_group_index), groups_fetch(e), n_groups, e->stream, &err);
+  return driver_done(e, rc, err);
 }
 
 int vc_group_summary(vc_engine* e, const uint32_t* labels, uint64_t groups_cap, vc_group* groups, void* centroids, uint32_t* rep_labels,
@@ -1450,12 +1356,10 @@ int vc_group_summary(vc_engine* e, const uint32_t* labels, uint64_t groups_cap, 
   int rc = bind_device(e);
   if (rc) return rc;
   const StreamCall call(e, e->stream);
-  hipStream_t s = e->stream;
-  const VcGroupsFetch fetch = [e, s](const uint32_t* d_ids, uint32_t nq, uint64_t* d_rows) { return vc_get_codes_dev(e, d_ids, nq, d_rows, nullptr, (void*)s); };
   std::string err;
-  rc = vc_groups_run_host(groups_args(e, nullptr, groups_cap, nullptr, nullptr, nullptr, nullptr), fetch, labels, groups, centroids, rep_labels, group_index,
-                          n_groups, s, &err);
-  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;   // (an allocation failure has left its own text)
+  rc = vc_groups_run_host(groups_args(e, nullptr, groups_cap, nullptr, nullptr, nullptr, nullptr), groups_fetch(e), labels, groups, centroids, rep_labels,
+                          group_index, n_groups, e->stream, &err);
+  return driver_done(e, rc, err);
 }
 
 }  // extern "C"
@@ -1469,19 +1373,12 @@ static int check_kmajority_args(vc_engine* e, uint32_t n_centres, uint32_t max_i
   if (!e || !centres || !assign || n_centres == 0 || (e->n && n_centres > e->n) || max_iters > VC_KMAJ_MAX_ITERS) return VC_ERR_INVALID;
   return VC_OK;
 }
-static std::function<void*(int, size_t)> kmaj_alloc(vc_engine* e) {
-  return [e](int which, size_t bytes) -> void* { return grow(e, &e->d_kmaj[which], &e->kmaj_bytes[which], bytes) ? nullptr : e->d_kmaj[which]; };
-}
 // the records [first, first + count) against the centres on e->stream, inside the caller's StreamCall
 static VcAssignAll assign_range(vc_engine* e, uint32_t n_centres, uint64_t first, uint64_t count) {
   return [e, n_centres, first, count](const uint64_t* d_centres, uint64_t* d_out) -> int {
     VC_HIP(e, vc_launch_assign(e->d_cols, e->stride, e->W, first, count, d_centres, n_centres, d_out, e->n_cu, &e->knobs, e->stream));
     return VC_OK;
   };
-}
-static VcGroupsFetch groups_fetch(vc_engine* e) {
-  hipStream_t s = e->stream;
-  return [e, s](const uint32_t* d_ids, uint32_t nq, uint64_t* d_rows) { return vc_get_codes_dev(e, d_ids, nq, d_rows, nullptr, (void*)s); };
 }
 
 extern "C" {
@@ -1500,8 +1397,8 @@ int vc_assign_nearest(vc_engine* e, const void* centres, uint32_t n_centres, uin
   if ((rc = bind_device(e))) return rc;
   const StreamCall call(e, e->stream);
   std::string err;
-  rc = vc_assign_run_host(kmaj_alloc(e), e->W, centres, n_centres, count, out, assign_range(e, n_centres, first, count), e->stream, &err);
-  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
+  rc = vc_assign_run_host(scratch_alloc(e), e->W, centres, n_centres, count, out, assign_range(e, n_centres, first, count), e->stream, &err);
+  return driver_done(e, rc, err);
 }
 
 int vc_kmajority_dev(vc_engine* e, uint32_t n_centres, uint32_t max_iters, void* d_centres, uint64_t* d_assign, uint32_t* d_labels,
@@ -1513,9 +1410,9 @@ int vc_kmajority_dev(vc_engine* e, uint32_t n_centres, uint32_t max_iters, void*
   if ((rc = bind_device(e))) return rc;
   const StreamCall call(e, caller_stream(e, stream));
   std::string err;
-  rc = vc_kmajority_run(VcKmajArgs{n_centres, max_iters, (uint64_t*)d_centres, d_assign, d_labels, kmaj_alloc(e)}, groups_args(e, nullptr, 0, nullptr, nullptr, nullptr, nullptr),
+  rc = vc_kmajority_run(VcKmajArgs{n_centres, max_iters, (uint64_t*)d_centres, d_assign, d_labels, scratch_alloc(e)}, groups_args(e, nullptr, 0, nullptr, nullptr, nullptr, nullptr),
                         assign_range(e, n_centres, 0, e->n), groups_fetch(e), stats, e->stream, &err);
-  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
+  return driver_done(e, rc, err);
 }
 
 int vc_kmajority(vc_engine* e, uint32_t n_centres, uint32_t max_iters, void* centres, uint64_t* assign, uint32_t* labels, vc_kmajority_stats* stats) {
@@ -1526,9 +1423,9 @@ int vc_kmajority(vc_engine* e, uint32_t n_centres, uint32_t max_iters, void* cen
   if ((rc = bind_device(e))) return rc;
   const StreamCall call(e, e->stream);
   std::string err;
-  rc = vc_kmajority_run_host(VcKmajArgs{n_centres, max_iters, nullptr, nullptr, nullptr, kmaj_alloc(e)}, groups_args(e, nullptr, 0, nullptr, nullptr, nullptr, nullptr),
+  rc = vc_kmajority_run_host(VcKmajArgs{n_centres, max_iters, nullptr, nullptr, nullptr, scratch_alloc(e)}, groups_args(e, nullptr, 0, nullptr, nullptr, nullptr, nullptr),
                              assign_range(e, n_centres, 0, e->n), groups_fetch(e), centres, assign, labels, stats, e->stream, &err);
-  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
+  return driver_done(e, rc, err);
 }
 
 }  // extern "C"
@@ -1538,16 +1435,13 @@ static int check_seed_args(vc_engine* e, uint32_t n_centres, uint32_t method, co
   if (!e || !centres || n_centres == 0 || (e->n && n_centres > e->n) || (method != VC_SEED_FARTHEST && method != VC_SEED_WEIGHTED)) return VC_ERR_INVALID;
   return VC_OK;
 }
-static std::function<void*(int, size_t)> seed_alloc(vc_engine* e) {
-  return [e](int which, size_t bytes) -> void* { return grow(e, &e->d_seed[which], &e->seed_bytes[which], bytes) ? nullptr : e->d_seed[which]; };
-}
 // the whole call on e->stream, inside the caller's StreamCall
 static int seed_run(vc_engine* e, uint32_t n_centres, uint32_t method, uint64_t seed, uint64_t* d_centres, uint64_t* d_picks, uint64_t* d_assign,
                     vc_seed_stats* stats) {
   std::string err;
-  const int rc = vc_seed_run(VcSeedArgs{e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, n_centres, method, seed, d_centres, d_picks, d_assign, seed_alloc(e)},
+  const int rc = vc_seed_run(VcSeedArgs{e->d_cols, e->stride, e->n, e->W, e->cfg.id_base, n_centres, method, seed, d_centres, d_picks, d_assign, scratch_alloc(e)},
                              stats, e->stream, &err);
-  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
+  return driver_done(e, rc, err);
 }
 
 extern "C" {
@@ -1572,12 +1466,12 @@ int vc_seed_centres(vc_engine* e, uint32_t n_centres, uint32_t method, uint64_t 
   if ((rc = bind_device(e))) return rc;
   const StreamCall call(e, e->stream);
   std::string err;
-  rc = vc_seed_run_host(VcSeedHostArgs{e->n, e->W, n_centres, centres, picks, assign, stats, seed_alloc(e)},
+  rc = vc_seed_run_host(VcSeedHostArgs{e->n, e->W, n_centres, centres, picks, assign, stats, scratch_alloc(e)},
                         [&](uint64_t* d_centres, uint64_t* d_picks, uint64_t* d_assign, vc_seed_stats* st) {
                           return seed_run(e, n_centres, method, seed, d_centres, d_picks, d_assign, st);
                         },
                         e->stream, &err);
-  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
+  return driver_done(e, rc, err);
 }
 
 }  // extern "C"
@@ -1592,20 +1486,15 @@ static int check_distinct_args(vc_engine* e, const void* q, uint32_t nq, uint32_
   if (mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first (n_tables=%u)", e->m);
   return VC_OK;
 }
-static std::function<void*(int, size_t)> distinct_alloc(vc_engine* e) {
-  return [e](int which, size_t bytes) -> void* { return grow(e, &e->d_distinct[which], &e->distinct_bytes[which], bytes) ? nullptr : e->d_distinct[which]; };
-}
 // the whole call on e->stream, inside the caller's StreamCall
 static int distinct_run(vc_engine* e, const uint64_t* d_queries, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* d_labels, uint32_t k_first,
                         uint64_t* d_out, uint32_t* d_row_labels, uint32_t* d_counts, vc_distinct_stats* stats) {
   std::string err;
   const int rc = vc_distinct_run(VcDistinctArgs{e->n, e->cfg.id_base, e->W, d_queries, nq, k, k_first, d_labels, d_out, d_row_labels, d_counts,
-                                                e->knobs.distinct_scratch, mode == VC_MODE_MIH_EXACT, distinct_alloc(e)},
-                                 [&](const uint64_t* d_q, uint32_t n, uint32_t kp, uint64_t* d_rows, uint32_t* d_cnt) {
-                                   return knn_dev_run(e, d_q, n, kp, mode, d_rows, d_cnt, nullptr);
-                                 },
+                                                e->knobs.distinct_scratch, mode == VC_MODE_MIH_EXACT, scratch_alloc(e)},
+                                 store_view(e, mode).knn,
                                  stats, e->stream, &err);
-  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
+  return driver_done(e, rc, err);
 }
 
 extern "C" {
@@ -1627,12 +1516,12 @@ int vc_search_knn_distinct(vc_engine* e, const void* queries, uint32_t nq, uint3
   if ((rc = bind_device(e))) return rc;
   const StreamCall call(e, e->stream);
   std::string err;
-  rc = vc_distinct_run_host(VcDistinctHostArgs{e->n, e->W, nq, k, order, queries, labels, out, row_labels, counts, stats, distinct_alloc(e)},
+  rc = vc_distinct_run_host(VcDistinctHostArgs{e->n, e->W, nq, k, order, queries, labels, out, row_labels, counts, stats, scratch_alloc(e)},
                             [&](const uint64_t* d_q, const uint32_t* d_labels, uint64_t* d_out, uint32_t* d_rl, uint32_t* d_cnt, vc_distinct_stats* st) {
                               return distinct_run(e, d_q, nq, k, mode, d_labels, k_first, d_out, d_rl, d_cnt, st);
                             },
                             e->stream, &err);
-  return rc && !err.empty() ? fail(e, rc, "%s", err.c_str()) : rc;
+  return driver_done(e, rc, err);
 }
 
 }  // extern "C"

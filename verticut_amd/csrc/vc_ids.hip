@@ -143,3 +143,63 @@ void vc_ids_strip_host(const uint32_t* ids, const uint32_t* found, const uint64_
     if (stats) stats[i].n_results = w;
   }
 }
+
+// ---- k-NN by id over a VcStoreView: the one driver of vc_search_knn_ids* and vc_sharded_search_knn_ids* ----------------------------
+#define VC_IDS_HIP(call) VC_HIP_OR_FAIL("k-NN by id", call)
+
+int vc_ids_knn_reserve(const VcStoreView& v, uint32_t nq, uint32_t kp, VcIdsKnnBufs* b) {
+  b->d_q = (uint64_t*)v.alloc(VC_KIDS_Q, (size_t)nq * v.W * 8);
+  b->d_found = (uint32_t*)v.alloc(VC_KIDS_FOUND, (size_t)nq * 4);
+  b->d_rows = (uint64_t*)v.alloc(VC_KIDS_ROWS, (size_t)nq * kp * 8);
+  b->d_cnt = (uint32_t*)v.alloc(VC_KIDS_CNT, (size_t)nq * 4);
+  return b->d_q && b->d_found && b->d_rows && b->d_cnt ? VC_OK : VC_ERR_NOMEM;
+}
+
+int vc_ids_knn_run(const VcStoreView& v, const VcIdsKnnBufs& b, const uint32_t* d_ids, uint32_t nq, uint32_t kp, uint32_t k, uint64_t* d_out, uint32_t* d_counts,
+                   vc_query_stats* d_stats, hipStream_t s, std::string* err) {
+  int rc;
+  if ((rc = v.gather(d_ids, nq, b.d_q, b.d_found))) return rc;
+  if ((rc = v.knn(b.d_q, nq, kp, b.d_rows, b.d_cnt, d_stats))) return rc;
+  VC_IDS_HIP(vc_launch_ids_strip(d_ids, b.d_found, b.d_rows, b.d_cnt, nq, kp, k, d_out, d_counts, d_stats, s));
+  return VC_OK;
+}
+
+int vc_ids_knn_run_host(const VcStoreView& v, const VcIdsKnnHostArgs& a,
+                        const std::function<int(const VcIdsKnnBufs& b, const uint32_t* d_ids, uint64_t* d_out, uint32_t* d_counts, vc_query_stats* d_stats)>& run,
+                        const std::function<int(const uint64_t* codes, uint64_t* rows, uint32_t* counts)>& host_knn, hipStream_t s, std::string* err) {
+  const uint32_t nq = a.nq, k = a.k;
+  const size_t st_bytes = (size_t)nq * sizeof(vc_query_stats);
+  VcIdsKnnBufs b;
+  int rc = vc_ids_knn_reserve(v, nq, a.kp, &b);
+  if (rc) return rc;
+  uint32_t* d_hids = (uint32_t*)v.alloc(VC_KIDS_HIDS, (size_t)nq * 4);
+  uint64_t* d_hrows = (uint64_t*)v.alloc(VC_KIDS_HROWS, (size_t)nq * k * 8);
+  uint32_t* d_hcnt = (uint32_t*)v.alloc(VC_KIDS_HCNT, (size_t)nq * 4);
+  vc_query_stats* d_hstats = a.stats ? (vc_query_stats*)v.alloc(VC_KIDS_HSTATS, st_bytes) : nullptr;
+  if (!d_hids || !d_hrows || !d_hcnt || (a.stats && !d_hstats)) return VC_ERR_NOMEM;
+  VC_IDS_HIP(hipMemcpyAsync(d_hids, a.ids, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+  if ((rc = run(b, d_hids, d_hrows, d_hcnt, d_hstats))) return rc;
+  std::vector<uint32_t> cnt(nq);
+  VC_IDS_HIP(hipMemcpyAsync(a.out, d_hrows, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
+  VC_IDS_HIP(hipMemcpyAsync(cnt.data(), d_hcnt, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+  if (a.stats) VC_IDS_HIP(hipMemcpyAsync(a.stats, d_hstats, st_bytes, hipMemcpyDeviceToHost, s));
+  VC_IDS_HIP(hipStreamSynchronize(s));
+  if (a.linear && std::find(cnt.begin(), cnt.end(), 0xFFFFFFFFu) != cnt.end()) {
+    // a ring overflowed and the device-side recovery gave up: the batch is answered again by the handle's host-form k-NN, whose
+    // host-driven recovery always ends, on the gathered codes, and stripped here by the kernel's rule
+    std::vector<uint64_t> codes((size_t)nq * v.W), rows((size_t)nq * a.kp);
+    std::vector<uint32_t> found(nq), rcnt(nq);
+    VC_IDS_HIP(hipMemcpyAsync(codes.data(), b.d_q, codes.size() * 8, hipMemcpyDeviceToHost, s));
+    VC_IDS_HIP(hipMemcpyAsync(found.data(), b.d_found, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    VC_IDS_HIP(hipStreamSynchronize(s));
+    if ((rc = host_knn(codes.data(), rows.data(), rcnt.data()))) return rc;
+    vc_ids_strip_host(a.ids, found.data(), rows.data(), rcnt.data(), nq, a.kp, k, a.out, cnt.data(), a.stats);
+  }
+  for (uint32_t i = 0; i < nq; ++i) {
+    if (!a.linear) cnt[i] = std::min(cnt[i], k);   // (as vc_sharded_search_knn: a flagged MIH row has k entries)
+    if (a.order == VC_ORDER_FARTHEST_FIRST) std::reverse(a.out + (size_t)i * k, a.out + (size_t)i * k + cnt[i]);
+    if (a.counts) a.counts[i] = cnt[i];
+    if (a.stats) a.stats[i].n_results = cnt[i];
+  }
+  return VC_OK;
+}

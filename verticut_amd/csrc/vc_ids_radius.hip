@@ -183,3 +183,58 @@ hipError_t vc_launch_ids_radius_copy(const VcIdsRadiusWork& w, const uint64_t* d
                      w.chunk_base, d_offsets, d_out);
   return hipGetLastError();
 }
+
+// ---- radius search by id over a VcStoreView: the one driver of vc_search_radius_ids* and vc_sharded_search_radius_ids* ------------
+#define VC_RIDS_HIP(call) VC_HIP_OR_FAIL("radius search by id", call)
+
+int vc_ids_radius_run(const VcStoreView& v, const uint32_t* d_ids, uint32_t nq, uint32_t radius, uint32_t id_flags, uint64_t* d_out, uint64_t out_cap,
+                      uint64_t* d_offsets, hipStream_t s, std::string* err) {
+  uint64_t* d_q = (uint64_t*)v.alloc(VC_RIDS_Q, (size_t)nq * v.W * 8);
+  uint32_t* d_found = (uint32_t*)v.alloc(VC_RIDS_FOUND, (size_t)nq * 4);
+  uint64_t* d_roffs = (uint64_t*)v.alloc(VC_RIDS_ROFFS, ((size_t)nq + 1) * 8);
+  uint64_t* d_raw = (uint64_t*)v.alloc(VC_RIDS_RAW, VC_RAW_FIRST_BYTES);
+  if (!d_q || !d_found || !d_roffs || !d_raw) return VC_ERR_NOMEM;
+  int rc;
+  if ((rc = v.gather(d_ids, nq, d_q, d_found))) return rc;
+  uint64_t raw_total;
+  if ((rc = vc_search_raw(v, VC_RIDS_RAW, d_q, nq, radius, &d_raw, d_roffs, &raw_total))) return rc;
+  const uint64_t items = vc_ids_radius_items(nq, raw_total);
+  if (items > 0xFFFFFFFFull) {
+    *err = "radius search by id: more results than one compaction can place";
+    return VC_ERR_CAPACITY;
+  }
+  void* d_work = v.alloc(VC_RIDS_WORK, VcIdsRadiusWork::bytes(nq, items));
+  if (!d_work) return VC_ERR_NOMEM;
+  const VcIdsRadiusWork w(d_work, nq, items);
+  VC_RIDS_HIP(vc_launch_ids_radius_count(w, d_raw, d_roffs, d_ids, d_found, nq, id_flags, d_offsets, s));
+  if (raw_total > out_cap) {   // T <= raw_total: only then the host has to learn T
+    uint64_t T = 0;
+    VC_RIDS_HIP(hipMemcpyAsync(&T, w.total, 8, hipMemcpyDeviceToHost, s));
+    VC_RIDS_HIP(hipStreamSynchronize(s));
+    if (T > out_cap) {
+      *err = "radius search: output buffer too small (needed counts are in the offsets)";
+      return VC_ERR_CAPACITY;
+    }
+  }
+  if (d_out && raw_total) VC_RIDS_HIP(vc_launch_ids_radius_copy(w, d_raw, d_roffs, d_ids, nq, id_flags, d_offsets, d_out, s));
+  return VC_OK;
+}
+
+int vc_ids_radius_run_host(const VcStoreView& v, const uint32_t* ids, uint32_t nq, uint64_t* out, uint64_t out_cap, uint64_t* out_offsets,
+                           const std::function<int(const uint32_t* d_ids, uint64_t* d_out, uint64_t* d_offsets)>& run, hipStream_t s, std::string* err) {
+  uint32_t* d_ids = (uint32_t*)v.alloc(VC_RIDS_HIDS, (size_t)nq * 4);
+  uint64_t* d_offsets = (uint64_t*)v.alloc(VC_RIDS_HOFFS, ((size_t)nq + 1) * 8);
+  uint64_t* d_out = (uint64_t*)v.alloc(VC_RIDS_HOUT, (size_t)out_cap * 8);
+  if (!d_ids || !d_offsets || (out_cap && !d_out)) return VC_ERR_NOMEM;
+  VC_RIDS_HIP(hipMemcpyAsync(d_ids, ids, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+  const int rc = run(d_ids, out_cap ? d_out : nullptr, d_offsets);
+  if (rc != VC_OK && rc != VC_ERR_CAPACITY) return rc;
+  // the offsets come home in both cases (VC_ERR_CAPACITY: they are the needed counts); the staged results behind them
+  VC_RIDS_HIP(hipMemcpyAsync(out_offsets, d_offsets, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, s));
+  VC_RIDS_HIP(hipStreamSynchronize(s));
+  if (rc == VC_OK && out_offsets[nq]) {
+    VC_RIDS_HIP(hipMemcpyAsync(out, d_out, (size_t)out_offsets[nq] * 8, hipMemcpyDeviceToHost, s));
+    VC_RIDS_HIP(hipStreamSynchronize(s));
+  }
+  return rc;
+}

@@ -154,6 +154,73 @@ hipError_t vc_radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], uint64_t n,
 // n_lists x [nq][k] sorted lists -> merged top-k
 hipError_t vc_launch_select_lists(const uint64_t* d_lists, uint32_t n_lists, uint32_t nq, uint32_t k, uint64_t* d_out,
                                   uint32_t* d_out_count, hipStream_t s);
+// ---- a handle as the drivers below see it: one table of grow-only scratch and a view of its store ------------------
+// Grow-only device scratch: the pointer and how many bytes are behind it.  It has no destructor on purpose: hipFree acts on
+// the CURRENT device, so the owner binds the buffer's device and then releases it.
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  hipError_t regrow(size_t need) {   // at least `need` bytes (rounded up to 256), on the current device; the contents are lost when it grows
+    if (need <= bytes) return hipSuccess;
+    hipError_t r = p ? hipFree(p) : hipSuccess;
+    p = nullptr;
+    bytes = 0;
+    if (r != hipSuccess) return r;
+    need = (need + 255) & ~(size_t)255;
+    if ((r = hipMalloc(&p, need)) != hipSuccess) { p = nullptr; return r; }
+    bytes = need;
+    return hipSuccess;
+  }
+  void release() { (void)hipFree(p); p = nullptr; bytes = 0; }
+  template <class T> T* as() const { return (T*)p; }
+};
+// The scratch of the drivers that serve both handle kinds, family after family, one buffer per purpose.  An engine holds the table as
+// it is, a sharded store on its root device.  A driver writes every word it reads, so what an earlier call left there never matters.
+enum VcScratch {
+  // the clustering calls over the radius-graph walk (vc_walk.hip).  The walk's own: a batch's ids, gathered queries, found words, the
+  // nq + 1 offsets and the raw results of the search.  The consumers': the statistics; one word per record (dbscan's degrees / core
+  // distances when the caller passes none); leaders' state words of a batch; the host forms' staged labels.  The five calls share them.
+  VC_WALK_IDS, VC_WALK_Q, VC_WALK_FOUND, VC_WALK_ROFFS, VC_WALK_RAW, VC_WALK_STAT, VC_WALK_RECORD, VC_WALK_STATE, VC_WALK_HLAB,
+  VC_GROUPS_SCRATCH, VC_GROUPS_WORK, VC_GROUPS_STAGE,         // vc_groups.hip: sort / numbering arrays; rows + big-group tables; the host form's staging
+  VC_KMAJ_WORK, VC_KMAJ_STAGE,                                // vc_assign.hip: the round driver's arrays; the host forms' staging
+  VC_SEED_WORK, VC_SEED_STAGE,                                // vc_seed.hip: slots, statistics, partials, best; the host forms' staging
+  VC_DISTINCT_WORK, VC_DISTINCT_ROWS, VC_DISTINCT_STAGE,      // vc_distinct.hip: flags, maps, retry queries, counters; the k' rows; the host forms' staging
+  // k-NN by id (vc_ids.hip): gathered queries, found words, the k' rows and counts of the search underneath; the host form's staged
+  // ids, rows, counts and statistics
+  VC_KIDS_Q, VC_KIDS_FOUND, VC_KIDS_ROWS, VC_KIDS_CNT, VC_KIDS_HIDS, VC_KIDS_HROWS, VC_KIDS_HCNT, VC_KIDS_HSTATS,
+  // radius search by id (vc_ids_radius.hip): gathered queries, found words, the uncompacted results and offsets of the search underneath,
+  // the compaction's counts (VcIdsRadiusWork); the host form's staged ids, results and offsets
+  VC_RIDS_Q, VC_RIDS_FOUND, VC_RIDS_RAW, VC_RIDS_ROFFS, VC_RIDS_WORK, VC_RIDS_HIDS, VC_RIDS_HOUT, VC_RIDS_HOFFS,
+  VC_SCRATCH_BUFS
+};
+// buffer `which` of the handle's table, at least `bytes` large, on the current device; null when it cannot be had (the handle keeps the text)
+typedef std::function<void*(int which, size_t bytes)> VcScratchAlloc;
+// What a driver needs of a handle for one call (the search mode and the call's stream are the closures' own).  gather, search and knn
+// enqueue on that stream and return a VC_* code with the device of the handle's buffers current; none waits, but for search returning
+// VC_ERR_CAPACITY (*raw_total entries do not fit cap): then everything enqueued has been waited for, so that the raw buffer may be
+// regrown.  A closure that fails has left its text in the handle.
+// the handle's unchanged k-NN search of nq queries [nq][W] at kp into d_rows [nq][kp], d_cnt [nq] and d_stats (nullable)
+typedef std::function<int(const uint64_t* d_q, uint32_t nq, uint32_t kp, uint64_t* d_rows, uint32_t* d_cnt, vc_query_stats* d_stats)> VcKnnSearch;
+struct VcStoreView {
+  uint64_t n;               // resident records
+  uint32_t id_base, W;
+  VcScratchAlloc alloc;
+  std::function<size_t(int which)> held;   // the bytes behind buffer `which` now: an earlier call may have left more than this one asks for
+  std::function<int(const uint32_t* d_ids, uint32_t nq, uint64_t* d_q, uint32_t* d_found)> gather;   // ids -> rows [nq][W] + found words (vc_launch_ids_gather's fill rule)
+  std::function<int(const uint64_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_raw, uint64_t cap, uint64_t* d_roffs, uint64_t* raw_total)> search;
+  VcKnnSearch knn;
+};
+// v.search into buffer raw_buf of the table (*d_raw, holding at least the initial 64 Ki entries), at the capacity the handle really
+// holds; on VC_ERR_CAPACITY repeated once with the buffer grown to the total it reported.  *raw_total: the entries found.
+#define VC_RAW_FIRST_BYTES ((size_t)8 << 16)
+int vc_search_raw(const VcStoreView& v, int raw_buf, const uint64_t* d_q, uint32_t nq, uint32_t radius, uint64_t** d_raw, uint64_t* d_roffs, uint64_t* raw_total);
+// the text and code of a failed HIP call inside a driver: "<who>: <call>: <error>"
+int vc_hip_fail(std::string* err, const char* who, hipError_t r, const char* what);
+#define VC_HIP_OR_FAIL(who, call)                                      \
+  do {                                                                 \
+    hipError_t _r = (call);                                            \
+    if (_r != hipSuccess) return vc_hip_fail(err, who, _r, #call);     \
+  } while (0)
 // ---- vc_ids.hip: queries named by id ------------------------------------------------------------------------------
 // ids (global) -> d_q [nq][W] + d_found [nq] (nullable): an id outside [id_base, id_base + n) gives a zero row and found = 0.
 // fill_n != 0: an id outside [fill_base, fill_base + fill_n) (the whole store's resident range) gets local record 0's code as its
@@ -172,6 +239,33 @@ hipError_t vc_launch_ids_merge(const uint64_t* d_slots, uint64_t slot_words, uin
 // the strip kernel's rule on host memory (counts non-null)
 void vc_ids_strip_host(const uint32_t* ids, const uint32_t* found, const uint64_t* rows, const uint32_t* cnt, uint32_t nq, uint32_t kp, uint32_t k,
                        uint64_t* out, uint32_t* counts, vc_query_stats* stats);
+// k-NN by id of either handle kind (vc_search_knn_ids*, vc_sharded_search_knn_ids*) in two steps, so that a handle can keep the
+// allocations out of what it times: the VC_KIDS_* buffers of nq queries at kp = vc_ids_kp reserved, then gather, v.knn at kp and
+// strip on s, nothing waited for
+inline uint32_t vc_ids_kp(uint32_t k, uint32_t id_flags) { return k + ((id_flags & VC_IDS_EXCLUDE_SELF) ? 1u : 0u); }
+struct VcIdsKnnBufs {
+  uint64_t* d_q;
+  uint32_t* d_found;
+  uint64_t* d_rows;
+  uint32_t* d_cnt;
+};
+int vc_ids_knn_reserve(const VcStoreView& v, uint32_t nq, uint32_t kp, VcIdsKnnBufs* b);
+int vc_ids_knn_run(const VcStoreView& v, const VcIdsKnnBufs& b, const uint32_t* d_ids, uint32_t nq, uint32_t kp, uint32_t k, uint64_t* d_out, uint32_t* d_counts,
+                   vc_query_stats* d_stats, hipStream_t s, std::string* err);
+// either handle's host form: ids staged, `run` (the handle's device step on s) into staged outputs, which come home; waits for them.
+// A flagged row of a linear search -- the device-side recovery gave up -- has the batch answered again by host_knn (the handle's
+// host-form k-NN of the gathered codes at kp, ascending) and stripped by the kernel's rule.  counts, stats nullable
+struct VcIdsKnnHostArgs {
+  const uint32_t* ids;
+  uint32_t nq, kp, k, order;
+  bool linear;              // the mode is VC_MODE_LINEAR
+  uint64_t* out;
+  uint32_t* counts;
+  vc_query_stats* stats;
+};
+int vc_ids_knn_run_host(const VcStoreView& v, const VcIdsKnnHostArgs& a,
+                        const std::function<int(const VcIdsKnnBufs& b, const uint32_t* d_ids, uint64_t* d_out, uint32_t* d_counts, vc_query_stats* d_stats)>& run,
+                        const std::function<int(const uint64_t* codes, uint64_t* rows, uint32_t* counts)>& host_knn, hipStream_t s, std::string* err);
 // ---- vc_ids_radius.hip: radius search by id.  The raw result of the radius search underneath (d_raw ascending per query, d_roffs its nq + 1 offsets) is
 // compacted segment by segment -- an entry stays when its query's id is resident (d_found) and id_flags (VC_IDS_EXCLUDE_SELF,
 // VC_IDS_ONLY_GREATER) keep it.  The work is cut into (query, chunk) items of VC_IDS_RCHUNK entries; w.items bounds their number.
@@ -197,28 +291,20 @@ hipError_t vc_launch_ids_radius_count(const VcIdsRadiusWork& w, const uint64_t* 
 // the kept entries, in order, to d_out[d_offsets[q] ..): the caller has made sure that *w.total entries fit
 hipError_t vc_launch_ids_radius_copy(const VcIdsRadiusWork& w, const uint64_t* d_raw, const uint64_t* d_roffs, const uint32_t* d_ids, uint32_t nq,
                                      uint32_t id_flags, const uint64_t* d_offsets, uint64_t* d_out, hipStream_t s);
+// Radius search by id of either handle kind (vc_search_radius_ids*, vc_sharded_search_radius_ids*), the whole call on s with the
+// device of the handle's buffers current: gather, vc_search_raw into VC_RIDS_RAW, count / offsets, and, once T is known to fit (one
+// wait, only when the raw total exceeds out_cap), the copy.  VC_ERR_CAPACITY: d_offsets holds the needed counts.
+int vc_ids_radius_run(const VcStoreView& v, const uint32_t* d_ids, uint32_t nq, uint32_t radius, uint32_t id_flags, uint64_t* d_out, uint64_t out_cap,
+                      uint64_t* d_offsets, hipStream_t s, std::string* err);
+// either handle's host form: ids staged, `run` (the handle's device step on s) into staged outputs; the offsets come home also on
+// VC_ERR_CAPACITY, the results behind them; waits for both
+int vc_ids_radius_run_host(const VcStoreView& v, const uint32_t* ids, uint32_t nq, uint64_t* out, uint64_t out_cap, uint64_t* out_offsets,
+                           const std::function<int(const uint32_t* d_ids, uint64_t* d_out, uint64_t* d_offsets)>& run, hipStream_t s, std::string* err);
 // ---- vc_walk.hip: the radius-graph walk under the five clustering calls (vc_cluster_radius*, vc_cluster_levels*, vc_leaders_radius*,
 // vc_dbscan_radius*, vc_dbscan_levels*) of both handle kinds.  Every record from a first position on goes through the handle's radius
 // search, batch by batch in ascending id order, and one consume step per batch folds the RAW result into the caller's arrays.
 #define VC_CLUSTER_BATCH 4096u   // ids per radius search underneath when the caller passes batch = 0
 inline uint32_t vc_walk_batch(uint32_t batch) { return batch ? batch : VC_CLUSTER_BATCH; }
-// The handle's grow-only buffers of these calls (alloc as VcGroupsArgs::alloc).  The walk's own: a batch's ids, gathered queries, found
-// words, the nq + 1 offsets and the raw results of the search.  The consumers': the statistics; one word per record (dbscan's degrees /
-// core distances when the caller passes none); leaders' state words of a batch; the host forms' staged labels.  The calls share them:
-// each writes every word it reads.
-enum { VC_WALK_IDS, VC_WALK_Q, VC_WALK_FOUND, VC_WALK_ROFFS, VC_WALK_RAW, VC_WALK_STAT, VC_WALK_RECORD, VC_WALK_STATE, VC_WALK_HLAB, VC_WALK_BUFS };
-// What the walk needs of a handle for one call (the search mode and the call's stream are the closures' own).  gather and search
-// enqueue on that stream and return a VC_* code with the device of the handle's buffers current; neither waits, but for search
-// returning VC_ERR_CAPACITY (*raw_total entries do not fit cap): then everything enqueued has been waited for, so that the raw buffer
-// may be regrown.  A closure that fails has left its text in the handle.
-struct VcWalkView {
-  uint64_t n;               // resident records
-  uint32_t id_base, W;
-  std::function<void*(int which, size_t bytes)> alloc;
-  std::function<size_t(int which)> held;   // the bytes behind buffer `which` now: an earlier call may have left more than this one asks for
-  std::function<int(const uint32_t* d_ids, uint32_t nq, uint64_t* d_q, uint32_t* d_found)> gather;   // ids -> rows [nq][W] + found words
-  std::function<int(const uint64_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_raw, uint64_t cap, uint64_t* d_roffs, uint64_t* raw_total)> search;
-};
 struct VcWalkBatch {        // the raw result (ascending per query) of the queries first_id .. first_id + nq - 1, as it lies in the walk's buffers
   const uint64_t* d_raw;
   const uint64_t* d_roffs;  // nq + 1 offsets, d_roffs[nq] = raw_total
@@ -227,18 +313,13 @@ struct VcWalkBatch {        // the raw result (ascending per query) of the queri
   uint32_t first_id;
 };
 // The positions first_pos .. v.n - 1 in batches of vc_walk_batch(batch): per batch the ids filled on the device, the gather, the search
-// at `radius` -- repeated once with the raw buffer grown to the total it reported -- and consume (a VC_* code; it may wait).  The walk
-// itself waits for nothing.  err: the text of a failure of the walk's own; a closure's is in the handle.
-int vc_walk_run(const VcWalkView& v, uint64_t first_pos, uint32_t batch, uint32_t radius, const std::function<int(const VcWalkBatch&)>& consume, hipStream_t s,
+// at `radius` (vc_search_raw into VC_WALK_RAW) and consume (a VC_* code; it may wait).  The walk itself waits for nothing.  err: the
+// text of a failure of the walk's own; a closure's is in the handle.
+int vc_walk_run(const VcStoreView& v, uint64_t first_pos, uint32_t batch, uint32_t radius, const std::function<int(const VcWalkBatch&)>& consume, hipStream_t s,
                 std::string* err);
 // the host forms' labels staged in VC_WALK_HLAB (*d_labels): `planes` planes of v.n words, of each the first n_labelled copied in
-int vc_walk_stage_labels(const VcWalkView& v, const uint32_t* labels, size_t planes, uint64_t n_labelled, uint32_t** d_labels, hipStream_t s, std::string* err);
-int vc_walk_fail(std::string* err, hipError_t r, const char* what);   // the text and code of a failed HIP call
-#define VC_WALK_HIP(call)                                      \
-  do {                                                         \
-    hipError_t _r = (call);                                    \
-    if (_r != hipSuccess) return vc_walk_fail(err, _r, #call); \
-  } while (0)
+int vc_walk_stage_labels(const VcStoreView& v, const uint32_t* labels, size_t planes, uint64_t n_labelled, uint32_t** d_labels, hipStream_t s, std::string* err);
+#define VC_WALK_HIP(call) VC_HIP_OR_FAIL("radius walk", call)
 // The five consumers below come in two forms, both the whole call on s with the device of the handle's buffers current, n > 0:
 // vc_*_run on device pointers -- statistics zeroed, labels initialised, the walk, the passes after the last batch, then the one wait
 // for the statistics (stats: host memory, nullable) -- and vc_*_run_host on host pointers: labels staged, run, copied home, waited for.
@@ -253,9 +334,9 @@ hipError_t vc_launch_cluster_union(const uint64_t* d_raw, const uint64_t* d_roff
 // d_labels[i] = the root of record i (the smallest id of its component), in place; *d_n_clusters += the roots
 hipError_t vc_launch_cluster_flatten(uint32_t* d_labels, uint64_t n, uint32_t id_base, uint64_t* d_n_clusters, hipStream_t s);
 // the records from n_labelled on walked and united, one flatten over all n; VC_WALK_STAT: 2 x uint64 (pairs, clusters)
-int vc_cluster_run(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_cluster_stats* stats, hipStream_t s,
+int vc_cluster_run(const VcStoreView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_cluster_stats* stats, hipStream_t s,
                    std::string* err);
-int vc_cluster_run_host(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats, hipStream_t s,
+int vc_cluster_run_host(const VcStoreView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_cluster_stats* stats, hipStream_t s,
                         std::string* err);
 // ---- vc_leaders.hip: greedy leader dedup (vc_leaders_radius*).  d_labels [n]: slot i holds the global id of the smallest-id leader
 // within the radius of record id_base + i, its own id for a leader; entries below the batch are final and only read.
@@ -272,9 +353,9 @@ hipError_t vc_leaders_decide_batch(const uint64_t* d_raw, const uint64_t* d_roff
 hipError_t vc_launch_leaders_count(const uint32_t* d_labels, uint64_t n, uint32_t id_base, uint64_t* d_n_leaders, hipStream_t s);
 // the records from n_labelled on walked in batches of at most VC_LEADER_BATCH_MAX and decided (a wait per group of rounds), one count
 // over all n; the entries below n_labelled are only read, and the host form does not copy them back
-int vc_leaders_run(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_leader_stats* stats, hipStream_t s,
+int vc_leaders_run(const VcStoreView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_leader_stats* stats, hipStream_t s,
                    std::string* err);
-int vc_leaders_run_host(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats, hipStream_t s,
+int vc_leaders_run_host(const VcStoreView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats, hipStream_t s,
                         std::string* err);
 // ---- vc_dbscan.hip: density clustering (vc_dbscan_radius*).  d_labels [n] starts as the own ids (vc_launch_cluster_init): a core's
 // slot is the forest of vc_forest.hpp over the cores, a non-core's slot its smallest core neighbour seen so far, its own id for
@@ -290,9 +371,9 @@ hipError_t vc_launch_dbscan_edges(const uint64_t* d_raw, const uint64_t* d_roffs
 hipError_t vc_launch_dbscan_finish(uint32_t* d_labels, const uint32_t* d_degrees, uint64_t n, uint32_t id_base, uint32_t min_pts, uint64_t* d_counts,
                                    hipStream_t s);
 // every record walked from position 0, one finish pass; d_degrees null: the handle's own (VC_WALK_RECORD); degrees (host) nullable
-int vc_dbscan_run(const VcWalkView& v, uint32_t radius, uint32_t min_pts, uint32_t batch, uint32_t* d_labels, uint32_t* d_degrees, vc_dbscan_stats* stats,
+int vc_dbscan_run(const VcStoreView& v, uint32_t radius, uint32_t min_pts, uint32_t batch, uint32_t* d_labels, uint32_t* d_degrees, vc_dbscan_stats* stats,
                   hipStream_t s, std::string* err);
-int vc_dbscan_run_host(const VcWalkView& v, uint32_t radius, uint32_t min_pts, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats,
+int vc_dbscan_run_host(const VcStoreView& v, uint32_t radius, uint32_t min_pts, uint32_t batch, uint32_t* labels, uint32_t* degrees, vc_dbscan_stats* stats,
                        hipStream_t s, std::string* err);
 // ---- vc_levels.hip: single-linkage clusters at every radius 0 .. max_radius in one walk (vc_cluster_levels*).  d_labels is level-major,
 // (max_radius + 1) x n: level r at d_labels + r * n is a forest of vc_forest.hpp in place, as vc_cluster.hip's.  Nothing here waits.
@@ -306,9 +387,9 @@ hipError_t vc_launch_levels_cascade(uint32_t* d_labels, uint64_t n, uint32_t id_
 // d_labels[r * n + i] = the root of record i at level r, in place, every level in one launch; d_n_clusters[r] += the roots of level r
 hipError_t vc_launch_levels_flatten(uint32_t* d_labels, uint64_t n, uint32_t id_base, uint32_t max_radius, uint64_t* d_n_clusters, hipStream_t s);
 // the records from n_labelled on walked at max_radius (the first n_labelled of every level come in labelled), the cascade, one flatten
-int vc_levels_run(const VcWalkView& v, uint32_t max_radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_levels_stats* stats, hipStream_t s,
+int vc_levels_run(const VcStoreView& v, uint32_t max_radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_levels_stats* stats, hipStream_t s,
                   std::string* err);
-int vc_levels_run_host(const VcWalkView& v, uint32_t max_radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_levels_stats* stats, hipStream_t s,
+int vc_levels_run_host(const VcStoreView& v, uint32_t max_radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_levels_stats* stats, hipStream_t s,
                        std::string* err);
 // ---- vc_dbscan_levels.hip: density clustering at every radius 0 .. max_radius in one walk (vc_dbscan_levels*).  d_labels is level-major,
 // (max_radius + 1) x n, every slot starts as the own id (vc_launch_cluster_init per level); d_core_dist [n] says whether slot (r, i)
@@ -329,9 +410,9 @@ hipError_t vc_launch_dbscan_levels_finish(uint32_t* d_labels, const uint32_t* d_
                                           uint64_t* d_counts, hipStream_t s);
 // every record walked from position 0 at max_radius, the cascade, one finish pass; d_core_dist null: the handle's own (VC_WALK_RECORD);
 // core_dist (host) nullable
-int vc_dbscan_levels_run(const VcWalkView& v, uint32_t max_radius, uint32_t min_pts, uint32_t batch, uint32_t* d_labels, uint32_t* d_core_dist,
+int vc_dbscan_levels_run(const VcStoreView& v, uint32_t max_radius, uint32_t min_pts, uint32_t batch, uint32_t* d_labels, uint32_t* d_core_dist,
                          vc_dbscan_levels_stats* stats, hipStream_t s, std::string* err);
-int vc_dbscan_levels_run_host(const VcWalkView& v, uint32_t max_radius, uint32_t min_pts, uint32_t batch, uint32_t* labels, uint32_t* core_dist,
+int vc_dbscan_levels_run_host(const VcStoreView& v, uint32_t max_radius, uint32_t min_pts, uint32_t batch, uint32_t* labels, uint32_t* core_dist,
                               vc_dbscan_levels_stats* stats, hipStream_t s, std::string* err);
 // ---- vc_groups.hip: label groups summarised (vc_group_summary*, vc_sharded_group_summary*).  One driver for both handle kinds: the
 // codes of a window's sorted ids come through `fetch` (vc_get_codes_dev / the sharded gather, enqueued on s, nothing waited for)
@@ -347,9 +428,8 @@ struct VcGroupsArgs {
   uint32_t* d_group_index;
   // the handle's grow-only buffer number `which`, at least `bytes` large, on the current device; null when it cannot be had (the
   // handle keeps the error text).  The driver writes every word it reads, so what an earlier call left there never matters.
-  std::function<void*(int which, size_t bytes)> alloc;
+  VcScratchAlloc alloc;
 };
-enum { VC_GROUPS_SCRATCH, VC_GROUPS_WORK, VC_GROUPS_STAGE, VC_GROUPS_BUFS };   // sort / numbering arrays; rows + big-group tables; the host form's staging
 typedef std::function<int(const uint32_t* d_ids, uint32_t nq, uint64_t* d_rows)> VcGroupsFetch;
 // the whole call on s with the device of the buffers current: one wait (error flag, G, items, big groups), scratch from a.alloc
 int vc_groups_run(const VcGroupsArgs& a, const VcGroupsFetch& fetch, uint64_t* n_groups, hipStream_t s, std::string* err);
@@ -363,18 +443,17 @@ int vc_groups_run_host(VcGroupsArgs a, const VcGroupsFetch& fetch, const uint32_
 // whose centre slices meet in atomicMin; nothing is waited for, no scratch.
 hipError_t vc_launch_assign(const uint64_t* cols, uint64_t stride, uint32_t W, uint64_t first, uint64_t count, const uint64_t* d_centres, uint32_t K,
                             uint64_t* d_out, uint32_t n_cu, const VcKnobs* knobs, hipStream_t s);
-enum { VC_KMAJ_WORK, VC_KMAJ_STAGE, VC_KMAJ_BUFS };   // the round driver's arrays; the host forms' staging (alloc as VcGroupsArgs::alloc)
 // the handle's assign over a range fixed by the caller (all N records for the rounds), enqueued on the call's stream, nothing waited for
 typedef std::function<int(const uint64_t* d_centres, uint64_t* d_out)> VcAssignAll;
 // vc_assign_nearest for host pointers: centres staged, `run` into a staged output of `count` words, which comes home; waits for it
-int vc_assign_run_host(const std::function<void*(int which, size_t bytes)>& alloc, uint32_t W, const void* centres, uint32_t K, uint64_t count, uint64_t* out,
+int vc_assign_run_host(const VcScratchAlloc& alloc, uint32_t W, const void* centres, uint32_t K, uint64_t count, uint64_t* out,
                        const VcAssignAll& run, hipStream_t s, std::string* err);
 struct VcKmajArgs {
   uint32_t n_centres, max_iters;   // checked by the caller: 1 <= n_centres <= N, max_iters <= VC_KMAJ_MAX_ITERS
   uint64_t* d_centres;             // in: seeds, out: final
   uint64_t* d_assign;              // N packed
   uint32_t* d_labels;              // N, nullable
-  std::function<void*(int which, size_t bytes)> alloc;   // the handle's grow-only buffers VC_KMAJ_*
+  VcScratchAlloc alloc;   // the handle's grow-only buffers VC_KMAJ_*
 };
 // One driver for both handle kinds, on s with the device of the buffers current.  g: the handle's VcGroupsArgs (n, id_base, W, window,
 // alloc -- the pointers are set here); one wait per round and vc_groups_run's, one at the end.  stats nullable.
@@ -385,7 +464,6 @@ int vc_kmajority_run_host(VcKmajArgs k, const VcGroupsArgs& g, const VcAssignAll
                           uint32_t* labels, vc_kmajority_stats* stats, hipStream_t s, std::string* err);
 // ---- vc_seed.hip: device-side seeding (vc_seed_centres*, vc_sharded_seed_centres*).  The plan arithmetic -- generator, block ranges,
 // slot word (dist << 32 | 0xFFFFFFFF - i), prefix search -- is vc_seed_plan.hpp.  Nothing here waits but vc_seed_run with stats.
-enum { VC_SEED_WORK, VC_SEED_STAGE, VC_SEED_BUFS };   // slots, statistics, partials, best; the host forms' staging (alloc as VcGroupsArgs::alloc)
 // One round over the n records behind cols: best[i] lowered to (distance to the centre, t) where strictly smaller (t == 0: best counts
 // as infinity), then the reduction of the NEW best for the next pick.  A slot is n_slot <= VC_SEED_SUBSLOTS words VC_SEED_SLOT_STRIDE
 // apart whose maximum is the pick.  The centre is the record that slot d_slot_prev names (then its code goes to d_centre_out [W], the
@@ -425,7 +503,7 @@ struct VcSeedArgs {
   uint64_t* d_centres;             // [n_centres][W]
   uint64_t* d_picks;               // nullable
   uint64_t* d_assign;              // nullable: then best lives in the handle's scratch
-  std::function<void*(int which, size_t bytes)> alloc;   // the handle's grow-only buffers VC_SEED_*
+  VcScratchAlloc alloc;   // the handle's grow-only buffers VC_SEED_*
 };
 // the single engine's whole call on s; stats (host memory, nullable): one wait at the end for 16 bytes, none without
 int vc_seed_run(const VcSeedArgs& a, vc_seed_stats* stats, hipStream_t s, std::string* err);
@@ -437,16 +515,13 @@ struct VcSeedHostArgs {
   uint64_t* picks;
   uint64_t* assign;
   vc_seed_stats* stats;
-  std::function<void*(int which, size_t bytes)> alloc;
+  VcScratchAlloc alloc;
 };
 int vc_seed_run_host(const VcSeedHostArgs& a, const std::function<int(uint64_t* d_centres, uint64_t* d_picks, uint64_t* d_assign, vc_seed_stats* stats)>& run,
                      hipStream_t s, std::string* err);
 // ---- vc_distinct.hip: one result per label group in k-NN search (vc_search_knn_distinct*, vc_sharded_search_knn_distinct*).  One
-// driver for both handle kinds, parameterised on the search underneath; the plan arithmetic -- the k' schedule, the collapse kernel's
+// driver for both handle kinds over the view's k-NN search; the plan arithmetic -- the k' schedule, the collapse kernel's
 // form for a k', the verdict on a row, the sub-batches -- is vc_distinct_plan.hpp.
-enum { VC_DISTINCT_WORK, VC_DISTINCT_ROWS, VC_DISTINCT_STAGE, VC_DISTINCT_BUFS };   // flags, maps, retry queries, counters; the k' rows; the host forms' staging
-// the handle's unchanged k-NN search of nq queries [nq][W] at k' into d_rows [nq][k'] and d_cnt [nq], enqueued on the call's stream
-typedef std::function<int(const uint64_t* d_queries, uint32_t nq, uint32_t kp, uint64_t* d_rows, uint32_t* d_cnt)> VcDistinctSearch;
 struct VcDistinctArgs {
   uint64_t n_labels;               // N, the resident records: d_labels has one word for each, indexed by id - id_base
   uint32_t id_base, W;
@@ -458,10 +533,10 @@ struct VcDistinctArgs {
   uint32_t* d_counts;              // [nq], nullable
   uint64_t budget;                 // VcKnobs::distinct_scratch: bytes of rows scratch per sub-batch
   bool tie_cut;                    // the search underneath is exact MIH: its rows are sure only below their last distance (vc_distinct_sure_below)
-  std::function<void*(int which, size_t bytes)> alloc;   // the handle's grow-only buffers VC_DISTINCT_* (as VcGroupsArgs::alloc)
+  VcScratchAlloc alloc;   // the handle's grow-only buffers VC_DISTINCT_* (as VcGroupsArgs::alloc)
 };
 // the whole call on s with the device of the buffers current: one wait per round (24 bytes); stats (host memory) nullable
-int vc_distinct_run(const VcDistinctArgs& a, const VcDistinctSearch& search, vc_distinct_stats* stats, hipStream_t s, std::string* err);
+int vc_distinct_run(const VcDistinctArgs& a, const VcKnnSearch& search, vc_distinct_stats* stats, hipStream_t s, std::string* err);
 // either handle's host form: queries and the N labels staged, `run` (the device form on s) into staged outputs, which come home;
 // waits for them, then turns the valid part of every row round for VC_ORDER_FARTHEST_FIRST.  row_labels, counts, stats nullable
 struct VcDistinctHostArgs {
@@ -473,7 +548,7 @@ struct VcDistinctHostArgs {
   uint32_t* row_labels;
   uint32_t* counts;
   vc_distinct_stats* stats;
-  std::function<void*(int which, size_t bytes)> alloc;
+  VcScratchAlloc alloc;
 };
 int vc_distinct_run_host(const VcDistinctHostArgs& a, const std::function<int(const uint64_t* d_queries, const uint32_t* d_labels, uint64_t* d_out,
                                                                             uint32_t* d_row_labels, uint32_t* d_counts, vc_distinct_stats* stats)>& run,

@@ -204,7 +204,7 @@ hipError_t vc_leaders_decide_batch(const uint64_t* d_raw, const uint64_t* d_roff
   return hipGetLastError();
 }
 
-int vc_leaders_run(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_leader_stats* stats, hipStream_t s,
+int vc_leaders_run(const VcStoreView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_leader_stats* stats, hipStream_t s,
                    std::string* err) {
   const uint64_t N = v.n;
   batch = std::min(vc_walk_batch(batch), VC_LEADER_BATCH_MAX);
@@ -230,7 +230,7 @@ int vc_leaders_run(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_
   return VC_OK;
 }
 
-int vc_leaders_run_host(const VcWalkView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats, hipStream_t s,
+int vc_leaders_run_host(const VcStoreView& v, uint32_t radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_leader_stats* stats, hipStream_t s,
                         std::string* err) {
   uint32_t* d_labels = nullptr;
   int rc = vc_walk_stage_labels(v, labels, 1, n_labelled, &d_labels, s, err);

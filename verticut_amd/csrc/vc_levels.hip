@@ -116,7 +116,7 @@ hipError_t vc_launch_levels_flatten(uint32_t* d_labels, uint64_t n, uint32_t id_
   return hipGetLastError();
 }
 
-int vc_levels_run(const VcWalkView& v, uint32_t max_radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_levels_stats* stats, hipStream_t s,
+int vc_levels_run(const VcStoreView& v, uint32_t max_radius, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels, vc_levels_stats* stats, hipStream_t s,
                   std::string* err) {
   const uint64_t N = v.n, first_new = (uint64_t)v.id_base + n_labelled;
   uint64_t* d_stat = (uint64_t*)v.alloc(VC_WALK_STAT, VC_LEVELS_STAT_BYTES);
@@ -137,7 +137,7 @@ int vc_levels_run(const VcWalkView& v, uint32_t max_radius, uint32_t batch, uint
   return VC_OK;
 }
 
-int vc_levels_run_host(const VcWalkView& v, uint32_t max_radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_levels_stats* stats, hipStream_t s,
+int vc_levels_run_host(const VcStoreView& v, uint32_t max_radius, uint32_t batch, uint64_t n_labelled, uint32_t* labels, vc_levels_stats* stats, hipStream_t s,
                        std::string* err) {
   const size_t levels = (size_t)max_radius + 1;
   uint32_t* d_labels = nullptr;

@@ -16,7 +16,7 @@
 //                          behind the shard's search by an event; also the path when several shards share a device
 // No CPU compute anywhere: the host moves pointers, the merge is the device kernel of vc_scan.hip.
 //
-// In this file: DevBuf (grow-only scratch), Lane, vc_sharded | create / ingest / look-up | ShardBatch = one batch through the
+// In this file: Lane, vc_sharded (its grow-only scratch: DevBuf, vc_internal.hpp) | create / ingest / look-up | ShardBatch = one batch through the
 // shards (prepare_lanes, send_queries, run_lanes, exchange, merge; sharded_search_dev) | VC_FLAG_GLOBAL_STOP: the stop rule
 // (gs_stop_shell), the kernels, the layouts they share with the host (GsRoundLists, GsScanCols, GsScanBlock) and GsSearch,
 // the steps of a flagged call (sharded_global_stop, GsSearch::union_scan) | the device-resident radius search: its two kernels
@@ -82,17 +82,6 @@ struct RcclApi {
   }
 };
 
-// Grow-only device scratch: the pointer and how many bytes are behind it.  It has no destructor on purpose: hipFree acts on
-// the CURRENT device, so the owner binds the buffer's device and then releases it (vc_sharded_destroy, ScopedBufs).
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  int grow(vc_sharded* h, size_t need);   // at least `need` bytes, on the current device; the contents are lost when it grows
-  hipError_t regrow(size_t need);         // the same without the handle's error text (lane threads keep their own)
-  void release() { (void)hipFree(p); p = nullptr; bytes = 0; }
-  template <class T> T* as() const { return (T*)p; }
-};
-
 // One lane per distinct device: the shards that live there run ONE AFTER THE OTHER on the lane's stream -- at most one
 // persistent-grid kernel sequence per GPU (the recovery kernel's grid barrier needs its whole grid resident; a neighbour
 // shard's full-chip verify grid on another stream could keep it off the CUs for seconds: ADVICE round 3) -- while the
@@ -129,27 +118,8 @@ enum RootBuf {
   // of a round, the union scan's per-query words and the shards' tie ids (GsScanBlock, gs_root_block)
   GS_LISTS, GS_Q, GS_ROWS, GS_CNT, GS_ST, GS_SCAN,
   GA_LISTS,   // VC_FLAG_GLOBAL_APPROX: the open lists and counters of its rounds (GaRoundLists); gathered queries and a round's merged rows in GS_Q .. GS_ST
-  // queries named by id: gathered queries, found words, the k + 1 rows and counts of the search underneath; the host-pointer
-  // form's staged ids, rows, counts and statistics
-  IDS_Q, IDS_FOUND, IDS_ROWS, IDS_CNT, IDS_HIDS, IDS_HROWS, IDS_HCNT, IDS_HSTATS,
-  // radius search by id: gathered queries, found words, the union's uncompacted results and offsets, the compaction's counts
-  // (VcIdsRadiusWork); the host-pointer form's staged ids, results and offsets
-  RIDS_Q, RIDS_FOUND, RIDS_RAW, RIDS_ROFFS, RIDS_WORK, RIDS_HIDS, RIDS_HOUT, RIDS_HOFFS,
-  // the clustering calls over the radius-graph walk: the walk's batch buffers, the statistics, the per-record words, leaders' state words
-  // and the host forms' staged labels (WALK_FIRST + VC_WALK_*); shared by the five calls, each writes every word it reads
-  WALK_FIRST, WALK_LAST = WALK_FIRST + VC_WALK_BUFS - 1,
-  // label groups summarised: the sort and numbering arrays, the row buffer with the big groups' tables, the host form's staging
-  // (GRP_SCRATCH + VC_GROUPS_*); its own, every word written before it is read
-  GRP_SCRATCH, GRP_WORK, GRP_STAGE,
-  // nearest of K codes and k-majority: the round driver's arrays, the host forms' staging (KM_WORK + VC_KMAJ_*); their own, every word
-  // written before it is read
-  KM_WORK, KM_STAGE,
-  // seeding: the id word, the statistics and best when the caller gives no assign; the host form's staging (SD_WORK + VC_SEED_*); its own,
-  // every word written before it is read
-  SD_WORK, SD_STAGE,
-  // one result per label group: flags, maps, retry queries and counters; the k' rows; the host form's staging (DS_WORK + VC_DISTINCT_*);
-  // its own, every word written before it is read
-  DS_WORK, DS_ROWS, DS_STAGE,
+  // the scratch of the drivers shared with the single engine, on the root device: SCRATCH + a VcScratch (vc_internal.hpp)
+  SCRATCH, SCRATCH_LAST = SCRATCH + VC_SCRATCH_BUFS - 1,
   ROOT_BUFS
 };
 
@@ -204,20 +174,9 @@ static int sfail(vc_sharded* h, int code, const char* fmt, ...) {
       return sfail(h, _r == hipErrorOutOfMemory ? VC_ERR_NOMEM : VC_ERR_HIP, "%s: %s", #call, hipGetErrorString(_r)); \
   } while (0)
 
-hipError_t DevBuf::regrow(size_t need) {
-  if (need <= bytes) return hipSuccess;
-  hipError_t r = p ? hipFree(p) : hipSuccess;
-  p = nullptr;
-  bytes = 0;
-  if (r != hipSuccess) return r;
-  need = (need + 255) & ~(size_t)255;
-  if ((r = hipMalloc(&p, need)) != hipSuccess) { p = nullptr; return r; }
-  bytes = need;
-  return hipSuccess;
-}
-
-int DevBuf::grow(vc_sharded* h, size_t need) {
-  VS_HIP(h, regrow(need));
+// b of at least `need` bytes on the current device, the handle keeping the text of a failure
+static int grow(vc_sharded* h, DevBuf& b, size_t need) {
+  VS_HIP(h, b.regrow(need));
   return VC_OK;
 }
 
@@ -238,6 +197,9 @@ static uint32_t shard_of(const vc_sharded* h, uint64_t pos) {   // pos relative 
 static uint64_t shard_size(const vc_sharded* h, uint32_t g) {   // records shard g holds (ingest fills the id ranges in order)
   return h->n <= h->lo[g] ? 0 : std::min(h->n, h->hi[g]) - h->lo[g];
 }
+
+// the stream of a device-pointer call
+static hipStream_t sharded_caller_stream(const vc_sharded* h, void* stream) { return stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream; }
 
 extern "C" {
 
@@ -522,7 +484,7 @@ extern "C" __global__ void vc_sharded_stats_kernel(const uint64_t* __restrict__ 
 // A caller that passes no count buffer gets the handle's own (the root device is current).
 static int counts_or_own(vc_sharded* h, uint32_t nq, uint32_t** d_counts) {
   if (*d_counts) return VC_OK;
-  if (int rc = h->buf[ROOT_OCNT].grow(h, (size_t)nq * 4)) return rc;
+  if (int rc = grow(h, h->buf[ROOT_OCNT], (size_t)nq * 4)) return rc;
   *d_counts = h->buf[ROOT_OCNT].as<uint32_t>();
   return VC_OK;
 }
@@ -571,8 +533,8 @@ struct ShardBatch {
       Lane& l = h->lanes[li];
       const bool everything = li == h->root_lane || h->exchange == VC_EXCHANGE_RCCL;   // gathered results of all shards land here
       VS_HIP(h, hipSetDevice(l.dev));
-      if ((rc = l.buf[LANE_GATH].grow(h, L.words * 8 * (everything ? h->G : l.shards.back() + 1)))) return rc;
-      if (li != h->root_lane && (rc = l.buf[LANE_Q].grow(h, qbytes))) return rc;
+      if ((rc = grow(h, l.buf[LANE_GATH], L.words * 8 * (everything ? h->G : l.shards.back() + 1)))) return rc;
+      if (li != h->root_lane && (rc = grow(h, l.buf[LANE_Q], qbytes))) return rc;
     }
     if (!d_counts) {
       VS_HIP(h, hipSetDevice(h->root));
@@ -961,12 +923,12 @@ struct GsScanBlock {
 };
 // (the owning device is current: the buffer may grow)
 static int gs_root_block(vc_sharded* h, uint32_t nq, uint32_t k, GsScanBlock* out) {
-  if (int rc = h->buf[GS_SCAN].grow(h, GsScanBlock::words(h->lanes.size(), h->G, nq, k, false) * 4)) return rc;
+  if (int rc = grow(h, h->buf[GS_SCAN], GsScanBlock::words(h->lanes.size(), h->G, nq, k, false) * 4)) return rc;
   *out = GsScanBlock::carve(h->buf[GS_SCAN].as<uint32_t>(), h->lanes.size(), h->G, nq, k, false);
   return VC_OK;
 }
 static int gs_lane_block(vc_sharded* h, Lane& l, uint32_t nq, uint32_t k, GsScanBlock* out) {
-  if (int rc = l.buf[LANE_AUX].grow(h, GsScanBlock::words(1, l.shards.size(), nq, k, true) * 4)) return rc;
+  if (int rc = grow(h, l.buf[LANE_AUX], GsScanBlock::words(1, l.shards.size(), nq, k, true) * 4)) return rc;
   *out = GsScanBlock::carve(l.buf[LANE_AUX].as<uint32_t>(), 1, l.shards.size(), nq, k, true);
   return VC_OK;
 }
@@ -1016,11 +978,11 @@ struct GsSearch {
     int rc;
     VS_HIP(h, hipSetDevice(h->root));
     if ((rc = counts_or_own(h, nq, &d_counts))) return rc;
-    if ((rc = h->buf[GS_LISTS].grow(h, GsRoundLists::words(nq) * 4))) return rc;
-    if ((rc = h->buf[GS_Q].grow(h, (size_t)nq * h->nbytes))) return rc;
-    if ((rc = h->buf[GS_ROWS].grow(h, (size_t)nq * k * 8))) return rc;
-    if ((rc = h->buf[GS_CNT].grow(h, (size_t)nq * 4))) return rc;
-    if ((rc = h->buf[GS_ST].grow(h, (size_t)nq * sizeof(vc_query_stats)))) return rc;
+    if ((rc = grow(h, h->buf[GS_LISTS], GsRoundLists::words(nq) * 4))) return rc;
+    if ((rc = grow(h, h->buf[GS_Q], (size_t)nq * h->nbytes))) return rc;
+    if ((rc = grow(h, h->buf[GS_ROWS], (size_t)nq * k * 8))) return rc;
+    if ((rc = grow(h, h->buf[GS_CNT], (size_t)nq * 4))) return rc;
+    if ((rc = grow(h, h->buf[GS_ST], (size_t)nq * sizeof(vc_query_stats)))) return rc;
     ls = GsRoundLists::carve(h->buf[GS_LISTS].as<uint32_t>(), nq);
     gs_q = h->buf[GS_Q].as<uint64_t>();
     rows = h->buf[GS_ROWS].as<uint64_t>();
@@ -1362,11 +1324,11 @@ struct GaSearch {
     int rc;
     VS_HIP(h, hipSetDevice(h->root));
     if ((rc = counts_or_own(h, nq, &d_counts))) return rc;
-    if ((rc = h->buf[GA_LISTS].grow(h, GaRoundLists::words(nq) * 4))) return rc;
-    if ((rc = h->buf[GS_Q].grow(h, (size_t)nq * h->nbytes))) return rc;
-    if ((rc = h->buf[GS_ROWS].grow(h, (size_t)nq * k * 8))) return rc;
-    if ((rc = h->buf[GS_CNT].grow(h, (size_t)nq * 4))) return rc;
-    if ((rc = h->buf[GS_ST].grow(h, (size_t)nq * sizeof(vc_query_stats)))) return rc;
+    if ((rc = grow(h, h->buf[GA_LISTS], GaRoundLists::words(nq) * 4))) return rc;
+    if ((rc = grow(h, h->buf[GS_Q], (size_t)nq * h->nbytes))) return rc;
+    if ((rc = grow(h, h->buf[GS_ROWS], (size_t)nq * k * 8))) return rc;
+    if ((rc = grow(h, h->buf[GS_CNT], (size_t)nq * 4))) return rc;
+    if ((rc = grow(h, h->buf[GS_ST], (size_t)nq * sizeof(vc_query_stats)))) return rc;
     ls = GaRoundLists::carve(h->buf[GA_LISTS].as<uint32_t>(), nq);
     ga_q = h->buf[GS_Q].as<uint64_t>();
     rows = h->buf[GS_ROWS].as<uint64_t>();
@@ -1575,11 +1537,11 @@ struct ShardRadius {
     for (uint32_t li = 0; li < h->lanes.size(); ++li) {
       Lane& l = h->lanes[li];
       VS_HIP(h, hipSetDevice(l.dev));
-      if (li != h->root_lane && (rc = l.buf[LANE_Q].grow(h, qbytes))) return rc;
+      if (li != h->root_lane && (rc = grow(h, l.buf[LANE_Q], qbytes))) return rc;
       for (uint32_t g : l.shards) {
         if (shard_size(h, g) == 0) continue;
-        if ((rc = h->rad[g].offs.grow(h, vc_rshard_offs_bytes(nq)))) return rc;
-        if ((rc = h->rad[g].res.grow(h, first_bytes))) return rc;
+        if ((rc = grow(h, h->rad[g].offs, vc_rshard_offs_bytes(nq)))) return rc;
+        if ((rc = grow(h, h->rad[g].res, first_bytes))) return rc;
       }
     }
     return VC_OK;
@@ -1650,8 +1612,8 @@ struct ShardRadius {
       if (h->lane_of[g] == h->root_lane || shard_size(h, g) == 0) continue;
       size_t bytes;
       if (!vc_rshard_bytes(total_g[g], &bytes)) return sfail(h, VC_ERR_NOMEM, "radius search: shard %u found too much", g);
-      if ((rc = h->rad[g].root_offs.grow(h, vc_rshard_offs_bytes(nq)))) return rc;
-      if ((rc = h->rad[g].root_res.grow(h, bytes))) return rc;
+      if ((rc = grow(h, h->rad[g].root_offs, vc_rshard_offs_bytes(nq)))) return rc;
+      if ((rc = grow(h, h->rad[g].root_res, bytes))) return rc;
     }
     for (uint32_t li = 0; li < h->lanes.size(); ++li) {
       if (li == h->root_lane) continue;
@@ -1721,8 +1683,8 @@ static int sharded_gather_ids(vc_sharded* h, const uint32_t* d_ids, uint32_t nq,
   for (uint32_t li = 0; li < h->lanes.size(); ++li) {
     Lane& l = h->lanes[li];
     VS_HIP(h, hipSetDevice(l.dev));
-    if ((rc = l.buf[LANE_IDGATH].grow(h, slot_words * 8 * (li == h->root_lane ? h->G : l.shards.back() + 1)))) return rc;
-    if (li != h->root_lane && (rc = l.buf[LANE_IDS].grow(h, (size_t)nq * 4))) return rc;
+    if ((rc = grow(h, l.buf[LANE_IDGATH], slot_words * 8 * (li == h->root_lane ? h->G : l.shards.back() + 1)))) return rc;
+    if (li != h->root_lane && (rc = grow(h, l.buf[LANE_IDS], (size_t)nq * 4))) return rc;
   }
   if (h->lanes.size() > 1) {
     VS_HIP(h, hipSetDevice(h->root));
@@ -1783,7 +1745,7 @@ int vc_sharded_root_device(const vc_sharded* h, int* device) {
 int vc_sharded_search_knn_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out,
                               uint32_t* d_counts, vc_query_stats* d_stats, void* stream) {
   if (!h || !d_queries || !d_out || nq == 0 || k == 0 || k > VC_MAX_K || mode > VC_MODE_MIH_APPROX) return VC_ERR_INVALID;
-  return sharded_search_any(h, d_queries, nq, k, mode, d_out, d_counts, d_stats, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+  return sharded_search_any(h, d_queries, nq, k, mode, d_out, d_counts, d_stats, sharded_caller_stream(h, stream));
 }
 
 // the merged rows and counts (and statistics, when wanted) of the host-pointer call reach the host; waits for them
@@ -1803,7 +1765,7 @@ static int reanswer_linear_by_host(vc_sharded* h, const void* queries, uint32_t 
   Lane& R = h->root_lane_ref();
   int rc;
   VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = R.buf[LANE_GATH].grow(h, L.words * 8 * h->G))) return rc;
+  if ((rc = grow(h, R.buf[LANE_GATH], L.words * 8 * h->G))) return rc;
   std::vector<uint64_t> slot(L.words);
   for (uint32_t g = 0; g < h->G; ++g) {
     uint32_t* c = (uint32_t*)(slot.data() + L.cnt_off);
@@ -1832,10 +1794,10 @@ int vc_sharded_search_knn(vc_sharded* h, const void* queries, uint32_t nq, uint3
   int rc;
   hipStream_t S = h->root_stream;
   VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[ROOT_HQ].grow(h, qbytes))) return rc;
-  if ((rc = h->buf[ROOT_OUT].grow(h, rows * 8))) return rc;
-  if ((rc = h->buf[ROOT_OCNT].grow(h, (size_t)nq * 4))) return rc;
-  if (stats && (rc = h->buf[ROOT_OSTATS].grow(h, (size_t)nq * sizeof(vc_query_stats)))) return rc;
+  if ((rc = grow(h, h->buf[ROOT_HQ], qbytes))) return rc;
+  if ((rc = grow(h, h->buf[ROOT_OUT], rows * 8))) return rc;
+  if ((rc = grow(h, h->buf[ROOT_OCNT], (size_t)nq * 4))) return rc;
+  if (stats && (rc = grow(h, h->buf[ROOT_OSTATS], (size_t)nq * sizeof(vc_query_stats)))) return rc;
   VS_HIP(h, hipMemcpyAsync(h->buf[ROOT_HQ].p, queries, qbytes, hipMemcpyHostToDevice, S));
   if ((rc = sharded_search_any(h, h->buf[ROOT_HQ].p, nq, k, mode, h->buf[ROOT_OUT].as<uint64_t>(), h->buf[ROOT_OCNT].as<uint32_t>(),
                                stats ? h->buf[ROOT_OSTATS].as<vc_query_stats>() : nullptr, S)))
@@ -1886,10 +1848,10 @@ static int sort_segments_on_root(vc_sharded* h, const std::vector<uint64_t>& rin
   enum { RING, OFFS, OUT, COUNT, N_TMP };
   ScopedBufs<N_TMP> tmp;
   int rc;
-  if ((rc = tmp.b[RING].grow(h, ring.size() * 8))) return rc;
-  if ((rc = tmp.b[OFFS].grow(h, ((size_t)nq + 1) * 8))) return rc;
-  if ((rc = tmp.b[OUT].grow(h, total * 8))) return rc;
-  if ((rc = tmp.b[COUNT].grow(h, (size_t)nq * 4))) return rc;
+  if ((rc = grow(h, tmp.b[RING], ring.size() * 8))) return rc;
+  if ((rc = grow(h, tmp.b[OFFS], ((size_t)nq + 1) * 8))) return rc;
+  if ((rc = grow(h, tmp.b[OUT], total * 8))) return rc;
+  if ((rc = grow(h, tmp.b[COUNT], (size_t)nq * 4))) return rc;
   VS_HIP(h, hipMemcpyAsync(tmp.b[RING].p, ring.data(), ring.size() * 8, hipMemcpyHostToDevice, S));
   VS_HIP(h, hipMemcpyAsync(tmp.b[OFFS].p, out_offsets, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice, S));
   VS_HIP(h, hipMemcpyAsync(tmp.b[COUNT].p, count.data(), (size_t)nq * 4, hipMemcpyHostToDevice, S));
@@ -1942,167 +1904,132 @@ int vc_sharded_search_radius_dev(vc_sharded* h, const void* d_queries, uint32_t 
                                  uint64_t out_cap, uint64_t* d_offsets, void* stream) {
   if (!h || !d_queries || !d_offsets || nq == 0 || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) || (!d_out && out_cap))
     return VC_ERR_INVALID;
-  return sharded_radius_dev(h, d_queries, nq, radius, mode, d_out, out_cap, d_offsets, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+  return sharded_radius_dev(h, d_queries, nq, radius, mode, d_out, out_cap, d_offsets, sharded_caller_stream(h, stream));
 }
 
 int vc_sharded_get_codes_dev(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, void* d_codes, uint32_t* d_found, void* stream) {
   if (!h || !d_ids || !d_codes || nq == 0) return VC_ERR_INVALID;
-  return sharded_gather_ids(h, d_ids, nq, (uint64_t*)d_codes, d_found, false, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
-}
-
-int vc_sharded_search_knn_ids_dev(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t id_flags,
-                                  uint64_t* d_out, uint32_t* d_counts, vc_query_stats* d_stats, void* stream) {
-  int rc = check_sharded_ids_args(h, d_ids, nq, k, mode, id_flags, d_out);
-  if (rc) return rc;
-  hipStream_t S = stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream;
-  const uint32_t kp = k + ((id_flags & VC_IDS_EXCLUDE_SELF) ? 1u : 0u);
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[IDS_Q].grow(h, (size_t)nq * h->nbytes))) return rc;
-  if ((rc = h->buf[IDS_FOUND].grow(h, (size_t)nq * 4))) return rc;
-  if ((rc = h->buf[IDS_ROWS].grow(h, (size_t)nq * kp * 8))) return rc;
-  if ((rc = h->buf[IDS_CNT].grow(h, (size_t)nq * 4))) return rc;
-  if ((rc = sharded_gather_ids(h, d_ids, nq, h->buf[IDS_Q].as<uint64_t>(), h->buf[IDS_FOUND].as<uint32_t>(), true, S))) return rc;
-  if ((rc = sharded_search_any(h, h->buf[IDS_Q].p, nq, kp, mode, h->buf[IDS_ROWS].as<uint64_t>(), h->buf[IDS_CNT].as<uint32_t>(), d_stats, S))) return rc;
-  VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, vc_launch_ids_strip(d_ids, h->buf[IDS_FOUND].as<uint32_t>(), h->buf[IDS_ROWS].as<uint64_t>(), h->buf[IDS_CNT].as<uint32_t>(), nq, kp, k,
-                                d_out, d_counts, d_stats, S));
-  return VC_OK;
-}
-
-int vc_sharded_search_knn_ids(vc_sharded* h, const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order,
-                              uint32_t id_flags, uint64_t* out, uint32_t* counts, vc_query_stats* stats) {
-  int rc = check_sharded_ids_args(h, ids, nq, k, mode, id_flags, out);
-  if (rc) return rc;
-  if (order > VC_ORDER_FARTHEST_FIRST) return VC_ERR_INVALID;
-  hipStream_t S = h->root_stream;
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[IDS_HIDS].grow(h, (size_t)nq * 4))) return rc;
-  if ((rc = h->buf[IDS_HROWS].grow(h, (size_t)nq * k * 8))) return rc;
-  if ((rc = h->buf[IDS_HCNT].grow(h, (size_t)nq * 4))) return rc;
-  if (stats && (rc = h->buf[IDS_HSTATS].grow(h, (size_t)nq * sizeof(vc_query_stats)))) return rc;
-  VS_HIP(h, hipMemcpyAsync(h->buf[IDS_HIDS].p, ids, (size_t)nq * 4, hipMemcpyHostToDevice, S));
-  if ((rc = vc_sharded_search_knn_ids_dev(h, h->buf[IDS_HIDS].as<uint32_t>(), nq, k, mode, id_flags, h->buf[IDS_HROWS].as<uint64_t>(),
-                                          h->buf[IDS_HCNT].as<uint32_t>(), stats ? h->buf[IDS_HSTATS].as<vc_query_stats>() : nullptr, S)))
-    return rc;
-  std::vector<uint32_t> cnt(nq);
-  VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, hipMemcpyAsync(out, h->buf[IDS_HROWS].p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipMemcpyAsync(cnt.data(), h->buf[IDS_HCNT].p, (size_t)nq * 4, hipMemcpyDeviceToHost, S));
-  if (stats) VS_HIP(h, hipMemcpyAsync(stats, h->buf[IDS_HSTATS].p, (size_t)nq * sizeof(vc_query_stats), hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipStreamSynchronize(S));
-  if (mode == VC_MODE_LINEAR && std::find(cnt.begin(), cnt.end(), 0xFFFFFFFFu) != cnt.end()) {
-    // a shard's device-side ring-overflow recovery gave up: the batch is answered again by vc_sharded_search_knn (whose shards
-    // recover on the host) on the gathered codes, and stripped here by the kernel's rule
-    const uint32_t kp = k + ((id_flags & VC_IDS_EXCLUDE_SELF) ? 1u : 0u);
-    std::vector<uint64_t> codes((size_t)nq * (h->nbytes / 8)), rows((size_t)nq * kp);
-    std::vector<uint32_t> found(nq), rcnt(nq);
-    VS_HIP(h, hipMemcpyAsync(codes.data(), h->buf[IDS_Q].p, codes.size() * 8, hipMemcpyDeviceToHost, S));
-    VS_HIP(h, hipMemcpyAsync(found.data(), h->buf[IDS_FOUND].p, (size_t)nq * 4, hipMemcpyDeviceToHost, S));
-    VS_HIP(h, hipStreamSynchronize(S));
-    if ((rc = vc_sharded_search_knn(h, codes.data(), nq, kp, mode, VC_ORDER_ASCENDING, rows.data(), rcnt.data(), stats))) return rc;
-    vc_ids_strip_host(ids, found.data(), rows.data(), rcnt.data(), nq, kp, k, out, cnt.data(), stats);
-  }
-  for (uint32_t i = 0; i < nq; ++i) {
-    if (mode != VC_MODE_LINEAR) cnt[i] = std::min(cnt[i], k);   // (as vc_sharded_search_knn: a flagged MIH row has k entries)
-    if (order == VC_ORDER_FARTHEST_FIRST) std::reverse(out + (size_t)i * k, out + (size_t)i * k + cnt[i]);
-    if (counts) counts[i] = cnt[i];
-    if (stats) stats[i].n_results = cnt[i];
-  }
-  return VC_OK;
+  return sharded_gather_ids(h, d_ids, nq, (uint64_t*)d_codes, d_found, false, sharded_caller_stream(h, stream));
 }
 
 }  // extern "C"
 
-static int check_sharded_radius_ids_args(vc_sharded* h, const uint32_t* ids, uint32_t nq, uint32_t mode, uint32_t id_flags, const uint64_t* out,
-                                         uint64_t out_cap, const uint64_t* offsets) {
-  if (!h || !ids || !offsets || nq == 0 || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) || (!out && out_cap)) return VC_ERR_INVALID;
-  if (id_flags & ~(VC_IDS_EXCLUDE_SELF | VC_IDS_ONLY_GREATER)) return sfail(h, VC_ERR_INVALID, "unknown id_flags 0x%x", id_flags);
-  if (mode == VC_MODE_MIH_EXACT)
-    for (uint32_t g = 0; g < h->G; ++g)
-      if (shard_size(h, g) && !vc_engine_has_index(h->eng[g])) return sfail(h, VC_ERR_STATE, "shard %u: MIH search needs vc_sharded_build_index() first", g);
-  return VC_OK;
-}
-
-// Radius search by id over the shards, all on the root device's stream S: gather, the union's radius search into the handle's scratch --
-// repeated once with the scratch grown to the total it reported -- count / offsets, and, once T is known to fit, the copy.
-static int sharded_radius_ids_run(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags,
-                                  uint64_t* d_out, uint64_t out_cap, uint64_t* d_offsets, hipStream_t S) {
-  int rc;
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[RIDS_Q].grow(h, (size_t)nq * h->nbytes))) return rc;
-  if ((rc = h->buf[RIDS_FOUND].grow(h, (size_t)nq * 4))) return rc;
-  if ((rc = h->buf[RIDS_ROFFS].grow(h, ((size_t)nq + 1) * 8))) return rc;
-  if ((rc = h->buf[RIDS_RAW].grow(h, (size_t)8 << 16))) return rc;
-  if ((rc = sharded_gather_ids(h, d_ids, nq, h->buf[RIDS_Q].as<uint64_t>(), h->buf[RIDS_FOUND].as<uint32_t>(), true, S))) return rc;
-  uint64_t raw_total = 0;
-  for (int attempt = 0;; ++attempt) {
-    const uint64_t cap = h->buf[RIDS_RAW].bytes / 8;
-    rc = sharded_radius_dev(h, h->buf[RIDS_Q].p, nq, radius, mode, h->buf[RIDS_RAW].as<uint64_t>(), cap, h->buf[RIDS_ROFFS].as<uint64_t>(), S, &raw_total);
-    if (rc == VC_OK) break;
-    if (rc != VC_ERR_CAPACITY || attempt || raw_total <= cap) return rc;
-    VS_HIP(h, hipSetDevice(h->root));
-    if ((rc = h->buf[RIDS_RAW].grow(h, (size_t)raw_total * 8))) return rc;
-  }
-  VS_HIP(h, hipSetDevice(h->root));
-  const uint64_t items = vc_ids_radius_items(nq, raw_total);
-  if (items > 0xFFFFFFFFull) return sfail(h, VC_ERR_CAPACITY, "radius search by id: more results than one compaction can place");
-  if ((rc = h->buf[RIDS_WORK].grow(h, VcIdsRadiusWork::bytes(nq, items)))) return rc;
-  const VcIdsRadiusWork w(h->buf[RIDS_WORK].p, nq, items);
-  const uint64_t *raw = h->buf[RIDS_RAW].as<uint64_t>(), *roffs = h->buf[RIDS_ROFFS].as<uint64_t>();
-  VS_HIP(h, vc_launch_ids_radius_count(w, raw, roffs, d_ids, h->buf[RIDS_FOUND].as<uint32_t>(), nq, id_flags, d_offsets, S));
-  if (raw_total > out_cap) {   // T <= raw_total: only then the host has to learn T
-    uint64_t T = 0;
-    VS_HIP(h, hipMemcpyAsync(&T, w.total, 8, hipMemcpyDeviceToHost, S));
-    VS_HIP(h, hipStreamSynchronize(S));
-    if (T > out_cap) return sfail(h, VC_ERR_CAPACITY, "radius search: output buffer too small (needed counts are in the offsets)");
-  }
-  if (d_out && raw_total) VS_HIP(h, vc_launch_ids_radius_copy(w, raw, roffs, d_ids, nq, id_flags, d_offsets, d_out, S));
-  return VC_OK;
-}
-
-extern "C" {
-
-int vc_sharded_search_radius_ids_dev(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags,
-                                     uint64_t* d_out, uint64_t out_cap, uint64_t* d_offsets, void* stream) {
-  int rc = check_sharded_radius_ids_args(h, d_ids, nq, mode, id_flags, d_out, out_cap, d_offsets);
-  if (rc) return rc;
-  return sharded_radius_ids_run(h, d_ids, nq, radius, mode, id_flags, d_out, out_cap, d_offsets, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
-}
-
-int vc_sharded_search_radius_ids(vc_sharded* h, const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* out,
-                                 uint64_t out_cap, uint64_t* out_offsets) {
-  int rc = check_sharded_radius_ids_args(h, ids, nq, mode, id_flags, out, out_cap, out_offsets);
-  if (rc) return rc;
-  hipStream_t S = h->root_stream;
-  VS_HIP(h, hipSetDevice(h->root));
-  if ((rc = h->buf[RIDS_HIDS].grow(h, (size_t)nq * 4))) return rc;
-  if ((rc = h->buf[RIDS_HOFFS].grow(h, ((size_t)nq + 1) * 8))) return rc;
-  if ((rc = h->buf[RIDS_HOUT].grow(h, (size_t)out_cap * 8))) return rc;
-  VS_HIP(h, hipMemcpyAsync(h->buf[RIDS_HIDS].p, ids, (size_t)nq * 4, hipMemcpyHostToDevice, S));
-  rc = sharded_radius_ids_run(h, h->buf[RIDS_HIDS].as<uint32_t>(), nq, radius, mode, id_flags, out_cap ? h->buf[RIDS_HOUT].as<uint64_t>() : nullptr, out_cap,
-                              h->buf[RIDS_HOFFS].as<uint64_t>(), S);
-  if (rc != VC_OK && rc != VC_ERR_CAPACITY) return rc;
-  // the offsets come home in both cases (VC_ERR_CAPACITY: they are the needed counts); the staged results behind them
-  VS_HIP(h, hipSetDevice(h->root));
-  VS_HIP(h, hipMemcpyAsync(out_offsets, h->buf[RIDS_HOFFS].p, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, S));
-  VS_HIP(h, hipStreamSynchronize(S));
-  if (rc == VC_OK && out_offsets[nq]) {
-    VS_HIP(h, hipMemcpyAsync(out, h->buf[RIDS_HOUT].p, (size_t)out_offsets[nq] * 8, hipMemcpyDeviceToHost, S));
-    VS_HIP(h, hipStreamSynchronize(S));
-  }
-  return rc;
-}
-
-}  // extern "C"
-
-// ---- the clustering calls over the shards: the drivers of vc_cluster.hip, vc_levels.hip, vc_leaders.hip, vc_dbscan.hip and
-// vc_dbscan_levels.hip on the root, their walk (vc_walk.hip) through the sharded gather and the union's radius search ------------------
+// ---- the store as the drivers it shares with the single engine see it --------------------------------------------------------
 static int check_sharded_index(vc_sharded* h, uint32_t mode) {   // exact MIH needs an index on every non-empty shard
   if (mode == VC_MODE_MIH_EXACT)
     for (uint32_t g = 0; g < h->G; ++g)
       if (shard_size(h, g) && !vc_engine_has_index(h->eng[g])) return sfail(h, VC_ERR_STATE, "shard %u: MIH search needs vc_sharded_build_index() first", g);
   return VC_OK;
 }
+
+static VcScratchAlloc sharded_scratch_alloc(vc_sharded* h) {   // buffer `which` of the table (VcScratch) on the root, which it binds
+  return [h](int which, size_t bytes) -> void* {
+    if (hipSetDevice(h->root) != hipSuccess) return nullptr;
+    DevBuf& b = h->buf[SCRATCH + which];
+    return grow(h, b, bytes) ? nullptr : b.p;
+  };
+}
+
+// The view of one call: the buffers are the root's, everything the root does goes to S.  The gather and the searches visit the other
+// devices and come back with the root current, so the drivers never bind one.
+static VcStoreView sharded_store_view(vc_sharded* h, uint32_t mode, hipStream_t S) {
+  VcStoreView v;
+  v.n = h->n;
+  v.id_base = h->cfg.engine.id_base;
+  v.W = h->nbytes / 8;
+  v.alloc = sharded_scratch_alloc(h);
+  v.held = [h](int which) { return h->buf[SCRATCH + which].bytes; };
+  v.gather = [h, S](const uint32_t* d_ids, uint32_t nq, uint64_t* d_q, uint32_t* d_found) { return sharded_gather_ids(h, d_ids, nq, d_q, d_found, true, S); };
+  v.search = [h, mode, S](const uint64_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_raw, uint64_t cap, uint64_t* d_roffs, uint64_t* raw_total) -> int {
+    const int rc = sharded_radius_dev(h, d_q, nq, radius, mode, d_raw, cap, d_roffs, S, raw_total);
+    if (rc && rc != VC_ERR_CAPACITY) return rc;
+    VS_HIP(h, hipSetDevice(h->root));
+    return rc;
+  };
+  v.knn = [h, mode, S](const uint64_t* d_q, uint32_t nq, uint32_t kp, uint64_t* d_rows, uint32_t* d_cnt, vc_query_stats* d_stats) -> int {
+    const int rc = sharded_search_any(h, d_q, nq, kp, mode, d_rows, d_cnt, d_stats, S);
+    if (rc) return rc;
+    VS_HIP(h, hipSetDevice(h->root));
+    return VC_OK;
+  };
+  return v;
+}
+
+// An entry point after its checks: the root bound, `run` (a driver's vc_*_run or vc_*_run_host) with the view on stream S.
+template <class Run>
+static int sharded_store_call(vc_sharded* h, uint32_t mode, hipStream_t S, const Run& run) {
+  VS_HIP(h, hipSetDevice(h->root));
+  std::string err;
+  const int rc = run(sharded_store_view(h, mode, S), S, &err);
+  return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;   // (a closure of the view has left its own text)
+}
+
+// ---- queries named by id over the shards: the drivers of vc_ids.hip and vc_ids_radius.hip on the root --------------------------------
+static int check_sharded_radius_ids_args(vc_sharded* h, const uint32_t* ids, uint32_t nq, uint32_t mode, uint32_t id_flags, const uint64_t* out,
+                                         uint64_t out_cap, const uint64_t* offsets) {
+  if (!h || !ids || !offsets || nq == 0 || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) || (!out && out_cap)) return VC_ERR_INVALID;
+  if (id_flags & ~(VC_IDS_EXCLUDE_SELF | VC_IDS_ONLY_GREATER)) return sfail(h, VC_ERR_INVALID, "unknown id_flags 0x%x", id_flags);
+  return check_sharded_index(h, mode);
+}
+
+extern "C" {
+
+int vc_sharded_search_knn_ids_dev(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t id_flags,
+                                  uint64_t* d_out, uint32_t* d_counts, vc_query_stats* d_stats, void* stream) {
+  const int rc = check_sharded_ids_args(h, d_ids, nq, k, mode, id_flags, d_out);
+  if (rc) return rc;
+  const uint32_t kp = vc_ids_kp(k, id_flags);
+  return sharded_store_call(h, mode, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    VcIdsKnnBufs b;
+    const int r = vc_ids_knn_reserve(v, nq, kp, &b);
+    return r ? r : vc_ids_knn_run(v, b, d_ids, nq, kp, k, d_out, d_counts, d_stats, S, err);
+  });
+}
+
+int vc_sharded_search_knn_ids(vc_sharded* h, const uint32_t* ids, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order,
+                              uint32_t id_flags, uint64_t* out, uint32_t* counts, vc_query_stats* stats) {
+  const int rc = check_sharded_ids_args(h, ids, nq, k, mode, id_flags, out);
+  if (rc) return rc;
+  if (order > VC_ORDER_FARTHEST_FIRST) return VC_ERR_INVALID;
+  const uint32_t kp = vc_ids_kp(k, id_flags);
+  return sharded_store_call(h, mode, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_ids_knn_run_host(v, VcIdsKnnHostArgs{ids, nq, kp, k, order, mode == VC_MODE_LINEAR, out, counts, stats},
+                               [&](const VcIdsKnnBufs& b, const uint32_t* d_ids, uint64_t* d_out, uint32_t* d_counts, vc_query_stats* d_stats) {
+                                 return vc_ids_knn_run(v, b, d_ids, nq, kp, k, d_out, d_counts, d_stats, S, err);
+                               },
+                               [&](const uint64_t* codes, uint64_t* rows, uint32_t* rcnt) {   // (its shards recover on the host)
+                                 return vc_sharded_search_knn(h, codes, nq, kp, mode, VC_ORDER_ASCENDING, rows, rcnt, stats);
+                               },
+                               S, err);
+  });
+}
+
+int vc_sharded_search_radius_ids_dev(vc_sharded* h, const uint32_t* d_ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags,
+                                     uint64_t* d_out, uint64_t out_cap, uint64_t* d_offsets, void* stream) {
+  const int rc = check_sharded_radius_ids_args(h, d_ids, nq, mode, id_flags, d_out, out_cap, d_offsets);
+  if (rc) return rc;
+  return sharded_store_call(h, mode, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_ids_radius_run(v, d_ids, nq, radius, id_flags, d_out, out_cap, d_offsets, S, err);
+  });
+}
+
+int vc_sharded_search_radius_ids(vc_sharded* h, const uint32_t* ids, uint32_t nq, uint32_t radius, uint32_t mode, uint32_t id_flags, uint64_t* out,
+                                 uint64_t out_cap, uint64_t* out_offsets) {
+  const int rc = check_sharded_radius_ids_args(h, ids, nq, mode, id_flags, out, out_cap, out_offsets);
+  if (rc) return rc;
+  return sharded_store_call(h, mode, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_ids_radius_run_host(v, ids, nq, out, out_cap, out_offsets,
+                                  [&](const uint32_t* d_ids, uint64_t* d_out, uint64_t* d_offsets) {
+                                    return vc_ids_radius_run(v, d_ids, nq, radius, id_flags, d_out, out_cap, d_offsets, S, err);
+                                  },
+                                  S, err);
+  });
+}
+
+}  // extern "C"
+
+// ---- the clustering calls over the shards: the drivers of vc_cluster.hip, vc_levels.hip, vc_leaders.hip, vc_dbscan.hip and
+// vc_dbscan_levels.hip on the root, their walk (vc_walk.hip) through the sharded gather and the union's radius search ------------------
 static int check_sharded_cluster_args(vc_sharded* h, const char* what, uint32_t mode, uint64_t n_labelled, const uint32_t* labels) {   // what: "cluster" or "leaders"
   if (!h || !labels || (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT)) return VC_ERR_INVALID;
   if (n_labelled > h->n) return sfail(h, VC_ERR_INVALID, "%s: n_labelled %llu exceeds the %llu resident records", what, (unsigned long long)n_labelled, (unsigned long long)h->n);
@@ -2124,38 +2051,6 @@ static int check_sharded_dbscan_levels_args(vc_sharded* h, uint32_t max_radius, 
   return check_sharded_dbscan_args(h, min_pts, mode, labels);
 }
 
-// The store as the walk sees it: its buffers are the root's, everything the root does goes to S.  The gather and the search visit the
-// other devices and come back with the root current, so the drivers never bind one.
-static VcWalkView sharded_walk_view(vc_sharded* h, uint32_t mode, hipStream_t S) {
-  VcWalkView v;
-  v.n = h->n;
-  v.id_base = h->cfg.engine.id_base;
-  v.W = h->nbytes / 8;
-  v.alloc = [h](int which, size_t bytes) -> void* {
-    DevBuf& b = h->buf[WALK_FIRST + which];
-    return b.grow(h, bytes) ? nullptr : b.p;
-  };
-  v.held = [h](int which) { return h->buf[WALK_FIRST + which].bytes; };
-  v.gather = [h, S](const uint32_t* d_ids, uint32_t nq, uint64_t* d_q, uint32_t* d_found) { return sharded_gather_ids(h, d_ids, nq, d_q, d_found, true, S); };
-  v.search = [h, mode, S](const uint64_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_raw, uint64_t cap, uint64_t* d_roffs, uint64_t* raw_total) -> int {
-    const int rc = sharded_radius_dev(h, d_q, nq, radius, mode, d_raw, cap, d_roffs, S, raw_total);
-    if (rc && rc != VC_ERR_CAPACITY) return rc;
-    VS_HIP(h, hipSetDevice(h->root));
-    return rc;
-  };
-  return v;
-}
-
-// An entry point after its checks, h->n > 0: the root bound, `run` (a vc_*_run or vc_*_run_host) with the view on stream S.
-template <class Run>
-static int sharded_walk_call(vc_sharded* h, uint32_t mode, hipStream_t S, const Run& run) {
-  VS_HIP(h, hipSetDevice(h->root));
-  std::string err;
-  const int rc = run(sharded_walk_view(h, mode, S), S, &err);
-  return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;   // (a closure of the view has left its own text)
-}
-static hipStream_t sharded_caller_stream(const vc_sharded* h, void* stream) { return stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream; }
-
 extern "C" {
 
 int vc_sharded_cluster_radius_dev(vc_sharded* h, uint32_t radius, uint32_t mode, uint32_t batch, uint64_t n_labelled, uint32_t* d_labels,
@@ -2164,7 +2059,7 @@ int vc_sharded_cluster_radius_dev(vc_sharded* h, uint32_t radius, uint32_t mode,
   if (rc) return rc;
   if (stats) *stats = vc_cluster_stats{0, 0};
   if (h->n == 0) return VC_OK;
-  return sharded_walk_call(h, mode, sharded_caller_stream(h, stream), [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+  return sharded_store_call(h, mode, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_cluster_run(v, radius, batch, n_labelled, d_labels, stats, S, err);
   });
 }
@@ -2175,7 +2070,7 @@ int vc_sharded_cluster_radius(vc_sharded* h, uint32_t radius, uint32_t mode, uin
   if (rc) return rc;
   if (stats) *stats = vc_cluster_stats{0, 0};
   if (h->n == 0) return VC_OK;
-  return sharded_walk_call(h, mode, h->root_stream, [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+  return sharded_store_call(h, mode, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_cluster_run_host(v, radius, batch, n_labelled, labels, stats, S, err);
   });
 }
@@ -2186,7 +2081,7 @@ int vc_sharded_cluster_levels_dev(vc_sharded* h, uint32_t max_radius, uint32_t m
   if (rc) return rc;
   if (stats) *stats = vc_levels_stats{};
   if (h->n == 0) return VC_OK;
-  return sharded_walk_call(h, mode, sharded_caller_stream(h, stream), [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+  return sharded_store_call(h, mode, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_levels_run(v, max_radius, batch, n_labelled, d_labels, stats, S, err);
   });
 }
@@ -2197,7 +2092,7 @@ int vc_sharded_cluster_levels(vc_sharded* h, uint32_t max_radius, uint32_t mode,
   if (rc) return rc;
   if (stats) *stats = vc_levels_stats{};
   if (h->n == 0) return VC_OK;
-  return sharded_walk_call(h, mode, h->root_stream, [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+  return sharded_store_call(h, mode, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_levels_run_host(v, max_radius, batch, n_labelled, labels, stats, S, err);
   });
 }
@@ -2208,7 +2103,7 @@ int vc_sharded_leaders_radius_dev(vc_sharded* h, uint32_t radius, uint32_t mode,
   if (rc) return rc;
   if (stats) *stats = vc_leader_stats{0, 0, 0};
   if (h->n == 0) return VC_OK;
-  return sharded_walk_call(h, mode, sharded_caller_stream(h, stream), [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+  return sharded_store_call(h, mode, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_leaders_run(v, radius, batch, n_labelled, d_labels, stats, S, err);
   });
 }
@@ -2219,7 +2114,7 @@ int vc_sharded_leaders_radius(vc_sharded* h, uint32_t radius, uint32_t mode, uin
   if (rc) return rc;
   if (stats) *stats = vc_leader_stats{0, 0, 0};
   if (h->n == 0) return VC_OK;
-  return sharded_walk_call(h, mode, h->root_stream, [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+  return sharded_store_call(h, mode, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_leaders_run_host(v, radius, batch, n_labelled, labels, stats, S, err);
   });
 }
@@ -2230,7 +2125,7 @@ int vc_sharded_dbscan_radius_dev(vc_sharded* h, uint32_t radius, uint32_t min_pt
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_stats{0, 0, 0, 0, 0};
   if (h->n == 0) return VC_OK;
-  return sharded_walk_call(h, mode, sharded_caller_stream(h, stream), [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+  return sharded_store_call(h, mode, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_dbscan_run(v, radius, min_pts, batch, d_labels, d_degrees, stats, S, err);
   });
 }
@@ -2241,7 +2136,7 @@ int vc_sharded_dbscan_radius(vc_sharded* h, uint32_t radius, uint32_t min_pts, u
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_stats{0, 0, 0, 0, 0};
   if (h->n == 0) return VC_OK;
-  return sharded_walk_call(h, mode, h->root_stream, [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+  return sharded_store_call(h, mode, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_dbscan_run_host(v, radius, min_pts, batch, labels, degrees, stats, S, err);
   });
 }
@@ -2252,7 +2147,7 @@ int vc_sharded_dbscan_levels_dev(vc_sharded* h, uint32_t max_radius, uint32_t mi
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_levels_stats{};
   if (h->n == 0) return VC_OK;
-  return sharded_walk_call(h, mode, sharded_caller_stream(h, stream), [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+  return sharded_store_call(h, mode, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_dbscan_levels_run(v, max_radius, min_pts, batch, d_labels, d_core_dist, stats, S, err);
   });
 }
@@ -2263,7 +2158,7 @@ int vc_sharded_dbscan_levels(vc_sharded* h, uint32_t max_radius, uint32_t min_pt
   if (rc) return rc;
   if (stats) *stats = vc_dbscan_levels_stats{};
   if (h->n == 0) return VC_OK;
-  return sharded_walk_call(h, mode, h->root_stream, [&](const VcWalkView& v, hipStream_t S, std::string* err) {
+  return sharded_store_call(h, mode, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_dbscan_levels_run_host(v, max_radius, min_pts, batch, labels, core_dist, stats, S, err);
   });
 }
@@ -2277,10 +2172,7 @@ static VcGroupsFetch sharded_groups_fetch(vc_sharded* h, hipStream_t S) {
 static VcGroupsArgs sharded_groups_args(vc_sharded* h, const uint32_t* d_labels, uint64_t groups_cap, vc_group* d_groups, void* d_centroids,
                                         uint32_t* d_rep_labels, uint32_t* d_group_index) {
   return VcGroupsArgs{h->n, h->cfg.engine.id_base, h->nbytes / 8, h->knobs.group_window, d_labels, groups_cap, d_groups, (uint64_t*)d_centroids, d_rep_labels,
-                      d_group_index, [h](int which, size_t bytes) -> void* {   // (the root device is current wherever the driver allocates)
-                        DevBuf& b = h->buf[GRP_SCRATCH + which];
-                        return b.grow(h, bytes) ? nullptr : b.p;
-                      }};
+                      d_group_index, sharded_scratch_alloc(h)};
 }
 
 extern "C" {
@@ -2290,7 +2182,7 @@ int vc_sharded_group_summary_dev(vc_sharded* h, const uint32_t* d_labels, uint64
   if (!h || (!d_labels && h->n) || (!d_groups && groups_cap)) return VC_ERR_INVALID;
   if (n_groups) *n_groups = 0;
   if (h->n == 0) return VC_OK;
-  hipStream_t S = stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream;
+  hipStream_t S = sharded_caller_stream(h, stream);
   VS_HIP(h, hipSetDevice(h->root));
   std::string err;
   const int rc = vc_groups_run(sharded_groups_args(h, d_labels, groups_cap, d_groups, d_centroids, d_rep_labels, d_group_index), sharded_groups_fetch(h, S),
@@ -2322,12 +2214,6 @@ static int check_sharded_kmajority_args(vc_sharded* h, uint32_t n_centres, uint3
   if (!h || !centres || !assign || n_centres == 0 || (h->n && n_centres > h->n) || max_iters > VC_KMAJ_MAX_ITERS) return VC_ERR_INVALID;
   return VC_OK;
 }
-static std::function<void*(int, size_t)> sharded_kmaj_alloc(vc_sharded* h) {
-  return [h](int which, size_t bytes) -> void* {   // (the root device is current wherever the driver allocates)
-    DevBuf& b = h->buf[KM_WORK + which];
-    return b.grow(h, bytes) ? nullptr : b.p;
-  };
-}
 
 // d_centres / d_out on the root device, valid on S; count > 0.  All enqueued, nothing waited for: the centres reach every other lane
 // by one peer copy behind ev_q, every non-empty shard assigns the part of [first, first + count) it owns on its own device -- a
@@ -2352,7 +2238,7 @@ static int sharded_assign_range(vc_sharded* h, const uint64_t* d_centres, uint32
     if (!words) continue;
     remote = true;
     VS_HIP(h, hipSetDevice(l.dev));
-    if ((rc = l.buf[LANE_ACENT].grow(h, cbytes)) || (rc = l.buf[LANE_AOUT].grow(h, (size_t)words * 8))) return rc;
+    if ((rc = grow(h, l.buf[LANE_ACENT], cbytes)) || (rc = grow(h, l.buf[LANE_AOUT], (size_t)words * 8))) return rc;
   }
   VS_HIP(h, hipSetDevice(h->root));
   if (remote) VS_HIP(h, hipEventRecord(h->ev_q, S));
@@ -2406,7 +2292,7 @@ int vc_sharded_assign_nearest_dev(vc_sharded* h, const void* d_centres, uint32_t
                                   void* stream) {
   const int rc = check_sharded_assign_args(h, d_centres, n_centres, first, count, d_out);
   if (rc || count == 0) return rc;
-  return sharded_assign_range(h, (const uint64_t*)d_centres, n_centres, first, count, d_out, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+  return sharded_assign_range(h, (const uint64_t*)d_centres, n_centres, first, count, d_out, sharded_caller_stream(h, stream));
 }
 
 int vc_sharded_assign_nearest(vc_sharded* h, const void* centres, uint32_t n_centres, uint64_t first, uint64_t count, uint64_t* out) {
@@ -2415,7 +2301,7 @@ int vc_sharded_assign_nearest(vc_sharded* h, const void* centres, uint32_t n_cen
   hipStream_t S = h->root_stream;
   VS_HIP(h, hipSetDevice(h->root));
   std::string err;
-  rc = vc_assign_run_host(sharded_kmaj_alloc(h), h->nbytes / 8, centres, n_centres, count, out, sharded_assign_all(h, n_centres, first, count, S), S, &err);
+  rc = vc_assign_run_host(sharded_scratch_alloc(h), h->nbytes / 8, centres, n_centres, count, out, sharded_assign_all(h, n_centres, first, count, S), S, &err);
   return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
 }
 
@@ -2425,10 +2311,10 @@ int vc_sharded_kmajority_dev(vc_sharded* h, uint32_t n_centres, uint32_t max_ite
   if (rc) return rc;
   if (stats) *stats = vc_kmajority_stats{};
   if (h->n == 0) return VC_OK;
-  hipStream_t S = stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream;
+  hipStream_t S = sharded_caller_stream(h, stream);
   VS_HIP(h, hipSetDevice(h->root));
   std::string err;
-  rc = vc_kmajority_run(VcKmajArgs{n_centres, max_iters, (uint64_t*)d_centres, d_assign, d_labels, sharded_kmaj_alloc(h)},
+  rc = vc_kmajority_run(VcKmajArgs{n_centres, max_iters, (uint64_t*)d_centres, d_assign, d_labels, sharded_scratch_alloc(h)},
                         sharded_groups_args(h, nullptr, 0, nullptr, nullptr, nullptr, nullptr), sharded_assign_all(h, n_centres, 0, h->n, S),
                         sharded_groups_fetch(h, S), stats, S, &err);
   return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
@@ -2443,7 +2329,7 @@ int vc_sharded_kmajority(vc_sharded* h, uint32_t n_centres, uint32_t max_iters, 
   hipStream_t S = h->root_stream;
   VS_HIP(h, hipSetDevice(h->root));
   std::string err;
-  rc = vc_kmajority_run_host(VcKmajArgs{n_centres, max_iters, nullptr, nullptr, nullptr, sharded_kmaj_alloc(h)},
+  rc = vc_kmajority_run_host(VcKmajArgs{n_centres, max_iters, nullptr, nullptr, nullptr, sharded_scratch_alloc(h)},
                              sharded_groups_args(h, nullptr, 0, nullptr, nullptr, nullptr, nullptr), sharded_assign_all(h, n_centres, 0, h->n, S),
                              sharded_groups_fetch(h, S), centres, assign, labels, stats, S, &err);
   return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
@@ -2455,12 +2341,6 @@ int vc_sharded_kmajority(vc_sharded* h, uint32_t n_centres, uint32_t max_iters, 
 static int check_sharded_seed_args(vc_sharded* h, uint32_t n_centres, uint32_t method, const void* centres) {
   if (!h || !centres || n_centres == 0 || (h->n && n_centres > h->n) || (method != VC_SEED_FARTHEST && method != VC_SEED_WEIGHTED)) return VC_ERR_INVALID;
   return VC_OK;
-}
-static std::function<void*(int, size_t)> sharded_seed_alloc(vc_sharded* h) {
-  return [h](int which, size_t bytes) -> void* {   // (the root device is current wherever the driver allocates)
-    DevBuf& b = h->buf[SD_WORK + which];
-    return b.grow(h, bytes) ? nullptr : b.p;
-  };
 }
 
 namespace {
@@ -2487,8 +2367,8 @@ static int sharded_seed_run(vc_sharded* h, uint32_t K, uint32_t method, uint64_t
   const uint64_t N = h->n;
   int rc;
   VS_HIP(h, hipSetDevice(h->root));
-  DevBuf& rb = h->buf[SD_WORK];   // the id word | the two statistics words | best [N] unless d_assign holds it
-  if ((rc = rb.grow(h, 24 + (d_assign ? 0 : (size_t)N * 8)))) return rc;
+  DevBuf& rb = h->buf[SCRATCH + VC_SEED_WORK];   // the id word | the two statistics words | best [N] unless d_assign holds it
+  if ((rc = grow(h, rb, 24 + (d_assign ? 0 : (size_t)N * 8)))) return rc;
   uint32_t* d_id = rb.as<uint32_t>();
   uint64_t* d_stat = rb.as<uint64_t>() + 1;
   uint64_t* best = d_assign ? d_assign : rb.as<uint64_t>() + 3;
@@ -2505,8 +2385,8 @@ static int sharded_seed_run(vc_sharded* h, uint32_t K, uint32_t method, uint64_t
     }
     if (!words) continue;
     VS_HIP(h, hipSetDevice(l.dev));
-    if ((rc = l.buf[LANE_SWORK].grow(h, (size_t)words * 8))) return rc;
-    if (!is_root && ((rc = l.buf[LANE_SCODE].grow(h, (size_t)W * 8)) || (rc = l.buf[LANE_SBEST].grow(h, (size_t)recs * 8)))) return rc;
+    if ((rc = grow(h, l.buf[LANE_SWORK], (size_t)words * 8))) return rc;
+    if (!is_root && ((rc = grow(h, l.buf[LANE_SCODE], (size_t)W * 8)) || (rc = grow(h, l.buf[LANE_SBEST], (size_t)recs * 8)))) return rc;
     remote |= !is_root;
     uint64_t at_w = 0, at_r = 0;
     for (uint32_t g : l.shards) {
@@ -2642,7 +2522,7 @@ int vc_sharded_seed_centres_dev(vc_sharded* h, uint32_t n_centres, uint32_t meth
   if (rc) return rc;
   if (stats) *stats = vc_seed_stats{};
   if (h->n == 0) return VC_OK;
-  return sharded_seed_run(h, n_centres, method, seed, (uint64_t*)d_centres, d_picks, d_assign, stats, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+  return sharded_seed_run(h, n_centres, method, seed, (uint64_t*)d_centres, d_picks, d_assign, stats, sharded_caller_stream(h, stream));
 }
 
 int vc_sharded_seed_centres(vc_sharded* h, uint32_t n_centres, uint32_t method, uint64_t seed, void* centres, uint64_t* picks, uint64_t* assign,
@@ -2654,7 +2534,7 @@ int vc_sharded_seed_centres(vc_sharded* h, uint32_t n_centres, uint32_t method, 
   hipStream_t S = h->root_stream;
   VS_HIP(h, hipSetDevice(h->root));
   std::string err;
-  rc = vc_seed_run_host(VcSeedHostArgs{h->n, h->nbytes / 8, n_centres, centres, picks, assign, stats, sharded_seed_alloc(h)},
+  rc = vc_seed_run_host(VcSeedHostArgs{h->n, h->nbytes / 8, n_centres, centres, picks, assign, stats, sharded_scratch_alloc(h)},
                         [&](uint64_t* d_centres, uint64_t* d_picks, uint64_t* d_assign, vc_seed_stats* st) {
                           return sharded_seed_run(h, n_centres, method, seed, d_centres, d_picks, d_assign, st, S);
                         },
@@ -2670,17 +2550,7 @@ static int check_sharded_distinct_args(vc_sharded* h, const void* q, uint32_t nq
   if (!h || !q || !labels || !out || nq == 0 || k == 0 || k > VC_MAX_K) return VC_ERR_INVALID;
   if (!vc_distinct_k_first_ok(k, k_first)) return sfail(h, VC_ERR_INVALID, "k_first must be 0 or in k..%u", VC_MAX_K);
   if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return sfail(h, VC_ERR_INVALID, "distinct search: mode must be LINEAR or MIH_EXACT");
-  if (mode == VC_MODE_MIH_EXACT)
-    for (uint32_t g = 0; g < h->G; ++g)
-      if (shard_size(h, g) && !vc_engine_has_index(h->eng[g])) return sfail(h, VC_ERR_STATE, "shard %u: MIH search needs vc_sharded_build_index() first", g);
-  return VC_OK;
-}
-static std::function<void*(int, size_t)> sharded_distinct_alloc(vc_sharded* h) {
-  return [h](int which, size_t bytes) -> void* {   // (the search underneath leaves the root device current)
-    if (hipSetDevice(h->root) != hipSuccess) return nullptr;
-    DevBuf& b = h->buf[DS_WORK + which];
-    return b.grow(h, bytes) ? nullptr : b.p;
-  };
+  return check_sharded_index(h, mode);
 }
 // All pointers on the root device, valid on S: the merged rows of the store's search are collapsed where the caller's labels live
 static int sharded_distinct_run(vc_sharded* h, const uint64_t* d_queries, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* d_labels, uint32_t k_first,
@@ -2688,12 +2558,8 @@ static int sharded_distinct_run(vc_sharded* h, const uint64_t* d_queries, uint32
   VS_HIP(h, hipSetDevice(h->root));
   std::string err;
   const int rc = vc_distinct_run(VcDistinctArgs{h->n, h->cfg.engine.id_base, h->nbytes / 8, d_queries, nq, k, k_first, d_labels, d_out, d_row_labels, d_counts,
-                                                h->knobs.distinct_scratch, mode == VC_MODE_MIH_EXACT, sharded_distinct_alloc(h)},
-                                 [&](const uint64_t* d_q, uint32_t n, uint32_t kp, uint64_t* d_rows, uint32_t* d_cnt) {
-                                   const int r = sharded_search_any(h, d_q, n, kp, mode, d_rows, d_cnt, nullptr, S);
-                                   if (r) return r;
-                                   return hipSetDevice(h->root) == hipSuccess ? VC_OK : sfail(h, VC_ERR_HIP, "hipSetDevice(root) failed");
-                                 },
+                                                h->knobs.distinct_scratch, mode == VC_MODE_MIH_EXACT, sharded_scratch_alloc(h)},
+                                 sharded_store_view(h, mode, S).knn,
                                  stats, S, &err);
   return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
 }
@@ -2705,7 +2571,7 @@ int vc_sharded_search_knn_distinct_dev(vc_sharded* h, const void* d_queries, uin
   const int rc = check_sharded_distinct_args(h, d_queries, nq, k, mode, d_labels, k_first, d_out);
   if (rc) return rc;
   return sharded_distinct_run(h, (const uint64_t*)d_queries, nq, k, mode, d_labels, k_first, d_out, d_row_labels, d_counts, stats,
-                              stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+                              sharded_caller_stream(h, stream));
 }
 
 int vc_sharded_search_knn_distinct(vc_sharded* h, const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* labels,
@@ -2716,7 +2582,7 @@ int vc_sharded_search_knn_distinct(vc_sharded* h, const void* queries, uint32_t 
   hipStream_t S = h->root_stream;
   VS_HIP(h, hipSetDevice(h->root));
   std::string err;
-  rc = vc_distinct_run_host(VcDistinctHostArgs{h->n, h->nbytes / 8, nq, k, order, queries, labels, out, row_labels, counts, stats, sharded_distinct_alloc(h)},
+  rc = vc_distinct_run_host(VcDistinctHostArgs{h->n, h->nbytes / 8, nq, k, order, queries, labels, out, row_labels, counts, stats, sharded_scratch_alloc(h)},
                             [&](const uint64_t* d_q, const uint32_t* d_labels, uint64_t* d_out, uint32_t* d_rl, uint32_t* d_cnt, vc_distinct_stats* st) {
                               return sharded_distinct_run(h, d_q, nq, k, mode, d_labels, k_first, d_out, d_rl, d_cnt, st, S);
                             },
@@ -2774,7 +2640,7 @@ static int sharded_retain_run(vc_sharded* h, const uint32_t* d_sel, uint32_t kin
       VS_HIP(h, hipSetDevice(h->dev[g]));
       ScopedBufs<2> tmp;
       hipStream_t L = stream_of(g);
-      if ((rc = tmp.b[0].grow(h, ng * 4)) || (map_g && (rc = tmp.b[1].grow(h, ng * 4)))) return rc;
+      if ((rc = grow(h, tmp.b[0], ng * 4)) || (map_g && (rc = grow(h, tmp.b[1], ng * 4)))) return rc;
       VS_HIP(h, hipMemcpyPeerAsync(tmp.b[0].p, h->dev[g], sel_g, h->root, ng * 4, L));
       rc = vc_retain_dev(h->eng[g], tmp.b[0].as<uint32_t>(), kind, map_g ? tmp.b[1].as<uint32_t>() : nullptr, &cur[g], L);
       if (rc == VC_OK && map_g) VS_HIP(h, hipMemcpyPeerAsync(map_g, h->root, tmp.b[1].p, h->dev[g], ng * 4, L));
@@ -2838,7 +2704,7 @@ int vc_sharded_retain_dev(vc_sharded* h, const uint32_t* d_sel, uint32_t kind, u
     if (n_kept) *n_kept = 0;
     return VC_OK;
   }
-  return sharded_retain_run(h, d_sel, kind, d_new_ids, n_kept, stream == VC_STREAM_OWN ? h->root_stream : (hipStream_t)stream);
+  return sharded_retain_run(h, d_sel, kind, d_new_ids, n_kept, sharded_caller_stream(h, stream));
 }
 
 int vc_sharded_retain(vc_sharded* h, const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) {
@@ -2852,7 +2718,7 @@ int vc_sharded_retain(vc_sharded* h, const uint32_t* sel, uint32_t kind, uint32_
   hipStream_t S = h->root_stream;
   VS_HIP(h, hipSetDevice(h->root));
   ScopedBufs<2> tmp;   // staged selection and map: call-scoped
-  if ((rc = tmp.b[0].grow(h, N * 4)) || (new_ids && (rc = tmp.b[1].grow(h, N * 4)))) return rc;
+  if ((rc = grow(h, tmp.b[0], N * 4)) || (new_ids && (rc = grow(h, tmp.b[1], N * 4)))) return rc;
   VS_HIP(h, hipMemcpyAsync(tmp.b[0].p, sel, N * 4, hipMemcpyHostToDevice, S));
   rc = sharded_retain_run(h, tmp.b[0].as<uint32_t>(), kind, new_ids ? tmp.b[1].as<uint32_t>() : nullptr, n_kept, S);
   (void)hipSetDevice(h->root);   // (the buffers are released on the device they live on)
