@@ -847,6 +847,76 @@ int vc_search_knn_distinct(vc_engine* e, const void* queries, uint32_t nq, uint3
                            const uint32_t* labels, uint32_t k_first, uint64_t* out, uint32_t* row_labels, uint32_t* counts,
                            vc_distinct_stats* stats);
 
+/* ---- k-NN among the records a filter allows: vc_search_knn_filtered* --------------------------------------------------------------------
+ * "The k nearest among the records I allow": search only among the leaders or representatives of a grouper without cutting the
+ * store down with vc_retain*; inside one album, class or cluster, or everywhere but in it; under a caller's keep mask (tombstones,
+ * tenants, a date range computed elsewhere).  The reference has no such call; the host loop it would take -- search with a guessed
+ * larger k, copy rows home, filter, repeat -- runs into VC_MAX_K for a selective filter and then has no exact answer at all.
+ * THE FILTER is shared by all queries of the call (a filter per query is out of scope).  Record i has global id id_base + i:
+ *   VC_FILTER_MASK       sel[i] != 0                                                         N words
+ *   VC_FILTER_ROOTS      sel[i] == id_base + i (a grouper's labels: one representative per   N words
+ *                        group, as VC_RETAIN_ROOTS)
+ *   VC_FILTER_EQUAL      sel[i] == value                                                     N words
+ *   VC_FILTER_NOT_EQUAL  sel[i] != value                                                     N words
+ *   VC_FILTER_BITS       bit i & 31 of sel[i >> 5]                                           ceil(N / 32) words; the bits of the last
+ *                                                                                            word past N are ignored
+ * `value` is read only by EQUAL and NOT_EQUAL.  Every 32-bit value is legal in sel and in value; nothing is validated but the kind.
+ * THE RULE.  Row q holds the k smallest packed (dist << 32 | id) over the ALLOWED records, ascending, padded with UINT64_MAX;
+ * counts[q] = min(k, A), A the number of allowed records.  Ties go to the smaller id: the linear scan's order.  Every output word
+ * is a function of the codes, the filter and the call: not of mode, k_first, the route taken, the environment knobs below or what
+ * earlier calls left in the handle.  There is no truncation flag: the call is exact for every A from 0 to N.  A count of UINT32_MAX
+ * from the search underneath (its ring-overflow recovery gave up, see vc_device_status) is passed on as in vc_search_knn_distinct*.
+ * MODES.  VC_MODE_LINEAR and VC_MODE_MIH_EXACT.  VC_MODE_MIH_APPROX is refused, and so is VC_MODE_MIH_EXACT on a handle with
+ * VC_FLAG_REF_SIGNEXT_KEYS, or with VC_FLAG_REF_STOP_LITERAL4 at n_tables < 4: the rows underneath are not the true nearest
+ * records there, so the result would depend on the route.
+ * HOW.  sel becomes a bit per record and a rank directory (the keep set of vc_retain*); one host wait fetches A.  Then one of
+ *   the POST-FILTER route (dense filters; keeps the speed of the index): rounds as in vc_search_knn_distinct* -- the UNCHANGED search
+ *     at k' for the open queries, a strip kernel keeps the allowed entries of each row (under exact MIH only below the row's last
+ *     distance, the sure prefix).  A query is finished with k kept entries or a row that was not full; else k' doubles up to
+ *     VC_MAX_K, and a query still open there goes to the other route.  k_first sets k'_0; 0 means clamp(2 ceil(k N / A), k, VC_MAX_K).
+ *     One host wait per round.
+ *   the PRE-FILTER route (sparse filters, and the fallback): the allowed ids are listed ascending and taken in windows of
+ *     VC_FILTER_WINDOW ids (default 2^20); a window's codes are gathered by id and scanned by brute force -- a histogram of the
+ *     distances gives the k-th distance of every query, a count and a place walk put exactly the min(k, n) smallest (distance, id)
+ *     into the row -- and the rows of further windows are merged in.  Exact for every A, no waits.
+ * The plan takes the post-filter route when 2 ceil(k N / A) <= VC_FILTER_POST_MAX_K (vc_filter_plan.hpp), else the pre-filter route
+ * answers the whole batch.  Environment, read once at vc_create: VC_FILTER_ROUTE (0 the plan's, 1 post-filter first, 2 pre-filter
+ * only; tests and A/B runs), VC_FILTER_SCRATCH (bytes per sub-batch of k' rows and of per-slice counters, default 64 MiB, always
+ * at least one query), VC_FILTER_WINDOW.
+ * OUTPUT: d_out nq * k packed; d_counts (nq, may be NULL); stats (HOST memory in both forms, may be NULL).
+ * ERRORS, checked before any work, outputs and stats untouched: VC_ERR_INVALID for a null handle, queries, sel or out, nq == 0, k
+ * outside 1 .. VC_MAX_K, a bad k_first (0, or k .. VC_MAX_K), an unknown kind or mode, a refused mode, a bad order (host form);
+ * VC_ERR_STATE in MIH mode without a current index (a stale one counts as none).  N == 0 gives VC_OK with counts 0, padded rows and
+ * zero stats.
+ * Scratch: grow-only buffers of the handle, this call's own; every word is written before it is read. */
+#define VC_FILTER_MASK 0u
+#define VC_FILTER_ROOTS 1u
+#define VC_FILTER_EQUAL 2u
+#define VC_FILTER_NOT_EQUAL 3u
+#define VC_FILTER_BITS 4u
+#define VC_FILTER_RAN_POST 1u
+#define VC_FILTER_RAN_PRE 2u
+typedef struct vc_filter_stats {   /* 48 bytes */
+  uint64_t n_allowed;   /* A */
+  uint32_t routes;      /* VC_FILTER_RAN_POST 1 | VC_FILTER_RAN_PRE 2 */
+  uint32_t n_rounds;    /* post-filter search rounds run */
+  uint32_t k_last;      /* k' of the last round, 0 without one */
+  uint32_t n_windows;   /* subset windows scanned by the pre-filter route (per sub-batch of queries) */
+  uint64_t n_searched;  /* queries summed over post-filter rounds */
+  uint64_t n_fallback;  /* queries the post-filter rounds handed to the pre-filter route */
+  uint64_t n_short;     /* queries with count < k (A < k) */
+} vc_filter_stats;
+int vc_search_knn_filtered_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* d_sel,
+                               uint32_t kind, uint32_t value, uint32_t k_first, uint64_t* d_out, uint32_t* d_counts,
+                               vc_filter_stats* stats, void* stream);
+/* The same for queries, sel and results in host memory: queries and sel are staged on the engine's stream ON EVERY CALL, the device
+ * form runs into staged outputs, which come home; waits for them.  order as vc_search_knn: VC_ORDER_FARTHEST_FIRST reverses the
+ * valid part of every row.  Callers who search repeatedly should keep sel in HBM, preferably as VC_FILTER_BITS (N / 8 bytes), and
+ * use the device form. */
+int vc_search_knn_filtered(vc_engine* e, const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order,
+                           const uint32_t* sel, uint32_t kind, uint32_t value, uint32_t k_first, uint64_t* out, uint32_t* counts,
+                           vc_filter_stats* stats);
+
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
  * seconds); the affected queries kept d_counts[i] == UINT32_MAX.  0 in normal operation.  Synchronises the stream.
@@ -1096,6 +1166,17 @@ int vc_get_timing(const vc_engine* e, vc_timing* t);
  * after the first shard has changed leaves shards that are no longer filled in id order -- destroy the handle then. */
 int vc_sharded_retain_dev(vc_sharded* h, const uint32_t* d_sel, uint32_t kind, uint32_t* d_new_ids, uint64_t* n_kept, void* stream);
 int vc_sharded_retain(vc_sharded* h, const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept);
+
+/* k-NN among the allowed records over all shards: filter, rule, modes, outputs, errors, routes and waits as
+ * vc_search_knn_filtered_dev / vc_search_knn_filtered with N = vc_sharded_size and ids global over the whole store.  Every pointer of
+ * the device form lives on the ROOT device; the keep set and every pass run there, the shards are reached only through the store's
+ * own search and its gather by id.  The flags that refuse VC_MODE_MIH_EXACT are those of vc_sharded_config.engine. */
+int vc_sharded_search_knn_filtered_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* d_sel,
+                                       uint32_t kind, uint32_t value, uint32_t k_first, uint64_t* d_out, uint32_t* d_counts,
+                                       vc_filter_stats* stats, void* stream);
+int vc_sharded_search_knn_filtered(vc_sharded* h, const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order,
+                                   const uint32_t* sel, uint32_t kind, uint32_t value, uint32_t k_first, uint64_t* out, uint32_t* counts,
+                                   vc_filter_stats* stats);
 
 /* Stream of the host-pointer calls (default VC_STREAM_OWN). */
 int vc_set_stream(vc_engine* e, void* stream);

@@ -12,6 +12,7 @@
 #include <functional>
 
 #include "vc_distinct_plan.hpp"
+#include "vc_filter_plan.hpp"
 #include "vc_groups_plan.hpp"
 #include "vc_internal.hpp"
 #include "vc_mih.hpp"
@@ -157,6 +158,9 @@ void read_knobs(VcKnobs* k) {
   if (const char* v = getenv("VC_ASSIGN_TILE")) k->assign_tile = (uint32_t)strtoul(v, nullptr, 10);
   if (const char* v = getenv("VC_ASSIGN_SLICES")) k->assign_slices = (uint32_t)strtoul(v, nullptr, 10);
   if (const char* v = getenv("VC_DISTINCT_SCRATCH")) k->distinct_scratch = strtoull(v, nullptr, 10);
+  if (const char* v = getenv("VC_FILTER_ROUTE")) k->filter_route = (uint32_t)strtoul(v, nullptr, 10);
+  if (const char* v = getenv("VC_FILTER_SCRATCH")) k->filter_scratch = strtoull(v, nullptr, 10);
+  if (const char* v = getenv("VC_FILTER_WINDOW")) k->filter_window = (uint32_t)strtoul(v, nullptr, 10);
 }
 
 static int bind_device(vc_engine* e) {
@@ -1522,6 +1526,53 @@ int vc_search_knn_distinct(vc_engine* e, const void* queries, uint32_t nq, uint3
                             },
                             e->stream, &err);
   return driver_done(e, rc, err);
+}
+
+}  // extern "C"
+
+// ---- k-NN among the allowed records (vc_filter.hip) -----------------------------------------------------------------------------------
+static int check_filter_args(vc_engine* e, const void* q, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* sel, uint32_t kind, uint32_t k_first,
+                             const uint64_t* out) {
+  if (!e || !q || !sel || !out || nq == 0) return VC_ERR_INVALID;
+  if (k == 0 || k > VC_MAX_K) return fail(e, VC_ERR_INVALID, "k must be in 1..%u", VC_MAX_K);
+  if (!vc_distinct_k_first_ok(k, k_first)) return fail(e, VC_ERR_INVALID, "k_first must be 0 or in k..%u", VC_MAX_K);
+  if (kind >= VC_FILTER_KINDS) return fail(e, VC_ERR_INVALID, "filtered search: unknown kind %u", kind);
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "filtered search: mode must be LINEAR or MIH_EXACT");
+  if (mode == VC_MODE_MIH_EXACT && ((e->cfg.flags & VC_FLAG_REF_SIGNEXT_KEYS) || ((e->cfg.flags & VC_FLAG_REF_STOP_LITERAL4) && e->m < 4)))
+    return fail(e, VC_ERR_INVALID, "filtered search: MIH_EXACT rows are not the true nearest records under this handle's reference flags");
+  if (mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first (n_tables=%u)", e->m);
+  return VC_OK;
+}
+static VcFilterArgs filter_args(vc_engine* e, const uint64_t* d_queries, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* d_sel, uint32_t kind,
+                                uint32_t value, uint32_t k_first, uint64_t* d_out, uint32_t* d_counts) {
+  return VcFilterArgs{d_queries, nq, k, k_first, d_sel, kind, value, e->W * 64u, d_out, d_counts, e->knobs.filter_scratch, e->knobs.filter_window,
+                      e->knobs.filter_route, mode == VC_MODE_MIH_EXACT};
+}
+
+extern "C" {
+
+int vc_search_knn_filtered_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* d_sel, uint32_t kind, uint32_t value,
+                               uint32_t k_first, uint64_t* d_out, uint32_t* d_counts, vc_filter_stats* stats, void* stream) {
+  const int rc = check_filter_args(e, d_queries, nq, k, mode, d_sel, kind, k_first, d_out);
+  if (rc) return rc;
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_filter_run(store_view(e, mode), filter_args(e, (const uint64_t*)d_queries, nq, k, mode, d_sel, kind, value, k_first, d_out, d_counts), stats, s, err);
+  });
+}
+
+int vc_search_knn_filtered(vc_engine* e, const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* sel, uint32_t kind,
+                           uint32_t value, uint32_t k_first, uint64_t* out, uint32_t* counts, vc_filter_stats* stats) {
+  const int rc = check_filter_args(e, queries, nq, k, mode, sel, kind, k_first, out);
+  if (rc) return rc;
+  if (order > VC_ORDER_FARTHEST_FIRST) return VC_ERR_INVALID;
+  return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    const VcStoreView v = store_view(e, mode);
+    return vc_filter_run_host(v, VcFilterHostArgs{nq, k, order, kind, queries, sel, out, counts},
+                              [&](const uint64_t* d_q, const uint32_t* d_sel, uint64_t* d_out, uint32_t* d_cnt) {
+                                return vc_filter_run(v, filter_args(e, d_q, nq, k, mode, d_sel, kind, value, k_first, d_out, d_cnt), stats, s, err);
+                              },
+                              s, err);
+  });
 }
 
 }  // extern "C"

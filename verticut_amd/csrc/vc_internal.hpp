@@ -48,6 +48,9 @@ struct VcKnobs {
   uint32_t assign_tile = 0;                   // VC_ASSIGN_TILE (tests): centres per LDS tile of vc_assign_kernel (0 = all that fit, vc_assign_plan.hpp)
   uint32_t assign_slices = 0;                 // VC_ASSIGN_SLICES (tests): forces the number of centre slices of a vc_assign_kernel launch (0 = the plan's)
   uint64_t distinct_scratch = 64ull << 20;    // VC_DISTINCT_SCRATCH: bytes of k' rows a sub-batch of vc_search_knn_distinct* may hold (vc_distinct_plan.hpp)
+  uint32_t filter_route = 0;                  // VC_FILTER_ROUTE (tests, A/B runs): 0 the plan's route of vc_search_knn_filtered*, 1 post-filter first, 2 pre-filter only
+  uint64_t filter_scratch = 64ull << 20;      // VC_FILTER_SCRATCH: bytes of k' rows / of per-slice counters a sub-batch of vc_search_knn_filtered* may hold (vc_filter_plan.hpp)
+  uint32_t filter_window = 1u << 20;          // VC_FILTER_WINDOW: allowed ids per window of the pre-filter route (0 or above 2^24: the default)
 };
 void read_knobs(VcKnobs* k);   // vc_engine.hip: the one place that reads the environment (once per engine / sharded handle)
 
@@ -191,6 +194,9 @@ enum VcScratch {
   // radius search by id (vc_ids_radius.hip): gathered queries, found words, the uncompacted results and offsets of the search underneath,
   // the compaction's counts (VcIdsRadiusWork); the host form's staged ids, results and offsets
   VC_RIDS_Q, VC_RIDS_FOUND, VC_RIDS_RAW, VC_RIDS_ROFFS, VC_RIDS_WORK, VC_RIDS_HIDS, VC_RIDS_HOUT, VC_RIDS_HOFFS,
+  // filtered k-NN (vc_filter.hip): the keep set (bits, rank, scan work); the rounds' flags, maps and listed queries; the k' rows; the
+  // pre-filter route's arrays of a window and a sub-batch; a window's gathered codes; the host forms' staging
+  VC_FILTER_KEEP, VC_FILTER_WORK, VC_FILTER_ROWS, VC_FILTER_PRE, VC_FILTER_CODES, VC_FILTER_STAGE,
   VC_SCRATCH_BUFS
 };
 // buffer `which` of the handle's table, at least `bytes` large, on the current device; null when it cannot be had (the handle keeps the text)
@@ -553,6 +559,35 @@ struct VcDistinctHostArgs {
 int vc_distinct_run_host(const VcDistinctHostArgs& a, const std::function<int(const uint64_t* d_queries, const uint32_t* d_labels, uint64_t* d_out,
                                                                             uint32_t* d_row_labels, uint32_t* d_counts, vc_distinct_stats* stats)>& run,
                          hipStream_t s, std::string* err);
+// ---- vc_filter.hip: k-NN among the allowed records (vc_search_knn_filtered*, vc_sharded_search_knn_filtered*).  One driver for both
+// handle kinds over the view's knn, gather and alloc; the plan arithmetic -- the route, the k' schedule, the verdict on a row, the
+// sub-batches, the windows and wave-slices of the subset scan, the cut of a histogram -- is vc_filter_plan.hpp.
+struct VcFilterArgs {
+  const uint64_t* d_queries;       // [nq][W]
+  uint32_t nq, k, k_first;         // checked by the caller: nq > 0, 1 <= k <= VC_MAX_K, vc_distinct_k_first_ok
+  const uint32_t* d_sel;           // N words, ceil(N / 32) for VC_FILTER_BITS
+  uint32_t kind, value;            // checked by the caller: a known kind
+  uint32_t bits;                   // the code width, 64 W
+  uint64_t* d_out;                 // [nq][k]
+  uint32_t* d_counts;              // [nq], nullable
+  uint64_t budget;                 // VcKnobs::filter_scratch
+  uint32_t window, route;          // VcKnobs::filter_window, filter_route
+  bool tie_cut;                    // the search underneath is exact MIH: its rows are sure only below their last distance (vc_filter_sure_below)
+};
+// the whole call on s with the device of the buffers current: one wait for A, one per post-filter round; stats (host memory) nullable
+int vc_filter_run(const VcStoreView& v, const VcFilterArgs& a, vc_filter_stats* stats, hipStream_t s, std::string* err);
+// either handle's host form: queries and sel staged, `run` (the device form on s) into staged outputs, which come home; waits for
+// them, then turns the valid part of every row round for VC_ORDER_FARTHEST_FIRST.  counts nullable
+struct VcFilterHostArgs {
+  uint32_t nq, k, order, kind;
+  const void* queries;
+  const uint32_t* sel;
+  uint64_t* out;
+  uint32_t* counts;
+};
+int vc_filter_run_host(const VcStoreView& v, const VcFilterHostArgs& a,
+                       const std::function<int(const uint64_t* d_queries, const uint32_t* d_sel, uint64_t* d_out, uint32_t* d_counts)>& run, hipStream_t s,
+                       std::string* err);
 // ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
 struct VcKeepSet;
 #define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)

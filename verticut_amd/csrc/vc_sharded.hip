@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "vc_distinct_plan.hpp"
+#include "vc_filter_plan.hpp"
 #include "vc_internal.hpp"
 #include "vc_mih.hpp"
 #include "vc_seed_plan.hpp"
@@ -2588,6 +2589,51 @@ int vc_sharded_search_knn_distinct(vc_sharded* h, const void* queries, uint32_t 
                             },
                             S, &err);
   return rc && !err.empty() ? sfail(h, rc, "%s", err.c_str()) : rc;
+}
+
+}  // extern "C"
+
+// ---- k-NN among the allowed records over the shards: vc_filter.hip's driver on the root, the shards behind the view's knn and gather --------
+static int check_sharded_filter_args(vc_sharded* h, const void* q, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* sel, uint32_t kind, uint32_t k_first,
+                                     const uint64_t* out) {
+  if (!h || !q || !sel || !out || nq == 0 || k == 0 || k > VC_MAX_K) return VC_ERR_INVALID;
+  if (!vc_distinct_k_first_ok(k, k_first)) return sfail(h, VC_ERR_INVALID, "k_first must be 0 or in k..%u", VC_MAX_K);
+  if (kind >= VC_FILTER_KINDS) return sfail(h, VC_ERR_INVALID, "filtered search: unknown kind %u", kind);
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return sfail(h, VC_ERR_INVALID, "filtered search: mode must be LINEAR or MIH_EXACT");
+  const uint32_t f = h->cfg.engine.flags;
+  if (mode == VC_MODE_MIH_EXACT && ((f & VC_FLAG_REF_SIGNEXT_KEYS) || ((f & VC_FLAG_REF_STOP_LITERAL4) && h->cfg.engine.n_tables < 4)))
+    return sfail(h, VC_ERR_INVALID, "filtered search: MIH_EXACT rows are not the true nearest records under this store's reference flags");
+  return check_sharded_index(h, mode);
+}
+static VcFilterArgs sharded_filter_args(vc_sharded* h, const uint64_t* d_queries, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* d_sel, uint32_t kind,
+                                        uint32_t value, uint32_t k_first, uint64_t* d_out, uint32_t* d_counts) {
+  return VcFilterArgs{d_queries, nq, k, k_first, d_sel, kind, value, h->nbytes * 8u, d_out, d_counts, h->knobs.filter_scratch, h->knobs.filter_window,
+                      h->knobs.filter_route, mode == VC_MODE_MIH_EXACT};
+}
+
+extern "C" {
+
+int vc_sharded_search_knn_filtered_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, const uint32_t* d_sel, uint32_t kind,
+                                       uint32_t value, uint32_t k_first, uint64_t* d_out, uint32_t* d_counts, vc_filter_stats* stats, void* stream) {
+  const int rc = check_sharded_filter_args(h, d_queries, nq, k, mode, d_sel, kind, k_first, d_out);
+  if (rc) return rc;
+  return sharded_store_call(h, mode, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_filter_run(v, sharded_filter_args(h, (const uint64_t*)d_queries, nq, k, mode, d_sel, kind, value, k_first, d_out, d_counts), stats, S, err);
+  });
+}
+
+int vc_sharded_search_knn_filtered(vc_sharded* h, const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* sel, uint32_t kind,
+                                   uint32_t value, uint32_t k_first, uint64_t* out, uint32_t* counts, vc_filter_stats* stats) {
+  const int rc = check_sharded_filter_args(h, queries, nq, k, mode, sel, kind, k_first, out);
+  if (rc) return rc;
+  if (order > VC_ORDER_FARTHEST_FIRST) return VC_ERR_INVALID;
+  return sharded_store_call(h, mode, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_filter_run_host(v, VcFilterHostArgs{nq, k, order, kind, queries, sel, out, counts},
+                              [&](const uint64_t* d_q, const uint32_t* d_sel, uint64_t* d_out, uint32_t* d_cnt) {
+                                return vc_filter_run(v, sharded_filter_args(h, d_q, nq, k, mode, d_sel, kind, value, k_first, d_out, d_cnt), stats, S, err);
+                              },
+                              S, err);
+  });
 }
 
 }  // extern "C"

@@ -53,7 +53,10 @@ EXPORTS = [
     "vc_kmajority", "vc_kmajority_dev", "vc_sharded_kmajority", "vc_sharded_kmajority_dev",
     "vc_seed_centres", "vc_seed_centres_dev", "vc_sharded_seed_centres", "vc_sharded_seed_centres_dev",
     "vc_search_knn_distinct", "vc_search_knn_distinct_dev", "vc_sharded_search_knn_distinct", "vc_sharded_search_knn_distinct_dev",
+    "vc_search_knn_filtered", "vc_search_knn_filtered_dev", "vc_sharded_search_knn_filtered", "vc_sharded_search_knn_filtered_dev",
 ]
+FILTER_MASK, FILTER_ROOTS, FILTER_EQUAL, FILTER_NOT_EQUAL, FILTER_BITS = 0, 1, 2, 3, 4   # VC_FILTER_*: how search_knn_filtered reads `sel`
+FILTER_RAN_POST, FILTER_RAN_PRE = 1, 2   # VC_FILTER_RAN_*: bits of VcFilterStats.routes
 DISTINCT_TRUNCATED = 0x80000000   # VC_DISTINCT_TRUNCATED: flag in a count of search_knn_distinct -- the row holds the groups found within the 8192 nearest records
 SEED_FARTHEST, SEED_WEIGHTED = 0, 1   # VC_SEED_FARTHEST: farthest-first traversal; VC_SEED_WEIGHTED: distance-weighted sampling ("k-majority++")
 KMAJ_MAX_ITERS = 64       # VC_KMAJ_MAX_ITERS: kmajority takes max_iters 0 .. 64
@@ -136,6 +139,15 @@ class VcDistinctStats(C.Structure):
 
     def as_dict(self):
         """{n_rounds, k_last, n_searched, n_truncated, n_short: int}"""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class VcFilterStats(C.Structure):
+    _fields_ = [("n_allowed", C.c_uint64), ("routes", C.c_uint32), ("n_rounds", C.c_uint32), ("k_last", C.c_uint32), ("n_windows", C.c_uint32),
+                ("n_searched", C.c_uint64), ("n_fallback", C.c_uint64), ("n_short", C.c_uint64)]
+
+    def as_dict(self):
+        """{n_allowed, routes, n_rounds, k_last, n_windows, n_searched, n_fallback, n_short: int}"""
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
@@ -273,6 +285,10 @@ def load_library():
     L.vc_seed_centres_dev.argtypes = [vp, u32, u32, u64, vp, vp, vp, vp, vp]
     L.vc_sharded_seed_centres.argtypes = [vp, u32, u32, u64, vp, vp, vp, vp]
     L.vc_sharded_seed_centres_dev.argtypes = [vp, u32, u32, u64, vp, vp, vp, vp, vp]
+    L.vc_search_knn_filtered.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, u32, u32, vp, vp, vp]
+    L.vc_search_knn_filtered_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, u32, vp, vp, vp, vp]
+    L.vc_sharded_search_knn_filtered.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, u32, u32, vp, vp, vp]
+    L.vc_sharded_search_knn_filtered_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, u32, vp, vp, vp, vp]
     L.vc_search_knn_distinct.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, vp, vp, vp, vp]
     L.vc_search_knn_distinct_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp]
     L.vc_sharded_search_knn_distinct.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, vp, vp, vp, vp]
@@ -535,6 +551,28 @@ def _search_knn_distinct(self, fn, queries, k, labels, mode, order, k_first, wit
 def _search_knn_distinct_dev(self, fn, d_queries, nq, k, d_labels, d_out, d_row_labels, d_counts, mode, k_first, with_stats, stream):
     st = VcDistinctStats()
     self._check(fn(self._h, d_queries, nq, k, mode, d_labels, k_first, d_out, d_row_labels, d_counts, C.byref(st) if with_stats else None, stream))
+    return st.as_dict() if with_stats else None
+
+
+def _search_knn_filtered(self, fn, queries, k, sel, kind, value, mode, order, k_first, with_stats):
+    """shared by Engine.search_knn_filtered and ShardedEngine.search_knn_filtered: (out uint64 [nq, k], counts uint32 [nq][, stats dict])"""
+    q = np.ascontiguousarray(queries, dtype=np.uint8).reshape(-1, self.nbytes)
+    nq = q.shape[0]
+    sel = np.ascontiguousarray(sel, dtype=np.uint32).reshape(-1)
+    need = (len(self) + 31) // 32 if kind == FILTER_BITS else len(self)
+    if sel.shape[0] != need:
+        raise VcError(VC_ERR_INVALID, "sel must have one word per resident record (FILTER_BITS: one bit)")
+    if sel.shape[0] == 0:
+        sel = np.zeros(1, dtype=np.uint32)       # (an empty store: the call reads no word, but takes no null pointer)
+    out, counts = np.empty((nq, k), dtype=np.uint64), np.zeros(nq, dtype=np.uint32)
+    st = VcFilterStats()
+    self._check(fn(self._h, _p(q), nq, k, mode, order, _p(sel), kind, value, k_first, _p(out), _p(counts), C.byref(st)))
+    return (out, counts, st.as_dict()) if with_stats else (out, counts)
+
+
+def _search_knn_filtered_dev(self, fn, d_queries, nq, k, d_sel, kind, value, d_out, d_counts, mode, k_first, with_stats, stream):
+    st = VcFilterStats()
+    self._check(fn(self._h, d_queries, nq, k, mode, d_sel, kind, value, k_first, d_out, d_counts, C.byref(st) if with_stats else None, stream))
     return st.as_dict() if with_stats else None
 
 
@@ -914,6 +952,21 @@ class Engine:
         return _search_knn_distinct_dev(self, self._L.vc_search_knn_distinct_dev, d_queries, nq, k, d_labels, d_out, d_row_labels, d_counts, mode, k_first,
                                         with_stats, stream)
 
+    def search_knn_filtered(self, queries, k, sel, kind=FILTER_MASK, value=0, mode=MODE_LINEAR, order=ORDER_ASCENDING, k_first=0, with_stats=False):
+        """vc_search_knn_filtered: the k nearest among the records the filter allows, exact for every selectivity.  sel: one uint32 per
+        resident record -- FILTER_MASK (nonzero), FILTER_ROOTS (a grouper's labels: the representatives), FILTER_EQUAL / FILTER_NOT_EQUAL
+        (against `value`) -- or one bit per record (FILTER_BITS, ceil(N / 32) words).  Returns (out [nq, k] uint64, counts [nq][, stats
+        dict]); counts = min(k, allowed).  mode MODE_LINEAR or MODE_MIH_EXACT; k_first: the first post-filter round's k' (0 = the plan's),
+        which changes the statistics, never a row.  Stages sel on every call: search_knn_filtered_dev keeps it in HBM."""
+        return _search_knn_filtered(self, self._L.vc_search_knn_filtered, queries, k, sel, kind, value, mode, order, k_first, with_stats)
+
+    def search_knn_filtered_dev(self, d_queries, nq, k, d_sel, d_out, d_counts=None, kind=FILTER_MASK, value=0, mode=MODE_LINEAR, k_first=0, with_stats=True,
+                                stream=None):
+        """vc_search_knn_filtered_dev: raw device addresses; the host waits once for the allowed count and once per post-filter round, results
+        valid in `stream` order.  Returns the stats dict; with_stats=False returns None."""
+        return _search_knn_filtered_dev(self, self._L.vc_search_knn_filtered_dev, d_queries, nq, k, d_sel, kind, value, d_out, d_counts, mode, k_first, with_stats,
+                                        stream)
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -1227,6 +1280,21 @@ class ShardedEngine:
         Returns the stats dict; with_stats=False returns None."""
         return _search_knn_distinct_dev(self, self._L.vc_sharded_search_knn_distinct_dev, d_queries, nq, k, d_labels, d_out, d_row_labels, d_counts, mode, k_first,
                                         with_stats, stream)
+
+    def search_knn_filtered(self, queries, k, sel, kind=FILTER_MASK, value=0, mode=MODE_LINEAR, order=ORDER_ASCENDING, k_first=0, with_stats=False):
+        """vc_sharded_search_knn_filtered: the k nearest among the records the filter allows, exact for every selectivity.  sel: one uint32 per
+        resident record -- FILTER_MASK (nonzero), FILTER_ROOTS (a grouper's labels: the representatives), FILTER_EQUAL / FILTER_NOT_EQUAL
+        (against `value`) -- or one bit per record (FILTER_BITS, ceil(N / 32) words).  Returns (out [nq, k] uint64, counts [nq][, stats
+        dict]); counts = min(k, allowed).  mode MODE_LINEAR or MODE_MIH_EXACT; k_first: the first post-filter round's k' (0 = the plan's),
+        which changes the statistics, never a row.  Stages sel on every call: search_knn_filtered_dev keeps it in HBM."""
+        return _search_knn_filtered(self, self._L.vc_sharded_search_knn_filtered, queries, k, sel, kind, value, mode, order, k_first, with_stats)
+
+    def search_knn_filtered_dev(self, d_queries, nq, k, d_sel, d_out, d_counts=None, kind=FILTER_MASK, value=0, mode=MODE_LINEAR, k_first=0, with_stats=True,
+                                stream=None):
+        """vc_sharded_search_knn_filtered_dev: raw device addresses on the root device; the host waits once for the allowed count and once per post-filter round, results
+        valid in `stream` order.  Returns the stats dict; with_stats=False returns None."""
+        return _search_knn_filtered_dev(self, self._L.vc_sharded_search_knn_filtered_dev, d_queries, nq, k, d_sel, kind, value, d_out, d_counts, mode, k_first, with_stats,
+                                        stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

@@ -155,6 +155,11 @@ class Backend {
   // k_first 0 = the default first k'; row_labels, counts and stats may be null; a count may carry VC_DISTINCT_TRUNCATED
   virtual int search_knn_distinct(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* labels, uint32_t k_first,
                                   uint64_t* out, uint32_t* row_labels, uint32_t* counts, vc_distinct_stats* stats) = 0;
+  // the k nearest among the records a filter allows (vc_search_knn_filtered / vc_sharded_search_knn_filtered): sel and kind as
+  // VC_FILTER_* reads them, one filter for the whole batch; mode VC_MODE_LINEAR or VC_MODE_MIH_EXACT; k_first 0 = the plan's first k';
+  // counts and stats may be null; exact for every selectivity, counts = min(k, allowed)
+  virtual int search_knn_filtered(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* sel, uint32_t kind, uint32_t value,
+                                  uint32_t k_first, uint64_t* out, uint32_t* counts, vc_filter_stats* stats) = 0;
   // records taken out of the store and its index, the survivors renumbered in order (vc_retain / vc_sharded_retain; the reference has
   // no delete: this stands for build_hash_tables.cc run again over the code file without them).  kind VC_RETAIN_MASK / VC_RETAIN_ROOTS
   virtual int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) = 0;
@@ -240,6 +245,10 @@ class Engine : public Backend {
   int search_knn_distinct(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* labels, uint32_t k_first,
                           uint64_t* out, uint32_t* row_labels, uint32_t* counts, vc_distinct_stats* stats) override {
     return vc_search_knn_distinct(h_, queries, nq, k, mode, order, labels, k_first, out, row_labels, counts, stats);
+  }
+  int search_knn_filtered(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* sel, uint32_t kind, uint32_t value,
+                          uint32_t k_first, uint64_t* out, uint32_t* counts, vc_filter_stats* stats) override {
+    return vc_search_knn_filtered(h_, queries, nq, k, mode, order, sel, kind, value, k_first, out, counts, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_retain(h_, sel, kind, new_ids, n_kept); }
  private:
@@ -353,6 +362,10 @@ class ShardedEngine : public Backend {
   int search_knn_distinct(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* labels, uint32_t k_first,
                           uint64_t* out, uint32_t* row_labels, uint32_t* counts, vc_distinct_stats* stats) override {
     return vc_sharded_search_knn_distinct(h_, queries, nq, k, mode, order, labels, k_first, out, row_labels, counts, stats);
+  }
+  int search_knn_filtered(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* sel, uint32_t kind, uint32_t value,
+                          uint32_t k_first, uint64_t* out, uint32_t* counts, vc_filter_stats* stats) override {
+    return vc_sharded_search_knn_filtered(h_, queries, nq, k, mode, order, sel, kind, value, k_first, out, counts, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_sharded_retain(h_, sel, kind, new_ids, n_kept); }
  private:
