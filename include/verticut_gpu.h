@@ -852,7 +852,7 @@ int vc_search_knn_distinct(vc_engine* e, const void* queries, uint32_t nq, uint3
  * store down with vc_retain*; inside one album, class or cluster, or everywhere but in it; under a caller's keep mask (tombstones,
  * tenants, a date range computed elsewhere).  The reference has no such call; the host loop it would take -- search with a guessed
  * larger k, copy rows home, filter, repeat -- runs into VC_MAX_K for a selective filter and then has no exact answer at all.
- * THE FILTER is shared by all queries of the call (a filter per query is out of scope).  Record i has global id id_base + i:
+ * THE FILTER is shared by all queries of the call (a filter per query is out of scope) (see vc_search_knn_scoped*).  Record i has global id id_base + i:
  *   VC_FILTER_MASK       sel[i] != 0                                                         N words
  *   VC_FILTER_ROOTS      sel[i] == id_base + i (a grouper's labels: one representative per   N words
  *                        group, as VC_RETAIN_ROOTS)
@@ -916,6 +916,55 @@ int vc_search_knn_filtered_dev(vc_engine* e, const void* d_queries, uint32_t nq,
 int vc_search_knn_filtered(vc_engine* e, const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order,
                            const uint32_t* sel, uint32_t kind, uint32_t value, uint32_t k_first, uint64_t* out, uint32_t* counts,
                            vc_filter_stats* stats);
+
+/* ---- k-NN inside each query's own scope: vc_search_knn_scoped* -----------------------------------------------------------------------------
+ * "The k nearest records of MY tenant, album, class or cluster", for a batch in which every query brings its own value: a service
+ * that batches the queries of many tenants, a labelling pass that asks for the nearest pictures of the same album for thousands of
+ * pictures, a search inside a grouper's clusters.  With vc_search_knn_filtered* such a batch falls apart into one call -- one keep
+ * set over all N records and one host wait -- per distinct value; this call answers it at once.
+ * THE SCOPES.  scope holds N words, record i (global id id_base + i) carries scope[i]; qscope holds nq words, query q carries
+ * qscope[q].  Every 32-bit value is legal in both arrays, 0, 0x80000000 and 0xFFFFFFFF included; nothing is validated.
+ * THE RULE.  Row q holds the k smallest packed (dist << 32 | id) over the records with scope[i] == qscope[q], ascending, padded with
+ * UINT64_MAX; counts[q] = min(k, S_q), S_q the number of records that carry the query's value -- 0 when none does.  Ties go to the
+ * smaller id.  Every output word is a function of the codes, scope, qscope, the queries and k: not of the order of the queries, of
+ * the other queries of the call, of the environment knobs below or of what earlier calls left in the handle.  Row q equals, word
+ * for word, row 0 of vc_search_knn_filtered* called with VC_FILTER_EQUAL, value = qscope[q], VC_MODE_LINEAR and that one query.
+ * There is no truncation flag and no mode argument: the call is exact brute force over the scope and needs no index.
+ * flags is reserved and must be 0.  OUT OF SCOPE: VC_FILTER_NOT_EQUAL per query ("everywhere but my group") is a dense filter, which
+ * needs the post-filter rounds of vc_search_knn_filtered*; and a form for queries named by id.
+ * HOW.  The pairs (qscope[q], q) are sorted: the U distinct values ascending are the slots.  One pass over scope sets the bit of every
+ * record whose value is one of them (a binary search) in a keep set; a host wait fetches U and A, the number of matched records.
+ * Records that no query names cost nothing after this pass.  The A ids are listed ascending with their slots and sorted by slot with a
+ * stable radix sort: slots ascend in the list and ids ascend within a slot, so every scope is a segment in id order.  A second host
+ * wait fetches the segment table, 2 (U + 1) words.  The list is taken in windows of VC_SCOPE_WINDOW positions (default 2^20, 0 or
+ * above 2^24 means the default) whose codes are gathered by id; a wave holds a slice of the window in registers and loops over the
+ * sorted queries of the slots its slice touches, a pair counting only where the position's slot is the query's.  The selection is
+ * the three walks of vc_search_knn_filtered*'s pre-filter route -- histogram, counts, placement by rank -- over per-(query, slice)
+ * counters that a query owns only for the slices its segment touches; the queries are sub-batched so that these counters stay under
+ * VC_SCOPE_SCRATCH bytes (default 64 MiB, always at least one query).  A segment that straddles windows has its rows merged.  Both
+ * knobs are read once at vc_create.  COST: a slice that holds many tiny scopes computes a slice's worth of distances for every query of
+ * its range although only the matching ones count; stats.n_pairs is the number the answer needs.
+ * OUTPUT: d_out nq * k packed; d_counts (nq, may be NULL); stats (HOST memory in both forms, may be NULL).
+ * ERRORS, checked before any work, outputs and stats untouched: VC_ERR_INVALID for a null handle, queries, scope, qscope or out,
+ * nq == 0, k outside 1 .. VC_MAX_K, flags != 0, a bad order (host form).  N == 0 gives VC_OK with counts 0, padded rows and zero
+ * stats.
+ * Scratch: grow-only buffers of the handle, this call's own; every word is written before it is read. */
+typedef struct vc_scope_stats {   /* 40 bytes */
+  uint64_t n_matched;   /* A: records whose scope some query of the call names */
+  uint64_t n_pairs;     /* sum over the queries of S_q: the distances the answer needs */
+  uint32_t n_scopes;    /* U: distinct values in qscope */
+  uint32_t n_windows;   /* windows of the sorted list scanned (per sub-batch of queries) */
+  uint64_t n_short;     /* queries with count < k */
+  uint64_t n_empty;     /* queries with S_q == 0 */
+} vc_scope_stats;
+int vc_search_knn_scoped_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_scope,
+                             const uint32_t* d_qscope, uint32_t flags, uint64_t* d_out, uint32_t* d_counts, vc_scope_stats* stats,
+                             void* stream);
+/* The same for queries, scope, qscope and results in host memory: all three inputs are staged on the engine's stream ON EVERY CALL,
+ * the device form runs into staged outputs, which come home; waits for them.  order as vc_search_knn: VC_ORDER_FARTHEST_FIRST
+ * reverses the valid part of every row.  Callers who search repeatedly should keep scope in HBM and use the device form. */
+int vc_search_knn_scoped(vc_engine* e, const void* queries, uint32_t nq, uint32_t k, uint32_t order, const uint32_t* scope,
+                         const uint32_t* qscope, uint32_t flags, uint64_t* out, uint32_t* counts, vc_scope_stats* stats);
 
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
@@ -1177,6 +1226,15 @@ int vc_sharded_search_knn_filtered_dev(vc_sharded* h, const void* d_queries, uin
 int vc_sharded_search_knn_filtered(vc_sharded* h, const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order,
                                    const uint32_t* sel, uint32_t kind, uint32_t value, uint32_t k_first, uint64_t* out, uint32_t* counts,
                                    vc_filter_stats* stats);
+
+/* k-NN inside each query's own scope over all shards: scopes, rule, outputs, errors and waits as vc_search_knn_scoped_dev /
+ * vc_search_knn_scoped with N = vc_sharded_size and ids global over the whole store.  Every pointer of the device form lives on the
+ * ROOT device; every pass runs there, the shards are reached only through the store's gather by id. */
+int vc_sharded_search_knn_scoped_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_scope,
+                                     const uint32_t* d_qscope, uint32_t flags, uint64_t* d_out, uint32_t* d_counts, vc_scope_stats* stats,
+                                     void* stream);
+int vc_sharded_search_knn_scoped(vc_sharded* h, const void* queries, uint32_t nq, uint32_t k, uint32_t order, const uint32_t* scope,
+                                 const uint32_t* qscope, uint32_t flags, uint64_t* out, uint32_t* counts, vc_scope_stats* stats);
 
 /* Stream of the host-pointer calls (default VC_STREAM_OWN). */
 int vc_set_stream(vc_engine* e, void* stream);

@@ -161,6 +161,8 @@ void read_knobs(VcKnobs* k) {
   if (const char* v = getenv("VC_FILTER_ROUTE")) k->filter_route = (uint32_t)strtoul(v, nullptr, 10);
   if (const char* v = getenv("VC_FILTER_SCRATCH")) k->filter_scratch = strtoull(v, nullptr, 10);
   if (const char* v = getenv("VC_FILTER_WINDOW")) k->filter_window = (uint32_t)strtoul(v, nullptr, 10);
+  if (const char* v = getenv("VC_SCOPE_SCRATCH")) k->scope_scratch = strtoull(v, nullptr, 10);
+  if (const char* v = getenv("VC_SCOPE_WINDOW")) k->scope_window = (uint32_t)strtoul(v, nullptr, 10);
 }
 
 static int bind_device(vc_engine* e) {
@@ -1572,6 +1574,47 @@ int vc_search_knn_filtered(vc_engine* e, const void* queries, uint32_t nq, uint3
                                 return vc_filter_run(v, filter_args(e, d_q, nq, k, mode, d_sel, kind, value, k_first, d_out, d_cnt), stats, s, err);
                               },
                               s, err);
+  });
+}
+
+}  // extern "C"
+
+// ---- k-NN inside each query's own scope (vc_scope.hip): exact brute force, no index, no mode ---------------------------------------------
+static int check_scope_args(vc_engine* e, const void* q, uint32_t nq, uint32_t k, const uint32_t* scope, const uint32_t* qscope, uint32_t flags,
+                            const uint64_t* out) {
+  if (!e || !q || !scope || !qscope || !out || nq == 0) return VC_ERR_INVALID;
+  if (k == 0 || k > VC_MAX_K) return fail(e, VC_ERR_INVALID, "k must be in 1..%u", VC_MAX_K);
+  if (flags) return fail(e, VC_ERR_INVALID, "scoped search: flags is reserved and must be 0");
+  return VC_OK;
+}
+static VcScopeArgs scope_args(vc_engine* e, const uint64_t* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_scope, const uint32_t* d_qscope,
+                              uint64_t* d_out, uint32_t* d_counts) {
+  return VcScopeArgs{d_queries, nq, k, d_scope, d_qscope, e->W * 64u, d_out, d_counts, e->knobs.scope_scratch, e->knobs.scope_window};
+}
+
+extern "C" {
+
+int vc_search_knn_scoped_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_scope, const uint32_t* d_qscope, uint32_t flags,
+                             uint64_t* d_out, uint32_t* d_counts, vc_scope_stats* stats, void* stream) {
+  const int rc = check_scope_args(e, d_queries, nq, k, d_scope, d_qscope, flags, d_out);
+  if (rc) return rc;
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_scope_run(store_view(e, VC_MODE_LINEAR), scope_args(e, (const uint64_t*)d_queries, nq, k, d_scope, d_qscope, d_out, d_counts), stats, s, err);
+  });
+}
+
+int vc_search_knn_scoped(vc_engine* e, const void* queries, uint32_t nq, uint32_t k, uint32_t order, const uint32_t* scope, const uint32_t* qscope,
+                         uint32_t flags, uint64_t* out, uint32_t* counts, vc_scope_stats* stats) {
+  const int rc = check_scope_args(e, queries, nq, k, scope, qscope, flags, out);
+  if (rc) return rc;
+  if (order > VC_ORDER_FARTHEST_FIRST) return VC_ERR_INVALID;
+  return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    const VcStoreView v = store_view(e, VC_MODE_LINEAR);
+    return vc_scope_run_host(v, VcScopeHostArgs{nq, k, order, queries, scope, qscope, out, counts},
+                             [&](const uint64_t* d_q, const uint32_t* d_scope, const uint32_t* d_qscope, uint64_t* d_out, uint32_t* d_cnt) {
+                               return vc_scope_run(v, scope_args(e, d_q, nq, k, d_scope, d_qscope, d_out, d_cnt), stats, s, err);
+                             },
+                             s, err);
   });
 }
 

@@ -51,6 +51,8 @@ struct VcKnobs {
   uint32_t filter_route = 0;                  // VC_FILTER_ROUTE (tests, A/B runs): 0 the plan's route of vc_search_knn_filtered*, 1 post-filter first, 2 pre-filter only
   uint64_t filter_scratch = 64ull << 20;      // VC_FILTER_SCRATCH: bytes of k' rows / of per-slice counters a sub-batch of vc_search_knn_filtered* may hold (vc_filter_plan.hpp)
   uint32_t filter_window = 1u << 20;          // VC_FILTER_WINDOW: allowed ids per window of the pre-filter route (0 or above 2^24: the default)
+  uint64_t scope_scratch = 64ull << 20;       // VC_SCOPE_SCRATCH: bytes of (query, slice) counters a sub-batch of vc_search_knn_scoped* may hold (vc_scope_plan.hpp)
+  uint32_t scope_window = 1u << 20;           // VC_SCOPE_WINDOW: positions of the scope-sorted list per window (0 or above 2^24: the default)
 };
 void read_knobs(VcKnobs* k);   // vc_engine.hip: the one place that reads the environment (once per engine / sharded handle)
 
@@ -197,6 +199,9 @@ enum VcScratch {
   // filtered k-NN (vc_filter.hip): the keep set (bits, rank, scan work); the rounds' flags, maps and listed queries; the k' rows; the
   // pre-filter route's arrays of a window and a sub-batch; a window's gathered codes; the host forms' staging
   VC_FILTER_KEEP, VC_FILTER_WORK, VC_FILTER_ROWS, VC_FILTER_PRE, VC_FILTER_CODES, VC_FILTER_STAGE,
+  // scoped k-NN (vc_scope.hip): the query side's sort and tables; the keep set; the listed records, their sort and the segment table;
+  // a sub-batch's histograms, cuts and counters; its candidate, running and merge rows; a window's gathered codes; the host forms' staging
+  VC_SCOPE_QUERY, VC_SCOPE_KEEP, VC_SCOPE_LIST, VC_SCOPE_WORK, VC_SCOPE_ROWS, VC_SCOPE_CODES, VC_SCOPE_STAGE,
   VC_SCRATCH_BUFS
 };
 // buffer `which` of the handle's table, at least `bytes` large, on the current device; null when it cannot be had (the handle keeps the text)
@@ -588,6 +593,35 @@ struct VcFilterHostArgs {
 int vc_filter_run_host(const VcStoreView& v, const VcFilterHostArgs& a,
                        const std::function<int(const uint64_t* d_queries, const uint32_t* d_sel, uint64_t* d_out, uint32_t* d_counts)>& run, hipStream_t s,
                        std::string* err);
+// ---- vc_scope.hip: k-NN inside each query's own scope (vc_search_knn_scoped*, vc_sharded_search_knn_scoped*).  One driver for both
+// handle kinds over the view's gather and alloc; the plan arithmetic -- key bits, windows, the slice -> query-range rule, the counter
+// layout, the sub-batches -- is vc_scope_plan.hpp.
+struct VcScopeArgs {
+  const uint64_t* d_queries;       // [nq][W]
+  uint32_t nq, k;                  // checked by the caller: nq > 0, 1 <= k <= VC_MAX_K
+  const uint32_t* d_scope;         // N words
+  const uint32_t* d_qscope;        // nq words
+  uint32_t bits;                   // the code width, 64 W
+  uint64_t* d_out;                 // [nq][k]
+  uint32_t* d_counts;              // [nq], nullable
+  uint64_t budget;                 // VcKnobs::scope_scratch
+  uint32_t window;                 // VcKnobs::scope_window
+};
+// the whole call on s with the device of the buffers current: one wait for U and A, one for the segment table; stats (host memory) nullable
+int vc_scope_run(const VcStoreView& v, const VcScopeArgs& a, vc_scope_stats* stats, hipStream_t s, std::string* err);
+// either handle's host form: queries, scope and qscope staged, `run` (the device form on s) into staged outputs, which come home;
+// waits for them, then turns the valid part of every row round for VC_ORDER_FARTHEST_FIRST.  counts nullable
+struct VcScopeHostArgs {
+  uint32_t nq, k, order;
+  const void* queries;
+  const uint32_t* scope;
+  const uint32_t* qscope;
+  uint64_t* out;
+  uint32_t* counts;
+};
+int vc_scope_run_host(const VcStoreView& v, const VcScopeHostArgs& a,
+                      const std::function<int(const uint64_t* d_queries, const uint32_t* d_scope, const uint32_t* d_qscope, uint64_t* d_out, uint32_t* d_counts)>& run,
+                      hipStream_t s, std::string* err);
 // ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
 struct VcKeepSet;
 #define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)

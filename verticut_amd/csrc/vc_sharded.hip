@@ -2638,6 +2638,45 @@ int vc_sharded_search_knn_filtered(vc_sharded* h, const void* queries, uint32_t 
 
 }  // extern "C"
 
+// ---- k-NN inside each query's own scope over the shards: vc_scope.hip's driver on the root, the shards behind the view's gather -------------
+static int check_sharded_scope_args(vc_sharded* h, const void* q, uint32_t nq, uint32_t k, const uint32_t* scope, const uint32_t* qscope, uint32_t flags,
+                                    const uint64_t* out) {
+  if (!h || !q || !scope || !qscope || !out || nq == 0 || k == 0 || k > VC_MAX_K) return VC_ERR_INVALID;
+  if (flags) return sfail(h, VC_ERR_INVALID, "scoped search: flags is reserved and must be 0");
+  return VC_OK;
+}
+static VcScopeArgs sharded_scope_args(vc_sharded* h, const uint64_t* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_scope, const uint32_t* d_qscope,
+                                      uint64_t* d_out, uint32_t* d_counts) {
+  return VcScopeArgs{d_queries, nq, k, d_scope, d_qscope, h->nbytes * 8u, d_out, d_counts, h->knobs.scope_scratch, h->knobs.scope_window};
+}
+
+extern "C" {
+
+int vc_sharded_search_knn_scoped_dev(vc_sharded* h, const void* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_scope, const uint32_t* d_qscope,
+                                     uint32_t flags, uint64_t* d_out, uint32_t* d_counts, vc_scope_stats* stats, void* stream) {
+  const int rc = check_sharded_scope_args(h, d_queries, nq, k, d_scope, d_qscope, flags, d_out);
+  if (rc) return rc;
+  return sharded_store_call(h, VC_MODE_LINEAR, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_scope_run(v, sharded_scope_args(h, (const uint64_t*)d_queries, nq, k, d_scope, d_qscope, d_out, d_counts), stats, S, err);
+  });
+}
+
+int vc_sharded_search_knn_scoped(vc_sharded* h, const void* queries, uint32_t nq, uint32_t k, uint32_t order, const uint32_t* scope, const uint32_t* qscope,
+                                 uint32_t flags, uint64_t* out, uint32_t* counts, vc_scope_stats* stats) {
+  const int rc = check_sharded_scope_args(h, queries, nq, k, scope, qscope, flags, out);
+  if (rc) return rc;
+  if (order > VC_ORDER_FARTHEST_FIRST) return VC_ERR_INVALID;
+  return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_scope_run_host(v, VcScopeHostArgs{nq, k, order, queries, scope, qscope, out, counts},
+                             [&](const uint64_t* d_q, const uint32_t* d_scope, const uint32_t* d_qscope, uint64_t* d_out, uint32_t* d_cnt) {
+                               return vc_scope_run(v, sharded_scope_args(h, d_q, nq, k, d_scope, d_qscope, d_out, d_cnt), stats, S, err);
+                             },
+                             S, err);
+  });
+}
+
+}  // extern "C"
+
 // ---- removal over the shards ----------------------------------------------------------------------------------------------------------
 // a shard's map names ids of its own range (shard id_base + j); survivor j of shard g is survivor P_g + j of the store
 extern "C" __global__ void __launch_bounds__(256) vc_sharded_retain_shift_kernel(uint32_t* __restrict__ ids, uint64_t n, uint32_t delta) {

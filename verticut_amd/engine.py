@@ -54,6 +54,7 @@ EXPORTS = [
     "vc_seed_centres", "vc_seed_centres_dev", "vc_sharded_seed_centres", "vc_sharded_seed_centres_dev",
     "vc_search_knn_distinct", "vc_search_knn_distinct_dev", "vc_sharded_search_knn_distinct", "vc_sharded_search_knn_distinct_dev",
     "vc_search_knn_filtered", "vc_search_knn_filtered_dev", "vc_sharded_search_knn_filtered", "vc_sharded_search_knn_filtered_dev",
+    "vc_search_knn_scoped", "vc_search_knn_scoped_dev", "vc_sharded_search_knn_scoped", "vc_sharded_search_knn_scoped_dev",
 ]
 FILTER_MASK, FILTER_ROOTS, FILTER_EQUAL, FILTER_NOT_EQUAL, FILTER_BITS = 0, 1, 2, 3, 4   # VC_FILTER_*: how search_knn_filtered reads `sel`
 FILTER_RAN_POST, FILTER_RAN_PRE = 1, 2   # VC_FILTER_RAN_*: bits of VcFilterStats.routes
@@ -148,6 +149,15 @@ class VcFilterStats(C.Structure):
 
     def as_dict(self):
         """{n_allowed, routes, n_rounds, k_last, n_windows, n_searched, n_fallback, n_short: int}"""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class VcScopeStats(C.Structure):
+    _fields_ = [("n_matched", C.c_uint64), ("n_pairs", C.c_uint64), ("n_scopes", C.c_uint32), ("n_windows", C.c_uint32), ("n_short", C.c_uint64),
+                ("n_empty", C.c_uint64)]
+
+    def as_dict(self):
+        """{n_matched, n_pairs, n_scopes, n_windows, n_short, n_empty: int}"""
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
@@ -289,6 +299,10 @@ def load_library():
     L.vc_search_knn_filtered_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, u32, vp, vp, vp, vp]
     L.vc_sharded_search_knn_filtered.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, u32, u32, vp, vp, vp]
     L.vc_sharded_search_knn_filtered_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, u32, vp, vp, vp, vp]
+    L.vc_search_knn_scoped.argtypes = [vp, vp, u32, u32, u32, vp, vp, u32, vp, vp, vp]
+    L.vc_search_knn_scoped_dev.argtypes = [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, vp]
+    L.vc_sharded_search_knn_scoped.argtypes = [vp, vp, u32, u32, u32, vp, vp, u32, vp, vp, vp]
+    L.vc_sharded_search_knn_scoped_dev.argtypes = [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, vp]
     L.vc_search_knn_distinct.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, vp, vp, vp, vp]
     L.vc_search_knn_distinct_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp]
     L.vc_sharded_search_knn_distinct.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, vp, vp, vp, vp]
@@ -573,6 +587,30 @@ def _search_knn_filtered(self, fn, queries, k, sel, kind, value, mode, order, k_
 def _search_knn_filtered_dev(self, fn, d_queries, nq, k, d_sel, kind, value, d_out, d_counts, mode, k_first, with_stats, stream):
     st = VcFilterStats()
     self._check(fn(self._h, d_queries, nq, k, mode, d_sel, kind, value, k_first, d_out, d_counts, C.byref(st) if with_stats else None, stream))
+    return st.as_dict() if with_stats else None
+
+
+def _search_knn_scoped(self, fn, queries, k, scope, qscope, order, with_stats):
+    """shared by Engine.search_knn_scoped and ShardedEngine.search_knn_scoped: (out uint64 [nq, k], counts uint32 [nq][, stats dict])"""
+    q = np.ascontiguousarray(queries, dtype=np.uint8).reshape(-1, self.nbytes)
+    nq = q.shape[0]
+    scope = np.ascontiguousarray(scope, dtype=np.uint32).reshape(-1)
+    qscope = np.ascontiguousarray(qscope, dtype=np.uint32).reshape(-1)
+    if scope.shape[0] != len(self):
+        raise VcError(VC_ERR_INVALID, "scope must have one word per resident record")
+    if qscope.shape[0] != nq:
+        raise VcError(VC_ERR_INVALID, "qscope must have one word per query")
+    if scope.shape[0] == 0:
+        scope = np.zeros(1, dtype=np.uint32)       # (an empty store: the call reads no word, but takes no null pointer)
+    out, counts = np.empty((nq, k), dtype=np.uint64), np.zeros(nq, dtype=np.uint32)
+    st = VcScopeStats()
+    self._check(fn(self._h, _p(q), nq, k, order, _p(scope), _p(qscope), 0, _p(out), _p(counts), C.byref(st)))
+    return (out, counts, st.as_dict()) if with_stats else (out, counts)
+
+
+def _search_knn_scoped_dev(self, fn, d_queries, nq, k, d_scope, d_qscope, d_out, d_counts, with_stats, stream):
+    st = VcScopeStats()
+    self._check(fn(self._h, d_queries, nq, k, d_scope, d_qscope, 0, d_out, d_counts, C.byref(st) if with_stats else None, stream))
     return st.as_dict() if with_stats else None
 
 
@@ -967,6 +1005,18 @@ class Engine:
         return _search_knn_filtered_dev(self, self._L.vc_search_knn_filtered_dev, d_queries, nq, k, d_sel, kind, value, d_out, d_counts, mode, k_first, with_stats,
                                         stream)
 
+    def search_knn_scoped(self, queries, k, scope, qscope, order=ORDER_ASCENDING, with_stats=False):
+        """vc_search_knn_scoped: for every query the k nearest among the records whose scope word equals the query's own.  scope: one
+        uint32 per resident record, qscope: one per query; every value is legal.  Returns (out uint64 [nq, k], counts uint32 [nq][, stats
+        dict]); counts = min(k, size of the query's scope).  Exact brute force over the scope, no index.  Stages scope on every call:
+        search_knn_scoped_dev keeps it in HBM."""
+        return _search_knn_scoped(self, self._L.vc_search_knn_scoped, queries, k, scope, qscope, order, with_stats)
+
+    def search_knn_scoped_dev(self, d_queries, nq, k, d_scope, d_qscope, d_out, d_counts=None, with_stats=True, stream=None):
+        """vc_search_knn_scoped_dev: raw device addresses; the host waits twice (the matched count, the segment table), results valid in
+        `stream` order.  Returns the stats dict; with_stats=False returns None."""
+        return _search_knn_scoped_dev(self, self._L.vc_search_knn_scoped_dev, d_queries, nq, k, d_scope, d_qscope, d_out, d_counts, with_stats, stream)
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -1295,6 +1345,16 @@ class ShardedEngine:
         valid in `stream` order.  Returns the stats dict; with_stats=False returns None."""
         return _search_knn_filtered_dev(self, self._L.vc_sharded_search_knn_filtered_dev, d_queries, nq, k, d_sel, kind, value, d_out, d_counts, mode, k_first, with_stats,
                                         stream)
+
+    def search_knn_scoped(self, queries, k, scope, qscope, order=ORDER_ASCENDING, with_stats=False):
+        """vc_sharded_search_knn_scoped: for every query the k nearest among the records whose scope word equals the query's own, ids global
+        over the store.  Returns (out uint64 [nq, k], counts uint32 [nq][, stats dict]); counts = min(k, size of the query's scope)."""
+        return _search_knn_scoped(self, self._L.vc_sharded_search_knn_scoped, queries, k, scope, qscope, order, with_stats)
+
+    def search_knn_scoped_dev(self, d_queries, nq, k, d_scope, d_qscope, d_out, d_counts=None, with_stats=True, stream=None):
+        """vc_sharded_search_knn_scoped_dev: raw device addresses on the root device; the host waits twice, results valid in `stream` order.
+        Returns the stats dict; with_stats=False returns None."""
+        return _search_knn_scoped_dev(self, self._L.vc_sharded_search_knn_scoped_dev, d_queries, nq, k, d_scope, d_qscope, d_out, d_counts, with_stats, stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

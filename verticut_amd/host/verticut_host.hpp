@@ -160,6 +160,11 @@ class Backend {
   // counts and stats may be null; exact for every selectivity, counts = min(k, allowed)
   virtual int search_knn_filtered(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* sel, uint32_t kind, uint32_t value,
                                   uint32_t k_first, uint64_t* out, uint32_t* counts, vc_filter_stats* stats) = 0;
+  // the k nearest inside each query's own scope (vc_search_knn_scoped / vc_sharded_search_knn_scoped): scope one word per record, qscope
+  // one per query, a record counts for a query when the two words are equal; exact brute force, no mode; flags 0; counts and stats may
+  // be null, counts = min(k, size of the query's scope)
+  virtual int search_knn_scoped(const void* queries, uint32_t nq, uint32_t k, uint32_t order, const uint32_t* scope, const uint32_t* qscope, uint32_t flags,
+                                uint64_t* out, uint32_t* counts, vc_scope_stats* stats) = 0;
   // records taken out of the store and its index, the survivors renumbered in order (vc_retain / vc_sharded_retain; the reference has
   // no delete: this stands for build_hash_tables.cc run again over the code file without them).  kind VC_RETAIN_MASK / VC_RETAIN_ROOTS
   virtual int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) = 0;
@@ -249,6 +254,10 @@ class Engine : public Backend {
   int search_knn_filtered(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* sel, uint32_t kind, uint32_t value,
                           uint32_t k_first, uint64_t* out, uint32_t* counts, vc_filter_stats* stats) override {
     return vc_search_knn_filtered(h_, queries, nq, k, mode, order, sel, kind, value, k_first, out, counts, stats);
+  }
+  int search_knn_scoped(const void* queries, uint32_t nq, uint32_t k, uint32_t order, const uint32_t* scope, const uint32_t* qscope, uint32_t flags,
+                        uint64_t* out, uint32_t* counts, vc_scope_stats* stats) override {
+    return vc_search_knn_scoped(h_, queries, nq, k, order, scope, qscope, flags, out, counts, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_retain(h_, sel, kind, new_ids, n_kept); }
  private:
@@ -366,6 +375,10 @@ class ShardedEngine : public Backend {
   int search_knn_filtered(const void* queries, uint32_t nq, uint32_t k, uint32_t mode, uint32_t order, const uint32_t* sel, uint32_t kind, uint32_t value,
                           uint32_t k_first, uint64_t* out, uint32_t* counts, vc_filter_stats* stats) override {
     return vc_sharded_search_knn_filtered(h_, queries, nq, k, mode, order, sel, kind, value, k_first, out, counts, stats);
+  }
+  int search_knn_scoped(const void* queries, uint32_t nq, uint32_t k, uint32_t order, const uint32_t* scope, const uint32_t* qscope, uint32_t flags,
+                        uint64_t* out, uint32_t* counts, vc_scope_stats* stats) override {
+    return vc_sharded_search_knn_scoped(h_, queries, nq, k, order, scope, qscope, flags, out, counts, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_sharded_retain(h_, sel, kind, new_ids, n_kept); }
  private:
