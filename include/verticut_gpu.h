@@ -129,7 +129,9 @@ typedef struct vc_timing {
   float scan_ms;           /* sum over launches of the dominant verify kernel (vc_scan_kernel) */
   uint32_t scan_launches;
   uint32_t calls;
-  uint64_t scan_bytes;     /* algorithmic bytes those launches read: launches * N * B/8 */
+  uint64_t scan_bytes;     /* algorithmic bytes those launches read: N * B/8 per launch over the store's columns; per launch
+                              over the scan stream (vc_build_scan_stream) the bytes THAT launch streams, padded records * 12
+                              + granule headers * 8 */
   /* ABI 2 -- the MIH query kernel (mih_query_kernel: probe + verify + merge of the shells of a batch in one launch) */
   float mih_ms;            /* sum over its launches */
   uint32_t mih_launches;
@@ -193,6 +195,33 @@ int vc_build_index(vc_engine* e);
  * returns VC_ERR_STATE exactly as if there were none -- only its device memory stays allocated.
  * If an update fails, the handle is left with that stale index or with none; vc_build_index works after either. */
 int vc_update_index(vc_engine* e);
+
+/* ---- scan stream: a second, derived layout of a 128-bit store for linear k-NN passes of 1..8 queries -----------------
+ * The records sorted by their KEY -- the low 32 bits of code word 0, i.e. bytes 0..3 of a record -- as four uint32
+ * columns, a position -> local id table and one {prefix, mask} header per 256 sorted records (the leading key bits they
+ * share).  A linear pass of vc_search_knn / vc_search_knn_dev(_stats) with at most 8 queries per tile then streams 12 bytes
+ * per record instead of 16: the header stands in for the key as a lower bound, and only the rare records that pass it read
+ * their key.  Results are bit for bit those without the stream.  Larger tiles, other widths and every other call are served
+ * from the store's own columns as before.
+ * Cost: about 20.03 bytes per record held, plus sort temporaries of about 8 bytes per record during the call.  The build
+ * runs on the engine's stream and waits for it.  VC_ERR_INVALID unless bits == 128; VC_ERR_NOMEM, engine unchanged, when
+ * stream + temporaries exceed 55 % of the free device memory (the share an MIH index's bucket-order records may take) or an
+ * allocation fails.  Building again replaces the stream.
+ * Every call that changes the store -- vc_add_codes, vc_add_synthetic, vc_load_code_file, vc_retain* -- drops the stream and
+ * frees it; searches then run as without it.  Nothing rebuilds it but this call, so no result depends on call history. */
+int vc_build_scan_stream(vc_engine* e);
+typedef struct vc_scan_stream_state {
+  uint32_t built;          /* 0 / 1 */
+  uint32_t reserved;
+  uint64_t items;          /* records it covers */
+  uint64_t granules;       /* headers (256 sorted records each, padding included) */
+  uint64_t bytes;          /* device memory held */
+  uint64_t launches;       /* verify launches served from the stream since the build */
+  uint64_t bound_passes;   /* diagnostic build (VC_SCAN_DIAGNOSTICS) only, else 0: records of the LAST stream launch that */
+  uint64_t exact_passes;   /* passed the lower bound / passed the exact check (summed over its queries) */
+} vc_scan_stream_state;
+int vc_scan_stream_info(vc_engine* e, vc_scan_stream_state* info);
+
 /* HashIndex{table_id,index} -> Image_List get (search_worker.cc:224-246, base_proxy.h:18).
  * Writes up to cap (id, code) pairs in append (= id) order; *n = bucket length.
  * Returns VC_OK (PROXY_FOUND) or VC_NOT_FOUND.  ids / codes may be NULL. */

@@ -130,4 +130,13 @@ struct VcScanParams {
   uint64_t shist_cstride;
   uint32_t shist_copies;
   uint32_t bits;
+  // The prefix-sorted scan stream (vc_scan_kernel_stream only, vc_scan_stream_plan.hpp): the hot columns t0 | t1 | t2 sit
+  // st_stride words apart from st_tail on, st_key / st_perm are read on the exact check, one st_hdr entry per granule.
+  // nchunks counts stream chunks then, cols / stride still name the store's own columns.
+  const uint32_t* st_tail;
+  const uint32_t* st_key;
+  const uint32_t* st_perm;
+  const uint32_t* st_hdr;
+  uint64_t st_stride;
+  uint32_t* st_diag;        // diagnostic build: [0] items that passed the lower bound, [1] items that passed the exact check
 };

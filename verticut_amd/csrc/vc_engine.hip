@@ -18,6 +18,13 @@
 #include "vc_mih.hpp"
 #include "vc_retain.hpp"
 
+// (the diagnostic build of vc_scan.hip counts the stream form's lower-bound and exact passes: build.py passes the flag to every unit)
+#if defined(VC_SCAN_DIAGNOSTICS) && VC_SCAN_DIAGNOSTICS
+#define VC_SCAN_STREAM_DIAG 1
+#else
+#define VC_SCAN_STREAM_DIAG 0
+#endif
+
 struct vc_engine {
   vc_config cfg;
   int device = 0;
@@ -64,6 +71,7 @@ struct vc_engine {
   uint64_t scan_bytes = 0;
   vc_timing last{};
 
+  VcScanStream sstream;     // the prefix-sorted scan stream (vc_build_scan_stream); dropped by every call that changes the store
   VcMihIndex* mih = nullptr;
   uint64_t n_indexed = 0;   // records the index covers; n_indexed < n: the index is STALE (kept for vc_update_index, served to no one)
   VcRadiusWork radius_work;
@@ -163,6 +171,7 @@ void read_knobs(VcKnobs* k) {
   if (const char* v = getenv("VC_FILTER_WINDOW")) k->filter_window = (uint32_t)strtoul(v, nullptr, 10);
   if (const char* v = getenv("VC_SCOPE_SCRATCH")) k->scope_scratch = strtoull(v, nullptr, 10);
   if (const char* v = getenv("VC_SCOPE_WINDOW")) k->scope_window = (uint32_t)strtoul(v, nullptr, 10);
+  if (const char* v = getenv("VC_SCAN_STREAM_FREE")) { k->stream_free_set = true; k->stream_free = strtoull(v, nullptr, 10); }
 }
 
 static int bind_device(vc_engine* e) {
@@ -176,6 +185,10 @@ static void drop_index(vc_engine* e) {
   if (e->mih) vc_mih_free(e->mih);
   e->mih = nullptr;
   e->n_indexed = 0;
+}
+// the scan stream describes the store as it was built from: every call that changes the store drops it (device of e current)
+static void drop_scan_stream(vc_engine* e) {
+  if (e->sstream.built()) vc_scan_stream_free(&e->sstream);
 }
 static hipStream_t caller_stream(const vc_engine* e, void* stream) {   // NULL = the HIP null stream
   return stream == VC_STREAM_OWN ? e->own_stream : (hipStream_t)stream;
@@ -312,6 +325,7 @@ int vc_destroy(vc_engine* e) {
   (void)hipSetDevice(e->device);
   if (e->own_stream) (void)hipStreamSynchronize(e->own_stream);
   if (e->mih) vc_mih_free(e->mih);
+  drop_scan_stream(e);
   vc_radius_work_free(&e->radius_work);
   (void)hipFree(e->d_cols);
   (void)hipFree(e->d_stage);
@@ -354,6 +368,7 @@ int vc_add_codes(vc_engine* e, const void* codes, uint64_t n) {
   if (e->n + n > e->cfg.capacity) return fail(e, VC_ERR_CAPACITY, "add %llu codes: %llu + n > capacity %llu", (unsigned long long)n, (unsigned long long)e->n, (unsigned long long)e->cfg.capacity);
   int rc = bind_device(e);
   if (rc) return rc;
+  drop_scan_stream(e);
   const size_t rec = e->bits / 8;
   const uint64_t batch = std::max<uint64_t>(1, (64ull << 20) / rec);
   const uint8_t* src = (const uint8_t*)codes;
@@ -373,6 +388,7 @@ int vc_add_synthetic(vc_engine* e, uint64_t n, uint64_t seed, uint32_t kind, uin
   if (e->n + n > e->cfg.capacity) return fail(e, VC_ERR_CAPACITY, "add_synthetic beyond capacity");
   int rc = bind_device(e);
   if (rc) return rc;
+  drop_scan_stream(e);
   VC_HIP(e, vc_launch_fill_synth(e->d_cols, e->stride, e->W, e->n, n, (uint64_t)e->cfg.id_base + e->n, seed, kind, n_centres, max_flips, e->stream));
   VC_HIP(e, hipStreamSynchronize(e->stream));
   e->n += n;   // (an index, if any, is stale from here on: live_index)
@@ -616,6 +632,7 @@ struct LinearSearch {
   uint32_t k;
   LinearPlan plan;
   LinearState st;
+  bool stream_ok = false;   // the call is a plain k-NN search (vc_search_knn, vc_search_knn_dev*): its small tiles may take the scan stream
 
   // tile: 0 = the engine's (vc_config.query_tile / VC_QUERY_TILE, else fitted to the database), or the caller's own
   LinearSearch(vc_engine* e_, uint32_t nq, uint32_t k_, uint32_t tile = 0)
@@ -739,12 +756,16 @@ struct LinearSearch {
 
   // The verify launch between two events.  VC_FLAG_LEAN_TIMING with vc_config.timing_sample = N > 1: only every N-th verify
   // launch is bracketed (an event record is a barrier packet, ~4-5 us each; a 125 M-code shard step is 0.35 ms)
-  int timed_scan_launch(const VcScanParams& p, const VcScanShape& sh) {
+  int timed_scan_launch(const VcScanParams& p, const VcScanShape& sh, bool over_stream = false) {
     hipEvent_t a = nullptr, b = nullptr;
     const uint32_t every = (e->cfg.flags & VC_FLAG_LEAN_TIMING) ? std::max(e->cfg.timing_sample, 1u) : 1u;
     if (e->scan_event_tick++ % every == 0) ev_pair(e, &a, &b);
     if (a) VC_HIP(e, hipEventRecord(a, e->stream));
-    if (e->knobs.scan_trace) {
+    if (over_stream) {
+      const uint64_t resident_mb = e->knobs.resident_mb < 0 ? VC_RESIDENT_MB_DEFAULT : (uint64_t)e->knobs.resident_mb;
+      VC_HIP(e, vc_launch_scan_stream(p, e->sstream, resident_mb, e->n_cu, e->scan_blocks, &e->knobs, e->stream));
+      e->sstream.launches++;
+    } else if (e->knobs.scan_trace) {
       const int rc = dump_scan_trace(p, sh);
       if (rc) return rc;
     } else {
@@ -753,7 +774,7 @@ struct LinearSearch {
     if (a) {
       VC_HIP(e, hipEventRecord(b, e->stream));
       e->ev_scans.emplace_back(a, b);
-      e->scan_bytes += e->n * (e->bits / 8);
+      e->scan_bytes += over_stream ? vc_stream_scan_bytes(e->sstream.plan) : e->n * (e->bits / 8);
     }
     return VC_OK;
   }
@@ -761,7 +782,10 @@ struct LinearSearch {
   // one verify launch for a tile whose thresholds are set (or cut by the launch itself: LinearTile::d_shist)
   int verify(const LinearTile& t) {
     const VcScanShape sh = vc_scan_pick_shape(e->W, t.qt, &e->knobs, plan.shape_n(t.qt));
-    return timed_scan_launch(scan_params(t, sh), sh);
+    // the scan stream serves the small tiles of a plain k-NN search over 128-bit codes; host-driven recovery probes
+    // (d_limit) and everything else read the store's own columns
+    const bool over_stream = stream_ok && e->sstream.built() && e->bits == 128 && !t.d_limit && vc_scan_stream_tile(t.qt, &e->knobs);
+    return timed_scan_launch(scan_params(t, sh), sh, over_stream);
   }
 
   // rings -> rows and counts (UINT32_MAX == the ring overflowed: the row is only an upper bound until it is recovered)
@@ -1023,10 +1047,12 @@ int vc_engine_radius_dev(vc_engine* e, const void* d_queries, uint32_t nq, uint3
 
 // the search of vc_search_knn_dev_stats on e->stream, inside the caller's StreamCall
 static int knn_dev_run(vc_engine* e, const void* d_queries, uint32_t nq, uint32_t k, uint32_t mode, uint64_t* d_out, uint32_t* cnt,
-                       vc_query_stats* d_stats) {
+                       vc_query_stats* d_stats, bool stream_ok = false) {
   int rc;
   if (mode == VC_MODE_LINEAR) {
-    rc = LinearSearch(e, nq, k).run((const uint64_t*)d_queries, nq, d_out, cnt);
+    LinearSearch ls(e, nq, k);
+    ls.stream_ok = stream_ok;
+    rc = ls.run((const uint64_t*)d_queries, nq, d_out, cnt);
     if (rc == VC_OK && d_stats) {
       hipLaunchKernelGGL(vc_linear_stats_kernel, dim3((nq + 255) / 256), dim3(256), 0, e->stream, (const uint32_t*)cnt, nq, e->n, d_stats);
       if (hipGetLastError() != hipSuccess) rc = fail(e, VC_ERR_HIP, "vc_linear_stats_kernel launch failed");
@@ -1049,7 +1075,7 @@ int vc_search_knn_dev_stats(vc_engine* e, const void* d_queries, uint32_t nq, ui
   if ((rc = bind_device(e))) return rc;
   if ((rc = grow(e, &e->d_cnt, &e->cnt_bytes, (size_t)nq * 8))) return rc;   // outside the timed bracket; grow() uses no stream
   const StreamCall call(e, caller_stream(e, stream));
-  return knn_dev_run(e, d_queries, nq, k, mode, d_out, d_counts ? d_counts : e->d_cnt, d_stats);
+  return knn_dev_run(e, d_queries, nq, k, mode, d_out, d_counts ? d_counts : e->d_cnt, d_stats, true);
 }
 
 }  // extern "C"
@@ -1702,7 +1728,9 @@ int vc_search_knn(vc_engine* e, const void* queries, uint32_t nq, uint32_t k, ui
   std::vector<vc_query_stats> st;
   timing_begin(e);
   if (mode == VC_MODE_LINEAR) {
-    rc = LinearSearch(e, nq, k).run(e->d_q, nq, e->d_out, e->d_cnt);
+    LinearSearch ls(e, nq, k);
+    ls.stream_ok = true;
+    rc = ls.run(e->d_q, nq, e->d_out, e->d_cnt);
   } else {
     if (stats) st.resize(nq);      // (the statistics cost four read-backs and a wait per launch: only when asked for)
     const VcMihScanFallback fb{mih_scan_fallback, e, e->n_cu};
@@ -1804,6 +1832,51 @@ int vc_update_index(vc_engine* e) {
   return rc;
 }
 
+// ---- the prefix-sorted scan stream (vc_scan_stream.hip) ---------------------------------------------------------------
+int vc_build_scan_stream(vc_engine* e) {
+  if (!e) return VC_ERR_INVALID;
+  if (e->bits != 128) return fail(e, VC_ERR_INVALID, "the scan stream is built for 128-bit codes only (bits = %u)", e->bits);
+  int rc = bind_device(e);
+  if (rc) return rc;
+  VC_HIP(e, hipStreamSynchronize(e->stream));   // no search still reads the stream that is about to go
+  // the memory rule sees the memory as it is with the old stream still held: a refused build leaves the engine as it was
+  size_t free_b = 0, total_b = 0;
+  bool have_free = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+  if (!have_free) (void)hipGetLastError();
+  uint64_t free_bytes = (uint64_t)free_b + (e->sstream.built() ? e->sstream.plan.bytes : 0);
+  if (e->knobs.stream_free_set) { have_free = true; free_bytes = e->knobs.stream_free; }   // test knob VC_SCAN_STREAM_FREE
+  if (!vc_stream_fits(vc_stream_plan(e->n, vc_radix_sort_work_words(e->n)), have_free, free_bytes))
+    return fail(e, VC_ERR_NOMEM, "scan stream of %llu records does not fit %u %% of %llu free bytes", (unsigned long long)e->n,
+                VC_STREAM_MEM_SHARE, (unsigned long long)free_bytes);
+  drop_scan_stream(e);
+  const hipError_t r = vc_scan_stream_build(e->d_cols, e->stride, e->n, have_free, free_bytes, &e->sstream, e->stream);
+  if (r == hipErrorOutOfMemory) (void)hipGetLastError();
+  if (r != hipSuccess)
+    return fail(e, r == hipErrorOutOfMemory ? VC_ERR_NOMEM : VC_ERR_HIP, "scan stream build: %s", hipGetErrorString(r));
+  return VC_OK;
+}
+
+int vc_scan_stream_info(vc_engine* e, vc_scan_stream_state* info) {
+  if (!e || !info) return VC_ERR_INVALID;
+  memset(info, 0, sizeof *info);
+  if (!e->sstream.built()) return VC_OK;
+  info->built = 1;
+  info->items = e->sstream.plan.n;
+  info->granules = e->sstream.plan.granules;
+  info->bytes = e->sstream.plan.bytes;
+  info->launches = e->sstream.launches;
+#if VC_SCAN_STREAM_DIAG
+  int rc = bind_device(e);
+  if (rc) return rc;
+  uint32_t c[2] = {0, 0};
+  VC_HIP(e, hipStreamSynchronize(e->stream));
+  VC_HIP(e, hipMemcpy(c, e->sstream.d_diag, 8, hipMemcpyDeviceToHost));
+  info->bound_passes = c[0];
+  info->exact_passes = c[1];
+#endif
+  return VC_OK;
+}
+
 }  // extern "C"
 
 // ---- removal: the store and its index cut down to the surviving records ---------------------------------------------------------
@@ -1846,6 +1919,7 @@ static int retain_run(vc_engine* e, const uint32_t* d_sel, uint32_t kind, uint64
     return VC_OK;
   }
   const bool had_live = live_index(e) != nullptr;
+  drop_scan_stream(e);
   if (K == 0) {
     for (uint32_t j = 0; j < e->W; ++j) VC_HIP(e, hipMemsetAsync(e->d_cols + j * e->stride, 0, N * 8, s));
   } else {
@@ -1884,6 +1958,7 @@ int vc_engine_append_from(vc_engine* e, vc_engine* src, uint64_t first, uint64_t
   if (count == 0) return VC_OK;
   int rc = bind_device(e);
   if (rc) return rc;
+  drop_scan_stream(e);
   for (uint32_t j = 0; j < e->W; ++j) {
     uint64_t* dst = e->d_cols + j * e->stride + e->n;
     const uint64_t* from = src->d_cols + j * src->stride + first;

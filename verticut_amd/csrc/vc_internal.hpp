@@ -3,6 +3,7 @@
 #include <functional>
 
 #include "vc_common.hpp"
+#include "vc_scan_stream_plan.hpp"
 
 // Developer / test knobs from the environment, read ONCE per engine at vc_create (never on a launch path).
 struct VcKnobs {
@@ -53,6 +54,8 @@ struct VcKnobs {
   uint32_t filter_window = 1u << 20;          // VC_FILTER_WINDOW: allowed ids per window of the pre-filter route (0 or above 2^24: the default)
   uint64_t scope_scratch = 64ull << 20;       // VC_SCOPE_SCRATCH: bytes of (query, slice) counters a sub-batch of vc_search_knn_scoped* may hold (vc_scope_plan.hpp)
   uint32_t scope_window = 1u << 20;           // VC_SCOPE_WINDOW: positions of the scope-sorted list per window (0 or above 2^24: the default)
+  bool stream_free_set = false;              // VC_SCAN_STREAM_FREE (tests): the free device memory, in bytes, that vc_build_scan_stream's memory rule is given
+  uint64_t stream_free = 0;
 };
 void read_knobs(VcKnobs* k);   // vc_engine.hip: the one place that reads the environment (once per engine / sharded handle)
 
@@ -112,6 +115,24 @@ bool vc_scan_is_small(uint32_t W, uint32_t qt, const VcKnobs* knobs);
 // grid = min(chunks, CUs x resident blocks per CU, want_blocks if non-zero); sh: the shape p.nchunks was derived from
 hipError_t vc_launch_scan(const VcScanParams& p, const VcScanShape& sh, uint32_t W, uint32_t n_cu, uint32_t want_blocks,
                           const VcKnobs* knobs, hipStream_t s);
+// ---- the prefix-sorted 96-bit scan stream of a 128-bit store (vc_scan_stream.hip; arithmetic: vc_scan_stream_plan.hpp) --------
+struct VcScanStream {
+  uint32_t* d_base = nullptr;   // the one allocation, carved by `plan`; null = not built
+  uint32_t* d_diag = nullptr;   // diagnostic build: the last launch's two counters (VcScanParams::st_diag)
+  VcStreamPlan plan{};
+  uint64_t launches = 0;        // stream verify launches since the build
+  bool built() const { return d_base != nullptr; }
+};
+// true when a tile of qt queries over 128-bit codes may take the stream form: the rule of the small-tile form
+bool vc_scan_stream_tile(uint32_t qt, const VcKnobs* knobs);
+// Builds the stream of the n records behind cols (W = 2) on s and waits for it; *out must be unbuilt.  have_free / free_bytes:
+// what the memory rule is given.  hipErrorOutOfMemory: the rule or an allocation refused, nothing is held.
+hipError_t vc_scan_stream_build(const uint64_t* cols, uint64_t stride, uint64_t n, bool have_free, uint64_t free_bytes, VcScanStream* out,
+                                hipStream_t s);
+void vc_scan_stream_free(VcScanStream* st);   // on the current device
+// the stream form of the verify launch: p as for vc_launch_scan (its extent is replaced by the stream's), 1 <= p.qt <= 8
+hipError_t vc_launch_scan_stream(VcScanParams p, const VcScanStream& st, uint64_t resident_mb, uint32_t n_cu, uint32_t want_blocks,
+                                 const VcKnobs* knobs, hipStream_t s);
 // ring -> sorted top-k (per query); out padded with VC_PACK_INF
 // d_tau (nullable): final per-query distance thresholds of the scan -- farther entries are dropped before sorting
 hipError_t vc_launch_select_ring(const uint64_t* d_buf, uint32_t cap, const uint32_t* d_count, const uint32_t* d_tau, uint32_t qs,

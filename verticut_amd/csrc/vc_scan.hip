@@ -383,8 +383,8 @@ __device__ __forceinline__ void vc_scan_slow(const VcScanRare& p, const vc_u64x2
 
 // Counted wait for hand-issued tile loads: at most N vector-memory operations younger than the tile may still be in
 // flight.  The tile's registers pass through the asm as read-write operands, so every use is ordered behind the wait.
-template <int N, int U, int W>
-__device__ __forceinline__ void vc_tile_wait(vc_u64x2 (&r)[U][W]) {
+template <int N, class T, int U, int W>
+__device__ __forceinline__ void vc_tile_wait(T (&r)[U][W]) {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N < 63 ? N : 63));   // 6-bit counter on gfx9; waiting for fewer is only stricter
 #pragma unroll
   for (int u = 0; u < U; ++u)
@@ -620,6 +620,220 @@ __global__ void __launch_bounds__(BLK, MINW ? MINW : (BLK == 512 ? 2 : ((W >= 4 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (p.trace && threadIdx.x == 0) p.trace[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
 #endif
+}
+
+// ------------------------------------------------------------------------------------------
+// The small-tile form over the prefix-sorted scan stream of a 128-bit store (layout and arithmetic: vc_scan_stream_plan.hpp).
+//
+// The records lie sorted by their key word, so the 256 records of one wave-load -- a granule -- share the leading key bits its
+// header names.  The hot loop streams the other three words only (12 bytes per record, a lane owns FOUR consecutive records per
+// 16-byte load, 6 loads per lane and 2048-record chunk) and runs 3 xor + 3 accumulating v_bcnt per record: the key enters as
+// the wave-uniform start value of the chain, tau + the most key bits that can still match (vc_stream_chain_start), computed
+// with scalar instructions from the header and handed to the first v_bcnt as its SGPR accumulate operand.  The chain is then
+// an UPPER bound of tau + matching bits, i.e. the test is a lower bound on the distance, and it is the same OR-reduce and one
+// compare per query as in vc_scan_kernel's small-tile form.  Where it fires, the items whose lower bound passes read their
+// key word and finish the exact distance; survivors read perm[] for their id and append as vc_scan_slow does: ring, cursor,
+// histogram and tau keep their contract, so select, recovery and the clean hand-back follow unchanged.
+// Everything else is vc_scan_kernel's machinery: persistent grid, hand-issued loads from an SGPR base (nt beyond the
+// resident prefix), counted vmcnt over two register buffers, complemented query words in LDS, one rare-path copy behind the
+// query loop.  The headers of the NEXT chunk are fetched with the tile (scalar loads the compiler counts itself).
+// ------------------------------------------------------------------------------------------
+typedef uint32_t vc_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t vc_u32x2 __attribute__((ext_vector_type(2)));
+#define VC_ST_U 2   // wave-loads per column and chunk: VC_STREAM_CHUNK = VC_ST_U * 256 threads * 4 records
+static_assert(VC_STREAM_CHUNK == VC_ST_U * 256 * 4 && VC_STREAM_GRANULE == VC_WAVE * 4, "a chunk is VC_ST_U loads of 256 lanes x 4 records, a granule one wave-load");
+
+// v_bcnt_u32_b32 with a wave-uniform (SGPR) accumulate operand: the start of a chain costs no instruction of its own
+__device__ __forceinline__ uint32_t vc_bcnt_acc_s(uint32_t x, uint32_t acc_uniform) {
+  uint32_t r;
+  asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "s"(acc_uniform));
+  return r;
+}
+
+// Exact check of the stream form for query q: the caller's register tile one wave-load at a time.  sw: the complemented query
+// words in LDS ([q][4]: key, t0, t1, t2).  Nothing but wave-uniform scalars lives across the wave-loads.
+__device__ __forceinline__ void vc_scan_slow_stream(const VcScanRare& p, const VcScanParams& sp, const vc_u32x4 (&r)[VC_ST_U][3],
+                                                    const VcStreamHeader (&h)[VC_ST_U], const uint32_t* sw, uint32_t q, uint64_t chunk_base,
+                                                    uint32_t* st) {
+  const uint32_t lane = vc_lane();
+  uint32_t tid = threadIdx.x;   // opaque inside the rare branch, as in vc_scan_slow
+  asm volatile("" : "+v"(tid));
+  uint32_t* const tau_q = p.tau + (size_t)q * p.qs;
+  uint32_t t = min(vc_ld_relaxed(tau_q), st[q]);
+  uint64_t* ring = p.buf + (uint64_t)q * p.cap;
+  uint32_t* hist = p.hist + (uint64_t)q * p.hist_stride;
+  const uint32_t qk = ~sw[q * 4], q0 = ~sw[q * 4 + 1], q1 = ~sw[q * 4 + 2], q2 = ~sw[q * 4 + 3];
+  uint32_t seen = 0;
+  bool recut = false;
+#pragma unroll
+  for (int u = 0; u < VC_ST_U; ++u) {
+    const uint32_t klb = vc_stream_key_bound(h[u], qk);
+    const uint64_t pos0 = chunk_base + (uint64_t)u * 4 * 256 + 4 * tid;   // a multiple of 4 below the padded size
+    uint32_t dt[4];
+    bool c[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      dt[i] = (uint32_t)__builtin_popcount(r[u][0][i] ^ q0) + (uint32_t)__builtin_popcount(r[u][1][i] ^ q1) + (uint32_t)__builtin_popcount(r[u][2][i] ^ q2);
+      c[i] = dt[i] + klb <= t && pos0 + i < p.n;
+    }
+    const bool anyc = c[0] || c[1] || c[2] || c[3];
+    if (__ballot(anyc) == 0) continue;
+    vc_u32x4 kw = {0, 0, 0, 0};
+    if (anyc) kw = *reinterpret_cast<const vc_u32x4*>(sp.st_key + pos0);
+    uint32_t d[4], cnt = 0;
+    bool ok[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      d[i] = dt[i] + (uint32_t)__builtin_popcount(kw[i] ^ qk);
+      ok[i] = c[i] && d[i] <= t;
+      cnt += (uint32_t)ok[i];
+    }
+#if VC_SCAN_DIAGNOSTICS
+    if (sp.st_diag && anyc) {
+      atomicAdd(sp.st_diag + 0, (uint32_t)c[0] + (uint32_t)c[1] + (uint32_t)c[2] + (uint32_t)c[3]);
+      if (cnt) atomicAdd(sp.st_diag + 1, cnt);
+    }
+#endif
+    if (__ballot(cnt != 0) == 0) continue;
+    vc_u32x4 id = {0, 0, 0, 0};
+    if (cnt) id = *reinterpret_cast<const vc_u32x4*>(sp.st_perm + pos0);
+    uint32_t total;
+    uint32_t slot = vc_wave_excl_scan(cnt, total);
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(p.count + (size_t)q * p.qs, total);
+    base = __builtin_amdgcn_readfirstlane(base);
+    slot += base;
+    seen = base + total;
+    recut = recut || (base / VC_SCAN_RECUT_EVERY != seen / VC_SCAN_RECUT_EVERY) || (base < p.k && seen >= p.k);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (ok[i]) {
+        if (slot < p.cap) ring[slot] = vc_pack(d[i], p.id_base + id[i]);
+        ++slot;
+        atomicAdd(hist + d[i], 1u);
+      }
+    }
+  }
+  if (seen >= p.k && recut) {   // the re-cut rule of vc_scan_slow
+    const uint32_t cut = vc_hist_cut(hist, t + 1, p.k, true);
+    if (cut < t) {
+      t = cut;
+      if (lane == 0) atomicMin(tau_q, t);
+    }
+  }
+  if (lane == 0) st[q] = t;
+}
+
+template <int QT>
+__global__ void __launch_bounds__(256, VC_SCAN_SMALL_WAVES) vc_scan_kernel_stream(const VcScanParams p) {
+  constexpr int BLK = 256, U = VC_ST_U, C = 3;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint64_t* sq = (uint64_t*)smem;                           // [QT][2] complemented query words
+  uint32_t* st = (uint32_t*)(smem + (size_t)QT * 16);       // [QT]    block-local copy of tau
+  for (uint32_t i = threadIdx.x; i < QT * 2; i += BLK) sq[i] = ~p.queries[i];
+  if (p.shist) {   // bootstrap folded into the prologue, as in vc_scan_kernel
+    for (uint32_t q = threadIdx.x / VC_WAVE; q < QT; q += BLK / VC_WAVE) {
+      uint32_t cut = vc_hist_cut(p.shist + (uint64_t)q * p.hist_stride, p.bits + 1, p.k, false, p.shist_copies, p.shist_cstride);
+      if (cut == 0xFFFFFFFFu) cut = p.bits;
+      if ((threadIdx.x & (VC_WAVE - 1)) == 0) {
+        st[q] = cut;
+        if (blockIdx.x == 0) atomicMin(p.tau + (size_t)q * p.qs, cut);
+      }
+    }
+  } else {
+    for (uint32_t i = threadIdx.x; i < QT; i += BLK) st[i] = vc_ld_relaxed(p.tau + (size_t)i * p.qs);
+  }
+  __syncthreads();
+
+  const VcScanRare rare{p.n, p.tau, p.count, p.hist, p.buf, nullptr, p.id_base, p.k, p.cap, p.hist_stride, p.qs, nullptr};
+  const uint32_t* sw = (const uint32_t*)sq;
+  uint32_t ck[QT];   // the complemented key word of every query, wave-uniform (SGPRs)
+#pragma unroll
+  for (int q = 0; q < QT; ++q) ck[q] = __builtin_amdgcn_readfirstlane(sw[q * 4]);
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / VC_WAVE);
+  // the headers are constant while the kernel runs: through the constant address space a uniform read of them is a scalar load
+  // whatever the kernel stores elsewhere
+  typedef const __attribute__((address_space(4))) vc_u32x2* hdr_ptr;
+  const hdr_ptr hdr = (hdr_ptr)(uintptr_t)p.st_hdr;
+
+  vc_u32x4 ra[U][C], rb[U][C];
+  VcStreamHeader ha[U], hb[U];
+  const uint64_t G = gridDim.x;
+  uint64_t pf = blockIdx.x;   // prefetch cursor, as in vc_scan_kernel: past the block's last chunk it stays put
+  const uint32_t lane_off = threadIdx.x * (uint32_t)sizeof(vc_u32x4);
+  auto load = [&](vc_u32x4(&r)[U][C], VcStreamHeader(&h)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int j = 0; j < C; ++j) {
+        const uint32_t* sbase = p.st_tail + (uint64_t)j * p.st_stride + pf * VC_STREAM_CHUNK + (uint64_t)u * 4 * BLK;
+        const uint32_t* sb;
+        if (pf < p.resident)
+          asm volatile("s_mov_b64 %1, %3\n\tglobal_load_dwordx4 %0, %2, %1" : "=&v"(r[u][j]), "=&s"(sb) : "v"(lane_off), "s"(sbase));
+        else
+          asm volatile("s_mov_b64 %1, %3\n\tglobal_load_dwordx4 %0, %2, %1 nt" : "=&v"(r[u][j]), "=&s"(sb) : "v"(lane_off), "s"(sbase));
+      }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const vc_u32x2 v = hdr[pf * (VC_STREAM_CHUNK / VC_STREAM_GRANULE) + (uint64_t)u * (BLK / VC_WAVE) + wave];
+      h[u] = VcStreamHeader{v.x, v.y};
+    }
+    pf += pf + G < p.nchunks ? G : 0;
+  };
+
+  auto verify = [&](const vc_u32x4(&r)[U][C], const VcStreamHeader(&h)[U], uint64_t chunk) {
+    uint32_t slack[U];   // key bits the header leaves unknown: they count as matching
+#pragma unroll
+    for (int u = 0; u < U; ++u) slack[u] = 32u - vc_stream_popc(h[u].mask);
+    uint32_t hm = 0;
+    uint32_t wq[2][3], tq[2];   // the LDS reads of query q + 1 are in flight while query q is verified
+#pragma unroll
+    for (int j = 0; j < 3; ++j) wq[0][j] = sw[1 + j];
+    tq[0] = st[0];
+#pragma unroll
+    for (int q = 0; q < QT; ++q) {
+      if (q + 1 < QT) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) wq[(q + 1) & 1][j] = sw[(q + 1) * 4 + 1 + j];
+        tq[(q + 1) & 1] = st[q + 1];
+      }
+      const uint32_t(&w)[3] = wq[q & 1];
+      const uint32_t tau = __builtin_amdgcn_readfirstlane(tq[q & 1]);
+      uint32_t orv = 0;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const uint32_t start = tau + slack[u] + vc_stream_popc((ck[q] ^ h[u].prefix) & h[u].mask);   // = vc_stream_chain_start
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          uint32_t d = vc_bcnt_acc_s(r[u][0][i] ^ w[0], start);
+          d = vc_bcnt_acc(r[u][1][i] ^ w[1], d);
+          d = vc_bcnt_acc(r[u][2][i] ^ w[2], d);
+          orv |= d;
+        }
+      }
+      if (__ballot(orv >= 128u) != 0) hm |= 1u << q;
+    }
+    while (hm) {
+      const uint32_t q = (uint32_t)__builtin_ctz(hm);
+      hm &= hm - 1u;
+      vc_scan_slow_stream(rare, p, r, h, sw, q, chunk * VC_STREAM_CHUNK, st);
+    }
+  };
+
+  uint64_t chunk = blockIdx.x;
+  if (chunk >= p.nchunks) return;
+  constexpr int T = U * C;   // loads per tile
+  load(ra, ha);
+  for (;;) {
+    load(rb, hb);
+    vc_tile_wait<T>(ra);
+    verify(ra, ha, chunk);
+    if ((chunk += G) >= p.nchunks) break;
+    load(ra, ha);
+    vc_tile_wait<T>(rb);
+    verify(rb, hb, chunk);
+    if ((chunk += G) >= p.nchunks) break;
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1400,6 +1614,54 @@ hipError_t vc_launch_scan(const VcScanParams& p, const VcScanShape& sh, uint32_t
   if (p.nchunks == 0 || p.qt == 0) return hipSuccess;
   const bool tr = knobs && knobs->scan_shape_trace;
   return dispatch_w(W, [&](auto w) { return launch_scan_w<decltype(w)::value>(p, sh, n_cu, want_blocks, tr, s); });
+}
+
+bool vc_scan_stream_tile(uint32_t qt, const VcKnobs* knobs) {
+  if (qt == 0 || (VC_SCAN_DIAGNOSTICS && knobs && (knobs->scan_wrap || knobs->scan_diag))) return false;
+  return vc_scan_shape_is_small(vc_scan_pick_shape(2, qt, knobs), 2, qt);
+}
+
+hipError_t vc_launch_scan_stream(VcScanParams p, const VcScanStream& st, uint64_t resident_mb, uint32_t n_cu, uint32_t want_blocks,
+                                 const VcKnobs* knobs, hipStream_t s) {
+  if (!st.built() || p.qt == 0 || p.qt > 8 || p.n != st.plan.n) return hipErrorInvalidValue;
+  if (st.plan.chunks == 0) return hipSuccess;
+  p.nchunks = st.plan.chunks;
+  p.resident = (resident_mb << 20) / (VC_STREAM_CHUNK * 12);
+  p.limit = nullptr;
+  p.st_tail = st.d_base + st.plan.t0;
+  p.st_key = st.d_base + st.plan.key;
+  p.st_perm = st.d_base + st.plan.perm;
+  p.st_hdr = st.d_base + st.plan.hdr;
+  p.st_stride = st.plan.stride;
+  p.st_diag = nullptr;
+#if VC_SCAN_DIAGNOSTICS
+  p.st_diag = st.d_diag;
+  if (st.d_diag) {
+    const hipError_t r = hipMemsetAsync(st.d_diag, 0, 8, s);
+    if (r != hipSuccess) return r;
+  }
+#endif
+#define VC_LAUNCH_STREAM(QT_)                                                                                   \
+  {                                                                                                             \
+    auto kern = vc_scan_kernel_stream<QT_>;                                                                     \
+    const size_t lds_q = (size_t)QT_ * (2 * 8 + 4);                                                             \
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(p.nchunks, resident_grid(kern, 256, lds_q, n_cu, want_blocks)); \
+    if (knobs && knobs->scan_shape_trace)                                                                       \
+      fprintf(stderr, "[scan shape] stream QT=%d grid=%u nchunks=%llu qt=%u\n", (int)(QT_), grid, (unsigned long long)p.nchunks, p.qt); \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_q, s, p);                                               \
+    return hipGetLastError();                                                                                   \
+  }
+  switch (p.qt) {
+    case 1: VC_LAUNCH_STREAM(1)
+    case 2: VC_LAUNCH_STREAM(2)
+    case 3: VC_LAUNCH_STREAM(3)
+    case 4: VC_LAUNCH_STREAM(4)
+    case 5: VC_LAUNCH_STREAM(5)
+    case 6: VC_LAUNCH_STREAM(6)
+    case 7: VC_LAUNCH_STREAM(7)
+    default: VC_LAUNCH_STREAM(8)
+  }
+#undef VC_LAUNCH_STREAM
 }
 
 hipError_t vc_launch_select_ring(const uint64_t* d_buf, uint32_t cap, const uint32_t* d_count, const uint32_t* d_tau,

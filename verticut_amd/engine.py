@@ -41,7 +41,7 @@ EXPORTS = [
     "vc_get_codes_dev", "vc_search_knn_ids", "vc_search_knn_ids_dev",
     "vc_sharded_get_codes_dev", "vc_sharded_search_knn_ids", "vc_sharded_search_knn_ids_dev",
     "vc_search_radius_ids", "vc_search_radius_ids_dev", "vc_sharded_search_radius_ids", "vc_sharded_search_radius_ids_dev",
-    "vc_update_index", "vc_sharded_update_index",
+    "vc_update_index", "vc_sharded_update_index", "vc_build_scan_stream", "vc_scan_stream_info",
     "vc_cluster_radius", "vc_cluster_radius_dev", "vc_sharded_cluster_radius", "vc_sharded_cluster_radius_dev",
     "vc_retain", "vc_retain_dev", "vc_sharded_retain", "vc_sharded_retain_dev",
     "vc_leaders_radius", "vc_leaders_radius_dev", "vc_sharded_leaders_radius", "vc_sharded_leaders_radius_dev",
@@ -170,6 +170,17 @@ class VcTiming(C.Structure):
     ]
 
 
+class VcScanStreamState(C.Structure):
+    """vc_scan_stream_state: what vc_scan_stream_info reports of an engine's prefix-sorted scan stream"""
+    _fields_ = [
+        ("built", C.c_uint32), ("reserved", C.c_uint32), ("items", C.c_uint64), ("granules", C.c_uint64), ("bytes", C.c_uint64),
+        ("launches", C.c_uint64), ("bound_passes", C.c_uint64), ("exact_passes", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
 class VcError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("verticut_gpu error %d: %s" % (code, msg))
@@ -209,6 +220,8 @@ def load_library():
     L.vc_get_code.argtypes = [vp, u32, vp]
     L.vc_build_index.argtypes = [vp]
     L.vc_update_index.argtypes = [vp]
+    L.vc_build_scan_stream.argtypes = [vp]
+    L.vc_scan_stream_info.argtypes = [vp, C.POINTER(VcScanStreamState)]
     L.vc_get_bucket.argtypes = [vp, u32, u32, vp, vp, u32, C.POINTER(u32)]
     L.vc_bitmap_test.argtypes = [vp, u32, u32, C.POINTER(C.c_int)]
     L.vc_bitmap_read.argtypes = [vp, u32, u64, u64, vp]
@@ -747,6 +760,19 @@ class Engine:
     def update_index(self):
         """Merge the records added since the index was built, loaded or last updated into it (a build when there is none)."""
         self._check(self._L.vc_update_index(self._h))
+
+    # -- scan stream
+    def build_scan_stream(self):
+        """Build the prefix-sorted scan stream of a 128-bit store (vc_build_scan_stream): linear k-NN passes of up to 8
+        queries then stream 12 bytes per record instead of 16, results unchanged.  About 20 bytes per record of device memory;
+        raises VcError with code VC_ERR_NOMEM when that does not fit.  Every call that changes the store drops it."""
+        self._check(self._L.vc_build_scan_stream(self._h))
+
+    def scan_stream_info(self):
+        """{built, items, granules, bytes, launches, bound_passes, exact_passes} of the scan stream (all 0 when there is none)"""
+        st = VcScanStreamState()
+        self._check(self._L.vc_scan_stream_info(self._h, C.byref(st)))
+        return st.as_dict()
 
     def get_bucket(self, table, index, cap=1 << 16, with_codes=True):
         """BaseProxy.get(HashIndex{table,index}) -> (ids, codes) or None (PROXY_NOT_FOUND)."""

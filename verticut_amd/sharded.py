@@ -8,6 +8,8 @@ inside the scan.
 
 torch is plumbing here (device buffers, streams, the process group); all compute goes through the C ABI.
 """
+import os
+
 import torch
 import torch.distributed as dist
 
@@ -27,17 +29,33 @@ class GpuBackend:
         kw["flags"] = kw.get("flags", 0) | vc.FLAG_LEAN_TIMING
         self.engine = vc.Engine(bits, capacity=max(capacity, 1), n_tables=n_tables, id_base=id_base, device=device, **kw)
         self.device = torch.device("cuda", device)
+        # A linear-only shard of 128-bit codes serves repeated k-NN passes over a fixed store: it gets the engine's prefix-sorted
+        # scan stream (Engine.build_scan_stream), built before the first search after a change.  VC_SCAN_STREAM=0 turns it off.
+        self._stream_wanted = bits == 128 and n_tables == 0 and os.environ.get("VC_SCAN_STREAM", "1") != "0"
+        self._stream_dirty = True
 
     def add_synthetic(self, n, seed, kind=vc.SYNTH_UNIFORM, n_centres=0, max_flips=0):
+        self._stream_dirty = True
         self.engine.add_synthetic(n, seed, kind, n_centres, max_flips)
 
     def add_codes(self, codes):
+        self._stream_dirty = True
         self.engine.add_codes(codes)
 
     def build_index(self):
         self.engine.build_index()
 
+    def _ensure_scan_stream(self):
+        self._stream_dirty = False
+        try:
+            self.engine.build_scan_stream()
+        except vc.VcError as ex:
+            if ex.code != vc.VC_ERR_NOMEM:   # a refused build is not an error: the shard serves from its columns as before
+                raise
+
     def local_topk(self, queries, k, out, counts, mode):
+        if self._stream_wanted and self._stream_dirty:
+            self._ensure_scan_stream()
         s = torch.cuda.current_stream(self.device).cuda_stream
         self.engine.search_knn_dev(queries.data_ptr(), queries.shape[0], k, out.data_ptr(), counts.data_ptr(), mode=mode,
                                    stream=s)
