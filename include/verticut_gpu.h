@@ -995,6 +995,101 @@ int vc_search_knn_scoped_dev(vc_engine* e, const void* d_queries, uint32_t nq, u
 int vc_search_knn_scoped(vc_engine* e, const void* queries, uint32_t nq, uint32_t k, uint32_t order, const uint32_t* scope,
                          const uint32_t* qscope, uint32_t flags, uint64_t* out, uint32_t* counts, vc_scope_stats* stats);
 
+/* ---- the exact k-NN graph of the store: vc_knn_graph* -------------------------------------------------------------------------------------
+ * "For every resident record its k nearest other records": the input of UMAP / t-SNE maps, label propagation, hubness checks and
+ * density-adaptive grouping (vc_cluster_knn* below).  The reference has no such call.  The host loop over vc_search_knn_ids_dev with
+ * VC_IDS_EXCLUDE_SELF does not give a usable graph: under VC_MODE_MIH_EXACT the members of a row at its last distance are genuine but
+ * not necessarily the smallest ids, so "j lists i" is not a function of the database; and every batch is a host round trip.
+ * THE RULE.  The call covers the positions p in [first, first + count); count == 0 means "to the end" (as vc_assign_nearest).  Row
+ * p - first holds the k smallest packed (dist << 32 | id) over all resident records OTHER than record id_base + p itself, ascending,
+ * padded with UINT64_MAX; d_counts[p - first] = min(k, N - 1).  Ties go to the smaller id.  Duplicates of the record are ordinary
+ * neighbours at distance 0.  Rows and counts are THE SAME WORDS in VC_MODE_LINEAR and VC_MODE_MIH_EXACT, for every batch, every
+ * k_first and both handle kinds: a function of the database, k and the range only.  VC_MODE_MIH_APPROX is refused.
+ * This holds wherever the rows underneath are the true nearest records: VC_MODE_LINEAR always, VC_MODE_MIH_EXACT without
+ * VC_FLAG_REF_SIGNEXT_KEYS and without VC_FLAG_REF_STOP_LITERAL4 at n_tables < 4.  Under those flags a row is what the rule below
+ * makes of the rows the underlying call returns.
+ * k lies in 1 .. VC_MAX_K - 1.  batch: ids per search underneath, 0 means 4096, any value >= 1 is legal.
+ * HOW.  Per batch of ids: the ids are made and their codes gathered on the device; then ROUNDS of the UNCHANGED k-NN search
+ * (vc_search_knn_dev) at k', and after each a settle kernel that judges every row:
+ *   - the entry equal to (uint64)own id -- distance 0, own id -- is dropped BY VALUE (binary search; vc_search_knn_ids' rule: with
+ *     more than k' - 1 duplicates of smaller id it is not in the row at all);
+ *   - a row that is not full (count < k') holds the whole store and is SETTLED;
+ *   - VC_MODE_LINEAR runs one round at k' = k + 1, whose full rows are settled: the scan's order is (dist, id);
+ *   - VC_MODE_MIH_EXACT starts at k' = k_first (0 means min(VC_MAX_K, 2 (k + 1)); any other value must lie in k + 1 .. VC_MAX_K)
+ *     and doubles k' up to VC_MAX_K.  A full row is settled only if at least k entries other than the own record lie BELOW the
+ *     row's last distance D -- the sure prefix of vc_search_knn_distinct*: the row holds every record nearer than D, of the ties
+ *     at D only some.  A count above k', or of UINT32_MAX, is an unsettled full row.  (So k_first = k + 1 is legal but settles
+ *     no full row: the last of k + 1 entries lies AT D, at most k - 1 others below it.  k + 2 is the smallest k' that can.);
+ *   - a settled query gets its first k stripped entries and its count, written straight into the caller's rows; the others form the
+ *     next round's list (an exclusive scan of a flag per query and a compacting gather: ascending, independent of block order);
+ *   - a query still unsettled at k' = VC_MAX_K -- more than about 8191 records tie at or below its k-th distance -- is answered by
+ *     the store's LINEAR k-NN at k + 1 and settled by the same kernel.  There is no truncation flag; stats.n_linear counts them.
+ * A linear row whose count is UINT32_MAX (the scan's ring-overflow recovery gave up, see vc_device_status) is passed on as it is,
+ * stripped, with that count, and counted in stats.n_gave_up; the host form answers such rows again through the handle's host k-NN.
+ * The k' rows of a round take at most VC_KGRAPH_SCRATCH bytes (environment, read at create; default 64 MiB; always at least one
+ * row): a round runs in sub-batches of max(1, budget / (8 k')) queries.
+ * OUTPUT: d_rows count * k packed; d_counts (count words, may be NULL); stats (HOST memory in both forms, may be NULL).
+ * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle or rows, k outside 1 .. VC_MAX_K - 1, a bad
+ * k_first, an approximate or unknown mode, first + count > N; VC_ERR_STATE in MIH mode without a current index.  N == 0, or an empty
+ * range (first == N), gives VC_OK and zero stats.
+ * WAITS.  VC_MODE_MIH_EXACT: once per round of a batch, for the length of the retry list (4 bytes), on top of the search's own; both
+ * modes: once at the end for the statistics when stats is given.  Results are valid in stream order.
+ * Scratch: grow-only buffers of the handle, this call's own; every word is written before it is read. */
+typedef struct vc_knn_graph_stats {   /* 32 bytes */
+  uint32_t n_rounds_max;  /* the most searches any record went through (the LINEAR answer after VC_MAX_K counts as one) */
+  uint32_t k_last;        /* the largest k' any round ran at (k + 1 in VC_MODE_LINEAR) */
+  uint64_t n_searched;    /* queries summed over the rounds of the mode's own search */
+  uint64_t n_linear;      /* VC_MODE_MIH_EXACT: queries answered by the LINEAR k-NN after k' = VC_MAX_K */
+  uint64_t n_gave_up;     /* rows the linear scan passed on with count UINT32_MAX */
+} vc_knn_graph_stats;
+int vc_knn_graph_dev(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first,
+                     uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_stats* stats, void* stream);
+/* The same for rows and counts in host memory: nothing is staged but the outputs, which come home; waits for them.  There is no
+ * `order` argument: graph rows are always ascending. */
+int vc_knn_graph(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first,
+                 uint64_t* rows, uint32_t* counts, vc_knn_graph_stats* stats);
+
+/* ---- components and in-degrees of the k-NN graph: vc_cluster_knn* -------------------------------------------------------------------------
+ * Density-adaptive grouping: where one radius is too tight in sparse regions and too loose in dense ones, "i and j list each other
+ * among their kk nearest" adapts to the local density.  Nothing is searched: the call reads a graph that vc_knn_graph* built and
+ * touches the store only for N and id_base, so it may be run for any kk <= k, flag and cap on one graph build.
+ * PRECONDITION.  d_rows (N * k) and d_counts (N) are what vc_knn_graph* wrote for this store over the full range first = 0, count = N
+ * with this k.  d_counts may be NULL: every row then holds min(k, N - 1) entries, which is what vc_knn_graph* writes.  A count above k
+ * (UINT32_MAX included) or an entry whose id is outside the store is found ON THE DEVICE and gives VC_ERR_INVALID -- vc_group_summary*'s
+ * protocol: one wait for the error word together with the stats; the outputs are then undefined.
+ * EDGES.  kk lies in 1 .. k.  Row i LISTS j iff j is among the first min(kk, count_i) entries of row i and dist(i, j) <= max_dist;
+ * max_dist >= bits means no cap.  With count_j < kk (N - 1 < kk) every other record is in row j: every entry is listed.
+ * OUTPUTS.  d_in_degree[j] (N words, may be NULL): the number of rows that list j, by exact integer atomics.  d_labels (N words):
+ * the connected components of the graph in which i and j are joined
+ *   VC_KNN_MUTUAL (flags 0)  iff each lists the other,
+ *   VC_KNN_EITHER            iff one lists the other;
+ * labels[i] is the smallest global id of record i's component, as vc_cluster_radius*: it feeds vc_group_summary*,
+ * vc_retain*(VC_RETAIN_ROOTS), vc_search_knn_distinct* and the filtered and scoped calls unchanged.  stats (HOST memory in both forms,
+ * may be NULL): n_edges the listed (directed) entries, n_mutual the unordered pairs that list each other (each counted once, from its
+ * smaller member; under both flags), n_clusters the components, max_in_degree.
+ * HOW.  Row j is exactly the min(k, N - 1) smallest packed (dist << 32 | id) over the other records and the distance is symmetric,
+ * so "j lists i among its first m" is the ONE COMPARE (d << 32 | i) <= row_j[m - 1], m = min(kk, count_j): no search inside row j.
+ * An init launch; one edge launch over the N * kk entries (the in-degree atomic, the compare, the union in the lock-free forest of
+ * vc_cluster_radius*); the flatten-and-count pass; the largest in-degree.  Every output word is a function of the graph and the
+ * call, not of the order in which the lanes ran.
+ * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle, rows or labels, k outside 1 .. VC_MAX_K - 1,
+ * kk outside 1 .. k, unknown flags.  N == 0 gives VC_OK and zero stats.  WAITS: one, at the end.
+ * Over a sharded store every pointer of the device form lives on the ROOT device. */
+#define VC_KNN_MUTUAL 0u
+#define VC_KNN_EITHER 1u
+typedef struct vc_cluster_knn_stats {   /* 32 bytes */
+  uint64_t n_edges;        /* listed entries (directed) */
+  uint64_t n_mutual;       /* unordered pairs that list each other */
+  uint64_t n_clusters;
+  uint32_t max_in_degree;
+  uint32_t pad;
+} vc_cluster_knn_stats;
+int vc_cluster_knn_dev(vc_engine* e, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags,
+                       uint32_t max_dist, uint32_t* d_labels, uint32_t* d_in_degree, vc_cluster_knn_stats* stats, void* stream);
+/* The same for host pointers: rows and counts are staged ON EVERY CALL, labels and in-degrees come home; waits for them. */
+int vc_cluster_knn(vc_engine* e, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags,
+                   uint32_t max_dist, uint32_t* labels, uint32_t* in_degree, vc_cluster_knn_stats* stats);
+
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
  * seconds); the affected queries kept d_counts[i] == UINT32_MAX.  0 in normal operation.  Synchronises the stream.
@@ -1264,6 +1359,20 @@ int vc_sharded_search_knn_scoped_dev(vc_sharded* h, const void* d_queries, uint3
                                      void* stream);
 int vc_sharded_search_knn_scoped(vc_sharded* h, const void* queries, uint32_t nq, uint32_t k, uint32_t order, const uint32_t* scope,
                                  const uint32_t* qscope, uint32_t flags, uint64_t* out, uint32_t* counts, vc_scope_stats* stats);
+
+/* The exact k-NN graph over all shards: rule, modes, outputs, errors, rounds and waits as vc_knn_graph_dev / vc_knn_graph with
+ * N = vc_sharded_size and ids global over the whole store.  Every pointer of the device form lives on the ROOT device; the settle
+ * passes run there, the shards are reached only through the store's own search and its gather by id. */
+int vc_sharded_knn_graph_dev(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first,
+                             uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_stats* stats, void* stream);
+int vc_sharded_knn_graph(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first,
+                         uint64_t* rows, uint32_t* counts, vc_knn_graph_stats* stats);
+/* Components and in-degrees of that graph: as vc_cluster_knn_dev / vc_cluster_knn; the rows live on the ROOT device, no shard is
+ * touched. */
+int vc_sharded_cluster_knn_dev(vc_sharded* h, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags,
+                               uint32_t max_dist, uint32_t* d_labels, uint32_t* d_in_degree, vc_cluster_knn_stats* stats, void* stream);
+int vc_sharded_cluster_knn(vc_sharded* h, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags,
+                           uint32_t max_dist, uint32_t* labels, uint32_t* in_degree, vc_cluster_knn_stats* stats);
 
 /* Stream of the host-pointer calls (default VC_STREAM_OWN). */
 int vc_set_stream(vc_engine* e, void* stream);

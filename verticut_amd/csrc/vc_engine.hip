@@ -15,6 +15,7 @@
 #include "vc_filter_plan.hpp"
 #include "vc_groups_plan.hpp"
 #include "vc_internal.hpp"
+#include "vc_knn_graph_plan.hpp"
 #include "vc_mih.hpp"
 #include "vc_retain.hpp"
 
@@ -171,6 +172,7 @@ void read_knobs(VcKnobs* k) {
   if (const char* v = getenv("VC_FILTER_WINDOW")) k->filter_window = (uint32_t)strtoul(v, nullptr, 10);
   if (const char* v = getenv("VC_SCOPE_SCRATCH")) k->scope_scratch = strtoull(v, nullptr, 10);
   if (const char* v = getenv("VC_SCOPE_WINDOW")) k->scope_window = (uint32_t)strtoul(v, nullptr, 10);
+  if (const char* v = getenv("VC_KGRAPH_SCRATCH")) k->kgraph_scratch = strtoull(v, nullptr, 10);
   if (const char* v = getenv("VC_SCAN_STREAM_FREE")) { k->stream_free_set = true; k->stream_free = strtoull(v, nullptr, 10); }
 }
 
@@ -1641,6 +1643,95 @@ int vc_search_knn_scoped(vc_engine* e, const void* queries, uint32_t nq, uint32_
                                return vc_scope_run(v, scope_args(e, d_q, nq, k, d_scope, d_qscope, d_out, d_cnt), stats, s, err);
                              },
                              s, err);
+  });
+}
+
+}  // extern "C"
+
+// ---- the exact k-NN graph of the store and its components (vc_knn_graph.hip) ---------------------------------------------------------------
+static int check_kgraph_args(vc_engine* e, uint32_t k, uint32_t mode, uint64_t first, uint64_t count, uint32_t k_first, const uint64_t* rows, uint64_t* n_rows) {
+  if (!e || !rows) return VC_ERR_INVALID;
+  if (!vc_kgraph_k_ok(k)) return fail(e, VC_ERR_INVALID, "k-NN graph: k must be in 1..%u", VC_MAX_K - 1);
+  if (!vc_kgraph_k_first_ok(k, k_first)) return fail(e, VC_ERR_INVALID, "k-NN graph: k_first must be 0 or in k+1..%u", VC_MAX_K);
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return fail(e, VC_ERR_INVALID, "k-NN graph: mode must be LINEAR or MIH_EXACT");
+  if (!vc_kgraph_range(e->n, first, count, n_rows))
+    return fail(e, VC_ERR_INVALID, "k-NN graph: first %llu + count %llu exceeds the %llu resident records", (unsigned long long)first, (unsigned long long)count,
+                (unsigned long long)e->n);
+  if (e->n && mode == VC_MODE_MIH_EXACT && !live_index(e)) return fail(e, VC_ERR_STATE, "MIH search needs vc_build_index() first (n_tables=%u)", e->m);
+  return VC_OK;
+}
+static VcKgraphArgs kgraph_args(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t n_rows, uint32_t k_first, uint64_t* d_rows,
+                                uint32_t* d_counts) {
+  return VcKgraphArgs{k, k_first, batch, mode == VC_MODE_LINEAR, first, n_rows, d_rows, d_counts, e->knobs.kgraph_scratch};
+}
+static int check_cluster_knn_args(vc_engine* e, const uint64_t* rows, uint32_t k, uint32_t kk, uint32_t flags, const uint32_t* labels) {
+  if (!e || !rows || !labels) return VC_ERR_INVALID;
+  if (!vc_kgraph_k_ok(k)) return fail(e, VC_ERR_INVALID, "k-NN clusters: k must be in 1..%u", VC_MAX_K - 1);
+  if (kk == 0 || kk > k) return fail(e, VC_ERR_INVALID, "k-NN clusters: kk must be in 1..k");
+  if (flags & ~VC_KNN_EITHER) return fail(e, VC_ERR_INVALID, "k-NN clusters: unknown flags 0x%x", flags);
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_knn_graph_dev(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first, uint64_t* d_rows,
+                     uint32_t* d_counts, vc_knn_graph_stats* stats, void* stream) {
+  uint64_t n_rows = 0;
+  const int rc = check_kgraph_args(e, k, mode, first, count, k_first, d_rows, &n_rows);
+  if (rc) return rc;
+  if (stats) *stats = vc_knn_graph_stats{};
+  if (n_rows == 0) return VC_OK;
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_knn_graph_run(store_view(e, mode), store_view(e, VC_MODE_LINEAR).knn, kgraph_args(e, k, mode, batch, first, n_rows, k_first, d_rows, d_counts), stats,
+                            s, err);
+  });
+}
+
+int vc_knn_graph(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first, uint64_t* rows, uint32_t* counts,
+                 vc_knn_graph_stats* stats) {
+  uint64_t n_rows = 0;
+  int rc = check_kgraph_args(e, k, mode, first, count, k_first, rows, &n_rows);
+  if (rc) return rc;
+  if (stats) *stats = vc_knn_graph_stats{};
+  if (n_rows == 0) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const VcStoreView v = store_view(e, mode);
+  hipStream_t s = e->stream;
+  std::string err;
+  rc = vc_knn_graph_run_host(v, kgraph_args(e, k, mode, batch, first, n_rows, k_first, nullptr, nullptr), rows, counts, stats,
+                             [&](uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_stats* st) {
+                               return store_call(e, s, [&](hipStream_t cs, std::string* cerr) {
+                                 return vc_knn_graph_run(v, store_view(e, VC_MODE_LINEAR).knn, kgraph_args(e, k, mode, batch, first, n_rows, k_first, d_rows, d_counts),
+                                                         st, cs, cerr);
+                               });
+                             },
+                             [&](const uint64_t* codes, uint32_t nq, uint64_t* hrows, uint32_t* rcnt) {
+                               return vc_search_knn(e, codes, nq, k + 1, VC_MODE_LINEAR, VC_ORDER_ASCENDING, hrows, rcnt, nullptr);
+                             },
+                             s, &err);
+  return driver_done(e, rc, err);
+}
+
+int vc_cluster_knn_dev(vc_engine* e, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist,
+                       uint32_t* d_labels, uint32_t* d_in_degree, vc_cluster_knn_stats* stats, void* stream) {
+  const int rc = check_cluster_knn_args(e, d_rows, k, kk, flags, d_labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_cluster_knn_stats{};
+  if (e->n == 0) return VC_OK;
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_cluster_knn_run(store_view(e, VC_MODE_LINEAR), VcKgraphClusterArgs{d_rows, d_counts, k, kk, flags, max_dist, d_labels, d_in_degree}, stats, s, err);
+  });
+}
+
+int vc_cluster_knn(vc_engine* e, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t* labels,
+                   uint32_t* in_degree, vc_cluster_knn_stats* stats) {
+  const int rc = check_cluster_knn_args(e, rows, k, kk, flags, labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_cluster_knn_stats{};
+  if (e->n == 0) return VC_OK;
+  return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_cluster_knn_run_host(store_view(e, VC_MODE_LINEAR), VcKgraphClusterArgs{nullptr, nullptr, k, kk, flags, max_dist, nullptr, nullptr}, rows, counts,
+                                   labels, in_degree, stats, s, err);
   });
 }
 

@@ -54,6 +54,7 @@ struct VcKnobs {
   uint32_t filter_window = 1u << 20;          // VC_FILTER_WINDOW: allowed ids per window of the pre-filter route (0 or above 2^24: the default)
   uint64_t scope_scratch = 64ull << 20;       // VC_SCOPE_SCRATCH: bytes of (query, slice) counters a sub-batch of vc_search_knn_scoped* may hold (vc_scope_plan.hpp)
   uint32_t scope_window = 1u << 20;           // VC_SCOPE_WINDOW: positions of the scope-sorted list per window (0 or above 2^24: the default)
+  uint64_t kgraph_scratch = 64ull << 20;      // VC_KGRAPH_SCRATCH: bytes of k' rows a sub-batch of vc_knn_graph* may hold (vc_knn_graph_plan.hpp)
   bool stream_free_set = false;              // VC_SCAN_STREAM_FREE (tests): the free device memory, in bytes, that vc_build_scan_stream's memory rule is given
   uint64_t stream_free = 0;
 };
@@ -223,6 +224,9 @@ enum VcScratch {
   // scoped k-NN (vc_scope.hip): the query side's sort and tables; the keep set; the listed records, their sort and the segment table;
   // a sub-batch's histograms, cuts and counters; its candidate, running and merge rows; a window's gathered codes; the host forms' staging
   VC_SCOPE_QUERY, VC_SCOPE_KEEP, VC_SCOPE_LIST, VC_SCOPE_WORK, VC_SCOPE_ROWS, VC_SCOPE_CODES, VC_SCOPE_STAGE,
+  // the k-NN graph (vc_knn_graph.hip): a batch's ids, codes, flags, maps and retry codes (VcKgraphWork); the k' rows; the host forms'
+  // staging; vc_cluster_knn*'s statistics block and its in-degrees when the caller passes none
+  VC_KGRAPH_WORK, VC_KGRAPH_ROWS, VC_KGRAPH_STAGE, VC_KGRAPH_STAT, VC_KGRAPH_DEG,
   VC_SCRATCH_BUFS
 };
 // buffer `which` of the handle's table, at least `bytes` large, on the current device; null when it cannot be had (the handle keeps the text)
@@ -643,6 +647,41 @@ struct VcScopeHostArgs {
 int vc_scope_run_host(const VcStoreView& v, const VcScopeHostArgs& a,
                       const std::function<int(const uint64_t* d_queries, const uint32_t* d_scope, const uint32_t* d_qscope, uint64_t* d_out, uint32_t* d_counts)>& run,
                       hipStream_t s, std::string* err);
+// ---- vc_knn_graph.hip: the exact k-NN graph of the store (vc_knn_graph*, vc_sharded_knn_graph*) and its analysis (vc_cluster_knn*,
+// vc_sharded_cluster_knn*).  One driver for both handle kinds over the view's gather, knn and alloc; the plan arithmetic -- the range,
+// the k' schedule, the verdict on a row, the sub-batches, the scratch layout -- is vc_knn_graph_plan.hpp.
+struct VcKgraphArgs {
+  uint32_t k, k_first, batch;      // checked by the caller: vc_kgraph_k_ok, vc_kgraph_k_first_ok; batch as the caller passed it
+  bool linear;                     // the mode is VC_MODE_LINEAR: one round at k + 1; else the view's knn is exact MIH
+  uint64_t first, rows;            // the positions [first, first + rows) of the store, rows > 0 (vc_kgraph_range)
+  uint64_t* d_rows;                // [rows][k]
+  uint32_t* d_counts;              // [rows], nullable
+  uint64_t budget;                 // VcKnobs::kgraph_scratch
+};
+// the whole call on s with the device of the buffers current: under exact MIH one wait per round of a batch (4 bytes), one at the end
+// for the statistics when stats (host memory, nullable) is given.  linear_knn: the store's LINEAR k-NN, which answers the queries
+// exact MIH leaves unsettled at k' = VC_MAX_K (in LINEAR mode the view's own)
+int vc_knn_graph_run(const VcStoreView& v, const VcKnnSearch& linear_knn, const VcKgraphArgs& a, vc_knn_graph_stats* stats, hipStream_t s, std::string* err);
+// either handle's host form (a's pointers are ignored): `run` (the device form on s) into staged rows and counts, which come home;
+// waits for them.  A row the linear scan passed on (count UINT32_MAX) is answered again by host_knn -- the handle's host-form LINEAR
+// k-NN of nq codes at k + 1, ascending -- and stripped by vc_ids_strip_host.  counts, stats nullable
+int vc_knn_graph_run_host(const VcStoreView& v, const VcKgraphArgs& a, uint64_t* rows, uint32_t* counts, vc_knn_graph_stats* stats,
+                          const std::function<int(uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_stats* stats)>& run,
+                          const std::function<int(const uint64_t* codes, uint32_t nq, uint64_t* rows, uint32_t* counts)>& host_knn, hipStream_t s,
+                          std::string* err);
+struct VcKgraphClusterArgs {
+  const uint64_t* d_rows;          // [n][k]: vc_knn_graph*'s rows over the whole store
+  const uint32_t* d_counts;        // [n], nullable: then every row holds vc_kgraph_row_count(n, k) entries
+  uint32_t k, kk, flags, max_dist; // checked by the caller: vc_kgraph_k_ok, 1 <= kk <= k, known flags
+  uint32_t* d_labels;              // [n]
+  uint32_t* d_in_degree;           // [n], nullable: then the handle's own (VC_KGRAPH_DEG)
+};
+// the whole call on s, v.n > 0: init, the edge launch, flatten, the largest in-degree, then the one wait for the statistics and the
+// error word (VC_ERR_INVALID: a count above k or an id outside the store).  Only n, id_base and alloc of the view are used
+int vc_cluster_knn_run(const VcStoreView& v, const VcKgraphClusterArgs& a, vc_cluster_knn_stats* stats, hipStream_t s, std::string* err);
+// the same for host pointers (a's pointers are ignored): rows and counts staged, labels and in-degrees (nullable) come home, waited for
+int vc_cluster_knn_run_host(const VcStoreView& v, VcKgraphClusterArgs a, const uint64_t* rows, const uint32_t* counts, uint32_t* labels, uint32_t* in_degree,
+                            vc_cluster_knn_stats* stats, hipStream_t s, std::string* err);
 // ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
 struct VcKeepSet;
 #define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)

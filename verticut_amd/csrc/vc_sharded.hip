@@ -40,6 +40,7 @@
 #include "vc_distinct_plan.hpp"
 #include "vc_filter_plan.hpp"
 #include "vc_internal.hpp"
+#include "vc_knn_graph_plan.hpp"
 #include "vc_mih.hpp"
 #include "vc_seed_plan.hpp"
 #include "vc_sharded_radius.hpp"
@@ -2672,6 +2673,93 @@ int vc_sharded_search_knn_scoped(vc_sharded* h, const void* queries, uint32_t nq
                                return vc_scope_run(v, sharded_scope_args(h, d_q, nq, k, d_scope, d_qscope, d_out, d_cnt), stats, S, err);
                              },
                              S, err);
+  });
+}
+
+}  // extern "C"
+
+// ---- the exact k-NN graph over the shards and its components: vc_knn_graph.hip's drivers on the root, the shards behind the view's knn and gather ----
+static int check_sharded_kgraph_args(vc_sharded* h, uint32_t k, uint32_t mode, uint64_t first, uint64_t count, uint32_t k_first, const uint64_t* rows,
+                                     uint64_t* n_rows) {
+  if (!h || !rows) return VC_ERR_INVALID;
+  if (!vc_kgraph_k_ok(k)) return sfail(h, VC_ERR_INVALID, "k-NN graph: k must be in 1..%u", VC_MAX_K - 1);
+  if (!vc_kgraph_k_first_ok(k, k_first)) return sfail(h, VC_ERR_INVALID, "k-NN graph: k_first must be 0 or in k+1..%u", VC_MAX_K);
+  if (mode != VC_MODE_LINEAR && mode != VC_MODE_MIH_EXACT) return sfail(h, VC_ERR_INVALID, "k-NN graph: mode must be LINEAR or MIH_EXACT");
+  if (!vc_kgraph_range(h->n, first, count, n_rows))
+    return sfail(h, VC_ERR_INVALID, "k-NN graph: first %llu + count %llu exceeds the %llu resident records", (unsigned long long)first, (unsigned long long)count,
+                 (unsigned long long)h->n);
+  return check_sharded_index(h, mode);
+}
+static VcKgraphArgs sharded_kgraph_args(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t n_rows, uint32_t k_first,
+                                        uint64_t* d_rows, uint32_t* d_counts) {
+  return VcKgraphArgs{k, k_first, batch, mode == VC_MODE_LINEAR, first, n_rows, d_rows, d_counts, h->knobs.kgraph_scratch};
+}
+static int check_sharded_cluster_knn_args(vc_sharded* h, const uint64_t* rows, uint32_t k, uint32_t kk, uint32_t flags, const uint32_t* labels) {
+  if (!h || !rows || !labels) return VC_ERR_INVALID;
+  if (!vc_kgraph_k_ok(k)) return sfail(h, VC_ERR_INVALID, "k-NN clusters: k must be in 1..%u", VC_MAX_K - 1);
+  if (kk == 0 || kk > k) return sfail(h, VC_ERR_INVALID, "k-NN clusters: kk must be in 1..k");
+  if (flags & ~VC_KNN_EITHER) return sfail(h, VC_ERR_INVALID, "k-NN clusters: unknown flags 0x%x", flags);
+  return VC_OK;
+}
+
+extern "C" {
+
+int vc_sharded_knn_graph_dev(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first, uint64_t* d_rows,
+                             uint32_t* d_counts, vc_knn_graph_stats* stats, void* stream) {
+  uint64_t n_rows = 0;
+  const int rc = check_sharded_kgraph_args(h, k, mode, first, count, k_first, d_rows, &n_rows);
+  if (rc) return rc;
+  if (stats) *stats = vc_knn_graph_stats{};
+  if (n_rows == 0) return VC_OK;
+  return sharded_store_call(h, mode, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_knn_graph_run(v, sharded_store_view(h, VC_MODE_LINEAR, S).knn, sharded_kgraph_args(h, k, mode, batch, first, n_rows, k_first, d_rows, d_counts), stats,
+                            S, err);
+  });
+}
+
+int vc_sharded_knn_graph(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first, uint64_t* rows,
+                         uint32_t* counts, vc_knn_graph_stats* stats) {
+  uint64_t n_rows = 0;
+  const int rc = check_sharded_kgraph_args(h, k, mode, first, count, k_first, rows, &n_rows);
+  if (rc) return rc;
+  if (stats) *stats = vc_knn_graph_stats{};
+  if (n_rows == 0) return VC_OK;
+  return sharded_store_call(h, mode, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_knn_graph_run_host(v, sharded_kgraph_args(h, k, mode, batch, first, n_rows, k_first, nullptr, nullptr), rows, counts, stats,
+                                 [&](uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_stats* st) {
+                                   return vc_knn_graph_run(v, sharded_store_view(h, VC_MODE_LINEAR, S).knn,
+                                                           sharded_kgraph_args(h, k, mode, batch, first, n_rows, k_first, d_rows, d_counts), st, S, err);
+                                 },
+                                 [&](const uint64_t* codes, uint32_t nq, uint64_t* hrows, uint32_t* rcnt) {   // (its shards recover on the host)
+                                   const int r = vc_sharded_search_knn(h, codes, nq, k + 1, VC_MODE_LINEAR, VC_ORDER_ASCENDING, hrows, rcnt, nullptr);
+                                   if (r) return r;
+                                   VS_HIP(h, hipSetDevice(h->root));
+                                   return (int)VC_OK;
+                                 },
+                                 S, err);
+  });
+}
+
+int vc_sharded_cluster_knn_dev(vc_sharded* h, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist,
+                               uint32_t* d_labels, uint32_t* d_in_degree, vc_cluster_knn_stats* stats, void* stream) {
+  const int rc = check_sharded_cluster_knn_args(h, d_rows, k, kk, flags, d_labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_cluster_knn_stats{};
+  if (h->n == 0) return VC_OK;
+  return sharded_store_call(h, VC_MODE_LINEAR, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_cluster_knn_run(v, VcKgraphClusterArgs{d_rows, d_counts, k, kk, flags, max_dist, d_labels, d_in_degree}, stats, S, err);
+  });
+}
+
+int vc_sharded_cluster_knn(vc_sharded* h, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist,
+                           uint32_t* labels, uint32_t* in_degree, vc_cluster_knn_stats* stats) {
+  const int rc = check_sharded_cluster_knn_args(h, rows, k, kk, flags, labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_cluster_knn_stats{};
+  if (h->n == 0) return VC_OK;
+  return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_cluster_knn_run_host(v, VcKgraphClusterArgs{nullptr, nullptr, k, kk, flags, max_dist, nullptr, nullptr}, rows, counts, labels, in_degree, stats, S,
+                                   err);
   });
 }
 

@@ -55,7 +55,10 @@ EXPORTS = [
     "vc_search_knn_distinct", "vc_search_knn_distinct_dev", "vc_sharded_search_knn_distinct", "vc_sharded_search_knn_distinct_dev",
     "vc_search_knn_filtered", "vc_search_knn_filtered_dev", "vc_sharded_search_knn_filtered", "vc_sharded_search_knn_filtered_dev",
     "vc_search_knn_scoped", "vc_search_knn_scoped_dev", "vc_sharded_search_knn_scoped", "vc_sharded_search_knn_scoped_dev",
+    "vc_knn_graph", "vc_knn_graph_dev", "vc_sharded_knn_graph", "vc_sharded_knn_graph_dev",
+    "vc_cluster_knn", "vc_cluster_knn_dev", "vc_sharded_cluster_knn", "vc_sharded_cluster_knn_dev",
 ]
+KNN_MUTUAL, KNN_EITHER = 0, 1   # VC_KNN_*: cluster_knn joins i and j iff each lists the other / iff one lists the other
 FILTER_MASK, FILTER_ROOTS, FILTER_EQUAL, FILTER_NOT_EQUAL, FILTER_BITS = 0, 1, 2, 3, 4   # VC_FILTER_*: how search_knn_filtered reads `sel`
 FILTER_RAN_POST, FILTER_RAN_PRE = 1, 2   # VC_FILTER_RAN_*: bits of VcFilterStats.routes
 DISTINCT_TRUNCATED = 0x80000000   # VC_DISTINCT_TRUNCATED: flag in a count of search_knn_distinct -- the row holds the groups found within the 8192 nearest records
@@ -159,6 +162,22 @@ class VcScopeStats(C.Structure):
     def as_dict(self):
         """{n_matched, n_pairs, n_scopes, n_windows, n_short, n_empty: int}"""
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class VcKnnGraphStats(C.Structure):
+    _fields_ = [("n_rounds_max", C.c_uint32), ("k_last", C.c_uint32), ("n_searched", C.c_uint64), ("n_linear", C.c_uint64), ("n_gave_up", C.c_uint64)]
+
+    def as_dict(self):
+        """{n_rounds_max, k_last, n_searched, n_linear, n_gave_up: int}"""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class VcClusterKnnStats(C.Structure):
+    _fields_ = [("n_edges", C.c_uint64), ("n_mutual", C.c_uint64), ("n_clusters", C.c_uint64), ("max_in_degree", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        """{n_edges, n_mutual, n_clusters, max_in_degree: int}"""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "pad"}
 
 
 class VcTiming(C.Structure):
@@ -320,6 +339,14 @@ def load_library():
     L.vc_search_knn_distinct_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp]
     L.vc_sharded_search_knn_distinct.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, vp, vp, vp, vp]
     L.vc_sharded_search_knn_distinct_dev.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp]
+    L.vc_knn_graph.argtypes = [vp, u32, u32, u32, u64, u64, u32, vp, vp, vp]
+    L.vc_knn_graph_dev.argtypes = [vp, u32, u32, u32, u64, u64, u32, vp, vp, vp, vp]
+    L.vc_sharded_knn_graph.argtypes = [vp, u32, u32, u32, u64, u64, u32, vp, vp, vp]
+    L.vc_sharded_knn_graph_dev.argtypes = [vp, u32, u32, u32, u64, u64, u32, vp, vp, vp, vp]
+    L.vc_cluster_knn.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]
+    L.vc_cluster_knn_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]
+    L.vc_sharded_cluster_knn.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]
+    L.vc_sharded_cluster_knn_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -624,6 +651,51 @@ def _search_knn_scoped(self, fn, queries, k, scope, qscope, order, with_stats):
 def _search_knn_scoped_dev(self, fn, d_queries, nq, k, d_scope, d_qscope, d_out, d_counts, with_stats, stream):
     st = VcScopeStats()
     self._check(fn(self._h, d_queries, nq, k, d_scope, d_qscope, 0, d_out, d_counts, C.byref(st) if with_stats else None, stream))
+    return st.as_dict() if with_stats else None
+
+
+def _knn_graph(self, fn, k, mode, batch, first, count, k_first, with_stats):
+    """shared by Engine.knn_graph and ShardedEngine.knn_graph: (rows uint64 [n, k], counts uint32 [n][, stats dict]), n the positions covered"""
+    n = len(self)
+    if first > n or count > n - first:
+        raise VcError(VC_ERR_INVALID, "the range leaves the resident records")
+    rows_n = count if count else n - first
+    rows, counts = np.empty((rows_n, k), dtype=np.uint64), np.zeros(rows_n, dtype=np.uint32)
+    keep = rows if rows_n else np.zeros(1, dtype=np.uint64)   # (an empty range: the call writes no word, but takes no null pointer)
+    st = VcKnnGraphStats()
+    self._check(fn(self._h, k, mode, batch, first, count, k_first, _p(keep), _p(counts) if rows_n else None, C.byref(st)))
+    return (rows, counts, st.as_dict()) if with_stats else (rows, counts)
+
+
+def _knn_graph_dev(self, fn, k, d_rows, d_counts, mode, batch, first, count, k_first, with_stats, stream):
+    st = VcKnnGraphStats()
+    self._check(fn(self._h, k, mode, batch, first, count, k_first, d_rows, d_counts, C.byref(st) if with_stats else None, stream))
+    return st.as_dict() if with_stats else None
+
+
+def _cluster_knn(self, fn, rows, counts, kk, flags, max_dist, with_in_degree):
+    """shared by Engine.cluster_knn and ShardedEngine.cluster_knn: (labels uint32 [N], in_degree uint32 [N] | None, stats dict)"""
+    n = len(self)
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    if rows.ndim != 2 or rows.shape[0] != n:
+        raise VcError(VC_ERR_INVALID, "rows must be the [N, k] graph of knn_graph over the whole store")
+    k = rows.shape[1]
+    if counts is not None:
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        if counts.shape[0] != n:
+            raise VcError(VC_ERR_INVALID, "counts must have one word per resident record")
+    labels = np.empty(n, dtype=np.uint32)
+    deg = np.zeros(n, dtype=np.uint32) if with_in_degree else None
+    keep = rows if n else np.zeros(1, dtype=np.uint64)
+    st = VcClusterKnnStats()
+    self._check(fn(self._h, _p(keep), _p(counts) if counts is not None and n else None, k, kk, flags, max_dist,
+                   _p(labels) if n else _p(np.zeros(1, dtype=np.uint32)), _p(deg) if with_in_degree and n else None, C.byref(st)))
+    return labels, deg, st.as_dict()
+
+
+def _cluster_knn_dev(self, fn, d_rows, d_counts, k, kk, flags, max_dist, d_labels, d_in_degree, with_stats, stream):
+    st = VcClusterKnnStats()
+    self._check(fn(self._h, d_rows, d_counts, k, kk, flags, max_dist, d_labels, d_in_degree, C.byref(st) if with_stats else None, stream))
     return st.as_dict() if with_stats else None
 
 
@@ -1043,6 +1115,29 @@ class Engine:
         `stream` order.  Returns the stats dict; with_stats=False returns None."""
         return _search_knn_scoped_dev(self, self._L.vc_search_knn_scoped_dev, d_queries, nq, k, d_scope, d_qscope, d_out, d_counts, with_stats, stream)
 
+    def knn_graph(self, k, mode=MODE_LINEAR, batch=0, first=0, count=0, k_first=0, with_stats=False):
+        """vc_knn_graph: the exact k-NN graph of the store.  Row p - first holds the k smallest packed (dist << 32 | id) over all resident
+        records other than record id_base + p, ascending, UINT64_MAX padded; counts = min(k, N - 1).  The same words in MODE_LINEAR and
+        MODE_MIH_EXACT, for every batch and k_first.  count == 0: to the end.  Returns (rows [n, k], counts [n][, stats dict])."""
+        return _knn_graph(self, self._L.vc_knn_graph, k, mode, batch, first, count, k_first, with_stats)
+
+    def knn_graph_dev(self, k, d_rows, d_counts=None, mode=MODE_MIH_EXACT, batch=0, first=0, count=0, k_first=0, with_stats=True, stream=None):
+        """vc_knn_graph_dev: raw device addresses (d_rows n * k uint64, d_counts n uint32 or None); results valid in `stream`
+        order.  Returns the stats dict (None without with_stats)."""
+        return _knn_graph_dev(self, self._L.vc_knn_graph_dev, k, d_rows, d_counts, mode, batch, first, count, k_first, with_stats, stream)
+
+    def cluster_knn(self, rows, counts, kk, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, with_in_degree=True):
+        """vc_cluster_knn: components and in-degrees of a graph knn_graph built over the whole store (rows [N, k], counts [N] or None).
+        Row i lists j iff j is among its first kk entries at a distance <= max_dist; KNN_MUTUAL joins i and j iff each lists the other,
+        KNN_EITHER iff one does.  Returns (labels [N] -- the smallest id of each component, as cluster_radius --, in_degree [N] | None,
+        stats dict of n_edges, n_mutual, n_clusters, max_in_degree)."""
+        return _cluster_knn(self, self._L.vc_cluster_knn, rows, counts, kk, flags, max_dist, with_in_degree)
+
+    def cluster_knn_dev(self, d_rows, d_counts, k, kk, d_labels, d_in_degree=None, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, with_stats=True, stream=None):
+        """vc_cluster_knn_dev: raw device addresses; nothing is searched, the host waits once.  Returns the stats dict (None without
+        with_stats)."""
+        return _cluster_knn_dev(self, self._L.vc_cluster_knn_dev, d_rows, d_counts, k, kk, flags, max_dist, d_labels, d_in_degree, with_stats, stream)
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -1381,6 +1476,29 @@ class ShardedEngine:
         """vc_sharded_search_knn_scoped_dev: raw device addresses on the root device; the host waits twice, results valid in `stream` order.
         Returns the stats dict; with_stats=False returns None."""
         return _search_knn_scoped_dev(self, self._L.vc_sharded_search_knn_scoped_dev, d_queries, nq, k, d_scope, d_qscope, d_out, d_counts, with_stats, stream)
+
+    def knn_graph(self, k, mode=MODE_LINEAR, batch=0, first=0, count=0, k_first=0, with_stats=False):
+        """vc_sharded_knn_graph: the exact k-NN graph of the store.  Row p - first holds the k smallest packed (dist << 32 | id) over all resident
+        records other than record id_base + p, ascending, UINT64_MAX padded; counts = min(k, N - 1).  The same words in MODE_LINEAR and
+        MODE_MIH_EXACT, for every batch and k_first.  count == 0: to the end.  Returns (rows [n, k], counts [n][, stats dict])."""
+        return _knn_graph(self, self._L.vc_sharded_knn_graph, k, mode, batch, first, count, k_first, with_stats)
+
+    def knn_graph_dev(self, k, d_rows, d_counts=None, mode=MODE_MIH_EXACT, batch=0, first=0, count=0, k_first=0, with_stats=True, stream=None):
+        """vc_sharded_knn_graph_dev: raw device addresses on the root device (d_rows n * k uint64, d_counts n uint32 or None); results valid in `stream`
+        order.  Returns the stats dict (None without with_stats)."""
+        return _knn_graph_dev(self, self._L.vc_sharded_knn_graph_dev, k, d_rows, d_counts, mode, batch, first, count, k_first, with_stats, stream)
+
+    def cluster_knn(self, rows, counts, kk, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, with_in_degree=True):
+        """vc_sharded_cluster_knn: components and in-degrees of a graph knn_graph built over the whole store (rows [N, k], counts [N] or None).
+        Row i lists j iff j is among its first kk entries at a distance <= max_dist; KNN_MUTUAL joins i and j iff each lists the other,
+        KNN_EITHER iff one does.  Returns (labels [N] -- the smallest id of each component, as cluster_radius --, in_degree [N] | None,
+        stats dict of n_edges, n_mutual, n_clusters, max_in_degree)."""
+        return _cluster_knn(self, self._L.vc_sharded_cluster_knn, rows, counts, kk, flags, max_dist, with_in_degree)
+
+    def cluster_knn_dev(self, d_rows, d_counts, k, kk, d_labels, d_in_degree=None, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, with_stats=True, stream=None):
+        """vc_sharded_cluster_knn_dev: raw device addresses on the root device; nothing is searched, the host waits once.  Returns the stats dict (None without
+        with_stats)."""
+        return _cluster_knn_dev(self, self._L.vc_sharded_cluster_knn_dev, d_rows, d_counts, k, kk, flags, max_dist, d_labels, d_in_degree, with_stats, stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

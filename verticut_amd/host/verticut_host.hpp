@@ -165,6 +165,16 @@ class Backend {
   // be null, counts = min(k, size of the query's scope)
   virtual int search_knn_scoped(const void* queries, uint32_t nq, uint32_t k, uint32_t order, const uint32_t* scope, const uint32_t* qscope, uint32_t flags,
                                 uint64_t* out, uint32_t* counts, vc_scope_stats* stats) = 0;
+  // the exact k-NN graph of the store (vc_knn_graph / vc_sharded_knn_graph): row p - first = the k nearest OTHER records of record
+  // first + p as packed (dist << 32 | id), ascending, ties to the smaller id; count 0 = to the end; the same words in VC_MODE_LINEAR and
+  // VC_MODE_MIH_EXACT; counts and stats may be null
+  virtual int knn_graph(uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first, uint64_t* rows, uint32_t* counts,
+                        vc_knn_graph_stats* stats) = 0;
+  // components and in-degrees of that graph over the whole store (vc_cluster_knn / vc_sharded_cluster_knn): an edge is one of a row's
+  // first kk entries at a distance <= max_dist; VC_KNN_MUTUAL joins two records iff each lists the other, VC_KNN_EITHER iff one does;
+  // labels[i] = the smallest id of the component; counts, in_degree and stats may be null
+  virtual int cluster_knn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t* labels,
+                          uint32_t* in_degree, vc_cluster_knn_stats* stats) = 0;
   // records taken out of the store and its index, the survivors renumbered in order (vc_retain / vc_sharded_retain; the reference has
   // no delete: this stands for build_hash_tables.cc run again over the code file without them).  kind VC_RETAIN_MASK / VC_RETAIN_ROOTS
   virtual int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) = 0;
@@ -258,6 +268,14 @@ class Engine : public Backend {
   int search_knn_scoped(const void* queries, uint32_t nq, uint32_t k, uint32_t order, const uint32_t* scope, const uint32_t* qscope, uint32_t flags,
                         uint64_t* out, uint32_t* counts, vc_scope_stats* stats) override {
     return vc_search_knn_scoped(h_, queries, nq, k, order, scope, qscope, flags, out, counts, stats);
+  }
+  int knn_graph(uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first, uint64_t* rows, uint32_t* counts,
+                vc_knn_graph_stats* stats) override {
+    return vc_knn_graph(h_, k, mode, batch, first, count, k_first, rows, counts, stats);
+  }
+  int cluster_knn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t* labels,
+                  uint32_t* in_degree, vc_cluster_knn_stats* stats) override {
+    return vc_cluster_knn(h_, rows, counts, k, kk, flags, max_dist, labels, in_degree, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_retain(h_, sel, kind, new_ids, n_kept); }
  private:
@@ -379,6 +397,14 @@ class ShardedEngine : public Backend {
   int search_knn_scoped(const void* queries, uint32_t nq, uint32_t k, uint32_t order, const uint32_t* scope, const uint32_t* qscope, uint32_t flags,
                         uint64_t* out, uint32_t* counts, vc_scope_stats* stats) override {
     return vc_sharded_search_knn_scoped(h_, queries, nq, k, order, scope, qscope, flags, out, counts, stats);
+  }
+  int knn_graph(uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first, uint64_t* rows, uint32_t* counts,
+                vc_knn_graph_stats* stats) override {
+    return vc_sharded_knn_graph(h_, k, mode, batch, first, count, k_first, rows, counts, stats);
+  }
+  int cluster_knn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t* labels,
+                  uint32_t* in_degree, vc_cluster_knn_stats* stats) override {
+    return vc_sharded_cluster_knn(h_, rows, counts, k, kk, flags, max_dist, labels, in_degree, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_sharded_retain(h_, sel, kind, new_ids, n_kept); }
  private:
