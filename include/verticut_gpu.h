@@ -1049,6 +1049,54 @@ int vc_knn_graph_dev(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, ui
 int vc_knn_graph(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first,
                  uint64_t* rows, uint32_t* counts, vc_knn_graph_stats* stats);
 
+/* ---- a built k-NN graph after an append: vc_knn_graph_update* -----------------------------------------------------------------------------
+ * vc_knn_graph* is the most expensive call of the library; after vc_add_codes of a few records to a large store this call brings a
+ * built graph up to date without building it again.
+ * PRECONDITION.  d_rows has room for N * k words and d_counts for N words, N the resident count now.  The first n_old rows and counts
+ * are what vc_knn_graph* wrote when the store held exactly its first n_old records, over the full range, with this k; the records
+ * [n_old, N) were appended since.  d_counts may be NULL: every old row then holds min(k, n_old - 1) entries, and no counts are
+ * written.  In VC_MODE_MIH_EXACT the index must be current: the caller has run vc_update_index (or vc_build_index).
+ * POSTCONDITION.  Rows and counts [0, N) are THE SAME WORDS as vc_knn_graph*(first = 0, count = N) writes for this store with this k,
+ * in both modes, for every batch, k_first, window size, old-batch size and scratch budget, on both handle kinds -- under vc_knn_graph*'s
+ * clause for the reference-fidelity flags, which governs the new records' rows.
+ * k, mode, batch and k_first mean what they mean to vc_knn_graph* and govern the new records' rows only; the join below has no mode.
+ * HOW.  1. The rows of the new records are vc_knn_graph* over [n_old, N), unchanged.  2. Old row i changes only where a new record j
+ * has (dist(i, j) << 32 | id_j) < T_i, with T_i = row_i[k - 1] for a full row and UINT64_MAX otherwise: a threshold join of the old
+ * records against the new ones, no search.  The new records' codes are gathered once.  The old records go by batches of
+ * VC_KGRAPH_OLD_BATCH ids (environment, read at create; default 2^18; 0 or above 2^24 means the default), each against WINDOWS of
+ * VC_KGRAPH_WINDOW new records (default 1024; 0 or above 2^20 means the default).  Per (old batch, window): a count pass of the join
+ * kernel (old records in registers with their thresholds, read from the rows as they are now, so they tighten from window to window;
+ * the window's codes in LDS tiles read as broadcasts); ONE WAIT of 16 bytes for the hits H and the affected records; if the hit list
+ * of 8 H bytes exceeds VC_KGRAPH_SCRATCH and the window holds more than one record, the window is cut in half -- for the rest of this
+ * old batch -- and counted again; two exclusive scans and a compacting gather (offsets, the ascending list of affected records); the
+ * fill pass, which writes every record's hits at its own offset without atomics and which a block without a hit leaves at once; a
+ * merge, one wave per affected record, that places the k smallest of row_i and its hits by rank counting into out-of-place rows
+ * (sub-batches of max(1, VC_KGRAPH_SCRATCH / (8 k)) records), and a copy back.  3. One wait at the end for the stats and the error word.
+ * STATS (HOST memory in both forms, may be NULL).  n_rows_changed and n_inserted are functions of the database, n_old and k only;
+ * n_hits (the hits of the accepted count pass of every window), n_windows and n_halvings depend on the three knobs as well.
+ * DEGENERATE.  n_old == N: VC_OK, nothing written, zero stats.  n_old == 0: a plain build.
+ * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle or rows, k outside 1 .. VC_MAX_K - 1, a bad
+ * k_first, an approximate or unknown mode, n_old > N; VC_ERR_STATE in MIH mode without a current index (a stale index after
+ * vc_add_codes counts as none).  An old count above k (UINT32_MAX included) is found ON THE DEVICE and gives VC_ERR_INVALID --
+ * vc_cluster_knn*'s protocol: the error word comes home with the stats; THE OUTPUTS ARE THEN UNDEFINED.
+ * Not offered: a form for vc_retain* (a row that listed a removed record needs a search), graphs over a part of the range, and an
+ * automatic switch to a rebuild when the append is large -- the join costs n_old * n_new pair-words, which the caller weighs.
+ * Scratch: grow-only buffers of the handle, this call's own; every word is written before it is read. */
+typedef struct vc_knn_graph_update_stats {   /* 64 bytes */
+  vc_knn_graph_stats build;   /* of the new records' rows: vc_knn_graph* over [n_old, N) */
+  uint64_t n_rows_changed;    /* old rows of which at least one word changed */
+  uint64_t n_inserted;        /* entries of old rows, after the call, whose id is a new record's */
+  uint64_t n_hits;            /* pairs that passed a threshold, summed over the windows (depends on the knobs) */
+  uint32_t n_windows;         /* (old batch, window) count passes run, retried ones included */
+  uint32_t n_halvings;        /* windows cut in half because their hits exceeded the scratch budget */
+} vc_knn_graph_update_stats;
+int vc_knn_graph_update_dev(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first,
+                            uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_update_stats* stats, void* stream);
+/* The same for rows and counts in host memory: the old rows and counts are staged up, all N rows and counts come home; waits for
+ * them.  A new row that the linear scan passed on with count UINT32_MAX is answered again as vc_knn_graph does it. */
+int vc_knn_graph_update(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first,
+                        uint64_t* rows, uint32_t* counts, vc_knn_graph_update_stats* stats);
+
 /* ---- components and in-degrees of the k-NN graph: vc_cluster_knn* -------------------------------------------------------------------------
  * Density-adaptive grouping: where one radius is too tight in sparse regions and too loose in dense ones, "i and j list each other
  * among their kk nearest" adapts to the local density.  Nothing is searched: the call reads a graph that vc_knn_graph* built and
@@ -1367,6 +1415,13 @@ int vc_sharded_knn_graph_dev(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t 
                              uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_stats* stats, void* stream);
 int vc_sharded_knn_graph(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first,
                          uint64_t* rows, uint32_t* counts, vc_knn_graph_stats* stats);
+/* That graph after vc_sharded_add_codes: contract, steps, stats and errors as vc_knn_graph_update_dev / vc_knn_graph_update.  Every
+ * pointer of the device form lives on the ROOT device, where the join, the merge and the scans run; the shards are reached only
+ * through the store's own search and its gather by id, so an append that crosses a shard boundary is nothing special. */
+int vc_sharded_knn_graph_update_dev(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first,
+                                    uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_update_stats* stats, void* stream);
+int vc_sharded_knn_graph_update(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first,
+                                uint64_t* rows, uint32_t* counts, vc_knn_graph_update_stats* stats);
 /* Components and in-degrees of that graph: as vc_cluster_knn_dev / vc_cluster_knn; the rows live on the ROOT device, no shard is
  * touched. */
 int vc_sharded_cluster_knn_dev(vc_sharded* h, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags,

@@ -16,6 +16,7 @@
 #include "vc_groups_plan.hpp"
 #include "vc_internal.hpp"
 #include "vc_knn_graph_plan.hpp"
+#include "vc_knn_graph_update_plan.hpp"
 #include "vc_mih.hpp"
 #include "vc_retain.hpp"
 
@@ -173,6 +174,8 @@ void read_knobs(VcKnobs* k) {
   if (const char* v = getenv("VC_SCOPE_SCRATCH")) k->scope_scratch = strtoull(v, nullptr, 10);
   if (const char* v = getenv("VC_SCOPE_WINDOW")) k->scope_window = (uint32_t)strtoul(v, nullptr, 10);
   if (const char* v = getenv("VC_KGRAPH_SCRATCH")) k->kgraph_scratch = strtoull(v, nullptr, 10);
+  if (const char* v = getenv("VC_KGRAPH_OLD_BATCH")) k->kgraph_old_batch = strtoull(v, nullptr, 10);
+  if (const char* v = getenv("VC_KGRAPH_WINDOW")) k->kgraph_window = strtoull(v, nullptr, 10);
   if (const char* v = getenv("VC_SCAN_STREAM_FREE")) { k->stream_free_set = true; k->stream_free = strtoull(v, nullptr, 10); }
 }
 
@@ -1671,6 +1674,18 @@ static int check_cluster_knn_args(vc_engine* e, const uint64_t* rows, uint32_t k
   if (flags & ~VC_KNN_EITHER) return fail(e, VC_ERR_INVALID, "k-NN clusters: unknown flags 0x%x", flags);
   return VC_OK;
 }
+// a built graph after vc_add_codes (vc_knn_graph_update.hip): vc_knn_graph*'s checks with n_old as the first position
+static int check_kgupd_args(vc_engine* e, uint32_t k, uint32_t mode, uint64_t n_old, uint32_t k_first, const uint64_t* rows) {
+  uint64_t n_rows = 0;
+  if (!e || !rows) return VC_ERR_INVALID;
+  if (n_old > e->n)
+    return fail(e, VC_ERR_INVALID, "k-NN graph update: n_old %llu exceeds the %llu resident records", (unsigned long long)n_old, (unsigned long long)e->n);
+  return check_kgraph_args(e, k, mode, n_old, 0, k_first, rows, &n_rows);
+}
+static VcKgupdArgs kgupd_args(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, uint64_t* d_rows, uint32_t* d_counts) {
+  return VcKgupdArgs{kgraph_args(e, k, mode, batch, n_old, e->n - n_old, k_first, d_rows ? d_rows + n_old * k : nullptr, d_counts ? d_counts + n_old : nullptr),
+                     n_old, d_rows, d_counts, e->knobs.kgraph_scratch, vc_kgupd_old_batch(e->knobs.kgraph_old_batch), vc_kgupd_window(e->knobs.kgraph_window)};
+}
 
 extern "C" {
 
@@ -1709,6 +1724,42 @@ int vc_knn_graph(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64
                                return vc_search_knn(e, codes, nq, k + 1, VC_MODE_LINEAR, VC_ORDER_ASCENDING, hrows, rcnt, nullptr);
                              },
                              s, &err);
+  return driver_done(e, rc, err);
+}
+
+int vc_knn_graph_update_dev(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, uint64_t* d_rows, uint32_t* d_counts,
+                            vc_knn_graph_update_stats* stats, void* stream) {
+  const int rc = check_kgupd_args(e, k, mode, n_old, k_first, d_rows);
+  if (rc) return rc;
+  if (stats) *stats = vc_knn_graph_update_stats{};
+  if (n_old == e->n) return VC_OK;
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_knn_graph_update_run(store_view(e, mode), store_view(e, VC_MODE_LINEAR).knn, kgupd_args(e, k, mode, batch, n_old, k_first, d_rows, d_counts), stats, s,
+                                   err);
+  });
+}
+
+int vc_knn_graph_update(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, uint64_t* rows, uint32_t* counts,
+                        vc_knn_graph_update_stats* stats) {
+  int rc = check_kgupd_args(e, k, mode, n_old, k_first, rows);
+  if (rc) return rc;
+  if (stats) *stats = vc_knn_graph_update_stats{};
+  if (n_old == e->n) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const VcStoreView v = store_view(e, mode);
+  hipStream_t s = e->stream;
+  std::string err;
+  rc = vc_knn_graph_update_run_host(v, kgupd_args(e, k, mode, batch, n_old, k_first, nullptr, nullptr), rows, counts, stats,
+                                    [&](uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_update_stats* st) {
+                                      return store_call(e, s, [&](hipStream_t cs, std::string* cerr) {
+                                        return vc_knn_graph_update_run(v, store_view(e, VC_MODE_LINEAR).knn,
+                                                                       kgupd_args(e, k, mode, batch, n_old, k_first, d_rows, d_counts), st, cs, cerr);
+                                      });
+                                    },
+                                    [&](const uint64_t* codes, uint32_t nq, uint64_t* hrows, uint32_t* rcnt) {
+                                      return vc_search_knn(e, codes, nq, k + 1, VC_MODE_LINEAR, VC_ORDER_ASCENDING, hrows, rcnt, nullptr);
+                                    },
+                                    s, &err);
   return driver_done(e, rc, err);
 }
 

@@ -55,7 +55,9 @@ struct VcKnobs {
   uint64_t scope_scratch = 64ull << 20;       // VC_SCOPE_SCRATCH: bytes of (query, slice) counters a sub-batch of vc_search_knn_scoped* may hold (vc_scope_plan.hpp)
   uint32_t scope_window = 1u << 20;           // VC_SCOPE_WINDOW: positions of the scope-sorted list per window (0 or above 2^24: the default)
   uint64_t kgraph_scratch = 64ull << 20;      // VC_KGRAPH_SCRATCH: bytes of k' rows a sub-batch of vc_knn_graph* may hold (vc_knn_graph_plan.hpp)
-  bool stream_free_set = false;              // VC_SCAN_STREAM_FREE (tests): the free device memory, in bytes, that vc_build_scan_stream's memory rule is given
+  uint64_t kgraph_old_batch = 0;              // VC_KGRAPH_OLD_BATCH: old ids per batch of vc_knn_graph_update* (0 or above 2^24: the default 2^18, vc_knn_graph_update_plan.hpp)
+  uint64_t kgraph_window = 0;                 // VC_KGRAPH_WINDOW: new records per window of vc_knn_graph_update* (0 or above 2^20: the default 1024)
+  bool stream_free_set = false;             // VC_SCAN_STREAM_FREE (tests): the free device memory, in bytes, that vc_build_scan_stream's memory rule is given
   uint64_t stream_free = 0;
 };
 void read_knobs(VcKnobs* k);   // vc_engine.hip: the one place that reads the environment (once per engine / sharded handle)
@@ -227,6 +229,9 @@ enum VcScratch {
   // the k-NN graph (vc_knn_graph.hip): a batch's ids, codes, flags, maps and retry codes (VcKgraphWork); the k' rows; the host forms'
   // staging; vc_cluster_knn*'s statistics block and its in-degrees when the caller passes none
   VC_KGRAPH_WORK, VC_KGRAPH_ROWS, VC_KGRAPH_STAGE, VC_KGRAPH_STAT, VC_KGRAPH_DEG,
+  // the graph's update (vc_knn_graph_update.hip): an old batch's arrays (VcKgupdWork); the new records' codes; a window's hit list;
+  // the out-of-place rows of a merge launch; the host forms' staging
+  VC_KGRAPH_UPD_WORK, VC_KGRAPH_UPD_NEW, VC_KGRAPH_UPD_HITS, VC_KGRAPH_UPD_ROWS, VC_KGRAPH_UPD_STAGE,
   VC_SCRATCH_BUFS
 };
 // buffer `which` of the handle's table, at least `bytes` large, on the current device; null when it cannot be had (the handle keeps the text)
@@ -669,6 +674,31 @@ int vc_knn_graph_run_host(const VcStoreView& v, const VcKgraphArgs& a, uint64_t*
                           const std::function<int(uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_stats* stats)>& run,
                           const std::function<int(const uint64_t* codes, uint32_t nq, uint64_t* rows, uint32_t* counts)>& host_knn, hipStream_t s,
                           std::string* err);
+// the second answer of vc_knn_graph_run_host alone: rows [a.rows][k] and cnt [a.rows] are the range's outputs in host memory
+int vc_knn_graph_answer_again_host(const VcStoreView& v, const VcKgraphArgs& a, uint64_t* rows, uint32_t* cnt,
+                                   const std::function<int(const uint64_t* codes, uint32_t nq, uint64_t* rows, uint32_t* counts)>& host_knn, hipStream_t s,
+                                   std::string* err);
+// ---- vc_knn_graph_update.hip: a built graph after vc_add_codes (vc_knn_graph_update*, vc_sharded_knn_graph_update*).  One driver for
+// both handle kinds; the plan arithmetic -- the join kernel's map and tile, the window rule, the sub-batches, the scratch layout -- is
+// vc_knn_graph_update_plan.hpp.
+struct VcKgupdArgs {
+  VcKgraphArgs build;              // of the new records' rows: first = n_old, rows = N - n_old > 0, its pointers those of row n_old
+  uint64_t n_old;                  // checked by the caller: n_old < N
+  uint64_t* d_rows;                // [N][k]: the first n_old rows are the graph as it was
+  uint32_t* d_counts;              // [N], nullable
+  uint64_t budget;                 // VcKnobs::kgraph_scratch: the hit list of a window, the out-of-place rows of a merge launch
+  uint32_t old_batch, window;      // vc_kgupd_old_batch(VcKnobs::kgraph_old_batch), vc_kgupd_window(VcKnobs::kgraph_window)
+};
+// the whole call on s with the device of the buffers current: vc_knn_graph_run's waits for the new rows, one wait of 16 bytes per
+// count pass of a window, one at the end for the statistics and the error word (VC_ERR_INVALID: an old count above k)
+int vc_knn_graph_update_run(const VcStoreView& v, const VcKnnSearch& linear_knn, const VcKgupdArgs& a, vc_knn_graph_update_stats* stats, hipStream_t s,
+                            std::string* err);
+// either handle's host form (a's pointers are ignored): the old rows and counts staged up, `run` (the device form on s, which sets
+// the pointers) on them, all N rows and counts home; waits for them.  host_knn as vc_knn_graph_run_host's.  counts, stats nullable
+int vc_knn_graph_update_run_host(const VcStoreView& v, const VcKgupdArgs& a, uint64_t* rows, uint32_t* counts, vc_knn_graph_update_stats* stats,
+                                 const std::function<int(uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_update_stats* stats)>& run,
+                                 const std::function<int(const uint64_t* codes, uint32_t nq, uint64_t* rows, uint32_t* counts)>& host_knn, hipStream_t s,
+                                 std::string* err);
 struct VcKgraphClusterArgs {
   const uint64_t* d_rows;          // [n][k]: vc_knn_graph*'s rows over the whole store
   const uint32_t* d_counts;        // [n], nullable: then every row holds vc_kgraph_row_count(n, k) entries

@@ -200,6 +200,44 @@ int vc_knn_graph_run(const VcStoreView& v, const VcKnnSearch& linear_knn, const 
   return VC_OK;
 }
 
+// A ring overflowed and the device-side recovery gave up: the records of the range whose count is UINT32_MAX are answered again by
+// the handle's host-form LINEAR k-NN, whose host-driven recovery always ends, on their gathered codes, and stripped by the strip
+// kernel's rule.  rows [a.rows][k] and cnt [a.rows] are the range's outputs in host memory.
+int vc_knn_graph_answer_again_host(const VcStoreView& v, const VcKgraphArgs& a, uint64_t* rows, uint32_t* cnt,
+                                   const std::function<int(const uint64_t* codes, uint32_t nq, uint64_t* rows, uint32_t* counts)>& host_knn, hipStream_t s,
+                                   std::string* err) {
+  const size_t n = (size_t)a.rows, k = a.k;
+  int rc;
+  std::vector<uint32_t> ids, where;
+  for (size_t i = 0; i < n; ++i)
+    if (cnt[i] == 0xFFFFFFFFu) {
+      where.push_back((uint32_t)i);
+      ids.push_back(v.id_base + (uint32_t)(a.first + i));
+    }
+  const uint32_t nf = (uint32_t)ids.size(), kp = a.k + 1;
+  if (nf) {
+    const VcKgraphWork wp(nf, v.W, 0);
+    uint8_t* work = (uint8_t*)v.alloc(VC_KGRAPH_WORK, wp.total);   // (the device form is over: its words are free)
+    if (!work) return VC_ERR_NOMEM;
+    uint32_t* d_ids = (uint32_t*)(work + wp.ids);
+    uint32_t* d_found = (uint32_t*)(work + wp.found);
+    uint64_t* d_q = (uint64_t*)(work + wp.q);
+    std::vector<uint64_t> codes((size_t)nf * v.W), hrows((size_t)nf * kp), hout((size_t)nf * k);
+    std::vector<uint32_t> found(nf, 1u), rcnt(nf), hcnt(nf);
+    KG_HIP(hipMemcpyAsync(d_ids, ids.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));
+    if ((rc = v.gather(d_ids, nf, d_q, d_found))) return rc;
+    KG_HIP(hipMemcpyAsync(codes.data(), d_q, codes.size() * 8, hipMemcpyDeviceToHost, s));
+    KG_HIP(hipStreamSynchronize(s));
+    if ((rc = host_knn(codes.data(), nf, hrows.data(), rcnt.data()))) return rc;
+    vc_ids_strip_host(ids.data(), found.data(), hrows.data(), rcnt.data(), nf, kp, a.k, hout.data(), hcnt.data(), nullptr);
+    for (uint32_t f = 0; f < nf; ++f) {
+      std::copy(hout.begin() + (size_t)f * k, hout.begin() + (size_t)(f + 1) * k, rows + (size_t)where[f] * k);
+      cnt[where[f]] = hcnt[f];
+    }
+  }
+  return VC_OK;
+}
+
 int vc_knn_graph_run_host(const VcStoreView& v, const VcKgraphArgs& a, uint64_t* rows, uint32_t* counts, vc_knn_graph_stats* stats,
                           const std::function<int(uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_stats* stats)>& run,
                           const std::function<int(const uint64_t* codes, uint32_t nq, uint64_t* rows, uint32_t* counts)>& host_knn, hipStream_t s,
@@ -221,37 +259,7 @@ int vc_knn_graph_run_host(const VcStoreView& v, const VcKgraphArgs& a, uint64_t*
   KG_HIP(hipMemcpyAsync(rows, d_rows, rbytes, hipMemcpyDeviceToHost, s));
   if (cnt) KG_HIP(hipMemcpyAsync(cnt, d_cnt, cbytes, hipMemcpyDeviceToHost, s));
   KG_HIP(hipStreamSynchronize(s));
-  if (st.n_gave_up) {
-    // a ring overflowed and the device-side recovery gave up: those records are answered again by the handle's host-form LINEAR
-    // k-NN, whose host-driven recovery always ends, on their gathered codes, and stripped by the strip kernel's rule
-    std::vector<uint32_t> ids, where;
-    for (size_t i = 0; i < n; ++i)
-      if (cnt[i] == 0xFFFFFFFFu) {
-        where.push_back((uint32_t)i);
-        ids.push_back(v.id_base + (uint32_t)(a.first + i));
-      }
-    const uint32_t nf = (uint32_t)ids.size(), kp = a.k + 1;
-    if (nf) {
-      const VcKgraphWork wp(nf, v.W, 0);
-      uint8_t* work = (uint8_t*)v.alloc(VC_KGRAPH_WORK, wp.total);   // (the device form is over: its words are free)
-      if (!work) return VC_ERR_NOMEM;
-      uint32_t* d_ids = (uint32_t*)(work + wp.ids);
-      uint32_t* d_found = (uint32_t*)(work + wp.found);
-      uint64_t* d_q = (uint64_t*)(work + wp.q);
-      std::vector<uint64_t> codes((size_t)nf * v.W), hrows((size_t)nf * kp), hout((size_t)nf * k);
-      std::vector<uint32_t> found(nf, 1u), rcnt(nf), hcnt(nf);
-      KG_HIP(hipMemcpyAsync(d_ids, ids.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));
-      if ((rc = v.gather(d_ids, nf, d_q, d_found))) return rc;
-      KG_HIP(hipMemcpyAsync(codes.data(), d_q, codes.size() * 8, hipMemcpyDeviceToHost, s));
-      KG_HIP(hipStreamSynchronize(s));
-      if ((rc = host_knn(codes.data(), nf, hrows.data(), rcnt.data()))) return rc;
-      vc_ids_strip_host(ids.data(), found.data(), hrows.data(), rcnt.data(), nf, kp, a.k, hout.data(), hcnt.data(), nullptr);
-      for (uint32_t f = 0; f < nf; ++f) {
-        std::copy(hout.begin() + (size_t)f * k, hout.begin() + (size_t)(f + 1) * k, rows + (size_t)where[f] * k);
-        cnt[where[f]] = hcnt[f];
-      }
-    }
-  }
+  if (st.n_gave_up && (rc = vc_knn_graph_answer_again_host(v, a, rows, cnt, host_knn, s, err))) return rc;
   if (stats) *stats = st;
   return VC_OK;
 }

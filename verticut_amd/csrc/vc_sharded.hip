@@ -41,6 +41,7 @@
 #include "vc_filter_plan.hpp"
 #include "vc_internal.hpp"
 #include "vc_knn_graph_plan.hpp"
+#include "vc_knn_graph_update_plan.hpp"
 #include "vc_mih.hpp"
 #include "vc_seed_plan.hpp"
 #include "vc_sharded_radius.hpp"
@@ -2701,6 +2702,20 @@ static int check_sharded_cluster_knn_args(vc_sharded* h, const uint64_t* rows, u
   if (flags & ~VC_KNN_EITHER) return sfail(h, VC_ERR_INVALID, "k-NN clusters: unknown flags 0x%x", flags);
   return VC_OK;
 }
+// a built graph after vc_sharded_add_codes (vc_knn_graph_update.hip): the graph call's checks with n_old as the first position
+static int check_sharded_kgupd_args(vc_sharded* h, uint32_t k, uint32_t mode, uint64_t n_old, uint32_t k_first, const uint64_t* rows) {
+  uint64_t n_rows = 0;
+  if (!h || !rows) return VC_ERR_INVALID;
+  if (n_old > h->n)
+    return sfail(h, VC_ERR_INVALID, "k-NN graph update: n_old %llu exceeds the %llu resident records", (unsigned long long)n_old, (unsigned long long)h->n);
+  return check_sharded_kgraph_args(h, k, mode, n_old, 0, k_first, rows, &n_rows);
+}
+static VcKgupdArgs sharded_kgupd_args(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, uint64_t* d_rows,
+                                      uint32_t* d_counts) {
+  return VcKgupdArgs{sharded_kgraph_args(h, k, mode, batch, n_old, h->n - n_old, k_first, d_rows ? d_rows + n_old * k : nullptr,
+                                         d_counts ? d_counts + n_old : nullptr),
+                     n_old, d_rows, d_counts, h->knobs.kgraph_scratch, vc_kgupd_old_batch(h->knobs.kgraph_old_batch), vc_kgupd_window(h->knobs.kgraph_window)};
+}
 
 extern "C" {
 
@@ -2737,6 +2752,40 @@ int vc_sharded_knn_graph(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batc
                                    return (int)VC_OK;
                                  },
                                  S, err);
+  });
+}
+
+int vc_sharded_knn_graph_update_dev(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, uint64_t* d_rows,
+                                    uint32_t* d_counts, vc_knn_graph_update_stats* stats, void* stream) {
+  const int rc = check_sharded_kgupd_args(h, k, mode, n_old, k_first, d_rows);
+  if (rc) return rc;
+  if (stats) *stats = vc_knn_graph_update_stats{};
+  if (n_old == h->n) return VC_OK;
+  return sharded_store_call(h, mode, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_knn_graph_update_run(v, sharded_store_view(h, VC_MODE_LINEAR, S).knn, sharded_kgupd_args(h, k, mode, batch, n_old, k_first, d_rows, d_counts), stats, S,
+                                   err);
+  });
+}
+
+int vc_sharded_knn_graph_update(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, uint64_t* rows, uint32_t* counts,
+                                vc_knn_graph_update_stats* stats) {
+  const int rc = check_sharded_kgupd_args(h, k, mode, n_old, k_first, rows);
+  if (rc) return rc;
+  if (stats) *stats = vc_knn_graph_update_stats{};
+  if (n_old == h->n) return VC_OK;
+  return sharded_store_call(h, mode, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_knn_graph_update_run_host(v, sharded_kgupd_args(h, k, mode, batch, n_old, k_first, nullptr, nullptr), rows, counts, stats,
+                                        [&](uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_update_stats* st) {
+                                          return vc_knn_graph_update_run(v, sharded_store_view(h, VC_MODE_LINEAR, S).knn,
+                                                                         sharded_kgupd_args(h, k, mode, batch, n_old, k_first, d_rows, d_counts), st, S, err);
+                                        },
+                                        [&](const uint64_t* codes, uint32_t nq, uint64_t* hrows, uint32_t* rcnt) {   // (its shards recover on the host)
+                                          const int r = vc_sharded_search_knn(h, codes, nq, k + 1, VC_MODE_LINEAR, VC_ORDER_ASCENDING, hrows, rcnt, nullptr);
+                                          if (r) return r;
+                                          VS_HIP(h, hipSetDevice(h->root));
+                                          return (int)VC_OK;
+                                        },
+                                        S, err);
   });
 }
 

@@ -57,6 +57,7 @@ EXPORTS = [
     "vc_search_knn_scoped", "vc_search_knn_scoped_dev", "vc_sharded_search_knn_scoped", "vc_sharded_search_knn_scoped_dev",
     "vc_knn_graph", "vc_knn_graph_dev", "vc_sharded_knn_graph", "vc_sharded_knn_graph_dev",
     "vc_cluster_knn", "vc_cluster_knn_dev", "vc_sharded_cluster_knn", "vc_sharded_cluster_knn_dev",
+    "vc_knn_graph_update", "vc_knn_graph_update_dev", "vc_sharded_knn_graph_update", "vc_sharded_knn_graph_update_dev",
 ]
 KNN_MUTUAL, KNN_EITHER = 0, 1   # VC_KNN_*: cluster_knn joins i and j iff each lists the other / iff one lists the other
 FILTER_MASK, FILTER_ROOTS, FILTER_EQUAL, FILTER_NOT_EQUAL, FILTER_BITS = 0, 1, 2, 3, 4   # VC_FILTER_*: how search_knn_filtered reads `sel`
@@ -170,6 +171,15 @@ class VcKnnGraphStats(C.Structure):
     def as_dict(self):
         """{n_rounds_max, k_last, n_searched, n_linear, n_gave_up: int}"""
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class VcKnnGraphUpdateStats(C.Structure):
+    _fields_ = [("build", VcKnnGraphStats), ("n_rows_changed", C.c_uint64), ("n_inserted", C.c_uint64), ("n_hits", C.c_uint64),
+                ("n_windows", C.c_uint32), ("n_halvings", C.c_uint32)]
+
+    def as_dict(self):
+        """{build: VcKnnGraphStats' dict, n_rows_changed, n_inserted, n_hits, n_windows, n_halvings: int}"""
+        return {name: getattr(self, name).as_dict() if name == "build" else int(getattr(self, name)) for name, _ in self._fields_}
 
 
 class VcClusterKnnStats(C.Structure):
@@ -343,6 +353,10 @@ def load_library():
     L.vc_knn_graph_dev.argtypes = [vp, u32, u32, u32, u64, u64, u32, vp, vp, vp, vp]
     L.vc_sharded_knn_graph.argtypes = [vp, u32, u32, u32, u64, u64, u32, vp, vp, vp]
     L.vc_sharded_knn_graph_dev.argtypes = [vp, u32, u32, u32, u64, u64, u32, vp, vp, vp, vp]
+    L.vc_knn_graph_update.argtypes = [vp, u32, u32, u32, u64, u32, vp, vp, vp]
+    L.vc_knn_graph_update_dev.argtypes = [vp, u32, u32, u32, u64, u32, vp, vp, vp, vp]
+    L.vc_sharded_knn_graph_update.argtypes = [vp, u32, u32, u32, u64, u32, vp, vp, vp]
+    L.vc_sharded_knn_graph_update_dev.argtypes = [vp, u32, u32, u32, u64, u32, vp, vp, vp, vp]
     L.vc_cluster_knn.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]
     L.vc_cluster_knn_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]
     L.vc_sharded_cluster_knn.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]
@@ -670,6 +684,35 @@ def _knn_graph(self, fn, k, mode, batch, first, count, k_first, with_stats):
 def _knn_graph_dev(self, fn, k, d_rows, d_counts, mode, batch, first, count, k_first, with_stats, stream):
     st = VcKnnGraphStats()
     self._check(fn(self._h, k, mode, batch, first, count, k_first, d_rows, d_counts, C.byref(st) if with_stats else None, stream))
+    return st.as_dict() if with_stats else None
+
+
+def _knn_graph_update(self, fn, rows, counts, k, mode, batch, k_first, with_stats):
+    """shared by Engine.knn_graph_update and ShardedEngine.knn_graph_update: (rows uint64 [N, k], counts uint32 [N] | None[, stats dict])"""
+    n = len(self)
+    old = np.ascontiguousarray(rows, dtype=np.uint64)
+    if old.ndim != 2 or old.shape[0] > n or (k is not None and old.shape[1] != k):
+        raise VcError(VC_ERR_INVALID, "rows must be the [n_old, k] graph of knn_graph over the store before the append")
+    n_old, k = old.shape
+    if counts is not None:
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        if counts.shape[0] != n_old:
+            raise VcError(VC_ERR_INVALID, "counts must have one word per old row")
+    out = np.empty((max(n, 1), k), dtype=np.uint64)        # (an empty store: the call writes no word, but takes no null pointer)
+    out[:n_old] = old
+    cnt = None
+    if counts is not None:
+        cnt = np.zeros(max(n, 1), dtype=np.uint32)
+        cnt[:n_old] = counts
+    st = VcKnnGraphUpdateStats()
+    self._check(fn(self._h, k, mode, batch, n_old, k_first, _p(out), _p(cnt) if cnt is not None else None, C.byref(st)))
+    out, cnt = out[:n], cnt[:n] if cnt is not None else None
+    return (out, cnt, st.as_dict()) if with_stats else (out, cnt)
+
+
+def _knn_graph_update_dev(self, fn, k, n_old, d_rows, d_counts, mode, batch, k_first, with_stats, stream):
+    st = VcKnnGraphUpdateStats()
+    self._check(fn(self._h, k, mode, batch, n_old, k_first, d_rows, d_counts, C.byref(st) if with_stats else None, stream))
     return st.as_dict() if with_stats else None
 
 
@@ -1126,6 +1169,17 @@ class Engine:
         order.  Returns the stats dict (None without with_stats)."""
         return _knn_graph_dev(self, self._L.vc_knn_graph_dev, k, d_rows, d_counts, mode, batch, first, count, k_first, with_stats, stream)
 
+    def knn_graph_update(self, rows, counts=None, mode=MODE_LINEAR, batch=0, k_first=0, with_stats=False):
+        """vc_knn_graph_update: the graph after an append.  rows [n_old, k] (and counts [n_old] or None) are knn_graph's over the store
+        when it held its first n_old records; returns the rows [N, k] and counts [N] (None without counts) of knn_graph over the store
+        now, the same words.  In MODE_MIH_EXACT run update_index() first."""
+        return _knn_graph_update(self, self._L.vc_knn_graph_update, rows, counts, None, mode, batch, k_first, with_stats)
+
+    def knn_graph_update_dev(self, k, n_old, d_rows, d_counts=None, mode=MODE_MIH_EXACT, batch=0, k_first=0, with_stats=True, stream=None):
+        """vc_knn_graph_update_dev: raw device addresses (d_rows N * k uint64 whose first n_old rows are the graph as it was, d_counts
+        N uint32 or None); results valid in `stream` order.  Returns the stats dict (or None)."""
+        return _knn_graph_update_dev(self, self._L.vc_knn_graph_update_dev, k, n_old, d_rows, d_counts, mode, batch, k_first, with_stats, stream)
+
     def cluster_knn(self, rows, counts, kk, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, with_in_degree=True):
         """vc_cluster_knn: components and in-degrees of a graph knn_graph built over the whole store (rows [N, k], counts [N] or None).
         Row i lists j iff j is among its first kk entries at a distance <= max_dist; KNN_MUTUAL joins i and j iff each lists the other,
@@ -1487,6 +1541,17 @@ class ShardedEngine:
         """vc_sharded_knn_graph_dev: raw device addresses on the root device (d_rows n * k uint64, d_counts n uint32 or None); results valid in `stream`
         order.  Returns the stats dict (None without with_stats)."""
         return _knn_graph_dev(self, self._L.vc_sharded_knn_graph_dev, k, d_rows, d_counts, mode, batch, first, count, k_first, with_stats, stream)
+
+    def knn_graph_update(self, rows, counts=None, mode=MODE_LINEAR, batch=0, k_first=0, with_stats=False):
+        """vc_sharded_knn_graph_update: the graph after an append.  rows [n_old, k] (and counts [n_old] or None) are knn_graph's over the
+        store when it held its first n_old records; returns the rows [N, k] and counts [N] (None without counts) of knn_graph over the
+        store now, the same words.  In MODE_MIH_EXACT run update_index() first."""
+        return _knn_graph_update(self, self._L.vc_sharded_knn_graph_update, rows, counts, None, mode, batch, k_first, with_stats)
+
+    def knn_graph_update_dev(self, k, n_old, d_rows, d_counts=None, mode=MODE_MIH_EXACT, batch=0, k_first=0, with_stats=True, stream=None):
+        """vc_sharded_knn_graph_update_dev: raw device addresses on the root device (d_rows N * k uint64 whose first n_old rows are the
+        graph as it was, d_counts N uint32 or None); results valid in `stream` order.  Returns the stats dict (or None)."""
+        return _knn_graph_update_dev(self, self._L.vc_sharded_knn_graph_update_dev, k, n_old, d_rows, d_counts, mode, batch, k_first, with_stats, stream)
 
     def cluster_knn(self, rows, counts, kk, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, with_in_degree=True):
         """vc_sharded_cluster_knn: components and in-degrees of a graph knn_graph built over the whole store (rows [N, k], counts [N] or None).

@@ -170,6 +170,11 @@ class Backend {
   // VC_MODE_MIH_EXACT; counts and stats may be null
   virtual int knn_graph(uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first, uint64_t* rows, uint32_t* counts,
                         vc_knn_graph_stats* stats) = 0;
+  // that graph after add_codes (vc_knn_graph_update / vc_sharded_knn_graph_update): rows has room for N * k words and counts (nullable)
+  // for N, and their first n_old rows are knn_graph's over the store when it held its first n_old records; afterwards all N rows are
+  // knn_graph's over the store now, the same words.  In VC_MODE_MIH_EXACT the index must be current (update_index)
+  virtual int knn_graph_update(uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, uint64_t* rows, uint32_t* counts,
+                               vc_knn_graph_update_stats* stats) = 0;
   // components and in-degrees of that graph over the whole store (vc_cluster_knn / vc_sharded_cluster_knn): an edge is one of a row's
   // first kk entries at a distance <= max_dist; VC_KNN_MUTUAL joins two records iff each lists the other, VC_KNN_EITHER iff one does;
   // labels[i] = the smallest id of the component; counts, in_degree and stats may be null
@@ -272,6 +277,10 @@ class Engine : public Backend {
   int knn_graph(uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first, uint64_t* rows, uint32_t* counts,
                 vc_knn_graph_stats* stats) override {
     return vc_knn_graph(h_, k, mode, batch, first, count, k_first, rows, counts, stats);
+  }
+  int knn_graph_update(uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, uint64_t* rows, uint32_t* counts,
+                       vc_knn_graph_update_stats* stats) override {
+    return vc_knn_graph_update(h_, k, mode, batch, n_old, k_first, rows, counts, stats);
   }
   int cluster_knn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t* labels,
                   uint32_t* in_degree, vc_cluster_knn_stats* stats) override {
@@ -401,6 +410,10 @@ class ShardedEngine : public Backend {
   int knn_graph(uint32_t k, uint32_t mode, uint32_t batch, uint64_t first, uint64_t count, uint32_t k_first, uint64_t* rows, uint32_t* counts,
                 vc_knn_graph_stats* stats) override {
     return vc_sharded_knn_graph(h_, k, mode, batch, first, count, k_first, rows, counts, stats);
+  }
+  int knn_graph_update(uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, uint64_t* rows, uint32_t* counts,
+                       vc_knn_graph_update_stats* stats) override {
+    return vc_sharded_knn_graph_update(h_, k, mode, batch, n_old, k_first, rows, counts, stats);
   }
   int cluster_knn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t* labels,
                   uint32_t* in_degree, vc_cluster_knn_stats* stats) override {
