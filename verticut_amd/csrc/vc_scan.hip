@@ -43,6 +43,11 @@
 #ifndef VC_SCAN_RECUT_EVERY
 #define VC_SCAN_RECUT_EVERY 32u
 #endif
+// blocks per CU (= waves per SIMD) the stream form (vc_scan_kernel_stream) is launched with: its 78 VGPRs would admit six,
+// five stream faster
+#ifndef VC_STREAM_BLOCKS_PER_CU
+#define VC_STREAM_BLOCKS_PER_CU 5
+#endif
 
 namespace {
 
@@ -628,10 +633,12 @@ __global__ void __launch_bounds__(BLK, MINW ? MINW : (BLK == 512 ? 2 : ((W >= 4 
 // The records lie sorted by their key word, so the 256 records of one wave-load -- a granule -- share the leading key bits its
 // header names.  The hot loop streams the other three words only (12 bytes per record, a lane owns FOUR consecutive records per
 // 16-byte load, 6 loads per lane and 2048-record chunk) and runs 3 xor + 3 accumulating v_bcnt per record: the key enters as
-// the wave-uniform start value of the chain, tau + the most key bits that can still match (vc_stream_chain_start), computed
-// with scalar instructions from the header and handed to the first v_bcnt as its SGPR accumulate operand.  The chain is then
-// an UPPER bound of tau + matching bits, i.e. the test is a lower bound on the distance, and it is the same OR-reduce and one
-// compare per query as in vc_scan_kernel's small-tile form.  Where it fires, the items whose lower bound passes read their
+// the wave-uniform start value of the chain, the most key bits that can still match (vc_stream_chain_base), computed with
+// scalar instructions from the header and handed to the first v_bcnt as its SGPR accumulate operand.  The chain is then an
+// UPPER bound of the matching bits, i.e. a lower bound on the distance; the eight chains of a tile are max-reduced
+// (v_max3_u32) and compared once per query with 128 - tau (vc_stream_fire_level), which sits in LDS next to the block's tau
+// and arrives as a VGPR with the next query's words -- tau itself never has to become a scalar (vc_stream_chain_start is the
+// same test in one piece).  Where it fires, the items whose lower bound passes read their
 // key word and finish the exact distance; survivors read perm[] for their id and append as vc_scan_slow does: ring, cursor,
 // histogram and tau keep their contract, so select, recovery and the clean hand-back follow unchanged.
 // Everything else is vc_scan_kernel's machinery: persistent grid, hand-issued loads from an SGPR base (nt beyond the
@@ -654,7 +661,7 @@ __device__ __forceinline__ uint32_t vc_bcnt_acc_s(uint32_t x, uint32_t acc_unifo
 // words in LDS ([q][4]: key, t0, t1, t2).  Nothing but wave-uniform scalars lives across the wave-loads.
 __device__ __forceinline__ void vc_scan_slow_stream(const VcScanRare& p, const VcScanParams& sp, const vc_u32x4 (&r)[VC_ST_U][3],
                                                     const VcStreamHeader (&h)[VC_ST_U], const uint32_t* sw, uint32_t q, uint64_t chunk_base,
-                                                    uint32_t* st) {
+                                                    uint32_t* st, uint32_t* sl) {
   const uint32_t lane = vc_lane();
   uint32_t tid = threadIdx.x;   // opaque inside the rare branch, as in vc_scan_slow
   asm volatile("" : "+v"(tid));
@@ -662,7 +669,9 @@ __device__ __forceinline__ void vc_scan_slow_stream(const VcScanRare& p, const V
   uint32_t t = min(vc_ld_relaxed(tau_q), st[q]);
   uint64_t* ring = p.buf + (uint64_t)q * p.cap;
   uint32_t* hist = p.hist + (uint64_t)q * p.hist_stride;
-  const uint32_t qk = ~sw[q * 4], q0 = ~sw[q * 4 + 1], q1 = ~sw[q * 4 + 2], q2 = ~sw[q * 4 + 3];
+  // The streamed words are recounted in the hot loop's own matching-bits form, r ^ (complemented word): written as
+  // r ^ ~word hipcc turns it into ~r ^ word and hoists the 24 complements of the tile into the hot block.
+  const uint32_t qk = ~sw[q * 4], s0 = sw[q * 4 + 1], s1 = sw[q * 4 + 2], s2 = sw[q * 4 + 3];
   uint32_t seen = 0;
   bool recut = false;
 #pragma unroll
@@ -673,7 +682,7 @@ __device__ __forceinline__ void vc_scan_slow_stream(const VcScanRare& p, const V
     bool c[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      dt[i] = (uint32_t)__builtin_popcount(r[u][0][i] ^ q0) + (uint32_t)__builtin_popcount(r[u][1][i] ^ q1) + (uint32_t)__builtin_popcount(r[u][2][i] ^ q2);
+      dt[i] = 96u - ((uint32_t)__builtin_popcount(r[u][0][i] ^ s0) + (uint32_t)__builtin_popcount(r[u][1][i] ^ s1) + (uint32_t)__builtin_popcount(r[u][2][i] ^ s2));
       c[i] = dt[i] + klb <= t && pos0 + i < p.n;
     }
     const bool anyc = c[0] || c[1] || c[2] || c[3];
@@ -721,7 +730,10 @@ __device__ __forceinline__ void vc_scan_slow_stream(const VcScanRare& p, const V
       if (lane == 0) atomicMin(tau_q, t);
     }
   }
-  if (lane == 0) st[q] = t;
+  if (lane == 0) {
+    st[q] = t;
+    sl[q] = vc_stream_fire_level(t);
+  }
 }
 
 template <int QT>
@@ -730,6 +742,7 @@ __global__ void __launch_bounds__(256, VC_SCAN_SMALL_WAVES) vc_scan_kernel_strea
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint64_t* sq = (uint64_t*)smem;                           // [QT][2] complemented query words
   uint32_t* st = (uint32_t*)(smem + (size_t)QT * 16);       // [QT]    block-local copy of tau
+  uint32_t* sl = st + QT;                                   // [QT]    vc_stream_fire_level(st[q]): what the hot loop compares with
   for (uint32_t i = threadIdx.x; i < QT * 2; i += BLK) sq[i] = ~p.queries[i];
   if (p.shist) {   // bootstrap folded into the prologue, as in vc_scan_kernel
     for (uint32_t q = threadIdx.x / VC_WAVE; q < QT; q += BLK / VC_WAVE) {
@@ -737,11 +750,16 @@ __global__ void __launch_bounds__(256, VC_SCAN_SMALL_WAVES) vc_scan_kernel_strea
       if (cut == 0xFFFFFFFFu) cut = p.bits;
       if ((threadIdx.x & (VC_WAVE - 1)) == 0) {
         st[q] = cut;
+        sl[q] = vc_stream_fire_level(cut);
         if (blockIdx.x == 0) atomicMin(p.tau + (size_t)q * p.qs, cut);
       }
     }
   } else {
-    for (uint32_t i = threadIdx.x; i < QT; i += BLK) st[i] = vc_ld_relaxed(p.tau + (size_t)i * p.qs);
+    for (uint32_t i = threadIdx.x; i < QT; i += BLK) {
+      const uint32_t t = vc_ld_relaxed(p.tau + (size_t)i * p.qs);
+      st[i] = t;
+      sl[i] = vc_stream_fire_level(t);
+    }
   }
   __syncthreads();
 
@@ -789,34 +807,33 @@ __global__ void __launch_bounds__(256, VC_SCAN_SMALL_WAVES) vc_scan_kernel_strea
     uint32_t wq[2][3], tq[2];   // the LDS reads of query q + 1 are in flight while query q is verified
 #pragma unroll
     for (int j = 0; j < 3; ++j) wq[0][j] = sw[1 + j];
-    tq[0] = st[0];
+    tq[0] = sl[0];
 #pragma unroll
     for (int q = 0; q < QT; ++q) {
       if (q + 1 < QT) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) wq[(q + 1) & 1][j] = sw[(q + 1) * 4 + 1 + j];
-        tq[(q + 1) & 1] = st[q + 1];
+        tq[(q + 1) & 1] = sl[q + 1];
       }
       const uint32_t(&w)[3] = wq[q & 1];
-      const uint32_t tau = __builtin_amdgcn_readfirstlane(tq[q & 1]);
-      uint32_t orv = 0;
+      uint32_t mx = 0;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const uint32_t start = tau + slack[u] + vc_stream_popc((ck[q] ^ h[u].prefix) & h[u].mask);   // = vc_stream_chain_start
+        const uint32_t base = slack[u] + vc_stream_popc((ck[q] ^ h[u].prefix) & h[u].mask);   // = vc_stream_chain_base
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          uint32_t d = vc_bcnt_acc_s(r[u][0][i] ^ w[0], start);
+          uint32_t d = vc_bcnt_acc_s(r[u][0][i] ^ w[0], base);
           d = vc_bcnt_acc(r[u][1][i] ^ w[1], d);
           d = vc_bcnt_acc(r[u][2][i] ^ w[2], d);
-          orv |= d;
+          mx = max(mx, d);
         }
       }
-      if (__ballot(orv >= 128u) != 0) hm |= 1u << q;
+      if (__ballot(mx >= tq[q & 1]) != 0) hm |= 1u << q;   // tq = vc_stream_fire_level(tau): a VGPR, tau never becomes a scalar
     }
     while (hm) {
       const uint32_t q = (uint32_t)__builtin_ctz(hm);
       hm &= hm - 1u;
-      vc_scan_slow_stream(rare, p, r, h, sw, q, chunk * VC_STREAM_CHUNK, st);
+      vc_scan_slow_stream(rare, p, r, h, sw, q, chunk * VC_STREAM_CHUNK, st, sl);
     }
   };
 
@@ -1644,8 +1661,9 @@ hipError_t vc_launch_scan_stream(VcScanParams p, const VcScanStream& st, uint64_
 #define VC_LAUNCH_STREAM(QT_)                                                                                   \
   {                                                                                                             \
     auto kern = vc_scan_kernel_stream<QT_>;                                                                     \
-    const size_t lds_q = (size_t)QT_ * (2 * 8 + 4);                                                             \
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(p.nchunks, resident_grid(kern, 256, lds_q, n_cu, want_blocks)); \
+    const size_t lds_q = (size_t)QT_ * (2 * 8 + 4 + 4);                                                         \
+    const uint32_t resident = std::min(resident_grid(kern, 256, lds_q, n_cu, want_blocks), n_cu * VC_STREAM_BLOCKS_PER_CU); \
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(p.nchunks, resident);                                    \
     if (knobs && knobs->scan_shape_trace)                                                                       \
       fprintf(stderr, "[scan shape] stream QT=%d grid=%u nchunks=%llu qt=%u\n", (int)(QT_), grid, (unsigned long long)p.nchunks, p.qt); \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_q, s, p);                                               \

@@ -50,6 +50,15 @@ VC_STREAM_HD static inline uint32_t vc_stream_chain_start(VcStreamHeader h, uint
   return tau + (32u - vc_stream_popc(h.mask)) + vc_stream_popc(~(qkey ^ h.prefix) & h.mask);
 }
 
+// The kernel splits that formula so that tau never has to become a scalar: the chain starts at the header's part alone, the
+// most key bits that can match (wave-uniform, scalar arithmetic) ...
+VC_STREAM_HD static inline uint32_t vc_stream_chain_base(VcStreamHeader h, uint32_t qkey) {
+  return (32u - vc_stream_popc(h.mask)) + vc_stream_popc(~(qkey ^ h.prefix) & h.mask);
+}
+// ... and is compared against the fire level of tau: chain_base + matching >= fire_level(tau) <=> chain_start + matching >= 128
+// for every tau <= 128 (a larger tau accepts everything, as 128 does).
+VC_STREAM_HD static inline uint32_t vc_stream_fire_level(uint32_t tau) { return 128u - (tau < 128u ? tau : 128u); }
+
 // One allocation of uint32 words: key | t0 | t1 | t2 (stride words each) | perm (n_pad) | headers (2 words per granule).
 struct VcStreamPlan {
   uint64_t n, n_pad, chunks, granules, stride;
