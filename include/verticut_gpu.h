@@ -1079,8 +1079,8 @@ int vc_knn_graph(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64
  * k_first, an approximate or unknown mode, n_old > N; VC_ERR_STATE in MIH mode without a current index (a stale index after
  * vc_add_codes counts as none).  An old count above k (UINT32_MAX included) is found ON THE DEVICE and gives VC_ERR_INVALID --
  * vc_cluster_knn*'s protocol: the error word comes home with the stats; THE OUTPUTS ARE THEN UNDEFINED.
- * Not offered: a form for vc_retain* (a row that listed a removed record needs a search), graphs over a part of the range, and an
- * automatic switch to a rebuild when the append is large -- the join costs n_old * n_new pair-words, which the caller weighs.
+ * Not offered: a form for vc_retain* in this call (a row that listed a removed record may need a search: that form is
+ * vc_knn_graph_retain* below), graphs over a part of the range, and an automatic switch to a rebuild when the append is large -- the join costs n_old * n_new pair-words, which the caller weighs.
  * Scratch: grow-only buffers of the handle, this call's own; every word is written before it is read. */
 typedef struct vc_knn_graph_update_stats {   /* 64 bytes */
   vc_knn_graph_stats build;   /* of the new records' rows: vc_knn_graph* over [n_old, N) */
@@ -1096,6 +1096,60 @@ int vc_knn_graph_update_dev(vc_engine* e, uint32_t k, uint32_t mode, uint32_t ba
  * them.  A new row that the linear scan passed on with count UINT32_MAX is answered again as vc_knn_graph does it. */
 int vc_knn_graph_update(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first,
                         uint64_t* rows, uint32_t* counts, vc_knn_graph_update_stats* stats);
+
+/* ---- a built k-NN graph after a removal: vc_knn_graph_retain* ------------------------------------------------------------------------------
+ * The other half of the store's life cycle: after vc_retain* swept tombstones, a grouper's duplicates or one tenant out of a large
+ * store, this call brings a built graph up to date without building it again.
+ * PRECONDITION.  vc_retain* has run; n_old is the record count before it and d_new_ids (n_old words) the map it wrote.  d_rows
+ * (n_old * k words) and d_counts (n_old words) are what vc_knn_graph* wrote, over the full range and with this k, for the store as it
+ * was before the removal.  d_counts may be NULL: every old row then holds min(k, n_old - 1) entries, and no counts are written.  In
+ * VC_MODE_MIH_EXACT the index must be current; vc_retain* leaves a current index current.
+ * POSTCONDITION.  K = vc_size now.  Rows and counts [0, K) are THE SAME WORDS as vc_knn_graph*(first = 0, count = K) writes for the
+ * store now with this k, in both modes, for every batch, k_first and scratch budget, on both handle kinds -- under vc_knn_graph*'s
+ * clause for the reference-fidelity flags, which governs the repaired rows.  Rows and counts [K, n_old) are unspecified afterwards.
+ * Nothing outside the two buffers is written.
+ * k, mode, batch and k_first mean what they mean to vc_knn_graph* and govern the repaired rows only; the translation has no mode.
+ * WHY.  vc_retain* renumbers the survivors monotonically, so the order of (dist << 32 | id) among survivors is the same before and
+ * after.  An old row whose entries all survive is, once its ids are translated, word for word the row a rebuild writes.  If some
+ * entries died, the m that survive are exactly the m smallest entries of the rebuilt row, because every record the old row did not
+ * list lies at or above the row's last entry.  Such a row is wrong only if it became SHORT: m < min(k, K - 1).  A row that held the
+ * whole old store (count < k) holds the whole new store after the drop and is never short.
+ * HOW.  1. The map is checked once: a live flag per word, an exclusive scan, and every live word compared with id_base + its rank.
+ * 2. The old rows go by CHUNKS of max(1, VC_KGRAPH_SCRATCH / (8 k)) rows in ascending order.  The translate kernel skips the row of a
+ * removed record, reads every entry's new id straight from the map, repacks the live entries as dist << 32 | new id in their old
+ * order, pads the tail with UINT64_MAX and writes the row OUT OF PLACE with its new count; a copy puts the chunk's rows back at their
+ * new positions, which lie at or before the chunk's own start, so nothing depends on block order.  3. The short flags are scanned and a
+ * compacting gather gives the ascending list of the short rows' ids.  4. ONE WAIT for the length S of that list, the error word and
+ * the tallies.  5. If S > 0, vc_knn_graph*'s driver runs over that id list -- batches, rounds, waits and the linear hand-over as in
+ * vc_knn_graph* -- and writes each settled row and count to its own place.  6. One last wait fetches the repair's stats, and only
+ * when stats is given.
+ * STATS (HOST memory in both forms, may be NULL).  n_rows_kept, n_rows_short and n_entries_dropped are functions of the database
+ * before, the removal and k only; `repair` depends on the knobs as vc_knn_graph_stats does.
+ * DEGENERATE.  K == n_old: VC_OK, nothing written, the stats zero apart from n_rows_kept.  K == 0 or n_old == 0: VC_OK, nothing
+ * written.  K == 1: count 0 and a UINT64_MAX row.
+ * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle, null rows or a null map, k outside
+ * 1 .. VC_MAX_K - 1, a bad k_first, an approximate or unknown mode, n_old < vc_size; VC_ERR_STATE in MIH mode without a current
+ * index.  Found ON THE DEVICE, giving VC_ERR_INVALID through the error word that comes home with the first wait -- vc_cluster_knn*'s
+ * protocol; THE OUTPUTS ARE THEN UNDEFINED, but nothing outside the two buffers is read or written: an old count above k (UINT32_MAX
+ * included), an entry whose id lies outside the old store, and a map that is not vc_retain*'s -- the live words must number exactly K,
+ * and the j-th live word must equal id_base + j.
+ * Not offered: graphs over a part of the range, and an automatic switch to a rebuild when most rows are short (after a dedup of a
+ * clustered store nearly every row is): the call then costs the rebuild plus the translation, which the caller weighs.
+ * Scratch: grow-only buffers of the handle, this call's own and vc_knn_graph*'s; every word is written before it is read. */
+typedef struct vc_knn_graph_retain_stats {   /* 64 bytes */
+  vc_knn_graph_stats repair;     /* of the searches that repaired the short rows (zero if none) */
+  uint64_t n_rows_kept;          /* K */
+  uint64_t n_rows_short;         /* surviving rows with m < min(k, K - 1): searched again */
+  uint64_t n_entries_dropped;    /* entries of SURVIVING rows whose record was removed */
+  uint64_t pad;
+} vc_knn_graph_retain_stats;
+int vc_knn_graph_retain_dev(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first,
+                            const uint32_t* d_new_ids, uint64_t* d_rows, uint32_t* d_counts,
+                            vc_knn_graph_retain_stats* stats, void* stream);
+/* The same for the map, rows and counts in host memory: all three are staged up, the K rows and counts come home; waits for them.  A
+ * repaired row that the linear scan passed on with count UINT32_MAX is answered again as vc_knn_graph does it. */
+int vc_knn_graph_retain(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first,
+                        const uint32_t* new_ids, uint64_t* rows, uint32_t* counts, vc_knn_graph_retain_stats* stats);
 
 /* ---- components and in-degrees of the k-NN graph: vc_cluster_knn* -------------------------------------------------------------------------
  * Density-adaptive grouping: where one radius is too tight in sparse regions and too loose in dense ones, "i and j list each other
@@ -1422,6 +1476,14 @@ int vc_sharded_knn_graph_update_dev(vc_sharded* h, uint32_t k, uint32_t mode, ui
                                     uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_update_stats* stats, void* stream);
 int vc_sharded_knn_graph_update(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first,
                                 uint64_t* rows, uint32_t* counts, vc_knn_graph_update_stats* stats);
+/* That graph after vc_sharded_retain*: contract, steps, stats and errors as vc_knn_graph_retain_dev / vc_knn_graph_retain.  Every
+ * pointer of the device form lives on the ROOT device, where the translation and the scans run; the shards are reached only through
+ * the store's own search and its gather by id, so a removal that moves records across a shard boundary is nothing special. */
+int vc_sharded_knn_graph_retain_dev(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first,
+                                    const uint32_t* d_new_ids, uint64_t* d_rows, uint32_t* d_counts,
+                                    vc_knn_graph_retain_stats* stats, void* stream);
+int vc_sharded_knn_graph_retain(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first,
+                                const uint32_t* new_ids, uint64_t* rows, uint32_t* counts, vc_knn_graph_retain_stats* stats);
 /* Components and in-degrees of that graph: as vc_cluster_knn_dev / vc_cluster_knn; the rows live on the ROOT device, no shard is
  * touched. */
 int vc_sharded_cluster_knn_dev(vc_sharded* h, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags,

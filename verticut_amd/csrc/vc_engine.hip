@@ -1686,6 +1686,28 @@ static VcKgupdArgs kgupd_args(vc_engine* e, uint32_t k, uint32_t mode, uint32_t 
   return VcKgupdArgs{kgraph_args(e, k, mode, batch, n_old, e->n - n_old, k_first, d_rows ? d_rows + n_old * k : nullptr, d_counts ? d_counts + n_old : nullptr),
                      n_old, d_rows, d_counts, e->knobs.kgraph_scratch, vc_kgupd_old_batch(e->knobs.kgraph_old_batch), vc_kgupd_window(e->knobs.kgraph_window)};
 }
+// a built graph after vc_retain* (vc_knn_graph_retain.hip): vc_knn_graph*'s checks over the store as it is now
+static int check_kgret_args(vc_engine* e, uint32_t k, uint32_t mode, uint64_t n_old, uint32_t k_first, const uint32_t* new_ids, const uint64_t* rows) {
+  uint64_t n_rows = 0;
+  if (!e || !rows || !new_ids) return VC_ERR_INVALID;
+  const int rc = check_kgraph_args(e, k, mode, 0, 0, k_first, rows, &n_rows);
+  if (rc) return rc;
+  if (n_old < e->n)
+    return fail(e, VC_ERR_INVALID, "k-NN graph retain: n_old %llu is below the %llu resident records", (unsigned long long)n_old, (unsigned long long)e->n);
+  return VC_OK;
+}
+static VcKgretArgs kgret_args(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, const uint32_t* d_new_ids, uint64_t* d_rows,
+                              uint32_t* d_counts) {
+  return VcKgretArgs{kgraph_args(e, k, mode, batch, 0, e->n, k_first, d_rows, d_counts), n_old, d_new_ids};
+}
+// the degenerate cases, which write nothing: K == n_old, K == 0 (n_old == 0 is one of the two)
+static bool kgret_nothing_to_do(uint64_t K, uint64_t n_old, vc_knn_graph_retain_stats* stats) {
+  if (stats) {
+    *stats = vc_knn_graph_retain_stats{};
+    stats->n_rows_kept = K;
+  }
+  return K == n_old || K == 0;
+}
 
 extern "C" {
 
@@ -1754,6 +1776,40 @@ int vc_knn_graph_update(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch,
                                       return store_call(e, s, [&](hipStream_t cs, std::string* cerr) {
                                         return vc_knn_graph_update_run(v, store_view(e, VC_MODE_LINEAR).knn,
                                                                        kgupd_args(e, k, mode, batch, n_old, k_first, d_rows, d_counts), st, cs, cerr);
+                                      });
+                                    },
+                                    [&](const uint64_t* codes, uint32_t nq, uint64_t* hrows, uint32_t* rcnt) {
+                                      return vc_search_knn(e, codes, nq, k + 1, VC_MODE_LINEAR, VC_ORDER_ASCENDING, hrows, rcnt, nullptr);
+                                    },
+                                    s, &err);
+  return driver_done(e, rc, err);
+}
+
+int vc_knn_graph_retain_dev(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, const uint32_t* d_new_ids, uint64_t* d_rows,
+                            uint32_t* d_counts, vc_knn_graph_retain_stats* stats, void* stream) {
+  const int rc = check_kgret_args(e, k, mode, n_old, k_first, d_new_ids, d_rows);
+  if (rc) return rc;
+  if (kgret_nothing_to_do(e->n, n_old, stats)) return VC_OK;
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_knn_graph_retain_run(store_view(e, mode), store_view(e, VC_MODE_LINEAR).knn, kgret_args(e, k, mode, batch, n_old, k_first, d_new_ids, d_rows, d_counts),
+                                   stats, s, err);
+  });
+}
+
+int vc_knn_graph_retain(vc_engine* e, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, const uint32_t* new_ids, uint64_t* rows,
+                        uint32_t* counts, vc_knn_graph_retain_stats* stats) {
+  int rc = check_kgret_args(e, k, mode, n_old, k_first, new_ids, rows);
+  if (rc) return rc;
+  if (kgret_nothing_to_do(e->n, n_old, stats)) return VC_OK;
+  if ((rc = bind_device(e))) return rc;
+  const VcStoreView v = store_view(e, mode);
+  hipStream_t s = e->stream;
+  std::string err;
+  rc = vc_knn_graph_retain_run_host(v, kgret_args(e, k, mode, batch, n_old, k_first, nullptr, nullptr, nullptr), new_ids, rows, counts, stats,
+                                    [&](const uint32_t* d_new_ids, uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_retain_stats* st) {
+                                      return store_call(e, s, [&](hipStream_t cs, std::string* cerr) {
+                                        return vc_knn_graph_retain_run(v, store_view(e, VC_MODE_LINEAR).knn,
+                                                                       kgret_args(e, k, mode, batch, n_old, k_first, d_new_ids, d_rows, d_counts), st, cs, cerr);
                                       });
                                     },
                                     [&](const uint64_t* codes, uint32_t nq, uint64_t* hrows, uint32_t* rcnt) {

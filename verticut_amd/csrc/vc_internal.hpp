@@ -232,6 +232,9 @@ enum VcScratch {
   // the graph's update (vc_knn_graph_update.hip): an old batch's arrays (VcKgupdWork); the new records' codes; a window's hit list;
   // the out-of-place rows of a merge launch; the host forms' staging
   VC_KGRAPH_UPD_WORK, VC_KGRAPH_UPD_NEW, VC_KGRAPH_UPD_HITS, VC_KGRAPH_UPD_ROWS, VC_KGRAPH_UPD_STAGE,
+  // the graph after a removal (vc_knn_graph_retain.hip): the flags, ranks and the short list (VcKgretWork); the out-of-place rows and
+  // counts of a chunk; the host forms' staging
+  VC_KGRAPH_RET_WORK, VC_KGRAPH_RET_ROWS, VC_KGRAPH_RET_STAGE,
   VC_SCRATCH_BUFS
 };
 // buffer `which` of the handle's table, at least `bytes` large, on the current device; null when it cannot be had (the handle keeps the text)
@@ -662,6 +665,8 @@ struct VcKgraphArgs {
   uint64_t* d_rows;                // [rows][k]
   uint32_t* d_counts;              // [rows], nullable
   uint64_t budget;                 // VcKnobs::kgraph_scratch
+  const uint32_t* d_id_list = nullptr;   // [rows] ascending global ids, device memory: the records to answer in place of the range (first is
+                                   // then ignored), and d_rows / d_counts are those of the WHOLE store: record id's row goes to row id - id_base
 };
 // the whole call on s with the device of the buffers current: under exact MIH one wait per round of a batch (4 bytes), one at the end
 // for the statistics when stats (host memory, nullable) is given.  linear_knn: the store's LINEAR k-NN, which answers the queries
@@ -697,6 +702,25 @@ int vc_knn_graph_update_run(const VcStoreView& v, const VcKnnSearch& linear_knn,
 // the pointers) on them, all N rows and counts home; waits for them.  host_knn as vc_knn_graph_run_host's.  counts, stats nullable
 int vc_knn_graph_update_run_host(const VcStoreView& v, const VcKgupdArgs& a, uint64_t* rows, uint32_t* counts, vc_knn_graph_update_stats* stats,
                                  const std::function<int(uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_update_stats* stats)>& run,
+                                 const std::function<int(const uint64_t* codes, uint32_t nq, uint64_t* rows, uint32_t* counts)>& host_knn, hipStream_t s,
+                                 std::string* err);
+// ---- vc_knn_graph_retain.hip: a built graph after vc_retain* (vc_knn_graph_retain*, vc_sharded_knn_graph_retain*).  One driver for both
+// handle kinds; the plan arithmetic -- the lane map, the chunks, the short rule, the scratch layout -- is vc_knn_graph_retain_plan.hpp.
+struct VcKgretArgs {
+  VcKgraphArgs repair;             // of the short rows' searches: its pointers those of the WHOLE buffers [n_old][k] / [n_old] (counts nullable);
+                                   // first, rows and d_id_list are set by the driver
+  uint64_t n_old;                  // checked by the caller: 0 < K = v.n < n_old
+  const uint32_t* d_new_ids;       // [n_old]: vc_retain*'s map
+};
+// the whole call on s with the device of the buffers current: one wait of 32 bytes for the short list's length, the error word
+// (VC_ERR_INVALID) and the tallies, then vc_knn_graph_run's waits over the short list
+int vc_knn_graph_retain_run(const VcStoreView& v, const VcKnnSearch& linear_knn, const VcKgretArgs& a, vc_knn_graph_retain_stats* stats, hipStream_t s,
+                            std::string* err);
+// either handle's host form (a's pointers are ignored): the old rows, counts and map staged up, `run` (the device form on s, which
+// sets the pointers) on them, the K rows and counts home; waits for them.  host_knn as vc_knn_graph_run_host's.  counts, stats nullable
+int vc_knn_graph_retain_run_host(const VcStoreView& v, const VcKgretArgs& a, const uint32_t* new_ids, uint64_t* rows, uint32_t* counts,
+                                 vc_knn_graph_retain_stats* stats,
+                                 const std::function<int(const uint32_t* d_new_ids, uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_retain_stats* stats)>& run,
                                  const std::function<int(const uint64_t* codes, uint32_t nq, uint64_t* rows, uint32_t* counts)>& host_knn, hipStream_t s,
                                  std::string* err);
 struct VcKgraphClusterArgs {

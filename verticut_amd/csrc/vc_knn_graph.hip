@@ -3,7 +3,8 @@
 // (vc_cluster_knn*, vc_sharded_cluster_knn*); the header states both contracts.  One driver each for both handle kinds over a
 // VcStoreView; the plan arithmetic is vc_knn_graph_plan.hpp.
 //   vc_kgraph_settle_kernel   one thread per output entry: the own record dropped by value, the verdict on the row, a settled row and
-//                             its count written through the index map, flag[row] = 1 for a query that goes to the next round
+//                             its count written through the index map, flag[row] = 1 for a query that goes to the next round; with
+//                             an id list in place of the range (vc_knn_graph_retain.hip) the own id and the row's place come from it
 //   vc_kgraph_gather_kernel   the retry list of a round: the exclusive scan of the flags (vc_sort.hip) places the flagged rows, so the
 //                             list is ascending and nothing depends on block order
 //   vc_kgraph_init_kernel     vc_cluster_knn: labels[i] = id_base + i, in_degree[i] = 0
@@ -35,6 +36,8 @@ struct SettleArgs {
   const uint32_t* map;       // [n] compact row -> the batch's query; null: first + row
   uint32_t first;
   uint32_t first_id;         // the global id of the batch's query 0: query oq is record first_id + oq
+  const uint32_t* ids;       // [nb] nullable: the batch comes from an id list; query oq is record ids[oq], and its row and count go
+  uint32_t id_base;          //   to place ids[oq] - id_base of out and counts, which are then those of the whole store
   uint64_t* out;             // [nb][k]
   uint32_t* counts;          // [nb], nullable
   uint32_t* flag;            // [n]
@@ -60,7 +63,8 @@ __global__ void __launch_bounds__(KG_BLK) vc_kgraph_settle_kernel(const SettleAr
     const uint64_t* row = a.rows + (uint64_t)r * a.kp;
     const uint32_t c = a.cnt[r], m = vc_kgraph_row_entries(c, a.kp);
     const uint32_t oq = a.map ? a.map[r] : a.first + r;
-    const uint64_t self = (uint64_t)(a.first_id + oq);
+    const uint32_t own = a.ids ? a.ids[oq] : a.first_id + oq;
+    const uint64_t self = (uint64_t)own, to = a.ids ? (uint64_t)(own - a.id_base) : (uint64_t)oq;
     const uint32_t lo = kg_lower_bound(row, m, self);
     const bool present = lo < m && row[lo] == self;
     uint32_t below = 0;
@@ -71,10 +75,10 @@ __global__ void __launch_bounds__(KG_BLK) vc_kgraph_settle_kernel(const SettleAr
       continue;
     }
     const uint32_t left = vc_kgraph_count(m, present, a.k);
-    a.out[(uint64_t)oq * a.k + j] = j < left ? row[j + (present && j >= lo ? 1u : 0u)] : VC_PACK_INF;   // (j < left: the index stays below m)
+    a.out[to * a.k + j] = j < left ? row[j + (present && j >= lo ? 1u : 0u)] : VC_PACK_INF;   // (j < left: the index stays below m)
     if (j == 0) {
       a.flag[r] = 0u;
-      if (a.counts) a.counts[oq] = verdict == VC_KGRAPH_PASSED ? 0xFFFFFFFFu : left;
+      if (a.counts) a.counts[to] = verdict == VC_KGRAPH_PASSED ? 0xFFFFFFFFu : left;
       if (verdict == VC_KGRAPH_PASSED) atomicAdd(a.tally, 1ull);
     }
   }
@@ -134,10 +138,12 @@ int vc_knn_graph_run(const VcStoreView& v, const VcKnnSearch& linear_knn, const 
   int rc;
   for (uint64_t pos = 0; pos < a.rows; pos += batch) {
     const uint32_t nb = (uint32_t)std::min<uint64_t>(batch, a.rows - pos), first_id = v.id_base + (uint32_t)(a.first + pos);
-    KG_HIP(vc_launch_cluster_init(d_ids, nb, first_id, s));
+    if (a.d_id_list) KG_HIP(hipMemcpyAsync(d_ids, a.d_id_list + pos, (size_t)nb * 4, hipMemcpyDeviceToDevice, s));
+    else KG_HIP(vc_launch_cluster_init(d_ids, nb, first_id, s));
     if ((rc = v.gather(d_ids, nb, d_q, d_found))) return rc;
-    uint64_t* out = a.d_rows + pos * k;
-    uint32_t* counts = a.d_counts ? a.d_counts + pos : nullptr;
+    // a range writes the batch's rows in order; an id list writes every row to its record's own place (the settle kernel)
+    uint64_t* out = a.d_id_list ? a.d_rows : a.d_rows + pos * k;
+    uint32_t* counts = !a.d_counts ? nullptr : a.d_id_list ? a.d_counts : a.d_counts + pos;
     // one round over the list (q, map, n) at kp through `search`
     auto round = [&](const VcKnnSearch& search, const uint64_t* q, const uint32_t* map, uint32_t n, uint32_t kp, bool tie_cut) -> int {
       const uint32_t sub = vc_kgraph_sub_batch(a.budget, kp);
@@ -150,6 +156,7 @@ int vc_knn_graph_run(const VcStoreView& v, const VcKnnSearch& linear_knn, const 
         SettleArgs c{};
         c.rows = rows; c.cnt = cnt; c.n = ns; c.kp = kp; c.k = k; c.tie_cut = tie_cut ? 1u : 0u;
         c.map = map ? map + first : nullptr; c.first = first; c.first_id = first_id;
+        c.ids = a.d_id_list ? d_ids : nullptr; c.id_base = v.id_base;
         c.out = out; c.counts = counts; c.flag = flag + first; c.tally = tally;
         KG_HIP(launch_settle(c, s));
       }

@@ -2716,6 +2716,27 @@ static VcKgupdArgs sharded_kgupd_args(vc_sharded* h, uint32_t k, uint32_t mode, 
                                          d_counts ? d_counts + n_old : nullptr),
                      n_old, d_rows, d_counts, h->knobs.kgraph_scratch, vc_kgupd_old_batch(h->knobs.kgraph_old_batch), vc_kgupd_window(h->knobs.kgraph_window)};
 }
+// a built graph after vc_sharded_retain* (vc_knn_graph_retain.hip): the graph call's checks over the store as it is now
+static int check_sharded_kgret_args(vc_sharded* h, uint32_t k, uint32_t mode, uint64_t n_old, uint32_t k_first, const uint32_t* new_ids, const uint64_t* rows) {
+  uint64_t n_rows = 0;
+  if (!h || !rows || !new_ids) return VC_ERR_INVALID;
+  const int rc = check_sharded_kgraph_args(h, k, mode, 0, 0, k_first, rows, &n_rows);
+  if (rc) return rc;
+  if (n_old < h->n)
+    return sfail(h, VC_ERR_INVALID, "k-NN graph retain: n_old %llu is below the %llu resident records", (unsigned long long)n_old, (unsigned long long)h->n);
+  return VC_OK;
+}
+static VcKgretArgs sharded_kgret_args(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, const uint32_t* d_new_ids,
+                                      uint64_t* d_rows, uint32_t* d_counts) {
+  return VcKgretArgs{sharded_kgraph_args(h, k, mode, batch, 0, h->n, k_first, d_rows, d_counts), n_old, d_new_ids};
+}
+static bool sharded_kgret_nothing_to_do(uint64_t K, uint64_t n_old, vc_knn_graph_retain_stats* stats) {
+  if (stats) {
+    *stats = vc_knn_graph_retain_stats{};
+    stats->n_rows_kept = K;
+  }
+  return K == n_old || K == 0;
+}
 
 extern "C" {
 
@@ -2778,6 +2799,39 @@ int vc_sharded_knn_graph_update(vc_sharded* h, uint32_t k, uint32_t mode, uint32
                                         [&](uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_update_stats* st) {
                                           return vc_knn_graph_update_run(v, sharded_store_view(h, VC_MODE_LINEAR, S).knn,
                                                                          sharded_kgupd_args(h, k, mode, batch, n_old, k_first, d_rows, d_counts), st, S, err);
+                                        },
+                                        [&](const uint64_t* codes, uint32_t nq, uint64_t* hrows, uint32_t* rcnt) {   // (its shards recover on the host)
+                                          const int r = vc_sharded_search_knn(h, codes, nq, k + 1, VC_MODE_LINEAR, VC_ORDER_ASCENDING, hrows, rcnt, nullptr);
+                                          if (r) return r;
+                                          VS_HIP(h, hipSetDevice(h->root));
+                                          return (int)VC_OK;
+                                        },
+                                        S, err);
+  });
+}
+
+int vc_sharded_knn_graph_retain_dev(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, const uint32_t* d_new_ids,
+                                    uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_retain_stats* stats, void* stream) {
+  const int rc = check_sharded_kgret_args(h, k, mode, n_old, k_first, d_new_ids, d_rows);
+  if (rc) return rc;
+  if (sharded_kgret_nothing_to_do(h->n, n_old, stats)) return VC_OK;
+  return sharded_store_call(h, mode, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_knn_graph_retain_run(v, sharded_store_view(h, VC_MODE_LINEAR, S).knn, sharded_kgret_args(h, k, mode, batch, n_old, k_first, d_new_ids, d_rows, d_counts),
+                                   stats, S, err);
+  });
+}
+
+int vc_sharded_knn_graph_retain(vc_sharded* h, uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, const uint32_t* new_ids, uint64_t* rows,
+                                uint32_t* counts, vc_knn_graph_retain_stats* stats) {
+  const int rc = check_sharded_kgret_args(h, k, mode, n_old, k_first, new_ids, rows);
+  if (rc) return rc;
+  if (sharded_kgret_nothing_to_do(h->n, n_old, stats)) return VC_OK;
+  return sharded_store_call(h, mode, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_knn_graph_retain_run_host(v, sharded_kgret_args(h, k, mode, batch, n_old, k_first, nullptr, nullptr, nullptr), new_ids, rows, counts, stats,
+                                        [&](const uint32_t* d_new_ids, uint64_t* d_rows, uint32_t* d_counts, vc_knn_graph_retain_stats* st) {
+                                          return vc_knn_graph_retain_run(v, sharded_store_view(h, VC_MODE_LINEAR, S).knn,
+                                                                         sharded_kgret_args(h, k, mode, batch, n_old, k_first, d_new_ids, d_rows, d_counts), st, S,
+                                                                         err);
                                         },
                                         [&](const uint64_t* codes, uint32_t nq, uint64_t* hrows, uint32_t* rcnt) {   // (its shards recover on the host)
                                           const int r = vc_sharded_search_knn(h, codes, nq, k + 1, VC_MODE_LINEAR, VC_ORDER_ASCENDING, hrows, rcnt, nullptr);

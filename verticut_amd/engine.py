@@ -58,6 +58,7 @@ EXPORTS = [
     "vc_knn_graph", "vc_knn_graph_dev", "vc_sharded_knn_graph", "vc_sharded_knn_graph_dev",
     "vc_cluster_knn", "vc_cluster_knn_dev", "vc_sharded_cluster_knn", "vc_sharded_cluster_knn_dev",
     "vc_knn_graph_update", "vc_knn_graph_update_dev", "vc_sharded_knn_graph_update", "vc_sharded_knn_graph_update_dev",
+    "vc_knn_graph_retain", "vc_knn_graph_retain_dev", "vc_sharded_knn_graph_retain", "vc_sharded_knn_graph_retain_dev",
 ]
 KNN_MUTUAL, KNN_EITHER = 0, 1   # VC_KNN_*: cluster_knn joins i and j iff each lists the other / iff one lists the other
 FILTER_MASK, FILTER_ROOTS, FILTER_EQUAL, FILTER_NOT_EQUAL, FILTER_BITS = 0, 1, 2, 3, 4   # VC_FILTER_*: how search_knn_filtered reads `sel`
@@ -180,6 +181,15 @@ class VcKnnGraphUpdateStats(C.Structure):
     def as_dict(self):
         """{build: VcKnnGraphStats' dict, n_rows_changed, n_inserted, n_hits, n_windows, n_halvings: int}"""
         return {name: getattr(self, name).as_dict() if name == "build" else int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class VcKnnGraphRetainStats(C.Structure):
+    _fields_ = [("repair", VcKnnGraphStats), ("n_rows_kept", C.c_uint64), ("n_rows_short", C.c_uint64), ("n_entries_dropped", C.c_uint64),
+                ("pad", C.c_uint64)]
+
+    def as_dict(self):
+        """{repair: VcKnnGraphStats' dict, n_rows_kept, n_rows_short, n_entries_dropped: int}"""
+        return {name: getattr(self, name).as_dict() if name == "repair" else int(getattr(self, name)) for name, _ in self._fields_ if name != "pad"}
 
 
 class VcClusterKnnStats(C.Structure):
@@ -357,6 +367,10 @@ def load_library():
     L.vc_knn_graph_update_dev.argtypes = [vp, u32, u32, u32, u64, u32, vp, vp, vp, vp]
     L.vc_sharded_knn_graph_update.argtypes = [vp, u32, u32, u32, u64, u32, vp, vp, vp]
     L.vc_sharded_knn_graph_update_dev.argtypes = [vp, u32, u32, u32, u64, u32, vp, vp, vp, vp]
+    L.vc_knn_graph_retain.argtypes = [vp, u32, u32, u32, u64, u32, vp, vp, vp, vp]
+    L.vc_knn_graph_retain_dev.argtypes = [vp, u32, u32, u32, u64, u32, vp, vp, vp, vp, vp]
+    L.vc_sharded_knn_graph_retain.argtypes = [vp, u32, u32, u32, u64, u32, vp, vp, vp, vp]
+    L.vc_sharded_knn_graph_retain_dev.argtypes = [vp, u32, u32, u32, u64, u32, vp, vp, vp, vp, vp]
     L.vc_cluster_knn.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]
     L.vc_cluster_knn_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]
     L.vc_sharded_cluster_knn.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]
@@ -713,6 +727,33 @@ def _knn_graph_update(self, fn, rows, counts, k, mode, batch, k_first, with_stat
 def _knn_graph_update_dev(self, fn, k, n_old, d_rows, d_counts, mode, batch, k_first, with_stats, stream):
     st = VcKnnGraphUpdateStats()
     self._check(fn(self._h, k, mode, batch, n_old, k_first, d_rows, d_counts, C.byref(st) if with_stats else None, stream))
+    return st.as_dict() if with_stats else None
+
+
+def _knn_graph_retain(self, fn, rows, new_ids, counts, mode, batch, k_first, with_stats):
+    """shared by Engine.knn_graph_retain and ShardedEngine.knn_graph_retain: (rows uint64 [K, k], counts uint32 [K] | None[, stats dict])"""
+    n = len(self)
+    out = np.array(rows, dtype=np.uint64, order="C")            # a copy: the call works in place
+    new_ids = np.ascontiguousarray(new_ids, dtype=np.uint32).reshape(-1)
+    if out.ndim != 2 or out.shape[0] < n or out.shape[1] == 0 or new_ids.shape[0] != out.shape[0]:
+        raise VcError(VC_ERR_INVALID, "rows must be the [n_old, k] graph of knn_graph over the store before retain, new_ids the map retain returned")
+    n_old, k = out.shape
+    cnt = None
+    if counts is not None:
+        cnt = np.array(counts, dtype=np.uint32).reshape(-1)
+        if cnt.shape[0] != n_old:
+            raise VcError(VC_ERR_INVALID, "counts must have one word per old row")
+    if n_old == 0:
+        out, new_ids = np.empty((1, k), dtype=np.uint64), np.zeros(1, dtype=np.uint32)   # (the call writes no word, but takes no null pointer)
+    st = VcKnnGraphRetainStats()
+    self._check(fn(self._h, k, mode, batch, n_old, k_first, _p(new_ids), _p(out), _p(cnt) if cnt is not None and n_old else None, C.byref(st)))
+    out, cnt = out[:n], cnt[:n] if cnt is not None else None
+    return (out, cnt, st.as_dict()) if with_stats else (out, cnt)
+
+
+def _knn_graph_retain_dev(self, fn, k, n_old, d_new_ids, d_rows, d_counts, mode, batch, k_first, with_stats, stream):
+    st = VcKnnGraphRetainStats()
+    self._check(fn(self._h, k, mode, batch, n_old, k_first, d_new_ids, d_rows, d_counts, C.byref(st) if with_stats else None, stream))
     return st.as_dict() if with_stats else None
 
 
@@ -1180,6 +1221,17 @@ class Engine:
         N uint32 or None); results valid in `stream` order.  Returns the stats dict (or None)."""
         return _knn_graph_update_dev(self, self._L.vc_knn_graph_update_dev, k, n_old, d_rows, d_counts, mode, batch, k_first, with_stats, stream)
 
+    def knn_graph_retain(self, rows, new_ids, counts=None, mode=MODE_LINEAR, batch=0, k_first=0, with_stats=False):
+        """vc_knn_graph_retain: the graph after a removal.  rows [n_old, k] (and counts [n_old] or None) are knn_graph's over the store
+        before retain(), new_ids the map retain() returned; returns the rows [K, k] and counts [K] (None without counts) of knn_graph
+        over the store now, the same words.  Only the rows that lost too many entries are searched again."""
+        return _knn_graph_retain(self, self._L.vc_knn_graph_retain, rows, new_ids, counts, mode, batch, k_first, with_stats)
+
+    def knn_graph_retain_dev(self, k, n_old, d_new_ids, d_rows, d_counts=None, mode=MODE_MIH_EXACT, batch=0, k_first=0, with_stats=True, stream=None):
+        """vc_knn_graph_retain_dev: raw device addresses (d_new_ids n_old uint32 as retain_dev wrote it, d_rows n_old * k uint64 and
+        d_counts n_old uint32 or None, the graph as it was); results valid in `stream` order.  Returns the stats dict (or None)."""
+        return _knn_graph_retain_dev(self, self._L.vc_knn_graph_retain_dev, k, n_old, d_new_ids, d_rows, d_counts, mode, batch, k_first, with_stats, stream)
+
     def cluster_knn(self, rows, counts, kk, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, with_in_degree=True):
         """vc_cluster_knn: components and in-degrees of a graph knn_graph built over the whole store (rows [N, k], counts [N] or None).
         Row i lists j iff j is among its first kk entries at a distance <= max_dist; KNN_MUTUAL joins i and j iff each lists the other,
@@ -1552,6 +1604,17 @@ class ShardedEngine:
         """vc_sharded_knn_graph_update_dev: raw device addresses on the root device (d_rows N * k uint64 whose first n_old rows are the
         graph as it was, d_counts N uint32 or None); results valid in `stream` order.  Returns the stats dict (or None)."""
         return _knn_graph_update_dev(self, self._L.vc_sharded_knn_graph_update_dev, k, n_old, d_rows, d_counts, mode, batch, k_first, with_stats, stream)
+
+    def knn_graph_retain(self, rows, new_ids, counts=None, mode=MODE_LINEAR, batch=0, k_first=0, with_stats=False):
+        """vc_sharded_knn_graph_retain: the graph after a removal.  rows [n_old, k] (and counts [n_old] or None) are knn_graph's over the store
+        before retain(), new_ids the map retain() returned; returns the rows [K, k] and counts [K] (None without counts) of knn_graph
+        over the store now, the same words.  Only the rows that lost too many entries are searched again."""
+        return _knn_graph_retain(self, self._L.vc_sharded_knn_graph_retain, rows, new_ids, counts, mode, batch, k_first, with_stats)
+
+    def knn_graph_retain_dev(self, k, n_old, d_new_ids, d_rows, d_counts=None, mode=MODE_MIH_EXACT, batch=0, k_first=0, with_stats=True, stream=None):
+        """vc_sharded_knn_graph_retain_dev: raw device addresses on the root device (d_new_ids n_old uint32 as retain_dev wrote it, d_rows n_old * k uint64 and
+        d_counts n_old uint32 or None, the graph as it was); results valid in `stream` order.  Returns the stats dict (or None)."""
+        return _knn_graph_retain_dev(self, self._L.vc_sharded_knn_graph_retain_dev, k, n_old, d_new_ids, d_rows, d_counts, mode, batch, k_first, with_stats, stream)
 
     def cluster_knn(self, rows, counts, kk, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, with_in_degree=True):
         """vc_sharded_cluster_knn: components and in-degrees of a graph knn_graph built over the whole store (rows [N, k], counts [N] or None).

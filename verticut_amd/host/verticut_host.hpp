@@ -175,6 +175,11 @@ class Backend {
   // knn_graph's over the store now, the same words.  In VC_MODE_MIH_EXACT the index must be current (update_index)
   virtual int knn_graph_update(uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, uint64_t* rows, uint32_t* counts,
                                vc_knn_graph_update_stats* stats) = 0;
+  // that graph after retain (vc_knn_graph_retain / vc_sharded_knn_graph_retain): rows [n_old][k] and counts (nullable) are knn_graph's
+  // over the store before retain, new_ids the map retain wrote; afterwards the first K rows are knn_graph's over the store now, the same
+  // words.  Only rows that lost too many entries are searched again
+  virtual int knn_graph_retain(uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, const uint32_t* new_ids, uint64_t* rows,
+                               uint32_t* counts, vc_knn_graph_retain_stats* stats) = 0;
   // components and in-degrees of that graph over the whole store (vc_cluster_knn / vc_sharded_cluster_knn): an edge is one of a row's
   // first kk entries at a distance <= max_dist; VC_KNN_MUTUAL joins two records iff each lists the other, VC_KNN_EITHER iff one does;
   // labels[i] = the smallest id of the component; counts, in_degree and stats may be null
@@ -281,6 +286,10 @@ class Engine : public Backend {
   int knn_graph_update(uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, uint64_t* rows, uint32_t* counts,
                        vc_knn_graph_update_stats* stats) override {
     return vc_knn_graph_update(h_, k, mode, batch, n_old, k_first, rows, counts, stats);
+  }
+  int knn_graph_retain(uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, const uint32_t* new_ids, uint64_t* rows, uint32_t* counts,
+                       vc_knn_graph_retain_stats* stats) override {
+    return vc_knn_graph_retain(h_, k, mode, batch, n_old, k_first, new_ids, rows, counts, stats);
   }
   int cluster_knn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t* labels,
                   uint32_t* in_degree, vc_cluster_knn_stats* stats) override {
@@ -414,6 +423,10 @@ class ShardedEngine : public Backend {
   int knn_graph_update(uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, uint64_t* rows, uint32_t* counts,
                        vc_knn_graph_update_stats* stats) override {
     return vc_sharded_knn_graph_update(h_, k, mode, batch, n_old, k_first, rows, counts, stats);
+  }
+  int knn_graph_retain(uint32_t k, uint32_t mode, uint32_t batch, uint64_t n_old, uint32_t k_first, const uint32_t* new_ids, uint64_t* rows, uint32_t* counts,
+                       vc_knn_graph_retain_stats* stats) override {
+    return vc_sharded_knn_graph_retain(h_, k, mode, batch, n_old, k_first, new_ids, rows, counts, stats);
   }
   int cluster_knn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t* labels,
                   uint32_t* in_degree, vc_cluster_knn_stats* stats) override {
