@@ -1192,6 +1192,60 @@ int vc_cluster_knn_dev(vc_engine* e, const uint64_t* d_rows, const uint32_t* d_c
 int vc_cluster_knn(vc_engine* e, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags,
                    uint32_t max_dist, uint32_t* labels, uint32_t* in_degree, vc_cluster_knn_stats* stats);
 
+/* ---- shared-nearest-neighbour clusters of the k-NN graph: vc_cluster_snn* -----------------------------------------------------------------
+ * vc_cluster_knn* judges an edge by rank alone: on data with noise between the groups one stray mutual pair welds two groups
+ * together.  Shared-nearest-neighbour clustering (Jarvis and Patrick, 1973) joins i and j only if their neighbour lists overlap in
+ * at least min_shared records; the overlap counts themselves are the edge weights of community detection and of Jaccard-weighted
+ * graph pipelines, and their histogram is what one reads min_shared from.  Nothing is searched and the store is touched only for N
+ * and id_base.  The reference has no such call.
+ * PRECONDITION AND "LISTS": exactly vc_cluster_knn*'s.  d_rows (N * k) and d_counts (N, may be NULL: every row then holds
+ * min(k, N - 1) entries) are what vc_knn_graph* wrote over the full range with this k.  Row i LISTS j iff j is among the first
+ * min(kk, count_i) entries of row i and dist(i, j) <= max_dist.  S_i is the set of records row i lists; the record itself is never
+ * in its own set.  kk lies in 1 .. min(k, VC_SNN_MAX_KK).  flags is VC_KNN_MUTUAL or VC_KNN_EITHER and decides which pairs are
+ * CANDIDATES: each lists the other / one lists the other.
+ * OUTPUTS.  shared(i, j) = |S_i n S_j|, symmetric, in 0 .. kk - 1.
+ *   d_shared (N * kk words, stride kk, may be NULL): word i * kk + jj is shared(i, j) when entry jj of row i is listed, VC_SNN_NONE
+ *     otherwise.  Every word is written.
+ *   d_hist (kk words of uint64_t, may be NULL): hist[s] = the listed (directed) entries with shared == s; it sums to n_edges.
+ *   d_labels (N words, required): the components of the graph in which i and j are joined iff they are a candidate pair AND
+ *     shared(i, j) >= min_shared; labels[i] is the smallest global id of the component, as vc_cluster_knn*, and feeds
+ *     vc_group_summary*, vc_retain*(VC_RETAIN_ROOTS) and the distinct, filtered and scoped searches unchanged.
+ *   stats (HOST memory in both forms, may be NULL): n_edges and n_mutual as vc_cluster_knn*; n_joined the unordered candidate pairs
+ *     with shared >= min_shared, each counted once -- a mutual pair from its smaller member, a one-sided pair (VC_KNN_EITHER) from
+ *     the row that lists it; n_clusters; max_shared over the listed entries, 0 if none.
+ * min_shared == 0 gives vc_cluster_knn*'s labels, n_edges, n_mutual and n_clusters bit for bit; min_shared >= kk joins nothing.
+ * Every output word is a function of the graph and the call, not of lane order, block order or the hash function used.
+ * HOW.  One team of lanes per row -- a wave up to kk = 128, a block above -- puts S_i into an open-addressing set in LDS, at most
+ * half full, then for each listed entry (d, j) strides over row j's first min(kk, count_j) entries with coalesced loads, tests the
+ * cap and probes the set; a ballot's popcount is shared(i, j).  "j lists i" stays vc_cluster_knn*'s one compare.  The weights'
+ * histogram is summed per block in LDS; the unions go into the lock-free forest of vc_cluster_radius*; then the flatten-and-count pass.
+ * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle, rows or labels, k outside 1 .. VC_MAX_K - 1,
+ * kk outside 1 .. min(k, VC_SNN_MAX_KK), unknown flags.  Found ON THE DEVICE, VC_ERR_INVALID through vc_cluster_knn*'s protocol (the
+ * error word comes home with the stats; THE OUTPUTS ARE THEN UNDEFINED, but nothing is read or written out of bounds): a count above
+ * k, an entry whose id is outside the store, an entry whose id equals the row's own.  A row that lists one id twice is not a
+ * vc_knn_graph* row: the result is then unspecified, but the call terminates and stays in bounds.
+ * N == 0 gives VC_OK and zero stats; N == 1 gives the record its own label and all of d_shared VC_SNN_NONE.  WAITS: one, at the end.
+ * Over a sharded store every pointer of the device form lives on the ROOT device and no shard is touched.
+ * NOT OFFERED: closed neighbour sets (the record counted in its own set); a Jaccard threshold, which the caller derives from d_shared
+ * and the counts; kk above 1024. */
+#define VC_SNN_MAX_KK 1024u
+#define VC_SNN_NONE   0xFFFFFFFFu
+typedef struct vc_cluster_snn_stats {   /* 40 bytes */
+  uint64_t n_edges;      /* listed entries (directed), as vc_cluster_knn* */
+  uint64_t n_mutual;     /* unordered pairs that list each other, as vc_cluster_knn* */
+  uint64_t n_joined;     /* unordered candidate pairs with shared >= min_shared, each counted once */
+  uint64_t n_clusters;
+  uint32_t max_shared;   /* over the listed entries; 0 if none */
+  uint32_t pad;
+} vc_cluster_snn_stats;
+int vc_cluster_snn_dev(vc_engine* e, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags,
+                       uint32_t max_dist, uint32_t min_shared, uint32_t* d_labels, uint32_t* d_shared, uint64_t* d_hist,
+                       vc_cluster_snn_stats* stats, void* stream);
+/* The same for host pointers: rows and counts are staged ON EVERY CALL; labels, weights and histogram come home; waits for them. */
+int vc_cluster_snn(vc_engine* e, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags,
+                   uint32_t max_dist, uint32_t min_shared, uint32_t* labels, uint32_t* shared, uint64_t* hist,
+                   vc_cluster_snn_stats* stats);
+
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
  * seconds); the affected queries kept d_counts[i] == UINT32_MAX.  0 in normal operation.  Synchronises the stream.
@@ -1490,6 +1544,14 @@ int vc_sharded_cluster_knn_dev(vc_sharded* h, const uint64_t* d_rows, const uint
                                uint32_t max_dist, uint32_t* d_labels, uint32_t* d_in_degree, vc_cluster_knn_stats* stats, void* stream);
 int vc_sharded_cluster_knn(vc_sharded* h, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags,
                            uint32_t max_dist, uint32_t* labels, uint32_t* in_degree, vc_cluster_knn_stats* stats);
+/* Shared-nearest-neighbour clusters of that graph: as vc_cluster_snn_dev / vc_cluster_snn; every pointer of the device form lives
+ * on the ROOT device, no shard is touched. */
+int vc_sharded_cluster_snn_dev(vc_sharded* h, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags,
+                               uint32_t max_dist, uint32_t min_shared, uint32_t* d_labels, uint32_t* d_shared, uint64_t* d_hist,
+                               vc_cluster_snn_stats* stats, void* stream);
+int vc_sharded_cluster_snn(vc_sharded* h, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags,
+                           uint32_t max_dist, uint32_t min_shared, uint32_t* labels, uint32_t* shared, uint64_t* hist,
+                           vc_cluster_snn_stats* stats);
 
 /* Stream of the host-pointer calls (default VC_STREAM_OWN). */
 int vc_set_stream(vc_engine* e, void* stream);

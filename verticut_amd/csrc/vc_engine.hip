@@ -16,6 +16,7 @@
 #include "vc_groups_plan.hpp"
 #include "vc_internal.hpp"
 #include "vc_knn_graph_plan.hpp"
+#include "vc_snn_plan.hpp"
 #include "vc_knn_graph_update_plan.hpp"
 #include "vc_mih.hpp"
 #include "vc_retain.hpp"
@@ -1674,6 +1675,13 @@ static int check_cluster_knn_args(vc_engine* e, const uint64_t* rows, uint32_t k
   if (flags & ~VC_KNN_EITHER) return fail(e, VC_ERR_INVALID, "k-NN clusters: unknown flags 0x%x", flags);
   return VC_OK;
 }
+static int check_cluster_snn_args(vc_engine* e, const uint64_t* rows, uint32_t k, uint32_t kk, uint32_t flags, const uint32_t* labels) {
+  if (!e || !rows || !labels) return VC_ERR_INVALID;
+  if (!vc_kgraph_k_ok(k)) return fail(e, VC_ERR_INVALID, "SNN clusters: k must be in 1..%u", VC_MAX_K - 1);
+  if (!vc_snn_kk_ok(k, kk)) return fail(e, VC_ERR_INVALID, "SNN clusters: kk must be in 1..min(k, %u)", VC_SNN_MAX_KK);
+  if (!vc_snn_flags_ok(flags)) return fail(e, VC_ERR_INVALID, "SNN clusters: unknown flags 0x%x", flags);
+  return VC_OK;
+}
 // a built graph after vc_add_codes (vc_knn_graph_update.hip): vc_knn_graph*'s checks with n_old as the first position
 static int check_kgupd_args(vc_engine* e, uint32_t k, uint32_t mode, uint64_t n_old, uint32_t k_first, const uint64_t* rows) {
   uint64_t n_rows = 0;
@@ -1839,6 +1847,30 @@ int vc_cluster_knn(vc_engine* e, const uint64_t* rows, const uint32_t* counts, u
   return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
     return vc_cluster_knn_run_host(store_view(e, VC_MODE_LINEAR), VcKgraphClusterArgs{nullptr, nullptr, k, kk, flags, max_dist, nullptr, nullptr}, rows, counts,
                                    labels, in_degree, stats, s, err);
+  });
+}
+
+int vc_cluster_snn_dev(vc_engine* e, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist,
+                       uint32_t min_shared, uint32_t* d_labels, uint32_t* d_shared, uint64_t* d_hist, vc_cluster_snn_stats* stats, void* stream) {
+  const int rc = check_cluster_snn_args(e, d_rows, k, kk, flags, d_labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_cluster_snn_stats{};
+  if (e->n == 0) return VC_OK;
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_cluster_snn_run(store_view(e, VC_MODE_LINEAR), VcSnnArgs{d_rows, d_counts, k, kk, flags, max_dist, min_shared, d_labels, d_shared, d_hist}, stats, s,
+                              err);
+  });
+}
+
+int vc_cluster_snn(vc_engine* e, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t min_shared,
+                   uint32_t* labels, uint32_t* shared, uint64_t* hist, vc_cluster_snn_stats* stats) {
+  const int rc = check_cluster_snn_args(e, rows, k, kk, flags, labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_cluster_snn_stats{};
+  if (e->n == 0) return VC_OK;
+  return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_cluster_snn_run_host(store_view(e, VC_MODE_LINEAR), VcSnnArgs{nullptr, nullptr, k, kk, flags, max_dist, min_shared, nullptr, nullptr, nullptr}, rows,
+                                   counts, labels, shared, hist, stats, s, err);
   });
 }
 

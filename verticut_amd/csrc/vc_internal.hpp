@@ -235,6 +235,8 @@ enum VcScratch {
   // the graph after a removal (vc_knn_graph_retain.hip): the flags, ranks and the short list (VcKgretWork); the out-of-place rows and
   // counts of a chunk; the host forms' staging
   VC_KGRAPH_RET_WORK, VC_KGRAPH_RET_ROWS, VC_KGRAPH_RET_STAGE,
+  // shared-nearest-neighbour clusters (vc_snn.hip): the statistics block; the host forms' staging (VcSnnStage) and their labels
+  VC_SNN_STAT, VC_SNN_STAGE, VC_SNN_HLAB,
   VC_SCRATCH_BUFS
 };
 // buffer `which` of the handle's table, at least `bytes` large, on the current device; null when it cannot be had (the handle keeps the text)
@@ -736,6 +738,23 @@ int vc_cluster_knn_run(const VcStoreView& v, const VcKgraphClusterArgs& a, vc_cl
 // the same for host pointers (a's pointers are ignored): rows and counts staged, labels and in-degrees (nullable) come home, waited for
 int vc_cluster_knn_run_host(const VcStoreView& v, VcKgraphClusterArgs a, const uint64_t* rows, const uint32_t* counts, uint32_t* labels, uint32_t* in_degree,
                             vc_cluster_knn_stats* stats, hipStream_t s, std::string* err);
+// ---- vc_snn.hip: shared-nearest-neighbour clusters of a built graph (vc_cluster_snn*, vc_sharded_cluster_snn*).  One driver for both
+// handle kinds; the plan arithmetic -- the argument checks, the set's size, the team shapes, the staging layout -- is vc_snn_plan.hpp.
+struct VcSnnArgs {
+  const uint64_t* d_rows;          // [n][k]: vc_knn_graph*'s rows over the whole store
+  const uint32_t* d_counts;        // [n], nullable: then every row holds vc_kgraph_row_count(n, k) entries
+  uint32_t k, kk, flags, max_dist; // checked by the caller: vc_kgraph_k_ok, vc_snn_kk_ok, vc_snn_flags_ok
+  uint32_t min_shared;
+  uint32_t* d_labels;              // [n]
+  uint32_t* d_shared;              // [n][kk], nullable
+  uint64_t* d_hist;                // [kk], nullable
+};
+// the whole call on s, v.n > 0: the memsets, init, the intersection launch, flatten, then the one wait for the statistics and the
+// error word (VC_ERR_INVALID: a count above k, an id outside the store, a row's own id).  Only n, id_base and alloc of the view are used
+int vc_cluster_snn_run(const VcStoreView& v, const VcSnnArgs& a, vc_cluster_snn_stats* stats, hipStream_t s, std::string* err);
+// the same for host pointers (a's pointers are ignored): rows and counts staged; labels, weights and histogram (both nullable) come home, waited for
+int vc_cluster_snn_run_host(const VcStoreView& v, VcSnnArgs a, const uint64_t* rows, const uint32_t* counts, uint32_t* labels, uint32_t* shared, uint64_t* hist,
+                            vc_cluster_snn_stats* stats, hipStream_t s, std::string* err);
 // ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
 struct VcKeepSet;
 #define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)

@@ -41,6 +41,7 @@
 #include "vc_filter_plan.hpp"
 #include "vc_internal.hpp"
 #include "vc_knn_graph_plan.hpp"
+#include "vc_snn_plan.hpp"
 #include "vc_knn_graph_update_plan.hpp"
 #include "vc_mih.hpp"
 #include "vc_seed_plan.hpp"
@@ -2702,6 +2703,13 @@ static int check_sharded_cluster_knn_args(vc_sharded* h, const uint64_t* rows, u
   if (flags & ~VC_KNN_EITHER) return sfail(h, VC_ERR_INVALID, "k-NN clusters: unknown flags 0x%x", flags);
   return VC_OK;
 }
+static int check_sharded_cluster_snn_args(vc_sharded* h, const uint64_t* rows, uint32_t k, uint32_t kk, uint32_t flags, const uint32_t* labels) {
+  if (!h || !rows || !labels) return VC_ERR_INVALID;
+  if (!vc_kgraph_k_ok(k)) return sfail(h, VC_ERR_INVALID, "SNN clusters: k must be in 1..%u", VC_MAX_K - 1);
+  if (!vc_snn_kk_ok(k, kk)) return sfail(h, VC_ERR_INVALID, "SNN clusters: kk must be in 1..min(k, %u)", VC_SNN_MAX_KK);
+  if (!vc_snn_flags_ok(flags)) return sfail(h, VC_ERR_INVALID, "SNN clusters: unknown flags 0x%x", flags);
+  return VC_OK;
+}
 // a built graph after vc_sharded_add_codes (vc_knn_graph_update.hip): the graph call's checks with n_old as the first position
 static int check_sharded_kgupd_args(vc_sharded* h, uint32_t k, uint32_t mode, uint64_t n_old, uint32_t k_first, const uint64_t* rows) {
   uint64_t n_rows = 0;
@@ -2863,6 +2871,29 @@ int vc_sharded_cluster_knn(vc_sharded* h, const uint64_t* rows, const uint32_t* 
   return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_cluster_knn_run_host(v, VcKgraphClusterArgs{nullptr, nullptr, k, kk, flags, max_dist, nullptr, nullptr}, rows, counts, labels, in_degree, stats, S,
                                    err);
+  });
+}
+
+int vc_sharded_cluster_snn_dev(vc_sharded* h, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist,
+                               uint32_t min_shared, uint32_t* d_labels, uint32_t* d_shared, uint64_t* d_hist, vc_cluster_snn_stats* stats, void* stream) {
+  const int rc = check_sharded_cluster_snn_args(h, d_rows, k, kk, flags, d_labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_cluster_snn_stats{};
+  if (h->n == 0) return VC_OK;
+  return sharded_store_call(h, VC_MODE_LINEAR, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_cluster_snn_run(v, VcSnnArgs{d_rows, d_counts, k, kk, flags, max_dist, min_shared, d_labels, d_shared, d_hist}, stats, S, err);
+  });
+}
+
+int vc_sharded_cluster_snn(vc_sharded* h, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist,
+                           uint32_t min_shared, uint32_t* labels, uint32_t* shared, uint64_t* hist, vc_cluster_snn_stats* stats) {
+  const int rc = check_sharded_cluster_snn_args(h, rows, k, kk, flags, labels);
+  if (rc) return rc;
+  if (stats) *stats = vc_cluster_snn_stats{};
+  if (h->n == 0) return VC_OK;
+  return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_cluster_snn_run_host(v, VcSnnArgs{nullptr, nullptr, k, kk, flags, max_dist, min_shared, nullptr, nullptr, nullptr}, rows, counts, labels, shared, hist,
+                                   stats, S, err);
   });
 }
 

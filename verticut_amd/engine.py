@@ -59,8 +59,10 @@ EXPORTS = [
     "vc_cluster_knn", "vc_cluster_knn_dev", "vc_sharded_cluster_knn", "vc_sharded_cluster_knn_dev",
     "vc_knn_graph_update", "vc_knn_graph_update_dev", "vc_sharded_knn_graph_update", "vc_sharded_knn_graph_update_dev",
     "vc_knn_graph_retain", "vc_knn_graph_retain_dev", "vc_sharded_knn_graph_retain", "vc_sharded_knn_graph_retain_dev",
+    "vc_cluster_snn", "vc_cluster_snn_dev", "vc_sharded_cluster_snn", "vc_sharded_cluster_snn_dev",
 ]
 KNN_MUTUAL, KNN_EITHER = 0, 1   # VC_KNN_*: cluster_knn joins i and j iff each lists the other / iff one lists the other
+SNN_NONE, SNN_MAX_KK = 0xFFFFFFFF, 1024   # VC_SNN_NONE: the weight word of an entry that is not listed; VC_SNN_MAX_KK: the widest kk of cluster_snn
 FILTER_MASK, FILTER_ROOTS, FILTER_EQUAL, FILTER_NOT_EQUAL, FILTER_BITS = 0, 1, 2, 3, 4   # VC_FILTER_*: how search_knn_filtered reads `sel`
 FILTER_RAN_POST, FILTER_RAN_PRE = 1, 2   # VC_FILTER_RAN_*: bits of VcFilterStats.routes
 DISTINCT_TRUNCATED = 0x80000000   # VC_DISTINCT_TRUNCATED: flag in a count of search_knn_distinct -- the row holds the groups found within the 8192 nearest records
@@ -197,6 +199,15 @@ class VcClusterKnnStats(C.Structure):
 
     def as_dict(self):
         """{n_edges, n_mutual, n_clusters, max_in_degree: int}"""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "pad"}
+
+
+class VcClusterSnnStats(C.Structure):
+    _fields_ = [("n_edges", C.c_uint64), ("n_mutual", C.c_uint64), ("n_joined", C.c_uint64), ("n_clusters", C.c_uint64), ("max_shared", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        """{n_edges, n_mutual, n_joined, n_clusters, max_shared: int}"""
         return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "pad"}
 
 
@@ -375,6 +386,10 @@ def load_library():
     L.vc_cluster_knn_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]
     L.vc_sharded_cluster_knn.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]
     L.vc_sharded_cluster_knn_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp]
+    L.vc_cluster_snn.argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, vp]
+    L.vc_cluster_snn_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp]
+    L.vc_sharded_cluster_snn.argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, vp]
+    L.vc_sharded_cluster_snn_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -780,6 +795,35 @@ def _cluster_knn(self, fn, rows, counts, kk, flags, max_dist, with_in_degree):
 def _cluster_knn_dev(self, fn, d_rows, d_counts, k, kk, flags, max_dist, d_labels, d_in_degree, with_stats, stream):
     st = VcClusterKnnStats()
     self._check(fn(self._h, d_rows, d_counts, k, kk, flags, max_dist, d_labels, d_in_degree, C.byref(st) if with_stats else None, stream))
+    return st.as_dict() if with_stats else None
+
+
+def _cluster_snn(self, fn, rows, counts, kk, min_shared, flags, max_dist, with_shared, with_hist):
+    """shared by Engine.cluster_snn and ShardedEngine.cluster_snn: (labels uint32 [N], shared uint32 [N, kk] | None, hist uint64 [kk] | None, stats dict)"""
+    n = len(self)
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    if rows.ndim != 2 or rows.shape[0] != n:
+        raise VcError(VC_ERR_INVALID, "rows must be the [N, k] graph of knn_graph over the whole store")
+    k = rows.shape[1]
+    if counts is not None:
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        if counts.shape[0] != n:
+            raise VcError(VC_ERR_INVALID, "counts must have one word per resident record")
+    labels = np.empty(n, dtype=np.uint32)
+    width = kk if 1 <= kk <= SNN_MAX_KK else 1                       # (a refused kk writes nothing)
+    shared = np.full((n, width), SNN_NONE, dtype=np.uint32) if with_shared else None
+    hist = np.zeros(width, dtype=np.uint64) if with_hist else None
+    keep = rows if n else np.zeros(1, dtype=np.uint64)
+    st = VcClusterSnnStats()
+    self._check(fn(self._h, _p(keep), _p(counts) if counts is not None and n else None, k, kk, flags, max_dist, min_shared,
+                   _p(labels) if n else _p(np.zeros(1, dtype=np.uint32)), _p(shared) if with_shared and n else None, _p(hist) if with_hist and n else None,
+                   C.byref(st)))
+    return labels, shared, hist, st.as_dict()
+
+
+def _cluster_snn_dev(self, fn, d_rows, d_counts, k, kk, min_shared, flags, max_dist, d_labels, d_shared, d_hist, with_stats, stream):
+    st = VcClusterSnnStats()
+    self._check(fn(self._h, d_rows, d_counts, k, kk, flags, max_dist, min_shared, d_labels, d_shared, d_hist, C.byref(st) if with_stats else None, stream))
     return st.as_dict() if with_stats else None
 
 
@@ -1244,6 +1288,19 @@ class Engine:
         with_stats)."""
         return _cluster_knn_dev(self, self._L.vc_cluster_knn_dev, d_rows, d_counts, k, kk, flags, max_dist, d_labels, d_in_degree, with_stats, stream)
 
+    def cluster_snn(self, rows, counts, kk, min_shared, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, with_shared=True, with_hist=True):
+        """vc_cluster_snn: shared-nearest-neighbour clusters of a graph knn_graph built over the whole store (rows [N, k], counts [N] or None).
+        "Lists" and the candidate pairs are cluster_knn's; a candidate pair is joined iff the two lists of kk share at least min_shared
+        records.  Returns (labels [N], shared [N, kk] | None -- the weight of every listed entry, SNN_NONE elsewhere --, hist [kk] | None
+        -- the listed entries by weight --, stats dict of n_edges, n_mutual, n_joined, n_clusters, max_shared)."""
+        return _cluster_snn(self, self._L.vc_cluster_snn, rows, counts, kk, min_shared, flags, max_dist, with_shared, with_hist)
+
+    def cluster_snn_dev(self, d_rows, d_counts, k, kk, min_shared, d_labels, d_shared=None, d_hist=None, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, with_stats=True,
+                        stream=None):
+        """vc_cluster_snn_dev: raw device addresses; nothing is searched, the host waits once.  Returns the stats dict (None without
+        with_stats)."""
+        return _cluster_snn_dev(self, self._L.vc_cluster_snn_dev, d_rows, d_counts, k, kk, min_shared, flags, max_dist, d_labels, d_shared, d_hist, with_stats, stream)
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -1627,6 +1684,19 @@ class ShardedEngine:
         """vc_sharded_cluster_knn_dev: raw device addresses on the root device; nothing is searched, the host waits once.  Returns the stats dict (None without
         with_stats)."""
         return _cluster_knn_dev(self, self._L.vc_sharded_cluster_knn_dev, d_rows, d_counts, k, kk, flags, max_dist, d_labels, d_in_degree, with_stats, stream)
+
+    def cluster_snn(self, rows, counts, kk, min_shared, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, with_shared=True, with_hist=True):
+        """vc_sharded_cluster_snn: shared-nearest-neighbour clusters of a graph knn_graph built over the whole store (rows [N, k], counts [N] or None).
+        "Lists" and the candidate pairs are cluster_knn's; a candidate pair is joined iff the two lists of kk share at least min_shared
+        records.  Returns (labels [N], shared [N, kk] | None -- the weight of every listed entry, SNN_NONE elsewhere --, hist [kk] | None
+        -- the listed entries by weight --, stats dict of n_edges, n_mutual, n_joined, n_clusters, max_shared)."""
+        return _cluster_snn(self, self._L.vc_sharded_cluster_snn, rows, counts, kk, min_shared, flags, max_dist, with_shared, with_hist)
+
+    def cluster_snn_dev(self, d_rows, d_counts, k, kk, min_shared, d_labels, d_shared=None, d_hist=None, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, with_stats=True,
+                        stream=None):
+        """vc_sharded_cluster_snn_dev: raw device addresses on the root device; nothing is searched, the host waits once.  Returns the stats dict (None without
+        with_stats)."""
+        return _cluster_snn_dev(self, self._L.vc_sharded_cluster_snn_dev, d_rows, d_counts, k, kk, min_shared, flags, max_dist, d_labels, d_shared, d_hist, with_stats, stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

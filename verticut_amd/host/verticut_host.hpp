@@ -185,6 +185,11 @@ class Backend {
   // labels[i] = the smallest id of the component; counts, in_degree and stats may be null
   virtual int cluster_knn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t* labels,
                           uint32_t* in_degree, vc_cluster_knn_stats* stats) = 0;
+  // shared-nearest-neighbour clusters of that graph (vc_cluster_snn / vc_sharded_cluster_snn): a candidate pair (flags as cluster_knn)
+  // is joined iff its two lists of kk share at least min_shared records; shared [N][kk] the weights (VC_SNN_NONE where nothing is
+  // listed), hist [kk] their histogram; counts, shared, hist and stats may be null
+  virtual int cluster_snn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t min_shared,
+                          uint32_t* labels, uint32_t* shared, uint64_t* hist, vc_cluster_snn_stats* stats) = 0;
   // records taken out of the store and its index, the survivors renumbered in order (vc_retain / vc_sharded_retain; the reference has
   // no delete: this stands for build_hash_tables.cc run again over the code file without them).  kind VC_RETAIN_MASK / VC_RETAIN_ROOTS
   virtual int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) = 0;
@@ -294,6 +299,10 @@ class Engine : public Backend {
   int cluster_knn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t* labels,
                   uint32_t* in_degree, vc_cluster_knn_stats* stats) override {
     return vc_cluster_knn(h_, rows, counts, k, kk, flags, max_dist, labels, in_degree, stats);
+  }
+  int cluster_snn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t min_shared,
+                  uint32_t* labels, uint32_t* shared, uint64_t* hist, vc_cluster_snn_stats* stats) override {
+    return vc_cluster_snn(h_, rows, counts, k, kk, flags, max_dist, min_shared, labels, shared, hist, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_retain(h_, sel, kind, new_ids, n_kept); }
  private:
@@ -431,6 +440,10 @@ class ShardedEngine : public Backend {
   int cluster_knn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t* labels,
                   uint32_t* in_degree, vc_cluster_knn_stats* stats) override {
     return vc_sharded_cluster_knn(h_, rows, counts, k, kk, flags, max_dist, labels, in_degree, stats);
+  }
+  int cluster_snn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t min_shared,
+                  uint32_t* labels, uint32_t* shared, uint64_t* hist, vc_cluster_snn_stats* stats) override {
+    return vc_sharded_cluster_snn(h_, rows, counts, k, kk, flags, max_dist, min_shared, labels, shared, hist, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_sharded_retain(h_, sel, kind, new_ids, n_kept); }
  private:
