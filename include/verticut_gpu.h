@@ -1246,6 +1246,71 @@ int vc_cluster_snn(vc_engine* e, const uint64_t* rows, const uint32_t* counts, u
                    uint32_t max_dist, uint32_t min_shared, uint32_t* labels, uint32_t* shared, uint64_t* hist,
                    vc_cluster_snn_stats* stats);
 
+/* ---- the reverse, mutual and symmetrised k-NN graph in CSR form: vc_knn_adjacency* --------------------------------------------------------
+ * Every call above walks the graph FORWARDS: row i tells whom i lists.  This call answers who lists j -- the ids behind
+ * vc_cluster_knn*'s in_degree[j] -- and writes the adjacency of the mutual and of the symmetrised graph, the input of community
+ * detection, label propagation, spectral and UMAP-style pipelines, in CSR.  Nothing is searched and the store is touched only for N,
+ * id_base and the code width.  The reference has no such call.
+ * PRECONDITION AND "LISTS": exactly vc_cluster_knn*'s.  d_rows (N * k) and d_counts (N, may be NULL: every row then holds
+ * min(k, N - 1) entries) are what vc_knn_graph* wrote over the full range with this k.  Row i LISTS j iff j is among the first
+ * min(kk, count_i) entries of row i and dist(i, j) <= max_dist; "j lists i" stays the one compare.  kk lies in 1 .. k.
+ * OUTPUTS.  d_offsets has N + 1 words; segment j is d_adj[d_offsets[j] .. d_offsets[j + 1]) and holds the packed
+ * dist << 32 | id of i for every record i of the set below, ASCENDING in the packed word: nearest first, ties to the smaller id -- the
+ * order of a vc_knn_graph* row.  T = d_offsets[N].
+ *   VC_KNN_REVERSE: every i that lists j.  The segment lengths are vc_cluster_knn*'s in_degree; T = n_edges.
+ *   VC_KNN_MUTUAL:  every i that lists j and is listed by j: the adjacency of the graph vc_cluster_knn*(VC_KNN_MUTUAL) takes the
+ *                   components of; T = 2 n_mutual.
+ *   VC_KNN_EITHER:  every i that lists j or is listed by j, each once: the adjacency of the symmetrised graph;
+ *                   T = 2 (n_edges - n_mutual).
+ *   stats (HOST memory in both forms, may be NULL): n_edges as vc_cluster_knn*; n_entries = T; n_empty the records whose segment is
+ *   empty; max_degree the longest segment.
+ * Every word of d_offsets and of d_adj[0 .. T) is a function of the graph and the call only: not of lane or block order, of earlier
+ * calls on the handle or of the shard layout.
+ * CAPACITY, the protocol of the radius calls.  T <= N kk under VC_KNN_REVERSE and VC_KNN_MUTUAL, T <= 2 N kk under VC_KNN_EITHER.
+ * T > adj_cap returns VC_ERR_CAPACITY: d_offsets is then filled (d_offsets[N] = T), d_adj is untouched, stats is filled.  adj_cap == 0
+ * with a NULL d_adj is the sizing call: it costs the count pass only -- no item is written, nothing is sorted.
+ * HOW.  VC_KNN_REVERSE and VC_KNN_EITHER: one thread per (record, entry < kk) writes a sort item -- key = the target's position,
+ * value = dist << 32 | id of the source; under VC_KNN_EITHER only for the one-sided entries, the mutual ones being in the target's row
+ * already -- and bumps the target's counter by an exact atomic; what is no item gets the key N and sorts to the end.  The counters
+ * are scanned; ONE copy brings T, the statistics and the error word home.  Then a stable LSD radix sort of the items, first by the
+ * distance (ceil(bitlength(min(max_dist, bits)) / 8) passes: one up to 128-bit codes, two above), then by the key
+ * (ceil(bitlength(N) / 8) passes); the enumerate order is source-major, so stability yields the (target, dist, source id) order --
+ * no segment-length limit and no ordering left to chance, whatever hubs the data hold.  VC_KNN_REVERSE copies the first T values out;
+ * VC_KNN_EITHER merges each row's listed entries with the record's sorted run by rank counting, a wave per record, the block for a
+ * segment above 1024 words.  VC_KNN_MUTUAL sorts nothing: segment i is the mutual entries of row i in row order, a ballot count and a
+ * ballot compaction.
+ * SCRATCH, in the handle's grow-only buffers: 24 N kk bytes for the two item buffer pairs (none under VC_KNN_MUTUAL and in a sizing
+ * call), the sort's work words and (N + 1) counters, 2 (N + 1) under VC_KNN_EITHER.  It is NOT bounded by VC_KGRAPH_SCRATCH: a sort
+ * cannot be chunked.
+ * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle, rows or offsets, a null adj with adj_cap > 0,
+ * k outside 1 .. VC_MAX_K - 1, kk outside 1 .. k, flags above 2, N kk > 2^31 - 1 (this version's limit: the scans and the sort's
+ * positions are 32-bit; the offsets are uint64_t so that lifting it changes no signature).  Found ON THE DEVICE, VC_ERR_INVALID: a
+ * count above k, an entry whose id is outside the store, an entry whose id equals the row's own.  They come home through the error
+ * word of the single wait, and NO OUTPUT WORD IS WRITTEN BEFORE THAT WAIT: d_offsets and d_adj are then untouched -- a stronger
+ * promise than vc_cluster_knn*'s.  A row that is not ascending, lists an id twice or holds a distance above the code width is not a
+ * vc_knn_graph* row: the result is then unspecified, but the call terminates and stays in bounds.
+ * N == 0 gives VC_OK, zero stats and d_offsets[0] = 0.  VC_ERR_NOMEM leaves the outputs untouched: every buffer is grown before the
+ * first launch.  WAITS: one in the device form.  Over a sharded store every pointer of the device form lives on the ROOT device and
+ * no shard is touched; the result equals the single engine's word for word.
+ * NOT OFFERED: segments ordered by neighbour id; a per-segment degree cap; N kk above 2^31 - 1; an incremental form after
+ * vc_add_codes / vc_retain*; weights other than the distance (vc_cluster_snn*'s d_shared is indexed by row entry and can be joined
+ * by the caller). */
+#define VC_KNN_REVERSE 2u        /* beside VC_KNN_MUTUAL 0u and VC_KNN_EITHER 1u; accepted by vc_knn_adjacency* only */
+typedef struct vc_knn_adjacency_stats {   /* 32 bytes */
+  uint64_t n_edges;      /* listed entries (directed), as vc_cluster_knn* */
+  uint64_t n_entries;    /* T = offsets[N] */
+  uint64_t n_empty;      /* records whose segment is empty */
+  uint32_t max_degree;   /* the longest segment */
+  uint32_t pad;
+} vc_knn_adjacency_stats;
+int vc_knn_adjacency_dev(vc_engine* e, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags,
+                         uint32_t max_dist, uint64_t* d_adj, uint64_t adj_cap, uint64_t* d_offsets,
+                         vc_knn_adjacency_stats* stats, void* stream);
+/* The same for host pointers: rows and counts are staged ON EVERY CALL; the offsets come home also on VC_ERR_CAPACITY, the T words of
+ * adj on VC_OK; waits for the copy home. */
+int vc_knn_adjacency(vc_engine* e, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags,
+                     uint32_t max_dist, uint64_t* adj, uint64_t adj_cap, uint64_t* offsets, vc_knn_adjacency_stats* stats);
+
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
  * seconds); the affected queries kept d_counts[i] == UINT32_MAX.  0 in normal operation.  Synchronises the stream.
@@ -1552,6 +1617,13 @@ int vc_sharded_cluster_snn_dev(vc_sharded* h, const uint64_t* d_rows, const uint
 int vc_sharded_cluster_snn(vc_sharded* h, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags,
                            uint32_t max_dist, uint32_t min_shared, uint32_t* labels, uint32_t* shared, uint64_t* hist,
                            vc_cluster_snn_stats* stats);
+/* The reverse, mutual or symmetrised graph in CSR form: as vc_knn_adjacency_dev / vc_knn_adjacency; every pointer of the device form
+ * lives on the ROOT device, no shard is touched, and the words equal the single engine's. */
+int vc_sharded_knn_adjacency_dev(vc_sharded* h, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags,
+                                 uint32_t max_dist, uint64_t* d_adj, uint64_t adj_cap, uint64_t* d_offsets,
+                                 vc_knn_adjacency_stats* stats, void* stream);
+int vc_sharded_knn_adjacency(vc_sharded* h, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags,
+                             uint32_t max_dist, uint64_t* adj, uint64_t adj_cap, uint64_t* offsets, vc_knn_adjacency_stats* stats);
 
 /* Stream of the host-pointer calls (default VC_STREAM_OWN). */
 int vc_set_stream(vc_engine* e, void* stream);

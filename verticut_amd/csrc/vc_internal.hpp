@@ -180,6 +180,11 @@ hipError_t vc_exclusive_scan_u32(const uint32_t* d_in, uint32_t* d_out, uint64_t
 uint32_t vc_radix_sort_passes(uint32_t key_bits);
 size_t vc_radix_sort_work_words(uint64_t n);
 hipError_t vc_radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], uint64_t n, uint32_t key_bits, uint32_t* d_work, hipStream_t s);
+// the same kernels with a 64-bit payload: stable sort of n items by (the low key_bits bits of the key, the low hi_bits bits of
+// value >> 32) -- the passes over the value's high word first, then the key's; items equal in both keep their input order.  Buffers,
+// work words and ping-pong as above; the result is in pair (vc_radix_sort_item_passes(hi_bits, key_bits) & 1).
+uint32_t vc_radix_sort_item_passes(uint32_t hi_bits, uint32_t key_bits);
+hipError_t vc_radix_sort_items(uint32_t* keys[2], uint64_t* vals[2], uint64_t n, uint32_t hi_bits, uint32_t key_bits, uint32_t* d_work, hipStream_t s);
 // n_lists x [nq][k] sorted lists -> merged top-k
 hipError_t vc_launch_select_lists(const uint64_t* d_lists, uint32_t n_lists, uint32_t nq, uint32_t k, uint64_t* d_out,
                                   uint32_t* d_out_count, hipStream_t s);
@@ -237,6 +242,9 @@ enum VcScratch {
   VC_KGRAPH_RET_WORK, VC_KGRAPH_RET_ROWS, VC_KGRAPH_RET_STAGE,
   // shared-nearest-neighbour clusters (vc_snn.hip): the statistics block; the host forms' staging (VcSnnStage) and their labels
   VC_SNN_STAT, VC_SNN_STAGE, VC_SNN_HLAB,
+  // the graph's adjacency (vc_knn_adjacency.hip): the statistics block; the counters and the scan's work; the two key and the two value
+  // buffers of the items; the sort's work; the host forms' staging (VcAdjStage)
+  VC_ADJ_STAT, VC_ADJ_COUNT, VC_ADJ_KEYS, VC_ADJ_VALS, VC_ADJ_SORT, VC_ADJ_STAGE,
   VC_SCRATCH_BUFS
 };
 // buffer `which` of the handle's table, at least `bytes` large, on the current device; null when it cannot be had (the handle keeps the text)
@@ -755,6 +763,25 @@ int vc_cluster_snn_run(const VcStoreView& v, const VcSnnArgs& a, vc_cluster_snn_
 // the same for host pointers (a's pointers are ignored): rows and counts staged; labels, weights and histogram (both nullable) come home, waited for
 int vc_cluster_snn_run_host(const VcStoreView& v, VcSnnArgs a, const uint64_t* rows, const uint32_t* counts, uint32_t* labels, uint32_t* shared, uint64_t* hist,
                             vc_cluster_snn_stats* stats, hipStream_t s, std::string* err);
+// ---- vc_knn_adjacency.hip: the reverse, mutual and symmetrised graph in CSR form (vc_knn_adjacency*, vc_sharded_knn_adjacency*).  One
+// driver for both handle kinds; the plan arithmetic -- the argument checks, the passes, the scratch, the teams -- is vc_knn_adjacency_plan.hpp.
+struct VcAdjArgs {
+  const uint64_t* d_rows;          // [n][k]: vc_knn_graph*'s rows over the whole store
+  const uint32_t* d_counts;        // [n], nullable: then every row holds vc_kgraph_row_count(n, k) entries
+  uint32_t k, kk, flags, max_dist; // checked by the caller: vc_kgraph_k_ok, vc_adj_kk_ok, vc_adj_flags_ok, vc_adj_items_ok
+  uint64_t* d_adj;                 // [adj_cap], null when adj_cap == 0
+  uint64_t adj_cap;
+  uint64_t* d_offsets;             // [n + 1]
+};
+// the whole call on s: every buffer grown, the enumerate (or mutual count) launch, the scans, the one wait for the statistics and the
+// error word (VC_ERR_INVALID: a count above k, an id outside the store, a row's own id -- no output word written), the offsets,
+// VC_ERR_CAPACITY where T > adj_cap (d_adj untouched), then the sort and the fill.  n == 0: offsets[0] = 0.  Only n, id_base, W and
+// alloc of the view are used
+int vc_knn_adjacency_run(const VcStoreView& v, const VcAdjArgs& a, vc_knn_adjacency_stats* stats, hipStream_t s, std::string* err);
+// the same for host pointers (a's pointers are ignored): rows and counts staged; the offsets come home also on VC_ERR_CAPACITY, the
+// T words of adj on VC_OK; waited for
+int vc_knn_adjacency_run_host(const VcStoreView& v, VcAdjArgs a, const uint64_t* rows, const uint32_t* counts, uint64_t* adj, uint64_t* offsets,
+                              vc_knn_adjacency_stats* stats, hipStream_t s, std::string* err);
 // ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
 struct VcKeepSet;
 #define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)

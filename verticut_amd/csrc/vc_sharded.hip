@@ -42,6 +42,7 @@
 #include "vc_internal.hpp"
 #include "vc_knn_graph_plan.hpp"
 #include "vc_snn_plan.hpp"
+#include "vc_knn_adjacency_plan.hpp"
 #include "vc_knn_graph_update_plan.hpp"
 #include "vc_mih.hpp"
 #include "vc_seed_plan.hpp"
@@ -2710,6 +2711,15 @@ static int check_sharded_cluster_snn_args(vc_sharded* h, const uint64_t* rows, u
   if (!vc_snn_flags_ok(flags)) return sfail(h, VC_ERR_INVALID, "SNN clusters: unknown flags 0x%x", flags);
   return VC_OK;
 }
+static int check_sharded_knn_adjacency_args(vc_sharded* h, const uint64_t* rows, uint32_t k, uint32_t kk, uint32_t flags, const uint64_t* adj, uint64_t adj_cap,
+                                            const uint64_t* offsets) {
+  if (!h || !rows || !offsets || (!adj && adj_cap)) return VC_ERR_INVALID;
+  if (!vc_kgraph_k_ok(k)) return sfail(h, VC_ERR_INVALID, "k-NN adjacency: k must be in 1..%u", VC_MAX_K - 1);
+  if (!vc_adj_kk_ok(k, kk)) return sfail(h, VC_ERR_INVALID, "k-NN adjacency: kk must be in 1..k");
+  if (!vc_adj_flags_ok(flags)) return sfail(h, VC_ERR_INVALID, "k-NN adjacency: unknown flags 0x%x", flags);
+  if (!vc_adj_items_ok(h->n, kk)) return sfail(h, VC_ERR_INVALID, "k-NN adjacency: N * kk must not exceed 2^31 - 1");
+  return VC_OK;
+}
 // a built graph after vc_sharded_add_codes (vc_knn_graph_update.hip): the graph call's checks with n_old as the first position
 static int check_sharded_kgupd_args(vc_sharded* h, uint32_t k, uint32_t mode, uint64_t n_old, uint32_t k_first, const uint64_t* rows) {
   uint64_t n_rows = 0;
@@ -2894,6 +2904,24 @@ int vc_sharded_cluster_snn(vc_sharded* h, const uint64_t* rows, const uint32_t* 
   return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_cluster_snn_run_host(v, VcSnnArgs{nullptr, nullptr, k, kk, flags, max_dist, min_shared, nullptr, nullptr, nullptr}, rows, counts, labels, shared, hist,
                                    stats, S, err);
+  });
+}
+
+int vc_sharded_knn_adjacency_dev(vc_sharded* h, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist,
+                                 uint64_t* d_adj, uint64_t adj_cap, uint64_t* d_offsets, vc_knn_adjacency_stats* stats, void* stream) {
+  const int rc = check_sharded_knn_adjacency_args(h, d_rows, k, kk, flags, d_adj, adj_cap, d_offsets);
+  if (rc) return rc;
+  return sharded_store_call(h, VC_MODE_LINEAR, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_knn_adjacency_run(v, VcAdjArgs{d_rows, d_counts, k, kk, flags, max_dist, d_adj, adj_cap, d_offsets}, stats, S, err);
+  });
+}
+
+int vc_sharded_knn_adjacency(vc_sharded* h, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist,
+                             uint64_t* adj, uint64_t adj_cap, uint64_t* offsets, vc_knn_adjacency_stats* stats) {
+  const int rc = check_sharded_knn_adjacency_args(h, rows, k, kk, flags, adj, adj_cap, offsets);
+  if (rc) return rc;
+  return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_knn_adjacency_run_host(v, VcAdjArgs{nullptr, nullptr, k, kk, flags, max_dist, nullptr, adj_cap, nullptr}, rows, counts, adj, offsets, stats, S, err);
   });
 }
 

@@ -14,6 +14,9 @@
 //                      the lanes with the same digit (8 ballots -> peer mask -> popcount below the lane), the per-wave
 //                      digit counters live in LDS, the sub-tile is staged in LDS in sorted order and written out as
 //                      contiguous runs (one run per digit), the block's running digit offsets advance.
+// The two kernels are templates on the payload (uint32_t ids, or the 64-bit packed dist << 32 | id of vc_knn_adjacency.hip: 48 KiB of
+// staging instead of 32) and on where a pass takes its digit from (the key, or bits 32 .. 63 of the value): vc_radix_sort_items
+// sorts by the value's high word first, then by the key.
 // Exclusive scan: reduce per 8192-element block -> scan of the block sums by one block -> scan with the block base.
 // ============================================================================
 #include "vc_internal.hpp"
@@ -29,7 +32,16 @@
 
 namespace {
 
-__global__ void __launch_bounds__(RS_THREADS) rs_hist_kernel(const uint32_t* __restrict__ keys, uint64_t n, uint32_t shift,
+// Where a pass takes its digit from: the 32-bit key, or bits 32 .. 63 of a 64-bit value (a packed dist << 32 | id: the distance).
+enum { RS_DIGIT_KEY = 0, RS_DIGIT_VAL_HI = 1 };
+template <class V, int SRC>
+__device__ __forceinline__ uint32_t rs_digit(uint32_t key, V val, uint32_t shift) {
+  if constexpr (SRC == RS_DIGIT_KEY) return (key >> shift) & 255u;
+  else return ((uint32_t)(val >> 32) >> shift) & 255u;
+}
+
+template <class V, int SRC>
+__global__ void __launch_bounds__(RS_THREADS) rs_hist_kernel(const uint32_t* __restrict__ keys, const V* __restrict__ vals, uint64_t n, uint32_t shift,
                                                              uint32_t nblocks, uint32_t* __restrict__ hist) {
   __shared__ uint32_t h[256];
   h[threadIdx.x] = 0;
@@ -37,21 +49,29 @@ __global__ void __launch_bounds__(RS_THREADS) rs_hist_kernel(const uint32_t* __r
   const uint64_t base = (uint64_t)blockIdx.x * RS_BLOCK_ITEMS;
   for (uint32_t i = threadIdx.x; i < RS_BLOCK_ITEMS; i += RS_THREADS) {
     const uint64_t idx = base + i;
-    if (idx < n) atomicAdd(&h[(keys[idx] >> shift) & 255u], 1u);
+    if (idx < n) {
+      uint32_t d;
+      if constexpr (SRC == RS_DIGIT_KEY) d = rs_digit<V, SRC>(keys[idx], V(0), shift);
+      else d = rs_digit<V, SRC>(0u, vals[idx], shift);
+      atomicAdd(&h[d], 1u);
+    }
   }
   __syncthreads();
   hist[(uint64_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];   // digit-major: the scan order is (digit, block)
 }
 
-// offs = exclusive scan of hist (digit-major): offs[d * nblocks + b] = first output position of block b's digit-d run
-__global__ void __launch_bounds__(RS_THREADS) rs_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
-                                                                uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
+// offs = exclusive scan of hist (digit-major): offs[d * nblocks + b] = first output position of block b's digit-d run.
+// V is the payload -- uint32_t (32 KiB of staging) or uint64_t (48 KiB) --, SRC where the digit comes from.
+template <class V, int SRC>
+__global__ void __launch_bounds__(RS_THREADS) rs_scatter_kernel(const uint32_t* __restrict__ keys_in, const V* __restrict__ vals_in,
+                                                                uint32_t* __restrict__ keys_out, V* __restrict__ vals_out,
                                                                 uint64_t n, uint32_t shift, uint32_t nblocks,
                                                                 const uint32_t* __restrict__ offs) {
   __shared__ uint32_t s_wcnt[RS_WAVES][256];   // per wave: items of each digit seen so far in this sub-tile
   __shared__ uint32_t s_dstart[257];           // sub-tile: start of every digit's run in sorted order
   __shared__ uint32_t s_run[256];              // block: next global output position of every digit
-  __shared__ uint32_t s_key[RS_TILE], s_val[RS_TILE];
+  __shared__ uint32_t s_key[RS_TILE];
+  __shared__ V s_val[RS_TILE];
   __shared__ uint32_t s_wsum[RS_WAVES];
   const uint32_t tid = threadIdx.x, lane = vc_lane(), wave = tid / VC_WAVE;
   s_run[tid] = offs[(uint64_t)tid * nblocks + blockIdx.x];
@@ -65,19 +85,20 @@ __global__ void __launch_bounds__(RS_THREADS) rs_scatter_kernel(const uint32_t* 
     __syncthreads();
     // ---- rank: wave w owns items [w * 1024, (w + 1) * 1024) of the sub-tile, 64 consecutive items per round, so that
     // (wave, round, lane) order is input order (the sort must be stable)
-    uint32_t key[RS_ROUNDS], val[RS_ROUNDS], rnk[RS_ROUNDS];
+    uint32_t key[RS_ROUNDS], rnk[RS_ROUNDS];
+    V val[RS_ROUNDS];
 #pragma unroll
     for (uint32_t j = 0; j < RS_ROUNDS; ++j) {
       const uint32_t li = (wave * RS_ROUNDS + j) * VC_WAVE + lane;   // index inside the sub-tile
       const bool ok = li < tcount;
       key[j] = ok ? keys_in[tbase + li] : 0xFFFFFFFFu;
-      val[j] = ok ? vals_in[tbase + li] : 0u;
+      val[j] = ok ? vals_in[tbase + li] : V(0);
     }
 #pragma unroll
     for (uint32_t j = 0; j < RS_ROUNDS; ++j) {
       const uint32_t li = (wave * RS_ROUNDS + j) * VC_WAVE + lane;
       const bool ok = li < tcount;
-      const uint32_t d = (key[j] >> shift) & 255u;
+      const uint32_t d = rs_digit<V, SRC>(key[j], val[j], shift);
       uint64_t peers = __ballot(ok);            // lanes of this round with the same digit (padding lanes excluded)
 #pragma unroll
       for (uint32_t b = 0; b < 8; ++b) {
@@ -121,7 +142,7 @@ __global__ void __launch_bounds__(RS_THREADS) rs_scatter_kernel(const uint32_t* 
     for (uint32_t j = 0; j < RS_ROUNDS; ++j) {
       const uint32_t li = (wave * RS_ROUNDS + j) * VC_WAVE + lane;
       if (li < tcount) {
-        const uint32_t d = (key[j] >> shift) & 255u;
+        const uint32_t d = rs_digit<V, SRC>(key[j], val[j], shift);
         const uint32_t pos = s_wcnt[wave][d] + rnk[j];
         s_key[pos] = key[j];
         s_val[pos] = val[j];
@@ -131,10 +152,11 @@ __global__ void __launch_bounds__(RS_THREADS) rs_scatter_kernel(const uint32_t* 
     // ---- write out: consecutive sorted positions of one digit are consecutive global addresses
     for (uint32_t pos = tid; pos < tcount; pos += RS_THREADS) {
       const uint32_t k = s_key[pos];
-      const uint32_t d = (k >> shift) & 255u;
+      const V v = s_val[pos];
+      const uint32_t d = rs_digit<V, SRC>(k, v, shift);
       const uint32_t g = s_run[d] + (pos - s_dstart[d]);
       keys_out[g] = k;
-      vals_out[g] = s_val[pos];
+      vals_out[g] = v;
     }
     __syncthreads();
     s_run[tid] += s_dstart[tid + 1] - s_dstart[tid];
@@ -226,6 +248,19 @@ size_t vc_radix_sort_work_words(uint64_t n) {
   return (size_t)L + vc_scan_work_words(L);
 }
 
+// one pass: histogram, scan, scatter from pair `in` to pair `out`
+template <class V, int SRC>
+static hipError_t rs_pass(const uint32_t* keys_in, const V* vals_in, uint32_t* keys_out, V* vals_out, uint64_t n, uint32_t shift, uint32_t nblocks,
+                          uint32_t* d_hist, uint32_t* d_scan, hipStream_t s) {
+  const uint64_t L = 256ull * nblocks;
+  hipLaunchKernelGGL((rs_hist_kernel<V, SRC>), dim3(nblocks), dim3(RS_THREADS), 0, s, keys_in, vals_in, n, shift, nblocks, d_hist);
+  hipError_t r = vc_exclusive_scan_u32(d_hist, d_hist, L, d_scan, s);
+  if (r != hipSuccess) return r;
+  hipLaunchKernelGGL((rs_scatter_kernel<V, SRC>), dim3(nblocks), dim3(RS_THREADS), 0, s, keys_in, vals_in, keys_out, vals_out, n, shift, nblocks,
+                     (const uint32_t*)d_hist);
+  return hipGetLastError();
+}
+
 // Stable sort of n (key, value) pairs by the low key_bits bits of the key.  Input in (keys[0], vals[0]); the passes
 // ping-pong between the two buffer pairs; the result is in pair (passes & 1).
 hipError_t vc_radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], uint64_t n, uint32_t key_bits, uint32_t* d_work, hipStream_t s) {
@@ -233,17 +268,32 @@ hipError_t vc_radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], uint64_t n,
   if (n == 0) return hipSuccess;
   const uint32_t nblocks = (uint32_t)((n + RS_BLOCK_ITEMS - 1) / RS_BLOCK_ITEMS);
   const uint64_t L = 256ull * nblocks;
-  uint32_t* d_hist = d_work;
-  uint32_t* d_scan = d_work + L;
   int cur = 0;
   for (uint32_t p = 0; p < passes; ++p) {
-    const uint32_t shift = 8 * p;
-    hipLaunchKernelGGL(rs_hist_kernel, dim3(nblocks), dim3(RS_THREADS), 0, s, keys[cur], n, shift, nblocks, d_hist);
-    hipError_t r = vc_exclusive_scan_u32(d_hist, d_hist, L, d_scan, s);
+    const hipError_t r = rs_pass<uint32_t, RS_DIGIT_KEY>(keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, 8 * p, nblocks, d_work, d_work + L, s);
     if (r != hipSuccess) return r;
-    hipLaunchKernelGGL(rs_scatter_kernel, dim3(nblocks), dim3(RS_THREADS), 0, s, keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, shift,
-                       nblocks, d_hist);
-    r = hipGetLastError();
+    cur ^= 1;
+  }
+  return hipSuccess;
+}
+
+// Stable sort of n items (key, 64-bit value) by (the low key_bits bits of the key, the low hi_bits bits of value >> 32): LSD, so the
+// passes over the value's high word come first, then the key's.  Items that agree in both keep their input order.  Same buffers,
+// work words and ping-pong as vc_radix_sort_pairs; the result is in pair (vc_radix_sort_item_passes(hi_bits, key_bits) & 1).
+uint32_t vc_radix_sort_item_passes(uint32_t hi_bits, uint32_t key_bits) { return vc_radix_sort_passes(hi_bits) + vc_radix_sort_passes(key_bits); }
+
+hipError_t vc_radix_sort_items(uint32_t* keys[2], uint64_t* vals[2], uint64_t n, uint32_t hi_bits, uint32_t key_bits, uint32_t* d_work, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const uint32_t nblocks = (uint32_t)((n + RS_BLOCK_ITEMS - 1) / RS_BLOCK_ITEMS);
+  const uint64_t L = 256ull * nblocks;
+  int cur = 0;
+  for (uint32_t p = 0; p < vc_radix_sort_passes(hi_bits); ++p) {
+    const hipError_t r = rs_pass<uint64_t, RS_DIGIT_VAL_HI>(keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, 8 * p, nblocks, d_work, d_work + L, s);
+    if (r != hipSuccess) return r;
+    cur ^= 1;
+  }
+  for (uint32_t p = 0; p < vc_radix_sort_passes(key_bits); ++p) {
+    const hipError_t r = rs_pass<uint64_t, RS_DIGIT_KEY>(keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, 8 * p, nblocks, d_work, d_work + L, s);
     if (r != hipSuccess) return r;
     cur ^= 1;
   }

@@ -60,8 +60,10 @@ EXPORTS = [
     "vc_knn_graph_update", "vc_knn_graph_update_dev", "vc_sharded_knn_graph_update", "vc_sharded_knn_graph_update_dev",
     "vc_knn_graph_retain", "vc_knn_graph_retain_dev", "vc_sharded_knn_graph_retain", "vc_sharded_knn_graph_retain_dev",
     "vc_cluster_snn", "vc_cluster_snn_dev", "vc_sharded_cluster_snn", "vc_sharded_cluster_snn_dev",
+    "vc_knn_adjacency", "vc_knn_adjacency_dev", "vc_sharded_knn_adjacency", "vc_sharded_knn_adjacency_dev",
 ]
 KNN_MUTUAL, KNN_EITHER = 0, 1   # VC_KNN_*: cluster_knn joins i and j iff each lists the other / iff one lists the other
+KNN_REVERSE = 2                 # VC_KNN_REVERSE: knn_adjacency only -- segment j holds every record that lists j
 SNN_NONE, SNN_MAX_KK = 0xFFFFFFFF, 1024   # VC_SNN_NONE: the weight word of an entry that is not listed; VC_SNN_MAX_KK: the widest kk of cluster_snn
 FILTER_MASK, FILTER_ROOTS, FILTER_EQUAL, FILTER_NOT_EQUAL, FILTER_BITS = 0, 1, 2, 3, 4   # VC_FILTER_*: how search_knn_filtered reads `sel`
 FILTER_RAN_POST, FILTER_RAN_PRE = 1, 2   # VC_FILTER_RAN_*: bits of VcFilterStats.routes
@@ -208,6 +210,14 @@ class VcClusterSnnStats(C.Structure):
 
     def as_dict(self):
         """{n_edges, n_mutual, n_joined, n_clusters, max_shared: int}"""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "pad"}
+
+
+class VcKnnAdjacencyStats(C.Structure):
+    _fields_ = [("n_edges", C.c_uint64), ("n_entries", C.c_uint64), ("n_empty", C.c_uint64), ("max_degree", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        """{n_edges, n_entries, n_empty, max_degree: int}"""
         return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "pad"}
 
 
@@ -390,6 +400,10 @@ def load_library():
     L.vc_cluster_snn_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp]
     L.vc_sharded_cluster_snn.argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, vp]
     L.vc_sharded_cluster_snn_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp]
+    L.vc_knn_adjacency.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, u64, vp, vp]
+    L.vc_knn_adjacency_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, u64, vp, vp, vp]
+    L.vc_sharded_knn_adjacency.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, u64, vp, vp]
+    L.vc_sharded_knn_adjacency_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, u64, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -825,6 +839,35 @@ def _cluster_snn_dev(self, fn, d_rows, d_counts, k, kk, min_shared, flags, max_d
     st = VcClusterSnnStats()
     self._check(fn(self._h, d_rows, d_counts, k, kk, flags, max_dist, min_shared, d_labels, d_shared, d_hist, C.byref(st) if with_stats else None, stream))
     return st.as_dict() if with_stats else None
+
+
+def _knn_adjacency(self, fn, rows, counts, kk, flags, max_dist):
+    """shared by Engine.knn_adjacency and ShardedEngine.knn_adjacency: (offsets uint64 [N + 1], adj uint64 [T], stats dict); the
+    output is sized by the bound, N kk words, twice that under KNN_EITHER"""
+    n = len(self)
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    if rows.ndim != 2 or rows.shape[0] != n:
+        raise VcError(VC_ERR_INVALID, "rows must be the [N, k] graph of knn_graph over the whole store")
+    k = rows.shape[1]
+    if counts is not None:
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        if counts.shape[0] != n:
+            raise VcError(VC_ERR_INVALID, "counts must have one word per resident record")
+    cap = (2 if flags == KNN_EITHER else 1) * n * kk if 1 <= kk <= k else 0     # (a refused kk writes nothing)
+    offsets = np.zeros(n + 1, dtype=np.uint64)
+    adj = np.empty(max(cap, 1), dtype=np.uint64)
+    keep = rows if n else np.zeros(1, dtype=np.uint64)
+    st = VcKnnAdjacencyStats()
+    self._check(fn(self._h, _p(keep), _p(counts) if counts is not None and n else None, k, kk, flags, max_dist, _p(adj), cap, _p(offsets), C.byref(st)))
+    return offsets, adj[:int(offsets[n])].copy(), st.as_dict()
+
+
+def _knn_adjacency_dev(self, fn, d_rows, d_counts, k, kk, flags, max_dist, d_adj, adj_cap, d_offsets, with_stats, stream):
+    """returns (rc, stats): rc is VC_OK or VC_ERR_CAPACITY (T > adj_cap: the offsets and the stats are filled, d_adj is untouched)"""
+    st = VcKnnAdjacencyStats()
+    rc = self._check(fn(self._h, d_rows, d_counts, k, kk, flags, max_dist, d_adj, adj_cap, d_offsets, C.byref(st) if with_stats else None, stream),
+                     ok=(VC_OK, VC_ERR_CAPACITY))
+    return rc, st.as_dict() if with_stats else None
 
 
 def _retain(self, fn, sel, kind, with_map):
@@ -1301,6 +1344,19 @@ class Engine:
         with_stats)."""
         return _cluster_snn_dev(self, self._L.vc_cluster_snn_dev, d_rows, d_counts, k, kk, min_shared, flags, max_dist, d_labels, d_shared, d_hist, with_stats, stream)
 
+    def knn_adjacency(self, rows, counts, kk, flags=KNN_REVERSE, max_dist=0xFFFFFFFF):
+        """vc_knn_adjacency: the reverse (KNN_REVERSE: who lists j), mutual (KNN_MUTUAL) or symmetrised (KNN_EITHER) graph of a graph
+        knn_graph built over the whole store (rows [N, k], counts [N] or None), in CSR form; "lists" is cluster_knn's.  Returns
+        (offsets [N + 1], adj [T], stats dict of n_edges, n_entries, n_empty, max_degree): segment j is adj[offsets[j]:offsets[j + 1]],
+        packed dist << 32 | id, ascending."""
+        return _knn_adjacency(self, self._L.vc_knn_adjacency, rows, counts, kk, flags, max_dist)
+
+    def knn_adjacency_dev(self, d_rows, d_counts, k, kk, d_adj, adj_cap, d_offsets, flags=KNN_REVERSE, max_dist=0xFFFFFFFF, with_stats=True, stream=None):
+        """vc_knn_adjacency_dev: raw device addresses; nothing is searched, the host waits once.  Returns (rc, stats dict | None): rc is
+        VC_OK, or VC_ERR_CAPACITY when T > adj_cap (d_offsets and the stats are filled, d_adj is untouched; adj_cap = 0 with d_adj None
+        is the sizing call)."""
+        return _knn_adjacency_dev(self, self._L.vc_knn_adjacency_dev, d_rows, d_counts, k, kk, flags, max_dist, d_adj, adj_cap, d_offsets, with_stats, stream)
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -1697,6 +1753,17 @@ class ShardedEngine:
         """vc_sharded_cluster_snn_dev: raw device addresses on the root device; nothing is searched, the host waits once.  Returns the stats dict (None without
         with_stats)."""
         return _cluster_snn_dev(self, self._L.vc_sharded_cluster_snn_dev, d_rows, d_counts, k, kk, min_shared, flags, max_dist, d_labels, d_shared, d_hist, with_stats, stream)
+
+    def knn_adjacency(self, rows, counts, kk, flags=KNN_REVERSE, max_dist=0xFFFFFFFF):
+        """vc_sharded_knn_adjacency: the reverse (KNN_REVERSE), mutual (KNN_MUTUAL) or symmetrised (KNN_EITHER) graph of a graph knn_graph
+        built over the whole store, in CSR form.  Returns (offsets [N + 1], adj [T], stats dict), word for word Engine.knn_adjacency's."""
+        return _knn_adjacency(self, self._L.vc_sharded_knn_adjacency, rows, counts, kk, flags, max_dist)
+
+    def knn_adjacency_dev(self, d_rows, d_counts, k, kk, d_adj, adj_cap, d_offsets, flags=KNN_REVERSE, max_dist=0xFFFFFFFF, with_stats=True, stream=None):
+        """vc_sharded_knn_adjacency_dev: raw device addresses on the root device; no shard is touched, the host waits once.  Returns
+        (rc, stats dict | None) as Engine.knn_adjacency_dev."""
+        return _knn_adjacency_dev(self, self._L.vc_sharded_knn_adjacency_dev, d_rows, d_counts, k, kk, flags, max_dist, d_adj, adj_cap, d_offsets, with_stats,
+                                  stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

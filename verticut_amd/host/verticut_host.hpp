@@ -190,6 +190,12 @@ class Backend {
   // listed), hist [kk] their histogram; counts, shared, hist and stats may be null
   virtual int cluster_snn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t min_shared,
                           uint32_t* labels, uint32_t* shared, uint64_t* hist, vc_cluster_snn_stats* stats) = 0;
+  // that graph turned round, in CSR form (vc_knn_adjacency / vc_sharded_knn_adjacency): segment j = adj[offsets[j] .. offsets[j + 1])
+  // holds dist << 32 | id, ascending, of every record that lists j (VC_KNN_REVERSE), that lists j and is listed by it (VC_KNN_MUTUAL)
+  // or either (VC_KNN_EITHER); offsets has N + 1 words; VC_ERR_CAPACITY where offsets[N] > adj_cap (adj_cap 0 with a null adj sizes);
+  // counts and stats may be null
+  virtual int knn_adjacency(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint64_t* adj,
+                            uint64_t adj_cap, uint64_t* offsets, vc_knn_adjacency_stats* stats) = 0;
   // records taken out of the store and its index, the survivors renumbered in order (vc_retain / vc_sharded_retain; the reference has
   // no delete: this stands for build_hash_tables.cc run again over the code file without them).  kind VC_RETAIN_MASK / VC_RETAIN_ROOTS
   virtual int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) = 0;
@@ -303,6 +309,10 @@ class Engine : public Backend {
   int cluster_snn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t min_shared,
                   uint32_t* labels, uint32_t* shared, uint64_t* hist, vc_cluster_snn_stats* stats) override {
     return vc_cluster_snn(h_, rows, counts, k, kk, flags, max_dist, min_shared, labels, shared, hist, stats);
+  }
+  int knn_adjacency(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint64_t* adj,
+                    uint64_t adj_cap, uint64_t* offsets, vc_knn_adjacency_stats* stats) override {
+    return vc_knn_adjacency(h_, rows, counts, k, kk, flags, max_dist, adj, adj_cap, offsets, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_retain(h_, sel, kind, new_ids, n_kept); }
  private:
@@ -444,6 +454,10 @@ class ShardedEngine : public Backend {
   int cluster_snn(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t min_shared,
                   uint32_t* labels, uint32_t* shared, uint64_t* hist, vc_cluster_snn_stats* stats) override {
     return vc_sharded_cluster_snn(h_, rows, counts, k, kk, flags, max_dist, min_shared, labels, shared, hist, stats);
+  }
+  int knn_adjacency(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint64_t* adj,
+                    uint64_t adj_cap, uint64_t* offsets, vc_knn_adjacency_stats* stats) override {
+    return vc_sharded_knn_adjacency(h_, rows, counts, k, kk, flags, max_dist, adj, adj_cap, offsets, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_sharded_retain(h_, sel, kind, new_ids, n_kept); }
  private:
