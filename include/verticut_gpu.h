@@ -1311,6 +1311,89 @@ int vc_knn_adjacency_dev(vc_engine* e, const uint64_t* d_rows, const uint32_t* d
 int vc_knn_adjacency(vc_engine* e, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags,
                      uint32_t max_dist, uint64_t* adj, uint64_t adj_cap, uint64_t* offsets, vc_knn_adjacency_stats* stats);
 
+/* ---- the minimum spanning forest of the k-NN graph in Kruskal order: vc_knn_mst*, vc_mst_cut* -------------------------------------------
+ * vc_cluster_knn* gives the components at ONE cut.  The minimum spanning forest (MSF) of the mutual or symmetrised graph gives them
+ * at EVERY cut: at most N - 1 edges, ascending, from which the labels at any height, the number of clusters at every height and --
+ * under mutual-reachability weights -- the tree that HDBSCAN-style pipelines condense all follow without reading the N kk entries
+ * again, and with no limit on the number of levels (vc_cluster_levels* stops at radius 63 and costs N words per level).
+ * PRECONDITION AND "LISTS": exactly vc_cluster_knn*'s.  d_rows (N * k) and d_counts (N, may be NULL: every row then holds
+ * min(k, N - 1) entries) are what vc_knn_graph* wrote over the full range with this k.  Row i LISTS j iff j is among the first
+ * min(kk, count_i) entries of row i and dist(i, j) <= max_dist.  kk lies in 1 .. k, and N kk <= 2^31 - 1 (vc_knn_adjacency*'s limit:
+ * an entry's index takes the low word of the edge key).
+ * GRAPH.  flags is VC_KNN_MUTUAL or VC_KNN_EITHER: the undirected pair {i, j} is an edge iff each lists the other / iff one lists
+ * the other.  VC_KNN_REVERSE is refused.
+ * WEIGHT.  weight_kind = VC_MST_DISTANCE: w = dist(i, j); min_pts must be 1.  VC_MST_REACHABILITY: w = max(dist(i, j), c_i, c_j), the
+ * mutual-reachability distance; min_pts lies in 1 .. k + 1 and counts the record itself, as vc_dbscan_levels*'s: c_i = 0 for
+ * min_pts = 1, otherwise the distance of entry min_pts - 2 of row i, read from the k columns regardless of kk and max_dist; when
+ * count_i < min_pts - 1, c_i = bits.  min_pts = 1 under VC_MST_REACHABILITY gives VC_MST_DISTANCE's output bit for bit.
+ * THE ORDER, which makes every word a function of the graph and the call.  An edge is written as vc_mst_edge { a, b, weight, dist }
+ * with global ids.  a is the HOME end: the smaller id if it lists the other, otherwise the larger (the larger then lists the smaller;
+ * such one-sided edges exist only under VC_KNN_EITHER); b is the other end.  Edges are ordered lexicographically by
+ * (weight, a, dist, b), which is the order of the 64-bit key weight << 32 | (pos(a) * kk + jj), jj the position of b in row a, because
+ * rows ascend in (dist, id).  The order is strict, so the MSF is unique: the edges Kruskal keeps, taking edges ascending.
+ * OUTPUTS of vc_knn_mst_dev.
+ *   d_edges has room for max(N, 1) - 1 entries: the M forest edges, ascending in the order above; words beyond M are untouched.
+ *   d_labels (N words, may be NULL): the components of the whole graph, smallest global id -- vc_cluster_knn*'s labels for the same
+ *     kk, flags and max_dist, bit for bit.
+ *   d_hist (bits + 1 words of uint64_t, may be NULL): hist[w] = forest edges of weight w; the clusters at height h are
+ *     N - sum of hist[w] over w <= h.
+ *   stats (HOST memory in both forms, may be NULL): n_edges the listed (directed) entries as vc_cluster_knn*, n_graph_edges the
+ *     undirected edges of the chosen graph, n_tree = M, n_clusters = N - M, total_weight, max_weight, n_rounds the Boruvka rounds
+ *     that hooked something -- implementation-defined, at most ceil(log2 N) + 1.
+ * vc_mst_cut_dev: the components of the N records under the given edges of weight <= max_weight, smallest-id labels; it takes ANY
+ * edge list, sorted or not (dist is not read).  An end outside the store gives VC_ERR_INVALID, found on the device.  On the MSF under
+ * VC_MST_DISTANCE it equals vc_cluster_knn*(max_dist = min(the build's cap, max_weight)) bit for bit.  Its labels feed
+ * vc_group_summary*, vc_retain*(VC_RETAIN_ROOTS), vc_search_knn_distinct* and the filtered and scoped calls unchanged.  *n_clusters
+ * (HOST memory, may be NULL) gets the number of components.
+ * HOW.  Boruvka on the device.  One thread per (record, entry < kk) validates the entry, does vc_cluster_knn*'s one compare and
+ * appends every HOME entry to a compact live list (key, the other end) by ballot rank.  A round: every live edge whose ends lie in
+ * two components offers its key to both by a 64-bit atomicMin behind a relaxed load, and survives into the other live buffer; every
+ * component with a pick writes it to the picked list exactly once and unites the two trees in the lock-free forest of
+ * vc_cluster_radius*; a flatten pass takes the round's snapshot.  The host reads the picked count and stops when a round hooked
+ * nothing.  The strict order forbids cycles, and a chain of any length may hook in one round.  Then vc_knn_adjacency*'s stable radix
+ * sort of the M picked edges by (weight, home index), and one launch writes the edges, the histogram and the sums.
+ * SCRATCH, in the handle's grow-only buffers: 24 bytes per home entry (at most N kk of them, N kk / 2 under VC_KNN_MUTUAL) for the two
+ * live buffers, 16 N for the forest, 24 N for the picked list and the sort's work words.
+ * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle, rows or edges, k outside 1 .. VC_MAX_K - 1,
+ * kk outside 1 .. k, flags other than VC_KNN_MUTUAL / VC_KNN_EITHER, an unknown weight_kind, min_pts outside its range,
+ * N kk > 2^31 - 1; vc_mst_cut*: a null handle or labels, null edges with n_edges > 0.  Found ON THE DEVICE, VC_ERR_INVALID through
+ * vc_cluster_knn*'s protocol (THE OUTPUTS ARE THEN UNDEFINED, everything stays in bounds): a count above k, an entry whose id is
+ * outside the store, an entry whose id equals the row's own.  N == 0 gives VC_OK and zero stats (d_hist zeroed); N == 1 gives M = 0
+ * and the own label.
+ * WAITS: one small read-back per round, plus one at the end; vc_mst_cut*: one.  Over a sharded store every pointer of the device
+ * forms lives on the ROOT device and no shard is touched; the result equals the single engine's word for word.
+ * NOT OFFERED: an incremental form; the condensed tree and stability selection (host work on N - 1 edges); N kk above 2^31 - 1. */
+#define VC_MST_DISTANCE 0u
+#define VC_MST_REACHABILITY 1u
+typedef struct vc_mst_edge {   /* 16 bytes */
+  uint32_t a;        /* the home end, global id */
+  uint32_t b;        /* the other end, global id */
+  uint32_t weight;
+  uint32_t dist;
+} vc_mst_edge;
+typedef struct vc_knn_mst_stats {   /* 48 bytes */
+  uint64_t n_edges;        /* listed entries (directed), as vc_cluster_knn* */
+  uint64_t n_graph_edges;  /* undirected edges of the chosen graph */
+  uint64_t n_tree;         /* M */
+  uint64_t n_clusters;     /* N - M */
+  uint64_t total_weight;
+  uint32_t max_weight;
+  uint32_t n_rounds;       /* rounds that hooked something */
+} vc_knn_mst_stats;
+int vc_knn_mst_dev(vc_engine* e, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags,
+                   uint32_t max_dist, uint32_t weight_kind, uint32_t min_pts, vc_mst_edge* d_edges, uint32_t* d_labels,
+                   uint64_t* d_hist, vc_knn_mst_stats* stats, void* stream);
+/* The same for host pointers: rows and counts are staged ON EVERY CALL; the M edges, the labels and the histogram (both may be NULL)
+ * come home; waits for them.  M is stats->n_tree. */
+int vc_knn_mst(vc_engine* e, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags,
+               uint32_t max_dist, uint32_t weight_kind, uint32_t min_pts, vc_mst_edge* edges, uint32_t* labels, uint64_t* hist,
+               vc_knn_mst_stats* stats);
+int vc_mst_cut_dev(vc_engine* e, const vc_mst_edge* d_edges, uint64_t n_edges, uint32_t max_weight, uint32_t* d_labels,
+                   uint64_t* n_clusters, void* stream);
+/* The same for host pointers: the edges are staged, the labels come home; waits for them. */
+int vc_mst_cut(vc_engine* e, const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels,
+               uint64_t* n_clusters);
+
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
  * seconds); the affected queries kept d_counts[i] == UINT32_MAX.  0 in normal operation.  Synchronises the stream.
@@ -1624,6 +1707,18 @@ int vc_sharded_knn_adjacency_dev(vc_sharded* h, const uint64_t* d_rows, const ui
                                  vc_knn_adjacency_stats* stats, void* stream);
 int vc_sharded_knn_adjacency(vc_sharded* h, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags,
                              uint32_t max_dist, uint64_t* adj, uint64_t adj_cap, uint64_t* offsets, vc_knn_adjacency_stats* stats);
+/* The minimum spanning forest and the cut of an edge list: as vc_knn_mst_dev / vc_knn_mst / vc_mst_cut_dev / vc_mst_cut; every pointer
+ * of the device forms lives on the ROOT device, no shard is touched, and the words equal the single engine's. */
+int vc_sharded_knn_mst_dev(vc_sharded* h, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags,
+                           uint32_t max_dist, uint32_t weight_kind, uint32_t min_pts, vc_mst_edge* d_edges, uint32_t* d_labels,
+                           uint64_t* d_hist, vc_knn_mst_stats* stats, void* stream);
+int vc_sharded_knn_mst(vc_sharded* h, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags,
+                       uint32_t max_dist, uint32_t weight_kind, uint32_t min_pts, vc_mst_edge* edges, uint32_t* labels, uint64_t* hist,
+                       vc_knn_mst_stats* stats);
+int vc_sharded_mst_cut_dev(vc_sharded* h, const vc_mst_edge* d_edges, uint64_t n_edges, uint32_t max_weight, uint32_t* d_labels,
+                           uint64_t* n_clusters, void* stream);
+int vc_sharded_mst_cut(vc_sharded* h, const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels,
+                       uint64_t* n_clusters);
 
 /* Stream of the host-pointer calls (default VC_STREAM_OWN). */
 int vc_set_stream(vc_engine* e, void* stream);

@@ -245,6 +245,9 @@ enum VcScratch {
   // the graph's adjacency (vc_knn_adjacency.hip): the statistics block; the counters and the scan's work; the two key and the two value
   // buffers of the items; the sort's work; the host forms' staging (VcAdjStage)
   VC_ADJ_STAT, VC_ADJ_COUNT, VC_ADJ_KEYS, VC_ADJ_VALS, VC_ADJ_SORT, VC_ADJ_STAGE,
+  // the graph's spanning forest (vc_knn_mst.hip): the statistics block; best, the forest and the snapshot; the two live buffers; the two
+  // key and value buffers of the picked list; the sort's work; the host forms' staging (VcMstStage, VcMstCutStage)
+  VC_MST_STAT, VC_MST_FOREST, VC_MST_LIVE, VC_MST_PICK, VC_MST_SORT, VC_MST_STAGE,
   VC_SCRATCH_BUFS
 };
 // buffer `which` of the handle's table, at least `bytes` large, on the current device; null when it cannot be had (the handle keeps the text)
@@ -782,6 +785,32 @@ int vc_knn_adjacency_run(const VcStoreView& v, const VcAdjArgs& a, vc_knn_adjace
 // T words of adj on VC_OK; waited for
 int vc_knn_adjacency_run_host(const VcStoreView& v, VcAdjArgs a, const uint64_t* rows, const uint32_t* counts, uint64_t* adj, uint64_t* offsets,
                               vc_knn_adjacency_stats* stats, hipStream_t s, std::string* err);
+// ---- vc_knn_mst.hip: the minimum spanning forest of a built graph in Kruskal order (vc_knn_mst*, vc_sharded_knn_mst*) and the cut of
+// an edge list (vc_mst_cut*, vc_sharded_mst_cut*).  One driver for both handle kinds; the plan arithmetic -- the argument checks, the
+// key, the home rule, the sizes, the round bound -- is vc_knn_mst_plan.hpp.
+struct VcMstArgs {
+  const uint64_t* d_rows;          // [n][k]: vc_knn_graph*'s rows over the whole store
+  const uint32_t* d_counts;        // [n], nullable: then every row holds vc_kgraph_row_count(n, k) entries
+  uint32_t k, kk, flags, max_dist; // checked by the caller: vc_kgraph_k_ok, vc_mst_kk_ok, vc_mst_flags_ok, vc_mst_items_ok
+  uint32_t weight_kind, min_pts;   // vc_mst_kind_ok, vc_mst_min_pts_ok
+  vc_mst_edge* d_edges;            // [max(n, 1) - 1]
+  uint32_t* d_labels;              // [n], nullable
+  uint64_t* d_hist;                // [bits + 1], nullable
+};
+// the whole call on s: init, the enumeration, the rounds (one wait each; the first brings the error word: VC_ERR_INVALID for a count
+// above k, an id outside the store, a row's own id), the sort, the outputs, the last wait.  n == 0: the histogram zeroed.  Only n,
+// id_base, W and alloc of the view are used
+int vc_knn_mst_run(const VcStoreView& v, const VcMstArgs& a, vc_knn_mst_stats* stats, hipStream_t s, std::string* err);
+// the same for host pointers (a's pointers are ignored): rows and counts staged; the M edges, the labels and the histogram (both
+// nullable) come home, waited for
+int vc_knn_mst_run_host(const VcStoreView& v, VcMstArgs a, const uint64_t* rows, const uint32_t* counts, vc_mst_edge* edges, uint32_t* labels, uint64_t* hist,
+                        vc_knn_mst_stats* stats, hipStream_t s, std::string* err);
+// the components under the edges of weight <= max_weight: init, one launch over the edges, flatten, one wait (VC_ERR_INVALID: an end
+// outside the store).  n_clusters: host memory, nullable
+int vc_mst_cut_run(const VcStoreView& v, const vc_mst_edge* d_edges, uint64_t n_edges, uint32_t max_weight, uint32_t* d_labels, uint64_t* n_clusters, hipStream_t s,
+                   std::string* err);
+int vc_mst_cut_run_host(const VcStoreView& v, const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels, uint64_t* n_clusters, hipStream_t s,
+                        std::string* err);
 // ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
 struct VcKeepSet;
 #define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)

@@ -43,6 +43,7 @@
 #include "vc_knn_graph_plan.hpp"
 #include "vc_snn_plan.hpp"
 #include "vc_knn_adjacency_plan.hpp"
+#include "vc_knn_mst_plan.hpp"
 #include "vc_knn_graph_update_plan.hpp"
 #include "vc_mih.hpp"
 #include "vc_seed_plan.hpp"
@@ -2720,6 +2721,18 @@ static int check_sharded_knn_adjacency_args(vc_sharded* h, const uint64_t* rows,
   if (!vc_adj_items_ok(h->n, kk)) return sfail(h, VC_ERR_INVALID, "k-NN adjacency: N * kk must not exceed 2^31 - 1");
   return VC_OK;
 }
+static int check_sharded_knn_mst_args(vc_sharded* h, const uint64_t* rows, uint32_t k, uint32_t kk, uint32_t flags, uint32_t weight_kind, uint32_t min_pts,
+                                      const vc_mst_edge* edges) {
+  if (!h || !rows || !edges) return VC_ERR_INVALID;
+  if (!vc_kgraph_k_ok(k)) return sfail(h, VC_ERR_INVALID, "k-NN spanning forest: k must be in 1..%u", VC_MAX_K - 1);
+  if (!vc_mst_kk_ok(k, kk)) return sfail(h, VC_ERR_INVALID, "k-NN spanning forest: kk must be in 1..k");
+  if (!vc_mst_flags_ok(flags)) return sfail(h, VC_ERR_INVALID, "k-NN spanning forest: flags must be VC_KNN_MUTUAL or VC_KNN_EITHER, not 0x%x", flags);
+  if (!vc_mst_kind_ok(weight_kind)) return sfail(h, VC_ERR_INVALID, "k-NN spanning forest: unknown weight_kind %u", weight_kind);
+  if (!vc_mst_min_pts_ok(weight_kind, k, min_pts))
+    return sfail(h, VC_ERR_INVALID, "k-NN spanning forest: min_pts must be 1 under VC_MST_DISTANCE and in 1..k+1 under VC_MST_REACHABILITY");
+  if (!vc_mst_items_ok(h->n, kk)) return sfail(h, VC_ERR_INVALID, "k-NN spanning forest: N * kk must not exceed 2^31 - 1");
+  return VC_OK;
+}
 // a built graph after vc_sharded_add_codes (vc_knn_graph_update.hip): the graph call's checks with n_old as the first position
 static int check_sharded_kgupd_args(vc_sharded* h, uint32_t k, uint32_t mode, uint64_t n_old, uint32_t k_first, const uint64_t* rows) {
   uint64_t n_rows = 0;
@@ -2922,6 +2935,41 @@ int vc_sharded_knn_adjacency(vc_sharded* h, const uint64_t* rows, const uint32_t
   if (rc) return rc;
   return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_knn_adjacency_run_host(v, VcAdjArgs{nullptr, nullptr, k, kk, flags, max_dist, nullptr, adj_cap, nullptr}, rows, counts, adj, offsets, stats, S, err);
+  });
+}
+
+int vc_sharded_knn_mst_dev(vc_sharded* h, const uint64_t* d_rows, const uint32_t* d_counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist,
+                           uint32_t weight_kind, uint32_t min_pts, vc_mst_edge* d_edges, uint32_t* d_labels, uint64_t* d_hist, vc_knn_mst_stats* stats,
+                           void* stream) {
+  const int rc = check_sharded_knn_mst_args(h, d_rows, k, kk, flags, weight_kind, min_pts, d_edges);
+  if (rc) return rc;
+  return sharded_store_call(h, VC_MODE_LINEAR, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_knn_mst_run(v, VcMstArgs{d_rows, d_counts, k, kk, flags, max_dist, weight_kind, min_pts, d_edges, d_labels, d_hist}, stats, S, err);
+  });
+}
+
+int vc_sharded_knn_mst(vc_sharded* h, const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist,
+                       uint32_t weight_kind, uint32_t min_pts, vc_mst_edge* edges, uint32_t* labels, uint64_t* hist, vc_knn_mst_stats* stats) {
+  const int rc = check_sharded_knn_mst_args(h, rows, k, kk, flags, weight_kind, min_pts, edges);
+  if (rc) return rc;
+  return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_knn_mst_run_host(v, VcMstArgs{nullptr, nullptr, k, kk, flags, max_dist, weight_kind, min_pts, nullptr, nullptr, nullptr}, rows, counts, edges, labels,
+                               hist, stats, S, err);
+  });
+}
+
+int vc_sharded_mst_cut_dev(vc_sharded* h, const vc_mst_edge* d_edges, uint64_t n_edges, uint32_t max_weight, uint32_t* d_labels, uint64_t* n_clusters,
+                           void* stream) {
+  if (!h || !d_labels || (!d_edges && n_edges)) return VC_ERR_INVALID;
+  return sharded_store_call(h, VC_MODE_LINEAR, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_mst_cut_run(v, d_edges, n_edges, max_weight, d_labels, n_clusters, S, err);
+  });
+}
+
+int vc_sharded_mst_cut(vc_sharded* h, const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels, uint64_t* n_clusters) {
+  if (!h || !labels || (!edges && n_edges)) return VC_ERR_INVALID;
+  return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_mst_cut_run_host(v, edges, n_edges, max_weight, labels, n_clusters, S, err);
   });
 }
 

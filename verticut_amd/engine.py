@@ -61,9 +61,12 @@ EXPORTS = [
     "vc_knn_graph_retain", "vc_knn_graph_retain_dev", "vc_sharded_knn_graph_retain", "vc_sharded_knn_graph_retain_dev",
     "vc_cluster_snn", "vc_cluster_snn_dev", "vc_sharded_cluster_snn", "vc_sharded_cluster_snn_dev",
     "vc_knn_adjacency", "vc_knn_adjacency_dev", "vc_sharded_knn_adjacency", "vc_sharded_knn_adjacency_dev",
+    "vc_knn_mst", "vc_knn_mst_dev", "vc_sharded_knn_mst", "vc_sharded_knn_mst_dev",
+    "vc_mst_cut", "vc_mst_cut_dev", "vc_sharded_mst_cut", "vc_sharded_mst_cut_dev",
 ]
 KNN_MUTUAL, KNN_EITHER = 0, 1   # VC_KNN_*: cluster_knn joins i and j iff each lists the other / iff one lists the other
 KNN_REVERSE = 2                 # VC_KNN_REVERSE: knn_adjacency only -- segment j holds every record that lists j
+MST_DISTANCE, MST_REACHABILITY = 0, 1   # VC_MST_*: knn_mst weighs an edge by its distance / by max(distance, the two core distances at min_pts)
 SNN_NONE, SNN_MAX_KK = 0xFFFFFFFF, 1024   # VC_SNN_NONE: the weight word of an entry that is not listed; VC_SNN_MAX_KK: the widest kk of cluster_snn
 FILTER_MASK, FILTER_ROOTS, FILTER_EQUAL, FILTER_NOT_EQUAL, FILTER_BITS = 0, 1, 2, 3, 4   # VC_FILTER_*: how search_knn_filtered reads `sel`
 FILTER_RAN_POST, FILTER_RAN_PRE = 1, 2   # VC_FILTER_RAN_*: bits of VcFilterStats.routes
@@ -219,6 +222,18 @@ class VcKnnAdjacencyStats(C.Structure):
     def as_dict(self):
         """{n_edges, n_entries, n_empty, max_degree: int}"""
         return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "pad"}
+
+
+class VcKnnMstStats(C.Structure):
+    _fields_ = [("n_edges", C.c_uint64), ("n_graph_edges", C.c_uint64), ("n_tree", C.c_uint64), ("n_clusters", C.c_uint64), ("total_weight", C.c_uint64),
+                ("max_weight", C.c_uint32), ("n_rounds", C.c_uint32)]
+
+    def as_dict(self):
+        """{n_edges, n_graph_edges, n_tree, n_clusters, total_weight, max_weight, n_rounds: int}"""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+MST_EDGE = np.dtype([("a", np.uint32), ("b", np.uint32), ("weight", np.uint32), ("dist", np.uint32)])   # vc_mst_edge, 16 bytes
 
 
 class VcTiming(C.Structure):
@@ -404,6 +419,11 @@ def load_library():
     L.vc_knn_adjacency_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, u64, vp, vp, vp]
     L.vc_sharded_knn_adjacency.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, u64, vp, vp]
     L.vc_sharded_knn_adjacency_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, u64, vp, vp, vp]
+    for pre in ("vc_", "vc_sharded_"):
+        getattr(L, pre + "knn_mst").argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, u32, vp, vp, vp, vp]
+        getattr(L, pre + "knn_mst_dev").argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp]
+        getattr(L, pre + "mst_cut").argtypes = [vp, vp, u64, u32, vp, vp]
+        getattr(L, pre + "mst_cut_dev").argtypes = [vp, vp, u64, u32, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -868,6 +888,50 @@ def _knn_adjacency_dev(self, fn, d_rows, d_counts, k, kk, flags, max_dist, d_adj
     rc = self._check(fn(self._h, d_rows, d_counts, k, kk, flags, max_dist, d_adj, adj_cap, d_offsets, C.byref(st) if with_stats else None, stream),
                      ok=(VC_OK, VC_ERR_CAPACITY))
     return rc, st.as_dict() if with_stats else None
+
+
+def _knn_mst(self, fn, rows, counts, kk, flags, max_dist, weight_kind, min_pts, with_labels, with_hist):
+    """shared by Engine.knn_mst and ShardedEngine.knn_mst: (edges MST_EDGE [M], labels uint32 [N] | None, hist uint64 [bits + 1] | None,
+    stats dict)"""
+    n = len(self)
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    if rows.ndim != 2 or rows.shape[0] != n:
+        raise VcError(VC_ERR_INVALID, "rows must be the [N, k] graph of knn_graph over the whole store")
+    k = rows.shape[1]
+    if counts is not None:
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        if counts.shape[0] != n:
+            raise VcError(VC_ERR_INVALID, "counts must have one word per resident record")
+    edges = np.zeros(max(n - 1, 1), dtype=MST_EDGE)
+    labels = np.empty(n, dtype=np.uint32) if with_labels else None
+    hist = np.zeros(self.bits + 1, dtype=np.uint64) if with_hist else None
+    keep = rows if n else np.zeros(1, dtype=np.uint64)
+    st = VcKnnMstStats()
+    self._check(fn(self._h, _p(keep), _p(counts) if counts is not None and n else None, k, kk, flags, max_dist, weight_kind, min_pts, _p(edges),
+                   _p(labels) if with_labels and n else None, _p(hist) if with_hist else None, C.byref(st)))
+    return edges[:int(st.n_tree)].copy(), labels, hist, st.as_dict()
+
+
+def _knn_mst_dev(self, fn, d_rows, d_counts, k, kk, flags, max_dist, weight_kind, min_pts, d_edges, d_labels, d_hist, with_stats, stream):
+    st = VcKnnMstStats()
+    self._check(fn(self._h, d_rows, d_counts, k, kk, flags, max_dist, weight_kind, min_pts, d_edges, d_labels, d_hist, C.byref(st) if with_stats else None, stream))
+    return st.as_dict() if with_stats else None
+
+
+def _mst_cut(self, fn, edges, max_weight):
+    """shared by Engine.mst_cut and ShardedEngine.mst_cut: (labels uint32 [N], n_clusters)"""
+    n = len(self)
+    edges = np.ascontiguousarray(edges, dtype=MST_EDGE).reshape(-1)
+    labels = np.empty(n, dtype=np.uint32)
+    count = C.c_uint64(0)
+    self._check(fn(self._h, _p(edges) if len(edges) else None, len(edges), max_weight, _p(labels) if n else _p(np.zeros(1, dtype=np.uint32)), C.byref(count)))
+    return labels, int(count.value)
+
+
+def _mst_cut_dev(self, fn, d_edges, n_edges, max_weight, d_labels, stream):
+    count = C.c_uint64(0)
+    self._check(fn(self._h, d_edges, n_edges, max_weight, d_labels, C.byref(count), stream))
+    return int(count.value)
 
 
 def _retain(self, fn, sel, kind, with_map):
@@ -1357,6 +1421,30 @@ class Engine:
         is the sizing call)."""
         return _knn_adjacency_dev(self, self._L.vc_knn_adjacency_dev, d_rows, d_counts, k, kk, flags, max_dist, d_adj, adj_cap, d_offsets, with_stats, stream)
 
+    def knn_mst(self, rows, counts, kk, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, weight_kind=MST_DISTANCE, min_pts=1, with_labels=True, with_hist=True):
+        """vc_knn_mst: the minimum spanning forest, in Kruskal order, of the mutual (KNN_MUTUAL) or symmetrised (KNN_EITHER) graph of a
+        graph knn_graph built over the whole store (rows [N, k], counts [N] or None); "lists" is cluster_knn's.  weight_kind
+        MST_DISTANCE weighs an edge by its distance, MST_REACHABILITY by max(distance, the two core distances at min_pts).  Returns
+        (edges MST_EDGE [M] ascending in (weight, a, dist, b), labels [N] | None, hist [bits + 1] | None, stats dict of n_edges,
+        n_graph_edges, n_tree, n_clusters, total_weight, max_weight, n_rounds)."""
+        return _knn_mst(self, self._L.vc_knn_mst, rows, counts, kk, flags, max_dist, weight_kind, min_pts, with_labels, with_hist)
+
+    def knn_mst_dev(self, d_rows, d_counts, k, kk, d_edges, d_labels=None, d_hist=None, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, weight_kind=MST_DISTANCE,
+                    min_pts=1, with_stats=True, stream=None):
+        """vc_knn_mst_dev: raw device addresses; d_edges has room for max(N, 1) - 1 vc_mst_edge; nothing is searched, the host
+        waits once per Boruvka round and once at the end.  Returns the stats dict (None without with_stats)."""
+        return _knn_mst_dev(self, self._L.vc_knn_mst_dev, d_rows, d_counts, k, kk, flags, max_dist, weight_kind, min_pts, d_edges, d_labels, d_hist, with_stats,
+                            stream)
+
+    def mst_cut(self, edges, max_weight):
+        """vc_mst_cut: the components of the store under the edges (MST_EDGE records, any order) of weight <= max_weight.  Returns
+        (labels [N] -- the smallest id of each component --, n_clusters)."""
+        return _mst_cut(self, self._L.vc_mst_cut, edges, max_weight)
+
+    def mst_cut_dev(self, d_edges, n_edges, max_weight, d_labels, stream=None):
+        """vc_mst_cut_dev: raw device addresses; the host waits once.  Returns n_clusters."""
+        return _mst_cut_dev(self, self._L.vc_mst_cut_dev, d_edges, n_edges, max_weight, d_labels, stream)
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -1764,6 +1852,30 @@ class ShardedEngine:
         (rc, stats dict | None) as Engine.knn_adjacency_dev."""
         return _knn_adjacency_dev(self, self._L.vc_sharded_knn_adjacency_dev, d_rows, d_counts, k, kk, flags, max_dist, d_adj, adj_cap, d_offsets, with_stats,
                                   stream)
+
+    def knn_mst(self, rows, counts, kk, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, weight_kind=MST_DISTANCE, min_pts=1, with_labels=True, with_hist=True):
+        """vc_sharded_knn_mst: the minimum spanning forest, in Kruskal order, of the mutual (KNN_MUTUAL) or symmetrised (KNN_EITHER) graph of a
+        graph knn_graph built over the whole store (rows [N, k], counts [N] or None); "lists" is cluster_knn's.  weight_kind
+        MST_DISTANCE weighs an edge by its distance, MST_REACHABILITY by max(distance, the two core distances at min_pts).  Returns
+        (edges MST_EDGE [M] ascending in (weight, a, dist, b), labels [N] | None, hist [bits + 1] | None, stats dict of n_edges,
+        n_graph_edges, n_tree, n_clusters, total_weight, max_weight, n_rounds)."""
+        return _knn_mst(self, self._L.vc_sharded_knn_mst, rows, counts, kk, flags, max_dist, weight_kind, min_pts, with_labels, with_hist)
+
+    def knn_mst_dev(self, d_rows, d_counts, k, kk, d_edges, d_labels=None, d_hist=None, flags=KNN_MUTUAL, max_dist=0xFFFFFFFF, weight_kind=MST_DISTANCE,
+                    min_pts=1, with_stats=True, stream=None):
+        """vc_sharded_knn_mst_dev: raw device addresses on the root device; d_edges has room for max(N, 1) - 1 vc_mst_edge; nothing is searched, the host
+        waits once per Boruvka round and once at the end.  Returns the stats dict (None without with_stats)."""
+        return _knn_mst_dev(self, self._L.vc_sharded_knn_mst_dev, d_rows, d_counts, k, kk, flags, max_dist, weight_kind, min_pts, d_edges, d_labels, d_hist, with_stats,
+                            stream)
+
+    def mst_cut(self, edges, max_weight):
+        """vc_sharded_mst_cut: the components of the store under the edges (MST_EDGE records, any order) of weight <= max_weight.  Returns
+        (labels [N] -- the smallest id of each component --, n_clusters)."""
+        return _mst_cut(self, self._L.vc_sharded_mst_cut, edges, max_weight)
+
+    def mst_cut_dev(self, d_edges, n_edges, max_weight, d_labels, stream=None):
+        """vc_sharded_mst_cut_dev: raw device addresses on the root device; the host waits once.  Returns n_clusters."""
+        return _mst_cut_dev(self, self._L.vc_sharded_mst_cut_dev, d_edges, n_edges, max_weight, d_labels, stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

@@ -196,6 +196,14 @@ class Backend {
   // counts and stats may be null
   virtual int knn_adjacency(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint64_t* adj,
                             uint64_t adj_cap, uint64_t* offsets, vc_knn_adjacency_stats* stats) = 0;
+  // the minimum spanning forest of that graph in Kruskal order (vc_knn_mst / vc_sharded_knn_mst): flags VC_KNN_MUTUAL / VC_KNN_EITHER,
+  // weight_kind VC_MST_DISTANCE (min_pts 1) or VC_MST_REACHABILITY (min_pts in 1 .. k + 1); edges has room for max(N, 1) - 1 entries and
+  // gets stats->n_tree of them, ascending in (weight, a, dist, b); labels [N], hist [bits + 1], counts and stats may be null
+  virtual int knn_mst(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t weight_kind,
+                      uint32_t min_pts, vc_mst_edge* edges, uint32_t* labels, uint64_t* hist, vc_knn_mst_stats* stats) = 0;
+  // the components of the store under the edges of weight <= max_weight, smallest-id labels (vc_mst_cut / vc_sharded_mst_cut); any
+  // edge list, sorted or not; n_clusters may be null
+  virtual int mst_cut(const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels, uint64_t* n_clusters) = 0;
   // records taken out of the store and its index, the survivors renumbered in order (vc_retain / vc_sharded_retain; the reference has
   // no delete: this stands for build_hash_tables.cc run again over the code file without them).  kind VC_RETAIN_MASK / VC_RETAIN_ROOTS
   virtual int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) = 0;
@@ -313,6 +321,13 @@ class Engine : public Backend {
   int knn_adjacency(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint64_t* adj,
                     uint64_t adj_cap, uint64_t* offsets, vc_knn_adjacency_stats* stats) override {
     return vc_knn_adjacency(h_, rows, counts, k, kk, flags, max_dist, adj, adj_cap, offsets, stats);
+  }
+  int knn_mst(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t weight_kind,
+              uint32_t min_pts, vc_mst_edge* edges, uint32_t* labels, uint64_t* hist, vc_knn_mst_stats* stats) override {
+    return vc_knn_mst(h_, rows, counts, k, kk, flags, max_dist, weight_kind, min_pts, edges, labels, hist, stats);
+  }
+  int mst_cut(const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels, uint64_t* n_clusters) override {
+    return vc_mst_cut(h_, edges, n_edges, max_weight, labels, n_clusters);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_retain(h_, sel, kind, new_ids, n_kept); }
  private:
@@ -458,6 +473,13 @@ class ShardedEngine : public Backend {
   int knn_adjacency(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint64_t* adj,
                     uint64_t adj_cap, uint64_t* offsets, vc_knn_adjacency_stats* stats) override {
     return vc_sharded_knn_adjacency(h_, rows, counts, k, kk, flags, max_dist, adj, adj_cap, offsets, stats);
+  }
+  int knn_mst(const uint64_t* rows, const uint32_t* counts, uint32_t k, uint32_t kk, uint32_t flags, uint32_t max_dist, uint32_t weight_kind,
+              uint32_t min_pts, vc_mst_edge* edges, uint32_t* labels, uint64_t* hist, vc_knn_mst_stats* stats) override {
+    return vc_sharded_knn_mst(h_, rows, counts, k, kk, flags, max_dist, weight_kind, min_pts, edges, labels, hist, stats);
+  }
+  int mst_cut(const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels, uint64_t* n_clusters) override {
+    return vc_sharded_mst_cut(h_, edges, n_edges, max_weight, labels, n_clusters);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_sharded_retain(h_, sel, kind, new_ids, n_kept); }
  private:
