@@ -1394,6 +1394,97 @@ int vc_mst_cut_dev(vc_engine* e, const vc_mst_edge* d_edges, uint64_t n_edges, u
 int vc_mst_cut(vc_engine* e, const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels,
                uint64_t* n_clusters);
 
+/* ---- the weighted label vote of a segment: the k-NN classifier vc_knn_vote* and label propagation vc_label_propagate* ----------------------
+ * Every call above groups records without supervision.  These two use labels the caller already has: "which album, class or tag does
+ * this picture belong to?" is the majority label among its k nearest records (vc_knn_vote*, over the rows of any search or of a
+ * graph, which never leave HBM), and a few thousand hand-tagged records tag the rest of the store along the adjacency of
+ * vc_knn_adjacency* (vc_label_propagate*); started from labels[i] = id_base + i the second call is community detection by label
+ * propagation.  Both are exact integers and a function of their inputs only.
+ * THE VOTE RULE, shared by both calls.  A SEGMENT is an ordered list of packed entries dist << 32 | id, ascending in the packed word.
+ * labels holds one uint32_t per resident record, indexed by id - id_base; VC_VOTE_NONE means "unlabelled": such an entry does not
+ * vote.  The weight of a voting entry at distance d is 1 under VC_VOTE_COUNT and bits + 1 - d under VC_VOTE_CLOSENESS (at least 1,
+ * the nearest weighs most).  tally[l] is the sum of the weights of the entries labelled l, total the sum of all tallies.  THE WINNER
+ * is the label first in this strict order: (1) the larger tally; (2) then the segment's CURRENT label -- only vc_label_propagate*
+ * has one: the standard damping of label propagation; (3) then the label whose first occurrence in the segment comes earliest, so
+ * among tied labels the nearest neighbour's wins, ties in distance going to the smaller id, which is the segment order itself.  A
+ * segment with no voting entry has winner VC_VOTE_NONE, votes = 0 and total = 0.  The order is strict, so every output word is a
+ * function of the segment and the labels: it does not depend on lane or block order, on earlier calls on the handle or on the shard
+ * layout.  A row is DECIDED BY RULE 3 when several labels hold the largest tally and the current label is none of them.
+ * vc_knn_vote_dev.  d_rows (n_rows * k) holds ANY rows whose ids are resident: a graph of vc_knn_graph* (n_rows = N) or the rows of
+ * vc_search_knn_dev and its distinct, filtered, scoped and ids forms for a batch of queries.  d_counts (n_rows) may be NULL: every row
+ * then holds min(k, N) entries.  Row r's segment is its first min(kk, count_r) entries at distance <= max_dist.  kk lies in 1 .. k, k
+ * in 1 .. VC_MAX_K.  An entry equal to a record's own id is an ordinary entry.  d_labels has N words.  d_out_label (n_rows) gets the
+ * winners; d_out_votes and d_out_total (n_rows each, may be NULL) the winner's tally and the total: votes / total is the confidence,
+ * and both stay integers.  stats (HOST memory in both forms, may be NULL): n_voted rows with a winner, n_unlabelled rows without one,
+ * n_ties rows decided by rule 3, n_entries voting entries.
+ * vc_label_propagate_dev.  d_offsets (N + 1 words) and d_adj are what vc_knn_adjacency* wrote for this store, with any flag;
+ * n_entries must equal d_offsets[N].  Any CSR with non-decreasing offsets from 0, ascending segments and resident ids qualifies.
+ * ROUNDS: L_0 = labels_in.  In round t every record i takes the winner of segment i under L_{t-1}, with current label L_{t-1}[i]; if
+ * the segment has no voting entry, i keeps L_{t-1}[i].  With VC_LP_CLAMP_SEEDS in flags every record with labels_in[i] !=
+ * VC_VOTE_NONE keeps labels_in[i] in every round: the semi-supervised form.  Without the flag and with labels_in[i] = id_base + i the
+ * call is community detection by label propagation.  Rounds are double-buffered: no record ever reads a label written in the same
+ * round, so the result does not depend on execution order.  The call stops after the first round that changes no label, or after
+ * max_iters rounds (1 .. VC_LP_MAX_ITERS); synchronous propagation can oscillate, so the stats say which stop happened.
+ * d_labels_out (N) holds L_T.  d_votes and d_total (N each, may be NULL) are the winner's tally and the total of the LAST round run,
+ * that is under L_{T-1}; they are also written for clamped seeds, so a seed that its neighbourhood outvotes is visible.  stats:
+ * n_iters = T, converged (0 or 1), n_changed_last, n_labelled the records with a label other than VC_VOTE_NONE in L_T, n_ties_last the
+ * records whose vote in the last round was decided by rule 3 (clamped seeds included).  The labels feed vc_group_summary*, vc_retain*
+ * and the distinct, filtered and scoped searches unchanged whenever they are resident ids, which the community form guarantees; the
+ * caller's class values of the semi-supervised form are taken by the sel and scope consumers only.
+ * HOW.  One tally routine serves both views.  Up to 64 entries a team of P lanes (P the power of two at or above the length) holds
+ * the entries, `length` broadcast steps give every lane the tally of its label, and a butterfly max over the key (tally, is-current,
+ * inverted position) of the first occurrences picks the winner: no LDS, no atomics.  Up to 8192 entries a wave or a block fills an
+ * open-addressing table of (label, tally) slots in LDS, at most half full, and a second walk in order max-reduces the key.  Above
+ * that -- CSR hubs -- the table lies in the handle's scratch and 64 blocks stride over the segment; there is no limit on a segment's
+ * length other than the 32-bit tally.  vc_label_propagate* first runs a plan pass: offsets and entries validated, the records listed
+ * per degree bin by one scan (no atomic cursor), the long tables laid out, ONE wait; then a round is one launch per non-empty bin.
+ * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle, rows, labels or out_label, k outside
+ * 1 .. VC_MAX_K, kk outside 1 .. k, an unknown weight_kind; vc_label_propagate*: a null handle, offsets, adj (with n_entries > 0),
+ * labels_in or labels_out, an unknown weight_kind or flag, max_iters outside 1 .. VC_LP_MAX_ITERS.  Found ON THE DEVICE by
+ * vc_knn_vote*, VC_ERR_INVALID through vc_cluster_knn*'s protocol (THE OUTPUTS ARE THEN UNDEFINED, everything stays in bounds): a
+ * count above k, an id outside the store, under VC_VOTE_CLOSENESS a voting entry with d > bits.  Found on the device by
+ * vc_label_propagate* with NO OUTPUT WORD WRITTEN (the plan waits before the first round): d_offsets[0] != 0, decreasing offsets,
+ * d_offsets[N] != n_entries, an id outside the store, d > bits under VC_VOTE_CLOSENESS, a segment so long that length * (bits + 1)
+ * does not fit 32 bits.  n_rows == 0 and N == 0 give VC_OK and zero stats.
+ * WAITS: vc_knn_vote*: one.  vc_label_propagate*: one for the plan, then one small read-back per round.  Over a sharded store every
+ * pointer of the device forms lives on the ROOT device and no shard is touched; the result equals the single engine's word for word.
+ * NOT OFFERED: caller-given edge weights such as vc_cluster_snn*'s d_shared; asynchronous propagation; an incremental form after
+ * vc_add_codes or vc_retain*; more than 64 rounds per call -- a caller continues by passing labels_out back in. */
+#define VC_VOTE_NONE 0xFFFFFFFFu
+#define VC_VOTE_COUNT 0u
+#define VC_VOTE_CLOSENESS 1u
+#define VC_LP_CLAMP_SEEDS 1u
+#define VC_LP_MAX_ITERS 64u
+typedef struct vc_knn_vote_stats {   /* 32 bytes */
+  uint64_t n_voted;        /* rows with a winner */
+  uint64_t n_unlabelled;   /* rows without a winner */
+  uint64_t n_ties;         /* rows whose winner was decided by rule 3 */
+  uint64_t n_entries;      /* voting entries */
+} vc_knn_vote_stats;
+typedef struct vc_label_propagate_stats {   /* 32 bytes */
+  uint32_t n_iters;          /* rounds run */
+  uint32_t converged;        /* 1: the last round changed no label */
+  uint64_t n_changed_last;   /* labels the last round changed */
+  uint64_t n_labelled;       /* records with a label other than VC_VOTE_NONE in L_T */
+  uint64_t n_ties_last;      /* records whose vote in the last round was decided by rule 3 */
+} vc_label_propagate_stats;
+int vc_knn_vote_dev(vc_engine* e, const uint64_t* d_rows, const uint32_t* d_counts, uint64_t n_rows, uint32_t k, uint32_t kk,
+                    uint32_t max_dist, const uint32_t* d_labels, uint32_t weight_kind, uint32_t* d_out_label, uint32_t* d_out_votes,
+                    uint32_t* d_out_total, vc_knn_vote_stats* stats, void* stream);
+/* The same for host pointers: rows, counts and labels are staged ON EVERY CALL; the three outputs (votes and total may be NULL) come
+ * home; waits for them. */
+int vc_knn_vote(vc_engine* e, const uint64_t* rows, const uint32_t* counts, uint64_t n_rows, uint32_t k, uint32_t kk, uint32_t max_dist,
+                const uint32_t* labels, uint32_t weight_kind, uint32_t* out_label, uint32_t* out_votes, uint32_t* out_total,
+                vc_knn_vote_stats* stats);
+int vc_label_propagate_dev(vc_engine* e, const uint64_t* d_offsets, const uint64_t* d_adj, uint64_t n_entries, const uint32_t* d_labels_in,
+                           uint32_t weight_kind, uint32_t flags, uint32_t max_iters, uint32_t* d_labels_out, uint32_t* d_votes,
+                           uint32_t* d_total, vc_label_propagate_stats* stats, void* stream);
+/* The same for host pointers: offsets, adj and labels_in are staged on every call; labels_out, votes and total (both may be NULL)
+ * come home; waits for them. */
+int vc_label_propagate(vc_engine* e, const uint64_t* offsets, const uint64_t* adj, uint64_t n_entries, const uint32_t* labels_in,
+                       uint32_t weight_kind, uint32_t flags, uint32_t max_iters, uint32_t* labels_out, uint32_t* votes, uint32_t* total,
+                       vc_label_propagate_stats* stats);
+
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
  * seconds); the affected queries kept d_counts[i] == UINT32_MAX.  0 in normal operation.  Synchronises the stream.
@@ -1719,6 +1810,20 @@ int vc_sharded_mst_cut_dev(vc_sharded* h, const vc_mst_edge* d_edges, uint64_t n
                            uint64_t* n_clusters, void* stream);
 int vc_sharded_mst_cut(vc_sharded* h, const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels,
                        uint64_t* n_clusters);
+/* The label vote and label propagation: as vc_knn_vote_dev / vc_knn_vote / vc_label_propagate_dev / vc_label_propagate; every pointer of
+ * the device forms lives on the ROOT device, no shard is touched, and the words equal the single engine's. */
+int vc_sharded_knn_vote_dev(vc_sharded* h, const uint64_t* d_rows, const uint32_t* d_counts, uint64_t n_rows, uint32_t k, uint32_t kk,
+                            uint32_t max_dist, const uint32_t* d_labels, uint32_t weight_kind, uint32_t* d_out_label, uint32_t* d_out_votes,
+                            uint32_t* d_out_total, vc_knn_vote_stats* stats, void* stream);
+int vc_sharded_knn_vote(vc_sharded* h, const uint64_t* rows, const uint32_t* counts, uint64_t n_rows, uint32_t k, uint32_t kk, uint32_t max_dist,
+                        const uint32_t* labels, uint32_t weight_kind, uint32_t* out_label, uint32_t* out_votes, uint32_t* out_total,
+                        vc_knn_vote_stats* stats);
+int vc_sharded_label_propagate_dev(vc_sharded* h, const uint64_t* d_offsets, const uint64_t* d_adj, uint64_t n_entries, const uint32_t* d_labels_in,
+                                   uint32_t weight_kind, uint32_t flags, uint32_t max_iters, uint32_t* d_labels_out, uint32_t* d_votes,
+                                   uint32_t* d_total, vc_label_propagate_stats* stats, void* stream);
+int vc_sharded_label_propagate(vc_sharded* h, const uint64_t* offsets, const uint64_t* adj, uint64_t n_entries, const uint32_t* labels_in,
+                               uint32_t weight_kind, uint32_t flags, uint32_t max_iters, uint32_t* labels_out, uint32_t* votes, uint32_t* total,
+                               vc_label_propagate_stats* stats);
 
 /* Stream of the host-pointer calls (default VC_STREAM_OWN). */
 int vc_set_stream(vc_engine* e, void* stream);

@@ -19,6 +19,7 @@
 #include "vc_snn_plan.hpp"
 #include "vc_knn_adjacency_plan.hpp"
 #include "vc_knn_mst_plan.hpp"
+#include "vc_vote_plan.hpp"
 #include "vc_knn_graph_update_plan.hpp"
 #include "vc_mih.hpp"
 #include "vc_retain.hpp"
@@ -1709,6 +1710,21 @@ static int check_mst_cut_args(vc_engine* e, const vc_mst_edge* edges, uint64_t n
   if (!e || !labels || (!edges && n_edges)) return VC_ERR_INVALID;
   return VC_OK;
 }
+static int check_knn_vote_args(vc_engine* e, const uint64_t* rows, uint32_t k, uint32_t kk, const uint32_t* labels, uint32_t weight_kind, const uint32_t* out_label) {
+  if (!e || !rows || !labels || !out_label) return VC_ERR_INVALID;
+  if (!vc_vote_k_ok(k, VC_MAX_K)) return fail(e, VC_ERR_INVALID, "label vote: k must be in 1..%u", VC_MAX_K);
+  if (!vc_vote_kk_ok(k, kk)) return fail(e, VC_ERR_INVALID, "label vote: kk must be in 1..k");
+  if (!vc_vote_kind_ok(weight_kind)) return fail(e, VC_ERR_INVALID, "label vote: unknown weight_kind %u", weight_kind);
+  return VC_OK;
+}
+static int check_label_propagate_args(vc_engine* e, const uint64_t* offsets, const uint64_t* adj, uint64_t n_entries, const uint32_t* labels_in,
+                                      uint32_t weight_kind, uint32_t flags, uint32_t max_iters, const uint32_t* labels_out) {
+  if (!e || !offsets || (!adj && n_entries) || !labels_in || !labels_out) return VC_ERR_INVALID;
+  if (!vc_vote_kind_ok(weight_kind)) return fail(e, VC_ERR_INVALID, "label propagation: unknown weight_kind %u", weight_kind);
+  if (!vc_vote_lp_flags_ok(flags)) return fail(e, VC_ERR_INVALID, "label propagation: unknown flags 0x%x", flags);
+  if (!vc_vote_iters_ok(max_iters)) return fail(e, VC_ERR_INVALID, "label propagation: max_iters must be in 1..%u", VC_LP_MAX_ITERS);
+  return VC_OK;
+}
 // a built graph after vc_add_codes (vc_knn_graph_update.hip): vc_knn_graph*'s checks with n_old as the first position
 static int check_kgupd_args(vc_engine* e, uint32_t k, uint32_t mode, uint64_t n_old, uint32_t k_first, const uint64_t* rows) {
   uint64_t n_rows = 0;
@@ -1953,6 +1969,49 @@ int vc_mst_cut(vc_engine* e, const vc_mst_edge* edges, uint64_t n_edges, uint32_
   if (rc) return rc;
   return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
     return vc_mst_cut_run_host(store_view(e, VC_MODE_LINEAR), edges, n_edges, max_weight, labels, n_clusters, s, err);
+  });
+}
+
+int vc_knn_vote_dev(vc_engine* e, const uint64_t* d_rows, const uint32_t* d_counts, uint64_t n_rows, uint32_t k, uint32_t kk, uint32_t max_dist,
+                    const uint32_t* d_labels, uint32_t weight_kind, uint32_t* d_out_label, uint32_t* d_out_votes, uint32_t* d_out_total, vc_knn_vote_stats* stats,
+                    void* stream) {
+  const int rc = check_knn_vote_args(e, d_rows, k, kk, d_labels, weight_kind, d_out_label);
+  if (rc) return rc;
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_knn_vote_run(store_view(e, VC_MODE_LINEAR), VcVoteArgs{d_rows, d_counts, n_rows, k, kk, max_dist, d_labels, weight_kind, d_out_label, d_out_votes, d_out_total},
+                           stats, s, err);
+  });
+}
+
+int vc_knn_vote(vc_engine* e, const uint64_t* rows, const uint32_t* counts, uint64_t n_rows, uint32_t k, uint32_t kk, uint32_t max_dist, const uint32_t* labels,
+                uint32_t weight_kind, uint32_t* out_label, uint32_t* out_votes, uint32_t* out_total, vc_knn_vote_stats* stats) {
+  const int rc = check_knn_vote_args(e, rows, k, kk, labels, weight_kind, out_label);
+  if (rc) return rc;
+  return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_knn_vote_run_host(store_view(e, VC_MODE_LINEAR), VcVoteArgs{nullptr, nullptr, n_rows, k, kk, max_dist, nullptr, weight_kind, nullptr, nullptr, nullptr}, rows,
+                                counts, labels, out_label, out_votes, out_total, stats, s, err);
+  });
+}
+
+int vc_label_propagate_dev(vc_engine* e, const uint64_t* d_offsets, const uint64_t* d_adj, uint64_t n_entries, const uint32_t* d_labels_in, uint32_t weight_kind,
+                           uint32_t flags, uint32_t max_iters, uint32_t* d_labels_out, uint32_t* d_votes, uint32_t* d_total, vc_label_propagate_stats* stats,
+                           void* stream) {
+  const int rc = check_label_propagate_args(e, d_offsets, d_adj, n_entries, d_labels_in, weight_kind, flags, max_iters, d_labels_out);
+  if (rc) return rc;
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_label_propagate_run(store_view(e, VC_MODE_LINEAR),
+                                  VcLabelPropagateArgs{d_offsets, d_adj, n_entries, d_labels_in, weight_kind, flags, max_iters, d_labels_out, d_votes, d_total}, stats, s, err);
+  });
+}
+
+int vc_label_propagate(vc_engine* e, const uint64_t* offsets, const uint64_t* adj, uint64_t n_entries, const uint32_t* labels_in, uint32_t weight_kind, uint32_t flags,
+                       uint32_t max_iters, uint32_t* labels_out, uint32_t* votes, uint32_t* total, vc_label_propagate_stats* stats) {
+  const int rc = check_label_propagate_args(e, offsets, adj, n_entries, labels_in, weight_kind, flags, max_iters, labels_out);
+  if (rc) return rc;
+  return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_label_propagate_run_host(store_view(e, VC_MODE_LINEAR),
+                                       VcLabelPropagateArgs{nullptr, nullptr, n_entries, nullptr, weight_kind, flags, max_iters, nullptr, nullptr, nullptr}, offsets, adj,
+                                       labels_in, labels_out, votes, total, stats, s, err);
   });
 }
 

@@ -248,6 +248,9 @@ enum VcScratch {
   // the graph's spanning forest (vc_knn_mst.hip): the statistics block; best, the forest and the snapshot; the two live buffers; the two
   // key and value buffers of the picked list; the sort's work; the host forms' staging (VcMstStage, VcMstCutStage)
   VC_MST_STAT, VC_MST_FOREST, VC_MST_LIVE, VC_MST_PICK, VC_MST_SORT, VC_MST_STAGE,
+  // the label vote and label propagation (vc_vote.hip): the plan's and the rounds' statistics blocks; the list, the two label buffers
+  // and the bin counts; the scan's work; the long segments' table offsets; their tables; the host forms' staging (VcVoteStage, VcVoteLpStage)
+  VC_VOTE_STAT, VC_VOTE_PLAN, VC_VOTE_SCAN, VC_VOTE_LONG_OFF, VC_VOTE_LONG, VC_VOTE_STAGE,
   VC_SCRATCH_BUFS
 };
 // buffer `which` of the handle's table, at least `bytes` large, on the current device; null when it cannot be had (the handle keeps the text)
@@ -811,6 +814,44 @@ int vc_mst_cut_run(const VcStoreView& v, const vc_mst_edge* d_edges, uint64_t n_
                    std::string* err);
 int vc_mst_cut_run_host(const VcStoreView& v, const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels, uint64_t* n_clusters, hipStream_t s,
                         std::string* err);
+// ---- vc_vote.hip: the weighted label tally of a segment -- the k-NN classifier over any rows (vc_knn_vote*, vc_sharded_knn_vote*) and
+// synchronous label propagation over a CSR graph (vc_label_propagate*, vc_sharded_label_propagate*).  One driver per call for both
+// handle kinds; the plan arithmetic -- the argument checks, the weight, the key, the team shapes, the sizes -- is vc_vote_plan.hpp.
+struct VcVoteArgs {
+  const uint64_t* d_rows;            // [n_rows][k]: any rows whose ids are resident
+  const uint32_t* d_counts;          // [n_rows], nullable: then every row holds vc_vote_row_count(n, k) entries
+  uint64_t n_rows;
+  uint32_t k, kk, max_dist;          // checked by the caller: vc_vote_k_ok, vc_vote_kk_ok
+  const uint32_t* d_labels;          // [n]
+  uint32_t weight_kind;              // vc_vote_kind_ok
+  uint32_t* d_out_label;             // [n_rows]
+  uint32_t* d_out_votes;             // [n_rows], nullable
+  uint32_t* d_out_total;             // [n_rows], nullable
+};
+// the whole call on s: one tally launch shaped by kk, ONE wait (the counters and the error word: VC_ERR_INVALID for a count above k, an
+// id outside the store, a voting entry beyond the code width under CLOSENESS).  Only n, id_base, W and alloc of the view are used
+int vc_knn_vote_run(const VcStoreView& v, const VcVoteArgs& a, vc_knn_vote_stats* stats, hipStream_t s, std::string* err);
+// the same for host pointers (a's pointers are ignored): rows, counts and labels staged; the outputs (votes and total nullable) come
+// home, waited for
+int vc_knn_vote_run_host(const VcStoreView& v, VcVoteArgs a, const uint64_t* rows, const uint32_t* counts, const uint32_t* labels, uint32_t* out_label,
+                         uint32_t* out_votes, uint32_t* out_total, vc_knn_vote_stats* stats, hipStream_t s, std::string* err);
+struct VcLabelPropagateArgs {
+  const uint64_t* d_offsets;         // [n + 1]
+  const uint64_t* d_adj;             // [n_entries]
+  uint64_t n_entries;
+  const uint32_t* d_labels_in;       // [n]
+  uint32_t weight_kind, flags, max_iters;   // checked by the caller: vc_vote_kind_ok, vc_vote_lp_flags_ok, vc_vote_iters_ok
+  uint32_t* d_labels_out;            // [n]
+  uint32_t* d_votes;                 // [n], nullable
+  uint32_t* d_total;                 // [n], nullable
+};
+// the whole call on s: the plan (checks, bins, long tables; one wait, VC_ERR_INVALID before any output word is written), then the
+// rounds, one read-back each; the copy into d_labels_out is enqueued behind the last one
+int vc_label_propagate_run(const VcStoreView& v, const VcLabelPropagateArgs& a, vc_label_propagate_stats* stats, hipStream_t s, std::string* err);
+// the same for host pointers (a's pointers are ignored): offsets, adj and labels_in staged; labels_out, votes and totals (both
+// nullable) come home, waited for
+int vc_label_propagate_run_host(const VcStoreView& v, VcLabelPropagateArgs a, const uint64_t* offsets, const uint64_t* adj, const uint32_t* labels_in,
+                                uint32_t* labels_out, uint32_t* votes, uint32_t* totals, vc_label_propagate_stats* stats, hipStream_t s, std::string* err);
 // ---- vc_retain.hip: removal of records (vc_retain*).  The keep set is VcKeepSet (vc_retain.hpp); nothing here waits.
 struct VcKeepSet;
 #define VC_RETAIN_FROM 2u   // internal kind: the records from `first_kept` on survive, sel is not read (a shard giving away a prefix of its records)

@@ -44,6 +44,7 @@
 #include "vc_snn_plan.hpp"
 #include "vc_knn_adjacency_plan.hpp"
 #include "vc_knn_mst_plan.hpp"
+#include "vc_vote_plan.hpp"
 #include "vc_knn_graph_update_plan.hpp"
 #include "vc_mih.hpp"
 #include "vc_seed_plan.hpp"
@@ -2733,6 +2734,22 @@ static int check_sharded_knn_mst_args(vc_sharded* h, const uint64_t* rows, uint3
   if (!vc_mst_items_ok(h->n, kk)) return sfail(h, VC_ERR_INVALID, "k-NN spanning forest: N * kk must not exceed 2^31 - 1");
   return VC_OK;
 }
+static int check_sharded_knn_vote_args(vc_sharded* h, const uint64_t* rows, uint32_t k, uint32_t kk, const uint32_t* labels, uint32_t weight_kind,
+                                       const uint32_t* out_label) {
+  if (!h || !rows || !labels || !out_label) return VC_ERR_INVALID;
+  if (!vc_vote_k_ok(k, VC_MAX_K)) return sfail(h, VC_ERR_INVALID, "label vote: k must be in 1..%u", VC_MAX_K);
+  if (!vc_vote_kk_ok(k, kk)) return sfail(h, VC_ERR_INVALID, "label vote: kk must be in 1..k");
+  if (!vc_vote_kind_ok(weight_kind)) return sfail(h, VC_ERR_INVALID, "label vote: unknown weight_kind %u", weight_kind);
+  return VC_OK;
+}
+static int check_sharded_label_propagate_args(vc_sharded* h, const uint64_t* offsets, const uint64_t* adj, uint64_t n_entries, const uint32_t* labels_in,
+                                              uint32_t weight_kind, uint32_t flags, uint32_t max_iters, const uint32_t* labels_out) {
+  if (!h || !offsets || (!adj && n_entries) || !labels_in || !labels_out) return VC_ERR_INVALID;
+  if (!vc_vote_kind_ok(weight_kind)) return sfail(h, VC_ERR_INVALID, "label propagation: unknown weight_kind %u", weight_kind);
+  if (!vc_vote_lp_flags_ok(flags)) return sfail(h, VC_ERR_INVALID, "label propagation: unknown flags 0x%x", flags);
+  if (!vc_vote_iters_ok(max_iters)) return sfail(h, VC_ERR_INVALID, "label propagation: max_iters must be in 1..%u", VC_LP_MAX_ITERS);
+  return VC_OK;
+}
 // a built graph after vc_sharded_add_codes (vc_knn_graph_update.hip): the graph call's checks with n_old as the first position
 static int check_sharded_kgupd_args(vc_sharded* h, uint32_t k, uint32_t mode, uint64_t n_old, uint32_t k_first, const uint64_t* rows) {
   uint64_t n_rows = 0;
@@ -2970,6 +2987,49 @@ int vc_sharded_mst_cut(vc_sharded* h, const vc_mst_edge* edges, uint64_t n_edges
   if (!h || !labels || (!edges && n_edges)) return VC_ERR_INVALID;
   return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_mst_cut_run_host(v, edges, n_edges, max_weight, labels, n_clusters, S, err);
+  });
+}
+
+int vc_sharded_knn_vote_dev(vc_sharded* h, const uint64_t* d_rows, const uint32_t* d_counts, uint64_t n_rows, uint32_t k, uint32_t kk, uint32_t max_dist,
+                            const uint32_t* d_labels, uint32_t weight_kind, uint32_t* d_out_label, uint32_t* d_out_votes, uint32_t* d_out_total,
+                            vc_knn_vote_stats* stats, void* stream) {
+  const int rc = check_sharded_knn_vote_args(h, d_rows, k, kk, d_labels, weight_kind, d_out_label);
+  if (rc) return rc;
+  return sharded_store_call(h, VC_MODE_LINEAR, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t s, std::string* err) {
+    return vc_knn_vote_run(v, VcVoteArgs{d_rows, d_counts, n_rows, k, kk, max_dist, d_labels, weight_kind, d_out_label, d_out_votes, d_out_total},
+                           stats, s, err);
+  });
+}
+
+int vc_sharded_knn_vote(vc_sharded* h, const uint64_t* rows, const uint32_t* counts, uint64_t n_rows, uint32_t k, uint32_t kk, uint32_t max_dist, const uint32_t* labels,
+                        uint32_t weight_kind, uint32_t* out_label, uint32_t* out_votes, uint32_t* out_total, vc_knn_vote_stats* stats) {
+  const int rc = check_sharded_knn_vote_args(h, rows, k, kk, labels, weight_kind, out_label);
+  if (rc) return rc;
+  return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t s, std::string* err) {
+    return vc_knn_vote_run_host(v, VcVoteArgs{nullptr, nullptr, n_rows, k, kk, max_dist, nullptr, weight_kind, nullptr, nullptr, nullptr}, rows,
+                                counts, labels, out_label, out_votes, out_total, stats, s, err);
+  });
+}
+
+int vc_sharded_label_propagate_dev(vc_sharded* h, const uint64_t* d_offsets, const uint64_t* d_adj, uint64_t n_entries, const uint32_t* d_labels_in, uint32_t weight_kind,
+                                   uint32_t flags, uint32_t max_iters, uint32_t* d_labels_out, uint32_t* d_votes, uint32_t* d_total,
+                                   vc_label_propagate_stats* stats, void* stream) {
+  const int rc = check_sharded_label_propagate_args(h, d_offsets, d_adj, n_entries, d_labels_in, weight_kind, flags, max_iters, d_labels_out);
+  if (rc) return rc;
+  return sharded_store_call(h, VC_MODE_LINEAR, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t s, std::string* err) {
+    return vc_label_propagate_run(v,
+                                  VcLabelPropagateArgs{d_offsets, d_adj, n_entries, d_labels_in, weight_kind, flags, max_iters, d_labels_out, d_votes, d_total}, stats, s, err);
+  });
+}
+
+int vc_sharded_label_propagate(vc_sharded* h, const uint64_t* offsets, const uint64_t* adj, uint64_t n_entries, const uint32_t* labels_in, uint32_t weight_kind, uint32_t flags,
+                               uint32_t max_iters, uint32_t* labels_out, uint32_t* votes, uint32_t* total, vc_label_propagate_stats* stats) {
+  const int rc = check_sharded_label_propagate_args(h, offsets, adj, n_entries, labels_in, weight_kind, flags, max_iters, labels_out);
+  if (rc) return rc;
+  return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t s, std::string* err) {
+    return vc_label_propagate_run_host(v,
+                                       VcLabelPropagateArgs{nullptr, nullptr, n_entries, nullptr, weight_kind, flags, max_iters, nullptr, nullptr, nullptr}, offsets, adj,
+                                       labels_in, labels_out, votes, total, stats, s, err);
   });
 }
 

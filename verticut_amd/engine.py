@@ -63,9 +63,14 @@ EXPORTS = [
     "vc_knn_adjacency", "vc_knn_adjacency_dev", "vc_sharded_knn_adjacency", "vc_sharded_knn_adjacency_dev",
     "vc_knn_mst", "vc_knn_mst_dev", "vc_sharded_knn_mst", "vc_sharded_knn_mst_dev",
     "vc_mst_cut", "vc_mst_cut_dev", "vc_sharded_mst_cut", "vc_sharded_mst_cut_dev",
+    "vc_knn_vote", "vc_knn_vote_dev", "vc_sharded_knn_vote", "vc_sharded_knn_vote_dev",
+    "vc_label_propagate", "vc_label_propagate_dev", "vc_sharded_label_propagate", "vc_sharded_label_propagate_dev",
 ]
 KNN_MUTUAL, KNN_EITHER = 0, 1   # VC_KNN_*: cluster_knn joins i and j iff each lists the other / iff one lists the other
 KNN_REVERSE = 2                 # VC_KNN_REVERSE: knn_adjacency only -- segment j holds every record that lists j
+VOTE_NONE = 0xFFFFFFFF               # VC_VOTE_NONE: the label word of an unlabelled record; such an entry does not vote
+VOTE_COUNT, VOTE_CLOSENESS = 0, 1    # VC_VOTE_*: a voting entry weighs 1 / bits + 1 - its distance
+LP_CLAMP_SEEDS, LP_MAX_ITERS = 1, 64   # VC_LP_*: label_propagate keeps every labelled record of labels_in fixed; the most rounds of a call
 MST_DISTANCE, MST_REACHABILITY = 0, 1   # VC_MST_*: knn_mst weighs an edge by its distance / by max(distance, the two core distances at min_pts)
 SNN_NONE, SNN_MAX_KK = 0xFFFFFFFF, 1024   # VC_SNN_NONE: the weight word of an entry that is not listed; VC_SNN_MAX_KK: the widest kk of cluster_snn
 FILTER_MASK, FILTER_ROOTS, FILTER_EQUAL, FILTER_NOT_EQUAL, FILTER_BITS = 0, 1, 2, 3, 4   # VC_FILTER_*: how search_knn_filtered reads `sel`
@@ -230,6 +235,22 @@ class VcKnnMstStats(C.Structure):
 
     def as_dict(self):
         """{n_edges, n_graph_edges, n_tree, n_clusters, total_weight, max_weight, n_rounds: int}"""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class VcKnnVoteStats(C.Structure):
+    _fields_ = [("n_voted", C.c_uint64), ("n_unlabelled", C.c_uint64), ("n_ties", C.c_uint64), ("n_entries", C.c_uint64)]
+
+    def as_dict(self):
+        """{n_voted, n_unlabelled, n_ties, n_entries: int}"""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class VcLabelPropagateStats(C.Structure):
+    _fields_ = [("n_iters", C.c_uint32), ("converged", C.c_uint32), ("n_changed_last", C.c_uint64), ("n_labelled", C.c_uint64), ("n_ties_last", C.c_uint64)]
+
+    def as_dict(self):
+        """{n_iters, converged, n_changed_last, n_labelled, n_ties_last: int}"""
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
@@ -424,6 +445,10 @@ def load_library():
         getattr(L, pre + "knn_mst_dev").argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp]
         getattr(L, pre + "mst_cut").argtypes = [vp, vp, u64, u32, vp, vp]
         getattr(L, pre + "mst_cut_dev").argtypes = [vp, vp, u64, u32, vp, vp, vp]
+        getattr(L, pre + "knn_vote").argtypes = [vp, vp, vp, u64, u32, u32, u32, vp, u32, vp, vp, vp, vp]
+        getattr(L, pre + "knn_vote_dev").argtypes = [vp, vp, vp, u64, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp]
+        getattr(L, pre + "label_propagate").argtypes = [vp, vp, vp, u64, vp, u32, u32, u32, vp, vp, vp, vp]
+        getattr(L, pre + "label_propagate_dev").argtypes = [vp, vp, vp, u64, vp, u32, u32, u32, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if getattr(L, name).restype is not C.c_char_p:
             getattr(L, name).restype = C.c_int
@@ -932,6 +957,63 @@ def _mst_cut_dev(self, fn, d_edges, n_edges, max_weight, d_labels, stream):
     count = C.c_uint64(0)
     self._check(fn(self._h, d_edges, n_edges, max_weight, d_labels, C.byref(count), stream))
     return int(count.value)
+
+
+def _knn_vote(self, fn, rows, counts, kk, labels, weight_kind, max_dist, with_votes):
+    """shared by Engine.knn_vote and ShardedEngine.knn_vote: (label uint32 [n_rows], votes [n_rows] | None, total [n_rows] | None, stats dict)"""
+    n = len(self)
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    if rows.ndim != 2:
+        raise VcError(VC_ERR_INVALID, "rows must be [n_rows, k]")
+    n_rows, k = rows.shape
+    if counts is not None:
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        if counts.shape[0] != n_rows:
+            raise VcError(VC_ERR_INVALID, "counts must have one word per row")
+    labels = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+    if labels.shape[0] != n:
+        raise VcError(VC_ERR_INVALID, "labels must have one word per resident record")
+    out = np.empty(n_rows, dtype=np.uint32)
+    votes = np.empty(n_rows, dtype=np.uint32) if with_votes else None
+    total = np.empty(n_rows, dtype=np.uint32) if with_votes else None
+    one = np.zeros(1, dtype=np.uint64)
+    st = VcKnnVoteStats()
+    self._check(fn(self._h, _p(rows if rows.size else one), _p(counts) if counts is not None and n_rows else None, n_rows, k, kk, max_dist,
+                   _p(labels if n else one), weight_kind, _p(out if n_rows else one), _p(votes) if with_votes and n_rows else None,
+                   _p(total) if with_votes and n_rows else None, C.byref(st)))
+    return out, votes, total, st.as_dict()
+
+
+def _knn_vote_dev(self, fn, d_rows, d_counts, n_rows, k, kk, d_labels, weight_kind, max_dist, d_out_label, d_out_votes, d_out_total, with_stats, stream):
+    st = VcKnnVoteStats()
+    self._check(fn(self._h, d_rows, d_counts, n_rows, k, kk, max_dist, d_labels, weight_kind, d_out_label, d_out_votes, d_out_total,
+                   C.byref(st) if with_stats else None, stream))
+    return st.as_dict() if with_stats else None
+
+
+def _label_propagate(self, fn, offsets, adj, labels, weight_kind, flags, max_iters, with_votes):
+    """shared by Engine.label_propagate and ShardedEngine.label_propagate: (labels uint32 [N], votes [N] | None, total [N] | None, stats dict)"""
+    n = len(self)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    adj = np.ascontiguousarray(adj, dtype=np.uint64).reshape(-1)
+    labels = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+    if offsets.shape[0] != n + 1 or labels.shape[0] != n:
+        raise VcError(VC_ERR_INVALID, "offsets must have N + 1 words and labels N")
+    out = np.empty(n, dtype=np.uint32)
+    votes = np.empty(n, dtype=np.uint32) if with_votes else None
+    total = np.empty(n, dtype=np.uint32) if with_votes else None
+    one = np.zeros(1, dtype=np.uint64)
+    st = VcLabelPropagateStats()
+    self._check(fn(self._h, _p(offsets), _p(adj) if len(adj) else None, len(adj), _p(labels if n else one), weight_kind, flags, max_iters,
+                   _p(out if n else one), _p(votes) if with_votes and n else None, _p(total) if with_votes and n else None, C.byref(st)))
+    return out, votes, total, st.as_dict()
+
+
+def _label_propagate_dev(self, fn, d_offsets, d_adj, n_entries, d_labels_in, weight_kind, flags, max_iters, d_labels_out, d_votes, d_total, with_stats, stream):
+    st = VcLabelPropagateStats()
+    self._check(fn(self._h, d_offsets, d_adj, n_entries, d_labels_in, weight_kind, flags, max_iters, d_labels_out, d_votes, d_total,
+                   C.byref(st) if with_stats else None, stream))
+    return st.as_dict() if with_stats else None
 
 
 def _retain(self, fn, sel, kind, with_map):
@@ -1445,6 +1527,36 @@ class Engine:
         """vc_mst_cut_dev: raw device addresses; the host waits once.  Returns n_clusters."""
         return _mst_cut_dev(self, self._L.vc_mst_cut_dev, d_edges, n_edges, max_weight, d_labels, stream)
 
+    def knn_vote(self, rows, counts, kk, labels, weight_kind=VOTE_COUNT, max_dist=0xFFFFFFFF, with_votes=True):
+        """vc_knn_vote: the k-NN classifier over any rows [n_rows, k] whose ids are resident (counts [n_rows] or None: min(k, N) entries
+        each) -- a graph of knn_graph or the rows of a search.  Row r's label is the winner among its first min(kk, count) entries
+        within max_dist under labels [N] (VOTE_NONE does not vote): the larger tally (VOTE_COUNT: 1 an entry, VOTE_CLOSENESS:
+        bits + 1 - distance), ties to the label met first.  Returns (label [n_rows], votes | None, total | None, stats dict of
+        n_voted, n_unlabelled, n_ties, n_entries)."""
+        return _knn_vote(self, self._L.vc_knn_vote, rows, counts, kk, labels, weight_kind, max_dist, with_votes)
+
+    def knn_vote_dev(self, d_rows, d_counts, n_rows, k, kk, d_labels, d_out_label, d_out_votes=None, d_out_total=None, weight_kind=VOTE_COUNT,
+                     max_dist=0xFFFFFFFF, with_stats=True, stream=None):
+        """vc_knn_vote_dev: raw device addresses; one launch and one wait.  Returns the stats dict (None without with_stats)."""
+        return _knn_vote_dev(self, self._L.vc_knn_vote_dev, d_rows, d_counts, n_rows, k, kk, d_labels, weight_kind, max_dist, d_out_label, d_out_votes,
+                             d_out_total, with_stats, stream)
+
+    def label_propagate(self, offsets, adj, labels, weight_kind=VOTE_COUNT, flags=0, max_iters=LP_MAX_ITERS, with_votes=True):
+        """vc_label_propagate: synchronous label propagation over the CSR (offsets [N + 1], adj) of knn_adjacency from labels [N]:
+        every round each record takes the winner of its segment under the previous round's labels (the larger tally, then its
+        current label, then the label met first) or keeps its label when nothing votes; LP_CLAMP_SEEDS keeps every labelled record
+        of `labels` fixed (semi-supervised), labels = id_base + arange(N) without it is community detection.  Stops after the first
+        round without a change or after max_iters <= LP_MAX_ITERS.  Returns (labels [N], votes | None, total | None of the last round,
+        stats dict of n_iters, converged, n_changed_last, n_labelled, n_ties_last)."""
+        return _label_propagate(self, self._L.vc_label_propagate, offsets, adj, labels, weight_kind, flags, max_iters, with_votes)
+
+    def label_propagate_dev(self, d_offsets, d_adj, n_entries, d_labels_in, d_labels_out, d_votes=None, d_total=None, weight_kind=VOTE_COUNT, flags=0,
+                            max_iters=LP_MAX_ITERS, with_stats=True, stream=None):
+        """vc_label_propagate_dev: raw device addresses; one wait for the plan and one small read-back per round.  Returns the
+        stats dict (None without with_stats)."""
+        return _label_propagate_dev(self, self._L.vc_label_propagate_dev, d_offsets, d_adj, n_entries, d_labels_in, weight_kind, flags, max_iters,
+                                    d_labels_out, d_votes, d_total, with_stats, stream)
+
     def timing(self):
         t = VcTiming()
         self._check(self._L.vc_get_timing(self._h, C.byref(t)))
@@ -1876,6 +1988,36 @@ class ShardedEngine:
     def mst_cut_dev(self, d_edges, n_edges, max_weight, d_labels, stream=None):
         """vc_sharded_mst_cut_dev: raw device addresses on the root device; the host waits once.  Returns n_clusters."""
         return _mst_cut_dev(self, self._L.vc_sharded_mst_cut_dev, d_edges, n_edges, max_weight, d_labels, stream)
+
+    def knn_vote(self, rows, counts, kk, labels, weight_kind=VOTE_COUNT, max_dist=0xFFFFFFFF, with_votes=True):
+        """vc_sharded_knn_vote: the k-NN classifier over any rows [n_rows, k] whose ids are resident (counts [n_rows] or None: min(k, N) entries
+        each) -- a graph of knn_graph or the rows of a search.  Row r's label is the winner among its first min(kk, count) entries
+        within max_dist under labels [N] (VOTE_NONE does not vote): the larger tally (VOTE_COUNT: 1 an entry, VOTE_CLOSENESS:
+        bits + 1 - distance), ties to the label met first.  Returns (label [n_rows], votes | None, total | None, stats dict of
+        n_voted, n_unlabelled, n_ties, n_entries)."""
+        return _knn_vote(self, self._L.vc_sharded_knn_vote, rows, counts, kk, labels, weight_kind, max_dist, with_votes)
+
+    def knn_vote_dev(self, d_rows, d_counts, n_rows, k, kk, d_labels, d_out_label, d_out_votes=None, d_out_total=None, weight_kind=VOTE_COUNT,
+                     max_dist=0xFFFFFFFF, with_stats=True, stream=None):
+        """vc_sharded_knn_vote_dev: raw device addresses on the root device; one launch and one wait.  Returns the stats dict (None without with_stats)."""
+        return _knn_vote_dev(self, self._L.vc_sharded_knn_vote_dev, d_rows, d_counts, n_rows, k, kk, d_labels, weight_kind, max_dist, d_out_label, d_out_votes,
+                             d_out_total, with_stats, stream)
+
+    def label_propagate(self, offsets, adj, labels, weight_kind=VOTE_COUNT, flags=0, max_iters=LP_MAX_ITERS, with_votes=True):
+        """vc_sharded_label_propagate: synchronous label propagation over the CSR (offsets [N + 1], adj) of knn_adjacency from labels [N]:
+        every round each record takes the winner of its segment under the previous round's labels (the larger tally, then its
+        current label, then the label met first) or keeps its label when nothing votes; LP_CLAMP_SEEDS keeps every labelled record
+        of `labels` fixed (semi-supervised), labels = id_base + arange(N) without it is community detection.  Stops after the first
+        round without a change or after max_iters <= LP_MAX_ITERS.  Returns (labels [N], votes | None, total | None of the last round,
+        stats dict of n_iters, converged, n_changed_last, n_labelled, n_ties_last)."""
+        return _label_propagate(self, self._L.vc_sharded_label_propagate, offsets, adj, labels, weight_kind, flags, max_iters, with_votes)
+
+    def label_propagate_dev(self, d_offsets, d_adj, n_entries, d_labels_in, d_labels_out, d_votes=None, d_total=None, weight_kind=VOTE_COUNT, flags=0,
+                            max_iters=LP_MAX_ITERS, with_stats=True, stream=None):
+        """vc_sharded_label_propagate_dev: raw device addresses on the root device; one wait for the plan and one small read-back per round.  Returns the
+        stats dict (None without with_stats)."""
+        return _label_propagate_dev(self, self._L.vc_sharded_label_propagate_dev, d_offsets, d_adj, n_entries, d_labels_in, weight_kind, flags, max_iters,
+                                    d_labels_out, d_votes, d_total, with_stats, stream)
 
     def search_knn(self, queries, k, mode=MODE_LINEAR, order=ORDER_ASCENDING, with_stats=False):
         q = np.ascontiguousarray(queries, dtype=np.uint8)

@@ -204,6 +204,15 @@ class Backend {
   // the components of the store under the edges of weight <= max_weight, smallest-id labels (vc_mst_cut / vc_sharded_mst_cut); any
   // edge list, sorted or not; n_clusters may be null
   virtual int mst_cut(const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels, uint64_t* n_clusters) = 0;
+  // the majority label among the first kk entries within max_dist of every row (vc_knn_vote / vc_sharded_knn_vote): rows are any rows
+  // whose ids are resident (a graph, or a search's rows: the k-NN classifier), labels [N] with VC_VOTE_NONE for "unlabelled",
+  // weight_kind VC_VOTE_COUNT / VC_VOTE_CLOSENESS; out_label [n_rows]; counts, out_votes, out_total and stats may be null
+  virtual int knn_vote(const uint64_t* rows, const uint32_t* counts, uint64_t n_rows, uint32_t k, uint32_t kk, uint32_t max_dist, const uint32_t* labels,
+                       uint32_t weight_kind, uint32_t* out_label, uint32_t* out_votes, uint32_t* out_total, vc_knn_vote_stats* stats) = 0;
+  // synchronous label propagation over the CSR of knn_adjacency (vc_label_propagate / vc_sharded_label_propagate): flags 0 or
+  // VC_LP_CLAMP_SEEDS, max_iters in 1 .. VC_LP_MAX_ITERS; labels_out [N]; votes, total [N] and stats may be null
+  virtual int label_propagate(const uint64_t* offsets, const uint64_t* adj, uint64_t n_entries, const uint32_t* labels_in, uint32_t weight_kind, uint32_t flags,
+                              uint32_t max_iters, uint32_t* labels_out, uint32_t* votes, uint32_t* total, vc_label_propagate_stats* stats) = 0;
   // records taken out of the store and its index, the survivors renumbered in order (vc_retain / vc_sharded_retain; the reference has
   // no delete: this stands for build_hash_tables.cc run again over the code file without them).  kind VC_RETAIN_MASK / VC_RETAIN_ROOTS
   virtual int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) = 0;
@@ -328,6 +337,14 @@ class Engine : public Backend {
   }
   int mst_cut(const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels, uint64_t* n_clusters) override {
     return vc_mst_cut(h_, edges, n_edges, max_weight, labels, n_clusters);
+  }
+  int knn_vote(const uint64_t* rows, const uint32_t* counts, uint64_t n_rows, uint32_t k, uint32_t kk, uint32_t max_dist, const uint32_t* labels,
+               uint32_t weight_kind, uint32_t* out_label, uint32_t* out_votes, uint32_t* out_total, vc_knn_vote_stats* stats) override {
+    return vc_knn_vote(h_, rows, counts, n_rows, k, kk, max_dist, labels, weight_kind, out_label, out_votes, out_total, stats);
+  }
+  int label_propagate(const uint64_t* offsets, const uint64_t* adj, uint64_t n_entries, const uint32_t* labels_in, uint32_t weight_kind, uint32_t flags,
+                      uint32_t max_iters, uint32_t* labels_out, uint32_t* votes, uint32_t* total, vc_label_propagate_stats* stats) override {
+    return vc_label_propagate(h_, offsets, adj, n_entries, labels_in, weight_kind, flags, max_iters, labels_out, votes, total, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_retain(h_, sel, kind, new_ids, n_kept); }
  private:
@@ -480,6 +497,14 @@ class ShardedEngine : public Backend {
   }
   int mst_cut(const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels, uint64_t* n_clusters) override {
     return vc_sharded_mst_cut(h_, edges, n_edges, max_weight, labels, n_clusters);
+  }
+  int knn_vote(const uint64_t* rows, const uint32_t* counts, uint64_t n_rows, uint32_t k, uint32_t kk, uint32_t max_dist, const uint32_t* labels,
+               uint32_t weight_kind, uint32_t* out_label, uint32_t* out_votes, uint32_t* out_total, vc_knn_vote_stats* stats) override {
+    return vc_sharded_knn_vote(h_, rows, counts, n_rows, k, kk, max_dist, labels, weight_kind, out_label, out_votes, out_total, stats);
+  }
+  int label_propagate(const uint64_t* offsets, const uint64_t* adj, uint64_t n_entries, const uint32_t* labels_in, uint32_t weight_kind, uint32_t flags,
+                      uint32_t max_iters, uint32_t* labels_out, uint32_t* votes, uint32_t* total, vc_label_propagate_stats* stats) override {
+    return vc_sharded_label_propagate(h_, offsets, adj, n_entries, labels_in, weight_kind, flags, max_iters, labels_out, votes, total, stats);
   }
   int retain(const uint32_t* sel, uint32_t kind, uint32_t* new_ids, uint64_t* n_kept) override { return vc_sharded_retain(h_, sel, kind, new_ids, n_kept); }
  private:
