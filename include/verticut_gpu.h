@@ -1362,7 +1362,8 @@ int vc_knn_adjacency(vc_engine* e, const uint64_t* rows, const uint32_t* counts,
  * and the own label.
  * WAITS: one small read-back per round, plus one at the end; vc_mst_cut*: one.  Over a sharded store every pointer of the device
  * forms lives on the ROOT device and no shard is touched; the result equals the single engine's word for word.
- * NOT OFFERED: an incremental form; the condensed tree and stability selection (host work on N - 1 edges); N kk above 2^31 - 1. */
+ * NOT OFFERED: an incremental form; the condensed tree and stability selection (host work on N - 1 edges); N kk above 2^31 - 1.
+ * (The condensed tree and its selection are a call of their own, on the device: vc_mst_condense* below takes these edges as they are.) */
 #define VC_MST_DISTANCE 0u
 #define VC_MST_REACHABILITY 1u
 typedef struct vc_mst_edge {   /* 16 bytes */
@@ -1484,6 +1485,97 @@ int vc_label_propagate_dev(vc_engine* e, const uint64_t* d_offsets, const uint64
 int vc_label_propagate(vc_engine* e, const uint64_t* offsets, const uint64_t* adj, uint64_t n_entries, const uint32_t* labels_in,
                        uint32_t weight_kind, uint32_t flags, uint32_t max_iters, uint32_t* labels_out, uint32_t* votes, uint32_t* total,
                        vc_label_propagate_stats* stats);
+
+/* ---- HDBSCAN-style clusters from a spanning forest: vc_mst_condense* ---------------------------------------------------------------------
+ * vc_mst_cut* gives the components of a forest at ONE height the caller names.  This call gives the clusters that PERSIST, each at its
+ * own density: the condensed tree of the forest, the stability of every node, the excess-of-mass (or leaf) selection and the flat
+ * labels with noise -- on the device, in integers, every output word a function of the input.
+ * INPUT.  d_edges[0 .. n_edges) are vc_mst_edge records as vc_knn_mst* writes them; only a, b and weight are read.  The list must be
+ * a FOREST over the N resident records, non-decreasing in weight, every weight <= bits.  Any such list qualifies, not only a
+ * vc_knn_mst* output, and the order of the edges WITHIN one weight influences no output word.  min_cluster_size (mcs) lies in
+ * 2 .. 2^31.  root_weight is 0, or lies in 1 .. bits + 1 and is above every edge weight: the height at which the components of the
+ * forest are deemed to merge.  method is VC_CONDENSE_EOM or VC_CONDENSE_LEAF.
+ * THE TREE, bottom-up over the distinct weights w, ascending.  The components at height h are those of the edges of weight <= h.
+ * When the edges of weight w are taken, each new component X is the union of a group of previous components (singletons included);
+ * its children of size >= mcs are BIG, the others SMALL.  A component of size >= mcs always carries exactly one live cluster.
+ *   two or more big children: their clusters END at w; a new node P FORMS at w with those clusters as its children, size |X|, and every
+ *     record of X has leave level w in P; the small children's records get own = P, leave = w.
+ *   exactly one big child: its cluster C continues as X, the same node, grown by the small children's records: own = C, leave = w.
+ *   no big child and |X| >= mcs: a new LEAF node forms at w with size |X|; all its records get own = that node, leave = w.
+ *   no big child and |X| < mcs: nothing.
+ * A cluster alive when the edges run out is a ROOT: its end is root_weight and its parent VC_CONDENSE_NONE.  A record whose
+ * component never reaches mcs has own = leave = VC_CONDENSE_NONE.  rep(C) is the smallest global id of C's component at its end.
+ * STABILITY, the integer excess of mass in the distance domain: stability(C) = end(C) size(C) - the sum of leave(p) over the records
+ * that ever joined C, which for a node formed at f is f size_at_formation + the sum of w absorbed_at_w.  A root under
+ * root_weight == 0 has stability 0 and is never selected (per forest component, "no single cluster").
+ * SELECTION.  Nodes are numbered ascending by (form, rep); the order is strict and children have smaller indices than parents.
+ * Ascending: sub(C) = the sum of best(child); keep(C) = stability(C) >= sub(C), a tie going to the parent, and false for a root under
+ * root_weight == 0; best(C) = keep ? stability : sub.  Then C is SELECTED iff keep(C) and no ancestor has keep.  Under
+ * VC_CONDENSE_LEAF, C is selected iff it has no children (the same root rule); stability, best and the keep bit are written all the same.
+ * OUTPUTS of vc_mst_condense_dev.
+ *   d_nodes has room for max(N, 1) - 1 vc_condensed_node records (there are at most 2 floor(N / mcs) - 1): the n_nodes nodes in their
+ *     order; words beyond n_nodes are untouched.  flags: VC_CONDENSE_SELECTED | VC_CONDENSE_KEEP | VC_CONDENSE_ROOT; pad is 0.
+ *   d_labels (N words): rep of the selected node that is own(p) or an ancestor of it; otherwise the record's OWN global id -- noise,
+ *     vc_dbscan_radius*'s convention, so the labels feed vc_group_summary*, vc_retain*(VC_RETAIN_ROOTS) and the distinct, filtered and
+ *     scoped searches unchanged.
+ *   d_node (N words, may be NULL): the index of that selected node, VC_CONDENSE_NONE for noise -- it tells a cluster's representative
+ *     from a noise record.
+ *   d_own, d_leave (N words each, may be NULL): own(p) as a node index and leave(p), the inputs of a GLOSH-style outlier score.
+ *   stats (HOST memory in both forms, may be NULL): n_nodes, n_leaves (nodes without children), n_roots, n_selected, n_clustered and
+ *     n_noise (they sum to N), total_stability over the selected nodes, n_levels the distinct weights.
+ * HOW.  A plan launch validates every edge and notes the first edge of every weight; the host compacts that into at most bits + 1
+ * levels.  Per level, with no wait: the level's edges are united in vc_cluster_radius*'s lock-free forest; every edge end claims its
+ * previous component once and adds its size to the new root's sums (integer atomics); every new root applies the table above and
+ * creates its node, in any order; the previous components are told; a pass over the records hands out own and leave and takes the
+ * next snapshot.  Then the nodes are sorted by (form, rep) with vc_knn_adjacency*'s radix sort, one launch folds best upwards (the
+ * last child to arrive serves the parent), one finds every node's selected ancestor, one writes the labels.
+ * SCRATCH, in the handle's grow-only buffers: 48 bytes per record, 88 per node of the N - 1 the output may hold (the sort's two buffers among them), and the sort's work words.
+ * ERRORS, checked before any work, outputs untouched: VC_ERR_INVALID for a null handle, labels or nodes, null edges with n_edges > 0,
+ * n_edges > max(N, 1) - 1, mcs outside 2 .. 2^31, root_weight > bits + 1, an unknown method.  Found ON THE DEVICE, VC_ERR_INVALID
+ * through the error word of the first wait with NO OUTPUT WORD WRITTEN: an end outside the store, a == b, a weight above bits,
+ * descending weights, root_weight != 0 and not above the last weight.  A CYCLE (the components at the end must number N - n_edges)
+ * is found at the second wait, also before any output word is written.  N == 0 gives VC_OK and zero stats; n_edges == 0 gives no
+ * nodes and identity labels.
+ * WAITS: three small read-backs -- the plan, the number of nodes (with the cycle check), the statistics.  Over a sharded store every
+ * pointer of the device forms lives on the ROOT device and no shard is touched; the result equals the single engine's word for word.
+ * NOT OFFERED: the outlier scores themselves, a cluster_selection_epsilon, max_cluster_size, soft memberships. */
+#define VC_CONDENSE_EOM 0u
+#define VC_CONDENSE_LEAF 1u
+#define VC_CONDENSE_NONE 0xFFFFFFFFu
+#define VC_CONDENSE_SELECTED 1u
+#define VC_CONDENSE_KEEP 2u
+#define VC_CONDENSE_ROOT 4u
+typedef struct vc_condensed_node {   /* 48 bytes */
+  uint32_t parent;       /* node index, VC_CONDENSE_NONE for a root */
+  uint32_t rep;          /* smallest global id of the component at the node's end */
+  uint32_t form;
+  uint32_t end;
+  uint32_t size;         /* records that ever joined */
+  uint32_t n_children;
+  uint32_t flags;
+  uint32_t pad;
+  uint64_t stability;
+  uint64_t best;
+} vc_condensed_node;
+typedef struct vc_mst_condense_stats {   /* 64 bytes */
+  uint64_t n_nodes;
+  uint64_t n_leaves;
+  uint64_t n_roots;
+  uint64_t n_selected;
+  uint64_t n_clustered;
+  uint64_t n_noise;
+  uint64_t total_stability;
+  uint32_t n_levels;
+  uint32_t pad;
+} vc_mst_condense_stats;
+int vc_mst_condense_dev(vc_engine* e, const vc_mst_edge* d_edges, uint64_t n_edges, uint32_t min_cluster_size, uint32_t root_weight,
+                        uint32_t method, vc_condensed_node* d_nodes, uint32_t* d_labels, uint32_t* d_node, uint32_t* d_own,
+                        uint32_t* d_leave, vc_mst_condense_stats* stats, void* stream);
+/* The same for host pointers: the edges are staged ON EVERY CALL; the n_nodes nodes, the labels and the three optional arrays come
+ * home; waits for them.  n_nodes is stats->n_nodes; without stats, count the nodes by pre-filling `nodes`. */
+int vc_mst_condense(vc_engine* e, const vc_mst_edge* edges, uint64_t n_edges, uint32_t min_cluster_size, uint32_t root_weight,
+                    uint32_t method, vc_condensed_node* nodes, uint32_t* labels, uint32_t* node, uint32_t* own, uint32_t* leave,
+                    vc_mst_condense_stats* stats);
 
 /* Sticky status of the asynchronous device path: *n_gave_up = calls since the previous vc_device_status() in which the
  * device-side ring-overflow recovery could not complete (its grid never met: the GPU was held by other kernels for
@@ -1824,6 +1916,14 @@ int vc_sharded_label_propagate_dev(vc_sharded* h, const uint64_t* d_offsets, con
 int vc_sharded_label_propagate(vc_sharded* h, const uint64_t* offsets, const uint64_t* adj, uint64_t n_entries, const uint32_t* labels_in,
                                uint32_t weight_kind, uint32_t flags, uint32_t max_iters, uint32_t* labels_out, uint32_t* votes, uint32_t* total,
                                vc_label_propagate_stats* stats);
+/* The condensed tree of a spanning forest and its selection: as vc_mst_condense_dev / vc_mst_condense; every pointer of the device form
+ * lives on the ROOT device, no shard is touched, and the words equal the single engine's. */
+int vc_sharded_mst_condense_dev(vc_sharded* h, const vc_mst_edge* d_edges, uint64_t n_edges, uint32_t min_cluster_size, uint32_t root_weight,
+                                uint32_t method, vc_condensed_node* d_nodes, uint32_t* d_labels, uint32_t* d_node, uint32_t* d_own,
+                                uint32_t* d_leave, vc_mst_condense_stats* stats, void* stream);
+int vc_sharded_mst_condense(vc_sharded* h, const vc_mst_edge* edges, uint64_t n_edges, uint32_t min_cluster_size, uint32_t root_weight,
+                            uint32_t method, vc_condensed_node* nodes, uint32_t* labels, uint32_t* node, uint32_t* own, uint32_t* leave,
+                            vc_mst_condense_stats* stats);
 
 /* Stream of the host-pointer calls (default VC_STREAM_OWN). */
 int vc_set_stream(vc_engine* e, void* stream);

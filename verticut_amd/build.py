@@ -8,8 +8,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libverticut_gpu.so")
-SOURCES = ["vc_scan.hip", "vc_scan_stream.hip", "vc_mih.hip", "vc_sort.hip", "vc_engine.hip", "vc_ids.hip", "vc_ids_radius.hip", "vc_walk.hip", "vc_cluster.hip", "vc_levels.hip", "vc_leaders.hip", "vc_dbscan.hip", "vc_dbscan_levels.hip", "vc_groups.hip", "vc_assign.hip", "vc_seed.hip", "vc_distinct.hip", "vc_filter.hip", "vc_scope.hip", "vc_knn_graph.hip", "vc_knn_graph_update.hip", "vc_knn_graph_retain.hip", "vc_snn.hip", "vc_knn_adjacency.hip", "vc_knn_mst.hip", "vc_vote.hip", "vc_retain.hip", "vc_sharded.hip"]
-HEADERS = ["vc_common.hpp", "vc_internal.hpp", "vc_forest.hpp", "vc_mih.hpp", "vc_retain.hpp", "vc_groups_plan.hpp", "vc_assign_plan.hpp", "vc_seed_plan.hpp", "vc_distinct_plan.hpp", "vc_filter_plan.hpp", "vc_scope_plan.hpp", "vc_knn_graph_plan.hpp", "vc_knn_graph_update_plan.hpp", "vc_knn_graph_retain_plan.hpp", "vc_snn_plan.hpp", "vc_knn_adjacency_plan.hpp", "vc_knn_mst_plan.hpp", "vc_vote_plan.hpp", "vc_sharded_radius.hpp", "vc_linear_plan.hpp", "vc_scan_stream_plan.hpp", "vc_mih_policy.hpp", os.path.join("..", "..", "include", "verticut_gpu.h")]
+SOURCES = ["vc_scan.hip", "vc_scan_stream.hip", "vc_mih.hip", "vc_sort.hip", "vc_engine.hip", "vc_ids.hip", "vc_ids_radius.hip", "vc_walk.hip", "vc_cluster.hip", "vc_levels.hip", "vc_leaders.hip", "vc_dbscan.hip", "vc_dbscan_levels.hip", "vc_groups.hip", "vc_assign.hip", "vc_seed.hip", "vc_distinct.hip", "vc_filter.hip", "vc_scope.hip", "vc_knn_graph.hip", "vc_knn_graph_update.hip", "vc_knn_graph_retain.hip", "vc_snn.hip", "vc_knn_adjacency.hip", "vc_knn_mst.hip", "vc_mst_condense.hip", "vc_vote.hip", "vc_retain.hip", "vc_sharded.hip"]
+HEADERS = ["vc_common.hpp", "vc_internal.hpp", "vc_forest.hpp", "vc_mih.hpp", "vc_retain.hpp", "vc_groups_plan.hpp", "vc_assign_plan.hpp", "vc_seed_plan.hpp", "vc_distinct_plan.hpp", "vc_filter_plan.hpp", "vc_scope_plan.hpp", "vc_knn_graph_plan.hpp", "vc_knn_graph_update_plan.hpp", "vc_knn_graph_retain_plan.hpp", "vc_snn_plan.hpp", "vc_knn_adjacency_plan.hpp", "vc_knn_mst_plan.hpp", "vc_mst_condense_plan.hpp", "vc_vote_plan.hpp", "vc_sharded_radius.hpp", "vc_linear_plan.hpp", "vc_scan_stream_plan.hpp", "vc_mih_policy.hpp", os.path.join("..", "..", "include", "verticut_gpu.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-pass-failed"]
 
 

@@ -19,6 +19,7 @@
 #include "vc_snn_plan.hpp"
 #include "vc_knn_adjacency_plan.hpp"
 #include "vc_knn_mst_plan.hpp"
+#include "vc_mst_condense_plan.hpp"
 #include "vc_vote_plan.hpp"
 #include "vc_knn_graph_update_plan.hpp"
 #include "vc_mih.hpp"
@@ -1710,6 +1711,15 @@ static int check_mst_cut_args(vc_engine* e, const vc_mst_edge* edges, uint64_t n
   if (!e || !labels || (!edges && n_edges)) return VC_ERR_INVALID;
   return VC_OK;
 }
+static int check_mst_condense_args(vc_engine* e, const vc_mst_edge* edges, uint64_t n_edges, uint32_t mcs, uint32_t root_weight, uint32_t method,
+                                   const vc_condensed_node* nodes, const uint32_t* labels) {
+  if (!e || !labels || !nodes || (!edges && n_edges)) return VC_ERR_INVALID;
+  if (!vc_cond_edges_ok(e->n, n_edges)) return fail(e, VC_ERR_INVALID, "condensed tree: a forest over N records has at most max(N, 1) - 1 edges");
+  if (!vc_cond_mcs_ok(mcs)) return fail(e, VC_ERR_INVALID, "condensed tree: min_cluster_size must be in 2..2^31");
+  if (!vc_cond_root_weight_ok(root_weight, e->bits)) return fail(e, VC_ERR_INVALID, "condensed tree: root_weight must not exceed bits + 1");
+  if (!vc_cond_method_ok(method)) return fail(e, VC_ERR_INVALID, "condensed tree: unknown method %u", method);
+  return VC_OK;
+}
 static int check_knn_vote_args(vc_engine* e, const uint64_t* rows, uint32_t k, uint32_t kk, const uint32_t* labels, uint32_t weight_kind, const uint32_t* out_label) {
   if (!e || !rows || !labels || !out_label) return VC_ERR_INVALID;
   if (!vc_vote_k_ok(k, VC_MAX_K)) return fail(e, VC_ERR_INVALID, "label vote: k must be in 1..%u", VC_MAX_K);
@@ -1969,6 +1979,28 @@ int vc_mst_cut(vc_engine* e, const vc_mst_edge* edges, uint64_t n_edges, uint32_
   if (rc) return rc;
   return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
     return vc_mst_cut_run_host(store_view(e, VC_MODE_LINEAR), edges, n_edges, max_weight, labels, n_clusters, s, err);
+  });
+}
+
+int vc_mst_condense_dev(vc_engine* e, const vc_mst_edge* d_edges, uint64_t n_edges, uint32_t min_cluster_size, uint32_t root_weight, uint32_t method,
+                        vc_condensed_node* d_nodes, uint32_t* d_labels, uint32_t* d_node, uint32_t* d_own, uint32_t* d_leave, vc_mst_condense_stats* stats,
+                        void* stream) {
+  const int rc = check_mst_condense_args(e, d_edges, n_edges, min_cluster_size, root_weight, method, d_nodes, d_labels);
+  if (rc) return rc;
+  return store_call(e, caller_stream(e, stream), [&](hipStream_t s, std::string* err) {
+    return vc_mst_condense_run(store_view(e, VC_MODE_LINEAR),
+                               VcCondenseArgs{d_edges, n_edges, min_cluster_size, root_weight, method, d_nodes, d_labels, d_node, d_own, d_leave}, stats, s, err);
+  });
+}
+
+int vc_mst_condense(vc_engine* e, const vc_mst_edge* edges, uint64_t n_edges, uint32_t min_cluster_size, uint32_t root_weight, uint32_t method,
+                    vc_condensed_node* nodes, uint32_t* labels, uint32_t* node, uint32_t* own, uint32_t* leave, vc_mst_condense_stats* stats) {
+  const int rc = check_mst_condense_args(e, edges, n_edges, min_cluster_size, root_weight, method, nodes, labels);
+  if (rc) return rc;
+  return store_call(e, e->stream, [&](hipStream_t s, std::string* err) {
+    return vc_mst_condense_run_host(store_view(e, VC_MODE_LINEAR),
+                                    VcCondenseArgs{nullptr, n_edges, min_cluster_size, root_weight, method, nullptr, nullptr, nullptr, nullptr, nullptr}, edges,
+                                    nodes, labels, node, own, leave, stats, s, err);
   });
 }
 

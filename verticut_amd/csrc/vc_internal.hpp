@@ -251,6 +251,10 @@ enum VcScratch {
   // the label vote and label propagation (vc_vote.hip): the plan's and the rounds' statistics blocks; the list, the two label buffers
   // and the bin counts; the scan's work; the long segments' table offsets; their tables; the host forms' staging (VcVoteStage, VcVoteLpStage)
   VC_VOTE_STAT, VC_VOTE_PLAN, VC_VOTE_SCAN, VC_VOTE_LONG_OFF, VC_VOTE_LONG, VC_VOTE_STAGE,
+  // the condensed tree of a spanning forest (vc_mst_condense.hip): the statistics block; the plan's first-edge table; the twelve words
+  // per record; the working nodes and the finish's words per node; the sort's two key and value buffers; its work; the host form's
+  // staging (VcCondStage)
+  VC_COND_STAT, VC_COND_PLAN, VC_COND_WORK, VC_COND_TREE, VC_COND_SORT, VC_COND_SORT_WORK, VC_COND_STAGE,
   VC_SCRATCH_BUFS
 };
 // buffer `which` of the handle's table, at least `bytes` large, on the current device; null when it cannot be had (the handle keeps the text)
@@ -814,6 +818,27 @@ int vc_mst_cut_run(const VcStoreView& v, const vc_mst_edge* d_edges, uint64_t n_
                    std::string* err);
 int vc_mst_cut_run_host(const VcStoreView& v, const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels, uint64_t* n_clusters, hipStream_t s,
                         std::string* err);
+// ---- vc_mst_condense.hip: the condensed tree of a spanning forest, its stabilities, the selection and the flat labels
+// (vc_mst_condense*, vc_sharded_mst_condense*).  One driver for both handle kinds; the plan arithmetic -- the argument checks, the level
+// table, the stability, the sizes -- is vc_mst_condense_plan.hpp.
+struct VcCondenseArgs {
+  const vc_mst_edge* d_edges;      // [n_edges]: a forest over the store, ascending in weight
+  uint64_t n_edges;                // checked by the caller: vc_cond_edges_ok
+  uint32_t min_cluster_size, root_weight, method;   // vc_cond_mcs_ok, vc_cond_root_weight_ok, vc_cond_method_ok
+  vc_condensed_node* d_nodes;      // [max(n, 1) - 1]
+  uint32_t* d_labels;              // [n]
+  uint32_t* d_node;                // [n], nullable
+  uint32_t* d_own;                 // [n], nullable
+  uint32_t* d_leave;               // [n], nullable
+};
+// the whole call on s: the plan (THE FIRST WAIT: VC_ERR_INVALID for an edge or a root weight the contract refuses), the levels without
+// a wait, the roots (the second wait: the node count; VC_ERR_INVALID for a cycle), the sort, the fold, the selection, the labels, the
+// last wait.  No output word is written before the second wait.  Only n, id_base, W and alloc of the view are used
+int vc_mst_condense_run(const VcStoreView& v, const VcCondenseArgs& a, vc_mst_condense_stats* stats, hipStream_t s, std::string* err);
+// the same for host pointers (a's pointers are ignored): the edges staged; the n_nodes nodes, the labels and the three nullable
+// arrays come home, waited for
+int vc_mst_condense_run_host(const VcStoreView& v, VcCondenseArgs a, const vc_mst_edge* edges, vc_condensed_node* nodes, uint32_t* labels, uint32_t* node, uint32_t* own,
+                             uint32_t* leave, vc_mst_condense_stats* stats, hipStream_t s, std::string* err);
 // ---- vc_vote.hip: the weighted label tally of a segment -- the k-NN classifier over any rows (vc_knn_vote*, vc_sharded_knn_vote*) and
 // synchronous label propagation over a CSR graph (vc_label_propagate*, vc_sharded_label_propagate*).  One driver per call for both
 // handle kinds; the plan arithmetic -- the argument checks, the weight, the key, the team shapes, the sizes -- is vc_vote_plan.hpp.

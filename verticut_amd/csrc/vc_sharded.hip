@@ -44,6 +44,7 @@
 #include "vc_snn_plan.hpp"
 #include "vc_knn_adjacency_plan.hpp"
 #include "vc_knn_mst_plan.hpp"
+#include "vc_mst_condense_plan.hpp"
 #include "vc_vote_plan.hpp"
 #include "vc_knn_graph_update_plan.hpp"
 #include "vc_mih.hpp"
@@ -2734,6 +2735,15 @@ static int check_sharded_knn_mst_args(vc_sharded* h, const uint64_t* rows, uint3
   if (!vc_mst_items_ok(h->n, kk)) return sfail(h, VC_ERR_INVALID, "k-NN spanning forest: N * kk must not exceed 2^31 - 1");
   return VC_OK;
 }
+static int check_sharded_mst_condense_args(vc_sharded* h, const vc_mst_edge* edges, uint64_t n_edges, uint32_t mcs, uint32_t root_weight, uint32_t method,
+                                           const vc_condensed_node* nodes, const uint32_t* labels) {
+  if (!h || !labels || !nodes || (!edges && n_edges)) return VC_ERR_INVALID;
+  if (!vc_cond_edges_ok(h->n, n_edges)) return sfail(h, VC_ERR_INVALID, "condensed tree: a forest over N records has at most max(N, 1) - 1 edges");
+  if (!vc_cond_mcs_ok(mcs)) return sfail(h, VC_ERR_INVALID, "condensed tree: min_cluster_size must be in 2..2^31");
+  if (!vc_cond_root_weight_ok(root_weight, (uint32_t)h->nbytes * 8u)) return sfail(h, VC_ERR_INVALID, "condensed tree: root_weight must not exceed bits + 1");
+  if (!vc_cond_method_ok(method)) return sfail(h, VC_ERR_INVALID, "condensed tree: unknown method %u", method);
+  return VC_OK;
+}
 static int check_sharded_knn_vote_args(vc_sharded* h, const uint64_t* rows, uint32_t k, uint32_t kk, const uint32_t* labels, uint32_t weight_kind,
                                        const uint32_t* out_label) {
   if (!h || !rows || !labels || !out_label) return VC_ERR_INVALID;
@@ -2987,6 +2997,26 @@ int vc_sharded_mst_cut(vc_sharded* h, const vc_mst_edge* edges, uint64_t n_edges
   if (!h || !labels || (!edges && n_edges)) return VC_ERR_INVALID;
   return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
     return vc_mst_cut_run_host(v, edges, n_edges, max_weight, labels, n_clusters, S, err);
+  });
+}
+
+int vc_sharded_mst_condense_dev(vc_sharded* h, const vc_mst_edge* d_edges, uint64_t n_edges, uint32_t min_cluster_size, uint32_t root_weight, uint32_t method,
+                                vc_condensed_node* d_nodes, uint32_t* d_labels, uint32_t* d_node, uint32_t* d_own, uint32_t* d_leave, vc_mst_condense_stats* stats,
+                                void* stream) {
+  const int rc = check_sharded_mst_condense_args(h, d_edges, n_edges, min_cluster_size, root_weight, method, d_nodes, d_labels);
+  if (rc) return rc;
+  return sharded_store_call(h, VC_MODE_LINEAR, sharded_caller_stream(h, stream), [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_mst_condense_run(v, VcCondenseArgs{d_edges, n_edges, min_cluster_size, root_weight, method, d_nodes, d_labels, d_node, d_own, d_leave}, stats, S, err);
+  });
+}
+
+int vc_sharded_mst_condense(vc_sharded* h, const vc_mst_edge* edges, uint64_t n_edges, uint32_t min_cluster_size, uint32_t root_weight, uint32_t method,
+                            vc_condensed_node* nodes, uint32_t* labels, uint32_t* node, uint32_t* own, uint32_t* leave, vc_mst_condense_stats* stats) {
+  const int rc = check_sharded_mst_condense_args(h, edges, n_edges, min_cluster_size, root_weight, method, nodes, labels);
+  if (rc) return rc;
+  return sharded_store_call(h, VC_MODE_LINEAR, h->root_stream, [&](const VcStoreView& v, hipStream_t S, std::string* err) {
+    return vc_mst_condense_run_host(v, VcCondenseArgs{nullptr, n_edges, min_cluster_size, root_weight, method, nullptr, nullptr, nullptr, nullptr, nullptr}, edges,
+                                    nodes, labels, node, own, leave, stats, S, err);
   });
 }
 

@@ -65,12 +65,16 @@ EXPORTS = [
     "vc_mst_cut", "vc_mst_cut_dev", "vc_sharded_mst_cut", "vc_sharded_mst_cut_dev",
     "vc_knn_vote", "vc_knn_vote_dev", "vc_sharded_knn_vote", "vc_sharded_knn_vote_dev",
     "vc_label_propagate", "vc_label_propagate_dev", "vc_sharded_label_propagate", "vc_sharded_label_propagate_dev",
+    "vc_mst_condense", "vc_mst_condense_dev", "vc_sharded_mst_condense", "vc_sharded_mst_condense_dev",
 ]
 KNN_MUTUAL, KNN_EITHER = 0, 1   # VC_KNN_*: cluster_knn joins i and j iff each lists the other / iff one lists the other
 KNN_REVERSE = 2                 # VC_KNN_REVERSE: knn_adjacency only -- segment j holds every record that lists j
 VOTE_NONE = 0xFFFFFFFF               # VC_VOTE_NONE: the label word of an unlabelled record; such an entry does not vote
 VOTE_COUNT, VOTE_CLOSENESS = 0, 1    # VC_VOTE_*: a voting entry weighs 1 / bits + 1 - its distance
 LP_CLAMP_SEEDS, LP_MAX_ITERS = 1, 64   # VC_LP_*: label_propagate keeps every labelled record of labels_in fixed; the most rounds of a call
+CONDENSE_EOM, CONDENSE_LEAF = 0, 1     # VC_CONDENSE_*: mst_condense selects by excess of mass / selects the leaves of the condensed tree
+CONDENSE_NONE = 0xFFFFFFFF             # VC_CONDENSE_NONE: no node -- a root's parent, a noise record's node, own and leave
+CONDENSE_SELECTED, CONDENSE_KEEP, CONDENSE_ROOT = 1, 2, 4   # bits of CONDENSED_NODE's flags
 MST_DISTANCE, MST_REACHABILITY = 0, 1   # VC_MST_*: knn_mst weighs an edge by its distance / by max(distance, the two core distances at min_pts)
 SNN_NONE, SNN_MAX_KK = 0xFFFFFFFF, 1024   # VC_SNN_NONE: the weight word of an entry that is not listed; VC_SNN_MAX_KK: the widest kk of cluster_snn
 FILTER_MASK, FILTER_ROOTS, FILTER_EQUAL, FILTER_NOT_EQUAL, FILTER_BITS = 0, 1, 2, 3, 4   # VC_FILTER_*: how search_knn_filtered reads `sel`
@@ -255,6 +259,17 @@ class VcLabelPropagateStats(C.Structure):
 
 
 MST_EDGE = np.dtype([("a", np.uint32), ("b", np.uint32), ("weight", np.uint32), ("dist", np.uint32)])   # vc_mst_edge, 16 bytes
+CONDENSED_NODE = np.dtype([("parent", np.uint32), ("rep", np.uint32), ("form", np.uint32), ("end", np.uint32), ("size", np.uint32), ("n_children", np.uint32),
+                           ("flags", np.uint32), ("pad", np.uint32), ("stability", np.uint64), ("best", np.uint64)])   # vc_condensed_node, 48 bytes
+
+
+class VcMstCondenseStats(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint64), ("n_leaves", C.c_uint64), ("n_roots", C.c_uint64), ("n_selected", C.c_uint64), ("n_clustered", C.c_uint64),
+                ("n_noise", C.c_uint64), ("total_stability", C.c_uint64), ("n_levels", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        """{n_nodes, n_leaves, n_roots, n_selected, n_clustered, n_noise, total_stability, n_levels: int}"""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "pad"}
 
 
 class VcTiming(C.Structure):
@@ -445,6 +460,8 @@ def load_library():
         getattr(L, pre + "knn_mst_dev").argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp]
         getattr(L, pre + "mst_cut").argtypes = [vp, vp, u64, u32, vp, vp]
         getattr(L, pre + "mst_cut_dev").argtypes = [vp, vp, u64, u32, vp, vp, vp]
+        getattr(L, pre + "mst_condense").argtypes = [vp, vp, u64, u32, u32, u32, vp, vp, vp, vp, vp, vp]
+        getattr(L, pre + "mst_condense_dev").argtypes = [vp, vp, u64, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]
         getattr(L, pre + "knn_vote").argtypes = [vp, vp, vp, u64, u32, u32, u32, vp, u32, vp, vp, vp, vp]
         getattr(L, pre + "knn_vote_dev").argtypes = [vp, vp, vp, u64, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp]
         getattr(L, pre + "label_propagate").argtypes = [vp, vp, vp, u64, vp, u32, u32, u32, vp, vp, vp, vp]
@@ -957,6 +974,30 @@ def _mst_cut_dev(self, fn, d_edges, n_edges, max_weight, d_labels, stream):
     count = C.c_uint64(0)
     self._check(fn(self._h, d_edges, n_edges, max_weight, d_labels, C.byref(count), stream))
     return int(count.value)
+
+
+def _mst_condense(self, fn, edges, min_cluster_size, root_weight, method, with_node, with_own, with_leave):
+    """shared by Engine.mst_condense and ShardedEngine.mst_condense: (nodes CONDENSED_NODE [n_nodes], labels uint32 [N], node [N] | None,
+    own [N] | None, leave [N] | None, stats dict)"""
+    n = len(self)
+    edges = np.ascontiguousarray(edges, dtype=MST_EDGE).reshape(-1)
+    nodes = np.zeros(max(n - 1, 1), dtype=CONDENSED_NODE)
+    one = np.zeros(1, dtype=np.uint32)
+    labels = np.empty(n, dtype=np.uint32)
+    node = np.empty(n, dtype=np.uint32) if with_node else None
+    own = np.empty(n, dtype=np.uint32) if with_own else None
+    leave = np.empty(n, dtype=np.uint32) if with_leave else None
+    st = VcMstCondenseStats()
+    self._check(fn(self._h, _p(edges) if len(edges) else None, len(edges), min_cluster_size, root_weight, method, _p(nodes), _p(labels if n else one),
+                   _p(node) if with_node and n else None, _p(own) if with_own and n else None, _p(leave) if with_leave and n else None, C.byref(st)))
+    return nodes[:int(st.n_nodes)].copy(), labels, node, own, leave, st.as_dict()
+
+
+def _mst_condense_dev(self, fn, d_edges, n_edges, min_cluster_size, root_weight, method, d_nodes, d_labels, d_node, d_own, d_leave, with_stats, stream):
+    st = VcMstCondenseStats()
+    self._check(fn(self._h, d_edges, n_edges, min_cluster_size, root_weight, method, d_nodes, d_labels, d_node, d_own, d_leave,
+                   C.byref(st) if with_stats else None, stream))
+    return st.as_dict() if with_stats else None
 
 
 def _knn_vote(self, fn, rows, counts, kk, labels, weight_kind, max_dist, with_votes):
@@ -1527,6 +1568,23 @@ class Engine:
         """vc_mst_cut_dev: raw device addresses; the host waits once.  Returns n_clusters."""
         return _mst_cut_dev(self, self._L.vc_mst_cut_dev, d_edges, n_edges, max_weight, d_labels, stream)
 
+    def mst_condense(self, edges, min_cluster_size, root_weight=0, method=CONDENSE_EOM, with_node=True, with_own=True, with_leave=True):
+        """vc_mst_condense: the HDBSCAN-style clusters of a spanning forest (MST_EDGE records ascending in weight, as knn_mst returns them,
+        best under MST_REACHABILITY): the condensed tree at min_cluster_size, the integer stability of every node, the excess-of-mass
+        (CONDENSE_EOM) or leaf (CONDENSE_LEAF) selection and the flat labels.  root_weight 0 never selects a whole component of the forest;
+        otherwise it is the height, above every edge, at which the components are deemed to merge.  Returns (nodes CONDENSED_NODE [n_nodes]
+        ascending in (form, rep), labels [N] -- rep of the record's selected cluster, its own id for noise --, node [N] | None -- that
+        cluster's index, CONDENSE_NONE for noise --, own [N] | None, leave [N] | None, stats dict of n_nodes, n_leaves, n_roots, n_selected,
+        n_clustered, n_noise, total_stability, n_levels)."""
+        return _mst_condense(self, self._L.vc_mst_condense, edges, min_cluster_size, root_weight, method, with_node, with_own, with_leave)
+
+    def mst_condense_dev(self, d_edges, n_edges, min_cluster_size, d_nodes, d_labels, d_node=None, d_own=None, d_leave=None, root_weight=0, method=CONDENSE_EOM,
+                         with_stats=True, stream=None):
+        """vc_mst_condense_dev: raw device addresses; d_nodes has room for max(N, 1) - 1 vc_condensed_node; the host waits three times for a
+        few words.  Returns the stats dict (n_nodes says how many nodes were written) or None."""
+        return _mst_condense_dev(self, self._L.vc_mst_condense_dev, d_edges, n_edges, min_cluster_size, root_weight, method, d_nodes, d_labels, d_node, d_own,
+                                 d_leave, with_stats, stream)
+
     def knn_vote(self, rows, counts, kk, labels, weight_kind=VOTE_COUNT, max_dist=0xFFFFFFFF, with_votes=True):
         """vc_knn_vote: the k-NN classifier over any rows [n_rows, k] whose ids are resident (counts [n_rows] or None: min(k, N) entries
         each) -- a graph of knn_graph or the rows of a search.  Row r's label is the winner among its first min(kk, count) entries
@@ -1988,6 +2046,23 @@ class ShardedEngine:
     def mst_cut_dev(self, d_edges, n_edges, max_weight, d_labels, stream=None):
         """vc_sharded_mst_cut_dev: raw device addresses on the root device; the host waits once.  Returns n_clusters."""
         return _mst_cut_dev(self, self._L.vc_sharded_mst_cut_dev, d_edges, n_edges, max_weight, d_labels, stream)
+
+    def mst_condense(self, edges, min_cluster_size, root_weight=0, method=CONDENSE_EOM, with_node=True, with_own=True, with_leave=True):
+        """vc_sharded_mst_condense: the HDBSCAN-style clusters of a spanning forest (MST_EDGE records ascending in weight, as knn_mst returns them,
+        best under MST_REACHABILITY): the condensed tree at min_cluster_size, the integer stability of every node, the excess-of-mass
+        (CONDENSE_EOM) or leaf (CONDENSE_LEAF) selection and the flat labels.  root_weight 0 never selects a whole component of the forest;
+        otherwise it is the height, above every edge, at which the components are deemed to merge.  Returns (nodes CONDENSED_NODE [n_nodes]
+        ascending in (form, rep), labels [N] -- rep of the record's selected cluster, its own id for noise --, node [N] | None -- that
+        cluster's index, CONDENSE_NONE for noise --, own [N] | None, leave [N] | None, stats dict of n_nodes, n_leaves, n_roots, n_selected,
+        n_clustered, n_noise, total_stability, n_levels)."""
+        return _mst_condense(self, self._L.vc_sharded_mst_condense, edges, min_cluster_size, root_weight, method, with_node, with_own, with_leave)
+
+    def mst_condense_dev(self, d_edges, n_edges, min_cluster_size, d_nodes, d_labels, d_node=None, d_own=None, d_leave=None, root_weight=0, method=CONDENSE_EOM,
+                         with_stats=True, stream=None):
+        """vc_sharded_mst_condense_dev: raw device addresses on the root device; d_nodes has room for max(N, 1) - 1 vc_condensed_node; the host waits three times for a
+        few words.  Returns the stats dict (n_nodes says how many nodes were written) or None."""
+        return _mst_condense_dev(self, self._L.vc_sharded_mst_condense_dev, d_edges, n_edges, min_cluster_size, root_weight, method, d_nodes, d_labels, d_node, d_own,
+                                 d_leave, with_stats, stream)
 
     def knn_vote(self, rows, counts, kk, labels, weight_kind=VOTE_COUNT, max_dist=0xFFFFFFFF, with_votes=True):
         """vc_sharded_knn_vote: the k-NN classifier over any rows [n_rows, k] whose ids are resident (counts [n_rows] or None: min(k, N) entries

@@ -204,6 +204,11 @@ class Backend {
   // the components of the store under the edges of weight <= max_weight, smallest-id labels (vc_mst_cut / vc_sharded_mst_cut); any
   // edge list, sorted or not; n_clusters may be null
   virtual int mst_cut(const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels, uint64_t* n_clusters) = 0;
+  // the HDBSCAN-style clusters of a spanning forest (vc_mst_condense / vc_sharded_mst_condense): the condensed tree at min_cluster_size, its
+  // stabilities, the VC_CONDENSE_EOM or VC_CONDENSE_LEAF selection and the flat labels (own id = noise); nodes has room for max(N, 1) - 1
+  // entries and gets stats->n_nodes of them; node, own and leave may be null
+  virtual int mst_condense(const vc_mst_edge* edges, uint64_t n_edges, uint32_t min_cluster_size, uint32_t root_weight, uint32_t method, vc_condensed_node* nodes,
+                           uint32_t* labels, uint32_t* node, uint32_t* own, uint32_t* leave, vc_mst_condense_stats* stats) = 0;
   // the majority label among the first kk entries within max_dist of every row (vc_knn_vote / vc_sharded_knn_vote): rows are any rows
   // whose ids are resident (a graph, or a search's rows: the k-NN classifier), labels [N] with VC_VOTE_NONE for "unlabelled",
   // weight_kind VC_VOTE_COUNT / VC_VOTE_CLOSENESS; out_label [n_rows]; counts, out_votes, out_total and stats may be null
@@ -337,6 +342,10 @@ class Engine : public Backend {
   }
   int mst_cut(const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels, uint64_t* n_clusters) override {
     return vc_mst_cut(h_, edges, n_edges, max_weight, labels, n_clusters);
+  }
+  int mst_condense(const vc_mst_edge* edges, uint64_t n_edges, uint32_t min_cluster_size, uint32_t root_weight, uint32_t method, vc_condensed_node* nodes,
+                   uint32_t* labels, uint32_t* node, uint32_t* own, uint32_t* leave, vc_mst_condense_stats* stats) override {
+    return vc_mst_condense(h_, edges, n_edges, min_cluster_size, root_weight, method, nodes, labels, node, own, leave, stats);
   }
   int knn_vote(const uint64_t* rows, const uint32_t* counts, uint64_t n_rows, uint32_t k, uint32_t kk, uint32_t max_dist, const uint32_t* labels,
                uint32_t weight_kind, uint32_t* out_label, uint32_t* out_votes, uint32_t* out_total, vc_knn_vote_stats* stats) override {
@@ -497,6 +506,10 @@ class ShardedEngine : public Backend {
   }
   int mst_cut(const vc_mst_edge* edges, uint64_t n_edges, uint32_t max_weight, uint32_t* labels, uint64_t* n_clusters) override {
     return vc_sharded_mst_cut(h_, edges, n_edges, max_weight, labels, n_clusters);
+  }
+  int mst_condense(const vc_mst_edge* edges, uint64_t n_edges, uint32_t min_cluster_size, uint32_t root_weight, uint32_t method, vc_condensed_node* nodes,
+                   uint32_t* labels, uint32_t* node, uint32_t* own, uint32_t* leave, vc_mst_condense_stats* stats) override {
+    return vc_sharded_mst_condense(h_, edges, n_edges, min_cluster_size, root_weight, method, nodes, labels, node, own, leave, stats);
   }
   int knn_vote(const uint64_t* rows, const uint32_t* counts, uint64_t n_rows, uint32_t k, uint32_t kk, uint32_t max_dist, const uint32_t* labels,
                uint32_t weight_kind, uint32_t* out_label, uint32_t* out_votes, uint32_t* out_total, vc_knn_vote_stats* stats) override {
